@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- ORB extract + stereo match throughput on KITTI geometry (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--pairs P]
+    python bench.py --gpus N --steps K --warmup W [--pairs P] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps once (no events inside them), writes the last step's outputs to DIR if
+--dump-outputs is given (dump_outputs) and prints the line: metric, value (pairs/s), unit, ms_per_step, dtype, ... .  --full adds
+everything else described below -- the timed region repeated (--repeat, --min-region-ms), the roofline with its per-stage table,
+the pipelined / one-chain / strong-scaling passes, small batch, natural image, secondary configs, host-fed rate, the CPU baseline
+and the post-run oracle spot check.
 
 One process per GPU.  The driver launches N>1 through torch.distributed.run; started WITHOUT a launcher (`python bench.py --gpus N`, no
 RANK / WORLD_SIZE in the environment) this process spawns the N ranks itself before anything touches the GPU and relays rank 0's line
@@ -19,7 +25,7 @@ that one step's latency-bound stages (pyramid chain, quadtree, median) hide unde
 That regime is timed right after the headline region with the same protocol and reported as config.pipelined (--pipelined C,
 default 3; kernels of different chains share the chip there, so their individual durations stretch while throughput rises),
 and for BASELINE config 4's 8 pairs per GPU as config.small_batch.  The timed region is repeated --repeat times (same --steps
-each); `value` is the median, config.repeat holds min / max.
+each; --full: 5 by default, else once); `value` is the median, config.repeat holds min / max.
 
 Two sharding modes (BASELINE.json config 4 = "64 frame pairs in flight, sharded across 8x"):
   --mode weak   (default, the headline `value`): P pairs per step PER GPU, "scaling": "weak";
@@ -606,6 +612,38 @@ def strong_pass(args, D, torch, make_ctx, d_images, share, P_total, world, cdev)
     return out
 
 
+DUMP_BUDGET = 64 << 20  # --dump-outputs: bytes of .npy data at most
+WARM_S = 0.25  # without --full: warm-up steps go on until the chip has been busy this long (at least --warmup steps)
+
+
+def dump_outputs(ctx, n_pairs, out_dir, budget=DUMP_BUDGET):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step, as float32 .npy files, so that two builds
+    can be compared output for output.  Per stereo pair: the left and the right keypoints (cv::KeyPoint fields x, y, size, angle,
+    response, octave, class_id), their descriptors (32 bytes, one column each) and uRight / depth of the left keypoints; the images
+    of the dumped pairs are concatenated in pair order and counts_left / counts_right say how many keypoints each one holds.  All
+    pairs while the worst case (every image at keypoint capacity) fits in `budget` bytes, else a fixed seeded sample of pairs;
+    pairs.npy lists the pairs dumped.  Written by rank 0 from its own batch."""
+    per_pair = ctx.capacity * (2 * (7 + 32) * 4 + 2 * 4) + 3 * 4
+    k = max(1, min(n_pairs, budget // per_pair))
+    pairs = np.arange(n_pairs) if k == n_pairs else np.sort(np.random.default_rng(0).choice(n_pairs, k, replace=False))
+    cols = ("x", "y", "size", "angle", "response", "octave", "class_id")
+    got = {"left": [], "right": []}
+    for i in pairs:
+        got["left"].append(ctx.fetch_image(2 * int(i), stereo=True))
+        got["right"].append(ctx.fetch_image(2 * int(i) + 1))
+    arrays = {"pairs": pairs.astype(np.float32)}
+    for side, imgs in got.items():
+        kps = np.concatenate([g["kps"] for g in imgs])
+        arrays["counts_" + side] = np.array([len(g["kps"]) for g in imgs], np.float32)
+        arrays["keypoints_" + side] = np.stack([kps[c].astype(np.float32) for c in cols], 1)
+        arrays["descriptors_" + side] = np.concatenate([g["desc"] for g in imgs]).astype(np.float32)
+    arrays["u_right"] = np.concatenate([g["u_right"] for g in got["left"]]).astype(np.float32)
+    arrays["depth"] = np.concatenate([g["depth"] for g in got["left"]]).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(n: int) -> int:
     """`python bench.py --gpus N` with N > 1 and no launcher environment (the way the driver starts the N = 1 run): this process starts
     the N ranks itself -- one child per GPU with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, exactly what torch.distributed.run
@@ -755,25 +793,35 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--pairs", type=int, default=64, help="stereo pairs per step per GPU (in flight in HBM; BASELINE.json config 4 batches 64 pairs)")
     ap.add_argument("--chains", type=int, default=0, help="0 = 1 in --mode weak, --strong-chains in --mode strong; step chains in flight per GPU in the HEADLINE region: step k runs on context k %% chains and its stream (1 = one chain at a time)")
-    ap.add_argument("--pipelined", type=int, default=3, help="after the headline region, time the same steps with this many chains in flight -> config.pipelined (0 / 1 = skip)")
-    ap.add_argument("--repeat", type=int, default=5, help="the timed region (--steps steps) is repeated this often; value = median, config.repeat = min / max")
-    ap.add_argument("--min-region-ms", type=float, default=100.0, help="keep repeating the timed region until the regions add up to this much timed GPU work (at most 64 regions)")
-    ap.add_argument("--strong-chains", type=int, default=4, help="step chains in flight in the strong-scaling regime (8 pairs per GPU per step at N = 8 are launch-latency-bound with one): --mode strong runs its headline with this many, the strong pass beside a weak run reports 1 and this many")
+    ap.add_argument("--full", action="store_true", help="besides the headline, everything else the benchmark measures and checks: the repeated timed region, "
+                    "the roofline and per-stage table, the pipelined / one-chain / strong-scaling passes, small batch, natural image, secondary configs, "
+                    "host-fed rate, CPU baseline and the oracle spot check.  Without it a run sets up, warms up, times exactly --steps steps once and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; dump_outputs)")
+    ap.add_argument("--pipelined", type=int, default=3, help="--full: after the headline region, time the same steps with this many chains in flight -> config.pipelined (0 / 1 = skip)")
+    ap.add_argument("--repeat", type=int, default=None, help="the timed region (--steps steps) is repeated this often; value = median, config.repeat = min / max (default 5 with --full, else 1)")
+    ap.add_argument("--min-region-ms", type=float, default=None, help="keep repeating the timed region until the regions add up to this much timed GPU work (at most 64 regions; default 100 with --full, else 0)")
+    ap.add_argument("--strong-chains", type=int, default=4, help="step chains in flight in the strong-scaling regime (the strong pass beside a weak run: --full) (8 pairs per GPU per step at N = 8 are launch-latency-bound with one): --mode strong runs its headline with this many, the strong pass beside a weak run reports 1 and this many")
     ap.add_argument("--streams", type=int, default=1, help="stream groups the batch is cut into inside the library (1 keeps per-kernel times clean)")
-    ap.add_argument("--cpu-pairs", type=int, default=300, help="pairs in the CPU baseline sample (0 = skip)")
+    ap.add_argument("--cpu-pairs", type=int, default=300, help="--full: pairs in the CPU baseline sample (0 = skip)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals)")
-    ap.add_argument("--no-check", action="store_true", help="skip the post-run oracle spot check")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the post-run oracle spot check")
     ap.add_argument("--mode", default="weak", choices=["weak", "strong"], help="weak: --pairs per GPU; strong: --pairs in total, sharded by dist.shard_pairs")
     ap.add_argument("--distinct", type=int, default=16, help="distinct synthetic pairs the batch cycles through")
-    ap.add_argument("--host-fed", type=int, default=1, help="1: after the timed region also measure the PCIe-inclusive rate (N = 1 only; never `value`)")
+    ap.add_argument("--host-fed", type=int, default=1, help="--full, 1: after the timed region also measure the PCIe-inclusive rate (N = 1 only; never `value`)")
     ap.add_argument("--rehearse-rccl", action="store_true", help="N = 1: run over a ONE-RANK process group of --backend, so a one-GPU box exercises the very RCCL calls of the multi-GPU path (parameter / vocabulary broadcast, barrier, MAX all-reduce)")
-    ap.add_argument("--natural", type=int, default=1, help="1: N = 1 only, also time the step on a photograph at the benchmark geometry -> config.natural_image")
-    ap.add_argument("--small-batch", type=int, default=8, help="N = 1 only: also time steps of this many pairs (BASELINE config 4's 8 pairs per GPU) with 4 chains in flight -> config.small_batch; 0 = skip")
-    ap.add_argument("--secondary", type=int, default=1, help="1: N = 1 only, also time BASELINE configs 1, 3, 5 and the one-Frame-per-call pattern through the host entry points -> config.secondary, config.single_frame")
+    ap.add_argument("--natural", type=int, default=1, help="--full, 1: N = 1 only, also time the step on a photograph at the benchmark geometry -> config.natural_image")
+    ap.add_argument("--small-batch", type=int, default=8, help="--full, N = 1 only: also time steps of this many pairs (BASELINE config 4's 8 pairs per GPU) with 4 chains in flight -> config.small_batch; 0 = skip")
+    ap.add_argument("--secondary", type=int, default=1, help="--full, 1: N = 1 only, also time BASELINE configs 1, 3, 5 and the one-Frame-per-call pattern through the host entry points -> config.secondary, config.single_frame")
     ap.add_argument("--launcher-selftest", action="store_true", help="CPU-only check of the N > 1 plumbing (self-launch, rendezvous, the one-time broadcasts, rank count, exit codes); prints the line's distributed fields and runs NO compute")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench: --steps must be >= 1")
+    if args.repeat is None:
+        args.repeat = 5 if args.full else 1
+    if args.min_region_ms is None:
+        args.min_region_ms = 100.0 if args.full else 0.0
 
     # --gpus N > 1 without a launcher's environment: this process becomes the launcher.  It never touches the GPU.
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -848,7 +896,7 @@ def main():
     if args.chains <= 0:
         args.chains = 1 if args.mode == "weak" else args.strong_chains
     C = max(1, min(args.chains, 8))
-    CP = max(C, min(args.pipelined, 8)) if args.pipelined > 1 else C  # contexts needed in all
+    CP = max(C, min(args.pipelined, 8)) if args.full and args.pipelined > 1 else C  # contexts needed in all
     G = max(1, min(args.streams, P, 8))
 
     def make_ctx(pairs=P):
@@ -902,72 +950,83 @@ def main():
         barrier()
         return D.max_over_ranks(time.perf_counter() - t0, cdev)
 
-    for _ in range(max(args.warmup, CP)):  # every chain's context runs at least once before the clock starts
+    n_warm = max(args.warmup, CP)
+    for _ in range(n_warm):  # every chain's context runs at least once before the clock starts
         step(CP)
     barrier()
-    # Timed region: HIP events only around the dominant kernel (cell-wise FAST, stage 3) on the stream of its chain -- an event
-    # at every stage boundary costs ~6 us of idle GPU each, i.e. ~6 % of a step.  The full per-stage table comes from a separate,
-    # untimed single-chain pass after the timed region.
+    if not args.full:  # one timed region only: it starts on a chip that has been busy for a while (--full's first region of 5 does not)
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < WARM_S:  # ranks may run different counts: local synchronise, one barrier after
+            for _ in range(16):
+                step(CP)
+            torch.cuda.synchronize()
+            n_warm += 16
+        barrier()
+    # Timed region (--full): HIP events only around the dominant kernel (cell-wise FAST, stage 3) on the stream of its chain -- an
+    # event at every stage boundary costs ~6 us of idle GPU each, i.e. ~6 % of a step.  The full per-stage table comes from a
+    # separate, untimed single-chain pass after the timed region.  Without --full the timed region records no events.
     DOM = "fast"
     EVERY = 10  # events on every 10th step of a chain (two recorded steps per 20-step repeat): the two events of a step cost ~2 % of it
-    for c in ctxs[:C]:
-        c.set_profiling(2 + api.STAGE_NAMES.index(DOM))
-        c.set_profiling_interval(EVERY)
+    if args.full:
+        for c in ctxs[:C]:
+            c.set_profiling(2 + api.STAGE_NAMES.index(DOM))
+            c.set_profiling_interval(EVERY)
     R = max(1, args.repeat)
     dts, dom_ms_sum, dom_calls = [], 0.0, 0
     # the region of EXACTLY --steps steps (barrier + synchronize on both sides) is repeated at least --repeat times and until the
-    # regions add up to --min-region-ms of timed GPU work (20 steps are ~13 ms: too short for a stable median on a fresh box);
-    # value = the median region, config.repeat = n / min / max
+    # regions add up to --min-region-ms of timed GPU work (--full: 5 times and 100 ms, as 20 steps are ~13 ms: too short for a
+    # stable median on a fresh box; otherwise once); value = the median region, config.repeat = n / min / max
     while len(dts) < R or (sum(dts) * 1e3 < args.min_region_ms and len(dts) < 64):
         dts.append(timed(args.steps))
-        for c in ctxs[:C]:
-            ms, calls = c.stage_times(reset=True)
-            dom_ms_sum += ms[DOM]; dom_calls += calls
+        if args.full:
+            for c in ctxs[:C]:
+                ms, calls = c.stage_times(reset=True)
+                dom_ms_sum += ms[DOM]; dom_calls += calls
     R = len(dts)
     dt = sorted(dts)[len(dts) // 2]
-    # the dominant kernel alone on the chip (one chain at a time): what the co-scheduled figure of the timed region stretches
-    for c in ctxs:
-        c.set_profiling_interval(1)
-    dom_alone = None
-    if C > 1:
+    if args.dump_outputs and rank == 0:  # the last timed step ran on context (steps - 1) % C
+        dump_outputs(ctxs[(args.steps - 1) % C], P, args.dump_outputs)
+    dom_alone = single = piped = strong = None
+    if args.full:
+        # the dominant kernel alone on the chip (one chain at a time): what the co-scheduled figure of the timed region stretches
+        for c in ctxs:
+            c.set_profiling_interval(1)
+        if C > 1:
+            k_step[0] = 0
+            for _ in range(min(args.steps, 10)):
+                step(1)
+            barrier()
+            ms, calls = ctx.stage_times(reset=True)
+            dom_alone = ms[DOM] / max(calls, 1) / G
+        for c in ctxs:
+            c.set_profiling(0)
+        if C > 1:  # one chain at a time beside it, no events
+            single = sorted(timed(args.steps, 1) for _ in range(3))[1]
+        if CP > C:  # the deployment regime: CP step chains in flight, same steps, same barrier protocol, no events
+            for _ in range(CP):
+                step(CP)
+            piped = sorted(timed(args.steps, CP) for _ in range(R))
+        ctx.set_profiling(1)
         k_step[0] = 0
         for _ in range(min(args.steps, 10)):
             step(1)
         barrier()
-        ms, calls = ctx.stage_times(reset=True)
-        dom_alone = ms[DOM] / max(calls, 1) / G
-    for c in ctxs:
-        c.set_profiling(0)
-    single = None
-    if C > 1:  # one chain at a time beside it, no events
-        single = sorted(timed(args.steps, 1) for _ in range(3))[1]
-    piped = None
-    if CP > C:  # the deployment regime: CP step chains in flight, same steps, same barrier protocol, no events
-        for _ in range(CP):
-            step(CP)
-        piped = sorted(timed(args.steps, CP) for _ in range(R))
-    ctx.set_profiling(1)
-    k_step[0] = 0
-    for _ in range(min(args.steps, 10)):
-        step(1)
-    barrier()
-    stage_ms, calls = ctx.stage_times(reset=True)
-    for c in ctxs:
-        c.set_profiling(0)
+        stage_ms, calls = ctx.stage_times(reset=True)
+        for c in ctxs:
+            c.set_profiling(0)
 
-    # strong-scaling pass beside a weak run on several GPUs: P_total pairs in total, this rank's share per step -- with ONE step
-    # chain and with --strong-chains chains in flight (contexts sized for the share, step k on context k % chains: the product mode
-    # of config.small_batch; 8 pairs per GPU per step are launch-latency-bound with one chain, which says nothing about xGMI)
-    strong = None
-    if args.mode == "weak" and world > 1 and len(mine) >= 1:
-        strong = strong_pass(args, D, torch, make_ctx, d_images, len(mine), P_total, world, cdev)
-    k_step[0] = 0
-    step(1)  # leave the full batch's results in context 0 for the checks below
-    barrier()
+        # strong-scaling pass beside a weak run on several GPUs: P_total pairs in total, this rank's share per step -- with ONE step
+        # chain and with --strong-chains chains in flight (contexts sized for the share, step k on context k % chains: the product mode
+        # of config.small_batch; 8 pairs per GPU per step are launch-latency-bound with one chain, which says nothing about xGMI)
+        if args.mode == "weak" and world > 1 and len(mine) >= 1:
+            strong = strong_pass(args, D, torch, make_ctx, d_images, len(mine), P_total, world, cdev)
+        k_step[0] = 0
+        step(1)  # leave the full batch's results in context 0 for the checks below
+        barrier()
 
     counts = ctx.fetch_counts(2 * P)
     n_cand = 0
-    if rank == 0:
+    if rank == 0 and args.full:
         n_cand = sum(len(ctx.fetch_candidates(0, l)[0]) for l in range(nl))
         if not args.no_check:  # the timed path must be the correct path: spot-check pair 0 of EVERY chain's context against the oracle
             from oracle import oracle as O
@@ -984,53 +1043,55 @@ def main():
     if rank == 0:
         pairs_per_step = P * world if args.mode == "weak" else P_total
         value = pairs_per_step * args.steps / dt
-        alg = stage_alg_bytes_per_pair(n_cand)
-        # stage time per step, summed over the G stream groups (they overlap in wall time)
-        per_launch_ms = {k: v / max(calls, 1) for k, v in stage_ms.items()}
-        dom = DOM
-        if max(per_launch_ms, key=per_launch_ms.get) != DOM:
-            print("bench: note: stage %s is now longer than %s" % (max(per_launch_ms, key=per_launch_ms.get), DOM), file=sys.stderr)
-        launches = G  # per step a stage is G launches (one per stream group)
-        dom_ms = dom_ms_sum / max(dom_calls, 1) / launches  # from the events of the timed region, on the launching stream
-        # FAST's launch also carries the blur of the levels the pyramid launches leave unblurred: level NLEVELS - 1 for batches of
-        # 64 images and more per launch (smaller batches carry more levels: not counted, i.e. understated); its algorithmic bytes
-        # (one read, one write of the level, SURVEY's blur row) belong to the launch that does the work
-        riding = list(range(ctx.blur_ride_from(2 * P // launches), NLEVELS)) if dom == "fast" else []  # orbfe_blur_ride_from: the plan the library actually runs
-        dom_alg = alg[dom] + sum(2 * 2 * LEVEL_PX[l] for l in riding)
-        achieved = dom_alg * P / launches / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
         metric = "frames/sec ORB extract+match, KITTI 1241x376 stereo, 2000 feats"
         try:
             metric = json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
         except Exception:
             pass
         step_ms = dt / args.steps * 1e3
-        roof = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic_bytes(dom, P, launches),
-                "launch_ms": dom_ms, "alg_bytes_per_launch": dom_alg * P / launches, "blur_levels_riding_in_launch": riding,
-                "events_every_nth_step": EVERY,
-                "valu_issue": valu_issue(P, launches, dom_ms, step_ms),
-                "whole_pipeline": {"alg_bytes_per_pair": B_PAIR, "achieved": B_PAIR * value / world / 1e9,
-                                   "frac": B_PAIR * value / world / 1e9 / HBM_PEAK_GBS},
-                "stage_ms_per_step_summed_over_groups": per_launch_ms,
-                "stage_ms_note": "per-stage table from a separate untimed single-chain pass with events at every stage boundary; launch_ms from the timed region; 'ingest' holds no launch (level 0 is the caller's image, read in place: what is left is the gap between two events); 'pyramid' = the resize launches alone for batches of 64 images and more (round 5: the blur of every level rides in FAST's launch, blur_levels_riding_in_launch; smaller batches blur beside the resize launches), 'blur' holds no launch; roofline.alg_bytes_per_launch = FAST's bytes + the riding levels' blur; ORBFE_NO_FUSE=1 separates them all"}
-        roof["build_id"] = lib_build_id()
-        roof["traffic_source"] = ("replayed from profiles/%s_traffic.json (rocprofv3 --pmc passes of this build: build ids match)" % PROFILE_ROUND) if roof["traffic"] else None
-        if roof["traffic"]:
-            roof["traffic_ratio"] = roof["traffic"] / roof["alg_bytes_per_launch"]  # counter bytes / algorithmic bytes of the dominant kernel
-        wt, wsrc = whole_step_traffic_per_pair()
-        if wt:
-            roof["whole_pipeline"].update({"traffic_bytes_per_pair": wt, "traffic_ratio": wt / B_PAIR, "traffic_source": "profiles/" + wsrc})
-        if _STALE:  # counter files of this round that were taken on another build: not replayed (their fields are null / absent)
-            roof["stale_profile"] = True
-            roof["stale_profiles"] = sorted(_STALE)
-        if dom_alone is not None:
-            roof["launch_ms_one_chain"] = dom_alone
-            roof["frac_one_chain"] = alg[dom] * P / launches / (dom_alone * 1e-3) / 1e9 / HBM_PEAK_GBS
-            roof["launch_ms_note"] = ("launch_ms: the kernel co-scheduled with the other %d chains' kernels (timed region); launch_ms_one_chain: the same "
-                                      "launch with one chain at a time" % (C - 1))
+        roof = None
+        if args.full:
+            alg = stage_alg_bytes_per_pair(n_cand)
+            # stage time per step, summed over the G stream groups (they overlap in wall time)
+            per_launch_ms = {k: v / max(calls, 1) for k, v in stage_ms.items()}
+            dom = DOM
+            if max(per_launch_ms, key=per_launch_ms.get) != DOM:
+                print("bench: note: stage %s is now longer than %s" % (max(per_launch_ms, key=per_launch_ms.get), DOM), file=sys.stderr)
+            launches = G  # per step a stage is G launches (one per stream group)
+            dom_ms = dom_ms_sum / max(dom_calls, 1) / launches  # from the events of the timed region, on the launching stream
+            # FAST's launch also carries the blur of the levels the pyramid launches leave unblurred: level NLEVELS - 1 for batches of
+            # 64 images and more per launch (smaller batches carry more levels: not counted, i.e. understated); its algorithmic bytes
+            # (one read, one write of the level, SURVEY's blur row) belong to the launch that does the work
+            riding = list(range(ctx.blur_ride_from(2 * P // launches), NLEVELS)) if dom == "fast" else []  # orbfe_blur_ride_from: the plan the library actually runs
+            dom_alg = alg[dom] + sum(2 * 2 * LEVEL_PX[l] for l in riding)
+            achieved = dom_alg * P / launches / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+            roof = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic_bytes(dom, P, launches),
+                    "launch_ms": dom_ms, "alg_bytes_per_launch": dom_alg * P / launches, "blur_levels_riding_in_launch": riding,
+                    "events_every_nth_step": EVERY,
+                    "valu_issue": valu_issue(P, launches, dom_ms, step_ms),
+                    "whole_pipeline": {"alg_bytes_per_pair": B_PAIR, "achieved": B_PAIR * value / world / 1e9,
+                                       "frac": B_PAIR * value / world / 1e9 / HBM_PEAK_GBS},
+                    "stage_ms_per_step_summed_over_groups": per_launch_ms,
+                    "stage_ms_note": "per-stage table from a separate untimed single-chain pass with events at every stage boundary; launch_ms from the timed region; 'ingest' holds no launch (level 0 is the caller's image, read in place: what is left is the gap between two events); 'pyramid' = the resize launches alone for batches of 64 images and more (round 5: the blur of every level rides in FAST's launch, blur_levels_riding_in_launch; smaller batches blur beside the resize launches), 'blur' holds no launch; roofline.alg_bytes_per_launch = FAST's bytes + the riding levels' blur; ORBFE_NO_FUSE=1 separates them all"}
+            roof["build_id"] = lib_build_id()
+            roof["traffic_source"] = ("replayed from profiles/%s_traffic.json (rocprofv3 --pmc passes of this build: build ids match)" % PROFILE_ROUND) if roof["traffic"] else None
+            if roof["traffic"]:
+                roof["traffic_ratio"] = roof["traffic"] / roof["alg_bytes_per_launch"]  # counter bytes / algorithmic bytes of the dominant kernel
+            wt, wsrc = whole_step_traffic_per_pair()
+            if wt:
+                roof["whole_pipeline"].update({"traffic_bytes_per_pair": wt, "traffic_ratio": wt / B_PAIR, "traffic_source": "profiles/" + wsrc})
+            if _STALE:  # counter files of this round that were taken on another build: not replayed (their fields are null / absent)
+                roof["stale_profile"] = True
+                roof["stale_profiles"] = sorted(_STALE)
+            if dom_alone is not None:
+                roof["launch_ms_one_chain"] = dom_alone
+                roof["frac_one_chain"] = alg[dom] * P / launches / (dom_alone * 1e-3) / 1e9 / HBM_PEAK_GBS
+                roof["launch_ms_note"] = ("launch_ms: the kernel co-scheduled with the other %d chains' kernels (timed region); launch_ms_one_chain: the same "
+                                          "launch with one chain at a time" % (C - 1))
         out = {
             "metric": metric, "value": value, "unit": "frames/s (1 frame = 1 stereo pair)",
-            "n_gpus": ranks_joined, "steps": args.steps, "warmup": max(args.warmup, CP),
+            "n_gpus": ranks_joined, "steps": args.steps, "warmup": n_warm,
             "ms_per_step": step_ms, "higher_is_better": True, "scaling": args.mode,
             "vs_baseline": None, "dtype": "u8", "data": "synthetic",
             "config": {"workload": "Stereo-KITTI00-02 1241x376, 2000 features, 8 levels: extract L+R + ComputeStereoMatches"
@@ -1040,8 +1101,9 @@ def main():
                        "quadtree_kernel": ctx.quadtree_kernel(), "parallelism": "frame-pair sharding, no data-path collective",
                        "repeat": {"n": R, "min": pairs_per_step * args.steps / max(dts), "max": pairs_per_step * args.steps / min(dts), "value_is": "median"},
                        "keypoints_left_right_pair0": [int(counts[0]), int(counts[1])]},
-            "roofline": roof,
         }
+        if roof is not None:
+            out["roofline"] = roof
         if piped is not None:
             pv = pairs_per_step * args.steps / piped[len(piped) // 2]
             out["config"]["pipelined"] = {"chains_in_flight": CP, "value": pv, "ms_per_step": piped[len(piped) // 2] / args.steps * 1e3,
@@ -1065,19 +1127,19 @@ def main():
     for c in ctxs[1:]:
         c.close()
     if rank == 0:
-        if world == 1 and args.small_batch > 0 and args.mode == "weak":
+        if args.full and world == 1 and args.small_batch > 0 and args.mode == "weak":
             out["config"]["small_batch"] = small_batch(api, torch, d_images, min(args.small_batch, P), make_ctx)
-        if world == 1 and args.natural and args.mode == "weak":
+        if args.full and world == 1 and args.natural and args.mode == "weak":
             out["config"]["natural_image"] = natural_scene(api, torch, dev, P, make_ctx)
-        if world == 1 and args.secondary and args.mode == "weak":
+        if args.full and world == 1 and args.secondary and args.mode == "weak":
             try:
                 out["config"]["secondary"] = secondary_configs(api, torch, dev)
                 out["config"]["single_frame"] = single_frame(api, torch, dev)
             except Exception as e:  # an extra must not cost the headline its line
                 out["config"]["secondary"] = {"error": repr(e)}
-        if world == 1 and args.host_fed:
+        if args.full and world == 1 and args.host_fed:
             out["config"]["host_fed"] = host_fed(api, torch, dev, host, P, make_ctx)
-        if world == 1 and args.cpu_pairs > 0:
+        if args.full and world == 1 and args.cpu_pairs > 0:
             out["cpu_baseline"] = cpu_baseline(args.cpu_pairs)
         else:
             out["cpu_baseline"] = None

@@ -10,7 +10,7 @@ out=gpurun_out/final; mkdir -p $out
 # bench.py replays roofline.traffic / valu_issue only from files whose id equals the id of the library it has just run
 bid=$(python3 -c "import ctypes; l = ctypes.CDLL('orbslam2_amd/liborbfe.so'); l.orbfe_build_id.restype = ctypes.c_char_p; print(l.orbfe_build_id().decode())") || exit 1
 echo "build_id: $bid" > $out/build_id.txt
-python3 bench.py > $out/bench.json 2> $out/bench.err || exit 1
+python3 bench.py --full > $out/bench.json 2> $out/bench.err || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --cpu-pairs 0 --pipelined 0 --small-batch 0 --natural 0 --host-fed 0 --secondary 0 --no-check  > $out/bench_under_rocprof.json 2>/dev/null || exit 1
 cp $out/stats/*/*kernel_stats.csv $out/kernel_stats.csv
 for c in FETCH_SIZE WRITE_SIZE; do

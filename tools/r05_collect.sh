@@ -32,10 +32,10 @@ cp $out/stats/*/*kernel_stats.csv $out/kernel_stats.csv; rm -rf $out/stats
 bash tools/step_trace.sh r05 > $out/step_trace.txt 2>/dev/null
 bash tools/pmc_mem.sh $out/pmc_mem > /dev/null 2>&1; for f in $out/pmc_mem/TA_TA_BUSY_sum.txt $out/pmc_mem/TCP_PENDING_STALL_CYCLES_sum.txt; do [ -f $f ] && sed -i "1i # build_id: $bid" $f; done
 echo "traces done"
-python3 bench.py > $out/bench.json 2> $out/bench.err || { echo "bench failed"; tail -5 $out/bench.err; exit 1; }
+python3 bench.py --full > $out/bench.json 2> $out/bench.err || { echo "bench failed"; tail -5 $out/bench.err; exit 1; }
 timeout -k 10 300 python3 tools/pcie_rate2.py > $out/pcie.json 2>/dev/null
-ORBFE_BENCH_ONE_GPU=1 timeout -k 10 300 python3 bench.py --gpus 2 --backend gloo --cpu-pairs 0 --host-fed 0 --natural 0 --small-batch 0 --secondary 0 --pipelined 0 > $out/bench_2rank_gloo_one_gpu.json 2> $out/bench_2rank.err; echo "2-rank self-launch rc=$?"
-ORBFE_BENCH_ONE_GPU=1 timeout -k 10 300 python3 bench.py --gpus 4 --backend gloo --cpu-pairs 0 --host-fed 0 --natural 0 --small-batch 0 --secondary 0 --pipelined 0 > $out/bench_4rank_gloo_one_gpu.json 2> $out/bench_4rank.err; echo "4-rank self-launch rc=$?"
+ORBFE_BENCH_ONE_GPU=1 timeout -k 10 300 python3 bench.py --full --gpus 2 --backend gloo --cpu-pairs 0 --host-fed 0 --natural 0 --small-batch 0 --secondary 0 --pipelined 0 > $out/bench_2rank_gloo_one_gpu.json 2> $out/bench_2rank.err; echo "2-rank self-launch rc=$?"
+ORBFE_BENCH_ONE_GPU=1 timeout -k 10 300 python3 bench.py --full --gpus 4 --backend gloo --cpu-pairs 0 --host-fed 0 --natural 0 --small-batch 0 --secondary 0 --pipelined 0 > $out/bench_4rank_gloo_one_gpu.json 2> $out/bench_4rank.err; echo "4-rank self-launch rc=$?"
 python3 - <<'PY'
 import json
 d = json.load(open("gpurun_out/final/bench.json"))
