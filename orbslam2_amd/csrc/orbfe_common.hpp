@@ -8,8 +8,6 @@
 #include <cstdlib>
 
 typedef short pk16 __attribute__((ext_vector_type(2))); // two int16 lanes in one VGPR (v_pk_* ops)
-#define PYR_MX 4 // reflect-101 margin of every pyramid level: pixels left of column 0 ...
-#define PYR_MY 3 // ... and rows above row 0 / below the last row
 #define ORBFE_RSRC_FLAGS 0x00020000 // word 3 of a gfx9 raw buffer descriptor (__builtin_amdgcn_make_buffer_rsrc): 32-bit data format, no swizzle, no stride
 
 // ---------------------------------------------------------------------------
@@ -64,7 +62,7 @@ __device__ __forceinline__ bool xcd_map_of(int bid, int blocks_per_unit, int n_u
 {
     const int lg = xcd_split_log2(n_units), xcd = bid & 7, jb = bid >> 3;
     const int per_xcd = (blocks_per_unit + (1 << lg) - 1) >> lg;
-    const int round = small_div(jb, per_xcd); // jb < 2^21: at most 2^24 blocks per launch (orbfe_create refuses blocks x images >= 2^23)
+    const int round = small_div(jb, per_xcd); // jb < 2^21: at most 2^24 blocks per launch (the planner refuses blocks x images >= 2^23)
     unit = round * (8 >> lg) + (xcd >> lg);
     blk = ((jb - round * per_xcd) << lg) + (xcd & ((1 << lg) - 1));
     return unit < n_units && blk < blocks_per_unit;

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256, 8) void describe_generic_kernel(DeviceConfig c
     // (0 outside |u| <= umax[|v|]).  Integer sums: the order does not matter, the result is IC_Angle's exactly.
     uint32_t mw_u[4] = {0, 0, 0, 0}, mw_1[4] = {0, 0, 0, 0};
     int mw_v[4] = {0, 0, 0, 0};
-    if (dot_moments) { // host-built per-lane constants (orbfe_api.hip), 48 bytes per lane: three 128-bit loads per wave
+    if (dot_moments) { // host-built per-lane constants (orbfe_plan.cpp), 48 bytes per lane: three 128-bit loads per wave
         const uint4 *mt = (const uint4 *)buf.mom_tab + 3 * lane;
         const uint4 a = mt[0], b = mt[1], c = mt[2];
         mw_u[0] = a.x; mw_u[1] = a.y; mw_u[2] = a.z; mw_u[3] = a.w;
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(256, 8) void describe_kernel(DeviceConfig cfg, Devi
         }
     }
     const int c_l = lane < cfg.nlevels ? sel_cnt[lane] : 0;
-    // per-lane moment weights (host-built, orbfe_api.hip): 4 words (u + 16 inside the circle, else 0), 4 words (1 / 0), v
+    // per-lane moment weights (host-built, orbfe_plan.cpp): 4 words (u + 16 inside the circle, else 0), 4 words (1 / 0), v
     const uint4 *mt = (const uint4 *)buf.mom_tab + 3 * lane;
     const uint4 mwu = mt[0], mw1 = mt[1];
     const int mv = (int)mt[2].x;

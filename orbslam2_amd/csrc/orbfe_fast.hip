@@ -294,7 +294,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
         const int dr = (int)((aux_g >> 17) & 0x7fu); // 64 / ng, ng = (iw + 3) >> 2 groups per interior row; group j covers c = 4 j .. 4 j + 3
         const int pw = tile_pitch >> 2;
         const pk16 tp = {(short)t, (short)t};
-        // From fast_lane_tab (orbfe_api.hip builds it with these formulas): rl = lane / ng, jg = lane - rl * ng, c0 = 4 jg; the lane works when rl < dr;
+        // From fast_lane_tab (orbfe_plan.cpp builds it with these formulas): rl = lane / ng, jg = lane - rl * ng, c0 = 4 jg; the lane works when rl < dr;
         // vm01 / vm23: which of the lane's four pixels exist, as sign bits of the halves (a ballot of `value & mask != 0` is one compare; a
         // ballot of a boolean expression is a select plus a compare); vl01 / vl23: the same in the last band, which the cell's bottom may cut;
         // e01: entries c | (r + 1) << 8 of pixels 0 1 in the two halves (the row bias keeps the word positive)
@@ -489,10 +489,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 }
 
 
-static inline int max_cell_w(const DeviceConfig &cfg) { int m = 0; for (int l = 0; l < cfg.nlevels; l++) m = cfg.lv[l].w_cell > m ? cfg.lv[l].w_cell : m; return m; }
 static inline int max_cell_h(const DeviceConfig &cfg) { int m = 0; for (int l = 0; l < cfg.nlevels; l++) m = cfg.lv[l].h_cell > m ? cfg.lv[l].h_cell : m; return m; }
-
-int orbfe_fast_tile_pitch(const DeviceConfig &cfg) { return (max_cell_w(cfg) + 6 + 15) & ~15; } // whole 16-byte chunks (the staging stores 128 bits at a time)
 
 void orbfe_launch_fast(const DeviceConfig &cfg_in, const DeviceBuffers &buf, int n_images, bool buckets, hipStream_t s, int blur_first_level)
 {

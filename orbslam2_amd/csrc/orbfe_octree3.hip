@@ -31,16 +31,13 @@
 // per CU and two rounds of 25 us each).  What left the LDS: the node boxes (never read: a node's children come from the count
 // pyramid, its box is implied by root + path), the best-key pyramid after the pyramid step (copied to an HBM scratch slice, read
 // back by the final selection: one more dependent load per kept node), half of the count pyramid (depths 4 and 5 are 16 bit:
-// a bucket holds at most a few thousand strict-NMS survivors, orbfe_create checks), the sort keys (they alias the node array
+// a bucket holds at most a few thousand strict-NMS survivors, the planner checks), the sort keys (they alias the node array
 // that is being built).
 #ifndef OT3_THREADS
 #define OT3_THREADS 256
 #endif
 #define OT3_WAVES (OT3_THREADS / 64)
 #define OT3_DB 5                       // bucket depth
-#define OT3_ROOTS 4                    // root slots per level (n_ini <= 4)
-#define OT3_PYR (OT3_ROOTS * 1365)     // sum_{d=0..5} 4^d = 1365 entries per root
-#define OT3_HI (OT3_ROOTS * 85)        // entries of depths 0..3 (32-bit counts); depths 4 and 5 follow as 16-bit counts
 static_assert(OT3_PYR == ORBFE_BK_PYR, "the best-key scratch of orbfe_api.hip holds one pyramid per (image, level)");
 #define OT3_BUCKETS (OT3_ROOTS * 1024)
 // best key: score (8 bits) << 24 | ~(cell (12 bits) << 12 | slot (12 bits)); the host checks the field widths
@@ -121,14 +118,6 @@ struct Ot3Nodes {
     int *dr;                 // depth | root << 4
 };
 
-// bytes of one node array: three words per node, and room for the sort keys of the "largest node first" phase, which are built
-// in the array that is not in use (the next pass's nodes are written after the ranking)
-__host__ __device__ __forceinline__ size_t ot3_slot_bytes(int cap, int sort_cap)
-{
-    const size_t a = 3 * sizeof(int) * (size_t)cap, k = sizeof(unsigned long long) * (size_t)sort_cap;
-    return ((a > k ? a : k) + 15) & ~(size_t)15;
-}
-
 __device__ __forceinline__ void ot3_bind(Ot3Nodes &n, uint8_t *&p, int cap, int sort_cap)
 {
     uint8_t *q = p;
@@ -136,22 +125,6 @@ __device__ __forceinline__ void ot3_bind(Ot3Nodes &n, uint8_t *&p, int cap, int 
     n.path = (unsigned *)q; q += sizeof(unsigned) * cap;
     n.dr = (int *)q;
     p += ot3_slot_bytes(cap, sort_cap);
-}
-
-// bytes of the node tables (two node arrays, per-node bookkeeping) of one workgroup
-size_t orbfe_octree3_node_bytes(int max_nodes, int sort_cap)
-{
-    const size_t cap = (size_t)max_nodes;
-    return ((2 * ot3_slot_bytes(max_nodes, sort_cap) + sizeof(int) * cap * (4 + 1 + 1 + 1 + 1) + 64) + 255) & ~(size_t)255;
-}
-
-// dynamic LDS of octree3_kernel: the count pyramid (32-bit entries for depths 0..3, 16-bit for depths 4 and 5), then one region
-// that holds the best-key pyramid while the buckets are summed up and the node tables afterwards (unless those live in HBM)
-size_t orbfe_octree3_lds_bytes(int max_nodes, int sort_cap, bool nodes_in_hbm)
-{
-    const size_t cnt = sizeof(int) * OT3_HI + sizeof(uint16_t) * (OT3_PYR - OT3_HI), best = sizeof(int) * OT3_PYR;
-    const size_t nodes = nodes_in_hbm ? 0 : orbfe_octree3_node_bytes(max_nodes, sort_cap);
-    return ((cnt + 15) & ~(size_t)15) + (best > nodes ? best : nodes) + 64;
 }
 
 // root and quadrant path of a point down to `depth` (src/ORBextractor.cc:537-564 for the root, :145-209 for a split)
@@ -261,7 +234,7 @@ __global__ __launch_bounds__(OT3_THREADS) __attribute__((amdgpu_waves_per_eu(4))
     const int region_h = (L.h - cfg.edge_threshold + 3) - cfg.min_border;
     const int n_ini = L.n_ini, quota = L.quota;
     const float hx = L.hx;
-    const int db = L.bk_depth; // this level's bucket depth: 5, or 4 (small levels: orbfe_create picks it so that every FAST cell has bucket partials)
+    const int db = L.bk_depth; // this level's bucket depth: 5, or 4 (small levels: the planner picks it so that every FAST cell has bucket partials)
 
     // ---- 1. buckets: the per-cell partial (count, best key) entries of fast_cell_kernel<.., true> (phase E), summed / maximised
     //      per bucket in LDS; bk_emap (host-built) names the bucket of every entry.  The candidates of cells without entries
@@ -274,7 +247,7 @@ __global__ __launch_bounds__(OT3_THREADS) __attribute__((amdgpu_waves_per_eu(4))
         auto cnt5_add = [&](int b, int v) { atomicAdd(&cnt5w[b >> 1], (unsigned)v << (16 * (b & 1))); };
         // 24 entries per thread in flight as six 128-bit loads of each array (one batch = 6144 entries covers level 0 of a KITTI frame;
         // with ten dword loads per array and 256 threads that level was three dependent load rounds: 7 us of the launch's critical
-        // path); orbfe_create starts every level's entries on a 16-byte boundary (padding entries are zero and never written); the
+        // path); the planner starts every level's entries on a 16-byte boundary (padding entries are zero and never written); the
         // first batch is issued before the LDS arrays are cleared
         const uint32_t *part = buf.bk_part + ib * cfg.bk_part_total + L.bk_part_off;
         const uint32_t *emap = buf.bk_emap + L.bk_part_off;

@@ -313,15 +313,6 @@ __global__ __launch_bounds__(OT_THREADS) void octree_generic_kernel(DeviceConfig
 }
 
 
-static inline int ot_sort_cap(const DeviceConfig &cfg) { int p = 1; while (p < cfg.max_nodes) p <<= 1; return p; }
-
-size_t orbfe_octree_lds_bytes(const DeviceConfig &cfg)
-{
-    const int cap = cfg.max_nodes;
-    const size_t node = 2 * sizeof(int) * cap + 4 * sizeof(short) * cap + ((cap + 7) / 8) * 8;
-    return sizeof(unsigned long long) * ot_sort_cap(cfg) + 2 * node + sizeof(int) * 4 * cap + 4 * sizeof(int) * cap;
-}
-
 void orbfe_launch_octree_generic(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_images, hipStream_t s)
 {
     dim3 grid(cfg.nlevels, n_images);
@@ -334,5 +325,5 @@ void orbfe_launch_octree_generic(const DeviceConfig &cfg, const DeviceBuffers &b
         (void)hipFuncSetAttribute((const void *)octree_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         attr_set[dev] = true;
     }
-    hipLaunchKernelGGL(octree_generic_kernel, grid, dim3(OT_THREADS), orbfe_octree_lds_bytes(cfg), s, cfg, buf, ot_sort_cap(cfg));
+    hipLaunchKernelGGL(octree_generic_kernel, grid, dim3(OT_THREADS), orbfe_octree_lds_bytes(cfg), s, cfg, buf, orbfe_sort_cap(cfg.max_nodes));
 }

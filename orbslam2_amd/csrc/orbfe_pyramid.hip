@@ -280,26 +280,7 @@ __global__ __launch_bounds__(256) void pyr_resize_kernel(DeviceConfig cfg, Devic
 // 0.110; a wave walking 16 / 32 / 64 rows with the next group's loads in flight: 0.124 / 0.130 / 0.154 (fewer, longer waves
 // lose: these launches live on the number of independent waves).  Levels whose words reach further than 8 bytes (scale
 // factors above ~2) keep pyr_resize_kernel, and ORBFE_PYR_LDS=1 forces it.
-// first source column of extended column i (cv::resize's xofs, as orbfe_create builds the table; it checks this formula against it)
-__host__ __device__ __forceinline__ int resize_first_source(int dx, double scale, int src_w)
-{
-    const float fx = (float)(((double)dx + 0.5) * scale - 0.5);
-    int sx = (int)floorf(fx);
-    sx = sx < 0 ? 0 : sx;
-    return sx >= src_w - 1 ? src_w - 1 : sx;
-}
-__host__ __device__ __forceinline__ int resize_word_base(int xw, int dst_w, double scale, int src_w)
-{
-    int lo = 0x7fffffff;
-    for (int j = 0; j < 4; j++) {
-        int q = 4 * xw + j - PYR_MX;
-        if (dst_w == 1) q = 0;
-        else while (q < 0 || q >= dst_w) q = q < 0 ? -q : 2 * dst_w - 2 - q;
-        lo = q < lo ? q : lo;
-    }
-    return resize_first_source(lo, scale, src_w);
-}
-int orbfe_resize_word_base_host(int xw, int dst_w, double scale, int src_w) { return resize_word_base(xw, dst_w, scale, src_w); }
+// resize_word_base (orbfe_config.h) is the first-source-column formula the planner checks against the column table
 
 // PACKED0 (round 4): the source is level 0 read IN PLACE from the caller's packed image (DeviceBuffers::lv0_packed) -- rows at any
 // alignment, so the 96-bit window is loaded at the row's own 4-byte boundary and the byte shift is per row; the one window that
@@ -346,7 +327,7 @@ __device__ __forceinline__ void resize_direct_rows(const DeviceConfig &cfg, cons
     // (wave-uniform) reads scalar loads whatever stores to the pyramid are around
     typedef const __attribute__((address_space(4))) uint32_t *rs_const_ptr;
     const rs_const_ptr yt = (rs_const_ptr)(uintptr_t)(buf.rs_tab + D.rs_ytab_off);
-    const int base = LOOKUP ? (int)dt[nx + xw] : resize_word_base(xw, D.w, D.rs_scale_x, S.w); // orbfe_create checks the formula against the table
+    const int base = LOOKUP ? (int)dt[nx + xw] : resize_word_base(xw, D.w, D.rs_scale_x, S.w); // the planner checks the formula against the table
     // three words in ONE global_load_dwordx3 (a struct of three fields is split into two overlapping 64-bit loads as soon as its
     // fields are selected between, as the clamped-window fix-up below does)
     typedef uint32_t win_v __attribute__((ext_vector_type(3)));
@@ -438,7 +419,7 @@ __global__ __launch_bounds__(256) void pyr_resize_direct_kernel(DeviceConfig cfg
 // 2 us of work at 346 x 105), and each re-reads from HBM what the previous one just wrote.  Here a workgroup owns a STRIP of
 // ORBFE_TAIL_COLS extended columns of the last level over all its rows and walks the chain in LDS: it stages the columns of
 // level F - 1 it needs (all rows), computes from them its columns of level F (written to HBM and kept in LDS), from those its
-// columns of level F + 1, and so on.  Which columns those are is a host-built plan (orbfe_api.hip, from the same column
+// columns of level F + 1, and so on.  Which columns those are is a host-built plan (orbfe_plan.cpp, from the same column
 // tables), including the margin columns at the left / right of each level, which no later level reads; a strip's neighbours
 // share one or two columns per level with it (computed by both: same arithmetic, same bytes) -- cutting by rows instead costs
 // 40 % in halo rows (measured: no gain over the separate launches).
@@ -619,7 +600,7 @@ __global__ __launch_bounds__(256) void blur_kernel(DeviceConfig cfg, DeviceBuffe
 // the two kinds of waves slow each other down by more than the overlap returns: the blur streams whole rows at ~5 TB/s, the
 // resize lives on many short waves); 16- / 8-row blur bands in the interleaved order 0.189 / 0.192; s_setprio 3 for the
 // resize waves: no change.  So what the fusion buys is the launch boundary and the drain of the blur's last waves, 4 x ~1 us.
-// ORBFE_NO_FUSE=1 (orbfe_create) keeps the launches apart.
+// ORBFE_NO_FUSE=1 (read by the planner) keeps the launches apart.
 template <int RB, bool PACKED0 = false, bool LOOKUP = false>
 __global__ __launch_bounds__(256) void pyr_resize_blur_kernel(DeviceConfig cfg, DeviceBuffers buf, int level, int strips, int n_resize, int tile_begin, int tile_end)
 {
@@ -647,7 +628,7 @@ __global__ __launch_bounds__(256) void pyr_resize_blur_kernel(DeviceConfig cfg, 
 // same arithmetic, same bytes; ~12 % more level-l work).  Phase 2 (after one barrier): the same resize from the LDS tile (three
 // aligned LDS words per row and lane instead of a 96-bit global load, then the identical v_alignbyte / v_perm / v_dot2 passes).
 // Both levels must be resizable by the LDS-free kernel (LevelInfo::rs_direct); the host plans the rectangles from the same tables
-// (orbfe_api.hip: pair plan) and falls back to single-level launches when a rectangle would not fit.  ORBFE_NO_PAIR=1 disables it.
+// (orbfe_plan.cpp: pair plan) and falls back to single-level launches when a rectangle would not fit.  ORBFE_NO_PAIR=1 disables it.
 // ---------------------------------------------------------------------------
 #define PP_LDS_ROWS 17 // 16 tile rows + one spare: a lane's 12-byte window may run past its row's last word
 template <bool PACKED0>

@@ -51,3 +51,35 @@ def test_half_precision_thresholds():
             e = t.bit_length() - 1
             bits = ((e + 15) << 10) | ((t << (10 - e)) & 0x3ff)
         assert bits == int(np.float16(t).view(np.uint16)), t
+
+
+def test_real_cell_aux_words(tmp_path):
+    # the words the planner really writes (tests/asan/plan_harness.cpp runs orbfe_plan.cpp): for every cell with a FAST call,
+    # x = shape | (64 / ng) << 17 | last band's first row << 24 and y = ceil(2^16 / cpr) | (64 / cpr) << 17, whose multiplier
+    # divides every lane exactly
+    from tests.test_plan_host import NAMED, _line, run_harness
+    lines = [_line(n, w, h, nf) for n, w, h, nf in NAMED] + [_line("wide_sf", 700, 420, 2400, sf=2.2, nl=4, hp=9, edge=19)]
+    r = run_harness(lines, tmp_path, "--dump", "cell_info,cell_aux")
+    dumps = {}
+    for ln in r.stdout.splitlines():
+        if ln.startswith("dump "):
+            f = ln.split()
+            dumps[(f[1], f[2])] = [int(x, 16) for x in f[3:]]
+    checked = 0
+    for name in [ln.split()[0] for ln in lines]:
+        info, aux = dumps[(name, "cell_info")], dumps[(name, "cell_aux")]
+        assert len(info) == 2 * len(aux)
+        for k in range(len(aux) // 2):
+            if not info[4 * k] & 0x100:
+                continue
+            tw, th = info[4 * k + 2] & 0xff, (info[4 * k + 2] >> 8) & 0xff
+            iw, ih = tw - 6, th - 6
+            ng = (iw + 3) >> 2
+            dr = 64 // ng
+            cpr = (((tw + 3) >> 2) + 3) >> 2
+            assert (aux[2 * k] >> 17) & 0x7f == dr >= 1 and aux[2 * k] >> 24 == ((ih - 1) // dr) * dr, (name, k)
+            m = aux[2 * k + 1] & 0x1ffff
+            assert m == (65536 + cpr - 1) // cpr and aux[2 * k + 1] >> 17 == 64 // cpr, (name, k)
+            assert all((lane * m) >> 16 == lane // cpr for lane in range(64))
+            checked += 1
+    assert checked > 5000
