@@ -3,7 +3,9 @@
 //   name width height nfeatures scale_factor nlevels ini_th min_th patch_size half_patch edge_threshold max_images knobs
 // (knobs: "-" or NAME=VALUE,NAME=VALUE of the ORBFE_* environment knobs, set before PlanKnobs::from_env()).  Prints per case
 // the status and FNV-1a digests of the config, the per-level tables and every named device table (tests/test_plan_host.py
-// compares them with tests/golden/plan_digests.json), and a VIOLATION line for every coverage invariant an accepted plan breaks.
+// compares them with tests/golden/plan_digests.json), a "facts" line with the launch choices of an accepted plan (tail, pair and
+// ride thresholds, level 0 in place, per level rs_direct / rs_rw / pp_ok), and a VIOLATION line for every coverage invariant an
+// accepted plan breaks.
 // --dump NAME[,NAME]: also print those tables' words (cell_info, cell_aux).
 #include "../../orbslam2_amd/csrc/orbfe_plan.h"
 
@@ -125,6 +127,12 @@ int main(int argc, char **argv)
             tab("cell_info", P->cell_info); tab("cell_aux", P->cell_aux); tab("fast_lane_tab", P->fast_lane_tab);
             tab("bk_tab", P->bk_tab); tab("bk_off", P->bk_off); tab("bk_emap", P->bk_emap); tab("blur_tile_info", P->blur_tile_info);
             tab("slot_level", P->slot_level); tab("patch_uv", P->patch_uv); tab("mom_tab", P->mom_tab);
+            // the plan facts the GPU tests are chosen for (tests/test_plan_host.py); not part of the digests
+            printf("facts %s tail_first %d tail_n %d tail_max_images %d pp_max_images %d blur_ride_min_images %d blur_ride_from %d inplace_ok %d",
+                   name, P->cfg.tail_first, P->cfg.tail_n, P->cfg.tail_max_images, P->cfg.pp_max_images, P->blur_ride_min_images,
+                   P->blur_ride_from, (int)P->inplace_ok);
+            for (int l = 1; l < nl; l++) printf(" L%d %d,%d,%d", l, P->cfg.lv[l].rs_direct, P->cfg.lv[l].rs_rw, P->cfg.lv[l].pp_ok);
+            printf("\n");
             check(name, p, *P);
             for (const char *t : {"cell_info", "cell_aux"}) {
                 if (dump.find(t) == std::string::npos) continue;

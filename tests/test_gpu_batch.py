@@ -92,31 +92,50 @@ def test_fetch_batch_async_into_pinned_buffers(batch):
 
 
 KITTI = dict(width=1241, height=376, nfeatures=2000, fx=718.856, fy=718.856, cx=607.1928, cy=185.2157, bf=386.1448)
+# geometry -> (config, stereo pairs per call, distinct pairs): the BASELINE cameras (TUM1, EuRoC and D435i plan no pyramid tail, KITTI a
+# three-level one) and widths of every other residue mod 4 (level 1 read in place by pyr_resize_direct_kernel<4, true, true>)
+BATCH_GEOMS = {
+    "kitti": (KITTI, 64, 16),
+    "tum1": (dict(width=640, height=480, nfeatures=1000, fx=517.3, fy=516.5, cx=318.6, cy=255.3, bf=40.0), 32, 6),
+    "euroc": (dict(width=752, height=480, nfeatures=1200, fx=458.654, fy=457.296, cx=367.215, cy=248.375, bf=47.9), 32, 4),
+    "d435i": (dict(width=1280, height=720, nfeatures=2500, fx=911.0, fy=911.0, cx=640.0, cy=360.0, bf=45.5), 32, 4),
+    "402x201": (dict(width=402, height=201, nfeatures=600, fx=350.0, fy=350.0, cx=201.0, cy=100.5, bf=140.0), 33, 6),
+    "403x202": (dict(width=403, height=202, nfeatures=600, fx=350.0, fy=350.0, cx=201.5, cy=101.0, bf=140.0), 32, 4),
+    "404x200": (dict(width=404, height=200, nfeatures=600, fx=350.0, fy=350.0, cx=202.0, cy=100.0, bf=140.0), 32, 4),
+}
 
 
-def test_kitti_batch_of_64_pairs_every_distinct_pair_vs_oracle():
+@pytest.mark.parametrize("geom", list(BATCH_GEOMS))
+def test_kitti_batch_of_64_pairs_every_distinct_pair_vs_oracle(geom, monkeypatch):
     """BASELINE.json config 4 at its stated size: 64 KITTI-geometry stereo pairs in flight in ONE orbfe_enqueue_stereo call
     (what bench.py times), built from 16 distinct seeds; EVERY slot's keypoints (all fields), descriptors, uRight and depth
-    are compared with the CPU oracle of its pair, bit for bit (uRight / depth: north_star's 1e-4 is met with margin 0)."""
+    are compared with the CPU oracle of its pair, bit for bit (uRight / depth: north_star's 1e-4 is met with margin 0).
+    The other cameras and row alignments run the same 64-image plan (one launch per level, word bases from rs_tab / rs_blk,
+    every blur in FAST's launch) at 32 or more pairs from 4 to 6 distinct ones; three stream groups cut the same batch into
+    chains below 64 images, which run the small-batch plan."""
     import torch
     from oracle import oracle as O
     from orbslam2_amd import api
-    P, ND = 64, 16
-    distinct = [synth.stereo_pair(KITTI["width"], KITTI["height"], seed=7100 + 13 * i) for i in range(ND)]
+    from tests.plan_knobs import clear_plan_knobs
+    clear_plan_knobs(monkeypatch)  # tools/r05_fullsuite.sh may force another plan for the whole run
+    cfg, P, ND = BATCH_GEOMS[geom]
+    distinct = [synth.stereo_pair(cfg["width"], cfg["height"], seed=7100 + 13 * i) for i in range(ND)]
     refs = []
     for l, r in distinct:
-        exl, exr = O.Extractor(nfeatures=KITTI["nfeatures"]), O.Extractor(nfeatures=KITTI["nfeatures"])
+        exl, exr = O.Extractor(nfeatures=cfg["nfeatures"]), O.Extractor(nfeatures=cfg["nfeatures"])
         kl, dl = exl.extract(l); kr, dr = exr.extract(r)
-        ur, dp, m = O.stereo_matches(exl, exr, kl, dl, kr, dr, KITTI["bf"], KITTI["fx"])
+        ur, dp, m = O.stereo_matches(exl, exr, kl, dl, kr, dr, cfg["bf"], cfg["fx"])
         assert m > 100
         refs.append((kl, dl, kr, dr, ur, dp))
     order = [(5 * i + 3) % ND for i in range(P)]  # neighbouring slots hold different pairs
-    host = np.empty((2 * P, KITTI["height"], KITTI["width"]), np.uint8)
+    assert all(a != b for a, b in zip(order, order[1:]))
+    host = np.empty((2 * P, cfg["height"], cfg["width"]), np.uint8)
     for i, k in enumerate(order):
         host[2 * i], host[2 * i + 1] = distinct[k]
     dev = torch.from_numpy(host).cuda()
-    ctx = api.Context(max_images=2 * P, **KITTI)
-    for groups in (1, 2):
+    ctx = api.Context(max_images=2 * P, **cfg)
+    assert ctx.blur_ride_from(2 * P) == 0  # the plan under test: every level's blur in FAST's launch
+    for groups in (1, 2, 3):
         ctx.set_streams(groups)
         ctx.enqueue_stereo(dev.data_ptr(), P, torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
@@ -125,7 +144,7 @@ def test_kitti_batch_of_64_pairs_every_distinct_pair_vs_oracle():
             kl, dl, kr, dr, ur, dp = refs[k]
             left = ctx.fetch_image(2 * i, stereo=True)
             right = ctx.fetch_image(2 * i + 1)
-            what = "groups %d slot %d (pair %d)" % (groups, i, k)
+            what = "%s groups %d slot %d (pair %d)" % (geom, groups, i, k)
             assert counts[2 * i] == len(kl) and counts[2 * i + 1] == len(kr), what
             for f in ("x", "y", "size", "angle", "response", "octave", "class_id"):
                 assert np.array_equal(left["kps"][f], kl[f]), what + " left " + f

@@ -187,6 +187,20 @@ def test_lds_resize_kernel_still_matches(monkeypatch):
             assert np.array_equal(ctx.fetch_pyramid(0, l), ex.pyramid_level(l)), (lds, l)
         assert np.array_equal(k, kr.astype(api.KP_DTYPE)) and np.array_equal(d, dr), lds
         ctx.close()
+    # 3840 x 2160: the source rows of 16 output rows of levels 1 and 2 do not fit 60 KB of LDS, so the planner stages 2 rows per
+    # wave there (pyr_resize_kernel<2>; tests/test_plan_host.py pins that choice)
+    from tests.plan_knobs import clear_plan_knobs
+    clear_plan_knobs(monkeypatch)
+    monkeypatch.setenv("ORBFE_PYR_LDS", "1")
+    big = synth.mono_image(3840, 2160, seed=14)
+    ex = O.Extractor(nfeatures=8000)
+    kr, dr = ex.extract(big)
+    ctx = api.Context(width=3840, height=2160, nfeatures=8000)
+    k, d = ctx.extract(big)
+    for l in range(8):
+        assert np.array_equal(ctx.fetch_pyramid(0, l), ex.pyramid_level(l)), ("4K", l)
+    assert len(kr) > 4000 and np.array_equal(k, kr.astype(api.KP_DTYPE)) and np.array_equal(d, dr)
+    ctx.close()
 
 
 @pytest.mark.parametrize("w,h,nlevels", [(48, 45, 2), (65, 49, 3), (257, 52, 4), (60, 300, 5), (1029, 70, 6)])

@@ -101,3 +101,66 @@ def test_host_trace_lines_are_unchanged(tmp_path):
     r = run_harness([_line("kitti_trace", 1241, 376, 2000, knobs="ORBFE_HOST_TRACE=1")], tmp_path)
     trace = [ln for ln in r.stderr.splitlines() if ln.startswith("orbfe: ")]
     assert len(trace) == 23 and digest(trace) == json.load(open(FIXTURE))["trace_kitti"], "\n".join(trace)
+
+
+def facts(stdout):
+    """case name -> the plan facts of its "facts" line (which blocks() leaves out of the digests): tail_first, tail_n,
+    tail_max_images, pp_max_images, blur_ride_min_images, blur_ride_from, inplace_ok and levels {l: (rs_direct, rs_rw, pp_ok)}"""
+    out = {}
+    for ln in stdout.splitlines():
+        t = ln.split()
+        if t and t[0] == "facts":
+            f = {t[i]: int(t[i + 1]) for i in range(2, 16, 2)}
+            f["levels"] = {int(t[i][1:]): tuple(int(v) for v in t[i + 1].split(",")) for i in range(16, len(t), 2)}
+            out[t[1]] = f
+    return out
+
+
+BIG = 1 << 30  # a threshold no batch reaches (ORBFE_NO_TAIL=0 / ORBFE_NO_PAIR=0: INT_MAX)
+NO_TAIL = lambda f: f["tail_n"] == 0
+TAIL3 = lambda f: f["tail_n"] == 3 and f["inplace_ok"] == 1 and f["levels"][1][0] == 1
+LARGE_KNOB = {  # what each knob of the 32-pair rows of test_launch_plan_knobs_change_no_result changes
+    "ORBFE_BLUR_RIDE_FROM=1": lambda f: f["blur_ride_from"] == 1 and f["blur_ride_min_images"] == 1 and f["inplace_ok"] == 1,
+    "ORBFE_BLUR_RIDE_FROM=3": lambda f: f["blur_ride_from"] == 3 and f["blur_ride_min_images"] == 1 and f["inplace_ok"] == 1,
+    "ORBFE_NO_FUSE=1": lambda f: f["inplace_ok"] == 1,
+    "ORBFE_PYR_LDS=1": lambda f: not any(v[0] for v in f["levels"].values()) and f["inplace_ok"] == 0,
+    "ORBFE_NO_TAIL=0": lambda f: f["tail_max_images"] >= BIG,
+    "ORBFE_NO_PAIR=0": lambda f: f["pp_max_images"] >= BIG and f["levels"][1][2] == 1,
+    "ORBFE_NO_INPLACE=1": lambda f: f["inplace_ok"] == 0,
+}
+# level 1 read in place and not paired: pyr_resize_blur_kernel<4, true, false> / pyr_resize_direct_kernel<4, true, false> below 64 images
+UNPAIRED_IN_PLACE = lambda f: f["inplace_ok"] == 1 and f["levels"][1][0] == 1 and f["tail_first"] != 1 and not any(v[2] for v in f["levels"].values())
+
+
+def gpu_plan_cases():
+    """(harness line, the property the GPU case of the same geometry and knobs is there for)"""
+    c = [(_line("tum1", 640, 480, 1000, mi=64), NO_TAIL), (_line("euroc", 752, 480, 1200, mi=64), NO_TAIL),
+         (_line("d435i", 1280, 720, 2500, mi=64), NO_TAIL), (_line("kitti", 1241, 376, 2000, mi=128), TAIL3),
+         (_line("w402", 402, 201, 600, mi=66), TAIL3), (_line("w403", 403, 202, 600, mi=64), TAIL3),
+         (_line("w404", 404, 200, 600, mi=64), TAIL3), (_line("s400", 400, 200, 400, mi=130), TAIL3),
+         (_line("s400_l3", 400, 200, 400, nl=3, mi=64), lambda f: (f["tail_first"], f["tail_n"], f["inplace_ok"]) == (1, 2, 0)),
+         (_line("s400_sf26", 400, 200, 400, sf=2.6, nl=3, mi=64), lambda f: all(v[:2] == (0, 4) for v in f["levels"].values())),
+         (_line("uhd_lds", 3840, 2160, 8000, knobs="ORBFE_PYR_LDS=1", mi=2),
+          lambda f: [f["levels"][l][:2] for l in (1, 2)] == [(0, 2), (0, 2)])]
+    for name, w, h, nf in [("s400", 400, 200, 400), ("tum1", 640, 480, 1000)]:
+        c += [(_line("%s/%s" % (name, k), w, h, nf, knobs=k, mi=64), p) for k, p in LARGE_KNOB.items()]
+    for name, w, h, nf, mi in [("kitti", 1241, 376, 2000, 6), ("tum1", 640, 480, 1000, 2)]:
+        c += [(_line("%s/%s" % (name, k), w, h, nf, knobs=k, mi=mi), p) for k, p in
+              [("ORBFE_NO_PAIR=1", UNPAIRED_IN_PLACE),
+               ("ORBFE_NO_PAIR=1,ORBFE_BLUR_RIDE_FROM=0", lambda f: UNPAIRED_IN_PLACE(f) and f["blur_ride_from"] == 0)]]
+    return c
+
+
+def test_gpu_cases_run_the_plans_they_are_chosen_for(tmp_path):
+    """The GPU tests of the batch-size-dependent plans (tests/test_gpu_plan_switches.py, the geometry sweep of
+    tests/test_gpu_batch.py, the knob rows of tests/test_round4_entry_points.py, the 4K case of tests/test_gpu_sweep.py) each
+    target a plan variant; a planner change that moves a case off its variant fails here instead of silently testing another."""
+    cases = gpu_plan_cases()
+    got = facts(run_harness([ln for ln, _ in cases], tmp_path).stdout)
+    assert len(got) == len(cases)
+    for ln, prop in cases:
+        name = ln.split()[0]
+        assert prop(got[name]), (name, got[name])
+        if ln.split()[-1] == "-":  # the default thresholds: pairs and the tail up to 63 images, every blur in FAST's launch from 64
+            f = got[name]
+            assert (f["tail_max_images"], f["pp_max_images"], f["blur_ride_min_images"], f["blur_ride_from"]) == (63, 63, 64, 0), name

@@ -125,6 +125,9 @@ def _compare(ctx, s, T0, outlier=None):
     (15, dict(n=4000, has_frac=0.5)),
     (16, dict(n=64, bad_frac=0.0, noise_px=0.0)),
     (17, dict(rv=(0.2, -0.1, 0.15), t=(0.8, -0.3, 0.9))),  # far from the identity start: rejected trials, lambda growth
+    (18, dict(n=4096)),                              # the most keypoint slots the LDS edge table holds (PO_LDS_CAP_MAX)
+    (19, dict(n=4097)),                              # one more: pose_opt_kernel<TH, false>, edge table in HBM
+    (20, dict(n=6000, bad_frac=0.3)),
 ])
 def test_gpu_pose_optimization_matches_oracle(seed, kw):
     ctx = _ctx()
@@ -177,6 +180,17 @@ def test_gpu_pose_optimization_batch_is_per_problem():
         assert np.array_equal(Tg, Tb[k]) and ng == nb[k] and np.array_equal(outg, outb[off[k]:off[k + 1]])
         Tr, outr, nr = _oracle(s, T0[k])
         assert nr == nb[k] and np.array_equal(outr, outb[off[k]:off[k + 1]]) and np.abs(Tr - Tb[k]).max() <= POSE_ATOL
+    # one problem above the LDS edge table's 4096 slots among small ones: the whole batch takes the HBM kernel
+    scenes = [scene(40 + k, n=n) for k, n in enumerate([300, 4500, 17, 0, 1200])]
+    off = np.cumsum([0] + [len(s["keys"]) for s in scenes]).astype(np.int32)
+    cat = {k: np.concatenate([s[k] for s in scenes]) for k in ("keys", "ur", "has", "Xw")}
+    T0 = np.tile(np.eye(4, dtype=np.float32), (len(scenes), 1, 1))
+    T0[4, :3, 3] = [-0.1, 0.02, 0.15]
+    Tb, outb, nb = ctx.pose_optimization_batch(T0, off, cat["keys"], cat["ur"], cat["has"], cat["Xw"])
+    for k, s in enumerate(scenes):
+        Tr, outr, nr = _oracle(s, T0[k])
+        assert nr == nb[k] and np.array_equal(outr, outb[off[k]:off[k + 1]]) and np.abs(Tr - Tb[k]).max() <= POSE_ATOL, k
+    assert nb[1] > 1000
     ctx.close()
 
 

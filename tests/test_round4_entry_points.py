@@ -87,34 +87,46 @@ def test_packed_block_on_goldens_and_natural_pairs():
         ctx.close()
 
 
-@pytest.mark.parametrize("u16", [False, True])
-def test_enqueue_rgbd_equals_single_rgbd_frames(u16):
+@pytest.mark.parametrize("u16,n", [pytest.param(False, 5, id="False"), pytest.param(True, 5, id="True"),
+                                   pytest.param(False, 65, id="False-65"), pytest.param(True, 65, id="True-65")])
+def test_enqueue_rgbd_equals_single_rgbd_frames(u16, n):
+    """orbfe_enqueue_rgbd == orbfe_rgbd_frame of every frame == the oracle (extraction, then uRight / depth from the depth map);
+    65 frames (6 distinct, neighbours different) run the 64-image plan."""
     import torch
+    from oracle import oracle as O
     from orbslam2_amd import api
-    W, H, NF, n = 424, 240, 500, 5
+    W, H, NF = 424, 240, 500
     cfg = dict(width=W, height=H, nfeatures=NF, fx=300.0, fy=300.0, cx=W / 2, cy=H / 2, bf=15.0)
-    frames = []
-    for i in range(n):
+    nd = min(n, 6)
+    order = list(range(n)) if n <= nd else [(5 * i + 3) % nd for i in range(n)]
+    factor = np.float32(1.0) / np.float32(1000.0)
+    frames, oracle = [], []
+    for i in range(nd):
         img, _, depth = synth.stereo_pair(W, H, seed=700 + i, with_depth=True, bf=cfg["bf"])
         if u16:
             depth = np.clip(np.round(depth * 1000.0), 0, 65535).astype(np.uint16)
         frames.append((img, depth))
+        k, d = O.Extractor(nfeatures=NF).extract(img)
+        ur, dp = O.stereo_from_rgbd(k, k, depth.astype(np.float32) * factor if u16 else depth, cfg["bf"])
+        oracle.append((k.astype(api.KP_DTYPE), d, ur, dp))
     single = api.Context(max_images=1, **cfg)
-    factor = 1.0 / 1000.0
-    ref = [single.rgbd_frame(g, d, factor) for g, d in frames]
+    ref = [single.rgbd_frame(g, d, float(factor)) for g, d in frames]
     single.close()
+    for r, (k, d, ur, dp) in zip(ref, oracle):
+        assert r["kps"].tobytes() == k.tobytes() and np.array_equal(r["desc"], d)
+        assert r["u_right"].tobytes() == ur.tobytes() and r["depth"].tobytes() == dp.tobytes()
     ctx = api.Context(max_images=n, **cfg)
-    d_gray = torch.from_numpy(np.stack([g for g, _ in frames])).cuda()
-    dstack = np.stack([d for _, d in frames])
+    d_gray = torch.from_numpy(np.stack([frames[j][0] for j in order])).cuda()
+    dstack = np.stack([frames[j][1] for j in order])
     d_depth = torch.from_numpy(dstack.view(np.int16) if u16 else dstack).cuda()  # torch has no uint16 on every build: same bytes
     st = torch.cuda.Stream()
     for rep in range(2):
-        ctx.enqueue_rgbd(d_gray.data_ptr(), d_depth.data_ptr(), n, depth_is_u16=u16, depth_map_factor=factor, stream=st.cuda_stream)
+        ctx.enqueue_rgbd(d_gray.data_ptr(), d_depth.data_ptr(), n, depth_is_u16=u16, depth_map_factor=float(factor), stream=st.cuda_stream)
         st.synchronize()
-        for i in range(n):
+        for i, j in enumerate(order):
             got = ctx.fetch_image(i, stereo=True)
-            assert got["kps"].tobytes() == ref[i]["kps"].tobytes() and np.array_equal(got["desc"], ref[i]["desc"])
-            assert got["u_right"].tobytes() == ref[i]["u_right"].tobytes() and got["depth"].tobytes() == ref[i]["depth"].tobytes()
+            assert got["kps"].tobytes() == ref[j]["kps"].tobytes() and np.array_equal(got["desc"], ref[j]["desc"]), (n, i)
+            assert got["u_right"].tobytes() == ref[j]["u_right"].tobytes() and got["depth"].tobytes() == ref[j]["depth"].tobytes(), (n, i)
     assert sum((r["depth"] > 0).sum() for r in ref) > 200
     ctx.close()
 
@@ -213,23 +225,65 @@ def test_packed_block_stored_directly_into_pinned_host_memory(batch):
     ctx.close()
 
 
+def _knob_rows():
+    """(w, h, nf, n_pairs, knobs), pytest id.  The first rows force one knob on small batches; the rows of 32 pairs run the 64-image
+    plan (one launch per level, word bases from the table, every blur in FAST's launch) under each alternative, on a geometry with
+    a pyramid tail (400 x 200) and one without (TUM1); the small-batch ORBFE_NO_PAIR=1 rows send level 1, read in place, through
+    pyr_resize_blur_kernel<4, true, false> (alone) and pyr_resize_direct_kernel<4, true, false> (with ORBFE_BLUR_RIDE_FROM=0)."""
+    rows = [((w, h, nf, n, ((k, v),))) for w, h, nf, n in [(1241, 376, 2000, 3), (640, 480, 1000, 1), (403, 202, 300, 2)]
+            for k, v in [("ORBFE_NO_PROC_ORDER", "1"), ("ORBFE_BLUR_RIDE_FROM", "0"), ("ORBFE_BLUR_RIDE_FROM", "3")]]
+    large = [("ORBFE_BLUR_RIDE_FROM", "1"), ("ORBFE_BLUR_RIDE_FROM", "3"), ("ORBFE_NO_FUSE", "1"), ("ORBFE_PYR_LDS", "1"),
+             ("ORBFE_NO_TAIL", "0"), ("ORBFE_NO_PAIR", "0"), ("ORBFE_NO_INPLACE", "1")]
+    rows += [(w, h, nf, 32, (kv,)) for w, h, nf in [(400, 200, 400), (640, 480, 1000)] for kv in large]
+    rows += [(w, h, nf, n, ks) for w, h, nf, n in [(1241, 376, 2000, 3), (640, 480, 1000, 1)]
+             for ks in [(("ORBFE_NO_PAIR", "1"),), (("ORBFE_NO_PAIR", "1"), ("ORBFE_BLUR_RIDE_FROM", "0"))]]
+    return [pytest.param(*r, id="-".join(str(x) for x in r[:4] + sum(r[4], ()))) for r in rows]
+
+
+KNOB_ROWS = _knob_rows()
+
+
+@pytest.fixture(scope="module")
+def knob_oracle():
+    """(w, h, nf, seed) -> the oracle's keypoints, descriptors, uRight, depth and the right image's blurred pyramid, computed once"""
+    from oracle import oracle as O
+    cache = {}
+
+    def get(w, h, nf, seed):
+        key = (w, h, nf, seed)
+        if key not in cache:
+            l, r = synth.stereo_pair(w, h, seed=seed)
+            exl, exr = O.Extractor(nfeatures=nf), O.Extractor(nfeatures=nf)
+            kl, dl = exl.extract(l); kr, dr = exr.extract(r)
+            ur, dp, _ = O.stereo_matches(exl, exr, kl, dl, kr, dr, 140.0, 350.0)
+            cache[key] = dict(images=(l, r), kl=kl, dl=dl, kr=kr, dr=dr, ur=ur, dp=dp,
+                              blur=[O.gaussian7(exr.pyramid_level(lv)) for lv in range(8)])
+        return cache[key]
+    return get
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("knob,off", [("ORBFE_NO_PROC_ORDER", "1"), ("ORBFE_BLUR_RIDE_FROM", "0"), ("ORBFE_BLUR_RIDE_FROM", "3")])
-@pytest.mark.parametrize("w,h,nf,n_pairs", [(1241, 376, 2000, 3), (640, 480, 1000, 1), (403, 202, 300, 2)])
-def test_launch_plan_knobs_change_no_result(knob, off, w, h, nf, n_pairs, monkeypatch):
+@pytest.mark.parametrize("w,h,nf,n_pairs,knobs", KNOB_ROWS)
+def test_launch_plan_knobs_change_no_result(w, h, nf, n_pairs, knobs, knob_oracle, monkeypatch):
     """describe_kernel walking the quadtree kernel's spatial processing order (default) or the slots (ORBFE_NO_PROC_ORDER=1), and the
     blur of every level / of levels 3.. riding in FAST's launch (ORBFE_BLUR_RIDE_FROM: the default of 64-image batches, forced here on small
-    ones) instead of beside the resize launches: the same bytes out, also for the blurred pyramid of every level (which the knob moves between launches)."""
+    ones) instead of beside the resize launches: the same bytes out, also for the blurred pyramid of every level (which the knob moves between launches).
+    Every other plan knob on 64-image batches, and sets of knobs: the same bytes as the default plan and as the oracle, every slot."""
     import torch
     from orbslam2_amd import api
+    from tests.plan_knobs import clear_plan_knobs
+    clear_plan_knobs(monkeypatch)  # tools/r05_fullsuite.sh may force another plan for the whole run
     cfg = dict(width=w, height=h, nfeatures=nf, fx=350.0, fy=350.0, cx=w / 2, cy=h / 2, bf=140.0, max_images=2 * n_pairs)
-    pairs = [synth.stereo_pair(w, h, seed=90 + i) for i in range(n_pairs)]
-    host = np.stack([im for p in pairs for im in p])
+    nd = min(n_pairs, 4)  # large batches: 4 distinct pairs, neighbouring slots different
+    order = list(range(n_pairs)) if n_pairs <= nd else [(5 * i + 3) % nd for i in range(n_pairs)]
+    refs = [knob_oracle(w, h, nf, 90 + k) for k in order]
+    host = np.stack([im for r in refs for im in r["images"]])
     dev = torch.from_numpy(host).cuda()
     res = {}
     for mode in ("default", "off"):
         if mode == "off":
-            monkeypatch.setenv(knob, off)
+            for k, v in knobs:
+                monkeypatch.setenv(k, v)
         ctx = api.Context(**cfg)
         ctx.enqueue_stereo(dev.data_ptr(), n_pairs, 0)
         ctx.synchronize()
@@ -243,3 +297,10 @@ def test_launch_plan_knobs_change_no_result(knob, off, w, h, nf, n_pairs, monkey
     for a, b in zip(res["defaultb"], res["offb"]):
         assert np.array_equal(a, b)
     assert len(res["default"][0]["kps"]) > 100
+    for i, r in enumerate(refs):
+        left, right = res["off"][2 * i], res["off"][2 * i + 1]
+        assert left["kps"].tobytes() == r["kl"].astype(api.KP_DTYPE).tobytes() and np.array_equal(left["desc"], r["dl"]), (knobs, i)
+        assert right["kps"].tobytes() == r["kr"].astype(api.KP_DTYPE).tobytes() and np.array_equal(right["desc"], r["dr"]), (knobs, i)
+        assert left["u_right"].tobytes() == r["ur"].tobytes() and left["depth"].tobytes() == r["dp"].tobytes(), (knobs, i)
+    for l in range(8):
+        assert np.array_equal(res["offb"][l], refs[-1]["blur"][l]), (knobs, l)
