@@ -61,7 +61,7 @@
 extern "C" {
 #endif
 
-#define ORBFE_ABI_VERSION 6 /* 2: orbfe_frame_view.device_slot_plus1; 3: .keyframe; 4: orbfe_get_camera, orbfe_assign_features_to_grid, orbfe_stereo_batch, orbfe_device_count, orbfe_set_profiling_interval; 5: orbfe_get_packed_layout, orbfe_fetch_batch_packed, orbfe_expand_packed, orbfe_stereo_batch_packed, orbfe_enqueue_rgbd; 6: orbfe_build_id, orbfe_set_pattern, orbfe_get_pattern, orbfe_blur_ride_from, orbfe_set_input_retained (additive: no struct changed; orbfe_fetch_pyramid(level 0) of an in-place batched call now needs the latter) */
+#define ORBFE_ABI_VERSION 6 /* 2: orbfe_frame_view.device_slot_plus1; 3: .keyframe; 4: orbfe_get_camera, orbfe_assign_features_to_grid, orbfe_stereo_batch, orbfe_device_count, orbfe_set_profiling_interval; 5: orbfe_get_packed_layout, orbfe_fetch_batch_packed, orbfe_expand_packed, orbfe_stereo_batch_packed, orbfe_enqueue_rgbd; 6: orbfe_build_id, orbfe_set_pattern, orbfe_get_pattern, orbfe_blur_ride_from, orbfe_set_input_retained (additive: no struct changed; orbfe_fetch_pyramid(level 0) of an in-place batched call now needs the latter); still 6, additive: orbfe_enqueue_search_by_projection_last, orbfe_enqueue_is_in_frustum, orbfe_enqueue_search_by_projection_points, orbfe_device_keys_un */
 
 enum {
     ORBFE_OK = 0,
@@ -338,9 +338,12 @@ int orbfe_hamming_matrix(orbfe_context *ctx, const uint8_t *desc_a, int na,
 
 /* ---- Tracking-thread matchers ----
  * Pointer-rich reference state is passed flattened: a MapPoint* becomes an index into the caller's
- * arrays (GetWorldPos -> pos[i][3], GetDescriptor -> desc[i][32], Observations() -> obs[i]).  All
- * arrays are host memory; calls are synchronous.  Window queries and Hamming distances run on the
- * GPU, the sequentially greedy resolution runs in order on the host (see orbfe_match.hip).
+ * arrays (GetWorldPos -> pos[i][3], GetDescriptor -> desc[i][32], Observations() -> obs[i]).  In the
+ * functions of this block all arrays are host memory and calls are synchronous: window queries and
+ * Hamming distances run on the GPU, the sequentially greedy resolution runs in order on the host (see
+ * orbfe_match.hip).  The two per-frame matchers of Tracking and isInFrustum also have an asynchronous
+ * form on device-resident arrays, orbfe_enqueue_* further down, where the resolution runs in order in
+ * one workgroup on the GPU (orbfe_match_device.hip) and the matches stay in HBM.
  * Camera intrinsics, bf and the scale factors are those of the context.  Poses are 3x4 row-major
  * [R|t] (the top rows of Frame::mTcw). */
 typedef struct orbfe_frame_view { /* what the matchers read from a Frame (include/Frame.h) */
@@ -537,6 +540,46 @@ int orbfe_enqueue_pose_optimization(orbfe_context *ctx, int n_problems, const in
                                     const orbfe_keypoint *d_keys_un, const float *d_u_right, const uint8_t *d_has_point,
                                     const float *d_Xw, float *d_Tcw, uint8_t *d_outlier, int32_t *d_n_inliers,
                                     int max_keypoints, void *stream);
+/* ---- the per-frame matchers of Tracking on device-resident data (orbfe_match_device.hip) ----
+ * Asynchronous on `stream` (NULL: the context's stream): nothing in these calls waits for the GPU or copies to the host, and
+ * nothing is allocated after the first call with a given size.  They are ordered after the latest extraction call by an event,
+ * whatever stream that ran on.  The calls of one context share scratch memory, so queue them on one stream (or order the
+ * streams yourself); the outputs of a call are complete when `stream` reaches that point.  Argument errors the host can see
+ * (NULL where not allowed, slot out of range, negative counts) return ORBFE_ERR_INVALID at once and queue nothing; what only
+ * the device can see is reported in d_status.  Every result equals that of the synchronous entry point on the same inputs.
+ * Device arrays must be aligned to their element type (descriptors: 4 bytes).
+ *
+ * SearchByProjection(CurrentFrame, LastFrame, th, bMono) on device-resident data.
+ * The current frame is image slot `slot` of this context's latest extraction call (as orbfe_frame_view.device_slot_plus1 - 1):
+ * keypoints (undistorted on the device when orbfe_set_distortion is active), descriptors, mvuRight (unless mono) and the
+ * keypoint count are read where the extraction left them.  bounds = mnMinX, mnMaxX, mnMinY, mnMaxY (4 host floats).
+ * d_Tcw_cur / d_Tcw_last: device, row-major, the first 12 floats are read ([R|t]; a 4x4 written by
+ * orbfe_enqueue_pose_optimization can be passed as it is).  The d_last_* arrays have n_last rows and the meaning of the
+ * host entry point's arguments.  d_cur_has_obs may be NULL.
+ * Outputs (device): d_cur_match[capacity] (entries >= the slot's count are left untouched), d_nmatches[1] (the reference's
+ * counter), d_status[1] (0, or an ORBFE_ERR_* code for what only the device can see: ORBFE_ERR_INVALID for an octave out of
+ * range in a valid row -- that row is then skipped, the other outputs are not meaningful).
+ * Optional outputs for orbfe_enqueue_pose_optimization, any may be NULL: d_has_point[capacity] (cur_match >= 0),
+ * d_Xw[capacity][3] (last_pos of the matched row, untouched where there is no match). */
+int orbfe_enqueue_search_by_projection_last(orbfe_context *ctx, int slot, const float *bounds,
+        const float *d_Tcw_cur, const float *d_Tcw_last, int n_last,
+        const float *d_last_pos, const uint8_t *d_last_desc, const int32_t *d_last_valid, const int32_t *d_last_obs,
+        const int32_t *d_last_octave, const float *d_last_angle, const uint8_t *d_cur_has_obs,
+        float th, int mono, int check_ori,
+        int32_t *d_cur_match, int32_t *d_nmatches, int32_t *d_status, uint8_t *d_has_point, float *d_Xw, void *stream);
+/* Frame::isInFrustum for n map points, device in / device out (orbfe_track_point records), asynchronous. */
+int orbfe_enqueue_is_in_frustum(orbfe_context *ctx, const float *d_Tcw, const float *bounds, int n,
+        const float *d_pos, const float *d_normal, const float *d_max_distance, const float *d_min_distance,
+        float viewing_cos_limit, orbfe_track_point *d_out, void *stream);
+/* SearchByProjection(F, vpMapPoints, th) on device-resident data; d_pts as written by orbfe_enqueue_is_in_frustum.  mvuRight of
+ * the slot is read (a stereo or RGB-D extraction call).  d_pt_pos (GetWorldPos, n_pts x 3) is only read for d_Xw. */
+int orbfe_enqueue_search_by_projection_points(orbfe_context *ctx, int slot, const float *bounds, int n_pts,
+        const orbfe_track_point *d_pts, const uint8_t *d_pt_desc, const int32_t *d_pt_obs, const float *d_pt_pos /* may be NULL */,
+        const uint8_t *d_cur_has_obs, float th, float nnratio,
+        int32_t *d_cur_match, int32_t *d_nmatches, int32_t *d_status, uint8_t *d_has_point, float *d_Xw, void *stream);
+/* mvKeysUn of image slot `slot` as the device-side matchers see it: the extraction's keypoint array, or, with distortion
+ * active, the undistorted copy (enqueued on `stream` if this frame has none yet).  For orbfe_enqueue_pose_optimization. */
+int orbfe_device_keys_un(orbfe_context *ctx, int slot, const orbfe_keypoint **d_keys_un, void *stream);
 /* KeyFrameDatabase::DetectLoopCandidates(KeyFrame *pKF, float minScore) (src/KeyFrameDatabase.cc:73-194; LoopClosing::DetectLoop,
  * src/LoopClosing.cc:131).  connected[k] != 0 marks the keyframes of pKF->GetConnectedKeyFrames() (may be NULL: none); covisibility
  * lists as for the relocalisation query.  Stateless: mLoopScore is only read for keyframes scored by the same call. */

@@ -36,6 +36,7 @@ EXPORTS = [
     "orbfe_png_last_error", "orbfe_png_info", "orbfe_png_decode", "orbfe_png_decode_batch",
     "orbfe_get_camera", "orbfe_assign_features_to_grid", "orbfe_set_profiling_interval", "orbfe_stereo_batch", "orbfe_device_count", "orbfe_vocab_bytes",
     "orbfe_get_packed_layout", "orbfe_fetch_batch_packed", "orbfe_expand_packed", "orbfe_enqueue_rgbd", "orbfe_stereo_batch_packed",
+    "orbfe_enqueue_search_by_projection_last", "orbfe_enqueue_is_in_frustum", "orbfe_enqueue_search_by_projection_points", "orbfe_device_keys_un",
 ]
 NUM_STAGES = 8
 STAGE_NAMES = ["ingest", "pyramid", "blur", "fast", "octree", "describe", "stereo_match", "stereo_median"]  # orbfe_stage_name()
@@ -190,6 +191,14 @@ def load():
     L.orbfe_enqueue_pose_optimization.argtypes = [vp, C.c_int] + [vp] * 8 + [C.c_int, vp]
     L.orbfe_search_for_initialization.restype = C.c_int
     L.orbfe_search_for_initialization.argtypes = [vp, fvp, fvp, vp, C.c_int, C.c_float, C.c_int, vp, ip]
+    L.orbfe_enqueue_search_by_projection_last.restype = C.c_int
+    L.orbfe_enqueue_search_by_projection_last.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 7 + [C.c_float, C.c_int, C.c_int] + [vp] * 6
+    L.orbfe_enqueue_is_in_frustum.restype = C.c_int
+    L.orbfe_enqueue_is_in_frustum.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_float, vp, vp]
+    L.orbfe_enqueue_search_by_projection_points.restype = C.c_int
+    L.orbfe_enqueue_search_by_projection_points.argtypes = [vp, C.c_int, vp, C.c_int] + [vp] * 5 + [C.c_float, C.c_float] + [vp] * 6
+    L.orbfe_device_keys_un.restype = C.c_int
+    L.orbfe_device_keys_un.argtypes = [vp, C.c_int, C.POINTER(vp), vp]
     _lib = L
     return L
 
@@ -518,6 +527,38 @@ class Context:
         self._check(self.L.orbfe_search_by_projection_points(self.h, C.byref(view), len(pts), _p(pts), _p(pd), _p(po),
                                                              None if ho is None else _p(ho), th, nnratio, _p(out), C.byref(nm)))
         return out[: view.n].copy(), nm.value
+
+    # ---- the same on device-resident data, asynchronous (integer device pointers and a stream; see include/orbfe.h) ----
+    def enqueue_search_by_projection_last(self, slot, bounds, d_Tcw_cur, d_Tcw_last, n_last, d_last_pos, d_last_desc, d_last_valid, d_last_obs,
+                                          d_last_octave, d_last_angle, d_cur_has_obs, th, mono, check_ori, d_cur_match, d_nmatches, d_status,
+                                          d_has_point=0, d_Xw=0, stream=0):
+        b = np.ascontiguousarray(bounds, np.float32)
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_search_by_projection_last(
+            self.h, slot, _p(b), v(d_Tcw_cur), v(d_Tcw_last), n_last, v(d_last_pos), v(d_last_desc), v(d_last_valid), v(d_last_obs), v(d_last_octave),
+            v(d_last_angle), v(d_cur_has_obs or None), th, int(mono), int(check_ori), v(d_cur_match), v(d_nmatches), v(d_status),
+            v(d_has_point or None), v(d_Xw or None), v(stream or None)))
+
+    def enqueue_is_in_frustum(self, d_Tcw, bounds, n, d_pos, d_normal, d_max_distance, d_min_distance, viewing_cos_limit, d_out, stream=0):
+        """d_out: n orbfe_track_point records (TP_DTYPE, 24 bytes each)."""
+        b = np.ascontiguousarray(bounds, np.float32)
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_is_in_frustum(self.h, v(d_Tcw), _p(b), n, v(d_pos), v(d_normal), v(d_max_distance), v(d_min_distance),
+                                                       viewing_cos_limit, v(d_out), v(stream or None)))
+
+    def enqueue_search_by_projection_points(self, slot, bounds, n_pts, d_pts, d_pt_desc, d_pt_obs, d_pt_pos, d_cur_has_obs, th, nnratio,
+                                            d_cur_match, d_nmatches, d_status, d_has_point=0, d_Xw=0, stream=0):
+        b = np.ascontiguousarray(bounds, np.float32)
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_search_by_projection_points(
+            self.h, slot, _p(b), n_pts, v(d_pts), v(d_pt_desc), v(d_pt_obs), v(d_pt_pos or None), v(d_cur_has_obs or None), th, nnratio,
+            v(d_cur_match), v(d_nmatches), v(d_status), v(d_has_point or None), v(d_Xw or None), v(stream or None)))
+
+    def device_keys_un(self, slot, stream=0) -> int:
+        """Device pointer to mvKeysUn of image slot `slot` (orbfe_keypoint records) for enqueue_pose_optimization."""
+        out = C.c_void_p()
+        self._check(self.L.orbfe_device_keys_un(self.h, slot, C.byref(out), C.c_void_p(stream or None)))
+        return out.value or 0
 
     def search_by_projection_kf(self, view, Tcw_cur, kf_pos, kf_desc, kf_valid, kf_angle, kf_max_distance, kf_min_distance, cur_has_point,
                                 th, orb_dist, check_ori):

@@ -123,6 +123,18 @@ int orbfe_ctx_wait_foreign_stream(orbfe_context *ctx)
         return fail(ctx, ORBFE_ERR_HIP, "hipStreamWaitEvent on the latest extraction failed");
     return ORBFE_OK;
 }
+// Orders stream `s` after the latest extraction call without a host wait.  The call's own stream handle is not kept (see
+// ev_latest), so a caller stream always waits for the event; waiting for an event of the same stream costs nothing on the GPU.
+int orbfe_ctx_order_after_extraction(orbfe_context *ctx, hipStream_t s)
+{
+    if (!ctx->latest_foreign) {
+        if (s == ctx->stream || ctx->epoch == 0) return ORBFE_OK;
+        if (hipEventRecord(ctx->ev_latest, ctx->stream) != hipSuccess) return fail(ctx, ORBFE_ERR_HIP, "hipEventRecord on the context's stream failed");
+    }
+    if (hipStreamWaitEvent(s, ctx->ev_latest, 0) != hipSuccess) return fail(ctx, ORBFE_ERR_HIP, "hipStreamWaitEvent on the latest extraction failed");
+    return ORBFE_OK;
+}
+int orbfe_ctx_last_images(const orbfe_context *ctx) { return ctx->last_images; }
 std::recursive_mutex &orbfe_ctx_mutex(orbfe_context *ctx) { return ctx->mu; }
 // Keypoint count of image slot `slot` of the latest extraction call: from the host copy the frame entry points leave behind,
 // else one blocking read of the counters per call (batched calls whose results were not fetched yet).

@@ -49,6 +49,13 @@ const DeviceBuffers *orbfe_ctx_buffers(const orbfe_context *ctx);
 int orbfe_ctx_slot_count(orbfe_context *ctx, int slot, int *cnt); // keypoints in image slot `slot` of the latest extraction call
 unsigned orbfe_ctx_epoch(const orbfe_context *ctx);          // counts the extraction calls enqueued on this context
 int orbfe_ctx_wait_foreign_stream(orbfe_context *ctx);      // makes the context's stream wait for the latest extraction call (event, no host wait)
+int orbfe_ctx_order_after_extraction(orbfe_context *ctx, hipStream_t s); // the same for any stream `s` (the asynchronous matchers run on the caller's)
+int orbfe_ctx_last_images(const orbfe_context *ctx);        // image slots the latest extraction call filled
+
+// scratch and caches of the asynchronous, device-resident matchers (orbfe_match_device.hip); owned by orbfe_match_state
+struct orbfe_match_device_state;
+orbfe_match_device_state *orbfe_ctx_match_device_state(orbfe_context *ctx);
+void orbfe_match_device_state_destroy(orbfe_match_device_state *s);
 
 struct orbfe_bow_state;
 orbfe_bow_state *orbfe_bow_state_create();

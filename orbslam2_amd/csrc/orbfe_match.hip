@@ -268,7 +268,8 @@ struct orbfe_match_state {
     unsigned grid_epoch = 0;
     int grid_slot = -1, grid_n = -1;
     float grid_bounds[4] = {0, 0, 0, 0};
-    ~orbfe_match_state() { if (h_in) (void)hipHostFree(h_in); if (h_out) (void)hipHostFree(h_out); }
+    orbfe_match_device_state *dev = nullptr; // the asynchronous matchers keep their own scratch and grid (orbfe_match_device.hip)
+    ~orbfe_match_state() { if (h_in) (void)hipHostFree(h_in); if (h_out) (void)hipHostFree(h_out); if (dev) orbfe_match_device_state_destroy(dev); }
 };
 
 static orbfe_match_state *match_state(orbfe_context *ctx) { return orbfe_ctx_match_state(ctx); }
@@ -969,4 +970,5 @@ try {
 } ORBFE_CATCH(ctx)
 
 orbfe_match_state *orbfe_match_state_create() { return new (std::nothrow) orbfe_match_state(); }
+orbfe_match_device_state **orbfe_match_device_slot(orbfe_match_state *s) { return &s->dev; }
 void orbfe_match_state_destroy(orbfe_match_state *s) { delete s; }

@@ -1,0 +1,708 @@
+// orbfe_match_device.hip -- the two per-frame matchers of Tracking on device-resident data, asynchronous on the caller's stream:
+// SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cc:1324-1466), Frame::isInFrustum (src/Frame.cc:256-315)
+// and SearchByProjection(F, vpMapPoints, th) (src/ORBmatcher.cc:43-135).  Device pointers in, matches in HBM, no host wait.
+//
+// orbfe_match.hip is the synchronous form and the second implementation this one is tested against: there the map points are
+// projected on the host, the four best keys per query come back over the link and orbfe_match_resolve.h replays the accept
+// rules.  Here the same steps are kernels:
+//   grid_build_kernel     Frame::AssignFeaturesToGrid of the slot (its keypoint count read from the extraction's counter)
+//   window_topk_kernel    one wave per map point: its 32-byte MatchQuery (the per-point functions of orbfe_match_resolve.h), then
+//                         GetFeaturesInArea + Hamming distances, the 4 smallest statically admissible keys
+//   frustum_kernel        Frame::isInFrustum, one lane per map point
+//   resolve_kernel        ONE workgroup replays the sequentially greedy accept rules in query order (see there)
+//   gather_kernel         optional has_point / Xw for orbfe_enqueue_pose_optimization
+// Candidate keys are those of orbfe_match.hip: dist << 36 | ix << 30 | iy << 24 | idx << 8 | octave; the smallest key is the
+// reference loop's first minimum.  No candidate list is kept: a query whose four keys are all taken recomputes its window.
+#include "../../include/orbfe.h"
+#include "orbfe_device.h"
+#include "orbfe_host.h"
+#include "orbfe_match_resolve.h"
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#define GRID_COLS 64 // FRAME_GRID_COLS include/Frame.h:36
+#define GRID_ROWS 48 // FRAME_GRID_ROWS include/Frame.h:37
+#define GRID_CELLS (GRID_COLS * GRID_ROWS)
+#define TOPK 4
+#define RESOLVE_THREADS 512 // queries evaluated per step of the resolve kernel
+#define RESOLVE_CHUNK 1024  // queries staged in LDS at a time
+#define NO_KEY (~0ull)
+#define Q_BAD 4 // MatchQuery::flags bit of the device path: the point's octave / predicted level is out of range
+
+using orbfe_resolve::Camera;
+using orbfe_resolve::HISTO_LENGTH;
+using orbfe_resolve::key_dist;
+using orbfe_resolve::key_idx;
+using orbfe_resolve::key_level;
+using orbfe_resolve::MatchQuery;
+using orbfe_resolve::TH_HIGH;
+
+// the resident frame as the kernels see it
+struct DevFrame {
+    const KeyPointPOD *keys; // mvKeysUn
+    const uint8_t *desc;
+    const float *u_right;    // null: no mvuRight gate
+    const int *n_ptr;        // the slot's keypoint counter (DeviceBuffers::kp_cnt)
+    int cap;                 // keypoint capacity of a slot
+    float min_x, min_y, inv_w, inv_h;
+    int *cell_off, *cell_idx; // CSR over ix * GRID_ROWS + iy
+};
+struct Projection {
+    Camera C;
+    float sf[ORBFE_MAX_LEVELS];
+    int nlevels;
+    float log_sf;
+    float min_x, max_x, min_y, max_y;
+};
+
+__device__ __forceinline__ int frame_count(const DevFrame &f)
+{
+    const int n = *f.n_ptr;
+    return n < 0 ? 0 : (n > f.cap ? f.cap : n);
+}
+// Frame::PosInGrid (src/Frame.cc:383-393; Q6: round(), column 64 dropped), as grid_count_kernel of orbfe_match.hip
+__device__ __forceinline__ int grid_cell(const DevFrame &f, int i)
+{
+    const int px = (int)roundf(__fmul_rn(__fsub_rn(f.keys[i].x, f.min_x), f.inv_w));
+    const int py = (int)roundf(__fmul_rn(__fsub_rn(f.keys[i].y, f.min_y), f.inv_h));
+    return (px >= 0 && px < GRID_COLS && py >= 0 && py < GRID_ROWS) ? px * GRID_ROWS + py : -1;
+}
+
+// Frame::AssignFeaturesToGrid in one workgroup: count, scan and fill over LDS counters
+__global__ __launch_bounds__(1024) void grid_build_kernel(DevFrame f)
+{
+    __shared__ int s_cnt[GRID_CELLS];
+    __shared__ int s_scan[1024];
+    const int tid = threadIdx.x, n = frame_count(f);
+    for (int c = tid; c < GRID_CELLS; c += 1024) s_cnt[c] = 0;
+    __syncthreads();
+    for (int i = tid; i < n; i += 1024) {
+        const int c = grid_cell(f, i);
+        if (c >= 0) atomicAdd(&s_cnt[c], 1);
+    }
+    __syncthreads();
+    const int per = GRID_CELLS / 1024; // 3
+    int sum = 0;
+    for (int k = 0; k < per; k++) sum += s_cnt[tid * per + k];
+    s_scan[tid] = sum;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int v = tid >= o ? s_scan[tid - o] : 0;
+        __syncthreads();
+        s_scan[tid] += v;
+        __syncthreads();
+    }
+    int run = s_scan[tid] - sum;
+    for (int k = 0; k < per; k++) {
+        const int c = tid * per + k, v = s_cnt[c];
+        f.cell_off[c] = run;
+        s_cnt[c] = run; // becomes the fill cursor
+        run += v;
+    }
+    if (tid == 1023) f.cell_off[GRID_CELLS] = s_scan[1023];
+    __syncthreads();
+    for (int i = tid; i < n; i += 1024) {
+        const int c = grid_cell(f, i);
+        if (c >= 0) f.cell_idx[atomicAdd(&s_cnt[c], 1)] = i; // order inside a cell is irrelevant (keys carry it)
+    }
+}
+static_assert(GRID_CELLS % 1024 == 0, "grid_build_kernel gives every thread the same number of cells");
+
+// ---- projection: where a query comes from.  The window kernel asks for query i (every lane of its wave states the same
+// arithmetic), so the matchers need no launch of their own for it ----
+struct LastSource { // SearchByProjection(CurrentFrame, LastFrame, th, bMono)
+    Projection P;
+    const float *Tcw_cur, *Tcw_last, *pos;
+    const int32_t *valid, *octave;
+    float th;
+    int mono;
+    __device__ __forceinline__ MatchQuery query(int i) const
+    {
+        float Tc[12], Tl[12];
+        for (int k = 0; k < 12; k++) { Tc[k] = Tcw_cur[k]; Tl[k] = Tcw_last[k]; }
+        bool forward, backward;
+        orbfe_resolve::last_motion(P.C, Tc, Tl, mono, forward, backward);
+        MatchQuery Q = {0, 0, 0, 0, -1, 0, 0, 0};
+        const float p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]};
+        if (orbfe_resolve::query_last_point(P.C, P.sf, P.nlevels, P.min_x, P.max_x, P.min_y, P.max_y, Tc, forward, backward, p, valid[i], octave[i], th, Q) < 0)
+            Q.flags = Q_BAD;
+        return Q;
+    }
+};
+struct PointsSource { // SearchByProjection(F, vpMapPoints, th)
+    Projection P;
+    const orbfe_track_point *pts;
+    float th;
+    __device__ __forceinline__ MatchQuery query(int i) const
+    {
+        MatchQuery Q = {0, 0, 0, 0, -1, 0, 0, 0};
+        const orbfe_track_point pt = pts[i];
+        if (orbfe_resolve::query_track_point(P.sf, P.nlevels, pt, th, Q) < 0) Q.flags = Q_BAD;
+        return Q;
+    }
+};
+
+__global__ __launch_bounds__(256) void frustum_kernel(Projection P, const float *__restrict__ Tcw, int n, const float *__restrict__ pos,
+                                                      const float *__restrict__ normal, const float *__restrict__ max_distance,
+                                                      const float *__restrict__ min_distance, float viewing_cos_limit, orbfe_track_point *__restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float T[12], ow[3];
+    for (int k = 0; k < 12; k++) T[k] = Tcw[k];
+    orbfe_resolve::camera_center(T, ow);
+    const float p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]}, nr[3] = {normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]};
+    orbfe_track_point o;
+    orbfe_resolve::frustum_point(P.C, P.nlevels, P.log_sf, T, ow, P.min_x, P.max_x, P.min_y, P.max_y, p, nr, max_distance[i], min_distance[i], viewing_cos_limit, o);
+    out[i] = o;
+}
+
+// ---- window query ----
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long w)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)w, o, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(w >> 32), o, 64);
+        const unsigned long long t = ((unsigned long long)hi << 32) | lo;
+        w = t < w ? t : w;
+    }
+    return w;
+}
+__device__ __forceinline__ int wave_sum_i(int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// The cells of a query's window (Frame::GetFeaturesInArea, src/Frame.cc:328-381); the arithmetic of window_candidates_kernel
+struct Window { int min_cx, min_cy, ncy, ncells; };
+__device__ __forceinline__ Window query_window(const DevFrame &f, const MatchQuery &Q)
+{
+    Window w = {0, 0, 1, 0};
+    if (!(Q.flags & 1)) return w;
+    int v = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(Q.u, f.min_x), Q.r), f.inv_w));
+    w.min_cx = v > 0 ? v : 0;
+    v = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(Q.u, f.min_x), Q.r), f.inv_w));
+    const int max_cx = v < GRID_COLS - 1 ? v : GRID_COLS - 1;
+    v = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(Q.v, f.min_y), Q.r), f.inv_h));
+    w.min_cy = v > 0 ? v : 0;
+    v = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(Q.v, f.min_y), Q.r), f.inv_h));
+    const int max_cy = v < GRID_ROWS - 1 ? v : GRID_ROWS - 1;
+    if (w.min_cx < GRID_COLS && max_cx >= 0 && w.min_cy < GRID_ROWS && max_cy >= 0 && max_cx >= w.min_cx && max_cy >= w.min_cy) {
+        w.ncy = max_cy - w.min_cy + 1;
+        w.ncells = (max_cx - w.min_cx + 1) * w.ncy;
+    }
+    return w;
+}
+
+// Calls emit(key, idx) for every keypoint of the window this lane owns (cells lane, lane + 64, ...) that passes the level and
+// radius tests, with the Hamming distance to the query descriptor in the key (511: failed the mvuRight gate).
+template <class Emit>
+__device__ __forceinline__ void scan_window(const DevFrame &f, const MatchQuery &Q, const Window &w, const uint32_t *__restrict__ qdesc, int lane, Emit emit)
+{
+    const bool check_levels = (Q.min_level > 0) || (Q.max_level >= 0); // Q5, literally
+    uint32_t qd[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) qd[k] = qdesc[k];
+    for (int c = lane; c < w.ncells; c += 64) {
+        const int ix = w.min_cx + c / w.ncy, iy = w.min_cy + c % w.ncy;
+        const int cell = ix * GRID_ROWS + iy;
+        for (int j = f.cell_off[cell]; j < f.cell_off[cell + 1]; j++) {
+            const int idx = f.cell_idx[j];
+            const KeyPointPOD kp = f.keys[idx];
+            if (check_levels && (kp.octave < Q.min_level || (Q.max_level >= 0 && kp.octave > Q.max_level))) continue;
+            if (!(fabsf(__fsub_rn(kp.x, Q.u)) < Q.r && fabsf(__fsub_rn(kp.y, Q.v)) < Q.r)) continue;
+            unsigned dist = 0;
+            const uint32_t *p = (const uint32_t *)(f.desc + (size_t)idx * 32);
+#pragma unroll
+            for (int k = 0; k < 8; k++) dist += __popc(qd[k] ^ p[k]);
+            // the mvuRight gate (src/ORBmatcher.cc:93-98,1403-1409) is a pure function of the pair: mark it
+            if ((Q.flags & 2) && f.u_right && f.u_right[idx] > 0 && fabsf(__fsub_rn(Q.ur, f.u_right[idx])) > Q.ur_rad) dist = 511;
+            emit(((unsigned long long)dist << 36) | ((unsigned long long)ix << 30) | ((unsigned long long)iy << 24) | ((unsigned long long)idx << 8) |
+                     (unsigned long long)(kp.octave & 255),
+                 idx);
+        }
+    }
+}
+
+// One wave per query: the map point is projected into its MatchQuery (kept in q[] for the resolve kernel's re-scans), then every
+// lane keeps the TOPK smallest admissible keys of its own cells in registers and the wave merges them: any window size, no staging.
+// n_static = how many keys passed the static filters, -1 for a Q_BAD query.  The threads below the frame's keypoint count also
+// reset cur_match (the launch covers the keypoint capacity).
+template <class Source>
+__global__ __launch_bounds__(256) void window_topk_kernel(DevFrame f, Source src, MatchQuery *__restrict__ q, const uint8_t *__restrict__ qdesc, int nq,
+                                                          const uint8_t *__restrict__ blocked0, unsigned long long *__restrict__ topk,
+                                                          int *__restrict__ n_static, int32_t *__restrict__ cur_match)
+{
+    const int gid = blockIdx.x * 256 + threadIdx.x;
+    if (gid < frame_count(f)) cur_match[gid] = -1;
+    const int iq = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (iq >= nq) return;
+    const MatchQuery Q = src.query(iq);
+    if (lane == 0) q[iq] = Q;
+    const Window w = query_window(f, Q);
+    unsigned long long t0 = NO_KEY, t1 = NO_KEY, t2 = NO_KEY, t3 = NO_KEY;
+    int passed = 0;
+    if (w.ncells > 0)
+        scan_window(f, Q, w, (const uint32_t *)(qdesc + (size_t)iq * 32), lane, [&](unsigned long long key, int idx) {
+            if (key_dist(key) >= 256 || (blocked0 && blocked0[idx])) return; // static filters
+            passed++;
+            if (key < t3) {
+                t3 = key;
+                if (t3 < t2) { const unsigned long long x = t2; t2 = t3; t3 = x; }
+                if (t2 < t1) { const unsigned long long x = t1; t1 = t2; t2 = x; }
+                if (t1 < t0) { const unsigned long long x = t0; t0 = t1; t1 = x; }
+            }
+        });
+    passed = wave_sum_i(passed);
+    for (int r = 0; r < TOPK; r++) {
+        const unsigned long long m = wave_min_u64(t0);
+        if (lane == 0) topk[(size_t)iq * TOPK + r] = m;
+        if (m != NO_KEY && t0 == m) { t0 = t1; t1 = t2; t2 = t3; t3 = NO_KEY; } // keys are unique within a query: one lane retires it
+    }
+    if (lane == 0) n_static[iq] = (Q.flags & Q_BAD) ? -1 : passed;
+}
+
+// ---- resolve ----
+struct ResolveArgs {
+    DevFrame f;
+    const MatchQuery *q;
+    const uint8_t *qdesc;
+    int nq;
+    const unsigned long long *topk;
+    const int *n_static;
+    const int32_t *obs;       // Observations() of the map point of query i
+    const float *angle;       // last_angle (check_ori), else null
+    const uint8_t *blocked0;  // keypoints taken before the call, or null
+    int points;               // 0: the last-frame rule, 1: the local-map rule (best / second best, nnratio)
+    int check_ori;
+    float nnratio;
+    int32_t *ev;              // [nq] scratch: keypoint accepted by query i, or -1
+    int32_t *cur_match, *nmatches, *status;
+};
+
+__device__ __forceinline__ bool blk_test(const uint32_t *blk, int idx) { return (blk[idx >> 5] >> (idx & 31)) & 1u; }
+
+// What the resolve kernel keeps of a candidate key: dist << 24 | octave << 16 | idx.  The order of a query's keys is their position
+// in its prefix, so 32 bits are enough; admissible keys have dist < 256 and idx < 65535, so NO_PKEY is no key.
+#define NO_PKEY 0xffffffffu
+__device__ __forceinline__ uint32_t pack_key(unsigned long long k)
+{
+    return k == NO_KEY ? NO_PKEY : ((uint32_t)key_dist(k) << 24) | ((uint32_t)key_level(k) << 16) | (uint32_t)key_idx(k);
+}
+__device__ __forceinline__ int pkey_idx(uint32_t k) { return (int)(k & 0xffffu); }
+// the accept rules of resolve_last / resolve_points (orbfe_match_resolve.h) for one query, given its best and second-best free key
+__device__ __forceinline__ bool accept_rule(int points, float nnratio, uint32_t best, uint32_t second)
+{
+    if (best == NO_PKEY) return false;
+    const int best_dist = (int)(best >> 24);
+    if (!points) return best_dist <= TH_HIGH;
+    const int best_level = (int)((best >> 16) & 255u);
+    const int best_dist2 = second != NO_PKEY ? (int)(second >> 24) : 256, best_level2 = second != NO_PKEY ? (int)((second >> 16) & 255u) : -1;
+    if (best_dist > TH_HIGH) return false;
+    return !(best_level == best_level2 && (float)best_dist > nnratio * (float)best_dist2);
+}
+
+// One workgroup per call.  The accept rules are sequential only through the `blocked` flags (a keypoint taken by a map point
+// with observations is closed to every later query), and the flags only ever go from free to blocked.  So the workgroup
+// evaluates RESOLVE_THREADS consecutive queries at once against the current flags (512: measured best of 256 / 512 / 1024 -- a step
+// costs about a microsecond at any of these widths, a narrower one needs more steps, a wider one dearer barriers); a thread's answer is final unless an
+// EARLIER thread of the same step blocks a keypoint that this thread looked at and found free (its best, for the local-map
+// rule also its second best).  Every thread that would block a keypoint posts its index into a claim table (LDS, atomic
+// minimum, hashed by keypoint: a collision can only report a conflict that is none, which costs a step, never an answer);
+// the threads before the first conflict -- or before the first query whose four-key prefix ran out -- commit, the window
+// slides there and the rest are evaluated again.  At least one query commits per step, so the loop ends after at most nq steps.
+// A query whose prefix ran out (all of its keys blocked, more than TOPK statically admissible ones) gets its window scanned
+// again by wave 0 for the smallest keys that pass the static filters AND the current flags: exact, never a truncated answer.
+// cur_match[k] = the LAST query that took keypoint k = the largest index: an atomic maximum, so no store order matters.
+// LDS: blocked bitmask 8 KB (65536 keypoints) + claim table 16 KB + RESOLVE_CHUNK x (4 packed keys 16 B + event 4 B + n_static
+// and observation flag 2 B) = 46 KB.
+#define CLAIM_SLOTS 4096
+#define NO_CLAIM 0x7fffffff
+__global__ __launch_bounds__(RESOLVE_THREADS) void resolve_kernel(ResolveArgs a)
+{
+    __shared__ uint32_t s_blk[65536 / 32];
+    __shared__ int s_claim[CLAIM_SLOTS];
+    __shared__ uint32_t s_keys[TOPK][RESOLVE_CHUNK]; // packed key k of every query side by side: conflict-free reads
+    __shared__ int s_ev[RESOLVE_CHUNK];   // keypoint accepted by the chunk's query, or -1
+    __shared__ int8_t s_ns[RESOLVE_CHUNK]; // n_static clamped to [-1, TOPK + 1]
+    __shared__ uint8_t s_obs[RESOLVE_CHUNK];
+    __shared__ int s_hist[32];
+    __shared__ int s_nm, s_err, s_keep[3], s_stop;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int n = frame_count(a.f);
+    for (int w = tid; w < 65536 / 32; w += RESOLVE_THREADS) s_blk[w] = 0;
+    for (int w = tid; w < CLAIM_SLOTS; w += RESOLVE_THREADS) s_claim[w] = NO_CLAIM;
+    if (tid < 32) s_hist[tid] = 0;
+    if (tid == 0) { s_nm = 0; s_err = 0; }
+    __syncthreads();
+    if (a.blocked0)
+        for (int k = tid; k < n; k += RESOLVE_THREADS)
+            if (a.blocked0[k]) atomicOr(&s_blk[k >> 5], 1u << (k & 31));
+    for (int base = 0; base < a.nq; base += RESOLVE_CHUNK) {
+        const int cnt = a.nq - base < RESOLVE_CHUNK ? a.nq - base : RESOLVE_CHUNK;
+        for (int t = tid; t < cnt; t += RESOLVE_THREADS) { // stage the chunk
+            const ulonglong2 *tk = (const ulonglong2 *)(a.topk + (size_t)(base + t) * TOPK);
+            const ulonglong2 k01 = tk[0], k23 = tk[1];
+            s_keys[0][t] = pack_key(k01.x); s_keys[1][t] = pack_key(k01.y); s_keys[2][t] = pack_key(k23.x); s_keys[3][t] = pack_key(k23.y);
+            const int ns = a.n_static[base + t];
+            s_ns[t] = (int8_t)(ns < 0 ? -1 : (ns > TOPK ? TOPK + 1 : ns));
+            s_obs[t] = a.obs[base + t] > 0;
+            if (ns < 0) s_err = 1;
+        }
+        __syncthreads(); // also: the flags of blocked0 are set, the previous chunk's events are consumed
+        int b = 0;       // the same in every thread
+        while (b < cnt) {
+            const int j = b + tid;
+            const bool active = j < cnt;
+            uint32_t best = NO_PKEY, second = NO_PKEY;
+            bool need_full = false;
+            if (active) {
+                // the four keys and their flags are read at once (two LDS round trips instead of eight dependent ones); the keys
+                // ascend and NO_PKEY pads the end, whose index 0xffff reads a valid flag word
+                uint32_t key[TOPK];
+                bool free_[TOPK];
+#pragma unroll
+                for (int k = 0; k < TOPK; k++) key[k] = s_keys[k][j];
+#pragma unroll
+                for (int k = 0; k < TOPK; k++) free_[k] = !blk_test(s_blk, pkey_idx(key[k])) && key[k] != NO_PKEY;
+#pragma unroll
+                for (int k = TOPK - 1; k >= 0; k--)
+                    if (free_[k]) { second = best; best = key[k]; } // ends with the first free key in best, the next free one in second
+                if (!a.points) second = NO_PKEY;
+                const bool found = a.points ? second != NO_PKEY : best != NO_PKEY;
+                need_full = !found && s_ns[j] > TOPK; // the prefix ran out before the answer was found
+            }
+            const bool acc = active && !need_full && accept_rule(a.points, a.nnratio, best, second);
+            const int e1 = best != NO_PKEY ? pkey_idx(best) : -1, e2 = second != NO_PKEY ? pkey_idx(second) : -1;
+            const int blocks = (acc && s_obs[active ? j : 0]) ? e1 : -1; // the keypoint this thread closes
+            if (tid == 0) s_stop = NO_CLAIM;
+            if (blocks >= 0) atomicMin(&s_claim[blocks & (CLAIM_SLOTS - 1)], tid);
+            __syncthreads();
+            const bool conflict = (e1 >= 0 && s_claim[e1 & (CLAIM_SLOTS - 1)] < tid) || (e2 >= 0 && s_claim[e2 & (CLAIM_SLOTS - 1)] < tid);
+            if (active && (conflict || need_full)) atomicMin(&s_stop, 2 * tid + (need_full ? 0 : 1)); // need_full stays true whatever commits before
+            __syncthreads();
+            const int stop = s_stop;
+            const int left = cnt - b < RESOLVE_THREADS ? cnt - b : RESOLVE_THREADS;
+            const int fstop = stop == NO_CLAIM ? left : stop >> 1;       // threads below commit
+            const bool full = stop != NO_CLAIM && !(stop & 1);           // query b + fstop needs its window scanned again
+            if (blocks >= 0) s_claim[blocks & (CLAIM_SLOTS - 1)] = NO_CLAIM; // every claimant clears its slot
+            const bool commit = tid < fstop;
+            if (commit) {
+                s_ev[j] = acc ? e1 : -1;
+                if (blocks >= 0) atomicOr(&s_blk[blocks >> 5], 1u << (blocks & 31));
+            }
+            const int wave_acc = __popcll(__ballot(commit && acc));
+            if (lane == 0 && wave_acc) atomicAdd(&s_nm, wave_acc);
+            __syncthreads(); // the flags, the claim table and s_stop are settled for the next step
+            b += fstop;
+            if (!full) continue;
+            if (tid < 64) { // wave 0 scans the window of query b again under the current flags
+                const int gq = base + b;
+                const MatchQuery Q = a.q[gq];
+                const Window w = query_window(a.f, Q);
+                unsigned long long t0 = NO_KEY, t1 = NO_KEY;
+                if (w.ncells > 0)
+                    scan_window(a.f, Q, w, (const uint32_t *)(a.qdesc + (size_t)gq * 32), lane, [&](unsigned long long key, int idx) {
+                        if (key_dist(key) >= 256 || blk_test(s_blk, idx)) return; // s_blk holds the static blocks too
+                        if (key < t1) {
+                            t1 = key;
+                            if (t1 < t0) { const unsigned long long x = t0; t0 = t1; t1 = x; }
+                        }
+                    });
+                const unsigned long long fbest = wave_min_u64(t0);
+                const unsigned long long fsecond = wave_min_u64((fbest != NO_KEY && t0 == fbest) ? t1 : t0);
+                const bool facc = accept_rule(a.points, a.nnratio, pack_key(fbest), pack_key(fsecond));
+                if (lane == 0) {
+                    s_ev[b] = facc ? key_idx(fbest) : -1;
+                    if (facc) s_nm += 1; // no other thread touches s_nm between the two barriers around this block
+                    if (facc && s_obs[b]) atomicOr(&s_blk[key_idx(fbest) >> 5], 1u << (key_idx(fbest) & 31));
+                }
+            }
+            __syncthreads();
+            b += 1;
+        }
+        // the chunk's events: the last query that took a keypoint keeps it; rotHist[bin].push_back(bestIdx2), src/ORBmatcher.cc:1436-1445
+        for (int t = tid; t < cnt; t += RESOLVE_THREADS) {
+            const int kp = s_ev[t];
+            if (kp >= 0) atomicMax(&a.cur_match[kp], base + t);
+            if (a.check_ori) {
+                int e = -1;
+                if (kp >= 0) {
+                    const int bin = orbfe_resolve::rot_bin(a.angle[base + t], a.f.keys[kp].angle);
+                    atomicAdd(&s_hist[bin], 1);
+                    e = kp | (bin << 16);
+                }
+                a.ev[base + t] = e; // read back by this very thread below
+            }
+        }
+    }
+    if (a.check_ori) {
+        __syncthreads();
+        if (tid < 64) { // ComputeThreeMaxima as three_maxima (orbfe_match_resolve.h) states it, one bin per lane
+            const int sz = lane < HISTO_LENGTH ? s_hist[lane] : 0;
+            unsigned long long key = sz > 0 ? ((unsigned long long)sz << 32) | (unsigned)(0x7fffffff - lane) : 0ull; // 0: empty bin
+            int ind[3] = {-1, -1, -1}, val[3] = {0, 0, 0};
+            for (int r = 0; r < 3; r++) {
+                const unsigned long long m = ~wave_min_u64(~key); // the largest remaining (size, -index)
+                if (m == 0ull) break;
+                ind[r] = 0x7fffffff - (int)(unsigned)m;
+                val[r] = (int)(m >> 32);
+                if (key == m) key = 0ull;
+            }
+            if ((float)val[1] < 0.1f * (float)val[0]) { ind[1] = -1; ind[2] = -1; } // :1628-1637
+            else if ((float)val[2] < 0.1f * (float)val[0]) ind[2] = -1;
+            if (lane == 0) { s_keep[0] = ind[0]; s_keep[1] = ind[1]; s_keep[2] = ind[2]; }
+        }
+        __syncthreads(); // also orders the atomic maxima above before the stores below
+        for (int i = tid; i < a.nq; i += RESOLVE_THREADS) {
+            const int e = a.ev[i];
+            if (e < 0) continue;
+            const int bin = e >> 16;
+            if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) { // once per event, duplicates included (:1452-1463)
+                a.cur_match[e & 0xffff] = -1;
+                atomicSub(&s_nm, 1);
+            }
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        *a.nmatches = s_nm;
+        *a.status = s_err ? ORBFE_ERR_INVALID : ORBFE_OK;
+    }
+}
+static_assert(RESOLVE_CHUNK % RESOLVE_THREADS == 0, "resolve_kernel: the thread that stores an event of a chunk reads it back in the last pass");
+
+// mvpMapPoints of the matched keypoints as orbfe_enqueue_pose_optimization reads them
+__global__ __launch_bounds__(256) void gather_kernel(DevFrame f, const int32_t *__restrict__ cur_match, const float *__restrict__ pos,
+                                                     uint8_t *__restrict__ has_point, float *__restrict__ Xw)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= frame_count(f)) return;
+    const int m = cur_match[k];
+    if (has_point) has_point[k] = m >= 0;
+    if (Xw && pos && m >= 0) {
+        Xw[3 * k] = pos[3 * m];
+        Xw[3 * k + 1] = pos[3 * m + 1];
+        Xw[3 * k + 2] = pos[3 * m + 2];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------------------------
+struct orbfe_match_device_state {
+    DevBuf q, topk, n_static, ev, cells, keys_un; // grow-only scratch; calls of one context share it, so they are queued in stream order
+    std::vector<unsigned> un_epoch;               // per image slot: the extraction call whose keypoints keys_un holds undistorted
+    int un_ndist = 0;                             // ... with these coefficients (orbfe_set_distortion may change them between calls)
+    float un_dist[5] = {0, 0, 0, 0, 0};
+    unsigned grid_epoch = 0;                      // the grid in `cells`: slot grid_slot of extraction call grid_epoch, these keys and bounds
+    int grid_slot = -1;
+    const void *grid_keys = nullptr;
+    float grid_bounds[4] = {0, 0, 0, 0};
+};
+orbfe_match_device_state **orbfe_match_device_slot(orbfe_match_state *s); // orbfe_match.hip
+void orbfe_match_device_state_destroy(orbfe_match_device_state *s) { delete s; }
+orbfe_match_device_state *orbfe_ctx_match_device_state(orbfe_context *ctx)
+{
+    orbfe_match_state *ms = orbfe_ctx_match_state(ctx);
+    if (!ms) return nullptr;
+    orbfe_match_device_state **slot = orbfe_match_device_slot(ms);
+    if (!*slot) *slot = new (std::nothrow) orbfe_match_device_state();
+    return *slot;
+}
+
+#define DTRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return orbfe_fail(ctx, ORBFE_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
+
+static Projection projection_of(orbfe_context *ctx, const float *bounds)
+{
+    const orbfe_params *P = orbfe_ctx_params(ctx);
+    Projection p;
+    p.C = orbfe_resolve::camera_of(P);
+    const float *sf = orbfe_ctx_scale_factors(ctx);
+    for (int l = 0; l < ORBFE_MAX_LEVELS; l++) p.sf[l] = l < P->nlevels ? sf[l] : 0.f;
+    p.nlevels = P->nlevels;
+    p.log_sf = logf((float)(double)P->scale_factor); // mfLogScaleFactor = log(mfScaleFactor), src/Frame.cc:71
+    p.min_x = bounds[0]; p.max_x = bounds[1]; p.min_y = bounds[2]; p.max_y = bounds[3];
+    return p;
+}
+
+// Common entry work of the calls on a resident slot: argument checks, stream order, mvKeysUn.  No host wait.
+static int resident_frame(orbfe_context *ctx, int slot, hipStream_t s, orbfe_match_device_state *&st, const KeyPointPOD *&keys)
+{
+    const DeviceConfig *cfg = orbfe_ctx_config(ctx);
+    const DeviceBuffers *buf = orbfe_ctx_buffers(ctx);
+    if (slot < 0 || slot >= orbfe_ctx_last_images(ctx))
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d: the latest extraction call filled %d image slots", slot, orbfe_ctx_last_images(ctx));
+    if (cfg->sel_total > 65535) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "frames with more than 65535 keypoints are not supported by the matchers");
+    st = orbfe_ctx_match_device_state(ctx);
+    if (!st) return orbfe_fail(ctx, ORBFE_ERR_HIP, "out of host memory");
+    DTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    const unsigned epoch = orbfe_ctx_epoch(ctx);
+    const int rc = orbfe_ctx_order_after_extraction(ctx, s); // an event wait on the stream, no host wait
+    if (rc != ORBFE_OK) return rc;
+    const KeyPointPOD *raw = (const KeyPointPOD *)buf->kps + (size_t)slot * cfg->sel_total;
+    keys = raw;
+    if (cfg->n_dist > 0 && cfg->dist[0] != 0.0f) { // mvKeysUn: undistorted on the device once per frame (Frame::UndistortKeyPoints)
+        const int max_images = orbfe_ctx_params(ctx)->max_images;
+        if (st->keys_un.ensure(sizeof(KeyPointPOD) * (size_t)cfg->sel_total * max_images)) return orbfe_fail(ctx, ORBFE_ERR_HIP, "matcher scratch allocation failed");
+        bool same = st->un_ndist == cfg->n_dist && (int)st->un_epoch.size() >= max_images;
+        for (int k = 0; k < 5; k++) same = same && st->un_dist[k] == cfg->dist[k];
+        if (!same) {
+            st->un_epoch.assign(max_images, 0); // epoch 0 = no extraction call yet
+            st->un_ndist = cfg->n_dist;
+            for (int k = 0; k < 5; k++) st->un_dist[k] = cfg->dist[k];
+        }
+        KeyPointPOD *un = (KeyPointPOD *)st->keys_un.p + (size_t)slot * cfg->sel_total;
+        if (st->un_epoch[slot] != epoch) {
+            // the slot's count is only known on the device: every row of the slot goes through, rows past the count are never read
+            orbfe_launch_undistort(*cfg, raw, un, cfg->sel_total, s);
+            st->un_epoch[slot] = epoch;
+            if (st->grid_slot == slot) st->grid_slot = -1; // the grid was built from other keys
+        }
+        keys = un;
+    }
+    return ORBFE_OK;
+}
+
+// the slot as the kernels read it, its grid built if this is the first call on this frame with these bounds
+static int resident_grid(orbfe_context *ctx, int slot, const float *bounds, bool stereo, hipStream_t s, orbfe_match_device_state *&st, DevFrame &f)
+{
+    const DeviceConfig *cfg = orbfe_ctx_config(ctx);
+    const DeviceBuffers *buf = orbfe_ctx_buffers(ctx);
+    if (!bounds || !(bounds[1] > bounds[0]) || !(bounds[3] > bounds[2])) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "bad image bounds");
+    const KeyPointPOD *keys = nullptr;
+    int rc = resident_frame(ctx, slot, s, st, keys);
+    if (rc != ORBFE_OK) return rc;
+    if (st->cells.ensure(sizeof(int) * (size_t)(GRID_CELLS + 1 + cfg->sel_total))) return orbfe_fail(ctx, ORBFE_ERR_HIP, "matcher scratch allocation failed");
+    const size_t so = (size_t)slot * cfg->sel_total;
+    f.keys = keys;
+    f.desc = buf->desc + so * 32;
+    f.u_right = stereo ? buf->u_right + so : nullptr;
+    f.n_ptr = buf->kp_cnt + slot;
+    f.cap = cfg->sel_total;
+    f.min_x = bounds[0]; f.min_y = bounds[2];
+    f.inv_w = (float)GRID_COLS / (bounds[1] - bounds[0]); // mfGridElementWidthInv, src/Frame.cc:99
+    f.inv_h = (float)GRID_ROWS / (bounds[3] - bounds[2]);
+    f.cell_off = (int *)st->cells.p; f.cell_idx = f.cell_off + GRID_CELLS + 1;
+    const unsigned epoch = orbfe_ctx_epoch(ctx);
+    if (!(st->grid_epoch == epoch && st->grid_slot == slot && st->grid_keys == (const void *)f.keys && st->grid_bounds[0] == bounds[0] && st->grid_bounds[1] == bounds[1] &&
+          st->grid_bounds[2] == bounds[2] && st->grid_bounds[3] == bounds[3])) {
+        hipLaunchKernelGGL(grid_build_kernel, dim3(1), dim3(1024), 0, s, f);
+        st->grid_epoch = epoch; st->grid_slot = slot; st->grid_keys = f.keys;
+        for (int k = 0; k < 4; k++) st->grid_bounds[k] = bounds[k];
+    }
+    return ORBFE_OK;
+}
+
+static int ensure_query_scratch(orbfe_context *ctx, orbfe_match_device_state *st, int nq)
+{
+    const size_t m = nq > 0 ? nq : 1;
+    if (st->q.ensure(sizeof(MatchQuery) * m) || st->topk.ensure(sizeof(unsigned long long) * TOPK * m) || st->n_static.ensure(sizeof(int) * m) ||
+        st->ev.ensure(sizeof(int32_t) * m))
+        return orbfe_fail(ctx, ORBFE_ERR_HIP, "matcher scratch allocation failed");
+    return ORBFE_OK;
+}
+
+// window query, resolution and the optional gather: what the two matchers share once their queries are written
+template <class Source>
+static int enqueue_window_resolve(orbfe_context *ctx, orbfe_match_device_state *st, const DevFrame &f, const Source &src, int nq, const uint8_t *d_qdesc, const int32_t *d_obs,
+                                  const float *d_angle, const uint8_t *d_blocked0, int points, int check_ori, float nnratio, const float *d_pos,
+                                  int32_t *d_cur_match, int32_t *d_nmatches, int32_t *d_status, uint8_t *d_has_point, float *d_Xw, hipStream_t s)
+{
+    const int blocks = std::max((nq + 3) / 4, (f.cap + 255) / 256); // one wave per query, and a thread per keypoint slot
+    hipLaunchKernelGGL(window_topk_kernel<Source>, dim3(blocks), dim3(256), 0, s, f, src, (MatchQuery *)st->q.p, d_qdesc, nq, d_blocked0,
+                       (unsigned long long *)st->topk.p, (int *)st->n_static.p, d_cur_match);
+    ResolveArgs a;
+    a.f = f; a.q = (const MatchQuery *)st->q.p; a.qdesc = d_qdesc; a.nq = nq;
+    a.topk = (const unsigned long long *)st->topk.p; a.n_static = (const int *)st->n_static.p;
+    a.obs = d_obs; a.angle = d_angle; a.blocked0 = d_blocked0;
+    a.points = points; a.check_ori = check_ori; a.nnratio = nnratio;
+    a.ev = (int32_t *)st->ev.p;
+    a.cur_match = d_cur_match; a.nmatches = d_nmatches; a.status = d_status;
+    hipLaunchKernelGGL(resolve_kernel, dim3(1), dim3(RESOLVE_THREADS), 0, s, a);
+    if (d_has_point || (d_Xw && d_pos))
+        hipLaunchKernelGGL(gather_kernel, dim3((f.cap + 255) / 256), dim3(256), 0, s, f, (const int32_t *)d_cur_match, d_pos, d_has_point, d_Xw);
+    DTRY(ctx, hipGetLastError());
+    return ORBFE_OK;
+}
+
+extern "C" int orbfe_enqueue_search_by_projection_last(orbfe_context *ctx, int slot, const float *bounds, const float *d_Tcw_cur, const float *d_Tcw_last,
+                                                       int n_last, const float *d_last_pos, const uint8_t *d_last_desc, const int32_t *d_last_valid,
+                                                       const int32_t *d_last_obs, const int32_t *d_last_octave, const float *d_last_angle,
+                                                       const uint8_t *d_cur_has_obs, float th, int mono, int check_ori, int32_t *d_cur_match,
+                                                       int32_t *d_nmatches, int32_t *d_status, uint8_t *d_has_point, float *d_Xw, void *stream)
+try {
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    ORBFE_ENTRY(ctx);
+    if (!bounds || !d_Tcw_cur || !d_Tcw_last || !d_cur_match || !d_nmatches || !d_status || n_last < 0 ||
+        (n_last > 0 && (!d_last_pos || !d_last_desc || !d_last_valid || !d_last_obs || !d_last_octave || !d_last_angle)))
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
+    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
+    orbfe_match_device_state *st = nullptr;
+    DevFrame f;
+    int rc = resident_grid(ctx, slot, bounds, !mono, s, st, f);
+    if (rc != ORBFE_OK) return rc;
+    rc = ensure_query_scratch(ctx, st, n_last);
+    if (rc != ORBFE_OK) return rc;
+    const LastSource src = {projection_of(ctx, bounds), d_Tcw_cur, d_Tcw_last, d_last_pos, d_last_valid, d_last_octave, th, mono};
+    return enqueue_window_resolve(ctx, st, f, src, n_last, d_last_desc, d_last_obs, d_last_angle, d_cur_has_obs, 0, check_ori != 0, 0.f, d_last_pos,
+                                  d_cur_match, d_nmatches, d_status, d_has_point, d_Xw, s);
+} ORBFE_CATCH(ctx)
+
+extern "C" int orbfe_enqueue_is_in_frustum(orbfe_context *ctx, const float *d_Tcw, const float *bounds, int n, const float *d_pos, const float *d_normal,
+                                           const float *d_max_distance, const float *d_min_distance, float viewing_cos_limit,
+                                           orbfe_track_point *d_out, void *stream)
+try {
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    ORBFE_ENTRY(ctx);
+    if (!d_Tcw || !bounds || n < 0 || (n > 0 && (!d_pos || !d_normal || !d_max_distance || !d_min_distance || !d_out)))
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
+    if (n == 0) return ORBFE_OK;
+    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
+    DTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    hipLaunchKernelGGL(frustum_kernel, dim3((n + 255) / 256), dim3(256), 0, s, projection_of(ctx, bounds), d_Tcw, n, d_pos, d_normal, d_max_distance,
+                       d_min_distance, viewing_cos_limit, d_out);
+    DTRY(ctx, hipGetLastError());
+    return ORBFE_OK;
+} ORBFE_CATCH(ctx)
+
+extern "C" int orbfe_enqueue_search_by_projection_points(orbfe_context *ctx, int slot, const float *bounds, int n_pts, const orbfe_track_point *d_pts,
+                                                         const uint8_t *d_pt_desc, const int32_t *d_pt_obs, const float *d_pt_pos,
+                                                         const uint8_t *d_cur_has_obs, float th, float nnratio, int32_t *d_cur_match,
+                                                         int32_t *d_nmatches, int32_t *d_status, uint8_t *d_has_point, float *d_Xw, void *stream)
+try {
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    ORBFE_ENTRY(ctx);
+    if (!bounds || !d_cur_match || !d_nmatches || !d_status || n_pts < 0 || (n_pts > 0 && (!d_pts || !d_pt_desc || !d_pt_obs)))
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
+    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
+    orbfe_match_device_state *st = nullptr;
+    DevFrame f;
+    int rc = resident_grid(ctx, slot, bounds, true, s, st, f);
+    if (rc != ORBFE_OK) return rc;
+    rc = ensure_query_scratch(ctx, st, n_pts);
+    if (rc != ORBFE_OK) return rc;
+    const PointsSource src = {projection_of(ctx, bounds), d_pts, th};
+    return enqueue_window_resolve(ctx, st, f, src, n_pts, d_pt_desc, d_pt_obs, nullptr, d_cur_has_obs, 1, 0, nnratio, d_pt_pos, d_cur_match, d_nmatches,
+                                  d_status, d_has_point, d_Xw, s);
+} ORBFE_CATCH(ctx)
+
+extern "C" int orbfe_device_keys_un(orbfe_context *ctx, int slot, const orbfe_keypoint **d_keys_un, void *stream)
+try {
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    ORBFE_ENTRY(ctx);
+    if (!d_keys_un) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
+    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
+    orbfe_match_device_state *st = nullptr;
+    const KeyPointPOD *keys = nullptr;
+    const int rc = resident_frame(ctx, slot, s, st, keys);
+    if (rc != ORBFE_OK) return rc;
+    DTRY(ctx, hipGetLastError());
+    *d_keys_un = (const orbfe_keypoint *)keys;
+    return ORBFE_OK;
+} ORBFE_CATCH(ctx)

@@ -5,6 +5,9 @@
 // Pure C++ (no HIP, no device types) on purpose: liborbfe.so's orbfe_match.hip includes it for the product path, and
 // tests/asan/resolve_harness.cpp compiles the very same text for the CPU with -fsanitize=address,undefined (GPU ASan does not
 // exist on this pool; the host logic is where the index arithmetic of the matchers lives).
+// The per-point arithmetic (one map point -> one window query, one isInFrustum record, rot_bin, three_maxima) is marked
+// ORBFE_RESOLVE_HD: empty in a plain C++ compile, host + device under hipcc, where orbfe_match_device.hip runs the same
+// statements one lane per map point (device code is compiled without FMA contraction and with IEEE divide / sqrt too).
 //
 // A candidate is one 64-bit key
 //      dist << 36 | ix << 30 | iy << 24 | idx << 8 | octave
@@ -23,6 +26,12 @@
 #include <vector>
 
 #include "../../include/orbfe.h"
+
+#ifdef __HIPCC__
+#define ORBFE_RESOLVE_HD __attribute__((host, device))
+#else
+#define ORBFE_RESOLVE_HD
+#endif
 
 namespace orbfe_resolve
 {
@@ -45,19 +54,19 @@ static inline Camera camera_of(const orbfe_params *P)
 // ---- projection arithmetic of the matchers: the reference's float expressions in its evaluation order (contract Q4: no FMA
 // contraction -- this header must be compiled with -ffp-contract=off) ----
 // OPENCV-4.5.5-SEMANTICS: cv::Mat R*x+t for 3x3 * 3x1 CV_32F (small-matrix gemm path)
-static inline void rt_apply(const float *T, const float *x, float *out)
+ORBFE_RESOLVE_HD static inline void rt_apply(const float *T, const float *x, float *out)
 {
     for (int i = 0; i < 3; i++) {
         const float t = (T[4 * i] * x[0] + T[4 * i + 1] * x[1]) + T[4 * i + 2] * x[2];
         out[i] = t + T[4 * i + 3];
     }
 }
-static inline void camera_center(const float *T, float *ow) // -Rcw.t()*tcw
+ORBFE_RESOLVE_HD static inline void camera_center(const float *T, float *ow) // -Rcw.t()*tcw
 {
     for (int i = 0; i < 3; i++) ow[i] = ((-T[i]) * T[3] + (-T[4 + i]) * T[7]) + (-T[8 + i]) * T[11];
 }
 // deterministic log for MapPoint::PredictScale (contract Q4)
-static inline float log_det(float xf)
+ORBFE_RESOLVE_HD static inline float log_det(float xf)
 {
     double x = (double)xf;
     int e;
@@ -71,7 +80,7 @@ static inline float log_det(float xf)
     const double LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10;
     return (float)((double)e * LN2_HI + (2.0 * s * p + (double)e * LN2_LO));
 }
-static inline int predict_scale(float max_distance, float current_dist, float log_sf, int n_levels) // src/MapPoint.cc:402-417
+ORBFE_RESOLVE_HD static inline int predict_scale(float max_distance, float current_dist, float log_sf, int n_levels) // src/MapPoint.cc:402-417
 {
     const float ratio = max_distance / current_dist;
     int n_scale = (int)ceilf(log_det(ratio) / log_sf);
@@ -79,65 +88,89 @@ static inline int predict_scale(float max_distance, float current_dist, float lo
     else if (n_scale >= n_levels) n_scale = n_levels - 1;
     return n_scale;
 }
-static inline float norm3(const float *po) { return (float)sqrt((double)po[0] * po[0] + (double)po[1] * po[1] + (double)po[2] * po[2]); }
+ORBFE_RESOLVE_HD static inline float norm3(const float *po) { return (float)sqrt((double)po[0] * po[0] + (double)po[1] * po[1] + (double)po[2] * po[2]); }
 
 // ---- one window query per map point: the part of each matcher's loop body that precedes GetFeaturesInArea ----
 static const MatchQuery NO_QUERY = {0, 0, 0, 0, -1, 0, 0, 0};
 
-// ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono), src/ORBmatcher.cc:1335-1390.  Returns -1 on a bad octave.
+// ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono), src/ORBmatcher.cc:1335-1390.
+// The motion test of :1347-1352 (the same for every point) ...
+ORBFE_RESOLVE_HD static inline void last_motion(const Camera &C, const float *Tcw_cur, const float *Tcw_last, int mono, bool &forward, bool &backward)
+{
+    float twc[3], tlc[3];
+    camera_center(Tcw_cur, twc);
+    rt_apply(Tcw_last, twc, tlc);
+    forward = tlc[2] > C.mb && !mono;
+    backward = -tlc[2] > C.mb && !mono;
+}
+// ... and the loop body for one map point of the last frame.  Q must hold NO_QUERY; returns -1 on a bad octave.
+ORBFE_RESOLVE_HD static inline int query_last_point(const Camera &C, const float *sf, int nlevels, float min_x, float max_x, float min_y, float max_y,
+                                                    const float *Tcw_cur, bool forward, bool backward, const float *pos, int valid, int octave, float th,
+                                                    MatchQuery &Q)
+{
+    if (!valid) return 0;
+    if (octave < 0 || octave >= nlevels) return -1;
+    float xc[3];
+    rt_apply(Tcw_cur, pos, xc);
+    const float invzc = (float)(1.0 / (double)xc[2]);
+    if (invzc < 0) return 0;
+    const float u = C.fx * xc[0] * invzc + C.cx;
+    const float v = C.fy * xc[1] * invzc + C.cy;
+    if (u < min_x || u > max_x) return 0;
+    if (v < min_y || v > max_y) return 0;
+    const int oct = octave;
+    const float radius = th * sf[oct];
+    Q.u = u; Q.v = v; Q.r = radius; Q.flags = 1 | 2;
+    Q.ur = u - C.bf * invzc; Q.ur_rad = radius;
+    if (forward) { Q.min_level = oct; Q.max_level = -1; }
+    else if (backward) { Q.min_level = 0; Q.max_level = oct; }
+    else { Q.min_level = oct - 1; Q.max_level = oct + 1; }
+    return 1;
+}
+// Returns -1 on a bad octave.
 static inline int build_queries_last(const Camera &C, const float *sf, int nlevels, float min_x, float max_x, float min_y, float max_y,
                                      const float *Tcw_cur, const float *Tcw_last, int n_last, const float *last_pos, const uint8_t *last_desc,
                                      const int32_t *last_valid, const int32_t *last_octave, float th, int mono, std::vector<MatchQuery> &q,
                                      std::vector<uint8_t> &qd)
 {
-    float twc[3], tlc[3];
-    camera_center(Tcw_cur, twc);
-    rt_apply(Tcw_last, twc, tlc);
-    const bool forward = tlc[2] > C.mb && !mono, backward = -tlc[2] > C.mb && !mono;
+    bool forward, backward;
+    last_motion(C, Tcw_cur, Tcw_last, mono, forward, backward);
     q.assign(n_last > 0 ? n_last : 0, NO_QUERY);
     qd.assign((size_t)32 * (n_last > 0 ? n_last : 1), 0);
     for (int i = 0; i < n_last; i++) {
-        MatchQuery &Q = q[i];
-        if (!last_valid[i]) continue;
-        if (last_octave[i] < 0 || last_octave[i] >= nlevels) return -1;
-        float xc[3];
-        rt_apply(Tcw_cur, last_pos + 3 * i, xc);
-        const float invzc = (float)(1.0 / (double)xc[2]);
-        if (invzc < 0) continue;
-        const float u = C.fx * xc[0] * invzc + C.cx;
-        const float v = C.fy * xc[1] * invzc + C.cy;
-        if (u < min_x || u > max_x) continue;
-        if (v < min_y || v > max_y) continue;
-        const int oct = last_octave[i];
-        const float radius = th * sf[oct];
-        Q.u = u; Q.v = v; Q.r = radius; Q.flags = 1 | 2;
-        Q.ur = u - C.bf * invzc; Q.ur_rad = radius;
-        if (forward) { Q.min_level = oct; Q.max_level = -1; }
-        else if (backward) { Q.min_level = 0; Q.max_level = oct; }
-        else { Q.min_level = oct - 1; Q.max_level = oct + 1; }
-        memcpy(&qd[(size_t)32 * i], last_desc + (size_t)32 * i, 32);
+        const int rc = query_last_point(C, sf, nlevels, min_x, max_x, min_y, max_y, Tcw_cur, forward, backward, last_pos + 3 * i, last_valid[i],
+                                        last_octave[i], th, q[i]);
+        if (rc < 0) return -1;
+        if (rc > 0) memcpy(&qd[(size_t)32 * i], last_desc + (size_t)32 * i, 32);
     }
     return 0;
 }
 
-// ORBmatcher::SearchByProjection(F, vpMapPoints, th), src/ORBmatcher.cc:49-70.  Returns -1 on a bad predicted level.
+// ORBmatcher::SearchByProjection(F, vpMapPoints, th), src/ORBmatcher.cc:49-70: the loop body for one map point.
+// Q must hold NO_QUERY; returns -1 on a bad predicted level.
+ORBFE_RESOLVE_HD static inline int query_track_point(const float *sf, int nlevels, const orbfe_track_point &pt, float th, MatchQuery &Q)
+{
+    const bool b_factor = th != 1.0;
+    if (!pt.in_view) return 0;
+    const int lvl = pt.level;
+    if (lvl < 0 || lvl >= nlevels) return -1;
+    float r = pt.view_cos > 0.998 ? 2.5f : 4.0f; // RadiusByViewingCos, :129-135
+    if (b_factor) r *= th;
+    Q.u = pt.proj_x; Q.v = pt.proj_y; Q.r = r * sf[lvl];
+    Q.min_level = lvl - 1; Q.max_level = lvl; Q.flags = 1 | 2;
+    Q.ur = pt.proj_xr; Q.ur_rad = r * sf[lvl];
+    return 1;
+}
+// Returns -1 on a bad predicted level.
 static inline int build_queries_points(const float *sf, int nlevels, int n_pts, const orbfe_track_point *pts, const uint8_t *pt_desc, float th,
                                        std::vector<MatchQuery> &q, std::vector<uint8_t> &qd)
 {
-    const bool b_factor = th != 1.0;
     q.assign(n_pts > 0 ? n_pts : 0, NO_QUERY);
     qd.assign((size_t)32 * (n_pts > 0 ? n_pts : 1), 0);
     for (int i = 0; i < n_pts; i++) {
-        MatchQuery &Q = q[i];
-        if (!pts[i].in_view) continue;
-        const int lvl = pts[i].level;
-        if (lvl < 0 || lvl >= nlevels) return -1;
-        float r = pts[i].view_cos > 0.998 ? 2.5f : 4.0f; // RadiusByViewingCos, :129-135
-        if (b_factor) r *= th;
-        Q.u = pts[i].proj_x; Q.v = pts[i].proj_y; Q.r = r * sf[lvl];
-        Q.min_level = lvl - 1; Q.max_level = lvl; Q.flags = 1 | 2;
-        Q.ur = pts[i].proj_xr; Q.ur_rad = r * sf[lvl];
-        memcpy(&qd[(size_t)32 * i], pt_desc + (size_t)32 * i, 32);
+        const int rc = query_track_point(sf, nlevels, pts[i], th, q[i]);
+        if (rc < 0) return -1;
+        if (rc > 0) memcpy(&qd[(size_t)32 * i], pt_desc + (size_t)32 * i, 32);
     }
     return 0;
 }
@@ -188,51 +221,57 @@ static inline void build_queries_initialization(int n1, const orbfe_keypoint *ke
     }
 }
 
-// Frame::isInFrustum, src/Frame.cc:256-315, for n map points
+// Frame::isInFrustum, src/Frame.cc:256-315, for one map point (ow = camera_center(Tcw))
+ORBFE_RESOLVE_HD static inline void frustum_point(const Camera &C, int nlevels, float log_sf, const float *Tcw, const float *ow, float min_x, float max_x,
+                                                  float min_y, float max_y, const float *pos, const float *normal, float max_distance, float min_distance,
+                                                  float viewing_cos_limit, orbfe_track_point &o)
+{
+    o.in_view = 0; o.proj_x = o.proj_y = o.proj_xr = 0.f; o.level = 0; o.view_cos = 0.f;
+    float pc[3];
+    rt_apply(Tcw, pos, pc);
+    if (pc[2] < 0.0f) return;
+    const float invz = 1.0f / pc[2];
+    const float u = C.fx * pc[0] * invz + C.cx;
+    const float v = C.fy * pc[1] * invz + C.cy;
+    if (u < min_x || u > max_x) return;
+    if (v < min_y || v > max_y) return;
+    float po[3];
+    for (int k = 0; k < 3; k++) po[k] = pos[k] - ow[k];
+    const float dist = norm3(po);
+    if (dist < 0.8f * min_distance || dist > 1.2f * max_distance) return;
+    const double dot = (double)po[0] * normal[0] + (double)po[1] * normal[1] + (double)po[2] * normal[2];
+    const float view_cos = (float)(dot / (double)dist);
+    if (view_cos < viewing_cos_limit) return;
+    o.in_view = 1;
+    o.proj_x = u; o.proj_xr = u - C.bf * invz; o.proj_y = v;
+    o.level = predict_scale(max_distance, dist, log_sf, nlevels);
+    o.view_cos = view_cos;
+}
+// ... and for n of them
 static inline void is_in_frustum(const Camera &C, int nlevels, float log_sf, const float *Tcw, float min_x, float max_x, float min_y, float max_y, int n,
                                  const float *pos, const float *normal, const float *max_distance, const float *min_distance,
                                  float viewing_cos_limit, orbfe_track_point *out)
 {
     float ow[3];
     camera_center(Tcw, ow);
-    for (int i = 0; i < n; i++) {
-        orbfe_track_point &o = out[i];
-        o.in_view = 0; o.proj_x = o.proj_y = o.proj_xr = 0.f; o.level = 0; o.view_cos = 0.f;
-        float pc[3];
-        rt_apply(Tcw, pos + 3 * i, pc);
-        if (pc[2] < 0.0f) continue;
-        const float invz = 1.0f / pc[2];
-        const float u = C.fx * pc[0] * invz + C.cx;
-        const float v = C.fy * pc[1] * invz + C.cy;
-        if (u < min_x || u > max_x) continue;
-        if (v < min_y || v > max_y) continue;
-        float po[3];
-        for (int k = 0; k < 3; k++) po[k] = pos[3 * i + k] - ow[k];
-        const float dist = norm3(po);
-        if (dist < 0.8f * min_distance[i] || dist > 1.2f * max_distance[i]) continue;
-        const double dot = (double)po[0] * normal[3 * i] + (double)po[1] * normal[3 * i + 1] + (double)po[2] * normal[3 * i + 2];
-        const float view_cos = (float)(dot / (double)dist);
-        if (view_cos < viewing_cos_limit) continue;
-        o.in_view = 1;
-        o.proj_x = u; o.proj_xr = u - C.bf * invz; o.proj_y = v;
-        o.level = predict_scale(max_distance[i], dist, log_sf, nlevels);
-        o.view_cos = view_cos;
-    }
+    for (int i = 0; i < n; i++)
+        frustum_point(C, nlevels, log_sf, Tcw, ow, min_x, max_x, min_y, max_y, pos + 3 * i, normal + 3 * i, max_distance[i], min_distance[i],
+                      viewing_cos_limit, out[i]);
 }
 
 enum { HISTO_LENGTH = 30, TH_LOW = 50, TH_HIGH = 100, TOPK = 4 };
 typedef unsigned long long ckey_t;
 static const ckey_t NO_KEY = ~0ull;
 
-static inline int key_dist(ckey_t k) { return (int)(k >> 36); }
-static inline int key_idx(ckey_t k) { return (int)((k >> 8) & 0xffffu); }
-static inline int key_level(ckey_t k) { return (int)(k & 0xffu); }
+ORBFE_RESOLVE_HD static inline int key_dist(ckey_t k) { return (int)(k >> 36); }
+ORBFE_RESOLVE_HD static inline int key_idx(ckey_t k) { return (int)((k >> 8) & 0xffffu); }
+ORBFE_RESOLVE_HD static inline int key_level(ckey_t k) { return (int)(k & 0xffu); }
 
 // ORBmatcher::ComputeThreeMaxima, src/ORBmatcher.cc:1597-1638, on the bin sizes.  The reference keeps a running top three with
 // strict comparisons, i.e. the three largest NON-EMPTY bins in the order (size descending, index ascending); written here as
 // three selections of the largest remaining (size, -index) key instead of the reference's shifting if-chain (the oracle and
 // oracle/literal_matchers.py keep that form, so the two formulations check each other).
-static inline void three_maxima(const int32_t *sizes, int L, int *ind1, int *ind2, int *ind3)
+ORBFE_RESOLVE_HD static inline void three_maxima(const int32_t *sizes, int L, int *ind1, int *ind2, int *ind3)
 {
     int ind[3] = {-1, -1, -1};
     int32_t val[3] = {0, 0, 0};
@@ -250,7 +289,7 @@ static inline void three_maxima(const int32_t *sizes, int L, int *ind1, int *ind
     *ind1 = ind[0]; *ind2 = ind[1]; *ind3 = ind[2];
 }
 
-static inline int rot_bin(float a1, float a2) // Q8: 30 slots, bin = round(rot / 30): the reference's three float statements (:1438-1443), the same in any restatement
+ORBFE_RESOLVE_HD static inline int rot_bin(float a1, float a2) // Q8: 30 slots, bin = round(rot / 30): the reference's three float statements (:1438-1443), the same in any restatement
 {
     const float factor = 1.0f / HISTO_LENGTH;
     float rot = a1 - a2;

@@ -5,6 +5,12 @@ beside the CPU oracle on the same inputs (1 thread).  Prints one JSON object; ru
     python3 tools/bench_matchers.py > gpurun_out/matchers.json
 The scenario is the keypoint-level scene of tests/test_matchers.py scaled to 2000 last-frame points, and the
 BoW case of tests/test_bow.py (k=10, L=3 vocabulary, 1500 / 1600 descriptors).
+    python3 tools/bench_matchers.py --resident-only
+runs only the rows on the resident scene (a real extracted frame): the synchronous device-resident call, and -- when the
+library has them -- the asynchronous matcher (orbfe_enqueue_search_by_projection_last) as wall time of enqueue + one stream
+synchronise and as GPU time between two events, and match -> pose as two host calls against the one-stream chain.  The
+asynchronous rows are skipped on a library that does not export the entry points, so the same script measures an older build
+(profiles/matchers_device_resolve.json).
 """
 import json
 import os
@@ -27,8 +33,104 @@ def timeit(fn, reps):
     return (time.perf_counter() - t0) / reps * 1e3
 
 
+def resident_async_rows(ctx2, out, fs, fb, fk, fur, v_dev, args_sync):
+    """Rows (a), (b), (c) of the asynchronous matcher on the resident scene; arguments prepared once, C ABI called directly."""
+    import ctypes as C
+    import torch
+    L = ctx2.L
+    if not hasattr(L, "orbfe_enqueue_search_by_projection_last"):
+        out["async"] = "not exported by this library"
+        return
+    dev = torch.device("cuda:0")
+    up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, t)).to(dev)
+    T4 = np.eye(4, dtype=np.float32); T4[:3] = fs["T_cur"]
+    d = dict(tc=up(T4, np.float32), tl=up(fs["T_last"], np.float32), pos=up(fs["pos"], np.float32), desc=up(fs["desc"], np.uint8),
+             val=up(fs["valid"], np.int32), obs=up(fs["obs"], np.int32), oct=up(fs["octave"], np.int32), ang=up(fs["angle"], np.float32),
+             has=up(fs["has"], np.uint8))
+    cap = ctx2.capacity
+    o_match = torch.full((cap,), -1, dtype=torch.int32, device=dev); o_nm = torch.zeros(1, dtype=torch.int32, device=dev)
+    o_st = torch.zeros(1, dtype=torch.int32, device=dev); o_has = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    o_xw = torch.zeros((cap, 3), dtype=torch.float32, device=dev)
+    st = torch.cuda.Stream()
+    vp = C.c_void_p
+    bounds = (C.c_float * 4)(*fb)
+    sp = vp(st.cuda_stream)
+
+    def margs(pose):
+        return (ctx2.h, 0, bounds, vp(d["tc"].data_ptr()), vp(d["tl"].data_ptr()), len(fs["valid"]), vp(d["pos"].data_ptr()), vp(d["desc"].data_ptr()),
+                vp(d["val"].data_ptr()), vp(d["obs"].data_ptr()), vp(d["oct"].data_ptr()), vp(d["ang"].data_ptr()), vp(d["has"].data_ptr()),
+                C.c_float(7.0), 0, 1, vp(o_match.data_ptr()), vp(o_nm.data_ptr()), vp(o_st.data_ptr()),
+                vp(o_has.data_ptr()) if pose else None, vp(o_xw.data_ptr()) if pose else None, sp)
+    a_plain, a_pose = margs(False), margs(True)
+    enq, sync = L.orbfe_enqueue_search_by_projection_last, L.orbfe_synchronize
+    torch.cuda.synchronize()
+
+    def async_call():
+        assert enq(*a_plain) == 0
+        assert sync(ctx2.h, sp) == 0
+
+    ref_m, ref_n = ctx2.search_by_projection_last(v_dev, fs["T_cur"], fs["T_last"], fs["pos"], fs["desc"], fs["valid"], fs["obs"], fs["octave"],
+                                                  fs["angle"], fs["has"], 7.0, False, True)
+    async_call()
+    assert np.array_equal(o_match.cpu().numpy()[: v_dev.n], ref_m) and int(o_nm.item()) == ref_n and int(o_st.item()) == 0
+    rows = out["rows"]
+    rows["(a) asynchronous matcher, enqueue + one stream synchronise, C ABI called directly"] = {"gpu_ms": round(timeit(async_call, 200), 4)}
+    # (b) GPU time of the matcher's kernels: 200 calls queued between two events (no host wait in between)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    async_call()
+    e0.record(st)
+    for _ in range(200):
+        assert enq(*a_plain) == 0
+    e1.record(st)
+    st.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(200):
+        assert enq(*a_plain) == 0
+    t_enq = (time.perf_counter() - t0) / 200 * 1e3
+    st.synchronize()
+    rows["(b) asynchronous matcher, GPU time of its kernels between two events (200 calls queued back to back)"] = {
+        "gpu_ms": round(e0.elapsed_time(e1) / 200, 4), "host_enqueue_ms": round(t_enq, 4)}
+    # (c) match -> pose: two host calls against the one-stream chain
+    nk = v_dev.n
+    from orbslam2_amd import api
+    k_host = np.ascontiguousarray(fk, api.KP_DTYPE); ur_host = np.ascontiguousarray(fur, np.float32)
+    P = lambda a: a.ctypes.data_as(C.c_void_p)
+    a_out = args_sync["out"]; hp = np.zeros(nk, np.uint8); xw = np.zeros((nk, 3), np.float32); outl = np.zeros(nk, np.uint8)
+    Th = T4.copy(); ninl = C.c_int()  # both chains optimise their pose in place: after the first repeat they start from the converged pose
+    pos_host = np.ascontiguousarray(fs["pos"], np.float32)
+
+    def host_chain():
+        assert L.orbfe_search_by_projection_last(*args_sync["args"]) == 0
+        m = a_out[:nk]
+        np.greater_equal(m, 0, out=hp.view(bool))
+        xw[:] = pos_host[np.maximum(m, 0)]
+        assert L.orbfe_pose_optimization(ctx2.h, P(Th), nk, P(k_host), P(ur_host), P(hp), P(xw), P(outl), C.byref(ninl)) == 0
+
+    bufs = [C.c_void_p() for _ in range(5)]
+    assert L.orbfe_device_buffers(ctx2.h, *[C.byref(x) for x in bufs]) == 0
+    d_keys = C.c_void_p()
+    d_off = torch.tensor([0, nk], dtype=torch.int32, device=dev)
+    d_T = torch.from_numpy(T4).to(dev); d_outl = torch.zeros(cap, dtype=torch.uint8, device=dev); d_ninl = torch.zeros(1, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+
+    def device_chain():
+        assert enq(*a_pose) == 0
+        assert L.orbfe_device_keys_un(ctx2.h, 0, C.byref(d_keys), sp) == 0
+        assert L.orbfe_enqueue_pose_optimization(ctx2.h, 1, vp(d_off.data_ptr()), d_keys, bufs[3], vp(o_has.data_ptr()), vp(o_xw.data_ptr()),
+                                                 vp(d_T.data_ptr()), vp(d_outl.data_ptr()), vp(d_ninl.data_ptr()), cap, sp) == 0
+        assert sync(ctx2.h, sp) == 0
+
+    host_chain(); device_chain()
+    assert int(d_ninl.item()) == ninl.value
+    rows["(c) match -> pose, two host calls (orbfe_search_by_projection_last + orbfe_pose_optimization)"] = {"gpu_ms": round(timeit(host_chain, 100), 4)}
+    rows["(c) match -> pose, one-stream chain (enqueue matcher + device_keys_un + enqueue pose + one synchronise)"] = {
+        "gpu_ms": round(timeit(device_chain, 100), 4),
+        "note": "the matcher reads the same fixed pose in both chains; %d inliers" % ninl.value}
+
+
 def main():
     from orbslam2_amd import api
+    resident_only = "--resident-only" in sys.argv[1:]
     ctx = api.Context(width=TM.W, height=TM.H, fx=TM.FX, fy=TM.FY, cx=TM.CX, cy=TM.CY, bf=TM.BF)
     s = TM._scene(3, n_last=2000, n_distract=700)
     g = O.Grid(s["k"], *s["bounds"])
@@ -39,11 +141,12 @@ def main():
         g_ms, c_ms = timeit(gpu_fn, reps), timeit(cpu_fn, max(3, reps // 4))
         out["rows"][name] = {"gpu_ms": round(g_ms, 4), "oracle_1thread_ms": round(c_ms, 4)}
 
-    row("SearchByProjection(Frame, LastFrame) [row 14]",
-        lambda: ctx.search_by_projection_last(view, s["T_cur"], s["T_last"], s["pos"], s["desc_last"], s["valid"], s["obs"], s["octave"],
-                                              s["angle"], s["cur_has_obs"], 7.0, False, True),
-        lambda: O.search_by_projection_last(g, s["ur"], s["d"], s["sf"], TM.CAM, s["T_cur"], s["T_last"], s["pos"], s["desc_last"],
-                                            s["valid"], s["obs"], s["octave"], s["angle"], s["cur_has_obs"], 7.0, False, True))
+    if not resident_only:
+        row("SearchByProjection(Frame, LastFrame) [row 14]",
+            lambda: ctx.search_by_projection_last(view, s["T_cur"], s["T_last"], s["pos"], s["desc_last"], s["valid"], s["obs"], s["octave"],
+                                                  s["angle"], s["cur_has_obs"], 7.0, False, True),
+            lambda: O.search_by_projection_last(g, s["ur"], s["d"], s["sf"], TM.CAM, s["T_cur"], s["T_last"], s["pos"], s["desc_last"],
+                                                s["valid"], s["obs"], s["octave"], s["angle"], s["cur_has_obs"], 7.0, False, True))
     # the same matcher on a REAL extracted frame: upload path against the device-resident frame (orbfe_frame_view.device_slot_plus1:
     # keypoints / descriptors read where the extraction left them in HBM, grid built once per frame)
     from orbslam2_amd import synth
@@ -88,6 +191,12 @@ def main():
     out["rows"]["SearchByProjection(Frame, LastFrame), device-resident, C ABI called directly [row 14]"] = {
         "gpu_ms": round(timeit(raw_call, 200), 4),
         "note": "inside the call (ORBFE_HOST_TRACE=1): projection of the points 0.006, upload + kernel + download 0.062, replay 0.007 ms"}
+    resident_async_rows(ctx2, out, fs, fb, fk, fur, v_dev, {"args": args, "out": a_out})
+    if resident_only:
+        out["build_id"] = api.build_id()
+        print(json.dumps(out, indent=1))
+        ctx.close(); ctx2.close()
+        return
     rng = np.random.default_rng(5)
     qs = [(float(rng.uniform(0, TM.W)), float(rng.uniform(0, TM.H)), float(rng.uniform(5, 60))) for _ in range(64)]
     row("GetFeaturesInArea x64 [rows 13]",
