@@ -580,6 +580,35 @@ int orbfe_enqueue_search_by_projection_points(orbfe_context *ctx, int slot, cons
 /* mvKeysUn of image slot `slot` as the device-side matchers see it: the extraction's keypoint array, or, with distortion
  * active, the undistorted copy (enqueued on `stream` if this frame has none yet).  For orbfe_enqueue_pose_optimization. */
 int orbfe_device_keys_un(orbfe_context *ctx, int slot, const orbfe_keypoint **d_keys_un, void *stream);
+/* ---- bag of words on device-resident data (orbfe_bow_device.hip): TrackReferenceKeyFrame (src/Tracking.cc:858-875) and
+ * Relocalization (:1445-1476) without a host round trip.  The contract of the enqueue matchers above holds for both calls.
+ *
+ * Frame::ComputeFboW (src/Frame.cc:395-400 = Vocabulary::transform, Thirdparty/fbow/src/fbow.h:400-444) for image slot `slot` of
+ * the latest extraction call: descriptors and the keypoint count are read where the extraction left them; `level` as for
+ * orbfe_bow_transform.  Outputs are device arrays of orbfe_keypoint_capacity() entries (d_node_off: one more):
+ *   d_word_id, d_weight, d_node_id   per feature, each may be NULL
+ *   d_words, d_word_w, d_n_words[1]  fBow: ascending word ids, weights summed in feature order
+ *   d_nodes, d_node_off, d_node_feat, d_n_nodes[1]  fBow2 as orbfe_bow_maps writes it
+ *   d_status[1]  0, or ORBFE_ERR_INVALID for a slot without keypoints (fbow's "No input data"; both counts are then 0)
+ * Entries at or beyond the counts are left untouched.  ORBFE_ERR_INVALID from the call itself when no vocabulary is loaded. */
+int orbfe_enqueue_compute_bow(orbfe_context *ctx, int slot, int level, uint32_t *d_word_id, float *d_weight, uint32_t *d_node_id,
+        uint32_t *d_words, float *d_word_w, int32_t *d_n_words,
+        uint32_t *d_nodes, int32_t *d_node_off, int32_t *d_node_feat, int32_t *d_n_nodes, int32_t *d_status, void *stream);
+/* ORBmatcher::SearchByFboW(KeyFrame*, Frame&, vpMapPointMatches) (src/ORBmatcher.cc:157-283), the frame being image slot `slot`:
+ * its descriptors, angles (mvKeys[].angle) and keypoint count are read from the slot, its feature vector (d_f_nodes, d_f_off,
+ * d_f_feat, the DEVICE count d_f_n_nodes) as orbfe_enqueue_compute_bow wrote it.  The keyframe's arrays are device copies of what
+ * orbfe_search_by_bow takes; d_kf_nodes must ascend strictly and d_kf_off[kf_nnodes] may not exceed n_kf (a keypoint lies in one
+ * node).  d_kf_pos (n_kf x 3, the map points' GetWorldPos) may be NULL and is only read for d_Xw.
+ * Outputs (device): d_f_match[capacity] (KF keypoint or -1; entries >= the slot's count are left untouched), d_nmatches[1],
+ * d_status[1]: 0, or ORBFE_ERR_INVALID for a slot without keypoints (nothing else is written but d_nmatches = 0), for a feature
+ * index or CSR offset out of range or keyframe nodes out of order (that entry / node is skipped, the other outputs are not
+ * meaningful).  Optional d_has_point[capacity], d_Xw[capacity][3] as for the matchers above. */
+int orbfe_enqueue_search_by_bow(orbfe_context *ctx, int slot,
+        const uint32_t *d_kf_nodes, const int32_t *d_kf_off, const int32_t *d_kf_feat, int kf_nnodes,
+        const int32_t *d_kf_valid, const uint8_t *d_kf_desc, const float *d_kf_angle, int n_kf, const float *d_kf_pos /* may be NULL */,
+        const uint32_t *d_f_nodes, const int32_t *d_f_off, const int32_t *d_f_feat, const int32_t *d_f_n_nodes,
+        float nnratio, int check_ori, int32_t *d_f_match, int32_t *d_nmatches, int32_t *d_status,
+        uint8_t *d_has_point, float *d_Xw, void *stream);
 /* KeyFrameDatabase::DetectLoopCandidates(KeyFrame *pKF, float minScore) (src/KeyFrameDatabase.cc:73-194; LoopClosing::DetectLoop,
  * src/LoopClosing.cc:131).  connected[k] != 0 marks the keyframes of pKF->GetConnectedKeyFrames() (may be NULL: none); covisibility
  * lists as for the relocalisation query.  Stateless: mLoopScore is only read for keyframes scored by the same call. */

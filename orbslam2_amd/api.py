@@ -37,6 +37,7 @@ EXPORTS = [
     "orbfe_get_camera", "orbfe_assign_features_to_grid", "orbfe_set_profiling_interval", "orbfe_stereo_batch", "orbfe_device_count", "orbfe_vocab_bytes",
     "orbfe_get_packed_layout", "orbfe_fetch_batch_packed", "orbfe_expand_packed", "orbfe_enqueue_rgbd", "orbfe_stereo_batch_packed",
     "orbfe_enqueue_search_by_projection_last", "orbfe_enqueue_is_in_frustum", "orbfe_enqueue_search_by_projection_points", "orbfe_device_keys_un",
+    "orbfe_enqueue_compute_bow", "orbfe_enqueue_search_by_bow",
 ]
 NUM_STAGES = 8
 STAGE_NAMES = ["ingest", "pyramid", "blur", "fast", "octree", "describe", "stereo_match", "stereo_median"]  # orbfe_stage_name()
@@ -199,6 +200,10 @@ def load():
     L.orbfe_enqueue_search_by_projection_points.argtypes = [vp, C.c_int, vp, C.c_int] + [vp] * 5 + [C.c_float, C.c_float] + [vp] * 6
     L.orbfe_device_keys_un.restype = C.c_int
     L.orbfe_device_keys_un.argtypes = [vp, C.c_int, C.POINTER(vp), vp]
+    L.orbfe_enqueue_compute_bow.restype = C.c_int
+    L.orbfe_enqueue_compute_bow.argtypes = [vp, C.c_int, C.c_int] + [vp] * 12
+    L.orbfe_enqueue_search_by_bow.restype = C.c_int
+    L.orbfe_enqueue_search_by_bow.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp] + [vp] * 4 + [C.c_float, C.c_int] + [vp] * 6
     _lib = L
     return L
 
@@ -559,6 +564,25 @@ class Context:
         out = C.c_void_p()
         self._check(self.L.orbfe_device_keys_un(self.h, slot, C.byref(out), C.c_void_p(stream or None)))
         return out.value or 0
+
+    def enqueue_compute_bow(self, slot, level, d_words, d_word_w, d_n_words, d_nodes, d_node_off, d_node_feat, d_n_nodes, d_status,
+                            d_word_id=0, d_weight=0, d_node_id=0, stream=0):
+        """Frame::ComputeFboW of image slot `slot` (needs bow.vocab_load): fBow and fBow2 as device arrays of `capacity` entries
+        (d_node_off: capacity + 1), the counts and the status as one int32 each; the per-feature arrays are optional."""
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_compute_bow(
+            self.h, slot, level, v(d_word_id or None), v(d_weight or None), v(d_node_id or None), v(d_words), v(d_word_w), v(d_n_words),
+            v(d_nodes), v(d_node_off), v(d_node_feat), v(d_n_nodes), v(d_status), v(stream or None)))
+
+    def enqueue_search_by_bow(self, slot, d_kf_nodes, d_kf_off, d_kf_feat, kf_nnodes, d_kf_valid, d_kf_desc, d_kf_angle, n_kf,
+                              d_f_nodes, d_f_off, d_f_feat, d_f_n_nodes, nnratio, check_ori, d_f_match, d_nmatches, d_status,
+                              d_kf_pos=0, d_has_point=0, d_Xw=0, stream=0):
+        """ORBmatcher::SearchByFboW(KeyFrame*, Frame&) against image slot `slot`, whose feature vector enqueue_compute_bow wrote."""
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_search_by_bow(
+            self.h, slot, v(d_kf_nodes or None), v(d_kf_off or None), v(d_kf_feat or None), kf_nnodes, v(d_kf_valid or None), v(d_kf_desc or None),
+            v(d_kf_angle or None), n_kf, v(d_kf_pos or None), v(d_f_nodes), v(d_f_off), v(d_f_feat), v(d_f_n_nodes), nnratio, int(check_ori),
+            v(d_f_match), v(d_nmatches), v(d_status), v(d_has_point or None), v(d_Xw or None), v(stream or None)))
 
     def search_by_projection_kf(self, view, Tcw_cur, kf_pos, kf_desc, kf_valid, kf_angle, kf_max_distance, kf_min_distance, cur_has_point,
                                 th, orb_dist, check_ori):

@@ -1,0 +1,474 @@
+// orbfe_bow_device.hip -- Frame::ComputeFboW (src/Frame.cc:395-400; fbow transform, Thirdparty/fbow/src/fbow.h:400-444) and
+// ORBmatcher::SearchByFboW(KeyFrame*, Frame&) (src/ORBmatcher.cc:157-283) on a device-resident frame, asynchronous on the
+// caller's stream: device pointers in, results in HBM, no host wait.  orbfe_bow.hip is the synchronous form (descriptors
+// uploaded again, maps and greedy resolve on the host) and the second implementation this one is tested against.
+//
+// orbfe_enqueue_compute_bow, three launches sized by the keypoint capacity (the slot's count is only known on the device):
+//   bow_descend_resident_kernel  bow_walk per descriptor; word id, node id and weight of feature f go to entry f of HBM scratch
+//   bow_rank_kernel              sorts the keys (id << 32 | feature) of both maps by rank: a key's place is the number of smaller
+//                                keys.  The feature half of key f is f, its position, so only the 32-bit ids are staged in LDS
+//                                (tiles of BOW_RANK_TILE) and compared.  Keys are unique, so the ranks are a permutation and the
+//                                features inside a word / node ascend.  One tile covers a usual frame; above that the kernel walks
+//                                the id array in HBM scratch tile by tile, up to the capacity.
+//   bow_segments_kernel          one workgroup per map: segment heads -> scan -> CSR.  A word's weights are added by ONE thread in
+//                                feature order (fbow.h:431): a tree sum rounds differently.
+// orbfe_enqueue_search_by_bow, three launches:
+//   bow_match_init_kernel        f_match = -1 below the slot's count, d_status
+//   bow_node_match_kernel        one wave per keyframe node.  A frame keypoint lies in one node of the frame's feature vector and
+//                                the greedy rule of :203-229 only skips frame keypoints matched earlier, so it is sequential only
+//                                inside a node: the wave takes the node's KF features in order, its lanes stride over the node's
+//                                frame features, and the "already matched" flags of a lane's features stay in that lane's registers.
+//   bow_match_tail_kernel        the rotation histogram needs every node: bins, ComputeThreeMaxima, losers removed, the count,
+//                                and the optional has_point / Xw for orbfe_enqueue_pose_optimization
+#include "../../include/orbfe.h"
+#include "orbfe_device.h"
+#include "orbfe_host.h"
+#include "orbfe_bow_vocab.h"
+#include "orbfe_match_resolve.h"
+
+#include <cmath>
+
+using orbfe_resolve::HISTO_LENGTH;
+using orbfe_resolve::TH_LOW;
+
+#define BOW_RANK_TILE 4096 // ids per LDS tile of bow_rank_kernel: 16 KB
+#define BOW_SEG_LDS 4096   // entries per map that bow_segments_kernel stages in LDS: 32 KB
+#define BOW_REG_CHUNKS 2   // a lane keeps the descriptors of its first two features of a node in registers (nodes up to 128 features)
+#define BOW_FLAG_CHUNKS 64 // a lane keeps the flags of its first 64 features of a node in one 64-bit register (nodes up to 4096 features)
+
+#define WTRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return orbfe_fail(ctx, ORBFE_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
+
+typedef unsigned long long u64;
+
+__device__ __forceinline__ int slot_count(const int *n_ptr, int cap)
+{
+    const int n = *n_ptr;
+    return n < 0 ? 0 : (n > cap ? cap : n);
+}
+
+// ---------------------------------------------------------------------------------------------
+// ComputeFboW
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void bow_descend_resident_kernel(BowTree t, int store_level, const uint8_t *__restrict__ desc, const int *__restrict__ n_ptr, int cap,
+                                                                   uint32_t *__restrict__ word_id, float *__restrict__ weight, uint32_t *__restrict__ node_id,
+                                                                   uint32_t *__restrict__ id_w, uint32_t *__restrict__ id_n, float *__restrict__ wt, int32_t *__restrict__ status)
+{
+    const int n = slot_count(n_ptr, cap);
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f == 0) *status = n > 0 ? ORBFE_OK : ORBFE_ERR_INVALID; // fbow: "Vocabulary::transform No input data"
+    if (f >= n) return;
+    uint32_t wid, nid;
+    float w;
+    bow_walk(t, store_level, desc + (size_t)32 * f, wid, w, nid);
+    if (word_id) word_id[f] = wid;
+    if (weight) weight[f] = w;
+    if (node_id) node_id[f] = nid;
+    id_w[f] = wid; id_n[f] = nid; wt[f] = w;
+}
+
+// How many of 16 ids are below `mid` (LE: or equal to it)
+template <bool LE>
+__device__ __forceinline__ int count_below(const uint4 *__restrict__ v4, uint32_t mid)
+{
+    int c = 0;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const uint4 v = v4[u];
+        c += LE ? (int)(v.x <= mid) + (int)(v.y <= mid) + (int)(v.z <= mid) + (int)(v.w <= mid)
+                : (int)(v.x < mid) + (int)(v.y < mid) + (int)(v.z < mid) + (int)(v.w < mid);
+    }
+    return c;
+}
+
+// blockIdx.y = 0: the word keys, 1: the node keys (ids / sorted_id / sorted_pay hold both maps, `cap` entries apart).  A
+// workgroup ranks 64 keys, its four waves each against a quarter of every tile:
+//      key j < key i  <=>  id_j <= id_i for j < i, id_j < id_i for j > i.
+// What travels with a key to its place: a word's weight, a node's feature index.
+__global__ __launch_bounds__(256) void bow_rank_kernel(const uint32_t *__restrict__ ids, const float *__restrict__ wt, uint32_t *__restrict__ sorted_id,
+                                                       uint32_t *__restrict__ sorted_pay, const int *__restrict__ n_ptr, int cap)
+{
+    __shared__ uint4 s_id[BOW_RANK_TILE / 4];
+    __shared__ int s_part[4][64];
+    const int n = slot_count(n_ptr, cap);
+    if ((int)blockIdx.x * 64 >= n) return; // the whole workgroup
+    const uint32_t *k = ids + (size_t)blockIdx.y * cap;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = blockIdx.x * 64 + lane;
+    const uint32_t mid = i < n ? k[i] : 0xffffffffu;
+    int rank = 0;
+    for (int base = 0; base < n; base += BOW_RANK_TILE) {
+        const int cnt = n - base < BOW_RANK_TILE ? n - base : BOW_RANK_TILE;
+        if (base) __syncthreads();
+        // the padding (last tile only, positions beyond every feature) is never below an id
+#pragma unroll
+        for (int u = 0; u < BOW_RANK_TILE / 256; u++) {
+            const int j = tid + 256 * u;
+            ((uint32_t *)s_id)[j] = j < cnt ? k[base + j] : 0xffffffffu;
+        }
+        __syncthreads();
+        const int li = i - base; // this thread's own position in the tile (beyond it: a later tile, negative: an earlier one)
+        const int steps = (cnt + 15) >> 4, per = (steps + 3) >> 2; // 16 ids per step, the steps of this tile split evenly over the waves
+        const int s1 = (wave + 1) * per < steps ? (wave + 1) * per : steps;
+        for (int s = wave * per; s < s1; s++) { // every lane reads the same address: a broadcast
+            const int j0 = 16 * s;
+            if (j0 + 16 <= li) rank += count_below<true>(s_id + 4 * s, mid);
+            else if (j0 >= li) rank += count_below<false>(s_id + 4 * s, mid);
+            else { // the step holds this thread's own key
+#pragma unroll
+                for (int u = 0; u < 16; u++) {
+                    const uint32_t v = ((const uint32_t *)s_id)[j0 + u];
+                    rank += j0 + u < li ? (int)(v <= mid) : (int)(v < mid);
+                }
+            }
+        }
+    }
+    s_part[wave][lane] = rank;
+    __syncthreads();
+    if (wave == 0 && i < n) {
+        const size_t r = (size_t)blockIdx.y * cap + s_part[0][lane] + s_part[1][lane] + s_part[2][lane] + s_part[3][lane]; // n distinct keys: rank < n
+        sorted_id[r] = mid;
+        sorted_pay[r] = blockIdx.y == 0 ? __float_as_uint(wt[i]) : (uint32_t)i;
+    }
+}
+static_assert(BOW_RANK_TILE % 256 == 0, "bow_rank_kernel: every thread stages the same number of ids, a quarter of the tile is whole 16-id steps");
+
+// blockIdx.x = 0: fBow (words, summed weights), 1: fBow2 (nodes -> features).  A usual frame (up to BOW_SEG_LDS keypoints) is staged
+// in LDS in one batch of loads, 32 KB; a larger one is read in place.
+__global__ __launch_bounds__(1024) void bow_segments_kernel(const uint32_t *__restrict__ sorted_id, const uint32_t *__restrict__ sorted_pay,
+                                                            const int *__restrict__ n_ptr, int cap,
+                                                            uint32_t *__restrict__ words, float *__restrict__ word_w, int32_t *__restrict__ n_words,
+                                                            uint32_t *__restrict__ nodes, int32_t *__restrict__ node_off, int32_t *__restrict__ node_feat,
+                                                            int32_t *__restrict__ n_nodes)
+{
+    __shared__ uint32_t s_id[BOW_SEG_LDS], s_pay[BOW_SEG_LDS];
+    __shared__ int s_wave[16];
+    const int n = slot_count(n_ptr, cap);
+    const int tid = threadIdx.x, which = blockIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t *id = sorted_id + (size_t)which * cap, *pay = sorted_pay + (size_t)which * cap;
+    if (n <= BOW_SEG_LDS) {
+#pragma unroll
+        for (int u = 0; u < BOW_SEG_LDS / 1024; u++) {
+            const int j = tid + 1024 * u;
+            if (j < n) { s_id[j] = id[j]; s_pay[j] = pay[j]; }
+        }
+        id = s_id; pay = s_pay;
+        __syncthreads();
+    }
+    const int chunk = (n + 1023) / 1024;
+    const int lo = tid * chunk < n ? tid * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
+    int heads = 0;
+    for (int p = lo; p < hi; p++) heads += p == 0 || id[p - 1] != id[p];
+    int incl = heads; // inclusive scan inside the wave, then over the 16 wave totals
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int w = 0; w < 16; w++) {
+        const int t = s_wave[w];
+        before += w < wave ? t : 0;
+        total += t;
+    }
+    int seg = before + incl - heads;
+    for (int p = lo; p < hi; p++) {
+        const uint32_t v = id[p];
+        const bool head = p == 0 || id[p - 1] != v;
+        if (which == 0) {
+            if (!head) continue;
+            float sum = 0.f; // std::map's value-initialised float, then += in feature order
+            for (int q = p; q < n && id[q] == v; q++) sum = __fadd_rn(sum, __uint_as_float(pay[q]));
+            words[seg] = v; word_w[seg] = sum;
+            seg++;
+        } else {
+            node_feat[p] = (int32_t)pay[p];
+            if (head) { nodes[seg] = v; node_off[seg] = p; seg++; }
+        }
+    }
+    if (tid == 0) {
+        if (which == 0) *n_words = total;
+        else {
+            *n_nodes = total;
+            if (n > 0) node_off[total] = n;
+        }
+    }
+}
+static_assert(BOW_SEG_LDS % 1024 == 0, "bow_segments_kernel: every thread stages the same number of entries");
+
+extern "C" int orbfe_enqueue_compute_bow(orbfe_context *ctx, int slot, int level, uint32_t *d_word_id, float *d_weight, uint32_t *d_node_id,
+                                         uint32_t *d_words, float *d_word_w, int32_t *d_n_words,
+                                         uint32_t *d_nodes, int32_t *d_node_off, int32_t *d_node_feat, int32_t *d_n_nodes,
+                                         int32_t *d_status, void *stream)
+try {
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    ORBFE_ENTRY(ctx);
+    if (level < 0 || !d_words || !d_word_w || !d_n_words || !d_nodes || !d_node_off || !d_node_feat || !d_n_nodes || !d_status)
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
+    orbfe_bow_state *st = orbfe_ctx_bow_state(ctx);
+    if (!st || !st->loaded) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "no vocabulary loaded (orbfe_vocab_load)");
+    const DeviceConfig *cfg = orbfe_ctx_config(ctx);
+    const DeviceBuffers *buf = orbfe_ctx_buffers(ctx);
+    if (slot < 0 || slot >= orbfe_ctx_last_images(ctx))
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d: the latest extraction call filled %d image slots", slot, orbfe_ctx_last_images(ctx));
+    const int cap = cfg->sel_total;
+    if (cap <= 0 || cap > 65535) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "frames with more than 65535 keypoints are not supported");
+    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
+    WTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    if (st->resident.ensure((size_t)cap * 7 * sizeof(uint32_t))) return orbfe_fail(ctx, ORBFE_ERR_HIP, "BoW scratch allocation failed");
+    const int rc = orbfe_ctx_order_after_extraction(ctx, s); // an event wait on the stream, no host wait
+    if (rc != ORBFE_OK) return rc;
+    uint32_t *ids = (uint32_t *)st->resident.p, *sorted_id = ids + 2 * (size_t)cap, *sorted_pay = sorted_id + 2 * (size_t)cap; // [2][cap] each: words, nodes
+    float *wt = (float *)(sorted_pay + 2 * (size_t)cap);
+    const BowTree t = {st->d_data, (unsigned)st->p.block_size_bytes_wp, (unsigned)st->p.feature_off_start, (unsigned)st->p.child_off_start,
+                       (unsigned)st->p.desc_size_bytes_wp, (int)ceil(log2((double)st->p.m_k))};
+    const uint8_t *desc = buf->desc + (size_t)slot * cap * 32;
+    const int *n_ptr = buf->kp_cnt + slot;
+    hipLaunchKernelGGL(bow_descend_resident_kernel, dim3((cap + 255) / 256), dim3(256), 0, s, t, level, desc, n_ptr, cap, d_word_id, d_weight, d_node_id, ids, ids + cap,
+                       wt, d_status);
+    hipLaunchKernelGGL(bow_rank_kernel, dim3((cap + 63) / 64, 2), dim3(256), 0, s, (const uint32_t *)ids, (const float *)wt, sorted_id, sorted_pay, n_ptr, cap);
+    hipLaunchKernelGGL(bow_segments_kernel, dim3(2), dim3(1024), 0, s, (const uint32_t *)sorted_id, (const uint32_t *)sorted_pay, n_ptr, cap, d_words, d_word_w,
+                       d_n_words, d_nodes, d_node_off, d_node_feat, d_n_nodes);
+    WTRY(ctx, hipGetLastError());
+    return ORBFE_OK;
+} ORBFE_CATCH(ctx)
+
+// ---------------------------------------------------------------------------------------------
+// SearchByFboW(KeyFrame*, Frame&)
+// ---------------------------------------------------------------------------------------------
+struct BowSearch {
+    const uint32_t *kf_nodes; const int32_t *kf_off, *kf_feat; int kf_nnodes;   // the keyframe's feature vector (CSR)
+    const int32_t *kf_valid; const uint8_t *kf_desc; const float *kf_angle; int n_kf;
+    const float *kf_pos;                                                        // optional, for Xw
+    const uint32_t *f_nodes; const int32_t *f_off, *f_feat, *f_n_nodes;         // the frame's, as orbfe_enqueue_compute_bow wrote it
+    const KeyPointPOD *keys; const uint8_t *desc; const int *n_ptr; int cap;    // the slot
+    float nnratio; int check_ori;
+    int32_t *match, *nmatches, *status;
+    uint8_t *has_point; float *Xw;
+};
+
+__global__ __launch_bounds__(256) void bow_match_init_kernel(BowSearch a)
+{
+    const int n = slot_count(a.n_ptr, a.cap);
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k == 0) *a.status = n > 0 ? ORBFE_OK : ORBFE_ERR_INVALID; // a frame without keypoints has no BoW vector to search by
+    if (k < n) a.match[k] = -1;
+}
+
+// Minimum over the wave in six DPP steps (no LDS round trip): inside each quad, inside each row of 16 by two rotations, then the
+// last lane of a row into the next row (rows 1 and 3), of row 1 into rows 2 and 3; lane 63 holds the result.  Lanes a step does
+// not write keep their value, and a minimum does not mind seeing a value twice.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned dpp_min_step(unsigned v)
+{
+    const unsigned t = (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xf, false);
+    return t < v ? t : v;
+}
+__device__ __forceinline__ unsigned wave_min_u32(unsigned v)
+{
+    v = dpp_min_step<0xb1, 0xf>(v);  // quad_perm:[1,0,3,2]
+    v = dpp_min_step<0x4e, 0xf>(v);  // quad_perm:[2,3,0,1]
+    v = dpp_min_step<0x124, 0xf>(v); // row_ror:4
+    v = dpp_min_step<0x128, 0xf>(v); // row_ror:8
+    v = dpp_min_step<0x142, 0xa>(v); // row_bcast:15
+    v = dpp_min_step<0x143, 0xc>(v); // row_bcast:31
+    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
+__device__ __forceinline__ int hamming256(const uint32_t *a, const uint32_t *b)
+{
+    int d = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) d += __popc(a[k] ^ b[k]);
+    return d;
+}
+
+// One wave per keyframe node.  Position j of the node's frame features belongs to lane j & 63 (its chunk j >> 6); the flag "frame
+// keypoint already matched" of chunk c < BOW_FLAG_CHUNKS is bit c of the lane's `taken`, of a later chunk it is f_match itself,
+// which only this lane wrote (every frame keypoint lies in one node).  A lane's candidates come in list order, so its running
+// (d1, d2) is the if-chain of :213-222 on its share; the wave's bestDist1 is the smallest key d << 16 | j (first minimum in list
+// order), bestDist2 the smallest distance of all the others, duplicates of bestDist1 included.
+__global__ __launch_bounds__(256) void bow_node_match_kernel(BowSearch a)
+{
+    const int lane = threadIdx.x & 63;
+    const int node = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (node >= a.kf_nnodes) return;
+    const int n = slot_count(a.n_ptr, a.cap);
+    if (n == 0) return;
+    int nfn = *a.f_n_nodes;
+    nfn = nfn < 0 ? 0 : (nfn > a.cap ? a.cap : nfn);
+    const uint32_t id = a.kf_nodes[node];
+    if (node > 0 && a.kf_nodes[node - 1] >= id) { // std::map order: the merge-join of :173-282 relies on it
+        if (lane == 0) *a.status = ORBFE_ERR_INVALID;
+        return;
+    }
+    int lo = 0, hi = nfn; // first frame node >= id: the lanes probe 64 places at once, the range shrinks 64-fold per load
+    while (lo < hi) {
+        const int step = (hi - lo + 63) >> 6;
+        const int p = lo + lane * step;
+        const int c = __popcll(__ballot(p < hi && a.f_nodes[p] < id)); // probes below id: a prefix of the lanes
+        if (c == 0) { hi = lo; break; }
+        const int top = lo + c * step;
+        lo += (c - 1) * step + 1;
+        hi = top < hi ? top : hi;
+    }
+    if (lo >= nfn || a.f_nodes[lo] != id) return;
+    const int k0 = a.kf_off[node], k1 = a.kf_off[node + 1];
+    const int f0 = a.f_off[lo], f1 = a.f_off[lo + 1];
+    if (k0 < 0 || k1 < k0 || k1 > a.n_kf || f0 < 0 || f1 < f0 || f1 > a.cap) { // a keypoint lies in one node: no CSR is longer than its keypoint array
+        if (lane == 0) *a.status = ORBFE_ERR_INVALID;
+        return;
+    }
+    const int nf = f1 - f0;
+    if (k1 == k0 || nf == 0) return;
+    bool bad = false;
+    for (int j = lane; j < nf; j += 64) {
+        const int idx = a.f_feat[f0 + j];
+        bad = bad || idx < 0 || idx >= n;
+    }
+    // this lane's first BOW_REG_CHUNKS features stay in registers: few nodes hold more than 64 * BOW_REG_CHUNKS
+    int idxc[BOW_REG_CHUNKS];
+    uint32_t fdc[BOW_REG_CHUNKS][8];
+#pragma unroll
+    for (int c = 0; c < BOW_REG_CHUNKS; c++) {
+        const int j = lane + 64 * c;
+        idxc[c] = j < nf ? a.f_feat[f0 + j] : -1;
+        if (idxc[c] >= n) idxc[c] = -1;
+#pragma unroll
+        for (int k = 0; k < 8; k++) fdc[c][k] = idxc[c] >= 0 ? ((const uint32_t *)(a.desc + (size_t)idxc[c] * 32))[k] : 0u;
+    }
+    u64 taken = 0;
+    for (int kbase = k0; kbase < k1; kbase += 64) {
+        // 64 KF features at a time are fetched by the lanes side by side, so that no load sits in the sequential loop below
+        int my_kf = -1;
+        bool my_ok = false;
+        uint32_t my_kd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (kbase + lane < k1) {
+            my_kf = a.kf_feat[kbase + lane];
+            if (my_kf < 0 || my_kf >= a.n_kf) bad = true;
+            else if (a.kf_valid[my_kf]) {
+                my_ok = true;
+#pragma unroll
+                for (int k = 0; k < 8; k++) my_kd[k] = ((const uint32_t *)(a.kf_desc + (size_t)my_kf * 32))[k];
+            }
+        }
+        for (u64 todo = __ballot(my_ok); todo; todo &= todo - 1) { // the valid KF features in order
+            const int src = __ffsll((long long)todo) - 1;
+            const int real_kf = __builtin_amdgcn_readlane(my_kf, src);
+            uint32_t kd[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) kd[k] = (uint32_t)__builtin_amdgcn_readlane((int)my_kd[k], src);
+            int d1 = 256, d2 = 256, c1 = 1023, i1 = -1; // 256 differing bits are no candidate (`dist < bestDist1`), chunk 1023 is none
+#pragma unroll
+            for (int c = 0; c < BOW_REG_CHUNKS; c++) {
+                if (idxc[c] < 0 || ((taken >> c) & 1ull)) continue;
+                const int d = hamming256(kd, fdc[c]);
+                if (d < d1) { d2 = d1; d1 = d; c1 = c; i1 = idxc[c]; }
+                else if (d < d2) d2 = d;
+            }
+            for (int j = lane + 64 * BOW_REG_CHUNKS, c = BOW_REG_CHUNKS; j < nf; j += 64, c++) {
+                const int idx = a.f_feat[f0 + j];
+                if (idx < 0 || idx >= n) continue;
+                if (c < BOW_FLAG_CHUNKS ? (int)((taken >> c) & 1ull) : a.match[idx] >= 0) continue;
+                const int d = hamming256(kd, (const uint32_t *)(a.desc + (size_t)idx * 32));
+                if (d < d1) { d2 = d1; d1 = d; c1 = c; i1 = idx; }
+                else if (d < d2) d2 = d;
+            }
+            // bestDist1: the smallest key distance << 16 | list position (chunk * 64 + lane): the first minimum in list order
+            const unsigned key = ((unsigned)d1 << 16) | (unsigned)(c1 * 64 + lane);
+            const unsigned m = wave_min_u32(key);
+            const int best1 = (int)(m >> 16);
+            if (best1 > TH_LOW) continue; // also: no candidate at all
+            const bool winner = key == m; // list positions are unique
+            const int best2 = (int)wave_min_u32((unsigned)(winner ? d2 : d1)); // the smallest of all the others, duplicates of bestDist1 included
+            if (!((float)best1 < a.nnratio * (float)best2)) continue;
+            if (winner) {
+                a.match[i1] = real_kf;
+                if (c1 < BOW_FLAG_CHUNKS) taken |= 1ull << c1;
+            }
+        }
+    }
+    if (__any(bad) && lane == 0) *a.status = ORBFE_ERR_INVALID;
+}
+
+// One workgroup.  A frame keypoint is matched at most once, so the accepted events are the non-negative entries of f_match.
+__global__ __launch_bounds__(1024) void bow_match_tail_kernel(BowSearch a)
+{
+    __shared__ int32_t s_hist[32];
+    __shared__ int s_keep[3], s_nm;
+    const int tid = threadIdx.x;
+    const int n = slot_count(a.n_ptr, a.cap);
+    if (tid < 32) s_hist[tid] = 0;
+    if (tid == 0) s_nm = 0;
+    __syncthreads();
+    if (a.check_ori) {
+        for (int k = tid; k < n; k += 1024) {
+            const int m = a.match[k];
+            if (m < 0) continue;
+            int bin = orbfe_resolve::rot_bin(a.kf_angle[m], a.keys[k].angle); // rotHist[bin].push_back(bestIdxF), :240-250
+            if ((unsigned)bin >= (unsigned)HISTO_LENGTH) { bin = 0; *a.status = ORBFE_ERR_INVALID; } // angles outside [0, 360)
+            atomicAdd(&s_hist[bin], 1);
+        }
+        __syncthreads();
+        if (tid == 0) orbfe_resolve::three_maxima(s_hist, HISTO_LENGTH, &s_keep[0], &s_keep[1], &s_keep[2]);
+        __syncthreads();
+    }
+    int cnt = 0;
+    for (int k = tid; k < n; k += 1024) {
+        int m = a.match[k];
+        if (m >= 0 && a.check_ori) {
+            int bin = orbfe_resolve::rot_bin(a.kf_angle[m], a.keys[k].angle);
+            if ((unsigned)bin >= (unsigned)HISTO_LENGTH) bin = 0;
+            if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) { a.match[k] = -1; m = -1; } // :263-278
+        }
+        cnt += m >= 0;
+        if (a.has_point) a.has_point[k] = m >= 0;
+        if (a.Xw && a.kf_pos && m >= 0) {
+            a.Xw[3 * k] = a.kf_pos[3 * m];
+            a.Xw[3 * k + 1] = a.kf_pos[3 * m + 1];
+            a.Xw[3 * k + 2] = a.kf_pos[3 * m + 2];
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((tid & 63) == 0 && cnt) atomicAdd(&s_nm, cnt);
+    __syncthreads();
+    if (tid == 0) *a.nmatches = s_nm;
+}
+
+extern "C" int orbfe_enqueue_search_by_bow(orbfe_context *ctx, int slot,
+                                           const uint32_t *d_kf_nodes, const int32_t *d_kf_off, const int32_t *d_kf_feat, int kf_nnodes,
+                                           const int32_t *d_kf_valid, const uint8_t *d_kf_desc, const float *d_kf_angle, int n_kf, const float *d_kf_pos,
+                                           const uint32_t *d_f_nodes, const int32_t *d_f_off, const int32_t *d_f_feat, const int32_t *d_f_n_nodes,
+                                           float nnratio, int check_ori, int32_t *d_f_match, int32_t *d_nmatches, int32_t *d_status,
+                                           uint8_t *d_has_point, float *d_Xw, void *stream)
+try {
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    ORBFE_ENTRY(ctx);
+    if (kf_nnodes < 0 || n_kf < 0 || !d_f_nodes || !d_f_off || !d_f_feat || !d_f_n_nodes || !d_f_match || !d_nmatches || !d_status ||
+        (kf_nnodes > 0 && (!d_kf_nodes || !d_kf_off || !d_kf_feat || !d_kf_valid || !d_kf_desc || !d_kf_angle)))
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
+    const DeviceConfig *cfg = orbfe_ctx_config(ctx);
+    const DeviceBuffers *buf = orbfe_ctx_buffers(ctx);
+    if (slot < 0 || slot >= orbfe_ctx_last_images(ctx))
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d: the latest extraction call filled %d image slots", slot, orbfe_ctx_last_images(ctx));
+    const int cap = cfg->sel_total;
+    if (cap <= 0 || cap > 65535) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "frames with more than 65535 keypoints are not supported");
+    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
+    WTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    const int rc = orbfe_ctx_order_after_extraction(ctx, s);
+    if (rc != ORBFE_OK) return rc;
+    BowSearch a;
+    a.kf_nodes = d_kf_nodes; a.kf_off = d_kf_off; a.kf_feat = d_kf_feat; a.kf_nnodes = kf_nnodes;
+    a.kf_valid = d_kf_valid; a.kf_desc = d_kf_desc; a.kf_angle = d_kf_angle; a.n_kf = n_kf; a.kf_pos = d_kf_pos;
+    a.f_nodes = d_f_nodes; a.f_off = d_f_off; a.f_feat = d_f_feat; a.f_n_nodes = d_f_n_nodes;
+    a.keys = (const KeyPointPOD *)buf->kps + (size_t)slot * cap; // mvKeys[].angle
+    a.desc = buf->desc + (size_t)slot * cap * 32;
+    a.n_ptr = buf->kp_cnt + slot; a.cap = cap;
+    a.nnratio = nnratio; a.check_ori = check_ori != 0;
+    a.match = d_f_match; a.nmatches = d_nmatches; a.status = d_status; a.has_point = d_has_point; a.Xw = d_Xw;
+    hipLaunchKernelGGL(bow_match_init_kernel, dim3((cap + 255) / 256), dim3(256), 0, s, a);
+    if (kf_nnodes > 0) hipLaunchKernelGGL(bow_node_match_kernel, dim3((kf_nnodes + 3) / 4), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(bow_match_tail_kernel, dim3(1), dim3(1024), 0, s, a);
+    WTRY(ctx, hipGetLastError());
+    return ORBFE_OK;
+} ORBFE_CATCH(ctx)

@@ -11,6 +11,11 @@ library has them -- the asynchronous matcher (orbfe_enqueue_search_by_projection
 synchronise and as GPU time between two events, and match -> pose as two host calls against the one-stream chain.  The
 asynchronous rows are skipped on a library that does not export the entry points, so the same script measures an older build
 (profiles/matchers_device_resolve.json).
+    python3 tools/bench_matchers.py --bow-only
+runs only the TrackReferenceKeyFrame rows (profiles/bow_device.json): (a) the synchronous trio orbfe_bow_transform + orbfe_bow_maps +
+orbfe_search_by_bow on the 1500 / 1600 descriptor scene, (b) orbfe_enqueue_compute_bow + orbfe_enqueue_search_by_bow on the same
+frame resident in slot 0, as enqueue + one stream synchronise and as GPU time between two events, (c) BoW -> match -> pose on
+a real extracted frame as host calls against the one-stream chain.  (b) and the chain are skipped on a library without them.
 """
 import json
 import os
@@ -128,8 +133,190 @@ def resident_async_rows(ctx2, out, fs, fb, fk, fur, v_dev, args_sync):
         "note": "the matcher reads the same fixed pose in both chains; %d inliers" % ninl.value}
 
 
+def bow_rows(out):
+    """Rows (a), (b), (c) of --bow-only; arguments prepared once, C ABI called directly."""
+    import ctypes as C
+    import torch
+    from orbslam2_amd import api, synth
+    from orbslam2_amd import bow as B
+    from tests import test_bow as TB
+    vp, P = C.c_void_p, TB._p
+    dev = torch.device("cuda:0")
+    up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, t).view(np.uint8).reshape(-1)).to(dev)
+    i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
+    ctx = api.Context(width=TM.W, height=TM.H, nfeatures=2000, fx=TM.FX, fy=TM.FY, cx=TM.CX, cy=TM.CY, bf=TM.BF)
+    L = ctx.L
+    B._bind()
+    have = hasattr(L, "orbfe_enqueue_compute_bow") and hasattr(L, "orbfe_enqueue_search_by_bow")
+    if have:  # set here too, so that the script also drives a library newer than the Python package beside it
+        L.orbfe_enqueue_compute_bow.restype = C.c_int
+        L.orbfe_enqueue_compute_bow.argtypes = [vp, C.c_int, C.c_int] + [vp] * 12
+        L.orbfe_enqueue_search_by_bow.restype = C.c_int
+        L.orbfe_enqueue_search_by_bow.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp] + [vp] * 4 + [C.c_float, C.c_int] + [vp] * 6
+    blob = B.build_vocabulary(TB._descs(1, 6000), k=10, levels=5, seed=7)
+    B.vocab_load(ctx, blob)
+    Lo, v = TB._oracle_voc(blob)
+    st = torch.cuda.Stream()
+    sp = vp(st.cuda_stream)
+    cap = ctx.capacity
+    rows = out["rows"]
+    bufs = [C.c_void_p() for _ in range(5)]
+
+    class Host:
+        """The synchronous trio on host arrays (kf = its precomputed feature vector, frame = descriptors and angles)."""
+
+        def __init__(self, kf_fv, kf_valid, kf_d, kf_ang, f_d, f_ang):
+            n = len(f_d)
+            self.n = n
+            self.keep = [np.ascontiguousarray(x, t) for x, t in ((kf_fv[0], np.uint32), (kf_fv[1], np.int32), (kf_fv[2], np.int32), (kf_valid, np.int32),
+                                                                 (kf_d, np.uint8), (kf_ang, np.float32), (f_d, np.uint8), (f_ang, np.float32))]
+            k = self.keep
+            self.w, self.wt, self.nd = np.zeros(n, np.uint32), np.zeros(n, np.float32), np.zeros(n, np.uint32)
+            self.words, self.ww, self.nodes = np.zeros(n, np.uint32), np.zeros(n, np.float32), np.zeros(n, np.uint32)
+            self.off, self.feat, self.match = np.zeros(n + 1, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+            self.nw, self.nn, self.nm = C.c_int(), C.c_int(), C.c_int()
+            self.a_tr = (ctx.h, P(k[6]), n, 4, P(self.w), P(self.wt), P(self.nd))
+            self.a_maps = (P(self.w), P(self.wt), P(self.nd), n, P(self.words), P(self.ww), C.byref(self.nw), P(self.nodes), P(self.off), P(self.feat),
+                           C.byref(self.nn))
+            self.a_search = [ctx.h, P(k[0]), P(k[1]), P(k[2]), len(k[0]), P(k[3]), P(k[4]), P(k[5]), len(k[4]), P(self.nodes), P(self.off), P(self.feat), 0,
+                             P(k[6]), P(k[7]), n, C.c_float(0.7), 1, P(self.match), C.byref(self.nm)]
+
+        def __call__(self):
+            assert L.orbfe_bow_transform(*self.a_tr) == 0
+            assert L.orbfe_bow_maps(*self.a_maps) == 0
+            self.a_search[12] = self.nn.value
+            assert L.orbfe_search_by_bow(*self.a_search) == 0
+
+    class Device:
+        """The resident pair: the keyframe's arrays uploaded once, the frame is slot 0."""
+
+        def __init__(self, kf_fv, kf_valid, kf_d, kf_ang, kf_pos=None):
+            self.kf = [up(kf_fv[0], np.uint32), up(kf_fv[1], np.int32), up(kf_fv[2], np.int32), up(kf_valid, np.int32), up(kf_d, np.uint8), up(kf_ang, np.float32)]
+            self.pos = None if kf_pos is None else up(kf_pos, np.float32)
+            self.o = [i32(cap) for _ in range(4)] + [i32(cap + 1)] + [i32(1) for _ in range(3)]  # words, word_w, nodes, node_feat, node_off, n_words, n_nodes, status
+            self.match, self.nm, self.status = i32(cap), i32(1), i32(1)
+            self.has = torch.zeros(cap, dtype=torch.uint8, device=dev); self.xw = torch.zeros((cap, 3), dtype=torch.float32, device=dev)
+            o = [vp(t.data_ptr()) for t in self.o]
+            self.a_bow = (ctx.h, 0, 4, None, None, None, o[0], o[1], o[5], o[2], o[4], o[3], o[6], o[7], sp)
+            k = [vp(t.data_ptr()) for t in self.kf]
+            pose = self.pos is not None
+            self.a_search = (ctx.h, 0, k[0], k[1], k[2], len(kf_fv[0]), k[3], k[4], k[5], len(kf_d), vp(self.pos.data_ptr()) if pose else None,
+                             o[2], o[4], o[3], o[6], C.c_float(0.7), 1, vp(self.match.data_ptr()), vp(self.nm.data_ptr()), vp(self.status.data_ptr()),
+                             vp(self.has.data_ptr()) if pose else None, vp(self.xw.data_ptr()) if pose else None, sp)
+
+        def enqueue(self):
+            assert L.orbfe_enqueue_compute_bow(*self.a_bow) == 0
+            assert L.orbfe_enqueue_search_by_bow(*self.a_search) == 0
+
+        def __call__(self):
+            self.enqueue()
+            assert L.orbfe_synchronize(ctx.h, sp) == 0
+
+    # ---- (a), (b): the scene of tests/test_bow.py, 1500 keyframe / 1600 frame descriptors, the frame copied into slot 0
+    kf_d = TB._descs(4, 1500)
+    rng = np.random.default_rng(5)
+    perm = rng.permutation(1500)[:1200]
+    f_d = np.concatenate([TB._descs(6, 0, base=kf_d[perm], flip=0.04), TB._descs(7, 400)])
+    kf_valid = (rng.random(len(kf_d)) < 0.8).astype(np.int32)
+    kf_ang = rng.uniform(0, 360, len(kf_d)).astype(np.float32)
+    f_ang = np.concatenate([(kf_ang[perm] + rng.normal(0, 5, 1200)) % 360, rng.uniform(0, 360, 400)]).astype(np.float32)
+    _, _, kf_fv = TB._oracle_transform(Lo, v, kf_d, 4)
+    host = Host(kf_fv, kf_valid, kf_d, kf_ang, f_d, f_ang)
+    host()
+    out["bow_scene"] = "%d keyframe / %d frame descriptors, level 4, %d matches" % (len(kf_d), len(f_d), host.nm.value)
+    rows["(a) synchronous trio orbfe_bow_transform + orbfe_bow_maps + orbfe_search_by_bow, wall time"] = {"gpu_ms": round(timeit(host, 200), 4)}
+    rows["(a) ... of which orbfe_bow_transform"] = {"gpu_ms": round(timeit(lambda: L.orbfe_bow_transform(*host.a_tr), 200), 4)}
+    rows["(a) ... of which orbfe_bow_maps (host only)"] = {"gpu_ms": round(timeit(lambda: L.orbfe_bow_maps(*host.a_maps), 200), 4)}
+    rows["(a) ... of which orbfe_search_by_bow"] = {"gpu_ms": round(timeit(lambda: L.orbfe_search_by_bow(*host.a_search), 200), 4)}
+    if have:
+        left, right = synth.stereo_pair(TM.W, TM.H, seed=77)
+        ctx.stereo_frame(left, right)  # the extraction call slot 0 belongs to; then the scene's frame is copied over it
+        assert L.orbfe_device_buffers(ctx.h, *[C.byref(x) for x in bufs]) == 0
+        n = len(f_d)
+        k = np.zeros(n, api.KP_DTYPE); k["angle"] = f_ang
+
+        def raw(ptr, nbytes):
+            class R:
+                __cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
+            return torch.as_tensor(R(), device=dev)
+        raw(bufs[0].value, 28 * n)[:] = torch.from_numpy(k.view(np.uint8).reshape(-1).copy()).to(dev)
+        raw(bufs[1].value, 32 * n)[:] = up(f_d, np.uint8)
+        raw(bufs[2].value, 4)[:] = up(np.array([n], np.int32), np.int32)
+        torch.cuda.synchronize()
+        d = Device(kf_fv, kf_valid, kf_d, kf_ang)
+        d()
+        assert int(d.status.item()) == 0 and int(d.nm.item()) == host.nm.value and np.array_equal(d.match.cpu().numpy()[:n], host.match)
+        rows["(b) orbfe_enqueue_compute_bow + orbfe_enqueue_search_by_bow, enqueue + one stream synchronise"] = {"gpu_ms": round(timeit(d, 200), 4)}
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(200):
+            d.enqueue()
+        e1.record(st)
+        st.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(200):
+            d.enqueue()
+        t_enq = (time.perf_counter() - t0) / 200 * 1e3
+        st.synchronize()
+        rows["(b) the same pair, GPU time between two events (200 pairs queued back to back)"] = {"gpu_ms": round(e0.elapsed_time(e1) / 200, 4),
+                                                                                                   "host_enqueue_ms": round(t_enq, 4)}
+    else:
+        out["async"] = "not exported by this library"
+    # ---- (c) TrackReferenceKeyFrame on a real extracted frame: the keyframe is its perturbed copy (tests/test_matchers.py, _frame_scene)
+    left, right = synth.stereo_pair(TM.W, TM.H, seed=77)
+    fr = ctx.stereo_frame(left, right)
+    fk, fd, fur = fr["kps_left"], fr["desc_left"], fr["u_right"]
+    fs = TM._frame_scene(fk, fd, fur, 77, all_points=True)
+    nk = len(fk)
+    _, _, kfv = TB._oracle_transform(Lo, v, fs["desc"], 4)
+    host = Host(kfv, fs["valid"], fs["desc"], fs["angle"], fd, np.ascontiguousarray(fk["angle"]))
+    T4 = np.eye(4, dtype=np.float32); T4[:3] = fs["T_cur"]
+    k_host = np.ascontiguousarray(fk, api.KP_DTYPE); ur_host = np.ascontiguousarray(fur, np.float32)
+    hp = np.zeros(nk, np.uint8); xw = np.zeros((nk, 3), np.float32); outl = np.zeros(nk, np.uint8)
+    Th = T4.copy(); ninl = C.c_int()  # both chains optimise their pose in place: after the first repeat they start from the converged pose
+    pos_host = np.ascontiguousarray(fs["pos"], np.float32)
+
+    def host_chain():
+        host()
+        np.greater_equal(host.match, 0, out=hp.view(bool))
+        xw[:] = pos_host[np.maximum(host.match, 0)]
+        assert L.orbfe_pose_optimization(ctx.h, P(Th), nk, P(k_host), P(ur_host), P(hp), P(xw), P(outl), C.byref(ninl)) == 0
+
+    host_chain()
+    out["chain_scene"] = "%d keypoints extracted from a synthetic 640x480 pair, keyframe of %d map points, %d matches, %d inliers" % (
+        nk, len(fs["pos"]), host.nm.value, ninl.value)
+    rows["(c) TrackReferenceKeyFrame, host calls (the trio + orbfe_pose_optimization)"] = {"gpu_ms": round(timeit(host_chain, 100), 4)}
+    if have:
+        assert L.orbfe_device_buffers(ctx.h, *[C.byref(x) for x in bufs]) == 0
+        d = Device(kfv, fs["valid"], fs["desc"], fs["angle"], fs["pos"])
+        d_keys = C.c_void_p()
+        d_off = torch.tensor([0, nk], dtype=torch.int32, device=dev)
+        d_T = torch.from_numpy(T4).to(dev); d_outl = torch.zeros(cap, dtype=torch.uint8, device=dev); d_ninl = i32(1)
+        torch.cuda.synchronize()
+
+        def device_chain():
+            d.enqueue()
+            assert L.orbfe_device_keys_un(ctx.h, 0, C.byref(d_keys), sp) == 0
+            assert L.orbfe_enqueue_pose_optimization(ctx.h, 1, vp(d_off.data_ptr()), d_keys, bufs[3], vp(d.has.data_ptr()), vp(d.xw.data_ptr()),
+                                                     vp(d_T.data_ptr()), vp(d_outl.data_ptr()), vp(d_ninl.data_ptr()), cap, sp) == 0
+            assert L.orbfe_synchronize(ctx.h, sp) == 0
+
+        device_chain()
+        assert int(d.nm.item()) == host.nm.value and np.array_equal(d.match.cpu().numpy()[:nk], host.match) and int(d_ninl.item()) == ninl.value
+        rows["(c) TrackReferenceKeyFrame, one-stream chain (compute_bow + search_by_bow + device_keys_un + enqueue pose + one synchronise)"] = {
+            "gpu_ms": round(timeit(device_chain, 100), 4)}
+    Lo.orc_vocab_destroy(v)
+    ctx.close()
+
+
 def main():
     from orbslam2_amd import api
+    if "--bow-only" in sys.argv[1:]:
+        out = {"unit": "ms per call", "rows": {}}
+        bow_rows(out)
+        out["build_id"] = api.build_id()
+        print(json.dumps(out, indent=1))
+        return
     resident_only = "--resident-only" in sys.argv[1:]
     ctx = api.Context(width=TM.W, height=TM.H, fx=TM.FX, fy=TM.FY, cx=TM.CX, cy=TM.CY, bf=TM.BF)
     s = TM._scene(3, n_last=2000, n_distract=700)
