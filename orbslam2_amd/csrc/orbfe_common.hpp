@@ -200,12 +200,18 @@ __device__ __forceinline__ int hamming256(const uint32_t *a, const uint32_t *b)
 // Raw pyramid level `level` of image `img`: first pixel and row pitch.  Level 0 goes through DeviceBuffers::lv0 (the library's
 // pitched copy, or the caller's packed images read in place); `level` is wave-uniform at every call site but the stereo
 // refinement's, where it is a select per lane.
+// level_image_at(): the same for a caller that already holds the level's LevelInfo::pitch and pyr_off.
+__device__ __forceinline__ const uint8_t *level_image_at(const DeviceConfig &cfg, const DeviceBuffers &buf, int img, int level, int lv_pitch, int lv_pyr_off, int &pitch)
+{
+    if (level == 0) { pitch = buf.lv0_pitch; return buf.lv0 + (size_t)img * buf.lv0_stride; }
+    pitch = lv_pitch;
+    return buf.pyr + (size_t)img * cfg.pyr_bytes + lv_pyr_off;
+}
 __device__ __forceinline__ const uint8_t *level_image(const DeviceConfig &cfg, const DeviceBuffers &buf, int img, int level, int &pitch)
 {
     if (level == 0) { pitch = buf.lv0_pitch; return buf.lv0 + (size_t)img * buf.lv0_stride; }
     const LevelInfo &L = cfg.lv[level];
-    pitch = L.pitch;
-    return buf.pyr + (size_t)img * cfg.pyr_bytes + L.pyr_off;
+    return level_image_at(cfg, buf, img, level, L.pitch, L.pyr_off, pitch);
 }
 
 // 16 bytes from an address that is only 4-byte aligned: one global_load_dwordx4 (fine on this memory system).  A plain struct

@@ -3,17 +3,24 @@
 
 
 // ---------------------------------------------------------------------------
-// stereo: one wave per left keypoint (coarse Hamming band search + SAD + parabola)
+// stereo: coarse Hamming band search per left keypoint, then SAD + parabola over the workgroup's pooled coarse matches
 // ---------------------------------------------------------------------------
-// One 16-lane group per left keypoint (four keypoints per wave, sixteen per workgroup): a row list holds a few
-// dozen candidates of which ~10 pass the octave / disparity filter, so a whole wave per keypoint idles most lanes
-// and, with ~7 dependent global round trips per keypoint, needs 4x the waves to hide the same latency.
-//   coarse search: lanes stride the row list; arg-min key dist << 16 | iR (= the reference's first minimum);
-//   SAD: the 11 x 11 left window and the 11 x 21 right band go through LDS (three 128-bit loads by 11 lanes); lane handles window
-//        pixels p = gl, gl + 16, .. < 121; the 11 shifted right-image bytes of a pixel are 12 contiguous bytes of its band row;
-//        sums reduced over the group by xor shuffles.
+// One 16-lane group per left keypoint (four keypoints per wave): a row list holds a few dozen candidates of which ~10 pass the
+// octave / disparity filter, so a whole wave per keypoint idles most lanes and needs 4x the waves to hide the same latency.
+// Two phases in one launch, joined through LDS by one workgroup barrier:
+//   coarse search: lanes stride the row list; arg-min key dist << 16 | iR (= the reference's first minimum).  A keypoint that
+//        does not reach the SAD gets its three result words here; one that does leaves a 32-byte job record (what the SAD phase
+//        needs, window addresses included: it fetches nothing but pixels) in its wave's segment of an LDS list.
+//   SAD: group g of wave w takes job 4 w + g of the workgroup's sixteen keypoints, so the waves that run the SAD are full of
+//        coarse matches (about half of the left keypoints have one, spread over nine waves in ten) and the others leave.
+//        Lane r < 11 holds row r of the 11 x 11 left window and of the 11 x 21 right band in registers (three 128-bit loads) as
+//        16-bit pixel pairs; one add and one v_sad_u16 per pair and shift; sums reduced over the group by DPP row operations.
+// With the SAD's instructions cut by a third the launch is bound by the length of a keypoint's chain of dependent loads, not by
+// issue, so every load whose address is known early is issued early: keypoint -> {level geometry, row
+// count, first 64 list entries} -> descriptors -> barrier -> pixels.
 #define SM_G 16
-#define SM_WIN_BYTES (11 * 16 + 11 * 32 + 16) // left window rows (16 B each), right band rows (32 B each), + 16: a row's shifted read may touch the next word
+#define SM_GROUPS (256 / SM_G)       // groups of a workgroup
+#define SM_K SM_GROUPS               // consecutive left keypoints whose coarse matches one workgroup pools: one per group
 __device__ __forceinline__ unsigned group_min_u32(unsigned v)
 {
 #pragma unroll
@@ -40,17 +47,16 @@ __global__ __launch_bounds__(256) void stereo_match_kernel(DeviceConfig cfg, Dev
 {
     // XCD-aware block -> (pair, block) map: all blocks of a pair on one XCD (its L2 then holds the pair's
     // descriptors, keypoints and the pyramid rows the SAD windows touch)
-    __shared__ uint2 s_cand[(256 / SM_G) * 4 * SM_G]; // per 16-lane group: the candidates of a 64-entry chunk that passed the filter
-    __shared__ __attribute__((aligned(16))) uint8_t s_win[(256 / SM_G) * SM_WIN_BYTES]; // per group: the SAD windows
-    const int kpb = 256 / SM_G;
-    const int bpp = (cfg.sel_total + kpb - 1) / kpb;
+    __shared__ uint2 s_cand[SM_GROUPS * 4 * SM_G]; // per 16-lane group: the candidates of a 64-entry chunk that passed the filter
+    __shared__ uint4 s_job[SM_GROUPS][2];  // per wave, for its keypoints that reach the SAD: iL | cr << 16, row pitch, level scale, uL; first byte of the left window, of the right band
+    __shared__ int s_njob[4];                      // per wave: how many
+    const int bpp = (cfg.sel_total + SM_K - 1) / SM_K;
     int pair, blk;
-    if (!xcd_map_magic(bpp, n_pairs, cfg.xcd_magic, pair, blk)) return;
+    if (!xcd_map_magic(bpp, n_pairs, cfg.xcd_magic, pair, blk)) return; // the whole workgroup
     const int imgL = 2 * pair, imgR = 2 * pair + 1;
-    const int gl = threadIdx.x & (SM_G - 1);
-    const int iL = blk * kpb + (threadIdx.x / SM_G);
+    const int gl = threadIdx.x & (SM_G - 1), grp = threadIdx.x / SM_G;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nL = buf.kp_cnt[imgL], nR = buf.kp_cnt[imgR];
-    if (iL >= nL) return; // whole group; the groups of a wave only meet in xor shuffles below the group size
     const KeyPointPOD *kL = (const KeyPointPOD *)buf.kps + (size_t)imgL * cfg.sel_total;
     const KeyPointPOD *kR = (const KeyPointPOD *)buf.kps + (size_t)imgR * cfg.sel_total;
     const uint8_t *dL = buf.desc + (size_t)imgL * cfg.sel_total * 32;
@@ -58,212 +64,245 @@ __global__ __launch_bounds__(256) void stereo_match_kernel(DeviceConfig cfg, Dev
     float *u_right = buf.u_right + (size_t)imgL * cfg.sel_total;
     float *depth = buf.depth + (size_t)imgL * cfg.sel_total;
     int *sad_out = buf.sad + (size_t)imgL * cfg.sel_total;
-
-    const KeyPointPOD kp = kL[iL];
-    const int level_l = kp.octave;
-    const float uL = kp.x, vL = kp.y;
-    const int row = (int)vL;
     const float min_z = cfg.mb;
     const float max_d = __fdiv_rn(cfg.bf, min_z);
-    const float min_u = __fsub_rn(uL, max_d);
-    const float max_u = uL; // uL - minD, minD = 0
 
-    uint32_t dl[8];
+    // ---- coarse phase.  No group leaves before the barrier: a keypoint index past the count is a predicate (an empty row list).
+    int wave_jobs; // wave-uniform
     {
-        const uint4 *p = (const uint4 *)(dL + (size_t)iL * 32);
-        const uint4 lo = p[0], hi = p[1];
-        dl[0] = lo.x; dl[1] = lo.y; dl[2] = lo.z; dl[3] = lo.w; dl[4] = hi.x; dl[5] = hi.y; dl[6] = hi.z; dl[7] = hi.w;
-    }
-    unsigned best = (100u << 16) | 0xffffu; // TH_HIGH; the index field only matters below it
-    float best_x = 0.f;
-    auto consider = [&](int iR, int oct, float xr) {
-        if (oct >= level_l - 1 && oct <= level_l + 1 && xr >= min_u && xr <= max_u) {
-            const uint4 *p = (const uint4 *)(dR + (size_t)iR * 32);
+        const int iL = blk * SM_K + grp; // fetched side by side with the count: a slot past the capacity's end is the right image's first
+        const KeyPointPOD kp = kL[iL];
+        const bool valid = iL < nL;
+        const int level_l = valid ? kp.octave : 0;
+        const float uL = kp.x, vL = kp.y;
+        const int row = (int)vL;
+        // everything whose address is known once the keypoint is here is fetched now, side by side: the level's geometry for the
+        // gates and the SAD phase (the configuration indexed per lane is a load like any other), the row's count and the first
+        // chunk of its list
+        const LevelInfo &L = cfg.lv[level_l];
+        const int lv_w = L.w, lv_h = L.h, lv_pitch = L.pitch, lv_off = L.pyr_off;
+        const float lv_scale = L.scale, sf = L.inv_scale;
+        const float min_u = __fsub_rn(uL, max_d);
+        const float max_u = uL; // uL - minD, minD = 0
+
+        uint32_t dl[8];
+        {
+            const uint4 *p = (const uint4 *)(dL + (size_t)iL * 32);
             const uint4 lo = p[0], hi = p[1];
-            const uint32_t dr[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-            const unsigned key = ((unsigned)hamming256(dl, dr) << 16) | (unsigned)iR;
-            if (key < best) { best = key; best_x = xr; }
+            dl[0] = lo.x; dl[1] = lo.y; dl[2] = lo.z; dl[3] = lo.w; dl[4] = hi.x; dl[5] = hi.y; dl[6] = hi.z; dl[7] = hi.w;
         }
-    };
-    // candidates = right keypoints whose row band covers int(vL) (vRowIndices[vL], src/Frame.cc:513), listed per row by the
-    // row-list waves (orbfe_rowlist.hpp); the arg-min key (dist << 16 | iR) makes the result independent of the order inside a row list
-    int cnt = 0;
-    if (row >= 0 && row < cfg.height) cnt = buf.row_cnt[(size_t)pair * cfg.height + row];
-    if (cnt <= cfg.row_cap) {
-        // Two rounds of loads instead of two per candidate: (1) every lane fetches up to four list entries at once and applies
-        // the octave / disparity filter (about a fifth pass); (2) the survivors are packed into a per-group LDS list through a
-        // ballot, so that each lane then fetches ONE survivor's descriptor -- all in flight together.  A row list of ~50
-        // entries used to cost four dependent entry -> descriptor round trips per lane.
-        const uint2 *rent = buf.row_ent + ((size_t)pair * cfg.height + row) * cfg.row_cap;
-        uint2 *s_list = s_cand + (threadIdx.x / SM_G) * (4 * SM_G);
-        const int gshift = (threadIdx.x & 63) & ~(SM_G - 1); // first lane of this group inside its wave
-        for (int j0 = 0; j0 < cnt; j0 += 4 * SM_G) {
-            uint2 e[4];
-            bool ok[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const int j = j0 + gl + SM_G * u;
-                e[u] = rent[j < cnt ? j : cnt - 1];
-            }
-            int n_pass = 0;
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const int j = j0 + gl + SM_G * u;
-                const int oct = (int)(e[u].x >> 16);
-                const float xr = __uint_as_float(e[u].y);
-                ok[u] = j < cnt && oct >= level_l - 1 && oct <= level_l + 1 && xr >= min_u && xr <= max_u;
-                const unsigned slice = (unsigned)(__ballot(ok[u]) >> gshift) & ((1u << SM_G) - 1u);
-                if (ok[u]) s_list[n_pass + __popc(slice & ((1u << gl) - 1u))] = e[u];
-                n_pass += __popc(slice);
-            }
-            __builtin_amdgcn_s_waitcnt(0xc07f); // this wave's LDS writes have landed (the groups of a wave run in lockstep)
-            __builtin_amdgcn_wave_barrier();
-            for (int k = gl; k < n_pass; k += SM_G) {
-                const uint2 c = s_list[k];
-                const int iR = (int)(c.x & 0xffffu);
+        unsigned best = (100u << 16) | 0xffffu; // TH_HIGH; the index field only matters below it
+        float best_x = 0.f;
+        auto consider = [&](int iR, int oct, float xr) {
+            if (oct >= level_l - 1 && oct <= level_l + 1 && xr >= min_u && xr <= max_u) {
                 const uint4 *p = (const uint4 *)(dR + (size_t)iR * 32);
                 const uint4 lo = p[0], hi = p[1];
                 const uint32_t dr[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
                 const unsigned key = ((unsigned)hamming256(dl, dr) << 16) | (unsigned)iR;
-                if (key < best) { best = key; best_x = __uint_as_float(c.y); }
+                if (key < best) { best = key; best_x = xr; }
             }
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_wave_barrier(); // the list is rewritten by the next chunk
+        };
+        // candidates = right keypoints whose row band covers int(vL) (vRowIndices[vL], src/Frame.cc:513), listed per row by the
+        // row-list waves (orbfe_rowlist.hpp); the arg-min key (dist << 16 | iR) makes the result independent of the order inside a row list
+        const bool row_ok = valid && row >= 0 && row < cfg.height;
+        const uint2 *rent = buf.row_ent + ((size_t)pair * cfg.height + (row_ok ? row : 0)) * cfg.row_cap;
+        uint2 e[4]; // slots past the row's count hold whatever an earlier call left there: masked by j < cnt below
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int j = gl + SM_G * u;
+            e[u] = rent[j < cfg.row_cap ? j : cfg.row_cap - 1];
         }
-    } else { // the row's list overflowed its capacity: test every right keypoint's band
-        for (int iR = gl; iR < nR; iR += SM_G) {
-            const KeyPointPOD kr = kR[iR];
-            const float r = __fmul_rn(2.0f, cfg.lv[kr.octave].scale);
-            const int maxr = (int)ceilf(__fadd_rn(kr.y, r));
-            const int minr = (int)floorf(__fsub_rn(kr.y, r));
-            if (row >= minr && row <= maxr) consider(iR, kr.octave, kr.x);
-        }
-    }
-    const unsigned gbest = group_min_u32(best);
-    const int best_dist = (int)(gbest >> 16);
-    // x of the winning candidate: held by the lane whose key won (keys are unique per iR)
-    float uR0 = best == gbest ? best_x : 0.f;
-    {
-        int bits = __float_as_int(uR0);
+        int cnt = 0;
+        if (row_ok) cnt = buf.row_cnt[(size_t)pair * cfg.height + row];
+        if (cnt <= cfg.row_cap) {
+            // Two rounds of loads instead of two per candidate: (1) every lane fetches up to four list entries at once and applies
+            // the octave / disparity filter (about a fifth pass); (2) the survivors are packed into a per-group LDS list through a
+            // ballot, so that each lane then fetches ONE survivor's descriptor -- all in flight together.  A row list of ~50
+            // entries used to cost four dependent entry -> descriptor round trips per lane.
+            uint2 *s_list = s_cand + grp * (4 * SM_G);
+            const int gshift = lane & ~(SM_G - 1); // first lane of this group inside its wave
+            for (int j0 = 0; j0 < cnt; j0 += 4 * SM_G) {
+                bool ok[4];
+                if (j0 > 0) {
 #pragma unroll
-        for (int o = SM_G / 2; o > 0; o >>= 1) bits |= __shfl_xor(bits, o, 64); // one lane holds it, the others 0
-        uR0 = __int_as_float(bits);
-    }
-    float out_u = -1.0f, out_d = -1.0f;
-    int out_sad = -1;
-    if (best_dist < 75) { // (TH_HIGH + TH_LOW) / 2
-        const float sf = cfg.lv[level_l].inv_scale;
-        const float s_uL = roundf(__fmul_rn(kp.x, sf));
-        const float s_vL = roundf(__fmul_rn(kp.y, sf));
-        const float s_uR0 = roundf(__fmul_rn(uR0, sf));
-        const LevelInfo &L = cfg.lv[level_l];
-        const int cu = (int)s_uL, cv = (int)s_vL, cr = (int)s_uR0;
-        const float iniu = s_uR0;                        // scaleduR0 + L - w
-        const float endu = __fadd_rn(s_uR0, 11.0f);      // scaleduR0 + L + w + 1
-        const bool in_ref = !(iniu < 0 || endu >= (float)L.w);
-        // the reference would throw on a window outside the level image; unreachable for
-        // keypoints >= 19 px from the border, kept as a memory-safety guard
-        const bool safe = cu - 5 >= 0 && cu + 5 < L.w && cv - 5 >= 0 && cv + 5 < L.h && cr - 10 >= 0 && cr + 10 < L.w;
-        if (in_ref && safe) {
-            int lpitch;
-            const uint8_t *imL = level_image(cfg, buf, imgL, level_l, lpitch);
-            const uint8_t *imR = level_image(cfg, buf, imgR, level_l, lpitch);
-            // the group's windows through LDS: lane r < 11 fetches row r of the left window (11 bytes from column cu - 5: one
-            // unaligned 128-bit load) and of the right band (21 bytes from column cr - 10: two), instead of every lane fetching a
-            // byte and a 12-byte piece for each of its 8 window pixels (18 load instructions per lane; the texture addresser was
-            // busy 62 % of this kernel).  The extra bytes (up to column cu + 10 / cr + 21) lie in the row's right margin
-            // (level 0 read in place: in the first bytes of the next row; the window's last row is >= 14 rows above the image's).
-            uint8_t *wl = s_win + (threadIdx.x / SM_G) * SM_WIN_BYTES, *wr = wl + 11 * 16;
-            if (gl < 11) {
-                const unsigned ro = (unsigned)__mul24(cv - 5 + gl, lpitch);
-                const uint4 a = load16_unaligned(imL + ro + cu - 5);
-                const uint4 b0 = load16_unaligned(imR + ro + cr - 10), b1 = load16_unaligned(imR + ro + cr + 6);
-                *(uint4 *)(wl + 16 * gl) = a;
-                *(uint4 *)(wr + 32 * gl) = b0;
-                *(uint4 *)(wr + 32 * gl + 16) = b1;
-            }
-            __builtin_amdgcn_s_waitcnt(0xc07f); // this wave's LDS writes have landed (the lanes of a group run in lockstep)
-            __builtin_amdgcn_wave_barrier();
-            // 12 bytes from byte o of a right-band row: four aligned words, shifted
-            auto window = [&](int row, int o, uint32_t (&w)[3]) {
-                const uint32_t *q = (const uint32_t *)(wr + 32 * row + (o & ~3));
-                const uint32_t q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-                const unsigned sh = (unsigned)(o & 3);
-                w[0] = __builtin_amdgcn_alignbyte(q1, q0, sh); w[1] = __builtin_amdgcn_alignbyte(q2, q1, sh); w[2] = __builtin_amdgcn_alignbyte(q3, q2, sh);
-            };
-            const int lc = wl[16 * 5 + 5];
-            // centre row of the right image: bytes cr-5 .. cr+5 (+1 spare) = rc of the 11 shifts
-            uint32_t rcw[3];
-            window(5, 5, rcw);
-            // |(IL - lc) - (IR_i - rc_i)| = |(IL + rc_i) - (IR_i + lc)| for the 11 shifts i: both sides are in [0, 510], so TWO window
-            // pixels per register (16-bit halves, plain 32-bit adds: no carry crosses) and one v_sad_u16 per shift and pixel pair,
-            // which also accumulates: 4 ops per pair and shift (byte pair by v_perm_b32, two adds, the sad) instead of 12.  A
-            // lane's sum over its 8 window pixels is below 4088.
-            const uint32_t lc2 = (uint32_t)lc * 0x10001u;
-            uint32_t rc2[11], acc[11];
-#pragma unroll
-            for (int i = 0; i < 11; i++) {
-                const uint32_t word = rcw[i >> 2];
-                const uint32_t sel = (i & 3) == 0 ? 0x0c000c00u : ((i & 3) == 1 ? 0x0c010c01u : ((i & 3) == 2 ? 0x0c020c02u : 0x0c030c03u));
-                rc2[i] = __builtin_amdgcn_perm(0u, word, sel); // rc_i in both halves
-                acc[i] = 0u;
-            }
-#pragma unroll
-            for (int t = 0; t < 8; t += 2) {
-                const int p0 = gl + SM_G * t, p1 = p0 + SM_G;
-                const int py0 = (p0 * 745) >> 13, px0 = p0 - py0 * 11; // p / 11 for p < 128
-                const int p1c = p1 < 121 ? p1 : p0;                    // only t = 6 of lanes 9 .. 15: masked out below
-                const int py1 = (p1c * 745) >> 13, px1 = p1c - py1 * 11;
-                const uint32_t il2 = (uint32_t)wl[16 * py0 + px0] | ((uint32_t)wl[16 * py1 + px1] << 16);
-                uint32_t w0[3], w1[3];
-                window(py0, px0, w0); // right bytes cr + dx - 5 .. cr + dx + 6, dx = px - 5
-                window(py1, px1, w1);
-                const uint32_t m = p1 < 121 ? 0xffffffffu : 0x0000ffffu;
-#pragma unroll
-                for (int i = 0; i < 11; i++) {
-                    const uint32_t sel = (i & 3) == 0 ? 0x0c040c00u : ((i & 3) == 1 ? 0x0c050c01u : ((i & 3) == 2 ? 0x0c060c02u : 0x0c070c03u));
-                    const uint32_t ir2 = __builtin_amdgcn_perm(w1[i >> 2], w0[i >> 2], sel); // byte i of pixel t | byte i of pixel t + 1 << 16
-                    uint32_t x2 = il2 + rc2[i], y2 = ir2 + lc2;
-                    if (t == 6) { x2 &= m; y2 &= m; }
-                    acc[i] = sad_u16(x2, y2, acc[i]);
-                }
-            }
-            int dists[11];
-#pragma unroll
-            for (int i = 0; i < 11; i++) dists[i] = (int)acc[i];
-            int sad_best = 0x7fffffff, best_inc = 0;
-#pragma unroll
-            for (int i = 0; i < 11; i++) {
-                dists[i] = group_sum_i32(dists[i]);
-                if (dists[i] < sad_best) { sad_best = dists[i]; best_inc = i - 5; }
-            }
-            out_sad = -2 - sad_best; // coarse match without an accepted disparity (debug tap): negative
-            if (best_inc != -5 && best_inc != 5) {
-                float d1 = 0.f, d2 = 0.f, d3 = 0.f;
-#pragma unroll
-                for (int t = 1; t < 10; t++)
-                    if (t == best_inc + 5) { d1 = (float)dists[t - 1]; d2 = (float)dists[t]; d3 = (float)dists[t + 1]; }
-                const float delta = __fdiv_rn(__fsub_rn(d1, d3), __fmul_rn(2.0f, __fsub_rn(__fadd_rn(d1, d3), __fmul_rn(2.0f, d2))));
-                if (!(delta < -1.0f || delta > 1.0f)) {
-                    float best_ur = __fmul_rn(L.scale, __fadd_rn(__fadd_rn(s_uR0, (float)best_inc), delta));
-                    float disparity = __fsub_rn(uL, best_ur);
-                    if (disparity >= 0.0f && disparity < max_d) {
-                        if (disparity <= 0.0f) {
-                            disparity = 0.01f;
-                            best_ur = (float)__dsub_rn((double)uL, 0.01);
-                        }
-                        out_d = __fdiv_rn(cfg.bf, disparity);
-                        out_u = best_ur;
-                        out_sad = sad_best;
+                    for (int u = 0; u < 4; u++) {
+                        const int j = j0 + gl + SM_G * u;
+                        e[u] = rent[j < cnt ? j : cnt - 1];
                     }
                 }
+                int n_pass = 0;
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int j = j0 + gl + SM_G * u;
+                    const int oct = (int)(e[u].x >> 16);
+                    const float xr = __uint_as_float(e[u].y);
+                    ok[u] = j < cnt && oct >= level_l - 1 && oct <= level_l + 1 && xr >= min_u && xr <= max_u;
+                    const unsigned slice = (unsigned)(__ballot(ok[u]) >> gshift) & ((1u << SM_G) - 1u);
+                    if (ok[u]) s_list[n_pass + __popc(slice & ((1u << gl) - 1u))] = e[u];
+                    n_pass += __popc(slice);
+                }
+                __builtin_amdgcn_s_waitcnt(0xc07f); // this wave's LDS writes have landed (the groups of a wave run in lockstep)
+                __builtin_amdgcn_wave_barrier();
+                for (int k = gl; k < n_pass; k += SM_G) {
+                    const uint2 c = s_list[k];
+                    const int iR = (int)(c.x & 0xffffu);
+                    const uint4 *p = (const uint4 *)(dR + (size_t)iR * 32);
+                    const uint4 lo = p[0], hi = p[1];
+                    const uint32_t dr[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+                    const unsigned key = ((unsigned)hamming256(dl, dr) << 16) | (unsigned)iR;
+                    if (key < best) { best = key; best_x = __uint_as_float(c.y); }
+                }
+                __builtin_amdgcn_s_waitcnt(0xc07f);
+                __builtin_amdgcn_wave_barrier(); // the list is rewritten by the next chunk
+            }
+        } else { // the row's list overflowed its capacity: test every right keypoint's band
+            for (int iR = gl; iR < nR; iR += SM_G) {
+                const KeyPointPOD kr = kR[iR];
+                const float r = __fmul_rn(2.0f, cfg.lv[kr.octave].scale);
+                const int maxr = (int)ceilf(__fadd_rn(kr.y, r));
+                const int minr = (int)floorf(__fsub_rn(kr.y, r));
+                if (row >= minr && row <= maxr) consider(iR, kr.octave, kr.x);
             }
         }
+        const unsigned gbest = group_min_u32(best);
+        const int best_dist = (int)(gbest >> 16);
+        // x of the winning candidate: held by the lane whose key won (keys are unique per iR)
+        float uR0 = best == gbest ? best_x : 0.f;
+        {
+            int bits = __float_as_int(uR0);
+#pragma unroll
+            for (int o = SM_G / 2; o > 0; o >>= 1) bits |= __shfl_xor(bits, o, 64); // one lane holds it, the others 0
+            uR0 = __int_as_float(bits);
+        }
+        // the gates in front of the SAD (every lane of a group holds the same values)
+        bool reach = false;
+        int cu = 0, cv = 0, cr = 0;
+        if (best_dist < 75) { // (TH_HIGH + TH_LOW) / 2; never for a keypoint index past the count (no candidate: 100)
+            const float s_uL = roundf(__fmul_rn(kp.x, sf));
+            const float s_vL = roundf(__fmul_rn(kp.y, sf));
+            const float s_uR0 = roundf(__fmul_rn(uR0, sf));
+            cu = (int)s_uL; cv = (int)s_vL; cr = (int)s_uR0;
+            const float iniu = s_uR0;                        // scaleduR0 + L - w
+            const float endu = __fadd_rn(s_uR0, 11.0f);      // scaleduR0 + L + w + 1
+            const bool in_ref = !(iniu < 0 || endu >= (float)lv_w);
+            // the reference would throw on a window outside the level image; unreachable for
+            // keypoints >= 19 px from the border, kept as a memory-safety guard
+            const bool safe = cu - 5 >= 0 && cu + 5 < lv_w && cv - 5 >= 0 && cv + 5 < lv_h && cr - 10 >= 0 && cr + 10 < lv_w;
+            reach = in_ref && safe;
+        }
+        const unsigned long long heads = __ballot(reach && gl == 0);
+        if (gl == 0) {
+            if (reach) { // s_uR0 == (float)cr exactly (an integer-valued float below 2^15); keypoint indices fit 16 bits (row-list entries)
+                uint4 *rec = s_job[wave * 4 + __popcll(heads & ((1ull << lane) - 1ull))];
+                int lpitch;
+                const uint8_t *imL = level_image_at(cfg, buf, imgL, level_l, lv_pitch, lv_off, lpitch); // level 0 may be the caller's packed image
+                const uint8_t *imR = level_image_at(cfg, buf, imgR, level_l, lv_pitch, lv_off, lpitch);
+                const unsigned ro = (unsigned)__mul24(cv - 5, lpitch);
+                const uint64_t pl = (uint64_t)(uintptr_t)(imL + ro + cu - 5), pr = (uint64_t)(uintptr_t)(imR + ro + cr - 10);
+                rec[0] = make_uint4((unsigned)iL | ((unsigned)cr << 16), (unsigned)lpitch, __float_as_uint(lv_scale), __float_as_uint(uL));
+                rec[1] = make_uint4((unsigned)pl, (unsigned)(pl >> 32), (unsigned)pr, (unsigned)(pr >> 32));
+            } else if (valid) {
+                u_right[iL] = -1.0f;
+                depth[iL] = -1.0f;
+                sad_out[iL] = -1;
+            }
+        }
+        wave_jobs = __popcll(heads);
     }
-    if (gl == 0) {
-        u_right[iL] = out_u;
-        depth[iL] = out_d;
-        sad_out[iL] = out_sad;
+    if (lane == 0) s_njob[wave] = wave_jobs;
+    __syncthreads();
+
+    // ---- SAD phase: group `grp` takes job grp of the four segments taken as one list; a wave without a job is done
+    const int c0 = s_njob[0], c1 = s_njob[1], c2 = s_njob[2], c3 = s_njob[3];
+    const int n_jobs = c0 + c1 + c2 + c3;
+    if (grp < n_jobs) {
+        int seg = 0, k = grp;
+        if (k >= c0) { k -= c0; seg = 1; if (k >= c1) { k -= c1; seg = 2; if (k >= c2) { k -= c2; seg = 3; } } }
+        const uint4 job = s_job[seg * 4 + k][0], win = s_job[seg * 4 + k][1];
+        const int iL = (int)(job.x & 0xffffu);
+        const float uL = __uint_as_float(job.w), s_uR0 = (float)(job.x >> 16);
+        const uint8_t *pL = (const uint8_t *)(uintptr_t)((uint64_t)win.x | ((uint64_t)win.y << 32));
+        const uint8_t *pR = (const uint8_t *)(uintptr_t)((uint64_t)win.z | ((uint64_t)win.w << 32));
+        // lane r < 11 fetches row r of the left window (11 bytes from column cu - 5: one unaligned 128-bit load) and of the
+        // right band (21 bytes from column cr - 10: two) and keeps them.  The extra bytes (up to column cu + 10 / cr + 21) lie
+        // in the row's right margin (level 0 read in place: in the first bytes of the next row; the window's last row is >= 14
+        // rows above the image's).
+        uint32_t lw[3] = {0u, 0u, 0u}, rw[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+        if (gl < 11) {
+            const unsigned ro = (unsigned)__mul24(gl, (int)job.y);
+            const uint4 a = load16_unaligned(pL + ro);
+            const uint4 b0 = load16_unaligned(pR + ro), b1 = load16_unaligned(pR + ro + 16);
+            lw[0] = a.x; lw[1] = a.y; lw[2] = a.z;
+            rw[0] = b0.x; rw[1] = b0.y; rw[2] = b0.z; rw[3] = b0.w; rw[4] = b1.x; rw[5] = b1.y;
+        }
+        // centre row (lane 5 of the group): lc = its left byte 5; rc of shift i = its right byte i + 5 (column cr + i - 5)
+        const uint32_t clw = (uint32_t)__shfl((int)lw[1], 5, SM_G);
+        const uint32_t crw[4] = {0u, (uint32_t)__shfl((int)rw[1], 5, SM_G), (uint32_t)__shfl((int)rw[2], 5, SM_G), (uint32_t)__shfl((int)rw[3], 5, SM_G)};
+        // |(IL - lc) - (IR_i - rc_i)| = |(IL + rc_i) - (IR_i + lc)| for the 11 shifts i: both sides are in [0, 510], so TWO window
+        // pixels per register (16-bit halves, plain 32-bit adds: no carry crosses) and one v_sad_u16 per shift and pixel pair,
+        // which also accumulates.  Left pair k = row bytes 2 k, 2 k + 1; band pair j = row bytes j, j + 1 (+ lc in both halves);
+        // shift i sets left pair k against band pair 2 k + i.  A lane's sum over its 11 row pixels is below 5611.
+        const uint32_t lc2 = __builtin_amdgcn_perm(0u, clw, 0x0c010c01u);
+        uint32_t rc2[11], acc[11], A[6], B[21];
+#pragma unroll
+        for (int i = 0; i < 11; i++) {
+            const uint32_t o = (uint32_t)((i + 5) & 3);
+            rc2[i] = __builtin_amdgcn_perm(0u, crw[(i + 5) >> 2], 0x0c000c00u | o | (o << 16)); // rc_i in both halves
+            acc[i] = 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            const uint32_t o = (uint32_t)((2 * k) & 3);
+            A[k] = __builtin_amdgcn_perm(0u, lw[(2 * k) >> 2], k < 5 ? (0x0c000c00u | o | ((o + 1u) << 16)) : (0x0c0c0c00u | o)); // pair 5: pixel 10 alone
+        }
+#pragma unroll
+        for (int j = 0; j < 21; j++) {
+            const uint32_t o = (uint32_t)(j & 3);
+            B[j] = __builtin_amdgcn_perm(rw[(j >> 2) + (j < 20 ? 1 : 0)], rw[j >> 2], 0x0c000c00u | o | ((o + 1u) << 16)) + lc2; // byte 4 = the next word's first
+        }
+#pragma unroll
+        for (int i = 0; i < 11; i++) {
+#pragma unroll
+            for (int k = 0; k < 5; k++) acc[i] = sad_u16(A[k] + rc2[i], B[2 * k + i], acc[i]);
+            // pixel 10 has no partner: the upper half is rc_i on both sides and adds 0
+            acc[i] = sad_u16(A[5] + rc2[i], __builtin_amdgcn_perm(rc2[i], B[10 + i], 0x07060100u), acc[i]);
+        }
+        int dists[11];
+#pragma unroll
+        for (int i = 0; i < 11; i++) dists[i] = gl < 11 ? (int)acc[i] : 0;
+        int sad_best = 0x7fffffff, best_inc = 0;
+#pragma unroll
+        for (int i = 0; i < 11; i++) {
+            dists[i] = group_sum_i32(dists[i]);
+            if (dists[i] < sad_best) { sad_best = dists[i]; best_inc = i - 5; }
+        }
+        float out_u = -1.0f, out_d = -1.0f;
+        int out_sad = -2 - sad_best; // coarse match without an accepted disparity (debug tap): negative
+        if (best_inc != -5 && best_inc != 5) {
+            float d1 = 0.f, d2 = 0.f, d3 = 0.f;
+#pragma unroll
+            for (int t = 1; t < 10; t++)
+                if (t == best_inc + 5) { d1 = (float)dists[t - 1]; d2 = (float)dists[t]; d3 = (float)dists[t + 1]; }
+            const float delta = __fdiv_rn(__fsub_rn(d1, d3), __fmul_rn(2.0f, __fsub_rn(__fadd_rn(d1, d3), __fmul_rn(2.0f, d2))));
+            if (!(delta < -1.0f || delta > 1.0f)) {
+                float best_ur = __fmul_rn(__uint_as_float(job.z), __fadd_rn(__fadd_rn(s_uR0, (float)best_inc), delta));
+                float disparity = __fsub_rn(uL, best_ur);
+                if (disparity >= 0.0f && disparity < max_d) {
+                    if (disparity <= 0.0f) {
+                        disparity = 0.01f;
+                        best_ur = (float)__dsub_rn((double)uL, 0.01);
+                    }
+                    out_d = __fdiv_rn(cfg.bf, disparity);
+                    out_u = best_ur;
+                    out_sad = sad_best;
+                }
+            }
+        }
+        if (gl == 0) {
+            u_right[iL] = out_u;
+            depth[iL] = out_d;
+            sad_out[iL] = out_sad;
+        }
     }
 }
 
@@ -426,7 +465,7 @@ void orbfe_launch_stereo_rowlists(const DeviceConfig &cfg, const DeviceBuffers &
 
 void orbfe_launch_stereo_match(const DeviceConfig &cfg_in, const DeviceBuffers &buf, int n_pairs, hipStream_t s)
 {
-    const int kpb = 256 / SM_G;
+    const int kpb = SM_K;
     DeviceConfig cfg = cfg_in;
     cfg.xcd_magic = xcd_map_magic_host((cfg.sel_total + kpb - 1) / kpb, n_pairs);
     dim3 grid(xcd_grid((cfg.sel_total + kpb - 1) / kpb, n_pairs));
