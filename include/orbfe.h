@@ -19,7 +19,11 @@
  * Environment (read once, by orbfe_create; meant for tests and A/B measurements):
  *   ORBFE_OCTREE=1     force the generic node-parallel DistributeOctTree kernel (the fallback beyond the
  *                      bucket-pyramid kernel's limits) instead of the bucket-pyramid one
- *                      (orbfe_quadtree_kernel() reports the choice);
+ *                      (orbfe_quadtree_kernel() reports the choice), its node tables in LDS: a per-level
+ *                      quota beyond that budget (about 1800 nodes) is refused under this knob;
+ *   ORBFE_OCTREE=2     force the same kernel with its node tables in HBM scratch, for any geometry (what
+ *                      the planner chooses by itself where neither the bucket-pyramid kernel nor the LDS
+ *                      tables fit; orbfe_quadtree_plan() reports it);
  *   ORBFE_NO_TAIL=1|0  never / always run the last three pyramid levels in the fused tail
  *                      kernel (default: for batches of fewer than 64 images; larger
  *                      batches run them as single launches);
@@ -244,6 +248,10 @@ int orbfe_set_streams(orbfe_context *ctx, int groups);
  * 1 = generic node-parallel (chosen at create time from the geometry / LDS limits; 2 was the point-parallel
  * kernel, removed in round 5). */
 int orbfe_quadtree_kernel(const orbfe_context *ctx);
+/* Which form of that kernel the context launches, after the run-time fallbacks of orbfe_create: 0 = bucket pyramid with its node
+ * tables in LDS, 1 = bucket pyramid with node tables in HBM, 2 = generic with node tables in LDS, 3 = generic with node tables in
+ * HBM scratch (any per-level quota up to the keypoint capacity); negative: an ORBFE_ERR_* code. */
+int orbfe_quadtree_plan(const orbfe_context *ctx);
 /* Copy the results of image slot `image` to host.  u_right/depth may be NULL.  The blocking fetch functions
  * (orbfe_fetch_image / _counts / _keys_un / _pyramid / _candidates) first wait for the stream of the latest
  * orbfe_enqueue_* call, so no orbfe_synchronize is needed in between; orbfe_fetch_batch_async does not wait. */

@@ -27,7 +27,7 @@ EXPORTS = [
     "orbfe_stereo_frame", "orbfe_rgbd_frame", "orbfe_rgbd_frame_u16", "orbfe_fetch_pyramid", "orbfe_enqueue_extract",
     "orbfe_enqueue_stereo", "orbfe_synchronize", "orbfe_fetch_image", "orbfe_fetch_counts",
     "orbfe_device_buffers", "orbfe_fetch_candidates", "orbfe_hamming_matrix",
-    "orbfe_set_profiling", "orbfe_stage_name", "orbfe_stage_times", "orbfe_set_streams", "orbfe_quadtree_kernel",
+    "orbfe_set_profiling", "orbfe_stage_name", "orbfe_stage_times", "orbfe_set_streams", "orbfe_quadtree_kernel", "orbfe_quadtree_plan",
     "orbfe_features_in_area", "orbfe_features_in_area_batch", "orbfe_three_maxima", "orbfe_search_by_projection_last", "orbfe_is_in_frustum",
     "orbfe_search_by_projection_points", "orbfe_search_by_projection_kf", "orbfe_search_for_initialization",
     "orbfe_vocab_load", "orbfe_bow_transform", "orbfe_bow_maps", "orbfe_search_by_bow", "orbfe_search_by_bow_kf",  # bound in orbslam2_amd/bow.py
@@ -140,6 +140,7 @@ def load():
     L.orbfe_stage_times.restype = C.c_int; L.orbfe_stage_times.argtypes = [vp, vp, C.POINTER(C.c_int), C.c_int]
     L.orbfe_set_streams.restype = C.c_int; L.orbfe_set_streams.argtypes = [vp, C.c_int]
     L.orbfe_quadtree_kernel.restype = C.c_int; L.orbfe_quadtree_kernel.argtypes = [vp]
+    L.orbfe_quadtree_plan.restype = C.c_int; L.orbfe_quadtree_plan.argtypes = [vp]
     fvp, ip = C.POINTER(FrameView), C.POINTER(C.c_int)
     L.orbfe_features_in_area.restype = C.c_int
     L.orbfe_features_in_area.argtypes = [vp, fvp, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, vp, C.c_int, ip]
@@ -454,6 +455,13 @@ class Context:
 
     def quadtree_kernel(self) -> int:
         return int(self.L.orbfe_quadtree_kernel(self.h))
+
+    def quadtree_plan(self) -> int:
+        """0 / 1: bucket-pyramid kernel with node tables in LDS / HBM; 2 / 3: generic kernel with node tables in LDS / HBM"""
+        rc = int(self.L.orbfe_quadtree_plan(self.h))
+        if rc < 0:
+            self._check(rc)
+        return rc
 
     def set_streams(self, groups: int):
         self._check(self.L.orbfe_set_streams(self.h, groups))

@@ -78,6 +78,7 @@ struct orbfe_context {
     orbfe_match_state *match = nullptr;
     orbfe_bow_state *bow = nullptr;
     orbfe_pose_state *pose = nullptr;
+    hipError_t chain_err = hipSuccess; // a launcher's refusal inside run_chain (enqueue_batch reports it)
     char err[512];
 };
 
@@ -229,7 +230,17 @@ try {
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return fail(nullptr, ORBFE_ERR_NO_DEVICE, "hipStreamCreate failed"); }
     if (hipEventCreateWithFlags(&ctx->ev_latest, hipEventDisableTiming) != hipSuccess) { orbfe_destroy(ctx); return fail(nullptr, ORBFE_ERR_NO_DEVICE, "hipEventCreate failed"); }
     // the one runtime input of the plan: the LDS attribute of the bucket-pyramid quadtree (else the generic kernel, walking the slots)
-    if (ctx->plan.use_octree3 && orbfe_octree3_prepare(ctx->plan.ot3_lds, ctx->plan.ot3_nodes_in_hbm) != 0) { ctx->plan.use_octree3 = false; ctx->cfg.proc_order = 0; }
+    if (ctx->plan.use_octree3 && orbfe_octree3_prepare(ctx->plan.ot3_lds, ctx->plan.ot3_nodes_in_hbm) != 0) {
+        ctx->plan.use_octree3 = false; ctx->cfg.proc_order = 0;
+        // the generic kernel takes over: its LDS tables may not fit where the bucket-pyramid kernel kept its nodes in HBM
+        if (orbfe_octree_lds_bytes(ctx->cfg) > 150 * 1024) { ctx->plan.otg_nodes_in_hbm = true; ctx->plan.otg_scratch_bytes = orbfe_otg_level_off(ctx->cfg, ctx->cfg.nlevels); }
+        for (int l = 0; l < ctx->cfg.nlevels; l++) // the planner's bound on the generic kernel (orbfe_plan.cpp)
+            if (ctx->cfg.lv[l].cand_cap >= (1 << 24)) { orbfe_destroy(ctx); return fail(nullptr, ORBFE_ERR_UNSUPPORTED, "level %d: the bucket-pyramid quadtree kernel could not be prepared and the generic kernel holds fewer than 2^24 candidates per level", l); }
+    }
+    if (!ctx->plan.use_octree3 && orbfe_octree_generic_prepare(ctx->cfg, ctx->plan.otg_nodes_in_hbm) != 0) {
+        // the LDS tables were refused by the runtime: the HBM instantiation needs no attribute
+        ctx->plan.otg_nodes_in_hbm = true; ctx->plan.otg_scratch_bytes = orbfe_otg_level_off(ctx->cfg, ctx->cfg.nlevels);
+    }
     const DeviceConfig &c = ctx->cfg;
     const size_t B = (size_t)p.max_images;
     DeviceBuffers &b = ctx->buf;
@@ -252,6 +263,7 @@ try {
     A(b.bk_end, B * c.nlevels * 4097);
     if (ctx->plan.use_octree3) A(b.bk_best, B * c.nlevels * ORBFE_BK_PYR);
     if (ctx->plan.use_octree3 && ctx->plan.ot3_nodes_in_hbm) A(b.ot3_scratch, B * c.nlevels * orbfe_octree3_node_bytes(c.max_nodes, ctx->plan.ot_sort_cap));
+    if (!ctx->plan.use_octree3 && ctx->plan.otg_nodes_in_hbm) A(b.otg_scratch, B * ctx->plan.otg_scratch_bytes);
     A(b.lvl_ncand, B * c.nlevels); A(b.sel_cnt, B * c.nlevels);
     A(b.sel_xy, B * c.sel_total + 4); // + 4: stereo_rowlist_kernel reads whole quads of slots
     A(b.sel_sc, B * c.sel_total);
@@ -484,6 +496,7 @@ static DeviceBuffers shift_buffers(const DeviceBuffers &b, const DeviceConfig &c
     o.bk_part += i * c.bk_part_total; o.bk_end += i * c.nlevels * 4097;
     if (o.ot3_scratch) o.ot3_scratch += i * c.nlevels * orbfe_octree3_node_bytes(c.max_nodes, orbfe_sort_cap(c.max_nodes));
     if (o.bk_best) o.bk_best += i * c.nlevels * ORBFE_BK_PYR;
+    if (o.otg_scratch) o.otg_scratch += i * orbfe_otg_level_off(c, c.nlevels);
     o.sel_xy += i * c.sel_total; o.sel_sc += i * c.sel_total; o.proc_xy += i * c.sel_total; o.proc_meta += i * c.sel_total;
     o.kps = (KeyPointPOD *)o.kps + i * c.sel_total; o.desc += i * c.sel_total * 32;
     o.kp_cnt += i; o.status += i;
@@ -533,7 +546,7 @@ static void run_chain(orbfe_context *ctx, const uint8_t *d_images, int img0, int
     orbfe_launch_fast(cfg, buf, n_images, ctx->plan.use_octree3, s, ctx->plan.fuse_blur ? blurred : cfg.nlevels);
     prof_mark(ctx, group, 4, s);
     if (ctx->plan.use_octree3) orbfe_launch_octree3(cfg, buf, n_images, ctx->plan.ot_sort_cap, ctx->plan.ot3_lds, ctx->plan.ot3_nodes_in_hbm, s);
-    else orbfe_launch_octree_generic(cfg, buf, n_images, s);
+    else if (const hipError_t e = orbfe_launch_octree_generic(cfg, buf, n_images, ctx->plan.otg_nodes_in_hbm, s)) ctx->chain_err = e;
 #ifdef ORBFE_PROFILE_CUTS
     { // EXPERIMENT: see dbg_sort_sel_kernel (orbfe_describe.hip)
         extern void orbfe_launch_dbg_sort_sel(const DeviceConfig &, const DeviceBuffers &, int, int, hipStream_t);
@@ -579,6 +592,7 @@ static int enqueue_batch(orbfe_context *ctx, const uint8_t *d_images, int n_unit
             u0 += nu;
         }
     }
+    if (ctx->chain_err != hipSuccess) { const hipError_t e = ctx->chain_err; ctx->chain_err = hipSuccess; return fail(ctx, ORBFE_ERR_HIP, "quadtree launch: %s", hipGetErrorString(e)); }
     HIP_TRY(ctx, hipGetLastError());
     ctx->last_src = (ctx->plan.inplace_ok && ctx->cfg.in_cn == 1 && !ctx->cfg.rm_on) ? d_images : nullptr;
     ctx->last_src_owned = ctx->last_src && ctx->last_src == ctx->d_in;
@@ -595,6 +609,13 @@ extern "C" int orbfe_quadtree_kernel(const orbfe_context *ctx)
 try {
     if (!ctx) return 0;
     return ctx->plan.use_octree3 ? 3 : 1;
+} ORBFE_CATCH(nullptr)
+
+extern "C" int orbfe_quadtree_plan(const orbfe_context *ctx)
+try {
+    if (!ctx) return ORBFE_ERR_INVALID;
+    if (ctx->plan.use_octree3) return ctx->plan.ot3_nodes_in_hbm ? 1 : 0;
+    return ctx->plan.otg_nodes_in_hbm ? 3 : 2;
 } ORBFE_CATCH(nullptr)
 
 extern "C" int orbfe_set_streams(orbfe_context *ctx, int groups)

@@ -187,3 +187,21 @@ static inline size_t orbfe_octree_lds_bytes(const DeviceConfig &cfg)
     const size_t node = 2 * sizeof(int) * cap + 4 * sizeof(short) * cap + ((cap + 7) / 8) * 8;
     return sizeof(unsigned long long) * orbfe_sort_cap(cfg.max_nodes) + 2 * node + sizeof(int) * 4 * cap + 4 * sizeof(int) * cap;
 }
+// octree_generic_kernel<true>: the same tables in HBM scratch, one region per (image, level) sized by the level's own node capacity
+// (sel_cap + 1 >= max(quota + 3, 4 * n_ini) + 2 nodes, the bound max_nodes states for the largest level) and the power of two above it
+ORBFE_HD int orbfe_otg_level_cap(const DeviceConfig &cfg, int level) { return cfg.lv[level].sel_cap + 1; }
+ORBFE_HD int orbfe_otg_sort_cap(int cap) { int p = 1; while (p < cap) p <<= 1; return p; }
+ORBFE_HD size_t orbfe_otg_level_bytes(const DeviceConfig &cfg, int level)
+{
+    const size_t cap = (size_t)orbfe_otg_level_cap(cfg, level);
+    const size_t node = 2 * sizeof(int) * cap + 4 * sizeof(short) * cap + ((cap + 7) / 8) * 8;
+    const size_t b = sizeof(unsigned long long) * (size_t)orbfe_otg_sort_cap((int)cap) + 2 * node + sizeof(int) * 4 * cap + 4 * sizeof(int) * cap;
+    return (b + 255) & ~(size_t)255;
+}
+// byte offset of level `level`'s region inside one image's scratch; level == nlevels: the bytes of one image
+ORBFE_HD size_t orbfe_otg_level_off(const DeviceConfig &cfg, int level)
+{
+    size_t off = 0;
+    for (int l = 0; l < level; l++) off += orbfe_otg_level_bytes(cfg, l);
+    return off;
+}

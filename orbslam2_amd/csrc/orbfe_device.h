@@ -83,6 +83,7 @@ struct DeviceBuffers {
     const uint32_t *mom_tab; // [64 lanes][12] byte-dot-product weights of the same patch (hp == 15), see orbfe_plan.cpp
     const uint32_t *pattern; // [256] the extractor's copy of the rBRIEF tests (src/ORBextractor.cc:442-444): x0 | y0 << 8 | x1 << 16 | y1 << 24 as int8;
                              // the compiled bit_pattern_31_ unless orbfe_set_pattern replaced it
+    uint8_t *otg_scratch;    // [img][orbfe_otg_level_off(cfg, nlevels)] node tables of octree_generic_kernel<true>, level after level (else null)
 };
 
 struct KeyPointPOD {
@@ -97,7 +98,10 @@ void orbfe_launch_ingest(const DeviceConfig &cfg, const DeviceBuffers &buf, cons
 int orbfe_launch_pyramid(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_images, bool fuse_blur, hipStream_t s, int ride_from = ORBFE_MAX_LEVELS); // returns the number of levels (from 0) whose blur it launched too
 void orbfe_launch_blur(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_images, int first_level, hipStream_t s);
 void orbfe_launch_fast(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_images, bool buckets, hipStream_t s, int blur_first_level);
-void orbfe_launch_octree_generic(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_images, hipStream_t s);
+// orbfe_octree_generic.hip: nodes_in_hbm selects octree_generic_kernel<true> (node tables in DeviceBuffers::otg_scratch); the error of a
+// refused LDS attribute is returned and nothing is launched
+hipError_t orbfe_launch_octree_generic(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_images, bool nodes_in_hbm, hipStream_t s);
+int orbfe_octree_generic_prepare(const DeviceConfig &cfg, bool nodes_in_hbm);
 // orbfe_octree3.hip
 void orbfe_launch_octree3(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_images, int sort_cap, size_t lds, bool nodes_in_hbm, hipStream_t s);
 void orbfe_launch_candidates_gather(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_images, hipStream_t s);

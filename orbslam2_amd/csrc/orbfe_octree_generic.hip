@@ -2,6 +2,7 @@
 #include "orbfe_common.hpp"
 
 #define OT_THREADS 512
+#define OT_HIST 1024 // roots per pass of the HBM instantiation's LDS root histogram
 
 // ---------------------------------------------------------------------------
 // DistributeOctTree, generic node-parallel kernel (any n_ini; fallback of orbfe_octree3.hip): one workgroup per (image, level)
@@ -32,7 +33,13 @@ __device__ __forceinline__ void ot_bind(OtNodes &n, uint8_t *&p, int cap)
     n.bf = p; p += ((cap + 7) / 8) * 8;
 }
 
-__global__ __launch_bounds__(OT_THREADS) void octree_generic_kernel(DeviceConfig cfg, DeviceBuffers buf, int sort_cap)
+// NODES_IN_HBM: the per-node tables (sort keys, both node arrays, s_ccnt / s_rank / s_plist / s_kk / s_un) live in the (image, level)'s
+// region of DeviceBuffers::otg_scratch instead of dynamic LDS, sized by the level's own capacity (orbfe_otg_level_cap), so the LDS
+// the kernel uses (s_scan, s_hist, the scalars) does not depend on the quota.  The tables are private to the workgroup and handed
+// between its waves at __syncthreads() like idx0 / idx1; the two steps the LDS instantiation leaves to one thread (root emission,
+// first rank that reaches the quota) run block-wide here, since a table may hold up to the keypoint capacity (65535 nodes).
+template <bool NODES_IN_HBM>
+__global__ __launch_bounds__(OT_THREADS) void octree_generic_kernel(DeviceConfig cfg, DeviceBuffers buf, int sort_cap_lds)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_raw[];
     __shared__ int s_scan[OT_THREADS];
@@ -40,9 +47,11 @@ __global__ __launch_bounds__(OT_THREADS) void octree_generic_kernel(DeviceConfig
     const int level = blockIdx.x, img = blockIdx.y;
     const LevelInfo &L = cfg.lv[level];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = OT_THREADS / 64;
-    const int MAXN = cfg.max_nodes;
+    const int MAXN = NODES_IN_HBM ? orbfe_otg_level_cap(cfg, level) : cfg.max_nodes;
+    const int sort_cap = NODES_IN_HBM ? orbfe_otg_sort_cap(MAXN) : sort_cap_lds;
 
     uint8_t *p = s_raw;
+    if constexpr (NODES_IN_HBM) p = buf.otg_scratch + (size_t)img * orbfe_otg_level_off(cfg, cfg.nlevels) + orbfe_otg_level_off(cfg, level);
     unsigned long long *s_key = (unsigned long long *)p; p += sizeof(unsigned long long) * sort_cap;
     OtNodes A, B;
     ot_bind(A, p, MAXN);
@@ -88,33 +97,65 @@ __global__ __launch_bounds__(OT_THREADS) void octree_generic_kernel(DeviceConfig
     // ---- roots: stable partition by int(x / hX) (src/ORBextractor.cc:537-564) ----
     const int n_ini = L.n_ini;
     const int region_h = (L.h - cfg.edge_threshold + 3) - cfg.min_border;
-    for (int i = tid; i < n_ini; i += OT_THREADS) s_kk[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < nc; i += OT_THREADS) {
-        int b = (int)__fdiv_rn((float)(cxy[i] & 0xffffu), L.hx);
-        b = b < 0 ? 0 : (b >= n_ini ? n_ini - 1 : b);
-        atomicAdd(&s_kk[b], 1);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int run = 0, n = 0;
-        for (int b = 0; b < n_ini; b++) {
-            const int c = s_kk[b];
-            s_un[b] = run; // segment begin of bucket b
-            if (c > 0) {
-                A.x0[n] = (short)(int)__fmul_rn(L.hx, (float)b);
-                A.x1[n] = (short)(int)__fmul_rn(L.hx, (float)(b + 1));
-                A.y0[n] = 0;
-                A.y1[n] = (short)region_h;
-                A.beg[n] = run; A.cnt[n] = c; A.bf[n] = 0;
-                n++;
+    if constexpr (NODES_IN_HBM) {
+        // root histogram in LDS, OT_HIST roots at a time (any n_ini), then scans instead of one thread's walk over the roots
+        __shared__ int s_hist[OT_HIST];
+        for (int b0 = 0; b0 < n_ini; b0 += OT_HIST) {
+            for (int i = tid; i < OT_HIST; i += OT_THREADS) s_hist[i] = 0;
+            __syncthreads();
+            for (int i = tid; i < nc; i += OT_THREADS) {
+                int b = (int)__fdiv_rn((float)(cxy[i] & 0xffffu), L.hx);
+                b = b < 0 ? 0 : (b >= n_ini ? n_ini - 1 : b);
+                if (b >= b0 && b < b0 + OT_HIST) atomicAdd(&s_hist[b - b0], 1);
             }
-            run += c;
+            __syncthreads();
+            for (int i = tid; i < OT_HIST && b0 + i < n_ini; i += OT_THREADS) { s_kk[b0 + i] = s_hist[i]; s_rank[b0 + i] = s_hist[i] > 0 ? 1 : 0; }
+            __syncthreads();
         }
-        s_n = n;
-        s_done = 0;
+        block_excl_scan(s_kk, s_un, n_ini, s_scan);                  // s_un[b] = segment begin of bucket b
+        const int n = block_excl_scan(s_rank, s_rank, n_ini, s_scan); // s_rank[b] = node of bucket b (non-empty buckets, in order)
+        for (int b = tid; b < n_ini; b += OT_THREADS) {
+            const int c = s_kk[b];
+            if (c > 0) {
+                const int q = s_rank[b];
+                A.x0[q] = (short)(int)__fmul_rn(L.hx, (float)b);
+                A.x1[q] = (short)(int)__fmul_rn(L.hx, (float)(b + 1));
+                A.y0[q] = 0;
+                A.y1[q] = (short)region_h;
+                A.beg[q] = s_un[b]; A.cnt[q] = c; A.bf[q] = 0;
+            }
+        }
+        if (tid == 0) { s_n = n; s_done = 0; }
+        __syncthreads();
+    } else {
+        for (int i = tid; i < n_ini; i += OT_THREADS) s_kk[i] = 0;
+        __syncthreads();
+        for (int i = tid; i < nc; i += OT_THREADS) {
+            int b = (int)__fdiv_rn((float)(cxy[i] & 0xffffu), L.hx);
+            b = b < 0 ? 0 : (b >= n_ini ? n_ini - 1 : b);
+            atomicAdd(&s_kk[b], 1);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int run = 0, n = 0;
+            for (int b = 0; b < n_ini; b++) {
+                const int c = s_kk[b];
+                s_un[b] = run; // segment begin of bucket b
+                if (c > 0) {
+                    A.x0[n] = (short)(int)__fmul_rn(L.hx, (float)b);
+                    A.x1[n] = (short)(int)__fmul_rn(L.hx, (float)(b + 1));
+                    A.y0[n] = 0;
+                    A.y1[n] = (short)region_h;
+                    A.beg[n] = run; A.cnt[n] = c; A.bf[n] = 0;
+                    n++;
+                }
+                run += c;
+            }
+            s_n = n;
+            s_done = 0;
+        }
+        __syncthreads();
     }
-    __syncthreads();
     for (int b = wave; b < n_ini; b += nwaves) {
         int run = s_un[b];
         for (int i0 = 0; i0 < nc; i0 += 64) {
@@ -196,20 +237,37 @@ __global__ __launch_bounds__(OT_THREADS) void octree_generic_kernel(DeviceConfig
         }
         __syncthreads();
         block_excl_scan(s_kk, s_un, m, s_scan); // s_un[r] = sum of k over ranks < r
-        if (tid == 0) {
-            int nproc = m;
+        if constexpr (NODES_IN_HBM) {
+            // the prefix n + incl - (r + 1) never decreases with r (k >= 1 for a multi-point node), so the first rank that reaches the
+            // quota is the smallest one that does: a block-wide minimum
+            if (tid == 0) s_nproc = m;
+            __syncthreads();
             if (sorted_phase) {
-                // first r with n + sum_{r'<=r}(k-1) >= quota (src/ORBextractor.cc:724-725)
-                nproc = m;
-                for (int r = 0; r < m; r++) {
-                    const int incl = s_un[r] + s_kk[r];
-                    if (n + incl - (r + 1) >= L.quota) { nproc = r + 1; break; }
-                }
+                int first = m;
+                for (int r = tid; r < m; r += OT_THREADS) // ranks ascend per thread: its first hit is its smallest
+                    if (n + s_un[r] + s_kk[r] - (r + 1) >= L.quota) { first = r + 1; break; }
+                first = (int)wave_min_u32((unsigned)first);
+                if (lane == 0 && first < m) atomicMin(&s_nproc, first);
             }
-            s_nproc = nproc;
-            s_total_k = nproc > 0 ? s_un[nproc - 1] + s_kk[nproc - 1] : 0;
+            __syncthreads();
+            if (tid == 0) { const int np = s_nproc; s_total_k = np > 0 ? s_un[np - 1] + s_kk[np - 1] : 0; }
+            __syncthreads();
+        } else {
+            if (tid == 0) {
+                int nproc = m;
+                if (sorted_phase) {
+                    // first r with n + sum_{r'<=r}(k-1) >= quota (src/ORBextractor.cc:724-725)
+                    nproc = m;
+                    for (int r = 0; r < m; r++) {
+                        const int incl = s_un[r] + s_kk[r];
+                        if (n + incl - (r + 1) >= L.quota) { nproc = r + 1; break; }
+                    }
+                }
+                s_nproc = nproc;
+                s_total_k = nproc > 0 ? s_un[nproc - 1] + s_kk[nproc - 1] : 0;
+            }
+            __syncthreads();
         }
-        __syncthreads();
         const int nproc = s_nproc, total_k = s_total_k;
         for (int r = tid; r < nproc; r += OT_THREADS) s_rank[s_plist[r]] = r;
         __syncthreads();
@@ -313,17 +371,30 @@ __global__ __launch_bounds__(OT_THREADS) void octree_generic_kernel(DeviceConfig
 }
 
 
-void orbfe_launch_octree_generic(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_images, hipStream_t s)
+// The LDS instantiation's node tables may exceed the default 64 KB of dynamic LDS (wide-aspect images with large quotas): the
+// attribute is per device, so orbfe_create calls this with the context's device current.  0, or -1 when the runtime refuses it.
+int orbfe_octree_generic_prepare(const DeviceConfig &cfg, bool nodes_in_hbm)
+{
+    if (nodes_in_hbm || orbfe_octree_lds_bytes(cfg) <= 64 * 1024) return 0;
+    return hipFuncSetAttribute((const void *)octree_generic_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess ? 0 : -1;
+}
+
+hipError_t orbfe_launch_octree_generic(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_images, bool nodes_in_hbm, hipStream_t s)
 {
     dim3 grid(cfg.nlevels, n_images);
-    // node tables beyond the default 64 KB of dynamic LDS (wide-aspect images with large quotas); the attribute is per
-    // device, so it is remembered per device ordinal
+    if (nodes_in_hbm) {
+        hipLaunchKernelGGL(octree_generic_kernel<true>, grid, dim3(OT_THREADS), 0, s, cfg, buf, 0);
+        return hipSuccess;
+    }
+    // a context created on another device than the one orbfe_create prepared (the attribute is per device): remembered per device ordinal
     static bool attr_set[64] = {};
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        (void)hipFuncSetAttribute((const void *)octree_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        const hipError_t e = hipFuncSetAttribute((const void *)octree_generic_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        if (e != hipSuccess) return e; // nothing launched: the caller reports it
         attr_set[dev] = true;
     }
-    hipLaunchKernelGGL(octree_generic_kernel, grid, dim3(OT_THREADS), orbfe_octree_lds_bytes(cfg), s, cfg, buf, orbfe_sort_cap(cfg.max_nodes));
+    hipLaunchKernelGGL(octree_generic_kernel<false>, grid, dim3(OT_THREADS), orbfe_octree_lds_bytes(cfg), s, cfg, buf, orbfe_sort_cap(cfg.max_nodes));
+    return hipSuccess;
 }

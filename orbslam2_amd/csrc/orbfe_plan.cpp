@@ -31,7 +31,7 @@ PlanKnobs PlanKnobs::from_env()
     k.pyr_lds = first("ORBFE_PYR_LDS") == '1';
     k.no_fuse = first("ORBFE_NO_FUSE") == '1';
     k.no_proc_order = first("ORBFE_NO_PROC_ORDER") == '1';
-    { const char *v = getenv("ORBFE_OCTREE"); k.octree_generic = v && atoi(v) == 1; }
+    { const char *v = getenv("ORBFE_OCTREE"); k.octree_generic = v && atoi(v) == 1; k.octree_generic_hbm = v && atoi(v) == 2; }
     { const char *v = getenv("ORBFE_BLUR_RIDE_FROM"); if (v && v[0] >= '0' && v[0] <= '9') k.blur_ride_from = atoi(v); }
     k.host_trace = getenv("ORBFE_HOST_TRACE") != nullptr;
     return k;
@@ -233,11 +233,28 @@ int orbfe_build_plan(const orbfe_params &p, int max_images, const PlanKnobs &kno
             }
             P.ot3_nodes_in_hbm = orbfe_octree3_lds_bytes(c.max_nodes, sc, false) > 150 * 1024;
             P.ot3_lds = orbfe_octree3_lds_bytes(c.max_nodes, sc, P.ot3_nodes_in_hbm);
-            // ORBFE_OCTREE=1 (test knob): the generic node-parallel kernel (the fallback beyond the bucket-pyramid kernel's limits)
-            P.use_octree3 = ok3 && P.ot3_lds <= 150 * 1024 && !knobs.octree_generic;
+            // ORBFE_OCTREE=1 (test knob): the generic node-parallel kernel (the fallback beyond the bucket-pyramid kernel's limits) with
+            // its node tables in LDS; ORBFE_OCTREE=2: the same kernel with its node tables in HBM scratch
+            P.use_octree3 = ok3 && P.ot3_lds <= 150 * 1024 && !knobs.octree_generic && !knobs.octree_generic_hbm;
         }
-        if (!P.use_octree3 && orbfe_octree_lds_bytes(c) > 150 * 1024)
-            return plan_fail(err, err_len, ORBFE_ERR_UNSUPPORTED, "nfeatures too large for the quadtree LDS budget");
+        // the generic kernel's node tables: LDS while they fit, else HBM scratch (any quota up to the keypoint capacity); the forced LDS
+        // form of ORBFE_OCTREE=1 refuses instead
+        P.otg_nodes_in_hbm = false; P.otg_scratch_bytes = 0;
+        if (!P.use_octree3) {
+            if (knobs.octree_generic_hbm || (orbfe_octree_lds_bytes(c) > 150 * 1024 && !knobs.octree_generic)) P.otg_nodes_in_hbm = true;
+            else if (orbfe_octree_lds_bytes(c) > 150 * 1024)
+                return plan_fail(err, err_len, ORBFE_ERR_UNSUPPORTED, "nfeatures too large for the quadtree LDS budget");
+            // best response of a node: score << 24 | position inside the node, and a root may hold every candidate of its level
+            for (int l = 0; l < p.nlevels; l++)
+                if (c.lv[l].cand_cap >= (1 << 24))
+                    return plan_fail(err, err_len, ORBFE_ERR_UNSUPPORTED, "level %d: %d candidate slots exceed the 2^24 in-node positions of the generic quadtree kernel", l, c.lv[l].cand_cap);
+        }
+        // scratch of octree_generic_kernel<true>, also what orbfe_create allocates when the bucket-pyramid kernel cannot be prepared
+        // at run time and the LDS tables would not fit
+        if (P.otg_nodes_in_hbm) {
+            P.otg_scratch_bytes = orbfe_otg_level_off(c, c.nlevels);
+            if (knobs.host_trace) fprintf(stderr, "orbfe: generic quadtree kernel: node tables in HBM scratch, %zu bytes per image\n", P.otg_scratch_bytes);
+        }
     }
     // the tables and launch plans of that geometry
     // the XCD-aware block maps divide jb = blockIdx.x / 8 through a float reciprocal that is exact for jb < 2^21 (small_div,

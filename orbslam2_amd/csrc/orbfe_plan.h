@@ -16,7 +16,8 @@ struct PlanKnobs {
     bool pyr_lds = false;       // ORBFE_PYR_LDS=1: LDS-staged resize on every level
     bool no_fuse = false;       // ORBFE_NO_FUSE=1: blur in launches of its own
     bool no_proc_order = false; // ORBFE_NO_PROC_ORDER=1: describe_kernel walks the slots
-    bool octree_generic = false;// ORBFE_OCTREE=1: the generic node-parallel quadtree kernel
+    bool octree_generic = false;// ORBFE_OCTREE=1: the generic node-parallel quadtree kernel, node tables in LDS
+    bool octree_generic_hbm = false; // ORBFE_OCTREE=2: the generic quadtree kernel, node tables in HBM scratch
     int blur_ride_from = -1;    // ORBFE_BLUR_RIDE_FROM=<n>: first level whose blur rides in FAST's launch, for every batch size
     bool host_trace = false;    // ORBFE_HOST_TRACE set: print the plan's choices to stderr
     static PlanKnobs from_env();
@@ -30,6 +31,8 @@ struct LaunchPlan {
     size_t ot3_lds = 0;
     bool ot3_nodes_in_hbm = false; // node tables of the bucket-pyramid quadtree in HBM scratch (large per-level quotas)
     int ot_sort_cap = 0;           // power of two >= max_nodes: the quadtree kernels' sort buffer
+    bool otg_nodes_in_hbm = false; // generic quadtree kernel (use_octree3 false): node tables in HBM scratch (they exceed 150 KB of LDS, or ORBFE_OCTREE=2)
+    size_t otg_scratch_bytes = 0;  // ... and that scratch's bytes per image (orbfe_otg_level_off(cfg, nlevels)), 0 when not used
     bool fuse_blur = true;         // blur level l - 1 in the launch that resizes it into level l (ORBFE_NO_FUSE=1: separate launches)
     // The blur of level l only needs level l, is memory-bound and is first read by describe_kernel: levels >= blur_ride_from are
     // blurred by workgroups that ride in FAST's launch (issue-bound) instead of beside the resize that reads the level, for

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """One-off soak: many random scenes / sizes / thresholds, stereo frame HIP vs oracle, bit for bit.  python3 tools/soak.py [n]
 SOAK_SEED=<int> shifts the case list; SOAK_GEOM=1 also draws the scale factor (1.04-2.3) and the number of levels (1-10); SOAK_PATCH=1 draws half_patch_size 8-18 and the edge
-threshold for every second case."""
+threshold for every second case; SOAK_WIDE=1 draws strips instead (widths up to 2048, heights 100-200, 1-3 levels, up to 6000 features): more than 4
+quadtree roots and large per-level quotas, the generic quadtree kernel with its node tables in LDS or in HBM (the plan counts are printed).
+Refusals by the oracle's constructor and by orbfe_create are counted apart."""
 import os
 import sys
 
@@ -13,12 +15,16 @@ from orbslam2_amd import api, synth  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 100
-bad = 0
+bad = refused_oracle = refused_create = 0
+plans = [0, 0, 0, 0]  # contexts per orbfe_quadtree_plan() value
 for i in range(n):
     rng = np.random.default_rng(int(os.environ.get("SOAK_SEED", "7000")) + i)
     w, h = int(rng.integers(120, 700)), int(rng.integers(100, 420))
     nf = int(rng.integers(50, 2500))
     ini = int(rng.integers(8, 45)); mn = int(rng.integers(3, ini + 1))
+    if os.environ.get("SOAK_WIDE"):  # a generator of its own: the draws of the other modes stay what they were
+        wr = np.random.default_rng(int(os.environ.get("SOAK_SEED", "7000")) + 500000 + i)
+        w, h, nf = int(wr.integers(400, 2049)), int(wr.integers(100, 201)), int(wr.integers(200, 6001))
     left, right = synth.stereo_pair(w, h, seed=int(os.environ.get("SOAK_SEED", "7000")) + 2000 + i)
     if i % 3 == 1:  # low contrast: many cells fall back to minTh
         f = float(rng.uniform(0.05, 0.4))
@@ -48,12 +54,20 @@ for i in range(n):
     if os.environ.get("SOAK_PATCH") and i % 2:  # other patch geometries: describe_generic_kernel + the row-list launch of its own
         hp = int(rng.integers(8, 19)); edge = max(19, hp + 4) + int(rng.integers(0, 4))
         kw.update(half_patch_size=hp, patch_size=2 * hp + 1, edge_threshold=edge)
+    if os.environ.get("SOAK_WIDE"):
+        kw.update(nlevels=int(wr.integers(1, 4)))
     try:
         O.Extractor(**kw)
-        ctx = api.Context(width=w, height=h, fx=fx, fy=fx, cx=w / 2, cy=h / 2, bf=bf, **kw)
-    except (ValueError, api.OrbfeError):
-        skipped = globals().get("skipped", 0) + 1
+    except ValueError:
+        refused_oracle += 1
         continue
+    try:
+        ctx = api.Context(width=w, height=h, fx=fx, fy=fx, cx=w / 2, cy=h / 2, bf=bf, **kw)
+    except api.OrbfeError as e:
+        refused_create += 1
+        print("REFUSED by orbfe_create: case", i, w, h, kw, e)
+        continue
+    plans[ctx.quadtree_plan()] += 1
     exl, exr = O.Extractor(**kw), O.Extractor(**kw)
     if i % 5 == 4:  # round 5: the context's own copy of the rBRIEF table (orbfe_set_pattern), here a random one inside the supported reach
         pat = rng.integers(-13, 14, (256, 4)).astype(np.int32)
@@ -76,5 +90,6 @@ for i in range(n):
         bad += 1
         print("MISMATCH case", i, w, h, kw)
     ctx.close()
-print("soak: %d cases (%d refused by the oracle or orbfe_create), %d mismatches" % (n, globals().get("skipped", 0), bad))
+print("soak: %d cases (%d refused by the oracle's constructor, %d refused by orbfe_create), %d mismatches; quadtree plans 0/1/2/3: %d/%d/%d/%d"
+      % (n, refused_oracle, refused_create, bad, *plans))
 sys.exit(1 if bad else 0)
