@@ -7,7 +7,9 @@
 // 439-440) runs in order on the host over the returned candidate lists.  A candidate is one 64-bit key
 //      dist << 36 | ix << 30 | iy << 24 | idx << 8 | octave
 // so "first minimum in GetFeaturesInArea order" (cell-x major, cell-y, insertion = keypoint index) is
-// simply the smallest key, independent of the order in which the GPU emitted the list.
+// simply the smallest key, independent of the order in which the GPU emitted the list.  The grid (grid_build_kernel behind
+// orbfe_launch_grid_build), the window, its walk, the key and the top-4 selection are the statements of orbfe_match_window.hpp,
+// shared with orbfe_match_device.hip: the two files differ in the resolution, not below it.
 // Projection / frustum arithmetic is host code in the reference's evaluation order (contract Q4: no FMA
 // contraction; cv::Mat 3x3*3x1+t as OpenCV's small-matrix gemm path; PredictScale's log through one
 // deterministic routine).  The candidate machinery (64-bit keys, top-4 prefixes, replays) has no counterpart in the oracle, which
@@ -17,6 +19,7 @@
 #include "orbfe_device.h"
 #include "orbfe_host.h"
 #include "orbfe_match_resolve.h"
+#include "orbfe_match_window.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -34,89 +37,19 @@ static inline bool kf_is_in_image(const orbfe_frame_view *kf, float u, float v)
     if (kf->keyframe) return u >= (float)(int)kf->min_x && u < (float)(int)kf->max_x && v >= (float)(int)kf->min_y && v < (float)(int)kf->max_y;
     return u >= kf->min_x && u < kf->max_x && v >= kf->min_y && v < kf->max_y;
 }
-#define GRID_COLS 64 // FRAME_GRID_COLS include/Frame.h:36
-#define GRID_ROWS 48 // FRAME_GRID_ROWS include/Frame.h:37
 using orbfe_resolve::HISTO_LENGTH;
+using orbfe_resolve::key_dist;
+using orbfe_resolve::key_idx;
+using orbfe_resolve::key_level;
 using orbfe_resolve::TH_HIGH;
 using orbfe_resolve::TH_LOW;
-#define MATCH_TOPK 4       // orbfe_resolve::TOPK
-#define MATCH_TOPK_LDS 256 // candidates per query the top-K selection stages in LDS; longer lists fall back to the full list
+#define MATCH_TOPK 4 // orbfe_resolve::TOPK
 
 using orbfe_resolve::MatchQuery;
-
-struct MatchFrame {
-    const KeyPointPOD *keys; // mvKeysUn
-    const uint8_t *desc;
-    const float *u_right;    // may be null
-    int n;
-    float min_x, min_y, inv_w, inv_h;    // Frame::mnMinX / mnMinY, mfGridElementWidthInv / HeightInv: the grid ASSIGNMENT
-    float q_min_x, q_min_y;              // bounds of the window QUERY: the same, or (float)(int) of them for a KeyFrame (src/KeyFrame.cc:568-580)
-    int *cell_cnt, *cell_off, *cell_idx; // CSR over ix * GRID_ROWS + iy
-};
 
 // ---------------------------------------------------------------------------------------------
 // device
 // ---------------------------------------------------------------------------------------------
-// Frame::AssignFeaturesToGrid / PosInGrid (src/Frame.cc:231-246,383-393; Q6: round(), column 64 dropped)
-__global__ __launch_bounds__(256) void grid_count_kernel(MatchFrame f, int *cell_of)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= f.n) return;
-    const int px = (int)roundf(__fmul_rn(__fsub_rn(f.keys[i].x, f.min_x), f.inv_w));
-    const int py = (int)roundf(__fmul_rn(__fsub_rn(f.keys[i].y, f.min_y), f.inv_h));
-    int c = -1;
-    if (px >= 0 && px < GRID_COLS && py >= 0 && py < GRID_ROWS) {
-        c = px * GRID_ROWS + py;
-        atomicAdd(&f.cell_cnt[c], 1);
-    }
-    cell_of[i] = c;
-}
-
-__global__ __launch_bounds__(1024) void grid_scan_kernel(MatchFrame f)
-{
-    __shared__ int s[1024];
-    const int tid = threadIdx.x;
-    const int per = (GRID_COLS * GRID_ROWS + 1023) / 1024; // 3
-    int sum = 0;
-    for (int k = 0; k < per; k++) {
-        const int c = tid * per + k;
-        if (c < GRID_COLS * GRID_ROWS) sum += f.cell_cnt[c];
-    }
-    s[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int v = tid >= o ? s[tid - o] : 0;
-        __syncthreads();
-        s[tid] += v;
-        __syncthreads();
-    }
-    int run = s[tid] - sum;
-    for (int k = 0; k < per; k++) {
-        const int c = tid * per + k;
-        if (c < GRID_COLS * GRID_ROWS) {
-            const int v = f.cell_cnt[c];
-            f.cell_off[c] = run;
-            f.cell_cnt[c] = run; // becomes the fill cursor
-            run += v;
-        }
-    }
-    if (tid == 1023) f.cell_off[GRID_COLS * GRID_ROWS] = s[1023];
-}
-
-__global__ __launch_bounds__(256) void grid_fill_kernel(MatchFrame f, const int *cell_of)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= f.n) return;
-    const int c = cell_of[i];
-    if (c >= 0) f.cell_idx[atomicAdd(&f.cell_cnt[c], 1)] = i; // order inside a cell is irrelevant (keys carry it)
-}
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ int wave_excl_scan(int v, int lane)
 {
     int inc = v;
@@ -131,45 +64,21 @@ __device__ __forceinline__ int wave_excl_scan(int v, int lane)
 // One wave per query: Frame::GetFeaturesInArea + DescriptorDistance of every hit.
 // With topk != null the wave also selects the MATCH_TOPK smallest keys that pass the call's STATIC filters (blocked0[idx] == 0;
 // gate_drop: dist < 256) and reports how many passed: the host replays the greedy rules on that prefix (orbfe_match_resolve.h).
-__global__ __launch_bounds__(256) void window_candidates_kernel(MatchFrame f, const MatchQuery *__restrict__ q, const uint8_t *__restrict__ qdesc,
+__global__ __launch_bounds__(256) void window_candidates_kernel(GridFrame f, const MatchQuery *__restrict__ q, const uint8_t *__restrict__ qdesc,
                                                                 int nq, int *__restrict__ q_off, int *__restrict__ q_cnt,
                                                                 unsigned long long *__restrict__ list, int *__restrict__ cursor, int list_cap,
                                                                 unsigned long long *__restrict__ topk, int *__restrict__ n_static,
                                                                 const uint8_t *__restrict__ blocked0, int gate_drop)
 {
-    __shared__ unsigned long long s_keys[4][MATCH_TOPK_LDS];
     const int iq = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (iq >= nq) return;
     const MatchQuery Q = q[iq];
-    int total = 0, ncx = 0, ncy = 0, min_cx = 0, min_cy = 0;
-    if (Q.flags & 1) {
-        int v = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(Q.u, f.q_min_x), Q.r), f.inv_w));
-        min_cx = v > 0 ? v : 0;
-        v = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(Q.u, f.q_min_x), Q.r), f.inv_w));
-        const int max_cx = v < GRID_COLS - 1 ? v : GRID_COLS - 1;
-        v = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(Q.v, f.q_min_y), Q.r), f.inv_h));
-        min_cy = v > 0 ? v : 0;
-        v = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(Q.v, f.q_min_y), Q.r), f.inv_h));
-        const int max_cy = v < GRID_ROWS - 1 ? v : GRID_ROWS - 1;
-        if (min_cx < GRID_COLS && max_cx >= 0 && min_cy < GRID_ROWS && max_cy >= 0) {
-            ncx = max_cx - min_cx + 1;
-            ncy = max_cy - min_cy + 1;
-        }
-    }
-    const int ncells = ncx > 0 && ncy > 0 ? ncx * ncy : 0;
-    const bool check_levels = (Q.min_level > 0) || (Q.max_level >= 0); // Q5, literally
-    // pass 1: count hits per lane (lane owns cells lane, lane + 64, ...)
+    const Window w = query_window(f, Q);
+    // pass 1: count hits per lane
     int mine = 0;
-    for (int c = lane; c < ncells; c += 64) {
-        const int cell = (min_cx + c / ncy) * GRID_ROWS + (min_cy + c % ncy);
-        for (int j = f.cell_off[cell]; j < f.cell_off[cell + 1]; j++) {
-            const KeyPointPOD kp = f.keys[f.cell_idx[j]];
-            if (check_levels && (kp.octave < Q.min_level || (Q.max_level >= 0 && kp.octave > Q.max_level))) continue;
-            if (fabsf(__fsub_rn(kp.x, Q.u)) < Q.r && fabsf(__fsub_rn(kp.y, Q.v)) < Q.r) mine++;
-        }
-    }
-    total = wave_sum(mine);
+    for_each_hit(f, Q, w, lane, [&](int, int, int, const KeyPointPOD &) { mine++; });
+    const int total = wave_sum_i32(mine);
     int base = 0;
     if (lane == 0) {
         base = total > 0 ? atomicAdd(cursor, total) : 0;
@@ -178,75 +87,32 @@ __global__ __launch_bounds__(256) void window_candidates_kernel(MatchFrame f, co
     }
     base = __shfl(base, 0, 64);
     if (topk && (total == 0 || base + total > list_cap)) { // nothing (or nothing usable): an empty prefix, the host re-runs on overflow
-        if (lane < MATCH_TOPK) topk[(size_t)iq * MATCH_TOPK + lane] = ~0ull;
+        if (lane < MATCH_TOPK) topk[(size_t)iq * MATCH_TOPK + lane] = NO_KEY;
         if (lane == 0) n_static[iq] = 0;
     }
     if (total == 0 || base + total > list_cap) return;
-    const int rel0 = wave_excl_scan(mine, lane);
-    int pos = base + rel0;
-    unsigned long long *sk = s_keys[threadIdx.x >> 6];
-    const bool stage = topk && total <= MATCH_TOPK_LDS;
-    int rel = rel0;
+    // pass 2: every lane writes its keys behind those of the lanes before it, and keeps its four smallest admissible ones
+    int pos = base + wave_excl_scan(mine, lane);
     uint32_t qd[8];
     {
         const uint32_t *p = (const uint32_t *)(qdesc + (size_t)iq * 32);
 #pragma unroll
         for (int k = 0; k < 8; k++) qd[k] = p[k];
     }
-    for (int c = lane; c < ncells; c += 64) {
-        const int ix = min_cx + c / ncy, iy = min_cy + c % ncy;
-        const int cell = ix * GRID_ROWS + iy;
-        for (int j = f.cell_off[cell]; j < f.cell_off[cell + 1]; j++) {
-            const int idx = f.cell_idx[j];
-            const KeyPointPOD kp = f.keys[idx];
-            if (check_levels && (kp.octave < Q.min_level || (Q.max_level >= 0 && kp.octave > Q.max_level))) continue;
-            if (!(fabsf(__fsub_rn(kp.x, Q.u)) < Q.r && fabsf(__fsub_rn(kp.y, Q.v)) < Q.r)) continue;
-            unsigned dist = 0;
-            const uint32_t *p = (const uint32_t *)(f.desc + (size_t)idx * 32);
-#pragma unroll
-            for (int k = 0; k < 8; k++) dist += __popc(qd[k] ^ p[k]);
-            // the mvuRight gate (src/ORBmatcher.cc:93-98,1403-1409) is a pure function of the pair: mark it
-            if ((Q.flags & 2) && f.u_right && f.u_right[idx] > 0 && fabsf(__fsub_rn(Q.ur, f.u_right[idx])) > Q.ur_rad) dist = 511;
-            const unsigned long long key = ((unsigned long long)dist << 36) | ((unsigned long long)ix << 30) | ((unsigned long long)iy << 24) |
-                                           ((unsigned long long)idx << 8) | (unsigned long long)(kp.octave & 255);
-            list[pos++] = key;
-            if (stage) sk[rel++] = ((gate_drop && dist >= 256) || (blocked0 && blocked0[idx])) ? ~0ull : key; // static filters
-        }
-    }
-    if (!topk) return;
-    if (!stage) { // too long for the LDS stage: the host takes this query from the full list
-        if (lane < MATCH_TOPK) topk[(size_t)iq * MATCH_TOPK + lane] = ~0ull;
-        if (lane == 0) n_static[iq] = INT_MAX;
-        return;
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-    // each lane owns keys lane, lane + 64, ...; MATCH_TOPK rounds of (lane minimum, wave minimum, owner retires its key)
-    unsigned long long mykeys[MATCH_TOPK_LDS / 64];
+    Top4 top;
     int passed = 0;
-#pragma unroll
-    for (int j = 0; j < MATCH_TOPK_LDS / 64; j++) {
-        mykeys[j] = (lane + 64 * j < total) ? sk[lane + 64 * j] : ~0ull;
-        passed += mykeys[j] != ~0ull;
-    }
-    passed = wave_sum(passed);
+    for_each_hit(f, Q, w, lane, [&](int ix, int iy, int idx, const KeyPointPOD &kp) {
+        const unsigned long long key = candidate_key(f, Q, qd, ix, iy, idx, kp);
+        list[pos++] = key;
+        if (!topk || (gate_drop && key_dist(key) >= 256) || (blocked0 && blocked0[idx])) return; // static filters
+        passed++;
+        top.insert(key);
+    });
+    if (!topk) return;
+    passed = wave_sum_i32(passed);
     for (int r = 0; r < MATCH_TOPK; r++) {
-        unsigned long long m = mykeys[0];
-#pragma unroll
-        for (int j = 1; j < MATCH_TOPK_LDS / 64; j++) m = mykeys[j] < m ? mykeys[j] : m;
-        unsigned long long w = m;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)w, o, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(w >> 32), o, 64);
-            const unsigned long long t = ((unsigned long long)hi << 32) | lo;
-            w = t < w ? t : w;
-        }
-        if (lane == 0) topk[(size_t)iq * MATCH_TOPK + r] = w;
-        if (w != ~0ull) { // keys are unique within a query (they carry the keypoint index): exactly one lane retires it
-#pragma unroll
-            for (int j = 0; j < MATCH_TOPK_LDS / 64; j++)
-                if (mykeys[j] == w) mykeys[j] = ~0ull;
-        }
+        const unsigned long long m = top.pop_wave_min();
+        if (lane == 0) topk[(size_t)iq * MATCH_TOPK + r] = m;
     }
     if (lane == 0) n_static[iq] = passed;
 }
@@ -255,7 +121,7 @@ __global__ __launch_bounds__(256) void window_candidates_kernel(MatchFrame f, co
 // host: device session for one frame + candidate query
 // ---------------------------------------------------------------------------------------------
 struct orbfe_match_state {
-    DevBuf in_blk, out_blk, cells, cell_of, list, keys_un; // inputs of a call in one block (one pinned copy up), results in another
+    DevBuf in_blk, out_blk, cells, list, keys_un; // inputs of a call in one block (one pinned copy up), results in another
     uint8_t *h_in = nullptr, *h_out = nullptr;               // pinned images of in_blk / out_blk
     size_t h_in_bytes = 0, h_out_bytes = 0;
     std::vector<int> h_off, h_cnt, h_nstatic;
@@ -311,7 +177,6 @@ static int run_window_queries(orbfe_context *ctx, const orbfe_frame_view *fv, co
     if (n <= 0 || nq == 0) return ORBFE_OK;
     if (n > 65535) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "frames with more than 65535 keypoints are not supported by the matchers");
     MTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
-    const size_t ncell = GRID_COLS * GRID_ROWS;
     const bool resident = fv->device_slot_plus1 > 0;
     const int slot = fv->device_slot_plus1 - 1;
     const DeviceConfig *cfg = orbfe_ctx_config(ctx);
@@ -336,21 +201,21 @@ static int run_window_queries(orbfe_context *ctx, const orbfe_frame_view *fv, co
     const size_t o_cur = 0, o_ns = 16, o_tk = up16(o_ns + sizeof(int) * nq), o_off = up16(o_tk + sizeof(unsigned long long) * MATCH_TOPK * nq);
     const size_t o_cnt = up16(o_off + sizeof(int) * nq), out_bytes = up16(o_cnt + sizeof(int) * nq);
     const size_t topk_bytes = o_off; // prefix of the result block a top-K replay downloads
-    if (st->in_blk.ensure(in_bytes) || st->out_blk.ensure(out_bytes) || st->cells.ensure(sizeof(int) * (2 * ncell + 2 + cfg->sel_total + n)) ||
-        st->cell_of.ensure(sizeof(int) * (size_t)(n > cfg->sel_total ? n : cfg->sel_total)))
+    if (st->in_blk.ensure(in_bytes) || st->out_blk.ensure(out_bytes) || st->cells.ensure(sizeof(int) * (size_t)(GRID_CELLS + 1 + n)))
         return orbfe_fail(ctx, ORBFE_ERR_HIP, "matcher scratch allocation failed");
     int rc = ensure_pinned(ctx, st->h_in, st->h_in_bytes, in_bytes);
     if (rc != ORBFE_OK) return rc;
     rc = ensure_pinned(ctx, st->h_out, st->h_out_bytes, out_bytes);
     if (rc != ORBFE_OK) return rc;
     uint8_t *din = (uint8_t *)st->in_blk.p, *dout = (uint8_t *)st->out_blk.p;
-    MatchFrame f;
-    f.n = n; f.min_x = fv->min_x; f.min_y = fv->min_y;
+    GridFrame f;
+    f.n_ptr = nullptr; f.cap = n; // the host knows the count of the frame it uploads, and of the slot it has just checked
+    f.min_x = fv->min_x; f.min_y = fv->min_y;
     f.q_min_x = fv->keyframe ? (float)(int)fv->min_x : fv->min_x; // KeyFrame::mnMinX is an int initialised from the frame's float
     f.q_min_y = fv->keyframe ? (float)(int)fv->min_y : fv->min_y;
     f.inv_w = (float)GRID_COLS / (fv->max_x - fv->min_x); // mfGridElementWidthInv, src/Frame.cc:99
     f.inv_h = (float)GRID_ROWS / (fv->max_y - fv->min_y);
-    f.cell_cnt = (int *)st->cells.p; f.cell_off = f.cell_cnt + ncell; f.cell_idx = f.cell_off + ncell + 1;
+    f.cell_off = (int *)st->cells.p; f.cell_idx = f.cell_off + GRID_CELLS + 1;
     bool build_grid = true;
     if (resident) {
         const size_t so = (size_t)slot * cfg->sel_total;
@@ -382,12 +247,7 @@ static int run_window_queries(orbfe_context *ctx, const orbfe_frame_view *fv, co
     memcpy(st->h_in + i_qd, qdesc.data(), (size_t)32 * nq);
     if (topk && topk->blocked0) memcpy(st->h_in + i_blk, topk->blocked0, (size_t)n);
     MTRY(ctx, hipMemcpyAsync(din, st->h_in, in_bytes, hipMemcpyHostToDevice, s));
-    if (build_grid) {
-        MTRY(ctx, hipMemsetAsync(f.cell_cnt, 0, sizeof(int) * ncell, s));
-        hipLaunchKernelGGL(grid_count_kernel, dim3((n + 255) / 256), dim3(256), 0, s, f, (int *)st->cell_of.p);
-        hipLaunchKernelGGL(grid_scan_kernel, dim3(1), dim3(1024), 0, s, f);
-        hipLaunchKernelGGL(grid_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, s, f, (const int *)st->cell_of.p);
-    }
+    if (build_grid) orbfe_launch_grid_build(f, s);
     // candidate list capacity: grown and the query re-run if a frame overflows it
     size_t cap = st->list.bytes / 8;
     if (cap < (size_t)nq * 64) cap = (size_t)nq * 64;
@@ -456,10 +316,6 @@ static orbfe_resolve::CandidateSource topk_source(orbfe_match_state *st, FullLis
     return src;
 }
 
-using orbfe_resolve::key_dist;
-using orbfe_resolve::key_idx;
-using orbfe_resolve::key_level;
-
 using orbfe_resolve::camera_center;
 using orbfe_resolve::predict_scale;
 using orbfe_resolve::rt_apply;
@@ -505,14 +361,14 @@ try {
 } ORBFE_CATCH(ctx)
 
 // Frame::AssignFeaturesToGrid (src/Frame.cc:231-246): mGrid as CSR.  The grid is the one every matcher call on this frame uses
-// (built by the same kernels; for a device-resident frame it stays cached for the calls that follow).
+// (built by the same kernel; for a device-resident frame it stays cached for the calls that follow).
 extern "C" int orbfe_assign_features_to_grid(orbfe_context *ctx, const orbfe_frame_view *fv, int32_t *cell_off, int32_t *cell_idx)
 try {
     ORBFE_ENTRY(ctx);
     int rc = check_view(ctx, fv);
     if (rc != ORBFE_OK) return rc;
     if (!cell_off || (fv->n > 0 && !cell_idx)) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
-    const int ncell = GRID_COLS * GRID_ROWS;
+    const int ncell = GRID_CELLS;
     if (fv->n == 0) { memset(cell_off, 0, sizeof(int32_t) * (ncell + 1)); return ORBFE_OK; }
     std::vector<MatchQuery> q(1);
     q[0] = MatchQuery{0.f, 0.f, 0.f, -1, -1, 0.f, 0.f, 0}; // flags 0: no window is searched, the call only builds the grid
@@ -520,12 +376,12 @@ try {
     rc = run_window_queries(ctx, fv, q, qd);
     if (rc != ORBFE_OK) return rc;
     orbfe_match_state *st = match_state(ctx);
-    const int *d_off = (const int *)st->cells.p + ncell;
+    const int *d_off = (const int *)st->cells.p; // GridFrame::cell_off, cell_idx behind it (run_window_queries)
     MTRY(ctx, hipMemcpy(cell_off, d_off, sizeof(int) * (ncell + 1), hipMemcpyDeviceToHost));
     const int total = cell_off[ncell]; // keypoints that fell inside the grid (PosInGrid drops the others)
     if (total < 0 || total > fv->n) return orbfe_fail(ctx, ORBFE_ERR_HIP, "grid holds %d entries for %d keypoints", total, fv->n);
     if (total > 0) MTRY(ctx, hipMemcpy(cell_idx, d_off + ncell + 1, sizeof(int) * total, hipMemcpyDeviceToHost));
-    // the fill kernel claims a cell's slots through an atomic cursor (the matchers order candidates by their keys, not by list
+    // grid_build_kernel claims a cell's slots through an atomic cursor (the matchers order candidates by their keys, not by list
     // position); mGrid[ix][iy] is in push_back order = ascending keypoint index
     for (int c = 0; c < ncell; c++)
         if (cell_off[c + 1] - cell_off[c] > 1) std::sort(cell_idx + cell_off[c], cell_idx + cell_off[c + 1]);

@@ -5,30 +5,29 @@
 // orbfe_match.hip is the synchronous form and the second implementation this one is tested against: there the map points are
 // projected on the host, the four best keys per query come back over the link and orbfe_match_resolve.h replays the accept
 // rules.  Here the same steps are kernels:
-//   grid_build_kernel     Frame::AssignFeaturesToGrid of the slot (its keypoint count read from the extraction's counter)
+//   grid_build_kernel     Frame::AssignFeaturesToGrid in one workgroup, for this path (the slot's keypoint count read from the
+//                         extraction's counter) and, through orbfe_launch_grid_build, for orbfe_match.hip
 //   window_topk_kernel    one wave per map point: its 32-byte MatchQuery (the per-point functions of orbfe_match_resolve.h), then
 //                         GetFeaturesInArea + Hamming distances, the 4 smallest statically admissible keys
 //   frustum_kernel        Frame::isInFrustum, one lane per map point
 //   resolve_kernel        ONE workgroup replays the sequentially greedy accept rules in query order (see there)
 //   gather_kernel         optional has_point / Xw for orbfe_enqueue_pose_optimization
-// Candidate keys are those of orbfe_match.hip: dist << 36 | ix << 30 | iy << 24 | idx << 8 | octave; the smallest key is the
-// reference loop's first minimum.  No candidate list is kept: a query whose four keys are all taken recomputes its window.
+// The grid cell, the window, its walk, the candidate key and the top-4 selection are orbfe_match_window.hpp, shared with
+// orbfe_match.hip; the smallest key is the reference loop's first minimum.  No candidate list is kept: a query whose four keys are
+// all taken recomputes its window.
 #include "../../include/orbfe.h"
 #include "orbfe_device.h"
 #include "orbfe_host.h"
 #include "orbfe_match_resolve.h"
+#include "orbfe_match_window.hpp"
 
 #include <algorithm>
 #include <new>
 #include <vector>
 
-#define GRID_COLS 64 // FRAME_GRID_COLS include/Frame.h:36
-#define GRID_ROWS 48 // FRAME_GRID_ROWS include/Frame.h:37
-#define GRID_CELLS (GRID_COLS * GRID_ROWS)
 #define TOPK 4
 #define RESOLVE_THREADS 512 // queries evaluated per step of the resolve kernel
 #define RESOLVE_CHUNK 1024  // queries staged in LDS at a time
-#define NO_KEY (~0ull)
 #define Q_BAD 4 // MatchQuery::flags bit of the device path: the point's octave / predicted level is out of range
 
 using orbfe_resolve::Camera;
@@ -39,16 +38,6 @@ using orbfe_resolve::key_level;
 using orbfe_resolve::MatchQuery;
 using orbfe_resolve::TH_HIGH;
 
-// the resident frame as the kernels see it
-struct DevFrame {
-    const KeyPointPOD *keys; // mvKeysUn
-    const uint8_t *desc;
-    const float *u_right;    // null: no mvuRight gate
-    const int *n_ptr;        // the slot's keypoint counter (DeviceBuffers::kp_cnt)
-    int cap;                 // keypoint capacity of a slot
-    float min_x, min_y, inv_w, inv_h;
-    int *cell_off, *cell_idx; // CSR over ix * GRID_ROWS + iy
-};
 struct Projection {
     Camera C;
     float sf[ORBFE_MAX_LEVELS];
@@ -57,21 +46,8 @@ struct Projection {
     float min_x, max_x, min_y, max_y;
 };
 
-__device__ __forceinline__ int frame_count(const DevFrame &f)
-{
-    const int n = *f.n_ptr;
-    return n < 0 ? 0 : (n > f.cap ? f.cap : n);
-}
-// Frame::PosInGrid (src/Frame.cc:383-393; Q6: round(), column 64 dropped), as grid_count_kernel of orbfe_match.hip
-__device__ __forceinline__ int grid_cell(const DevFrame &f, int i)
-{
-    const int px = (int)roundf(__fmul_rn(__fsub_rn(f.keys[i].x, f.min_x), f.inv_w));
-    const int py = (int)roundf(__fmul_rn(__fsub_rn(f.keys[i].y, f.min_y), f.inv_h));
-    return (px >= 0 && px < GRID_COLS && py >= 0 && py < GRID_ROWS) ? px * GRID_ROWS + py : -1;
-}
-
 // Frame::AssignFeaturesToGrid in one workgroup: count, scan and fill over LDS counters
-__global__ __launch_bounds__(1024) void grid_build_kernel(DevFrame f)
+__global__ __launch_bounds__(1024) void grid_build_kernel(GridFrame f)
 {
     __shared__ int s_cnt[GRID_CELLS];
     __shared__ int s_scan[1024];
@@ -160,80 +136,12 @@ __global__ __launch_bounds__(256) void frustum_kernel(Projection P, const float 
 }
 
 // ---- window query ----
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long w)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)w, o, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(w >> 32), o, 64);
-        const unsigned long long t = ((unsigned long long)hi << 32) | lo;
-        w = t < w ? t : w;
-    }
-    return w;
-}
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// The cells of a query's window (Frame::GetFeaturesInArea, src/Frame.cc:328-381); the arithmetic of window_candidates_kernel
-struct Window { int min_cx, min_cy, ncy, ncells; };
-__device__ __forceinline__ Window query_window(const DevFrame &f, const MatchQuery &Q)
-{
-    Window w = {0, 0, 1, 0};
-    if (!(Q.flags & 1)) return w;
-    int v = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(Q.u, f.min_x), Q.r), f.inv_w));
-    w.min_cx = v > 0 ? v : 0;
-    v = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(Q.u, f.min_x), Q.r), f.inv_w));
-    const int max_cx = v < GRID_COLS - 1 ? v : GRID_COLS - 1;
-    v = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(Q.v, f.min_y), Q.r), f.inv_h));
-    w.min_cy = v > 0 ? v : 0;
-    v = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(Q.v, f.min_y), Q.r), f.inv_h));
-    const int max_cy = v < GRID_ROWS - 1 ? v : GRID_ROWS - 1;
-    if (w.min_cx < GRID_COLS && max_cx >= 0 && w.min_cy < GRID_ROWS && max_cy >= 0 && max_cx >= w.min_cx && max_cy >= w.min_cy) {
-        w.ncy = max_cy - w.min_cy + 1;
-        w.ncells = (max_cx - w.min_cx + 1) * w.ncy;
-    }
-    return w;
-}
-
-// Calls emit(key, idx) for every keypoint of the window this lane owns (cells lane, lane + 64, ...) that passes the level and
-// radius tests, with the Hamming distance to the query descriptor in the key (511: failed the mvuRight gate).
-template <class Emit>
-__device__ __forceinline__ void scan_window(const DevFrame &f, const MatchQuery &Q, const Window &w, const uint32_t *__restrict__ qdesc, int lane, Emit emit)
-{
-    const bool check_levels = (Q.min_level > 0) || (Q.max_level >= 0); // Q5, literally
-    uint32_t qd[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) qd[k] = qdesc[k];
-    for (int c = lane; c < w.ncells; c += 64) {
-        const int ix = w.min_cx + c / w.ncy, iy = w.min_cy + c % w.ncy;
-        const int cell = ix * GRID_ROWS + iy;
-        for (int j = f.cell_off[cell]; j < f.cell_off[cell + 1]; j++) {
-            const int idx = f.cell_idx[j];
-            const KeyPointPOD kp = f.keys[idx];
-            if (check_levels && (kp.octave < Q.min_level || (Q.max_level >= 0 && kp.octave > Q.max_level))) continue;
-            if (!(fabsf(__fsub_rn(kp.x, Q.u)) < Q.r && fabsf(__fsub_rn(kp.y, Q.v)) < Q.r)) continue;
-            unsigned dist = 0;
-            const uint32_t *p = (const uint32_t *)(f.desc + (size_t)idx * 32);
-#pragma unroll
-            for (int k = 0; k < 8; k++) dist += __popc(qd[k] ^ p[k]);
-            // the mvuRight gate (src/ORBmatcher.cc:93-98,1403-1409) is a pure function of the pair: mark it
-            if ((Q.flags & 2) && f.u_right && f.u_right[idx] > 0 && fabsf(__fsub_rn(Q.ur, f.u_right[idx])) > Q.ur_rad) dist = 511;
-            emit(((unsigned long long)dist << 36) | ((unsigned long long)ix << 30) | ((unsigned long long)iy << 24) | ((unsigned long long)idx << 8) |
-                     (unsigned long long)(kp.octave & 255),
-                 idx);
-        }
-    }
-}
-
 // One wave per query: the map point is projected into its MatchQuery (kept in q[] for the resolve kernel's re-scans), then every
 // lane keeps the TOPK smallest admissible keys of its own cells in registers and the wave merges them: any window size, no staging.
 // n_static = how many keys passed the static filters, -1 for a Q_BAD query.  The threads below the frame's keypoint count also
 // reset cur_match (the launch covers the keypoint capacity).
 template <class Source>
-__global__ __launch_bounds__(256) void window_topk_kernel(DevFrame f, Source src, MatchQuery *__restrict__ q, const uint8_t *__restrict__ qdesc, int nq,
+__global__ __launch_bounds__(256) void window_topk_kernel(GridFrame f, Source src, MatchQuery *__restrict__ q, const uint8_t *__restrict__ qdesc, int nq,
                                                           const uint8_t *__restrict__ blocked0, unsigned long long *__restrict__ topk,
                                                           int *__restrict__ n_static, int32_t *__restrict__ cur_match)
 {
@@ -245,31 +153,25 @@ __global__ __launch_bounds__(256) void window_topk_kernel(DevFrame f, Source src
     const MatchQuery Q = src.query(iq);
     if (lane == 0) q[iq] = Q;
     const Window w = query_window(f, Q);
-    unsigned long long t0 = NO_KEY, t1 = NO_KEY, t2 = NO_KEY, t3 = NO_KEY;
+    Top4 top;
     int passed = 0;
     if (w.ncells > 0)
         scan_window(f, Q, w, (const uint32_t *)(qdesc + (size_t)iq * 32), lane, [&](unsigned long long key, int idx) {
             if (key_dist(key) >= 256 || (blocked0 && blocked0[idx])) return; // static filters
             passed++;
-            if (key < t3) {
-                t3 = key;
-                if (t3 < t2) { const unsigned long long x = t2; t2 = t3; t3 = x; }
-                if (t2 < t1) { const unsigned long long x = t1; t1 = t2; t2 = x; }
-                if (t1 < t0) { const unsigned long long x = t0; t0 = t1; t1 = x; }
-            }
+            top.insert(key);
         });
-    passed = wave_sum_i(passed);
+    passed = wave_sum_i32(passed);
     for (int r = 0; r < TOPK; r++) {
-        const unsigned long long m = wave_min_u64(t0);
+        const unsigned long long m = top.pop_wave_min();
         if (lane == 0) topk[(size_t)iq * TOPK + r] = m;
-        if (m != NO_KEY && t0 == m) { t0 = t1; t1 = t2; t2 = t3; t3 = NO_KEY; } // keys are unique within a query: one lane retires it
     }
     if (lane == 0) n_static[iq] = (Q.flags & Q_BAD) ? -1 : passed;
 }
 
 // ---- resolve ----
 struct ResolveArgs {
-    DevFrame f;
+    GridFrame f;
     const MatchQuery *q;
     const uint8_t *qdesc;
     int nq;
@@ -478,7 +380,7 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void resolve_kernel(ResolveArgs a)
 static_assert(RESOLVE_CHUNK % RESOLVE_THREADS == 0, "resolve_kernel: the thread that stores an event of a chunk reads it back in the last pass");
 
 // mvpMapPoints of the matched keypoints as orbfe_enqueue_pose_optimization reads them
-__global__ __launch_bounds__(256) void gather_kernel(DevFrame f, const int32_t *__restrict__ cur_match, const float *__restrict__ pos,
+__global__ __launch_bounds__(256) void gather_kernel(GridFrame f, const int32_t *__restrict__ cur_match, const float *__restrict__ pos,
                                                      uint8_t *__restrict__ has_point, float *__restrict__ Xw)
 {
     const int k = blockIdx.x * 256 + threadIdx.x;
@@ -507,6 +409,7 @@ struct orbfe_match_device_state {
 };
 orbfe_match_device_state **orbfe_match_device_slot(orbfe_match_state *s); // orbfe_match.hip
 void orbfe_match_device_state_destroy(orbfe_match_device_state *s) { delete s; }
+void orbfe_launch_grid_build(const GridFrame &f, hipStream_t s) { hipLaunchKernelGGL(grid_build_kernel, dim3(1), dim3(1024), 0, s, f); }
 orbfe_match_device_state *orbfe_ctx_match_device_state(orbfe_context *ctx)
 {
     orbfe_match_state *ms = orbfe_ctx_match_state(ctx);
@@ -570,7 +473,7 @@ static int resident_frame(orbfe_context *ctx, int slot, hipStream_t s, orbfe_mat
 }
 
 // the slot as the kernels read it, its grid built if this is the first call on this frame with these bounds
-static int resident_grid(orbfe_context *ctx, int slot, const float *bounds, bool stereo, hipStream_t s, orbfe_match_device_state *&st, DevFrame &f)
+static int resident_grid(orbfe_context *ctx, int slot, const float *bounds, bool stereo, hipStream_t s, orbfe_match_device_state *&st, GridFrame &f)
 {
     const DeviceConfig *cfg = orbfe_ctx_config(ctx);
     const DeviceBuffers *buf = orbfe_ctx_buffers(ctx);
@@ -585,14 +488,14 @@ static int resident_grid(orbfe_context *ctx, int slot, const float *bounds, bool
     f.u_right = stereo ? buf->u_right + so : nullptr;
     f.n_ptr = buf->kp_cnt + slot;
     f.cap = cfg->sel_total;
-    f.min_x = bounds[0]; f.min_y = bounds[2];
+    f.min_x = f.q_min_x = bounds[0]; f.min_y = f.q_min_y = bounds[2];
     f.inv_w = (float)GRID_COLS / (bounds[1] - bounds[0]); // mfGridElementWidthInv, src/Frame.cc:99
     f.inv_h = (float)GRID_ROWS / (bounds[3] - bounds[2]);
     f.cell_off = (int *)st->cells.p; f.cell_idx = f.cell_off + GRID_CELLS + 1;
     const unsigned epoch = orbfe_ctx_epoch(ctx);
     if (!(st->grid_epoch == epoch && st->grid_slot == slot && st->grid_keys == (const void *)f.keys && st->grid_bounds[0] == bounds[0] && st->grid_bounds[1] == bounds[1] &&
           st->grid_bounds[2] == bounds[2] && st->grid_bounds[3] == bounds[3])) {
-        hipLaunchKernelGGL(grid_build_kernel, dim3(1), dim3(1024), 0, s, f);
+        orbfe_launch_grid_build(f, s);
         st->grid_epoch = epoch; st->grid_slot = slot; st->grid_keys = f.keys;
         for (int k = 0; k < 4; k++) st->grid_bounds[k] = bounds[k];
     }
@@ -610,7 +513,7 @@ static int ensure_query_scratch(orbfe_context *ctx, orbfe_match_device_state *st
 
 // window query, resolution and the optional gather: what the two matchers share once their queries are written
 template <class Source>
-static int enqueue_window_resolve(orbfe_context *ctx, orbfe_match_device_state *st, const DevFrame &f, const Source &src, int nq, const uint8_t *d_qdesc, const int32_t *d_obs,
+static int enqueue_window_resolve(orbfe_context *ctx, orbfe_match_device_state *st, const GridFrame &f, const Source &src, int nq, const uint8_t *d_qdesc, const int32_t *d_obs,
                                   const float *d_angle, const uint8_t *d_blocked0, int points, int check_ori, float nnratio, const float *d_pos,
                                   int32_t *d_cur_match, int32_t *d_nmatches, int32_t *d_status, uint8_t *d_has_point, float *d_Xw, hipStream_t s)
 {
@@ -644,7 +547,7 @@ try {
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
     hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
     orbfe_match_device_state *st = nullptr;
-    DevFrame f;
+    GridFrame f;
     int rc = resident_grid(ctx, slot, bounds, !mono, s, st, f);
     if (rc != ORBFE_OK) return rc;
     rc = ensure_query_scratch(ctx, st, n_last);
@@ -682,7 +585,7 @@ try {
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
     hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
     orbfe_match_device_state *st = nullptr;
-    DevFrame f;
+    GridFrame f;
     int rc = resident_grid(ctx, slot, bounds, true, s, st, f);
     if (rc != ORBFE_OK) return rc;
     rc = ensure_query_scratch(ctx, st, n_pts);

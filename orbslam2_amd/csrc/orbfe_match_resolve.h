@@ -36,7 +36,7 @@
 namespace orbfe_resolve
 {
 
-// One window query of the device kernel (window_candidates_kernel, orbfe_match.hip): what a map point asks of the frame grid
+// One window query of the device kernels (query_window / for_each_hit, orbfe_match_window.hpp): what a map point asks of the frame grid
 struct MatchQuery { // 32 bytes
     float u, v, r;
     int min_level, max_level;

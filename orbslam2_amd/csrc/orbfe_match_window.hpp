@@ -1,0 +1,138 @@
+// orbfe_match_window.hpp -- the device statements the Tracking matchers share below their resolution: the frame grid
+// (Frame::PosInGrid), the window of a query (Frame::GetFeaturesInArea), the walk over its keypoints, the candidate key and the
+// selection of a query's four smallest keys.  orbfe_match.hip (candidate lists for the host replay) and orbfe_match_device.hip
+// (resolution on the device) both include it, so every statement of the bit-exactness contracts -- Q4 (no FMA contraction, no
+// fast-math), Q5 (the level check), Q6 (round(), column 64 dropped) -- and the key layout
+//      dist << 36 | ix << 30 | iy << 24 | idx << 8 | octave        (dist 511: failed the mvuRight gate)
+// exists once.  Only __device__ __forceinline__ functions, structs and constants: the library has no relocatable device code, so
+// the one kernel over these (grid_build_kernel, orbfe_match_device.hip) is reached through orbfe_launch_grid_build.
+#pragma once
+
+#include "orbfe_common.hpp"
+#include "orbfe_match_resolve.h"
+
+#define GRID_COLS 64 // FRAME_GRID_COLS include/Frame.h:36
+#define GRID_ROWS 48 // FRAME_GRID_ROWS include/Frame.h:37
+#define GRID_CELLS (GRID_COLS * GRID_ROWS)
+#define NO_KEY (~0ull)
+
+// a frame as the kernels see it
+struct GridFrame {
+    const KeyPointPOD *keys; // mvKeysUn
+    const uint8_t *desc;
+    const float *u_right;    // null: no mvuRight gate
+    const int *n_ptr;        // the keypoint counter of a resident slot (DeviceBuffers::kp_cnt); null: the frame holds `cap` keypoints
+    int cap;                 // keypoint capacity of the slot, or the count of an uploaded frame
+    float min_x, min_y, inv_w, inv_h; // Frame::mnMinX / mnMinY, mfGridElementWidthInv / HeightInv: the grid ASSIGNMENT
+    float q_min_x, q_min_y;           // bounds of the window QUERY: the same, or (float)(int) of them for a KeyFrame (src/KeyFrame.cc:568-580)
+    int *cell_off, *cell_idx;         // CSR over ix * GRID_ROWS + iy
+};
+
+__device__ __forceinline__ int frame_count(const GridFrame &f)
+{
+    if (!f.n_ptr) return f.cap;
+    const int n = *f.n_ptr;
+    return n < 0 ? 0 : (n > f.cap ? f.cap : n);
+}
+// Frame::PosInGrid (src/Frame.cc:383-393; Q6: round(), column 64 dropped)
+__device__ __forceinline__ int grid_cell(const GridFrame &f, int i)
+{
+    const int px = (int)roundf(__fmul_rn(__fsub_rn(f.keys[i].x, f.min_x), f.inv_w));
+    const int py = (int)roundf(__fmul_rn(__fsub_rn(f.keys[i].y, f.min_y), f.inv_h));
+    return (px >= 0 && px < GRID_COLS && py >= 0 && py < GRID_ROWS) ? px * GRID_ROWS + py : -1;
+}
+
+// The cells of a query's window (Frame::GetFeaturesInArea, src/Frame.cc:328-381)
+struct Window { int min_cx, min_cy, ncy, ncells; };
+__device__ __forceinline__ Window query_window(const GridFrame &f, const orbfe_resolve::MatchQuery &Q)
+{
+    Window w = {0, 0, 1, 0};
+    if (!(Q.flags & 1)) return w;
+    int v = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(Q.u, f.q_min_x), Q.r), f.inv_w));
+    w.min_cx = v > 0 ? v : 0;
+    v = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(Q.u, f.q_min_x), Q.r), f.inv_w));
+    const int max_cx = v < GRID_COLS - 1 ? v : GRID_COLS - 1;
+    v = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(Q.v, f.q_min_y), Q.r), f.inv_h));
+    w.min_cy = v > 0 ? v : 0;
+    v = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(Q.v, f.q_min_y), Q.r), f.inv_h));
+    const int max_cy = v < GRID_ROWS - 1 ? v : GRID_ROWS - 1;
+    if (w.min_cx < GRID_COLS && max_cx >= 0 && w.min_cy < GRID_ROWS && max_cy >= 0 && max_cx >= w.min_cx && max_cy >= w.min_cy) {
+        w.ncy = max_cy - w.min_cy + 1;
+        w.ncells = (max_cx - w.min_cx + 1) * w.ncy;
+    }
+    return w;
+}
+
+// Calls fn(ix, iy, idx, kp) for every keypoint of the window this lane owns (cells lane, lane + 64, ...) that passes the level
+// and radius tests.
+template <class Fn>
+__device__ __forceinline__ void for_each_hit(const GridFrame &f, const orbfe_resolve::MatchQuery &Q, const Window &w, int lane, Fn fn)
+{
+    const bool check_levels = (Q.min_level > 0) || (Q.max_level >= 0); // Q5, literally
+    for (int c = lane; c < w.ncells; c += 64) {
+        const int ix = w.min_cx + c / w.ncy, iy = w.min_cy + c % w.ncy;
+        const int cell = ix * GRID_ROWS + iy;
+#pragma unroll 1 // a counting fn would otherwise be unrolled 16 deep: a cell holds a keypoint or two, and the registers cost occupancy
+        for (int j = f.cell_off[cell]; j < f.cell_off[cell + 1]; j++) {
+            const int idx = f.cell_idx[j];
+            const KeyPointPOD kp = f.keys[idx];
+            if (check_levels && (kp.octave < Q.min_level || (Q.max_level >= 0 && kp.octave > Q.max_level))) continue;
+            if (!(fabsf(__fsub_rn(kp.x, Q.u)) < Q.r && fabsf(__fsub_rn(kp.y, Q.v)) < Q.r)) continue;
+            fn(ix, iy, idx, kp);
+        }
+    }
+}
+// The key of a hit: the Hamming distance to the query descriptor qd over the hit's place in GetFeaturesInArea order
+__device__ __forceinline__ unsigned long long candidate_key(const GridFrame &f, const orbfe_resolve::MatchQuery &Q, const uint32_t (&qd)[8], int ix, int iy, int idx,
+                                                            const KeyPointPOD &kp)
+{
+    unsigned dist = 0;
+    const uint32_t *p = (const uint32_t *)(f.desc + (size_t)idx * 32);
+#pragma unroll
+    for (int k = 0; k < 8; k++) dist += __popc(qd[k] ^ p[k]);
+    // the mvuRight gate (src/ORBmatcher.cc:93-98,1403-1409) is a pure function of the pair: mark it
+    if ((Q.flags & 2) && f.u_right && f.u_right[idx] > 0 && fabsf(__fsub_rn(Q.ur, f.u_right[idx])) > Q.ur_rad) dist = 511;
+    return ((unsigned long long)dist << 36) | ((unsigned long long)ix << 30) | ((unsigned long long)iy << 24) | ((unsigned long long)idx << 8) |
+           (unsigned long long)(kp.octave & 255);
+}
+// emit(key, idx) for every hit of the lane
+template <class Emit>
+__device__ __forceinline__ void scan_window(const GridFrame &f, const orbfe_resolve::MatchQuery &Q, const Window &w, const uint32_t *__restrict__ qdesc, int lane, Emit emit)
+{
+    uint32_t qd[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) qd[k] = qdesc[k];
+    for_each_hit(f, Q, w, lane, [&](int ix, int iy, int idx, const KeyPointPOD &kp) { emit(candidate_key(f, Q, qd, ix, iy, idx, kp), idx); });
+}
+
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long w)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)w, o, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(w >> 32), o, 64);
+        const unsigned long long t = ((unsigned long long)hi << 32) | lo;
+        w = t < w ? t : w;
+    }
+    return w;
+}
+
+// The four smallest keys a lane has seen, ascending, in registers; the wave merges its lanes' four by four pops: any window size
+struct Top4 {
+    unsigned long long t0 = NO_KEY, t1 = NO_KEY, t2 = NO_KEY, t3 = NO_KEY;
+    __device__ __forceinline__ void insert(unsigned long long key)
+    {
+        if (key < t3) {
+            t3 = key;
+            if (t3 < t2) { const unsigned long long x = t2; t2 = t3; t3 = x; }
+            if (t2 < t1) { const unsigned long long x = t1; t1 = t2; t2 = x; }
+            if (t1 < t0) { const unsigned long long x = t0; t0 = t1; t1 = x; }
+        }
+    }
+    // the smallest key left in the wave (NO_KEY: none); keys are unique within a query (they carry the keypoint index), so exactly one lane retires it
+    __device__ __forceinline__ unsigned long long pop_wave_min()
+    {
+        const unsigned long long m = wave_min_u64(t0);
+        if (m != NO_KEY && t0 == m) { t0 = t1; t1 = t2; t2 = t3; t3 = NO_KEY; }
+        return m;
+    }
+};

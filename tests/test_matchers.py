@@ -527,8 +527,8 @@ def test_gpu_topk_prefix_runs_out_and_the_full_list_takes_over(gpu):
     """The device hands the host the 4 best statically admissible keys per query; when earlier queries have taken all of them
     the replay must continue on the full list (orbfe_match_resolve.h: first_two).  Forced here: every map point appears 10 times
     and the frame holds a cluster of 8 near-copies of its keypoint (Hamming distance 0 .. 7), so copy j takes the j-th best
-    keypoint and copies 5 .. 8 need candidates beyond the prefix; and with windows of more than 256 candidates the LDS stage of
-    the top-K selection gives up and the whole query goes to the full list."""
+    keypoint and copies 5 .. 8 need candidates beyond the prefix; and with 120 px windows the prefix runs out in front of hundreds
+    of statically admissible candidates (a large, exact n_static), so the replay walks a long full list."""
     api, ctx = gpu
     s = _scene(90, n_last=150, n_distract=700)
     rng = np.random.default_rng(91)
