@@ -617,6 +617,34 @@ int orbfe_enqueue_search_by_bow(orbfe_context *ctx, int slot,
         const uint32_t *d_f_nodes, const int32_t *d_f_off, const int32_t *d_f_feat, const int32_t *d_f_n_nodes,
         float nnratio, int check_ori, int32_t *d_f_match, int32_t *d_nmatches, int32_t *d_status,
         uint8_t *d_has_point, float *d_Xw, void *stream);
+/* One candidate keyframe of orbfe_enqueue_search_by_bow_batch: the arguments of orbfe_enqueue_search_by_bow's keyframe side.
+ * Every pointer is a device pointer; pos may be NULL.  64 bytes. */
+typedef struct orbfe_bow_keyframe {
+    const uint32_t *nodes; const int32_t *off; const int32_t *feat;   /* feature vector, CSR; nodes ascend strictly */
+    const int32_t *valid; const uint8_t *desc; const float *angle;    /* per keypoint */
+    const float *pos;                                                 /* n x 3, only read for d_Xw */
+    int32_t nnodes, n;
+} orbfe_bow_keyframe;
+/* orbfe_enqueue_search_by_bow against n_kfs keyframes in the same three launches (Relocalization, src/Tracking.cc:1445-1476: one
+ * SearchByFboW per candidate, each with its own vvpMapPointMatches[i], the frame never written).  d_kfs is a DEVICE array of n_kfs
+ * records, uploaded by the caller when the candidate set is known; the call copies nothing from host memory.  The host cannot
+ * see the records, so max_kf_nnodes, an upper bound of every nnodes, sizes the grid (as max_keypoints of
+ * orbfe_enqueue_pose_optimization does).  The frame's side and the settings are those of the single call.
+ * Outputs are n_kfs rows: d_f_match[n_kfs][capacity], d_nmatches[n_kfs], d_status[n_kfs], optional d_has_point[n_kfs][capacity]
+ * and d_Xw[n_kfs][capacity][3].  Row k is exactly what orbfe_enqueue_search_by_bow writes for keyframe k alone (entries at or
+ * beyond the slot's count untouched, d_status[k] with the single call's meanings); a fault in keyframe k's arrays changes no
+ * other row.  What the single call refuses on the host and only the device can see here sets d_status[k] = ORBFE_ERR_INVALID
+ * and searches keyframe k as one without nodes: nnodes < 0 or nnodes > max_kf_nnodes (no node is ever silently left
+ * unsearched), n < 0, a NULL array other than pos under nnodes > 0.
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL required pointer (d_kfs under n_kfs > 0), a slot out of range,
+ * n_kfs < 0, n_kfs > 65535 (the grid's y limit), max_kf_nnodes < 0.  n_kfs == 0: ORBFE_OK, nothing queued. */
+int orbfe_enqueue_search_by_bow_batch(orbfe_context *ctx, int slot,
+        const orbfe_bow_keyframe *d_kfs, int n_kfs, int max_kf_nnodes,
+        const uint32_t *d_f_nodes, const int32_t *d_f_off, const int32_t *d_f_feat, const int32_t *d_f_n_nodes,
+        float nnratio, int check_ori,
+        int32_t *d_f_match /* [n_kfs][capacity] */, int32_t *d_nmatches /* [n_kfs] */, int32_t *d_status /* [n_kfs] */,
+        uint8_t *d_has_point /* [n_kfs][capacity], may be NULL */, float *d_Xw /* [n_kfs][capacity][3], may be NULL */,
+        void *stream);
 /* KeyFrameDatabase::DetectLoopCandidates(KeyFrame *pKF, float minScore) (src/KeyFrameDatabase.cc:73-194; LoopClosing::DetectLoop,
  * src/LoopClosing.cc:131).  connected[k] != 0 marks the keyframes of pKF->GetConnectedKeyFrames() (may be NULL: none); covisibility
  * lists as for the relocalisation query.  Stateless: mLoopScore is only read for keyframes scored by the same call. */

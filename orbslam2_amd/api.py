@@ -37,7 +37,7 @@ EXPORTS = [
     "orbfe_get_camera", "orbfe_assign_features_to_grid", "orbfe_set_profiling_interval", "orbfe_stereo_batch", "orbfe_device_count", "orbfe_vocab_bytes",
     "orbfe_get_packed_layout", "orbfe_fetch_batch_packed", "orbfe_expand_packed", "orbfe_enqueue_rgbd", "orbfe_stereo_batch_packed",
     "orbfe_enqueue_search_by_projection_last", "orbfe_enqueue_is_in_frustum", "orbfe_enqueue_search_by_projection_points", "orbfe_device_keys_un",
-    "orbfe_enqueue_compute_bow", "orbfe_enqueue_search_by_bow",
+    "orbfe_enqueue_compute_bow", "orbfe_enqueue_search_by_bow", "orbfe_enqueue_search_by_bow_batch",
 ]
 NUM_STAGES = 8
 STAGE_NAMES = ["ingest", "pyramid", "blur", "fast", "octree", "describe", "stereo_match", "stereo_median"]  # orbfe_stage_name()
@@ -63,6 +63,12 @@ class PackedLayout(C.Structure):
     _fields_ = [("n_images_out", C.c_int32), ("capacity", C.c_int32), ("nlevels", C.c_int32), ("n_pairs", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
                 ("counts_off", C.c_size_t), ("level_counts_off", C.c_size_t), ("xy_off", C.c_size_t), ("angle_off", C.c_size_t),
                 ("response_off", C.c_size_t), ("desc_off", C.c_size_t), ("u_right_off", C.c_size_t), ("depth_off", C.c_size_t), ("bytes", C.c_size_t)]
+
+
+class BowKeyframe(C.Structure):
+    """orbfe_bow_keyframe (include/orbfe.h): one candidate keyframe of enqueue_search_by_bow_batch, device pointers."""
+    _fields_ = [("nodes", C.c_void_p), ("off", C.c_void_p), ("feat", C.c_void_p), ("valid", C.c_void_p), ("desc", C.c_void_p),
+                ("angle", C.c_void_p), ("pos", C.c_void_p), ("nnodes", C.c_int32), ("n", C.c_int32)]
 
 
 PACK_STEREO, PACK_LEFT_ONLY, PACK_DIRECT = 1, 2, 4
@@ -205,6 +211,8 @@ def load():
     L.orbfe_enqueue_compute_bow.argtypes = [vp, C.c_int, C.c_int] + [vp] * 12
     L.orbfe_enqueue_search_by_bow.restype = C.c_int
     L.orbfe_enqueue_search_by_bow.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp] + [vp] * 4 + [C.c_float, C.c_int] + [vp] * 6
+    L.orbfe_enqueue_search_by_bow_batch.restype = C.c_int
+    L.orbfe_enqueue_search_by_bow_batch.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int] + [vp] * 4 + [C.c_float, C.c_int] + [vp] * 6
     _lib = L
     return L
 
@@ -590,6 +598,15 @@ class Context:
         self._check(self.L.orbfe_enqueue_search_by_bow(
             self.h, slot, v(d_kf_nodes or None), v(d_kf_off or None), v(d_kf_feat or None), kf_nnodes, v(d_kf_valid or None), v(d_kf_desc or None),
             v(d_kf_angle or None), n_kf, v(d_kf_pos or None), v(d_f_nodes), v(d_f_off), v(d_f_feat), v(d_f_n_nodes), nnratio, int(check_ori),
+            v(d_f_match), v(d_nmatches), v(d_status), v(d_has_point or None), v(d_Xw or None), v(stream or None)))
+
+    def enqueue_search_by_bow_batch(self, slot, d_kfs, n_kfs, max_kf_nnodes, d_f_nodes, d_f_off, d_f_feat, d_f_n_nodes, nnratio, check_ori,
+                                    d_f_match, d_nmatches, d_status, d_has_point=0, d_Xw=0, stream=0):
+        """enqueue_search_by_bow against n_kfs keyframes at once (Relocalization): d_kfs is a device array of BowKeyframe records,
+        max_kf_nnodes an upper bound of their nnodes; the outputs hold one row per keyframe."""
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_search_by_bow_batch(
+            self.h, slot, v(d_kfs or None), n_kfs, max_kf_nnodes, v(d_f_nodes), v(d_f_off), v(d_f_feat), v(d_f_n_nodes), nnratio, int(check_ori),
             v(d_f_match), v(d_nmatches), v(d_status), v(d_has_point or None), v(d_Xw or None), v(stream or None)))
 
     def search_by_projection_kf(self, view, Tcw_cur, kf_pos, kf_desc, kf_valid, kf_angle, kf_max_distance, kf_min_distance, cur_has_point,

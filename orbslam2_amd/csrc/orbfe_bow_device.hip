@@ -20,6 +20,9 @@
 //                                frame features, and the "already matched" flags of a lane's features stay in that lane's registers.
 //   bow_match_tail_kernel        the rotation histogram needs every node: bins, ComputeThreeMaxima, losers removed, the count,
 //                                and the optional has_point / Xw for orbfe_enqueue_pose_optimization
+// orbfe_enqueue_search_by_bow_batch (Relocalization, src/Tracking.cc:1445-1476: the candidates are independent), the same three
+// launches for all keyframes: bow_*_batch_kernel run the same device functions on a BowSearch built from record blockIdx.y
+// (tail: blockIdx.x) of the caller's orbfe_bow_keyframe array and that row of the outputs.
 #include "../../include/orbfe.h"
 #include "orbfe_device.h"
 #include "orbfe_host.h"
@@ -247,7 +250,7 @@ struct BowSearch {
     uint8_t *has_point; float *Xw;
 };
 
-__global__ __launch_bounds__(256) void bow_match_init_kernel(BowSearch a)
+__device__ __forceinline__ void bow_match_init(const BowSearch &a)
 {
     const int n = slot_count(a.n_ptr, a.cap);
     const int k = blockIdx.x * 256 + threadIdx.x;
@@ -287,7 +290,7 @@ __device__ __forceinline__ int hamming256(const uint32_t *a, const uint32_t *b)
 // which only this lane wrote (every frame keypoint lies in one node).  A lane's candidates come in list order, so its running
 // (d1, d2) is the if-chain of :213-222 on its share; the wave's bestDist1 is the smallest key d << 16 | j (first minimum in list
 // order), bestDist2 the smallest distance of all the others, duplicates of bestDist1 included.
-__global__ __launch_bounds__(256) void bow_node_match_kernel(BowSearch a)
+__device__ __forceinline__ void bow_node_match(const BowSearch &a)
 {
     const int lane = threadIdx.x & 63;
     const int node = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -391,7 +394,7 @@ __global__ __launch_bounds__(256) void bow_node_match_kernel(BowSearch a)
 }
 
 // One workgroup.  A frame keypoint is matched at most once, so the accepted events are the non-negative entries of f_match.
-__global__ __launch_bounds__(1024) void bow_match_tail_kernel(BowSearch a)
+__device__ __forceinline__ void bow_match_tail(const BowSearch &a)
 {
     __shared__ int32_t s_hist[32];
     __shared__ int s_keep[3], s_nm;
@@ -435,6 +438,61 @@ __global__ __launch_bounds__(1024) void bow_match_tail_kernel(BowSearch a)
     if (tid == 0) *a.nmatches = s_nm;
 }
 
+__global__ __launch_bounds__(256) void bow_match_init_kernel(BowSearch a) { bow_match_init(a); }
+__global__ __launch_bounds__(256) void bow_node_match_kernel(BowSearch a) { bow_node_match(a); }
+__global__ __launch_bounds__(1024) void bow_match_tail_kernel(BowSearch a) { bow_match_tail(a); }
+
+// The batch: `a` holds the frame's side, the settings and row 0 of the outputs.  Record k is the same for every lane (k is a
+// workgroup index) and is read before any store, so it arrives by scalar loads and the BowSearch built from it stays in SGPRs.
+// A record the single call would refuse on the host (a negative count, a NULL array under nnodes > 0), or whose nnodes lies
+// outside [0, max_kf_nnodes] (the node grid would not cover it), is searched as a keyframe without nodes and reported in its status.
+static_assert(sizeof(orbfe_bow_keyframe) == 64, "orbfe_bow_keyframe: seven pointers and two counts");
+__device__ __forceinline__ BowSearch bow_batch_row(BowSearch a, const orbfe_bow_keyframe *__restrict__ kfs, int max_kf_nnodes, int k, bool *refused)
+{
+    const orbfe_bow_keyframe kf = kfs[k];
+    *refused = kf.nnodes < 0 || kf.nnodes > max_kf_nnodes || kf.n < 0 ||
+               (kf.nnodes > 0 && (!kf.nodes || !kf.off || !kf.feat || !kf.valid || !kf.desc || !kf.angle));
+    a.kf_nodes = kf.nodes; a.kf_off = kf.off; a.kf_feat = kf.feat; a.kf_nnodes = *refused ? 0 : kf.nnodes;
+    a.kf_valid = kf.valid; a.kf_desc = kf.desc; a.kf_angle = kf.angle; a.n_kf = kf.n; a.kf_pos = kf.pos;
+    a.match += (size_t)k * a.cap; a.nmatches += k; a.status += k;
+    if (a.has_point) a.has_point += (size_t)k * a.cap;
+    if (a.Xw) a.Xw += (size_t)k * a.cap * 3;
+    return a;
+}
+
+__global__ __launch_bounds__(256) void bow_match_init_batch_kernel(BowSearch a, const orbfe_bow_keyframe *__restrict__ kfs, int max_kf_nnodes)
+{
+    bool refused;
+    const BowSearch r = bow_batch_row(a, kfs, max_kf_nnodes, blockIdx.y, &refused);
+    bow_match_init(r);
+    if (refused && blockIdx.x == 0 && threadIdx.x == 0) *r.status = ORBFE_ERR_INVALID; // the thread that wrote it in bow_match_init
+}
+__global__ __launch_bounds__(256) void bow_node_match_batch_kernel(BowSearch a, const orbfe_bow_keyframe *__restrict__ kfs, int max_kf_nnodes)
+{
+    bool refused;
+    bow_node_match(bow_batch_row(a, kfs, max_kf_nnodes, blockIdx.y, &refused)); // a node at or past kf_nnodes returns first of all
+}
+__global__ __launch_bounds__(1024) void bow_match_tail_batch_kernel(BowSearch a, const orbfe_bow_keyframe *__restrict__ kfs, int max_kf_nnodes)
+{
+    bool refused;
+    bow_match_tail(bow_batch_row(a, kfs, max_kf_nnodes, blockIdx.x, &refused));
+}
+
+// The slot's side of a BowSearch and the checks both entry points share.
+static int bow_search_frame_side(orbfe_context *ctx, int slot, BowSearch *a)
+{
+    const DeviceConfig *cfg = orbfe_ctx_config(ctx);
+    const DeviceBuffers *buf = orbfe_ctx_buffers(ctx);
+    if (slot < 0 || slot >= orbfe_ctx_last_images(ctx))
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d: the latest extraction call filled %d image slots", slot, orbfe_ctx_last_images(ctx));
+    const int cap = cfg->sel_total;
+    if (cap <= 0 || cap > 65535) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "frames with more than 65535 keypoints are not supported");
+    a->keys = (const KeyPointPOD *)buf->kps + (size_t)slot * cap; // mvKeys[].angle
+    a->desc = buf->desc + (size_t)slot * cap * 32;
+    a->n_ptr = buf->kp_cnt + slot; a->cap = cap;
+    return ORBFE_OK;
+}
+
 extern "C" int orbfe_enqueue_search_by_bow(orbfe_context *ctx, int slot,
                                            const uint32_t *d_kf_nodes, const int32_t *d_kf_off, const int32_t *d_kf_feat, int kf_nnodes,
                                            const int32_t *d_kf_valid, const uint8_t *d_kf_desc, const float *d_kf_angle, int n_kf, const float *d_kf_pos,
@@ -447,28 +505,54 @@ try {
     if (kf_nnodes < 0 || n_kf < 0 || !d_f_nodes || !d_f_off || !d_f_feat || !d_f_n_nodes || !d_f_match || !d_nmatches || !d_status ||
         (kf_nnodes > 0 && (!d_kf_nodes || !d_kf_off || !d_kf_feat || !d_kf_valid || !d_kf_desc || !d_kf_angle)))
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
-    const DeviceConfig *cfg = orbfe_ctx_config(ctx);
-    const DeviceBuffers *buf = orbfe_ctx_buffers(ctx);
-    if (slot < 0 || slot >= orbfe_ctx_last_images(ctx))
-        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d: the latest extraction call filled %d image slots", slot, orbfe_ctx_last_images(ctx));
-    const int cap = cfg->sel_total;
-    if (cap <= 0 || cap > 65535) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "frames with more than 65535 keypoints are not supported");
+    BowSearch a;
+    int rc = bow_search_frame_side(ctx, slot, &a);
+    if (rc != ORBFE_OK) return rc;
+    const int cap = a.cap;
     hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
     WTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
-    const int rc = orbfe_ctx_order_after_extraction(ctx, s);
+    rc = orbfe_ctx_order_after_extraction(ctx, s);
     if (rc != ORBFE_OK) return rc;
-    BowSearch a;
     a.kf_nodes = d_kf_nodes; a.kf_off = d_kf_off; a.kf_feat = d_kf_feat; a.kf_nnodes = kf_nnodes;
     a.kf_valid = d_kf_valid; a.kf_desc = d_kf_desc; a.kf_angle = d_kf_angle; a.n_kf = n_kf; a.kf_pos = d_kf_pos;
     a.f_nodes = d_f_nodes; a.f_off = d_f_off; a.f_feat = d_f_feat; a.f_n_nodes = d_f_n_nodes;
-    a.keys = (const KeyPointPOD *)buf->kps + (size_t)slot * cap; // mvKeys[].angle
-    a.desc = buf->desc + (size_t)slot * cap * 32;
-    a.n_ptr = buf->kp_cnt + slot; a.cap = cap;
     a.nnratio = nnratio; a.check_ori = check_ori != 0;
     a.match = d_f_match; a.nmatches = d_nmatches; a.status = d_status; a.has_point = d_has_point; a.Xw = d_Xw;
     hipLaunchKernelGGL(bow_match_init_kernel, dim3((cap + 255) / 256), dim3(256), 0, s, a);
     if (kf_nnodes > 0) hipLaunchKernelGGL(bow_node_match_kernel, dim3((kf_nnodes + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(bow_match_tail_kernel, dim3(1), dim3(1024), 0, s, a);
+    WTRY(ctx, hipGetLastError());
+    return ORBFE_OK;
+} ORBFE_CATCH(ctx)
+
+extern "C" int orbfe_enqueue_search_by_bow_batch(orbfe_context *ctx, int slot, const orbfe_bow_keyframe *d_kfs, int n_kfs, int max_kf_nnodes,
+                                                 const uint32_t *d_f_nodes, const int32_t *d_f_off, const int32_t *d_f_feat, const int32_t *d_f_n_nodes,
+                                                 float nnratio, int check_ori, int32_t *d_f_match, int32_t *d_nmatches, int32_t *d_status,
+                                                 uint8_t *d_has_point, float *d_Xw, void *stream)
+try {
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    ORBFE_ENTRY(ctx);
+    if (n_kfs < 0 || n_kfs > 65535 || max_kf_nnodes < 0)
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "n_kfs = %d (0 .. 65535, the grid's y limit), max_kf_nnodes = %d", n_kfs, max_kf_nnodes);
+    if (!d_f_nodes || !d_f_off || !d_f_feat || !d_f_n_nodes || !d_f_match || !d_nmatches || !d_status || (n_kfs > 0 && !d_kfs))
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
+    BowSearch a;
+    int rc = bow_search_frame_side(ctx, slot, &a);
+    if (rc != ORBFE_OK) return rc;
+    if (n_kfs == 0) return ORBFE_OK;
+    const int cap = a.cap;
+    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
+    WTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    rc = orbfe_ctx_order_after_extraction(ctx, s);
+    if (rc != ORBFE_OK) return rc;
+    a.kf_nodes = nullptr; a.kf_off = a.kf_feat = a.kf_valid = nullptr; a.kf_desc = nullptr; a.kf_angle = a.kf_pos = nullptr; // per record, on the device
+    a.kf_nnodes = a.n_kf = 0;
+    a.f_nodes = d_f_nodes; a.f_off = d_f_off; a.f_feat = d_f_feat; a.f_n_nodes = d_f_n_nodes;
+    a.nnratio = nnratio; a.check_ori = check_ori != 0;
+    a.match = d_f_match; a.nmatches = d_nmatches; a.status = d_status; a.has_point = d_has_point; a.Xw = d_Xw; // row 0
+    hipLaunchKernelGGL(bow_match_init_batch_kernel, dim3((cap + 255) / 256, n_kfs), dim3(256), 0, s, a, d_kfs, max_kf_nnodes);
+    if (max_kf_nnodes > 0) hipLaunchKernelGGL(bow_node_match_batch_kernel, dim3((max_kf_nnodes + 3) / 4, n_kfs), dim3(256), 0, s, a, d_kfs, max_kf_nnodes);
+    hipLaunchKernelGGL(bow_match_tail_batch_kernel, dim3(n_kfs), dim3(1024), 0, s, a, d_kfs, max_kf_nnodes);
     WTRY(ctx, hipGetLastError());
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)

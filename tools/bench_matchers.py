@@ -16,6 +16,12 @@ runs only the TrackReferenceKeyFrame rows (profiles/bow_device.json): (a) the sy
 orbfe_search_by_bow on the 1500 / 1600 descriptor scene, (b) orbfe_enqueue_compute_bow + orbfe_enqueue_search_by_bow on the same
 frame resident in slot 0, as enqueue + one stream synchronise and as GPU time between two events, (c) BoW -> match -> pose on
 a real extracted frame as host calls against the one-stream chain.  (b) and the chain are skipped on a library without them.
+    python3 tools/bench_matchers.py --bow-batch [--lib path/to/another/liborbfe.so]
+runs only the Relocalization rows (profiles/bow_device_batch.json) on the --bow-only scene: the 1600-descriptor frame resident in
+slot 0 against K = 1, 4, 16 candidate keyframes of 1500 descriptors (the scene's keyframe and perturbed copies of it), level 4,
+ratio 0.7, rotation check on.  Per K: orbfe_enqueue_search_by_bow queued K times + one stream synchronise, and -- when the library
+has it -- orbfe_enqueue_search_by_bow_batch + one stream synchronise, each as wall time and as GPU time between two events.  --lib
+loads another build of the library (the parent commit's, for the baseline leg) under the same Python package.
 """
 import json
 import os
@@ -309,8 +315,173 @@ def bow_rows(out):
     ctx.close()
 
 
+def bow_batch_rows(out):
+    """Rows of --bow-batch; arguments prepared once, C ABI called directly."""
+    import ctypes as C
+    import torch
+    from orbslam2_amd import api, synth
+    from orbslam2_amd import bow as B
+    from tests import test_bow as TB
+    vp = C.c_void_p
+    dev = torch.device("cuda:0")
+    up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, t).view(np.uint8).reshape(-1)).to(dev)
+    i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
+    ctx = api.Context(width=TM.W, height=TM.H, nfeatures=2000, fx=TM.FX, fy=TM.FY, cx=TM.CX, cy=TM.CY, bf=TM.BF)
+    L = ctx.L
+    B._bind()
+    have = hasattr(L, "orbfe_enqueue_search_by_bow_batch")
+    L.orbfe_enqueue_compute_bow.restype = C.c_int
+    L.orbfe_enqueue_compute_bow.argtypes = [vp, C.c_int, C.c_int] + [vp] * 12
+    L.orbfe_enqueue_search_by_bow.restype = C.c_int
+    L.orbfe_enqueue_search_by_bow.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp] + [vp] * 4 + [C.c_float, C.c_int] + [vp] * 6
+    if have:
+        L.orbfe_enqueue_search_by_bow_batch.restype = C.c_int
+        L.orbfe_enqueue_search_by_bow_batch.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int] + [vp] * 4 + [C.c_float, C.c_int] + [vp] * 6
+    blob = B.build_vocabulary(TB._descs(1, 6000), k=10, levels=5, seed=7)
+    B.vocab_load(ctx, blob)
+    Lo, v = TB._oracle_voc(blob)
+    st = torch.cuda.Stream()
+    sp = vp(st.cuda_stream)
+    cap = ctx.capacity
+    KMAX, REPS = 16, 200
+    # the --bow-only scene; candidate 0 is its keyframe, candidate k a copy with 1 % of the bits flipped, angles moved by N(0, 2 deg)
+    # and its own valid flags
+    kf_d = TB._descs(4, 1500)
+    rng = np.random.default_rng(5)
+    perm = rng.permutation(1500)[:1200]
+    f_d = np.concatenate([TB._descs(6, 0, base=kf_d[perm], flip=0.04), TB._descs(7, 400)])
+    kf_valid = (rng.random(len(kf_d)) < 0.8).astype(np.int32)
+    kf_ang = rng.uniform(0, 360, len(kf_d)).astype(np.float32)
+    f_ang = np.concatenate([(kf_ang[perm] + rng.normal(0, 5, 1200)) % 360, rng.uniform(0, 360, 400)]).astype(np.float32)
+    cands = [(kf_d, kf_valid, kf_ang)]
+    for k in range(1, KMAX):
+        r = np.random.default_rng(900 + k)
+        ang = ((kf_ang + r.normal(0, 2, len(kf_d))) % 360).astype(np.float32)
+        ang[ang >= 360] = 0
+        cands.append((TB._descs(950 + k, 0, base=kf_d, flip=0.01), (r.random(len(kf_d)) < 0.8).astype(np.int32), ang))
+    _, _, f_fv = TB._oracle_transform(Lo, v, f_d, 4)
+    n = len(f_d)
+    refs, kfs, recs = [], [], (api.BowKeyframe * KMAX)() if have else None
+    for k, (d, valid, ang) in enumerate(cands):
+        fv = TB._oracle_transform(Lo, v, d, 4)[2]
+        ref = np.zeros(n, np.int32)
+        nref = Lo.orc_search_by_bow(TB._p(fv[0]), TB._p(fv[1]), TB._p(fv[2]), len(fv[0]), TB._p(valid), TB._p(np.ascontiguousarray(d)), TB._p(ang),
+                                    TB._p(f_fv[0]), TB._p(f_fv[1]), TB._p(f_fv[2]), len(f_fv[0]), TB._p(f_d), TB._p(f_ang), n, 0.7, 1, TB._p(ref))
+        refs.append((ref, nref))
+        t = [up(fv[0], np.uint32), up(fv[1], np.int32), up(fv[2], np.int32), up(valid, np.int32), up(d, np.uint8), up(ang, np.float32)]
+        kfs.append((t, len(fv[0]), len(d)))
+        if have:
+            recs[k] = api.BowKeyframe(*[x.data_ptr() for x in t], None, len(fv[0]), len(d))
+    max_nn = max(nn for _, nn, _ in kfs)
+    d_recs = up(np.frombuffer(bytes(recs), np.uint8), np.uint8) if have else None
+    # the frame into slot 0 of a real extraction call, its feature vector computed once on the device
+    left, right = synth.stereo_pair(TM.W, TM.H, seed=77)
+    ctx.stereo_frame(left, right)
+    bufs = [C.c_void_p() for _ in range(5)]
+    assert L.orbfe_device_buffers(ctx.h, *[C.byref(x) for x in bufs]) == 0
+    kp = np.zeros(n, api.KP_DTYPE); kp["angle"] = f_ang
+
+    def raw(ptr, nbytes):
+        class R:
+            __cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
+        return torch.as_tensor(R(), device=dev)
+    raw(bufs[0].value, 28 * n)[:] = torch.from_numpy(kp.view(np.uint8).reshape(-1).copy()).to(dev)
+    raw(bufs[1].value, 32 * n)[:] = up(f_d, np.uint8)
+    raw(bufs[2].value, 4)[:] = up(np.array([n], np.int32), np.int32)
+    o = [i32(cap) for _ in range(4)] + [i32(cap + 1)] + [i32(1) for _ in range(3)]  # words, word_w, nodes, node_feat, node_off, n_words, n_nodes, status
+    op = [vp(t.data_ptr()) for t in o]
+    torch.cuda.synchronize()
+    assert L.orbfe_enqueue_compute_bow(ctx.h, 0, 4, None, None, None, op[0], op[1], op[5], op[2], op[4], op[3], op[6], op[7], sp) == 0
+    assert L.orbfe_synchronize(ctx.h, sp) == 0 and int(o[7].item()) == 0
+    frame = (op[2], op[4], op[3], op[6], C.c_float(0.7), 1)
+
+    class Rows:
+        def __init__(self):
+            self.match, self.nm, self.status = i32(KMAX * cap), i32(KMAX), i32(KMAX)
+
+        def check(self, K, what):
+            m, nm, stt = self.match.cpu().numpy().reshape(KMAX, cap), self.nm.cpu().numpy(), self.status.cpu().numpy()
+            for k in range(K):
+                assert stt[k] == 0 and nm[k] == refs[k][1] and np.array_equal(m[k, :n], refs[k][0]), (what, K, k)
+
+    one, bat = Rows(), Rows()
+    single_args = [(ctx.h, 0, *[vp(x.data_ptr()) for x in t[:3]], nn, *[vp(x.data_ptr()) for x in t[3:]], nd, None, *frame,
+                    vp(one.match.data_ptr() + 4 * k * cap), vp(one.nm.data_ptr() + 4 * k), vp(one.status.data_ptr() + 4 * k), None, None, sp)
+                   for k, (t, nn, nd) in enumerate(kfs)]
+    torch.cuda.synchronize()
+
+    def measure(enqueue):
+        def call():
+            enqueue()
+            assert L.orbfe_synchronize(ctx.h, sp) == 0
+        wall = timeit(call, REPS)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(REPS):
+            enqueue()
+        e1.record(st)
+        st.synchronize()
+        return {"wall_ms": round(wall, 4), "gpu_ms": round(e0.elapsed_time(e1) / REPS, 4)}
+
+    out["scene"] = "%d frame descriptors against K candidates of %d, level 4, ratio 0.7, rotation check on; matches per candidate %d .. %d" % (
+        n, len(kf_d), min(r[1] for r in refs), max(r[1] for r in refs))
+    for K in (1, 4, 16):
+        def singles(K=K):
+            for a in single_args[:K]:
+                assert L.orbfe_enqueue_search_by_bow(*a) == 0
+        singles()
+        assert L.orbfe_synchronize(ctx.h, sp) == 0
+        one.check(K, "single")
+        row = {"orbfe_enqueue_search_by_bow x K + one stream synchronise": measure(singles)}
+        if have:
+            def batch(K=K):
+                assert L.orbfe_enqueue_search_by_bow_batch(ctx.h, 0, vp(d_recs.data_ptr()), K, max_nn, *frame, vp(bat.match.data_ptr()), vp(bat.nm.data_ptr()),
+                                                           vp(bat.status.data_ptr()), None, None, sp) == 0
+            batch()
+            assert L.orbfe_synchronize(ctx.h, sp) == 0
+            bat.check(K, "batch")
+            row["orbfe_enqueue_search_by_bow_batch + one stream synchronise"] = measure(batch)
+        out["rows"]["K = %d" % K] = row
+    if not have:
+        out["batch"] = "not exported by this library"
+    Lo.orc_vocab_destroy(v)
+    ctx.close()
+
+
+def load_other_build(api, path):
+    """api.load() on the library at `path`, which may be older than the package: the prototypes load() sets for entry points
+    that build lacks land on stand-ins that are not kept, so hasattr(lib, name) is False afterwards and a call fails loudly."""
+    import ctypes as C
+    import types
+    import torch  # noqa: F401  (load() imports it before the library; here before CDLL is swapped)
+
+    class Tolerant(C.CDLL):
+        def __getattr__(self, name):
+            try:
+                return super().__getattr__(name)
+            except AttributeError:
+                if not name.startswith("orbfe_"):
+                    raise
+                return types.SimpleNamespace()
+
+    api.LIB_PATH, real = path, C.CDLL
+    C.CDLL = Tolerant
+    try:
+        api.load().__class__ = real
+    finally:
+        C.CDLL = real
+
+
 def main():
     from orbslam2_amd import api
+    if "--lib" in sys.argv[1:]:  # another build of the library under this package (load() has not run yet)
+        load_other_build(api, os.path.abspath(sys.argv[sys.argv.index("--lib") + 1]))
+    if "--bow-batch" in sys.argv[1:]:
+        out = {"unit": "ms per call", "rows": {}}
+        bow_batch_rows(out)
+        out["build_id"] = api.build_id()
+        print(json.dumps(out, indent=1))
+        return
     if "--bow-only" in sys.argv[1:]:
         out = {"unit": "ms per call", "rows": {}}
         bow_rows(out)
