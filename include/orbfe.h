@@ -585,6 +585,54 @@ int orbfe_enqueue_search_by_projection_points(orbfe_context *ctx, int slot, cons
         const orbfe_track_point *d_pts, const uint8_t *d_pt_desc, const int32_t *d_pt_obs, const float *d_pt_pos /* may be NULL */,
         const uint8_t *d_cur_has_obs, float th, float nnratio,
         int32_t *d_cur_match, int32_t *d_nmatches, int32_t *d_status, uint8_t *d_has_point, float *d_Xw, void *stream);
+/* SearchByProjection(CurrentFrame, KeyFrame, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1468-1595) on device-resident data, as
+ * Relocalization calls it between its pose optimisations (src/Tracking.cc:1540-1580).  The d_kf_* arrays have n_kf rows and the
+ * meaning of orbfe_search_by_projection_kf's arguments; the window is a plain GetFeaturesInArea (no mvuRight).
+ * d_cur_point[capacity], in/out, is mvpMapPoints of the current frame in terms of this keyframe: the keyframe index whose map
+ * point keypoint k holds, or -1.  With count = the slot's keypoint count (entries at or beyond it are never read or written):
+ *  1. found[i] = exclude_held && some k < count has d_cur_point[k] == i at entry (sAlreadyFound of :1552 and :1566);
+ *  2. d_outlier (may be NULL; mvbOutlier as orbfe_enqueue_pose_optimization wrote it): d_cur_point[k] = -1 where d_outlier[k] != 0
+ *     (:1545-1547), after step 1;
+ *  3. the matcher is orbfe_search_by_projection_kf with kf_valid[i] && !found[i] and cur_has_point[k] = d_cur_point[k] >= 0;
+ *  4. d_cur_match[k] = the keyframe index newly matched to keypoint k or -1, d_nmatches[1] = the reference's return value,
+ *     d_cur_point[k] = d_cur_match[k] where that is >= 0, and the optional d_has_point[k] = d_cur_point[k] >= 0 and
+ *     d_Xw[k] = d_kf_pos[d_cur_point[k]] for every held keypoint, old and new (rows of keypoints without a point untouched): what
+ *     orbfe_enqueue_pose_optimization reads, so pose -> projection -> pose needs no host step;
+ *  5. d_status[1] = 0, or ORBFE_ERR_INVALID for a d_cur_point[k] outside [-1, n_kf): it is treated (and stored) as -1, never used as
+ *     an index; the other outputs of that row are then not meaningful. */
+int orbfe_enqueue_search_by_projection_kf(orbfe_context *ctx, int slot, const float *bounds, const float *d_Tcw, int n_kf,
+        const float *d_kf_pos, const uint8_t *d_kf_desc, const int32_t *d_kf_valid, const float *d_kf_angle,
+        const float *d_kf_max_distance, const float *d_kf_min_distance,
+        int32_t *d_cur_point /* in/out */, const uint8_t *d_outlier /* may be NULL */,
+        float th, int orb_dist, int check_ori, int exclude_held,
+        int32_t *d_cur_match, int32_t *d_nmatches, int32_t *d_status, uint8_t *d_has_point /* may be NULL */, float *d_Xw /* may be NULL */,
+        void *stream);
+/* One candidate keyframe of orbfe_enqueue_search_by_projection_kf_batch: the single call's per-keyframe arguments.  All pointers are
+ * device pointers.  88 bytes. */
+typedef struct orbfe_reloc_candidate {
+    const float   *Tcw;                  /* the first 12 floats are read: [R|t]; a 4x4 written by the pose call passes as it is */
+    const float   *pos;                  /* n x 3, GetWorldPos of the keyframe's map points */
+    const uint8_t *desc;                 /* n x 32 */
+    const int32_t *valid;                /* pMP && !pMP->isBad() */
+    const float   *angle, *max_distance, *min_distance;   /* n each, as orbfe_search_by_projection_kf takes them */
+    int32_t       *cur_point;            /* [capacity] in/out: the keyframe index whose map point keypoint k holds, or -1 */
+    const uint8_t *outlier;              /* [capacity] or NULL: mvbOutlier as the pose call wrote it */
+    int32_t n; float th; int32_t orb_dist; int32_t reserved;
+} orbfe_reloc_candidate;
+/* The same for the n_cands candidates of one relocalisation in the same four launches: d_cands is a DEVICE array of records (the
+ * call copies nothing from host memory), max_n_kf an upper bound of every n.  Outputs are rows: d_cur_match[n_cands][capacity],
+ * d_nmatches[n_cands], d_status[n_cands], optional d_has_point[n_cands][capacity] and d_Xw[n_cands][capacity][3].  Row c is exactly
+ * what the single call writes for candidate c alone (th and orb_dist are per record: candidates at the 10 / 100 stage and at the
+ * 3 / 64 stage share a call); a fault in candidate c's record changes no other row.  A record with n < 0, n > max_n_kf or, under
+ * n > 0, a NULL array other than outlier sets d_status[c] = ORBFE_ERR_INVALID and is searched as a keyframe without points
+ * (d_cur_match row -1, d_nmatches 0, d_has_point row 0); these fields are checked before any pointer of the record is followed.
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL required pointer, a slot out of range, n_cands < 0,
+ * n_cands > 65535, max_n_kf < 0.  ORBFE_ERR_CAPACITY: n_cands * max_n_kf > 2^20 (the grow-only scratch rows
+ * [n_cands][max_n_kf]).  n_cands == 0: ORBFE_OK, nothing queued. */
+int orbfe_enqueue_search_by_projection_kf_batch(orbfe_context *ctx, int slot, const float *bounds,
+        const orbfe_reloc_candidate *d_cands, int n_cands, int max_n_kf, int check_ori, int exclude_held,
+        int32_t *d_cur_match /* [n_cands][capacity] */, int32_t *d_nmatches /* [n_cands] */, int32_t *d_status /* [n_cands] */,
+        uint8_t *d_has_point /* [n_cands][capacity], may be NULL */, float *d_Xw /* [n_cands][capacity][3], may be NULL */, void *stream);
 /* mvKeysUn of image slot `slot` as the device-side matchers see it: the extraction's keypoint array, or, with distortion
  * active, the undistorted copy (enqueued on `stream` if this frame has none yet).  For orbfe_enqueue_pose_optimization. */
 int orbfe_device_keys_un(orbfe_context *ctx, int slot, const orbfe_keypoint **d_keys_un, void *stream);

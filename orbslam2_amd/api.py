@@ -38,6 +38,7 @@ EXPORTS = [
     "orbfe_get_packed_layout", "orbfe_fetch_batch_packed", "orbfe_expand_packed", "orbfe_enqueue_rgbd", "orbfe_stereo_batch_packed",
     "orbfe_enqueue_search_by_projection_last", "orbfe_enqueue_is_in_frustum", "orbfe_enqueue_search_by_projection_points", "orbfe_device_keys_un",
     "orbfe_enqueue_compute_bow", "orbfe_enqueue_search_by_bow", "orbfe_enqueue_search_by_bow_batch",
+    "orbfe_enqueue_search_by_projection_kf", "orbfe_enqueue_search_by_projection_kf_batch",
 ]
 NUM_STAGES = 8
 STAGE_NAMES = ["ingest", "pyramid", "blur", "fast", "octree", "describe", "stereo_match", "stereo_median"]  # orbfe_stage_name()
@@ -69,6 +70,13 @@ class BowKeyframe(C.Structure):
     """orbfe_bow_keyframe (include/orbfe.h): one candidate keyframe of enqueue_search_by_bow_batch, device pointers."""
     _fields_ = [("nodes", C.c_void_p), ("off", C.c_void_p), ("feat", C.c_void_p), ("valid", C.c_void_p), ("desc", C.c_void_p),
                 ("angle", C.c_void_p), ("pos", C.c_void_p), ("nnodes", C.c_int32), ("n", C.c_int32)]
+
+
+class RelocCandidate(C.Structure):
+    """orbfe_reloc_candidate (include/orbfe.h): one candidate keyframe of enqueue_search_by_projection_kf_batch, device pointers."""
+    _fields_ = [("Tcw", C.c_void_p), ("pos", C.c_void_p), ("desc", C.c_void_p), ("valid", C.c_void_p), ("angle", C.c_void_p),
+                ("max_distance", C.c_void_p), ("min_distance", C.c_void_p), ("cur_point", C.c_void_p), ("outlier", C.c_void_p),
+                ("n", C.c_int32), ("th", C.c_float), ("orb_dist", C.c_int32), ("reserved", C.c_int32)]
 
 
 PACK_STEREO, PACK_LEFT_ONLY, PACK_DIRECT = 1, 2, 4
@@ -213,6 +221,10 @@ def load():
     L.orbfe_enqueue_search_by_bow.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp] + [vp] * 4 + [C.c_float, C.c_int] + [vp] * 6
     L.orbfe_enqueue_search_by_bow_batch.restype = C.c_int
     L.orbfe_enqueue_search_by_bow_batch.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int] + [vp] * 4 + [C.c_float, C.c_int] + [vp] * 6
+    L.orbfe_enqueue_search_by_projection_kf.restype = C.c_int
+    L.orbfe_enqueue_search_by_projection_kf.argtypes = [vp, C.c_int, vp, vp, C.c_int] + [vp] * 8 + [C.c_float, C.c_int, C.c_int, C.c_int] + [vp] * 6
+    L.orbfe_enqueue_search_by_projection_kf_batch.restype = C.c_int
+    L.orbfe_enqueue_search_by_projection_kf_batch.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 6
     _lib = L
     return L
 
@@ -574,6 +586,29 @@ class Context:
         self._check(self.L.orbfe_enqueue_search_by_projection_points(
             self.h, slot, _p(b), n_pts, v(d_pts), v(d_pt_desc), v(d_pt_obs), v(d_pt_pos or None), v(d_cur_has_obs or None), th, nnratio,
             v(d_cur_match), v(d_nmatches), v(d_status), v(d_has_point or None), v(d_Xw or None), v(stream or None)))
+
+    def enqueue_search_by_projection_kf(self, slot, bounds, d_Tcw, n_kf, d_kf_pos, d_kf_desc, d_kf_valid, d_kf_angle, d_kf_max_distance,
+                                        d_kf_min_distance, d_cur_point, d_outlier, th, orb_dist, check_ori, exclude_held, d_cur_match,
+                                        d_nmatches, d_status, d_has_point=0, d_Xw=0, stream=0):
+        """SearchByProjection(CurrentFrame, KeyFrame, sAlreadyFound, th, ORBdist) on image slot `slot`, asynchronous: d_cur_point
+        (int32[capacity], in/out) is the keyframe index whose map point each keypoint holds; see include/orbfe.h."""
+        b = np.ascontiguousarray(bounds, np.float32)
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_search_by_projection_kf(
+            self.h, slot, _p(b), v(d_Tcw or None), n_kf, v(d_kf_pos or None), v(d_kf_desc or None), v(d_kf_valid or None), v(d_kf_angle or None),
+            v(d_kf_max_distance or None), v(d_kf_min_distance or None), v(d_cur_point or None), v(d_outlier or None), th, int(orb_dist),
+            int(check_ori), int(exclude_held), v(d_cur_match or None), v(d_nmatches or None), v(d_status or None), v(d_has_point or None),
+            v(d_Xw or None), v(stream or None)))
+
+    def enqueue_search_by_projection_kf_batch(self, slot, bounds, d_cands, n_cands, max_n_kf, check_ori, exclude_held, d_cur_match, d_nmatches,
+                                              d_status, d_has_point=0, d_Xw=0, stream=0):
+        """enqueue_search_by_projection_kf for n_cands candidates at once (Relocalization): d_cands is a device array of
+        RelocCandidate records, max_n_kf an upper bound of their n; the outputs hold one row per candidate."""
+        b = np.ascontiguousarray(bounds, np.float32)
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_search_by_projection_kf_batch(
+            self.h, slot, _p(b), v(d_cands or None), n_cands, max_n_kf, int(check_ori), int(exclude_held), v(d_cur_match or None),
+            v(d_nmatches or None), v(d_status or None), v(d_has_point or None), v(d_Xw or None), v(stream or None)))
 
     def device_keys_un(self, slot, stream=0) -> int:
         """Device pointer to mvKeysUn of image slot `slot` (orbfe_keypoint records) for enqueue_pose_optimization."""

@@ -12,6 +12,10 @@
 //   frustum_kernel        Frame::isInFrustum, one lane per map point
 //   resolve_kernel        ONE workgroup replays the sequentially greedy accept rules in query order (see there)
 //   gather_kernel         optional has_point / Xw for orbfe_enqueue_pose_optimization
+// and SearchByProjection(CurrentFrame, KeyFrame, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1468-1595) for every candidate of a
+// relocalisation (src/Tracking.cc:1540-1580) through the same kernels: a grid row (window, gather) or a workgroup (resolve) per
+// candidate, whose arguments come from its orbfe_reloc_candidate record (KfBatch); kf_prepare_kernel builds sAlreadyFound and the
+// keypoints' has-point flags from cur_point first.
 // The grid cell, the window, its walk, the candidate key and the top-4 selection are orbfe_match_window.hpp, shared with
 // orbfe_match.hip; the smallest key is the reference loop's first minimum.  No candidate list is kept: a query whose four keys are
 // all taken recomputes its window.
@@ -86,6 +90,18 @@ __global__ __launch_bounds__(1024) void grid_build_kernel(GridFrame f)
 }
 static_assert(GRID_CELLS % 1024 == 0, "grid_build_kernel gives every thread the same number of cells");
 
+// What the window kernel reads and writes for one row of its grid (blockIdx.y): the launch's arguments, which a source with more
+// than one row (KfBatch) replaces by that row's
+struct WindowRow {
+    MatchQuery *q;
+    const uint8_t *qdesc;
+    int nq;
+    const uint8_t *blocked0;
+    unsigned long long *topk;
+    int *n_static;
+    int32_t *cur_match;
+};
+
 // ---- projection: where a query comes from.  The window kernel asks for query i (every lane of its wave states the same
 // arithmetic), so the matchers need no launch of their own for it ----
 struct LastSource { // SearchByProjection(CurrentFrame, LastFrame, th, bMono)
@@ -94,6 +110,7 @@ struct LastSource { // SearchByProjection(CurrentFrame, LastFrame, th, bMono)
     const int32_t *valid, *octave;
     float th;
     int mono;
+    __device__ __forceinline__ const LastSource &row(int, WindowRow &) const { return *this; }
     __device__ __forceinline__ MatchQuery query(int i) const
     {
         float Tc[12], Tl[12];
@@ -111,6 +128,7 @@ struct PointsSource { // SearchByProjection(F, vpMapPoints, th)
     Projection P;
     const orbfe_track_point *pts;
     float th;
+    __device__ __forceinline__ const PointsSource &row(int, WindowRow &) const { return *this; }
     __device__ __forceinline__ MatchQuery query(int i) const
     {
         MatchQuery Q = {0, 0, 0, 0, -1, 0, 0, 0};
@@ -141,35 +159,41 @@ __global__ __launch_bounds__(256) void frustum_kernel(Projection P, const float 
 // n_static = how many keys passed the static filters, -1 for a Q_BAD query.  The threads below the frame's keypoint count also
 // reset cur_match (the launch covers the keypoint capacity).
 template <class Source>
-__global__ __launch_bounds__(256) void window_topk_kernel(GridFrame f, Source src, MatchQuery *__restrict__ q, const uint8_t *__restrict__ qdesc, int nq,
-                                                          const uint8_t *__restrict__ blocked0, unsigned long long *__restrict__ topk,
-                                                          int *__restrict__ n_static, int32_t *__restrict__ cur_match)
+__global__ __launch_bounds__(256) void window_topk_kernel(GridFrame f, Source src0, WindowRow r)
 {
+    const auto &src = src0.row(blockIdx.y, r); // the source and the arguments of this row
     const int gid = blockIdx.x * 256 + threadIdx.x;
-    if (gid < frame_count(f)) cur_match[gid] = -1;
+    if (gid < frame_count(f)) r.cur_match[gid] = -1;
     const int iq = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (iq >= nq) return;
+    if (iq >= r.nq) return;
     const MatchQuery Q = src.query(iq);
-    if (lane == 0) q[iq] = Q;
+    if (lane == 0) r.q[iq] = Q;
     const Window w = query_window(f, Q);
     Top4 top;
     int passed = 0;
     if (w.ncells > 0)
-        scan_window(f, Q, w, (const uint32_t *)(qdesc + (size_t)iq * 32), lane, [&](unsigned long long key, int idx) {
-            if (key_dist(key) >= 256 || (blocked0 && blocked0[idx])) return; // static filters
+        scan_window(f, Q, w, (const uint32_t *)(r.qdesc + (size_t)iq * 32), lane, [&](unsigned long long key, int idx) {
+            if (key_dist(key) >= 256 || (r.blocked0 && r.blocked0[idx])) return; // static filters
             passed++;
             top.insert(key);
         });
     passed = wave_sum_i32(passed);
-    for (int r = 0; r < TOPK; r++) {
+    for (int k = 0; k < TOPK; k++) {
         const unsigned long long m = top.pop_wave_min();
-        if (lane == 0) topk[(size_t)iq * TOPK + r] = m;
+        if (lane == 0) r.topk[(size_t)iq * TOPK + k] = m;
     }
-    if (lane == 0) n_static[iq] = (Q.flags & Q_BAD) ? -1 : passed;
+    if (lane == 0) r.n_static[iq] = (Q.flags & Q_BAD) ? -1 : passed;
 }
 
 // ---- resolve ----
+struct GatherRow { // what gather_kernel reads and writes for one row
+    const int32_t *cur_match;
+    const float *pos;
+    int32_t *cur_point; // null but for the keyframe matcher
+    uint8_t *has_point;
+    float *Xw;
+};
 struct ResolveArgs {
     GridFrame f;
     const MatchQuery *q;
@@ -177,12 +201,14 @@ struct ResolveArgs {
     int nq;
     const unsigned long long *topk;
     const int *n_static;
-    const int32_t *obs;       // Observations() of the map point of query i
+    const int32_t *obs;       // Observations() of the map point of query i; null: every accepted keypoint is closed (the keyframe rule)
     const float *angle;       // last_angle (check_ori), else null
     const uint8_t *blocked0;  // keypoints taken before the call, or null
     int points;               // 0: the last-frame rule, 1: the local-map rule (best / second best, nnratio)
+    int th_high;              // the largest accepted distance: TH_HIGH, or ORBdist of the keyframe rule
     int check_ori;
     float nnratio;
+    int row_err;              // the row's arguments were refused before the kernel looked at a query
     int32_t *ev;              // [nq] scratch: keypoint accepted by query i, or -1
     int32_t *cur_match, *nmatches, *status;
 };
@@ -197,20 +223,22 @@ __device__ __forceinline__ uint32_t pack_key(unsigned long long k)
     return k == NO_KEY ? NO_PKEY : ((uint32_t)key_dist(k) << 24) | ((uint32_t)key_level(k) << 16) | (uint32_t)key_idx(k);
 }
 __device__ __forceinline__ int pkey_idx(uint32_t k) { return (int)(k & 0xffffu); }
-// the accept rules of resolve_last / resolve_points (orbfe_match_resolve.h) for one query, given its best and second-best free key
-__device__ __forceinline__ bool accept_rule(int points, float nnratio, uint32_t best, uint32_t second)
+// the accept rules of resolve_last / resolve_kf / resolve_points (orbfe_match_resolve.h) for one query, given its best and second-best free key
+__device__ __forceinline__ bool accept_rule(int points, int th_high, float nnratio, uint32_t best, uint32_t second)
 {
     if (best == NO_PKEY) return false;
     const int best_dist = (int)(best >> 24);
-    if (!points) return best_dist <= TH_HIGH;
+    if (!points) return best_dist <= th_high;
     const int best_level = (int)((best >> 16) & 255u);
     const int best_dist2 = second != NO_PKEY ? (int)(second >> 24) : 256, best_level2 = second != NO_PKEY ? (int)((second >> 16) & 255u) : -1;
-    if (best_dist > TH_HIGH) return false;
+    if (best_dist > th_high) return false;
     return !(best_level == best_level2 && (float)best_dist > nnratio * (float)best_dist2);
 }
 
-// One workgroup per call.  The accept rules are sequential only through the `blocked` flags (a keypoint taken by a map point
-// with observations is closed to every later query), and the flags only ever go from free to blocked.  So the workgroup
+// One workgroup per row of the call (one row, or one per relocalisation candidate: rows.resolve replaces the arguments by those of
+// row blockIdx.x).  The accept rules are sequential only through the `blocked` flags (a keypoint taken by a map point with
+// observations -- under the keyframe rule, by any map point -- is closed to every later query), and the flags only ever go from
+// free to blocked.  So the workgroup
 // evaluates RESOLVE_THREADS consecutive queries at once against the current flags (512: measured best of 256 / 512 / 1024 -- a step
 // costs about a microsecond at any of these widths, a narrower one needs more steps, a wider one dearer barriers); a thread's answer is final unless an
 // EARLIER thread of the same step blocks a keypoint that this thread looked at and found free (its best, for the local-map
@@ -225,8 +253,14 @@ __device__ __forceinline__ bool accept_rule(int points, float nnratio, uint32_t 
 // and observation flag 2 B) = 46 KB.
 #define CLAIM_SLOTS 4096
 #define NO_CLAIM 0x7fffffff
-__global__ __launch_bounds__(RESOLVE_THREADS) void resolve_kernel(ResolveArgs a)
+struct OneRow { // the three matchers of one row: the launch's arguments are the row's
+    __device__ __forceinline__ void resolve(int, ResolveArgs &) const {}
+    __device__ __forceinline__ void gather(int, GatherRow &) const {}
+};
+template <class Rows>
+__global__ __launch_bounds__(RESOLVE_THREADS) void resolve_kernel(ResolveArgs a, Rows rows)
 {
+    rows.resolve(blockIdx.x, a);
     __shared__ uint32_t s_blk[65536 / 32];
     __shared__ int s_claim[CLAIM_SLOTS];
     __shared__ uint32_t s_keys[TOPK][RESOLVE_CHUNK]; // packed key k of every query side by side: conflict-free reads
@@ -240,7 +274,7 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void resolve_kernel(ResolveArgs a)
     for (int w = tid; w < 65536 / 32; w += RESOLVE_THREADS) s_blk[w] = 0;
     for (int w = tid; w < CLAIM_SLOTS; w += RESOLVE_THREADS) s_claim[w] = NO_CLAIM;
     if (tid < 32) s_hist[tid] = 0;
-    if (tid == 0) { s_nm = 0; s_err = 0; }
+    if (tid == 0) { s_nm = 0; s_err = a.row_err; }
     __syncthreads();
     if (a.blocked0)
         for (int k = tid; k < n; k += RESOLVE_THREADS)
@@ -253,7 +287,7 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void resolve_kernel(ResolveArgs a)
             s_keys[0][t] = pack_key(k01.x); s_keys[1][t] = pack_key(k01.y); s_keys[2][t] = pack_key(k23.x); s_keys[3][t] = pack_key(k23.y);
             const int ns = a.n_static[base + t];
             s_ns[t] = (int8_t)(ns < 0 ? -1 : (ns > TOPK ? TOPK + 1 : ns));
-            s_obs[t] = a.obs[base + t] > 0;
+            s_obs[t] = a.obs ? a.obs[base + t] > 0 : 1;
             if (ns < 0) s_err = 1;
         }
         __syncthreads(); // also: the flags of blocked0 are set, the previous chunk's events are consumed
@@ -279,7 +313,7 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void resolve_kernel(ResolveArgs a)
                 const bool found = a.points ? second != NO_PKEY : best != NO_PKEY;
                 need_full = !found && s_ns[j] > TOPK; // the prefix ran out before the answer was found
             }
-            const bool acc = active && !need_full && accept_rule(a.points, a.nnratio, best, second);
+            const bool acc = active && !need_full && accept_rule(a.points, a.th_high, a.nnratio, best, second);
             const int e1 = best != NO_PKEY ? pkey_idx(best) : -1, e2 = second != NO_PKEY ? pkey_idx(second) : -1;
             const int blocks = (acc && s_obs[active ? j : 0]) ? e1 : -1; // the keypoint this thread closes
             if (tid == 0) s_stop = NO_CLAIM;
@@ -318,7 +352,7 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void resolve_kernel(ResolveArgs a)
                     });
                 const unsigned long long fbest = wave_min_u64(t0);
                 const unsigned long long fsecond = wave_min_u64((fbest != NO_KEY && t0 == fbest) ? t1 : t0);
-                const bool facc = accept_rule(a.points, a.nnratio, pack_key(fbest), pack_key(fsecond));
+                const bool facc = accept_rule(a.points, a.th_high, a.nnratio, pack_key(fbest), pack_key(fsecond));
                 if (lane == 0) {
                     s_ev[b] = facc ? key_idx(fbest) : -1;
                     if (facc) s_nm += 1; // no other thread touches s_nm between the two barriers around this block
@@ -379,26 +413,133 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void resolve_kernel(ResolveArgs a)
 }
 static_assert(RESOLVE_CHUNK % RESOLVE_THREADS == 0, "resolve_kernel: the thread that stores an event of a chunk reads it back in the last pass");
 
-// mvpMapPoints of the matched keypoints as orbfe_enqueue_pose_optimization reads them
-__global__ __launch_bounds__(256) void gather_kernel(GridFrame f, const int32_t *__restrict__ cur_match, const float *__restrict__ pos,
-                                                     uint8_t *__restrict__ has_point, float *__restrict__ Xw)
+// mvpMapPoints of the matched keypoints as orbfe_enqueue_pose_optimization reads them, one grid row per row of the call.  With
+// cur_point (the keyframe matcher: the map point every keypoint holds, in/out) a new match is entered there and the outputs
+// cover the points held before the call too.
+template <class Rows>
+__global__ __launch_bounds__(256) void gather_kernel(GridFrame f, GatherRow g, Rows rows)
 {
+    rows.gather(blockIdx.y, g);
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= frame_count(f)) return;
-    const int m = cur_match[k];
-    if (has_point) has_point[k] = m >= 0;
-    if (Xw && pos && m >= 0) {
-        Xw[3 * k] = pos[3 * m];
-        Xw[3 * k + 1] = pos[3 * m + 1];
-        Xw[3 * k + 2] = pos[3 * m + 2];
+    int m = g.cur_match[k];
+    if (g.cur_point) {
+        if (m >= 0) g.cur_point[k] = m;
+        else m = g.cur_point[k]; // in [-1, n): kf_prepare_kernel checked it
     }
+    if (g.has_point) g.has_point[k] = m >= 0;
+    if (g.Xw && g.pos && m >= 0) {
+        g.Xw[3 * k] = g.pos[3 * m];
+        g.Xw[3 * k + 1] = g.pos[3 * m + 1];
+        g.Xw[3 * k + 2] = g.pos[3 * m + 2];
+    }
+}
+
+// ---- SearchByProjection(CurrentFrame, KeyFrame, sAlreadyFound, th, ORBdist) for the candidates of a relocalisation ----
+// The candidates of one call: a device array of records, or (cands == null) the single call's record by value.  Row c of every
+// scratch array belongs to candidate c: found / q / topk / n_static / ev [n_cands][max_n], held [n_cands][cap], err [n_cands].
+struct KfRowSource { // one candidate as the window kernel's source
+    const Projection &P;
+    orbfe_reloc_candidate rec;
+    const uint8_t *found;
+    __device__ __forceinline__ MatchQuery query(int i) const
+    {
+        float Tc[12], ow[3];
+        for (int k = 0; k < 12; k++) Tc[k] = rec.Tcw[k];
+        orbfe_resolve::camera_center(Tc, ow);
+        MatchQuery Q = {0, 0, 0, 0, -1, 0, 0, 0};
+        const float p[3] = {rec.pos[3 * i], rec.pos[3 * i + 1], rec.pos[3 * i + 2]};
+        orbfe_resolve::query_kf_point(P.C, P.sf, P.nlevels, P.log_sf, P.min_x, P.max_x, P.min_y, P.max_y, Tc, ow, p, rec.valid[i] && !found[i],
+                                      rec.max_distance[i], rec.min_distance[i], rec.th, Q);
+        return Q;
+    }
+};
+struct KfBatch {
+    Projection P;
+    const orbfe_reloc_candidate *cands;
+    orbfe_reloc_candidate one;
+    int max_n, cap, exclude_held;
+    uint8_t *found, *held;
+    int32_t *err;
+    MatchQuery *q; // the scratch rows of the window and resolve kernels
+    unsigned long long *topk;
+    int *n_static;
+    int32_t *ev;
+    int32_t *cur_match, *nmatches, *status; // the outputs, a row per candidate
+    uint8_t *has_point;
+    float *Xw;
+
+    // Record c with its counts checked BEFORE any of its pointers is followed: a refused record comes back as a keyframe without
+    // points whose cur_point and outlier are not read either.
+    __device__ __forceinline__ orbfe_reloc_candidate record(int c, bool &refused) const
+    {
+        orbfe_reloc_candidate r = cands ? cands[c] : one;
+        refused = r.n < 0 || r.n > max_n ||
+                  (r.n > 0 && (!r.Tcw || !r.pos || !r.desc || !r.valid || !r.angle || !r.max_distance || !r.min_distance || !r.cur_point));
+        if (refused) { r.n = 0; r.cur_point = nullptr; r.outlier = nullptr; }
+        return r;
+    }
+    __device__ __forceinline__ KfRowSource row(int c, WindowRow &w) const
+    {
+        bool refused;
+        const KfRowSource s = {P, record(c, refused), found + (size_t)c * max_n};
+        w.q = q + (size_t)c * max_n; w.topk = topk + (size_t)c * max_n * TOPK; w.n_static = n_static + (size_t)c * max_n;
+        w.qdesc = s.rec.desc; w.nq = s.rec.n;
+        w.blocked0 = held + (size_t)c * cap;
+        w.cur_match = cur_match + (size_t)c * cap;
+        return s;
+    }
+    __device__ __forceinline__ void resolve(int c, ResolveArgs &a) const
+    {
+        bool refused;
+        const orbfe_reloc_candidate r = record(c, refused);
+        a.q = q + (size_t)c * max_n; a.topk = topk + (size_t)c * max_n * TOPK; a.n_static = n_static + (size_t)c * max_n; a.ev = ev + (size_t)c * max_n;
+        a.qdesc = r.desc; a.nq = r.n; a.angle = r.angle; a.th_high = r.orb_dist;
+        a.blocked0 = held + (size_t)c * cap;
+        a.row_err = refused || err[c];
+        a.cur_match = cur_match + (size_t)c * cap; a.nmatches = nmatches + c; a.status = status + c;
+    }
+    __device__ __forceinline__ void gather(int c, GatherRow &g) const
+    {
+        bool refused;
+        const orbfe_reloc_candidate r = record(c, refused);
+        g.cur_match = cur_match + (size_t)c * cap; g.pos = r.pos; g.cur_point = r.cur_point;
+        g.has_point = has_point ? has_point + (size_t)c * cap : nullptr;
+        g.Xw = Xw ? Xw + (size_t)c * cap * 3 : nullptr;
+    }
+};
+
+// One workgroup per candidate, before its window queries: found[i] = some keypoint holds map point i at entry (sAlreadyFound of
+// src/Tracking.cc:1552,1566; only with exclude_held), then the outlier clear of :1545-1547 on cur_point, and held[k] = keypoint k
+// still holds a point, the has-point flags the matcher starts from.  A cur_point outside [-1, n) is reported in err and becomes
+// -1 before anything uses it as an index.
+__global__ __launch_bounds__(1024) void kf_prepare_kernel(GridFrame f, KfBatch b)
+{
+    __shared__ int s_err;
+    const int c = blockIdx.x, tid = threadIdx.x, count = frame_count(f);
+    bool refused;
+    const orbfe_reloc_candidate r = b.record(c, refused);
+    uint8_t *found = b.found + (size_t)c * b.max_n, *held = b.held + (size_t)c * b.cap;
+    if (tid == 0) s_err = 0;
+    for (int i = tid; i < r.n; i += 1024) found[i] = 0;
+    __syncthreads(); // the flags are cleared (the workgroup's own global stores) before any is set
+    for (int k = tid; k < count; k += 1024) {
+        int p = r.cur_point ? r.cur_point[k] : -1;
+        if (p < -1 || p >= r.n) { s_err = 1; p = -1; }
+        if (p >= 0 && b.exclude_held) found[p] = 1;
+        if (r.outlier && r.outlier[k]) p = -1;
+        if (r.cur_point) r.cur_point[k] = p;
+        held[k] = p >= 0;
+    }
+    __syncthreads();
+    if (tid == 0) b.err[c] = s_err;
 }
 
 // ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
 struct orbfe_match_device_state {
-    DevBuf q, topk, n_static, ev, cells, keys_un; // grow-only scratch; calls of one context share it, so they are queued in stream order
+    DevBuf q, topk, n_static, ev, cells, keys_un, found, held, err; // grow-only scratch; calls of one context share it, so they are queued in stream order
     std::vector<unsigned> un_epoch;               // per image slot: the extraction call whose keypoints keys_un holds undistorted
     int un_ndist = 0;                             // ... with these coefficients (orbfe_set_distortion may change them between calls)
     float un_dist[5] = {0, 0, 0, 0, 0};
@@ -518,18 +659,51 @@ static int enqueue_window_resolve(orbfe_context *ctx, orbfe_match_device_state *
                                   int32_t *d_cur_match, int32_t *d_nmatches, int32_t *d_status, uint8_t *d_has_point, float *d_Xw, hipStream_t s)
 {
     const int blocks = std::max((nq + 3) / 4, (f.cap + 255) / 256); // one wave per query, and a thread per keypoint slot
-    hipLaunchKernelGGL(window_topk_kernel<Source>, dim3(blocks), dim3(256), 0, s, f, src, (MatchQuery *)st->q.p, d_qdesc, nq, d_blocked0,
-                       (unsigned long long *)st->topk.p, (int *)st->n_static.p, d_cur_match);
+    const WindowRow w = {(MatchQuery *)st->q.p, d_qdesc, nq, d_blocked0, (unsigned long long *)st->topk.p, (int *)st->n_static.p, d_cur_match};
+    hipLaunchKernelGGL(window_topk_kernel<Source>, dim3(blocks), dim3(256), 0, s, f, src, w);
     ResolveArgs a;
     a.f = f; a.q = (const MatchQuery *)st->q.p; a.qdesc = d_qdesc; a.nq = nq;
     a.topk = (const unsigned long long *)st->topk.p; a.n_static = (const int *)st->n_static.p;
     a.obs = d_obs; a.angle = d_angle; a.blocked0 = d_blocked0;
-    a.points = points; a.check_ori = check_ori; a.nnratio = nnratio;
+    a.points = points; a.th_high = TH_HIGH; a.check_ori = check_ori; a.nnratio = nnratio; a.row_err = 0;
     a.ev = (int32_t *)st->ev.p;
     a.cur_match = d_cur_match; a.nmatches = d_nmatches; a.status = d_status;
-    hipLaunchKernelGGL(resolve_kernel, dim3(1), dim3(RESOLVE_THREADS), 0, s, a);
-    if (d_has_point || (d_Xw && d_pos))
-        hipLaunchKernelGGL(gather_kernel, dim3((f.cap + 255) / 256), dim3(256), 0, s, f, (const int32_t *)d_cur_match, d_pos, d_has_point, d_Xw);
+    hipLaunchKernelGGL(resolve_kernel<OneRow>, dim3(1), dim3(RESOLVE_THREADS), 0, s, a, OneRow());
+    if (d_has_point || (d_Xw && d_pos)) {
+        const GatherRow g = {d_cur_match, d_pos, nullptr, d_has_point, d_Xw};
+        hipLaunchKernelGGL(gather_kernel<OneRow>, dim3((f.cap + 255) / 256), dim3(256), 0, s, f, g, OneRow());
+    }
+    DTRY(ctx, hipGetLastError());
+    return ORBFE_OK;
+}
+
+// The keyframe matcher for n_cands candidates: four launches whatever n_cands is
+static int enqueue_kf(orbfe_context *ctx, int slot, const float *bounds, const orbfe_reloc_candidate *d_cands, const orbfe_reloc_candidate &one, int n_cands,
+                      int max_n, int check_ori, int exclude_held, int32_t *d_cur_match, int32_t *d_nmatches, int32_t *d_status, uint8_t *d_has_point,
+                      float *d_Xw, hipStream_t s)
+{
+    orbfe_match_device_state *st = nullptr;
+    GridFrame f;
+    int rc = resident_grid(ctx, slot, bounds, false, s, st, f); // a plain GetFeaturesInArea: no mvuRight
+    if (rc != ORBFE_OK) return rc;
+    const size_t rows = (size_t)n_cands * (size_t)max_n;
+    rc = ensure_query_scratch(ctx, st, (int)rows);
+    if (rc != ORBFE_OK) return rc;
+    if (st->found.ensure(rows ? rows : 1) || st->held.ensure((size_t)n_cands * f.cap) || st->err.ensure(sizeof(int32_t) * (size_t)n_cands))
+        return orbfe_fail(ctx, ORBFE_ERR_HIP, "matcher scratch allocation failed");
+    KfBatch b;
+    b.P = projection_of(ctx, bounds);
+    b.cands = d_cands; b.one = one; b.max_n = max_n; b.cap = f.cap; b.exclude_held = exclude_held != 0;
+    b.found = (uint8_t *)st->found.p; b.held = (uint8_t *)st->held.p; b.err = (int32_t *)st->err.p;
+    b.q = (MatchQuery *)st->q.p; b.topk = (unsigned long long *)st->topk.p; b.n_static = (int *)st->n_static.p; b.ev = (int32_t *)st->ev.p;
+    b.cur_match = d_cur_match; b.nmatches = d_nmatches; b.status = d_status; b.has_point = d_has_point; b.Xw = d_Xw;
+    hipLaunchKernelGGL(kf_prepare_kernel, dim3(n_cands), dim3(1024), 0, s, f, b);
+    const int blocks = std::max((max_n + 3) / 4, (f.cap + 255) / 256);
+    hipLaunchKernelGGL(window_topk_kernel<KfBatch>, dim3(blocks, n_cands), dim3(256), 0, s, f, b, WindowRow());
+    ResolveArgs a = {};
+    a.f = f; a.points = 0; a.check_ori = check_ori != 0; a.nnratio = 0.f; // obs stays null: every accepted keypoint is closed
+    hipLaunchKernelGGL(resolve_kernel<KfBatch>, dim3(n_cands), dim3(RESOLVE_THREADS), 0, s, a, b);
+    hipLaunchKernelGGL(gather_kernel<KfBatch>, dim3((f.cap + 255) / 256, n_cands), dim3(256), 0, s, f, GatherRow(), b);
     DTRY(ctx, hipGetLastError());
     return ORBFE_OK;
 }
@@ -593,6 +767,42 @@ try {
     const PointsSource src = {projection_of(ctx, bounds), d_pts, th};
     return enqueue_window_resolve(ctx, st, f, src, n_pts, d_pt_desc, d_pt_obs, nullptr, d_cur_has_obs, 1, 0, nnratio, d_pt_pos, d_cur_match, d_nmatches,
                                   d_status, d_has_point, d_Xw, s);
+} ORBFE_CATCH(ctx)
+
+extern "C" int orbfe_enqueue_search_by_projection_kf(orbfe_context *ctx, int slot, const float *bounds, const float *d_Tcw, int n_kf, const float *d_kf_pos,
+                                                     const uint8_t *d_kf_desc, const int32_t *d_kf_valid, const float *d_kf_angle,
+                                                     const float *d_kf_max_distance, const float *d_kf_min_distance, int32_t *d_cur_point,
+                                                     const uint8_t *d_outlier, float th, int orb_dist, int check_ori, int exclude_held,
+                                                     int32_t *d_cur_match, int32_t *d_nmatches, int32_t *d_status, uint8_t *d_has_point, float *d_Xw,
+                                                     void *stream)
+try {
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    ORBFE_ENTRY(ctx);
+    if (!bounds || !d_Tcw || !d_cur_point || !d_cur_match || !d_nmatches || !d_status || n_kf < 0 ||
+        (n_kf > 0 && (!d_kf_pos || !d_kf_desc || !d_kf_valid || !d_kf_angle || !d_kf_max_distance || !d_kf_min_distance)))
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
+    if (n_kf > (1 << 20)) return orbfe_fail(ctx, ORBFE_ERR_CAPACITY, "%d keyframe points: the matcher's scratch rows hold 2^20", n_kf);
+    const orbfe_reloc_candidate one = {d_Tcw, d_kf_pos, d_kf_desc, d_kf_valid, d_kf_angle, d_kf_max_distance, d_kf_min_distance, d_cur_point, d_outlier,
+                                       n_kf, th, orb_dist, 0};
+    return enqueue_kf(ctx, slot, bounds, nullptr, one, 1, n_kf, check_ori, exclude_held, d_cur_match, d_nmatches, d_status, d_has_point, d_Xw,
+                      stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx));
+} ORBFE_CATCH(ctx)
+
+extern "C" int orbfe_enqueue_search_by_projection_kf_batch(orbfe_context *ctx, int slot, const float *bounds, const orbfe_reloc_candidate *d_cands, int n_cands,
+                                                           int max_n_kf, int check_ori, int exclude_held, int32_t *d_cur_match, int32_t *d_nmatches,
+                                                           int32_t *d_status, uint8_t *d_has_point, float *d_Xw, void *stream)
+try {
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    ORBFE_ENTRY(ctx);
+    if (!bounds || n_cands < 0 || n_cands > 65535 || max_n_kf < 0 || (n_cands > 0 && (!d_cands || !d_cur_match || !d_nmatches || !d_status)))
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument or count out of range");
+    if (slot < 0 || slot >= orbfe_ctx_last_images(ctx))
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d: the latest extraction call filled %d image slots", slot, orbfe_ctx_last_images(ctx));
+    if ((long long)n_cands * max_n_kf > (1ll << 20))
+        return orbfe_fail(ctx, ORBFE_ERR_CAPACITY, "%d candidates x %d points: the matcher's scratch rows hold 2^20", n_cands, max_n_kf);
+    if (n_cands == 0) return ORBFE_OK;
+    return enqueue_kf(ctx, slot, bounds, d_cands, orbfe_reloc_candidate(), n_cands, max_n_kf, check_ori, exclude_held, d_cur_match, d_nmatches, d_status,
+                      d_has_point, d_Xw, stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx));
 } ORBFE_CATCH(ctx)
 
 extern "C" int orbfe_device_keys_un(orbfe_context *ctx, int slot, const orbfe_keypoint **d_keys_un, void *stream)

@@ -175,7 +175,29 @@ static inline int build_queries_points(const float *sf, int nlevels, int n_pts, 
     return 0;
 }
 
-// ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist), src/ORBmatcher.cc:1484-1527
+// ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist), src/ORBmatcher.cc:1484-1527: the loop body for one
+// map point of the keyframe (ow = camera_center(Tcw_cur); valid = pMP && !pMP->isBad() && !sAlreadyFound.count(pMP)).
+// Q must hold NO_QUERY; returns 1 when the point opens a window.
+ORBFE_RESOLVE_HD static inline int query_kf_point(const Camera &C, const float *sf, int nlevels, float log_sf, float min_x, float max_x, float min_y,
+                                                  float max_y, const float *Tcw_cur, const float *ow, const float *pos, int valid, float max_distance,
+                                                  float min_distance, float th, MatchQuery &Q)
+{
+    if (!valid) return 0;
+    float xc[3];
+    rt_apply(Tcw_cur, pos, xc);
+    const float invzc = (float)(1.0 / (double)xc[2]);
+    const float u = C.fx * xc[0] * invzc + C.cx;
+    const float v = C.fy * xc[1] * invzc + C.cy;
+    if (u < min_x || u > max_x) return 0;
+    if (v < min_y || v > max_y) return 0;
+    float po[3];
+    for (int k = 0; k < 3; k++) po[k] = pos[k] - ow[k];
+    const float dist3d = norm3(po);
+    if (dist3d < 0.8f * min_distance || dist3d > 1.2f * max_distance) return 0;
+    const int lvl = predict_scale(max_distance, dist3d, log_sf, nlevels);
+    Q.u = u; Q.v = v; Q.r = th * sf[lvl]; Q.min_level = lvl - 1; Q.max_level = lvl + 1; Q.flags = 1;
+    return 1;
+}
 static inline void build_queries_kf(const Camera &C, const float *sf, int nlevels, float log_sf, float min_x, float max_x, float min_y, float max_y,
                                     const float *Tcw_cur, int n_kf, const float *kf_pos, const uint8_t *kf_desc, const int32_t *kf_valid,
                                     const float *kf_max_distance, const float *kf_min_distance, float th, std::vector<MatchQuery> &q,
@@ -185,24 +207,10 @@ static inline void build_queries_kf(const Camera &C, const float *sf, int nlevel
     camera_center(Tcw_cur, ow);
     q.assign(n_kf > 0 ? n_kf : 0, NO_QUERY);
     qd.assign((size_t)32 * (n_kf > 0 ? n_kf : 1), 0);
-    for (int i = 0; i < n_kf; i++) {
-        MatchQuery &Q = q[i];
-        if (!kf_valid[i]) continue;
-        float xc[3];
-        rt_apply(Tcw_cur, kf_pos + 3 * i, xc);
-        const float invzc = (float)(1.0 / (double)xc[2]);
-        const float u = C.fx * xc[0] * invzc + C.cx;
-        const float v = C.fy * xc[1] * invzc + C.cy;
-        if (u < min_x || u > max_x) continue;
-        if (v < min_y || v > max_y) continue;
-        float po[3];
-        for (int k = 0; k < 3; k++) po[k] = kf_pos[3 * i + k] - ow[k];
-        const float dist3d = norm3(po);
-        if (dist3d < 0.8f * kf_min_distance[i] || dist3d > 1.2f * kf_max_distance[i]) continue;
-        const int lvl = predict_scale(kf_max_distance[i], dist3d, log_sf, nlevels);
-        Q.u = u; Q.v = v; Q.r = th * sf[lvl]; Q.min_level = lvl - 1; Q.max_level = lvl + 1; Q.flags = 1;
-        memcpy(&qd[(size_t)32 * i], kf_desc + (size_t)32 * i, 32);
-    }
+    for (int i = 0; i < n_kf; i++)
+        if (query_kf_point(C, sf, nlevels, log_sf, min_x, max_x, min_y, max_y, Tcw_cur, ow, kf_pos + 3 * i, kf_valid[i], kf_max_distance[i],
+                           kf_min_distance[i], th, q[i]) > 0)
+            memcpy(&qd[(size_t)32 * i], kf_desc + (size_t)32 * i, 32);
 }
 
 // ORBmatcher::SearchForInitialization, src/ORBmatcher.cc:414-421

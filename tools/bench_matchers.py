@@ -22,6 +22,12 @@ slot 0 against K = 1, 4, 16 candidate keyframes of 1500 descriptors (the scene's
 ratio 0.7, rotation check on.  Per K: orbfe_enqueue_search_by_bow queued K times + one stream synchronise, and -- when the library
 has it -- orbfe_enqueue_search_by_bow_batch + one stream synchronise, each as wall time and as GPU time between two events.  --lib
 loads another build of the library (the parent commit's, for the baseline leg) under the same Python package.
+    python3 tools/bench_matchers.py --reloc [--lib path/to/another/liborbfe.so]
+runs only the refinement rows of Relocalization (profiles/reloc_projection_batch.json): a real extracted frame of about 2000 keypoints
+resident in slot 0 against 8 candidate keyframes of about 2000 map points (one per keypoint; candidate k sees them from a pose of its
+own), th 10, ORBdist 100, rotation check on, nothing held.  (a) 8 synchronous resident orbfe_search_by_projection_kf calls; (b) -- when
+the library has it -- one orbfe_enqueue_search_by_projection_kf_batch + one stream synchronise, as wall time and as GPU time between
+two events.  Five repeats of each, interleaved; every repeat is the mean of 50 calls.
 """
 import json
 import os
@@ -448,6 +454,103 @@ def bow_batch_rows(out):
     ctx.close()
 
 
+def reloc_rows(out):
+    """Rows of --reloc; arguments prepared once, C ABI called directly."""
+    import ctypes as C
+    import torch
+    from orbslam2_amd import api, synth
+    vp = C.c_void_p
+    P = lambda a: a.ctypes.data_as(vp)
+    dev = torch.device("cuda:0")
+    up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, t).view(np.uint8).reshape(-1)).to(dev)
+    ctx = api.Context(width=TM.W, height=TM.H, nfeatures=2000, fx=TM.FX, fy=TM.FY, cx=TM.CX, cy=TM.CY, bf=TM.BF)
+    L = ctx.L
+    have = hasattr(L, "orbfe_enqueue_search_by_projection_kf_batch")
+    K, REPS, REPEATS = 8, 50, 5
+    left, right = synth.stereo_pair(TM.W, TM.H, seed=77)
+    fr = ctx.stereo_frame(left, right)
+    fk, fd, fur = fr["kps_left"], fr["desc_left"], fr["u_right"]
+    fs = TM._frame_scene(fk, fd, fur, 77, all_points=True)
+    fb = (0.0, float(TM.W), 0.0, float(TM.H))
+    sf = O.Extractor().scale_factors()
+    n, nk, cap = len(fs["pos"]), len(fk), ctx.capacity
+    dist0 = np.linalg.norm(fs["pos"], axis=1).astype(np.float32)
+    max_d = (dist0 * sf[fs["octave"]]).astype(np.float32); min_d = (max_d / sf[TM.NL - 1]).astype(np.float32)
+    rng = np.random.default_rng(11)
+    poses = []
+    for k in range(K):  # candidate k: the scene's pose moved by a few centimetres
+        T = np.eye(4, dtype=np.float32); T[:3] = fs["T_cur"]
+        if k:
+            T[:3, 3] += rng.normal(0, 0.02, 3).astype(np.float32)
+        poses.append(T)
+    host = [np.ascontiguousarray(x, t) for x, t in ((fs["pos"], np.float32), (fs["desc"], np.uint8), (fs["valid"], np.int32), (fs["angle"], np.float32),
+                                                    (max_d, np.float32), (min_d, np.float32))]
+    has0 = np.zeros(nk, np.uint8)
+    view = ctx._view(fk, None, fd, fb, device_slot=0)
+    sync_out = [np.zeros(max(nk, 1), np.int32) for _ in range(K)]
+    sync_nm = [C.c_int() for _ in range(K)]
+    sync_args = [(ctx.h, C.byref(view), P(poses[k]), n, *[P(a) for a in host], P(has0), C.c_float(10.0), 100, 1, P(sync_out[k]), C.byref(sync_nm[k])) for k in range(K)]
+
+    def sync_calls():
+        for a in sync_args:
+            assert L.orbfe_search_by_projection_kf(*a) == 0
+
+    sync_calls()
+    out["scene"] = "%d keypoints extracted from a synthetic 640x480 pair, %d candidates of %d map points, th 10, ORBdist 100, rotation check on; matches per candidate %d .. %d" % (
+        nk, K, n, min(x.value for x in sync_nm), max(x.value for x in sync_nm))
+    a_rows, b_wall, b_gpu = [], [], []
+    if have:
+        L.orbfe_enqueue_search_by_projection_kf_batch.restype = C.c_int
+        L.orbfe_enqueue_search_by_projection_kf_batch.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 6
+        d_host = [up(a, a.dtype) for a in host]
+        d_T = up(np.stack(poses), np.float32)
+        d_cp = torch.full((K, cap), -1, dtype=torch.int32, device=dev)
+        d_clear = torch.ones(cap, dtype=torch.uint8, device=dev)  # every keypoint an outlier: each call starts with nothing held, as (a) does
+        recs = (api.RelocCandidate * K)()
+        for k in range(K):
+            recs[k] = api.RelocCandidate(d_T.data_ptr() + 64 * k, *[x.data_ptr() for x in d_host], d_cp.data_ptr() + 4 * cap * k, d_clear.data_ptr(), n, 10.0, 100, 0)
+        d_recs = up(np.frombuffer(bytes(recs), np.uint8), np.uint8)
+        o_match = torch.zeros((K, cap), dtype=torch.int32, device=dev)
+        o_nm = torch.zeros(K, dtype=torch.int32, device=dev); o_st = torch.zeros(K, dtype=torch.int32, device=dev)
+        st = torch.cuda.Stream()
+        sp = vp(st.cuda_stream)
+        bounds = (C.c_float * 4)(*fb)
+        b_args = (ctx.h, 0, bounds, vp(d_recs.data_ptr()), K, n, 1, 0, vp(o_match.data_ptr()), vp(o_nm.data_ptr()), vp(o_st.data_ptr()), None, None, sp)
+        torch.cuda.synchronize()
+
+        def enqueue():
+            assert L.orbfe_enqueue_search_by_projection_kf_batch(*b_args) == 0
+
+        def batch_call():
+            enqueue()
+            assert L.orbfe_synchronize(ctx.h, sp) == 0
+
+        for rep in range(2):  # the second call starts from the cur_point rows the first one left
+            batch_call()
+            m, nm = o_match.cpu().numpy(), o_nm.cpu().numpy()
+            for k in range(K):
+                assert int(o_st[k].item()) == 0 and nm[k] == sync_nm[k].value and np.array_equal(m[k, :nk], sync_out[k][:nk]), (rep, k)
+    for _ in range(REPEATS):
+        a_rows.append(round(timeit(sync_calls, REPS), 4))
+        if have:
+            b_wall.append(round(timeit(batch_call, REPS), 4))
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            for _ in range(REPS):
+                enqueue()
+            e1.record(st)
+            st.synchronize()
+            b_gpu.append(round(e0.elapsed_time(e1) / REPS, 4))
+    out["rows"]["(a) orbfe_search_by_projection_kf x %d, synchronous resident calls, wall time" % K] = {"ms_per_repeat": a_rows}
+    if have:
+        out["rows"]["(b) orbfe_enqueue_search_by_projection_kf_batch of %d + one stream synchronise, wall time" % K] = {"ms_per_repeat": b_wall}
+        out["rows"]["(b) the same call, GPU time of its kernels between two events (50 calls queued back to back)"] = {"ms_per_repeat": b_gpu}
+        out["max (b) < min (a)"] = bool(max(b_wall) < min(a_rows))
+    else:
+        out["batch"] = "not exported by this library"
+    ctx.close()
+
+
 def load_other_build(api, path):
     """api.load() on the library at `path`, which may be older than the package: the prototypes load() sets for entry points
     that build lacks land on stand-ins that are not kept, so hasattr(lib, name) is False afterwards and a call fails loudly."""
@@ -476,6 +579,12 @@ def main():
     from orbslam2_amd import api
     if "--lib" in sys.argv[1:]:  # another build of the library under this package (load() has not run yet)
         load_other_build(api, os.path.abspath(sys.argv[sys.argv.index("--lib") + 1]))
+    if "--reloc" in sys.argv[1:]:
+        out = {"unit": "ms per group of 8 candidates", "rows": {}}
+        reloc_rows(out)
+        out["build_id"] = api.build_id()
+        print(json.dumps(out, indent=1))
+        return
     if "--bow-batch" in sys.argv[1:]:
         out = {"unit": "ms per call", "rows": {}}
         bow_batch_rows(out)
