@@ -693,6 +693,41 @@ int orbfe_enqueue_search_by_bow_batch(orbfe_context *ctx, int slot,
         int32_t *d_f_match /* [n_kfs][capacity] */, int32_t *d_nmatches /* [n_kfs] */, int32_t *d_status /* [n_kfs] */,
         uint8_t *d_has_point /* [n_kfs][capacity], may be NULL */, float *d_Xw /* [n_kfs][capacity][3], may be NULL */,
         void *stream);
+/* One keyframe of orbfe_enqueue_search_for_triangulation: the per-keyframe arguments of orbfe_search_for_triangulation as device
+ * arrays that the keyframe owns, uploaded once when it is made (descriptors, keypoints and mvuRight of a keyframe never change;
+ * has_mp is patched when a map point is added or erased).  Every pointer is a device pointer.  64 bytes. */
+typedef struct orbfe_tri_keyframe {
+    const uint32_t *nodes; const int32_t *off; const int32_t *feat;   /* mFbowFeatVec as CSR (orbfe_bow_maps / orbfe_enqueue_compute_bow); nodes ascend strictly */
+    const orbfe_keypoint *keys_un;        /* mvKeysUn: x, y, octave, angle are read */
+    const float   *u_right;               /* mvuRight, < 0 = monocular keypoint */
+    const uint8_t *has_mp;                /* GetMapPoint(i) != NULL -- bad or not, unlike orbfe_bow_keyframe.valid */
+    const uint8_t *desc;                  /* 32 bytes per keypoint */
+    int32_t nnodes, n;
+} orbfe_tri_keyframe;
+/* ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:652-819) on two device-resident keyframes, asynchronous on `stream` (NULL:
+ * the context's stream) under the contract of the enqueue matchers above: nothing waits for the GPU, nothing is copied from host
+ * memory on the stream.  kf1 / kf2 are HOST structs holding device pointers; F12 (3x3), Cw1 (3) and T2w (3x4), row major, are HOST
+ * arrays read before the call returns (they travel as kernel arguments, and the epipole of :658-664 is computed on the host by the
+ * expression the synchronous call uses).  Scale factors and mvLevelSigma2 are the context's; no vocabulary is needed and no image
+ * slot is read.  The calls of one context share scratch memory (here KF2's "already matched" flags, reset on the stream by every
+ * call): queue them on one stream.
+ * Outputs (device): d_match12[kf1->n] = KF2 keypoint or -1; d_pairs, optional, [2 * min(n1, n2)]: vMatchedPairs (:808-816) as
+ * (idx1, idx2) in ascending idx1, entries from 2 * count on untouched; d_nmatches[1]; d_status[1].  Every result equals
+ * orbfe_search_for_triangulation on the same inputs.
+ * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:237-268) calls this once per neighbour and adds the triangulated points to
+ * KF1 between two neighbours, so kf1->has_mp is an array the caller patches ON THE STREAM between two calls; that dependence is
+ * why there is no batch over neighbours.
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL record, matrix or output other than d_pairs, a negative n or
+ * nnodes, n > 65535, a NULL array in a record with nnodes > 0.  d_status = ORBFE_ERR_INVALID for what only the device can see: node
+ * ids not strictly ascending, a CSR offset negative, descending or beyond n, a feature index outside [0, n), an octave outside
+ * [0, nlevels) on a KF2 keypoint that is a candidate, a rotation bin outside [0, 30) (angles outside [0, 360)).  Each is checked
+ * before it is used as an address and that node / entry is skipped; the other outputs are then not meaningful, but nothing is
+ * written outside d_match12[0, n1), d_pairs, the count and the status. */
+int orbfe_enqueue_search_for_triangulation(orbfe_context *ctx, const orbfe_tri_keyframe *kf1, const orbfe_tri_keyframe *kf2,
+        const float *F12, const float *Cw1, const float *T2w, float fx2, float fy2, float cx2, float cy2,
+        int only_stereo, int check_ori,
+        int32_t *d_match12 /* [kf1->n] */, int32_t *d_pairs /* [2 * min(n1, n2)], may be NULL */,
+        int32_t *d_nmatches, int32_t *d_status, void *stream);
 /* KeyFrameDatabase::DetectLoopCandidates(KeyFrame *pKF, float minScore) (src/KeyFrameDatabase.cc:73-194; LoopClosing::DetectLoop,
  * src/LoopClosing.cc:131).  connected[k] != 0 marks the keyframes of pKF->GetConnectedKeyFrames() (may be NULL: none); covisibility
  * lists as for the relocalisation query.  Stateless: mLoopScore is only read for keyframes scored by the same call. */

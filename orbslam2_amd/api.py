@@ -39,6 +39,7 @@ EXPORTS = [
     "orbfe_enqueue_search_by_projection_last", "orbfe_enqueue_is_in_frustum", "orbfe_enqueue_search_by_projection_points", "orbfe_device_keys_un",
     "orbfe_enqueue_compute_bow", "orbfe_enqueue_search_by_bow", "orbfe_enqueue_search_by_bow_batch",
     "orbfe_enqueue_search_by_projection_kf", "orbfe_enqueue_search_by_projection_kf_batch",
+    "orbfe_enqueue_search_for_triangulation",
 ]
 NUM_STAGES = 8
 STAGE_NAMES = ["ingest", "pyramid", "blur", "fast", "octree", "describe", "stereo_match", "stereo_median"]  # orbfe_stage_name()
@@ -70,6 +71,15 @@ class BowKeyframe(C.Structure):
     """orbfe_bow_keyframe (include/orbfe.h): one candidate keyframe of enqueue_search_by_bow_batch, device pointers."""
     _fields_ = [("nodes", C.c_void_p), ("off", C.c_void_p), ("feat", C.c_void_p), ("valid", C.c_void_p), ("desc", C.c_void_p),
                 ("angle", C.c_void_p), ("pos", C.c_void_p), ("nnodes", C.c_int32), ("n", C.c_int32)]
+
+
+class TriKeyframe(C.Structure):
+    """orbfe_tri_keyframe (include/orbfe.h): one keyframe of enqueue_search_for_triangulation, device pointers."""
+    _fields_ = [("nodes", C.c_void_p), ("off", C.c_void_p), ("feat", C.c_void_p), ("keys_un", C.c_void_p), ("u_right", C.c_void_p),
+                ("has_mp", C.c_void_p), ("desc", C.c_void_p), ("nnodes", C.c_int32), ("n", C.c_int32)]
+
+
+assert C.sizeof(TriKeyframe) == 64
 
 
 class RelocCandidate(C.Structure):
@@ -225,6 +235,9 @@ def load():
     L.orbfe_enqueue_search_by_projection_kf.argtypes = [vp, C.c_int, vp, vp, C.c_int] + [vp] * 8 + [C.c_float, C.c_int, C.c_int, C.c_int] + [vp] * 6
     L.orbfe_enqueue_search_by_projection_kf_batch.restype = C.c_int
     L.orbfe_enqueue_search_by_projection_kf_batch.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 6
+    L.orbfe_enqueue_search_for_triangulation.restype = C.c_int
+    L.orbfe_enqueue_search_for_triangulation.argtypes = [vp, C.POINTER(TriKeyframe), C.POINTER(TriKeyframe), vp, vp, vp] + [C.c_float] * 4 + \
+        [C.c_int, C.c_int] + [vp] * 5
     _lib = L
     return L
 
@@ -643,6 +656,18 @@ class Context:
         self._check(self.L.orbfe_enqueue_search_by_bow_batch(
             self.h, slot, v(d_kfs or None), n_kfs, max_kf_nnodes, v(d_f_nodes), v(d_f_off), v(d_f_feat), v(d_f_n_nodes), nnratio, int(check_ori),
             v(d_f_match), v(d_nmatches), v(d_status), v(d_has_point or None), v(d_Xw or None), v(stream or None)))
+
+    def enqueue_search_for_triangulation(self, kf1, kf2, F12, Cw1, T2w, fx2, fy2, cx2, cy2, only_stereo, check_ori,
+                                         d_match12, d_nmatches, d_status, d_pairs=0, stream=0):
+        """ORBmatcher::SearchForTriangulation on two device-resident keyframes (TriKeyframe records on the host, device pointers inside),
+        asynchronous on `stream`.  F12 (3x3), Cw1 (3), T2w (3x4) are host arrays read before the call returns.  One call per neighbour:
+        the caller patches kf1.has_mp on the stream between two calls (CreateNewMapPoints adds points in between)."""
+        v = C.c_void_p
+        f = np.ascontiguousarray(F12, np.float32); c = np.ascontiguousarray(Cw1, np.float32); t = np.ascontiguousarray(T2w, np.float32)
+        assert f.size == 9 and c.size == 3 and t.size == 12
+        self._check(self.L.orbfe_enqueue_search_for_triangulation(
+            self.h, C.byref(kf1), C.byref(kf2), _p(f), _p(c), _p(t), fx2, fy2, cx2, cy2, int(only_stereo), int(check_ori),
+            v(d_match12 or None), v(d_pairs or None), v(d_nmatches or None), v(d_status or None), v(stream or None)))
 
     def search_by_projection_kf(self, view, Tcw_cur, kf_pos, kf_desc, kf_valid, kf_angle, kf_max_distance, kf_min_distance, cur_has_point,
                                 th, orb_dist, check_ori):

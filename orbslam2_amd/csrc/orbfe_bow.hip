@@ -13,6 +13,7 @@
 #include "orbfe_device.h"
 #include "orbfe_host.h"
 #include "orbfe_bow_vocab.h"
+#include "orbfe_epipolar.h"
 
 #include <algorithm>
 #include <cmath>
@@ -682,19 +683,8 @@ try {
 // ---------------------------------------------------------------------------------------------
 // ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:652-819; LocalMapping::CreateNewMapPoints)
 // ---------------------------------------------------------------------------------------------
-// ORBmatcher::CheckDistEpipolarLine (:138-155): float arithmetic left to right, the last comparison in double
-static bool check_dist_epipolar_line(float x1, float y1, float x2, float y2, const float *F12, float sigma2_kp2)
-{
-    const float a = x1 * F12[0] + y1 * F12[3] + F12[6];
-    const float b = x1 * F12[1] + y1 * F12[4] + F12[7];
-    const float c = x1 * F12[2] + y1 * F12[5] + F12[8];
-    const float num = a * x2 + b * y2 + c;
-    const float den = a * a + b * b;
-    if (den == 0) return false;
-    const float dsqr = num * num / den;
-    return (double)dsqr < 3.84 * (double)sigma2_kp2;
-}
-
+// the epipole, its exclusion disc and CheckDistEpipolarLine (:138-155) are orbfe_epipolar.h's: one text with the device-resident
+// form (orbfe_enqueue_search_for_triangulation, orbfe_bow_device.hip)
 extern "C" int orbfe_search_for_triangulation(orbfe_context *ctx,
                                               const uint32_t *nodes1, const int32_t *off1, const int32_t *feat1, int nnodes1,
                                               const orbfe_keypoint *keys1, const float *u_right1, const uint8_t *has_mp1, const uint8_t *desc1, int n1,
@@ -714,15 +704,8 @@ try {
     const float *scale = orbfe_ctx_scale_factors(ctx);
     for (int j = 0; j < n1; j++) match12[j] = -1;
     *nmatches = 0;
-    // epipole in the second image (:658-664): cv::Mat R*x+t in float, small-matrix evaluation order
-    float C2[3];
-    for (int i = 0; i < 3; i++) {
-        const float t = (T2w[4 * i] * Cw1[0] + T2w[4 * i + 1] * Cw1[1]) + T2w[4 * i + 2] * Cw1[2];
-        C2[i] = t + T2w[4 * i + 3];
-    }
-    const float invz = 1.0f / C2[2];
-    const float ex = fx2 * C2[0] * invz + cx2;
-    const float ey = fy2 * C2[1] * invz + cy2;
+    float ex, ey; // epipole in the second image (:658-664)
+    orbfe_epipolar::epipole(Cw1, T2w, fx2, fy2, cx2, cy2, &ex, &ey);
     // pairs of the shared nodes whose endpoints pass the per-keypoint filters; Hamming distances on the device
     struct Seg { int a, b, pair0; };
     std::vector<Seg> segs;
@@ -786,11 +769,8 @@ try {
                 if (matched2[idx2]) continue;
                 if (d > TH_LOW || d > best_dist) continue;
                 const bool stereo2 = u_right2[idx2] >= 0;
-                if (!stereo1 && !stereo2) {
-                    const float distex = ex - keys2[idx2].x, distey = ey - keys2[idx2].y;
-                    if (distex * distex + distey * distey < 100 * scale[keys2[idx2].octave]) continue;
-                }
-                if (check_dist_epipolar_line(keys1[idx1].x, keys1[idx1].y, keys2[idx2].x, keys2[idx2].y, F12, sigma2[keys2[idx2].octave])) {
+                if (!stereo1 && !stereo2 && orbfe_epipolar::inside_epipole_disc(ex, ey, keys2[idx2].x, keys2[idx2].y, scale[keys2[idx2].octave])) continue;
+                if (orbfe_epipolar::check_dist_epipolar_line(keys1[idx1].x, keys1[idx1].y, keys2[idx2].x, keys2[idx2].y, F12, sigma2[keys2[idx2].octave])) {
                     best_idx2 = idx2;
                     best_dist = d;
                 }

@@ -23,11 +23,19 @@
 // orbfe_enqueue_search_by_bow_batch (Relocalization, src/Tracking.cc:1445-1476: the candidates are independent), the same three
 // launches for all keyframes: bow_*_batch_kernel run the same device functions on a BowSearch built from record blockIdx.y
 // (tail: blockIdx.x) of the caller's orbfe_bow_keyframe array and that row of the outputs.
+// orbfe_enqueue_search_for_triangulation (ORBmatcher::SearchForTriangulation, src/ORBmatcher.cc:652-819; the synchronous form is in
+// orbfe_bow.hip), both keyframes device-resident, three launches:
+//   tri_init_kernel              match12 = -1, status, count, the KF2 "taken" flags in scratch
+//   tri_node_match_kernel        one wave per KF1 node, the shape of bow_node_match with the acceptance rule of :731-779: Hamming <= TH_LOW,
+//                                epipole disc, CheckDistEpipolarLine (orbfe_epipolar.h), last of the equal minima, no ratio test
+//   tri_tail_kernel              rotation histogram, ComputeThreeMaxima, the count, vMatchedPairs by an ordered compaction
+// One call per neighbour, never a batch: CreateNewMapPoints adds points to KF1 between two neighbours.
 #include "../../include/orbfe.h"
 #include "orbfe_device.h"
 #include "orbfe_host.h"
 #include "orbfe_bow_vocab.h"
 #include "orbfe_match_resolve.h"
+#include "orbfe_epipolar.h"
 
 #include <cmath>
 
@@ -285,6 +293,23 @@ __device__ __forceinline__ int hamming256(const uint32_t *a, const uint32_t *b)
     return d;
 }
 
+// First of the n ascending node ids that is >= id (n: none), by the whole wave: the lanes probe 64 places at once, the range
+// shrinks 64-fold per load.
+__device__ __forceinline__ int bow_lower_bound(const uint32_t *__restrict__ nodes, int n, uint32_t id, int lane)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int step = (hi - lo + 63) >> 6;
+        const int p = lo + lane * step;
+        const int c = __popcll(__ballot(p < hi && nodes[p] < id)); // probes below id: a prefix of the lanes
+        if (c == 0) { hi = lo; break; }
+        const int top = lo + c * step;
+        lo += (c - 1) * step + 1;
+        hi = top < hi ? top : hi;
+    }
+    return lo;
+}
+
 // One wave per keyframe node.  Position j of the node's frame features belongs to lane j & 63 (its chunk j >> 6); the flag "frame
 // keypoint already matched" of chunk c < BOW_FLAG_CHUNKS is bit c of the lane's `taken`, of a later chunk it is f_match itself,
 // which only this lane wrote (every frame keypoint lies in one node).  A lane's candidates come in list order, so its running
@@ -304,16 +329,7 @@ __device__ __forceinline__ void bow_node_match(const BowSearch &a)
         if (lane == 0) *a.status = ORBFE_ERR_INVALID;
         return;
     }
-    int lo = 0, hi = nfn; // first frame node >= id: the lanes probe 64 places at once, the range shrinks 64-fold per load
-    while (lo < hi) {
-        const int step = (hi - lo + 63) >> 6;
-        const int p = lo + lane * step;
-        const int c = __popcll(__ballot(p < hi && a.f_nodes[p] < id)); // probes below id: a prefix of the lanes
-        if (c == 0) { hi = lo; break; }
-        const int top = lo + c * step;
-        lo += (c - 1) * step + 1;
-        hi = top < hi ? top : hi;
-    }
+    const int lo = bow_lower_bound(a.f_nodes, nfn, id, lane);
     if (lo >= nfn || a.f_nodes[lo] != id) return;
     const int k0 = a.kf_off[node], k1 = a.kf_off[node + 1];
     const int f0 = a.f_off[lo], f1 = a.f_off[lo + 1];
@@ -553,6 +569,272 @@ try {
     hipLaunchKernelGGL(bow_match_init_batch_kernel, dim3((cap + 255) / 256, n_kfs), dim3(256), 0, s, a, d_kfs, max_kf_nnodes);
     if (max_kf_nnodes > 0) hipLaunchKernelGGL(bow_node_match_batch_kernel, dim3((max_kf_nnodes + 3) / 4, n_kfs), dim3(256), 0, s, a, d_kfs, max_kf_nnodes);
     hipLaunchKernelGGL(bow_match_tail_batch_kernel, dim3(n_kfs), dim3(1024), 0, s, a, d_kfs, max_kf_nnodes);
+    WTRY(ctx, hipGetLastError());
+    return ORBFE_OK;
+} ORBFE_CATCH(ctx)
+
+// ---------------------------------------------------------------------------------------------
+// SearchForTriangulation(KeyFrame*, KeyFrame*) (src/ORBmatcher.cc:652-819)
+// ---------------------------------------------------------------------------------------------
+#define TRI_REG_CHUNKS 2   // a lane keeps descriptor, position, level thresholds and stereo bit of its first two KF2 features of a node in registers
+#define TRI_FLAG_CHUNKS 64 // and the "taken" flags of its first 64 in one 64-bit register; later ones live in TriSearch::taken2
+
+static_assert(sizeof(orbfe_tri_keyframe) == 64, "orbfe_tri_keyframe: seven pointers and two counts");
+static_assert(sizeof(orbfe_keypoint) == sizeof(KeyPointPOD), "orbfe_keypoint is the extraction's keypoint record");
+
+struct TriSearch {
+    orbfe_tri_keyframe k1, k2;
+    float F12[9], ex, ey;                                         // the three small matrices travel as kernel arguments; the epipole is the host's
+    float scale[ORBFE_MAX_LEVELS], sigma2[ORBFE_MAX_LEVELS];      // mvScaleFactors, mvLevelSigma2
+    int nlevels, only_stereo, check_ori;
+    int32_t *match12, *pairs, *nmatches, *status;
+    uint8_t *taken2;                                              // [k2.n] scratch: vbMatched2 beyond the lane-held flags, zeroed by every call
+};
+
+__global__ __launch_bounds__(256) void tri_init_kernel(TriSearch a)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k == 0) { *a.status = ORBFE_OK; *a.nmatches = 0; }
+    if (k < a.k1.n) a.match12[k] = -1;
+    if (k < a.k2.n) a.taken2[k] = 0;
+}
+
+// What a lane knows of one KF2 feature of the node: idx < 0 is no candidate (beyond the list, refused, has a map point, monocular
+// under only_stereo).
+struct TriCand {
+    int idx;
+    uint32_t d[8];
+    float x, y, scale, sigma2;
+    bool stereo;
+};
+
+// Feature `j` of the node's KF2 list.  Every index is checked before it is used as an address; `bad` collects what is refused.
+__device__ __forceinline__ void tri_load_cand(const TriSearch &a, int f0, int nf, int j, TriCand &c, bool &bad)
+{
+    c.idx = -1; c.x = c.y = 0.f; c.scale = c.sigma2 = 1.f; c.stereo = false;
+#pragma unroll
+    for (int k = 0; k < 8; k++) c.d[k] = 0u;
+    if (j >= nf) return;
+    const int idx = a.k2.feat[f0 + j];
+    if (idx < 0 || idx >= a.k2.n) { bad = true; return; }
+    if (a.k2.has_mp[idx]) return;
+    const bool stereo = a.k2.u_right[idx] >= 0;
+    if (a.only_stereo && !stereo) return;
+    const orbfe_keypoint *kp = a.k2.keys_un + idx;
+    const int octave = kp->octave;
+    if (octave < 0 || octave >= a.nlevels) { bad = true; return; }
+    c.idx = idx; c.stereo = stereo; c.x = kp->x; c.y = kp->y; c.scale = a.scale[octave]; c.sigma2 = a.sigma2[octave];
+#pragma unroll
+    for (int k = 0; k < 8; k++) c.d[k] = ((const uint32_t *)(a.k2.desc + (size_t)idx * 32))[k];
+}
+
+// One wave per KF1 node.  A KF2 keypoint lies in one node of KF2's feature vector, so vbMatched2 (:748, :800) is read and written
+// only by the KF1 features of the same node: the rule is sequential inside a node and nowhere else.  The wave takes the node's usable
+// KF1 features in list order; position j of the node's KF2 list belongs to lane j & 63 (chunk j >> 6).  The flag "KF2 keypoint
+// taken" of chunk c < TRI_FLAG_CHUNKS is bit c of the lane's `taken`, of a later chunk it is taken2[idx2], which only this lane
+// touches.  The reference's inner loop (:731-779) keeps the LAST candidate of the smallest distance that passes every gate
+// (`dist > bestDist` skips, bestDist starts at TH_LOW, and bestDist only moves when CheckDistEpipolarLine accepts): a lane's
+// candidates come in list order, so `d <= d1` keeps its last minimum, and the wave's winner is the smallest key
+// d << 16 | (0xffff - position).  No ratio test.
+__global__ __launch_bounds__(256) void tri_node_match_kernel(TriSearch a)
+{
+    const int lane = threadIdx.x & 63;
+    const int n1 = a.k1.n, n2 = a.k2.n, nn2 = a.k2.nnodes;
+    bool bad = false;
+    // KF2's node list and CSR, once over the grid: the merge-join of :676-806 relies on std::map order
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < nn2; k += gridDim.x * 256) {
+        const int o0 = a.k2.off[k], o1 = a.k2.off[k + 1];
+        bad = bad || (k > 0 && a.k2.nodes[k - 1] >= a.k2.nodes[k]) || o0 < 0 || o1 < o0 || o1 > n2;
+    }
+    if (__any(bad) && lane == 0) *a.status = ORBFE_ERR_INVALID;
+    bad = false;
+    const int node = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (node >= a.k1.nnodes) return;
+    const uint32_t id = a.k1.nodes[node];
+    const int k0 = a.k1.off[node], k1 = a.k1.off[node + 1];
+    if ((node > 0 && a.k1.nodes[node - 1] >= id) || k0 < 0 || k1 < k0 || k1 > n1) {
+        if (lane == 0) *a.status = ORBFE_ERR_INVALID;
+        return;
+    }
+    const int lo = bow_lower_bound(a.k2.nodes, nn2, id, lane);
+    if (lo >= nn2 || a.k2.nodes[lo] != id) return;
+    const int f0 = a.k2.off[lo], f1 = a.k2.off[lo + 1];
+    if (f0 < 0 || f1 < f0 || f1 > n2) { // a keypoint lies in one node: no CSR is longer than its keypoint array
+        if (lane == 0) *a.status = ORBFE_ERR_INVALID;
+        return;
+    }
+    const int nf = f1 - f0;
+    if (k1 == k0 || nf == 0) return;
+    TriCand rc[TRI_REG_CHUNKS];
+#pragma unroll
+    for (int c = 0; c < TRI_REG_CHUNKS; c++) tri_load_cand(a, f0, nf, lane + 64 * c, rc[c], bad);
+    u64 taken = 0;
+    for (int kbase = k0; kbase < k1; kbase += 64) {
+        // 64 KF1 features at a time are fetched by the lanes side by side, so that no load of KF1 sits in the sequential loop below
+        int my_i1 = -1;
+        bool my_ok = false, my_stereo = false;
+        float my_x = 0.f, my_y = 0.f;
+        uint32_t my_d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (kbase + lane < k1) {
+            my_i1 = a.k1.feat[kbase + lane];
+            if (my_i1 < 0 || my_i1 >= n1) bad = true;
+            else if (!a.k1.has_mp[my_i1]) {
+                my_stereo = a.k1.u_right[my_i1] >= 0;
+                if (!a.only_stereo || my_stereo) {
+                    my_ok = true;
+                    my_x = a.k1.keys_un[my_i1].x; my_y = a.k1.keys_un[my_i1].y;
+#pragma unroll
+                    for (int k = 0; k < 8; k++) my_d[k] = ((const uint32_t *)(a.k1.desc + (size_t)my_i1 * 32))[k];
+                }
+            }
+        }
+        const u64 stereo_mask = __ballot(my_stereo);
+        for (u64 todo = __ballot(my_ok); todo; todo &= todo - 1) { // the usable KF1 features in list order
+            const int src = __ffsll((long long)todo) - 1;
+            const int idx1 = __builtin_amdgcn_readlane(my_i1, src);
+            const float x1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_x), src));
+            const float y1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_y), src));
+            const bool stereo1 = (stereo_mask >> src) & 1ull;
+            uint32_t kd[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) kd[k] = (uint32_t)__builtin_amdgcn_readlane((int)my_d[k], src);
+            int d1 = 256, c1 = 0, i2 = -1; // 256 differing bits: no candidate yet
+#pragma unroll
+            for (int c = 0; c < TRI_REG_CHUNKS; c++) {
+                const TriCand &q = rc[c];
+                if (q.idx < 0 || ((taken >> c) & 1ull)) continue;
+                const int d = hamming256(kd, q.d);
+                if (d > TH_LOW || d > d1) continue;
+                if (!stereo1 && !q.stereo && orbfe_epipolar::inside_epipole_disc(a.ex, a.ey, q.x, q.y, q.scale)) continue;
+                if (!orbfe_epipolar::check_dist_epipolar_line(x1, y1, q.x, q.y, a.F12, q.sigma2)) continue;
+                d1 = d; c1 = c; i2 = q.idx;
+            }
+            for (int j = lane + 64 * TRI_REG_CHUNKS, c = TRI_REG_CHUNKS; j < nf; j += 64, c++) { // nodes beyond 64 * TRI_REG_CHUNKS features: read in place
+                TriCand q;
+                tri_load_cand(a, f0, nf, j, q, bad);
+                if (q.idx < 0) continue;
+                if (c < TRI_FLAG_CHUNKS ? (int)((taken >> c) & 1ull) : (int)a.taken2[q.idx]) continue;
+                const int d = hamming256(kd, q.d);
+                if (d > TH_LOW || d > d1) continue;
+                if (!stereo1 && !q.stereo && orbfe_epipolar::inside_epipole_disc(a.ex, a.ey, q.x, q.y, q.scale)) continue;
+                if (!orbfe_epipolar::check_dist_epipolar_line(x1, y1, q.x, q.y, a.F12, q.sigma2)) continue;
+                d1 = d; c1 = c; i2 = q.idx;
+            }
+            // the smallest distance; among equals the largest list position (chunk * 64 + lane < 65535): the last one the reference's loop meets
+            const unsigned key = ((unsigned)d1 << 16) | (0xffffu - (unsigned)(c1 * 64 + lane));
+            const unsigned m = wave_min_u32(key);
+            if ((int)(m >> 16) > TH_LOW) continue; // no candidate at all
+            if (key == m) { // list positions are unique
+                a.match12[idx1] = i2;
+                if (c1 < TRI_FLAG_CHUNKS) taken |= 1ull << c1;
+                else a.taken2[i2] = 1;
+            }
+        }
+    }
+    if (__any(bad) && lane == 0) *a.status = ORBFE_ERR_INVALID;
+}
+
+// One workgroup.  A KF1 keypoint lies in one node, so the accepted pairs are the non-negative entries of match12 (each a KF2
+// index the node kernel checked): rotation
+// histogram (:781-790), ComputeThreeMaxima, losers removed (:793-806), the count, and vMatchedPairs (:808-816) by an ordered
+// compaction: thread t owns a contiguous run of idx1, the runs' counts are scanned.
+__global__ __launch_bounds__(1024) void tri_tail_kernel(TriSearch a)
+{
+    __shared__ int32_t s_hist[32];
+    __shared__ int s_keep[3], s_wave[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n1 = a.k1.n;
+    if (tid < 32) s_hist[tid] = 0;
+    __syncthreads();
+    if (a.check_ori) {
+        for (int k = tid; k < n1; k += 1024) {
+            const int m = a.match12[k];
+            if (m < 0) continue;
+            int bin = orbfe_resolve::rot_bin(a.k1.keys_un[k].angle, a.k2.keys_un[m].angle); // rotHist[bin].push_back(idx1)
+            if ((unsigned)bin >= (unsigned)HISTO_LENGTH) { bin = 0; *a.status = ORBFE_ERR_INVALID; } // angles outside [0, 360)
+            atomicAdd(&s_hist[bin], 1);
+        }
+        __syncthreads();
+        if (tid == 0) orbfe_resolve::three_maxima(s_hist, HISTO_LENGTH, &s_keep[0], &s_keep[1], &s_keep[2]);
+        __syncthreads();
+    }
+    const int run = (n1 + 1023) / 1024;
+    const int lo = tid * run < n1 ? tid * run : n1, hi = lo + run < n1 ? lo + run : n1;
+    int cnt = 0;
+    for (int k = lo; k < hi; k++) {
+        int m = a.match12[k];
+        if (m >= 0 && a.check_ori) {
+            int bin = orbfe_resolve::rot_bin(a.k1.keys_un[k].angle, a.k2.keys_un[m].angle);
+            if ((unsigned)bin >= (unsigned)HISTO_LENGTH) bin = 0;
+            if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) { a.match12[k] = -1; m = -1; }
+        }
+        cnt += m >= 0;
+    }
+    int incl = cnt; // inclusive scan inside the wave, then over the 16 wave totals
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int w = 0; w < 16; w++) {
+        const int t = s_wave[w];
+        before += w < wave ? t : 0;
+        total += t;
+    }
+    if (tid == 0) *a.nmatches = total;
+    if (!a.pairs) return;
+    // a KF2 keypoint is taken once, so total <= min(n1, n2), the caller's array; only a refused feature vector (a KF2 keypoint in two
+    // nodes) can exceed it, and then the rest is dropped
+    const int room = n1 < a.k2.n ? n1 : a.k2.n;
+    int p = before + incl - cnt;
+    for (int k = lo; k < hi && p < room; k++) {
+        const int m = a.match12[k];
+        if (m < 0) continue;
+        a.pairs[2 * p] = k; a.pairs[2 * p + 1] = m;
+        p++;
+    }
+}
+
+extern "C" int orbfe_enqueue_search_for_triangulation(orbfe_context *ctx, const orbfe_tri_keyframe *kf1, const orbfe_tri_keyframe *kf2,
+                                                      const float *F12, const float *Cw1, const float *T2w, float fx2, float fy2, float cx2, float cy2,
+                                                      int only_stereo, int check_ori, int32_t *d_match12, int32_t *d_pairs, int32_t *d_nmatches,
+                                                      int32_t *d_status, void *stream)
+try {
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    ORBFE_ENTRY(ctx);
+    if (!kf1 || !kf2 || !F12 || !Cw1 || !T2w || !d_match12 || !d_nmatches || !d_status) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
+    for (const orbfe_tri_keyframe *kf : {kf1, kf2}) {
+        if (kf->n < 0 || kf->nnodes < 0) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "negative count");
+        if (kf->n > 65535) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "keyframes with more than 65535 keypoints are not supported");
+        if (kf->nnodes > 0 && (!kf->nodes || !kf->off || !kf->feat || !kf->keys_un || !kf->u_right || !kf->has_mp || !kf->desc))
+            return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null array in a keyframe record with nodes");
+    }
+    orbfe_bow_state *st = orbfe_ctx_bow_state(ctx);
+    if (!st) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "out of host memory");
+    const int nlevels = orbfe_ctx_params(ctx)->nlevels;
+    if (nlevels < 1 || nlevels > ORBFE_MAX_LEVELS) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "nlevels = %d", nlevels);
+    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
+    WTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    if (st->resident.ensure((size_t)(kf2->n > 64 ? kf2->n : 64))) return orbfe_fail(ctx, ORBFE_ERR_HIP, "BoW scratch allocation failed");
+    TriSearch a;
+    a.k1 = *kf1; a.k2 = *kf2; // a record without nodes may hold NULL arrays: the tail follows keys_un only through a match
+    for (int k = 0; k < 9; k++) a.F12[k] = F12[k];
+    orbfe_epipolar::epipole(Cw1, T2w, fx2, fy2, cx2, cy2, &a.ex, &a.ey);
+    const float *scale = orbfe_ctx_scale_factors(ctx);
+    for (int l = 0; l < ORBFE_MAX_LEVELS; l++) {
+        a.scale[l] = l < nlevels ? scale[l] : 1.f;
+        a.sigma2[l] = a.scale[l] * a.scale[l]; // mvLevelSigma2 (src/ORBextractor.cc:419-423)
+    }
+    a.nlevels = nlevels; a.only_stereo = only_stereo != 0; a.check_ori = check_ori != 0;
+    a.match12 = d_match12; a.pairs = d_pairs; a.nmatches = d_nmatches; a.status = d_status;
+    a.taken2 = (uint8_t *)st->resident.p;
+    const int cells = a.k1.n > a.k2.n ? a.k1.n : a.k2.n;
+    hipLaunchKernelGGL(tri_init_kernel, dim3(cells > 0 ? (cells + 255) / 256 : 1), dim3(256), 0, s, a);
+    if (a.k1.nnodes > 0 && a.k2.nnodes > 0) hipLaunchKernelGGL(tri_node_match_kernel, dim3((a.k1.nnodes + 3) / 4), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(tri_tail_kernel, dim3(1), dim3(1024), 0, s, a);
     WTRY(ctx, hipGetLastError());
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)

@@ -28,6 +28,14 @@ resident in slot 0 against 8 candidate keyframes of about 2000 map points (one p
 own), th 10, ORBdist 100, rotation check on, nothing held.  (a) 8 synchronous resident orbfe_search_by_projection_kf calls; (b) -- when
 the library has it -- one orbfe_enqueue_search_by_projection_kf_batch + one stream synchronise, as wall time and as GPU time between
 two events.  Five repeats of each, interleaved; every repeat is the mean of 50 calls.
+    python3 tools/bench_matchers.py --triangulation [--lib path/to/another/liborbfe.so]
+runs only the CreateNewMapPoints rows (profiles/triangulation_device.json): one keyframe of 2000 keypoints against 20 neighbours of
+2000 (the two-view scene of tests/triangulation_scenes.py, feature vectors from the test vocabulary), every neighbour's every other
+match given a map point before the next neighbour is searched.  (a) the 20 synchronous orbfe_search_for_triangulation calls, has_mp1
+patched on the host in between; (b) -- when the library has it -- 20 x (orbfe_enqueue_search_for_triangulation + download of the
+count and d_pairs into pinned memory + stream synchronise), the has_mp1 patch queued on the stream in between, as wall time, and the
+20 enqueues queued back to back as GPU time between two events.  Both are checked against the oracle run with the same patches.
+Five repeats of each, interleaved; every repeat is the mean of 10 loops over the 20 neighbours, its slowest loop beside it.
 """
 import json
 import os
@@ -551,6 +559,128 @@ def reloc_rows(out):
     ctx.close()
 
 
+def triangulation_rows(out):
+    """Rows of --triangulation; arguments prepared once."""
+    import ctypes as C
+    import torch
+    from orbslam2_amd import api
+    from orbslam2_amd import bow as B
+    from tests import triangulation_scenes as S
+    dev = torch.device("cuda:0")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
+    N, K, REPS, REPEATS = 2000, 20, 10, 5
+    ctx = api.Context(width=640, height=480, nfeatures=2000, fx=S.FX, fy=S.FY, cx=S.CX, cy=S.CY, bf=40.0)
+    L = ctx.L
+    B._bind()
+    have = hasattr(L, "orbfe_enqueue_search_for_triangulation")
+    base = S.two_view(2, N)
+    scs = [dict(base, kf2=S.view_of(2 + k, N)) for k in range(K)]
+    a = base["kf1"]
+    # the oracle, neighbour after neighbour, every other match becoming a map point of KF1
+    mp1, refs = a["mp"].copy(), []
+    for sc in scs:
+        ref, nref = S.oracle(sc, 0, 1, mp1=mp1)
+        refs.append((ref, nref, mp1.copy()))
+        mp1[np.nonzero(ref >= 0)[0][::2]] = 1
+    out["scene"] = "KF1 of %d keypoints in %d nodes against %d neighbours of %d, only_stereo off, rotation check on; matches per neighbour %d .. %d" % (
+        N, len(a["fv"][0]), K, N, min(r[1] for r in refs), max(r[1] for r in refs))
+
+    def sync_loop(check=False):
+        mp = a["mp"].copy()
+        for sc, (ref, nref, _) in zip(scs, refs):
+            b = sc["kf2"]
+            got, ngot = B.search_for_triangulation(ctx, a["fv"], a["k"], a["ur"], mp, a["d"], b["fv"], b["k"], b["ur"], b["mp"], b["d"],
+                                                   sc["F12"], sc["Cw1"], sc["T2w"], S.FX, S.FY, S.CX, S.CY, 0, 1)
+            if check:
+                assert ngot == nref and np.array_equal(got, ref)
+            mp[np.nonzero(got >= 0)[0][::2]] = 1
+
+    sync_loop(check=True)
+    if have:
+        st = torch.cuda.Stream()
+
+        def record(kf, mp_t=None):
+            t = [up(kf["fv"][0]), up(kf["fv"][1]), up(kf["fv"][2]), up(kf["k"]), up(kf["ur"]), up(kf["mp"]) if mp_t is None else mp_t, up(kf["d"])]
+            return t, api.TriKeyframe(*[x.data_ptr() for x in t], len(kf["fv"][0]), len(kf["k"]))
+
+        d_mp = up(a["mp"])
+        h_mp = torch.from_numpy(a["mp"].copy()).pin_memory()     # the host's mirror of has_mp1: patched, then queued as one 2 KB copy
+        keep1, rec1 = record(a, d_mp)
+        recs2 = [record(sc["kf2"]) for sc in scs]
+        d_match = torch.zeros(N, dtype=torch.int32, device=dev)
+        d_res = torch.zeros(2 + 2 * N, dtype=torch.int32, device=dev)  # count, status, pairs: one download
+        h_res = torch.zeros(2 + 2 * N, dtype=torch.int32).pin_memory()
+        res = h_res.numpy()
+        mp0 = a["mp"].copy()
+        torch.cuda.synchronize()
+
+        def enqueue(k):
+            sc = scs[k]
+            ctx.enqueue_search_for_triangulation(rec1, recs2[k][1], sc["F12"], sc["Cw1"], sc["T2w"], S.FX, S.FY, S.CX, S.CY, 0, 1, d_match.data_ptr(),
+                                                 d_res.data_ptr(), d_res.data_ptr() + 4, d_pairs=d_res.data_ptr() + 8, stream=st.cuda_stream)
+
+        def device_loop(check=False):
+            with torch.cuda.stream(st):
+                h_mp.numpy()[:] = mp0
+                d_mp.copy_(h_mp, non_blocking=True)
+                for k in range(K):
+                    enqueue(k)
+                    h_res.copy_(d_res, non_blocking=True)
+                    st.synchronize()
+                    nm = int(res[0])
+                    if check:
+                        ref, nref, _ = refs[k]
+                        assert res[1] == 0 and nm == nref and np.array_equal(res[2:2 + 2 * nm], S.pairs_of(ref)), k
+                    h_mp.numpy()[res[2:2 + 2 * nm:4]] = 1            # triangulation happens here; every other pair becomes a map point
+                    d_mp.copy_(h_mp, non_blocking=True)
+                st.synchronize()
+
+        device_loop(check=True)
+    def loops(fn):
+        """Mean and slowest of REPS loops over the neighbours, each timed on its own: one stalled loop shows as such.  The cyclic
+        garbage collector is off inside the window, as in the standard timeit module."""
+        import gc
+        fn()
+        gc.collect()
+        gc.disable()
+        try:
+            t = []
+            for _ in range(REPS):
+                t0 = time.perf_counter()
+                fn()
+                t.append((time.perf_counter() - t0) * 1e3)
+        finally:
+            gc.enable()
+        return round(sum(t) / REPS, 4), round(max(t), 4)
+
+    a_rows, a_worst, b_wall, b_worst, b_gpu = [], [], [], [], []
+    for _ in range(REPEATS):
+        m, w = loops(sync_loop)
+        a_rows.append(m); a_worst.append(w)
+        if have:
+            m, w = loops(device_loop)
+            b_wall.append(m); b_worst.append(w)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            for _ in range(REPS):
+                for k in range(K):
+                    enqueue(k)
+            e1.record(st)
+            st.synchronize()
+            b_gpu.append(round(e0.elapsed_time(e1) / REPS, 4))
+    out["rows"]["(a) orbfe_search_for_triangulation x %d, synchronous, has_mp1 patched on the host, wall time" % K] = {
+        "ms_per_repeat": a_rows, "slowest_loop_ms": a_worst}
+    if have:
+        out["rows"]["(b) %d x (orbfe_enqueue_search_for_triangulation + download of count and pairs + synchronise), has_mp1 patch queued in between, wall time" % K] = {
+            "ms_per_repeat": b_wall, "slowest_loop_ms": b_worst}
+        out["rows"]["(b) the %d enqueues alone, queued back to back, GPU time between two events" % K] = {"ms_per_repeat": b_gpu}
+        out["median (a) / median (b)"] = round(float(np.median(a_rows) / np.median(b_wall)), 2)
+        out["max (b) < min (a)"] = bool(max(b_wall) < min(a_rows))
+    else:
+        out["device"] = "not exported by this library"
+    ctx.close()
+
+
 def load_other_build(api, path):
     """api.load() on the library at `path`, which may be older than the package: the prototypes load() sets for entry points
     that build lacks land on stand-ins that are not kept, so hasattr(lib, name) is False afterwards and a call fails loudly."""
@@ -582,6 +712,12 @@ def main():
     if "--reloc" in sys.argv[1:]:
         out = {"unit": "ms per group of 8 candidates", "rows": {}}
         reloc_rows(out)
+        out["build_id"] = api.build_id()
+        print(json.dumps(out, indent=1))
+        return
+    if "--triangulation" in sys.argv[1:]:
+        out = {"unit": "ms per keyframe (20 neighbours)", "rows": {}}
+        triangulation_rows(out)
         out["build_id"] = api.build_id()
         print(json.dumps(out, indent=1))
         return
