@@ -65,7 +65,7 @@
 extern "C" {
 #endif
 
-#define ORBFE_ABI_VERSION 6 /* 2: orbfe_frame_view.device_slot_plus1; 3: .keyframe; 4: orbfe_get_camera, orbfe_assign_features_to_grid, orbfe_stereo_batch, orbfe_device_count, orbfe_set_profiling_interval; 5: orbfe_get_packed_layout, orbfe_fetch_batch_packed, orbfe_expand_packed, orbfe_stereo_batch_packed, orbfe_enqueue_rgbd; 6: orbfe_build_id, orbfe_set_pattern, orbfe_get_pattern, orbfe_blur_ride_from, orbfe_set_input_retained (additive: no struct changed; orbfe_fetch_pyramid(level 0) of an in-place batched call now needs the latter); still 6, additive: orbfe_enqueue_search_by_projection_last, orbfe_enqueue_is_in_frustum, orbfe_enqueue_search_by_projection_points, orbfe_device_keys_un */
+#define ORBFE_ABI_VERSION 6 /* 2: orbfe_frame_view.device_slot_plus1; 3: .keyframe; 4: orbfe_get_camera, orbfe_assign_features_to_grid, orbfe_stereo_batch, orbfe_device_count, orbfe_set_profiling_interval; 5: orbfe_get_packed_layout, orbfe_fetch_batch_packed, orbfe_expand_packed, orbfe_stereo_batch_packed, orbfe_enqueue_rgbd; 6: orbfe_build_id, orbfe_set_pattern, orbfe_get_pattern, orbfe_blur_ride_from, orbfe_set_input_retained (additive: no struct changed; orbfe_fetch_pyramid(level 0) of an in-place batched call now needs the latter); still 6, additive: orbfe_enqueue_search_by_projection_last, orbfe_enqueue_is_in_frustum, orbfe_enqueue_search_by_projection_points, orbfe_device_keys_un; the BoW, relocalisation and triangulation enqueue calls; orbfe_enqueue_keyframe_grid, orbfe_enqueue_fuse, orbfe_enqueue_fuse_sim3 (struct orbfe_grid_keyframe) */
 
 enum {
     ORBFE_OK = 0,
@@ -728,6 +728,66 @@ int orbfe_enqueue_search_for_triangulation(orbfe_context *ctx, const orbfe_tri_k
         int only_stereo, int check_ori,
         int32_t *d_match12 /* [kf1->n] */, int32_t *d_pairs /* [2 * min(n1, n2)], may be NULL */,
         int32_t *d_nmatches, int32_t *d_status, void *stream);
+/* ---- ORBmatcher::Fuse on device-resident keyframes (orbfe_fuse_device.hip): LocalMapping::SearchInNeighbors (src/LocalMapping.cc:454-531)
+ * and LoopClosing::SearchAndFuse without a host round trip inside the call.  The contract of the enqueue matchers above holds: asynchronous
+ * on `stream` (NULL: the context's stream), nothing waits for the GPU, nothing is copied from host memory on the stream, nothing is
+ * allocated at all.  No image slot is read and no vocabulary is needed.
+ *
+ * One keyframe as these calls read it: arrays the keyframe owns in HBM for its whole life (keypoints, descriptors, mvuRight and the
+ * grid of a keyframe never change), uploaded once when it is made.  keys_un, u_right and desc may be the very arrays of the
+ * keyframe's orbfe_tri_keyframe.  64 bytes; every pointer is a device pointer. */
+typedef struct orbfe_grid_keyframe {
+    const orbfe_keypoint *keys_un;        /* mvKeysUn: x, y, octave are read */
+    const float   *u_right;               /* mvuRight (< 0: monocular keypoint); NULL: a monocular keyframe, no stereo gate */
+    const uint8_t *desc;                  /* 32 bytes per keypoint, 4-byte aligned */
+    const int32_t *cell_off;              /* [64 * 48 + 1], as orbfe_enqueue_keyframe_grid wrote it */
+    const int32_t *cell_idx;              /* [n] */
+    float min_x, max_x, min_y, max_y;     /* the FRAME's float bounds (orbfe_frame_view.min_x ...) */
+    int32_t n;                            /* keypoints, <= 65535 (the candidate key holds 16 index bits) */
+    int32_t keyframe;                     /* as orbfe_frame_view.keyframe: windows and IsInImage use (float)(int) of the bounds */
+} orbfe_grid_keyframe;
+/* Frame::AssignFeaturesToGrid (src/Frame.cc:231-246) for a keyframe that is not an image slot: mGrid of the n keypoints d_keys_un under
+ * bounds = mnMinX, mnMaxX, mnMinY, mnMaxY (4 HOST floats, the frame's own) as CSR over cell ix * 48 + iy, written into arrays the
+ * caller owns: d_cell_off[3073], d_cell_idx[n] (entries from d_cell_off[3072] on are left untouched: PosInGrid drops keypoints outside
+ * the grid).  The offsets equal orbfe_assign_features_to_grid's; the order inside a cell is free (the matchers order candidates by
+ * their keys).  n == 0 writes 3073 zero offsets and reads no other pointer.  ORBFE_ERR_INVALID, nothing queued: a NULL context, bounds
+ * or d_cell_off, bounds that are not ascending, n < 0, n > 65535, a NULL d_keys_un or d_cell_idx under n > 0. */
+int orbfe_enqueue_keyframe_grid(orbfe_context *ctx, const orbfe_keypoint *d_keys_un, int n, const float *bounds,
+        int32_t *d_cell_off /* [3073] */, int32_t *d_cell_idx /* [n] */, void *stream);
+/* Search part of ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:821-971): per query the keypoint of `kf` its map point would
+ * be fused with.  The points do not interact (the map mutation of :943-964 stays with the caller), so the call is one kernel, one wave
+ * per query.  kf is a HOST struct holding device pointers and Tcw a HOST 3x4 row-major matrix; both are read before the call returns
+ * and travel as kernel arguments together with the context's camera, scale factors and level count.
+ * The map points are a TABLE of n_rows rows (d_pos and d_normal 3 floats, d_max_distance / d_min_distance one, d_pt_desc 32 bytes,
+ * 4-byte aligned); query q reads row d_pt_index[q], or row q when d_pt_index is NULL (then n_rows >= n_pts).  d_pt_valid[q] belongs to
+ * the QUERY, not the row, because it depends on the target: pMP && !pMP->isBad() && !pMP->IsInKeyFrame(pKF), as orbfe_fuse's pt_valid.
+ * So LocalMapping::SearchInNeighbors uploads one table per new keyframe: its first loop (:487) passes the current keyframe's rows to
+ * every target, its second call (:512) the index list that vpFuseCandidates is.  Between two targets MapPoint::Replace marks points
+ * bad and recomputes the survivor's descriptor (src/MapPoint.cc:177-215), so the caller patches d_pt_valid and descriptor rows ON THE
+ * STREAM between two calls; that dependence on the host's bookkeeping is why there is no batch over targets.
+ * Outputs (device), all three written by every call that queues anything and nothing else written: d_best_idx[n_pts] (keypoint of kf
+ * or -1), d_n_fused[1] (how many are >= 0), d_status[1].  n_pts == 0 writes count 0 and status 0 and queues nothing else; with
+ * kf->n == 0 every query gets -1 and no array of the record or the table is read.  Every result equals orbfe_fuse on the same inputs.
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL context, record, pose or output; n_pts, n_rows or kf->n negative;
+ * kf->n > 65535; bounds of the record that are not ascending; n_rows < n_pts with a NULL index; and, when n_pts > 0 and kf->n > 0, a
+ * NULL point array, d_pt_valid, or record pointer other than u_right.  d_status = ORBFE_ERR_INVALID for what only the device can see,
+ * each checked before it is used as an address: a d_pt_index entry outside [0, n_rows) (that query gets -1); a grid offset that is
+ * negative, descending or beyond n, a cell_idx entry outside [0, n), an octave outside [0, nlevels) on a keypoint of a walked cell
+ * (that cell / entry is skipped).  The other outputs of such a call are not meaningful.
+ * The calls keep no scratch, so calls on different streams do not disturb each other. */
+int orbfe_enqueue_fuse(orbfe_context *ctx, const orbfe_grid_keyframe *kf, const float *Tcw,
+        int n_pts, const int32_t *d_pt_index /* [n_pts] or NULL */, int n_rows,
+        const float *d_pos, const float *d_normal, const float *d_max_distance, const float *d_min_distance, const uint8_t *d_pt_desc,
+        const int32_t *d_pt_valid /* [n_pts] */, float th,
+        int32_t *d_best_idx /* [n_pts] */, int32_t *d_n_fused /* [1] */, int32_t *d_status /* [1] */, void *stream);
+/* The same for ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) of LoopClosing::SearchAndFuse (:973-1096): Scw is a HOST 3x4
+ * [sR | s t], decomposed on the host as orbfe_fuse_sim3 does; no chi-square gates; d_pt_valid[q] = !isBad() and not already one of the
+ * keyframe's map points (:1000-1002).  Every result equals orbfe_fuse_sim3 on the same inputs. */
+int orbfe_enqueue_fuse_sim3(orbfe_context *ctx, const orbfe_grid_keyframe *kf, const float *Scw,
+        int n_pts, const int32_t *d_pt_index /* [n_pts] or NULL */, int n_rows,
+        const float *d_pos, const float *d_normal, const float *d_max_distance, const float *d_min_distance, const uint8_t *d_pt_desc,
+        const int32_t *d_pt_valid /* [n_pts] */, float th,
+        int32_t *d_best_idx /* [n_pts] */, int32_t *d_n_fused /* [1] */, int32_t *d_status /* [1] */, void *stream);
 /* KeyFrameDatabase::DetectLoopCandidates(KeyFrame *pKF, float minScore) (src/KeyFrameDatabase.cc:73-194; LoopClosing::DetectLoop,
  * src/LoopClosing.cc:131).  connected[k] != 0 marks the keyframes of pKF->GetConnectedKeyFrames() (may be NULL: none); covisibility
  * lists as for the relocalisation query.  Stateless: mLoopScore is only read for keyframes scored by the same call. */

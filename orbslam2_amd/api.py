@@ -40,6 +40,7 @@ EXPORTS = [
     "orbfe_enqueue_compute_bow", "orbfe_enqueue_search_by_bow", "orbfe_enqueue_search_by_bow_batch",
     "orbfe_enqueue_search_by_projection_kf", "orbfe_enqueue_search_by_projection_kf_batch",
     "orbfe_enqueue_search_for_triangulation",
+    "orbfe_enqueue_keyframe_grid", "orbfe_enqueue_fuse", "orbfe_enqueue_fuse_sim3",
 ]
 NUM_STAGES = 8
 STAGE_NAMES = ["ingest", "pyramid", "blur", "fast", "octree", "describe", "stereo_match", "stereo_median"]  # orbfe_stage_name()
@@ -80,6 +81,17 @@ class TriKeyframe(C.Structure):
 
 
 assert C.sizeof(TriKeyframe) == 64
+
+
+class GridKeyframe(C.Structure):
+    """orbfe_grid_keyframe (include/orbfe.h): the keyframe of enqueue_fuse / enqueue_fuse_sim3, device pointers; cell_off / cell_idx as
+    enqueue_keyframe_grid wrote them, the bounds the frame's floats."""
+    _fields_ = [("keys_un", C.c_void_p), ("u_right", C.c_void_p), ("desc", C.c_void_p), ("cell_off", C.c_void_p), ("cell_idx", C.c_void_p),
+                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float), ("n", C.c_int32), ("keyframe", C.c_int32)]
+
+
+assert C.sizeof(GridKeyframe) == 64
+GRID_CELLS = 64 * 48  # FRAME_GRID_COLS * FRAME_GRID_ROWS: cell_off holds GRID_CELLS + 1 entries
 
 
 class RelocCandidate(C.Structure):
@@ -238,6 +250,11 @@ def load():
     L.orbfe_enqueue_search_for_triangulation.restype = C.c_int
     L.orbfe_enqueue_search_for_triangulation.argtypes = [vp, C.POINTER(TriKeyframe), C.POINTER(TriKeyframe), vp, vp, vp] + [C.c_float] * 4 + \
         [C.c_int, C.c_int] + [vp] * 5
+    L.orbfe_enqueue_keyframe_grid.restype = C.c_int
+    L.orbfe_enqueue_keyframe_grid.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
+    for fn in (L.orbfe_enqueue_fuse, L.orbfe_enqueue_fuse_sim3):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, C.POINTER(GridKeyframe), vp, C.c_int, vp, C.c_int] + [vp] * 6 + [C.c_float] + [vp] * 4
     _lib = L
     return L
 
@@ -668,6 +685,39 @@ class Context:
         self._check(self.L.orbfe_enqueue_search_for_triangulation(
             self.h, C.byref(kf1), C.byref(kf2), _p(f), _p(c), _p(t), fx2, fy2, cx2, cy2, int(only_stereo), int(check_ori),
             v(d_match12 or None), v(d_pairs or None), v(d_nmatches or None), v(d_status or None), v(stream or None)))
+
+    def enqueue_keyframe_grid(self, d_keys_un, n, bounds, d_cell_off, d_cell_idx, stream=0):
+        """Frame::AssignFeaturesToGrid for a keyframe's n device-resident keypoints: d_cell_off (int32[GRID_CELLS + 1]) and d_cell_idx
+        (int32[n]) are arrays the caller keeps for the keyframe's life (GridKeyframe.cell_off / cell_idx); bounds: the frame's floats."""
+        b = np.ascontiguousarray(bounds, np.float32)
+        assert b.size == 4
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_keyframe_grid(self.h, v(d_keys_un or None), n, _p(b), v(d_cell_off or None), v(d_cell_idx or None),
+                                                       v(stream or None)))
+
+    def _enqueue_fuse(self, fn, kf, pose, n_pts, d_pt_index, n_rows, d_pos, d_normal, d_max_distance, d_min_distance, d_pt_desc, d_pt_valid, th,
+                      d_best_idx, d_n_fused, d_status, stream):
+        v = C.c_void_p
+        t = np.ascontiguousarray(pose, np.float32)
+        assert t.size >= 12
+        self._check(fn(self.h, C.byref(kf), _p(t), n_pts, v(d_pt_index or None), n_rows, v(d_pos or None), v(d_normal or None),
+                       v(d_max_distance or None), v(d_min_distance or None), v(d_pt_desc or None), v(d_pt_valid or None), th, v(d_best_idx or None),
+                       v(d_n_fused or None), v(d_status or None), v(stream or None)))
+
+    def enqueue_fuse(self, kf, Tcw, n_pts, d_pt_index, n_rows, d_pos, d_normal, d_max_distance, d_min_distance, d_pt_desc, d_pt_valid, th,
+                     d_best_idx, d_n_fused, d_status, stream=0):
+        """Search part of ORBmatcher::Fuse(pKF, vpMapPoints, th) on a device-resident keyframe (a GridKeyframe record on the host, device
+        pointers inside), asynchronous on `stream`.  Tcw (3x4) is a host array read before the call returns.  The map points are a table
+        of n_rows rows in HBM; query q reads row d_pt_index[q] (0: row q) and its own d_pt_valid[q].  One call per target keyframe: the
+        caller patches d_pt_valid (and descriptor rows that MapPoint::Replace recomputed) on the stream between two calls."""
+        self._enqueue_fuse(self.L.orbfe_enqueue_fuse, kf, Tcw, n_pts, d_pt_index, n_rows, d_pos, d_normal, d_max_distance, d_min_distance, d_pt_desc,
+                           d_pt_valid, th, d_best_idx, d_n_fused, d_status, stream)
+
+    def enqueue_fuse_sim3(self, kf, Scw, n_pts, d_pt_index, n_rows, d_pos, d_normal, d_max_distance, d_min_distance, d_pt_desc, d_pt_valid, th,
+                          d_best_idx, d_n_fused, d_status, stream=0):
+        """The same for ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) of LoopClosing::SearchAndFuse: Scw = [sR | s t] (3x4, host)."""
+        self._enqueue_fuse(self.L.orbfe_enqueue_fuse_sim3, kf, Scw, n_pts, d_pt_index, n_rows, d_pos, d_normal, d_max_distance, d_min_distance,
+                           d_pt_desc, d_pt_valid, th, d_best_idx, d_n_fused, d_status, stream)
 
     def search_by_projection_kf(self, view, Tcw_cur, kf_pos, kf_desc, kf_valid, kf_angle, kf_max_distance, kf_min_distance, cur_has_point,
                                 th, orb_dist, check_ori):

@@ -31,11 +31,10 @@
 #include <new>
 #include <vector>
 
-// KeyFrame::IsInImage (src/KeyFrame.cc:604-607): the keyframe's bounds are ints initialised from the frame's floats
+// KeyFrame::IsInImage of a view (orbfe_match_resolve.h)
 static inline bool kf_is_in_image(const orbfe_frame_view *kf, float u, float v)
 {
-    if (kf->keyframe) return u >= (float)(int)kf->min_x && u < (float)(int)kf->max_x && v >= (float)(int)kf->min_y && v < (float)(int)kf->max_y;
-    return u >= kf->min_x && u < kf->max_x && v >= kf->min_y && v < kf->max_y;
+    return orbfe_resolve::kf_is_in_image(kf->min_x, kf->max_x, kf->min_y, kf->max_y, kf->keyframe, u, v);
 }
 using orbfe_resolve::HISTO_LENGTH;
 using orbfe_resolve::key_dist;
@@ -210,11 +209,7 @@ static int run_window_queries(orbfe_context *ctx, const orbfe_frame_view *fv, co
     uint8_t *din = (uint8_t *)st->in_blk.p, *dout = (uint8_t *)st->out_blk.p;
     GridFrame f;
     f.n_ptr = nullptr; f.cap = n; // the host knows the count of the frame it uploads, and of the slot it has just checked
-    f.min_x = fv->min_x; f.min_y = fv->min_y;
-    f.q_min_x = fv->keyframe ? (float)(int)fv->min_x : fv->min_x; // KeyFrame::mnMinX is an int initialised from the frame's float
-    f.q_min_y = fv->keyframe ? (float)(int)fv->min_y : fv->min_y;
-    f.inv_w = (float)GRID_COLS / (fv->max_x - fv->min_x); // mfGridElementWidthInv, src/Frame.cc:99
-    f.inv_h = (float)GRID_ROWS / (fv->max_y - fv->min_y);
+    grid_frame_geometry(f, fv->min_x, fv->max_x, fv->min_y, fv->max_y, fv->keyframe != 0);
     f.cell_off = (int *)st->cells.p; f.cell_idx = f.cell_off + GRID_CELLS + 1;
     bool build_grid = true;
     if (resident) {
@@ -565,29 +560,16 @@ try {
     camera_center(Tcw, ow);
     std::vector<MatchQuery> q(n_pts);
     std::vector<uint8_t> qd((size_t)32 * (n_pts > 0 ? n_pts : 1));
-    std::vector<float> pu(n_pts > 0 ? n_pts : 1), pv(n_pts > 0 ? n_pts : 1), pur(n_pts > 0 ? n_pts : 1);
+    std::vector<float> pur(n_pts > 0 ? n_pts : 1); // the projection into the right image; u and v stay in the query
+    const orbfe_resolve::Camera cam = orbfe_resolve::camera_of(P);
     for (int i = 0; i < n_pts; i++) {
         MatchQuery &Q = q[i];
         Q = MatchQuery{0, 0, 0, 0, -1, 0, 0, 0};
         best_idx[i] = -1;
-        if (!pt_valid[i]) continue;
-        float pc[3];
-        rt_apply(Tcw, pos + 3 * i, pc);
-        if (pc[2] < 0.0f) continue;
-        const float invz = 1 / pc[2];
-        const float x = pc[0] * invz, y = pc[1] * invz;
-        const float u = P->fx * x + P->cx;
-        const float v = P->fy * y + P->cy;
-        if (!kf_is_in_image(kf, u, v)) continue; // KeyFrame::IsInImage
-        float po[3];
-        for (int k = 0; k < 3; k++) po[k] = pos[3 * i + k] - ow[k];
-        const float dist3d = (float)sqrt((double)po[0] * po[0] + (double)po[1] * po[1] + (double)po[2] * po[2]);
-        if (dist3d < 0.8f * min_distance[i] || dist3d > 1.2f * max_distance[i]) continue;
-        const double dot = (double)po[0] * normal[3 * i] + (double)po[1] * normal[3 * i + 1] + (double)po[2] * normal[3 * i + 2];
-        if (dot < 0.5 * (double)dist3d) continue;
-        const int lvl = predict_scale(max_distance[i], dist3d, log_sf, P->nlevels);
-        Q.u = u; Q.v = v; Q.r = th * sf[lvl]; Q.min_level = lvl - 1; Q.max_level = lvl; Q.flags = 1;
-        pu[i] = u; pv[i] = v; pur[i] = u - P->bf * invz;
+        // the loop body up to GetFeaturesInArea: one text with the kernel of orbfe_enqueue_fuse (orbfe_fuse_device.hip)
+        if (orbfe_resolve::query_fuse_point(cam, sf, P->nlevels, log_sf, kf->min_x, kf->max_x, kf->min_y, kf->max_y, kf->keyframe, Tcw, ow, 0, pos + 3 * i,
+                                            normal + 3 * i, pt_valid[i], max_distance[i], min_distance[i], th, Q, &pur[i]) <= 0)
+            continue;
         memcpy(&qd[(size_t)32 * i], pt_desc + (size_t)32 * i, 32);
     }
     rc = run_window_queries(ctx, kf, q, qd);
@@ -600,16 +582,7 @@ try {
             const unsigned long long key = st->h_list[st->h_off[i] + k];
             const int idx = key_idx(key), lv = key_level(key);
             const orbfe_keypoint &kp = kf->keys_un[idx];
-            const float inv_sigma2 = 1.0f / (sf[lv] * sf[lv]); // mvInvLevelSigma2 (src/ORBextractor.cc:419-425)
-            if (kf->u_right && kf->u_right[idx] >= 0) { // reprojection error in stereo (:905-918)
-                const float ex = pu[i] - kp.x, ey = pv[i] - kp.y, er = pur[i] - kf->u_right[idx];
-                const float e2 = ex * ex + ey * ey + er * er;
-                if ((double)(e2 * inv_sigma2) > 7.8) continue;
-            } else {
-                const float ex = pu[i] - kp.x, ey = pv[i] - kp.y;
-                const float e2 = ex * ex + ey * ey;
-                if ((double)(e2 * inv_sigma2) > 5.99) continue;
-            }
+            if (!orbfe_resolve::fuse_chi2_passes(q[i].u, q[i].v, pur[i], kp.x, kp.y, kf->u_right ? kf->u_right[idx] : -1.f, sf[lv])) continue; // :905-930
             if (key < best) best = key; // smallest (distance, GetFeaturesInArea order) = the loop's first minimum
         }
         if (best != ~0ull && key_dist(best) <= TH_LOW) { best_idx[i] = key_idx(best); nf++; }
@@ -617,15 +590,6 @@ try {
     *n_fused = nf;
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)
-
-// Sim3 decomposition of the LoopClosing matchers (src/ORBmatcher.cc:293-298, 981-986); see oracle/orb_oracle_match.c
-static void sim3_to_rt(const float *Scw, float *T)
-{
-    const double d = (double)Scw[0] * Scw[0] + (double)Scw[1] * Scw[1] + (double)Scw[2] * Scw[2];
-    const float scw = (float)sqrt(d);
-    const float alpha = (float)(1.0 / (double)scw);
-    for (int i = 0; i < 12; i++) T[i] = Scw[i] * alpha;
-}
 
 // mode 0: ORBmatcher::SearchByProjection(KeyFrame*, Scw, vpPoints, vpMatched, th), src/ORBmatcher.cc:285-398 (greedy over points);
 // mode 1: search part of ORBmatcher::Fuse(KeyFrame*, Scw, vpPoints, th, vpReplacePoint), :973-1096 (points independent).
@@ -643,31 +607,20 @@ static int sim3_projection_impl(orbfe_context *ctx, int mode, const orbfe_frame_
     const float log_sf = logf((float)(double)P->scale_factor);
     const int N = kf->n;
     float T[12], ow[3];
-    sim3_to_rt(Scw, T);
+    orbfe_resolve::sim3_to_rt(Scw, T);
     camera_center(T, ow);
+    const orbfe_resolve::Camera cam = orbfe_resolve::camera_of(P);
     std::vector<MatchQuery> q(n_pts);
     std::vector<uint8_t> qd((size_t)32 * (n_pts > 0 ? n_pts : 1));
     for (int i = 0; i < n_pts; i++) {
         MatchQuery &Q = q[i];
         Q = MatchQuery{0, 0, 0, 0, -1, 0, 0, 0};
         pt_match[i] = -1;
-        if (!pt_valid[i]) continue;
-        float pc[3];
-        rt_apply(T, pos + 3 * i, pc);
-        if (mode == 0 ? ((double)pc[2] < 0.0) : (pc[2] < 0.0f)) continue;
-        const float invz = mode == 0 ? 1 / pc[2] : (float)(1.0 / (double)pc[2]);
-        const float x = pc[0] * invz, y = pc[1] * invz;
-        const float u = P->fx * x + P->cx;
-        const float v = P->fy * y + P->cy;
-        if (!kf_is_in_image(kf, u, v)) continue;
-        float po[3];
-        for (int k = 0; k < 3; k++) po[k] = pos[3 * i + k] - ow[k];
-        const float dist = (float)sqrt((double)po[0] * po[0] + (double)po[1] * po[1] + (double)po[2] * po[2]);
-        if (dist < 0.8f * min_distance[i] || dist > 1.2f * max_distance[i]) continue;
-        const double dot = (double)po[0] * normal[3 * i] + (double)po[1] * normal[3 * i + 1] + (double)po[2] * normal[3 * i + 2];
-        if (dot < 0.5 * (double)dist) continue;
-        const int lvl = predict_scale(max_distance[i], dist, log_sf, P->nlevels);
-        Q.u = u; Q.v = v; Q.r = th * sf[lvl]; Q.min_level = lvl - 1; Q.max_level = lvl; Q.flags = 1;
+        float ur; // not used by the Sim3 matchers
+        // one text with the kernel of orbfe_enqueue_fuse_sim3 (orbfe_fuse_device.hip); mode 1 takes the reciprocal of z in double
+        if (orbfe_resolve::query_fuse_point(cam, sf, P->nlevels, log_sf, kf->min_x, kf->max_x, kf->min_y, kf->max_y, kf->keyframe, T, ow, mode == 1,
+                                            pos + 3 * i, normal + 3 * i, pt_valid[i], max_distance[i], min_distance[i], th, Q, &ur) <= 0)
+            continue;
         memcpy(&qd[(size_t)32 * i], pt_desc + (size_t)32 * i, 32);
     }
     rc = run_window_queries(ctx, kf, q, qd);

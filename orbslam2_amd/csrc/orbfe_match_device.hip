@@ -629,9 +629,7 @@ static int resident_grid(orbfe_context *ctx, int slot, const float *bounds, bool
     f.u_right = stereo ? buf->u_right + so : nullptr;
     f.n_ptr = buf->kp_cnt + slot;
     f.cap = cfg->sel_total;
-    f.min_x = f.q_min_x = bounds[0]; f.min_y = f.q_min_y = bounds[2];
-    f.inv_w = (float)GRID_COLS / (bounds[1] - bounds[0]); // mfGridElementWidthInv, src/Frame.cc:99
-    f.inv_h = (float)GRID_ROWS / (bounds[3] - bounds[2]);
+    grid_frame_geometry(f, bounds[0], bounds[1], bounds[2], bounds[3], false); // a Frame: windows use the float bounds
     f.cell_off = (int *)st->cells.p; f.cell_idx = f.cell_off + GRID_CELLS + 1;
     const unsigned epoch = orbfe_ctx_epoch(ctx);
     if (!(st->grid_epoch == epoch && st->grid_slot == slot && st->grid_keys == (const void *)f.keys && st->grid_bounds[0] == bounds[0] && st->grid_bounds[1] == bounds[1] &&

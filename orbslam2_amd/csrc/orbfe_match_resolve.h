@@ -213,6 +213,64 @@ static inline void build_queries_kf(const Camera &C, const float *sf, int nlevel
             memcpy(&qd[(size_t)32 * i], kf_desc + (size_t)32 * i, 32);
 }
 
+// Sim3 decomposition of the LoopClosing matchers (src/ORBmatcher.cc:293-298, 981-986); see oracle/orb_oracle_match.c
+static inline void sim3_to_rt(const float *Scw, float *T)
+{
+    const double d = (double)Scw[0] * Scw[0] + (double)Scw[1] * Scw[1] + (double)Scw[2] * Scw[2];
+    const float scw = (float)sqrt(d);
+    const float alpha = (float)(1.0 / (double)scw);
+    for (int i = 0; i < 12; i++) T[i] = Scw[i] * alpha;
+}
+// KeyFrame::IsInImage (src/KeyFrame.cc:604-607): a keyframe's bounds are ints initialised from the frame's floats
+ORBFE_RESOLVE_HD static inline bool kf_is_in_image(float min_x, float max_x, float min_y, float max_y, int keyframe, float u, float v)
+{
+    if (keyframe) return u >= (float)(int)min_x && u < (float)(int)max_x && v >= (float)(int)min_y && v < (float)(int)max_y;
+    return u >= min_x && u < max_x && v >= min_y && v < max_y;
+}
+// ORBmatcher::Fuse(pKF, vpMapPoints, th), src/ORBmatcher.cc:821-971, and the Sim3 matchers of LoopClosing (SearchByProjection :285-398
+// and Fuse :973-1096, T and ow from the decomposed Scw): the loop body for one map point up to GetFeaturesInArea.  The three loops differ in one statement: the
+// Sim3 Fuse takes the reciprocal of the depth in double (`double_recip`); their depth tests, float or double, are the same test.
+// Q must hold NO_QUERY; returns 1 when the point opens a window, and then *ur is the projection into the right image (u - bf / z).
+ORBFE_RESOLVE_HD static inline int query_fuse_point(const Camera &C, const float *sf, int nlevels, float log_sf, float min_x, float max_x, float min_y,
+                                                    float max_y, int keyframe, const float *T, const float *ow, int double_recip, const float *pos,
+                                                    const float *normal, int valid, float max_distance, float min_distance, float th, MatchQuery &Q,
+                                                    float *ur)
+{
+    if (!valid) return 0;
+    float pc[3];
+    rt_apply(T, pos, pc);
+    if (pc[2] < 0.0f) return 0;
+    const float invz = double_recip ? (float)(1.0 / (double)pc[2]) : 1 / pc[2];
+    const float x = pc[0] * invz, y = pc[1] * invz;
+    const float u = C.fx * x + C.cx;
+    const float v = C.fy * y + C.cy;
+    if (!kf_is_in_image(min_x, max_x, min_y, max_y, keyframe, u, v)) return 0;
+    float po[3];
+    for (int k = 0; k < 3; k++) po[k] = pos[k] - ow[k];
+    const float dist3d = norm3(po);
+    if (dist3d < 0.8f * min_distance || dist3d > 1.2f * max_distance) return 0;
+    const double dot = (double)po[0] * normal[0] + (double)po[1] * normal[1] + (double)po[2] * normal[2];
+    if (dot < 0.5 * (double)dist3d) return 0;
+    const int lvl = predict_scale(max_distance, dist3d, log_sf, nlevels);
+    Q.u = u; Q.v = v; Q.r = th * sf[lvl]; Q.min_level = lvl - 1; Q.max_level = lvl; Q.flags = 1;
+    *ur = u - C.bf * invz;
+    return 1;
+}
+// The chi-square gates of Fuse on one candidate keypoint (src/ORBmatcher.cc:905-930): reprojection error in stereo where the keypoint
+// has a right coordinate (kur >= 0; pass -1 for a keyframe without mvuRight), else monocular; sf_lv = mvScaleFactors[kpLevel]
+ORBFE_RESOLVE_HD static inline bool fuse_chi2_passes(float u, float v, float ur, float kx, float ky, float kur, float sf_lv)
+{
+    const float inv_sigma2 = 1.0f / (sf_lv * sf_lv); // mvInvLevelSigma2 (src/ORBextractor.cc:419-425)
+    const float ex = u - kx, ey = v - ky;
+    if (kur >= 0) {
+        const float er = ur - kur;
+        const float e2 = ex * ex + ey * ey + er * er;
+        return !((double)(e2 * inv_sigma2) > 7.8);
+    }
+    const float e2 = ex * ex + ey * ey;
+    return !((double)(e2 * inv_sigma2) > 5.99);
+}
+
 // ORBmatcher::SearchForInitialization, src/ORBmatcher.cc:414-421
 static inline void build_queries_initialization(int n1, const orbfe_keypoint *keys1, const uint8_t *desc1, const float *prev_matched, int window_size,
                                                 std::vector<MatchQuery> &q, std::vector<uint8_t> &qd)

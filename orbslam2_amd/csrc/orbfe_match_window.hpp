@@ -28,6 +28,18 @@ struct GridFrame {
     int *cell_off, *cell_idx;         // CSR over ix * GRID_ROWS + iy
 };
 
+// The geometry of a GridFrame from the frame's float bounds, on the host, for every path that builds one: cells are assigned with the
+// floats (mfGridElementWidthInv / HeightInv, src/Frame.cc:99-100); a KeyFrame's windows use (float)(int) of the lower bounds
+// (KeyFrame::mnMinX is an int initialised from the frame's float, src/KeyFrame.cc:568-580)
+static inline void grid_frame_geometry(GridFrame &f, float min_x, float max_x, float min_y, float max_y, bool keyframe)
+{
+    f.min_x = min_x; f.min_y = min_y;
+    f.inv_w = (float)GRID_COLS / (max_x - min_x);
+    f.inv_h = (float)GRID_ROWS / (max_y - min_y);
+    f.q_min_x = keyframe ? (float)(int)min_x : min_x;
+    f.q_min_y = keyframe ? (float)(int)min_y : min_y;
+}
+
 __device__ __forceinline__ int frame_count(const GridFrame &f)
 {
     if (!f.n_ptr) return f.cap;
@@ -65,22 +77,38 @@ __device__ __forceinline__ Window query_window(const GridFrame &f, const orbfe_r
 
 // Calls fn(ix, iy, idx, kp) for every keypoint of the window this lane owns (cells lane, lane + 64, ...) that passes the level
 // and radius tests.
-template <class Fn>
-__device__ __forceinline__ void for_each_hit(const GridFrame &f, const orbfe_resolve::MatchQuery &Q, const Window &w, int lane, Fn fn)
+// CHECKED is for a grid and keypoints that the caller uploaded (orbfe_grid_keyframe) instead of grid_build_kernel and the extraction:
+// a cell's offsets must lie in 0 <= begin <= end <= n, an index in [0, n) and a keypoint's octave in [0, nlevels), each tested before
+// it is used as an address (the octave indexes the caller's level tables); what fails is skipped and the walk returns false.  The
+// octave is tested on every keypoint of a walked cell, before the level test drops it.  Unchecked, the walk is as it always was.
+template <bool CHECKED = false, class Fn>
+__device__ __forceinline__ bool for_each_hit(const GridFrame &f, const orbfe_resolve::MatchQuery &Q, const Window &w, int lane, Fn fn, int n = 0, int nlevels = 0)
 {
     const bool check_levels = (Q.min_level > 0) || (Q.max_level >= 0); // Q5, literally
+    bool ok = true;
     for (int c = lane; c < w.ncells; c += 64) {
         const int ix = w.min_cx + c / w.ncy, iy = w.min_cy + c % w.ncy;
         const int cell = ix * GRID_ROWS + iy;
+        int begin = 0, end = 0;
+        if constexpr (CHECKED) {
+            begin = f.cell_off[cell];
+            end = f.cell_off[cell + 1];
+            if (begin < 0 || end < begin || end > n) { ok = false; continue; }
+        }
 #pragma unroll 1 // a counting fn would otherwise be unrolled 16 deep: a cell holds a keypoint or two, and the registers cost occupancy
-        for (int j = f.cell_off[cell]; j < f.cell_off[cell + 1]; j++) {
+        for (int j = CHECKED ? begin : f.cell_off[cell]; j < (CHECKED ? end : f.cell_off[cell + 1]); j++) {
             const int idx = f.cell_idx[j];
+            if constexpr (CHECKED)
+                if (idx < 0 || idx >= n) { ok = false; continue; }
             const KeyPointPOD kp = f.keys[idx];
+            if constexpr (CHECKED)
+                if (kp.octave < 0 || kp.octave >= nlevels) { ok = false; continue; }
             if (check_levels && (kp.octave < Q.min_level || (Q.max_level >= 0 && kp.octave > Q.max_level))) continue;
             if (!(fabsf(__fsub_rn(kp.x, Q.u)) < Q.r && fabsf(__fsub_rn(kp.y, Q.v)) < Q.r)) continue;
             fn(ix, iy, idx, kp);
         }
     }
+    return ok;
 }
 // The key of a hit: the Hamming distance to the query descriptor qd over the hit's place in GetFeaturesInArea order
 __device__ __forceinline__ unsigned long long candidate_key(const GridFrame &f, const orbfe_resolve::MatchQuery &Q, const uint32_t (&qd)[8], int ix, int iy, int idx,

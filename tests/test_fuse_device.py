@@ -1,0 +1,386 @@
+"""ORBmatcher::Fuse on device-resident keyframes: orbfe_enqueue_keyframe_grid, orbfe_enqueue_fuse (src/ORBmatcher.cc:821-971) and
+orbfe_enqueue_fuse_sim3 (:973-1096) of orbslam2_amd/csrc/orbfe_fuse_device.hip.  Every comparison is exact: against the C oracle and
+against the synchronous entry point (orbfe_fuse / orbfe_fuse_sim3) on the same arrays.  The inputs are the census inputs of
+tests/matcher_census.py; the CPU test below pins what they reach, so that the GPU tests cannot pass on inputs that decide nothing.
+
+Device arrays are torch tensors, every input over-allocated by PAD zero entries (a check the kernel misses then reads inside the
+test's own allocation and shows as a wrong status or result), every output surrounded by GUARD sentinel cells; the stream is never
+the default one.
+"""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import pytest
+
+from oracle import oracle as O
+from tests import matcher_census as MC
+from tests.test_gpu_matcher_census import hip_run
+from tests.test_matchers_device import _ctx
+
+NAMES = ["orbfe_enqueue_keyframe_grid", "orbfe_enqueue_fuse", "orbfe_enqueue_fuse_sim3"]
+PAD, GUARD, UNTOUCHED = 64, 32, -7
+CELLS = 64 * 48
+FUSE_INPUTS = [name for name, v in MC.INPUTS.items() if "fuse" in v[1]]
+SIM3_INPUTS = [name for name, v in MC.INPUTS.items() if "sim3_fuse" in v[1]]
+REACHED = ("accepted_on_tie", "tie_winner_not_lowest_index", "cand_chi2_mono", "cand_chi2_stereo", "cand_below_level", "cand_above_level",
+           "best_above_threshold", "z_negative", "z_zero", "too_near", "too_far", "view_cos", "level_clamped_high", "window_empty",
+           "out_left", "out_right", "out_top", "out_bottom")
+
+
+# ------------------------------------------------------------------ CPU
+def test_the_library_exports_the_calls_and_the_keyframe_record():
+    from orbslam2_amd import api
+    L = api.load()
+    for name in NAMES:
+        assert name in api.EXPORTS
+        fn = getattr(L, name)  # AttributeError: the symbol is not exported
+        args = [0 if t is C.c_int else 0.0 if t is C.c_float else None for t in fn.argtypes]
+        assert fn(*args) == api.ERR_INVALID, name
+    for m in ("enqueue_keyframe_grid", "enqueue_fuse", "enqueue_fuse_sim3"):
+        assert callable(getattr(api.Context, m))
+    assert C.sizeof(api.GridKeyframe) == 64
+
+
+def test_the_census_inputs_reach_what_the_kernel_can_get_wrong():
+    """Summed over the inputs that have the matcher, every decision the kernel restates goes both ways (the pinned table of
+    tests/test_matcher_census.py): ties that the key order decides, both chi-square gates, both sides of the level band, every
+    projection gate, every image border.  z_zero on the Sim3 side exists only in among_kfbounds and is not asked for."""
+    table = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", MC.GOLDEN)))
+    assert len(FUSE_INPUTS) == 10 and len(SIM3_INPUTS) == 9
+    for matcher, names, skip in (("fuse", FUSE_INPUTS, ()), ("sim3_fuse", SIM3_INPUTS, ("cand_chi2_mono", "cand_chi2_stereo", "z_zero"))):
+        for key in REACHED:
+            if key in skip:
+                continue
+            total = sum(table["%s/%s" % (name, matcher)][key] for name in names)
+            assert total > 0, (matcher, key)
+        assert sum(table["%s/%s" % (name, matcher)]["accepted_on_tie"] for name in names) >= 70  # ties that the key order decides
+    assert table["overflow/fuse"]["cand_chi2_mono"] + table["overflow/fuse"]["cand_chi2_stereo"] >= 23218
+    s = MC.build("tie_wide")
+    ref, _ = MC.oracle_run("fuse", s, MC.INPUTS["tie_wide"][1]["fuse"])
+    assert ref.max() > 32768 and len(s["k"]) > 32768
+    # a query count that does not fill the last workgroup (four waves, one query each)
+    assert any(len(MC.build(name)["pos"]) % 4 for name in FUSE_INPUTS)
+
+
+# ------------------------------------------------------------------ helpers (GPU)
+def _dev(a):
+    import torch
+    a = np.ascontiguousarray(a)
+    a = np.concatenate([a, np.zeros(PAD, a.dtype)])
+    return torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to("cuda:0")
+
+
+def _guarded(n, dtype=None):
+    import torch
+    return torch.full((GUARD + max(n, 1) + GUARD,), UNTOUCHED, dtype=dtype or torch.int32, device="cuda:0")
+
+
+def _inside(t, n):
+    """The n cells between the guards; asserts that the guards still hold the sentinel."""
+    a = t.cpu().numpy()
+    assert (a[:GUARD] == UNTOUCHED).all() and (a[GUARD + n:] == UNTOUCHED).all(), "a guard cell was written"
+    return a[GUARD:GUARD + n]
+
+
+class _Kf:
+    """A keyframe's arrays in HBM, its grid (built by the call under test on `stream`) and its record."""
+
+    def __init__(self, api, ctx, stream, k, d, ur, bounds, keyframe, n=None, grid=True):
+        self.n = len(k) if n is None else n
+        self.keys, self.desc = _dev(k), _dev(np.ascontiguousarray(d, np.uint8).reshape(-1))
+        self.ur = None if ur is None else _dev(np.ascontiguousarray(ur, np.float32))
+        self.off, self.idx = _guarded(CELLS + 1), _guarded(self.n)
+        self.bounds, self.keyframe, self.api = bounds, keyframe, api
+        if grid:
+            ctx.enqueue_keyframe_grid(self.keys.data_ptr(), self.n, bounds, self.off.data_ptr() + 4 * GUARD, self.idx.data_ptr() + 4 * GUARD,
+                                      stream.cuda_stream)
+        self.rec = self.record()
+
+    def record(self, off=None, idx=None, keys=None, n=None):
+        p = lambda t: t.data_ptr() + 4 * GUARD
+        return self.api.GridKeyframe((keys if keys is not None else self.keys).data_ptr(), 0 if self.ur is None else self.ur.data_ptr(), self.desc.data_ptr(),
+                                     p(self.off if off is None else off), p(self.idx if idx is None else idx), *[float(b) for b in self.bounds],
+                                     self.n if n is None else n, 1 if self.keyframe else 0)
+
+
+def _kf_of(api, ctx, stream, s, ur):
+    return _Kf(api, ctx, stream, s["k"], s["d"], ur, s["bounds"], s["keyframe"])
+
+
+class _Table:
+    """The map points of a scene as a table in HBM, uploaded once."""
+
+    def __init__(self, s):
+        self.n = len(s["pos"])
+        self.t = [_dev(np.ascontiguousarray(s[key], dt).reshape(-1)) for key, dt in (("pos", np.float32), ("normal", np.float32), ("max_d", np.float32),
+                                                                                      ("min_d", np.float32), ("desc", np.uint8))]
+
+    def ptrs(self):
+        return [t.data_ptr() for t in self.t]
+
+
+class _Out:
+    """best_idx[n_pts], count, status between guards."""
+
+    def __init__(self, n_pts):
+        self.n = n_pts
+        self.best, self.count, self.status = _guarded(n_pts), _guarded(1), _guarded(1)
+
+    def ptrs(self):
+        return [t.data_ptr() + 4 * GUARD for t in (self.best, self.count, self.status)]
+
+    def fetch(self):
+        return _inside(self.best, self.n), int(_inside(self.count, 1)[0]), int(_inside(self.status, 1)[0])
+
+
+def _enqueue(ctx, sim3, rec, pose, table, d_valid, th, out, stream, n_pts=None, d_index=None):
+    fn = ctx.enqueue_fuse_sim3 if sim3 else ctx.enqueue_fuse
+    fn(rec, pose, table.n if n_pts is None else n_pts, 0 if d_index is None else d_index.data_ptr(), table.n, *table.ptrs(), d_valid.data_ptr(), th,
+       *out.ptrs(), stream=stream.cuda_stream)
+
+
+def _check(out, ref, nref, what):
+    best, count, status = out.fetch()
+    bad = np.nonzero(best != ref)[0]
+    assert status == 0, (what, status)
+    assert count == nref and bad.size == 0, "%s: count %d vs %d; differ at %s: device %s, reference %s" % (
+        what, count, nref, bad[:8].tolist(), best[bad[:8]].tolist(), ref[bad[:8]].tolist())
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+    from orbslam2_amd import api
+    ctx = _ctx(api)
+    assert np.array_equal(ctx.tables()["scale"], O.Extractor().scale_factors())
+    yield api, ctx, torch.cuda.Stream()
+    ctx.close()
+
+
+def _run_census_input(gpu, name, matcher):
+    import torch
+    api, ctx, st = gpu
+    sim3 = matcher == "sim3_fuse"
+    s, p = MC.build(name), MC.INPUTS[name][1][matcher]
+    ref, nref = MC.oracle_run(matcher, s, p)
+    sref, snref = hip_run(ctx, matcher, s, p)
+    assert snref == nref and np.array_equal(sref, ref), "the synchronous call differs from the oracle"
+    kf = _kf_of(api, ctx, st, s, MC._ur(s, matcher, p))  # a monocular case passes u_right = NULL
+    table, d_valid = _Table(s), _dev(s["valid"])
+    torch.cuda.synchronize()
+    for call in range(2):
+        out = _Out(table.n)
+        _enqueue(ctx, sim3, kf.rec, s["Scw"] if sim3 else s["T_cur"], table, d_valid, p[0], out, st)
+        st.synchronize()
+        _check(out, ref, nref, "%s / %s, call %d" % (name, matcher, call))
+    _inside(kf.off, CELLS + 1), _inside(kf.idx, kf.n)  # the grid's guards
+
+
+# ------------------------------------------------------------------ GPU
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["fuse_40", "kfbounds_71", "tie_wide"])
+def test_gpu_keyframe_grid_equals_assign_features_to_grid(gpu, name):
+    api, ctx, st = gpu
+    s = MC.build(name)
+    n = len(s["k"])
+    L = ctx.L
+    L.orbfe_assign_features_to_grid.restype = C.c_int
+    L.orbfe_assign_features_to_grid.argtypes = [C.c_void_p] * 4
+    off_ref, idx_ref = np.zeros(CELLS + 1, np.int32), np.zeros(n, np.int32)
+    view = ctx._view(s["k"], None, s["d"], s["bounds"])
+    assert L.orbfe_assign_features_to_grid(ctx.h, C.byref(view), off_ref.ctypes.data_as(C.c_void_p), idx_ref.ctypes.data_as(C.c_void_p)) == 0
+    kf = _kf_of(api, ctx, st, s, None)
+    st.synchronize()
+    off, idx = _inside(kf.off, CELLS + 1), _inside(kf.idx, n)
+    assert np.array_equal(off, off_ref)
+    total = int(off[CELLS])
+    assert 0 < total <= n and (idx[total:] == UNTOUCHED).all()
+    cell = np.repeat(np.arange(CELLS), np.diff(off))
+    order = np.lexsort((idx[:total], cell))  # ascending inside every cell: the order inside a cell is free
+    assert np.array_equal(idx[:total][order], idx_ref[:total])
+    if name == "kfbounds_71":
+        assert s["bounds"][0] != int(s["bounds"][0])  # cells are assigned with the frame's float bounds
+    # n == 0: 3073 zero offsets, no other pointer read
+    off0 = _guarded(CELLS + 1)
+    ctx.enqueue_keyframe_grid(0, 0, s["bounds"], off0.data_ptr() + 4 * GUARD, 0, st.cuda_stream)
+    st.synchronize()
+    assert (_inside(off0, CELLS + 1) == 0).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", FUSE_INPUTS)
+def test_gpu_fuse_equals_the_oracle_and_the_synchronous_call(gpu, name):
+    _run_census_input(gpu, name, "fuse")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SIM3_INPUTS)
+def test_gpu_fuse_sim3_equals_the_oracle_and_the_synchronous_call(gpu, name):
+    _run_census_input(gpu, name, "sim3_fuse")
+
+
+@pytest.mark.gpu
+def test_gpu_fuse_through_an_index_list_with_validity_per_query(gpu):
+    """A permuted list with duplicates over a table larger than the list: row q is the oracle's answer for point index[q] under the
+    query's own validity.  An entry equal to n_rows and one equal to -1 are refused before they address the table."""
+    import torch
+    api, ctx, st = gpu
+    s, p = MC.build("fuse_40"), MC.INPUTS["fuse_40"][1]["fuse"]
+    rng = np.random.default_rng(9)
+    n_rows, nq = len(s["pos"]), 1001
+    index = rng.permutation(n_rows)[:nq].astype(np.int32)
+    index[1::7] = index[0:-1:7][: len(index[1::7])]  # duplicates
+    assert nq < n_rows and nq % 4 and len(np.unique(index)) < nq
+    valid = (s["valid"][index] & (rng.random(nq) < 0.8)).astype(np.int32)  # per query: the same row may be valid in one and not in another
+    dup = index[0]
+    valid[np.nonzero(index == dup)[0][0]] = 1 - valid[np.nonzero(index == dup)[0][1]]
+    gathered = dict(s, valid=valid, **{key: s[key][index] for key in ("pos", "normal", "max_d", "min_d", "desc")})
+    ref, nref = MC.oracle_run("fuse", gathered, p)
+    assert nref > 100
+    kf, table = _kf_of(api, ctx, st, s, s["ur"]), _Table(s)
+    d_index, d_valid = _dev(index), _dev(valid)
+    out = _Out(nq)
+    torch.cuda.synchronize()
+    _enqueue(ctx, False, kf.rec, s["T_cur"], table, d_valid, p[0], out, st, nq, d_index)
+    st.synchronize()
+    _check(out, ref, nref, "index list")
+    hit = np.nonzero(ref >= 0)[0]
+    bad_index = index.copy()
+    bad_index[hit[0]], bad_index[hit[1]] = n_rows, -1
+    d_bad = _dev(bad_index)
+    out = _Out(nq)
+    torch.cuda.synchronize()
+    _enqueue(ctx, False, kf.rec, s["T_cur"], table, d_valid, p[0], out, st, nq, d_bad)
+    st.synchronize()
+    best, _, status = out.fetch()
+    expect = ref.copy()
+    expect[hit[:2]] = -1
+    assert status == api.ERR_INVALID and np.array_equal(best, expect)
+
+
+@pytest.mark.gpu
+def test_gpu_search_in_neighbors_loop_patches_validity_on_the_stream(gpu):
+    """One point table against three target keyframes that see it from three poses, the three calls queued on one stream; between two
+    calls a torch op on that stream clears d_pt_valid for every other point the previous call fused (what MapPoint::Replace and
+    IsInKeyFrame change between two targets).  One synchronise at the end; the oracle replays the same patches."""
+    import torch
+    from tests import test_matchers as TM
+    api, ctx, st = gpu
+    poses = [TM._se3(2.0, [0.02, -0.01, -0.3]), TM._se3(1.0, [0.25, 0.0, 0.03]), TM._se3(-1.5, [-0.1, 0.05, -0.2])]
+    scenes = [MC._camera_scene(301, T) for T in poses]
+    base = scenes[0]
+    n = len(base["pos"])
+    assert all(np.array_equal(sc["pos"], base["pos"]) and np.array_equal(sc["desc"], base["desc"]) for sc in scenes)
+    th, p = 3.0, (3.0, True)
+    # the oracle: target after target, the table and the first scene's normals, validity patched in between
+    valid, refs, unpatched = base["valid"].copy(), [], []
+    for sc in scenes:
+        tgt = dict(sc, normal=base["normal"], max_d=base["max_d"], min_d=base["min_d"])
+        refs.append(MC.oracle_run("fuse", dict(tgt, valid=valid), p))
+        unpatched.append(MC.oracle_run("fuse", dict(tgt, valid=base["valid"]), p))
+        valid = valid.copy()
+        valid[np.nonzero(refs[-1][0] >= 0)[0][::2]] = 0
+    assert all(nref > 50 for _, nref in refs) and any(not np.array_equal(a[0], b[0]) for a, b in zip(refs, unpatched))
+    kfs = [_kf_of(api, ctx, st, sc, sc["ur"]) for sc in scenes]
+    table, d_valid = _Table(base), _dev(base["valid"])
+    outs = [_Out(n) for _ in scenes]
+    torch.cuda.synchronize()
+    with torch.cuda.stream(st):
+        for sc, kf, out in zip(scenes, kfs, outs):
+            _enqueue(ctx, False, kf.rec, sc["T_cur"], table, d_valid, th, out, st)
+            m = out.best[GUARD:GUARD + n]
+            hit = m >= 0
+            every_other = (hit.to(torch.int32).cumsum(0) % 2 == 1) & hit  # the 1st, 3rd, ... fused point
+            d_valid.view(torch.int32)[:n] *= (~every_other).to(torch.int32)
+    st.synchronize()
+    for k, (out, (ref, nref)) in enumerate(zip(outs, refs)):
+        _check(out, ref, nref, "target %d" % k)
+    assert np.array_equal(d_valid.view(torch.int32)[:n].cpu().numpy(), valid)
+
+
+@pytest.mark.gpu
+def test_gpu_refused_inputs_are_reported_in_the_status_and_write_nothing_outside_the_outputs(gpu):
+    import torch
+    api, ctx, st = gpu
+    s, p = MC.build("fuse_40"), MC.INPUTS["fuse_40"][1]["fuse"]
+    ref, nref = MC.oracle_run("fuse", s, p)
+    n, n_pts = len(s["k"]), len(s["pos"])
+    cand = int(ref[ref >= 0][0])  # a keypoint that is a candidate of a valid point: the oracle's first match
+    kf, table, d_valid = _kf_of(api, ctx, st, s, s["ur"]), _Table(s), _dev(s["valid"])
+    st.synchronize()
+    off, idx = _inside(kf.off, CELLS + 1).copy(), _inside(kf.idx, n).copy()
+    j = int(np.nonzero(idx[: off[CELLS]] == cand)[0][0])
+    cell = int(np.searchsorted(off, j, side="right")) - 1
+    assert off[cell] <= j < off[cell + 1]
+
+    def guarded_copy(a):
+        t = _guarded(len(a))
+        t[GUARD:GUARD + len(a)] = torch.from_numpy(a).to("cuda:0")
+        return t
+
+    bad_octave = s["k"].copy()
+    bad_octave["octave"][cand] = MC.NL
+    bad_idx = idx.copy()
+    bad_idx[j] = n
+    bad_off = off.copy()
+    bad_off[cell + 1] = off[cell] - 1
+    keep = [_dev(bad_octave), guarded_copy(bad_idx), guarded_copy(bad_off)]
+    cases = {"octave == nlevels on a candidate keypoint": kf.record(keys=keep[0]), "a cell_idx entry equal to n": kf.record(idx=keep[1]),
+             "a descending cell_off": kf.record(off=keep[2])}
+    torch.cuda.synchronize()
+    for what, rec in cases.items():
+        out = _Out(n_pts)
+        _enqueue(ctx, False, rec, s["T_cur"], table, d_valid, p[0], out, st)
+        st.synchronize()
+        _, _, status = out.fetch()  # and the guards
+        assert status == api.ERR_INVALID, (what, status)
+        out = _Out(n_pts)  # the next call on clean inputs is exact again
+        _enqueue(ctx, False, kf.rec, s["T_cur"], table, d_valid, p[0], out, st)
+        st.synchronize()
+        _check(out, ref, nref, "clean call after: " + what)
+    # the refused grids were inputs: they and their guards are as they were uploaded
+    assert np.array_equal(_inside(keep[1], n), bad_idx) and np.array_equal(_inside(keep[2], CELLS + 1), bad_off)
+    assert np.array_equal(_inside(kf.idx, n), idx) and np.array_equal(_inside(kf.off, CELLS + 1), off)
+    # what the host can see is refused by the call itself and queues nothing
+    out = _Out(n_pts)
+    null_keys = kf.record()
+    null_keys.keys_un = None
+    for rec in (null_keys, kf.record(n=65536), kf.record(n=-1)):
+        with pytest.raises(api.OrbfeError):
+            _enqueue(ctx, False, rec, s["T_cur"], table, d_valid, p[0], out, st)
+    with pytest.raises(api.OrbfeError):  # more queries than rows without an index list
+        _enqueue(ctx, False, kf.rec, s["T_cur"], table, d_valid, p[0], out, st, n_pts=table.n + 1)
+    with pytest.raises(api.OrbfeError):
+        _enqueue(ctx, False, kf.rec, s["T_cur"], table, d_valid, p[0], out, st, n_pts=-1)
+    with pytest.raises(api.OrbfeError):  # a NULL output
+        ctx.enqueue_fuse(kf.rec, s["T_cur"], table.n, 0, table.n, *table.ptrs(), d_valid.data_ptr(), p[0], out.ptrs()[0], 0, out.ptrs()[2],
+                         stream=st.cuda_stream)
+    with pytest.raises(api.OrbfeError):
+        ctx.enqueue_keyframe_grid(kf.keys.data_ptr(), 65536, s["bounds"], kf.off.data_ptr() + 4 * GUARD, kf.idx.data_ptr() + 4 * GUARD, st.cuda_stream)
+    st.synchronize()
+    assert all((t == UNTOUCHED).all() for t in (out.best, out.count, out.status))
+
+
+@pytest.mark.gpu
+def test_gpu_empty_shapes(gpu):
+    import torch
+    api, ctx, st = gpu
+    s, p = MC.build("fuse_40"), MC.INPUTS["fuse_40"][1]["fuse"]
+    n_pts = len(s["pos"])
+    kf, table = _kf_of(api, ctx, st, s, s["ur"]), _Table(s)
+    d_valid, d_none = _dev(s["valid"]), _dev(np.zeros(n_pts, np.int32))
+    empty = api.GridKeyframe(0, 0, 0, 0, 0, *[float(b) for b in s["bounds"]], 0, 1)  # a keyframe without keypoints: no array at all
+    torch.cuda.synchronize()
+    for sim3 in (False, True):
+        pose = s["Scw"] if sim3 else s["T_cur"]
+        out = _Out(0)  # n_pts == 0: count 0, status 0, nothing else
+        _enqueue(ctx, sim3, kf.rec, pose, table, d_valid, p[0], out, st, n_pts=0)
+        st.synchronize()
+        assert out.fetch()[1:] == (0, 0) and (out.best == UNTOUCHED).all()
+        for what, rec, valid in (("kf->n == 0", empty, d_valid), ("every point invalid", kf.rec, d_none)):
+            out = _Out(n_pts)
+            _enqueue(ctx, sim3, rec, pose, table, valid, p[0], out, st)
+            st.synchronize()
+            _check(out, np.full(n_pts, -1, np.int32), 0, what)

@@ -36,6 +36,16 @@ patched on the host in between; (b) -- when the library has it -- 20 x (orbfe_en
 count and d_pairs into pinned memory + stream synchronise), the has_mp1 patch queued on the stream in between, as wall time, and the
 20 enqueues queued back to back as GPU time between two events.  Both are checked against the oracle run with the same patches.
 Five repeats of each, interleaved; every repeat is the mean of 10 loops over the 20 neighbours, its slowest loop beside it.
+    python3 tools/bench_matchers.py --fuse [--lib path/to/another/liborbfe.so]
+runs only the SearchInNeighbors rows (profiles/fuse_device.json): a stereo keyframe with 1500 map points against 30 target keyframes of
+about 2000 keypoints (the camera scene of tests/matcher_census.py seen from 30 poses), th 3, then the closing call: 30 000 candidate
+rows (jittered copies of the 1500 points, 1000 per target) against the current keyframe through an index list.  A point's validity
+depends on the target (a random 30 % are "already in that keyframe"), and after every target every eighth point it fused turns bad for
+the targets that follow (MapPoint::Replace).  (a) the 31 synchronous orbfe_fuse calls, validity patched on the host, the closing
+call's arrays gathered outside the timed window; (b) -- when the library has it -- 31 x (orbfe_enqueue_fuse + download of best_idx and
+the count into pinned memory + stream synchronise), the validity patch queued on the stream, grids and table uploaded outside the
+timed window; (c) the 31 enqueues queued back to back as GPU time between two events.  (a) and (b) are checked against the oracle run
+with the same patches.  Five repeats of each, interleaved; every repeat is the mean of 10 loops, its slowest loop beside it.
 """
 import json
 import os
@@ -681,6 +691,151 @@ def triangulation_rows(out):
     ctx.close()
 
 
+def fuse_rows(out):
+    """Rows of --fuse; arguments prepared once."""
+    import gc
+    import torch
+    from orbslam2_amd import api
+    from tests import matcher_census as MC
+    dev = torch.device("cuda:0")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
+    K, N_PTS, PER_TARGET, TH, REPS, REPEATS = 30, 1500, 1000, 3.0, 10, 5
+    ctx = api.Context(width=MC.W, height=MC.H, fx=MC.FX, fy=MC.FY, cx=MC.CX, cy=MC.CY, bf=MC.BF)
+    have = hasattr(ctx.L, "orbfe_enqueue_fuse")
+    rng = np.random.default_rng(77)
+    poses = [TM._se3(float(rng.uniform(-3, 3)), [float(rng.uniform(-0.3, 0.3)), float(rng.uniform(-0.1, 0.1)), float(rng.uniform(-0.4, 0.1))]) for _ in range(K)]
+    cur = MC._camera_scene(401, TM._se3(0.5, [0.05, 0.0, -0.1]), n_pts=N_PTS, n_distract=800)  # the current keyframe and the table's first rows
+    targets = [MC._camera_scene(401, T, n_pts=N_PTS, n_distract=800) for T in poses]
+    assert all(np.array_equal(t["pos"], cur["pos"]) for t in targets)
+    # the table: the current keyframe's 1500 points, then the targets' 30 x 1000: jittered copies of them
+    src = rng.integers(0, N_PTS, K * PER_TARGET)
+    flips = np.packbits(rng.random((len(src), 256)) < 0.03, axis=1, bitorder="little")
+    tab = dict(pos=np.concatenate([cur["pos"], (cur["pos"][src] + rng.normal(0, 0.01, (len(src), 3))).astype(np.float32)]),
+               normal=np.concatenate([cur["normal"], cur["normal"][src]]), max_d=np.concatenate([cur["max_d"], cur["max_d"][src]]),
+               min_d=np.concatenate([cur["min_d"], cur["min_d"][src]]), desc=np.concatenate([cur["desc"], cur["desc"][src] ^ flips]))
+    n_rows = len(tab["pos"])
+    index = (N_PTS + rng.permutation(K * PER_TARGET)).astype(np.int32)   # vpFuseCandidates of the closing call
+    valid_close = (rng.random(len(index)) < 0.85).astype(np.int32)
+    close = {k: np.ascontiguousarray(v[index]) for k, v in tab.items()}  # what the synchronous call takes: gathered arrays
+    fields = ("pos", "normal", "max_d", "min_d", "desc")
+    # validity per target: pMP && !isBad() && !IsInKeyFrame(target); every eighth fused point turns bad for the targets that follow
+    base_valid = (cur["valid"][None, :] & (rng.random((K, N_PTS)) >= 0.3)).astype(np.int32)
+    turns_bad = lambda got: np.nonzero(got >= 0)[0][::8]
+    # the oracle, target after target
+    bad, refs = np.zeros(N_PTS, bool), []
+    for k, t in enumerate(targets):
+        ref, nref = MC.oracle_run("fuse", dict(t, valid=base_valid[k] * ~bad, **{f: tab[f][:N_PTS] for f in fields}), (TH, True))
+        refs.append((ref, nref))
+        bad[turns_bad(ref)] = True
+    refs.append(MC.oracle_run("fuse", dict(cur, valid=valid_close, **close), (TH, True)))
+    out["scene"] = "%d map points against %d targets of %d .. %d keypoints, th %g, stereo; fused per target %d .. %d; closing call: %d rows of a %d-row table, %d fused" % (
+        N_PTS, K, min(len(t["k"]) for t in targets), max(len(t["k"]) for t in targets), TH, min(r[1] for r in refs[:K]), max(r[1] for r in refs[:K]),
+        len(index), n_rows, refs[K][1])
+    views = [ctx._view(t["k"], t["ur"], t["d"], t["bounds"], keyframe=True) for t in targets + [cur]]
+    first = {k: np.ascontiguousarray(tab[k][:N_PTS]) for k in fields}
+
+    def sync_loop(check=False):
+        bad = np.zeros(N_PTS, bool)
+        for k, t in enumerate(targets):
+            got, ngot = ctx.fuse(views[k], t["T_cur"], first["pos"], first["normal"], first["max_d"], first["min_d"], first["desc"], base_valid[k] * ~bad, TH)
+            if check:
+                assert ngot == refs[k][1] and np.array_equal(got, refs[k][0]), k
+            bad[turns_bad(got)] = True
+        got, ngot = ctx.fuse(views[K], cur["T_cur"], close["pos"], close["normal"], close["max_d"], close["min_d"], close["desc"], valid_close, TH)
+        if check:
+            assert ngot == refs[K][1] and np.array_equal(got, refs[K][0])
+
+    sync_loop(check=True)
+    if have:
+        st = torch.cuda.Stream()
+        keep, recs = [], []
+        for t in targets + [cur]:  # once per keyframe: arrays, grid, record
+            n = len(t["k"])
+            a = [up(t["k"]), up(t["ur"]), up(t["d"]), torch.zeros(64 * 48 + 1, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)]
+            ctx.enqueue_keyframe_grid(a[0].data_ptr(), n, t["bounds"], a[3].data_ptr(), a[4].data_ptr(), st.cuda_stream)
+            keep.append(a)
+            recs.append(api.GridKeyframe(*[x.data_ptr() for x in a], *[float(b) for b in t["bounds"]], n, 1))
+        d_tab = [up(tab[k]) for k in fields]  # once per new keyframe
+        tp = [x.data_ptr() for x in d_tab]
+        d_index, d_valid_close = up(index), up(valid_close)
+        d_valid = up(base_valid[0])
+        h_valid = torch.from_numpy(base_valid[0].copy()).pin_memory()  # the next target's validity, written on the host and queued as one 6 KB copy
+        nq = len(index)
+        d_res = torch.zeros(2 + nq, dtype=torch.int32, device=dev)     # count, status, best_idx: one download
+        h_res = torch.zeros(2 + nq, dtype=torch.int32).pin_memory()
+        res = h_res.numpy()
+        rp = d_res.data_ptr()
+        st.synchronize()
+
+        def enqueue(k):
+            if k < K:
+                ctx.enqueue_fuse(recs[k], targets[k]["T_cur"], N_PTS, 0, n_rows, *tp, d_valid.data_ptr(), TH, rp + 8, rp, rp + 4, stream=st.cuda_stream)
+            else:
+                ctx.enqueue_fuse(recs[K], cur["T_cur"], nq, d_index.data_ptr(), n_rows, *tp, d_valid_close.data_ptr(), TH, rp + 8, rp, rp + 4,
+                                 stream=st.cuda_stream)
+
+        def device_loop(check=False):
+            bad = np.zeros(N_PTS, bool)
+            with torch.cuda.stream(st):
+                h_valid.numpy()[:] = base_valid[0]
+                d_valid.view(torch.int32).copy_(h_valid, non_blocking=True)
+                for k in range(K + 1):
+                    enqueue(k)
+                    m = N_PTS if k < K else nq
+                    h_res[:2 + m].copy_(d_res[:2 + m], non_blocking=True)
+                    st.synchronize()
+                    got = res[2:2 + m]
+                    if check:
+                        assert res[1] == 0 and res[0] == refs[k][1] and np.array_equal(got, refs[k][0]), k
+                    if k + 1 < K:  # the map mutation happens here; then the next target's validity goes up
+                        bad[turns_bad(got)] = True
+                        h_valid.numpy()[:] = base_valid[k + 1] * ~bad
+                        d_valid.view(torch.int32).copy_(h_valid, non_blocking=True)
+                st.synchronize()
+
+        device_loop(check=True)
+
+    def loops(fn):
+        fn()
+        gc.collect()
+        gc.disable()  # the cyclic collector is off inside the window, as in the standard timeit module
+        try:
+            t = []
+            for _ in range(REPS):
+                t0 = time.perf_counter()
+                fn()
+                t.append((time.perf_counter() - t0) * 1e3)
+        finally:
+            gc.enable()
+        return round(sum(t) / REPS, 4), round(max(t), 4)
+
+    a_rows, a_worst, b_wall, b_worst, c_gpu = [], [], [], [], []
+    for _ in range(REPEATS):
+        m, w = loops(sync_loop)
+        a_rows.append(m); a_worst.append(w)
+        if have:
+            m, w = loops(device_loop)
+            b_wall.append(m); b_worst.append(w)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            for _ in range(REPS):
+                for k in range(K + 1):
+                    enqueue(k)
+            e1.record(st)
+            st.synchronize()
+            c_gpu.append(round(e0.elapsed_time(e1) / REPS, 4))
+    out["rows"]["(a) orbfe_fuse x %d, synchronous, validity patched on the host, wall time" % (K + 1)] = {"ms_per_repeat": a_rows, "slowest_loop_ms": a_worst}
+    if have:
+        out["rows"]["(b) %d x (orbfe_enqueue_fuse + download of best_idx and count + synchronise), validity patch queued in between, wall time" % (K + 1)] = {
+            "ms_per_repeat": b_wall, "slowest_loop_ms": b_worst}
+        out["rows"]["(c) the %d enqueues alone, queued back to back, GPU time between two events" % (K + 1)] = {"ms_per_repeat": c_gpu}
+        out["median (a) / median (b)"] = round(float(np.median(a_rows) / np.median(b_wall)), 2)
+        out["max (b) < min (a)"] = bool(max(b_wall) < min(a_rows))
+    else:
+        out["device"] = "not exported by this library"
+    ctx.close()
+
+
 def load_other_build(api, path):
     """api.load() on the library at `path`, which may be older than the package: the prototypes load() sets for entry points
     that build lacks land on stand-ins that are not kept, so hasattr(lib, name) is False afterwards and a call fails loudly."""
@@ -718,6 +873,12 @@ def main():
     if "--triangulation" in sys.argv[1:]:
         out = {"unit": "ms per keyframe (20 neighbours)", "rows": {}}
         triangulation_rows(out)
+        out["build_id"] = api.build_id()
+        print(json.dumps(out, indent=1))
+        return
+    if "--fuse" in sys.argv[1:]:
+        out = {"unit": "ms per keyframe (30 targets and the closing call)", "rows": {}}
+        fuse_rows(out)
         out["build_id"] = api.build_id()
         print(json.dumps(out, indent=1))
         return
