@@ -788,6 +788,57 @@ int orbfe_enqueue_fuse_sim3(orbfe_context *ctx, const orbfe_grid_keyframe *kf, c
         const float *d_pos, const float *d_normal, const float *d_max_distance, const float *d_min_distance, const uint8_t *d_pt_desc,
         const int32_t *d_pt_valid /* [n_pts] */, float th,
         int32_t *d_best_idx /* [n_pts] */, int32_t *d_n_fused /* [1] */, int32_t *d_status /* [1] */, void *stream);
+/* ---- the geometric matchers of LoopClosing::ComputeSim3 on device-resident keyframes (orbfe_sim3_device.hip, orbfe_match_device.hip).
+ * The contract of the enqueue matchers above holds: asynchronous on `stream` (NULL: the context's stream), nothing waits for the GPU,
+ * nothing is copied from host memory on the stream, no image slot is read and no vocabulary is needed.  The keyframes are the records of
+ * orbfe_enqueue_fuse, uploaded and bucketed once per keyframe; kf->u_right is never read.  Poses are HOST arrays read before the call
+ * returns; they travel as kernel arguments.
+ *
+ * ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (src/ORBmatcher.cc:1098-1322, src/LoopClosing.cc:359).  Arguments
+ * as orbfe_search_by_sim3: per keypoint SLOT of a keyframe its map point's position (3 floats), distance band, descriptor (32 bytes,
+ * 4-byte aligned) and valid = pMP && !isBad() && not already matched, all device arrays of kf->n entries; T1w, T2w (3x4), R12 (3x3) and
+ * t12 (3) are HOST arrays, sR12 / sR21 / t21 are formed on the host by orbfe_search_by_sim3's expression.  At most three launches: the
+ * reset of count and status, both directions in one kernel (one wave per keypoint slot), the agreement check of :1293-1308.
+ * Outputs (device), all written by every call and nothing else written: d_match12[kf1->n] (keypoint of KF2 or -1), d_n_found[1] (how
+ * many are >= 0), d_status[1].  kf1->n == 0 writes count 0 and status 0 and queues nothing else; with kf2->n == 0 every entry is -1 and
+ * no array of a record or of the map points is read.  Every result equals orbfe_search_by_sim3 on the same inputs.
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL context, record, pose or output; kf->n negative or > 65535; bounds of a
+ * record that are not ascending; and, when both keyframes have keypoints, a NULL map-point array or record pointer other than u_right.
+ * d_status = ORBFE_ERR_INVALID for what only the device can see, each checked before it is used as an address: a grid offset that is
+ * negative, descending or beyond n, a cell_idx entry outside [0, n), an octave outside [0, nlevels) on a keypoint of a walked cell (that
+ * cell / entry is skipped).  The other outputs of such a call are not meaningful.
+ * The two one-way results live in the context's grow-only matcher scratch: queue the calls of one context on one stream. */
+int orbfe_enqueue_search_by_sim3(orbfe_context *ctx,
+        const orbfe_grid_keyframe *kf1, const float *T1w, const float *d_pos1, const float *d_max_distance1,
+        const float *d_min_distance1, const uint8_t *d_pt_desc1, const int32_t *d_valid1,      /* one entry per keypoint slot of kf1 */
+        const orbfe_grid_keyframe *kf2, const float *T2w, const float *d_pos2, const float *d_max_distance2,
+        const float *d_min_distance2, const uint8_t *d_pt_desc2, const int32_t *d_valid2,
+        float s12, const float *R12, const float *t12, float th,
+        int32_t *d_match12 /* [kf1->n] */, int32_t *d_n_found /* [1] */, int32_t *d_status /* [1] */, void *stream);
+/* ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cc:285-398, src/LoopClosing.cc:411).  The point
+ * table, the index list and the per-query validity are those of orbfe_enqueue_fuse_sim3 -- one upload of mvpLoopMapPoints serves this
+ * call and SearchAndFuse's; d_pt_valid[q] = !isBad() && !spAlreadyFound.count(pMP).  Scw is a HOST 3x4 [sR | s t], decomposed on the host
+ * as orbfe_search_by_projection_sim3 does.  d_kf_matched[k] != 0: keypoint k holds a match on entry (vpMatched[k] != NULL); NULL: none.
+ * The points are taken in query order: a keypoint matched on entry, or taken by an earlier query of the call, is skipped; the smallest
+ * remaining (distance, GetFeaturesInArea order) is accepted at <= TH_LOW; no ratio and no rotation test.  Two launches: one wave per
+ * query keeps its four smallest admissible candidates, one workgroup replays the rule in order and scans a window again when its four
+ * are all taken, so the result is exact for any number of candidates per window.
+ * Outputs (device), all written by every call and nothing else written: d_pt_match[n_pts] (keypoint of kf or -1 = the synchronous
+ * call's pt_match), d_kf_match[kf->n] (the query that took keypoint k, or -1: what the reference writes into vpMatched; a keypoint is
+ * taken at most once, so the two are exact inverses), d_nmatches[1] (counts either), d_status[1].  With kf->n == 0 every query gets -1
+ * and no array of the record or of the table is read.
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: as orbfe_enqueue_fuse (a NULL d_kf_match is a NULL output); ORBFE_ERR_CAPACITY:
+ * n_pts > 2^20.  d_status = ORBFE_ERR_INVALID for what only the device can see, each checked before it is used as an address, in the
+ * first pass and in the rescan: a d_pt_index entry outside [0, n_rows) (that query gets -1), a grid offset that is negative, descending
+ * or beyond n, a cell_idx entry outside [0, n), an octave outside [0, nlevels) on a keypoint of a walked cell (that cell / entry is
+ * skipped).  The other outputs of such a call are not meaningful.
+ * The call uses the context's grow-only query scratch: queue the calls of one context on one stream. */
+int orbfe_enqueue_search_by_projection_sim3(orbfe_context *ctx, const orbfe_grid_keyframe *kf, const float *Scw,
+        int n_pts, const int32_t *d_pt_index /* [n_pts] or NULL */, int n_rows,
+        const float *d_pos, const float *d_normal, const float *d_max_distance, const float *d_min_distance, const uint8_t *d_pt_desc,
+        const int32_t *d_pt_valid /* [n_pts] */, const uint8_t *d_kf_matched /* [kf->n] or NULL: none */, float th,
+        int32_t *d_pt_match /* [n_pts]: keypoint of kf or -1 */, int32_t *d_kf_match /* [kf->n]: the query that took keypoint k, or -1 */,
+        int32_t *d_nmatches /* [1] */, int32_t *d_status /* [1] */, void *stream);
 /* KeyFrameDatabase::DetectLoopCandidates(KeyFrame *pKF, float minScore) (src/KeyFrameDatabase.cc:73-194; LoopClosing::DetectLoop,
  * src/LoopClosing.cc:131).  connected[k] != 0 marks the keyframes of pKF->GetConnectedKeyFrames() (may be NULL: none); covisibility
  * lists as for the relocalisation query.  Stateless: mLoopScore is only read for keyframes scored by the same call. */

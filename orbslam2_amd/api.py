@@ -41,6 +41,7 @@ EXPORTS = [
     "orbfe_enqueue_search_by_projection_kf", "orbfe_enqueue_search_by_projection_kf_batch",
     "orbfe_enqueue_search_for_triangulation",
     "orbfe_enqueue_keyframe_grid", "orbfe_enqueue_fuse", "orbfe_enqueue_fuse_sim3",
+    "orbfe_enqueue_search_by_sim3", "orbfe_enqueue_search_by_projection_sim3",
 ]
 NUM_STAGES = 8
 STAGE_NAMES = ["ingest", "pyramid", "blur", "fast", "octree", "describe", "stereo_match", "stereo_median"]  # orbfe_stage_name()
@@ -84,7 +85,7 @@ assert C.sizeof(TriKeyframe) == 64
 
 
 class GridKeyframe(C.Structure):
-    """orbfe_grid_keyframe (include/orbfe.h): the keyframe of enqueue_fuse / enqueue_fuse_sim3, device pointers; cell_off / cell_idx as
+    """orbfe_grid_keyframe (include/orbfe.h): the keyframe of enqueue_fuse / enqueue_fuse_sim3 and the Sim3 matchers, device pointers; cell_off / cell_idx as
     enqueue_keyframe_grid wrote them, the bounds the frame's floats."""
     _fields_ = [("keys_un", C.c_void_p), ("u_right", C.c_void_p), ("desc", C.c_void_p), ("cell_off", C.c_void_p), ("cell_idx", C.c_void_p),
                 ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float), ("n", C.c_int32), ("keyframe", C.c_int32)]
@@ -255,6 +256,10 @@ def load():
     for fn in (L.orbfe_enqueue_fuse, L.orbfe_enqueue_fuse_sim3):
         fn.restype = C.c_int
         fn.argtypes = [vp, C.POINTER(GridKeyframe), vp, C.c_int, vp, C.c_int] + [vp] * 6 + [C.c_float] + [vp] * 4
+    L.orbfe_enqueue_search_by_sim3.restype = C.c_int
+    L.orbfe_enqueue_search_by_sim3.argtypes = [vp] + [C.POINTER(GridKeyframe)] + [vp] * 6 + [C.POINTER(GridKeyframe)] + [vp] * 6 + [C.c_float, vp, vp, C.c_float] + [vp] * 4
+    L.orbfe_enqueue_search_by_projection_sim3.restype = C.c_int
+    L.orbfe_enqueue_search_by_projection_sim3.argtypes = [vp, C.POINTER(GridKeyframe), vp, C.c_int, vp, C.c_int] + [vp] * 7 + [C.c_float] + [vp] * 5
     _lib = L
     return L
 
@@ -718,6 +723,33 @@ class Context:
         """The same for ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) of LoopClosing::SearchAndFuse: Scw = [sR | s t] (3x4, host)."""
         self._enqueue_fuse(self.L.orbfe_enqueue_fuse_sim3, kf, Scw, n_pts, d_pt_index, n_rows, d_pos, d_normal, d_max_distance, d_min_distance,
                            d_pt_desc, d_pt_valid, th, d_best_idx, d_n_fused, d_status, stream)
+
+    def enqueue_search_by_sim3(self, kf1, T1w, d_pts1, kf2, T2w, d_pts2, s12, R12, t12, th, d_match12, d_n_found, d_status, stream=0):
+        """ORBmatcher::SearchBySim3 on two device-resident keyframes (GridKeyframe records on the host, device pointers inside),
+        asynchronous on `stream`.  d_pts = (d_pos, d_max_distance, d_min_distance, d_pt_desc, d_valid), one entry per keypoint slot, as
+        search_by_sim3's pts.  T1w, T2w (3x4), R12 (3x3) and t12 (3) are host arrays read before the call returns.  d_match12 holds
+        kf1.n entries.  The one-way results live in the context's scratch: queue the calls of one context on one stream."""
+        v = C.c_void_p
+        t1 = np.ascontiguousarray(T1w, np.float32); t2 = np.ascontiguousarray(T2w, np.float32)
+        R = np.ascontiguousarray(R12, np.float32); t = np.ascontiguousarray(t12, np.float32)
+        assert t1.size >= 12 and t2.size >= 12 and R.size == 9 and t.size == 3 and len(d_pts1) == 5 and len(d_pts2) == 5
+        self._check(self.L.orbfe_enqueue_search_by_sim3(self.h, C.byref(kf1), _p(t1), *[v(x or None) for x in d_pts1], C.byref(kf2), _p(t2),
+                                                        *[v(x or None) for x in d_pts2], float(s12), _p(R), _p(t), th, v(d_match12 or None),
+                                                        v(d_n_found or None), v(d_status or None), v(stream or None)))
+
+    def enqueue_search_by_projection_sim3(self, kf, Scw, n_pts, d_pt_index, n_rows, d_pos, d_normal, d_max_distance, d_min_distance, d_pt_desc,
+                                          d_pt_valid, d_kf_matched, th, d_pt_match, d_kf_match, d_nmatches, d_status, stream=0):
+        """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) of LoopClosing::ComputeSim3 on a device-resident keyframe,
+        asynchronous on `stream`.  The point table, the index list and the per-query validity are enqueue_fuse_sim3's; d_kf_matched
+        (uint8[kf.n], 0: none) marks the keypoints matched on entry.  d_pt_match[n_pts] and d_kf_match[kf.n] are exact inverses.  Uses
+        the context's query scratch: queue the calls of one context on one stream."""
+        v = C.c_void_p
+        t = np.ascontiguousarray(Scw, np.float32)
+        assert t.size >= 12
+        self._check(self.L.orbfe_enqueue_search_by_projection_sim3(
+            self.h, C.byref(kf), _p(t), n_pts, v(d_pt_index or None), n_rows, v(d_pos or None), v(d_normal or None), v(d_max_distance or None),
+            v(d_min_distance or None), v(d_pt_desc or None), v(d_pt_valid or None), v(d_kf_matched or None), th, v(d_pt_match or None),
+            v(d_kf_match or None), v(d_nmatches or None), v(d_status or None), v(stream or None)))
 
     def search_by_projection_kf(self, view, Tcw_cur, kf_pos, kf_desc, kf_valid, kf_angle, kf_max_distance, kf_min_distance, cur_has_point,
                                 th, orb_dist, check_ori):

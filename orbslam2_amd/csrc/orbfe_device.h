@@ -115,6 +115,10 @@ void orbfe_launch_rgbd(const DeviceConfig &cfg, const DeviceBuffers &buf, const 
 void orbfe_launch_undistort(const DeviceConfig &cfg, const void *d_keys_in, void *d_keys_out, int n, hipStream_t s);
 struct GridFrame; // orbfe_match_window.hpp
 void orbfe_launch_grid_build(const GridFrame &f, hipStream_t s); // Frame::AssignFeaturesToGrid into f.cell_off / f.cell_idx (orbfe_match_device.hip)
+struct orbfe_context;
+struct orbfe_grid_keyframe;
+// the GridFrame of a keyframe record, its count and bounds checked (orbfe_fuse_device.hip); ORBFE_ERR_INVALID through orbfe_fail
+int orbfe_grid_frame_of_record(orbfe_context *ctx, const orbfe_grid_keyframe *kf, GridFrame &f);
 void orbfe_launch_rgbd_u16(const DeviceConfig &cfg, const DeviceBuffers &buf, const uint16_t *d_depth, size_t depth_pitch_px,
                            float factor, int image, hipStream_t s);
 void orbfe_launch_rgbd_batch(const DeviceConfig &cfg, const DeviceBuffers &buf, const void *d_depth, bool is_u16, float factor, int n_images, hipStream_t s);

@@ -119,6 +119,15 @@ static int grid_frame_of(orbfe_context *ctx, const orbfe_keypoint *d_keys_un, in
     return ORBFE_OK;
 }
 
+// a keyframe record as the kernels read it (orbfe_match_device.hip and orbfe_sim3_device.hip build theirs here too)
+int orbfe_grid_frame_of_record(orbfe_context *ctx, const orbfe_grid_keyframe *kf, GridFrame &f)
+{
+    const int rc = grid_frame_of(ctx, kf->keys_un, kf->n, kf->min_x, kf->max_x, kf->min_y, kf->max_y, kf->keyframe, kf->cell_off, kf->cell_idx, f);
+    if (rc != ORBFE_OK) return rc;
+    f.desc = kf->desc; f.u_right = kf->u_right;
+    return ORBFE_OK;
+}
+
 extern "C" int orbfe_enqueue_keyframe_grid(orbfe_context *ctx, const orbfe_keypoint *d_keys_un, int n, const float *bounds, int32_t *d_cell_off,
                                            int32_t *d_cell_idx, void *stream)
 try {
@@ -142,14 +151,13 @@ static int enqueue_fuse(orbfe_context *ctx, int sim3, const orbfe_grid_keyframe 
     if (n_pts < 0 || n_rows < 0) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "negative count");
     if (!d_pt_index && n_rows < n_pts) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "%d queries without an index list over a table of %d rows", n_pts, n_rows);
     FuseArgs a;
-    int rc = grid_frame_of(ctx, kf->keys_un, kf->n, kf->min_x, kf->max_x, kf->min_y, kf->max_y, kf->keyframe, kf->cell_off, kf->cell_idx, a.f);
+    int rc = orbfe_grid_frame_of_record(ctx, kf, a.f);
     if (rc != ORBFE_OK) return rc;
     if (n_pts > 0 && kf->n > 0 &&
         (!d_pos || !d_normal || !d_max_distance || !d_min_distance || !d_pt_desc || !d_pt_valid || !kf->keys_un || !kf->desc || !kf->cell_off || !kf->cell_idx))
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null array in the point table or in the keyframe record");
     const orbfe_params *P = orbfe_ctx_params(ctx);
     if (P->nlevels < 1 || P->nlevels > ORBFE_MAX_LEVELS) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "nlevels = %d", P->nlevels);
-    a.f.desc = kf->desc; a.f.u_right = kf->u_right;
     a.C = orbfe_resolve::camera_of(P);
     const float *sf = orbfe_ctx_scale_factors(ctx);
     for (int l = 0; l < ORBFE_MAX_LEVELS; l++) a.sf[l] = l < P->nlevels ? sf[l] : 1.f;

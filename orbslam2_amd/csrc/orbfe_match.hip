@@ -673,24 +673,16 @@ static int sim3_one_way(orbfe_context *ctx, const float *Taw, const float *sRt, 
     const orbfe_params *P = orbfe_ctx_params(ctx);
     const float *sf = orbfe_ctx_scale_factors(ctx);
     const float log_sf = logf((float)(double)P->scale_factor);
+    const orbfe_resolve::Camera cam = orbfe_resolve::camera_of(P);
     std::vector<MatchQuery> q(n);
     std::vector<uint8_t> qd((size_t)32 * (n > 0 ? n : 1));
     for (int i = 0; i < n; i++) {
         MatchQuery &Q = q[i];
         Q = MatchQuery{0, 0, 0, 0, -1, 0, 0, 0};
-        if (!valid[i]) continue;
-        float pa[3], pb[3];
-        rt_apply(Taw, pos + 3 * i, pa);
-        rt_apply(sRt, pa, pb);
-        if ((double)pb[2] < 0.0) continue;
-        const float invz = (float)(1.0 / (double)pb[2]);
-        const float x = pb[0] * invz, y = pb[1] * invz;
-        const float u = P->fx * x + P->cx, v = P->fy * y + P->cy;
-        if (!kf_is_in_image(kfb, u, v)) continue;
-        const float dist = (float)sqrt((double)pb[0] * pb[0] + (double)pb[1] * pb[1] + (double)pb[2] * pb[2]);
-        if (dist < 0.8f * min_distance[i] || dist > 1.2f * max_distance[i]) continue;
-        const int lvl = predict_scale(max_distance[i], dist, log_sf, P->nlevels);
-        Q.u = u; Q.v = v; Q.r = th * sf[lvl]; Q.min_level = lvl - 1; Q.max_level = lvl; Q.flags = 1;
+        // one text with the kernel of orbfe_enqueue_search_by_sim3 (orbfe_sim3_device.hip)
+        if (orbfe_resolve::query_sim3_point(cam, sf, P->nlevels, log_sf, kfb->min_x, kfb->max_x, kfb->min_y, kfb->max_y, kfb->keyframe, Taw, sRt, pos + 3 * i,
+                                            valid[i], max_distance[i], min_distance[i], th, Q) <= 0)
+            continue;
         memcpy(&qd[(size_t)32 * i], desc + (size_t)32 * i, 32);
     }
     int rc = run_window_queries(ctx, kfb, q, qd);
@@ -725,16 +717,8 @@ try {
     if (!T1w || !T2w || !R12 || !t12 || !n_found || (N1 > 0 && (!pos1 || !max_distance1 || !min_distance1 || !pt_desc1 || !valid1 || !match12)) ||
         (N2 > 0 && (!pos2 || !max_distance2 || !min_distance2 || !pt_desc2 || !valid2)))
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
-    // sR12 = s12 * R12; sR21 = (1.0 / s12) * R12.t(); t21 = -sR21 * t12 (:1116-1119)
     float A12[12], A21[12];
-    const float inv_s = (float)(1.0 / (double)s12);
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) { A12[4 * i + j] = R12[3 * i + j] * s12; A21[4 * i + j] = R12[3 * j + i] * inv_s; }
-    for (int i = 0; i < 3; i++) {
-        A12[4 * i + 3] = t12[i];
-        const float t0 = (A21[4 * i] * t12[0] + A21[4 * i + 1] * t12[1]) + A21[4 * i + 2] * t12[2];
-        A21[4 * i + 3] = -t0;
-    }
+    orbfe_resolve::sim3_pair(s12, R12, t12, A12, A21);
     std::vector<int32_t> m1, m2;
     rc = sim3_one_way(ctx, T1w, A21, kf2, N1, pos1, max_distance1, min_distance1, pt_desc1, valid1, th, m1);
     if (rc != ORBFE_OK) return rc;

@@ -16,6 +16,11 @@
 // relocalisation (src/Tracking.cc:1540-1580) through the same kernels: a grid row (window, gather) or a workgroup (resolve) per
 // candidate, whose arguments come from its orbfe_reloc_candidate record (KfBatch); kf_prepare_kernel builds sAlreadyFound and the
 // keypoints' has-point flags from cur_point first.
+// SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) of LoopClosing::ComputeSim3 (src/ORBmatcher.cc:285-398) runs through the window
+// and resolve kernels as well, against an orbfe_grid_keyframe record instead of an image slot (Sim3Source, Sim3Points): the keyframe
+// rule with the keypoints matched on entry as static blocks and TH_LOW as the bound.  Its grid and keypoints are the caller's uploads,
+// so it has instantiations of its own (CHECKED) in which both walks -- the top-4 pass and wave 0's rescan -- test offsets, indices and
+// octaves before they become addresses; the instantiations of the matchers above are what they were.
 // The grid cell, the window, its walk, the candidate key and the top-4 selection are orbfe_match_window.hpp, shared with
 // orbfe_match.hip; the smallest key is the reference loop's first minimum.  No candidate list is kept: a query whose four keys are
 // all taken recomputes its window.
@@ -41,6 +46,7 @@ using orbfe_resolve::key_idx;
 using orbfe_resolve::key_level;
 using orbfe_resolve::MatchQuery;
 using orbfe_resolve::TH_HIGH;
+using orbfe_resolve::TH_LOW;
 
 struct Projection {
     Camera C;
@@ -138,6 +144,56 @@ struct PointsSource { // SearchByProjection(F, vpMapPoints, th)
     }
 };
 
+struct ResolveArgs;
+// SearchByProjection(pKF, Scw, vpPoints, vpMatched, th): the point table of orbfe_enqueue_fuse_sim3 -- rows, optionally read through an
+// index list -- as both kernels of the matcher need it
+struct Sim3Points {
+    const int32_t *pt_index;
+    int n_rows;
+    const uint8_t *pt_desc;
+    int nlevels;
+    int32_t *pt_match; // [n_pts] the keypoint query q took, or -1
+    // the row of query q, tested before it addresses the table; -1: outside [0, n_rows)
+    __device__ __forceinline__ int row(int q) const
+    {
+        if (!pt_index) return q; // n_rows >= n_pts: the call checked it
+        const int r = pt_index[q];
+        return (r < 0 || r >= n_rows) ? -1 : r;
+    }
+    __device__ __forceinline__ const uint8_t *desc(int q) const // only followed for a query with a window, whose row is good
+    {
+        const int r = row(q);
+        return pt_desc + (size_t)(r < 0 ? 0 : r) * 32;
+    }
+    __device__ __forceinline__ void resolve(int, ResolveArgs &) const {}
+};
+struct Sim3Source {
+    Projection P; // with the keyframe's bounds
+    Sim3Points pts;
+    int keyframe, kf_n;
+    float T[12], ow[3]; // [R|t] of the decomposed Scw and the camera centre, both computed on the host
+    const float *pos, *normal, *max_distance, *min_distance;
+    const int32_t *pt_valid;
+    float th;
+    __device__ __forceinline__ const Sim3Source &row(int, WindowRow &) const { return *this; }
+    __device__ __forceinline__ const uint8_t *desc(int q) const { return pts.desc(q); }
+    __device__ __forceinline__ int nlevels() const { return P.nlevels; }
+    __device__ __forceinline__ MatchQuery query(int q) const
+    {
+        MatchQuery Q = {0, 0, 0, 0, -1, 0, 0, 0};
+        if (kf_n == 0) return Q; // a keyframe without keypoints has no window: neither its arrays nor the table's are read
+        const int row = pts.row(q);
+        if (row < 0) { Q.flags = Q_BAD; return Q; }
+        float ur; // not used by this matcher
+        const float p[3] = {pos[3 * (size_t)row], pos[3 * (size_t)row + 1], pos[3 * (size_t)row + 2]};
+        const float nr[3] = {normal[3 * (size_t)row], normal[3 * (size_t)row + 1], normal[3 * (size_t)row + 2]};
+        // exactly as sim3_projection_impl mode 0 (orbfe_match.hip) calls it
+        orbfe_resolve::query_fuse_point(P.C, P.sf, P.nlevels, P.log_sf, P.min_x, P.max_x, P.min_y, P.max_y, keyframe, T, ow, 0, p, nr, pt_valid[q],
+                                        max_distance[row], min_distance[row], th, Q, &ur);
+        return Q;
+    }
+};
+
 __global__ __launch_bounds__(256) void frustum_kernel(Projection P, const float *__restrict__ Tcw, int n, const float *__restrict__ pos,
                                                       const float *__restrict__ normal, const float *__restrict__ max_distance,
                                                       const float *__restrict__ min_distance, float viewing_cos_limit, orbfe_track_point *__restrict__ out)
@@ -158,7 +214,9 @@ __global__ __launch_bounds__(256) void frustum_kernel(Projection P, const float 
 // lane keeps the TOPK smallest admissible keys of its own cells in registers and the wave merges them: any window size, no staging.
 // n_static = how many keys passed the static filters, -1 for a Q_BAD query.  The threads below the frame's keypoint count also
 // reset cur_match (the launch covers the keypoint capacity).
-template <class Source>
+// CHECKED (a keyframe record): the query's descriptor is the source's to find, the walk is the checked one and a walk that failed
+// makes the query a Q_BAD one, which the resolve kernel reports.
+template <class Source, bool CHECKED = false>
 __global__ __launch_bounds__(256) void window_topk_kernel(GridFrame f, Source src0, WindowRow r)
 {
     const auto &src = src0.row(blockIdx.y, r); // the source and the arguments of this row
@@ -172,18 +230,23 @@ __global__ __launch_bounds__(256) void window_topk_kernel(GridFrame f, Source sr
     const Window w = query_window(f, Q);
     Top4 top;
     int passed = 0;
-    if (w.ncells > 0)
-        scan_window(f, Q, w, (const uint32_t *)(r.qdesc + (size_t)iq * 32), lane, [&](unsigned long long key, int idx) {
-            if (key_dist(key) >= 256 || (r.blocked0 && r.blocked0[idx])) return; // static filters
-            passed++;
-            top.insert(key);
-        });
+    bool ok = true;
+    const auto emit = [&](unsigned long long key, int idx) {
+        if (key_dist(key) >= 256 || (r.blocked0 && r.blocked0[idx])) return; // static filters
+        passed++;
+        top.insert(key);
+    };
+    if (w.ncells > 0) {
+        if constexpr (CHECKED) ok = scan_window<true>(f, Q, w, (const uint32_t *)src.desc(iq), lane, emit, f.cap, src.nlevels());
+        else scan_window(f, Q, w, (const uint32_t *)(r.qdesc + (size_t)iq * 32), lane, emit);
+    }
+    if constexpr (CHECKED) ok = __all(ok) != 0;
     passed = wave_sum_i32(passed);
     for (int k = 0; k < TOPK; k++) {
         const unsigned long long m = top.pop_wave_min();
         if (lane == 0) r.topk[(size_t)iq * TOPK + k] = m;
     }
-    if (lane == 0) r.n_static[iq] = (Q.flags & Q_BAD) ? -1 : passed;
+    if (lane == 0) r.n_static[iq] = ((Q.flags & Q_BAD) || !ok) ? -1 : passed;
 }
 
 // ---- resolve ----
@@ -257,7 +320,9 @@ struct OneRow { // the three matchers of one row: the launch's arguments are the
     __device__ __forceinline__ void resolve(int, ResolveArgs &) const {}
     __device__ __forceinline__ void gather(int, GatherRow &) const {}
 };
-template <class Rows>
+// CHECKED (Rows = Sim3Points, a keyframe record): wave 0's rescan is the checked walk, a query's descriptor is the table row its index
+// names, and every query's event is also stored per query (rows.pt_match).
+template <class Rows, bool CHECKED = false>
 __global__ __launch_bounds__(RESOLVE_THREADS) void resolve_kernel(ResolveArgs a, Rows rows)
 {
     rows.resolve(blockIdx.x, a);
@@ -342,14 +407,19 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void resolve_kernel(ResolveArgs a,
                 const MatchQuery Q = a.q[gq];
                 const Window w = query_window(a.f, Q);
                 unsigned long long t0 = NO_KEY, t1 = NO_KEY;
-                if (w.ncells > 0)
-                    scan_window(a.f, Q, w, (const uint32_t *)(a.qdesc + (size_t)gq * 32), lane, [&](unsigned long long key, int idx) {
-                        if (key_dist(key) >= 256 || blk_test(s_blk, idx)) return; // s_blk holds the static blocks too
-                        if (key < t1) {
-                            t1 = key;
-                            if (t1 < t0) { const unsigned long long x = t0; t0 = t1; t1 = x; }
-                        }
-                    });
+                const auto emit = [&](unsigned long long key, int idx) {
+                    if (key_dist(key) >= 256 || blk_test(s_blk, idx)) return; // s_blk holds the static blocks too
+                    if (key < t1) {
+                        t1 = key;
+                        if (t1 < t0) { const unsigned long long x = t0; t0 = t1; t1 = x; }
+                    }
+                };
+                if (w.ncells > 0) {
+                    if constexpr (CHECKED) {
+                        const bool ok = scan_window<true>(a.f, Q, w, (const uint32_t *)rows.desc(gq), lane, emit, n, rows.nlevels);
+                        if (!__all(ok) && lane == 0) s_err = 1;
+                    } else scan_window(a.f, Q, w, (const uint32_t *)(a.qdesc + (size_t)gq * 32), lane, emit);
+                }
                 const unsigned long long fbest = wave_min_u64(t0);
                 const unsigned long long fsecond = wave_min_u64((fbest != NO_KEY && t0 == fbest) ? t1 : t0);
                 const bool facc = accept_rule(a.points, a.th_high, a.nnratio, pack_key(fbest), pack_key(fsecond));
@@ -366,6 +436,7 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void resolve_kernel(ResolveArgs a,
         for (int t = tid; t < cnt; t += RESOLVE_THREADS) {
             const int kp = s_ev[t];
             if (kp >= 0) atomicMax(&a.cur_match[kp], base + t);
+            if constexpr (CHECKED) rows.pt_match[base + t] = kp;
             if (a.check_ori) {
                 int e = -1;
                 if (kp >= 0) {
@@ -539,7 +610,7 @@ __global__ __launch_bounds__(1024) void kf_prepare_kernel(GridFrame f, KfBatch b
 // host
 // ---------------------------------------------------------------------------------------------
 struct orbfe_match_device_state {
-    DevBuf q, topk, n_static, ev, cells, keys_un, found, held, err; // grow-only scratch; calls of one context share it, so they are queued in stream order
+    DevBuf q, topk, n_static, ev, cells, keys_un, found, held, err, sim3; // grow-only scratch; calls of one context share it, so they are queued in stream order
     std::vector<unsigned> un_epoch;               // per image slot: the extraction call whose keypoints keys_un holds undistorted
     int un_ndist = 0;                             // ... with these coefficients (orbfe_set_distortion may change them between calls)
     float un_dist[5] = {0, 0, 0, 0, 0};
@@ -558,6 +629,14 @@ orbfe_match_device_state *orbfe_ctx_match_device_state(orbfe_context *ctx)
     orbfe_match_device_state **slot = orbfe_match_device_slot(ms);
     if (!*slot) *slot = new (std::nothrow) orbfe_match_device_state();
     return *slot;
+}
+
+// the two one-way results of orbfe_enqueue_search_by_sim3 (orbfe_sim3_device.hip): n int32_t of the context's grow-only scratch
+int32_t *orbfe_ctx_sim3_scratch(orbfe_context *ctx, size_t n)
+{
+    orbfe_match_device_state *st = orbfe_ctx_match_device_state(ctx);
+    if (!st || st->sim3.ensure(sizeof(int32_t) * (n > 0 ? n : 1))) return nullptr;
+    return (int32_t *)st->sim3.p;
 }
 
 #define DTRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return orbfe_fail(ctx, ORBFE_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
@@ -801,6 +880,59 @@ try {
     if (n_cands == 0) return ORBFE_OK;
     return enqueue_kf(ctx, slot, bounds, d_cands, orbfe_reloc_candidate(), n_cands, max_n_kf, check_ori, exclude_held, d_cur_match, d_nmatches, d_status,
                       d_has_point, d_Xw, stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx));
+} ORBFE_CATCH(ctx)
+
+// ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th), src/ORBmatcher.cc:285-398, on a keyframe record: two launches
+extern "C" int orbfe_enqueue_search_by_projection_sim3(orbfe_context *ctx, const orbfe_grid_keyframe *kf, const float *Scw, int n_pts, const int32_t *d_pt_index,
+                                                       int n_rows, const float *d_pos, const float *d_normal, const float *d_max_distance,
+                                                       const float *d_min_distance, const uint8_t *d_pt_desc, const int32_t *d_pt_valid,
+                                                       const uint8_t *d_kf_matched, float th, int32_t *d_pt_match, int32_t *d_kf_match, int32_t *d_nmatches,
+                                                       int32_t *d_status, void *stream)
+try {
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    ORBFE_ENTRY(ctx);
+    if (!kf || !Scw || !d_pt_match || !d_kf_match || !d_nmatches || !d_status) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
+    if (n_pts < 0 || n_rows < 0) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "negative count");
+    if (!d_pt_index && n_rows < n_pts) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "%d queries without an index list over a table of %d rows", n_pts, n_rows);
+    if (n_pts > (1 << 20)) return orbfe_fail(ctx, ORBFE_ERR_CAPACITY, "%d points: the matcher's scratch rows hold 2^20", n_pts);
+    GridFrame f;
+    int rc = orbfe_grid_frame_of_record(ctx, kf, f);
+    if (rc != ORBFE_OK) return rc;
+    f.u_right = nullptr; // this matcher has no mvuRight gate: kf->u_right is never read
+    if (n_pts > 0 && kf->n > 0 &&
+        (!d_pos || !d_normal || !d_max_distance || !d_min_distance || !d_pt_desc || !d_pt_valid || !kf->keys_un || !kf->desc || !kf->cell_off || !kf->cell_idx))
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null array in the point table or in the keyframe record");
+    const orbfe_params *P = orbfe_ctx_params(ctx);
+    if (P->nlevels < 1 || P->nlevels > ORBFE_MAX_LEVELS) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "nlevels = %d", P->nlevels);
+    orbfe_match_device_state *st = orbfe_ctx_match_device_state(ctx);
+    if (!st) return orbfe_fail(ctx, ORBFE_ERR_HIP, "out of host memory");
+    DTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    rc = ensure_query_scratch(ctx, st, n_pts);
+    if (rc != ORBFE_OK) return rc;
+    const float bounds[4] = {kf->min_x, kf->max_x, kf->min_y, kf->max_y};
+    Sim3Source src;
+    src.P = projection_of(ctx, bounds);
+    src.pts = {d_pt_index, n_rows, d_pt_desc, P->nlevels, d_pt_match};
+    src.keyframe = kf->keyframe != 0; src.kf_n = kf->n;
+    orbfe_resolve::sim3_to_rt(Scw, src.T);
+    orbfe_resolve::camera_center(src.T, src.ow);
+    src.pos = d_pos; src.normal = d_normal; src.max_distance = d_max_distance; src.min_distance = d_min_distance; src.pt_valid = d_pt_valid;
+    src.th = th;
+    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
+    // one wave per query, and a thread per keypoint for the reset of d_kf_match; neither: the resolve kernel alone writes count and status
+    const int blocks = std::max((n_pts + 3) / 4, (f.cap + 255) / 256);
+    const WindowRow w = {(MatchQuery *)st->q.p, nullptr, n_pts, d_kf_matched, (unsigned long long *)st->topk.p, (int *)st->n_static.p, d_kf_match};
+    if (blocks > 0) hipLaunchKernelGGL((window_topk_kernel<Sim3Source, true>), dim3(blocks), dim3(256), 0, s, f, src, w);
+    ResolveArgs a = {};
+    a.f = f; a.q = (const MatchQuery *)st->q.p; a.nq = n_pts;
+    a.topk = (const unsigned long long *)st->topk.p; a.n_static = (const int *)st->n_static.p;
+    a.blocked0 = d_kf_matched; // obs stays null: every accepted keypoint is closed (vpMatched[bestIdx] = pMP, :390)
+    a.th_high = TH_LOW;        // no ratio, no rotation test
+    a.ev = (int32_t *)st->ev.p;
+    a.cur_match = d_kf_match; a.nmatches = d_nmatches; a.status = d_status;
+    hipLaunchKernelGGL((resolve_kernel<Sim3Points, true>), dim3(1), dim3(RESOLVE_THREADS), 0, s, a, src.pts);
+    DTRY(ctx, hipGetLastError());
+    return ORBFE_OK;
 } ORBFE_CATCH(ctx)
 
 extern "C" int orbfe_device_keys_un(orbfe_context *ctx, int slot, const orbfe_keypoint **d_keys_un, void *stream)

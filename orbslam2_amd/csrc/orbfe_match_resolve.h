@@ -256,6 +256,40 @@ ORBFE_RESOLVE_HD static inline int query_fuse_point(const Camera &C, const float
     *ur = u - C.bf * invz;
     return 1;
 }
+// One direction of ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1143-1216 / 1218-1291): the loop body for one map point of keyframe A
+// up to GetFeaturesInArea on keyframe B.  Taw moves the point into camera A, sRt = [sR|t] from there into camera B; the bounds and
+// `keyframe` are B's.  valid = pMP && !pMP->isBad() && not already matched.  Q must hold NO_QUERY; returns 1 when the point opens a window.
+ORBFE_RESOLVE_HD static inline int query_sim3_point(const Camera &C, const float *sf, int nlevels, float log_sf, float min_x, float max_x, float min_y,
+                                                    float max_y, int keyframe, const float *Taw, const float *sRt, const float *pos, int valid,
+                                                    float max_distance, float min_distance, float th, MatchQuery &Q)
+{
+    if (!valid) return 0;
+    float pa[3], pb[3];
+    rt_apply(Taw, pos, pa);
+    rt_apply(sRt, pa, pb);
+    if ((double)pb[2] < 0.0) return 0;
+    const float invz = (float)(1.0 / (double)pb[2]);
+    const float x = pb[0] * invz, y = pb[1] * invz;
+    const float u = C.fx * x + C.cx, v = C.fy * y + C.cy;
+    if (!kf_is_in_image(min_x, max_x, min_y, max_y, keyframe, u, v)) return 0;
+    const float dist = norm3(pb);
+    if (dist < 0.8f * min_distance || dist > 1.2f * max_distance) return 0;
+    const int lvl = predict_scale(max_distance, dist, log_sf, nlevels);
+    Q.u = u; Q.v = v; Q.r = th * sf[lvl]; Q.min_level = lvl - 1; Q.max_level = lvl; Q.flags = 1;
+    return 1;
+}
+// sR12 = s12 * R12; sR21 = (1.0 / s12) * R12.t(); t21 = -sR21 * t12 (src/ORBmatcher.cc:1116-1119) as two [sR|t] rows of 4
+static inline void sim3_pair(float s12, const float *R12, const float *t12, float *A12, float *A21)
+{
+    const float inv_s = (float)(1.0 / (double)s12);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) { A12[4 * i + j] = R12[3 * i + j] * s12; A21[4 * i + j] = R12[3 * j + i] * inv_s; }
+    for (int i = 0; i < 3; i++) {
+        A12[4 * i + 3] = t12[i];
+        const float t0 = (A21[4 * i] * t12[0] + A21[4 * i + 1] * t12[1]) + A21[4 * i + 2] * t12[2];
+        A21[4 * i + 3] = -t0;
+    }
+}
 // The chi-square gates of Fuse on one candidate keypoint (src/ORBmatcher.cc:905-930): reprojection error in stereo where the keypoint
 // has a right coordinate (kur >= 0; pass -1 for a keyframe without mvuRight), else monocular; sf_lv = mvScaleFactors[kpLevel]
 ORBFE_RESOLVE_HD static inline bool fuse_chi2_passes(float u, float v, float ur, float kx, float ky, float kur, float sf_lv)

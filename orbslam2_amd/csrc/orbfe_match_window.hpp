@@ -123,14 +123,15 @@ __device__ __forceinline__ unsigned long long candidate_key(const GridFrame &f, 
     return ((unsigned long long)dist << 36) | ((unsigned long long)ix << 30) | ((unsigned long long)iy << 24) | ((unsigned long long)idx << 8) |
            (unsigned long long)(kp.octave & 255);
 }
-// emit(key, idx) for every hit of the lane
-template <class Emit>
-__device__ __forceinline__ void scan_window(const GridFrame &f, const orbfe_resolve::MatchQuery &Q, const Window &w, const uint32_t *__restrict__ qdesc, int lane, Emit emit)
+// emit(key, idx) for every hit of the lane; CHECKED, n and nlevels as for_each_hit, whose verdict is returned
+template <bool CHECKED = false, class Emit>
+__device__ __forceinline__ bool scan_window(const GridFrame &f, const orbfe_resolve::MatchQuery &Q, const Window &w, const uint32_t *__restrict__ qdesc, int lane, Emit emit,
+                                            int n = 0, int nlevels = 0)
 {
     uint32_t qd[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) qd[k] = qdesc[k];
-    for_each_hit(f, Q, w, lane, [&](int ix, int iy, int idx, const KeyPointPOD &kp) { emit(candidate_key(f, Q, qd, ix, iy, idx, kp), idx); });
+    return for_each_hit<CHECKED>(f, Q, w, lane, [&](int ix, int iy, int idx, const KeyPointPOD &kp) { emit(candidate_key(f, Q, qd, ix, iy, idx, kp), idx); }, n, nlevels);
 }
 
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long w)

@@ -46,6 +46,18 @@ call's arrays gathered outside the timed window; (b) -- when the library has it 
 the count into pinned memory + stream synchronise), the validity patch queued on the stream, grids and table uploaded outside the
 timed window; (c) the 31 enqueues queued back to back as GPU time between two events.  (a) and (b) are checked against the oracle run
 with the same patches.  Five repeats of each, interleaved; every repeat is the mean of 10 loops, its slowest loop beside it.
+    python3 tools/bench_matchers.py --sim3 [--lib path/to/another/liborbfe.so]
+runs only the ComputeSim3 rows (profiles/sim3_device.json): one current keyframe of 1500 keypoints (one map point each) against three
+candidate keyframes of about 1700 (the camera scene of tests/matcher_census.py seen from three poses), five SearchBySim3 calls per
+candidate (th 7.5, the Sim3 of every RANSAC round a little different), then one SearchByProjection(pKF, Scw, ...) of a 15 000-row
+loop-point table (ten keyframes' worth of DISTINCT map points, as mvpLoopMapPoints is deduplicated: the 1500 the current keyframe
+observes and 13 500 others in the same volume, shuffled) against the current keyframe, th 10, the keypoints the first candidate
+matched closed on entry.  (a) the 15 + 1 synchronous calls; (b) -- when the library has them -- 15 x
+(orbfe_enqueue_search_by_sim3 + download of match12, count and status into pinned memory + stream synchronise: Sim3Solver runs on the
+host) and the same for orbfe_enqueue_search_by_projection_sim3, keyframes, grids and tables uploaded outside the timed window; (c) the
+16 enqueues queued back to back as GPU time between two events, and the SearchByProjection enqueue alone.  (a) and (b) are checked
+against the oracle.  Five repeats of each,
+interleaved; every repeat is the mean of 10 loops, its slowest loop beside it.
 """
 import json
 import os
@@ -836,6 +848,147 @@ def fuse_rows(out):
     ctx.close()
 
 
+def sim3_rows(out):
+    """Rows of --sim3; arguments prepared once."""
+    import gc
+    import torch
+    from orbslam2_amd import api
+    from tests import matcher_census as MC
+    dev = torch.device("cuda:0")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
+    K, ROUNDS, N_PTS, N_KFS, TH, TH_PROJ, REPS, REPEATS = 3, 5, 1500, 10, 7.5, 10.0, 10, 5
+    ctx = api.Context(width=MC.W, height=MC.H, fx=MC.FX, fy=MC.FY, cx=MC.CX, cy=MC.CY, bf=MC.BF)
+    have = hasattr(ctx.L, "orbfe_enqueue_search_by_sim3") and hasattr(ctx.L, "orbfe_enqueue_search_by_projection_sim3")
+    rng = np.random.default_rng(78)
+    poses = [TM._se3(2.0, [0.02, -0.01, -0.3]), TM._se3(1.0, [0.25, 0.0, 0.03]), TM._se3(-1.5, [-0.1, 0.05, -0.2])]
+    cands = [MC._camera_scene(402, T, n_pts=N_PTS, n_distract=500) for T in poses]
+    cur = cands[0]  # the current keyframe: k1 / d1 / pts1 of the first scene, the same map points in all three
+    assert all(np.array_equal(c["pos"], cur["pos"]) and np.array_equal(c["desc"], cur["desc"]) for c in cands)
+    cands = [dict(c, k1=cur["k1"], d1=cur["d1"], pts1=cur["pts1"]) for c in cands]
+    sims = [[(np.float32(1.02 + 0.002 * r), c["R12"], (c["t12"] + np.float32(0.001 * r)).astype(np.float32)) for r in range(ROUNDS)] for c in cands]
+    refs = [[MC.oracle_run("by_sim3", dict(c, s12=s12, R12=R12, t12=t12), (TH,)) for s12, R12, t12 in sims[k]] for k, c in enumerate(cands)]
+    # the loop-point table: N_KFS keyframes' worth of distinct map points (mvpLoopMapPoints holds every point once, src/LoopClosing.cc:401):
+    # the current keyframe's own and (N_KFS - 1) * N_PTS others in the same volume, shuffled, searched in the current keyframe
+    other = MC._points_of(MC._map_points(rng, (N_KFS - 1) * N_PTS, cur["T_cur"], cur["sf"]), rng, 0.45)
+    perm = rng.permutation(N_KFS * N_PTS)
+    both = lambda f: np.concatenate([cur[f], other[f]])[perm]
+    src = perm  # one row per loop point
+    Scw = cur["T_last"].copy(); Scw *= np.float32(1.07)
+    loop = dict(cur, k=cur["k1"], d=cur["d1"], Scw=Scw, pos=both("pos"), normal=both("normal"), max_d=both("max_d"), min_d=both("min_d"), desc=both("desc"),
+                valid=(rng.random(len(src)) < 0.85).astype(np.int32), kf_matched=(refs[0][ROUNDS - 1][0] >= 0).astype(np.uint8))
+    ref_p = MC.oracle_run("sim3_projection", loop, (TH_PROJ,))
+    out["scene"] = ("current keyframe of %d keypoints against %d candidates of %d .. %d, %d SearchBySim3 calls each, th %g, matched per call %d .. %d; "
+                    "SearchByProjection of %d distinct loop points (%d keyframes' worth) against the current keyframe, th %g, %d keypoints matched on entry, %d matched") % (
+        len(cur["k1"]), K, min(len(c["k"]) for c in cands), max(len(c["k"]) for c in cands), ROUNDS, TH, min(r[1] for rr in refs for r in rr),
+        max(r[1] for rr in refs for r in rr), len(src), N_KFS, TH_PROJ, int(loop["kf_matched"].sum()), ref_p[1])
+    view1 = ctx._view(cur["k1"], None, cur["d1"], cur["bounds"], keyframe=True)
+    views = [ctx._view(c["k"], None, c["d"], c["bounds"], keyframe=True) for c in cands]
+
+    def sync_loop(check=False):
+        for k, c in enumerate(cands):
+            for r, (s12, R12, t12) in enumerate(sims[k]):
+                got, ngot = ctx.search_by_sim3(view1, c["T_last"], c["pts1"], views[k], c["T_cur"], c["pts2"], s12, R12, t12, TH)
+                if check:
+                    assert ngot == refs[k][r][1] and np.array_equal(got, refs[k][r][0]), (k, r)
+        got, ngot = ctx.sim3_projection(0, view1, Scw, loop["pos"], loop["normal"], loop["max_d"], loop["min_d"], loop["desc"], loop["valid"],
+                                        loop["kf_matched"], TH_PROJ)
+        if check:
+            assert ngot == ref_p[1] and np.array_equal(got, ref_p[0])
+
+    sync_loop(check=True)
+    if have:
+        st = torch.cuda.Stream()
+        keep, recs = [], []
+        for k_, d_ in [(cur["k1"], cur["d1"])] + [(c["k"], c["d"]) for c in cands]:  # once per keyframe: arrays, grid, record
+            n = len(k_)
+            a = [up(k_), up(d_), torch.zeros(64 * 48 + 1, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)]
+            ctx.enqueue_keyframe_grid(a[0].data_ptr(), n, cur["bounds"], a[2].data_ptr(), a[3].data_ptr(), st.cuda_stream)
+            keep.append(a)
+            recs.append(api.GridKeyframe(a[0].data_ptr(), 0, a[1].data_ptr(), a[2].data_ptr(), a[3].data_ptr(), *[float(b) for b in cur["bounds"]], n, 1))
+        pts_of = lambda pts: [up(np.ascontiguousarray(x)) for x in pts]
+        d_pts1, d_pts2 = pts_of(cur["pts1"]), [pts_of(c["pts2"]) for c in cands]  # once per keyframe: its map points per keypoint slot
+        p1, p2 = [x.data_ptr() for x in d_pts1], [[x.data_ptr() for x in d] for d in d_pts2]
+        d_tab = [up(loop[f]) for f in ("pos", "normal", "max_d", "min_d", "desc")]  # mvpLoopMapPoints, once per loop (SearchAndFuse reads it too)
+        tp = [x.data_ptr() for x in d_tab]
+        d_valid, d_matched = up(loop["valid"]), up(loop["kf_matched"])
+        n1, nq = len(cur["k1"]), len(src)
+        d_res = torch.zeros(2 + nq, dtype=torch.int32, device=dev)  # count, status, match12 / pt_match: one download
+        d_kfm = torch.zeros(n1, dtype=torch.int32, device=dev)
+        h_res = torch.zeros(2 + nq, dtype=torch.int32).pin_memory()
+        res = h_res.numpy()
+        rp = d_res.data_ptr()
+        st.synchronize()
+
+        def enqueue(k, r):
+            if k < K:
+                s12, R12, t12 = sims[k][r]
+                ctx.enqueue_search_by_sim3(recs[0], cands[k]["T_last"], p1, recs[1 + k], cands[k]["T_cur"], p2[k], s12, R12, t12, TH, rp + 8, rp, rp + 4,
+                                           stream=st.cuda_stream)
+            else:
+                ctx.enqueue_search_by_projection_sim3(recs[0], Scw, nq, 0, nq, *tp, d_valid.data_ptr(), d_matched.data_ptr(), TH_PROJ, rp + 8,
+                                                      d_kfm.data_ptr(), rp, rp + 4, stream=st.cuda_stream)
+
+        calls = [(k, r) for k in range(K) for r in range(ROUNDS)] + [(K, 0)]
+
+        def device_loop(check=False):
+            with torch.cuda.stream(st):
+                for k, r in calls:
+                    enqueue(k, r)
+                    m = n1 if k < K else nq
+                    h_res[:2 + m].copy_(d_res[:2 + m], non_blocking=True)
+                    st.synchronize()  # Sim3Solver / OptimizeSim3 run on the host here
+                    if check:
+                        ref = refs[k][r] if k < K else ref_p
+                        assert res[1] == 0 and res[0] == ref[1] and np.array_equal(res[2:2 + m], ref[0]), (k, r)
+
+        device_loop(check=True)
+
+    def loops(fn):
+        fn()
+        gc.collect()
+        gc.disable()  # the cyclic collector is off inside the window, as in the standard timeit module
+        try:
+            t = []
+            for _ in range(REPS):
+                t0 = time.perf_counter()
+                fn()
+                t.append((time.perf_counter() - t0) * 1e3)
+        finally:
+            gc.enable()
+        return round(sum(t) / REPS, 4), round(max(t), 4)
+
+    a_rows, a_worst, b_wall, b_worst, c_gpu, c_proj = [], [], [], [], [], []
+    for _ in range(REPEATS):
+        m, w = loops(sync_loop)
+        a_rows.append(m); a_worst.append(w)
+        if have:
+            m, w = loops(device_loop)
+            b_wall.append(m); b_worst.append(w)
+            e0, e1, e2 = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            e0.record(st)
+            for _ in range(REPS):
+                for k, r in calls:
+                    enqueue(k, r)
+            e1.record(st)
+            for _ in range(REPS):
+                enqueue(K, 0)
+            e2.record(st)
+            st.synchronize()
+            c_gpu.append(round(e0.elapsed_time(e1) / REPS, 4)); c_proj.append(round(e1.elapsed_time(e2) / REPS, 4))
+    n_calls = K * ROUNDS
+    out["rows"]["(a) orbfe_search_by_sim3 x %d + orbfe_search_by_projection_sim3, synchronous, wall time" % n_calls] = {"ms_per_repeat": a_rows, "slowest_loop_ms": a_worst}
+    if have:
+        out["rows"]["(b) %d x (orbfe_enqueue_search_by_sim3 + download + synchronise) + the same for orbfe_enqueue_search_by_projection_sim3, wall time" % n_calls] = {
+            "ms_per_repeat": b_wall, "slowest_loop_ms": b_worst}
+        out["rows"]["(c) the %d enqueues alone, queued back to back, GPU time between two events" % (n_calls + 1)] = {"ms_per_repeat": c_gpu}
+        out["rows"]["(c') of which the orbfe_enqueue_search_by_projection_sim3 call, queued back to back on its own"] = {"ms_per_repeat": c_proj}
+        out["median (a) / median (b)"] = round(float(np.median(a_rows) / np.median(b_wall)), 2)
+        out["max (b) < min (a)"] = bool(max(b_wall) < min(a_rows))
+    else:
+        out["device"] = "not exported by this library"
+    ctx.close()
+
+
 def load_other_build(api, path):
     """api.load() on the library at `path`, which may be older than the package: the prototypes load() sets for entry points
     that build lacks land on stand-ins that are not kept, so hasattr(lib, name) is False afterwards and a call fails loudly."""
@@ -879,6 +1032,12 @@ def main():
     if "--fuse" in sys.argv[1:]:
         out = {"unit": "ms per keyframe (30 targets and the closing call)", "rows": {}}
         fuse_rows(out)
+        out["build_id"] = api.build_id()
+        print(json.dumps(out, indent=1))
+        return
+    if "--sim3" in sys.argv[1:]:
+        out = {"unit": "ms per ComputeSim3 (3 candidates x 5 SearchBySim3 and one SearchByProjection)", "rows": {}}
+        sim3_rows(out)
         out["build_id"] = api.build_id()
         print(json.dumps(out, indent=1))
         return
