@@ -28,14 +28,13 @@
 orbfe_bow_state *orbfe_bow_state_create() { return new (std::nothrow) orbfe_bow_state(); }
 void orbfe_bow_state_destroy(orbfe_bow_state *s) { delete s; }
 
-#define BTRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return orbfe_fail(ctx, ORBFE_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
 
 static int ensure_scratch(orbfe_context *ctx, orbfe_bow_state *st, size_t need)
 {
     if (need <= st->scratch_bytes) return ORBFE_OK;
     if (st->d_scratch) hipFree(st->d_scratch);
     st->d_scratch = nullptr; st->scratch_bytes = 0;
-    BTRY(ctx, hipMalloc(&st->d_scratch, need));
+    ORBFE_HIP_TRY(ctx, hipMalloc(&st->d_scratch, need));
     st->scratch_bytes = need;
     return ORBFE_OK;
 }
@@ -121,11 +120,11 @@ try {
             }
         }
     }
-    BTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     if (st->d_data) { hipFree(st->d_data); st->d_data = nullptr; }
     st->loaded = false;
-    BTRY(ctx, hipMalloc((void **)&st->d_data, p.total_size));
-    BTRY(ctx, hipMemcpy(st->d_data, data, p.total_size, hipMemcpyHostToDevice));
+    ORBFE_HIP_TRY(ctx, hipMalloc((void **)&st->d_data, p.total_size));
+    ORBFE_HIP_TRY(ctx, hipMemcpy(st->d_data, data, p.total_size, hipMemcpyHostToDevice));
     st->p = p;
     st->loaded = true;
     return ORBFE_OK;
@@ -151,23 +150,23 @@ try {
     if (!st || !st->loaded) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "no vocabulary loaded (orbfe_vocab_load)");
     if (n == 0) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "Vocabulary::transform No input data"); // fbow.cpp:52
     hipStream_t s = orbfe_ctx_stream(ctx);
-    BTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     int rc = ensure_scratch(ctx, st, (size_t)n * (32 + 12));
     if (rc != ORBFE_OK) return rc;
     uint8_t *d_desc = (uint8_t *)st->d_scratch;
     uint32_t *d_word = (uint32_t *)(d_desc + (size_t)32 * n);
     float *d_w = (float *)(d_word + n);
     uint32_t *d_node = (uint32_t *)(d_w + n);
-    BTRY(ctx, hipMemcpyAsync(d_desc, desc, (size_t)32 * n, hipMemcpyHostToDevice, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_desc, desc, (size_t)32 * n, hipMemcpyHostToDevice, s));
     const int nbits = (int)ceil(log2((double)st->p.m_k));
     hipLaunchKernelGGL(bow_descend_kernel, dim3((n + 255) / 256), dim3(256), 0, s, st->d_data, (unsigned)st->p.block_size_bytes_wp,
                        (unsigned)st->p.feature_off_start, (unsigned)st->p.child_off_start, (unsigned)st->p.desc_size_bytes_wp, nbits, level,
                        d_desc, n, d_word, d_w, d_node);
-    BTRY(ctx, hipMemcpyAsync(word_id, d_word, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    BTRY(ctx, hipMemcpyAsync(weight, d_w, sizeof(float) * n, hipMemcpyDeviceToHost, s));
-    BTRY(ctx, hipMemcpyAsync(node_id, d_node, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    BTRY(ctx, hipStreamSynchronize(s));
-    BTRY(ctx, hipGetLastError());
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(word_id, d_word, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(weight, d_w, sizeof(float) * n, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(node_id, d_node, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)
 
@@ -251,21 +250,21 @@ static int search_by_bow_impl(orbfe_context *ctx, bool kf_kf,
     std::vector<uint16_t> dist(np > 0 ? np : 1);
     if (np > 0) {
         hipStream_t s = orbfe_ctx_stream(ctx);
-        BTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+        ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
         const size_t need = (size_t)32 * n_kf + (size_t)32 * n_f + (size_t)np * (4 + 4 + 2) + 64;
         int rc = ensure_scratch(ctx, st, need);
         if (rc != ORBFE_OK) return rc;
         uint8_t *d_a = (uint8_t *)st->d_scratch, *d_b = d_a + (size_t)32 * n_kf;
         uint32_t *d_pa = (uint32_t *)(d_b + (size_t)32 * n_f), *d_pb = d_pa + np;
         uint16_t *d_dist = (uint16_t *)(d_pb + np);
-        BTRY(ctx, hipMemcpyAsync(d_a, kf_desc, (size_t)32 * n_kf, hipMemcpyHostToDevice, s));
-        BTRY(ctx, hipMemcpyAsync(d_b, f_desc, (size_t)32 * n_f, hipMemcpyHostToDevice, s));
-        BTRY(ctx, hipMemcpyAsync(d_pa, pa.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
-        BTRY(ctx, hipMemcpyAsync(d_pb, pb.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_a, kf_desc, (size_t)32 * n_kf, hipMemcpyHostToDevice, s));
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_b, f_desc, (size_t)32 * n_f, hipMemcpyHostToDevice, s));
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_pa, pa.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_pb, pb.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(pair_hamming_kernel, dim3((np + 255) / 256), dim3(256), 0, s, d_a, d_b, d_pa, d_pb, np, d_dist);
-        BTRY(ctx, hipMemcpyAsync(dist.data(), d_dist, sizeof(uint16_t) * np, hipMemcpyDeviceToHost, s));
-        BTRY(ctx, hipStreamSynchronize(s));
-        BTRY(ctx, hipGetLastError());
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(dist.data(), d_dist, sizeof(uint16_t) * np, hipMemcpyDeviceToHost, s));
+        ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
+        ORBFE_HIP_TRY(ctx, hipGetLastError());
     }
     // greedy resolve in the reference's order
     std::vector<int> hist[HISTO_LENGTH];
@@ -415,26 +414,26 @@ try {
     if (!st) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "out of host memory");
     for (int i = 1; i < n; i++)
         if (words[i] <= words[i - 1]) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "BoW words must be strictly ascending (std::map order)");
-    BTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     hipStream_t s = orbfe_ctx_stream(ctx);
     if (st->db_used + (size_t)n > st->db_cap) { // grow: twice the need, contents moved device to device
         const size_t cap = 2 * (st->db_used + (size_t)n) + 1024;
         uint32_t *nw = nullptr; float *nv = nullptr;
-        BTRY(ctx, hipMalloc((void **)&nw, cap * sizeof(uint32_t)));
+        ORBFE_HIP_TRY(ctx, hipMalloc((void **)&nw, cap * sizeof(uint32_t)));
         if (hipMalloc((void **)&nv, cap * sizeof(float)) != hipSuccess) { hipFree(nw); return orbfe_fail(ctx, ORBFE_ERR_HIP, "hipMalloc failed"); }
         if (st->db_used) {
             hipMemcpyAsync(nw, st->d_db_words, st->db_used * sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
             hipMemcpyAsync(nv, st->d_db_w, st->db_used * sizeof(float), hipMemcpyDeviceToDevice, s);
         }
-        BTRY(ctx, hipStreamSynchronize(s));
+        ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
         if (st->d_db_words) hipFree(st->d_db_words);
         if (st->d_db_w) hipFree(st->d_db_w);
         st->d_db_words = nw; st->d_db_w = nv; st->db_cap = cap;
     }
     if (n > 0) {
-        BTRY(ctx, hipMemcpyAsync(st->d_db_words + st->db_used, words, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
-        BTRY(ctx, hipMemcpyAsync(st->d_db_w + st->db_used, weights, sizeof(float) * n, hipMemcpyHostToDevice, s));
-        BTRY(ctx, hipStreamSynchronize(s));
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(st->d_db_words + st->db_used, words, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(st->d_db_w + st->db_used, weights, sizeof(float) * n, hipMemcpyHostToDevice, s));
+        ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
     }
     if (kf_index) *kf_index = (int)st->db_off.size();
     st->db_off.push_back((int)st->db_used); st->db_len.push_back(n); st->db_dead.push_back(0);
@@ -446,14 +445,14 @@ try {
 // Rare (once the dead words outnumber the live ones), so it goes through the host.
 static int kfdb_compact(orbfe_context *ctx, orbfe_bow_state *st)
 {
-    BTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     hipStream_t s = orbfe_ctx_stream(ctx);
     std::vector<uint32_t> w(st->db_used ? st->db_used : 1);
     std::vector<float> v(st->db_used ? st->db_used : 1);
     if (st->db_used) {
-        BTRY(ctx, hipMemcpyAsync(w.data(), st->d_db_words, st->db_used * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        BTRY(ctx, hipMemcpyAsync(v.data(), st->d_db_w, st->db_used * sizeof(float), hipMemcpyDeviceToHost, s));
-        BTRY(ctx, hipStreamSynchronize(s));
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(w.data(), st->d_db_words, st->db_used * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(v.data(), st->d_db_w, st->db_used * sizeof(float), hipMemcpyDeviceToHost, s));
+        ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
     }
     size_t o = 0;
     for (size_t k = 0; k < st->db_off.size(); k++) {
@@ -464,9 +463,9 @@ static int kfdb_compact(orbfe_context *ctx, orbfe_bow_state *st)
         o += len;
     }
     if (o) {
-        BTRY(ctx, hipMemcpyAsync(st->d_db_words, w.data(), o * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        BTRY(ctx, hipMemcpyAsync(st->d_db_w, v.data(), o * sizeof(float), hipMemcpyHostToDevice, s));
-        BTRY(ctx, hipStreamSynchronize(s));
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(st->d_db_words, w.data(), o * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(st->d_db_w, v.data(), o * sizeof(float), hipMemcpyHostToDevice, s));
+        ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
     }
     st->db_used = o;
     st->db_dead_words = 0;
@@ -511,7 +510,7 @@ static int kfdb_scores(orbfe_context *ctx, orbfe_bow_state *st, const uint32_t *
         if (!st->db_dead[k]) { live.push_back(k); l_off.push_back(st->db_off[k]); l_len.push_back(st->db_len[k]); }
     const int n_live = (int)live.size();
     if (n_live == 0) return ORBFE_OK;
-    BTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     hipStream_t s = orbfe_ctx_stream(ctx);
     const size_t need = (size_t)nq * 8 + (size_t)n_live * 20 + 64;
     int rc = ensure_scratch(ctx, st, need);
@@ -524,17 +523,17 @@ static int kfdb_scores(orbfe_context *ctx, orbfe_bow_state *st, const uint32_t *
     std::vector<int> l_common(n_live);
     std::vector<uint32_t> l_first(n_live);
     std::vector<float> l_score(n_live);
-    BTRY(ctx, hipMemcpyAsync(d_qw, q_words, sizeof(uint32_t) * nq, hipMemcpyHostToDevice, s));
-    BTRY(ctx, hipMemcpyAsync(d_qv, q_w, sizeof(float) * nq, hipMemcpyHostToDevice, s));
-    BTRY(ctx, hipMemcpyAsync(d_off, l_off.data(), sizeof(int) * n_live, hipMemcpyHostToDevice, s));
-    BTRY(ctx, hipMemcpyAsync(d_len, l_len.data(), sizeof(int) * n_live, hipMemcpyHostToDevice, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_qw, q_words, sizeof(uint32_t) * nq, hipMemcpyHostToDevice, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_qv, q_w, sizeof(float) * nq, hipMemcpyHostToDevice, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_off, l_off.data(), sizeof(int) * n_live, hipMemcpyHostToDevice, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_len, l_len.data(), sizeof(int) * n_live, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(kfdb_score_kernel, dim3((n_live + 3) / 4), dim3(256), 0, s, d_qw, d_qv, nq, d_off, d_len, st->d_db_words, st->d_db_w, n_live,
                        d_common, d_first, d_score);
-    BTRY(ctx, hipMemcpyAsync(l_common.data(), d_common, sizeof(int) * n_live, hipMemcpyDeviceToHost, s));
-    BTRY(ctx, hipMemcpyAsync(l_first.data(), d_first, sizeof(uint32_t) * n_live, hipMemcpyDeviceToHost, s));
-    BTRY(ctx, hipMemcpyAsync(l_score.data(), d_score, sizeof(float) * n_live, hipMemcpyDeviceToHost, s));
-    BTRY(ctx, hipStreamSynchronize(s));
-    BTRY(ctx, hipGetLastError());
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(l_common.data(), d_common, sizeof(int) * n_live, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(l_first.data(), d_first, sizeof(uint32_t) * n_live, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(l_score.data(), d_score, sizeof(float) * n_live, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
     for (int i = 0; i < n_live; i++) { common[live[i]] = l_common[i]; first[live[i]] = l_first[i]; score[live[i]] = l_score[i]; }
     return ORBFE_OK;
 }
@@ -733,21 +732,21 @@ try {
     std::vector<uint16_t> dist(np > 0 ? np : 1);
     if (np > 0) {
         hipStream_t s = orbfe_ctx_stream(ctx);
-        BTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+        ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
         const size_t need = (size_t)32 * n1 + (size_t)32 * n2 + (size_t)np * (4 + 4 + 2) + 64;
         int rc = ensure_scratch(ctx, st, need);
         if (rc != ORBFE_OK) return rc;
         uint8_t *d_a = (uint8_t *)st->d_scratch, *d_b = d_a + (size_t)32 * n1;
         uint32_t *d_pa = (uint32_t *)(d_b + (size_t)32 * n2), *d_pb = d_pa + np;
         uint16_t *d_dist = (uint16_t *)(d_pb + np);
-        BTRY(ctx, hipMemcpyAsync(d_a, desc1, (size_t)32 * n1, hipMemcpyHostToDevice, s));
-        BTRY(ctx, hipMemcpyAsync(d_b, desc2, (size_t)32 * n2, hipMemcpyHostToDevice, s));
-        BTRY(ctx, hipMemcpyAsync(d_pa, pa.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
-        BTRY(ctx, hipMemcpyAsync(d_pb, pb.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_a, desc1, (size_t)32 * n1, hipMemcpyHostToDevice, s));
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_b, desc2, (size_t)32 * n2, hipMemcpyHostToDevice, s));
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_pa, pa.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_pb, pb.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(pair_hamming_kernel, dim3((np + 255) / 256), dim3(256), 0, s, d_a, d_b, d_pa, d_pb, np, d_dist);
-        BTRY(ctx, hipMemcpyAsync(dist.data(), d_dist, sizeof(uint16_t) * np, hipMemcpyDeviceToHost, s));
-        BTRY(ctx, hipStreamSynchronize(s));
-        BTRY(ctx, hipGetLastError());
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(dist.data(), d_dist, sizeof(uint16_t) * np, hipMemcpyDeviceToHost, s));
+        ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
+        ORBFE_HIP_TRY(ctx, hipGetLastError());
     }
     // sequential resolve in the reference's order (vbMatched2 makes it order dependent)
     std::vector<uint8_t> matched2(n2 > 0 ? n2 : 1, 0);

@@ -47,7 +47,6 @@ using orbfe_resolve::TH_LOW;
 #define BOW_REG_CHUNKS 2   // a lane keeps the descriptors of its first two features of a node in registers (nodes up to 128 features)
 #define BOW_FLAG_CHUNKS 64 // a lane keeps the flags of its first 64 features of a node in one 64-bit register (nodes up to 4096 features)
 
-#define WTRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return orbfe_fail(ctx, ORBFE_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
 
 typedef unsigned long long u64;
 
@@ -225,7 +224,7 @@ try {
     const int cap = cfg->sel_total;
     if (cap <= 0 || cap > 65535) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "frames with more than 65535 keypoints are not supported");
     hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    WTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     if (st->resident.ensure((size_t)cap * 7 * sizeof(uint32_t))) return orbfe_fail(ctx, ORBFE_ERR_HIP, "BoW scratch allocation failed");
     const int rc = orbfe_ctx_order_after_extraction(ctx, s); // an event wait on the stream, no host wait
     if (rc != ORBFE_OK) return rc;
@@ -240,7 +239,7 @@ try {
     hipLaunchKernelGGL(bow_rank_kernel, dim3((cap + 63) / 64, 2), dim3(256), 0, s, (const uint32_t *)ids, (const float *)wt, sorted_id, sorted_pay, n_ptr, cap);
     hipLaunchKernelGGL(bow_segments_kernel, dim3(2), dim3(1024), 0, s, (const uint32_t *)sorted_id, (const uint32_t *)sorted_pay, n_ptr, cap, d_words, d_word_w,
                        d_n_words, d_nodes, d_node_off, d_node_feat, d_n_nodes);
-    WTRY(ctx, hipGetLastError());
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)
 
@@ -526,7 +525,7 @@ try {
     if (rc != ORBFE_OK) return rc;
     const int cap = a.cap;
     hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    WTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     rc = orbfe_ctx_order_after_extraction(ctx, s);
     if (rc != ORBFE_OK) return rc;
     a.kf_nodes = d_kf_nodes; a.kf_off = d_kf_off; a.kf_feat = d_kf_feat; a.kf_nnodes = kf_nnodes;
@@ -537,7 +536,7 @@ try {
     hipLaunchKernelGGL(bow_match_init_kernel, dim3((cap + 255) / 256), dim3(256), 0, s, a);
     if (kf_nnodes > 0) hipLaunchKernelGGL(bow_node_match_kernel, dim3((kf_nnodes + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(bow_match_tail_kernel, dim3(1), dim3(1024), 0, s, a);
-    WTRY(ctx, hipGetLastError());
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)
 
@@ -558,7 +557,7 @@ try {
     if (n_kfs == 0) return ORBFE_OK;
     const int cap = a.cap;
     hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    WTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     rc = orbfe_ctx_order_after_extraction(ctx, s);
     if (rc != ORBFE_OK) return rc;
     a.kf_nodes = nullptr; a.kf_off = a.kf_feat = a.kf_valid = nullptr; a.kf_desc = nullptr; a.kf_angle = a.kf_pos = nullptr; // per record, on the device
@@ -569,7 +568,7 @@ try {
     hipLaunchKernelGGL(bow_match_init_batch_kernel, dim3((cap + 255) / 256, n_kfs), dim3(256), 0, s, a, d_kfs, max_kf_nnodes);
     if (max_kf_nnodes > 0) hipLaunchKernelGGL(bow_node_match_batch_kernel, dim3((max_kf_nnodes + 3) / 4, n_kfs), dim3(256), 0, s, a, d_kfs, max_kf_nnodes);
     hipLaunchKernelGGL(bow_match_tail_batch_kernel, dim3(n_kfs), dim3(1024), 0, s, a, d_kfs, max_kf_nnodes);
-    WTRY(ctx, hipGetLastError());
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)
 
@@ -817,7 +816,7 @@ try {
     const int nlevels = orbfe_ctx_params(ctx)->nlevels;
     if (nlevels < 1 || nlevels > ORBFE_MAX_LEVELS) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "nlevels = %d", nlevels);
     hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    WTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     if (st->resident.ensure((size_t)(kf2->n > 64 ? kf2->n : 64))) return orbfe_fail(ctx, ORBFE_ERR_HIP, "BoW scratch allocation failed");
     TriSearch a;
     a.k1 = *kf1; a.k2 = *kf2; // a record without nodes may hold NULL arrays: the tail follows keys_un only through a match
@@ -835,6 +834,6 @@ try {
     hipLaunchKernelGGL(tri_init_kernel, dim3(cells > 0 ? (cells + 255) / 256 : 1), dim3(256), 0, s, a);
     if (a.k1.nnodes > 0 && a.k2.nnodes > 0) hipLaunchKernelGGL(tri_node_match_kernel, dim3((a.k1.nnodes + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(tri_tail_kernel, dim3(1), dim3(1024), 0, s, a);
-    WTRY(ctx, hipGetLastError());
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)

@@ -7,44 +7,40 @@
 // there every point is projected on the host, the keyframe is uploaded and bucketed per call, the candidate list of every window
 // comes back over the link and the host applies the chi-square gates and takes the minimum.  Fuse has no greedy state -- the points
 // do not interact, the map mutation stays with the caller -- so here the whole search is ONE kernel:
-//   fuse_kernel   one wave per query: the point's window query (query_fuse_point, orbfe_match_resolve.h: the very text the synchronous
-//                 calls run on the host), GetFeaturesInArea over the keyframe's own grid (orbfe_match_window.hpp: lane j owns cells
-//                 j, j + 64, ...), the chi-square gates per hit (fuse_chi2_passes, again the host's text), the smallest candidate key
-//                 of the wave = the reference loop's first minimum; lane 0 writes best_idx and adds to the count
+//   fuse_kernel   one wave per query: its row of the PointTable, the point's window query against the keyframe's View (query_fuse_point,
+//                 orbfe_match_resolve.h: the very text the synchronous calls run on the host), then wave_best_key
+//                 (orbfe_match_window.hpp): GetFeaturesInArea over the keyframe's own grid (lane j owns cells j, j + 64, ...), the
+//                 chi-square gates per hit (fuse_chi2_passes, again the host's text), the smallest candidate key of the wave = the
+//                 reference loop's first minimum; lane 0 writes best_idx and adds to the count
 // behind fuse_reset_kernel, which clears the count and the status on the stream.  The keyframe's grid is built once per keyframe by
 // grid_build_kernel (orbfe_enqueue_keyframe_grid) into arrays the caller keeps.  The calls own no scratch.
 // The grid and the keypoints are the caller's uploads, so the walk is the CHECKED one: offsets, indices and octaves are tested
-// before they become addresses, and what fails is reported in d_status.
+// before they become addresses, and what fails is reported in d_status.  What the calls refuse before a launch is
+// orbfe_point_table_frame, which the Sim3 SearchByProjection (orbfe_match_device.hip) shares.
 #include "../../include/orbfe.h"
 #include "orbfe_device.h"
 #include "orbfe_host.h"
 #include "orbfe_match_resolve.h"
 #include "orbfe_match_window.hpp"
 
-using orbfe_resolve::Camera;
+#include <climits>
+
 using orbfe_resolve::key_dist;
 using orbfe_resolve::key_idx;
 using orbfe_resolve::MatchQuery;
 using orbfe_resolve::TH_LOW;
+using orbfe_resolve::View;
 
 static_assert(sizeof(orbfe_grid_keyframe) == 64, "orbfe_grid_keyframe: five pointers, four bounds and two counts");
 static_assert(sizeof(orbfe_keypoint) == sizeof(KeyPointPOD), "the keyframe's keypoints are read as KeyPointPOD");
 
 struct FuseArgs {
-    GridFrame f;                 // the keyframe: n_ptr null, cap = its keypoint count
-    Camera C;
-    float sf[ORBFE_MAX_LEVELS];  // mvScaleFactors
-    int nlevels;
-    float log_sf;
-    float min_x, max_x, min_y, max_y; // the frame's float bounds ...
-    int keyframe;                     // ... which KeyFrame::IsInImage truncates
-    float T[12], ow[3];               // [R|t] (of Tcw, or of the decomposed Scw) and the camera centre, both computed on the host
-    int sim3;                         // Fuse(pKF, Scw, ...): reciprocal of z in double, no chi-square gates
-    int n_pts, n_rows;
-    const int32_t *pt_index;
-    const float *pos, *normal, *max_distance, *min_distance;
-    const uint8_t *pt_desc;
-    const int32_t *pt_valid;
+    GridFrame f;        // the keyframe: n_ptr null, cap = its keypoint count
+    View V;             // with the keyframe's bounds
+    float T[12], ow[3]; // [R|t] (of Tcw, or of the decomposed Scw) and the camera centre, both computed on the host
+    int sim3;           // Fuse(pKF, Scw, ...): reciprocal of z in double, no chi-square gates
+    int n_pts;
+    PointTable pts;
     float th;
     int32_t *best_idx, *n_fused, *status;
 };
@@ -60,40 +56,24 @@ __global__ __launch_bounds__(256) void fuse_kernel(FuseArgs a)
     const int lane = threadIdx.x & 63;
     if (q >= a.n_pts) return;
     const int n = a.f.cap;
-    bool bad = false;
-    int row = q;
-    if (a.pt_index) {
-        row = a.pt_index[q];
-        if (row < 0 || row >= a.n_rows) { bad = true; row = -1; } // checked before it addresses the table: the query gets -1
-    }
+    const PointTable &t = a.pts;
+    const int row = t.row(q); // -1: the index list names no row of the table, the query gets -1 and the call ORBFE_ERR_INVALID
+    bool clean = true;
     unsigned long long best = NO_KEY;
     if (n > 0 && row >= 0) { // a keyframe without keypoints has no window, and none of its arrays (or the table's) is read
         MatchQuery Q = {0, 0, 0, 0, -1, 0, 0, 0};
         float ur = 0.f;
-        const float p[3] = {a.pos[3 * (size_t)row], a.pos[3 * (size_t)row + 1], a.pos[3 * (size_t)row + 2]};
-        const float nr[3] = {a.normal[3 * (size_t)row], a.normal[3 * (size_t)row + 1], a.normal[3 * (size_t)row + 2]};
-        orbfe_resolve::query_fuse_point(a.C, a.sf, a.nlevels, a.log_sf, a.min_x, a.max_x, a.min_y, a.max_y, a.keyframe, a.T, a.ow, a.sim3, p, nr,
-                                        a.pt_valid[q], a.max_distance[row], a.min_distance[row], a.th, Q, &ur);
-        const Window w = query_window(a.f, Q);
-        if (w.ncells > 0) {
-            uint32_t qd[8];
-            const uint32_t *d = (const uint32_t *)(a.pt_desc + (size_t)row * 32);
-#pragma unroll
-            for (int k = 0; k < 8; k++) qd[k] = d[k];
-            const bool ok = for_each_hit<true>(
-                a.f, Q, w, lane,
-                [&](int ix, int iy, int idx, const KeyPointPOD &kp) {
-                    // kp.octave lies in [0, nlevels): the checked walk has tested it
-                    if (!a.sim3 && !orbfe_resolve::fuse_chi2_passes(Q.u, Q.v, ur, kp.x, kp.y, a.f.u_right ? a.f.u_right[idx] : -1.f, a.sf[kp.octave])) return;
-                    const unsigned long long key = candidate_key(a.f, Q, qd, ix, iy, idx, kp);
-                    if (key < best) best = key;
-                },
-                n, a.nlevels);
-            bad = bad || !ok;
-        }
+        const float p[3] = {t.pos[3 * (size_t)row], t.pos[3 * (size_t)row + 1], t.pos[3 * (size_t)row + 2]};
+        const float nr[3] = {t.normal[3 * (size_t)row], t.normal[3 * (size_t)row + 1], t.normal[3 * (size_t)row + 2]};
+        orbfe_resolve::query_fuse_point(a.V, a.T, a.ow, a.sim3, p, nr, t.pt_valid[q], t.max_distance[row], t.min_distance[row], a.th, Q, &ur);
+        best = wave_best_key(
+            a.f, Q, t.pt_desc + (size_t)row * 32, lane,
+            [&](int idx, const KeyPointPOD &kp) {
+                return a.sim3 || orbfe_resolve::fuse_chi2_passes(Q.u, Q.v, ur, kp.x, kp.y, a.f.u_right ? a.f.u_right[idx] : -1.f, a.V.sf[kp.octave]);
+            },
+            n, a.V.nlevels, clean);
     }
-    best = wave_min_u64(best); // smallest (distance, GetFeaturesInArea order) = the reference loop's first minimum
-    bad = __any(bad) != 0;
+    const bool bad = row < 0 || !clean;
     if (lane == 0) {
         const int idx = (best != NO_KEY && key_dist(best) <= TH_LOW) ? key_idx(best) : -1;
         a.best_idx[q] = idx;
@@ -102,7 +82,6 @@ __global__ __launch_bounds__(256) void fuse_kernel(FuseArgs a)
     }
 }
 
-#define FTRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return orbfe_fail(ctx, ORBFE_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
 
 // the part of a GridFrame that the grid builder and the window walk share: where the keypoints are and how cells are assigned
 static int grid_frame_of(orbfe_context *ctx, const orbfe_keypoint *d_keys_un, int n, float min_x, float max_x, float min_y, float max_y, int keyframe,
@@ -137,46 +116,49 @@ try {
     GridFrame f;
     const int rc = grid_frame_of(ctx, d_keys_un, n, bounds[0], bounds[1], bounds[2], bounds[3], 0, d_cell_off, d_cell_idx, f);
     if (rc != ORBFE_OK) return rc;
-    FTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     orbfe_launch_grid_build(f, stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx)); // with n == 0: 3073 zero offsets, no other access
-    FTRY(ctx, hipGetLastError());
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)
+
+int orbfe_point_table_frame(orbfe_context *ctx, const orbfe_grid_keyframe *kf, int n_pts, int max_pts, const PointTable &t, GridFrame &f)
+{
+    if (n_pts < 0 || t.n_rows < 0) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "negative count");
+    if (!t.pt_index && t.n_rows < n_pts) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "%d queries without an index list over a table of %d rows", n_pts, t.n_rows);
+    if (n_pts > max_pts) return orbfe_fail(ctx, ORBFE_ERR_CAPACITY, "%d points: the matcher's scratch rows hold %d", n_pts, max_pts);
+    const int rc = orbfe_grid_frame_of_record(ctx, kf, f);
+    if (rc != ORBFE_OK) return rc;
+    if (n_pts > 0 && kf->n > 0 &&
+        (!t.pos || !t.normal || !t.max_distance || !t.min_distance || !t.pt_desc || !t.pt_valid || !kf->keys_un || !kf->desc || !kf->cell_off || !kf->cell_idx))
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null array in the point table or in the keyframe record");
+    const int nlevels = orbfe_ctx_params(ctx)->nlevels;
+    if (nlevels < 1 || nlevels > ORBFE_MAX_LEVELS) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "nlevels = %d", nlevels);
+    return ORBFE_OK;
+}
 
 static int enqueue_fuse(orbfe_context *ctx, int sim3, const orbfe_grid_keyframe *kf, const float *pose, int n_pts, const int32_t *d_pt_index, int n_rows,
                         const float *d_pos, const float *d_normal, const float *d_max_distance, const float *d_min_distance, const uint8_t *d_pt_desc,
                         const int32_t *d_pt_valid, float th, int32_t *d_best_idx, int32_t *d_n_fused, int32_t *d_status, void *stream)
 {
     if (!kf || !pose || !d_best_idx || !d_n_fused || !d_status) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
-    if (n_pts < 0 || n_rows < 0) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "negative count");
-    if (!d_pt_index && n_rows < n_pts) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "%d queries without an index list over a table of %d rows", n_pts, n_rows);
     FuseArgs a;
-    int rc = orbfe_grid_frame_of_record(ctx, kf, a.f);
+    a.pts = {d_pt_index, n_rows, d_pos, d_normal, d_max_distance, d_min_distance, d_pt_desc, d_pt_valid};
+    const int rc = orbfe_point_table_frame(ctx, kf, n_pts, INT_MAX, a.pts, a.f); // the calls own no scratch: any count
     if (rc != ORBFE_OK) return rc;
-    if (n_pts > 0 && kf->n > 0 &&
-        (!d_pos || !d_normal || !d_max_distance || !d_min_distance || !d_pt_desc || !d_pt_valid || !kf->keys_un || !kf->desc || !kf->cell_off || !kf->cell_idx))
-        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null array in the point table or in the keyframe record");
-    const orbfe_params *P = orbfe_ctx_params(ctx);
-    if (P->nlevels < 1 || P->nlevels > ORBFE_MAX_LEVELS) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "nlevels = %d", P->nlevels);
-    a.C = orbfe_resolve::camera_of(P);
-    const float *sf = orbfe_ctx_scale_factors(ctx);
-    for (int l = 0; l < ORBFE_MAX_LEVELS; l++) a.sf[l] = l < P->nlevels ? sf[l] : 1.f;
-    a.nlevels = P->nlevels;
-    a.log_sf = logf((float)(double)P->scale_factor); // mfLogScaleFactor = log(mfScaleFactor), src/Frame.cc:71
-    a.min_x = kf->min_x; a.max_x = kf->max_x; a.min_y = kf->min_y; a.max_y = kf->max_y; a.keyframe = kf->keyframe != 0;
+    a.V = orbfe_view(ctx, kf);
     if (sim3) orbfe_resolve::sim3_to_rt(pose, a.T);
     else for (int k = 0; k < 12; k++) a.T[k] = pose[k];
     orbfe_resolve::camera_center(a.T, a.ow);
     a.sim3 = sim3;
-    a.n_pts = n_pts; a.n_rows = n_rows; a.pt_index = d_pt_index;
-    a.pos = d_pos; a.normal = d_normal; a.max_distance = d_max_distance; a.min_distance = d_min_distance; a.pt_desc = d_pt_desc; a.pt_valid = d_pt_valid;
+    a.n_pts = n_pts;
     a.th = th;
     a.best_idx = d_best_idx; a.n_fused = d_n_fused; a.status = d_status;
     hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    FTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     hipLaunchKernelGGL(fuse_reset_kernel, dim3(1), dim3(64), 0, s, d_n_fused, d_status);
     if (n_pts > 0) hipLaunchKernelGGL(fuse_kernel, dim3((n_pts + 3) / 4), dim3(256), 0, s, a);
-    FTRY(ctx, hipGetLastError());
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
     return ORBFE_OK;
 }
 

@@ -28,6 +28,8 @@ orbfe_match_state *orbfe_match_state_create();
 void orbfe_match_state_destroy(orbfe_match_state *s);
 
 int orbfe_fail(orbfe_context *ctx, int code, const char *fmt, ...);
+// a HIP call inside a function that returns a status: its failure is the context's error, with the call's text
+#define ORBFE_HIP_TRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return orbfe_fail(ctx, ORBFE_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
 // Every entry point that takes a (non-const) context holds the context's mutex for its whole duration: the reference's
 // Tracking, LocalMapping and LoopClosing threads each construct ORBmatcher objects (src/LocalMapping.cc:215,482,
 // src/LoopClosing.cc:275,623) and the shim gives them all the left extractor's context, whose matcher / BoW / database state

@@ -10,7 +10,7 @@
 // simply the smallest key, independent of the order in which the GPU emitted the list.  The grid (grid_build_kernel behind
 // orbfe_launch_grid_build), the window, its walk, the key and the top-4 selection are the statements of orbfe_match_window.hpp,
 // shared with orbfe_match_device.hip: the two files differ in the resolution, not below it.
-// Projection / frustum arithmetic is host code in the reference's evaluation order (contract Q4: no FMA
+// Projection / frustum arithmetic is host code against the context's View (orbfe_view) in the reference's evaluation order (contract Q4: no FMA
 // contraction; cv::Mat 3x3*3x1+t as OpenCV's small-matrix gemm path; PredictScale's log through one
 // deterministic routine).  The candidate machinery (64-bit keys, top-4 prefixes, replays) has no counterpart in the oracle, which
 // walks vectors as the reference does; the float statements of the projections and rot_bin are the reference's own and therefore
@@ -31,11 +31,6 @@
 #include <new>
 #include <vector>
 
-// KeyFrame::IsInImage of a view (orbfe_match_resolve.h)
-static inline bool kf_is_in_image(const orbfe_frame_view *kf, float u, float v)
-{
-    return orbfe_resolve::kf_is_in_image(kf->min_x, kf->max_x, kf->min_y, kf->max_y, kf->keyframe, u, v);
-}
 using orbfe_resolve::HISTO_LENGTH;
 using orbfe_resolve::key_dist;
 using orbfe_resolve::key_idx;
@@ -139,14 +134,13 @@ struct orbfe_match_state {
 
 static orbfe_match_state *match_state(orbfe_context *ctx) { return orbfe_ctx_match_state(ctx); }
 
-#define MTRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return orbfe_fail(ctx, ORBFE_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
 
 static int ensure_pinned(orbfe_context *ctx, uint8_t *&h, size_t &have, size_t need)
 {
     if (have >= need) return ORBFE_OK;
     if (h) (void)hipHostFree(h);
     h = nullptr; have = 0;
-    MTRY(ctx, hipHostMalloc((void **)&h, need, hipHostMallocDefault));
+    ORBFE_HIP_TRY(ctx, hipHostMalloc((void **)&h, need, hipHostMallocDefault));
     have = need;
     return ORBFE_OK;
 }
@@ -175,7 +169,7 @@ static int run_window_queries(orbfe_context *ctx, const orbfe_frame_view *fv, co
     st->list_on_host = true; st->list_total = 0;
     if (n <= 0 || nq == 0) return ORBFE_OK;
     if (n > 65535) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "frames with more than 65535 keypoints are not supported by the matchers");
-    MTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     const bool resident = fv->device_slot_plus1 > 0;
     const int slot = fv->device_slot_plus1 - 1;
     const DeviceConfig *cfg = orbfe_ctx_config(ctx);
@@ -241,22 +235,22 @@ static int run_window_queries(orbfe_context *ctx, const orbfe_frame_view *fv, co
     memcpy(st->h_in + i_q, queries.data(), sizeof(MatchQuery) * nq);
     memcpy(st->h_in + i_qd, qdesc.data(), (size_t)32 * nq);
     if (topk && topk->blocked0) memcpy(st->h_in + i_blk, topk->blocked0, (size_t)n);
-    MTRY(ctx, hipMemcpyAsync(din, st->h_in, in_bytes, hipMemcpyHostToDevice, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(din, st->h_in, in_bytes, hipMemcpyHostToDevice, s));
     if (build_grid) orbfe_launch_grid_build(f, s);
     // candidate list capacity: grown and the query re-run if a frame overflows it
     size_t cap = st->list.bytes / 8;
     if (cap < (size_t)nq * 64) cap = (size_t)nq * 64;
     for (int attempt = 0; attempt < 2; attempt++) {
         if (st->list.ensure(cap * 8)) return orbfe_fail(ctx, ORBFE_ERR_HIP, "candidate list allocation failed");
-        MTRY(ctx, hipMemsetAsync(dout + o_cur, 0, sizeof(int), s));
+        ORBFE_HIP_TRY(ctx, hipMemsetAsync(dout + o_cur, 0, sizeof(int), s));
         hipLaunchKernelGGL(window_candidates_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, f, (const MatchQuery *)(din + i_q),
                            (const uint8_t *)(din + i_qd), nq, (int *)(dout + o_off), (int *)(dout + o_cnt),
                            (unsigned long long *)st->list.p, (int *)(dout + o_cur), (int)std::min<size_t>(cap, INT_MAX),
                            topk ? (unsigned long long *)(dout + o_tk) : nullptr, (int *)(dout + o_ns),
                            topk && topk->blocked0 ? (const uint8_t *)(din + i_blk) : nullptr, topk && topk->gate_drop ? 1 : 0);
-        MTRY(ctx, hipMemcpyAsync(st->h_out, dout, topk ? topk_bytes : out_bytes, hipMemcpyDeviceToHost, s));
-        MTRY(ctx, hipStreamSynchronize(s));
-        MTRY(ctx, hipGetLastError());
+        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(st->h_out, dout, topk ? topk_bytes : out_bytes, hipMemcpyDeviceToHost, s));
+        ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
+        ORBFE_HIP_TRY(ctx, hipGetLastError());
         const int total = *(const int *)(st->h_out + o_cur);
         if ((size_t)total <= cap) {
             st->list_total = total;
@@ -270,7 +264,7 @@ static int run_window_queries(orbfe_context *ctx, const orbfe_frame_view *fv, co
             memcpy(st->h_off.data(), st->h_out + o_off, sizeof(int) * nq);
             memcpy(st->h_cnt.data(), st->h_out + o_cnt, sizeof(int) * nq);
             st->h_list.resize(total);
-            if (total > 0) MTRY(ctx, hipMemcpy(st->h_list.data(), st->list.p, sizeof(unsigned long long) * total, hipMemcpyDeviceToHost));
+            if (total > 0) ORBFE_HIP_TRY(ctx, hipMemcpy(st->h_list.data(), st->list.p, sizeof(unsigned long long) * total, hipMemcpyDeviceToHost));
             return ORBFE_OK;
         }
         cap = (size_t)total + 1024;
@@ -309,6 +303,45 @@ static orbfe_resolve::CandidateSource topk_source(orbfe_match_state *st, FullLis
     src.user = fl;
     src.full = fetch_full_list;
     return src;
+}
+
+// A top-K replay (orbfe_match_resolve.h) over the frame's keypoints: `state` starts from the caller's flags (null: all free) and is
+// what the replay mutates; the static filter of the window query is a copy of it from BEFORE the replay.  Lives in the caller's frame:
+// src points into it.
+struct TopkReplay {
+    std::vector<uint8_t> state, blocked0;
+    FullListCtx fl;
+    orbfe_resolve::CandidateSource src;
+    int begin(orbfe_context *ctx, const orbfe_frame_view *fv, const uint8_t *flags, bool gate_drop, const std::vector<MatchQuery> &q,
+              const std::vector<uint8_t> &qd)
+    {
+        const int N = fv->n;
+        state.assign(N > 0 ? N : 1, 0);
+        for (int i = 0; i < N; i++) state[i] = flags ? (flags[i] != 0) : 0;
+        blocked0 = state;
+        TopkRequest req;
+        req.blocked0 = flags ? blocked0.data() : nullptr;
+        req.gate_drop = gate_drop; // 511 = failed the mvuRight gate
+        const int rc = run_window_queries(ctx, fv, q, qd, &req);
+        if (rc != ORBFE_OK) return rc;
+        fl = FullListCtx{ctx, match_state(ctx)};
+        src = topk_source(fl.st, &fl, req);
+        return ORBFE_OK;
+    }
+    int end(orbfe_context *ctx) const { return src.error ? orbfe_fail(ctx, ORBFE_ERR_HIP, "candidate list download failed") : ORBFE_OK; }
+};
+
+// The smallest key of query i's candidate list (the latest run_window_queries without a top-K request) that skip(key) does not drop:
+// smallest (distance, GetFeaturesInArea order) = the reference loop's first minimum; ~0ull: none
+template <class Skip>
+static unsigned long long smallest_key(const orbfe_match_state *st, int i, Skip skip)
+{
+    unsigned long long best = ~0ull;
+    for (int k = 0; k < st->h_cnt[i]; k++) {
+        const unsigned long long key = st->h_list[st->h_off[i] + k];
+        if (!skip(key) && key < best) best = key;
+    }
+    return best;
 }
 
 using orbfe_resolve::camera_center;
@@ -372,10 +405,10 @@ try {
     if (rc != ORBFE_OK) return rc;
     orbfe_match_state *st = match_state(ctx);
     const int *d_off = (const int *)st->cells.p; // GridFrame::cell_off, cell_idx behind it (run_window_queries)
-    MTRY(ctx, hipMemcpy(cell_off, d_off, sizeof(int) * (ncell + 1), hipMemcpyDeviceToHost));
+    ORBFE_HIP_TRY(ctx, hipMemcpy(cell_off, d_off, sizeof(int) * (ncell + 1), hipMemcpyDeviceToHost));
     const int total = cell_off[ncell]; // keypoints that fell inside the grid (PosInGrid drops the others)
     if (total < 0 || total > fv->n) return orbfe_fail(ctx, ORBFE_ERR_HIP, "grid holds %d entries for %d keypoints", total, fv->n);
-    if (total > 0) MTRY(ctx, hipMemcpy(cell_idx, d_off + ncell + 1, sizeof(int) * total, hipMemcpyDeviceToHost));
+    if (total > 0) ORBFE_HIP_TRY(ctx, hipMemcpy(cell_idx, d_off + ncell + 1, sizeof(int) * total, hipMemcpyDeviceToHost));
     // grid_build_kernel claims a cell's slots through an atomic cursor (the matchers order candidates by their keys, not by list
     // position); mGrid[ix][iy] is in push_back order = ascending keypoint index
     for (int c = 0; c < ncell; c++)
@@ -428,31 +461,22 @@ try {
     if (!Tcw_cur || !Tcw_last || !cur_match || !nmatches || n_last < 0 ||
         (n_last > 0 && (!last_pos || !last_desc || !last_valid || !last_obs || !last_octave || !last_angle)))
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
-    const orbfe_params *P = orbfe_ctx_params(ctx);
     const int N = cur->n;
     static const bool trace = getenv("ORBFE_HOST_TRACE") != nullptr; // where a call's time goes: projection | device round trip | replay
     auto now_ms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = trace ? now_ms() : 0.0;
     std::vector<MatchQuery> q;
     std::vector<uint8_t> qd;
-    if (orbfe_resolve::build_queries_last(orbfe_resolve::camera_of(P), orbfe_ctx_scale_factors(ctx), P->nlevels, cur->min_x, cur->max_x, cur->min_y, cur->max_y,
-                                          Tcw_cur, Tcw_last, n_last, last_pos, last_desc, last_valid, last_octave, th, mono, q, qd) != 0)
+    if (orbfe_resolve::build_queries_last(orbfe_view(ctx, cur), Tcw_cur, Tcw_last, n_last, last_pos, last_desc, last_valid, last_octave, th, mono, q, qd) != 0)
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "octave out of range");
-    std::vector<uint8_t> has_obs(N > 0 ? N : 1, 0);
-    for (int i = 0; i < N; i++) has_obs[i] = cur_has_obs ? (cur_has_obs[i] != 0) : 0;
-    std::vector<uint8_t> blocked0(has_obs); // the static filter is the state BEFORE the replay mutates has_obs
-    TopkRequest req;
-    req.blocked0 = cur_has_obs ? blocked0.data() : nullptr;
-    req.gate_drop = true; // 511 = failed the mvuRight gate
     const double t1 = trace ? now_ms() : 0.0;
-    rc = run_window_queries(ctx, cur, q, qd, &req);
+    TopkReplay r;
+    rc = r.begin(ctx, cur, cur_has_obs, true, q, qd);
     if (rc != ORBFE_OK) return rc;
     const double t2 = trace ? now_ms() : 0.0;
-    orbfe_match_state *st = match_state(ctx);
-    FullListCtx fl{ctx, st};
-    orbfe_resolve::CandidateSource src = topk_source(st, &fl, req);
-    *nmatches = orbfe_resolve::resolve_last(src, n_last, last_obs, last_angle, N, &cur->keys_un[0].angle, sizeof(orbfe_keypoint), has_obs, check_ori, cur_match);
-    if (src.error) return orbfe_fail(ctx, ORBFE_ERR_HIP, "candidate list download failed");
+    *nmatches = orbfe_resolve::resolve_last(r.src, n_last, last_obs, last_angle, N, &cur->keys_un[0].angle, sizeof(orbfe_keypoint), r.state, check_ori, cur_match);
+    rc = r.end(ctx);
+    if (rc != ORBFE_OK) return rc;
     if (trace)
         fprintf(stderr, "[orbfe] SearchByProjection(last): queries %.3f  device round trip %.3f  replay %.3f ms (%d points, %d keypoints)\n",
                 t1 - t0, t2 - t1, now_ms() - t2, n_last, N);
@@ -467,10 +491,7 @@ try {
     ORBFE_ENTRY(ctx);
     if (!ctx || !Tcw || n < 0 || (n > 0 && (!pos || !normal || !max_distance || !min_distance || !out)))
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
-    const orbfe_params *P = orbfe_ctx_params(ctx);
-    const float log_sf = logf((float)(double)P->scale_factor); // mfLogScaleFactor = log(mfScaleFactor), src/Frame.cc:71
-    orbfe_resolve::is_in_frustum(orbfe_resolve::camera_of(P), P->nlevels, log_sf, Tcw, min_x, max_x, min_y, max_y, n, pos, normal, max_distance, min_distance,
-                                 viewing_cos_limit, out);
+    orbfe_resolve::is_in_frustum(orbfe_view(ctx, min_x, max_x, min_y, max_y, 0), Tcw, n, pos, normal, max_distance, min_distance, viewing_cos_limit, out);
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)
 
@@ -484,26 +505,15 @@ try {
     int rc = check_view(ctx, cur);
     if (rc != ORBFE_OK) return rc;
     if (!cur_match || !nmatches || n_pts < 0 || (n_pts > 0 && (!pts || !pt_desc || !pt_obs))) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
-    const orbfe_params *P = orbfe_ctx_params(ctx);
-    const int N = cur->n;
     std::vector<MatchQuery> q;
     std::vector<uint8_t> qd;
-    if (orbfe_resolve::build_queries_points(orbfe_ctx_scale_factors(ctx), P->nlevels, n_pts, pts, pt_desc, th, q, qd) != 0)
+    if (orbfe_resolve::build_queries_points(orbfe_ctx_scale_factors(ctx), orbfe_ctx_params(ctx)->nlevels, n_pts, pts, pt_desc, th, q, qd) != 0)
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "predicted level out of range");
-    std::vector<uint8_t> has_obs(N > 0 ? N : 1, 0);
-    for (int i = 0; i < N; i++) has_obs[i] = cur_has_obs ? (cur_has_obs[i] != 0) : 0;
-    std::vector<uint8_t> blocked0(has_obs);
-    TopkRequest req;
-    req.blocked0 = cur_has_obs ? blocked0.data() : nullptr;
-    req.gate_drop = true;
-    rc = run_window_queries(ctx, cur, q, qd, &req);
+    TopkReplay r;
+    rc = r.begin(ctx, cur, cur_has_obs, true, q, qd);
     if (rc != ORBFE_OK) return rc;
-    orbfe_match_state *st = match_state(ctx);
-    FullListCtx fl{ctx, st};
-    orbfe_resolve::CandidateSource src = topk_source(st, &fl, req);
-    *nmatches = orbfe_resolve::resolve_points(src, n_pts, pt_obs, N, has_obs, nnratio, cur_match);
-    if (src.error) return orbfe_fail(ctx, ORBFE_ERR_HIP, "candidate list download failed");
-    return ORBFE_OK;
+    *nmatches = orbfe_resolve::resolve_points(r.src, n_pts, pt_obs, cur->n, r.state, nnratio, cur_match);
+    return r.end(ctx);
 } ORBFE_CATCH(ctx)
 
 // ORBmatcher::SearchByProjection(Frame&, KeyFrame*, set, th, ORBdist), src/ORBmatcher.cc:1468-1595
@@ -519,26 +529,14 @@ try {
     if (!Tcw_cur || !cur_match || !nmatches || n_kf < 0 ||
         (n_kf > 0 && (!kf_pos || !kf_desc || !kf_valid || !kf_angle || !kf_max_distance || !kf_min_distance)))
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
-    const orbfe_params *P = orbfe_ctx_params(ctx);
-    const int N = cur->n;
     std::vector<MatchQuery> q;
     std::vector<uint8_t> qd;
-    orbfe_resolve::build_queries_kf(orbfe_resolve::camera_of(P), orbfe_ctx_scale_factors(ctx), P->nlevels, logf((float)(double)P->scale_factor), cur->min_x, cur->max_x,
-                                    cur->min_y, cur->max_y, Tcw_cur, n_kf, kf_pos, kf_desc, kf_valid, kf_max_distance, kf_min_distance, th, q, qd);
-    std::vector<uint8_t> has_pt(N > 0 ? N : 1, 0);
-    for (int i = 0; i < N; i++) has_pt[i] = cur_has_point ? (cur_has_point[i] != 0) : 0;
-    std::vector<uint8_t> blocked0(has_pt);
-    TopkRequest req;
-    req.blocked0 = cur_has_point ? blocked0.data() : nullptr;
-    req.gate_drop = false; // this overload has no mvuRight gate
-    rc = run_window_queries(ctx, cur, q, qd, &req);
+    orbfe_resolve::build_queries_kf(orbfe_view(ctx, cur), Tcw_cur, n_kf, kf_pos, kf_desc, kf_valid, kf_max_distance, kf_min_distance, th, q, qd);
+    TopkReplay r;
+    rc = r.begin(ctx, cur, cur_has_point, false, q, qd); // this overload has no mvuRight gate
     if (rc != ORBFE_OK) return rc;
-    orbfe_match_state *st = match_state(ctx);
-    FullListCtx fl{ctx, st};
-    orbfe_resolve::CandidateSource src = topk_source(st, &fl, req);
-    *nmatches = orbfe_resolve::resolve_kf(src, n_kf, kf_angle, N, &cur->keys_un[0].angle, sizeof(orbfe_keypoint), has_pt, orb_dist, check_ori, cur_match);
-    if (src.error) return orbfe_fail(ctx, ORBFE_ERR_HIP, "candidate list download failed");
-    return ORBFE_OK;
+    *nmatches = orbfe_resolve::resolve_kf(r.src, n_kf, kf_angle, cur->n, &cur->keys_un[0].angle, sizeof(orbfe_keypoint), r.state, orb_dist, check_ori, cur_match);
+    return r.end(ctx);
 } ORBFE_CATCH(ctx)
 
 // Search part of ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th), src/ORBmatcher.cc:821-971: per candidate map
@@ -553,22 +551,18 @@ try {
     if (rc != ORBFE_OK) return rc;
     if (!Tcw || !n_fused || n_pts < 0 || (n_pts > 0 && (!pos || !normal || !max_distance || !min_distance || !pt_desc || !pt_valid || !best_idx)))
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
-    const orbfe_params *P = orbfe_ctx_params(ctx);
-    const float *sf = orbfe_ctx_scale_factors(ctx);
-    const float log_sf = logf((float)(double)P->scale_factor);
+    const orbfe_resolve::View V = orbfe_view(ctx, kf);
     float ow[3];
     camera_center(Tcw, ow);
     std::vector<MatchQuery> q(n_pts);
     std::vector<uint8_t> qd((size_t)32 * (n_pts > 0 ? n_pts : 1));
     std::vector<float> pur(n_pts > 0 ? n_pts : 1); // the projection into the right image; u and v stay in the query
-    const orbfe_resolve::Camera cam = orbfe_resolve::camera_of(P);
     for (int i = 0; i < n_pts; i++) {
         MatchQuery &Q = q[i];
         Q = MatchQuery{0, 0, 0, 0, -1, 0, 0, 0};
         best_idx[i] = -1;
         // the loop body up to GetFeaturesInArea: one text with the kernel of orbfe_enqueue_fuse (orbfe_fuse_device.hip)
-        if (orbfe_resolve::query_fuse_point(cam, sf, P->nlevels, log_sf, kf->min_x, kf->max_x, kf->min_y, kf->max_y, kf->keyframe, Tcw, ow, 0, pos + 3 * i,
-                                            normal + 3 * i, pt_valid[i], max_distance[i], min_distance[i], th, Q, &pur[i]) <= 0)
+        if (orbfe_resolve::query_fuse_point(V, Tcw, ow, 0, pos + 3 * i, normal + 3 * i, pt_valid[i], max_distance[i], min_distance[i], th, Q, &pur[i]) <= 0)
             continue;
         memcpy(&qd[(size_t)32 * i], pt_desc + (size_t)32 * i, 32);
     }
@@ -577,14 +571,11 @@ try {
     orbfe_match_state *st = match_state(ctx);
     int nf = 0;
     for (int i = 0; i < n_pts; i++) {
-        unsigned long long best = ~0ull;
-        for (int k = 0; k < st->h_cnt[i]; k++) {
-            const unsigned long long key = st->h_list[st->h_off[i] + k];
-            const int idx = key_idx(key), lv = key_level(key);
+        const unsigned long long best = smallest_key(st, i, [&](unsigned long long key) {
+            const int idx = key_idx(key);
             const orbfe_keypoint &kp = kf->keys_un[idx];
-            if (!orbfe_resolve::fuse_chi2_passes(q[i].u, q[i].v, pur[i], kp.x, kp.y, kf->u_right ? kf->u_right[idx] : -1.f, sf[lv])) continue; // :905-930
-            if (key < best) best = key; // smallest (distance, GetFeaturesInArea order) = the loop's first minimum
-        }
+            return !orbfe_resolve::fuse_chi2_passes(q[i].u, q[i].v, pur[i], kp.x, kp.y, kf->u_right ? kf->u_right[idx] : -1.f, V.sf[key_level(key)]); // :905-930
+        });
         if (best != ~0ull && key_dist(best) <= TH_LOW) { best_idx[i] = key_idx(best); nf++; }
     }
     *n_fused = nf;
@@ -602,14 +593,11 @@ static int sim3_projection_impl(orbfe_context *ctx, int mode, const orbfe_frame_
     if (rc != ORBFE_OK) return rc;
     if (!Scw || !nmatches || n_pts < 0 || (n_pts > 0 && (!pos || !normal || !max_distance || !min_distance || !pt_desc || !pt_valid || !pt_match)))
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
-    const orbfe_params *P = orbfe_ctx_params(ctx);
-    const float *sf = orbfe_ctx_scale_factors(ctx);
-    const float log_sf = logf((float)(double)P->scale_factor);
+    const orbfe_resolve::View V = orbfe_view(ctx, kf);
     const int N = kf->n;
     float T[12], ow[3];
     orbfe_resolve::sim3_to_rt(Scw, T);
     camera_center(T, ow);
-    const orbfe_resolve::Camera cam = orbfe_resolve::camera_of(P);
     std::vector<MatchQuery> q(n_pts);
     std::vector<uint8_t> qd((size_t)32 * (n_pts > 0 ? n_pts : 1));
     for (int i = 0; i < n_pts; i++) {
@@ -618,8 +606,7 @@ static int sim3_projection_impl(orbfe_context *ctx, int mode, const orbfe_frame_
         pt_match[i] = -1;
         float ur; // not used by the Sim3 matchers
         // one text with the kernel of orbfe_enqueue_fuse_sim3 (orbfe_fuse_device.hip); mode 1 takes the reciprocal of z in double
-        if (orbfe_resolve::query_fuse_point(cam, sf, P->nlevels, log_sf, kf->min_x, kf->max_x, kf->min_y, kf->max_y, kf->keyframe, T, ow, mode == 1,
-                                            pos + 3 * i, normal + 3 * i, pt_valid[i], max_distance[i], min_distance[i], th, Q, &ur) <= 0)
+        if (orbfe_resolve::query_fuse_point(V, T, ow, mode == 1, pos + 3 * i, normal + 3 * i, pt_valid[i], max_distance[i], min_distance[i], th, Q, &ur) <= 0)
             continue;
         memcpy(&qd[(size_t)32 * i], pt_desc + (size_t)32 * i, 32);
     }
@@ -631,12 +618,7 @@ static int sim3_projection_impl(orbfe_context *ctx, int mode, const orbfe_frame_
         for (int i = 0; i < N; i++) matched[i] = kf_matched[i];
     int nm = 0;
     for (int i = 0; i < n_pts; i++) {
-        unsigned long long best = ~0ull;
-        for (int k = 0; k < st->h_cnt[i]; k++) {
-            const unsigned long long key = st->h_list[st->h_off[i] + k];
-            if (matched[key_idx(key)]) continue;
-            if (key < best) best = key;
-        }
+        const unsigned long long best = smallest_key(st, i, [&](unsigned long long key) { return matched[key_idx(key)] != 0; });
         if (best != ~0ull && key_dist(best) <= TH_LOW) {
             pt_match[i] = key_idx(best);
             if (mode == 0) matched[key_idx(best)] = 1;
@@ -670,19 +652,14 @@ static int sim3_one_way(orbfe_context *ctx, const float *Taw, const float *sRt, 
                         const float *pos, const float *max_distance, const float *min_distance, const uint8_t *desc,
                         const int32_t *valid, float th, std::vector<int32_t> &match)
 {
-    const orbfe_params *P = orbfe_ctx_params(ctx);
-    const float *sf = orbfe_ctx_scale_factors(ctx);
-    const float log_sf = logf((float)(double)P->scale_factor);
-    const orbfe_resolve::Camera cam = orbfe_resolve::camera_of(P);
+    const orbfe_resolve::View V = orbfe_view(ctx, kfb);
     std::vector<MatchQuery> q(n);
     std::vector<uint8_t> qd((size_t)32 * (n > 0 ? n : 1));
     for (int i = 0; i < n; i++) {
         MatchQuery &Q = q[i];
         Q = MatchQuery{0, 0, 0, 0, -1, 0, 0, 0};
         // one text with the kernel of orbfe_enqueue_search_by_sim3 (orbfe_sim3_device.hip)
-        if (orbfe_resolve::query_sim3_point(cam, sf, P->nlevels, log_sf, kfb->min_x, kfb->max_x, kfb->min_y, kfb->max_y, kfb->keyframe, Taw, sRt, pos + 3 * i,
-                                            valid[i], max_distance[i], min_distance[i], th, Q) <= 0)
-            continue;
+        if (orbfe_resolve::query_sim3_point(V, Taw, sRt, pos + 3 * i, valid[i], max_distance[i], min_distance[i], th, Q) <= 0) continue;
         memcpy(&qd[(size_t)32 * i], desc + (size_t)32 * i, 32);
     }
     int rc = run_window_queries(ctx, kfb, q, qd);
@@ -690,11 +667,7 @@ static int sim3_one_way(orbfe_context *ctx, const float *Taw, const float *sRt, 
     orbfe_match_state *st = match_state(ctx);
     match.assign(n > 0 ? n : 1, -1);
     for (int i = 0; i < n; i++) {
-        unsigned long long best = ~0ull;
-        for (int k = 0; k < st->h_cnt[i]; k++) {
-            const unsigned long long key = st->h_list[st->h_off[i] + k];
-            if (key < best) best = key;
-        }
+        const unsigned long long best = smallest_key(st, i, [](unsigned long long) { return false; });
         if (best != ~0ull && key_dist(best) <= TH_HIGH) match[i] = key_idx(best);
     }
     return ORBFE_OK;
@@ -748,18 +721,14 @@ try {
     std::vector<MatchQuery> q;
     std::vector<uint8_t> qd;
     orbfe_resolve::build_queries_initialization(n1, f1->keys_un, f1->descriptors, prev_matched, window_size, q, qd);
-    TopkRequest req; // no static filter: the stealing rule (vMatchedDistance) is dynamic
-    rc = run_window_queries(ctx, f2, q, qd, &req);
+    TopkReplay r;
+    rc = r.begin(ctx, f2, nullptr, false, q, qd); // no static filter: the stealing rule (vMatchedDistance) is dynamic
     if (rc != ORBFE_OK) return rc;
-    orbfe_match_state *st = match_state(ctx);
-    FullListCtx fl{ctx, st};
-    orbfe_resolve::CandidateSource src = topk_source(st, &fl, req);
     static const orbfe_keypoint none = {};
-    *nmatches = orbfe_resolve::resolve_initialization(src, n1, n2, n1 > 0 ? &f1->keys_un[0].angle : &none.angle, sizeof(orbfe_keypoint),
+    *nmatches = orbfe_resolve::resolve_initialization(r.src, n1, n2, n1 > 0 ? &f1->keys_un[0].angle : &none.angle, sizeof(orbfe_keypoint),
                                                       n2 > 0 ? &f2->keys_un[0].angle : &none.angle, sizeof(orbfe_keypoint),
                                                       n2 > 0 ? &f2->keys_un[0].x : &none.x, nnratio, check_ori, prev_matched, matches12);
-    if (src.error) return orbfe_fail(ctx, ORBFE_ERR_HIP, "candidate list download failed");
-    return ORBFE_OK;
+    return r.end(ctx);
 } ORBFE_CATCH(ctx)
 
 orbfe_match_state *orbfe_match_state_create() { return new (std::nothrow) orbfe_match_state(); }

@@ -17,10 +17,12 @@
 // candidate, whose arguments come from its orbfe_reloc_candidate record (KfBatch); kf_prepare_kernel builds sAlreadyFound and the
 // keypoints' has-point flags from cur_point first.
 // SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) of LoopClosing::ComputeSim3 (src/ORBmatcher.cc:285-398) runs through the window
-// and resolve kernels as well, against an orbfe_grid_keyframe record instead of an image slot (Sim3Source, Sim3Points): the keyframe
-// rule with the keypoints matched on entry as static blocks and TH_LOW as the bound.  Its grid and keypoints are the caller's uploads,
+// and resolve kernels as well, against an orbfe_grid_keyframe record instead of an image slot (Sim3Source; Sim3Points, the PointTable of
+// orbfe_match_window.hpp that orbfe_fuse_device.hip reads too): the keyframe rule with the keypoints matched on entry as static blocks
+// and TH_LOW as the bound.  Its grid and keypoints are the caller's uploads,
 // so it has instantiations of its own (CHECKED) in which both walks -- the top-4 pass and wave 0's rescan -- test offsets, indices and
 // octaves before they become addresses; the instantiations of the matchers above are what they were.
+// Every source projects against a View (orbfe_match_resolve.h: camera, scale factors, bounds), built on the host by orbfe_view.
 // The grid cell, the window, its walk, the candidate key and the top-4 selection are orbfe_match_window.hpp, shared with
 // orbfe_match.hip; the smallest key is the reference loop's first minimum.  No candidate list is kept: a query whose four keys are
 // all taken recomputes its window.
@@ -39,7 +41,6 @@
 #define RESOLVE_CHUNK 1024  // queries staged in LDS at a time
 #define Q_BAD 4 // MatchQuery::flags bit of the device path: the point's octave / predicted level is out of range
 
-using orbfe_resolve::Camera;
 using orbfe_resolve::HISTO_LENGTH;
 using orbfe_resolve::key_dist;
 using orbfe_resolve::key_idx;
@@ -47,14 +48,7 @@ using orbfe_resolve::key_level;
 using orbfe_resolve::MatchQuery;
 using orbfe_resolve::TH_HIGH;
 using orbfe_resolve::TH_LOW;
-
-struct Projection {
-    Camera C;
-    float sf[ORBFE_MAX_LEVELS];
-    int nlevels;
-    float log_sf;
-    float min_x, max_x, min_y, max_y;
-};
+using orbfe_resolve::View;
 
 // Frame::AssignFeaturesToGrid in one workgroup: count, scan and fill over LDS counters
 __global__ __launch_bounds__(1024) void grid_build_kernel(GridFrame f)
@@ -111,7 +105,7 @@ struct WindowRow {
 // ---- projection: where a query comes from.  The window kernel asks for query i (every lane of its wave states the same
 // arithmetic), so the matchers need no launch of their own for it ----
 struct LastSource { // SearchByProjection(CurrentFrame, LastFrame, th, bMono)
-    Projection P;
+    View V;
     const float *Tcw_cur, *Tcw_last, *pos;
     const int32_t *valid, *octave;
     float th;
@@ -122,16 +116,15 @@ struct LastSource { // SearchByProjection(CurrentFrame, LastFrame, th, bMono)
         float Tc[12], Tl[12];
         for (int k = 0; k < 12; k++) { Tc[k] = Tcw_cur[k]; Tl[k] = Tcw_last[k]; }
         bool forward, backward;
-        orbfe_resolve::last_motion(P.C, Tc, Tl, mono, forward, backward);
+        orbfe_resolve::last_motion(V.C, Tc, Tl, mono, forward, backward);
         MatchQuery Q = {0, 0, 0, 0, -1, 0, 0, 0};
         const float p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]};
-        if (orbfe_resolve::query_last_point(P.C, P.sf, P.nlevels, P.min_x, P.max_x, P.min_y, P.max_y, Tc, forward, backward, p, valid[i], octave[i], th, Q) < 0)
-            Q.flags = Q_BAD;
+        if (orbfe_resolve::query_last_point(V, Tc, forward, backward, p, valid[i], octave[i], th, Q) < 0) Q.flags = Q_BAD;
         return Q;
     }
 };
 struct PointsSource { // SearchByProjection(F, vpMapPoints, th)
-    Projection P;
+    View V;
     const orbfe_track_point *pts;
     float th;
     __device__ __forceinline__ const PointsSource &row(int, WindowRow &) const { return *this; }
@@ -139,45 +132,27 @@ struct PointsSource { // SearchByProjection(F, vpMapPoints, th)
     {
         MatchQuery Q = {0, 0, 0, 0, -1, 0, 0, 0};
         const orbfe_track_point pt = pts[i];
-        if (orbfe_resolve::query_track_point(P.sf, P.nlevels, pt, th, Q) < 0) Q.flags = Q_BAD;
+        if (orbfe_resolve::query_track_point(V.sf, V.nlevels, pt, th, Q) < 0) Q.flags = Q_BAD;
         return Q;
     }
 };
 
 struct ResolveArgs;
-// SearchByProjection(pKF, Scw, vpPoints, vpMatched, th): the point table of orbfe_enqueue_fuse_sim3 -- rows, optionally read through an
-// index list -- as both kernels of the matcher need it
-struct Sim3Points {
-    const int32_t *pt_index;
-    int n_rows;
-    const uint8_t *pt_desc;
+// SearchByProjection(pKF, Scw, vpPoints, vpMatched, th): the point table (orbfe_match_window.hpp) as both kernels of the matcher need it
+struct Sim3Points : PointTable {
     int nlevels;
     int32_t *pt_match; // [n_pts] the keypoint query q took, or -1
-    // the row of query q, tested before it addresses the table; -1: outside [0, n_rows)
-    __device__ __forceinline__ int row(int q) const
-    {
-        if (!pt_index) return q; // n_rows >= n_pts: the call checked it
-        const int r = pt_index[q];
-        return (r < 0 || r >= n_rows) ? -1 : r;
-    }
-    __device__ __forceinline__ const uint8_t *desc(int q) const // only followed for a query with a window, whose row is good
-    {
-        const int r = row(q);
-        return pt_desc + (size_t)(r < 0 ? 0 : r) * 32;
-    }
     __device__ __forceinline__ void resolve(int, ResolveArgs &) const {}
 };
 struct Sim3Source {
-    Projection P; // with the keyframe's bounds
+    View V; // with the keyframe's bounds
     Sim3Points pts;
-    int keyframe, kf_n;
+    int kf_n;
     float T[12], ow[3]; // [R|t] of the decomposed Scw and the camera centre, both computed on the host
-    const float *pos, *normal, *max_distance, *min_distance;
-    const int32_t *pt_valid;
     float th;
     __device__ __forceinline__ const Sim3Source &row(int, WindowRow &) const { return *this; }
     __device__ __forceinline__ const uint8_t *desc(int q) const { return pts.desc(q); }
-    __device__ __forceinline__ int nlevels() const { return P.nlevels; }
+    __device__ __forceinline__ int nlevels() const { return V.nlevels; }
     __device__ __forceinline__ MatchQuery query(int q) const
     {
         MatchQuery Q = {0, 0, 0, 0, -1, 0, 0, 0};
@@ -185,16 +160,15 @@ struct Sim3Source {
         const int row = pts.row(q);
         if (row < 0) { Q.flags = Q_BAD; return Q; }
         float ur; // not used by this matcher
-        const float p[3] = {pos[3 * (size_t)row], pos[3 * (size_t)row + 1], pos[3 * (size_t)row + 2]};
-        const float nr[3] = {normal[3 * (size_t)row], normal[3 * (size_t)row + 1], normal[3 * (size_t)row + 2]};
+        const float p[3] = {pts.pos[3 * (size_t)row], pts.pos[3 * (size_t)row + 1], pts.pos[3 * (size_t)row + 2]};
+        const float nr[3] = {pts.normal[3 * (size_t)row], pts.normal[3 * (size_t)row + 1], pts.normal[3 * (size_t)row + 2]};
         // exactly as sim3_projection_impl mode 0 (orbfe_match.hip) calls it
-        orbfe_resolve::query_fuse_point(P.C, P.sf, P.nlevels, P.log_sf, P.min_x, P.max_x, P.min_y, P.max_y, keyframe, T, ow, 0, p, nr, pt_valid[q],
-                                        max_distance[row], min_distance[row], th, Q, &ur);
+        orbfe_resolve::query_fuse_point(V, T, ow, 0, p, nr, pts.pt_valid[q], pts.max_distance[row], pts.min_distance[row], th, Q, &ur);
         return Q;
     }
 };
 
-__global__ __launch_bounds__(256) void frustum_kernel(Projection P, const float *__restrict__ Tcw, int n, const float *__restrict__ pos,
+__global__ __launch_bounds__(256) void frustum_kernel(View V, const float *__restrict__ Tcw, int n, const float *__restrict__ pos,
                                                       const float *__restrict__ normal, const float *__restrict__ max_distance,
                                                       const float *__restrict__ min_distance, float viewing_cos_limit, orbfe_track_point *__restrict__ out)
 {
@@ -205,7 +179,7 @@ __global__ __launch_bounds__(256) void frustum_kernel(Projection P, const float 
     orbfe_resolve::camera_center(T, ow);
     const float p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]}, nr[3] = {normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]};
     orbfe_track_point o;
-    orbfe_resolve::frustum_point(P.C, P.nlevels, P.log_sf, T, ow, P.min_x, P.max_x, P.min_y, P.max_y, p, nr, max_distance[i], min_distance[i], viewing_cos_limit, o);
+    orbfe_resolve::frustum_point(V, T, ow, p, nr, max_distance[i], min_distance[i], viewing_cos_limit, o);
     out[i] = o;
 }
 
@@ -510,7 +484,7 @@ __global__ __launch_bounds__(256) void gather_kernel(GridFrame f, GatherRow g, R
 // The candidates of one call: a device array of records, or (cands == null) the single call's record by value.  Row c of every
 // scratch array belongs to candidate c: found / q / topk / n_static / ev [n_cands][max_n], held [n_cands][cap], err [n_cands].
 struct KfRowSource { // one candidate as the window kernel's source
-    const Projection &P;
+    const View &V;
     orbfe_reloc_candidate rec;
     const uint8_t *found;
     __device__ __forceinline__ MatchQuery query(int i) const
@@ -520,13 +494,12 @@ struct KfRowSource { // one candidate as the window kernel's source
         orbfe_resolve::camera_center(Tc, ow);
         MatchQuery Q = {0, 0, 0, 0, -1, 0, 0, 0};
         const float p[3] = {rec.pos[3 * i], rec.pos[3 * i + 1], rec.pos[3 * i + 2]};
-        orbfe_resolve::query_kf_point(P.C, P.sf, P.nlevels, P.log_sf, P.min_x, P.max_x, P.min_y, P.max_y, Tc, ow, p, rec.valid[i] && !found[i],
-                                      rec.max_distance[i], rec.min_distance[i], rec.th, Q);
+        orbfe_resolve::query_kf_point(V, Tc, ow, p, rec.valid[i] && !found[i], rec.max_distance[i], rec.min_distance[i], rec.th, Q);
         return Q;
     }
 };
 struct KfBatch {
-    Projection P;
+    View V;
     const orbfe_reloc_candidate *cands;
     orbfe_reloc_candidate one;
     int max_n, cap, exclude_held;
@@ -553,7 +526,7 @@ struct KfBatch {
     __device__ __forceinline__ KfRowSource row(int c, WindowRow &w) const
     {
         bool refused;
-        const KfRowSource s = {P, record(c, refused), found + (size_t)c * max_n};
+        const KfRowSource s = {V, record(c, refused), found + (size_t)c * max_n};
         w.q = q + (size_t)c * max_n; w.topk = topk + (size_t)c * max_n * TOPK; w.n_static = n_static + (size_t)c * max_n;
         w.qdesc = s.rec.desc; w.nq = s.rec.n;
         w.blocked0 = held + (size_t)c * cap;
@@ -639,20 +612,9 @@ int32_t *orbfe_ctx_sim3_scratch(orbfe_context *ctx, size_t n)
     return (int32_t *)st->sim3.p;
 }
 
-#define DTRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return orbfe_fail(ctx, ORBFE_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
 
-static Projection projection_of(orbfe_context *ctx, const float *bounds)
-{
-    const orbfe_params *P = orbfe_ctx_params(ctx);
-    Projection p;
-    p.C = orbfe_resolve::camera_of(P);
-    const float *sf = orbfe_ctx_scale_factors(ctx);
-    for (int l = 0; l < ORBFE_MAX_LEVELS; l++) p.sf[l] = l < P->nlevels ? sf[l] : 0.f;
-    p.nlevels = P->nlevels;
-    p.log_sf = logf((float)(double)P->scale_factor); // mfLogScaleFactor = log(mfScaleFactor), src/Frame.cc:71
-    p.min_x = bounds[0]; p.max_x = bounds[1]; p.min_y = bounds[2]; p.max_y = bounds[3];
-    return p;
-}
+// a Frame's view: its bounds are the floats they are given as
+static View frame_view(orbfe_context *ctx, const float *bounds) { return orbfe_view(ctx, bounds[0], bounds[1], bounds[2], bounds[3], 0); }
 
 // Common entry work of the calls on a resident slot: argument checks, stream order, mvKeysUn.  No host wait.
 static int resident_frame(orbfe_context *ctx, int slot, hipStream_t s, orbfe_match_device_state *&st, const KeyPointPOD *&keys)
@@ -664,7 +626,7 @@ static int resident_frame(orbfe_context *ctx, int slot, hipStream_t s, orbfe_mat
     if (cfg->sel_total > 65535) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "frames with more than 65535 keypoints are not supported by the matchers");
     st = orbfe_ctx_match_device_state(ctx);
     if (!st) return orbfe_fail(ctx, ORBFE_ERR_HIP, "out of host memory");
-    DTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     const unsigned epoch = orbfe_ctx_epoch(ctx);
     const int rc = orbfe_ctx_order_after_extraction(ctx, s); // an event wait on the stream, no host wait
     if (rc != ORBFE_OK) return rc;
@@ -750,7 +712,7 @@ static int enqueue_window_resolve(orbfe_context *ctx, orbfe_match_device_state *
         const GatherRow g = {d_cur_match, d_pos, nullptr, d_has_point, d_Xw};
         hipLaunchKernelGGL(gather_kernel<OneRow>, dim3((f.cap + 255) / 256), dim3(256), 0, s, f, g, OneRow());
     }
-    DTRY(ctx, hipGetLastError());
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
     return ORBFE_OK;
 }
 
@@ -769,7 +731,7 @@ static int enqueue_kf(orbfe_context *ctx, int slot, const float *bounds, const o
     if (st->found.ensure(rows ? rows : 1) || st->held.ensure((size_t)n_cands * f.cap) || st->err.ensure(sizeof(int32_t) * (size_t)n_cands))
         return orbfe_fail(ctx, ORBFE_ERR_HIP, "matcher scratch allocation failed");
     KfBatch b;
-    b.P = projection_of(ctx, bounds);
+    b.V = frame_view(ctx, bounds);
     b.cands = d_cands; b.one = one; b.max_n = max_n; b.cap = f.cap; b.exclude_held = exclude_held != 0;
     b.found = (uint8_t *)st->found.p; b.held = (uint8_t *)st->held.p; b.err = (int32_t *)st->err.p;
     b.q = (MatchQuery *)st->q.p; b.topk = (unsigned long long *)st->topk.p; b.n_static = (int *)st->n_static.p; b.ev = (int32_t *)st->ev.p;
@@ -781,7 +743,7 @@ static int enqueue_kf(orbfe_context *ctx, int slot, const float *bounds, const o
     a.f = f; a.points = 0; a.check_ori = check_ori != 0; a.nnratio = 0.f; // obs stays null: every accepted keypoint is closed
     hipLaunchKernelGGL(resolve_kernel<KfBatch>, dim3(n_cands), dim3(RESOLVE_THREADS), 0, s, a, b);
     hipLaunchKernelGGL(gather_kernel<KfBatch>, dim3((f.cap + 255) / 256, n_cands), dim3(256), 0, s, f, GatherRow(), b);
-    DTRY(ctx, hipGetLastError());
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
     return ORBFE_OK;
 }
 
@@ -803,7 +765,7 @@ try {
     if (rc != ORBFE_OK) return rc;
     rc = ensure_query_scratch(ctx, st, n_last);
     if (rc != ORBFE_OK) return rc;
-    const LastSource src = {projection_of(ctx, bounds), d_Tcw_cur, d_Tcw_last, d_last_pos, d_last_valid, d_last_octave, th, mono};
+    const LastSource src = {frame_view(ctx, bounds), d_Tcw_cur, d_Tcw_last, d_last_pos, d_last_valid, d_last_octave, th, mono};
     return enqueue_window_resolve(ctx, st, f, src, n_last, d_last_desc, d_last_obs, d_last_angle, d_cur_has_obs, 0, check_ori != 0, 0.f, d_last_pos,
                                   d_cur_match, d_nmatches, d_status, d_has_point, d_Xw, s);
 } ORBFE_CATCH(ctx)
@@ -818,10 +780,10 @@ try {
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
     if (n == 0) return ORBFE_OK;
     hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    DTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
-    hipLaunchKernelGGL(frustum_kernel, dim3((n + 255) / 256), dim3(256), 0, s, projection_of(ctx, bounds), d_Tcw, n, d_pos, d_normal, d_max_distance,
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    hipLaunchKernelGGL(frustum_kernel, dim3((n + 255) / 256), dim3(256), 0, s, frame_view(ctx, bounds), d_Tcw, n, d_pos, d_normal, d_max_distance,
                        d_min_distance, viewing_cos_limit, d_out);
-    DTRY(ctx, hipGetLastError());
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)
 
@@ -841,7 +803,7 @@ try {
     if (rc != ORBFE_OK) return rc;
     rc = ensure_query_scratch(ctx, st, n_pts);
     if (rc != ORBFE_OK) return rc;
-    const PointsSource src = {projection_of(ctx, bounds), d_pts, th};
+    const PointsSource src = {frame_view(ctx, bounds), d_pts, th};
     return enqueue_window_resolve(ctx, st, f, src, n_pts, d_pt_desc, d_pt_obs, nullptr, d_cur_has_obs, 1, 0, nnratio, d_pt_pos, d_cur_match, d_nmatches,
                                   d_status, d_has_point, d_Xw, s);
 } ORBFE_CATCH(ctx)
@@ -892,31 +854,21 @@ try {
     if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
     ORBFE_ENTRY(ctx);
     if (!kf || !Scw || !d_pt_match || !d_kf_match || !d_nmatches || !d_status) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
-    if (n_pts < 0 || n_rows < 0) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "negative count");
-    if (!d_pt_index && n_rows < n_pts) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "%d queries without an index list over a table of %d rows", n_pts, n_rows);
-    if (n_pts > (1 << 20)) return orbfe_fail(ctx, ORBFE_ERR_CAPACITY, "%d points: the matcher's scratch rows hold 2^20", n_pts);
+    Sim3Source src;
+    src.pts = {{d_pt_index, n_rows, d_pos, d_normal, d_max_distance, d_min_distance, d_pt_desc, d_pt_valid}, orbfe_ctx_params(ctx)->nlevels, d_pt_match};
     GridFrame f;
-    int rc = orbfe_grid_frame_of_record(ctx, kf, f);
+    int rc = orbfe_point_table_frame(ctx, kf, n_pts, 1 << 20, src.pts, f); // the scratch rows hold 2^20 queries
     if (rc != ORBFE_OK) return rc;
+    src.V = orbfe_view(ctx, kf);
     f.u_right = nullptr; // this matcher has no mvuRight gate: kf->u_right is never read
-    if (n_pts > 0 && kf->n > 0 &&
-        (!d_pos || !d_normal || !d_max_distance || !d_min_distance || !d_pt_desc || !d_pt_valid || !kf->keys_un || !kf->desc || !kf->cell_off || !kf->cell_idx))
-        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null array in the point table or in the keyframe record");
-    const orbfe_params *P = orbfe_ctx_params(ctx);
-    if (P->nlevels < 1 || P->nlevels > ORBFE_MAX_LEVELS) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "nlevels = %d", P->nlevels);
     orbfe_match_device_state *st = orbfe_ctx_match_device_state(ctx);
     if (!st) return orbfe_fail(ctx, ORBFE_ERR_HIP, "out of host memory");
-    DTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     rc = ensure_query_scratch(ctx, st, n_pts);
     if (rc != ORBFE_OK) return rc;
-    const float bounds[4] = {kf->min_x, kf->max_x, kf->min_y, kf->max_y};
-    Sim3Source src;
-    src.P = projection_of(ctx, bounds);
-    src.pts = {d_pt_index, n_rows, d_pt_desc, P->nlevels, d_pt_match};
-    src.keyframe = kf->keyframe != 0; src.kf_n = kf->n;
+    src.kf_n = kf->n;
     orbfe_resolve::sim3_to_rt(Scw, src.T);
     orbfe_resolve::camera_center(src.T, src.ow);
-    src.pos = d_pos; src.normal = d_normal; src.max_distance = d_max_distance; src.min_distance = d_min_distance; src.pt_valid = d_pt_valid;
     src.th = th;
     hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
     // one wave per query, and a thread per keypoint for the reset of d_kf_match; neither: the resolve kernel alone writes count and status
@@ -931,7 +883,7 @@ try {
     a.ev = (int32_t *)st->ev.p;
     a.cur_match = d_kf_match; a.nmatches = d_nmatches; a.status = d_status;
     hipLaunchKernelGGL((resolve_kernel<Sim3Points, true>), dim3(1), dim3(RESOLVE_THREADS), 0, s, a, src.pts);
-    DTRY(ctx, hipGetLastError());
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)
 
@@ -945,7 +897,7 @@ try {
     const KeyPointPOD *keys = nullptr;
     const int rc = resident_frame(ctx, slot, s, st, keys);
     if (rc != ORBFE_OK) return rc;
-    DTRY(ctx, hipGetLastError());
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
     *d_keys_un = (const orbfe_keypoint *)keys;
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)

@@ -5,6 +5,7 @@
 // Pure C++ (no HIP, no device types) on purpose: liborbfe.so's orbfe_match.hip includes it for the product path, and
 // tests/asan/resolve_harness.cpp compiles the very same text for the CPU with -fsanitize=address,undefined (GPU ASan does not
 // exist on this pool; the host logic is where the index arithmetic of the matchers lives).
+// What a point is projected against is a View (camera, scale factors, image bounds), built by view_of for host and device alike.
 // The per-point arithmetic (one map point -> one window query, one isInFrustum record, rot_bin, three_maxima) is marked
 // ORBFE_RESOLVE_HD: empty in a plain C++ compile, host + device under hipcc, where orbfe_match_device.hip runs the same
 // statements one lane per map point (device code is compiled without FMA contraction and with IEEE divide / sqrt too).
@@ -26,6 +27,7 @@
 #include <vector>
 
 #include "../../include/orbfe.h"
+#include "orbfe_config.h" // ORBFE_MAX_LEVELS
 
 #ifdef __HIPCC__
 #define ORBFE_RESOLVE_HD __attribute__((host, device))
@@ -49,6 +51,31 @@ static inline Camera camera_of(const orbfe_params *P)
 {
     Camera c = {P->fx, P->fy, P->cx, P->cy, P->bf, P->fx != 0.f ? P->bf / P->fx : 0.f}; // mb := mbf / fx
     return c;
+}
+// A view: the camera with the scale pyramid and the image bounds a map point is projected against.  `keyframe`: the bounds are a
+// KeyFrame's, which KeyFrame::IsInImage truncates to ints (kf_is_in_image).
+// The per-point functions bind the scalars they use to locals at their head: a kernel's view lies in its kernel-argument segment,
+// and a read at first use would wait for it in the middle of the function.
+struct View {
+    Camera C;
+    float sf[ORBFE_MAX_LEVELS]; // mvScaleFactors
+    int nlevels;
+    float log_sf;
+    float min_x, max_x, min_y, max_y;
+    int keyframe;
+};
+// scale_factors: the context's mvScaleFactors, nlevels of them.  The levels past nlevels hold 1 and are never read: every octave or
+// level is range-tested or clamped to [0, nlevels) before it indexes sf.
+static inline View view_of(const orbfe_params *P, const float *scale_factors, float min_x, float max_x, float min_y, float max_y, int keyframe)
+{
+    View V;
+    V.C = camera_of(P);
+    for (int l = 0; l < ORBFE_MAX_LEVELS; l++) V.sf[l] = l < P->nlevels ? scale_factors[l] : 1.f;
+    V.nlevels = P->nlevels;
+    V.log_sf = logf((float)(double)P->scale_factor); // mfLogScaleFactor = log(mfScaleFactor), src/Frame.cc:71
+    V.min_x = min_x; V.max_x = max_x; V.min_y = min_y; V.max_y = max_y;
+    V.keyframe = keyframe;
+    return V;
 }
 
 // ---- projection arithmetic of the matchers: the reference's float expressions in its evaluation order (contract Q4: no FMA
@@ -104,12 +131,13 @@ ORBFE_RESOLVE_HD static inline void last_motion(const Camera &C, const float *Tc
     backward = -tlc[2] > C.mb && !mono;
 }
 // ... and the loop body for one map point of the last frame.  Q must hold NO_QUERY; returns -1 on a bad octave.
-ORBFE_RESOLVE_HD static inline int query_last_point(const Camera &C, const float *sf, int nlevels, float min_x, float max_x, float min_y, float max_y,
-                                                    const float *Tcw_cur, bool forward, bool backward, const float *pos, int valid, int octave, float th,
-                                                    MatchQuery &Q)
+ORBFE_RESOLVE_HD static inline int query_last_point(const View &V, const float *Tcw_cur, bool forward, bool backward, const float *pos, int valid,
+                                                    int octave, float th, MatchQuery &Q)
 {
+    const Camera &C = V.C;
+    const float min_x = V.min_x, max_x = V.max_x, min_y = V.min_y, max_y = V.max_y;
     if (!valid) return 0;
-    if (octave < 0 || octave >= nlevels) return -1;
+    if (octave < 0 || octave >= V.nlevels) return -1;
     float xc[3];
     rt_apply(Tcw_cur, pos, xc);
     const float invzc = (float)(1.0 / (double)xc[2]);
@@ -119,7 +147,7 @@ ORBFE_RESOLVE_HD static inline int query_last_point(const Camera &C, const float
     if (u < min_x || u > max_x) return 0;
     if (v < min_y || v > max_y) return 0;
     const int oct = octave;
-    const float radius = th * sf[oct];
+    const float radius = th * V.sf[oct];
     Q.u = u; Q.v = v; Q.r = radius; Q.flags = 1 | 2;
     Q.ur = u - C.bf * invzc; Q.ur_rad = radius;
     if (forward) { Q.min_level = oct; Q.max_level = -1; }
@@ -128,18 +156,16 @@ ORBFE_RESOLVE_HD static inline int query_last_point(const Camera &C, const float
     return 1;
 }
 // Returns -1 on a bad octave.
-static inline int build_queries_last(const Camera &C, const float *sf, int nlevels, float min_x, float max_x, float min_y, float max_y,
-                                     const float *Tcw_cur, const float *Tcw_last, int n_last, const float *last_pos, const uint8_t *last_desc,
+static inline int build_queries_last(const View &V, const float *Tcw_cur, const float *Tcw_last, int n_last, const float *last_pos, const uint8_t *last_desc,
                                      const int32_t *last_valid, const int32_t *last_octave, float th, int mono, std::vector<MatchQuery> &q,
                                      std::vector<uint8_t> &qd)
 {
     bool forward, backward;
-    last_motion(C, Tcw_cur, Tcw_last, mono, forward, backward);
+    last_motion(V.C, Tcw_cur, Tcw_last, mono, forward, backward);
     q.assign(n_last > 0 ? n_last : 0, NO_QUERY);
     qd.assign((size_t)32 * (n_last > 0 ? n_last : 1), 0);
     for (int i = 0; i < n_last; i++) {
-        const int rc = query_last_point(C, sf, nlevels, min_x, max_x, min_y, max_y, Tcw_cur, forward, backward, last_pos + 3 * i, last_valid[i],
-                                        last_octave[i], th, q[i]);
+        const int rc = query_last_point(V, Tcw_cur, forward, backward, last_pos + 3 * i, last_valid[i], last_octave[i], th, q[i]);
         if (rc < 0) return -1;
         if (rc > 0) memcpy(&qd[(size_t)32 * i], last_desc + (size_t)32 * i, 32);
     }
@@ -178,10 +204,13 @@ static inline int build_queries_points(const float *sf, int nlevels, int n_pts, 
 // ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist), src/ORBmatcher.cc:1484-1527: the loop body for one
 // map point of the keyframe (ow = camera_center(Tcw_cur); valid = pMP && !pMP->isBad() && !sAlreadyFound.count(pMP)).
 // Q must hold NO_QUERY; returns 1 when the point opens a window.
-ORBFE_RESOLVE_HD static inline int query_kf_point(const Camera &C, const float *sf, int nlevels, float log_sf, float min_x, float max_x, float min_y,
-                                                  float max_y, const float *Tcw_cur, const float *ow, const float *pos, int valid, float max_distance,
+ORBFE_RESOLVE_HD static inline int query_kf_point(const View &V, const float *Tcw_cur, const float *ow, const float *pos, int valid, float max_distance,
                                                   float min_distance, float th, MatchQuery &Q)
 {
+    const Camera &C = V.C;
+    const int nlevels = V.nlevels;
+    const float log_sf = V.log_sf;
+    const float min_x = V.min_x, max_x = V.max_x, min_y = V.min_y, max_y = V.max_y;
     if (!valid) return 0;
     float xc[3];
     rt_apply(Tcw_cur, pos, xc);
@@ -195,11 +224,10 @@ ORBFE_RESOLVE_HD static inline int query_kf_point(const Camera &C, const float *
     const float dist3d = norm3(po);
     if (dist3d < 0.8f * min_distance || dist3d > 1.2f * max_distance) return 0;
     const int lvl = predict_scale(max_distance, dist3d, log_sf, nlevels);
-    Q.u = u; Q.v = v; Q.r = th * sf[lvl]; Q.min_level = lvl - 1; Q.max_level = lvl + 1; Q.flags = 1;
+    Q.u = u; Q.v = v; Q.r = th * V.sf[lvl]; Q.min_level = lvl - 1; Q.max_level = lvl + 1; Q.flags = 1;
     return 1;
 }
-static inline void build_queries_kf(const Camera &C, const float *sf, int nlevels, float log_sf, float min_x, float max_x, float min_y, float max_y,
-                                    const float *Tcw_cur, int n_kf, const float *kf_pos, const uint8_t *kf_desc, const int32_t *kf_valid,
+static inline void build_queries_kf(const View &V, const float *Tcw_cur, int n_kf, const float *kf_pos, const uint8_t *kf_desc, const int32_t *kf_valid,
                                     const float *kf_max_distance, const float *kf_min_distance, float th, std::vector<MatchQuery> &q,
                                     std::vector<uint8_t> &qd)
 {
@@ -208,8 +236,7 @@ static inline void build_queries_kf(const Camera &C, const float *sf, int nlevel
     q.assign(n_kf > 0 ? n_kf : 0, NO_QUERY);
     qd.assign((size_t)32 * (n_kf > 0 ? n_kf : 1), 0);
     for (int i = 0; i < n_kf; i++)
-        if (query_kf_point(C, sf, nlevels, log_sf, min_x, max_x, min_y, max_y, Tcw_cur, ow, kf_pos + 3 * i, kf_valid[i], kf_max_distance[i],
-                           kf_min_distance[i], th, q[i]) > 0)
+        if (query_kf_point(V, Tcw_cur, ow, kf_pos + 3 * i, kf_valid[i], kf_max_distance[i], kf_min_distance[i], th, q[i]) > 0)
             memcpy(&qd[(size_t)32 * i], kf_desc + (size_t)32 * i, 32);
 }
 
@@ -222,20 +249,22 @@ static inline void sim3_to_rt(const float *Scw, float *T)
     for (int i = 0; i < 12; i++) T[i] = Scw[i] * alpha;
 }
 // KeyFrame::IsInImage (src/KeyFrame.cc:604-607): a keyframe's bounds are ints initialised from the frame's floats
-ORBFE_RESOLVE_HD static inline bool kf_is_in_image(float min_x, float max_x, float min_y, float max_y, int keyframe, float u, float v)
+ORBFE_RESOLVE_HD static inline bool kf_is_in_image(const View &V, float u, float v)
 {
-    if (keyframe) return u >= (float)(int)min_x && u < (float)(int)max_x && v >= (float)(int)min_y && v < (float)(int)max_y;
+    const float min_x = V.min_x, max_x = V.max_x, min_y = V.min_y, max_y = V.max_y;
+    if (V.keyframe) return u >= (float)(int)min_x && u < (float)(int)max_x && v >= (float)(int)min_y && v < (float)(int)max_y;
     return u >= min_x && u < max_x && v >= min_y && v < max_y;
 }
 // ORBmatcher::Fuse(pKF, vpMapPoints, th), src/ORBmatcher.cc:821-971, and the Sim3 matchers of LoopClosing (SearchByProjection :285-398
 // and Fuse :973-1096, T and ow from the decomposed Scw): the loop body for one map point up to GetFeaturesInArea.  The three loops differ in one statement: the
 // Sim3 Fuse takes the reciprocal of the depth in double (`double_recip`); their depth tests, float or double, are the same test.
 // Q must hold NO_QUERY; returns 1 when the point opens a window, and then *ur is the projection into the right image (u - bf / z).
-ORBFE_RESOLVE_HD static inline int query_fuse_point(const Camera &C, const float *sf, int nlevels, float log_sf, float min_x, float max_x, float min_y,
-                                                    float max_y, int keyframe, const float *T, const float *ow, int double_recip, const float *pos,
-                                                    const float *normal, int valid, float max_distance, float min_distance, float th, MatchQuery &Q,
-                                                    float *ur)
+ORBFE_RESOLVE_HD static inline int query_fuse_point(const View &V, const float *T, const float *ow, int double_recip, const float *pos, const float *normal,
+                                                    int valid, float max_distance, float min_distance, float th, MatchQuery &Q, float *ur)
 {
+    const Camera &C = V.C;
+    const int nlevels = V.nlevels;
+    const float log_sf = V.log_sf;
     if (!valid) return 0;
     float pc[3];
     rt_apply(T, pos, pc);
@@ -244,7 +273,7 @@ ORBFE_RESOLVE_HD static inline int query_fuse_point(const Camera &C, const float
     const float x = pc[0] * invz, y = pc[1] * invz;
     const float u = C.fx * x + C.cx;
     const float v = C.fy * y + C.cy;
-    if (!kf_is_in_image(min_x, max_x, min_y, max_y, keyframe, u, v)) return 0;
+    if (!kf_is_in_image(V, u, v)) return 0;
     float po[3];
     for (int k = 0; k < 3; k++) po[k] = pos[k] - ow[k];
     const float dist3d = norm3(po);
@@ -252,17 +281,18 @@ ORBFE_RESOLVE_HD static inline int query_fuse_point(const Camera &C, const float
     const double dot = (double)po[0] * normal[0] + (double)po[1] * normal[1] + (double)po[2] * normal[2];
     if (dot < 0.5 * (double)dist3d) return 0;
     const int lvl = predict_scale(max_distance, dist3d, log_sf, nlevels);
-    Q.u = u; Q.v = v; Q.r = th * sf[lvl]; Q.min_level = lvl - 1; Q.max_level = lvl; Q.flags = 1;
+    Q.u = u; Q.v = v; Q.r = th * V.sf[lvl]; Q.min_level = lvl - 1; Q.max_level = lvl; Q.flags = 1;
     *ur = u - C.bf * invz;
     return 1;
 }
 // One direction of ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1143-1216 / 1218-1291): the loop body for one map point of keyframe A
-// up to GetFeaturesInArea on keyframe B.  Taw moves the point into camera A, sRt = [sR|t] from there into camera B; the bounds and
-// `keyframe` are B's.  valid = pMP && !pMP->isBad() && not already matched.  Q must hold NO_QUERY; returns 1 when the point opens a window.
-ORBFE_RESOLVE_HD static inline int query_sim3_point(const Camera &C, const float *sf, int nlevels, float log_sf, float min_x, float max_x, float min_y,
-                                                    float max_y, int keyframe, const float *Taw, const float *sRt, const float *pos, int valid,
-                                                    float max_distance, float min_distance, float th, MatchQuery &Q)
+// up to GetFeaturesInArea on keyframe B.  Taw moves the point into camera A, sRt = [sR|t] from there into camera B; the view is B's.  valid = pMP && !pMP->isBad() && not already matched.  Q must hold NO_QUERY; returns 1 when the point opens a window.
+ORBFE_RESOLVE_HD static inline int query_sim3_point(const View &V, const float *Taw, const float *sRt, const float *pos, int valid, float max_distance,
+                                                    float min_distance, float th, MatchQuery &Q)
 {
+    const Camera &C = V.C;
+    const int nlevels = V.nlevels;
+    const float log_sf = V.log_sf;
     if (!valid) return 0;
     float pa[3], pb[3];
     rt_apply(Taw, pos, pa);
@@ -271,11 +301,11 @@ ORBFE_RESOLVE_HD static inline int query_sim3_point(const Camera &C, const float
     const float invz = (float)(1.0 / (double)pb[2]);
     const float x = pb[0] * invz, y = pb[1] * invz;
     const float u = C.fx * x + C.cx, v = C.fy * y + C.cy;
-    if (!kf_is_in_image(min_x, max_x, min_y, max_y, keyframe, u, v)) return 0;
+    if (!kf_is_in_image(V, u, v)) return 0;
     const float dist = norm3(pb);
     if (dist < 0.8f * min_distance || dist > 1.2f * max_distance) return 0;
     const int lvl = predict_scale(max_distance, dist, log_sf, nlevels);
-    Q.u = u; Q.v = v; Q.r = th * sf[lvl]; Q.min_level = lvl - 1; Q.max_level = lvl; Q.flags = 1;
+    Q.u = u; Q.v = v; Q.r = th * V.sf[lvl]; Q.min_level = lvl - 1; Q.max_level = lvl; Q.flags = 1;
     return 1;
 }
 // sR12 = s12 * R12; sR21 = (1.0 / s12) * R12.t(); t21 = -sR21 * t12 (src/ORBmatcher.cc:1116-1119) as two [sR|t] rows of 4
@@ -322,10 +352,13 @@ static inline void build_queries_initialization(int n1, const orbfe_keypoint *ke
 }
 
 // Frame::isInFrustum, src/Frame.cc:256-315, for one map point (ow = camera_center(Tcw))
-ORBFE_RESOLVE_HD static inline void frustum_point(const Camera &C, int nlevels, float log_sf, const float *Tcw, const float *ow, float min_x, float max_x,
-                                                  float min_y, float max_y, const float *pos, const float *normal, float max_distance, float min_distance,
-                                                  float viewing_cos_limit, orbfe_track_point &o)
+ORBFE_RESOLVE_HD static inline void frustum_point(const View &V, const float *Tcw, const float *ow, const float *pos, const float *normal, float max_distance,
+                                                  float min_distance, float viewing_cos_limit, orbfe_track_point &o)
 {
+    const Camera &C = V.C;
+    const int nlevels = V.nlevels;
+    const float log_sf = V.log_sf;
+    const float min_x = V.min_x, max_x = V.max_x, min_y = V.min_y, max_y = V.max_y;
     o.in_view = 0; o.proj_x = o.proj_y = o.proj_xr = 0.f; o.level = 0; o.view_cos = 0.f;
     float pc[3];
     rt_apply(Tcw, pos, pc);
@@ -348,15 +381,13 @@ ORBFE_RESOLVE_HD static inline void frustum_point(const Camera &C, int nlevels, 
     o.view_cos = view_cos;
 }
 // ... and for n of them
-static inline void is_in_frustum(const Camera &C, int nlevels, float log_sf, const float *Tcw, float min_x, float max_x, float min_y, float max_y, int n,
-                                 const float *pos, const float *normal, const float *max_distance, const float *min_distance,
-                                 float viewing_cos_limit, orbfe_track_point *out)
+static inline void is_in_frustum(const View &V, const float *Tcw, int n, const float *pos, const float *normal, const float *max_distance,
+                                 const float *min_distance, float viewing_cos_limit, orbfe_track_point *out)
 {
     float ow[3];
     camera_center(Tcw, ow);
     for (int i = 0; i < n; i++)
-        frustum_point(C, nlevels, log_sf, Tcw, ow, min_x, max_x, min_y, max_y, pos + 3 * i, normal + 3 * i, max_distance[i], min_distance[i],
-                      viewing_cos_limit, out[i]);
+        frustum_point(V, Tcw, ow, pos + 3 * i, normal + 3 * i, max_distance[i], min_distance[i], viewing_cos_limit, out[i]);
 }
 
 enum { HISTO_LENGTH = 30, TH_LOW = 50, TH_HIGH = 100, TOPK = 4 };

@@ -4,11 +4,13 @@
 // (resolution on the device) both include it, so every statement of the bit-exactness contracts -- Q4 (no FMA contraction, no
 // fast-math), Q5 (the level check), Q6 (round(), column 64 dropped) -- and the key layout
 //      dist << 36 | ix << 30 | iy << 24 | idx << 8 | octave        (dist 511: failed the mvuRight gate)
-// exists once.  Only __device__ __forceinline__ functions, structs and constants: the library has no relocatable device code, so
+// exists once; so do the view of a context (orbfe_view), the table of candidate map points of the keyframe-side matchers (PointTable)
+// and their search without greedy state (wave_best_key).  Only __device__ __forceinline__ functions, host helpers, structs and constants: the library has no relocatable device code, so
 // the one kernel over these (grid_build_kernel, orbfe_match_device.hip) is reached through orbfe_launch_grid_build.
 #pragma once
 
 #include "orbfe_common.hpp"
+#include "orbfe_host.h"
 #include "orbfe_match_resolve.h"
 
 #define GRID_COLS 64 // FRAME_GRID_COLS include/Frame.h:36
@@ -39,6 +41,42 @@ static inline void grid_frame_geometry(GridFrame &f, float min_x, float max_x, f
     f.q_min_x = keyframe ? (float)(int)min_x : min_x;
     f.q_min_y = keyframe ? (float)(int)min_y : min_y;
 }
+
+// The context's view (orbfe_match_resolve.h) with these bounds, or with those of a frame view / keyframe record
+static inline orbfe_resolve::View orbfe_view(orbfe_context *ctx, float min_x, float max_x, float min_y, float max_y, int keyframe)
+{
+    return orbfe_resolve::view_of(orbfe_ctx_params(ctx), orbfe_ctx_scale_factors(ctx), min_x, max_x, min_y, max_y, keyframe);
+}
+template <class Record> // orbfe_frame_view, orbfe_grid_keyframe
+static inline orbfe_resolve::View orbfe_view(orbfe_context *ctx, const Record *r)
+{
+    return orbfe_view(ctx, r->min_x, r->max_x, r->min_y, r->max_y, r->keyframe != 0);
+}
+
+// The table of candidate map points of Fuse and of the Sim3 SearchByProjection on a keyframe record: n_rows rows in device memory,
+// query q reading row q or, through an index list, row pt_index[q].  pt_valid is per query, everything else per row.
+struct PointTable {
+    const int32_t *pt_index; // null: query q is row q (n_rows >= the query count: the call checked it)
+    int n_rows;
+    const float *pos, *normal, *max_distance, *min_distance;
+    const uint8_t *pt_desc;
+    const int32_t *pt_valid;
+    // the row of query q, tested before it addresses the table; -1: outside [0, n_rows)
+    __device__ __forceinline__ int row(int q) const
+    {
+        if (!pt_index) return q;
+        const int r = pt_index[q];
+        return (r < 0 || r >= n_rows) ? -1 : r;
+    }
+    __device__ __forceinline__ const uint8_t *desc(int q) const // only followed for a query with a window, whose row is good
+    {
+        const int r = row(q);
+        return pt_desc + (size_t)(r < 0 ? 0 : r) * 32;
+    }
+};
+// What a call refuses about n_pts queries over table t against keyframe record kf (max_pts: what its scratch holds), and kf as the
+// kernels read it (orbfe_fuse_device.hip)
+int orbfe_point_table_frame(orbfe_context *ctx, const orbfe_grid_keyframe *kf, int n_pts, int max_pts, const PointTable &t, GridFrame &f);
 
 __device__ __forceinline__ int frame_count(const GridFrame &f)
 {
@@ -143,6 +181,33 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long w)
         w = t < w ? t : w;
     }
     return w;
+}
+
+// Search without greedy state (Fuse, SearchBySim3: the points do not interact), one wave per query over a caller's keyframe record:
+// the checked walk of Q's window (n, nlevels as for_each_hit), gate(idx, kp) per hit, and the wave's smallest key = the reference
+// loop's first minimum (NO_KEY: none).  clean: the walk of every lane was.  Whole waves call it.
+template <class Gate>
+__device__ __forceinline__ unsigned long long wave_best_key(const GridFrame &f, const orbfe_resolve::MatchQuery &Q, const uint8_t *qdesc, int lane, Gate gate, int n,
+                                                            int nlevels, bool &clean)
+{
+    unsigned long long best = NO_KEY;
+    bool ok = true;
+    const Window w = query_window(f, Q);
+    if (w.ncells > 0) {
+        uint32_t qd[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) qd[k] = ((const uint32_t *)qdesc)[k];
+        ok = for_each_hit<true>(
+            f, Q, w, lane,
+            [&](int ix, int iy, int idx, const KeyPointPOD &kp) {
+                if (!gate(idx, kp)) return; // kp.octave lies in [0, nlevels): the checked walk has tested it
+                const unsigned long long key = candidate_key(f, Q, qd, ix, iy, idx, kp);
+                if (key < best) best = key;
+            },
+            n, nlevels);
+    }
+    clean = __all(ok) != 0;
+    return wave_min_u64(best);
 }
 
 // The four smallest keys a lane has seen, ascending, in registers; the wave merges its lanes' four by four pops: any window size

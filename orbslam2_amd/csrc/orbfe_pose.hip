@@ -698,7 +698,6 @@ void orbfe_pose_state_destroy(orbfe_pose_state *s)
     delete s;
 }
 
-#define PTRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return orbfe_fail(ctx, ORBFE_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
 
 extern "C" int orbfe_enqueue_pose_optimization(orbfe_context *ctx, int n_problems, const int32_t *d_offsets,
                                                const orbfe_keypoint *d_keys_un, const float *d_u_right, const uint8_t *d_has_point,
@@ -713,10 +712,10 @@ try {
     orbfe_pose_state *st = orbfe_ctx_pose_state(ctx);
     hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
     const orbfe_params *p = orbfe_ctx_params(ctx);
-    PTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     if (!st->sig.p) { // mvInvLevelSigma2 of the context's pyramid
         if (st->sig.ensure(sizeof(float) * ORBFE_MAX_LEVELS)) return orbfe_fail(ctx, ORBFE_ERR_HIP, "pose scratch allocation failed");
-        PTRY(ctx, hipMemcpy(st->sig.p, orbfe_ctx_inv_sigma2(ctx), sizeof(float) * p->nlevels, hipMemcpyHostToDevice));
+        ORBFE_HIP_TRY(ctx, hipMemcpy(st->sig.p, orbfe_ctx_inv_sigma2(ctx), sizeof(float) * p->nlevels, hipMemcpyHostToDevice));
     }
     constexpr int TH = PO_THREADS;
     if (max_keypoints <= PO_LDS_CAP_MAX) {
@@ -725,7 +724,7 @@ try {
         static bool attr_set[64] = {}; // the attribute is per device
         const int dev = orbfe_ctx_device(ctx);
         if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-            PTRY(ctx, hipFuncSetAttribute((const void *)pose_opt_kernel<TH, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pose_lds_bytes<TH>(PO_LDS_CAP_MAX)));
+            ORBFE_HIP_TRY(ctx, hipFuncSetAttribute((const void *)pose_opt_kernel<TH, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pose_lds_bytes<TH>(PO_LDS_CAP_MAX)));
             attr_set[dev] = true;
         }
         hipLaunchKernelGGL((pose_opt_kernel<TH, true>), dim3(n_problems), dim3(TH), lds, s, d_offsets, (const KeyPointPOD *)d_keys_un, d_u_right,
@@ -734,7 +733,7 @@ try {
         hipLaunchKernelGGL((pose_opt_kernel<TH, false>), dim3(n_problems), dim3(TH), pose_lds_bytes<TH>(0), s, d_offsets, (const KeyPointPOD *)d_keys_un,
                            d_u_right, d_has_point, d_Xw, d_Tcw, d_outlier, d_n_inliers, (const float *)st->sig.p, p->fx, p->fy, p->cx, p->cy, p->bf, 0);
     }
-    PTRY(ctx, hipGetLastError());
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)
 
@@ -768,7 +767,7 @@ try {
             return orbfe_fail(ctx, ORBFE_ERR_INVALID, "keypoint %d has octave %d outside the context's %d levels", i, keys_un[i].octave, p->nlevels);
     orbfe_pose_state *st = orbfe_ctx_pose_state(ctx);
     hipStream_t s = orbfe_ctx_stream(ctx);
-    PTRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     const size_t tn = (size_t)(total > 0 ? total : 1);
     // block layout: results first ([Tcw | n_inliers | outlier], copied back in one piece), then the inputs
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
@@ -780,7 +779,7 @@ try {
     if (st->h_bytes < bytes) {
         if (st->h_blk) (void)hipHostFree(st->h_blk);
         st->h_blk = nullptr; st->h_bytes = 0;
-        PTRY(ctx, hipHostMalloc((void **)&st->h_blk, bytes, hipHostMallocDefault));
+        ORBFE_HIP_TRY(ctx, hipHostMalloc((void **)&st->h_blk, bytes, hipHostMallocDefault));
         st->h_bytes = bytes;
     }
     uint8_t *hb = st->h_blk, *db = (uint8_t *)st->blk.p;
@@ -793,13 +792,13 @@ try {
         memcpy(hb + o_has, has_point, tn);
         memcpy(hb + o_xw, Xw, sizeof(float) * 3 * tn);
     }
-    PTRY(ctx, hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, s));
     int rc = orbfe_enqueue_pose_optimization(ctx, n_problems, (const int32_t *)(db + o_off), (const orbfe_keypoint *)(db + o_keys), (const float *)(db + o_ur),
                                              (const uint8_t *)(db + o_has), (const float *)(db + o_xw), (float *)(db + o_T), db + o_out,
                                              (int32_t *)(db + o_n), max_n, nullptr);
     if (rc != ORBFE_OK) return rc;
-    PTRY(ctx, hipMemcpyAsync(hb, db, down, hipMemcpyDeviceToHost, s));
-    PTRY(ctx, hipStreamSynchronize(s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(hb, db, down, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
     // problems with fewer than 3 correspondences leave their pose untouched on the device (the reference returns
     // before SetPose, src/Optimizer.cc:404-405)
     memcpy(Tcw, hb + o_T, sizeof(float) * 16 * n_problems);

@@ -7,9 +7,10 @@
 // comes back over the link.  ComputeSim3 calls the matcher for the same current keyframe once per candidate and RANSAC round; here the
 // keyframes are orbfe_grid_keyframe records whose arrays and grid stay in HBM.  The points do not interact, so the search is
 //   sim3_one_way_kernel   both directions in one launch (blockIdx.y), one wave per keypoint slot of the source keyframe: the point's
-//                         window query (query_sim3_point, orbfe_match_resolve.h: the very text the synchronous call runs on the host),
-//                         GetFeaturesInArea over the target's own grid (orbfe_match_window.hpp), the smallest candidate key of the
-//                         wave = the reference loop's first minimum, accepted at <= TH_HIGH
+//                         window query against the target's View (query_sim3_point, orbfe_match_resolve.h: the very text the
+//                         synchronous call runs on the host), then wave_best_key without a gate (orbfe_match_window.hpp):
+//                         GetFeaturesInArea over the target's own grid, the smallest candidate key of the wave = the reference loop's
+//                         first minimum, accepted at <= TH_HIGH
 //   sim3_agree_kernel     one thread per keypoint of KF1: the agreement check of :1293-1308, d_match12 and the count
 // behind sim3_reset_kernel, which clears the count and the status.  The one-way results live in the context's matcher scratch.
 // The grids and keypoints are the caller's uploads, so the walk is the CHECKED one, as in orbfe_fuse_device.hip.
@@ -21,20 +22,19 @@
 
 #include <algorithm>
 
-using orbfe_resolve::Camera;
 using orbfe_resolve::key_dist;
 using orbfe_resolve::key_idx;
 using orbfe_resolve::MatchQuery;
 using orbfe_resolve::TH_HIGH;
+using orbfe_resolve::View;
 
 int32_t *orbfe_ctx_sim3_scratch(orbfe_context *ctx, size_t n); // orbfe_match_device.hip
 
 struct Sim3Side { // one direction: the map points of keyframe A, one per keypoint slot, searched in keyframe B
-    GridFrame f;                      // B: n_ptr null, cap = its keypoint count
-    float min_x, max_x, min_y, max_y; // B's float bounds ...
-    int keyframe;                     // ... which KeyFrame::IsInImage truncates
-    float Taw[12], sRt[12];           // world -> camera A, and [sR|t] from there into camera B
-    int n;                            // keypoint slots of A
+    GridFrame f;            // B: n_ptr null, cap = its keypoint count
+    View V;                 // with B's bounds
+    float Taw[12], sRt[12]; // world -> camera A, and [sR|t] from there into camera B
+    int n;                  // keypoint slots of A
     const float *pos, *max_distance, *min_distance;
     const uint8_t *desc;
     const int32_t *valid;
@@ -42,10 +42,6 @@ struct Sim3Side { // one direction: the map points of keyframe A, one per keypoi
 };
 struct Sim3Args {
     Sim3Side side[2]; // 0: KF1's points in KF2 (:1143-1216), 1: KF2's points in KF1 (:1218-1291)
-    Camera C;
-    float sf[ORBFE_MAX_LEVELS]; // mvScaleFactors
-    int nlevels;
-    float log_sf;
     float th;
     int32_t *status;
 };
@@ -62,34 +58,17 @@ __global__ __launch_bounds__(256) void sim3_one_way_kernel(Sim3Args a)
     const int lane = threadIdx.x & 63;
     if (i >= S.n) return;
     const int n = S.f.cap;
-    bool bad = false;
+    bool clean = true;
     unsigned long long best = NO_KEY;
     if (n > 0) { // a target without keypoints has no window, and none of its arrays (or the points') is read
         MatchQuery Q = {0, 0, 0, 0, -1, 0, 0, 0};
         const float p[3] = {S.pos[3 * (size_t)i], S.pos[3 * (size_t)i + 1], S.pos[3 * (size_t)i + 2]};
-        orbfe_resolve::query_sim3_point(a.C, a.sf, a.nlevels, a.log_sf, S.min_x, S.max_x, S.min_y, S.max_y, S.keyframe, S.Taw, S.sRt, p, S.valid[i],
-                                        S.max_distance[i], S.min_distance[i], a.th, Q);
-        const Window w = query_window(S.f, Q);
-        if (w.ncells > 0) {
-            uint32_t qd[8];
-            const uint32_t *d = (const uint32_t *)(S.desc + (size_t)i * 32);
-#pragma unroll
-            for (int k = 0; k < 8; k++) qd[k] = d[k];
-            const bool ok = for_each_hit<true>(
-                S.f, Q, w, lane,
-                [&](int ix, int iy, int idx, const KeyPointPOD &kp) {
-                    const unsigned long long key = candidate_key(S.f, Q, qd, ix, iy, idx, kp);
-                    if (key < best) best = key;
-                },
-                n, a.nlevels);
-            bad = !ok;
-        }
+        orbfe_resolve::query_sim3_point(S.V, S.Taw, S.sRt, p, S.valid[i], S.max_distance[i], S.min_distance[i], a.th, Q);
+        best = wave_best_key(S.f, Q, S.desc + (size_t)i * 32, lane, [](int, const KeyPointPOD &) { return true; }, n, S.V.nlevels, clean);
     }
-    best = wave_min_u64(best); // smallest (distance, GetFeaturesInArea order) = the reference loop's first minimum
-    bad = __any(bad) != 0;
     if (lane == 0) {
         S.match[i] = (best != NO_KEY && key_dist(best) <= TH_HIGH) ? key_idx(best) : -1; // in [0, n): the checked walk has tested it
-        if (bad) *a.status = ORBFE_ERR_INVALID; // every wave that writes writes this value
+        if (!clean) *a.status = ORBFE_ERR_INVALID; // every wave that writes writes this value
     }
 }
 
@@ -108,13 +87,12 @@ __global__ __launch_bounds__(256) void sim3_agree_kernel(int n1, const int32_t *
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(n_found, cnt); // an integer count: the order of the waves does not matter
 }
 
-#define STRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return orbfe_fail(ctx, ORBFE_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
 
-static void sim3_side(Sim3Side &S, const orbfe_grid_keyframe *kfb, const float *Taw, const float *sRt, int n, const float *d_pos, const float *d_max_distance,
+static void sim3_side(orbfe_context *ctx, Sim3Side &S, const orbfe_grid_keyframe *kfb, const float *Taw, const float *sRt, int n, const float *d_pos, const float *d_max_distance,
                       const float *d_min_distance, const uint8_t *d_desc, const int32_t *d_valid, int32_t *d_match)
 {
     S.f.u_right = nullptr; // SearchBySim3 has no mvuRight gate: the record's u_right is never read
-    S.min_x = kfb->min_x; S.max_x = kfb->max_x; S.min_y = kfb->min_y; S.max_y = kfb->max_y; S.keyframe = kfb->keyframe != 0;
+    S.V = orbfe_view(ctx, kfb);
     for (int k = 0; k < 12; k++) { S.Taw[k] = Taw[k]; S.sRt[k] = sRt[k]; }
     S.n = n;
     S.pos = d_pos; S.max_distance = d_max_distance; S.min_distance = d_min_distance; S.desc = d_desc; S.valid = d_valid;
@@ -143,25 +121,20 @@ try {
     const orbfe_params *P = orbfe_ctx_params(ctx);
     if (P->nlevels < 1 || P->nlevels > ORBFE_MAX_LEVELS) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "nlevels = %d", P->nlevels);
     hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    STRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
     int32_t *m = orbfe_ctx_sim3_scratch(ctx, (size_t)n1 + (size_t)n2);
     if (!m) return orbfe_fail(ctx, ORBFE_ERR_HIP, "matcher scratch allocation failed");
     hipLaunchKernelGGL(sim3_reset_kernel, dim3(1), dim3(64), 0, s, d_n_found, d_status);
     if (n1 > 0) { // without keypoints in KF1 there is no d_match12 entry to write; without any in KF2 every entry is -1 and no array is read
         float A12[12], A21[12];
         orbfe_resolve::sim3_pair(s12, R12, t12, A12, A21);
-        sim3_side(a.side[0], kf2, T1w, A21, n1, d_pos1, d_max_distance1, d_min_distance1, d_pt_desc1, d_valid1, m);
-        sim3_side(a.side[1], kf1, T2w, A12, n2, d_pos2, d_max_distance2, d_min_distance2, d_pt_desc2, d_valid2, m + n1);
-        a.C = orbfe_resolve::camera_of(P);
-        const float *sf = orbfe_ctx_scale_factors(ctx);
-        for (int l = 0; l < ORBFE_MAX_LEVELS; l++) a.sf[l] = l < P->nlevels ? sf[l] : 1.f;
-        a.nlevels = P->nlevels;
-        a.log_sf = logf((float)(double)P->scale_factor); // mfLogScaleFactor = log(mfScaleFactor), src/Frame.cc:71
+        sim3_side(ctx, a.side[0], kf2, T1w, A21, n1, d_pos1, d_max_distance1, d_min_distance1, d_pt_desc1, d_valid1, m);
+        sim3_side(ctx, a.side[1], kf1, T2w, A12, n2, d_pos2, d_max_distance2, d_min_distance2, d_pt_desc2, d_valid2, m + n1);
         a.th = th;
         a.status = d_status;
         hipLaunchKernelGGL(sim3_one_way_kernel, dim3((std::max(n1, n2) + 3) / 4, 2), dim3(256), 0, s, a);
         hipLaunchKernelGGL(sim3_agree_kernel, dim3((n1 + 255) / 256), dim3(256), 0, s, n1, m, m + n1, d_match12, d_n_found);
     }
-    STRY(ctx, hipGetLastError());
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)

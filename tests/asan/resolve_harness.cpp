@@ -126,11 +126,10 @@ int main(int argc, char **argv)
     const std::vector<float> cam = rd<float>("cam.f32"), bounds = rd<float>("bounds.f32");
     orbfe_params P = {};
     P.fx = cam[0]; P.fy = cam[1]; P.cx = cam[2]; P.cy = cam[3]; P.bf = cam[4]; P.nlevels = 8; P.scale_factor = 1.2f;
-    const Camera C = camera_of(&P);
     float sf[8];
     sf[0] = 1.0f;
     for (int i = 1; i < 8; i++) sf[i] = (float)((double)sf[i - 1] * (double)1.2f);
-    const float log_sf = logf((float)(double)P.scale_factor);
+    const View V = view_of(&P, sf, bounds[0], bounds[1], bounds[2], bounds[3], 0);
 
     BruteFrame cur;
     cur.keys = rd<orbfe_keypoint>("cur_k.bin"); cur.desc = rd<uint8_t>("cur_d.bin"); cur.ur = rd<float>("cur_ur.bin");
@@ -152,7 +151,7 @@ int main(int argc, char **argv)
         std::vector<uint8_t> qd;
         // 1. SearchByProjection(CurrentFrame, LastFrame, 7, false), orientation check on
         {
-            if (build_queries_last(C, sf, 8, bounds[0], bounds[1], bounds[2], bounds[3], T_cur.data(), T_last.data(), M, pos.data(), last_desc.data(),
+            if (build_queries_last(V, T_cur.data(), T_last.data(), M, pos.data(), last_desc.data(),
                                    usable.data(), oct.data(), 7.0f, 0, q, qd) != 0) return 3;
             std::vector<uint8_t> has(cur_has), blocked0(cur_has);
             dev.run(cur, q, qd, blocked0.data(), true, starve);
@@ -164,7 +163,7 @@ int main(int argc, char **argv)
         // 2. isInFrustum + SearchByProjection(F, vpMapPoints, 3), nnratio 0.8
         {
             std::vector<orbfe_track_point> tp(M);
-            is_in_frustum(C, 8, log_sf, T_cur.data(), bounds[0], bounds[1], bounds[2], bounds[3], M, pos.data(), normal.data(), max_d.data(), min_d.data(), 0.5f, tp.data());
+            is_in_frustum(V, T_cur.data(), M, pos.data(), normal.data(), max_d.data(), min_d.data(), 0.5f, tp.data());
             if (!starve) wr("h_tp.bin", tp);
             if (build_queries_points(sf, 8, M, tp.data(), last_desc.data(), 3.0f, q, qd) != 0) return 4;
             std::vector<uint8_t> has(cur_has), blocked0(cur_has);
@@ -180,7 +179,7 @@ int main(int argc, char **argv)
             for (int i = 0; i < M; i++) kf_ok[i] = usable[i] && !found[i];
             BruteFrame mono = cur;
             mono.ur.clear();
-            build_queries_kf(C, sf, 8, log_sf, bounds[0], bounds[1], bounds[2], bounds[3], T_cur.data(), M, pos.data(), last_desc.data(), kf_ok.data(), max_d.data(),
+            build_queries_kf(V, T_cur.data(), M, pos.data(), last_desc.data(), kf_ok.data(), max_d.data(),
                              min_d.data(), 10.0f, q, qd);
             std::vector<uint8_t> has(cur_has), blocked0(cur_has);
             dev.run(mono, q, qd, blocked0.data(), false, starve);
