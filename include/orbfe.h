@@ -728,6 +728,49 @@ int orbfe_enqueue_search_for_triangulation(orbfe_context *ctx, const orbfe_tri_k
         int only_stereo, int check_ori,
         int32_t *d_match12 /* [kf1->n] */, int32_t *d_pairs /* [2 * min(n1, n2)], may be NULL */,
         int32_t *d_nmatches, int32_t *d_status, void *stream);
+/* ORBmatcher::SearchByFboW(KeyFrame *pKF1, KeyFrame *pKF2, vpMatches12) (src/ORBmatcher.cc:517-650) on two device-resident keyframes,
+ * the first step of LoopClosing::ComputeSim3 (src/LoopClosing.cc:288-316, call at :301), asynchronous on `stream` (NULL: the context's
+ * stream) under the contract of the enqueue matchers above: nothing waits for the GPU, nothing is copied from host memory on the
+ * stream, no vocabulary is needed and no image slot is read.  Both keyframes are orbfe_bow_keyframe records (valid = the keypoint has a
+ * map point that is not bad, :554-557 and :571-575; pos is never read); kf1 and kf2 are HOST structs holding device pointers, read
+ * before the call returns.  The rule is orbfe_search_by_bow_kf's: both validity arrays gate, a KF2 keypoint is taken at most once
+ * (vbMatched2), bestDist1 < TH_LOW strictly (:593), the rotation histogram collects idx1 under the bin of angle1 - angle2 (:602-609).
+ * Outputs (device): d_match12[kf1->n] = KF2 keypoint or -1; d_pairs, optional, [2 * kf1->n]: the accepted (idx1, idx2) in ascending
+ * idx1 after the rotation cut -- the order in which Sim3Solver's constructor walks vpMatched12, so the caller downloads the count and
+ * the pairs, not a row of n1 entries -- entries from 2 * count on untouched; d_nmatches[1]; d_status[1].  Nothing else is written.
+ * kf1->n == 0: count 0, status 0; kf1->nnodes == 0 or a kf2 without nodes: all -1, count 0, and no array of kf2 is read.  Every result
+ * equals orbfe_search_by_bow_kf on the same inputs.  At most three launches.
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL context, record or output other than d_pairs; in either record a
+ * negative n or nnodes, n > 65535, a NULL array other than pos under nnodes > 0.  d_status = ORBFE_ERR_INVALID for what only the
+ * device can see: node ids of either side not strictly ascending, a CSR offset negative, descending or beyond n, a feature index
+ * outside [0, n), a rotation bin outside [0, 30) (angles outside [0, 360)).  Each is checked before it is used as an address and that
+ * node / entry is skipped; the other outputs are then not meaningful, but nothing is written outside the four outputs.
+ * The vbMatched2 flags of a KF2 node list beyond its first 4096 positions live in the context's grow-only BoW scratch (kf2->n bytes,
+ * only when kf2->n > 4096; the wave that owns the node zeroes what it uses).  The context grows that scratch only when a call needs
+ * more than any call before it; such calls share it with orbfe_enqueue_search_for_triangulation: queue them on one stream. */
+int orbfe_enqueue_search_by_bow_kf(orbfe_context *ctx, const orbfe_bow_keyframe *kf1 /* host */, const orbfe_bow_keyframe *kf2 /* host */,
+        float nnratio, int check_ori,
+        int32_t *d_match12 /* [kf1->n]: KF2 keypoint or -1 */, int32_t *d_pairs /* [2 * kf1->n], may be NULL */,
+        int32_t *d_nmatches /* [1] */, int32_t *d_status /* [1] */, void *stream);
+/* The same for every candidate of ComputeSim3 in the same three launches (the candidates are independent: each has its own
+ * vvpMapPointMatches[i], mpCurrentKF is not written, vbMatched2 is local to one call -- unlike the neighbour loops of
+ * SearchForTriangulation and Fuse).  kf1 is a HOST struct (mpCurrentKF; its counts size the grid and the row strides), d_kfs a DEVICE
+ * array of n_kfs records, uploaded by the caller when the candidate set is known.  The host cannot see d_kfs[k].n, and the flags above
+ * need a row stride: max_kf_n is an upper bound of every n (scratch: n_kfs * max_kf_n bytes, only when max_kf_n > 4096).
+ * Outputs are n_kfs rows: d_match12[n_kfs][kf1->n], d_pairs[n_kfs][2 * kf1->n] (optional), d_nmatches[n_kfs], d_status[n_kfs].  Row k
+ * is bit for bit what the single call writes for candidate k alone; a fault in record k changes no other row and nothing is ever
+ * written outside row k of the four outputs.  What the single call refuses on the host and only the device can see here sets
+ * d_status[k] = ORBFE_ERR_INVALID and searches candidate k as a keyframe without nodes (row -1, count 0): nnodes < 0, n < 0,
+ * n > max_kf_n, a NULL array other than pos under nnodes > 0; these fields are checked before any pointer of the record is followed.
+ * A fault on the KF1 side (node order, CSR, feature index) is reported in every row that meets it.
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL context, kf1 or output other than d_pairs, d_kfs == NULL under
+ * n_kfs > 0; kf1->n or kf1->nnodes negative, kf1->n > 65535, a NULL array other than pos in kf1 under nnodes > 0; n_kfs < 0,
+ * n_kfs > 65535 (the grid's y limit), max_kf_n < 0, max_kf_n > 65535.  n_kfs == 0: ORBFE_OK, nothing queued. */
+int orbfe_enqueue_search_by_bow_kf_batch(orbfe_context *ctx, const orbfe_bow_keyframe *kf1 /* host */,
+        const orbfe_bow_keyframe *d_kfs /* DEVICE array */, int n_kfs, int max_kf_n,
+        float nnratio, int check_ori,
+        int32_t *d_match12 /* [n_kfs][kf1->n] */, int32_t *d_pairs /* [n_kfs][2 * kf1->n], may be NULL */,
+        int32_t *d_nmatches /* [n_kfs] */, int32_t *d_status /* [n_kfs] */, void *stream);
 /* ---- ORBmatcher::Fuse on device-resident keyframes (orbfe_fuse_device.hip): LocalMapping::SearchInNeighbors (src/LocalMapping.cc:454-531)
  * and LoopClosing::SearchAndFuse without a host round trip inside the call.  The contract of the enqueue matchers above holds: asynchronous
  * on `stream` (NULL: the context's stream), nothing waits for the GPU, nothing is copied from host memory on the stream, nothing is

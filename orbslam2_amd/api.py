@@ -42,6 +42,7 @@ EXPORTS = [
     "orbfe_enqueue_search_for_triangulation",
     "orbfe_enqueue_keyframe_grid", "orbfe_enqueue_fuse", "orbfe_enqueue_fuse_sim3",
     "orbfe_enqueue_search_by_sim3", "orbfe_enqueue_search_by_projection_sim3",
+    "orbfe_enqueue_search_by_bow_kf", "orbfe_enqueue_search_by_bow_kf_batch",
 ]
 NUM_STAGES = 8
 STAGE_NAMES = ["ingest", "pyramid", "blur", "fast", "octree", "describe", "stereo_match", "stereo_median"]  # orbfe_stage_name()
@@ -70,7 +71,8 @@ class PackedLayout(C.Structure):
 
 
 class BowKeyframe(C.Structure):
-    """orbfe_bow_keyframe (include/orbfe.h): one candidate keyframe of enqueue_search_by_bow_batch, device pointers."""
+    """orbfe_bow_keyframe (include/orbfe.h): one candidate keyframe of enqueue_search_by_bow_batch, either keyframe of
+    enqueue_search_by_bow_kf / _batch; device pointers."""
     _fields_ = [("nodes", C.c_void_p), ("off", C.c_void_p), ("feat", C.c_void_p), ("valid", C.c_void_p), ("desc", C.c_void_p),
                 ("angle", C.c_void_p), ("pos", C.c_void_p), ("nnodes", C.c_int32), ("n", C.c_int32)]
 
@@ -260,6 +262,10 @@ def load():
     L.orbfe_enqueue_search_by_sim3.argtypes = [vp] + [C.POINTER(GridKeyframe)] + [vp] * 6 + [C.POINTER(GridKeyframe)] + [vp] * 6 + [C.c_float, vp, vp, C.c_float] + [vp] * 4
     L.orbfe_enqueue_search_by_projection_sim3.restype = C.c_int
     L.orbfe_enqueue_search_by_projection_sim3.argtypes = [vp, C.POINTER(GridKeyframe), vp, C.c_int, vp, C.c_int] + [vp] * 7 + [C.c_float] + [vp] * 5
+    L.orbfe_enqueue_search_by_bow_kf.restype = C.c_int
+    L.orbfe_enqueue_search_by_bow_kf.argtypes = [vp, C.POINTER(BowKeyframe), C.POINTER(BowKeyframe), C.c_float, C.c_int] + [vp] * 5
+    L.orbfe_enqueue_search_by_bow_kf_batch.restype = C.c_int
+    L.orbfe_enqueue_search_by_bow_kf_batch.argtypes = [vp, C.POINTER(BowKeyframe), vp, C.c_int, C.c_int, C.c_float, C.c_int] + [vp] * 5
     _lib = L
     return L
 
@@ -678,6 +684,24 @@ class Context:
         self._check(self.L.orbfe_enqueue_search_by_bow_batch(
             self.h, slot, v(d_kfs or None), n_kfs, max_kf_nnodes, v(d_f_nodes), v(d_f_off), v(d_f_feat), v(d_f_n_nodes), nnratio, int(check_ori),
             v(d_f_match), v(d_nmatches), v(d_status), v(d_has_point or None), v(d_Xw or None), v(stream or None)))
+
+    def enqueue_search_by_bow_kf(self, kf1, kf2, nnratio, check_ori, d_match12, d_nmatches, d_status, d_pairs=0, stream=0):
+        """ORBmatcher::SearchByFboW(KeyFrame*, KeyFrame*) on two device-resident keyframes (BowKeyframe records on the host, device
+        pointers inside; None passes as a NULL record), asynchronous on `stream`: d_match12[kf1.n], the optional d_pairs[2 * kf1.n]
+        ((idx1, idx2) in ascending idx1), the count and the status as one int32 each."""
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_search_by_bow_kf(
+            self.h, None if kf1 is None else C.byref(kf1), None if kf2 is None else C.byref(kf2), nnratio, int(check_ori),
+            v(d_match12 or None), v(d_pairs or None), v(d_nmatches or None), v(d_status or None), v(stream or None)))
+
+    def enqueue_search_by_bow_kf_batch(self, kf1, d_kfs, n_kfs, max_kf_n, nnratio, check_ori, d_match12, d_nmatches, d_status, d_pairs=0, stream=0):
+        """enqueue_search_by_bow_kf of kf1 against n_kfs keyframes at once (LoopClosing::ComputeSim3): d_kfs is a device array of
+        BowKeyframe records, max_kf_n an upper bound of their n; the outputs hold one row per candidate (d_match12[n_kfs][kf1.n],
+        d_pairs[n_kfs][2 * kf1.n], d_nmatches[n_kfs], d_status[n_kfs])."""
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_search_by_bow_kf_batch(
+            self.h, None if kf1 is None else C.byref(kf1), v(d_kfs or None), n_kfs, max_kf_n, nnratio, int(check_ori),
+            v(d_match12 or None), v(d_pairs or None), v(d_nmatches or None), v(d_status or None), v(stream or None)))
 
     def enqueue_search_for_triangulation(self, kf1, kf2, F12, Cw1, T2w, fx2, fy2, cx2, cy2, only_stereo, check_ori,
                                          d_match12, d_nmatches, d_status, d_pairs=0, stream=0):

@@ -30,6 +30,12 @@
 //                                epipole disc, CheckDistEpipolarLine (orbfe_epipolar.h), last of the equal minima, no ratio test
 //   tri_tail_kernel              rotation histogram, ComputeThreeMaxima, the count, vMatchedPairs by an ordered compaction
 // One call per neighbour, never a batch: CreateNewMapPoints adds points to KF1 between two neighbours.
+// orbfe_enqueue_search_by_bow_kf / _batch (ORBmatcher::SearchByFboW(KeyFrame*, KeyFrame*), src/ORBmatcher.cc:517-650; the synchronous form
+// is in orbfe_bow.hip), both keyframes device-resident, three launches for all candidates of LoopClosing::ComputeSim3:
+//   bowkf_init_kernel            rows of match12 = -1, count, status
+//   bowkf_node_match_kernel      one wave per (KF1 node, candidate): bow_node_walk, the walk bow_node_match_kernel runs, with KF1 as the
+//                                query side, valid2 on the candidates, the flag on the KF2 side and the strict bound
+//   bowkf_tail_kernel            match12_tail, the tail tri_tail_kernel runs
 #include "../../include/orbfe.h"
 #include "orbfe_device.h"
 #include "orbfe_host.h"
@@ -309,11 +315,110 @@ __device__ __forceinline__ int bow_lower_bound(const uint32_t *__restrict__ node
     return lo;
 }
 
-// One wave per keyframe node.  Position j of the node's frame features belongs to lane j & 63 (its chunk j >> 6); the flag "frame
-// keypoint already matched" of chunk c < BOW_FLAG_CHUNKS is bit c of the lane's `taken`, of a later chunk it is f_match itself,
-// which only this lane wrote (every frame keypoint lies in one node).  A lane's candidates come in list order, so its running
-// (d1, d2) is the if-chain of :213-222 on its share; the wave's bestDist1 is the smallest key d << 16 | j (first minimum in list
-// order), bestDist2 the smallest distance of all the others, duplicates of bestDist1 included.
+// The walk of one shared node, by one wave, for both SearchByFboW overloads.  The QUERY side is the outer loop of the reference
+// (:203 / :563): its list entries q_list[k0, k1) are taken in list order, those with q_valid set.  The CANDIDATE side is the inner
+// loop (:213 / :567): position j of c_list[f0, f0 + nf) belongs to lane j & 63 (its chunk j >> 6).  The flag "candidate already
+// matched" of chunk c < BOW_FLAG_CHUNKS is bit c of the lane's `taken`; where the flag of a later chunk lives, which candidates
+// count at all, where an accepted pair is written and the bound on bestDist1 are the Side's:
+//   BOUND               accept at bestDist1 <= BOUND (:225 `<= TH_LOW`, :593 `< TH_LOW`)
+//   usable(idx)         folded in when a candidate is loaded
+//   late_reset(idx)     before the first query, for every candidate of a chunk >= BOW_FLAG_CHUNKS, by the lane that owns it
+//   late_taken(idx)     the flag of such a candidate; only the lane that owns it reads and writes it
+//   accept(q, idx, late)
+// A lane's candidates come in list order, so its running (d1, d2) is the if-chain of :213-222 on its share; the wave's bestDist1 is
+// the smallest key d << 16 | j (first minimum in list order), bestDist2 the smallest distance of all the others, duplicates of
+// bestDist1 included.  Every index is checked before it is used as an address; returns whether this lane refused one.
+template <class Side>
+__device__ __forceinline__ bool bow_node_walk(const Side &s, float nnratio, const int32_t *q_list, int k0, int k1, const int32_t *q_valid, const uint8_t *q_desc, int n_q,
+                                              const int32_t *c_list, int f0, int nf, const uint8_t *c_desc, int n, int lane)
+{
+    bool bad = false;
+    for (int j = lane; j < nf; j += 64) {
+        const int idx = c_list[f0 + j];
+        const bool out = idx < 0 || idx >= n;
+        bad = bad || out;
+        if (j >= 64 * BOW_FLAG_CHUNKS && !out) s.late_reset(idx);
+    }
+    // this lane's first BOW_REG_CHUNKS candidates stay in registers: few nodes hold more than 64 * BOW_REG_CHUNKS
+    int idxc[BOW_REG_CHUNKS];
+    uint32_t fdc[BOW_REG_CHUNKS][8];
+#pragma unroll
+    for (int c = 0; c < BOW_REG_CHUNKS; c++) {
+        const int j = lane + 64 * c;
+        idxc[c] = j < nf ? c_list[f0 + j] : -1;
+        if (idxc[c] >= n) idxc[c] = -1;
+        if (idxc[c] >= 0 && !s.usable(idxc[c])) idxc[c] = -1;
+#pragma unroll
+        for (int k = 0; k < 8; k++) fdc[c][k] = idxc[c] >= 0 ? ((const uint32_t *)(c_desc + (size_t)idxc[c] * 32))[k] : 0u;
+    }
+    u64 taken = 0;
+    for (int kbase = k0; kbase < k1; kbase += 64) {
+        // 64 queries at a time are fetched by the lanes side by side, so that no load sits in the sequential loop below
+        int my_kf = -1;
+        bool my_ok = false;
+        uint32_t my_kd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (kbase + lane < k1) {
+            my_kf = q_list[kbase + lane];
+            if (my_kf < 0 || my_kf >= n_q) bad = true;
+            else if (q_valid[my_kf]) {
+                my_ok = true;
+#pragma unroll
+                for (int k = 0; k < 8; k++) my_kd[k] = ((const uint32_t *)(q_desc + (size_t)my_kf * 32))[k];
+            }
+        }
+        for (u64 todo = __ballot(my_ok); todo; todo &= todo - 1) { // the valid queries in order
+            const int src = __ffsll((long long)todo) - 1;
+            const int real_kf = __builtin_amdgcn_readlane(my_kf, src);
+            uint32_t kd[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) kd[k] = (uint32_t)__builtin_amdgcn_readlane((int)my_kd[k], src);
+            int d1 = 256, d2 = 256, c1 = 1023, i1 = -1; // 256 differing bits are no candidate (`dist < bestDist1`), chunk 1023 is none
+#pragma unroll
+            for (int c = 0; c < BOW_REG_CHUNKS; c++) {
+                if (idxc[c] < 0 || ((taken >> c) & 1ull)) continue;
+                const int d = hamming256(kd, fdc[c]);
+                if (d < d1) { d2 = d1; d1 = d; c1 = c; i1 = idxc[c]; }
+                else if (d < d2) d2 = d;
+            }
+            for (int j = lane + 64 * BOW_REG_CHUNKS, c = BOW_REG_CHUNKS; j < nf; j += 64, c++) {
+                const int idx = c_list[f0 + j];
+                if (idx < 0 || idx >= n) continue;
+                if (!s.usable(idx)) continue;
+                if (c < BOW_FLAG_CHUNKS ? (int)((taken >> c) & 1ull) : (int)s.late_taken(idx)) continue;
+                const int d = hamming256(kd, (const uint32_t *)(c_desc + (size_t)idx * 32));
+                if (d < d1) { d2 = d1; d1 = d; c1 = c; i1 = idx; }
+                else if (d < d2) d2 = d;
+            }
+            // bestDist1: the smallest key distance << 16 | list position (chunk * 64 + lane): the first minimum in list order
+            const unsigned key = ((unsigned)d1 << 16) | (unsigned)(c1 * 64 + lane);
+            const unsigned m = wave_min_u32(key);
+            const int best1 = (int)(m >> 16);
+            if (best1 > Side::BOUND) continue; // also: no candidate at all
+            const bool winner = key == m; // list positions are unique
+            const int best2 = (int)wave_min_u32((unsigned)(winner ? d2 : d1)); // the smallest of all the others, duplicates of bestDist1 included
+            if (!((float)best1 < nnratio * (float)best2)) continue;
+            if (winner) {
+                s.accept(real_kf, i1, c1 >= BOW_FLAG_CHUNKS);
+                if (c1 < BOW_FLAG_CHUNKS) taken |= 1ull << c1;
+            }
+        }
+    }
+    return bad;
+}
+
+// SearchByFboW(KeyFrame*, Frame&): the keyframe's features are the queries, every frame keypoint of the node is a candidate, the
+// result is indexed by the candidate (f_match[idxF] = realIdxKF, :227), so the flag of a late chunk is f_match itself, which only
+// the lane that owns the keypoint wrote (every frame keypoint lies in one node).
+struct BowFrameSide {
+    static constexpr int BOUND = TH_LOW;
+    int32_t *match;
+    __device__ __forceinline__ bool usable(int) const { return true; }
+    __device__ __forceinline__ void late_reset(int) const {}
+    __device__ __forceinline__ bool late_taken(int idx) const { return match[idx] >= 0; }
+    __device__ __forceinline__ void accept(int q, int idx, bool) const { match[idx] = q; }
+};
+
+// One wave per keyframe node.
 __device__ __forceinline__ void bow_node_match(const BowSearch &a)
 {
     const int lane = threadIdx.x & 63;
@@ -338,73 +443,8 @@ __device__ __forceinline__ void bow_node_match(const BowSearch &a)
     }
     const int nf = f1 - f0;
     if (k1 == k0 || nf == 0) return;
-    bool bad = false;
-    for (int j = lane; j < nf; j += 64) {
-        const int idx = a.f_feat[f0 + j];
-        bad = bad || idx < 0 || idx >= n;
-    }
-    // this lane's first BOW_REG_CHUNKS features stay in registers: few nodes hold more than 64 * BOW_REG_CHUNKS
-    int idxc[BOW_REG_CHUNKS];
-    uint32_t fdc[BOW_REG_CHUNKS][8];
-#pragma unroll
-    for (int c = 0; c < BOW_REG_CHUNKS; c++) {
-        const int j = lane + 64 * c;
-        idxc[c] = j < nf ? a.f_feat[f0 + j] : -1;
-        if (idxc[c] >= n) idxc[c] = -1;
-#pragma unroll
-        for (int k = 0; k < 8; k++) fdc[c][k] = idxc[c] >= 0 ? ((const uint32_t *)(a.desc + (size_t)idxc[c] * 32))[k] : 0u;
-    }
-    u64 taken = 0;
-    for (int kbase = k0; kbase < k1; kbase += 64) {
-        // 64 KF features at a time are fetched by the lanes side by side, so that no load sits in the sequential loop below
-        int my_kf = -1;
-        bool my_ok = false;
-        uint32_t my_kd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (kbase + lane < k1) {
-            my_kf = a.kf_feat[kbase + lane];
-            if (my_kf < 0 || my_kf >= a.n_kf) bad = true;
-            else if (a.kf_valid[my_kf]) {
-                my_ok = true;
-#pragma unroll
-                for (int k = 0; k < 8; k++) my_kd[k] = ((const uint32_t *)(a.kf_desc + (size_t)my_kf * 32))[k];
-            }
-        }
-        for (u64 todo = __ballot(my_ok); todo; todo &= todo - 1) { // the valid KF features in order
-            const int src = __ffsll((long long)todo) - 1;
-            const int real_kf = __builtin_amdgcn_readlane(my_kf, src);
-            uint32_t kd[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) kd[k] = (uint32_t)__builtin_amdgcn_readlane((int)my_kd[k], src);
-            int d1 = 256, d2 = 256, c1 = 1023, i1 = -1; // 256 differing bits are no candidate (`dist < bestDist1`), chunk 1023 is none
-#pragma unroll
-            for (int c = 0; c < BOW_REG_CHUNKS; c++) {
-                if (idxc[c] < 0 || ((taken >> c) & 1ull)) continue;
-                const int d = hamming256(kd, fdc[c]);
-                if (d < d1) { d2 = d1; d1 = d; c1 = c; i1 = idxc[c]; }
-                else if (d < d2) d2 = d;
-            }
-            for (int j = lane + 64 * BOW_REG_CHUNKS, c = BOW_REG_CHUNKS; j < nf; j += 64, c++) {
-                const int idx = a.f_feat[f0 + j];
-                if (idx < 0 || idx >= n) continue;
-                if (c < BOW_FLAG_CHUNKS ? (int)((taken >> c) & 1ull) : a.match[idx] >= 0) continue;
-                const int d = hamming256(kd, (const uint32_t *)(a.desc + (size_t)idx * 32));
-                if (d < d1) { d2 = d1; d1 = d; c1 = c; i1 = idx; }
-                else if (d < d2) d2 = d;
-            }
-            // bestDist1: the smallest key distance << 16 | list position (chunk * 64 + lane): the first minimum in list order
-            const unsigned key = ((unsigned)d1 << 16) | (unsigned)(c1 * 64 + lane);
-            const unsigned m = wave_min_u32(key);
-            const int best1 = (int)(m >> 16);
-            if (best1 > TH_LOW) continue; // also: no candidate at all
-            const bool winner = key == m; // list positions are unique
-            const int best2 = (int)wave_min_u32((unsigned)(winner ? d2 : d1)); // the smallest of all the others, duplicates of bestDist1 included
-            if (!((float)best1 < a.nnratio * (float)best2)) continue;
-            if (winner) {
-                a.match[i1] = real_kf;
-                if (c1 < BOW_FLAG_CHUNKS) taken |= 1ull << c1;
-            }
-        }
-    }
+    const BowFrameSide side = {a.match};
+    const bool bad = bow_node_walk(side, a.nnratio, a.kf_feat, k0, k1, a.kf_valid, a.kf_desc, a.n_kf, a.f_feat, f0, nf, a.desc, n, lane);
     if (__any(bad) && lane == 0) *a.status = ORBFE_ERR_INVALID;
 }
 
@@ -733,24 +773,26 @@ __global__ __launch_bounds__(256) void tri_node_match_kernel(TriSearch a)
     if (__any(bad) && lane == 0) *a.status = ORBFE_ERR_INVALID;
 }
 
-// One workgroup.  A KF1 keypoint lies in one node, so the accepted pairs are the non-negative entries of match12 (each a KF2
-// index the node kernel checked): rotation
-// histogram (:781-790), ComputeThreeMaxima, losers removed (:793-806), the count, and vMatchedPairs (:808-816) by an ordered
-// compaction: thread t owns a contiguous run of idx1, the runs' counts are scanned.
-__global__ __launch_bounds__(1024) void tri_tail_kernel(TriSearch a)
+// One workgroup of 1024, for the matchers whose result is match12[idx1] = idx2.  A KF1 keypoint lies in one node, so the accepted
+// pairs are the non-negative entries of match12 (each a KF2 index the node kernel checked): rotation histogram (:781-790, :602-609;
+// the bin collects idx1), ComputeThreeMaxima, losers removed (:793-806, :619-633), the count, and the accepted (idx1, idx2) in
+// ascending idx1 (vMatchedPairs, :808-816; the order in which Sim3Solver walks vpMatched12) by an ordered compaction: thread t owns
+// a contiguous run of idx1, the runs' counts are scanned.  At most `room` pairs are written.
+template <class Angle1, class Angle2>
+__device__ __forceinline__ void match12_tail(int n1, int32_t *match12, int32_t *pairs, int room, int32_t *nmatches, int32_t *status, int check_ori,
+                                             Angle1 angle1, Angle2 angle2)
 {
     __shared__ int32_t s_hist[32];
     __shared__ int s_keep[3], s_wave[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n1 = a.k1.n;
     if (tid < 32) s_hist[tid] = 0;
     __syncthreads();
-    if (a.check_ori) {
+    if (check_ori) {
         for (int k = tid; k < n1; k += 1024) {
-            const int m = a.match12[k];
+            const int m = match12[k];
             if (m < 0) continue;
-            int bin = orbfe_resolve::rot_bin(a.k1.keys_un[k].angle, a.k2.keys_un[m].angle); // rotHist[bin].push_back(idx1)
-            if ((unsigned)bin >= (unsigned)HISTO_LENGTH) { bin = 0; *a.status = ORBFE_ERR_INVALID; } // angles outside [0, 360)
+            int bin = orbfe_resolve::rot_bin(angle1(k), angle2(m)); // rotHist[bin].push_back(idx1)
+            if ((unsigned)bin >= (unsigned)HISTO_LENGTH) { bin = 0; *status = ORBFE_ERR_INVALID; } // angles outside [0, 360)
             atomicAdd(&s_hist[bin], 1);
         }
         __syncthreads();
@@ -761,11 +803,11 @@ __global__ __launch_bounds__(1024) void tri_tail_kernel(TriSearch a)
     const int lo = tid * run < n1 ? tid * run : n1, hi = lo + run < n1 ? lo + run : n1;
     int cnt = 0;
     for (int k = lo; k < hi; k++) {
-        int m = a.match12[k];
-        if (m >= 0 && a.check_ori) {
-            int bin = orbfe_resolve::rot_bin(a.k1.keys_un[k].angle, a.k2.keys_un[m].angle);
+        int m = match12[k];
+        if (m >= 0 && check_ori) {
+            int bin = orbfe_resolve::rot_bin(angle1(k), angle2(m));
             if ((unsigned)bin >= (unsigned)HISTO_LENGTH) bin = 0;
-            if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) { a.match12[k] = -1; m = -1; }
+            if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) { match12[k] = -1; m = -1; }
         }
         cnt += m >= 0;
     }
@@ -783,18 +825,23 @@ __global__ __launch_bounds__(1024) void tri_tail_kernel(TriSearch a)
         before += w < wave ? t : 0;
         total += t;
     }
-    if (tid == 0) *a.nmatches = total;
-    if (!a.pairs) return;
-    // a KF2 keypoint is taken once, so total <= min(n1, n2), the caller's array; only a refused feature vector (a KF2 keypoint in two
-    // nodes) can exceed it, and then the rest is dropped
-    const int room = n1 < a.k2.n ? n1 : a.k2.n;
+    if (tid == 0) *nmatches = total;
+    if (!pairs) return;
     int p = before + incl - cnt;
     for (int k = lo; k < hi && p < room; k++) {
-        const int m = a.match12[k];
+        const int m = match12[k];
         if (m < 0) continue;
-        a.pairs[2 * p] = k; a.pairs[2 * p + 1] = m;
+        pairs[2 * p] = k; pairs[2 * p + 1] = m;
         p++;
     }
+}
+
+__global__ __launch_bounds__(1024) void tri_tail_kernel(TriSearch a)
+{
+    // a KF2 keypoint is taken once, so the count <= min(n1, n2), the caller's array; only a refused feature vector (a KF2 keypoint in
+    // two nodes) can exceed it, and then the rest is dropped
+    match12_tail(a.k1.n, a.match12, a.pairs, a.k1.n < a.k2.n ? a.k1.n : a.k2.n, a.nmatches, a.status, a.check_ori,
+                 [&](int k) { return a.k1.keys_un[k].angle; }, [&](int m) { return a.k2.keys_un[m].angle; });
 }
 
 extern "C" int orbfe_enqueue_search_for_triangulation(orbfe_context *ctx, const orbfe_tri_keyframe *kf1, const orbfe_tri_keyframe *kf2,
@@ -834,6 +881,202 @@ try {
     hipLaunchKernelGGL(tri_init_kernel, dim3(cells > 0 ? (cells + 255) / 256 : 1), dim3(256), 0, s, a);
     if (a.k1.nnodes > 0 && a.k2.nnodes > 0) hipLaunchKernelGGL(tri_node_match_kernel, dim3((a.k1.nnodes + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(tri_tail_kernel, dim3(1), dim3(1024), 0, s, a);
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
+    return ORBFE_OK;
+} ORBFE_CATCH(ctx)
+
+// ---------------------------------------------------------------------------------------------
+// SearchByFboW(KeyFrame*, KeyFrame*) (src/ORBmatcher.cc:517-650), LoopClosing::ComputeSim3 (src/LoopClosing.cc:288-316)
+// ---------------------------------------------------------------------------------------------
+// Both keyframes are orbfe_bow_keyframe records of device pointers.  vbMatched2[idx2] (:571 read, :598 written) is touched only by
+// the KF1 features of the node that holds idx2, so the rule is sequential inside a node and nowhere else: bow_node_walk with KF1 as
+// the query side.  Three launches whatever the number of candidates (the candidates of ComputeSim3 are independent: each has its own
+// vvpMapPointMatches[i], mpCurrentKF is not written, vbMatched2 is local to one call):
+//   bowkf_init_kernel         rows of match12 = -1, count, status
+//   bowkf_node_match_kernel   grid (ceil(kf1.nnodes / 4), K), one wave per (KF1 node, candidate)
+//   bowkf_tail_kernel         K workgroups: match12_tail
+// The _batch kernels run the same device functions on the BowKfSearch that bowkf_batch_row builds from record blockIdx.y (tail:
+// blockIdx.x) and that row of the outputs.
+struct BowKfSearch {
+    orbfe_bow_keyframe k1, k2;                    // pos is never read
+    float nnratio; int check_ori;
+    int32_t *match12, *pairs, *nmatches, *status;
+    uint8_t *taken2;                              // [max n2] scratch: vbMatched2 beyond the lane-held flags; NULL when no node can reach that far
+};
+
+// KF1's features are the queries; a KF2 keypoint is a candidate when it has a good map point (valid2, :571-575); the flag sits on the
+// candidate (vbMatched2) while the result is indexed by the query (vpMatches12[idx1], :597), so the flag of a late chunk needs memory
+// of its own: taken2[idx2], zeroed by the lane that owns position j of the node's list before the first query and touched by no
+// other thread (a KF2 keypoint lies in one node).  The bound is strict: bestDist1 < TH_LOW (:593).
+struct BowKfSide {
+    static constexpr int BOUND = TH_LOW - 1;
+    const int32_t *valid2; int32_t *match12; uint8_t *taken2;
+    __device__ __forceinline__ bool usable(int idx) const { return valid2[idx] != 0; }
+    __device__ __forceinline__ void late_reset(int idx) const { taken2[idx] = 0; }
+    __device__ __forceinline__ bool late_taken(int idx) const { return taken2[idx] != 0; }
+    __device__ __forceinline__ void accept(int q, int idx, bool late) const
+    {
+        match12[q] = idx;
+        if (late) taken2[idx] = 1;
+    }
+};
+
+__device__ __forceinline__ void bowkf_init(const BowKfSearch &a, bool refused)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k == 0) { *a.status = refused ? ORBFE_ERR_INVALID : ORBFE_OK; *a.nmatches = 0; }
+    if (k < a.k1.n) a.match12[k] = -1;
+}
+
+__device__ __forceinline__ void bowkf_node_match(const BowKfSearch &a)
+{
+    const int lane = threadIdx.x & 63;
+    const int n1 = a.k1.n, n2 = a.k2.n, nn2 = a.k2.nnodes;
+    if (nn2 == 0) return; // the whole workgroup: a candidate without nodes, or a refused record
+    bool bad = false;
+    // KF2's node list and CSR, once over the grid's x axis: the merge-join of :537-616 relies on std::map order
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < nn2; k += gridDim.x * 256) {
+        const int o0 = a.k2.off[k], o1 = a.k2.off[k + 1];
+        bad = bad || (k > 0 && a.k2.nodes[k - 1] >= a.k2.nodes[k]) || o0 < 0 || o1 < o0 || o1 > n2;
+    }
+    if (__any(bad) && lane == 0) *a.status = ORBFE_ERR_INVALID;
+    const int node = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (node >= a.k1.nnodes) return;
+    const uint32_t id = a.k1.nodes[node];
+    const int k0 = a.k1.off[node], k1 = a.k1.off[node + 1];
+    if ((node > 0 && a.k1.nodes[node - 1] >= id) || k0 < 0 || k1 < k0 || k1 > n1) {
+        if (lane == 0) *a.status = ORBFE_ERR_INVALID;
+        return;
+    }
+    const int lo = bow_lower_bound(a.k2.nodes, nn2, id, lane);
+    if (lo >= nn2 || a.k2.nodes[lo] != id) return;
+    const int f0 = a.k2.off[lo], f1 = a.k2.off[lo + 1];
+    if (f0 < 0 || f1 < f0 || f1 > n2) { // a keypoint lies in one node: no CSR is longer than its keypoint array
+        if (lane == 0) *a.status = ORBFE_ERR_INVALID;
+        return;
+    }
+    const int nf = f1 - f0;
+    if (k1 == k0 || nf == 0) return;
+    const BowKfSide side = {a.k2.valid, a.match12, a.taken2};
+    bad = bow_node_walk(side, a.nnratio, a.k1.feat, k0, k1, a.k1.valid, a.k1.desc, n1, a.k2.feat, f0, nf, a.k2.desc, n2, lane);
+    if (__any(bad) && lane == 0) *a.status = ORBFE_ERR_INVALID;
+}
+
+__device__ __forceinline__ void bowkf_tail(const BowKfSearch &a)
+{
+    // a KF1 keypoint is matched at most once: the count <= n1, the row of d_pairs
+    match12_tail(a.k1.n, a.match12, a.pairs, a.k1.n, a.nmatches, a.status, a.check_ori,
+                 [&](int k) { return a.k1.angle[k]; }, [&](int m) { return a.k2.angle[m]; });
+}
+
+// The batch: `a` holds KF1, the settings and row 0 of the outputs.  Record k is the same for every lane (k is a workgroup index) and
+// is read before any store, so it arrives by scalar loads and the BowKfSearch built from it stays in SGPRs.  A record the single
+// call would refuse on the host (a negative count, a NULL array under nnodes > 0), or whose n exceeds max_kf_n (the row stride of
+// the flags), is searched as a keyframe without nodes and reported in its status.
+__device__ __forceinline__ BowKfSearch bowkf_batch_row(BowKfSearch a, const orbfe_bow_keyframe *__restrict__ kfs, int max_kf_n, int k, bool *refused)
+{
+    const orbfe_bow_keyframe kf = kfs[k];
+    *refused = kf.nnodes < 0 || kf.n < 0 || kf.n > max_kf_n ||
+               (kf.nnodes > 0 && (!kf.nodes || !kf.off || !kf.feat || !kf.valid || !kf.desc || !kf.angle));
+    a.k2 = kf;
+    if (*refused) a.k2.nnodes = 0;
+    a.match12 += (size_t)k * a.k1.n; a.nmatches += k; a.status += k;
+    if (a.pairs) a.pairs += (size_t)k * 2 * a.k1.n;
+    if (a.taken2) a.taken2 += (size_t)k * max_kf_n;
+    return a;
+}
+
+__global__ __launch_bounds__(256) void bowkf_init_kernel(BowKfSearch a) { bowkf_init(a, false); }
+__global__ __launch_bounds__(256) void bowkf_node_match_kernel(BowKfSearch a) { bowkf_node_match(a); }
+__global__ __launch_bounds__(1024) void bowkf_tail_kernel(BowKfSearch a) { bowkf_tail(a); }
+__global__ __launch_bounds__(256) void bowkf_init_batch_kernel(BowKfSearch a, const orbfe_bow_keyframe *__restrict__ kfs, int max_kf_n)
+{
+    bool refused;
+    const BowKfSearch r = bowkf_batch_row(a, kfs, max_kf_n, blockIdx.y, &refused);
+    bowkf_init(r, refused);
+}
+__global__ __launch_bounds__(256) void bowkf_node_match_batch_kernel(BowKfSearch a, const orbfe_bow_keyframe *__restrict__ kfs, int max_kf_n)
+{
+    bool refused;
+    bowkf_node_match(bowkf_batch_row(a, kfs, max_kf_n, blockIdx.y, &refused));
+}
+__global__ __launch_bounds__(1024) void bowkf_tail_batch_kernel(BowKfSearch a, const orbfe_bow_keyframe *__restrict__ kfs, int max_kf_n)
+{
+    bool refused;
+    bowkf_tail(bowkf_batch_row(a, kfs, max_kf_n, blockIdx.x, &refused));
+}
+
+// What the host can see of a record; `what` names it in the message.
+static int bowkf_check_record(orbfe_context *ctx, const orbfe_bow_keyframe *kf, const char *what)
+{
+    if (kf->n < 0 || kf->nnodes < 0) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "%s: negative count", what);
+    if (kf->n > 65535) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "%s: keyframes with more than 65535 keypoints are not supported", what);
+    if (kf->nnodes > 0 && (!kf->nodes || !kf->off || !kf->feat || !kf->valid || !kf->desc || !kf->angle))
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "%s: null array in a keyframe record with nodes", what);
+    return ORBFE_OK;
+}
+
+// KF1, the settings, row 0 of the outputs and the flags: n_rows rows of max_n2 bytes of the grow-only BoW scratch, and only when a
+// node list can pass the 64 * BOW_FLAG_CHUNKS positions a lane's register covers (a list is no longer than its keyframe's n).
+static int bowkf_fill(orbfe_context *ctx, BowKfSearch *a, const orbfe_bow_keyframe *kf1, int n_rows, int max_n2, float nnratio, int check_ori,
+                      int32_t *d_match12, int32_t *d_pairs, int32_t *d_nmatches, int32_t *d_status)
+{
+    a->k1 = *kf1;
+    a->nnratio = nnratio; a->check_ori = check_ori != 0;
+    a->match12 = d_match12; a->pairs = d_pairs; a->nmatches = d_nmatches; a->status = d_status;
+    a->taken2 = nullptr;
+    if (max_n2 > 64 * BOW_FLAG_CHUNKS) {
+        orbfe_bow_state *st = orbfe_ctx_bow_state(ctx);
+        if (!st) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "out of host memory");
+        if (st->resident.ensure((size_t)n_rows * (size_t)max_n2)) return orbfe_fail(ctx, ORBFE_ERR_HIP, "BoW scratch allocation failed");
+        a->taken2 = (uint8_t *)st->resident.p;
+    }
+    return ORBFE_OK;
+}
+
+extern "C" int orbfe_enqueue_search_by_bow_kf(orbfe_context *ctx, const orbfe_bow_keyframe *kf1, const orbfe_bow_keyframe *kf2, float nnratio, int check_ori,
+                                              int32_t *d_match12, int32_t *d_pairs, int32_t *d_nmatches, int32_t *d_status, void *stream)
+try {
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    ORBFE_ENTRY(ctx);
+    if (!kf1 || !kf2 || !d_match12 || !d_nmatches || !d_status) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
+    int rc = bowkf_check_record(ctx, kf1, "kf1");
+    if (rc == ORBFE_OK) rc = bowkf_check_record(ctx, kf2, "kf2");
+    if (rc != ORBFE_OK) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    BowKfSearch a;
+    rc = bowkf_fill(ctx, &a, kf1, 1, kf2->n, nnratio, check_ori, d_match12, d_pairs, d_nmatches, d_status);
+    if (rc != ORBFE_OK) return rc;
+    a.k2 = *kf2;
+    hipLaunchKernelGGL(bowkf_init_kernel, dim3(a.k1.n > 0 ? (a.k1.n + 255) / 256 : 1), dim3(256), 0, s, a);
+    if (a.k1.nnodes > 0 && a.k2.nnodes > 0) hipLaunchKernelGGL(bowkf_node_match_kernel, dim3((a.k1.nnodes + 3) / 4), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(bowkf_tail_kernel, dim3(1), dim3(1024), 0, s, a);
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
+    return ORBFE_OK;
+} ORBFE_CATCH(ctx)
+
+extern "C" int orbfe_enqueue_search_by_bow_kf_batch(orbfe_context *ctx, const orbfe_bow_keyframe *kf1, const orbfe_bow_keyframe *d_kfs, int n_kfs, int max_kf_n,
+                                                    float nnratio, int check_ori, int32_t *d_match12, int32_t *d_pairs, int32_t *d_nmatches, int32_t *d_status,
+                                                    void *stream)
+try {
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    ORBFE_ENTRY(ctx);
+    if (!kf1 || !d_match12 || !d_nmatches || !d_status || (n_kfs > 0 && !d_kfs)) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
+    if (n_kfs < 0 || n_kfs > 65535 || max_kf_n < 0 || max_kf_n > 65535)
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "n_kfs = %d (0 .. 65535, the grid's y limit), max_kf_n = %d (0 .. 65535)", n_kfs, max_kf_n);
+    int rc = bowkf_check_record(ctx, kf1, "kf1");
+    if (rc != ORBFE_OK) return rc;
+    if (n_kfs == 0) return ORBFE_OK;
+    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
+    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    BowKfSearch a;
+    rc = bowkf_fill(ctx, &a, kf1, n_kfs, max_kf_n, nnratio, check_ori, d_match12, d_pairs, d_nmatches, d_status);
+    if (rc != ORBFE_OK) return rc;
+    a.k2 = orbfe_bow_keyframe{}; // per record, on the device
+    hipLaunchKernelGGL(bowkf_init_batch_kernel, dim3(a.k1.n > 0 ? (a.k1.n + 255) / 256 : 1, n_kfs), dim3(256), 0, s, a, d_kfs, max_kf_n);
+    if (a.k1.nnodes > 0) hipLaunchKernelGGL(bowkf_node_match_batch_kernel, dim3((a.k1.nnodes + 3) / 4, n_kfs), dim3(256), 0, s, a, d_kfs, max_kf_n);
+    hipLaunchKernelGGL(bowkf_tail_batch_kernel, dim3(n_kfs), dim3(1024), 0, s, a, d_kfs, max_kf_n);
     ORBFE_HIP_TRY(ctx, hipGetLastError());
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)

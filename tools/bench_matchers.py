@@ -58,6 +58,14 @@ host) and the same for orbfe_enqueue_search_by_projection_sim3, keyframes, grids
 16 enqueues queued back to back as GPU time between two events, and the SearchByProjection enqueue alone.  (a) and (b) are checked
 against the oracle.  Five repeats of each,
 interleaved; every repeat is the mean of 10 loops, its slowest loop beside it.
+    python3 tools/bench_matchers.py --bow-kf [--lib path/to/another/liborbfe.so]
+runs only the SearchByFboW(KeyFrame, KeyFrame) rows of ComputeSim3 (profiles/bow_kf_device.json): the current keyframe of 1500 keypoints
+(tests/bow_kf_scenes.py: kf1_of_family, 80 % with a map point) against K = 1, 3, 16 candidates of 1700 (perturbed copies of 1300 of its
+keypoints and 400 others, 90 % with a map point), vocabulary feature vectors at level 4, ratio 0.75, rotation check on.  Per K: (a) K
+synchronous orbfe_search_by_bow_kf calls, the C ABI called directly with arguments prepared once; (b) -- when the library has it -- one
+orbfe_enqueue_search_by_bow_kf_batch + one copy of counts, statuses and pairs into pinned memory + one stream synchronise, records
+uploaded outside the timed window; (c) the batch alone, queued back to back, as GPU time between two events.  (a) and (b) are checked
+against the oracle.  Ten repeats of each, interleaved; every repeat is the mean of 10 loops, its slowest loop beside it.
 """
 import json
 import os
@@ -989,6 +997,119 @@ def sim3_rows(out):
     ctx.close()
 
 
+def bow_kf_rows(out):
+    """Rows of --bow-kf; arguments prepared once."""
+    import ctypes as C
+    import gc
+    import torch
+    from orbslam2_amd import api
+    from orbslam2_amd import bow as B
+    from tests import bow_kf_scenes as S
+    dev = torch.device("cuda:0")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
+    KS, RATIO, ORI, REPS, REPEATS = (1, 3, 16), 0.75, True, 10, 10
+    ctx = api.Context(width=TM.W, height=TM.H, fx=TM.FX, fy=TM.FY, cx=TM.CX, cy=TM.CY, bf=TM.BF)
+    have = hasattr(ctx.L, "orbfe_enqueue_search_by_bow_kf_batch")
+    kf1 = S.kf1_of_family()
+    cands = [S._cand(kf1, 500 + k, 1300, 400, 0.03, 0.9, 5) for k in range(max(KS))]
+    refs = [S.oracle(kf1, c, RATIO, ORI) for c in cands]
+    n1 = len(kf1["d"])
+    out["scene"] = "current keyframe of %d keypoints (%d with a map point, %d nodes) against candidates of %d keypoints, matched per candidate %d .. %d" % (
+        n1, int(kf1["valid"].sum()), len(kf1["fv"][0]), len(cands[0]["d"]), min(r[1] for r in refs), max(r[1] for r in refs))
+    L = B._bind()
+    P = lambda a: a.ctypes.data_as(C.c_void_p)
+    side = lambda kf: (P(kf["fv"][0]), P(kf["fv"][1]), P(kf["fv"][2]), len(kf["fv"][0]), P(kf["valid"]), P(kf["d"]), P(kf["ang"]), len(kf["d"]))
+    h_out = [np.zeros(n1, np.int32) for _ in cands]
+    h_nm = C.c_int()
+    sync_args = [(ctx.h,) + side(kf1) + side(c) + (C.c_float(RATIO), int(ORI), P(h_out[k]), C.byref(h_nm)) for k, c in enumerate(cands)]
+
+    def sync_loop(K, check=False):
+        for k in range(K):
+            assert L.orbfe_search_by_bow_kf(*sync_args[k]) == 0
+            if check:
+                assert h_nm.value == refs[k][1] and np.array_equal(h_out[k], refs[k][0]), k
+
+    if have:
+        st = torch.cuda.Stream()
+        keep = []
+
+        def record(kf):
+            t = [up(kf["fv"][0]), up(kf["fv"][1]), up(kf["fv"][2]), up(kf["valid"]), up(kf["d"]), up(kf["ang"])]
+            keep.append(t)
+            return api.BowKeyframe(*[x.data_ptr() for x in t], None, len(kf["fv"][0]), len(kf["d"]))
+
+        rec1 = record(kf1)
+        recs = [record(c) for c in cands]
+        d_recs = up(np.frombuffer(bytes((api.BowKeyframe * len(recs))(*recs)), np.uint8))
+        max_n = max(len(c["d"]) for c in cands)
+        KM = max(KS)
+        d_match = torch.zeros(KM * n1, dtype=torch.int32, device=dev)
+        d_res = torch.zeros(2 * KM + KM * 2 * n1, dtype=torch.int32, device=dev)  # counts, statuses, pairs: one download
+        h_res = torch.zeros(2 * KM + KM * 2 * n1, dtype=torch.int32).pin_memory()
+        res = h_res.numpy()
+        rp = d_res.data_ptr()
+        torch.cuda.synchronize()
+
+        def enqueue(K):  # rows are laid out for K candidates: counts[K], statuses[K], pairs[K][2 * n1]
+            ctx.enqueue_search_by_bow_kf_batch(rec1, d_recs.data_ptr(), K, max_n, RATIO, ORI, d_match.data_ptr(), rp, rp + 4 * K, d_pairs=rp + 8 * K,
+                                               stream=st.cuda_stream)
+
+        def device_loop(K, check=False):
+            with torch.cuda.stream(st):
+                enqueue(K)
+                m = 2 * K + K * 2 * n1
+                h_res[:m].copy_(d_res[:m], non_blocking=True)
+                st.synchronize()  # Sim3Solver's constructor walks the pairs on the host here
+            if check:
+                for k in range(K):
+                    nm = int(res[k])
+                    assert res[K + k] == 0 and nm == refs[k][1], (K, k)
+                    assert np.array_equal(res[2 * K + k * 2 * n1:][:2 * nm], S.pairs_of(refs[k][0])), (K, k)
+
+    def loops(fn):
+        fn()
+        gc.collect()
+        gc.disable()  # the cyclic collector is off inside the window, as in the standard timeit module
+        try:
+            t = []
+            for _ in range(REPS):
+                t0 = time.perf_counter()
+                fn()
+                t.append((time.perf_counter() - t0) * 1e3)
+        finally:
+            gc.enable()
+        return round(sum(t) / REPS, 4), round(max(t), 4)
+
+    for K in KS:
+        sync_loop(K, check=True)
+        if have:
+            device_loop(K, check=True)
+        a_rows, a_worst, b_wall, b_worst, c_gpu = [], [], [], [], []
+        for _ in range(REPEATS):
+            m, w = loops(lambda: sync_loop(K))
+            a_rows.append(m); a_worst.append(w)
+            if have:
+                m, w = loops(lambda: device_loop(K))
+                b_wall.append(m); b_worst.append(w)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                for _ in range(REPS):
+                    enqueue(K)
+                e1.record(st)
+                st.synchronize()
+                c_gpu.append(round(e0.elapsed_time(e1) / REPS, 4))
+        rows = out["rows"]["K = %d" % K] = {"(a) %d x orbfe_search_by_bow_kf, synchronous, wall time" % K: {"ms_per_repeat": a_rows, "slowest_loop_ms": a_worst}}
+        if have:
+            rows["(b) orbfe_enqueue_search_by_bow_kf_batch + copy of counts and pairs into pinned memory + one synchronise, wall time"] = {
+                "ms_per_repeat": b_wall, "slowest_loop_ms": b_worst}
+            rows["(c) the batch alone, queued back to back, GPU time between two events"] = {"ms_per_repeat": c_gpu}
+            rows["median (a) / median (b)"] = round(float(np.median(a_rows) / np.median(b_wall)), 2)
+            rows["max (b) < min (a)"] = bool(max(b_wall) < min(a_rows))
+    if not have:
+        out["device"] = "not exported by this library"
+    ctx.close()
+
+
 def load_other_build(api, path):
     """api.load() on the library at `path`, which may be older than the package: the prototypes load() sets for entry points
     that build lacks land on stand-ins that are not kept, so hasattr(lib, name) is False afterwards and a call fails loudly."""
@@ -1038,6 +1159,12 @@ def main():
     if "--sim3" in sys.argv[1:]:
         out = {"unit": "ms per ComputeSim3 (3 candidates x 5 SearchBySim3 and one SearchByProjection)", "rows": {}}
         sim3_rows(out)
+        out["build_id"] = api.build_id()
+        print(json.dumps(out, indent=1))
+        return
+    if "--bow-kf" in sys.argv[1:]:
+        out = {"unit": "ms per group of K candidates", "rows": {}}
+        bow_kf_rows(out)
         out["build_id"] = api.build_id()
         print(json.dumps(out, indent=1))
         return
