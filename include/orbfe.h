@@ -882,6 +882,56 @@ int orbfe_enqueue_search_by_projection_sim3(orbfe_context *ctx, const orbfe_grid
         const int32_t *d_pt_valid /* [n_pts] */, const uint8_t *d_kf_matched /* [kf->n] or NULL: none */, float th,
         int32_t *d_pt_match /* [n_pts]: keypoint of kf or -1 */, int32_t *d_kf_match /* [kf->n]: the query that took keypoint k, or -1 */,
         int32_t *d_nmatches /* [1] */, int32_t *d_status /* [1] */, void *stream);
+/* ---- the writer of the map-point table (orbfe_map_point_device.hip): MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307)
+ * and MapPoint::UpdateNormalAndDepth (:330-371) for chosen rows of the table that orbfe_enqueue_fuse and the Sim3 matchers read, from
+ * observation lists over device-resident keyframes.  The contract of the enqueue matchers above holds: asynchronous on `stream` (NULL:
+ * the context's stream), nothing waits for the GPU, nothing is copied from host memory on the stream, nothing is allocated and no
+ * scratch of the context is used, so calls on different streams do not disturb each other. */
+#define ORBFE_MP_DESCRIPTOR   1   /* MapPoint::ComputeDistinctiveDescriptors */
+#define ORBFE_MP_NORMAL_DEPTH 2   /* MapPoint::UpdateNormalAndDepth */
+/* One keyframe as the map-point update reads it; 40 bytes, every pointer a device pointer.  desc / keys_un may be
+ * the very arrays of the keyframe's orbfe_tri_keyframe / orbfe_grid_keyframe.  Ow and bad change (bundle adjustment,
+ * culling): the caller patches the record on the stream. */
+typedef struct orbfe_obs_keyframe {
+    const uint8_t *desc;             /* 32 bytes per keypoint, 4-byte aligned */
+    const orbfe_keypoint *keys_un;   /* only .octave is read, only for a point's reference keyframe */
+    float Ow[3];                     /* KeyFrame::GetCameraCenter() */
+    int32_t n;                       /* keypoints */
+    int32_t bad;                     /* pKF->isBad() */
+    int32_t reserved;
+} orbfe_obs_keyframe;
+/* Update q (one wave) recomputes row r = d_row[q] (row q when d_row is NULL; the rows of one call must be distinct, which is the
+ * caller's promise) from its observation list L = entries d_obs_off[q] .. d_obs_off[q + 1] - 1 of d_obs_kf / d_obs_idx, given in the
+ * order in which the reference iterates mObservations (the tie rule depends on it).  An empty list writes nothing of row r.
+ * ORBFE_MP_DESCRIPTOR: G = the entries of L whose keyframe has bad == 0, in order; N = |G|; dist[i][j] = Hamming distance of descriptors
+ * i and j of G; median_i = element (int)(0.5 * (N - 1)) of row i sorted ascending (its own 0 included); the FIRST i with the smallest
+ * median wins and its 32 bytes become d_pt_desc row r.  d_best[q] (may be NULL) = the winner's position in L, or -1 when the descriptor
+ * row was not written (empty L, empty G, a faulty update, or `what` without ORBFE_MP_DESCRIPTOR).
+ * ORBFE_MP_NORMAL_DEPTH, over ALL entries of L (the reference does not test isBad there), floats by contract Q4 (a cv::norm is a double
+ * sum of double squares, left to right, and one sqrt; no FMA contraction): per entry in list order d = pos[r] - Ow,
+ * alpha = (float)(1.0 / norm(d)), acc_c = (float)(d_c * alpha) + acc_c from 0; then normal[r]_c = acc_c * (float)(1.0 / |L|),
+ * max_distance[r] = (float)norm(pos[r] - Ow_ref) * scale[level], min_distance[r] = max_distance[r] / scale[nlevels - 1], where the
+ * reference keyframe is entry d_ref[q] of L, level its keys_un[idx].octave, and the scale factors the context's (orbfe_get_tables).
+ * Columns that `what` does not select are neither read nor written; d_pos is read only under ORBFE_MP_NORMAL_DEPTH.
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL context or d_status; a negative n_kfs, n_upd, n_rows or n_obs; `what`
+ * outside 1..3; n_rows < n_upd with a NULL d_row; and under n_upd > 0 a NULL d_obs_off or d_pos, a NULL output column that `what`
+ * selects, a NULL d_ref under ORBFE_MP_NORMAL_DEPTH, a NULL d_kfs, d_obs_kf or d_obs_idx under n_obs > 0.  n_upd == 0 writes status 0
+ * and queues nothing else.
+ * d_status[1] = ORBFE_ERR_INVALID for what only the device can see, each checked before it is used as an address: a row outside
+ * [0, n_rows); an offset that is negative, descending or beyond n_obs; an obs_kf outside [0, n_kfs); an obs_idx outside [0, kf.n); a
+ * NULL desc in a record that an observation names or a NULL keys_un in a reference record; a d_ref[q] outside the list; an octave
+ * outside [0, nlevels).  A faulty update is skipped whole (its row untouched, d_best[q] = -1); every other update of the call is
+ * unaffected. */
+int orbfe_enqueue_update_map_points(orbfe_context *ctx,
+        const orbfe_obs_keyframe *d_kfs /* DEVICE array */, int n_kfs,
+        int n_upd, const int32_t *d_row /* [n_upd] table row per update, or NULL: update q is row q */, int n_rows,
+        const int32_t *d_obs_off /* [n_upd + 1] */, const int32_t *d_obs_kf /* [n_obs] index into d_kfs */,
+        const int32_t *d_obs_idx /* [n_obs] keypoint in that keyframe */, int n_obs,
+        const int32_t *d_ref /* [n_upd]: position INSIDE update q's list of mpRefKF's entry; read only under NORMAL_DEPTH */,
+        int what,
+        const float *d_pos, float *d_normal, float *d_max_distance, float *d_min_distance, uint8_t *d_pt_desc,
+        int32_t *d_best /* [n_upd], may be NULL: list position of the chosen descriptor, -1 = descriptor row untouched */,
+        int32_t *d_status /* [1] */, void *stream);
 /* KeyFrameDatabase::DetectLoopCandidates(KeyFrame *pKF, float minScore) (src/KeyFrameDatabase.cc:73-194; LoopClosing::DetectLoop,
  * src/LoopClosing.cc:131).  connected[k] != 0 marks the keyframes of pKF->GetConnectedKeyFrames() (may be NULL: none); covisibility
  * lists as for the relocalisation query.  Stateless: mLoopScore is only read for keyframes scored by the same call. */

@@ -43,6 +43,7 @@ EXPORTS = [
     "orbfe_enqueue_keyframe_grid", "orbfe_enqueue_fuse", "orbfe_enqueue_fuse_sim3",
     "orbfe_enqueue_search_by_sim3", "orbfe_enqueue_search_by_projection_sim3",
     "orbfe_enqueue_search_by_bow_kf", "orbfe_enqueue_search_by_bow_kf_batch",
+    "orbfe_enqueue_update_map_points",
 ]
 NUM_STAGES = 8
 STAGE_NAMES = ["ingest", "pyramid", "blur", "fast", "octree", "describe", "stereo_match", "stereo_median"]  # orbfe_stage_name()
@@ -94,6 +95,18 @@ class GridKeyframe(C.Structure):
 
 
 assert C.sizeof(GridKeyframe) == 64
+
+
+class ObsKeyframe(C.Structure):
+    """orbfe_obs_keyframe (include/orbfe.h): one keyframe as enqueue_update_map_points reads it, device pointers; an ARRAY of these
+    records lives in HBM (the keyframe directory), Ow and bad patched on the stream as the map changes."""
+    _fields_ = [("desc", C.c_void_p), ("keys_un", C.c_void_p), ("Ow", C.c_float * 3), ("n", C.c_int32), ("bad", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(ObsKeyframe) == 40
+OBS_KF_DTYPE = np.dtype([("desc", "<u8"), ("keys_un", "<u8"), ("Ow", "<f4", 3), ("n", "<i4"), ("bad", "<i4"), ("reserved", "<i4")])  # the same, as a numpy record
+assert OBS_KF_DTYPE.itemsize == 40
+MP_DESCRIPTOR, MP_NORMAL_DEPTH = 1, 2  # ORBFE_MP_*
 GRID_CELLS = 64 * 48  # FRAME_GRID_COLS * FRAME_GRID_ROWS: cell_off holds GRID_CELLS + 1 entries
 
 
@@ -266,6 +279,8 @@ def load():
     L.orbfe_enqueue_search_by_bow_kf.argtypes = [vp, C.POINTER(BowKeyframe), C.POINTER(BowKeyframe), C.c_float, C.c_int] + [vp] * 5
     L.orbfe_enqueue_search_by_bow_kf_batch.restype = C.c_int
     L.orbfe_enqueue_search_by_bow_kf_batch.argtypes = [vp, C.POINTER(BowKeyframe), vp, C.c_int, C.c_int, C.c_float, C.c_int] + [vp] * 5
+    L.orbfe_enqueue_update_map_points.restype = C.c_int
+    L.orbfe_enqueue_update_map_points.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int] + [vp] * 8
     _lib = L
     return L
 
@@ -747,6 +762,19 @@ class Context:
         """The same for ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) of LoopClosing::SearchAndFuse: Scw = [sR | s t] (3x4, host)."""
         self._enqueue_fuse(self.L.orbfe_enqueue_fuse_sim3, kf, Scw, n_pts, d_pt_index, n_rows, d_pos, d_normal, d_max_distance, d_min_distance,
                            d_pt_desc, d_pt_valid, th, d_best_idx, d_n_fused, d_status, stream)
+
+    def enqueue_update_map_points(self, d_kfs, n_kfs, n_upd, d_row, n_rows, d_obs_off, d_obs_kf, d_obs_idx, n_obs, d_ref, what, d_pos, d_normal,
+                                  d_max_distance, d_min_distance, d_pt_desc, d_best, d_status, stream=0):
+        """MapPoint::ComputeDistinctiveDescriptors (what & MP_DESCRIPTOR) and MapPoint::UpdateNormalAndDepth (what & MP_NORMAL_DEPTH) for
+        n_upd rows of the map-point table in HBM, asynchronous on `stream`.  d_kfs: device array of n_kfs ObsKeyframe records; update q
+        rewrites row d_row[q] (0: row q) from the observations d_obs_off[q] .. d_obs_off[q + 1] - 1 of d_obs_kf / d_obs_idx, given in
+        the order of the reference's mObservations; d_ref[q] is the position of mpRefKF's entry inside that list.  d_best (0: not
+        wanted) receives the list position of the chosen descriptor, or -1.  Every argument but the counts is a raw device pointer."""
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_update_map_points(
+            self.h, v(d_kfs or None), n_kfs, n_upd, v(d_row or None), n_rows, v(d_obs_off or None), v(d_obs_kf or None), v(d_obs_idx or None), n_obs,
+            v(d_ref or None), what, v(d_pos or None), v(d_normal or None), v(d_max_distance or None), v(d_min_distance or None), v(d_pt_desc or None),
+            v(d_best or None), v(d_status or None), v(stream or None)))
 
     def enqueue_search_by_sim3(self, kf1, T1w, d_pts1, kf2, T2w, d_pts2, s12, R12, t12, th, d_match12, d_n_found, d_status, stream=0):
         """ORBmatcher::SearchBySim3 on two device-resident keyframes (GridKeyframe records on the host, device pointers inside),

@@ -66,6 +66,15 @@ synchronous orbfe_search_by_bow_kf calls, the C ABI called directly with argumen
 orbfe_enqueue_search_by_bow_kf_batch + one copy of counts, statuses and pairs into pinned memory + one stream synchronise, records
 uploaded outside the timed window; (c) the batch alone, queued back to back, as GPU time between two events.  (a) and (b) are checked
 against the oracle.  Ten repeats of each, interleaved; every repeat is the mean of 10 loops, its slowest loop beside it.
+    python3 tools/bench_matchers.py --map-points
+runs only the map-point update rows (profiles/map_points_device.json): the closing step of SearchInNeighbors, ComputeDistinctiveDescriptors
+and UpdateNormalAndDepth for 1500 points with 2..40 observations each over 60 keyframes of 1500 keypoints (tests/map_point_scenes.py, 5 %
+of the keyframes bad).  (a) orbslam2_amd/host/MapPointUpdate.h on one host thread over host copies of the keyframes, then the upload of
+the 1500 rows (normal, both distances, descriptor) from pinned memory and one stream synchronise; (b) the observation lists (offsets,
+keyframe, keypoint, reference entry: one pinned block) uploaded, orbfe_enqueue_update_map_points, the 4-byte status downloaded, one
+stream synchronise -- the keyframe directory is resident, as it is for the matchers; (c) the enqueue alone, queued back to back, as
+GPU time between two events.  (b)'s table is compared with (a)'s bit for bit.  Five repeats of each, interleaved; every repeat is the
+mean of 10 loops, its slowest loop beside it.
 """
 import json
 import os
@@ -1110,6 +1119,127 @@ def bow_kf_rows(out):
     ctx.close()
 
 
+def map_point_rows(out):
+    """Rows of --map-points; arguments prepared once."""
+    import ctypes as C
+    import gc
+    import subprocess
+    import tempfile
+    import torch
+    from orbslam2_amd import api
+    from tests import map_point_scenes as S
+    dev = torch.device("cuda:0")
+    REPS, REPEATS, WHAT = 10, 5, 3
+    ctx = api.Context(width=TM.W, height=TM.H, fx=TM.FX, fy=TM.FY, cx=TM.CX, cy=TM.CY, bf=TM.BF)
+    scale = ctx.tables()["scale"]
+    rng = np.random.default_rng(8)
+    ns, cnt = np.unique(rng.integers(2, 41, 1500), return_counts=True)
+    s = S.build(dict(zip(ns.tolist(), cnt.tolist())), n_kfs=60, kp_range=(1500, 1500), bad_fraction=0.05, seed=9, scale=scale)
+    n_upd, n_obs, n_kfs = len(s["n_of"]), len(s["obs_kf"]), len(s["kf_n"])
+    out["scene"] = "%d points, %d observations (2..40 per point), %d keyframes of 1500 keypoints, %d of them bad" % (n_upd, n_obs, n_kfs, int(s["kf_bad"].sum()))
+    # the host form: MapPointUpdate.h behind one C symbol, built here
+    so = os.path.join(os.environ.get("BENCH_OUT") or tempfile.mkdtemp(), "map_point_host_shim.so")
+    subprocess.run(["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tools", "map_point_host_shim.cpp")], check=True)
+    host = C.CDLL(so).map_point_update_host
+    host.restype = C.c_int
+    P = lambda a: a.ctypes.data_as(C.c_void_p)
+    first = np.concatenate([[0], np.cumsum(s["kf_n"])[:-1]]).astype(np.int64)
+    h_desc = np.ascontiguousarray(np.concatenate(s["kf_desc"]))
+    h_keys = np.zeros(len(h_desc), O.KP_DTYPE)
+    h_keys["octave"] = np.concatenate(s["kf_octave"])
+
+    def records(desc_ptr, keys_ptr):
+        rec = np.zeros(n_kfs, api.OBS_KF_DTYPE)
+        rec["desc"], rec["keys_un"] = desc_ptr + 32 * first, keys_ptr + O.KP_DTYPE.itemsize * first
+        rec["Ow"], rec["n"], rec["bad"] = s["Ow"], s["kf_n"], s["kf_bad"]
+        return rec
+
+    h_rec = records(h_desc.ctypes.data, h_keys.ctypes.data)
+    table = S.fresh_table(s)
+    pin = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).pin_memory()
+    h_cols = {k: pin(table[k]) for k in ("normal", "max_d", "min_d", "desc")}  # (a) computes into pinned memory: the upload reads it in place
+    d_cols_a = {k: torch.zeros_like(v, device=dev) for k, v in h_cols.items()}
+    d_cols_b = {k: v.to(dev) for k, v in h_cols.items()}
+    h_best = np.zeros(n_upd, np.int32)
+    host_args = (P(h_rec), n_kfs, n_upd, None, n_upd, P(s["obs_off"]), P(s["obs_kf"]), P(s["obs_idx"]), n_obs, P(s["ref"]), WHAT, P(scale), len(scale),
+                 P(s["pos"])) + tuple(C.c_void_p(h_cols[k].data_ptr()) for k in ("normal", "max_d", "min_d", "desc")) + (P(h_best),)
+    st = torch.cuda.Stream()
+
+    def host_loop():
+        assert host(*host_args) == 0
+        with torch.cuda.stream(st):
+            for k in h_cols:
+                d_cols_a[k].copy_(h_cols[k], non_blocking=True)
+            st.synchronize()
+
+    # the device form: directory resident, the lists travel per call
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
+    d_desc, d_keys, d_pos = up(h_desc), up(h_keys), up(s["pos"])
+    d_rec = up(records(d_desc.data_ptr(), d_keys.data_ptr()))
+    lists = np.concatenate([s["obs_off"], s["obs_kf"], s["obs_idx"], s["ref"]]).astype(np.int32)
+    h_lists = torch.from_numpy(lists).pin_memory()
+    d_lists = torch.zeros_like(h_lists, device=dev)
+    lp = d_lists.data_ptr()
+    p_off, p_kf, p_idx, p_ref = lp, lp + 4 * (n_upd + 1), lp + 4 * (n_upd + 1 + n_obs), lp + 4 * (n_upd + 1 + 2 * n_obs)
+    d_best, d_status = torch.zeros(n_upd, dtype=torch.int32, device=dev), torch.full((1,), -9, dtype=torch.int32, device=dev)
+    h_status = torch.full((1,), -9, dtype=torch.int32).pin_memory()
+    torch.cuda.synchronize()
+
+    def enqueue():
+        ctx.enqueue_update_map_points(d_rec.data_ptr(), n_kfs, n_upd, 0, n_upd, p_off, p_kf, p_idx, n_obs, p_ref, WHAT, d_pos.data_ptr(),
+                                      d_cols_b["normal"].data_ptr(), d_cols_b["max_d"].data_ptr(), d_cols_b["min_d"].data_ptr(),
+                                      d_cols_b["desc"].data_ptr(), d_best.data_ptr(), d_status.data_ptr(), stream=st.cuda_stream)
+
+    def device_loop():
+        with torch.cuda.stream(st):
+            d_lists.copy_(h_lists, non_blocking=True)
+            enqueue()
+            h_status.copy_(d_status, non_blocking=True)
+            st.synchronize()
+        assert int(h_status[0]) == 0
+
+    host_loop(); device_loop()
+    for k in h_cols:
+        assert torch.equal(d_cols_a[k], d_cols_b[k]), "column %s: the device's table differs from the host form's" % k
+    assert np.array_equal(d_best.cpu().numpy(), h_best)
+    out["checked"] = "the device's table and winners equal the host form's bit for bit (%d descriptor rows written)" % int((h_best >= 0).sum())
+
+    def loops(fn):
+        fn()
+        gc.collect()
+        gc.disable()  # the cyclic collector is off inside the window, as in the standard timeit module
+        try:
+            t = []
+            for _ in range(REPS):
+                t0 = time.perf_counter()
+                fn()
+                t.append((time.perf_counter() - t0) * 1e3)
+        finally:
+            gc.enable()
+        return round(sum(t) / REPS, 4), round(max(t), 4)
+
+    a_rows, a_worst, b_wall, b_worst, c_gpu = [], [], [], [], []
+    for _ in range(REPEATS):
+        m, w = loops(host_loop)
+        a_rows.append(m); a_worst.append(w)
+        m, w = loops(device_loop)
+        b_wall.append(m); b_worst.append(w)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(REPS):
+            enqueue()
+        e1.record(st)
+        st.synchronize()
+        c_gpu.append(round(e0.elapsed_time(e1) / REPS, 4))
+    rows = out["rows"]
+    rows["(a) MapPointUpdate.h on one host thread + upload of the %d rows + one synchronise, wall time" % n_upd] = {"ms_per_repeat": a_rows, "slowest_loop_ms": a_worst}
+    rows["(b) upload of the observation lists + orbfe_enqueue_update_map_points + status download + one synchronise, wall time"] = {
+        "ms_per_repeat": b_wall, "slowest_loop_ms": b_worst}
+    rows["(c) the enqueue alone, queued back to back, GPU time between two events"] = {"ms_per_repeat": c_gpu}
+    rows["median (a) / median (b)"] = round(float(np.median(a_rows) / np.median(b_wall)), 2)
+    ctx.close()
+
+
 def load_other_build(api, path):
     """api.load() on the library at `path`, which may be older than the package: the prototypes load() sets for entry points
     that build lacks land on stand-ins that are not kept, so hasattr(lib, name) is False afterwards and a call fails loudly."""
@@ -1159,6 +1289,12 @@ def main():
     if "--sim3" in sys.argv[1:]:
         out = {"unit": "ms per ComputeSim3 (3 candidates x 5 SearchBySim3 and one SearchByProjection)", "rows": {}}
         sim3_rows(out)
+        out["build_id"] = api.build_id()
+        print(json.dumps(out, indent=1))
+        return
+    if "--map-points" in sys.argv[1:]:
+        out = {"unit": "ms per update of 1500 map points", "rows": {}}
+        map_point_rows(out)
         out["build_id"] = api.build_id()
         print(json.dumps(out, indent=1))
         return

@@ -337,6 +337,37 @@ void dump_primitives(const std::string &out_dir)
             w.put("undist" + std::to_string(nd) + "_out", F32, {200, 2}, m.data);
         }
     }
+    // case map_point: the MatExpr arithmetic of MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:348-369) on the fixed three-observation
+    // point of tests/test_map_point_model.py (reference keyframe: observation 1, level 2, scale 1.2, 8 levels).  DESIGN.md section 2 reads
+    // `Mat / double` as a scale by 1./s inside a scaleAdd and `Mat / int` as convertTo with a float scale; the model's bits for that
+    // reading are normal = 3f0c9862 bf1e6a48 becd6254, max = 40b45108, min = 3fc94ac6 (true divisions give 3f0c9861 bf1e6a47 for x, y).
+    {
+        const float pos[3] = {2.5f, -3.5f, -2.5f};
+        const float centres[3][3] = {{-1.0f, -1.25f, 1.25f}, {1.5f, 0.25f, -2.0f}, {-1.75f, -0.75f, -0.25f}};
+        auto vec3 = [](const float *v) { cv::Mat m(3, 1, CV_32F); for (int c = 0; c < 3; c++) m.at<float>(c) = v[c]; return m; };
+        const cv::Mat Pos = vec3(pos);
+        cv::Mat normal = cv::Mat::zeros(3, 1, CV_32F);
+        int n = 0;
+        for (int k = 0; k < 3; k++) {
+            const cv::Mat Owi = vec3(centres[k]);
+            cv::Mat normali = Pos - Owi;
+            normal = normal + normali / cv::norm(normali);
+            n++;
+        }
+        const cv::Mat PC = Pos - vec3(centres[1]);
+        const float dist = cv::norm(PC);
+        float sf[8];
+        sf[0] = 1.0f;
+        for (int l = 1; l < 8; l++) sf[l] = sf[l - 1] * 1.2f; // ORBextractor's mvScaleFactor
+        const float mfMaxDistance = dist * sf[2];
+        const float mfMinDistance = mfMaxDistance / sf[7];
+        cv::Mat mNormalVector = normal / n;
+        float out[5] = {mNormalVector.at<float>(0), mNormalVector.at<float>(1), mNormalVector.at<float>(2), mfMaxDistance, mfMinDistance};
+        w.put("map_point_normal_max_min", F32, {5}, out);
+        uint32_t bits[5];
+        std::memcpy(bits, out, sizeof(bits));
+        std::printf("map_point normal %08x %08x %08x mfMaxDistance %08x mfMinDistance %08x\n", bits[0], bits[1], bits[2], bits[3], bits[4]);
+    }
     std::printf("primitives written (OpenCV %s)\n", CV_VERSION);
 }
 } // namespace

@@ -46,15 +46,20 @@ public:
     Mat clone() const;
     void convertTo(Mat &dst, int type) const;
     static MatExpr ones(int r, int c, int type);
+    static MatExpr zeros(int r, int c, int type);
     static MatExpr eye(int r, int c, int type);
 };
 class MatExpr { public: operator Mat() const; };
 MatExpr operator-(const Mat &a, const MatExpr &b);
 MatExpr operator*(float s, const MatExpr &m);
+MatExpr operator-(const Mat &a, const Mat &b);
+MatExpr operator+(const Mat &a, const MatExpr &b);
+MatExpr operator/(const Mat &a, double s);
 typedef const Mat &InputArray;
 typedef Mat &OutputArray;
 enum { NORM_L1 = 2 };
 enum { BORDER_REFLECT_101 = 4 };
 double norm(const Mat &a, const Mat &b, int type);
+double norm(const Mat &a);
 float fastAtan2(float y, float x);
 } // namespace cv
