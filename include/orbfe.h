@@ -715,8 +715,10 @@ typedef struct orbfe_tri_keyframe {
  * (idx1, idx2) in ascending idx1, entries from 2 * count on untouched; d_nmatches[1]; d_status[1].  Every result equals
  * orbfe_search_for_triangulation on the same inputs.
  * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:237-268) calls this once per neighbour and adds the triangulated points to
- * KF1 between two neighbours, so kf1->has_mp is an array the caller patches ON THE STREAM between two calls; that dependence is
- * why there is no batch over neighbours.
+ * KF1 between two neighbours, so kf1->has_mp changes ON THE STREAM between two calls; that dependence is why there is no batch over
+ * neighbours.  orbfe_enqueue_triangulate_pairs (below) is that change on the device: it reads d_pairs and d_nmatches as this call
+ * leaves them, runs the triangulation tests of :286-431 and sets has_mp of both keyframes, so the loop is search, triangulate, search,
+ * ... queued on one stream.  A caller that runs the tests on the host instead patches has_mp itself between two calls, as before.
  * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL record, matrix or output other than d_pairs, a negative n or
  * nnodes, n > 65535, a NULL array in a record with nnodes > 0.  d_status = ORBFE_ERR_INVALID for what only the device can see: node
  * ids not strictly ascending, a CSR offset negative, descending or beyond n, a feature index outside [0, n), an octave outside
@@ -932,6 +934,84 @@ int orbfe_enqueue_update_map_points(orbfe_context *ctx,
         const float *d_pos, float *d_normal, float *d_max_distance, float *d_min_distance, uint8_t *d_pt_desc,
         int32_t *d_best /* [n_upd], may be NULL: list position of the chosen descriptor, -1 = descriptor row untouched */,
         int32_t *d_status /* [1] */, void *stream);
+/* ---- the triangulation stage of LocalMapping::CreateNewMapPoints (orbfe_triangulate_device.hip): src/LocalMapping.cc:286-450 for the
+ * pairs that orbfe_enqueue_search_for_triangulation left in HBM.  The contract of the enqueue matchers above holds: asynchronous on
+ * `stream` (NULL: the context's stream), nothing waits for the GPU, nothing is copied from host memory on the stream, nothing is
+ * allocated and no scratch of the context is used.  At most three launches: the reset of the status, one lane per pair, one wave that
+ * replays the created pairs in pair order.
+ *
+ * One keyframe as this call reads it: a HOST struct of device pointers and host scalars, read before the call returns (the scalars
+ * travel as kernel arguments).  keys_un, u_right and has_mp are the arrays of the keyframe's orbfe_tri_keyframe; has_mp is WRITABLE
+ * here.  136 bytes. */
+typedef struct orbfe_newpoint_keyframe {
+    const orbfe_keypoint *keys_un;   /* mvKeysUn: x, y, octave are read */
+    const orbfe_keypoint *keys;      /* mvKeys: KeyFrame::UnprojectStereo reads the DISTORTED keypoint (src/KeyFrame.cc:614-615); may equal keys_un */
+    const float *u_right;            /* mvuRight, < 0 = monocular keypoint */
+    const float *depth;              /* mvDepth; read only where u_right >= 0 */
+    const float *cos_stereo;         /* the reference's cos(2 * atan2(mb / 2, mvDepth[i])) (:312, :314), computed by the caller once when the
+                                      * keyframe is made (mb and mvDepth never change); read only where u_right >= 0 */
+    uint8_t *has_mp;                 /* GetMapPoint(i) != NULL; written (1 only) under patch_has_mp */
+    float Tcw[12];                   /* 3x4, row major */
+    float Ow[3];                     /* GetCameraCenter(): handed over, not recomputed */
+    float fx, fy, cx, cy, invfx, invfy;
+    int32_t n;                       /* keypoints */
+} orbfe_newpoint_keyframe;
+/* kf1 is mpCurrentKeyFrame, kf2 the neighbour.  mbf is the CURRENT keyframe's (the reference uses it for both, :380 and :406);
+ * ratio_factor = 1.5f * mfScaleFactor (:232); d_pairs / d_npairs[1] are (idx1, idx2) pairs and their count as
+ * orbfe_enqueue_search_for_triangulation leaves them -- the count is read ON THE DEVICE; max_pairs is a host bound of it that sizes the
+ * grid.  mvLevelSigma2 and mvScaleFactors are the context's.
+ * Outputs (device):
+ *   d_code[max_pairs]     per pair; entries from the count on untouched.  A point is created iff the code is <= 2:
+ *                         0 created by linear triangulation, 1 by UnprojectStereo of KF1, 2 by UnprojectStereo of KF2, 3 no stereo and low
+ *                         parallax (:349), 4 w == 0 (:333), 5 z1 <= 0, 6 z2 <= 0, 7 reprojection in KF1, 8 reprojection in KF2, 9 zero
+ *                         distance, 10 scale ratio, 11 faulty entry
+ *   d_x3d[max_pairs][3]   written for created pairs only
+ *   d_new[3 * max_pairs]  (idx1, idx2, row) of the k-th created pair IN PAIR ORDER -- the order in which the reference constructs the
+ *                         MapPoints and fills mlpRecentAddedMapPoints -- entries from 3 * nnew on untouched; d_nnew[1] = their number
+ *   table append, optional: with d_pos != NULL (the position column of the map-point table, n_rows rows), row = *d_rows_used + k and
+ *                         d_pos[row] = x3D; d_rows_used[1] is a DEVICE counter that is read and advanced by nnew (the host cannot know
+ *                         neighbour k + 1's base row before neighbour k has run).  With d_pos == NULL row = -1 and neither the table
+ *                         nor the counter is touched.  *d_rows_used + nnew > n_rows: d_status = ORBFE_ERR_CAPACITY; d_code, d_x3d,
+ *                         d_new (rows -1) and d_nnew are still written; table, counter and both has_mp arrays stay untouched.
+ *   patch_has_mp != 0:    kf1->has_mp[idx1] = kf2->has_mp[idx2] = 1 for every created pair (AddMapPoint, :439-440)
+ *   d_status[1]
+ * max_pairs == 0 or a count of 0: status 0 and d_nnew = 0.
+ * Not in this call: ComputeDistinctiveDescriptors / UpdateNormalAndDepth of the new points (:442-444) are a later
+ * orbfe_enqueue_update_map_points over the rows of d_new (its lists and n_upd are host arguments); MapPoint / Map bookkeeping, the
+ * baseline test (:244-261) and ComputeF12 stay the caller's.
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL context, record, d_pairs, d_npairs, d_code, d_x3d, d_new, d_nnew or
+ * d_status; a negative n, max_pairs or n_rows; max_pairs > 65535; a NULL array in a record when max_pairs > 0; d_pos without
+ * d_rows_used.  d_status = ORBFE_ERR_INVALID for what only the device can see, each checked before it becomes an address: a count
+ * outside [0, max_pairs] (then nothing else is written); an idx1 or idx2 outside [0, n), an octave outside [0, nlevels), or
+ * u_right >= 0 without depth > 0 (the reference would dereference an empty cv::Mat): code 11, that pair skipped, every other pair
+ * unaffected; a negative *d_rows_used (treated as a table without room, but reported as ORBFE_ERR_INVALID).
+ *
+ * Arithmetic (contract Q4: no contraction, IEEE divide and sqrt; the cv::Mat steps as DESIGN.md section 4k states them; the same
+ * operation order in tests/triangulate_model.py, orbslam2_amd/host/Triangulate.h and the kernel, which agree bit for bit):
+ *   xn = ((x - cx) * invfx, (y - cy) * invfy, 1) in float.  A cv::Mat product (Rwc * xn; Rwc * x3Dc + Ow, Ow added in double) is a
+ *   double sum over k in index order, rounded once to float.  Mat::dot is a double sum; cv::norm a double sum of double squares and one
+ *   sqrt.  cosParallaxRays = (float)(dot / (norm1 * norm2)).  The branches of :307-349 are literal, `else if (bStereo2)` included: KF2's
+ *   stereo cosine is used only when KF1's keypoint is monocular.  The device evaluates no transcendental.
+ *   A.row(r) = xn_c * Tcw.row(2) - Tcw.row(r'): a float multiply, then a float subtract, per element.  x3D = v[0..2] * (float)(1.0 / w)
+ *   (a MatExpr scalar divide is a scale).  z, x, y = (float)(double dot + float); invz = (float)(1.0 / z); u = fx * x * invz + cx in
+ *   float, left to right; the chi-square tests compare the float sum, promoted, with 5.991 * (double)sigma2 / 7.8 * (double)sigma2; the
+ *   scale gate is float as written in :430.
+ *   vt.row(3) of cv::SVD::compute(A, ..., MODIFY_A | FULL_UV) is a one-sided (Hestenes) Jacobi on the columns of A:
+ *   At[i][k] = A[k][i], Vt = I (float), W[i] = sum_k (double)At[i][k]^2; at most 30 sweeps over (i, j), i < j, in lexicographic
+ *   order: p = sum_k (double)At[i][k] * At[j][k]; skipped when |p| <= eps * sqrt(W[i] * W[j]), eps = 2 * FLT_EPSILON as a double;
+ *   otherwise p *= 2, beta = W[i] - W[j], gamma = sqrt(p * p + beta * beta) (a plain double sqrt, not hypot); beta < 0:
+ *   s = (float)sqrt(((gamma - beta) * 0.5) / gamma), c = (float)(p / (gamma * s * 2)); else c = (float)sqrt((gamma + beta) / (gamma * 2)),
+ *   s = (float)(p / (gamma * c * 2)); rows i and j of At and of Vt are rotated in float, t0 = c * a + s * b, t1 = -s * a + c * b, each
+ *   product rounded, then the sum; W[i], W[j] = the new double square sums.  A sweep without a rotation ends the loop.  Then
+ *   W[i] = sqrt(sum_k At[i][k]^2) and a selection sort, descending, strict < (j = i; for k > i: if (W[j] < W[k]) j = k; swap), which
+ *   carries the rows of Vt; the answer is Vt row 3. */
+int orbfe_enqueue_triangulate_pairs(orbfe_context *ctx,
+        const orbfe_newpoint_keyframe *kf1 /* host */, const orbfe_newpoint_keyframe *kf2 /* host */,
+        float mbf, float ratio_factor,
+        const int32_t *d_pairs /* [2 * max_pairs] */, const int32_t *d_npairs /* [1] */, int max_pairs,
+        uint8_t *d_code /* [max_pairs] */, float *d_x3d /* [max_pairs][3] */, int32_t *d_new /* [3 * max_pairs] */, int32_t *d_nnew /* [1] */,
+        float *d_pos /* [n_rows][3] or NULL */, int n_rows, int32_t *d_rows_used /* [1]; NULL only with d_pos == NULL */,
+        int patch_has_mp, int32_t *d_status /* [1] */, void *stream);
 /* KeyFrameDatabase::DetectLoopCandidates(KeyFrame *pKF, float minScore) (src/KeyFrameDatabase.cc:73-194; LoopClosing::DetectLoop,
  * src/LoopClosing.cc:131).  connected[k] != 0 marks the keyframes of pKF->GetConnectedKeyFrames() (may be NULL: none); covisibility
  * lists as for the relocalisation query.  Stateless: mLoopScore is only read for keyframes scored by the same call. */

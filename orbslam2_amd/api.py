@@ -44,6 +44,7 @@ EXPORTS = [
     "orbfe_enqueue_search_by_sim3", "orbfe_enqueue_search_by_projection_sim3",
     "orbfe_enqueue_search_by_bow_kf", "orbfe_enqueue_search_by_bow_kf_batch",
     "orbfe_enqueue_update_map_points",
+    "orbfe_enqueue_triangulate_pairs",
 ]
 NUM_STAGES = 8
 STAGE_NAMES = ["ingest", "pyramid", "blur", "fast", "octree", "describe", "stereo_match", "stereo_median"]  # orbfe_stage_name()
@@ -107,6 +108,17 @@ assert C.sizeof(ObsKeyframe) == 40
 OBS_KF_DTYPE = np.dtype([("desc", "<u8"), ("keys_un", "<u8"), ("Ow", "<f4", 3), ("n", "<i4"), ("bad", "<i4"), ("reserved", "<i4")])  # the same, as a numpy record
 assert OBS_KF_DTYPE.itemsize == 40
 MP_DESCRIPTOR, MP_NORMAL_DEPTH = 1, 2  # ORBFE_MP_*
+
+
+class NewpointKeyframe(C.Structure):
+    """orbfe_newpoint_keyframe (include/orbfe.h): one keyframe of enqueue_triangulate_pairs; device pointers (has_mp is written) and the
+    host scalars of the keyframe: Tcw (3x4, row major), GetCameraCenter() and the camera."""
+    _fields_ = [("keys_un", C.c_void_p), ("keys", C.c_void_p), ("u_right", C.c_void_p), ("depth", C.c_void_p), ("cos_stereo", C.c_void_p),
+                ("has_mp", C.c_void_p), ("Tcw", C.c_float * 12), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float), ("n", C.c_int32)]
+
+
+assert C.sizeof(NewpointKeyframe) == 136
 GRID_CELLS = 64 * 48  # FRAME_GRID_COLS * FRAME_GRID_ROWS: cell_off holds GRID_CELLS + 1 entries
 
 
@@ -279,6 +291,8 @@ def load():
     L.orbfe_enqueue_search_by_bow_kf.argtypes = [vp, C.POINTER(BowKeyframe), C.POINTER(BowKeyframe), C.c_float, C.c_int] + [vp] * 5
     L.orbfe_enqueue_search_by_bow_kf_batch.restype = C.c_int
     L.orbfe_enqueue_search_by_bow_kf_batch.argtypes = [vp, C.POINTER(BowKeyframe), vp, C.c_int, C.c_int, C.c_float, C.c_int] + [vp] * 5
+    L.orbfe_enqueue_triangulate_pairs.restype = C.c_int
+    L.orbfe_enqueue_triangulate_pairs.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp]
     L.orbfe_enqueue_update_map_points.restype = C.c_int
     L.orbfe_enqueue_update_map_points.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int] + [vp] * 8
     _lib = L
@@ -722,7 +736,8 @@ class Context:
                                          d_match12, d_nmatches, d_status, d_pairs=0, stream=0):
         """ORBmatcher::SearchForTriangulation on two device-resident keyframes (TriKeyframe records on the host, device pointers inside),
         asynchronous on `stream`.  F12 (3x3), Cw1 (3), T2w (3x4) are host arrays read before the call returns.  One call per neighbour:
-        the caller patches kf1.has_mp on the stream between two calls (CreateNewMapPoints adds points in between)."""
+        kf1.has_mp changes on the stream between two calls (CreateNewMapPoints adds points in between): enqueue_triangulate_pairs sets it,
+        or the caller patches it."""
         v = C.c_void_p
         f = np.ascontiguousarray(F12, np.float32); c = np.ascontiguousarray(Cw1, np.float32); t = np.ascontiguousarray(T2w, np.float32)
         assert f.size == 9 and c.size == 3 and t.size == 12
@@ -775,6 +790,19 @@ class Context:
             self.h, v(d_kfs or None), n_kfs, n_upd, v(d_row or None), n_rows, v(d_obs_off or None), v(d_obs_kf or None), v(d_obs_idx or None), n_obs,
             v(d_ref or None), what, v(d_pos or None), v(d_normal or None), v(d_max_distance or None), v(d_min_distance or None), v(d_pt_desc or None),
             v(d_best or None), v(d_status or None), v(stream or None)))
+
+    def enqueue_triangulate_pairs(self, kf1, kf2, mbf, ratio_factor, d_pairs, d_npairs, max_pairs, d_code, d_x3d, d_new, d_nnew, d_status,
+                                  d_pos=0, n_rows=0, d_rows_used=0, patch_has_mp=1, stream=0):
+        """The triangulation stage of LocalMapping::CreateNewMapPoints for the pairs enqueue_search_for_triangulation left in HBM
+        (d_pairs, and d_npairs read on the device; max_pairs bounds it), asynchronous on `stream`.  kf1 / kf2: NewpointKeyframe records on
+        the host (None passes as a NULL record).  d_code[max_pairs] (uint8; a point is created iff <= 2), d_x3d[max_pairs][3],
+        d_new[3 * max_pairs] = (idx1, idx2, row) of the created pairs in pair order, d_nnew[1], d_status[1]; with d_pos the positions
+        are appended to the table from row *d_rows_used on (a device counter, advanced); patch_has_mp sets has_mp of both keyframes."""
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_triangulate_pairs(
+            self.h, None if kf1 is None else C.byref(kf1), None if kf2 is None else C.byref(kf2), mbf, ratio_factor, v(d_pairs or None),
+            v(d_npairs or None), max_pairs, v(d_code or None), v(d_x3d or None), v(d_new or None), v(d_nnew or None), v(d_pos or None), n_rows,
+            v(d_rows_used or None), int(patch_has_mp), v(d_status or None), v(stream or None)))
 
     def enqueue_search_by_sim3(self, kf1, T1w, d_pts1, kf2, T2w, d_pts2, s12, R12, t12, th, d_match12, d_n_found, d_status, stream=0):
         """ORBmatcher::SearchBySim3 on two device-resident keyframes (GridKeyframe records on the host, device pointers inside),

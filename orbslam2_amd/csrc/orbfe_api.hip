@@ -1355,3 +1355,39 @@ try {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)
+
+// The triangulation stage of LocalMapping::CreateNewMapPoints on device-resident keyframes (kernels: orbfe_triangulate_device.hip).
+extern "C" int orbfe_enqueue_triangulate_pairs(orbfe_context *ctx, const orbfe_newpoint_keyframe *kf1, const orbfe_newpoint_keyframe *kf2, float mbf,
+                                               float ratio_factor, const int32_t *d_pairs, const int32_t *d_npairs, int max_pairs, uint8_t *d_code,
+                                               float *d_x3d, int32_t *d_new, int32_t *d_nnew, float *d_pos, int n_rows, int32_t *d_rows_used,
+                                               int patch_has_mp, int32_t *d_status, void *stream)
+try {
+    ORBFE_ENTRY(ctx);
+    // what the arguments alone show is refused first, so that the refusals can be told apart without a device
+    if (!kf1 || !kf2) return fail(ctx, ORBFE_ERR_INVALID, "triangulate_pairs: null keyframe record");
+    if (!d_pairs || !d_npairs) return fail(ctx, ORBFE_ERR_INVALID, "triangulate_pairs: null d_pairs or d_npairs");
+    if (!d_code || !d_x3d || !d_new || !d_nnew || !d_status) return fail(ctx, ORBFE_ERR_INVALID, "triangulate_pairs: null output");
+    if (kf1->n < 0 || kf2->n < 0 || max_pairs < 0 || n_rows < 0) return fail(ctx, ORBFE_ERR_INVALID, "triangulate_pairs: negative count");
+    if (max_pairs > 65535) return fail(ctx, ORBFE_ERR_INVALID, "triangulate_pairs: max_pairs = %d > 65535", max_pairs);
+    if (max_pairs > 0)
+        for (const orbfe_newpoint_keyframe *kf : {kf1, kf2})
+            if (!kf->keys_un || !kf->keys || !kf->u_right || !kf->depth || !kf->cos_stereo || !kf->has_mp)
+                return fail(ctx, ORBFE_ERR_INVALID, "triangulate_pairs: null array in a keyframe record");
+    if (d_pos && !d_rows_used) return fail(ctx, ORBFE_ERR_INVALID, "triangulate_pairs: d_pos without d_rows_used");
+    if (!ctx) return fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    orbfe_triangulate_args a;
+    a.nlevels = ctx->cfg.nlevels;
+    if (a.nlevels < 1 || a.nlevels > ORBFE_MAX_LEVELS) return fail(ctx, ORBFE_ERR_UNSUPPORTED, "nlevels = %d", a.nlevels);
+    for (int l = 0; l < ORBFE_MAX_LEVELS; l++) {
+        a.scale[l] = l < a.nlevels ? ctx->plan.scale[l] : 1.f;
+        a.sigma2[l] = l < a.nlevels ? ctx->plan.sigma2[l] : 1.f;
+    }
+    a.kf1 = *kf1; a.kf2 = *kf2;
+    a.pairs = d_pairs; a.npairs = d_npairs; a.code = d_code; a.x3d = d_x3d; a.new_points = d_new; a.nnew = d_nnew;
+    a.pos = d_pos; a.rows_used = d_rows_used; a.status = d_status;
+    a.mbf = mbf; a.ratio_factor = ratio_factor;
+    a.max_pairs = max_pairs; a.n_rows = n_rows; a.patch_has_mp = patch_has_mp;
+    HIP_TRY(ctx, hipSetDevice(ctx->params.device));
+    HIP_TRY(ctx, (hipError_t)orbfe_triangulate_launch(a, stream ? (hipStream_t)stream : ctx->stream));
+    return ORBFE_OK;
+} ORBFE_CATCH(ctx)

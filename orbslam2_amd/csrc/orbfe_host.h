@@ -70,6 +70,23 @@ void orbfe_pose_state_destroy(orbfe_pose_state *s);
 orbfe_pose_state *orbfe_ctx_pose_state(orbfe_context *ctx);
 const float *orbfe_ctx_inv_sigma2(const orbfe_context *ctx);
 
+// orbfe_enqueue_triangulate_pairs: what the entry point (orbfe_api.hip) hands to the launches (orbfe_triangulate_device.hip); the two
+// keyframe records travel by value, the level tables are the context's
+#include "orbfe_config.h"
+struct orbfe_triangulate_args {
+    orbfe_newpoint_keyframe kf1, kf2;
+    const int32_t *pairs, *npairs;
+    uint8_t *code;
+    float *x3d;
+    int32_t *new_points, *nnew;
+    float *pos;
+    int32_t *rows_used, *status;
+    float mbf, ratio_factor;
+    int max_pairs, n_rows, patch_has_mp, nlevels;
+    float scale[ORBFE_MAX_LEVELS], sigma2[ORBFE_MAX_LEVELS]; // mvScaleFactors, mvLevelSigma2
+};
+int orbfe_triangulate_launch(const orbfe_triangulate_args &a, hipStream_t s); // queues at most three launches; returns hipGetLastError()
+
 // No C++ exception may cross the C ABI (a ctypes / cgo / C caller would abort): every extern "C" function that returns a status is a
 // function-try-block closed by this handler.  The per-context lock of ORBFE_ENTRY is a local of the try block, so it is released first.
 #include <exception>

@@ -1,0 +1,324 @@
+// orbfe_triangulate_device.hip -- the triangulation stage of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:286-450, with
+// KeyFrame::UnprojectStereo, src/KeyFrame.cc:609-625) for the pairs that orbfe_enqueue_search_for_triangulation left in HBM, asynchronous on
+// the caller's stream.  The entry point and its checks are in orbfe_api.hip; the arithmetic contract is stated in include/orbfe.h and
+// DESIGN.md section 4k, and this file, orbslam2_amd/host/Triangulate.h and tests/triangulate_model.py follow it operation by operation.
+//
+//   triangulate_reset_kernel    status = 0 (and the count of new points when there is nothing else to queue)
+//   triangulate_kernel          one lane per pair, 256-thread workgroups.  The work of a pair is one dependent chain (the Jacobi rotations) and
+//                               a call has 100 to 600 pairs, so the kernel is latency-bound on a handful of waves; a lane group per pair would
+//                               change the order of the double sums, which the contract fixes.  At, Vt and W live in registers: the six (i, j)
+//                               rotations are instantiated with static indices and the selection sort carries values, not indices.
+//   triangulate_append_kernel   one wave replays the codes in pair order: ballot + popcount with a running base gives the k-th created pair
+//                               its slot of d_new and its table row; it learns the number of new points BEFORE it writes, so a table without
+//                               room is refused whole.  The has_mp bytes are written as 1 only, so two lanes never disagree.
+// All stores are plain vector stores.
+#include "../../include/orbfe.h"
+#include "orbfe_config.h"
+#include "orbfe_host.h"
+
+#include <cfloat>
+
+static_assert(sizeof(orbfe_newpoint_keyframe) == 136, "orbfe_newpoint_keyframe: six pointers, Tcw, Ow, six camera floats, n");
+
+typedef unsigned long long u64;
+typedef orbfe_triangulate_args Args;
+
+__global__ __launch_bounds__(64) void triangulate_reset_kernel(int32_t *status, int32_t *nnew)
+{
+    if (threadIdx.x == 0) {
+        *status = 0;
+        if (nnew) *nnew = 0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the null vector
+struct Jacobi {
+    float At[4][4], Vt[4][4];
+    double W[4];
+};
+
+// rows I and J of X rotated in float: t0 = c * a + s * b, t1 = -s * a + c * b, each product rounded, then the sum
+template <int I, int J> __device__ __forceinline__ void rotate_rows(float (&X)[4][4], float c, float s)
+{
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float t0 = __fadd_rn(__fmul_rn(c, X[I][k]), __fmul_rn(s, X[J][k]));
+        const float t1 = __fadd_rn(__fmul_rn(-s, X[I][k]), __fmul_rn(c, X[J][k]));
+        X[I][k] = t0; X[J][k] = t1;
+    }
+}
+
+template <int I> __device__ __forceinline__ double square_sum(const float (&X)[4][4])
+{
+    double sd = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) sd += (double)X[I][k] * (double)X[I][k];
+    return sd;
+}
+
+template <int I, int J> __device__ __forceinline__ bool jacobi_pair(Jacobi &m)
+{
+    const double a = m.W[I], b = m.W[J];
+    double p = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) p += (double)m.At[I][k] * (double)m.At[J][k];
+    const double eps = (double)FLT_EPSILON * 2;
+    if (fabs(p) <= eps * sqrt(a * b)) return false;
+    p *= 2;
+    const double beta = a - b, gamma = sqrt(p * p + beta * beta); // a plain double sqrt, not hypot
+    float c, s;
+    if (beta < 0) {
+        s = (float)sqrt(((gamma - beta) * 0.5) / gamma);
+        c = (float)(p / (gamma * (double)s * 2));
+    } else {
+        c = (float)sqrt((gamma + beta) / (gamma * 2));
+        s = (float)(p / (gamma * (double)c * 2));
+    }
+    rotate_rows<I, J>(m.At, c, s);
+    m.W[I] = square_sum<I>(m.At);
+    m.W[J] = square_sum<J>(m.At);
+    rotate_rows<I, J>(m.Vt, c, s);
+    return true;
+}
+
+// position I of the selection sort (descending, strict <): the largest of W[I..3] comes to I and carries its row of Vt
+template <int I> __device__ __forceinline__ void select_largest(Jacobi &m)
+{
+    int j = I;
+    double wj = m.W[I];
+#pragma unroll
+    for (int k = I + 1; k < 4; k++)
+        if (wj < m.W[k]) { j = k; wj = m.W[k]; }
+#pragma unroll
+    for (int k = I + 1; k < 4; k++)
+        if (j == k) {
+            const double t = m.W[I]; m.W[I] = m.W[k]; m.W[k] = t;
+#pragma unroll
+            for (int e = 0; e < 4; e++) { const float u = m.Vt[I][e]; m.Vt[I][e] = m.Vt[k][e]; m.Vt[k][e] = u; }
+        }
+}
+
+// vt.row(3) of cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV): m.At holds A transposed on entry
+__device__ __forceinline__ void null_vector(Jacobi &m, float (&v)[4])
+{
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int k = 0; k < 4; k++) m.Vt[i][k] = i == k ? 1.f : 0.f;
+    m.W[0] = square_sum<0>(m.At); m.W[1] = square_sum<1>(m.At); m.W[2] = square_sum<2>(m.At); m.W[3] = square_sum<3>(m.At);
+    for (int iter = 0; iter < 30; iter++) {
+        bool changed = jacobi_pair<0, 1>(m);
+        changed |= jacobi_pair<0, 2>(m);
+        changed |= jacobi_pair<0, 3>(m);
+        changed |= jacobi_pair<1, 2>(m);
+        changed |= jacobi_pair<1, 3>(m);
+        changed |= jacobi_pair<2, 3>(m);
+        if (!changed) break;
+    }
+    m.W[0] = sqrt(square_sum<0>(m.At)); m.W[1] = sqrt(square_sum<1>(m.At)); m.W[2] = sqrt(square_sum<2>(m.At)); m.W[3] = sqrt(square_sum<3>(m.At));
+    select_largest<0>(m);
+    select_largest<1>(m);
+    select_largest<2>(m);
+#pragma unroll
+    for (int k = 0; k < 4; k++) v[k] = m.Vt[3][k];
+}
+
+// ---------------------------------------------------------------------------------------------------------------- cv::Mat steps
+// Rwc * x (+ Ow): Rwc[i][k] = Tcw[k][i]; a double sum over k, one rounding
+__device__ __forceinline__ void rwc_times(const float (&Tcw)[12], const float (&x)[3], const float *plus, float (&out)[3])
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        double s = 0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) s += (double)Tcw[4 * k + i] * (double)x[k];
+        if (plus) s += (double)plus[i];
+        out[i] = (float)s;
+    }
+}
+
+// Rcw.row(R).dot(x3Dt) + tcw(R)
+template <int R> __device__ __forceinline__ float row_dot_plus(const float (&Tcw)[12], const float (&X)[3])
+{
+    double s = 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) s += (double)Tcw[4 * R + k] * (double)X[k];
+    return (float)(s + (double)Tcw[4 * R + 3]);
+}
+
+__device__ __forceinline__ double norm3(const float (&v)[3])
+{
+    return sqrt((double)v[0] * (double)v[0] + (double)v[1] * (double)v[1] + (double)v[2] * (double)v[2]);
+}
+
+// KeyFrame::UnprojectStereo(i): i is inside [0, n) and depth[i] > 0, both checked by the caller
+__device__ __forceinline__ void unproject_stereo(const orbfe_newpoint_keyframe &kf, int i, float (&X)[3])
+{
+    const float z = kf.depth[i];
+    const float u = kf.keys[i].x, v = kf.keys[i].y;
+    const float c[3] = {__fmul_rn(__fmul_rn(__fsub_rn(u, kf.cx), z), kf.invfx), __fmul_rn(__fmul_rn(__fsub_rn(v, kf.cy), z), kf.invfy), z};
+    rwc_times(kf.Tcw, c, kf.Ow, X);
+}
+
+// the chi-square test of :362-387 / :389-413; mbf is the CURRENT keyframe's for both
+__device__ __forceinline__ bool reprojection_fails(const orbfe_newpoint_keyframe &kf, float kx, float ky, float ur, bool stereo, const float (&X)[3], float z,
+                                                   float mbf, float sigma2)
+{
+    const float x = row_dot_plus<0>(kf.Tcw, X), y = row_dot_plus<1>(kf.Tcw, X);
+    const float invz = (float)(1.0 / (double)z);
+    const float u = __fadd_rn(__fmul_rn(__fmul_rn(kf.fx, x), invz), kf.cx);
+    const float v = __fadd_rn(__fmul_rn(__fmul_rn(kf.fy, y), invz), kf.cy);
+    const float ex = __fsub_rn(u, kx), ey = __fsub_rn(v, ky);
+    float e = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+    if (!stereo) return (double)e > 5.991 * (double)sigma2;
+    const float er = __fsub_rn(__fsub_rn(u, __fmul_rn(mbf, invz)), ur);
+    e = __fadd_rn(e, __fmul_rn(er, er));
+    return (double)e > 7.8 * (double)sigma2;
+}
+
+// one iteration of :286-450: the code, and for a created pair (code <= 2) its position
+__device__ __forceinline__ int triangulate_pair(const Args &a, int idx1, int idx2, float (&X)[3])
+{
+    const orbfe_newpoint_keyframe &kf1 = a.kf1, &kf2 = a.kf2;
+    if (idx1 < 0 || idx1 >= kf1.n || idx2 < 0 || idx2 >= kf2.n) return 11;
+    const orbfe_keypoint *kp1 = kf1.keys_un + idx1, *kp2 = kf2.keys_un + idx2;
+    const int o1 = kp1->octave, o2 = kp2->octave;
+    if (o1 < 0 || o1 >= a.nlevels || o2 < 0 || o2 >= a.nlevels) return 11;
+    const float x1 = kp1->x, y1 = kp1->y, x2 = kp2->x, y2 = kp2->y;
+    const float ur1 = kf1.u_right[idx1], ur2 = kf2.u_right[idx2];
+    const bool stereo1 = ur1 >= 0, stereo2 = ur2 >= 0;
+    if ((stereo1 && !(kf1.depth[idx1] > 0)) || (stereo2 && !(kf2.depth[idx2] > 0))) return 11; // UnprojectStereo would return an empty Mat
+
+    // Check parallax between rays
+    const float xn1[3] = {__fmul_rn(__fsub_rn(x1, kf1.cx), kf1.invfx), __fmul_rn(__fsub_rn(y1, kf1.cy), kf1.invfy), 1.f};
+    const float xn2[3] = {__fmul_rn(__fsub_rn(x2, kf2.cx), kf2.invfx), __fmul_rn(__fsub_rn(y2, kf2.cy), kf2.invfy), 1.f};
+    float ray1[3], ray2[3];
+    rwc_times(kf1.Tcw, xn1, nullptr, ray1);
+    rwc_times(kf2.Tcw, xn2, nullptr, ray2);
+    const double dot = (double)ray1[0] * (double)ray2[0] + (double)ray1[1] * (double)ray2[1] + (double)ray1[2] * (double)ray2[2];
+    const float cos_rays = (float)(dot / (norm3(ray1) * norm3(ray2)));
+    const float cos_plus = __fadd_rn(cos_rays, 1.f);
+    float cos1 = cos_plus, cos2 = cos_plus;
+    if (stereo1) cos1 = kf1.cos_stereo[idx1];
+    else if (stereo2) cos2 = kf2.cos_stereo[idx2];
+    const float cos_stereo = cos2 < cos1 ? cos2 : cos1; // std::min(cos1, cos2)
+
+    int code;
+    if (cos_rays < cos_stereo && cos_rays > 0 && (stereo1 || stereo2 || (double)cos_rays < 0.9998)) {
+        // Linear Triangulation Method: A.row(r) = xn_c * Tcw.row(2) - Tcw.row(r'), held transposed
+        Jacobi m;
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            m.At[c][0] = __fsub_rn(__fmul_rn(xn1[0], kf1.Tcw[8 + c]), kf1.Tcw[c]);
+            m.At[c][1] = __fsub_rn(__fmul_rn(xn1[1], kf1.Tcw[8 + c]), kf1.Tcw[4 + c]);
+            m.At[c][2] = __fsub_rn(__fmul_rn(xn2[0], kf2.Tcw[8 + c]), kf2.Tcw[c]);
+            m.At[c][3] = __fsub_rn(__fmul_rn(xn2[1], kf2.Tcw[8 + c]), kf2.Tcw[4 + c]);
+        }
+        float v[4];
+        null_vector(m, v);
+        if (v[3] == 0) return 4;
+        const float alpha = (float)(1.0 / (double)v[3]); // Mat / float is a scale
+        X[0] = __fmul_rn(v[0], alpha); X[1] = __fmul_rn(v[1], alpha); X[2] = __fmul_rn(v[2], alpha);
+        code = 0;
+    } else if (stereo1 && cos1 < cos2) {
+        unproject_stereo(kf1, idx1, X);
+        code = 1;
+    } else if (stereo2 && cos2 < cos1) {
+        unproject_stereo(kf2, idx2, X);
+        code = 2;
+    } else
+        return 3; // No stereo and very low parallax
+
+    // Check triangulation in front of cameras
+    const float z1 = row_dot_plus<2>(kf1.Tcw, X);
+    if (z1 <= 0) return 5;
+    const float z2 = row_dot_plus<2>(kf2.Tcw, X);
+    if (z2 <= 0) return 6;
+    // Check reprojection error in first keyframe, then in the second
+    if (reprojection_fails(kf1, x1, y1, ur1, stereo1, X, z1, a.mbf, a.sigma2[o1])) return 7;
+    if (reprojection_fails(kf2, x2, y2, ur2, stereo2, X, z2, a.mbf, a.sigma2[o2])) return 8;
+    // Check scale consistency
+    const float n1[3] = {__fsub_rn(X[0], kf1.Ow[0]), __fsub_rn(X[1], kf1.Ow[1]), __fsub_rn(X[2], kf1.Ow[2])};
+    const float n2[3] = {__fsub_rn(X[0], kf2.Ow[0]), __fsub_rn(X[1], kf2.Ow[1]), __fsub_rn(X[2], kf2.Ow[2])};
+    const float dist1 = (float)norm3(n1), dist2 = (float)norm3(n2);
+    if (dist1 == 0 || dist2 == 0) return 9;
+    const float ratio_dist = __fdiv_rn(dist2, dist1);
+    const float ratio_octave = __fdiv_rn(a.scale[o1], a.scale[o2]);
+    if (__fmul_rn(ratio_dist, a.ratio_factor) < ratio_octave || ratio_dist > __fmul_rn(ratio_octave, a.ratio_factor)) return 10;
+    return code;
+}
+
+__global__ __launch_bounds__(256) void triangulate_kernel(Args a)
+{
+    const int count = *a.npairs;
+    if (count < 0 || count > a.max_pairs) { // nothing else is written
+        if (blockIdx.x == 0 && threadIdx.x == 0) *a.status = ORBFE_ERR_INVALID;
+        return;
+    }
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= count) return;
+    float X[3] = {0.f, 0.f, 0.f};
+    const int code = triangulate_pair(a, a.pairs[2 * q], a.pairs[2 * q + 1], X);
+    a.code[q] = (uint8_t)code;
+    if (code == 11) *a.status = ORBFE_ERR_INVALID; // every lane that writes writes this value
+    if (code <= 2) {
+        a.x3d[3 * (size_t)q] = X[0]; a.x3d[3 * (size_t)q + 1] = X[1]; a.x3d[3 * (size_t)q + 2] = X[2];
+    }
+}
+
+__global__ __launch_bounds__(64) void triangulate_append_kernel(Args a)
+{
+    const int lane = threadIdx.x;
+    const int count = *a.npairs;
+    if (count < 0 || count > a.max_pairs) return;
+    int nnew = 0;
+    for (int base = 0; base < count; base += 64) {
+        const int q = base + lane;
+        nnew += __popcll(__ballot(q < count && a.code[q] <= 2));
+    }
+    bool table = a.pos != nullptr, fits = true;
+    int base_row = 0;
+    if (table) {
+        base_row = *a.rows_used; // read by every lane before lane 0 advances it below
+        const bool negative = base_row < 0;
+        if (negative || (long long)base_row + nnew > a.n_rows) { // the table, the counter and both has_mp arrays stay untouched
+            if (lane == 0) *a.status = negative ? ORBFE_ERR_INVALID : ORBFE_ERR_CAPACITY;
+            table = fits = false;
+        }
+    }
+    int k0 = 0;
+    for (int base = 0; base < count; base += 64) {
+        const int q = base + lane;
+        const bool created = q < count && a.code[q] <= 2;
+        const u64 mask = __ballot(created);
+        if (created) {
+            const int k = k0 + __popcll(mask & ((1ull << lane) - 1)); // pair order
+            const int idx1 = a.pairs[2 * q], idx2 = a.pairs[2 * q + 1];
+            const int row = table ? base_row + k : -1;
+            a.new_points[3 * (size_t)k] = idx1; a.new_points[3 * (size_t)k + 1] = idx2; a.new_points[3 * (size_t)k + 2] = row;
+            if (table) {
+                a.pos[3 * (size_t)row] = a.x3d[3 * (size_t)q]; a.pos[3 * (size_t)row + 1] = a.x3d[3 * (size_t)q + 1];
+                a.pos[3 * (size_t)row + 2] = a.x3d[3 * (size_t)q + 2];
+            }
+            if (a.patch_has_mp && fits && idx1 >= 0 && idx1 < a.kf1.n && idx2 >= 0 && idx2 < a.kf2.n) { // AddMapPoint (:439-440)
+                a.kf1.has_mp[idx1] = 1;
+                a.kf2.has_mp[idx2] = 1;
+            }
+        }
+        k0 += __popcll(mask);
+    }
+    if (lane == 0) {
+        *a.nnew = nnew;
+        if (table) *a.rows_used = base_row + nnew;
+    }
+}
+
+int orbfe_triangulate_launch(const orbfe_triangulate_args &a, hipStream_t s)
+{
+    hipLaunchKernelGGL(triangulate_reset_kernel, dim3(1), dim3(64), 0, s, a.status, a.max_pairs == 0 ? a.nnew : nullptr);
+    if (a.max_pairs > 0) {
+        hipLaunchKernelGGL(triangulate_kernel, dim3((a.max_pairs + 255) / 256), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(triangulate_append_kernel, dim3(1), dim3(64), 0, s, a);
+    }
+    return (int)hipGetLastError();
+}

@@ -75,6 +75,16 @@ keyframe, keypoint, reference entry: one pinned block) uploaded, orbfe_enqueue_u
 stream synchronise -- the keyframe directory is resident, as it is for the matchers; (c) the enqueue alone, queued back to back, as
 GPU time between two events.  (b)'s table is compared with (a)'s bit for bit.  Five repeats of each, interleaved; every repeat is the
 mean of 10 loops, its slowest loop beside it.
+    python3 tools/bench_matchers.py --create-new-map-points
+runs only the rows of the CreateNewMapPoints neighbour loop (profiles/create_new_map_points_device.json): KF1 of 2000 keypoints against 20
+neighbours (the scene of --triangulation, with poses, depths and stereo cosines added).  (a) today's loop: per neighbour the search
+enqueue, the download of count and pairs, one synchronise, orbslam2_amd/host/Triangulate.h on one host thread (g++ -O2, writing the
+has_mp mirrors in pinned memory) and two has_mp patches queued; (b) the queued loop: per neighbour the search enqueue and
+orbfe_enqueue_triangulate_pairs with the patch and the table append, each neighbour with its own output block, then one download of
+counts, codes and d_new of all neighbours, one of the table rows, and one synchronise; (c) the triangulate call alone on neighbour 0's
+pairs, queued back to back, as GPU time between two events.  Both loops reset has_mp and the row counter inside the window.  (b)'s
+points are compared with (a)'s bit for bit.  Five repeats of each, interleaved; every repeat is the mean of 10 loops, its slowest loop
+beside it.
 """
 import json
 import os
@@ -1240,6 +1250,179 @@ def map_point_rows(out):
     ctx.close()
 
 
+def create_new_map_points_rows(out):
+    """Rows of --create-new-map-points; arguments prepared once."""
+    import ctypes as C
+    import gc
+    import subprocess
+    import tempfile
+    import torch
+    from orbslam2_amd import api
+    from tests import triangulate_scenes as NS
+    from tests import triangulation_scenes as S
+    dev = torch.device("cuda:0")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
+    N, K, REPS, REPEATS, ROWS, MBF = 2000, 20, 10, 5, 8000, 40.0
+    ctx = api.Context(width=640, height=480, nfeatures=2000, fx=S.FX, fy=S.FY, cx=S.CX, cy=S.CY, bf=MBF)
+    t = ctx.tables()
+    scale, sigma2 = np.ascontiguousarray(t["scale"], np.float32), np.ascontiguousarray(t["sigma2"], np.float32)
+    ratio = float(np.float32(1.5) * scale[1])
+    base = S.two_view(2, N)
+    scs = [dict(base, kf2=S.view_of(2 + k, N)) for k in range(K)]
+    poses = S._two_view_base(N)
+    m1 = NS.from_search_keyframe(base["kf1"], poses["T1"], MBF)
+    m2s = [NS.from_search_keyframe(sc["kf2"], poses["T2"], MBF) for sc in scs]
+    out["scene"] = "KF1 of %d keypoints against %d neighbours of %d (tests/triangulation_scenes.py), bf = 40, half of the keypoints stereo" % (N, K, N)
+    so = os.path.join(os.environ.get("BENCH_OUT") or tempfile.mkdtemp(), "triangulate_host_shim.so")
+    subprocess.run(["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tools", "triangulate_host_shim.cpp")], check=True)
+    host = C.CDLL(so).triangulate_pairs_host
+    host.restype = C.c_int
+    host.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + \
+        [C.c_int, C.c_void_p, C.c_int]
+    st = torch.cuda.Stream()
+    pin = lambda a: torch.from_numpy(np.ascontiguousarray(a).copy()).pin_memory()
+
+    # has_mp: one pinned host mirror and one device array for KF1, one of each for all neighbours together
+    mp1_0, mp2_0 = m1["mp"].copy(), np.concatenate([m["mp"] for m in m2s])
+    h_mp1, h_mp2 = pin(mp1_0), pin(mp2_0)
+    d_mp1, d_mp2 = up(mp1_0), up(mp2_0)
+
+    def newpoint(m, ptr_of, has_mp):
+        return api.NewpointKeyframe(ptr_of("keys_un"), ptr_of("keys_un"), ptr_of("ur"), ptr_of("depth"), ptr_of("cos"), has_mp, (C.c_float * 12)(*m["Tcw"].tolist()),
+                                    (C.c_float * 3)(*m["Ow"].tolist()), *[float(m[k]) for k in ("fx", "fy", "cx", "cy", "invfx", "invfy")], m["n"])
+
+    def sides(sc_kf, m, h_mp_ptr, d_mp_t):
+        """The search record and the triangulation record of one keyframe on the device, and the triangulation record on the host."""
+        tri = [up(sc_kf["fv"][0]), up(sc_kf["fv"][1]), up(sc_kf["fv"][2]), up(sc_kf["k"]), up(sc_kf["ur"]), d_mp_t, up(sc_kf["d"])]
+        extra = {"depth": up(m["depth"]), "cos": up(m["cos"])}
+        dptr = {"keys_un": tri[3].data_ptr(), "ur": tri[4].data_ptr(), "depth": extra["depth"].data_ptr(), "cos": extra["cos"].data_ptr()}
+        return dict(keep=(tri, extra), tri=api.TriKeyframe(*[x.data_ptr() for x in tri], len(sc_kf["fv"][0]), len(sc_kf["k"])),
+                    dev=newpoint(m, dptr.__getitem__, d_mp_t.data_ptr()), host=newpoint(m, lambda k: m[k].ctypes.data, h_mp_ptr))
+
+    s1 = sides(base["kf1"], m1, h_mp1.data_ptr(), d_mp1)
+    s2s = [sides(sc["kf2"], m, h_mp2.data_ptr() + k * N, d_mp2[k * N:(k + 1) * N]) for k, (sc, m) in enumerate(zip(scs, m2s))]
+    # per neighbour on the device: match12[N], then the block that travels: count, status, nnew, triangulation status, new[3N] (int32), code[N]
+    WORDS = 4 + 3 * N
+    d_match = torch.zeros(N, dtype=torch.int32, device=dev)
+    d_pairs = torch.zeros((K, 2 * N), dtype=torch.int32, device=dev)
+    d_small = torch.zeros((K, WORDS * 4 + N), dtype=torch.uint8, device=dev)
+    h_small = torch.zeros((K, WORDS * 4 + N), dtype=torch.uint8).pin_memory()
+    d_x3d = torch.zeros((K, 3 * N), dtype=torch.float32, device=dev)
+    d_pos, h_pos = torch.zeros(3 * ROWS, dtype=torch.float32, device=dev), torch.zeros(3 * ROWS, dtype=torch.float32).pin_memory()
+    d_used, h_used0 = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32).pin_memory()
+    h_pairs = torch.zeros(2 * N, dtype=torch.int32).pin_memory()
+    h_head = torch.zeros(4, dtype=torch.int32).pin_memory()
+    small_np = h_small.numpy()
+    # the host form's outputs
+    a_code, a_x3d, a_new = np.zeros((K, N), np.uint8), np.zeros((K, 3 * N), np.float32), np.zeros((K, 3 * N), np.int32)
+    a_nnew, a_pos, a_used = np.zeros(K, np.int32), np.zeros(3 * ROWS, np.float32), np.zeros(1, np.int32)
+    a_count = np.zeros(1, np.int32)
+    P = lambda a: a.ctypes.data
+    torch.cuda.synchronize()
+
+    def search(k):
+        sc, base_ptr = scs[k], d_small[k].data_ptr()
+        ctx.enqueue_search_for_triangulation(s1["tri"], s2s[k]["tri"], sc["F12"], sc["Cw1"], sc["T2w"], S.FX, S.FY, S.CX, S.CY, 0, 1, d_match.data_ptr(),
+                                             base_ptr, base_ptr + 4, d_pairs=d_pairs[k].data_ptr(), stream=st.cuda_stream)
+
+    def triangulate(k):
+        base_ptr = d_small[k].data_ptr()
+        ctx.enqueue_triangulate_pairs(s1["dev"], s2s[k]["dev"], MBF, ratio, d_pairs[k].data_ptr(), base_ptr, N, base_ptr + 4 * WORDS, d_x3d[k].data_ptr(),
+                                      base_ptr + 16, base_ptr + 8, base_ptr + 12, d_pos=d_pos.data_ptr(), n_rows=ROWS, d_rows_used=d_used.data_ptr(),
+                                      patch_has_mp=1, stream=st.cuda_stream)
+
+    def reset():
+        h_mp1.numpy()[:] = mp1_0; h_mp2.numpy()[:] = mp2_0
+        d_mp1.copy_(h_mp1, non_blocking=True); d_mp2.copy_(h_mp2, non_blocking=True); d_used.copy_(h_used0, non_blocking=True)
+
+    def todays_loop():
+        with torch.cuda.stream(st):
+            reset()
+            a_used[0] = 0
+            for k in range(K):
+                search(k)
+                h_head.copy_(d_small[k, :16].view(torch.int32), non_blocking=True)
+                h_pairs.copy_(d_pairs[k], non_blocking=True)
+                st.synchronize()
+                a_count[0] = int(h_head[0])
+                status = host(C.addressof(s1["host"]), C.addressof(s2s[k]["host"]), MBF, ratio, h_pairs.data_ptr(), P(a_count), N, P(scale), P(sigma2), len(scale),
+                              P(a_code[k]), P(a_x3d[k]), P(a_new[k]), P(a_nnew[k:]), P(a_pos), ROWS, P(a_used), 1)
+                assert status == 0 and int(h_head[1]) == 0
+                d_mp1.copy_(h_mp1, non_blocking=True)                      # the two patches, queued: no wait
+                d_mp2[k * N:(k + 1) * N].copy_(h_mp2[k * N:(k + 1) * N], non_blocking=True)
+            st.synchronize()
+
+    def queued_loop():
+        with torch.cuda.stream(st):
+            reset()
+            for k in range(K):
+                search(k)
+                triangulate(k)
+            h_small.copy_(d_small, non_blocking=True)
+            h_pos.copy_(d_pos, non_blocking=True)
+            st.synchronize()
+
+    todays_loop()
+    a_mp1, a_mp2 = h_mp1.numpy().copy(), h_mp2.numpy().copy()     # the host mirrors as today's loop leaves them; the queued loop's reset overwrites them
+    queued_loop()
+    total = 0
+    for k in range(K):
+        head = small_np[k, :16].view(np.int32)
+        nnew = int(a_nnew[k]); cnt = int(head[0])
+        assert head[1] == 0 and head[3] == 0 and head[2] == nnew, k
+        assert np.array_equal(small_np[k, 16:16 + 12 * nnew].view(np.int32), a_new[k, :3 * nnew]), k
+        assert np.array_equal(small_np[k, 4 * WORDS:4 * WORDS + cnt], a_code[k, :cnt]), k
+        created = a_code[k, :cnt] <= 2
+        x = d_x3d[k].cpu().numpy().reshape(-1, 3)[:cnt][created]
+        assert np.array_equal(x.view(np.uint32), a_x3d[k].reshape(-1, 3)[:cnt][created].view(np.uint32)), k
+        total += nnew
+    assert int(d_used.cpu()[0]) == int(a_used[0]) == total
+    assert np.array_equal(h_pos.numpy()[:3 * total].view(np.uint32), a_pos[:3 * total].view(np.uint32))
+    assert np.array_equal(d_mp1.cpu().numpy(), a_mp1) and np.array_equal(d_mp2.cpu().numpy(), a_mp2) and (a_mp1 != mp1_0).any()
+    out["checked"] = "both forms create the same %d points bit for bit: codes, positions, d_new, table rows, row counter, has_mp of all %d keyframes" % (total, K + 1)
+    out["points_created"] = total
+
+    def loops(fn):
+        fn()
+        gc.collect()
+        gc.disable()  # the cyclic collector is off inside the window, as in the standard timeit module
+        try:
+            ts = []
+            for _ in range(REPS):
+                t0 = time.perf_counter()
+                fn()
+                ts.append((time.perf_counter() - t0) * 1e3)
+        finally:
+            gc.enable()
+        return round(sum(ts) / REPS, 4), round(max(ts), 4)
+
+    a_wall, a_worst, b_wall, b_worst, c_gpu = [], [], [], [], []
+    pairs_of_0 = int(small_np[0, :4].view(np.int32)[0])
+    for _ in range(REPEATS):
+        m, w = loops(todays_loop)
+        a_wall.append(m); a_worst.append(w)
+        m, w = loops(queued_loop)
+        b_wall.append(m); b_worst.append(w)
+        with torch.cuda.stream(st):
+            reset()
+            search(0)                                                      # leaves neighbour 0's pairs and count in place
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(REPS):
+            triangulate(0)
+        e1.record(st)
+        st.synchronize()
+        c_gpu.append(round(e0.elapsed_time(e1) / REPS, 4))
+    rows = out["rows"]
+    rows["(a) today's loop: %d x (enqueue search + download of count and pairs + synchronise + Triangulate.h on one host thread + two has_mp patches queued), wall time" % K] = {
+        "ms_per_repeat": a_wall, "slowest_loop_ms": a_worst}
+    rows["(b) the queued loop: %d x (enqueue search + orbfe_enqueue_triangulate_pairs), one download of counts, codes, d_new and table rows, one synchronise, wall time" % K] = {
+        "ms_per_repeat": b_wall, "slowest_loop_ms": b_worst}
+    rows["(c) orbfe_enqueue_triangulate_pairs alone (%d pairs under a bound of %d), queued back to back, GPU time between two events" % (pairs_of_0, N)] = {"ms_per_repeat": c_gpu}
+    rows["median (a) / median (b)"] = round(float(np.median(a_wall) / np.median(b_wall)), 2)
+    ctx.close()
+
+
 def load_other_build(api, path):
     """api.load() on the library at `path`, which may be older than the package: the prototypes load() sets for entry points
     that build lacks land on stand-ins that are not kept, so hasattr(lib, name) is False afterwards and a call fails loudly."""
@@ -1295,6 +1478,12 @@ def main():
     if "--map-points" in sys.argv[1:]:
         out = {"unit": "ms per update of 1500 map points", "rows": {}}
         map_point_rows(out)
+        out["build_id"] = api.build_id()
+        print(json.dumps(out, indent=1))
+        return
+    if "--create-new-map-points" in sys.argv[1:]:
+        out = {"unit": "ms per keyframe (20 neighbours)", "rows": {}}
+        create_new_map_points_rows(out)
         out["build_id"] = api.build_id()
         print(json.dumps(out, indent=1))
         return

@@ -368,6 +368,57 @@ void dump_primitives(const std::string &out_dir)
         std::memcpy(bits, out, sizeof(bits));
         std::printf("map_point normal %08x %08x %08x mfMaxDistance %08x mfMinDistance %08x\n", bits[0], bits[1], bits[2], bits[3], bits[4]);
     }
+    // case triangulate: the cv::Mat steps of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:303-337, :354) that DESIGN.md section 4k states
+    // from memory of OpenCV's source: `s * row - row`, a 3x3 * 3x1 product (with and without `+ col`), `row.dot(x) + float`, the 4x4 SVD
+    // and the scalar divide behind it, on a fixed pair (camera 1 at the origin; camera 2 yawed 3 degrees, t = (-0.4, 0.02, 0.05);
+    // xn1 = (0.1234, -0.0567), xn2 = (0.0461, -0.0512)).  The model's bits (tests/triangulate_model.py):
+    //   A rows 2, 3        bf802227 00000000 bbce68f8 3ecdfaec | 3b2f9c3e bf800000 bd516d83 bcb8cfc0
+    //   vt.row(3)          bdee762e 3d5ddc2f bf719fbc be9bdc2c   (3 sweeps; a LAPACK build may differ in sign and last bits)
+    //   x3D                3ec3d627 be3633d8 40466eff            (true divisions give 3ec3d626 for x)
+    //   Rwc2 * xn1         3d91315c bd683e42 3f80a6b7;  ... + (0.4, -0.02, -0.03): 3ef11924 bd9d14e4 3f799f5a
+    //   Rcw2.row(2).dot((1.5, -0.7, 9.25)) + tcw2(2)   41135753
+    {
+        const float t1[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        const float t2[12] = {0.9986295f, 0, 0.052335955f, -0.4f, 0, 1, 0, 0.02f, -0.052335955f, 0, 0.9986295f, 0.05f};
+        cv::Mat Tcw1(3, 4, CV_32F), Tcw2(3, 4, CV_32F);
+        std::memcpy(Tcw1.data, t1, sizeof(t1));
+        std::memcpy(Tcw2.data, t2, sizeof(t2));
+        auto vec3 = [](float a, float b, float c) { cv::Mat m(3, 1, CV_32F); m.at<float>(0) = a; m.at<float>(1) = b; m.at<float>(2) = c; return m; };
+        cv::Mat xn1 = vec3(0.1234f, -0.0567f, 1.0f);
+        cv::Mat xn2 = vec3(0.0461f, -0.0512f, 1.0f);
+        cv::Mat A(4, 4, CV_32F);
+        A.row(0) = xn1.at<float>(0) * Tcw1.row(2) - Tcw1.row(0);
+        A.row(1) = xn1.at<float>(1) * Tcw1.row(2) - Tcw1.row(1);
+        A.row(2) = xn2.at<float>(0) * Tcw2.row(2) - Tcw2.row(0);
+        A.row(3) = xn2.at<float>(1) * Tcw2.row(2) - Tcw2.row(1);
+        cv::Mat A_in = A.clone();
+        w.put("triangulate_A", F32, {4, 4}, A_in.data);
+        cv::Mat sw, su, svt;
+        cv::SVD::compute(A, sw, su, svt, cv::SVD::MODIFY_A | cv::SVD::FULL_UV);
+        cv::Mat v3 = svt.row(3).t();
+        w.put("triangulate_vt3", F32, {4}, v3.data);
+        cv::Mat x3D = v3.rowRange(0, 3) / v3.at<float>(3);
+        w.put("triangulate_x3D", F32, {3}, x3D.data);
+        const cv::Mat Rcw2 = Tcw2.colRange(0, 3), Rwc2 = Rcw2.t();
+        cv::Mat ray = Rwc2 * xn1;
+        w.put("triangulate_ray", F32, {3}, ray.data);
+        cv::Mat ow = vec3(0.4f, -0.02f, -0.03f);
+        cv::Mat unprojected = Rwc2 * xn1 + ow;
+        w.put("triangulate_unprojected", F32, {3}, unprojected.data);
+        cv::Mat X = vec3(1.5f, -0.7f, 9.25f);
+        cv::Mat Xt = X.t();
+        const float z = Rcw2.row(2).dot(Xt) + Tcw2.at<float>(2, 3);
+        w.put("triangulate_z", F32, {1}, &z);
+        uint32_t b[4];
+        std::memcpy(b, v3.data, 16);
+        std::printf("triangulate vt.row(3) %08x %08x %08x %08x", b[0], b[1], b[2], b[3]);
+        std::memcpy(b, x3D.data, 12);
+        std::printf("  x3D %08x %08x %08x", b[0], b[1], b[2]);
+        std::memcpy(b, unprojected.data, 12);
+        std::printf("  Rwc * x + Ow %08x %08x %08x", b[0], b[1], b[2]);
+        std::memcpy(b, &z, 4);
+        std::printf("  z %08x\n", b[0]);
+    }
     std::printf("primitives written (OpenCV %s)\n", CV_VERSION);
 }
 } // namespace

@@ -45,6 +45,8 @@ public:
     Mat reshape(int cn) const;
     Mat clone() const;
     void convertTo(Mat &dst, int type) const;
+    MatExpr t() const;
+    double dot(const Mat &m) const;
     static MatExpr ones(int r, int c, int type);
     static MatExpr zeros(int r, int c, int type);
     static MatExpr eye(int r, int c, int type);
@@ -55,6 +57,11 @@ MatExpr operator*(float s, const MatExpr &m);
 MatExpr operator-(const Mat &a, const Mat &b);
 MatExpr operator+(const Mat &a, const MatExpr &b);
 MatExpr operator/(const Mat &a, double s);
+MatExpr operator*(float s, const Mat &m);
+MatExpr operator*(const Mat &a, const Mat &b);
+MatExpr operator-(const MatExpr &a, const Mat &b);
+MatExpr operator+(const MatExpr &a, const Mat &b);
+struct SVD { enum { MODIFY_A = 1, NO_UV = 2, FULL_UV = 4 }; static void compute(const Mat &src, Mat &w, Mat &u, Mat &vt, int flags = 0); };
 typedef const Mat &InputArray;
 typedef Mat &OutputArray;
 enum { NORM_L1 = 2 };
