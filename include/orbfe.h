@@ -1012,6 +1012,76 @@ int orbfe_enqueue_triangulate_pairs(orbfe_context *ctx,
         uint8_t *d_code /* [max_pairs] */, float *d_x3d /* [max_pairs][3] */, int32_t *d_new /* [3 * max_pairs] */, int32_t *d_nnew /* [1] */,
         float *d_pos /* [n_rows][3] or NULL */, int n_rows, int32_t *d_rows_used /* [1]; NULL only with d_pos == NULL */,
         int patch_has_mp, int32_t *d_status /* [1] */, void *stream);
+/* ---- monocular initialisation: Initializer::FindHomography + Initializer::FindFundamental (orbfe_initializer_device.hip),
+ * src/Initializer.cc:123-467, for one frame pair in one call: every RANSAC hypothesis of both models.  The two std::threads of
+ * Initializer::Initialize (:103-108) become one call; the RH test (:111-117) on the two fetched scores and ReconstructH / ReconstructF /
+ * CheckRT / DecomposeE (:469-930) stay the caller's, as does drawing mvSets (:77-96: DUtils::Random is glibc rand(), process state) --
+ * mvSets is an INPUT -- and Normalize (:748-794), whose sequential float sums over a frame's keypoints are their own definition: the
+ * host passes (meanX, meanY, sX, sY) of each frame (ORB_SLAM2::NormalizeKeys in orbslam2_amd/host/Initializer.h is the literal form).
+ * The contract of the enqueue calls above holds: asynchronous on `stream` (NULL: the context's stream), nothing waits for the GPU,
+ * nothing is read from host memory on the stream (norm1 / norm2 are read before the call returns and travel as kernel arguments).  The
+ * per-hypothesis matrices and scores live in the context's scratch: queue the calls of one context on one stream.  One memset of
+ * d_status and three launches: one wave per (set, model) for the 8-point solutions, one lane per (hypothesis, model) for the scores, one
+ * workgroup per model for the winner and its inlier flags.
+ *
+ * Inputs (device): d_keys1_un[n1], d_keys2_un[n2] (mvKeysUn of the reference and the current frame; x and y are read);
+ * d_pairs[N][2] = mvMatches12 (:50-62), (i, vMatches12[i]) in ascending i; d_sets[iterations][8] = mvSets, indices into d_pairs.
+ * Outputs (device; model 0 = H, 1 = F):
+ *   d_H21[9], d_F21[9]     the winning H21i / F21i, row major; untouched when the model has no winner
+ *   d_score[2]             SH, SF; 0 without a winner
+ *   d_best[2]              the winning iteration: the lowest one whose score is strictly greater than every earlier one's (:164, :215),
+ *                          or -1 when no hypothesis scores above 0
+ *   d_inliers_h[N], d_inliers_f[N]   vbMatchesInliers of the winner (0 / 1), all 0 without a winner; each may be NULL
+ *   d_ninliers[2]          their counts; may be NULL
+ *   d_all_scores[2][iterations]      every hypothesis's score, H first; a NaN score is stored as 0x7fc00000; may be NULL
+ *   d_status[1]
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL context, input, norm, d_H21, d_F21, d_score, d_best or d_status;
+ * N < 8 (the reference's set drawing is undefined below 8) or N > ORBFE_INITIALIZER_MAX_MATCHES; iterations < 1 or
+ * > ORBFE_INITIALIZER_MAX_ITERATIONS; n1 or n2 negative or > ORBFE_INITIALIZER_MAX_KEYS; sigma not > 0.
+ * d_status = ORBFE_ERR_INVALID for what only the device can see, each checked before it becomes an address: a pair index outside
+ * [0, n1) / [0, n2) -- that match adds no term to any score and its flags are 0 -- and a set index outside [0, N) or naming such a
+ * match -- that hypothesis is skipped: both its scores are 0 and it never wins.  Nothing is written outside the outputs.
+ *
+ * Arithmetic (contract Q4: no contraction, IEEE divide and sqrt; the OpenCV steps as DESIGN.md section 4l states them; the same
+ * operation order in tests/initializer_model.py, orbslam2_amd/host/Initializer.h and the kernels, which agree bit for bit):
+ *   Normalised points: ((x - meanX) * sX, (y - meanY) * sY) in float.  T = [sX 0 -meanX * sX; 0 sY -meanY * sY; 0 0 1] in float.
+ *   The rows of A are the float products of :238-256 (H, 16 x 9) and :280-288 (F, 8 x 9, PADDED WITH A ZERO NINTH ROW).
+ *   vt.row(8) of cv::SVDecomp(A, ..., MODIFY_A | FULL_UV) is the one-sided Jacobi stated above orbfe_enqueue_triangulate_pairs with 9
+ *   columns instead of 4 and m = 16 / 9 rows: the same pair order, eps, 30-sweep cap, beta branches, float rotations, double square sums
+ *   and strict selection sort (which here carries the rows of At too); the answer is Vt row 8.  OpenCV decomposes the 8 x 9 matrix
+ *   through its transpose and completes the basis from a pseudo-random vector: that is NOT restated.  Both scores are invariant to the
+ *   sign and scale of the matrix.
+ *   Rank-2 step (:297-301): the same Jacobi on the 3 x 3 Fpre (At row i = column i of Fpre); w[i] = (float)W[i];
+ *   u[k][i] = At[i][k] * (float)(1 / W[i]) (0 when W[i] <= FLT_MIN; OpenCV's random completion of a zero singular value is not
+ *   restated); w[2] = 0; Fn = (u * diag(w)) * vt, each a cv::Mat product: per element a double sum over k in index order, rounded once.
+ *   T2.inv() and H21i.inv() are OpenCV's closed 3 x 3 form: d = m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20)
+ *   + m02 * (m10 * m21 - m11 * m20) in double; d == 0 gives the ZERO MATRIX; otherwise each cofactor in double times 1 / d, rounded
+ *   once.  H21i = (T2inv * Hn) * T1, F21i = (T2t * Fn) * T1 under the product rule.
+ *   CheckHomography / CheckFundamental (:336-384, :412-464) are literal float, left to right; invSigmaSquare =
+ *   (float)(1.0 / (double)(sigma * sigma)); w2in1inv = (float)(1.0 / (double)(h31inv * u2 + h32inv * v2 + h33inv)); the thresholds are
+ *   the floats 5.991f and 3.841f.  A singular H gives 1 / 0, then 0 * inf = NaN; `chiSquare > th` is false for NaN, so the score
+ *   becomes NaN, `currentScore > score` is false and the hypothesis never wins (0 / 0 in CheckFundamental likewise).  The score is the
+ *   sequential float sum in match order, the two terms of match i before those of match i + 1.  The winner's flags are evaluated again
+ *   with the same operations. */
+#define ORBFE_INITIALIZER_MAX_MATCHES 65535
+#define ORBFE_INITIALIZER_MAX_ITERATIONS 65535
+#define ORBFE_INITIALIZER_MAX_KEYS (1 << 24)
+int orbfe_enqueue_find_homography_fundamental(orbfe_context *ctx,
+        const orbfe_keypoint *d_keys1_un, int n1, const orbfe_keypoint *d_keys2_un, int n2,
+        const int32_t *d_pairs /* [N][2] */, int N, const int32_t *d_sets /* [iterations][8] */, int iterations,
+        const float norm1[4], const float norm2[4] /* HOST: meanX, meanY, sX, sY of Normalize(mvKeys1 / mvKeys2) */, float sigma,
+        float *d_H21 /* [9] */, float *d_F21 /* [9] */, float *d_score /* [2] */, int32_t *d_best /* [2] */,
+        uint8_t *d_inliers_h /* [N] or NULL */, uint8_t *d_inliers_f /* [N] or NULL */, int32_t *d_ninliers /* [2] or NULL */,
+        float *d_all_scores /* [2][iterations] or NULL */, int32_t *d_status /* [1] */, void *stream);
+/* The same from host arrays, synchronous on the context's stream: compacts matches12 (vMatches12: n1 entries, < 0 = none) into
+ * mvMatches12, runs Normalize on both frames, uploads, queues the call above, downloads.  *n_matches = N; inliers_h / inliers_f receive
+ * N entries in mvMatches12 order (n1 entries always suffice).  Outputs mirror the device ones; inliers_h, inliers_f, ninliers and
+ * all_scores may be NULL.  Returns ORBFE_ERR_INVALID as the call above does, and also -- after the outputs are written -- when the device
+ * reported a faulty index. */
+int orbfe_find_homography_fundamental(orbfe_context *ctx, const orbfe_keypoint *keys1_un, int n1, const orbfe_keypoint *keys2_un, int n2,
+        const int32_t *matches12 /* [n1] */, const int32_t *sets /* [iterations][8] */, int iterations, float sigma,
+        float *H21, float *F21, float *score, int32_t *best, uint8_t *inliers_h, uint8_t *inliers_f, int32_t *ninliers, float *all_scores,
+        int32_t *n_matches);
 /* KeyFrameDatabase::DetectLoopCandidates(KeyFrame *pKF, float minScore) (src/KeyFrameDatabase.cc:73-194; LoopClosing::DetectLoop,
  * src/LoopClosing.cc:131).  connected[k] != 0 marks the keyframes of pKF->GetConnectedKeyFrames() (may be NULL: none); covisibility
  * lists as for the relocalisation query.  Stateless: mLoopScore is only read for keyframes scored by the same call. */

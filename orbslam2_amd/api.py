@@ -45,6 +45,7 @@ EXPORTS = [
     "orbfe_enqueue_search_by_bow_kf", "orbfe_enqueue_search_by_bow_kf_batch",
     "orbfe_enqueue_update_map_points",
     "orbfe_enqueue_triangulate_pairs",
+    "orbfe_enqueue_find_homography_fundamental", "orbfe_find_homography_fundamental",
 ]
 NUM_STAGES = 8
 STAGE_NAMES = ["ingest", "pyramid", "blur", "fast", "octree", "describe", "stereo_match", "stereo_median"]  # orbfe_stage_name()
@@ -293,6 +294,10 @@ def load():
     L.orbfe_enqueue_search_by_bow_kf_batch.argtypes = [vp, C.POINTER(BowKeyframe), vp, C.c_int, C.c_int, C.c_float, C.c_int] + [vp] * 5
     L.orbfe_enqueue_triangulate_pairs.restype = C.c_int
     L.orbfe_enqueue_triangulate_pairs.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp]
+    L.orbfe_enqueue_find_homography_fundamental.restype = C.c_int
+    L.orbfe_enqueue_find_homography_fundamental.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_float] + [vp] * 10
+    L.orbfe_find_homography_fundamental.restype = C.c_int
+    L.orbfe_find_homography_fundamental.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_float] + [vp] * 9
     L.orbfe_enqueue_update_map_points.restype = C.c_int
     L.orbfe_enqueue_update_map_points.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int] + [vp] * 8
     _lib = L
@@ -803,6 +808,39 @@ class Context:
             self.h, None if kf1 is None else C.byref(kf1), None if kf2 is None else C.byref(kf2), mbf, ratio_factor, v(d_pairs or None),
             v(d_npairs or None), max_pairs, v(d_code or None), v(d_x3d or None), v(d_new or None), v(d_nnew or None), v(d_pos or None), n_rows,
             v(d_rows_used or None), int(patch_has_mp), v(d_status or None), v(stream or None)))
+
+    def enqueue_find_homography_fundamental(self, d_keys1_un, n1, d_keys2_un, n2, d_pairs, n_matches, d_sets, iterations, norm1, norm2, sigma,
+                                            d_H21, d_F21, d_score, d_best, d_status, d_inliers_h=0, d_inliers_f=0, d_ninliers=0, d_all_scores=0,
+                                            stream=0):
+        """Initializer::FindHomography + FindFundamental for one frame pair, every hypothesis of both models, asynchronous on `stream`.
+        d_pairs[n_matches][2] = mvMatches12, d_sets[iterations][8] = mvSets; norm1 / norm2 = (meanX, meanY, sX, sY) of Normalize on the
+        host (four floats each, None passes as NULL), read before the call returns.  d_H21[9], d_F21[9], d_score[2], d_best[2] (the
+        winning iteration or -1), d_status[1]; optional d_inliers_h / d_inliers_f[n_matches], d_ninliers[2], d_all_scores[2][iterations].
+        The per-hypothesis scratch is the context's: queue the calls of one context on one stream."""
+        v = C.c_void_p
+        nm = [None if n is None else (C.c_float * 4)(*[float(x) for x in n]) for n in (norm1, norm2)]
+        self._check(self.L.orbfe_enqueue_find_homography_fundamental(
+            self.h, v(d_keys1_un or None), n1, v(d_keys2_un or None), n2, v(d_pairs or None), n_matches, v(d_sets or None), iterations, nm[0], nm[1],
+            sigma, v(d_H21 or None), v(d_F21 or None), v(d_score or None), v(d_best or None), v(d_inliers_h or None), v(d_inliers_f or None),
+            v(d_ninliers or None), v(d_all_scores or None), v(d_status or None), v(stream or None)))
+
+    def find_homography_fundamental(self, keys1_un, keys2_un, matches12, sets, sigma=1.0):
+        """The same from host arrays, synchronous: keys*_un KP_DTYPE arrays, matches12 int32[n1] (vMatches12, < 0 = none), sets
+        int32[iterations][8].  Returns dict(H21, F21 (3x3, zeros without a winner), score[2], best[2], inliers_h, inliers_f (uint8[N]),
+        ninliers[2], all_scores[2][iterations], n_matches)."""
+        k1, k2 = np.ascontiguousarray(keys1_un, KP_DTYPE), np.ascontiguousarray(keys2_un, KP_DTYPE)
+        m = np.ascontiguousarray(matches12, np.int32)
+        st = np.ascontiguousarray(sets, np.int32).reshape(-1, 8)
+        assert len(m) == len(k1)
+        H, F = np.zeros(9, np.float32), np.zeros(9, np.float32)
+        score, best, nin = np.zeros(2, np.float32), np.zeros(2, np.int32), np.zeros(2, np.int32)
+        ih, jf = np.zeros(max(len(k1), 1), np.uint8), np.zeros(max(len(k1), 1), np.uint8)
+        scores = np.zeros((2, len(st)), np.float32)
+        n = C.c_int32(0)
+        self._check(self.L.orbfe_find_homography_fundamental(self.h, _p(k1), len(k1), _p(k2), len(k2), _p(m), _p(st), len(st), sigma, _p(H), _p(F),
+                                                             _p(score), _p(best), _p(ih), _p(jf), _p(nin), _p(scores), C.byref(n)))
+        return dict(H21=H.reshape(3, 3), F21=F.reshape(3, 3), score=score, best=best, inliers_h=ih[:n.value], inliers_f=jf[:n.value], ninliers=nin,
+                    all_scores=scores, n_matches=n.value)
 
     def enqueue_search_by_sim3(self, kf1, T1w, d_pts1, kf2, T2w, d_pts2, s12, R12, t12, th, d_match12, d_n_found, d_status, stream=0):
         """ORBmatcher::SearchBySim3 on two device-resident keyframes (GridKeyframe records on the host, device pointers inside),

@@ -87,6 +87,25 @@ struct orbfe_triangulate_args {
 };
 int orbfe_triangulate_launch(const orbfe_triangulate_args &a, hipStream_t s); // queues at most three launches; returns hipGetLastError()
 
+// orbfe_enqueue_find_homography_fundamental: what the entry point (orbfe_api.hip) hands to the launches (orbfe_initializer_device.hip).
+// T1, T2inv and T2t are made on the host from the two Normalize results; mats, ok and scores are the context's scratch.
+struct orbfe_initializer_args {
+    const orbfe_keypoint *keys1, *keys2;
+    const int32_t *pairs, *sets;
+    int n1, n2, N, iterations;
+    float norm1[4], norm2[4], T1[9], T2inv[9], T2t[9], inv_sigma2;
+    float *H21, *F21, *score;
+    int32_t *best;
+    uint8_t *inl_h, *inl_f;
+    int32_t *ninliers;
+    float *all_scores;
+    int32_t *status;
+    float *mats;     // [iterations][27]: H21i, H12i, F21i
+    int32_t *ok;     // [iterations]: the set's eight matches are addressable
+    float *scores;   // [2][iterations], as summed (a NaN keeps its bits here)
+};
+int orbfe_initializer_launch(const orbfe_initializer_args &a, hipStream_t s); // a memset and three launches; returns the first HIP error
+
 // No C++ exception may cross the C ABI (a ctypes / cgo / C caller would abort): every extern "C" function that returns a status is a
 // function-try-block closed by this handler.  The per-context lock of ORBFE_ENTRY is a local of the try block, so it is released first.
 #include <exception>

@@ -1,0 +1,403 @@
+// orbfe_initializer_device.hip -- Initializer::FindHomography and Initializer::FindFundamental (src/Initializer.cc:123-467) for one frame
+// pair, every RANSAC hypothesis of both models, asynchronous on the caller's stream.  The entry points and their checks are in
+// orbfe_api.hip; the arithmetic contract is stated in include/orbfe.h and DESIGN.md section 4l, and this file,
+// orbslam2_amd/host/Initializer.h and tests/initializer_model.py follow it operation by operation.
+//
+//   initializer_models_kernel   one wave per (set, model).  The 9 x 16 At, the 9 x 9 Vt and W live in LDS (dynamic row indices in private
+//                               arrays would go to scratch memory).  Every lane reads both rows of a pair whole (four b128 loads each, at a
+//                               fixed 16 entries: zero rows change no bit) and evaluates the double dot product, c, s, both rotated rows and
+//                               their square sums in index order -- the same values in all lanes, so the branches are uniform -- then
+//                               lanes 0..15 write one element of At each, lanes 16..24 one of Vt: one LDS round trip per rotation.  The 3 x 3 steps (products, inverse, the rank-2 step's second
+//                               Jacobi) follow in the same wave.  The wave leaves H21i, H12i / F21i in the context's scratch.
+//   initializer_score_kernel    one lane per (hypothesis, model) adds its 2 N terms in match order: the score is a sequential float sum by
+//                               definition, so a hypothesis is one dependent chain whatever computes the terms.  Lanes of a wave share the
+//                               match, so its keypoints are loaded once per wave.
+//   initializer_select_kernel   one workgroup per model: wave 0 takes the first strict maximum, then all 256 lanes evaluate the winner's
+//                               inlier flags (the same float operations as the score kernel, so the same bits) and count them.
+// All stores are plain vector stores.
+#include "../../include/orbfe.h"
+#include "orbfe_config.h"
+#include "orbfe_host.h"
+
+#include <cfloat>
+
+typedef orbfe_initializer_args Args;
+
+static_assert(sizeof(orbfe_keypoint) == 28, "orbfe_keypoint");
+
+#define AT_STRIDE 16 // row stride of At
+#define VT_STRIDE 9  // row stride of Vt
+
+// ---------------------------------------------------------------------------------------------------------------- the Jacobi, in LDS
+// one row of At (M floats, M a multiple of 4, 16-byte aligned) into registers: the address is wave-uniform, so the loads broadcast
+template <int M> __device__ __forceinline__ void load_row(const float *row, float (&r)[M])
+{
+#pragma unroll
+    for (int q = 0; q < M / 4; q++) {
+        const float4 v = reinterpret_cast<const float4 *>(row)[q];
+        r[4 * q] = v.x; r[4 * q + 1] = v.y; r[4 * q + 2] = v.z; r[4 * q + 3] = v.w;
+    }
+}
+
+template <int M> __device__ __forceinline__ double square_sum(const float (&r)[M])
+{
+    double sd = 0;
+#pragma unroll
+    for (int k = 0; k < M; k++) sd += (double)r[k] * (double)r[k];
+    return sd;
+}
+
+// cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) of an m x N float A (m <= M, rows m .. M - 1 of A ZERO: they change no bit) whose
+// transpose is in At, by one wave.  On return W holds the singular values, descending, and the rows of At and Vt are carried by the
+// selection sort.  Every lane reads both rows of a pair whole, evaluates p, the skip test, c, s, both rotated rows and their square sums
+// in index order -- the same values in all lanes, so every branch is wave-uniform -- and writes back the one element it owns.
+template <int N, int M> __device__ __forceinline__ void jacobi_wave(float *At, float *Vt, double *W, int lane)
+{
+    if (lane < N) {
+        float r[M];
+        load_row<M>(At + lane * AT_STRIDE, r);
+        W[lane] = square_sum<M>(r);
+        for (int k = 0; k < N; k++) Vt[lane * VT_STRIDE + k] = lane == k ? 1.f : 0.f;
+    }
+    __syncthreads();
+    const double eps = (double)FLT_EPSILON * 2;
+    const bool in_a = lane < M, in_v = lane >= 16 && lane < 16 + N;
+    for (int iter = 0; iter < 30; iter++) {
+        bool changed = false;
+        for (int i = 0; i < N - 1; i++)
+            for (int j = i + 1; j < N; j++) {
+                float *Ai = At + i * AT_STRIDE, *Aj = At + j * AT_STRIDE;
+                float *Xi = in_a ? Ai + lane : Vt + i * VT_STRIDE + (lane - 16), *Xj = in_a ? Aj + lane : Vt + j * VT_STRIDE + (lane - 16);
+                float ai[M], aj[M], x = 0.f, y = 0.f;
+                load_row<M>(Ai, ai);
+                load_row<M>(Aj, aj);
+                if (in_a || in_v) { x = *Xi; y = *Xj; }
+                const double a = W[i], b = W[j];
+                double p = 0;
+#pragma unroll
+                for (int k = 0; k < M; k++) p += (double)ai[k] * (double)aj[k];
+                if (fabs(p) <= eps * sqrt(a * b)) continue;
+                p *= 2;
+                const double beta = a - b, gamma = sqrt(p * p + beta * beta); // a plain double sqrt, not hypot
+                float c, s;
+                if (beta < 0) {
+                    s = (float)sqrt(((gamma - beta) * 0.5) / gamma);
+                    c = (float)(p / (gamma * (double)s * 2));
+                } else {
+                    c = (float)sqrt((gamma + beta) / (gamma * 2));
+                    s = (float)(p / (gamma * (double)c * 2));
+                }
+                double na = 0, nb = 0;
+#pragma unroll
+                for (int k = 0; k < M; k++) {
+                    const float t0 = __fadd_rn(__fmul_rn(c, ai[k]), __fmul_rn(s, aj[k]));
+                    const float t1 = __fadd_rn(__fmul_rn(-s, ai[k]), __fmul_rn(c, aj[k]));
+                    na += (double)t0 * (double)t0;
+                    nb += (double)t1 * (double)t1;
+                }
+                const float o0 = __fadd_rn(__fmul_rn(c, x), __fmul_rn(s, y));
+                const float o1 = __fadd_rn(__fmul_rn(-s, x), __fmul_rn(c, y));
+                __syncthreads(); // every lane has read rows i and j
+                if (in_a || in_v) { *Xi = o0; *Xj = o1; }
+                if (lane == 0) { W[i] = na; W[j] = nb; }
+                __syncthreads();
+                changed = true;
+            }
+        if (!changed) break;
+    }
+    double w = 0;
+    if (lane < N) {
+        float r[M];
+        load_row<M>(At + lane * AT_STRIDE, r);
+        w = sqrt(square_sum<M>(r));
+    }
+    __syncthreads();
+    if (lane < N) W[lane] = w;
+    __syncthreads();
+    for (int i = 0; i < N - 1; i++) {
+        int j = i;
+        for (int k = i + 1; k < N; k++)
+            if (W[j] < W[k]) j = k;
+        if (i != j) { // uniform
+            const double wi = W[i], wj = W[j];
+            float *Xi = in_a ? At + i * AT_STRIDE + lane : Vt + i * VT_STRIDE + (lane - 16), *Xj = in_a ? At + j * AT_STRIDE + lane : Vt + j * VT_STRIDE + (lane - 16);
+            __syncthreads();
+            if (in_a || in_v) { const float t = *Xi; *Xi = *Xj; *Xj = t; }
+            if (lane == 0) { W[i] = wj; W[j] = wi; }
+            __syncthreads();
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- 3 x 3 cv::Mat steps
+// a cv::Mat product: per element a double sum over k in index order, rounded once
+__device__ __forceinline__ void mul3(const float (&a)[9], const float (&b)[9], float (&out)[9])
+{
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            double s = 0;
+#pragma unroll
+            for (int k = 0; k < 3; k++) s += (double)a[3 * r + k] * (double)b[3 * k + c];
+            out[3 * r + c] = (float)s;
+        }
+}
+
+// cv::Mat::inv() of a 3 x 3 float matrix: determinant and cofactors in double; det == 0 gives the zero matrix
+__device__ __forceinline__ void inv3(const float (&m)[9], float (&out)[9])
+{
+    const double m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5], m20 = m[6], m21 = m[7], m22 = m[8];
+    double d = m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20);
+    if (d == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; k++) out[k] = 0.f;
+        return;
+    }
+    d = 1. / d;
+    out[0] = (float)((m11 * m22 - m12 * m21) * d); out[1] = (float)((m02 * m21 - m01 * m22) * d); out[2] = (float)((m01 * m12 - m02 * m11) * d);
+    out[3] = (float)((m12 * m20 - m10 * m22) * d); out[4] = (float)((m00 * m22 - m02 * m20) * d); out[5] = (float)((m02 * m10 - m00 * m12) * d);
+    out[6] = (float)((m10 * m21 - m11 * m20) * d); out[7] = (float)((m01 * m20 - m00 * m21) * d); out[8] = (float)((m00 * m11 - m01 * m10) * d);
+}
+
+__device__ __forceinline__ bool pair_ok(const Args &a, int i1, int i2) { return i1 >= 0 && i1 < a.n1 && i2 >= 0 && i2 < a.n2; }
+
+// ---------------------------------------------------------------------------------------------------------------- the models
+__global__ __launch_bounds__(64) void initializer_models_kernel(Args a)
+{
+    __shared__ __attribute__((aligned(16))) float At[9 * AT_STRIDE];
+    __shared__ float Vt[9 * VT_STRIDE];
+    __shared__ double W[9];
+    const int it = blockIdx.x, model = blockIdx.y, lane = threadIdx.x;
+
+    // Select a minimum set: lane j < 8 takes match mvSets[it][j]; every index is checked before it becomes an address
+    bool ok = true;
+    float u1 = 0.f, v1 = 0.f, u2 = 0.f, v2 = 0.f;
+    if (lane < 8) {
+        const int idx = a.sets[8 * (size_t)it + lane];
+        ok = idx >= 0 && idx < a.N;
+        if (ok) {
+            const int i1 = a.pairs[2 * idx], i2 = a.pairs[2 * idx + 1];
+            ok = pair_ok(a, i1, i2);
+            if (ok) {
+                u1 = __fmul_rn(__fsub_rn(a.keys1[i1].x, a.norm1[0]), a.norm1[2]); v1 = __fmul_rn(__fsub_rn(a.keys1[i1].y, a.norm1[1]), a.norm1[3]);
+                u2 = __fmul_rn(__fsub_rn(a.keys2[i2].x, a.norm2[0]), a.norm2[2]); v2 = __fmul_rn(__fsub_rn(a.keys2[i2].y, a.norm2[1]), a.norm2[3]);
+            }
+        }
+    }
+    if (!__all(ok)) { // a faulty hypothesis is skipped: the score kernel gives it 0 and it never wins
+        if (lane == 0) {
+            if (model == 0) a.ok[it] = 0;
+            *a.status = ORBFE_ERR_INVALID; // every lane that writes writes this value
+        }
+        return;
+    }
+    if (lane == 0 && model == 0) a.ok[it] = 1;
+
+    for (int e = lane; e < 9 * AT_STRIDE; e += 64) At[e] = 0.f;
+    __syncthreads();
+    if (lane < 8) {
+        if (model == 0) { // ComputeH21 (:238-256)
+            const float r0[9] = {0.f, 0.f, 0.f, -u1, -v1, -1.f, __fmul_rn(v2, u1), __fmul_rn(v2, v1), v2};
+            const float r1[9] = {u1, v1, 1.f, 0.f, 0.f, 0.f, __fmul_rn(-u2, u1), __fmul_rn(-u2, v1), -u2};
+#pragma unroll
+            for (int c = 0; c < 9; c++) { At[c * AT_STRIDE + 2 * lane] = r0[c]; At[c * AT_STRIDE + 2 * lane + 1] = r1[c]; }
+        } else {          // ComputeF21 (:280-288); row 8 stays zero
+            const float r[9] = {__fmul_rn(u2, u1), __fmul_rn(u2, v1), u2, __fmul_rn(v2, u1), __fmul_rn(v2, v1), v2, u1, v1, 1.f};
+#pragma unroll
+            for (int c = 0; c < 9; c++) At[c * AT_STRIDE + lane] = r[c];
+        }
+    }
+    __syncthreads();
+    jacobi_wave<9, 16>(At, Vt, W, lane); // F's rows 8 .. 15 are zero
+
+    float X[9], t[9], M[9]; // vt.row(8).reshape(0, 3), in every lane
+#pragma unroll
+    for (int k = 0; k < 9; k++) X[k] = Vt[8 * VT_STRIDE + k];
+    float *out = a.mats + (size_t)it * 27;
+    if (model == 0) {
+        mul3(a.T2inv, X, t);
+        mul3(t, a.T1, M);      // H21i = T2inv * Hn * T1
+        float Mi[9];
+        inv3(M, Mi);           // H12i = H21i.inv()
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < 9; k++) { out[k] = M[k]; out[9 + k] = Mi[k]; }
+        }
+        return;
+    }
+    // the rank-2 step (:297-301): the same Jacobi on the 3 x 3 Fpre; At row i = column i of Fpre
+    __syncthreads();
+    if (lane < 9) At[(lane / 3) * AT_STRIDE + lane % 3] = Vt[8 * VT_STRIDE + 3 * (lane % 3) + lane / 3];
+    if (lane < 3) At[lane * AT_STRIDE + 3] = 0.f; // the fourth, zero row of the 3 x 3 problem
+    __syncthreads(); // jacobi_wave's first step overwrites Vt only after its own reads of At; the read of Vt above is complete here
+    jacobi_wave<3, 4>(At, Vt, W, lane);
+    float u[9], d[9], vt[9];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const double w = W[i];
+        const float s = w > (double)FLT_MIN ? (float)(1 / w) : 0.f; // the basis completion of a zero singular value is not restated
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            u[3 * k + i] = __fmul_rn(At[i * AT_STRIDE + k], s);
+            vt[3 * i + k] = Vt[i * VT_STRIDE + k];
+            d[3 * i + k] = 0.f;
+        }
+    }
+    d[0] = (float)W[0]; d[4] = (float)W[1]; // w.at<float>(2) = 0
+    mul3(u, d, t);
+    mul3(t, vt, X);            // Fn = u * diag(w) * vt
+    mul3(a.T2t, X, t);
+    mul3(t, a.T1, M);          // F21i = T2t * Fn * T1
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; k++) out[18 + k] = M[k];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the scores
+// the two terms of one match in CheckHomography (:336-384): returns bIn, adds to the running float sum
+__device__ __forceinline__ bool score_h(const float (&H)[18], float u1, float v1, float u2, float v2, float inv_sigma2, float &score)
+{
+    const float th = 5.991f;
+    bool in = true;
+    const float w2 = (float)(1.0 / (double)__fadd_rn(__fadd_rn(__fmul_rn(H[15], u2), __fmul_rn(H[16], v2)), H[17]));
+    const float u2in1 = __fmul_rn(__fadd_rn(__fadd_rn(__fmul_rn(H[9], u2), __fmul_rn(H[10], v2)), H[11]), w2);
+    const float v2in1 = __fmul_rn(__fadd_rn(__fadd_rn(__fmul_rn(H[12], u2), __fmul_rn(H[13], v2)), H[14]), w2);
+    const float du1 = __fsub_rn(u1, u2in1), dv1 = __fsub_rn(v1, v2in1);
+    const float chi1 = __fmul_rn(__fadd_rn(__fmul_rn(du1, du1), __fmul_rn(dv1, dv1)), inv_sigma2);
+    if (chi1 > th) in = false;
+    else score = __fadd_rn(score, __fsub_rn(th, chi1));
+    const float w1 = (float)(1.0 / (double)__fadd_rn(__fadd_rn(__fmul_rn(H[6], u1), __fmul_rn(H[7], v1)), H[8]));
+    const float u1in2 = __fmul_rn(__fadd_rn(__fadd_rn(__fmul_rn(H[0], u1), __fmul_rn(H[1], v1)), H[2]), w1);
+    const float v1in2 = __fmul_rn(__fadd_rn(__fadd_rn(__fmul_rn(H[3], u1), __fmul_rn(H[4], v1)), H[5]), w1);
+    const float du2 = __fsub_rn(u2, u1in2), dv2 = __fsub_rn(v2, v1in2);
+    const float chi2 = __fmul_rn(__fadd_rn(__fmul_rn(du2, du2), __fmul_rn(dv2, dv2)), inv_sigma2);
+    if (chi2 > th) in = false;
+    else score = __fadd_rn(score, __fsub_rn(th, chi2));
+    return in;
+}
+
+// the same of CheckFundamental (:412-464)
+__device__ __forceinline__ bool score_f(const float (&F)[18], float u1, float v1, float u2, float v2, float inv_sigma2, float &score)
+{
+    const float th = 3.841f, th_score = 5.991f;
+    bool in = true;
+    const float a2 = __fadd_rn(__fadd_rn(__fmul_rn(F[0], u1), __fmul_rn(F[1], v1)), F[2]);
+    const float b2 = __fadd_rn(__fadd_rn(__fmul_rn(F[3], u1), __fmul_rn(F[4], v1)), F[5]);
+    const float c2 = __fadd_rn(__fadd_rn(__fmul_rn(F[6], u1), __fmul_rn(F[7], v1)), F[8]);
+    const float num2 = __fadd_rn(__fadd_rn(__fmul_rn(a2, u2), __fmul_rn(b2, v2)), c2);
+    const float chi1 = __fmul_rn(__fdiv_rn(__fmul_rn(num2, num2), __fadd_rn(__fmul_rn(a2, a2), __fmul_rn(b2, b2))), inv_sigma2);
+    if (chi1 > th) in = false;
+    else score = __fadd_rn(score, __fsub_rn(th_score, chi1));
+    const float a1 = __fadd_rn(__fadd_rn(__fmul_rn(F[0], u2), __fmul_rn(F[3], v2)), F[6]);
+    const float b1 = __fadd_rn(__fadd_rn(__fmul_rn(F[1], u2), __fmul_rn(F[4], v2)), F[7]);
+    const float c1 = __fadd_rn(__fadd_rn(__fmul_rn(F[2], u2), __fmul_rn(F[5], v2)), F[8]);
+    const float num1 = __fadd_rn(__fadd_rn(__fmul_rn(a1, u1), __fmul_rn(b1, v1)), c1);
+    const float chi2 = __fmul_rn(__fdiv_rn(__fmul_rn(num1, num1), __fadd_rn(__fmul_rn(a1, a1), __fmul_rn(b1, b1))), inv_sigma2);
+    if (chi2 > th) in = false;
+    else score = __fadd_rn(score, __fsub_rn(th_score, chi2));
+    return in;
+}
+
+// the matrices of hypothesis `it` for `model`: H21i, H12i or F21i (the second nine unused)
+__device__ __forceinline__ void load_mats(const float *mats, int it, int model, float (&M)[18])
+{
+    const float *src = mats + (size_t)it * 27 + (model ? 18 : 0);
+#pragma unroll
+    for (int k = 0; k < 18; k++) M[k] = (model == 0 || k < 9) ? src[k] : 0.f;
+}
+
+__global__ __launch_bounds__(64) void initializer_score_kernel(Args a)
+{
+    const int it = blockIdx.x * 64 + threadIdx.x, model = blockIdx.y;
+    if (it >= a.iterations) return;
+    float score = 0.f;
+    if (a.ok[it]) {
+        float M[18];
+        load_mats(a.mats, it, model, M);
+        for (int i = 0; i < a.N; i++) {
+            const int i1 = a.pairs[2 * i], i2 = a.pairs[2 * i + 1];
+            if (!pair_ok(a, i1, i2)) continue; // a faulty match adds nothing; the select kernel reports it
+            const float u1 = a.keys1[i1].x, v1 = a.keys1[i1].y, u2 = a.keys2[i2].x, v2 = a.keys2[i2].y;
+            if (model == 0) score_h(M, u1, v1, u2, v2, a.inv_sigma2, score);
+            else score_f(M, u1, v1, u2, v2, a.inv_sigma2, score);
+        }
+    }
+    a.scores[(size_t)model * a.iterations + it] = score;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the winner
+__global__ __launch_bounds__(256) void initializer_select_kernel(Args a)
+{
+    __shared__ int s_best, s_count;
+    __shared__ float s_M[18];
+    const int tid = threadIdx.x, model = blockIdx.x;
+    const float *scores = a.scores + (size_t)model * a.iterations;
+    if (tid < 64) {
+        // `currentScore > score` from score = 0 in iteration order (:164, :215) ends at the first occurrence of the largest score above 0;
+        // a NaN score compares false both ways.  Each lane scans its iterations in ascending order, then the lanes are merged.
+        float bs = 0.f;
+        int bi = -1;
+        for (int it = tid; it < a.iterations; it += 64) {
+            const float s = scores[it];
+            if (s > bs) { bs = s; bi = it; }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const float os = __shfl_xor(bs, off);
+            const int oi = __shfl_xor(bi, off);
+            if (oi >= 0 && (os > bs || (os == bs && (bi < 0 || oi < bi)))) { bs = os; bi = oi; }
+        }
+        if (tid == 0) {
+            s_best = bi; s_count = 0;
+            a.best[model] = bi;
+            a.score[model] = bi >= 0 ? bs : 0.f;
+        }
+    }
+    if (a.all_scores)
+        for (int it = tid; it < a.iterations; it += 256) {
+            const float s = scores[it];
+            a.all_scores[(size_t)model * a.iterations + it] = s != s ? __int_as_float(0x7fc00000) : s; // one bit pattern for NaN
+        }
+    __syncthreads();
+    const int best = s_best;
+    if (best >= 0 && tid < (model == 0 ? 18 : 9)) {
+        const float v = a.mats[(size_t)best * 27 + (model ? 18 : 0) + tid];
+        s_M[tid] = v;
+        if (tid < 9) (model == 0 ? a.H21 : a.F21)[tid] = v;
+    }
+    __syncthreads();
+    float M[18];
+#pragma unroll
+    for (int k = 0; k < 18; k++) M[k] = (best >= 0 && (model == 0 || k < 9)) ? s_M[k] : 0.f;
+    uint8_t *inl = model == 0 ? a.inl_h : a.inl_f;
+    int count = 0;
+    bool faulty = false;
+    for (int i = tid; i < a.N; i += 256) {
+        const int i1 = a.pairs[2 * i], i2 = a.pairs[2 * i + 1];
+        bool in = false;
+        if (!pair_ok(a, i1, i2)) faulty = true;
+        else if (best >= 0) {
+            const float u1 = a.keys1[i1].x, v1 = a.keys1[i1].y, u2 = a.keys2[i2].x, v2 = a.keys2[i2].y;
+            float unused = 0.f;
+            in = model == 0 ? score_h(M, u1, v1, u2, v2, a.inv_sigma2, unused) : score_f(M, u1, v1, u2, v2, a.inv_sigma2, unused);
+        }
+        if (inl) inl[i] = in ? 1 : 0;
+        count += in;
+    }
+    if (faulty) *a.status = ORBFE_ERR_INVALID; // every lane that writes writes this value
+    if (count) atomicAdd(&s_count, count);
+    __syncthreads();
+    if (tid == 0 && a.ninliers) a.ninliers[model] = s_count;
+}
+
+int orbfe_initializer_launch(const orbfe_initializer_args &a, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(a.status, 0, sizeof(int32_t), s);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(initializer_models_kernel, dim3(a.iterations, 2), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(initializer_score_kernel, dim3((a.iterations + 63) / 64, 2), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(initializer_select_kernel, dim3(2), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
+}

@@ -1423,6 +1423,124 @@ def create_new_map_points_rows(out):
     ctx.close()
 
 
+def initializer_rows(out):
+    """Rows of --initializer; arguments prepared once."""
+    import ctypes as C
+    import gc
+    import subprocess
+    import tempfile
+    import torch
+    from orbslam2_amd import api
+    from tests import initializer_scenes as S
+    dev = torch.device("cuda:0")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
+    N, ITER, REPS, REPEATS = 500, 200, 10, 5
+    p = S.scene("general", N, ITER)
+    n1, n2 = len(p["keys1"]), len(p["keys2"])
+    out["scene"] = "%d matches between frames of %d and %d keypoints (tests/initializer_scenes.py, general depth), %d sets, sigma 1" % (N, n1, n2, ITER)
+    ctx = api.Context(width=S.WIDTH, height=S.HEIGHT, nfeatures=1000, fx=S.FX, fy=S.FY, cx=S.CX, cy=S.CY, bf=40.0)
+    so = os.path.join(os.environ.get("BENCH_OUT") or tempfile.mkdtemp(), "initializer_host_shim.so")
+    subprocess.run(["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-shared", "-fPIC", "-pthread", "-o", so, os.path.join(ROOT, "tools", "initializer_host_shim.cpp")],
+                   check=True)
+    host = C.CDLL(so).find_homography_fundamental_host
+    host.restype = C.c_int
+    host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 8 + [C.c_int]
+    P = lambda a: a.ctypes.data
+    keys1, keys2 = np.ascontiguousarray(p["keys1"]), np.ascontiguousarray(p["keys2"])
+    pairs, sets, m12 = np.ascontiguousarray(p["pairs"]), np.ascontiguousarray(p["sets"]), np.ascontiguousarray(p["matches12"])
+    norm1, norm2 = np.ascontiguousarray(p["norm1"]), np.ascontiguousarray(p["norm2"])
+
+    def outputs():
+        return dict(H=np.zeros(9, np.float32), F=np.zeros(9, np.float32), score=np.zeros(2, np.float32), best=np.zeros(2, np.int32), ih=np.zeros(N, np.uint8),
+                    jf=np.zeros(N, np.uint8), nin=np.zeros(2, np.int32), all=np.zeros((2, ITER), np.float32))
+
+    ho = {1: outputs(), 2: outputs()}
+
+    def host_form(threads):
+        o = ho[threads]
+        rc = host(P(keys1), n1, P(keys2), n2, P(pairs), N, P(sets), ITER, P(norm1), P(norm2), 1.0, P(o["H"]), P(o["F"]), P(o["score"]), P(o["best"]), P(o["ih"]),
+                  P(o["jf"]), P(o["nin"]), P(o["all"]), threads)
+        assert rc == 0
+
+    # (c): resident inputs; the small outputs are one block: H21 [0, 9), F21 [9, 18), score [18, 20), best [20, 22), ninliers [22, 24), status [24]
+    d_in = [up(keys1), up(keys2), up(pairs), up(sets)]
+    d_small = torch.zeros(32, dtype=torch.float32, device=dev)
+    d_flags = torch.zeros(2 * N, dtype=torch.uint8, device=dev)
+    d_all = torch.zeros(2 * ITER, dtype=torch.float32, device=dev)
+    h_small, h_flags = torch.zeros(32, dtype=torch.float32).pin_memory(), torch.zeros(2 * N, dtype=torch.uint8).pin_memory()
+    st = torch.cuda.Stream()
+    sp = d_small.data_ptr()
+    torch.cuda.synchronize()
+
+    def enqueue():
+        ctx.enqueue_find_homography_fundamental(d_in[0].data_ptr(), n1, d_in[1].data_ptr(), n2, d_in[2].data_ptr(), N, d_in[3].data_ptr(), ITER, norm1, norm2, 1.0,
+                                                sp, sp + 36, sp + 72, sp + 80, sp + 96, d_inliers_h=d_flags.data_ptr(), d_inliers_f=d_flags.data_ptr() + N,
+                                                d_ninliers=sp + 88, d_all_scores=d_all.data_ptr(), stream=st.cuda_stream)
+
+    def device_form():
+        with torch.cuda.stream(st):
+            enqueue()
+            h_small.copy_(d_small, non_blocking=True)
+            h_flags.copy_(d_flags, non_blocking=True)
+            st.synchronize()
+
+    sync_out = {}
+
+    def sync_form():
+        sync_out["r"] = ctx.find_homography_fundamental(keys1, keys2, m12, sets, 1.0)
+
+    host_form(1); host_form(2); device_form(); sync_form()
+    small = h_small.numpy()
+    got = dict(H=small[:9], F=small[9:18], score=small[18:20], best=small[20:22].view(np.int32), nin=small[22:24].view(np.int32), ih=h_flags.numpy()[:N],
+               jf=h_flags.numpy()[N:], all=d_all.cpu().numpy().reshape(2, ITER))
+    r = sync_out["r"]
+    sync = dict(H=r["H21"].reshape(-1), F=r["F21"].reshape(-1), score=r["score"], best=r["best"], nin=r["ninliers"], ih=r["inliers_h"], jf=r["inliers_f"], all=r["all_scores"])
+    assert small[24:25].view(np.int32)[0] == 0
+    for name, other in (("two host threads", ho[2]), ("device call", got), ("synchronous form", sync)):
+        for k, v in ho[1].items():
+            assert np.array_equal(np.ascontiguousarray(other[k]).view(np.uint8).reshape(-1), v.view(np.uint8).reshape(-1)), (name, k)
+    out["checked"] = "all four forms agree bit for bit: both matrices, scores, winners %s, inlier flags (%d H, %d F), every hypothesis's score" % (
+        ho[1]["best"].tolist(), int(ho[1]["nin"][0]), int(ho[1]["nin"][1]))
+
+    def loops(fn):
+        fn()
+        gc.collect()
+        gc.disable()  # the cyclic collector is off inside the window, as in the standard timeit module
+        try:
+            ts = []
+            for _ in range(REPS):
+                t0 = time.perf_counter()
+                fn()
+                ts.append((time.perf_counter() - t0) * 1e3)
+        finally:
+            gc.enable()
+        return round(sum(ts) / REPS, 4), round(max(ts), 4)
+
+    forms = [("a", lambda: host_form(1)), ("b", lambda: host_form(2)), ("c", device_form), ("d", sync_form)]
+    wall, worst, e_gpu = {k: [] for k, _ in forms}, {k: [] for k, _ in forms}, []
+    for _ in range(REPEATS):
+        for k, fn in forms:
+            m, w = loops(fn)
+            wall[k].append(m); worst[k].append(w)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(REPS):
+            enqueue()
+        e1.record(st)
+        st.synchronize()
+        e_gpu.append(round(e0.elapsed_time(e1) / REPS, 4))
+    rows = out["rows"]
+    names = {"a": "(a) Initializer.h on one host thread (g++ -O2), wall time", "b": "(b) Initializer.h on two host threads, H and F as the reference splits them, wall time",
+             "c": "(c) orbfe_enqueue_find_homography_fundamental on resident inputs + download of matrices, scores, winners, counts and flags + one synchronise, wall time",
+             "d": "(d) orbfe_find_homography_fundamental from host arrays (compaction, Normalize, uploads, the call, downloads), wall time"}
+    for k, _ in forms:
+        rows[names[k]] = {"ms_per_repeat": wall[k], "slowest_loop_ms": worst[k]}
+    rows["(e) the enqueue call alone, queued back to back, GPU time between two events"] = {"ms_per_repeat": e_gpu}
+    rows["median (b) / median (c)"] = round(float(np.median(wall["b"]) / np.median(wall["c"])), 2)
+    rows["median (b) / median (d)"] = round(float(np.median(wall["b"]) / np.median(wall["d"])), 2)
+    ctx.close()
+
+
 def load_other_build(api, path):
     """api.load() on the library at `path`, which may be older than the package: the prototypes load() sets for entry points
     that build lacks land on stand-ins that are not kept, so hasattr(lib, name) is False afterwards and a call fails loudly."""
@@ -1484,6 +1602,12 @@ def main():
     if "--create-new-map-points" in sys.argv[1:]:
         out = {"unit": "ms per keyframe (20 neighbours)", "rows": {}}
         create_new_map_points_rows(out)
+        out["build_id"] = api.build_id()
+        print(json.dumps(out, indent=1))
+        return
+    if "--initializer" in sys.argv[1:]:
+        out = {"unit": "ms per frame pair (500 matches, 200 sets, both models)", "rows": {}}
+        initializer_rows(out)
         out["build_id"] = api.build_id()
         print(json.dumps(out, indent=1))
         return
