@@ -446,6 +446,30 @@ def pose_optimization(Tcw, keys_un, u_right, has_point, Xw, inv_level_sigma2, fx
     return T, out[: len(k)].copy(), n
 
 
+class PoseTrace(C.Structure):
+    _fields_ = [("ne", C.c_int32), ("input_branch", C.c_int32), ("exchange", (C.c_int32 * 6) * 6), ("solves", C.c_int32),
+                ("solves_not_positive", C.c_int32), ("accepted", C.c_int32), ("rejected", C.c_int32), ("qmax_max", C.c_int32),
+                ("rounds", C.c_int32), ("stop", C.c_int32 * 4), ("exp_small", C.c_int32), ("rounds_no_active", C.c_int32),
+                ("huber_above", C.c_int32), ("huber_below", C.c_int32), ("outlier_returned", C.c_int32),
+                ("rounds_end_rejected", C.c_int32), ("q11_witnesses", C.c_int32), ("min_margin", C.c_double)]
+
+
+POSE_STOP = ("not_run", "iterations", "qmax", "rho_zero", "no_progress", "no_active_edge")
+
+
+def pose_trace():
+    """What the last pose_optimization call went through (orc_pose_trace): a dict of plain Python values."""
+    L = lib()
+    L.orc_pose_trace.restype = C.POINTER(PoseTrace)
+    L.orc_pose_eval_count.restype = C.c_int
+    t = L.orc_pose_trace().contents
+    d = {n: getattr(t, n) for n, _ in PoseTrace._fields_ if n not in ("exchange", "stop")}
+    d["exchanges"] = sorted((k, c) for k in range(6) for c in range(6) if t.exchange[k][c])
+    d["stop"] = [POSE_STOP[v] for v in t.stop]
+    d["evaluations"] = L.orc_pose_eval_count()
+    return d
+
+
 def cvt_gray(img, rgb=True, legacy14=False):
     """cv::cvtColor(img, COLOR_{RGB,BGR}[A]2GRAY) for uint8 HxWx{3,4} (src/Tracking.cc:269-294)."""
     a = np.ascontiguousarray(img, np.uint8)

@@ -210,6 +210,27 @@ int orc_search_by_sim3(const orc_grid *g1, const uint8_t *desc_kf1, const float 
 int orc_pose_optimization(float *Tcw, int N, const orc_keypoint *keys_un, const float *u_right, const uint8_t *has_point,
                           const float *Xw, const float *inv_level_sigma2, float fx, float fy, float cx, float cy, float bf,
                           uint8_t *outlier);
+/* What the last orc_pose_optimization call went through (diagnostic, like orc_pose_eval_count). */
+enum { ORC_POSE_STOP_NOT_RUN = 0, ORC_POSE_STOP_ITERATIONS = 1, ORC_POSE_STOP_QMAX = 2, ORC_POSE_STOP_RHO_ZERO = 3,
+       ORC_POSE_STOP_NO_PROGRESS = 4, ORC_POSE_STOP_NO_ACTIVE_EDGE = 5 };
+typedef struct {
+    int32_t ne;                  /* edges (slots with a map point) */
+    int32_t input_branch;        /* Quaternion(Matrix3) branch of the input pose: 0 = trace > 0, 1 + i = largest diagonal entry i */
+    int32_t exchange[6][6];      /* [K][C], K < C: LDLT steps K that exchanged with C, over all solves */
+    int32_t solves, solves_not_positive;
+    int32_t accepted, rejected;  /* Levenberg trials */
+    int32_t qmax_max;            /* most trials one iteration made */
+    int32_t rounds;              /* rounds run (1 when ne < 10) */
+    int32_t stop[4];             /* per round: ORC_POSE_STOP_* */
+    int32_t exp_small;           /* SE3Quat::exp calls with theta < 1e-5 */
+    int32_t rounds_no_active;    /* rounds that found every edge an outlier */
+    int32_t huber_above, huber_below; /* robust edge evaluations with chi2 above / not above delta^2 */
+    int32_t outlier_returned;    /* edges classified inlier that were outliers before */
+    int32_t rounds_end_rejected; /* rounds whose last trial was rejected (Q11 applies) */
+    int32_t q11_witnesses;       /* in those rounds: inlier edges whose class at the estimate differs from the class they got */
+    double min_margin;           /* smallest |chi2 / threshold - 1| over all classifications */
+} orc_pose_trace_t;
+const orc_pose_trace_t *orc_pose_trace(void);
 double orc_bow_score(const uint32_t *w1, const float *v1, int n1, const uint32_t *w2, const float *v2, int n2);
 int orc_detect_reloc_candidates(const uint32_t *q_words, const float *q_w, int nq,
                                 int n_kf, const int32_t *kf_off, const uint32_t *db_words, const float *db_w,

@@ -28,6 +28,12 @@
 
 typedef struct { double x, y, z, w; double t[3]; } se3q;
 
+/* Census of the branches one orc_pose_optimization call took (tests/pose_scenes.py, tests/test_pose_census.py): read back
+ * through orc_pose_trace(), in the style of orc_pose_eval_count().  Diagnostic only: nothing below reads it. */
+static orc_pose_trace_t g_trace;
+static int g_quat_branch; /* branch of the last quat_from_matrix: 0 = trace > 0, 1 + i otherwise */
+const orc_pose_trace_t *orc_pose_trace(void) { return &g_trace; }
+
 static void quat_from_matrix(const double m[3][3], se3q *q) /* Eigen quaternionbase_assign_impl<Matrix3> */
 {
     double t = m[0][0] + m[1][1] + m[2][2];
@@ -39,11 +45,13 @@ static void quat_from_matrix(const double m[3][3], se3q *q) /* Eigen quaternionb
         c[0] = (m[2][1] - m[1][2]) * t;
         c[1] = (m[0][2] - m[2][0]) * t;
         c[2] = (m[1][0] - m[0][1]) * t;
+        g_quat_branch = 0;
     } else {
         int i = 0;
         if (m[1][1] > m[0][0]) i = 1;
         if (m[2][2] > m[i][i]) i = 2;
         const int j = (i + 1) % 3, k = (j + 1) % 3;
+        g_quat_branch = 1 + i;
         t = sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0);
         c[i] = 0.5 * t;
         t = 0.5 / t;
@@ -108,6 +116,7 @@ static void se3_exp(const double u[6], se3q *out) /* SE3Quat::exp, se3quat.h:218
     double O2[3][3], R[3][3], V[3][3];
     mat3_mul(O, O, O2);
     if (theta < 0.00001) {
+        g_trace.exp_small++;
         for (int i = 0; i < 3; i++)
             for (int j = 0; j < 3; j++) { R[i][j] = ((i == j) ? 1.0 : 0.0) + O[i][j] + O2[i][j]; V[i][j] = R[i][j]; }
     } else {
@@ -163,6 +172,7 @@ static int ldlt_solve6(const double Hin[6][6], const double *b, double *x)
             if (fabs(A[i][i]) > big) { big = fabs(A[i][i]); p = i; }
         perm[k] = p;
         if (p != k) { /* symmetric row / column exchange */
+            g_trace.exchange[k][p]++;
             for (int j = 0; j < 6; j++) { const double t = A[k][j]; A[k][j] = A[p][j]; A[p][j] = t; }
             for (int i = 0; i < 6; i++) { const double t = A[i][k]; A[i][k] = A[i][p]; A[i][p] = t; }
         }
@@ -177,7 +187,8 @@ static int ldlt_solve6(const double Hin[6][6], const double *b, double *x)
             A[i][k] = (fabs(d) > DBL_MIN) ? s / d : 0.0;
         }
     }
-    if (!positive) return 0;
+    g_trace.solves++;
+    if (!positive) { g_trace.solves_not_positive++; return 0; }
     double y[6];
     for (int i = 0; i < 6; i++) y[i] = b[i];
     for (int k = 0; k < 6; k++) if (perm[k] != k) { const double t = y[k]; y[k] = y[perm[k]]; y[perm[k]] = t; }
@@ -253,8 +264,12 @@ static double active_errors_and_chi(pose_edge *E, int ne, const se3q *est, const
     for (int k = 0; k < ne; k++) { /* activeRobustChi2 */
         if (E[k].level != 0) continue;
         const double e2 = edge_chi2(&E[k]);
-        if (E[k].robust) { double rho[3]; huber(&E[k], e2, rho); chi += rho[0]; }
-        else chi += e2;
+        if (E[k].robust) {
+            double rho[3];
+            huber(&E[k], e2, rho);
+            chi += rho[0];
+            if (e2 <= E[k].dsqr) g_trace.huber_below++; else g_trace.huber_above++;
+        } else chi += e2;
     }
     return chi;
 }
@@ -307,11 +322,13 @@ static void build_system(const pose_edge *E, int ne, const se3q *est, const cam_
 }
 
 /* One optimizer.optimize(10) call (core/sparse_optimizer.cpp:354-419 driving the Levenberg solver). */
-static void optimize_round(pose_edge *E, int ne, se3q *est, const cam_d *c, double *x /* solver's _x, persists */)
+/* Returns why the round stopped (ORC_POSE_STOP_*); *last_rejected: the last trial of the round was rejected. */
+static int optimize_round(pose_edge *E, int ne, se3q *est, const cam_d *c, double *x /* solver's _x, persists */, int *last_rejected)
 {
     int nactive = 0;
+    *last_rejected = 0;
     for (int k = 0; k < ne; k++) nactive += E[k].level == 0;
-    if (nactive == 0) return; /* no active vertex: optimize() returns -1 before touching anything */
+    if (nactive == 0) return ORC_POSE_STOP_NO_ACTIVE_EDGE; /* no active vertex: optimize() returns -1 before touching anything */
     double lambda = -1.0, ni = 2.0;
     int n_bad = 0;
     for (int it = 0; it < 10; it++) {
@@ -352,18 +369,25 @@ static void optimize_round(pose_edge *E, int ne, se3q *est, const cam_d *c, doub
                 lambda *= sf;
                 ni = 2;
                 current_chi = temp_chi;
+                g_trace.accepted++;
+                *last_rejected = 0;
             } else {
                 lambda *= ni;
                 ni *= 2;
                 *est = backup;
+                g_trace.rejected++;
+                *last_rejected = 1;
             }
             qmax++;
         } while (rho < 0 && qmax < 10);
-        if (qmax == 10 || rho == 0) return;
+        if (qmax > g_trace.qmax_max) g_trace.qmax_max = qmax;
+        if (qmax == 10) return ORC_POSE_STOP_QMAX;
+        if (rho == 0) return ORC_POSE_STOP_RHO_ZERO;
         if ((ini_chi - current_chi) * 1e3 < ini_chi) n_bad++;
         else n_bad = 0;
-        if (n_bad >= 3) return;
+        if (n_bad >= 3) return ORC_POSE_STOP_NO_PROGRESS;
     }
+    return ORC_POSE_STOP_ITERATIONS;
 }
 
 /* Optimizer::PoseOptimization (src/Optimizer.cc:283-495).  Tcw: 4x4 row-major float, in/out (pFrame->mTcw / SetPose).
@@ -376,6 +400,8 @@ int orc_pose_optimization(float *Tcw, int N, const orc_keypoint *keys_un, const 
 {
     pose_edge *E = (pose_edge *)calloc((size_t)(N > 0 ? N : 1), sizeof(pose_edge));
     g_eval_count = 0;
+    memset(&g_trace, 0, sizeof(g_trace));
+    g_trace.min_margin = DBL_MAX;
     const float delta_mono = (float)sqrt(5.991), delta_stereo = (float)sqrt(7.815);
     int ne = 0;
     for (int i = 0; i < N; i++) {
@@ -392,6 +418,7 @@ int orc_pose_optimization(float *Tcw, int N, const orc_keypoint *keys_un, const 
         for (int k = 0; k < 3; k++) e->Xw[k] = Xw[(size_t)i * 3 + k];
         e->level = 0;
     }
+    g_trace.ne = ne;
     if (ne < 3) { free(E); return 0; }
     const cam_d cam = {fx, fy, cx, cy, bf};
     const float chi2_mono = 5.991f, chi2_stereo = 7.815f;
@@ -400,15 +427,29 @@ int orc_pose_optimization(float *Tcw, int N, const orc_keypoint *keys_un, const 
     int n_bad = 0;
     for (int it = 0; it < 4; it++) {
         se3_from_cv(Tcw, &est);
-        optimize_round(E, ne, &est, &cam, x);
+        if (it == 0) g_trace.input_branch = g_quat_branch;
+        int last_rejected;
+        g_trace.stop[it] = optimize_round(E, ne, &est, &cam, x, &last_rejected);
+        g_trace.rounds = it + 1;
+        if (g_trace.stop[it] == ORC_POSE_STOP_NO_ACTIVE_EDGE) g_trace.rounds_no_active++;
+        if (last_rejected) g_trace.rounds_end_rejected++;
         n_bad = 0;
         /* the reference walks the mono edges, then the stereo edges; the two walks touch disjoint state */
         for (int k = 0; k < ne; k++) {
             pose_edge *e = &E[k];
-            if (outlier[e->idx]) edge_compute_error(e, &est, &cam);
+            const int was_outlier = outlier[e->idx];
+            if (was_outlier) edge_compute_error(e, &est, &cam);
             const float chi2 = (float)edge_chi2(e);
-            if (chi2 > (e->stereo ? chi2_stereo : chi2_mono)) { outlier[e->idx] = 1; e->level = 1; n_bad++; }
-            else { outlier[e->idx] = 0; e->level = 0; }
+            const float th = e->stereo ? chi2_stereo : chi2_mono;
+            const double margin = fabs((double)chi2 / (double)th - 1.0);
+            if (margin < g_trace.min_margin) g_trace.min_margin = margin; /* a NaN chi2 leaves it alone */
+            if (last_rejected && !was_outlier) { /* Q11 witness: the class at the estimate differs from the class that is kept */
+                pose_edge at_est = *e;
+                edge_compute_error(&at_est, &est, &cam);
+                if (((float)edge_chi2(&at_est) > th) != (chi2 > th)) g_trace.q11_witnesses++;
+            }
+            if (chi2 > th) { outlier[e->idx] = 1; e->level = 1; n_bad++; }
+            else { outlier[e->idx] = 0; e->level = 0; if (was_outlier) g_trace.outlier_returned++; }
             if (it == 2) e->robust = 0;
         }
         if (ne < 10) break;
