@@ -14,6 +14,7 @@
 #include "orbfe_host.h"
 #include "orbfe_bow_vocab.h"
 #include "orbfe_epipolar.h"
+#include "orbfe_match_resolve.h"
 
 #include <algorithm>
 #include <cmath>
@@ -120,7 +121,7 @@ try {
             }
         }
     }
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(ctx->params.device));
     if (st->d_data) { hipFree(st->d_data); st->d_data = nullptr; }
     st->loaded = false;
     ORBFE_HIP_TRY(ctx, hipMalloc((void **)&st->d_data, p.total_size));
@@ -149,8 +150,8 @@ try {
     orbfe_bow_state *st = orbfe_ctx_bow_state(ctx);
     if (!st || !st->loaded) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "no vocabulary loaded (orbfe_vocab_load)");
     if (n == 0) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "Vocabulary::transform No input data"); // fbow.cpp:52
-    hipStream_t s = orbfe_ctx_stream(ctx);
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    hipStream_t s = ctx->stream;
+    ORBFE_HIP_TRY(ctx, hipSetDevice(ctx->params.device));
     int rc = ensure_scratch(ctx, st, (size_t)n * (32 + 12));
     if (rc != ORBFE_OK) return rc;
     uint8_t *d_desc = (uint8_t *)st->d_scratch;
@@ -197,14 +198,31 @@ try {
     return ORBFE_OK;
 } ORBFE_CATCH(nullptr)
 
-static int rot_bin(float a1, float a2)
+using orbfe_resolve::rot_bin;
+
+// dist[k] = DescriptorDistance(desc_a[pa[k]], desc_b[pb[k]]) for the np > 0 pairs of a merge-join: both descriptor arrays and the pair
+// lists go up, pair_hamming_kernel runs, the distances come down; returns after the stream is idle
+static int pair_distances(orbfe_context *ctx, orbfe_bow_state *st, const uint8_t *desc_a, int n_a, const uint8_t *desc_b, int n_b,
+                          const std::vector<uint32_t> &pa, const std::vector<uint32_t> &pb, std::vector<uint16_t> &dist)
 {
-    const float factor = 1.0f / HISTO_LENGTH;
-    float rot = a1 - a2;
-    if (rot < 0.0) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == HISTO_LENGTH) bin = 0;
-    return bin;
+    const int np = (int)pa.size();
+    hipStream_t s = ctx->stream;
+    ORBFE_HIP_TRY(ctx, hipSetDevice(ctx->params.device));
+    const size_t need = (size_t)32 * n_a + (size_t)32 * n_b + (size_t)np * (4 + 4 + 2) + 64;
+    int rc = ensure_scratch(ctx, st, need);
+    if (rc != ORBFE_OK) return rc;
+    uint8_t *d_a = (uint8_t *)st->d_scratch, *d_b = d_a + (size_t)32 * n_a;
+    uint32_t *d_pa = (uint32_t *)(d_b + (size_t)32 * n_b), *d_pb = d_pa + np;
+    uint16_t *d_dist = (uint16_t *)(d_pb + np);
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_a, desc_a, (size_t)32 * n_a, hipMemcpyHostToDevice, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_b, desc_b, (size_t)32 * n_b, hipMemcpyHostToDevice, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_pa, pa.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_pb, pb.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(pair_hamming_kernel, dim3((np + 255) / 256), dim3(256), 0, s, d_a, d_b, d_pa, d_pb, np, d_dist);
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(dist.data(), d_dist, sizeof(uint16_t) * np, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
+    return ORBFE_OK;
 }
 
 // ORBmatcher::SearchByFboW(KeyFrame*, Frame&, vpMapPointMatches), src/ORBmatcher.cc:157-283
@@ -249,22 +267,8 @@ static int search_by_bow_impl(orbfe_context *ctx, bool kf_kf,
     const int np = (int)pa.size();
     std::vector<uint16_t> dist(np > 0 ? np : 1);
     if (np > 0) {
-        hipStream_t s = orbfe_ctx_stream(ctx);
-        ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
-        const size_t need = (size_t)32 * n_kf + (size_t)32 * n_f + (size_t)np * (4 + 4 + 2) + 64;
-        int rc = ensure_scratch(ctx, st, need);
+        const int rc = pair_distances(ctx, st, kf_desc, n_kf, f_desc, n_f, pa, pb, dist);
         if (rc != ORBFE_OK) return rc;
-        uint8_t *d_a = (uint8_t *)st->d_scratch, *d_b = d_a + (size_t)32 * n_kf;
-        uint32_t *d_pa = (uint32_t *)(d_b + (size_t)32 * n_f), *d_pb = d_pa + np;
-        uint16_t *d_dist = (uint16_t *)(d_pb + np);
-        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_a, kf_desc, (size_t)32 * n_kf, hipMemcpyHostToDevice, s));
-        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_b, f_desc, (size_t)32 * n_f, hipMemcpyHostToDevice, s));
-        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_pa, pa.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
-        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_pb, pb.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(pair_hamming_kernel, dim3((np + 255) / 256), dim3(256), 0, s, d_a, d_b, d_pa, d_pb, np, d_dist);
-        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(dist.data(), d_dist, sizeof(uint16_t) * np, hipMemcpyDeviceToHost, s));
-        ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
-        ORBFE_HIP_TRY(ctx, hipGetLastError());
     }
     // greedy resolve in the reference's order
     std::vector<int> hist[HISTO_LENGTH];
@@ -414,8 +418,8 @@ try {
     if (!st) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "out of host memory");
     for (int i = 1; i < n; i++)
         if (words[i] <= words[i - 1]) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "BoW words must be strictly ascending (std::map order)");
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
-    hipStream_t s = orbfe_ctx_stream(ctx);
+    ORBFE_HIP_TRY(ctx, hipSetDevice(ctx->params.device));
+    hipStream_t s = ctx->stream;
     if (st->db_used + (size_t)n > st->db_cap) { // grow: twice the need, contents moved device to device
         const size_t cap = 2 * (st->db_used + (size_t)n) + 1024;
         uint32_t *nw = nullptr; float *nv = nullptr;
@@ -445,8 +449,8 @@ try {
 // Rare (once the dead words outnumber the live ones), so it goes through the host.
 static int kfdb_compact(orbfe_context *ctx, orbfe_bow_state *st)
 {
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
-    hipStream_t s = orbfe_ctx_stream(ctx);
+    ORBFE_HIP_TRY(ctx, hipSetDevice(ctx->params.device));
+    hipStream_t s = ctx->stream;
     std::vector<uint32_t> w(st->db_used ? st->db_used : 1);
     std::vector<float> v(st->db_used ? st->db_used : 1);
     if (st->db_used) {
@@ -510,8 +514,8 @@ static int kfdb_scores(orbfe_context *ctx, orbfe_bow_state *st, const uint32_t *
         if (!st->db_dead[k]) { live.push_back(k); l_off.push_back(st->db_off[k]); l_len.push_back(st->db_len[k]); }
     const int n_live = (int)live.size();
     if (n_live == 0) return ORBFE_OK;
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
-    hipStream_t s = orbfe_ctx_stream(ctx);
+    ORBFE_HIP_TRY(ctx, hipSetDevice(ctx->params.device));
+    hipStream_t s = ctx->stream;
     const size_t need = (size_t)nq * 8 + (size_t)n_live * 20 + 64;
     int rc = ensure_scratch(ctx, st, need);
     if (rc != ORBFE_OK) return rc;
@@ -699,8 +703,8 @@ try {
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
     orbfe_bow_state *st = orbfe_ctx_bow_state(ctx);
     if (!st) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "out of host memory");
-    const int nlevels = orbfe_ctx_params(ctx)->nlevels;
-    const float *scale = orbfe_ctx_scale_factors(ctx);
+    const int nlevels = ctx->params.nlevels;
+    const float *scale = ctx->plan.scale;
     for (int j = 0; j < n1; j++) match12[j] = -1;
     *nmatches = 0;
     float ex, ey; // epipole in the second image (:658-664)
@@ -731,22 +735,8 @@ try {
     const int np = (int)pa.size();
     std::vector<uint16_t> dist(np > 0 ? np : 1);
     if (np > 0) {
-        hipStream_t s = orbfe_ctx_stream(ctx);
-        ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
-        const size_t need = (size_t)32 * n1 + (size_t)32 * n2 + (size_t)np * (4 + 4 + 2) + 64;
-        int rc = ensure_scratch(ctx, st, need);
+        const int rc = pair_distances(ctx, st, desc1, n1, desc2, n2, pa, pb, dist);
         if (rc != ORBFE_OK) return rc;
-        uint8_t *d_a = (uint8_t *)st->d_scratch, *d_b = d_a + (size_t)32 * n1;
-        uint32_t *d_pa = (uint32_t *)(d_b + (size_t)32 * n2), *d_pb = d_pa + np;
-        uint16_t *d_dist = (uint16_t *)(d_pb + np);
-        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_a, desc1, (size_t)32 * n1, hipMemcpyHostToDevice, s));
-        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_b, desc2, (size_t)32 * n2, hipMemcpyHostToDevice, s));
-        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_pa, pa.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
-        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d_pb, pb.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(pair_hamming_kernel, dim3((np + 255) / 256), dim3(256), 0, s, d_a, d_b, d_pa, d_pb, np, d_dist);
-        ORBFE_HIP_TRY(ctx, hipMemcpyAsync(dist.data(), d_dist, sizeof(uint16_t) * np, hipMemcpyDeviceToHost, s));
-        ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
-        ORBFE_HIP_TRY(ctx, hipGetLastError());
     }
     // sequential resolve in the reference's order (vbMatched2 makes it order dependent)
     std::vector<uint8_t> matched2(n2 > 0 ? n2 : 1, 0);

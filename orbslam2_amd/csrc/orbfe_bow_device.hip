@@ -223,17 +223,16 @@ try {
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
     orbfe_bow_state *st = orbfe_ctx_bow_state(ctx);
     if (!st || !st->loaded) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "no vocabulary loaded (orbfe_vocab_load)");
-    const DeviceConfig *cfg = orbfe_ctx_config(ctx);
-    const DeviceBuffers *buf = orbfe_ctx_buffers(ctx);
-    if (slot < 0 || slot >= orbfe_ctx_last_images(ctx))
-        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d: the latest extraction call filled %d image slots", slot, orbfe_ctx_last_images(ctx));
+    const DeviceConfig *cfg = &ctx->cfg;
+    const DeviceBuffers *buf = &ctx->buf;
+    if (slot < 0 || slot >= ctx->last_images)
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d: the latest extraction call filled %d image slots", slot, ctx->last_images);
     const int cap = cfg->sel_total;
     if (cap <= 0 || cap > 65535) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "frames with more than 65535 keypoints are not supported");
-    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
-    if (st->resident.ensure((size_t)cap * 7 * sizeof(uint32_t))) return orbfe_fail(ctx, ORBFE_ERR_HIP, "BoW scratch allocation failed");
-    const int rc = orbfe_ctx_order_after_extraction(ctx, s); // an event wait on the stream, no host wait
+    hipStream_t s;
+    const int rc = orbfe_enqueue_on(ctx, stream, true, &s); // an event wait on the stream, no host wait
     if (rc != ORBFE_OK) return rc;
+    if (st->resident.ensure((size_t)cap * 7 * sizeof(uint32_t))) return orbfe_fail(ctx, ORBFE_ERR_HIP, "BoW scratch allocation failed");
     uint32_t *ids = (uint32_t *)st->resident.p, *sorted_id = ids + 2 * (size_t)cap, *sorted_pay = sorted_id + 2 * (size_t)cap; // [2][cap] each: words, nodes
     float *wt = (float *)(sorted_pay + 2 * (size_t)cap);
     const BowTree t = {st->d_data, (unsigned)st->p.block_size_bytes_wp, (unsigned)st->p.feature_off_start, (unsigned)st->p.child_off_start,
@@ -536,10 +535,10 @@ __global__ __launch_bounds__(1024) void bow_match_tail_batch_kernel(BowSearch a,
 // The slot's side of a BowSearch and the checks both entry points share.
 static int bow_search_frame_side(orbfe_context *ctx, int slot, BowSearch *a)
 {
-    const DeviceConfig *cfg = orbfe_ctx_config(ctx);
-    const DeviceBuffers *buf = orbfe_ctx_buffers(ctx);
-    if (slot < 0 || slot >= orbfe_ctx_last_images(ctx))
-        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d: the latest extraction call filled %d image slots", slot, orbfe_ctx_last_images(ctx));
+    const DeviceConfig *cfg = &ctx->cfg;
+    const DeviceBuffers *buf = &ctx->buf;
+    if (slot < 0 || slot >= ctx->last_images)
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d: the latest extraction call filled %d image slots", slot, ctx->last_images);
     const int cap = cfg->sel_total;
     if (cap <= 0 || cap > 65535) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "frames with more than 65535 keypoints are not supported");
     a->keys = (const KeyPointPOD *)buf->kps + (size_t)slot * cap; // mvKeys[].angle
@@ -564,9 +563,8 @@ try {
     int rc = bow_search_frame_side(ctx, slot, &a);
     if (rc != ORBFE_OK) return rc;
     const int cap = a.cap;
-    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
-    rc = orbfe_ctx_order_after_extraction(ctx, s);
+    hipStream_t s;
+    rc = orbfe_enqueue_on(ctx, stream, true, &s);
     if (rc != ORBFE_OK) return rc;
     a.kf_nodes = d_kf_nodes; a.kf_off = d_kf_off; a.kf_feat = d_kf_feat; a.kf_nnodes = kf_nnodes;
     a.kf_valid = d_kf_valid; a.kf_desc = d_kf_desc; a.kf_angle = d_kf_angle; a.n_kf = n_kf; a.kf_pos = d_kf_pos;
@@ -596,9 +594,8 @@ try {
     if (rc != ORBFE_OK) return rc;
     if (n_kfs == 0) return ORBFE_OK;
     const int cap = a.cap;
-    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
-    rc = orbfe_ctx_order_after_extraction(ctx, s);
+    hipStream_t s;
+    rc = orbfe_enqueue_on(ctx, stream, true, &s);
     if (rc != ORBFE_OK) return rc;
     a.kf_nodes = nullptr; a.kf_off = a.kf_feat = a.kf_valid = nullptr; a.kf_desc = nullptr; a.kf_angle = a.kf_pos = nullptr; // per record, on the device
     a.kf_nnodes = a.n_kf = 0;
@@ -860,16 +857,16 @@ try {
     }
     orbfe_bow_state *st = orbfe_ctx_bow_state(ctx);
     if (!st) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "out of host memory");
-    const int nlevels = orbfe_ctx_params(ctx)->nlevels;
+    const int nlevels = ctx->params.nlevels;
     if (nlevels < 1 || nlevels > ORBFE_MAX_LEVELS) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "nlevels = %d", nlevels);
-    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    hipStream_t s;
+    if (const int rc = orbfe_enqueue_on(ctx, stream, false, &s)) return rc;
     if (st->resident.ensure((size_t)(kf2->n > 64 ? kf2->n : 64))) return orbfe_fail(ctx, ORBFE_ERR_HIP, "BoW scratch allocation failed");
     TriSearch a;
     a.k1 = *kf1; a.k2 = *kf2; // a record without nodes may hold NULL arrays: the tail follows keys_un only through a match
     for (int k = 0; k < 9; k++) a.F12[k] = F12[k];
     orbfe_epipolar::epipole(Cw1, T2w, fx2, fy2, cx2, cy2, &a.ex, &a.ey);
-    const float *scale = orbfe_ctx_scale_factors(ctx);
+    const float *scale = ctx->plan.scale;
     for (int l = 0; l < ORBFE_MAX_LEVELS; l++) {
         a.scale[l] = l < nlevels ? scale[l] : 1.f;
         a.sigma2[l] = a.scale[l] * a.scale[l]; // mvLevelSigma2 (src/ORBextractor.cc:419-423)
@@ -1043,8 +1040,9 @@ try {
     int rc = bowkf_check_record(ctx, kf1, "kf1");
     if (rc == ORBFE_OK) rc = bowkf_check_record(ctx, kf2, "kf2");
     if (rc != ORBFE_OK) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    hipStream_t s;
+    rc = orbfe_enqueue_on(ctx, stream, false, &s);
+    if (rc != ORBFE_OK) return rc;
     BowKfSearch a;
     rc = bowkf_fill(ctx, &a, kf1, 1, kf2->n, nnratio, check_ori, d_match12, d_pairs, d_nmatches, d_status);
     if (rc != ORBFE_OK) return rc;
@@ -1068,8 +1066,9 @@ try {
     int rc = bowkf_check_record(ctx, kf1, "kf1");
     if (rc != ORBFE_OK) return rc;
     if (n_kfs == 0) return ORBFE_OK;
-    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    hipStream_t s;
+    rc = orbfe_enqueue_on(ctx, stream, false, &s);
+    if (rc != ORBFE_OK) return rc;
     BowKfSearch a;
     rc = bowkf_fill(ctx, &a, kf1, n_kfs, max_kf_n, nnratio, check_ori, d_match12, d_pairs, d_nmatches, d_status);
     if (rc != ORBFE_OK) return rc;

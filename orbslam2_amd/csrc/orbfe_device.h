@@ -125,4 +125,3 @@ void orbfe_launch_rgbd_batch(const DeviceConfig &cfg, const DeviceBuffers &buf, 
 // byte offsets of the arrays inside a packed result block (orbfe_packed_layout of include/orbfe.h mirrors it)
 struct PackedOffsets { size_t counts, level_counts, xy, angle, response, desc, u_right, depth; };
 void orbfe_launch_pack_results(const DeviceConfig &cfg, const DeviceBuffers &buf, uint8_t *d_out, const PackedOffsets &lay, int n_out, int img_step, bool stereo, hipStream_t s);
-void orbfe_launch_hamming_matrix(const uint8_t *da, int na, const uint8_t *db, int nb, int *dist, hipStream_t s);

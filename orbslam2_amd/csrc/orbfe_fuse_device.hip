@@ -114,10 +114,12 @@ try {
     ORBFE_ENTRY(ctx);
     if (!bounds || !d_cell_off || (n > 0 && (!d_keys_un || !d_cell_idx))) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
     GridFrame f;
-    const int rc = grid_frame_of(ctx, d_keys_un, n, bounds[0], bounds[1], bounds[2], bounds[3], 0, d_cell_off, d_cell_idx, f);
+    int rc = grid_frame_of(ctx, d_keys_un, n, bounds[0], bounds[1], bounds[2], bounds[3], 0, d_cell_off, d_cell_idx, f);
     if (rc != ORBFE_OK) return rc;
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
-    orbfe_launch_grid_build(f, stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx)); // with n == 0: 3073 zero offsets, no other access
+    hipStream_t s;
+    rc = orbfe_enqueue_on(ctx, stream, false, &s);
+    if (rc != ORBFE_OK) return rc;
+    orbfe_launch_grid_build(f, s); // with n == 0: 3073 zero offsets, no other access
     ORBFE_HIP_TRY(ctx, hipGetLastError());
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)
@@ -132,7 +134,7 @@ int orbfe_point_table_frame(orbfe_context *ctx, const orbfe_grid_keyframe *kf, i
     if (n_pts > 0 && kf->n > 0 &&
         (!t.pos || !t.normal || !t.max_distance || !t.min_distance || !t.pt_desc || !t.pt_valid || !kf->keys_un || !kf->desc || !kf->cell_off || !kf->cell_idx))
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null array in the point table or in the keyframe record");
-    const int nlevels = orbfe_ctx_params(ctx)->nlevels;
+    const int nlevels = ctx->params.nlevels;
     if (nlevels < 1 || nlevels > ORBFE_MAX_LEVELS) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "nlevels = %d", nlevels);
     return ORBFE_OK;
 }
@@ -144,7 +146,7 @@ static int enqueue_fuse(orbfe_context *ctx, int sim3, const orbfe_grid_keyframe 
     if (!kf || !pose || !d_best_idx || !d_n_fused || !d_status) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
     FuseArgs a;
     a.pts = {d_pt_index, n_rows, d_pos, d_normal, d_max_distance, d_min_distance, d_pt_desc, d_pt_valid};
-    const int rc = orbfe_point_table_frame(ctx, kf, n_pts, INT_MAX, a.pts, a.f); // the calls own no scratch: any count
+    int rc = orbfe_point_table_frame(ctx, kf, n_pts, INT_MAX, a.pts, a.f); // the calls own no scratch: any count
     if (rc != ORBFE_OK) return rc;
     a.V = orbfe_view(ctx, kf);
     if (sim3) orbfe_resolve::sim3_to_rt(pose, a.T);
@@ -154,8 +156,9 @@ static int enqueue_fuse(orbfe_context *ctx, int sim3, const orbfe_grid_keyframe 
     a.n_pts = n_pts;
     a.th = th;
     a.best_idx = d_best_idx; a.n_fused = d_n_fused; a.status = d_status;
-    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    hipStream_t s;
+    rc = orbfe_enqueue_on(ctx, stream, false, &s);
+    if (rc != ORBFE_OK) return rc;
     hipLaunchKernelGGL(fuse_reset_kernel, dim3(1), dim3(64), 0, s, d_n_fused, d_status);
     if (n_pts > 0) hipLaunchKernelGGL(fuse_kernel, dim3((n_pts + 3) / 4), dim3(256), 0, s, a);
     ORBFE_HIP_TRY(ctx, hipGetLastError());

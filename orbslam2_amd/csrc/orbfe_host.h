@@ -1,8 +1,11 @@
-// orbfe_host.h -- internal host-side accessors shared by the translation units of liborbfe.so.
+// orbfe_host.h -- the context and the host-side helpers shared by the translation units of liborbfe.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <mutex>
+#include <vector>
 #include "../../include/orbfe.h"
+#include "orbfe_device.h"
+#include "orbfe_plan.h"
 
 // growable device scratch buffer shared by the host-side entry points (matchers, BoW, pose)
 struct DevBuf {
@@ -23,9 +26,76 @@ struct DevBuf {
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
-struct orbfe_match_state;
+// lazily created state of the feature files; each is destroyed by orbfe_destroy
+struct orbfe_match_state;        // orbfe_match.hip
 orbfe_match_state *orbfe_match_state_create();
 void orbfe_match_state_destroy(orbfe_match_state *s);
+struct orbfe_match_device_state; // scratch and caches of the asynchronous, device-resident matchers (orbfe_match_device.hip)
+void orbfe_match_device_state_destroy(orbfe_match_device_state *s);
+struct orbfe_bow_state;          // orbfe_bow.hip, orbfe_bow_device.hip
+orbfe_bow_state *orbfe_bow_state_create();
+void orbfe_bow_state_destroy(orbfe_bow_state *s);
+struct orbfe_pose_state;         // orbfe_pose.hip
+orbfe_pose_state *orbfe_pose_state_create();
+void orbfe_pose_state_destroy(orbfe_pose_state *s);
+
+#define ORBFE_MAX_GROUPS 8
+
+struct orbfe_context {
+    orbfe_params params;
+    DeviceConfig cfg;
+    DeviceBuffers buf;        // device-resident frames of the latest extraction call
+    hipStream_t stream = nullptr;
+    uint8_t *d_in = nullptr;      // staging for host-image entry points [max_images][w*h]
+    float *d_depth_in = nullptr;  // staging for RGB-D depth
+    // pinned host staging of the single-frame entry points (lazily allocated): packed input rows, then one block of
+    // outputs per call so a frame costs one stream synchronisation instead of one blocking copy per array
+    uint8_t *h_in = nullptr;      // [min(max_images,2)][w*h]
+    float *h_depth_in = nullptr;  // [w*h]
+    uint8_t *h_out = nullptr;     // see HostOut
+    DevBuf d_pack;                // device staging of orbfe_fetch_batch_packed (lazily allocated for max_images)
+    hipEvent_t ev_pack = nullptr; // recorded behind the staging's device-to-host copy: the next packed fetch (whatever its stream) waits for it before it refills d_pack
+    bool ev_pack_set = false;
+    DevBuf d_ham;                 // scratch for orbfe_hamming_matrix
+    DevBuf d_und;                 // scratch for the undistortion entry points
+    int last_images = 0;      // image slots the latest extraction call filled
+    unsigned epoch = 0;       // extraction calls enqueued so far (device-resident frame caches key on it)
+    std::vector<int> slot_cnt;    // keypoint counts of the slots of call `slot_cnt_epoch` (host copy, filled by the first fetch)
+    unsigned slot_cnt_epoch = ~0u;
+    LaunchPlan plan;          // the planner's choices (orbfe_plan.h) besides cfg; use_octree3 may be cleared by orbfe_create
+    const uint8_t *last_src = nullptr; // images of the latest enqueue when it ran in place (orbfe_fetch_pyramid's level 0), else null
+    bool last_src_owned = false;       // ... and they live in the library's own staging (d_in: the host entry points), which outlives the call
+    bool input_retained = false;       // orbfe_set_input_retained: the caller keeps the images of an enqueue call valid until its next call
+    // stage timing: ring of PROF_RING calls x (ORBFE_NUM_STAGES + 1) events
+    bool profiling = false;
+    int prof_every = 1;      // record events on every prof_every-th enqueue call only (orbfe_set_profiling_interval)
+    unsigned prof_seq = 0;   // enqueue calls seen while profiling
+    bool prof_now = false;   // the current call records
+    int prof_only = -1; // >= 0: record only the two events around that stage
+    std::vector<hipEvent_t> events;
+    int prof_calls = 0;      // calls recorded since the last reset
+    int prof_stages[64];     // number of stages recorded by each call in the ring
+    int prof_groups = 1;
+    // Recorded on the stream of every enqueue call when its work has been queued: what "the latest extraction" means to the
+    // blocking fetches and to the matchers on the resident frame.  The caller's stream handle itself is NOT kept -- a caller
+    // may enqueue, synchronise and destroy its stream before it fetches.
+    hipEvent_t ev_latest = nullptr;
+    bool latest_foreign = false; // the latest call ran on a caller's stream
+    std::recursive_mutex mu;
+    // stream groups (orbfe_set_streams)
+    int groups = 1;
+    hipStream_t gstreams[ORBFE_MAX_GROUPS] = {};
+    hipEvent_t ev_fork = nullptr, ev_join[ORBFE_MAX_GROUPS] = {};
+    int8_t pattern[1024];     // host copy of DeviceBuffers::pattern
+    std::vector<void *> allocs;
+    orbfe_match_state *match = nullptr;
+    orbfe_match_device_state *match_device = nullptr;
+    orbfe_bow_state *bow = nullptr;
+    orbfe_pose_state *pose = nullptr;
+    DevBuf init_scratch, init_sync; // orbfe_enqueue_find_homography_fundamental's per-hypothesis scratch; the synchronous form's arrays
+    hipError_t chain_err = hipSuccess; // a launcher's refusal inside run_chain (enqueue_batch reports it)
+    char err[512];
+};
 
 int orbfe_fail(orbfe_context *ctx, int code, const char *fmt, ...);
 // a HIP call inside a function that returns a status: its failure is the context's error, with the call's text
@@ -34,77 +104,20 @@ int orbfe_fail(orbfe_context *ctx, int code, const char *fmt, ...);
 // Tracking, LocalMapping and LoopClosing threads each construct ORBmatcher objects (src/LocalMapping.cc:215,482,
 // src/LoopClosing.cc:275,623) and the shim gives them all the left extractor's context, whose matcher / BoW / database state
 // (pinned staging, growable device buffers, grid cache, the stream) is single-user.  Recursive: entry points call each other.
-std::recursive_mutex &orbfe_ctx_mutex(orbfe_context *ctx);
 #define ORBFE_ENTRY(ctx)                                  \
     std::unique_lock<std::recursive_mutex> orbfe_entry_lock_; \
-    if (ctx) orbfe_entry_lock_ = std::unique_lock<std::recursive_mutex>(orbfe_ctx_mutex(ctx))
-orbfe_match_state *orbfe_ctx_match_state(orbfe_context *ctx);
-hipStream_t orbfe_ctx_stream(orbfe_context *ctx);
-int orbfe_ctx_device(const orbfe_context *ctx);
-const orbfe_params *orbfe_ctx_params(const orbfe_context *ctx);
-const float *orbfe_ctx_scale_factors(const orbfe_context *ctx);
-// device-resident frames of the latest extraction call (orbfe_match.hip, orbfe_bow.hip)
-struct DeviceConfig;
-struct DeviceBuffers;
-const DeviceConfig *orbfe_ctx_config(const orbfe_context *ctx);
-const DeviceBuffers *orbfe_ctx_buffers(const orbfe_context *ctx);
+    if (ctx) orbfe_entry_lock_ = std::unique_lock<std::recursive_mutex>((ctx)->mu)
+
 int orbfe_ctx_slot_count(orbfe_context *ctx, int slot, int *cnt); // keypoints in image slot `slot` of the latest extraction call
-unsigned orbfe_ctx_epoch(const orbfe_context *ctx);          // counts the extraction calls enqueued on this context
 int orbfe_ctx_wait_foreign_stream(orbfe_context *ctx);      // makes the context's stream wait for the latest extraction call (event, no host wait)
 int orbfe_ctx_order_after_extraction(orbfe_context *ctx, hipStream_t s); // the same for any stream `s` (the asynchronous matchers run on the caller's)
-int orbfe_ctx_last_images(const orbfe_context *ctx);        // image slots the latest extraction call filled
-
-// scratch and caches of the asynchronous, device-resident matchers (orbfe_match_device.hip); owned by orbfe_match_state
-struct orbfe_match_device_state;
+// The prologue of an enqueue entry point, after its argument checks: *s = the caller's stream or else the context's, the context's
+// device selected and, with after_extraction, *s ordered behind the latest extraction call.
+int orbfe_enqueue_on(orbfe_context *ctx, void *stream, bool after_extraction, hipStream_t *s);
+orbfe_match_state *orbfe_ctx_match_state(orbfe_context *ctx);
 orbfe_match_device_state *orbfe_ctx_match_device_state(orbfe_context *ctx);
-void orbfe_match_device_state_destroy(orbfe_match_device_state *s);
-
-struct orbfe_bow_state;
-orbfe_bow_state *orbfe_bow_state_create();
-void orbfe_bow_state_destroy(orbfe_bow_state *s);
 orbfe_bow_state *orbfe_ctx_bow_state(orbfe_context *ctx);
-
-struct orbfe_pose_state;
-orbfe_pose_state *orbfe_pose_state_create();
-void orbfe_pose_state_destroy(orbfe_pose_state *s);
 orbfe_pose_state *orbfe_ctx_pose_state(orbfe_context *ctx);
-const float *orbfe_ctx_inv_sigma2(const orbfe_context *ctx);
-
-// orbfe_enqueue_triangulate_pairs: what the entry point (orbfe_api.hip) hands to the launches (orbfe_triangulate_device.hip); the two
-// keyframe records travel by value, the level tables are the context's
-#include "orbfe_config.h"
-struct orbfe_triangulate_args {
-    orbfe_newpoint_keyframe kf1, kf2;
-    const int32_t *pairs, *npairs;
-    uint8_t *code;
-    float *x3d;
-    int32_t *new_points, *nnew;
-    float *pos;
-    int32_t *rows_used, *status;
-    float mbf, ratio_factor;
-    int max_pairs, n_rows, patch_has_mp, nlevels;
-    float scale[ORBFE_MAX_LEVELS], sigma2[ORBFE_MAX_LEVELS]; // mvScaleFactors, mvLevelSigma2
-};
-int orbfe_triangulate_launch(const orbfe_triangulate_args &a, hipStream_t s); // queues at most three launches; returns hipGetLastError()
-
-// orbfe_enqueue_find_homography_fundamental: what the entry point (orbfe_api.hip) hands to the launches (orbfe_initializer_device.hip).
-// T1, T2inv and T2t are made on the host from the two Normalize results; mats, ok and scores are the context's scratch.
-struct orbfe_initializer_args {
-    const orbfe_keypoint *keys1, *keys2;
-    const int32_t *pairs, *sets;
-    int n1, n2, N, iterations;
-    float norm1[4], norm2[4], T1[9], T2inv[9], T2t[9], inv_sigma2;
-    float *H21, *F21, *score;
-    int32_t *best;
-    uint8_t *inl_h, *inl_f;
-    int32_t *ninliers;
-    float *all_scores;
-    int32_t *status;
-    float *mats;     // [iterations][27]: H21i, H12i, F21i
-    int32_t *ok;     // [iterations]: the set's eight matches are addressable
-    float *scores;   // [2][iterations], as summed (a NaN keeps its bits here)
-};
-int orbfe_initializer_launch(const orbfe_initializer_args &a, hipStream_t s); // a memset and three launches; returns the first HIP error
 
 // No C++ exception may cross the C ABI (a ctypes / cgo / C caller would abort): every extern "C" function that returns a status is a
 // function-try-block closed by this handler.  The per-context lock of ORBFE_ENTRY is a local of the try block, so it is released first.

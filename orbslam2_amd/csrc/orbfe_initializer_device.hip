@@ -1,6 +1,6 @@
 // orbfe_initializer_device.hip -- Initializer::FindHomography and Initializer::FindFundamental (src/Initializer.cc:123-467) for one frame
-// pair, every RANSAC hypothesis of both models, asynchronous on the caller's stream.  The entry points and their checks are in
-// orbfe_api.hip; the arithmetic contract is stated in include/orbfe.h and DESIGN.md section 4l, and this file,
+// pair, every RANSAC hypothesis of both models, asynchronous on the caller's stream.  The entry points and their checks are at the
+// end of this file; the arithmetic contract is stated in include/orbfe.h and DESIGN.md section 4l, and this file,
 // orbslam2_amd/host/Initializer.h and tests/initializer_model.py follow it operation by operation.
 //
 //   initializer_models_kernel   one wave per (set, model).  The 9 x 16 At, the 9 x 9 Vt and W live in LDS (dynamic row indices in private
@@ -18,9 +18,27 @@
 #include "../../include/orbfe.h"
 #include "orbfe_config.h"
 #include "orbfe_host.h"
+#include "../host/Initializer.h"
 
 #include <cfloat>
 
+// what every kernel of this file takes.  T1, T2inv and T2t are made on the host from the two Normalize results; mats, ok and scores
+// are the context's scratch.
+struct orbfe_initializer_args {
+    const orbfe_keypoint *keys1, *keys2;
+    const int32_t *pairs, *sets;
+    int n1, n2, N, iterations;
+    float norm1[4], norm2[4], T1[9], T2inv[9], T2t[9], inv_sigma2;
+    float *H21, *F21, *score;
+    int32_t *best;
+    uint8_t *inl_h, *inl_f;
+    int32_t *ninliers;
+    float *all_scores;
+    int32_t *status;
+    float *mats;     // [iterations][27]: H21i, H12i, F21i
+    int32_t *ok;     // [iterations]: the set's eight matches are addressable
+    float *scores;   // [2][iterations], as summed (a NaN keeps its bits here)
+};
 typedef orbfe_initializer_args Args;
 
 static_assert(sizeof(orbfe_keypoint) == 28, "orbfe_keypoint");
@@ -392,12 +410,106 @@ __global__ __launch_bounds__(256) void initializer_select_kernel(Args a)
     if (tid == 0 && a.ninliers) a.ninliers[model] = s_count;
 }
 
-int orbfe_initializer_launch(const orbfe_initializer_args &a, hipStream_t s)
-{
-    hipError_t e = hipMemsetAsync(a.status, 0, sizeof(int32_t), s);
-    if (e != hipSuccess) return (int)e;
+// Initializer::FindHomography + FindFundamental for one frame pair: a memset and three launches.
+extern "C" int orbfe_enqueue_find_homography_fundamental(orbfe_context *ctx, const orbfe_keypoint *d_keys1_un, int n1, const orbfe_keypoint *d_keys2_un,
+                                                         int n2, const int32_t *d_pairs, int N, const int32_t *d_sets, int iterations, const float *norm1,
+                                                         const float *norm2, float sigma, float *d_H21, float *d_F21, float *d_score, int32_t *d_best,
+                                                         uint8_t *d_inliers_h, uint8_t *d_inliers_f, int32_t *d_ninliers, float *d_all_scores,
+                                                         int32_t *d_status, void *stream)
+try {
+    ORBFE_ENTRY(ctx);
+    // what the arguments alone show is refused first, so that the refusals can be told apart without a device
+    if (!d_keys1_un || !d_keys2_un || !d_pairs || !d_sets || !norm1 || !norm2) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "find_homography_fundamental: null input");
+    if (!d_H21 || !d_F21 || !d_score || !d_best || !d_status) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "find_homography_fundamental: null output");
+    if (N < 8) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "find_homography_fundamental: N = %d < 8", N);
+    if (iterations < 1) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "find_homography_fundamental: iterations = %d < 1", iterations);
+    if (n1 < 0 || n2 < 0) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "find_homography_fundamental: negative count");
+    if (N > ORBFE_INITIALIZER_MAX_MATCHES || iterations > ORBFE_INITIALIZER_MAX_ITERATIONS || n1 > ORBFE_INITIALIZER_MAX_KEYS || n2 > ORBFE_INITIALIZER_MAX_KEYS)
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "find_homography_fundamental: a count above its limit (N %d, iterations %d, n1 %d, n2 %d)", N, iterations, n1, n2);
+    if (!(sigma > 0)) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "find_homography_fundamental: sigma must be > 0");
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    hipStream_t s;
+    if (const int rc = orbfe_enqueue_on(ctx, stream, false, &s)) return rc;
+    const size_t it = (size_t)iterations;
+    if (ctx->init_scratch.ensure(it * (27 + 1 + 2) * 4) != 0) return orbfe_fail(ctx, ORBFE_ERR_HIP, "find_homography_fundamental: scratch allocation failed");
+    Args a;
+    a.keys1 = d_keys1_un; a.keys2 = d_keys2_un; a.pairs = d_pairs; a.sets = d_sets;
+    a.n1 = n1; a.n2 = n2; a.N = N; a.iterations = iterations;
+    float T2[9];
+    for (int k = 0; k < 4; k++) { a.norm1[k] = norm1[k]; a.norm2[k] = norm2[k]; }
+    ORB_SLAM2::InitializerT(a.norm1, a.T1);
+    ORB_SLAM2::InitializerT(a.norm2, T2);
+    ORB_SLAM2::InitializerInv3(T2, a.T2inv);
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) a.T2t[3 * r + c] = T2[3 * c + r];
+    a.inv_sigma2 = (float)(1.0 / (double)(sigma * sigma));
+    a.H21 = d_H21; a.F21 = d_F21; a.score = d_score; a.best = d_best; a.inl_h = d_inliers_h; a.inl_f = d_inliers_f; a.ninliers = d_ninliers;
+    a.all_scores = d_all_scores; a.status = d_status;
+    a.mats = (float *)ctx->init_scratch.p; a.ok = (int32_t *)(a.mats + it * 27); a.scores = (float *)(a.ok + it);
+    ORBFE_HIP_TRY(ctx, hipMemsetAsync(a.status, 0, sizeof(int32_t), s));
     hipLaunchKernelGGL(initializer_models_kernel, dim3(a.iterations, 2), dim3(64), 0, s, a);
     hipLaunchKernelGGL(initializer_score_kernel, dim3((a.iterations + 63) / 64, 2), dim3(64), 0, s, a);
     hipLaunchKernelGGL(initializer_select_kernel, dim3(2), dim3(256), 0, s, a);
-    return (int)hipGetLastError();
-}
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
+    return ORBFE_OK;
+} ORBFE_CATCH(ctx)
+
+extern "C" int orbfe_find_homography_fundamental(orbfe_context *ctx, const orbfe_keypoint *keys1_un, int n1, const orbfe_keypoint *keys2_un, int n2,
+                                                 const int32_t *matches12, const int32_t *sets, int iterations, float sigma, float *H21, float *F21,
+                                                 float *score, int32_t *best, uint8_t *inliers_h, uint8_t *inliers_f, int32_t *ninliers, float *all_scores,
+                                                 int32_t *n_matches)
+try {
+    ORBFE_ENTRY(ctx);
+    if (!keys1_un || !keys2_un || !matches12 || !sets) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "find_homography_fundamental: null input");
+    if (!H21 || !F21 || !score || !best || !n_matches) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "find_homography_fundamental: null output");
+    if (n1 < 0 || n2 < 0 || n1 > ORBFE_INITIALIZER_MAX_KEYS || n2 > ORBFE_INITIALIZER_MAX_KEYS || iterations < 1 || iterations > ORBFE_INITIALIZER_MAX_ITERATIONS)
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "find_homography_fundamental: a count outside its range (iterations %d, n1 %d, n2 %d)", iterations, n1, n2);
+    std::vector<int32_t> pairs; // mvMatches12 (:50-62)
+    pairs.reserve(2 * (size_t)n1);
+    for (int i = 0; i < n1; i++)
+        if (matches12[i] >= 0) { pairs.push_back(i); pairs.push_back(matches12[i]); }
+    const int N = (int)(pairs.size() / 2);
+    *n_matches = N;
+    if (N < 8) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "find_homography_fundamental: N = %d < 8", N);
+    if (N > ORBFE_INITIALIZER_MAX_MATCHES) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "find_homography_fundamental: N = %d above its limit", N);
+    if (!(sigma > 0)) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "find_homography_fundamental: sigma must be > 0");
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    float norm1[4], norm2[4];
+    ORB_SLAM2::NormalizeKeys(keys1_un, n1, norm1);
+    ORB_SLAM2::NormalizeKeys(keys2_un, n2, norm2);
+    hipStream_t s;
+    if (const int rc = orbfe_enqueue_on(ctx, nullptr, false, &s)) return rc;
+    // one device block: inputs, then outputs
+    const size_t it = (size_t)iterations, kb1 = sizeof(orbfe_keypoint) * (size_t)n1, kb2 = sizeof(orbfe_keypoint) * (size_t)n2;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 15) & ~(size_t)15; return o; };
+    const size_t o_k1 = take(kb1), o_k2 = take(kb2), o_pairs = take(8 * (size_t)N), o_sets = take(32 * it), o_small = take(32 * 4), o_ih = take(N), o_if = take(N),
+                 o_all = take(8 * it);
+    if (ctx->init_sync.ensure(off) != 0) return orbfe_fail(ctx, ORBFE_ERR_HIP, "find_homography_fundamental: device allocation failed");
+    uint8_t *d = (uint8_t *)ctx->init_sync.p;
+    if (kb1) ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d + o_k1, keys1_un, kb1, hipMemcpyHostToDevice, s));
+    if (kb2) ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d + o_k2, keys2_un, kb2, hipMemcpyHostToDevice, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d + o_pairs, pairs.data(), 8 * (size_t)N, hipMemcpyHostToDevice, s));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d + o_sets, sets, 32 * it, hipMemcpyHostToDevice, s));
+    // small outputs: H21 [0, 9), F21 [9, 18), score [18, 20), best [20, 22), ninliers [22, 24), status [24]; they start as the caller's H21 / F21
+    float small[32] = {};
+    memcpy(small, H21, 36); memcpy(small + 9, F21, 36);
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d + o_small, small, sizeof(small), hipMemcpyHostToDevice, s));
+    float *ds = (float *)(d + o_small);
+    const int rc = orbfe_enqueue_find_homography_fundamental(ctx, (const orbfe_keypoint *)(d + o_k1), n1, (const orbfe_keypoint *)(d + o_k2), n2,
+                                                             (const int32_t *)(d + o_pairs), N, (const int32_t *)(d + o_sets), iterations, norm1, norm2, sigma, ds,
+                                                             ds + 9, ds + 18, (int32_t *)(ds + 20), d + o_ih, d + o_if, (int32_t *)(ds + 22), (float *)(d + o_all),
+                                                             (int32_t *)(ds + 24), s);
+    if (rc != ORBFE_OK) return rc;
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(small, d + o_small, sizeof(small), hipMemcpyDeviceToHost, s));
+    if (inliers_h) ORBFE_HIP_TRY(ctx, hipMemcpyAsync(inliers_h, d + o_ih, N, hipMemcpyDeviceToHost, s));
+    if (inliers_f) ORBFE_HIP_TRY(ctx, hipMemcpyAsync(inliers_f, d + o_if, N, hipMemcpyDeviceToHost, s));
+    if (all_scores) ORBFE_HIP_TRY(ctx, hipMemcpyAsync(all_scores, d + o_all, 8 * it, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
+    memcpy(H21, small, 36); memcpy(F21, small + 9, 36); memcpy(score, small + 18, 8); memcpy(best, small + 20, 8);
+    if (ninliers) memcpy(ninliers, small + 22, 8);
+    int32_t status;
+    memcpy(&status, small + 24, 4);
+    if (status != 0) return orbfe_fail(ctx, status, "find_homography_fundamental: the device reported a faulty pair or set index");
+    return ORBFE_OK;
+} ORBFE_CATCH(ctx)

@@ -234,16 +234,16 @@ try {
     }
     if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
     MapPointArgs a;
-    a.nlevels = orbfe_ctx_params(ctx)->nlevels;
+    a.nlevels = ctx->params.nlevels;
     if (a.nlevels < 1 || a.nlevels > ORBFE_MAX_LEVELS) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "nlevels = %d", a.nlevels);
-    const float *sf = orbfe_ctx_scale_factors(ctx);
+    const float *sf = ctx->plan.scale;
     for (int l = 0; l < ORBFE_MAX_LEVELS; l++) a.sf[l] = l < a.nlevels ? sf[l] : 1.f;
     a.kfs = d_kfs; a.row = d_row; a.obs_off = d_obs_off; a.obs_kf = d_obs_kf; a.obs_idx = d_obs_idx; a.ref = d_ref;
     a.pos = d_pos; a.normal = d_normal; a.max_distance = d_max_distance; a.min_distance = d_min_distance; a.pt_desc = d_pt_desc;
     a.best = d_best; a.status = d_status;
     a.n_kfs = n_kfs; a.n_upd = n_upd; a.n_rows = n_rows; a.n_obs = n_obs; a.what = what;
-    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    hipStream_t s;
+    if (const int rc = orbfe_enqueue_on(ctx, stream, false, &s)) return rc;
     hipLaunchKernelGGL(map_point_reset_kernel, dim3(1), dim3(64), 0, s, d_status);
     if (n_upd > 0) hipLaunchKernelGGL(map_point_kernel, dim3((n_upd + 3) / 4), dim3(256), 0, s, a);
     ORBFE_HIP_TRY(ctx, hipGetLastError());

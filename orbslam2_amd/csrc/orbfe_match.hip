@@ -128,8 +128,7 @@ struct orbfe_match_state {
     unsigned grid_epoch = 0;
     int grid_slot = -1, grid_n = -1;
     float grid_bounds[4] = {0, 0, 0, 0};
-    orbfe_match_device_state *dev = nullptr; // the asynchronous matchers keep their own scratch and grid (orbfe_match_device.hip)
-    ~orbfe_match_state() { if (h_in) (void)hipHostFree(h_in); if (h_out) (void)hipHostFree(h_out); if (dev) orbfe_match_device_state_destroy(dev); }
+    ~orbfe_match_state() { if (h_in) (void)hipHostFree(h_in); if (h_out) (void)hipHostFree(h_out); }
 };
 
 static orbfe_match_state *match_state(orbfe_context *ctx) { return orbfe_ctx_match_state(ctx); }
@@ -162,20 +161,20 @@ static int run_window_queries(orbfe_context *ctx, const orbfe_frame_view *fv, co
                               const std::vector<uint8_t> &qdesc, const TopkRequest *topk = nullptr)
 {
     orbfe_match_state *st = match_state(ctx);
-    hipStream_t s = orbfe_ctx_stream(ctx);
+    hipStream_t s = ctx->stream;
     const int n = fv->n, nq = (int)queries.size();
     st->h_off.assign(nq, 0); st->h_cnt.assign(nq, 0); st->h_list.clear();
     st->h_topk.assign((size_t)nq * MATCH_TOPK, ~0ull); st->h_nstatic.assign(nq, 0);
     st->list_on_host = true; st->list_total = 0;
     if (n <= 0 || nq == 0) return ORBFE_OK;
     if (n > 65535) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "frames with more than 65535 keypoints are not supported by the matchers");
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    ORBFE_HIP_TRY(ctx, hipSetDevice(ctx->params.device));
     const bool resident = fv->device_slot_plus1 > 0;
     const int slot = fv->device_slot_plus1 - 1;
-    const DeviceConfig *cfg = orbfe_ctx_config(ctx);
-    const DeviceBuffers *buf = orbfe_ctx_buffers(ctx);
+    const DeviceConfig *cfg = &ctx->cfg;
+    const DeviceBuffers *buf = &ctx->buf;
     if (resident) {
-        if (slot >= orbfe_ctx_params(ctx)->max_images) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d out of range", slot);
+        if (slot >= ctx->params.max_images) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d out of range", slot);
         int rc = orbfe_ctx_wait_foreign_stream(ctx); // the extraction may have been enqueued on a caller stream
         if (rc != ORBFE_OK) return rc;
         // a stale or mismatched view would silently match against another frame's leftovers: the view's count must be the slot's
@@ -210,7 +209,7 @@ static int run_window_queries(orbfe_context *ctx, const orbfe_frame_view *fv, co
         const size_t so = (size_t)slot * cfg->sel_total;
         const KeyPointPOD *raw = (const KeyPointPOD *)buf->kps + so;
         const bool distorted = cfg->n_dist > 0 && cfg->dist[0] != 0.0f;
-        const unsigned epoch = orbfe_ctx_epoch(ctx);
+        const unsigned epoch = ctx->epoch;
         build_grid = !(st->grid_epoch == epoch && st->grid_slot == slot && st->grid_n == n && st->grid_bounds[0] == fv->min_x &&
                        st->grid_bounds[1] == fv->max_x && st->grid_bounds[2] == fv->min_y && st->grid_bounds[3] == fv->max_y);
         if (distorted) { // mvKeysUn: undistorted on the device once per frame (Frame::UndistortKeyPoints)
@@ -507,7 +506,7 @@ try {
     if (!cur_match || !nmatches || n_pts < 0 || (n_pts > 0 && (!pts || !pt_desc || !pt_obs))) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
     std::vector<MatchQuery> q;
     std::vector<uint8_t> qd;
-    if (orbfe_resolve::build_queries_points(orbfe_ctx_scale_factors(ctx), orbfe_ctx_params(ctx)->nlevels, n_pts, pts, pt_desc, th, q, qd) != 0)
+    if (orbfe_resolve::build_queries_points(ctx->plan.scale, ctx->params.nlevels, n_pts, pts, pt_desc, th, q, qd) != 0)
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "predicted level out of range");
     TopkReplay r;
     rc = r.begin(ctx, cur, cur_has_obs, true, q, qd);
@@ -732,5 +731,4 @@ try {
 } ORBFE_CATCH(ctx)
 
 orbfe_match_state *orbfe_match_state_create() { return new (std::nothrow) orbfe_match_state(); }
-orbfe_match_device_state **orbfe_match_device_slot(orbfe_match_state *s) { return &s->dev; }
 void orbfe_match_state_destroy(orbfe_match_state *s) { delete s; }

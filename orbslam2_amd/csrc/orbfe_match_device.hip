@@ -592,16 +592,12 @@ struct orbfe_match_device_state {
     const void *grid_keys = nullptr;
     float grid_bounds[4] = {0, 0, 0, 0};
 };
-orbfe_match_device_state **orbfe_match_device_slot(orbfe_match_state *s); // orbfe_match.hip
 void orbfe_match_device_state_destroy(orbfe_match_device_state *s) { delete s; }
 void orbfe_launch_grid_build(const GridFrame &f, hipStream_t s) { hipLaunchKernelGGL(grid_build_kernel, dim3(1), dim3(1024), 0, s, f); }
 orbfe_match_device_state *orbfe_ctx_match_device_state(orbfe_context *ctx)
 {
-    orbfe_match_state *ms = orbfe_ctx_match_state(ctx);
-    if (!ms) return nullptr;
-    orbfe_match_device_state **slot = orbfe_match_device_slot(ms);
-    if (!*slot) *slot = new (std::nothrow) orbfe_match_device_state();
-    return *slot;
+    if (!ctx->match_device) ctx->match_device = new (std::nothrow) orbfe_match_device_state();
+    return ctx->match_device;
 }
 
 // the two one-way results of orbfe_enqueue_search_by_sim3 (orbfe_sim3_device.hip): n int32_t of the context's grow-only scratch
@@ -616,24 +612,23 @@ int32_t *orbfe_ctx_sim3_scratch(orbfe_context *ctx, size_t n)
 // a Frame's view: its bounds are the floats they are given as
 static View frame_view(orbfe_context *ctx, const float *bounds) { return orbfe_view(ctx, bounds[0], bounds[1], bounds[2], bounds[3], 0); }
 
-// Common entry work of the calls on a resident slot: argument checks, stream order, mvKeysUn.  No host wait.
-static int resident_frame(orbfe_context *ctx, int slot, hipStream_t s, orbfe_match_device_state *&st, const KeyPointPOD *&keys)
+// Common entry work of the calls on a resident slot: argument checks, the stream `s` and its order, mvKeysUn.  No host wait.
+static int resident_frame(orbfe_context *ctx, int slot, void *stream, hipStream_t &s, orbfe_match_device_state *&st, const KeyPointPOD *&keys)
 {
-    const DeviceConfig *cfg = orbfe_ctx_config(ctx);
-    const DeviceBuffers *buf = orbfe_ctx_buffers(ctx);
-    if (slot < 0 || slot >= orbfe_ctx_last_images(ctx))
-        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d: the latest extraction call filled %d image slots", slot, orbfe_ctx_last_images(ctx));
+    const DeviceConfig *cfg = &ctx->cfg;
+    const DeviceBuffers *buf = &ctx->buf;
+    if (slot < 0 || slot >= ctx->last_images)
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d: the latest extraction call filled %d image slots", slot, ctx->last_images);
     if (cfg->sel_total > 65535) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "frames with more than 65535 keypoints are not supported by the matchers");
     st = orbfe_ctx_match_device_state(ctx);
     if (!st) return orbfe_fail(ctx, ORBFE_ERR_HIP, "out of host memory");
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
-    const unsigned epoch = orbfe_ctx_epoch(ctx);
-    const int rc = orbfe_ctx_order_after_extraction(ctx, s); // an event wait on the stream, no host wait
+    const int rc = orbfe_enqueue_on(ctx, stream, true, &s); // an event wait on the stream, no host wait
     if (rc != ORBFE_OK) return rc;
+    const unsigned epoch = ctx->epoch;
     const KeyPointPOD *raw = (const KeyPointPOD *)buf->kps + (size_t)slot * cfg->sel_total;
     keys = raw;
     if (cfg->n_dist > 0 && cfg->dist[0] != 0.0f) { // mvKeysUn: undistorted on the device once per frame (Frame::UndistortKeyPoints)
-        const int max_images = orbfe_ctx_params(ctx)->max_images;
+        const int max_images = ctx->params.max_images;
         if (st->keys_un.ensure(sizeof(KeyPointPOD) * (size_t)cfg->sel_total * max_images)) return orbfe_fail(ctx, ORBFE_ERR_HIP, "matcher scratch allocation failed");
         bool same = st->un_ndist == cfg->n_dist && (int)st->un_epoch.size() >= max_images;
         for (int k = 0; k < 5; k++) same = same && st->un_dist[k] == cfg->dist[k];
@@ -655,13 +650,13 @@ static int resident_frame(orbfe_context *ctx, int slot, hipStream_t s, orbfe_mat
 }
 
 // the slot as the kernels read it, its grid built if this is the first call on this frame with these bounds
-static int resident_grid(orbfe_context *ctx, int slot, const float *bounds, bool stereo, hipStream_t s, orbfe_match_device_state *&st, GridFrame &f)
+static int resident_grid(orbfe_context *ctx, int slot, const float *bounds, bool stereo, void *stream, hipStream_t &s, orbfe_match_device_state *&st, GridFrame &f)
 {
-    const DeviceConfig *cfg = orbfe_ctx_config(ctx);
-    const DeviceBuffers *buf = orbfe_ctx_buffers(ctx);
+    const DeviceConfig *cfg = &ctx->cfg;
+    const DeviceBuffers *buf = &ctx->buf;
     if (!bounds || !(bounds[1] > bounds[0]) || !(bounds[3] > bounds[2])) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "bad image bounds");
     const KeyPointPOD *keys = nullptr;
-    int rc = resident_frame(ctx, slot, s, st, keys);
+    int rc = resident_frame(ctx, slot, stream, s, st, keys);
     if (rc != ORBFE_OK) return rc;
     if (st->cells.ensure(sizeof(int) * (size_t)(GRID_CELLS + 1 + cfg->sel_total))) return orbfe_fail(ctx, ORBFE_ERR_HIP, "matcher scratch allocation failed");
     const size_t so = (size_t)slot * cfg->sel_total;
@@ -672,7 +667,7 @@ static int resident_grid(orbfe_context *ctx, int slot, const float *bounds, bool
     f.cap = cfg->sel_total;
     grid_frame_geometry(f, bounds[0], bounds[1], bounds[2], bounds[3], false); // a Frame: windows use the float bounds
     f.cell_off = (int *)st->cells.p; f.cell_idx = f.cell_off + GRID_CELLS + 1;
-    const unsigned epoch = orbfe_ctx_epoch(ctx);
+    const unsigned epoch = ctx->epoch;
     if (!(st->grid_epoch == epoch && st->grid_slot == slot && st->grid_keys == (const void *)f.keys && st->grid_bounds[0] == bounds[0] && st->grid_bounds[1] == bounds[1] &&
           st->grid_bounds[2] == bounds[2] && st->grid_bounds[3] == bounds[3])) {
         orbfe_launch_grid_build(f, s);
@@ -719,11 +714,12 @@ static int enqueue_window_resolve(orbfe_context *ctx, orbfe_match_device_state *
 // The keyframe matcher for n_cands candidates: four launches whatever n_cands is
 static int enqueue_kf(orbfe_context *ctx, int slot, const float *bounds, const orbfe_reloc_candidate *d_cands, const orbfe_reloc_candidate &one, int n_cands,
                       int max_n, int check_ori, int exclude_held, int32_t *d_cur_match, int32_t *d_nmatches, int32_t *d_status, uint8_t *d_has_point,
-                      float *d_Xw, hipStream_t s)
+                      float *d_Xw, void *stream)
 {
     orbfe_match_device_state *st = nullptr;
     GridFrame f;
-    int rc = resident_grid(ctx, slot, bounds, false, s, st, f); // a plain GetFeaturesInArea: no mvuRight
+    hipStream_t s;
+    int rc = resident_grid(ctx, slot, bounds, false, stream, s, st, f); // a plain GetFeaturesInArea: no mvuRight
     if (rc != ORBFE_OK) return rc;
     const size_t rows = (size_t)n_cands * (size_t)max_n;
     rc = ensure_query_scratch(ctx, st, (int)rows);
@@ -758,10 +754,10 @@ try {
     if (!bounds || !d_Tcw_cur || !d_Tcw_last || !d_cur_match || !d_nmatches || !d_status || n_last < 0 ||
         (n_last > 0 && (!d_last_pos || !d_last_desc || !d_last_valid || !d_last_obs || !d_last_octave || !d_last_angle)))
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
-    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
+    hipStream_t s;
     orbfe_match_device_state *st = nullptr;
     GridFrame f;
-    int rc = resident_grid(ctx, slot, bounds, !mono, s, st, f);
+    int rc = resident_grid(ctx, slot, bounds, !mono, stream, s, st, f);
     if (rc != ORBFE_OK) return rc;
     rc = ensure_query_scratch(ctx, st, n_last);
     if (rc != ORBFE_OK) return rc;
@@ -779,8 +775,8 @@ try {
     if (!d_Tcw || !bounds || n < 0 || (n > 0 && (!d_pos || !d_normal || !d_max_distance || !d_min_distance || !d_out)))
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
     if (n == 0) return ORBFE_OK;
-    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    hipStream_t s;
+    if (const int rc = orbfe_enqueue_on(ctx, stream, false, &s)) return rc;
     hipLaunchKernelGGL(frustum_kernel, dim3((n + 255) / 256), dim3(256), 0, s, frame_view(ctx, bounds), d_Tcw, n, d_pos, d_normal, d_max_distance,
                        d_min_distance, viewing_cos_limit, d_out);
     ORBFE_HIP_TRY(ctx, hipGetLastError());
@@ -796,10 +792,10 @@ try {
     ORBFE_ENTRY(ctx);
     if (!bounds || !d_cur_match || !d_nmatches || !d_status || n_pts < 0 || (n_pts > 0 && (!d_pts || !d_pt_desc || !d_pt_obs)))
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
-    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
+    hipStream_t s;
     orbfe_match_device_state *st = nullptr;
     GridFrame f;
-    int rc = resident_grid(ctx, slot, bounds, true, s, st, f);
+    int rc = resident_grid(ctx, slot, bounds, true, stream, s, st, f);
     if (rc != ORBFE_OK) return rc;
     rc = ensure_query_scratch(ctx, st, n_pts);
     if (rc != ORBFE_OK) return rc;
@@ -824,7 +820,7 @@ try {
     const orbfe_reloc_candidate one = {d_Tcw, d_kf_pos, d_kf_desc, d_kf_valid, d_kf_angle, d_kf_max_distance, d_kf_min_distance, d_cur_point, d_outlier,
                                        n_kf, th, orb_dist, 0};
     return enqueue_kf(ctx, slot, bounds, nullptr, one, 1, n_kf, check_ori, exclude_held, d_cur_match, d_nmatches, d_status, d_has_point, d_Xw,
-                      stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx));
+                      stream);
 } ORBFE_CATCH(ctx)
 
 extern "C" int orbfe_enqueue_search_by_projection_kf_batch(orbfe_context *ctx, int slot, const float *bounds, const orbfe_reloc_candidate *d_cands, int n_cands,
@@ -835,13 +831,13 @@ try {
     ORBFE_ENTRY(ctx);
     if (!bounds || n_cands < 0 || n_cands > 65535 || max_n_kf < 0 || (n_cands > 0 && (!d_cands || !d_cur_match || !d_nmatches || !d_status)))
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument or count out of range");
-    if (slot < 0 || slot >= orbfe_ctx_last_images(ctx))
-        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d: the latest extraction call filled %d image slots", slot, orbfe_ctx_last_images(ctx));
+    if (slot < 0 || slot >= ctx->last_images)
+        return orbfe_fail(ctx, ORBFE_ERR_INVALID, "device slot %d: the latest extraction call filled %d image slots", slot, ctx->last_images);
     if ((long long)n_cands * max_n_kf > (1ll << 20))
         return orbfe_fail(ctx, ORBFE_ERR_CAPACITY, "%d candidates x %d points: the matcher's scratch rows hold 2^20", n_cands, max_n_kf);
     if (n_cands == 0) return ORBFE_OK;
     return enqueue_kf(ctx, slot, bounds, d_cands, orbfe_reloc_candidate(), n_cands, max_n_kf, check_ori, exclude_held, d_cur_match, d_nmatches, d_status,
-                      d_has_point, d_Xw, stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx));
+                      d_has_point, d_Xw, stream);
 } ORBFE_CATCH(ctx)
 
 // ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th), src/ORBmatcher.cc:285-398, on a keyframe record: two launches
@@ -855,7 +851,7 @@ try {
     ORBFE_ENTRY(ctx);
     if (!kf || !Scw || !d_pt_match || !d_kf_match || !d_nmatches || !d_status) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
     Sim3Source src;
-    src.pts = {{d_pt_index, n_rows, d_pos, d_normal, d_max_distance, d_min_distance, d_pt_desc, d_pt_valid}, orbfe_ctx_params(ctx)->nlevels, d_pt_match};
+    src.pts = {{d_pt_index, n_rows, d_pos, d_normal, d_max_distance, d_min_distance, d_pt_desc, d_pt_valid}, ctx->params.nlevels, d_pt_match};
     GridFrame f;
     int rc = orbfe_point_table_frame(ctx, kf, n_pts, 1 << 20, src.pts, f); // the scratch rows hold 2^20 queries
     if (rc != ORBFE_OK) return rc;
@@ -863,14 +859,15 @@ try {
     f.u_right = nullptr; // this matcher has no mvuRight gate: kf->u_right is never read
     orbfe_match_device_state *st = orbfe_ctx_match_device_state(ctx);
     if (!st) return orbfe_fail(ctx, ORBFE_ERR_HIP, "out of host memory");
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    hipStream_t s;
+    rc = orbfe_enqueue_on(ctx, stream, false, &s);
+    if (rc != ORBFE_OK) return rc;
     rc = ensure_query_scratch(ctx, st, n_pts);
     if (rc != ORBFE_OK) return rc;
     src.kf_n = kf->n;
     orbfe_resolve::sim3_to_rt(Scw, src.T);
     orbfe_resolve::camera_center(src.T, src.ow);
     src.th = th;
-    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
     // one wave per query, and a thread per keypoint for the reset of d_kf_match; neither: the resolve kernel alone writes count and status
     const int blocks = std::max((n_pts + 3) / 4, (f.cap + 255) / 256);
     const WindowRow w = {(MatchQuery *)st->q.p, nullptr, n_pts, d_kf_matched, (unsigned long long *)st->topk.p, (int *)st->n_static.p, d_kf_match};
@@ -892,10 +889,10 @@ try {
     if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
     ORBFE_ENTRY(ctx);
     if (!d_keys_un) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
-    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
+    hipStream_t s;
     orbfe_match_device_state *st = nullptr;
     const KeyPointPOD *keys = nullptr;
-    const int rc = resident_frame(ctx, slot, s, st, keys);
+    const int rc = resident_frame(ctx, slot, stream, s, st, keys);
     if (rc != ORBFE_OK) return rc;
     ORBFE_HIP_TRY(ctx, hipGetLastError());
     *d_keys_un = (const orbfe_keypoint *)keys;

@@ -45,7 +45,7 @@ static inline void grid_frame_geometry(GridFrame &f, float min_x, float max_x, f
 // The context's view (orbfe_match_resolve.h) with these bounds, or with those of a frame view / keyframe record
 static inline orbfe_resolve::View orbfe_view(orbfe_context *ctx, float min_x, float max_x, float min_y, float max_y, int keyframe)
 {
-    return orbfe_resolve::view_of(orbfe_ctx_params(ctx), orbfe_ctx_scale_factors(ctx), min_x, max_x, min_y, max_y, keyframe);
+    return orbfe_resolve::view_of(&ctx->params, ctx->plan.scale, min_x, max_x, min_y, max_y, keyframe);
 }
 template <class Record> // orbfe_frame_view, orbfe_grid_keyframe
 static inline orbfe_resolve::View orbfe_view(orbfe_context *ctx, const Record *r)

@@ -238,19 +238,19 @@ try {
     if (!d_offsets || !d_keys_un || !d_u_right || !d_has_point || !d_Xw || !d_Tcw || !d_outlier || !d_n_inliers)
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null device pointer");
     orbfe_pose_state *st = orbfe_ctx_pose_state(ctx);
-    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    const orbfe_params *p = orbfe_ctx_params(ctx);
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    const orbfe_params *p = &ctx->params;
+    hipStream_t s;
+    if (const int rc = orbfe_enqueue_on(ctx, stream, false, &s)) return rc;
     if (!st->sig.p) { // mvInvLevelSigma2 of the context's pyramid
         if (st->sig.ensure(sizeof(float) * ORBFE_MAX_LEVELS)) return orbfe_fail(ctx, ORBFE_ERR_HIP, "pose scratch allocation failed");
-        ORBFE_HIP_TRY(ctx, hipMemcpy(st->sig.p, orbfe_ctx_inv_sigma2(ctx), sizeof(float) * p->nlevels, hipMemcpyHostToDevice));
+        ORBFE_HIP_TRY(ctx, hipMemcpy(st->sig.p, ctx->plan.inv_sigma2, sizeof(float) * p->nlevels, hipMemcpyHostToDevice));
     }
     constexpr int TH = PO_THREADS;
     if (max_keypoints <= PO_LDS_CAP_MAX) {
         const int cap = (std::max(max_keypoints, 1) + 3) & ~3;
         const size_t lds = pose_lds_bytes<TH>(cap);
         static bool attr_set[64] = {}; // the attribute is per device
-        const int dev = orbfe_ctx_device(ctx);
+        const int dev = ctx->params.device;
         if (dev >= 0 && dev < 64 && !attr_set[dev]) {
             ORBFE_HIP_TRY(ctx, hipFuncSetAttribute((const void *)pose_opt_kernel<TH, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pose_lds_bytes<TH>(PO_LDS_CAP_MAX)));
             attr_set[dev] = true;
@@ -283,7 +283,7 @@ try {
     if (n_problems == 0) return ORBFE_OK;
     if (!offsets || !Tcw || !outlier || !n_inliers) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null argument");
     const int total = offsets[n_problems];
-    const orbfe_params *p = orbfe_ctx_params(ctx);
+    const orbfe_params *p = &ctx->params;
     int max_n = 0;
     for (int k = 0; k < n_problems; k++) {
         if (offsets[k + 1] < offsets[k] || offsets[0] != 0) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "offsets must start at 0 and not decrease");
@@ -294,8 +294,8 @@ try {
         if (has_point[i] && (keys_un[i].octave < 0 || keys_un[i].octave >= p->nlevels))
             return orbfe_fail(ctx, ORBFE_ERR_INVALID, "keypoint %d has octave %d outside the context's %d levels", i, keys_un[i].octave, p->nlevels);
     orbfe_pose_state *st = orbfe_ctx_pose_state(ctx);
-    hipStream_t s = orbfe_ctx_stream(ctx);
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    hipStream_t s;
+    if (const int rc = orbfe_enqueue_on(ctx, nullptr, false, &s)) return rc;
     const size_t tn = (size_t)(total > 0 ? total : 1);
     // block layout: results first ([Tcw | n_inliers | outlier], copied back in one piece), then the inputs
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };

@@ -118,10 +118,11 @@ try {
         (!d_pos1 || !d_max_distance1 || !d_min_distance1 || !d_pt_desc1 || !d_valid1 || !d_pos2 || !d_max_distance2 || !d_min_distance2 || !d_pt_desc2 ||
          !d_valid2 || !kf1->keys_un || !kf1->desc || !kf1->cell_off || !kf1->cell_idx || !kf2->keys_un || !kf2->desc || !kf2->cell_off || !kf2->cell_idx))
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null array among the map points or in a keyframe record");
-    const orbfe_params *P = orbfe_ctx_params(ctx);
+    const orbfe_params *P = &ctx->params;
     if (P->nlevels < 1 || P->nlevels > ORBFE_MAX_LEVELS) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "nlevels = %d", P->nlevels);
-    hipStream_t s = stream ? (hipStream_t)stream : orbfe_ctx_stream(ctx);
-    ORBFE_HIP_TRY(ctx, hipSetDevice(orbfe_ctx_device(ctx)));
+    hipStream_t s;
+    rc = orbfe_enqueue_on(ctx, stream, false, &s);
+    if (rc != ORBFE_OK) return rc;
     int32_t *m = orbfe_ctx_sim3_scratch(ctx, (size_t)n1 + (size_t)n2);
     if (!m) return orbfe_fail(ctx, ORBFE_ERR_HIP, "matcher scratch allocation failed");
     hipLaunchKernelGGL(sim3_reset_kernel, dim3(1), dim3(64), 0, s, d_n_found, d_status);

@@ -1,5 +1,6 @@
 // orbfe_stereo.hip -- Frame::ComputeStereoMatches (src/Frame.cc:464-642), ComputeStereoFromRGBD (:645-666), batched DescriptorDistance.
 #include "orbfe_common.hpp"
+#include "orbfe_host.h"
 
 
 // ---------------------------------------------------------------------------
@@ -549,8 +550,19 @@ void orbfe_launch_pack_results(const DeviceConfig &cfg, const DeviceBuffers &buf
     hipLaunchKernelGGL(pack_results_kernel, grid, dim3(256), 0, s, cfg, buf, d_out, lay, img_step, stereo ? 1 : 0);
 }
 
-void orbfe_launch_hamming_matrix(const uint8_t *da, int na, const uint8_t *db, int nb, int *dist, hipStream_t s)
-{
-    dim3 grid((nb + 63) / 64, (na + 63) / 64);
-    hipLaunchKernelGGL(hamming_matrix_kernel, grid, dim3(256), 0, s, da, na, db, nb, dist);
-}
+extern "C" int orbfe_hamming_matrix(orbfe_context *ctx, const uint8_t *desc_a, int na, const uint8_t *desc_b, int nb, int32_t *dist)
+try {
+    ORBFE_ENTRY(ctx);
+    if (!ctx || !desc_a || !desc_b || !dist || na < 0 || nb < 0) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "bad argument");
+    if (na == 0 || nb == 0) return ORBFE_OK;
+    const size_t need = (size_t)32 * na + (size_t)32 * nb + sizeof(int) * (size_t)na * nb;
+    if (ctx->d_ham.ensure(need) != 0) return orbfe_fail(ctx, ORBFE_ERR_HIP, "hipMalloc(%zu) failed", need); // only this entry point's own scratch
+    uint8_t *da = (uint8_t *)ctx->d_ham.p, *db = da + (size_t)32 * na;
+    int *dd = (int *)(db + (size_t)32 * nb);
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(da, desc_a, (size_t)32 * na, hipMemcpyHostToDevice, ctx->stream));
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(db, desc_b, (size_t)32 * nb, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(hamming_matrix_kernel, dim3((nb + 63) / 64, (na + 63) / 64), dim3(256), 0, ctx->stream, da, na, db, nb, dd);
+    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(dist, dd, sizeof(int) * (size_t)na * nb, hipMemcpyDeviceToHost, ctx->stream));
+    ORBFE_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return ORBFE_OK;
+} ORBFE_CATCH(ctx)

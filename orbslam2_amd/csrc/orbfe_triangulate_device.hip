@@ -1,6 +1,6 @@
 // orbfe_triangulate_device.hip -- the triangulation stage of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:286-450, with
 // KeyFrame::UnprojectStereo, src/KeyFrame.cc:609-625) for the pairs that orbfe_enqueue_search_for_triangulation left in HBM, asynchronous on
-// the caller's stream.  The entry point and its checks are in orbfe_api.hip; the arithmetic contract is stated in include/orbfe.h and
+// the caller's stream.  The entry point and its checks are at the end of this file; the arithmetic contract is stated in include/orbfe.h and
 // DESIGN.md section 4k, and this file, orbslam2_amd/host/Triangulate.h and tests/triangulate_model.py follow it operation by operation.
 //
 //   triangulate_reset_kernel    status = 0 (and the count of new points when there is nothing else to queue)
@@ -21,6 +21,19 @@
 static_assert(sizeof(orbfe_newpoint_keyframe) == 136, "orbfe_newpoint_keyframe: six pointers, Tcw, Ow, six camera floats, n");
 
 typedef unsigned long long u64;
+// what every kernel of this file takes; the two keyframe records travel by value, the level tables are the context's
+struct orbfe_triangulate_args {
+    orbfe_newpoint_keyframe kf1, kf2;
+    const int32_t *pairs, *npairs;
+    uint8_t *code;
+    float *x3d;
+    int32_t *new_points, *nnew;
+    float *pos;
+    int32_t *rows_used, *status;
+    float mbf, ratio_factor;
+    int max_pairs, n_rows, patch_has_mp, nlevels;
+    float scale[ORBFE_MAX_LEVELS], sigma2[ORBFE_MAX_LEVELS]; // mvScaleFactors, mvLevelSigma2
+};
 typedef orbfe_triangulate_args Args;
 
 __global__ __launch_bounds__(64) void triangulate_reset_kernel(int32_t *status, int32_t *nnew)
@@ -313,12 +326,44 @@ __global__ __launch_bounds__(64) void triangulate_append_kernel(Args a)
     }
 }
 
-int orbfe_triangulate_launch(const orbfe_triangulate_args &a, hipStream_t s)
-{
+// The triangulation stage of LocalMapping::CreateNewMapPoints on device-resident keyframes: at most three launches.
+extern "C" int orbfe_enqueue_triangulate_pairs(orbfe_context *ctx, const orbfe_newpoint_keyframe *kf1, const orbfe_newpoint_keyframe *kf2, float mbf,
+                                               float ratio_factor, const int32_t *d_pairs, const int32_t *d_npairs, int max_pairs, uint8_t *d_code,
+                                               float *d_x3d, int32_t *d_new, int32_t *d_nnew, float *d_pos, int n_rows, int32_t *d_rows_used,
+                                               int patch_has_mp, int32_t *d_status, void *stream)
+try {
+    ORBFE_ENTRY(ctx);
+    // what the arguments alone show is refused first, so that the refusals can be told apart without a device
+    if (!kf1 || !kf2) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "triangulate_pairs: null keyframe record");
+    if (!d_pairs || !d_npairs) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "triangulate_pairs: null d_pairs or d_npairs");
+    if (!d_code || !d_x3d || !d_new || !d_nnew || !d_status) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "triangulate_pairs: null output");
+    if (kf1->n < 0 || kf2->n < 0 || max_pairs < 0 || n_rows < 0) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "triangulate_pairs: negative count");
+    if (max_pairs > 65535) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "triangulate_pairs: max_pairs = %d > 65535", max_pairs);
+    if (max_pairs > 0)
+        for (const orbfe_newpoint_keyframe *kf : {kf1, kf2})
+            if (!kf->keys_un || !kf->keys || !kf->u_right || !kf->depth || !kf->cos_stereo || !kf->has_mp)
+                return orbfe_fail(ctx, ORBFE_ERR_INVALID, "triangulate_pairs: null array in a keyframe record");
+    if (d_pos && !d_rows_used) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "triangulate_pairs: d_pos without d_rows_used");
+    if (!ctx) return orbfe_fail(nullptr, ORBFE_ERR_INVALID, "null context");
+    Args a;
+    a.nlevels = ctx->cfg.nlevels;
+    if (a.nlevels < 1 || a.nlevels > ORBFE_MAX_LEVELS) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "nlevels = %d", a.nlevels);
+    for (int l = 0; l < ORBFE_MAX_LEVELS; l++) {
+        a.scale[l] = l < a.nlevels ? ctx->plan.scale[l] : 1.f;
+        a.sigma2[l] = l < a.nlevels ? ctx->plan.sigma2[l] : 1.f;
+    }
+    a.kf1 = *kf1; a.kf2 = *kf2;
+    a.pairs = d_pairs; a.npairs = d_npairs; a.code = d_code; a.x3d = d_x3d; a.new_points = d_new; a.nnew = d_nnew;
+    a.pos = d_pos; a.rows_used = d_rows_used; a.status = d_status;
+    a.mbf = mbf; a.ratio_factor = ratio_factor;
+    a.max_pairs = max_pairs; a.n_rows = n_rows; a.patch_has_mp = patch_has_mp;
+    hipStream_t s;
+    if (const int rc = orbfe_enqueue_on(ctx, stream, false, &s)) return rc;
     hipLaunchKernelGGL(triangulate_reset_kernel, dim3(1), dim3(64), 0, s, a.status, a.max_pairs == 0 ? a.nnew : nullptr);
     if (a.max_pairs > 0) {
         hipLaunchKernelGGL(triangulate_kernel, dim3((a.max_pairs + 255) / 256), dim3(256), 0, s, a);
         hipLaunchKernelGGL(triangulate_append_kernel, dim3(1), dim3(64), 0, s, a);
     }
-    return (int)hipGetLastError();
-}
+    ORBFE_HIP_TRY(ctx, hipGetLastError());
+    return ORBFE_OK;
+} ORBFE_CATCH(ctx)
