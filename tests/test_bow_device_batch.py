@@ -15,11 +15,10 @@ from oracle import oracle as O
 from orbslam2_amd import bow as B
 from tests import test_bow as TB
 from tests import test_bow_device as TD
+from tests.device_arrays import HAS_UNTOUCHED, UNTOUCHED, XW_UNTOUCHED, Guarded, context, upload, upload_records
 
-UNTOUCHED = TD.UNTOUCHED
 NAMES = ["scene", "c11", "c12", "tiny", "self", "novalid"]
 SETTINGS = ((0.7, True), (0.9, False))
-HAS_UNTOUCHED, XW_UNTOUCHED = 9, -7.0
 
 
 # ------------------------------------------------------------------ the candidate family (CPU)
@@ -128,42 +127,36 @@ def _record(api, kf, nnodes=None):
     return api.BowKeyframe(p[0], p[1], p[2], p[3], p[4], p[5], None if kf.pos is None else kf.pos.data_ptr(), kf.nnodes if nnodes is None else nnodes, kf.n)
 
 
-def _records(api, recs):
-    arr = (api.BowKeyframe * len(recs))(*recs)
-    return TD._dev(np.frombuffer(bytes(arr), np.uint8))
-
-
 class _Rows:
-    """K rows of outputs, every cell holding a sentinel; filled by one batch call or row by row by the single call."""
+    """K rows of outputs between guards, every cell holding a sentinel; filled by one batch call or row by row by the single call."""
 
     def __init__(self, cap, K, pose=False):
-        import torch
         self.cap, self.K = cap, K
-        self.match, self.nm, self.status = TD._i32(max(K, 1) * cap), TD._i32(max(K, 1)), TD._i32(max(K, 1))
-        self.has = torch.full((max(K, 1) * cap,), HAS_UNTOUCHED, dtype=torch.uint8, device="cuda:0") if pose else None
-        self.Xw = torch.full((max(K, 1) * cap * 3,), XW_UNTOUCHED, dtype=torch.float32, device="cuda:0") if pose else None
+        self.match, self.nm, self.status = Guarded.cells(max(K, 1) * cap), Guarded.cells(max(K, 1)), Guarded.cells(max(K, 1))
+        self.has = Guarded(np.full(max(K, 1) * cap, HAS_UNTOUCHED, np.uint8)) if pose else None
+        self.Xw = Guarded(np.full(max(K, 1) * cap * 3, XW_UNTOUCHED, np.float32)) if pose else None
 
     def batch(self, ctx, d_recs, max_nn, fv, ratio, ori, st, n_kfs=None, slot=0):
         ctx.enqueue_search_by_bow_batch(slot, d_recs.data_ptr() if d_recs is not None and d_recs.numel() else 0, self.K if n_kfs is None else n_kfs, max_nn,
-                                        fv.nodes.data_ptr(), fv.node_off.data_ptr(), fv.node_feat.data_ptr(), fv.n_nodes.data_ptr(), ratio, ori,
-                                        self.match.data_ptr(), self.nm.data_ptr(), self.status.data_ptr(),
-                                        d_has_point=0 if self.has is None else self.has.data_ptr(), d_Xw=0 if self.Xw is None else self.Xw.data_ptr(),
+                                        fv.nodes.ptr, fv.node_off.ptr, fv.node_feat.ptr, fv.n_nodes.ptr, ratio, ori,
+                                        self.match.ptr, self.nm.ptr, self.status.ptr,
+                                        d_has_point=0 if self.has is None else self.has.ptr, d_Xw=0 if self.Xw is None else self.Xw.ptr,
                                         stream=st.cuda_stream)
 
     def single(self, ctx, k, kf, fv, ratio, ori, st):
         p = [t.data_ptr() if t.numel() else 0 for t in kf.keep]
         cap = self.cap
         ctx.enqueue_search_by_bow(0, p[0], p[1], p[2], kf.nnodes, p[3], p[4], p[5], kf.n,
-                                  fv.nodes.data_ptr(), fv.node_off.data_ptr(), fv.node_feat.data_ptr(), fv.n_nodes.data_ptr(), ratio, ori,
-                                  self.match.data_ptr() + 4 * k * cap, self.nm.data_ptr() + 4 * k, self.status.data_ptr() + 4 * k,
-                                  d_kf_pos=0 if kf.pos is None else kf.pos.data_ptr(), d_has_point=0 if self.has is None else self.has.data_ptr() + k * cap,
-                                  d_Xw=0 if self.Xw is None else self.Xw.data_ptr() + 12 * k * cap, stream=st.cuda_stream)
+                                  fv.nodes.ptr, fv.node_off.ptr, fv.node_feat.ptr, fv.n_nodes.ptr, ratio, ori,
+                                  self.match.ptr + 4 * k * cap, self.nm.ptr + 4 * k, self.status.ptr + 4 * k,
+                                  d_kf_pos=0 if kf.pos is None else kf.pos.data_ptr(), d_has_point=0 if self.has is None else self.has.ptr + k * cap,
+                                  d_Xw=0 if self.Xw is None else self.Xw.ptr + 12 * k * cap, stream=st.cuda_stream)
 
     def fetch(self):
         out = dict(match=TD._np(self.match).reshape(-1, self.cap), nm=TD._np(self.nm), status=TD._np(self.status))
         if self.has is not None:
-            out["has"] = self.has.cpu().numpy().reshape(-1, self.cap)
-            out["Xw"] = self.Xw.cpu().numpy().reshape(-1, self.cap, 3)
+            out["has"] = self.has.fetch().reshape(-1, self.cap)
+            out["Xw"] = self.Xw.fetch().reshape(-1, self.cap, 3)
         return out
 
     def check_row(self, got, k, ref, nref, what=""):
@@ -191,7 +184,7 @@ def _setup(api, level):
     import torch
     fam = _family(level)
     sc = fam["sc"]
-    ctx = TD._ctx(api)
+    ctx = context(api)
     B.vocab_load(ctx, sc["vocab"])
     TD._inject_desc(ctx, sc["f_d"], sc["f_ang"])
     st = torch.cuda.Stream()
@@ -213,7 +206,7 @@ def test_gpu_the_family_in_one_call(level):
     fam, ctx, st, fv = _setup(api, level)
     n = len(fam["sc"]["f_d"])
     kfs = [_kf_dev(kf, None if kf["name"] == "scene" else _pos(kf, 40 + i)) for i, kf in enumerate(fam["kfs"])]
-    d_recs = _records(api, [_record(api, kf) for kf in kfs])
+    d_recs = upload_records([_record(api, kf) for kf in kfs])
     max_nn = max(kf.nnodes for kf in kfs)
     for ratio, ori in SETTINGS:
         bat, one = _Rows(ctx.capacity, len(kfs), pose=True), _Rows(ctx.capacity, len(kfs), pose=True)
@@ -248,12 +241,12 @@ def test_gpu_batch_calls_queue_back_to_back_and_rows_follow_the_records():
     fam, ctx, st, fv = _setup(api, 4)
     kfs = [_kf_dev(kf) for kf in fam["kfs"]]
     K = len(kfs)
-    fwd = _records(api, [_record(api, kf) for kf in kfs])
-    rev = _records(api, [_record(api, kf) for kf in kfs[::-1]])
+    fwd = upload_records([_record(api, kf) for kf in kfs])
+    rev = upload_records([_record(api, kf) for kf in kfs[::-1]])
     max_nn = max(kf.nnodes for kf in kfs)
     a, b, c = _Rows(ctx.capacity, K), _Rows(ctx.capacity, K), _Rows(ctx.capacity, K)
     one, one_b = _Rows(ctx.capacity, 1), _Rows(ctx.capacity, 1)
-    just_one = _records(api, [_record(api, kfs[1])])
+    just_one = upload_records([_record(api, kfs[1])])
     torch.cuda.synchronize()  # the sentinels and records are in place; from here on nothing waits until the one synchronise
     a.batch(ctx, fwd, max_nn, fv, *SETTINGS[0], st)
     b.batch(ctx, rev, max_nn, fv, *SETTINGS[1], st)
@@ -286,7 +279,7 @@ def test_gpu_more_keyframes_than_a_wave_has_lanes():
         kf["fv"] = TB._oracle_transform(L, v, kf["d"], 4)[2]
         cands.append(kf)
         kfs.append(_kf_dev(kf))
-    out, d_recs = _Rows(ctx.capacity, 70), _records(api, [_record(api, kf) for kf in kfs])
+    out, d_recs = _Rows(ctx.capacity, 70), upload_records([_record(api, kf) for kf in kfs])
     torch.cuda.synchronize()
     out.batch(ctx, d_recs, max(kf.nnodes for kf in kfs), fv, 0.7, True, st)
     st.synchronize()
@@ -312,7 +305,7 @@ def test_gpu_batch_edge_cases():
     fam = _family(4)
     sc = fam["sc"]
     s0 = SETTINGS[0]
-    ctx = TD._ctx(api)
+    ctx = context(api)
     B.vocab_load(ctx, sc["vocab"])
     st = torch.cuda.Stream()
     kfs = [_kf_dev(kf) for kf in fam["kfs"]]
@@ -322,7 +315,7 @@ def test_gpu_batch_edge_cases():
     # a frame without keypoints
     flat = np.full((TM.H, TM.W), 128, np.uint8)
     assert len(ctx.stereo_frame(flat, flat)["kps_left"]) == 0
-    fv, out, d_recs = TD._Fv(ctx.capacity), _Rows(ctx.capacity, K, pose=True), _records(api, recs)
+    fv, out, d_recs = TD._Fv(ctx.capacity), _Rows(ctx.capacity, K, pose=True), upload_records(recs)
     torch.cuda.synchronize()
     fv.enqueue(ctx, 0, 4, st)
     out.batch(ctx, d_recs, max_nn, fv, *s0, st)
@@ -338,7 +331,7 @@ def test_gpu_batch_edge_cases():
     fv.enqueue(ctx, 0, 4, st)
 
     def run(rs, bound, refused=(), other=(), what=""):
-        out, d_rs = _Rows(ctx.capacity, len(rs)), _records(api, rs)
+        out, d_rs = _Rows(ctx.capacity, len(rs)), upload_records(rs)
         torch.cuda.synchronize()
         out.batch(ctx, d_rs, bound, fv, *s0, st)
         st.synchronize()
@@ -402,12 +395,12 @@ def test_gpu_extraction_bow_and_batch_on_one_stream():
     import torch
     from orbslam2_amd import api, synth
     from tests import test_matchers as TM
-    ctx = TD._ctx(api, nfeatures=1500)
+    ctx = context(api, nfeatures=1500)
     blob = TD._vocab()
     B.vocab_load(ctx, blob)
     L, v = TB._oracle_voc(blob)
     left, right = synth.stereo_pair(TM.W, TM.H, seed=702)
-    d_img = TD._dev(np.stack([left, right]).astype(np.uint8))
+    d_img = upload(np.stack([left, right]).astype(np.uint8))[0]
     st = torch.cuda.Stream()
     torch.cuda.synchronize()
     ctx.enqueue_stereo(d_img.data_ptr(), 1, st.cuda_stream)
@@ -426,7 +419,7 @@ def test_gpu_extraction_bow_and_batch_on_one_stream():
         kf["fv"] = TB._oracle_transform(L, v, kf["d"], 4)[2]
         cands.append(kf)
     kfs = [_kf_dev(kf) for kf in cands]
-    d_recs = _records(api, [_record(api, kf) for kf in kfs])
+    d_recs = upload_records([_record(api, kf) for kf in kfs])
     fv, out = TD._Fv(ctx.capacity), _Rows(ctx.capacity, 4)
     torch.cuda.synchronize()
     ctx.enqueue_stereo(d_img.data_ptr(), 1, st.cuda_stream)  # nothing is fetched and nothing waits until the end

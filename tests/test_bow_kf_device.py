@@ -14,10 +14,10 @@ import pytest
 
 from orbslam2_amd import bow as B
 from tests import bow_kf_scenes as S
-from tests import test_bow_device as TD
+from tests.device_arrays import UNTOUCHED, Guarded, context, upload, upload_records
 
 NAMES = ["orbfe_enqueue_search_by_bow_kf", "orbfe_enqueue_search_by_bow_kf_batch"]
-PAD, GUARD, UNTOUCHED = 64, 32, TD.UNTOUCHED
+PAD = 64
 FLOORS = dict(pos64=20, pos128=20, pos4096=8, second_round=1, flag_changed=10, valid2_changed=10, at_th_low=10, tie_rejected=10, pruned=5,
               only_kf1=1, only_kf2=1)
 
@@ -101,13 +101,6 @@ def test_the_candidate_family_tells_rows_apart():
 
 
 # ------------------------------------------------------------------ helpers (GPU)
-def _dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    a = np.concatenate([a, np.zeros(PAD, a.dtype)])
-    return torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to("cuda:0")
-
-
 class _Kf:
     """A keyframe's arrays in HBM and its record.  Edits (name -> array) replace arrays before the upload."""
 
@@ -116,28 +109,26 @@ class _Kf:
     def __init__(self, api, kf, nnodes=None, n=None, **edits):
         a = dict(nodes=kf["fv"][0], off=kf["fv"][1], feat=kf["fv"][2], valid=kf["valid"], desc=kf["d"].reshape(-1), angle=kf["ang"])
         a.update(edits)
-        self.t = {k: _dev(v) for k, v in a.items()}
+        self.t = {k: upload(v, pad=PAD) for k, v in a.items()}
         self.n = len(kf["d"]) if n is None else n
         self.nnodes = len(kf["fv"][0]) if nnodes is None else nnodes
-        self.rec = api.BowKeyframe(*[self.t[k].data_ptr() for k in self.ORDER], None, self.nnodes, self.n)
+        self.rec = api.BowKeyframe(*[self.t[k][1] for k in self.ORDER], None, self.nnodes, self.n)
 
 
-def _records(api, kfs):
-    recs = [kf.rec if isinstance(kf, _Kf) else kf for kf in kfs]
-    return TD._dev(np.frombuffer(bytes((api.BowKeyframe * len(recs))(*recs)), np.uint8))
+def _rec_array(kfs):
+    return upload_records(kf.rec if isinstance(kf, _Kf) else kf for kf in kfs)
 
 
 class _Out:
     """K rows of outputs between guards: match12[K][n1], pairs[K][2 * n1], count[K], status[K]."""
 
     def __init__(self, n1, K=1):
-        import torch
         self.n1, self.K = n1, K
         self.sizes = (K * n1, K * 2 * n1, K, K)
-        self.t = [torch.full((GUARD + max(s, 1) + GUARD,), UNTOUCHED, dtype=torch.int32, device="cuda:0") for s in self.sizes]
+        self.g = [Guarded.cells(s) for s in self.sizes]
 
     def ptr(self, k, row=0):
-        return self.t[k].data_ptr() + 4 * (GUARD + row * (self.sizes[k] // self.K))
+        return self.g[k].ptr + 4 * row * (self.sizes[k] // self.K)
 
     def single(self, ctx, k1, k2, ratio, ori, st, pairs=True, row=0):
         ctx.enqueue_search_by_bow_kf(k1 if k1 is None or not isinstance(k1, _Kf) else k1.rec, k2 if k2 is None or not isinstance(k2, _Kf) else k2.rec,
@@ -151,15 +142,10 @@ class _Out:
 
     def fetch(self):
         """(match12[K][n1], pairs[K][2 * n1], count[K], status[K]); asserts that every cell outside them still holds the sentinel."""
-        res = []
-        for t, s in zip(self.t, self.sizes):
-            a = t.cpu().numpy()
-            assert (a[:GUARD] == UNTOUCHED).all() and (a[GUARD + s:] == UNTOUCHED).all(), "a guard cell was written"
-            res.append(a[GUARD:GUARD + s].reshape(self.K, s // self.K))
-        return res
+        return [g.fetch().reshape(self.K, s // self.K) for g, s in zip(self.g, self.sizes)]
 
     def untouched(self):
-        return all(bool((t == UNTOUCHED).all()) for t in self.t)
+        return all(g.untouched() for g in self.g)
 
 
 def _check_row(got, k, ref, nref, pairs=True, what=""):
@@ -196,7 +182,7 @@ def test_gpu_every_scene_through_the_single_call():
     context: flags in scratch that survived a call would change the next."""
     import torch
     from orbslam2_amd import api
-    ctx = TD._ctx(api)
+    ctx = context(api)
     st = torch.cuda.Stream()
     for name, (kf1, kf2) in S.scenes().items():
         k1, k2 = _Kf(api, kf1), _Kf(api, kf2)
@@ -222,12 +208,12 @@ def test_gpu_the_family_in_one_batch_call_and_as_single_calls():
     scratch are reused by all of them and must be clean."""
     import torch
     from orbslam2_amd import api
-    ctx = TD._ctx(api)
+    ctx = context(api)
     st = torch.cuda.Stream()
     kf1, fam = S.family()
     K, n1 = len(fam), len(kf1["d"])
     k1, kfs = _Kf(api, kf1), [_Kf(api, kf) for kf in fam]
-    fwd, rev, just_one = _records(api, kfs), _records(api, kfs[::-1]), _records(api, kfs[2:3])
+    fwd, rev, just_one = _rec_array(kfs), _rec_array(kfs[::-1]), _rec_array(kfs[2:3])
     max_n = max(kf.n for kf in kfs)
     refs = {s: [S.oracle(kf1, kf, *s) for kf in fam] for s in S.SETTINGS}
     for s in S.SETTINGS:
@@ -270,11 +256,11 @@ def test_gpu_more_candidates_than_a_wave_has_lanes():
     """3. 70 candidates of 200 keypoints: every row equals the oracle."""
     import torch
     from orbslam2_amd import api
-    ctx = TD._ctx(api)
+    ctx = context(api)
     st = torch.cuda.Stream()
     kf1, cands = S.kf1_of_family(), S.small_candidates(70)
     k1, kfs = _Kf(api, kf1), [_Kf(api, kf) for kf in cands]
-    out, d_recs = _Out(k1.n, 70), _records(api, kfs)
+    out, d_recs = _Out(k1.n, 70), _rec_array(kfs)
     torch.cuda.synchronize()
     out.batch(ctx, k1, d_recs, 200, 0.75, True, st)
     st.synchronize()
@@ -294,12 +280,12 @@ def test_gpu_empty_shapes():
     """4."""
     import torch
     from orbslam2_amd import api
-    ctx = TD._ctx(api)
+    ctx = context(api)
     st = torch.cuda.Stream()
     kf1, fam = S.family()
     n1 = len(kf1["d"])
     k1, tiny, sparse = _Kf(api, kf1), _Kf(api, fam[2]), _Kf(api, fam[1])
-    recs = _records(api, [tiny, sparse])
+    recs = _rec_array([tiny, sparse])
     s0 = S.SETTINGS[0]
     # n_kfs == 0: OK, nothing queued (with and without a record array)
     out = _Out(n1, 2)
@@ -318,7 +304,7 @@ def test_gpu_empty_shapes():
     for o in (out, one):
         m, p, nm, status = o.fetch()
         assert (nm == 0).all() and (status == 0).all()
-        assert (o.t[0] == UNTOUCHED).all() and (o.t[1] == UNTOUCHED).all()
+        assert o.g[0].untouched() and o.g[1].untouched()
     # kf1 without nodes; a candidate record of all NULLs and zeros; a candidate with no node in common
     nothing = np.full(n1, -1, np.int32)
     null_rec = api.BowKeyframe(None, None, None, None, None, None, None, 0, 0)
@@ -329,7 +315,7 @@ def test_gpu_empty_shapes():
         "no node in common": (k1, [other, tiny], [(nothing, 0), S.oracle(kf1, fam[2], *s0)]),
     }
     for what, (q, kfs, refs) in cases.items():
-        out, d_recs = _Out(n1, len(kfs)), _records(api, kfs)
+        out, d_recs = _Out(n1, len(kfs)), _rec_array(kfs)
         torch.cuda.synchronize()
         out.batch(ctx, q, d_recs, 800, *s0, st)
         st.synchronize()
@@ -350,16 +336,16 @@ def test_gpu_what_the_host_refuses_queues_nothing():
     """5. Each refusal raises and leaves the outputs untouched; a clean call afterwards works."""
     import torch
     from orbslam2_amd import api
-    ctx = TD._ctx(api)
+    ctx = context(api)
     st = torch.cuda.Stream()
     kf1, fam = S.family()
     n1 = len(kf1["d"])
     k1, tiny = _Kf(api, kf1), _Kf(api, fam[2])
-    recs = _records(api, [tiny])
+    recs = _rec_array([tiny])
     s0 = S.SETTINGS[0]
     out = _Out(n1)
     torch.cuda.synchronize()
-    null_arrays = [api.BowKeyframe(*[None if j == i else k1.t[name].data_ptr() for j, name in enumerate(_Kf.ORDER)], None, k1.nnodes, k1.n) for i in range(6)]
+    null_arrays = [api.BowKeyframe(*[None if j == i else k1.t[name][1] for j, name in enumerate(_Kf.ORDER)], None, k1.nnodes, k1.n) for i in range(6)]
     bad_records = [None, _Kf(api, kf1, n=-1).rec, _Kf(api, kf1, nnodes=-1).rec, _Kf(api, kf1, n=65536).rec] + null_arrays
     for bad in bad_records:
         with pytest.raises(api.OrbfeError):
@@ -392,7 +378,7 @@ def test_gpu_what_only_the_device_sees_is_reported_in_the_row_and_changes_no_oth
     row that meets it), the other rows are exact, no guard cell is written, and a clean call follows each."""
     import torch
     from orbslam2_amd import api
-    ctx = TD._ctx(api)
+    ctx = context(api)
     st = torch.cuda.Stream()
     kf1, fam = S.family()
     n1 = len(kf1["d"])
@@ -400,7 +386,7 @@ def test_gpu_what_only_the_device_sees_is_reported_in_the_row_and_changes_no_oth
     s0 = S.SETTINGS[0]
     refs = [S.oracle(kf1, kf, *s0) for kf in cands]
     k1, kfs = _Kf(api, kf1), [_Kf(api, kf) for kf in cands]
-    clean = _records(api, kfs)
+    clean = _rec_array(kfs)
     max_n = max(kf.n for kf in kfs)
     pert = cands[0]
     fv1, fv2 = kf1["fv"], pert["fv"]
@@ -427,7 +413,7 @@ def test_gpu_what_only_the_device_sees_is_reported_in_the_row_and_changes_no_oth
     }
     assert np.isin(fv1[0][shared1[3]], cands[0]["fv"][0]) and len(cands[0]["d"]) > 1000 >= len(cands[2]["d"])
     for what, (q, recs, bound, refused) in cases.items():
-        out, again, d_recs = _Out(n1, 3), _Out(n1, 3), _records(api, recs)
+        out, again, d_recs = _Out(n1, 3), _Out(n1, 3), _rec_array(recs)
         torch.cuda.synchronize()
         out.batch(ctx, q, d_recs, bound, *s0, st)
         again.batch(ctx, k1, clean, max_n, *s0, st)
@@ -452,21 +438,21 @@ def test_gpu_two_batches_with_a_patch_of_valid1_on_the_stream_in_between():
     points on), a second batch, one synchronise: both equal the oracle run with the same patch."""
     import torch
     from orbslam2_amd import api
-    ctx = TD._ctx(api)
+    ctx = context(api)
     st = torch.cuda.Stream()
     kf1, fam = S.family()
     n1 = len(kf1["d"])
     cands = fam[:3]
     k1, kfs = _Kf(api, kf1), [_Kf(api, kf) for kf in cands]
-    d_recs = _records(api, kfs)
+    d_recs = _rec_array(kfs)
     max_n = max(kf.n for kf in kfs)
     s0 = S.SETTINGS[0]
     first, second = _Out(n1, 3), _Out(n1, 3)
-    valid1 = k1.t["valid"].view(torch.int32)
+    valid1 = k1.t["valid"][0].view(torch.int32)
     torch.cuda.synchronize()
     with torch.cuda.stream(st):
         first.batch(ctx, k1, d_recs, max_n, *s0, st)
-        row0 = first.t[0][GUARD:GUARD + n1]
+        row0 = first.g[0].view[:n1]
         valid1[:n1] = torch.where(row0 >= 0, torch.zeros_like(row0), valid1[:n1])
         second.batch(ctx, k1, d_recs, max_n, *s0, st)
     st.synchronize()

@@ -17,10 +17,10 @@ import pytest
 from oracle import oracle as O
 from tests import matcher_census as MC
 from tests.test_gpu_matcher_census import hip_run
-from tests.test_matchers_device import _ctx
+from tests.device_arrays import UNTOUCHED, Guarded, context, upload
 
 NAMES = ["orbfe_enqueue_keyframe_grid", "orbfe_enqueue_fuse", "orbfe_enqueue_fuse_sim3"]
-PAD, GUARD, UNTOUCHED = 64, 32, -7
+PAD = 64
 CELLS = 64 * 48
 FUSE_INPUTS = [name for name, v in MC.INPUTS.items() if "fuse" in v[1]]
 SIM3_INPUTS = [name for name, v in MC.INPUTS.items() if "sim3_fuse" in v[1]]
@@ -65,43 +65,23 @@ def test_the_census_inputs_reach_what_the_kernel_can_get_wrong():
 
 
 # ------------------------------------------------------------------ helpers (GPU)
-def _dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    a = np.concatenate([a, np.zeros(PAD, a.dtype)])
-    return torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to("cuda:0")
-
-
-def _guarded(n, dtype=None):
-    import torch
-    return torch.full((GUARD + max(n, 1) + GUARD,), UNTOUCHED, dtype=dtype or torch.int32, device="cuda:0")
-
-
-def _inside(t, n):
-    """The n cells between the guards; asserts that the guards still hold the sentinel."""
-    a = t.cpu().numpy()
-    assert (a[:GUARD] == UNTOUCHED).all() and (a[GUARD + n:] == UNTOUCHED).all(), "a guard cell was written"
-    return a[GUARD:GUARD + n]
-
-
 class _Kf:
     """A keyframe's arrays in HBM, its grid (built by the call under test on `stream`) and its record."""
 
     def __init__(self, api, ctx, stream, k, d, ur, bounds, keyframe, n=None, grid=True):
         self.n = len(k) if n is None else n
-        self.keys, self.desc = _dev(k), _dev(np.ascontiguousarray(d, np.uint8).reshape(-1))
-        self.ur = None if ur is None else _dev(np.ascontiguousarray(ur, np.float32))
-        self.off, self.idx = _guarded(CELLS + 1), _guarded(self.n)
+        self.keys, self.desc = upload(k, pad=PAD)[0], upload(np.ascontiguousarray(d, np.uint8).reshape(-1), pad=PAD)[0]
+        self.ur = None if ur is None else upload(np.ascontiguousarray(ur, np.float32), pad=PAD)[0]
+        self.off, self.idx = Guarded.cells(CELLS + 1), Guarded.cells(self.n)
         self.bounds, self.keyframe, self.api = bounds, keyframe, api
         if grid:
-            ctx.enqueue_keyframe_grid(self.keys.data_ptr(), self.n, bounds, self.off.data_ptr() + 4 * GUARD, self.idx.data_ptr() + 4 * GUARD,
+            ctx.enqueue_keyframe_grid(self.keys.data_ptr(), self.n, bounds, self.off.ptr, self.idx.ptr,
                                       stream.cuda_stream)
         self.rec = self.record()
 
     def record(self, off=None, idx=None, keys=None, n=None):
-        p = lambda t: t.data_ptr() + 4 * GUARD
         return self.api.GridKeyframe((keys if keys is not None else self.keys).data_ptr(), 0 if self.ur is None else self.ur.data_ptr(), self.desc.data_ptr(),
-                                     p(self.off if off is None else off), p(self.idx if idx is None else idx), *[float(b) for b in self.bounds],
+                                     (self.off if off is None else off).ptr, (self.idx if idx is None else idx).ptr, *[float(b) for b in self.bounds],
                                      self.n if n is None else n, 1 if self.keyframe else 0)
 
 
@@ -114,7 +94,7 @@ class _Table:
 
     def __init__(self, s):
         self.n = len(s["pos"])
-        self.t = [_dev(np.ascontiguousarray(s[key], dt).reshape(-1)) for key, dt in (("pos", np.float32), ("normal", np.float32), ("max_d", np.float32),
+        self.t = [upload(np.ascontiguousarray(s[key], dt).reshape(-1), pad=PAD)[0] for key, dt in (("pos", np.float32), ("normal", np.float32), ("max_d", np.float32),
                                                                                       ("min_d", np.float32), ("desc", np.uint8))]
 
     def ptrs(self):
@@ -126,13 +106,13 @@ class _Out:
 
     def __init__(self, n_pts):
         self.n = n_pts
-        self.best, self.count, self.status = _guarded(n_pts), _guarded(1), _guarded(1)
+        self.best, self.count, self.status = Guarded.cells(n_pts), Guarded.cells(1), Guarded.cells(1)
 
     def ptrs(self):
-        return [t.data_ptr() + 4 * GUARD for t in (self.best, self.count, self.status)]
+        return [g.ptr for g in (self.best, self.count, self.status)]
 
     def fetch(self):
-        return _inside(self.best, self.n), int(_inside(self.count, 1)[0]), int(_inside(self.status, 1)[0])
+        return self.best.fetch(), int(self.count.fetch()[0]), int(self.status.fetch()[0])
 
 
 def _enqueue(ctx, sim3, rec, pose, table, d_valid, th, out, stream, n_pts=None, d_index=None):
@@ -153,7 +133,7 @@ def _check(out, ref, nref, what):
 def gpu():
     import torch
     from orbslam2_amd import api
-    ctx = _ctx(api)
+    ctx = context(api)
     assert np.array_equal(ctx.tables()["scale"], O.Extractor().scale_factors())
     yield api, ctx, torch.cuda.Stream()
     ctx.close()
@@ -168,14 +148,14 @@ def _run_census_input(gpu, name, matcher):
     sref, snref = hip_run(ctx, matcher, s, p)
     assert snref == nref and np.array_equal(sref, ref), "the synchronous call differs from the oracle"
     kf = _kf_of(api, ctx, st, s, MC._ur(s, matcher, p))  # a monocular case passes u_right = NULL
-    table, d_valid = _Table(s), _dev(s["valid"])
+    table, d_valid = _Table(s), upload(s["valid"], pad=PAD)[0]
     torch.cuda.synchronize()
     for call in range(2):
         out = _Out(table.n)
         _enqueue(ctx, sim3, kf.rec, s["Scw"] if sim3 else s["T_cur"], table, d_valid, p[0], out, st)
         st.synchronize()
         _check(out, ref, nref, "%s / %s, call %d" % (name, matcher, call))
-    _inside(kf.off, CELLS + 1), _inside(kf.idx, kf.n)  # the grid's guards
+    kf.off.fetch(), kf.idx.fetch()  # the grid's guards
 
 
 # ------------------------------------------------------------------ GPU
@@ -193,7 +173,7 @@ def test_gpu_keyframe_grid_equals_assign_features_to_grid(gpu, name):
     assert L.orbfe_assign_features_to_grid(ctx.h, C.byref(view), off_ref.ctypes.data_as(C.c_void_p), idx_ref.ctypes.data_as(C.c_void_p)) == 0
     kf = _kf_of(api, ctx, st, s, None)
     st.synchronize()
-    off, idx = _inside(kf.off, CELLS + 1), _inside(kf.idx, n)
+    off, idx = kf.off.fetch(), kf.idx.fetch()
     assert np.array_equal(off, off_ref)
     total = int(off[CELLS])
     assert 0 < total <= n and (idx[total:] == UNTOUCHED).all()
@@ -203,10 +183,10 @@ def test_gpu_keyframe_grid_equals_assign_features_to_grid(gpu, name):
     if name == "kfbounds_71":
         assert s["bounds"][0] != int(s["bounds"][0])  # cells are assigned with the frame's float bounds
     # n == 0: 3073 zero offsets, no other pointer read
-    off0 = _guarded(CELLS + 1)
-    ctx.enqueue_keyframe_grid(0, 0, s["bounds"], off0.data_ptr() + 4 * GUARD, 0, st.cuda_stream)
+    off0 = Guarded.cells(CELLS + 1)
+    ctx.enqueue_keyframe_grid(0, 0, s["bounds"], off0.ptr, 0, st.cuda_stream)
     st.synchronize()
-    assert (_inside(off0, CELLS + 1) == 0).all()
+    assert (off0.fetch() == 0).all()
 
 
 @pytest.mark.gpu
@@ -240,7 +220,7 @@ def test_gpu_fuse_through_an_index_list_with_validity_per_query(gpu):
     ref, nref = MC.oracle_run("fuse", gathered, p)
     assert nref > 100
     kf, table = _kf_of(api, ctx, st, s, s["ur"]), _Table(s)
-    d_index, d_valid = _dev(index), _dev(valid)
+    d_index, d_valid = upload(index, pad=PAD)[0], upload(valid, pad=PAD)[0]
     out = _Out(nq)
     torch.cuda.synchronize()
     _enqueue(ctx, False, kf.rec, s["T_cur"], table, d_valid, p[0], out, st, nq, d_index)
@@ -249,7 +229,7 @@ def test_gpu_fuse_through_an_index_list_with_validity_per_query(gpu):
     hit = np.nonzero(ref >= 0)[0]
     bad_index = index.copy()
     bad_index[hit[0]], bad_index[hit[1]] = n_rows, -1
-    d_bad = _dev(bad_index)
+    d_bad = upload(bad_index, pad=PAD)[0]
     out = _Out(nq)
     torch.cuda.synchronize()
     _enqueue(ctx, False, kf.rec, s["T_cur"], table, d_valid, p[0], out, st, nq, d_bad)
@@ -284,13 +264,13 @@ def test_gpu_search_in_neighbors_loop_patches_validity_on_the_stream(gpu):
         valid[np.nonzero(refs[-1][0] >= 0)[0][::2]] = 0
     assert all(nref > 50 for _, nref in refs) and any(not np.array_equal(a[0], b[0]) for a, b in zip(refs, unpatched))
     kfs = [_kf_of(api, ctx, st, sc, sc["ur"]) for sc in scenes]
-    table, d_valid = _Table(base), _dev(base["valid"])
+    table, d_valid = _Table(base), upload(base["valid"], pad=PAD)[0]
     outs = [_Out(n) for _ in scenes]
     torch.cuda.synchronize()
     with torch.cuda.stream(st):
         for sc, kf, out in zip(scenes, kfs, outs):
             _enqueue(ctx, False, kf.rec, sc["T_cur"], table, d_valid, th, out, st)
-            m = out.best[GUARD:GUARD + n]
+            m = out.best.view
             hit = m >= 0
             every_other = (hit.to(torch.int32).cumsum(0) % 2 == 1) & hit  # the 1st, 3rd, ... fused point
             d_valid.view(torch.int32)[:n] *= (~every_other).to(torch.int32)
@@ -308,17 +288,12 @@ def test_gpu_refused_inputs_are_reported_in_the_status_and_write_nothing_outside
     ref, nref = MC.oracle_run("fuse", s, p)
     n, n_pts = len(s["k"]), len(s["pos"])
     cand = int(ref[ref >= 0][0])  # a keypoint that is a candidate of a valid point: the oracle's first match
-    kf, table, d_valid = _kf_of(api, ctx, st, s, s["ur"]), _Table(s), _dev(s["valid"])
+    kf, table, d_valid = _kf_of(api, ctx, st, s, s["ur"]), _Table(s), upload(s["valid"], pad=PAD)[0]
     st.synchronize()
-    off, idx = _inside(kf.off, CELLS + 1).copy(), _inside(kf.idx, n).copy()
+    off, idx = kf.off.fetch().copy(), kf.idx.fetch().copy()
     j = int(np.nonzero(idx[: off[CELLS]] == cand)[0][0])
     cell = int(np.searchsorted(off, j, side="right")) - 1
     assert off[cell] <= j < off[cell + 1]
-
-    def guarded_copy(a):
-        t = _guarded(len(a))
-        t[GUARD:GUARD + len(a)] = torch.from_numpy(a).to("cuda:0")
-        return t
 
     bad_octave = s["k"].copy()
     bad_octave["octave"][cand] = MC.NL
@@ -326,7 +301,7 @@ def test_gpu_refused_inputs_are_reported_in_the_status_and_write_nothing_outside
     bad_idx[j] = n
     bad_off = off.copy()
     bad_off[cell + 1] = off[cell] - 1
-    keep = [_dev(bad_octave), guarded_copy(bad_idx), guarded_copy(bad_off)]
+    keep = [upload(bad_octave, pad=PAD)[0], Guarded(bad_idx), Guarded(bad_off)]
     cases = {"octave == nlevels on a candidate keypoint": kf.record(keys=keep[0]), "a cell_idx entry equal to n": kf.record(idx=keep[1]),
              "a descending cell_off": kf.record(off=keep[2])}
     torch.cuda.synchronize()
@@ -341,8 +316,8 @@ def test_gpu_refused_inputs_are_reported_in_the_status_and_write_nothing_outside
         st.synchronize()
         _check(out, ref, nref, "clean call after: " + what)
     # the refused grids were inputs: they and their guards are as they were uploaded
-    assert np.array_equal(_inside(keep[1], n), bad_idx) and np.array_equal(_inside(keep[2], CELLS + 1), bad_off)
-    assert np.array_equal(_inside(kf.idx, n), idx) and np.array_equal(_inside(kf.off, CELLS + 1), off)
+    assert np.array_equal(keep[1].fetch(), bad_idx) and np.array_equal(keep[2].fetch(), bad_off)
+    assert np.array_equal(kf.idx.fetch(), idx) and np.array_equal(kf.off.fetch(), off)
     # what the host can see is refused by the call itself and queues nothing
     out = _Out(n_pts)
     null_keys = kf.record()
@@ -358,9 +333,9 @@ def test_gpu_refused_inputs_are_reported_in_the_status_and_write_nothing_outside
         ctx.enqueue_fuse(kf.rec, s["T_cur"], table.n, 0, table.n, *table.ptrs(), d_valid.data_ptr(), p[0], out.ptrs()[0], 0, out.ptrs()[2],
                          stream=st.cuda_stream)
     with pytest.raises(api.OrbfeError):
-        ctx.enqueue_keyframe_grid(kf.keys.data_ptr(), 65536, s["bounds"], kf.off.data_ptr() + 4 * GUARD, kf.idx.data_ptr() + 4 * GUARD, st.cuda_stream)
+        ctx.enqueue_keyframe_grid(kf.keys.data_ptr(), 65536, s["bounds"], kf.off.ptr, kf.idx.ptr, st.cuda_stream)
     st.synchronize()
-    assert all((t == UNTOUCHED).all() for t in (out.best, out.count, out.status))
+    assert all(g.untouched() for g in (out.best, out.count, out.status))
 
 
 @pytest.mark.gpu
@@ -370,7 +345,7 @@ def test_gpu_empty_shapes(gpu):
     s, p = MC.build("fuse_40"), MC.INPUTS["fuse_40"][1]["fuse"]
     n_pts = len(s["pos"])
     kf, table = _kf_of(api, ctx, st, s, s["ur"]), _Table(s)
-    d_valid, d_none = _dev(s["valid"]), _dev(np.zeros(n_pts, np.int32))
+    d_valid, d_none = upload(s["valid"], pad=PAD)[0], upload(np.zeros(n_pts, np.int32), pad=PAD)[0]
     empty = api.GridKeyframe(0, 0, 0, 0, 0, *[float(b) for b in s["bounds"]], 0, 1)  # a keyframe without keypoints: no array at all
     torch.cuda.synchronize()
     for sim3 in (False, True):
@@ -378,7 +353,7 @@ def test_gpu_empty_shapes(gpu):
         out = _Out(0)  # n_pts == 0: count 0, status 0, nothing else
         _enqueue(ctx, sim3, kf.rec, pose, table, d_valid, p[0], out, st, n_pts=0)
         st.synchronize()
-        assert out.fetch()[1:] == (0, 0) and (out.best == UNTOUCHED).all()
+        assert out.fetch()[1:] == (0, 0) and out.best.untouched()
         for what, rec, valid in (("kf->n == 0", empty, d_valid), ("every point invalid", kf.rec, d_none)):
             out = _Out(n_pts)
             _enqueue(ctx, sim3, rec, pose, table, valid, p[0], out, st)

@@ -18,7 +18,8 @@ import pytest
 
 from oracle import oracle as O
 from tests import matcher_census as MC
-from tests.test_matchers_device import _Last, _Out, _buffers, _ctx, _dev, _raw
+from tests import test_matchers_device as TD
+from tests.device_arrays import context, device_buffers, raw, upload
 
 NEW = [name for name in MC.INPUTS if name not in MC.EXISTING]
 KF_SIDE = ("fuse", "sim3_projection", "sim3_fuse", "by_sim3")
@@ -53,17 +54,17 @@ def _inject_unfetched(ctx, k, d, ur, stream, seed=501):
     import torch
     from orbslam2_amd import synth
     left, right = synth.stereo_pair(MC.W, MC.H, seed=seed)
-    d_img = _dev(np.stack([left, right]).astype(np.uint8))
+    d_img = upload(np.stack([left, right]).astype(np.uint8))[0]
     torch.cuda.synchronize()
     ctx.enqueue_stereo(d_img.data_ptr(), 1, stream.cuda_stream)
     ctx.synchronize(stream.cuda_stream)
     n = len(k)
     assert n <= ctx.capacity
-    b = _buffers(ctx)
-    _raw(b["kps"], 28 * ctx.capacity)[: 28 * n] = _dev(np.ascontiguousarray(k, O.KP_DTYPE))
-    _raw(b["desc"], 32 * ctx.capacity)[: 32 * n] = _dev(np.ascontiguousarray(d, np.uint8).reshape(-1))
-    _raw(b["u_right"], 4 * ctx.capacity)[: 4 * n] = _dev(np.ascontiguousarray(ur, np.float32).view(np.uint8))
-    _raw(b["counts"], 4)[:] = _dev(np.array([n], np.int32).view(np.uint8))
+    b = device_buffers(ctx)
+    raw(b["kps"], 28 * ctx.capacity)[: 28 * n] = upload(np.ascontiguousarray(k, O.KP_DTYPE))[0]
+    raw(b["desc"], 32 * ctx.capacity)[: 32 * n] = upload(np.ascontiguousarray(d, np.uint8).reshape(-1))[0]
+    raw(b["u_right"], 4 * ctx.capacity)[: 4 * n] = upload(np.ascontiguousarray(ur, np.float32).view(np.uint8))[0]
+    raw(b["counts"], 4)[:] = upload(np.array([n], np.int32).view(np.uint8))[0]
     torch.cuda.synchronize()
 
 
@@ -84,7 +85,7 @@ def _same_frustum(got_tp, ref_tp, what):
 @pytest.fixture(scope="module")
 def gpu():
     from orbslam2_amd import api
-    ctx = _ctx(api)
+    ctx = context(api)
     yield api, ctx
     ctx.close()
 
@@ -111,7 +112,7 @@ def test_gpu_census_input_on_the_resident_frame(name):
     s = MC.build(name)
     cases = MC.INPUTS[name][1]
     nk = len(s["k"])
-    ctx = _ctx(api, nfeatures=max(2000, nk + 200))
+    ctx = context(api, nfeatures=max(2000, nk + 200))
     assert ctx.capacity >= nk
     st = torch.cuda.Stream()
     _inject_unfetched(ctx, s["k"], s["d"], s["ur"], st)
@@ -122,9 +123,9 @@ def test_gpu_census_input_on_the_resident_frame(name):
     if "last" in cases:
         th, mono, ori = cases["last"]
         ref, nref = MC.oracle_run("last", s, cases["last"])
-        last = _Last(s["T_cur"], s["T_last"], s["pos"], s["desc"], s["valid"], s["obs"], s["octave"], s["angle"], s["has"])
+        last = TD._Last(s["T_cur"], s["T_last"], s["pos"], s["desc"], s["valid"], s["obs"], s["octave"], s["angle"], s["has"])
         for rep in range(2):
-            out = _Out(ctx.capacity)
+            out = TD._Out(ctx.capacity)
             torch.cuda.synchronize()
             last.enqueue(ctx, 0, s["bounds"], th, mono, ori, out, st)
             st.synchronize()
@@ -134,10 +135,10 @@ def test_gpu_census_input_on_the_resident_frame(name):
         n = len(s["pos"])
         ref_tp = MC.oracle_frustum(s)
         ref, nref = MC.oracle_run("points", s, cases["points"])
-        d_T, d_pos, d_nr, d_mx, d_mn = _dev(s["T_cur"]), _dev(s["pos"]), _dev(s["normal"]), _dev(s["max_d"]), _dev(s["min_d"])
-        d_desc, d_obs, d_has = _dev(s["desc"]), _dev(s["obs"]), _dev(s["has"])
+        d_T, d_pos, d_nr, d_mx, d_mn = upload(s["T_cur"])[0], upload(s["pos"])[0], upload(s["normal"])[0], upload(s["max_d"])[0], upload(s["min_d"])[0]
+        d_desc, d_obs, d_has = upload(s["desc"])[0], upload(s["obs"])[0], upload(s["has"])[0]
         d_tp = torch.zeros(n * 24, dtype=torch.uint8, device="cuda:0")
-        out = _Out(ctx.capacity)
+        out = TD._Out(ctx.capacity)
         torch.cuda.synchronize()
         ctx.enqueue_is_in_frustum(d_T.data_ptr(), s["bounds"], n, d_pos.data_ptr(), d_nr.data_ptr(), d_mx.data_ptr(), d_mn.data_ptr(), 0.5,
                                   d_tp.data_ptr(), st.cuda_stream)
@@ -161,7 +162,7 @@ def test_gpu_first_call_of_a_context_overflows_the_candidate_list(matcher):
     sizes, nq = MC.window_sizes(matcher, s, p)
     assert sum(sizes) > 64 * nq and max(sizes) > 256
     ref = MC.oracle_run(matcher, s, p)
-    ctx = _ctx(api)
+    ctx = context(api)
     _same(hip_run(ctx, matcher, s, p), ref, "overflow / %s, first call of the context" % matcher)
     _same(hip_run(ctx, matcher, s, p), ref, "overflow / %s, second call" % matcher)
     small = MC.build("tie")  # a call whose windows fit, on the grown list

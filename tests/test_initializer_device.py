@@ -12,7 +12,9 @@ import pytest
 from tests import initializer_model as M
 from tests import initializer_scenes as S
 from tests.test_initializer_model import FAULTS, fault_problem, nan_problem
-from tests.test_triangulate_device import _Guarded, _dev
+from tests.device_arrays import Guarded, upload
+
+FRONT, PAD = 64, 64
 
 OPTIONAL = ("inl_h", "inl_f", "ninliers", "all_scores")
 
@@ -20,7 +22,7 @@ OPTIONAL = ("inl_h", "inl_f", "ninliers", "all_scores")
 # ------------------------------------------------------------------ helpers
 class _Inputs:
     def __init__(self, p):
-        self.t = [_dev(np.ascontiguousarray(p[k]).reshape(-1)) for k in ("keys1", "keys2", "pairs", "sets")]
+        self.t = [upload(np.ascontiguousarray(p[k]).reshape(-1), FRONT, PAD) for k in ("keys1", "keys2", "pairs", "sets")]
         self.keys1, self.keys2, self.pairs, self.sets = [t[1] for t in self.t]
 
 
@@ -29,7 +31,7 @@ class _Block:
 
     def __init__(self, p):
         o = S.Outputs(p)
-        self.g = {k: _Guarded(getattr(o, k)) for k in S.Outputs.NAMES}
+        self.g = {k: Guarded(getattr(o, k)) for k in S.Outputs.NAMES}
 
     def ptr(self, k):
         return self.g[k].ptr

@@ -15,10 +15,10 @@ from tests import map_point_model as M
 from tests import map_point_scenes as S
 from tests import matcher_census as MC
 from tests import test_fuse_device as TF
-from tests.test_matchers_device import _ctx
+from tests.device_arrays import Guarded, context, upload
 
 NAME = "orbfe_enqueue_update_map_points"
-FRONT, PAD, GUARD, SENTINEL = 64, 64, 32, 0xA5
+FRONT, PAD = 64, 64
 SCALE = O.Extractor().scale_factors()
 GPU_NS = {1: 6, 2: 6, 3: 6, 4: 6, 5: 6, 8: 6, 33: 4, 63: 4, 64: 4, 65: 4, 130: 3, 300: 2}
 _cache = {}
@@ -113,35 +113,6 @@ def test_the_scene_reaches_every_path_of_the_kernel():
 
 
 # ------------------------------------------------------------------ helpers (GPU)
-def _dev(a, fill=None):
-    """FRONT entries, the payload, PAD entries (zeros, or copies of `fill`); returns the tensor and the payload's address."""
-    import torch
-    a = np.ascontiguousarray(a)
-    pad = lambda k: np.zeros((k,) + a.shape[1:], a.dtype) if fill is None else np.repeat(np.asarray([fill], a.dtype), k, axis=0)
-    whole = np.concatenate([pad(FRONT), a, pad(PAD)])
-    t = torch.from_numpy(whole.view(np.uint8).reshape(-1).copy()).to("cuda:0")
-    return t, t.data_ptr() + FRONT * (whole.nbytes // len(whole))
-
-
-class _Column:
-    """One output column of the table between GUARD sentinel rows."""
-
-    def __init__(self, a):
-        import torch
-        self.a = np.ascontiguousarray(a)
-        self.row_bytes = self.a.nbytes // len(self.a)
-        whole = np.full((len(self.a) + 2 * GUARD) * self.row_bytes, SENTINEL, np.uint8)
-        whole[GUARD * self.row_bytes: (GUARD + len(self.a)) * self.row_bytes] = self.a.view(np.uint8).reshape(-1)
-        self.t = torch.from_numpy(whole).to("cuda:0")
-        self.ptr = self.t.data_ptr() + GUARD * self.row_bytes
-
-    def fetch(self):
-        raw = self.t.cpu().numpy()
-        g = GUARD * self.row_bytes
-        assert (raw[:g] == SENTINEL).all() and (raw[len(raw) - g:] == SENTINEL).all(), "a guard row was written"
-        return raw[g: len(raw) - g].view(self.a.dtype).reshape(self.a.shape)
-
-
 class _Device:
     """A scene in HBM: the keyframe directory (one descriptor and one keypoint buffer, records into them) and the observation lists."""
 
@@ -150,32 +121,32 @@ class _Device:
         first = np.concatenate([[0], np.cumsum(s["kf_n"])[:-1]]).astype(np.int64)
         keys = np.zeros(int(s["kf_n"].sum()), O.KP_DTYPE)
         keys["octave"] = np.concatenate(s["kf_octave"])
-        self.desc, desc_ptr = _dev(np.concatenate(s["kf_desc"]))
-        self.keys, keys_ptr = _dev(keys)
+        self.desc, desc_ptr = upload(np.concatenate(s["kf_desc"]), FRONT, PAD)
+        self.keys, keys_ptr = upload(keys, FRONT, PAD)
         rec = np.zeros(len(s["kf_n"]), api.OBS_KF_DTYPE)
         rec["desc"], rec["keys_un"] = desc_ptr + 32 * first, keys_ptr + O.KP_DTYPE.itemsize * first
         rec["Ow"], rec["n"], rec["bad"] = s["Ow"], s["kf_n"], s["kf_bad"]
-        self.rec, self.rec_ptr = _dev(rec, fill=rec[len(rec) // 2])
-        self.lists = {k: _dev(s[k]) for k in ("obs_off", "obs_kf", "obs_idx", "ref")}
-        self.row = None if s["row"] is None else _dev(s["row"])
-        self.pos = _dev(s["pos"])
+        self.rec, self.rec_ptr = upload(rec, FRONT, PAD, fill=rec[len(rec) // 2])
+        self.lists = {k: upload(s[k], FRONT, PAD) for k in ("obs_off", "obs_kf", "obs_idx", "ref")}
+        self.row = None if s["row"] is None else upload(s["row"], FRONT, PAD)
+        self.pos = upload(s["pos"], FRONT, PAD)
 
     def run(self, ctx, stream, what, table, with_best=True):
         """Queues the update of `table` (numpy columns) on `stream`; returns (status, best or None, the table as the device left it)."""
         import torch
         s = self.s
         n_upd = len(s["obs_off"]) - 1
-        cols = {k: _Column(table[k]) for k in ("normal", "max_d", "min_d", "desc")}
-        best, status = TF._guarded(n_upd), TF._guarded(1)
+        cols = {k: Guarded(table[k]) for k in ("normal", "max_d", "min_d", "desc")}
+        best, status = Guarded.cells(n_upd), Guarded.cells(1)
         torch.cuda.synchronize()  # the uploads and fills above ran on torch's own stream
         ctx.enqueue_update_map_points(self.rec_ptr, len(s["kf_n"]), n_upd, 0 if self.row is None else self.row[1], s["n_rows"], self.lists["obs_off"][1],
                                       self.lists["obs_kf"][1], self.lists["obs_idx"][1], len(s["obs_kf"]), self.lists["ref"][1], what, self.pos[1],
                                       cols["normal"].ptr, cols["max_d"].ptr, cols["min_d"].ptr, cols["desc"].ptr,
-                                      best.data_ptr() + 4 * GUARD if with_best else 0, status.data_ptr() + 4 * GUARD, stream=stream.cuda_stream)
+                                      best.ptr if with_best else 0, status.ptr, stream=stream.cuda_stream)
         stream.synchronize()
         if not with_best:
-            assert (best == TF.UNTOUCHED).all()
-        return int(TF._inside(status, 1)[0]), TF._inside(best, n_upd).copy() if with_best else None, {k: c.fetch() for k, c in cols.items()}
+            assert best.untouched()
+        return int(status.fetch()[0]), best.fetch() if with_best else None, {k: c.fetch() for k, c in cols.items()}
 
 
 def _same(got, want, what):
@@ -190,7 +161,7 @@ def _same(got, want, what):
 def gpu():
     import torch
     from orbslam2_amd import api
-    ctx = _ctx(api)
+    ctx = context(api)
     assert np.array_equal(ctx.tables()["scale"], SCALE) and ctx.nlevels == len(SCALE)
     devices = {}
 
@@ -310,8 +281,8 @@ def test_gpu_refusals_queue_nothing_and_empty_calls_write_the_status_only(gpu):
     api, ctx, st, device_of = gpu
     s, dev = _scene("null"), device_of("null")
     n_upd = len(s["n_of"])
-    status = TF._guarded(1)
-    sp = status.data_ptr() + 4 * GUARD
+    status = Guarded.cells(1)
+    sp = status.ptr
     good = dict(d_kfs=dev.rec_ptr, n_kfs=len(s["kf_n"]), n_upd=n_upd, d_row=0, n_rows=s["n_rows"], d_obs_off=dev.lists["obs_off"][1],
                 d_obs_kf=dev.lists["obs_kf"][1], d_obs_idx=dev.lists["obs_idx"][1], n_obs=len(s["obs_kf"]), d_ref=dev.lists["ref"][1], what=3,
                 d_pos=dev.pos[1], d_normal=8, d_max_distance=8, d_min_distance=8, d_pt_desc=8, d_best=0, d_status=sp)
@@ -324,11 +295,11 @@ def test_gpu_refusals_queue_nothing_and_empty_calls_write_the_status_only(gpu):
     with pytest.raises(api.OrbfeError):
         ctx.enqueue_update_map_points(**dict(good, n_upd=s["n_rows"] + 1), stream=st.cuda_stream)
     st.synchronize()
-    assert (status == TF.UNTOUCHED).all()
+    assert status.untouched()
     # n_upd == 0: status 0 and nothing else, whatever the other pointers are
     ctx.enqueue_update_map_points(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 3, 0, 0, 0, 0, 0, 0, sp, stream=st.cuda_stream)
     st.synchronize()
-    assert int(TF._inside(status, 1)[0]) == 0
+    assert int(status.fetch()[0]) == 0
 
 
 def _chain_scene():
@@ -384,30 +355,30 @@ def test_gpu_fuse_reads_the_rows_the_update_has_just_written_on_the_same_stream(
         def ptrs(self):
             return self.p
 
-    kf, d_valid = TF._kf_of(api, ctx, st, f, f["ur"]), TF._dev(f["valid"])
+    kf, d_valid = TF._kf_of(api, ctx, st, f, f["ur"]), upload(f["valid"], pad=TF.PAD)[0]
     dev = _Device(api, s)
-    model_cols = {k: _Column(want[k]) for k in want}
+    model_cols = {k: Guarded(want[k]) for k in want}
     out_ref = TF._Out(n)
     torch.cuda.synchronize()
     TF._enqueue(ctx, False, kf.rec, f["T_cur"], Table(dev.pos[1], model_cols), d_valid, p[0], out_ref, st)
     st.synchronize()
     ref_best, ref_count, ref_status = out_ref.fetch()
     stale = TF._Out(n)
-    stale_cols = {k: _Column(before[k]) for k in before}
+    stale_cols = {k: Guarded(before[k]) for k in before}
     torch.cuda.synchronize()
     TF._enqueue(ctx, False, kf.rec, f["T_cur"], Table(dev.pos[1], stale_cols), d_valid, p[0], stale, st)
     st.synchronize()
     assert ref_status == 0 and ref_count > 100 and not np.array_equal(stale.fetch()[0], ref_best)  # the rewritten rows decide something
     # the chain: update, then fuse, one synchronise
-    cols = {k: _Column(before[k]) for k in before}
+    cols = {k: Guarded(before[k]) for k in before}
     out = TF._Out(n)
-    best, status = TF._guarded(n), TF._guarded(1)
+    best, status = Guarded.cells(n), Guarded.cells(1)
     torch.cuda.synchronize()
     ctx.enqueue_update_map_points(dev.rec_ptr, 4, n, 0, n, dev.lists["obs_off"][1], dev.lists["obs_kf"][1], dev.lists["obs_idx"][1], len(s["obs_kf"]),
                                   dev.lists["ref"][1], 3, dev.pos[1], cols["normal"].ptr, cols["max_d"].ptr, cols["min_d"].ptr, cols["desc"].ptr,
-                                  best.data_ptr() + 4 * GUARD, status.data_ptr() + 4 * GUARD, stream=st.cuda_stream)
+                                  best.ptr, status.ptr, stream=st.cuda_stream)
     TF._enqueue(ctx, False, kf.rec, f["T_cur"], Table(dev.pos[1], cols), d_valid, p[0], out, st)
     st.synchronize()
-    assert int(TF._inside(status, 1)[0]) == 0 and np.array_equal(TF._inside(best, n), want_best)
+    assert int(status.fetch()[0]) == 0 and np.array_equal(best.fetch(), want_best)
     _same({k: c.fetch() for k, c in cols.items()}, want, "chain")
     TF._check(out, ref_best, ref_count, "fuse behind the update")

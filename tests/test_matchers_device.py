@@ -15,11 +15,11 @@ import pytest
 
 from oracle import oracle as O
 from tests import test_matchers as TM
+from tests.device_arrays import UNTOUCHED, context, device_buffers, raw, upload
 
 W, H, FX, FY, CX, CY, BF, NL = TM.W, TM.H, TM.FX, TM.FY, TM.CX, TM.CY, TM.BF, TM.NL
 NEW = ["orbfe_enqueue_search_by_projection_last", "orbfe_enqueue_is_in_frustum", "orbfe_enqueue_search_by_projection_points",
        "orbfe_device_keys_un"]
-UNTOUCHED = -7  # what the output tensors hold before a call
 
 
 # ------------------------------------------------------------------ CPU
@@ -36,32 +36,6 @@ def test_the_library_exports_the_enqueue_matchers_and_they_refuse_a_null_context
 
 
 # ------------------------------------------------------------------ helpers (GPU)
-class _Raw:
-    """A raw device pointer as a zero-copy torch uint8 tensor."""
-
-    def __init__(self, ptr, nbytes):
-        self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
-
-
-def _raw(ptr, nbytes):
-    import torch
-    return torch.as_tensor(_Raw(ptr, nbytes), device="cuda:0")
-
-
-def _dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.dtype.fields:
-        a = a.view(np.uint8).reshape(-1)
-    return torch.from_numpy(a.copy()).to("cuda:0")
-
-
-def _buffers(ctx):
-    p = [C.c_void_p() for _ in range(5)]
-    ctx._check(ctx.L.orbfe_device_buffers(ctx.h, *[C.byref(x) for x in p]))
-    return dict(kps=p[0].value, desc=p[1].value, counts=p[2].value, u_right=p[3].value)
-
-
 def _inject(ctx, k, d, ur, seed=501):
     """Makes (k, d, ur) image slot 0 of a fresh extraction call of `ctx` (see the module docstring)."""
     import torch
@@ -70,11 +44,11 @@ def _inject(ctx, k, d, ur, seed=501):
     ctx.stereo_frame(left, right)
     n = len(k)
     assert n <= ctx.capacity
-    b = _buffers(ctx)
-    _raw(b["kps"], 28 * ctx.capacity)[: 28 * n] = _dev(np.ascontiguousarray(k, O.KP_DTYPE))
-    _raw(b["desc"], 32 * ctx.capacity)[: 32 * n] = _dev(np.ascontiguousarray(d, np.uint8).reshape(-1))
-    _raw(b["u_right"], 4 * ctx.capacity)[: 4 * n] = _dev(np.ascontiguousarray(ur, np.float32).view(np.uint8))
-    _raw(b["counts"], 4)[:] = _dev(np.array([n], np.int32).view(np.uint8))
+    b = device_buffers(ctx)
+    raw(b["kps"], 28 * ctx.capacity)[: 28 * n] = upload(np.ascontiguousarray(k, O.KP_DTYPE))[0]
+    raw(b["desc"], 32 * ctx.capacity)[: 32 * n] = upload(np.ascontiguousarray(d, np.uint8).reshape(-1))[0]
+    raw(b["u_right"], 4 * ctx.capacity)[: 4 * n] = upload(np.ascontiguousarray(ur, np.float32).view(np.uint8))[0]
+    raw(b["counts"], 4)[:] = upload(np.array([n], np.int32).view(np.uint8))[0]
     torch.cuda.synchronize()
 
 
@@ -102,9 +76,9 @@ class _Last:
 
     def __init__(self, T_cur, T_last, pos, desc, valid, obs, octave, angle, has):
         self.n = len(valid)
-        self.keep = [_dev(np.ascontiguousarray(x, t)) for x, t in ((T_cur, np.float32), (T_last, np.float32), (pos, np.float32), (desc, np.uint8),
+        self.keep = [upload(np.ascontiguousarray(x, t))[0] for x, t in ((T_cur, np.float32), (T_last, np.float32), (pos, np.float32), (desc, np.uint8),
                                                                    (valid, np.int32), (obs, np.int32), (octave, np.int32), (angle, np.float32))]
-        self.has = None if has is None else _dev(np.ascontiguousarray(has, np.uint8))
+        self.has = None if has is None else upload(np.ascontiguousarray(has, np.uint8))[0]
 
     def enqueue(self, ctx, slot, bounds, th, mono, ori, out, stream):
         p = [t.data_ptr() if t.numel() else 0 for t in self.keep]
@@ -116,10 +90,6 @@ class _Last:
 
 def _last_of(s, has_key="has", desc_key="desc"):
     return _Last(s["T_cur"], s["T_last"], s["pos"], s[desc_key], s["valid"], s["obs"], s["octave"], s["angle"], s[has_key])
-
-
-def _ctx(api, **kw):
-    return api.Context(width=W, height=H, fx=FX, fy=FY, cx=CX, cy=CY, bf=BF, **kw)
 
 
 def _prefix_scene():
@@ -163,7 +133,7 @@ def test_gpu_enqueue_last_on_a_real_extracted_frame(distorted):
     asynchronous call, synchronous resident call, asynchronous call again -- all equal to the oracle."""
     import torch
     from orbslam2_amd import api, synth
-    ctx = _ctx(api, nfeatures=1500)
+    ctx = context(api, nfeatures=1500)
     dist = [-0.28, 0.07, 2e-4, 1e-5, 0.0]
     if distorted:
         ctx.set_distortion(dist)
@@ -211,12 +181,12 @@ def test_gpu_enqueue_last_batched_back_to_back():
     synchronisation in between; one synchronise at the end.  Real frames."""
     import torch
     from orbslam2_amd import api, synth
-    ctx = _ctx(api, nfeatures=1200, max_images=8)
+    ctx = context(api, nfeatures=1200, max_images=8)
     imgs = []
     for seed in (601, 602, 603, 604):
         left, right = synth.stereo_pair(W, H, seed=seed)
         imgs += [left, right]
-    d_img = _dev(np.stack(imgs).astype(np.uint8))
+    d_img = upload(np.stack(imgs).astype(np.uint8))[0]
     st = torch.cuda.Stream()
     torch.cuda.synchronize()
     ctx.enqueue_stereo(d_img.data_ptr(), 4, st.cuda_stream)
@@ -259,7 +229,7 @@ def test_gpu_enqueue_last_forward_backward_neither(motion):
     ref, nref = O.search_by_projection_last(O.Grid(s["k"], *s["bounds"]), s["ur"], s["d"], s["sf"], TM.CAM, s["T_cur"], s["T_last"], s["pos"],
                                             s["desc_last"], s["valid"], s["obs"], s["octave"], s["angle"], s["cur_has_obs"], 14.0, False, False)
     assert nref > 50
-    ctx = _ctx(api)
+    ctx = context(api)
     got, ngot = ctx.search_by_projection_last(ctx._view(s["k"], s["ur"], s["d"], s["bounds"]), s["T_cur"], s["T_last"], s["pos"], s["desc_last"],
                                               s["valid"], s["obs"], s["octave"], s["angle"], s["cur_has_obs"], 14.0, False, False)
     assert ngot == nref and np.array_equal(got, ref)
@@ -282,7 +252,7 @@ def test_gpu_enqueue_prefix_runs_out_and_the_window_is_scanned_again():
     from orbslam2_amd import api
     p = _prefix_scene()
     g = O.Grid(p["k"], *p["bounds"])
-    ctx = _ctx(api)
+    ctx = context(api)
     view = ctx._view(p["k"], p["ur"], p["d"], p["bounds"])
     _inject(ctx, p["k"], p["d"], p["ur"])
     st = torch.cuda.Stream()
@@ -315,14 +285,14 @@ def test_gpu_enqueue_prefix_runs_out_and_the_window_is_scanned_again():
         _, n_on = last(mixed, angle, th, True, ("mixed, rotation check", th))
         assert n_on < n_off  # the rotation check removed at least one match
     # SearchByProjection(F, points): best AND second best beyond the prefix
-    d_tp, d_desc = _dev(p["tp"]), _dev(p["desc"])
-    d_has = _dev(p["has"])
+    d_tp, d_desc = upload(p["tp"])[0], upload(p["desc"])[0]
+    d_has = upload(p["has"])[0]
     for obs, what in ((ones, "obs 1"), (zeros, "obs 0"), (mixed, "mixed")):
         ref, nref = O.search_by_projection_points(g, p["ur"], p["d"], p["sf"], p["tp"], p["desc"], obs, p["has"], 3.0, 0.99)
         got, ngot = ctx.search_by_projection_points(view, p["tp"], p["desc"], obs, p["has"], 3.0, 0.99)
         assert ngot == nref and np.array_equal(got, ref) and nref > 200, what
         out = _Out(ctx.capacity)
-        d_obs = _dev(obs)
+        d_obs = upload(obs)[0]
         torch.cuda.synchronize()
         ctx.enqueue_search_by_projection_points(0, p["bounds"], n, d_tp.data_ptr(), d_desc.data_ptr(), d_obs.data_ptr(), 0, d_has.data_ptr(), 3.0, 0.99,
                                                 out.match.data_ptr(), out.nm.data_ptr(), out.status.data_ptr(), stream=st.cuda_stream)
@@ -346,10 +316,10 @@ def test_gpu_enqueue_frustum_and_points():
     max_d = (dist0 * rng.uniform(0.9, 3.0, n)).astype(np.float32); min_d = (max_d / np.float32(1.2 ** 7)).astype(np.float32)
     ref_tp = O.is_in_frustum(s["T_cur"], TM.CAM, s["bounds"], s["pos"], normal, max_d, min_d, 0.5, TM.LOG_SF, NL)
     assert ref_tp["in_view"].sum() > 300
-    ctx = _ctx(api)
+    ctx = context(api)
     _inject(ctx, s["k"], s["d"], s["ur"])
     st = torch.cuda.Stream()
-    d_T, d_pos, d_nr, d_mx, d_mn = _dev(s["T_cur"]), _dev(s["pos"]), _dev(normal), _dev(max_d), _dev(min_d)
+    d_T, d_pos, d_nr, d_mx, d_mn = upload(s["T_cur"])[0], upload(s["pos"])[0], upload(normal)[0], upload(max_d)[0], upload(min_d)[0]
     d_tp = torch.zeros(n * 24, dtype=torch.uint8, device="cuda:0")
     torch.cuda.synchronize()
     ctx.enqueue_is_in_frustum(d_T.data_ptr(), s["bounds"], n, d_pos.data_ptr(), d_nr.data_ptr(), d_mx.data_ptr(), d_mn.data_ptr(), 0.5,
@@ -363,7 +333,7 @@ def test_gpu_enqueue_frustum_and_points():
     assert np.array_equal(got_tp, ctx.is_in_frustum(s["T_cur"], s["bounds"], s["pos"], normal, max_d, min_d, 0.5))  # the host entry point, all rows
     g = O.Grid(s["k"], *s["bounds"])
     view = ctx._view(s["k"], s["ur"], s["d"], s["bounds"])
-    d_desc, d_obs, d_has = _dev(s["desc_last"]), _dev(s["obs"]), _dev(s["cur_has_obs"])
+    d_desc, d_obs, d_has = upload(s["desc_last"])[0], upload(s["obs"])[0], upload(s["cur_has_obs"])[0]
     for th, ratio in ((1.0, 0.8), (3.0, 0.8), (5.0, 0.6)):
         ref, nref = O.search_by_projection_points(g, s["ur"], s["d"], s["sf"], ref_tp, s["desc_last"], s["obs"], s["cur_has_obs"], th, ratio)
         assert nref > 100
@@ -390,7 +360,7 @@ def test_gpu_enqueue_edge_cases():
     valid row is reported in d_status while the host call itself succeeds."""
     import torch
     from orbslam2_amd import api
-    ctx = _ctx(api)
+    ctx = context(api)
     s = TM._scene(12)
     st = torch.cuda.Stream()
     _inject(ctx, s["k"], s["d"], s["ur"])
@@ -439,11 +409,11 @@ def test_gpu_extraction_match_pose_on_one_stream(distorted):
     inlier count are bit-equal to the host entry point fed with the same keys, uRight, has_point and Xw (same kernel)."""
     import torch
     from orbslam2_amd import api, synth
-    ctx = _ctx(api, nfeatures=1500)
+    ctx = context(api, nfeatures=1500)
     if distorted:
         ctx.set_distortion([-0.28, 0.07, 2e-4, 1e-5, 0.0])
     left, right = synth.stereo_pair(W, H, seed=701)
-    d_img = _dev(np.stack([left, right]).astype(np.uint8))
+    d_img = upload(np.stack([left, right]).astype(np.uint8))[0]
     st = torch.cuda.Stream()
     torch.cuda.synchronize()
     ctx.enqueue_stereo(d_img.data_ptr(), 1, st.cuda_stream)
@@ -463,14 +433,14 @@ def test_gpu_extraction_match_pose_on_one_stream(distorted):
     T_host, out_host, n_host = ctx.pose_optimization(T0, kun, ur, has_point, Xw)
     assert n_host > 20
     # the chain; nothing is fetched and nothing waits until the end
-    b = _buffers(ctx)
+    b = device_buffers(ctx)
     last = _last_of(s)
     out = _Out(ctx.capacity, pose=True)
-    d_T = _dev(T0)
+    d_T = upload(T0)[0]
     d_off = torch.zeros(2, dtype=torch.int32, device="cuda:0")
     d_outlier = torch.zeros(ctx.capacity, dtype=torch.uint8, device="cuda:0")
     d_ninl = torch.zeros(1, dtype=torch.int32, device="cuda:0")
-    counts = _raw(b["counts"], 4).view(torch.int32)
+    counts = raw(b["counts"], 4).view(torch.int32)
     torch.cuda.synchronize()
     ctx.enqueue_stereo(d_img.data_ptr(), 1, st.cuda_stream)
     last.keep[0] = d_T  # the 4x4 pose the optimisation will update: the matcher reads its first 12 floats

@@ -24,12 +24,11 @@ from oracle import oracle as O
 from tests import matcher_census as MC
 from tests import test_matchers as TM
 from tests import test_matchers_device as TD
+from tests.device_arrays import BEYOND, HAS_UNTOUCHED, UNTOUCHED, XW_UNTOUCHED, Guarded, context, device_buffers, raw, upload, upload_records
 
 W, H, NL, LOG_SF, CAM = TM.W, TM.H, TM.NL, TM.LOG_SF, TM.CAM
 NEW = ["orbfe_enqueue_search_by_projection_kf", "orbfe_enqueue_search_by_projection_kf_batch"]
 ERR_INVALID, ERR_CAPACITY = -1, -4
-UNTOUCHED, HAS_UNTOUCHED, XW_UNTOUCHED = TD.UNTOUCHED, 9, -7.0
-BEYOND = 1 << 30  # what cur_point holds at and beyond the frame's keypoint count: never read as a keypoint's, never written
 PLAIN = ("track_30", "among", "retreat", "sideways", "tie", "tie_wide", "overflow")  # every census input that lists `kf`
 STAGES = ((10.0, 100, False), (3.0, 64, True))  # the two call sites of Relocalization (src/Tracking.cc:1552, :1566)
 
@@ -230,15 +229,15 @@ class _Cand:
     def __init__(self, rec, cur_point, outlier, cap, T=None):
         import torch
         self.rec, self.n, nk = rec, len(rec["valid"]), len(cur_point)
-        self.T = TD._dev(rec["T"]) if T is None else T
-        self.keep = [TD._dev(np.ascontiguousarray(x, t)) for x, t in ((rec["pos"], np.float32), (rec["desc"], np.uint8), (rec["valid"], np.int32),
+        self.T = upload(rec["T"])[0] if T is None else T
+        self.keep = [upload(np.ascontiguousarray(x, t))[0] for x, t in ((rec["pos"], np.float32), (rec["desc"], np.uint8), (rec["valid"], np.int32),
                                                                       (rec["angle"], np.float32), (rec["max_d"], np.float32), (rec["min_d"], np.float32))]
         cp = np.full(cap, BEYOND, np.int32); cp[:nk] = cur_point
-        self.cur_point = TD._dev(cp)
+        self.cur_point = upload(cp)[0]
         self.outlier = None
         if outlier is not None:
             o = np.ones(cap, np.uint8); o[:nk] = outlier
-            self.outlier = TD._dev(o)
+            self.outlier = upload(o)[0]
         self.cp_in = np.asarray(cur_point, np.int32).copy()
         torch.cuda.synchronize()
 
@@ -254,37 +253,31 @@ class _Cand:
         return api.RelocCandidate(**f)
 
 
-def _records(api, recs):
-    arr = (api.RelocCandidate * len(recs))(*recs)
-    return TD._dev(np.frombuffer(bytes(arr), np.uint8))
-
-
 class _Rows:
-    """K rows of outputs, every cell holding a sentinel; filled by one batch call or row by row by the single call."""
+    """K rows of outputs between guards, every cell holding a sentinel; filled by one batch call or row by row by the single call."""
 
     def __init__(self, cap, K, has_fill=HAS_UNTOUCHED):
         import torch
         self.cap, self.K = cap, K
-        self.match = torch.full((K, cap), UNTOUCHED, dtype=torch.int32, device="cuda:0")
-        self.nm = torch.full((K,), UNTOUCHED, dtype=torch.int32, device="cuda:0")
-        self.status = torch.full((K,), UNTOUCHED, dtype=torch.int32, device="cuda:0")
-        self.has = torch.full((K, cap), has_fill, dtype=torch.uint8, device="cuda:0")
-        self.Xw = torch.full((K, cap, 3), XW_UNTOUCHED, dtype=torch.float32, device="cuda:0")
+        self.match, self.nm, self.status = Guarded.cells(K * cap), Guarded.cells(K), Guarded.cells(K)
+        self.has = Guarded(np.full(K * cap, has_fill, np.uint8))
+        self.Xw = Guarded(np.full(K * cap * 3, XW_UNTOUCHED, np.float32))
         torch.cuda.synchronize()
 
     def single(self, ctx, c, cand, bounds, ori, exclude, st):
         p = cand.ptrs()
         ctx.enqueue_search_by_projection_kf(0, bounds, p[0], cand.n, p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], cand.rec["th"], cand.rec["od"], ori, exclude,
-                                            self.match[c].data_ptr(), self.nm[c:].data_ptr(), self.status[c:].data_ptr(), self.has[c].data_ptr(),
-                                            self.Xw[c].data_ptr(), st.cuda_stream)
+                                            self.match.ptr + 4 * c * self.cap, self.nm.ptr + 4 * c, self.status.ptr + 4 * c, self.has.ptr + c * self.cap,
+                                            self.Xw.ptr + 12 * c * self.cap, st.cuda_stream)
 
     def batch(self, ctx, d_recs, K, max_n, bounds, ori, exclude, st):
-        ctx.enqueue_search_by_projection_kf_batch(0, bounds, d_recs.data_ptr(), K, max_n, ori, exclude, self.match.data_ptr(), self.nm.data_ptr(),
-                                                  self.status.data_ptr(), self.has.data_ptr(), self.Xw.data_ptr(), st.cuda_stream)
+        ctx.enqueue_search_by_projection_kf_batch(0, bounds, d_recs.data_ptr(), K, max_n, ori, exclude, self.match.ptr, self.nm.ptr,
+                                                  self.status.ptr, self.has.ptr, self.Xw.ptr, st.cuda_stream)
 
     def fetch(self, cands):
-        return dict(match=self.match.cpu().numpy(), nm=self.nm.cpu().numpy(), status=self.status.cpu().numpy(), has=self.has.cpu().numpy(),
-                    Xw=self.Xw.cpu().numpy(), cur_point=np.stack([c.cur_point.cpu().numpy() for c in cands]))
+        K, cap = self.K, self.cap
+        return dict(match=self.match.fetch().reshape(K, cap), nm=self.nm.fetch(), status=self.status.fetch(), has=self.has.fetch().reshape(K, cap),
+                    Xw=self.Xw.fetch().reshape(K, cap, 3), cur_point=np.stack([c.cur_point.cpu().numpy() for c in cands]))
 
 
 def _check_row(got, c, nk, cand, exp, what, has_fill=HAS_UNTOUCHED):
@@ -319,7 +312,7 @@ def _sync_kf(ctx, fr, rec, cur_point, outlier, exclude, ori):
 
 
 def _ctx_for(api, fr, **kw):
-    ctx = TD._ctx(api, nfeatures=max(2000, len(fr["k"]) + 200), **kw)
+    ctx = context(api, nfeatures=max(2000, len(fr["k"]) + 200), **kw)
     assert ctx.capacity >= len(fr["k"])
     return ctx
 
@@ -408,7 +401,7 @@ def test_gpu_prefix_runs_out_across_the_chunk_and_a_second_call_chains_on_cur_po
         st.synchronize()
         _check_row(rows1.fetch([cand]), 0, nk, cand, exp1, "first call at %s" % ((th, od, ori),))
         o = np.ones(ctx.capacity, np.uint8); o[:nk] = outl
-        cand.outlier = TD._dev(o)
+        cand.outlier = upload(o)[0]
         torch.cuda.synchronize()
         rows2.single(ctx, 0, cand, fr["bounds"], ori, 1, st)
         st.synchronize()
@@ -435,7 +428,7 @@ def test_gpu_batch_rows_equal_the_single_call_bit_for_bit_and_the_oracle(name):
     a = [_Cand(rec, cp, outl, cap) for _, rec, cp, outl in fam]
     b = [_Cand(fam[i][1], fam[i][2], fam[i][3], cap) for i in order2]
     rows_a, rows_b = _Rows(cap, len(a)), _Rows(cap, len(b))
-    recs_a, recs_b = _records(api, [c.record(api) for c in a]), _records(api, [c.record(api) for c in b])
+    recs_a, recs_b = upload_records([c.record(api) for c in a]), upload_records([c.record(api) for c in b])
     max_a, max_b = max(c.n for c in a), max(c.n for c in b)
     torch.cuda.synchronize()
     rows_a.batch(ctx, recs_a, len(a), max_a, fr["bounds"], True, 1, st)
@@ -485,7 +478,7 @@ def test_gpu_batch_refusals_on_the_device_and_on_the_host():
     recs = [cands[0].record(api), cands[1].record(api, n=max_n + 1), cands[2].record(api), cands[3].record(api, n=-1), cands[4].record(api),
             cands[5].record(api, pos=None), cands[6].record(api)]
     rows = _Rows(cap, len(recs))
-    d_recs = _records(api, recs)
+    d_recs = upload_records(recs)
     torch.cuda.synchronize()
     rows.batch(ctx, d_recs, len(recs), max_n, fr["bounds"], True, 1, st)
     st.synchronize()
@@ -500,8 +493,8 @@ def test_gpu_batch_refusals_on_the_device_and_on_the_host():
     assert int(got["status"][6]) == ERR_INVALID
     assert (got["cur_point"][6][nk:] == BEYOND).all() and (got["match"][6][nk:] == UNTOUCHED).all()
     # host side
-    ok = dict(d_cands=d_recs.data_ptr(), n_cands=2, max_n_kf=max_n, d_cur_match=rows.match.data_ptr(), d_nmatches=rows.nm.data_ptr(),
-              d_status=rows.status.data_ptr(), slot=0, bounds=fr["bounds"])
+    ok = dict(d_cands=d_recs.data_ptr(), n_cands=2, max_n_kf=max_n, d_cur_match=rows.match.ptr, d_nmatches=rows.nm.ptr,
+              d_status=rows.status.ptr, slot=0, bounds=fr["bounds"])
 
     def call(**over):
         a = dict(ok); a.update(over)
@@ -527,8 +520,8 @@ def test_gpu_batch_refusals_on_the_device_and_on_the_host():
         else:
             slot = over[1]
         with pytest.raises(api.OrbfeError) as e:
-            ctx.enqueue_search_by_projection_kf(slot, fr["bounds"], args[0], cands[0].n, *args[1:9], 10.0, 100, True, 1, rows.match.data_ptr(), rows.nm.data_ptr(),
-                                                rows.status.data_ptr(), 0, 0, st.cuda_stream)
+            ctx.enqueue_search_by_projection_kf(slot, fr["bounds"], args[0], cands[0].n, *args[1:9], 10.0, 100, True, 1, rows.match.ptr, rows.nm.ptr,
+                                                rows.status.ptr, 0, 0, st.cuda_stream)
         assert e.value.code == api.ERR_INVALID
     st.synchronize()
     after = rows.fetch(cands)
@@ -558,7 +551,7 @@ def test_gpu_real_extracted_frame_with_distortion_set():
     undistorted on the device.  Plain and chained mode equal the synchronous resident call and the oracle on the undistorted keys."""
     import torch
     from orbslam2_amd import api
-    ctx = TD._ctx(api, nfeatures=1500)
+    ctx = context(api, nfeatures=1500)
     ctx.set_distortion([-0.28, 0.07, 2e-4, 1e-5, 0.0])
     st = torch.cuda.Stream()
     fr, s = _real_frame(ctx, 501, True)
@@ -589,7 +582,7 @@ def test_gpu_projection_then_pose_on_one_stream_without_a_host_step():
     import torch
     from orbslam2_amd import api
     from tests.test_pose import POSE_ATOL
-    ctx = TD._ctx(api, nfeatures=1500)
+    ctx = context(api, nfeatures=1500)
     st = torch.cuda.Stream()
     fr, s = _real_frame(ctx, 701, False)
     nk, cap = len(fr["k"]), ctx.capacity
@@ -611,21 +604,21 @@ def test_gpu_projection_then_pose_on_one_stream_without_a_host_step():
         assert n_host > 20
         ref.append((exp, T_host, out_host, n_host))
     # the chain; nothing is fetched and nothing waits until the end
-    b = TD._buffers(ctx)
-    d_T = TD._dev(np.stack([T4, T4b]))
+    b = device_buffers(ctx)
+    d_T = upload(np.stack([T4, T4b]))[0]
     cands = [_Cand(rec, cp, outl, cap, T=d_T[c]) for c, (rec, (cp, outl)) in enumerate(zip(recs, held))]
     rows = _Rows(cap, 2, has_fill=0)  # the pose problems span the capacity: no point beyond the frame's keypoints
-    d_recs = _records(api, [c.record(api) for c in cands])
+    d_recs = upload_records([c.record(api) for c in cands])
     d_keys = ctx.device_keys_un(0, st.cuda_stream)
     st.synchronize()
-    keys2 = TD._raw(d_keys, 28 * cap).repeat(2)
-    ur2 = TD._raw(b["u_right"], 4 * cap).repeat(2)
-    d_off = TD._dev(np.array([0, cap, 2 * cap], np.int32))
+    keys2 = raw(d_keys, 28 * cap).repeat(2)
+    ur2 = raw(b["u_right"], 4 * cap).repeat(2)
+    d_off = upload(np.array([0, cap, 2 * cap], np.int32))[0]
     d_outlier = torch.zeros(2 * cap, dtype=torch.uint8, device="cuda:0")
     d_ninl = torch.zeros(2, dtype=torch.int32, device="cuda:0")
     torch.cuda.synchronize()
     rows.batch(ctx, d_recs, 2, max(c.n for c in cands), fr["bounds"], True, 1, st)
-    ctx._check(ctx.L.orbfe_enqueue_pose_optimization(ctx.h, 2, d_off.data_ptr(), keys2.data_ptr(), ur2.data_ptr(), rows.has.data_ptr(), rows.Xw.data_ptr(),
+    ctx._check(ctx.L.orbfe_enqueue_pose_optimization(ctx.h, 2, d_off.data_ptr(), keys2.data_ptr(), ur2.data_ptr(), rows.has.ptr, rows.Xw.ptr,
                                                      d_T.data_ptr(), d_outlier.data_ptr(), d_ninl.data_ptr(), cap, st.cuda_stream))
     st.synchronize()
     got = rows.fetch(cands)

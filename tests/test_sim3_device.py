@@ -22,9 +22,9 @@ import pytest
 from oracle import literal_kf_matchers as LK
 from oracle import oracle as O
 from tests import matcher_census as MC
-from tests.test_fuse_device import CELLS, GUARD, UNTOUCHED, _dev, _guarded, _inside, _Kf, _kf_of, _Table
+from tests.device_arrays import Guarded, context, upload
+from tests.test_fuse_device import CELLS, PAD, _Kf, _kf_of, _Table
 from tests.test_gpu_matcher_census import hip_run
-from tests.test_matchers_device import _ctx
 
 NAMES = ["orbfe_enqueue_search_by_sim3", "orbfe_enqueue_search_by_projection_sim3"]
 PROJ_INPUTS = [name for name, v in MC.INPUTS.items() if "sim3_projection" in v[1]]
@@ -175,20 +175,16 @@ def test_no_census_input_is_accepted_beyond_the_prefix():
 def gpu():
     import torch
     from orbslam2_amd import api
-    ctx = _ctx(api)
+    ctx = context(api)
     assert np.array_equal(ctx.tables()["scale"], O.Extractor().scale_factors())
     yield api, ctx, torch.cuda.Stream()
     ctx.close()
 
 
-def _at(t):
-    return t.data_ptr() + 4 * GUARD
-
-
 def _pts_dev(pts):
     pos, mx, mn, d, ok = pts
-    return [_dev(np.ascontiguousarray(pos, np.float32).reshape(-1)), _dev(np.ascontiguousarray(mx, np.float32)), _dev(np.ascontiguousarray(mn, np.float32)),
-            _dev(np.ascontiguousarray(d, np.uint8).reshape(-1)), _dev(np.ascontiguousarray(ok, np.int32))]
+    return [upload(np.ascontiguousarray(pos, np.float32).reshape(-1), pad=PAD)[0], upload(np.ascontiguousarray(mx, np.float32), pad=PAD)[0], upload(np.ascontiguousarray(mn, np.float32), pad=PAD)[0],
+            upload(np.ascontiguousarray(d, np.uint8).reshape(-1), pad=PAD)[0], upload(np.ascontiguousarray(ok, np.int32), pad=PAD)[0]]
 
 
 class _Pair:
@@ -212,13 +208,13 @@ class _Out12:
 
     def __init__(self, n1):
         self.n = n1
-        self.match, self.count, self.status = _guarded(n1), _guarded(1), _guarded(1)
+        self.match, self.count, self.status = Guarded.cells(n1), Guarded.cells(1), Guarded.cells(1)
 
     def ptrs(self):
-        return [_at(t) for t in (self.match, self.count, self.status)]
+        return [g.ptr for g in (self.match, self.count, self.status)]
 
     def fetch(self):
-        return _inside(self.match, self.n), int(_inside(self.count, 1)[0]), int(_inside(self.status, 1)[0])
+        return self.match.fetch(), int(self.count.fetch()[0]), int(self.status.fetch()[0])
 
     def check(self, ref, nref, what):
         m, count, status = self.fetch()
@@ -233,13 +229,13 @@ class _OutProj:
 
     def __init__(self, n_pts, n):
         self.n_pts, self.n = n_pts, n
-        self.pt, self.kf, self.count, self.status = _guarded(n_pts), _guarded(n), _guarded(1), _guarded(1)
+        self.pt, self.kf, self.count, self.status = Guarded.cells(n_pts), Guarded.cells(n), Guarded.cells(1), Guarded.cells(1)
 
     def ptrs(self):
-        return [_at(t) for t in (self.pt, self.kf, self.count, self.status)]
+        return [g.ptr for g in (self.pt, self.kf, self.count, self.status)]
 
     def fetch(self):
-        return _inside(self.pt, self.n_pts), _inside(self.kf, self.n), int(_inside(self.count, 1)[0]), int(_inside(self.status, 1)[0])
+        return self.pt.fetch(), self.kf.fetch(), int(self.count.fetch()[0]), int(self.status.fetch()[0])
 
     def check(self, ref, nref, what):
         pt, kf, count, status = self.fetch()
@@ -268,15 +264,15 @@ def _run_projection(gpu, s, p, what):
     assert snref == nref and np.array_equal(sref, ref), "the synchronous call differs from the oracle"
     none = dict(s, kf_matched=np.zeros(len(s["k"]), np.uint8))
     ref0, nref0 = MC.oracle_run("sim3_projection", none, p)
-    kf, table, d_valid = _kf_of(api, ctx, st, s, None), _Table(s), _dev(s["valid"])
-    d_matched, d_zero = _dev(s["kf_matched"]), _dev(none["kf_matched"])
+    kf, table, d_valid = _kf_of(api, ctx, st, s, None), _Table(s), upload(s["valid"], pad=PAD)[0]
+    d_matched, d_zero = upload(s["kf_matched"], pad=PAD)[0], upload(none["kf_matched"], pad=PAD)[0]
     torch.cuda.synchronize()
     for call, (d_m, r, nr) in enumerate(((d_matched, ref, nref), (d_matched, ref, nref), (None, ref0, nref0), (d_zero, ref0, nref0))):
         out = _OutProj(table.n, kf.n)
         _enqueue_proj(ctx, kf.rec, s, table, d_valid, d_m, p[0], out, st)
         st.synchronize()
         out.check(r, nr, "%s, call %d" % (what, call))
-    _inside(kf.off, CELLS + 1), _inside(kf.idx, kf.n)  # the grid's guards
+    kf.off.fetch(), kf.idx.fetch()  # the grid's guards
 
 
 # ------------------------------------------------------------------ GPU
@@ -298,7 +294,7 @@ def test_gpu_search_by_sim3_equals_the_oracle_and_the_synchronous_call(gpu, name
         st.synchronize()
         out.check(ref, nref, "%s / by_sim3, call %d" % (name, call))
     for kf in (pair.kf1, pair.kf2):
-        _inside(kf.off, CELLS + 1), _inside(kf.idx, kf.n)
+        kf.off.fetch(), kf.idx.fetch()
 
 
 @pytest.mark.gpu
@@ -331,7 +327,7 @@ def test_gpu_projection_through_an_index_list(gpu):
     shuffled = dict(full, **{key: full[key][perm] for key in fields})
     assert n % 4 and nref > 100 and not np.array_equal(index, np.arange(n))
     kf, table = _kf_of(api, ctx, st, s, None), _Table(shuffled)
-    d_valid, d_matched, d_index = _dev(s["valid"]), _dev(s["kf_matched"]), _dev(index)
+    d_valid, d_matched, d_index = upload(s["valid"], pad=PAD)[0], upload(s["kf_matched"], pad=PAD)[0], upload(index, pad=PAD)[0]
     out = _OutProj(n, kf.n)
     torch.cuda.synchronize()
     _enqueue_proj(ctx, kf.rec, s, table, d_valid, d_matched, p[0], out, st, n_pts=n, d_index=d_index)
@@ -343,7 +339,7 @@ def test_gpu_projection_through_an_index_list(gpu):
     without = s["valid"].copy()
     without[hit[:2]] = 0
     expect, _ = MC.oracle_run("sim3_projection", dict(s, valid=without), p)
-    d_bad = _dev(bad_index)
+    d_bad = upload(bad_index, pad=PAD)[0]
     out = _OutProj(n, kf.n)
     torch.cuda.synchronize()
     _enqueue_proj(ctx, kf.rec, s, table, d_valid, d_matched, p[0], out, st, n_pts=n, d_index=d_bad)
@@ -358,25 +354,25 @@ def test_gpu_degenerate_sizes(gpu):
     api, ctx, st = gpu
     s, p = MC.build("among"), MC.INPUTS["among"][1]
     n_pts = len(s["pos"])
-    kf, table, d_valid, d_matched = _kf_of(api, ctx, st, s, None), _Table(s), _dev(s["valid"]), _dev(s["kf_matched"])
+    kf, table, d_valid, d_matched = _kf_of(api, ctx, st, s, None), _Table(s), upload(s["valid"], pad=PAD)[0], upload(s["kf_matched"], pad=PAD)[0]
     empty = api.GridKeyframe(0, 0, 0, 0, 0, *[float(b) for b in s["bounds"]], 0, 1)  # a keyframe without keypoints: no array at all
     torch.cuda.synchronize()
     out = _OutProj(0, kf.n)  # n_pts == 0: every keypoint free, count 0, status 0, d_pt_match untouched
     _enqueue_proj(ctx, kf.rec, s, table, d_valid, d_matched, p["sim3_projection"][0], out, st, n_pts=0)
     st.synchronize()
     _, kfm, count, status = out.fetch()
-    assert (kfm == -1).all() and (count, status) == (0, 0) and (out.pt == UNTOUCHED).all()
+    assert (kfm == -1).all() and (count, status) == (0, 0) and out.pt.untouched()
     out = _OutProj(n_pts, 0)  # kf->n == 0: every query -1, d_kf_match untouched
     _enqueue_proj(ctx, empty, s, table, d_valid, None, p["sim3_projection"][0], out, st)
     st.synchronize()
     pt, _, count, status = out.fetch()
-    assert (pt == -1).all() and (count, status) == (0, 0) and (out.kf == UNTOUCHED).all()
+    assert (pt == -1).all() and (count, status) == (0, 0) and out.kf.untouched()
     pair = _Pair(api, ctx, st, s)
     torch.cuda.synchronize()
     out = _Out12(0)  # kf1->n == 0: count 0, status 0, d_match12 untouched
     pair.enqueue(ctx, p["by_sim3"][0], out, st, rec1=empty, p1=[0] * 5)
     st.synchronize()
-    assert out.fetch()[1:] == (0, 0) and (out.match == UNTOUCHED).all()
+    assert out.fetch()[1:] == (0, 0) and out.match.untouched()
     out = _Out12(pair.kf1.n)  # kf2->n == 0: every entry -1
     pair.enqueue(ctx, p["by_sim3"][0], out, st, rec2=empty, p2=[0] * 5)
     st.synchronize()
@@ -393,15 +389,10 @@ def test_gpu_corrupt_records_are_reported_in_the_status(gpu):
     ref12, nref12 = MC.oracle_run("by_sim3", s, p["by_sim3"])
     refp, nrefp = MC.oracle_run("sim3_projection", s, p["sim3_projection"])
     n, n_pts = len(s["k"]), len(s["pos"])
-    pair, table, d_valid, d_matched = _Pair(api, ctx, st, s), _Table(s), _dev(s["valid"]), _dev(s["kf_matched"])
+    pair, table, d_valid, d_matched = _Pair(api, ctx, st, s), _Table(s), upload(s["valid"], pad=PAD)[0], upload(s["kf_matched"], pad=PAD)[0]
     kf = pair.kf2  # s["k"]: the keyframe the projection matcher searches and direction 1 -> 2 of SearchBySim3 walks
     st.synchronize()
-    off, idx = _inside(kf.off, CELLS + 1).copy(), _inside(kf.idx, n).copy()
-
-    def guarded_copy(a):
-        t = _guarded(len(a))
-        t[GUARD:GUARD + len(a)] = torch.from_numpy(a).to("cuda:0")
-        return t
+    off, idx = kf.off.fetch().copy(), kf.idx.fetch().copy()
 
     def corrupt(cand):
         """Records that are wrong at keypoint `cand`, which the call's reference result holds: its cell is walked."""
@@ -415,7 +406,7 @@ def test_gpu_corrupt_records_are_reported_in_the_status(gpu):
         descending, beyond = off.copy(), off.copy()
         descending[cell + 1] = off[cell] - 1
         beyond[cell + 1] = n + 5  # a missed check reads five guard cells of cell_idx
-        keep = [_dev(bad_octave), guarded_copy(bad_idx), guarded_copy(descending), guarded_copy(beyond)]
+        keep = [upload(bad_octave, pad=PAD)[0], Guarded(bad_idx), Guarded(descending), Guarded(beyond)]
         return keep, {"octave == nlevels on a candidate keypoint": kf.record(keys=keep[0]), "a cell_idx entry equal to n": kf.record(idx=keep[1]),
                       "a descending cell_off": kf.record(off=keep[2]), "a cell_off beyond n": kf.record(off=keep[3])}
 
@@ -442,9 +433,9 @@ def test_gpu_corrupt_records_are_reported_in_the_status(gpu):
         out.check(refp, nrefp, "sim3_projection, clean call after: " + what)
     # the refused grids were inputs: they and their guards are as they were uploaded
     for keep in (keep12, keepp):
-        for t, m in zip(keep[1:], (n, CELLS + 1, CELLS + 1)):
-            _inside(t, m)
-    assert np.array_equal(_inside(kf.idx, n), idx) and np.array_equal(_inside(kf.off, CELLS + 1), off)
+        for g in keep[1:]:
+            g.fetch()
+    assert np.array_equal(kf.idx.fetch(), idx) and np.array_equal(kf.off.fetch(), off)
     # what the host can see is refused by the call itself and queues nothing
     out, out12 = _OutProj(n_pts, n), _Out12(pair.kf1.n)
     null_keys = kf.record()
@@ -464,7 +455,7 @@ def test_gpu_corrupt_records_are_reported_in_the_status(gpu):
         ctx.enqueue_search_by_projection_sim3(kf.rec, s["Scw"], table.n, 0, table.n, *table.ptrs(), d_valid.data_ptr(), 0, 4.0, out.ptrs()[0], 0,
                                               out.ptrs()[2], out.ptrs()[3], stream=st.cuda_stream)
     st.synchronize()
-    assert all((t == UNTOUCHED).all() for t in (out.pt, out.kf, out.count, out.status, out12.match, out12.count, out12.status))
+    assert all(g.untouched() for g in (out.pt, out.kf, out.count, out.status, out12.match, out12.count, out12.status))
 
 
 @pytest.mark.gpu
@@ -485,14 +476,14 @@ def test_gpu_compute_sim3_sequence_on_one_stream(gpu):
     free = MC.oracle_run("sim3_projection", dict(proj, kf_matched=np.zeros(len(a["k1"]), np.uint8)), pa["sim3_projection"])
     assert ref_a[1] > 20 and ref_b[1] > 20 and ref_p[1] > 20 and not np.array_equal(ref_p[0], free[0])
     pair_a, pair_b = _Pair(api, ctx, st, a), _Pair(api, ctx, st, b)
-    table, d_valid = _Table(a), _dev(a["valid"])
+    table, d_valid = _Table(a), upload(a["valid"], pad=PAD)[0]
     n1 = pair_a.kf1.n
     out_a, out_p, out_b = _Out12(n1), _OutProj(table.n, n1), _Out12(pair_b.kf1.n)
     d_matched = torch.zeros(n1 + 64, dtype=torch.uint8, device="cuda:0")
     torch.cuda.synchronize()
     with torch.cuda.stream(st):
         pair_a.enqueue(ctx, pa["by_sim3"][0], out_a, st)
-        d_matched[:n1] = (out_a.match[GUARD:GUARD + n1] >= 0).to(torch.uint8)
+        d_matched[:n1] = (out_a.match.view >= 0).to(torch.uint8)
         _enqueue_proj(ctx, pair_a.kf1.rec, proj, table, d_valid, d_matched, pa["sim3_projection"][0], out_p, st)
         pair_b.enqueue(ctx, pb["by_sim3"][0], out_b, st)
     st.synchronize()

@@ -13,48 +13,20 @@ import pytest
 
 from tests import triangulate_model as M
 from tests import triangulate_scenes as S
+from tests.device_arrays import Guarded, upload
 
-FRONT, PAD, GUARD, SENTINEL = 64, 64, 32, 0xA5
+FRONT, PAD = 64, 64
 UNTOUCHED = S.Outputs.SENT_I32
 _cache = {}
 
 
 # ------------------------------------------------------------------ helpers
-def _dev(a):
-    """FRONT zero entries, the payload, PAD zero entries; returns the tensor and the payload's address."""
-    import torch
-    a = np.ascontiguousarray(a)
-    item = a.dtype.itemsize
-    whole = np.concatenate([np.zeros(FRONT, a.dtype), a, np.zeros(PAD, a.dtype)])
-    t = torch.from_numpy(whole.view(np.uint8).reshape(-1).copy()).to("cuda:0")
-    return t, t.data_ptr() + FRONT * item
-
-
-class _Guarded:
-    """An array the device writes, between GUARD sentinel rows."""
-
-    def __init__(self, a):
-        import torch
-        self.a = np.ascontiguousarray(a)
-        self.row_bytes = max(self.a.nbytes // max(len(self.a), 1), self.a.dtype.itemsize)
-        whole = np.full(self.a.nbytes + 2 * GUARD * self.row_bytes, SENTINEL, np.uint8)
-        whole[GUARD * self.row_bytes: GUARD * self.row_bytes + self.a.nbytes] = self.a.view(np.uint8).reshape(-1)
-        self.t = torch.from_numpy(whole).to("cuda:0")
-        self.ptr = self.t.data_ptr() + GUARD * self.row_bytes
-
-    def fetch(self):
-        raw = self.t.cpu().numpy()
-        g = GUARD * self.row_bytes
-        assert (raw[:g] == SENTINEL).all() and (raw[g + self.a.nbytes:] == SENTINEL).all(), "a guard row was written"
-        return raw[g: g + self.a.nbytes].view(self.a.dtype).reshape(self.a.shape).copy()
-
-
 class _Kf:
     """A model keyframe in HBM and its record; has_mp is guarded (the call writes it) or a tensor the caller shares with another record."""
 
     def __init__(self, api, kf, has_mp_ptr=None):
-        self.t = {k: _dev(v) for k, v in (("keys_un", kf["keys_un"]), ("keys", kf["keys"]), ("ur", kf["ur"]), ("depth", kf["depth"]), ("cos", kf["cos"]))}
-        self.mp = None if has_mp_ptr is not None else _Guarded(kf["mp"])
+        self.t = {k: upload(v, FRONT, PAD) for k, v in (("keys_un", kf["keys_un"]), ("keys", kf["keys"]), ("ur", kf["ur"]), ("depth", kf["depth"]), ("cos", kf["cos"]))}
+        self.mp = None if has_mp_ptr is not None else Guarded(kf["mp"])
         self.kf = kf
         p = [self.t[k][1] for k in ("keys_un", "keys", "ur", "depth", "cos")] + [has_mp_ptr if has_mp_ptr is not None else self.mp.ptr]
         self.rec = api.NewpointKeyframe(*p, (C.c_float * 12)(*kf["Tcw"].tolist()), (C.c_float * 3)(*kf["Ow"].tolist()),
@@ -66,10 +38,10 @@ class _Block:
 
     def __init__(self, p, n_rows, rows_used):
         o = S.Outputs(p, n_rows, rows_used)
-        self.code, self.x3d, self.new = _Guarded(o.code), _Guarded(o.x3d), _Guarded(o.new)
-        self.nnew, self.status = _Guarded(np.array([UNTOUCHED], np.int32)), _Guarded(np.array([UNTOUCHED], np.int32))
-        self.pos = None if n_rows is None else _Guarded(o.pos)
-        self.used = _Guarded(np.array([rows_used], np.int32))
+        self.code, self.x3d, self.new = Guarded(o.code), Guarded(o.x3d), Guarded(o.new)
+        self.nnew, self.status = Guarded(np.array([UNTOUCHED], np.int32)), Guarded(np.array([UNTOUCHED], np.int32))
+        self.pos = None if n_rows is None else Guarded(o.pos)
+        self.used = Guarded(np.array([rows_used], np.int32))
         self.n_rows = n_rows
 
     def fetch(self):
@@ -90,7 +62,7 @@ def _run(api, ctx, st, p, n_rows=900, rows_used=11, patch=1):
     """Uploads a problem, queues the call, synchronises; returns the outputs and both has_mp arrays as the device left them."""
     import torch
     k1, k2 = _Kf(api, p["kf1"]), _Kf(api, p["kf2"])
-    pairs, npairs = _dev(p["pairs"]), _dev(np.array([p["npairs"]], np.int32))
+    pairs, npairs = upload(p["pairs"], FRONT, PAD), upload(np.array([p["npairs"]], np.int32), FRONT, PAD)
     blk = _Block(p, n_rows, rows_used)
     torch.cuda.synchronize()  # the uploads above ran on torch's own stream
     _enqueue(ctx, st, p, k1, k2, pairs[1], npairs[1], blk, patch)
@@ -131,8 +103,8 @@ def _first(p0, count, extra=3):
 def gpu():
     import torch
     from orbslam2_amd import api
-    from tests.test_triangulation_device import _ctx
-    ctx = _ctx(api)
+    from tests import test_triangulation_device as TT
+    ctx = TT._ctx(api)
     sf, s2 = S.levels()
     t = ctx.tables()
     assert np.array_equal(t["scale"], sf) and np.array_equal(t["sigma2"], s2) and ctx.nlevels == S.NLEVELS
@@ -296,7 +268,7 @@ def test_gpu_refusals_queue_nothing_and_an_empty_call_writes_status_and_count(gp
     api, ctx, st = gpu
     p = _first(S.scene("narrow"), 20)
     k1, k2 = _Kf(api, p["kf1"]), _Kf(api, p["kf2"])
-    pairs, npairs = _dev(p["pairs"]), _dev(np.array([p["npairs"]], np.int32))
+    pairs, npairs = upload(p["pairs"], FRONT, PAD), upload(np.array([p["npairs"]], np.int32), FRONT, PAD)
     blk = _Block(p, 50, 0)
     good = dict(kf1=k1.rec, kf2=k2.rec, mbf=float(p["mbf"]), ratio_factor=float(p["ratio"]), d_pairs=pairs[1], d_npairs=npairs[1], max_pairs=p["max_pairs"],
                 d_code=blk.code.ptr, d_x3d=blk.x3d.ptr, d_new=blk.new.ptr, d_nnew=blk.nnew.ptr, d_status=blk.status.ptr, d_pos=blk.pos.ptr, n_rows=50,
@@ -325,7 +297,7 @@ def test_gpu_refusals_queue_nothing_and_an_empty_call_writes_status_and_count(gp
     assert (got["status"], got["nnew"], got["rows_used"]) == (0, 0, 0) and (got["code"] == S.Outputs.SENT_U8).all()
     # a count of 0 under a bound: the same, and the table counter stays
     blk2 = _Block(p, 50, 9)
-    zero = _dev(np.array([0], np.int32))
+    zero = upload(np.array([0], np.int32), FRONT, PAD)
     torch.cuda.synchronize()
     ctx.enqueue_triangulate_pairs(**dict(good, d_npairs=zero[1], d_code=blk2.code.ptr, d_x3d=blk2.x3d.ptr, d_new=blk2.new.ptr, d_nnew=blk2.nnew.ptr,
                                          d_status=blk2.status.ptr, d_pos=blk2.pos.ptr, d_rows_used=blk2.used.ptr), stream=st.cuda_stream)
@@ -381,8 +353,8 @@ def test_gpu_the_queued_loop_equals_the_host_loop(gpu):
     t2s = [TT._Kf(api, dict(sc["kf2"], mp=mp)) for sc, mp in zip(scs, mp2_before)]
     # the triangulation records share keypoints, mvuRight and has_mp with the search records
     def newpoint(t, kf):
-        k = _Kf(api, kf, has_mp_ptr=t.t["mp"].data_ptr())
-        k.rec.keys_un = k.rec.keys = t.t["keys"].data_ptr(); k.rec.u_right = t.t["ur"].data_ptr()
+        k = _Kf(api, kf, has_mp_ptr=t.t["mp"][1])
+        k.rec.keys_un = k.rec.keys = t.t["keys"][1]; k.rec.u_right = t.t["ur"][1]
         return k
     k1, k2s = newpoint(t1, kf1), [newpoint(t, kf) for t, kf in zip(t2s, kf2s)]
     outs = [TT._Out(n1, n1) for _ in scs]
@@ -403,9 +375,9 @@ def test_gpu_the_queued_loop_equals_the_host_loop(gpu):
         _same(got, dict(code=step["code"], x3d=step["x3d"], new=step["new"]), "neighbour %d" % i)
     assert int(used.fetch()[0]) == rows_used and rows_used - 17 > 100
     _same(dict(pos=pos.fetch()), dict(pos=table), "table")
-    assert np.array_equal(t1.t["mp"][:n1].cpu().numpy(), kf1["mp"]) and (kf1["mp"] != mp1_before).any()
+    assert np.array_equal(t1.t["mp"][0][:n1].cpu().numpy(), kf1["mp"]) and (kf1["mp"] != mp1_before).any()
     for t2, kf2, before in zip(t2s, kf2s, mp2_before):
-        assert np.array_equal(t2.t["mp"][:n1].cpu().numpy(), kf2["mp"]) and (kf2["mp"] != before).any()
+        assert np.array_equal(t2.t["mp"][0][:n1].cpu().numpy(), kf2["mp"]) and (kf2["mp"] != before).any()
 
 
 # ------------------------------------------------------------------ chain into a reader
@@ -435,18 +407,18 @@ def test_gpu_fuse_reads_the_rows_the_call_has_just_appended(gpu):
     cols["min_d"][rows] = cols["max_d"][rows] / sf[-1]
     cols["desc"][rows] = kdesc[idx2] ^ np.packbits(rng.random((nnew, 256)) < 0.03, axis=1, bitorder="little")
     kf = TF._Kf(api, ctx, st, target["keys_un"], kdesc, None, (0.0, 640.0, 0.0, 480.0), 1)
-    index, valid = TF._dev(rows.astype(np.int32)), TF._dev(np.ones(nnew, np.int32))
+    index, valid = upload(rows.astype(np.int32), pad=TF.PAD)[0], upload(np.ones(nnew, np.int32), pad=TF.PAD)[0]
 
     class Table:
         def __init__(self, pos_ptr):
             self.n = n_rows
-            self.t = [TF._dev(cols[k].reshape(-1)) for k in ("normal", "max_d", "min_d", "desc")]
+            self.t = [upload(cols[k].reshape(-1), pad=TF.PAD)[0] for k in ("normal", "max_d", "min_d", "desc")]
             self.p = [pos_ptr] + [t.data_ptr() for t in self.t]
 
         def ptrs(self):
             return self.p
 
-    model_pos = TF._dev(want["pos"].reshape(-1))
+    model_pos = upload(want["pos"].reshape(-1), pad=TF.PAD)[0]
     ref = TF._Out(nnew)
     torch.cuda.synchronize()
     TF._enqueue(ctx, False, kf.rec, target["Tcw"], Table(model_pos.data_ptr()), valid, 3.0, ref, st, n_pts=nnew, d_index=index)
@@ -455,7 +427,7 @@ def test_gpu_fuse_reads_the_rows_the_call_has_just_appended(gpu):
     assert ref_status == 0 and ref_count > nnew // 4 and (ref_best[ref_best >= 0] == idx2[ref_best >= 0]).mean() > 0.8   # the rows decide something
     # the chain: triangulate, then fuse, one synchronise
     k1, k2 = _Kf(api, p["kf1"]), _Kf(api, p["kf2"])
-    pairs, npairs = _dev(p["pairs"]), _dev(np.array([p["npairs"]], np.int32))
+    pairs, npairs = upload(p["pairs"], FRONT, PAD), upload(np.array([p["npairs"]], np.int32), FRONT, PAD)
     blk = _Block(p, n_rows, base_row)
     out = TF._Out(nnew)
     chain = Table(blk.pos.ptr)

@@ -14,9 +14,10 @@ import pytest
 
 from orbslam2_amd import bow as B
 from tests import triangulation_scenes as S
+from tests.device_arrays import UNTOUCHED, Guarded, upload
 
 NAME = "orbfe_enqueue_search_for_triangulation"
-PAD, GUARD, UNTOUCHED = 64, 32, -7
+PAD = 64
 FLOORS = dict(pos64=20, pos128=20, pos4096=4, ties=10, flag_changed=10, line_changed=10, disc_changed=4, dist50=3, pruned=10)
 
 
@@ -69,23 +70,16 @@ def _ctx(api):
     return ctx
 
 
-def _dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    a = np.concatenate([a, np.zeros(PAD, a.dtype)])
-    return torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to("cuda:0")
-
-
 class _Kf:
     """A keyframe's arrays in HBM and its record.  Edits (name -> array) replace arrays before the upload."""
 
     def __init__(self, api, kf, nnodes=None, n=None, **edits):
         a = dict(nodes=kf["fv"][0], off=kf["fv"][1], feat=kf["fv"][2], keys=kf["k"], ur=kf["ur"], mp=kf["mp"], desc=kf["d"].reshape(-1))
         a.update(edits)
-        self.t = {k: _dev(v) for k, v in a.items()}
+        self.t = {k: upload(v, pad=PAD) for k, v in a.items()}
         self.n = len(kf["k"]) if n is None else n
         self.nnodes = len(kf["fv"][0]) if nnodes is None else nnodes
-        p = [self.t[k].data_ptr() for k in ("nodes", "off", "feat", "keys", "ur", "mp", "desc")]
+        p = [self.t[k][1] for k in ("nodes", "off", "feat", "keys", "ur", "mp", "desc")]
         self.rec = api.TriKeyframe(*p, self.nnodes, self.n)
 
 
@@ -93,21 +87,15 @@ class _Out:
     """Outputs between guards: match12[n1], pairs[2 * min(n1, n2)], count, status."""
 
     def __init__(self, n1, n2):
-        import torch
         self.n1, self.np = n1, 2 * min(n1, n2)
-        self.sizes = (n1, self.np, 1, 1)
-        self.t = [torch.full((GUARD + max(s, 1) + GUARD,), UNTOUCHED, dtype=torch.int32, device="cuda:0") for s in self.sizes]
+        self.g = [Guarded.cells(s) for s in (n1, self.np, 1, 1)]
 
     def ptr(self, k):
-        return self.t[k].data_ptr() + 4 * GUARD
+        return self.g[k].ptr
 
     def fetch(self):
         """(match12, pairs, count, status); asserts that every cell outside them still holds the sentinel."""
-        res = []
-        for t, s in zip(self.t, self.sizes):
-            a = t.cpu().numpy()
-            assert (a[:GUARD] == UNTOUCHED).all() and (a[GUARD + s:] == UNTOUCHED).all(), "a guard cell was written"
-            res.append(a[GUARD:GUARD + s])
+        res = [g.fetch() for g in self.g]
         return res[0], res[1], int(res[2][0]), int(res[3][0])
 
 
@@ -201,12 +189,12 @@ def test_gpu_create_new_map_points_loop_patches_has_mp_on_the_stream():
     k1 = _Kf(api, base["kf1"])
     k2s = [_Kf(api, sc["kf2"]) for sc in scs]
     outs = [_Out(n1, n1) for _ in scs]
-    has_mp = k1.t["mp"]
+    has_mp = k1.t["mp"][0]
     torch.cuda.synchronize()
     with torch.cuda.stream(st):
         for sc, k2, out in zip(scs, k2s, outs):
             _enqueue(ctx, sc, k1, k2, (0, 1), out, st)
-            m = out.t[0][GUARD:GUARD + n1]
+            m = out.g[0].view[:n1]
             hit = (m >= 0).to(torch.int32)
             every_other = (hit.cumsum(0) % 2 == 1) & (m >= 0)  # the 1st, 3rd, ... matched idx1
             has_mp[:n1] |= every_other.to(torch.uint8)
@@ -303,7 +291,7 @@ def test_gpu_refused_inputs_are_reported_in_the_status_and_write_nothing_outside
                                              0, out.ptr(2), out.ptr(3), stream=st.cuda_stream)
     st.synchronize()
     m, p, _, _ = out.fetch()
-    assert (m == UNTOUCHED).all() and (p == UNTOUCHED).all() and (out.t[2] == UNTOUCHED).all() and (out.t[3] == UNTOUCHED).all()
+    assert (m == UNTOUCHED).all() and (p == UNTOUCHED).all() and out.g[2].untouched() and out.g[3].untouched()
     ctx.close()
 
 

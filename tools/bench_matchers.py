@@ -97,6 +97,37 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import oracle as O  # noqa: E402
 from tests import test_matchers as TM  # noqa: E402
+from tests.device_arrays import raw, timed_loops, upload  # noqa: E402
+
+
+def up(a, dtype=None):
+    """`a` (as `dtype`) in HBM, as flat bytes."""
+    return upload(np.ascontiguousarray(a, dtype).view(np.uint8).reshape(-1))[0]
+
+
+def interleaved(repeats, reps, st, loops, enqueues=(), before=None):
+    """`repeats` times, interleaved: every callable of `loops` through timed_loops, then (after before()) every callable of `enqueues`
+    queued `reps` times back to back on `st`, each between two events.  Returns [(means, slowest) per loop], [GPU ms per enqueue]."""
+    import torch
+    wall, gpu = [([], []) for _ in loops], [[] for _ in enqueues]
+    for _ in range(repeats):
+        for (means, slowest), fn in zip(wall, loops):
+            m, w = timed_loops(fn, reps)
+            means.append(m); slowest.append(w)
+        if not enqueues:
+            continue
+        if before is not None:
+            before()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(enqueues) + 1)]
+        ev[0].record(st)
+        for e, enqueue in zip(ev[1:], enqueues):
+            for _ in range(reps):
+                enqueue()
+            e.record(st)
+        st.synchronize()
+        for ms, e0, e1 in zip(gpu, ev, ev[1:]):
+            ms.append(round(e0.elapsed_time(e1) / reps, 4))
+    return wall, gpu
 
 
 def timeit(fn, reps):
@@ -116,7 +147,6 @@ def resident_async_rows(ctx2, out, fs, fb, fk, fur, v_dev, args_sync):
         out["async"] = "not exported by this library"
         return
     dev = torch.device("cuda:0")
-    up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, t)).to(dev)
     T4 = np.eye(4, dtype=np.float32); T4[:3] = fs["T_cur"]
     d = dict(tc=up(T4, np.float32), tl=up(fs["T_last"], np.float32), pos=up(fs["pos"], np.float32), desc=up(fs["desc"], np.uint8),
              val=up(fs["valid"], np.int32), obs=up(fs["obs"], np.int32), oct=up(fs["octave"], np.int32), ang=up(fs["angle"], np.float32),
@@ -211,7 +241,6 @@ def bow_rows(out):
     from tests import test_bow as TB
     vp, P = C.c_void_p, TB._p
     dev = torch.device("cuda:0")
-    up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, t).view(np.uint8).reshape(-1)).to(dev)
     i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
     ctx = api.Context(width=TM.W, height=TM.H, nfeatures=2000, fx=TM.FX, fy=TM.FY, cx=TM.CX, cy=TM.CY, bf=TM.BF)
     L = ctx.L
@@ -304,10 +333,6 @@ def bow_rows(out):
         n = len(f_d)
         k = np.zeros(n, api.KP_DTYPE); k["angle"] = f_ang
 
-        def raw(ptr, nbytes):
-            class R:
-                __cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
-            return torch.as_tensor(R(), device=dev)
         raw(bufs[0].value, 28 * n)[:] = torch.from_numpy(k.view(np.uint8).reshape(-1).copy()).to(dev)
         raw(bufs[1].value, 32 * n)[:] = up(f_d, np.uint8)
         raw(bufs[2].value, 4)[:] = up(np.array([n], np.int32), np.int32)
@@ -387,7 +412,6 @@ def bow_batch_rows(out):
     from tests import test_bow as TB
     vp = C.c_void_p
     dev = torch.device("cuda:0")
-    up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, t).view(np.uint8).reshape(-1)).to(dev)
     i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
     ctx = api.Context(width=TM.W, height=TM.H, nfeatures=2000, fx=TM.FX, fy=TM.FY, cx=TM.CX, cy=TM.CY, bf=TM.BF)
     L = ctx.L
@@ -444,10 +468,6 @@ def bow_batch_rows(out):
     assert L.orbfe_device_buffers(ctx.h, *[C.byref(x) for x in bufs]) == 0
     kp = np.zeros(n, api.KP_DTYPE); kp["angle"] = f_ang
 
-    def raw(ptr, nbytes):
-        class R:
-            __cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
-        return torch.as_tensor(R(), device=dev)
     raw(bufs[0].value, 28 * n)[:] = torch.from_numpy(kp.view(np.uint8).reshape(-1).copy()).to(dev)
     raw(bufs[1].value, 32 * n)[:] = up(f_d, np.uint8)
     raw(bufs[2].value, 4)[:] = up(np.array([n], np.int32), np.int32)
@@ -519,7 +539,6 @@ def reloc_rows(out):
     vp = C.c_void_p
     P = lambda a: a.ctypes.data_as(vp)
     dev = torch.device("cuda:0")
-    up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, t).view(np.uint8).reshape(-1)).to(dev)
     ctx = api.Context(width=TM.W, height=TM.H, nfeatures=2000, fx=TM.FX, fy=TM.FY, cx=TM.CX, cy=TM.CY, bf=TM.BF)
     L = ctx.L
     have = hasattr(L, "orbfe_enqueue_search_by_projection_kf_batch")
@@ -616,7 +635,6 @@ def triangulation_rows(out):
     from orbslam2_amd import bow as B
     from tests import triangulation_scenes as S
     dev = torch.device("cuda:0")
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
     N, K, REPS, REPEATS = 2000, 20, 10, 5
     ctx = api.Context(width=640, height=480, nfeatures=2000, fx=S.FX, fy=S.FY, cx=S.CX, cy=S.CY, bf=40.0)
     L = ctx.L
@@ -685,38 +703,15 @@ def triangulation_rows(out):
                 st.synchronize()
 
         device_loop(check=True)
-    def loops(fn):
-        """Mean and slowest of REPS loops over the neighbours, each timed on its own: one stalled loop shows as such.  The cyclic
-        garbage collector is off inside the window, as in the standard timeit module."""
-        import gc
-        fn()
-        gc.collect()
-        gc.disable()
-        try:
-            t = []
-            for _ in range(REPS):
-                t0 = time.perf_counter()
-                fn()
-                t.append((time.perf_counter() - t0) * 1e3)
-        finally:
-            gc.enable()
-        return round(sum(t) / REPS, 4), round(max(t), 4)
 
-    a_rows, a_worst, b_wall, b_worst, b_gpu = [], [], [], [], []
-    for _ in range(REPEATS):
-        m, w = loops(sync_loop)
-        a_rows.append(m); a_worst.append(w)
-        if have:
-            m, w = loops(device_loop)
-            b_wall.append(m); b_worst.append(w)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(st)
-            for _ in range(REPS):
-                for k in range(K):
-                    enqueue(k)
-            e1.record(st)
-            st.synchronize()
-            b_gpu.append(round(e0.elapsed_time(e1) / REPS, 4))
+    def enqueue_all():
+        for k in range(K):
+            enqueue(k)
+
+    if have:
+        ((a_rows, a_worst), (b_wall, b_worst)), (b_gpu,) = interleaved(REPEATS, REPS, st, [sync_loop, device_loop], [enqueue_all])
+    else:
+        ((a_rows, a_worst),), _ = interleaved(REPEATS, REPS, None, [sync_loop])
     out["rows"]["(a) orbfe_search_for_triangulation x %d, synchronous, has_mp1 patched on the host, wall time" % K] = {
         "ms_per_repeat": a_rows, "slowest_loop_ms": a_worst}
     if have:
@@ -732,12 +727,10 @@ def triangulation_rows(out):
 
 def fuse_rows(out):
     """Rows of --fuse; arguments prepared once."""
-    import gc
     import torch
     from orbslam2_amd import api
     from tests import matcher_census as MC
     dev = torch.device("cuda:0")
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
     K, N_PTS, PER_TARGET, TH, REPS, REPEATS = 30, 1500, 1000, 3.0, 10, 5
     ctx = api.Context(width=MC.W, height=MC.H, fx=MC.FX, fy=MC.FY, cx=MC.CX, cy=MC.CY, bf=MC.BF)
     have = hasattr(ctx.L, "orbfe_enqueue_fuse")
@@ -834,35 +827,15 @@ def fuse_rows(out):
 
         device_loop(check=True)
 
-    def loops(fn):
-        fn()
-        gc.collect()
-        gc.disable()  # the cyclic collector is off inside the window, as in the standard timeit module
-        try:
-            t = []
-            for _ in range(REPS):
-                t0 = time.perf_counter()
-                fn()
-                t.append((time.perf_counter() - t0) * 1e3)
-        finally:
-            gc.enable()
-        return round(sum(t) / REPS, 4), round(max(t), 4)
 
-    a_rows, a_worst, b_wall, b_worst, c_gpu = [], [], [], [], []
-    for _ in range(REPEATS):
-        m, w = loops(sync_loop)
-        a_rows.append(m); a_worst.append(w)
-        if have:
-            m, w = loops(device_loop)
-            b_wall.append(m); b_worst.append(w)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(st)
-            for _ in range(REPS):
-                for k in range(K + 1):
-                    enqueue(k)
-            e1.record(st)
-            st.synchronize()
-            c_gpu.append(round(e0.elapsed_time(e1) / REPS, 4))
+    def enqueue_all():
+        for k in range(K + 1):
+            enqueue(k)
+
+    if have:
+        ((a_rows, a_worst), (b_wall, b_worst)), (c_gpu,) = interleaved(REPEATS, REPS, st, [sync_loop, device_loop], [enqueue_all])
+    else:
+        ((a_rows, a_worst),), _ = interleaved(REPEATS, REPS, None, [sync_loop])
     out["rows"]["(a) orbfe_fuse x %d, synchronous, validity patched on the host, wall time" % (K + 1)] = {"ms_per_repeat": a_rows, "slowest_loop_ms": a_worst}
     if have:
         out["rows"]["(b) %d x (orbfe_enqueue_fuse + download of best_idx and count + synchronise), validity patch queued in between, wall time" % (K + 1)] = {
@@ -877,12 +850,10 @@ def fuse_rows(out):
 
 def sim3_rows(out):
     """Rows of --sim3; arguments prepared once."""
-    import gc
     import torch
     from orbslam2_amd import api
     from tests import matcher_census as MC
     dev = torch.device("cuda:0")
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
     K, ROUNDS, N_PTS, N_KFS, TH, TH_PROJ, REPS, REPEATS = 3, 5, 1500, 10, 7.5, 10.0, 10, 5
     ctx = api.Context(width=MC.W, height=MC.H, fx=MC.FX, fy=MC.FY, cx=MC.CX, cy=MC.CY, bf=MC.BF)
     have = hasattr(ctx.L, "orbfe_enqueue_search_by_sim3") and hasattr(ctx.L, "orbfe_enqueue_search_by_projection_sim3")
@@ -970,38 +941,15 @@ def sim3_rows(out):
 
         device_loop(check=True)
 
-    def loops(fn):
-        fn()
-        gc.collect()
-        gc.disable()  # the cyclic collector is off inside the window, as in the standard timeit module
-        try:
-            t = []
-            for _ in range(REPS):
-                t0 = time.perf_counter()
-                fn()
-                t.append((time.perf_counter() - t0) * 1e3)
-        finally:
-            gc.enable()
-        return round(sum(t) / REPS, 4), round(max(t), 4)
 
-    a_rows, a_worst, b_wall, b_worst, c_gpu, c_proj = [], [], [], [], [], []
-    for _ in range(REPEATS):
-        m, w = loops(sync_loop)
-        a_rows.append(m); a_worst.append(w)
-        if have:
-            m, w = loops(device_loop)
-            b_wall.append(m); b_worst.append(w)
-            e0, e1, e2 = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-            e0.record(st)
-            for _ in range(REPS):
-                for k, r in calls:
-                    enqueue(k, r)
-            e1.record(st)
-            for _ in range(REPS):
-                enqueue(K, 0)
-            e2.record(st)
-            st.synchronize()
-            c_gpu.append(round(e0.elapsed_time(e1) / REPS, 4)); c_proj.append(round(e1.elapsed_time(e2) / REPS, 4))
+    def enqueue_all():
+        for k, r in calls:
+            enqueue(k, r)
+
+    if have:
+        ((a_rows, a_worst), (b_wall, b_worst)), (c_gpu, c_proj) = interleaved(REPEATS, REPS, st, [sync_loop, device_loop], [enqueue_all, lambda: enqueue(K, 0)])
+    else:
+        ((a_rows, a_worst),), _ = interleaved(REPEATS, REPS, None, [sync_loop])
     n_calls = K * ROUNDS
     out["rows"]["(a) orbfe_search_by_sim3 x %d + orbfe_search_by_projection_sim3, synchronous, wall time" % n_calls] = {"ms_per_repeat": a_rows, "slowest_loop_ms": a_worst}
     if have:
@@ -1019,13 +967,11 @@ def sim3_rows(out):
 def bow_kf_rows(out):
     """Rows of --bow-kf; arguments prepared once."""
     import ctypes as C
-    import gc
     import torch
     from orbslam2_amd import api
     from orbslam2_amd import bow as B
     from tests import bow_kf_scenes as S
     dev = torch.device("cuda:0")
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
     KS, RATIO, ORI, REPS, REPEATS = (1, 3, 16), 0.75, True, 10, 10
     ctx = api.Context(width=TM.W, height=TM.H, fx=TM.FX, fy=TM.FY, cx=TM.CX, cy=TM.CY, bf=TM.BF)
     have = hasattr(ctx.L, "orbfe_enqueue_search_by_bow_kf_batch")
@@ -1085,38 +1031,15 @@ def bow_kf_rows(out):
                     assert res[K + k] == 0 and nm == refs[k][1], (K, k)
                     assert np.array_equal(res[2 * K + k * 2 * n1:][:2 * nm], S.pairs_of(refs[k][0])), (K, k)
 
-    def loops(fn):
-        fn()
-        gc.collect()
-        gc.disable()  # the cyclic collector is off inside the window, as in the standard timeit module
-        try:
-            t = []
-            for _ in range(REPS):
-                t0 = time.perf_counter()
-                fn()
-                t.append((time.perf_counter() - t0) * 1e3)
-        finally:
-            gc.enable()
-        return round(sum(t) / REPS, 4), round(max(t), 4)
 
     for K in KS:
         sync_loop(K, check=True)
         if have:
             device_loop(K, check=True)
-        a_rows, a_worst, b_wall, b_worst, c_gpu = [], [], [], [], []
-        for _ in range(REPEATS):
-            m, w = loops(lambda: sync_loop(K))
-            a_rows.append(m); a_worst.append(w)
-            if have:
-                m, w = loops(lambda: device_loop(K))
-                b_wall.append(m); b_worst.append(w)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(st)
-                for _ in range(REPS):
-                    enqueue(K)
-                e1.record(st)
-                st.synchronize()
-                c_gpu.append(round(e0.elapsed_time(e1) / REPS, 4))
+        if have:
+            ((a_rows, a_worst), (b_wall, b_worst)), (c_gpu,) = interleaved(REPEATS, REPS, st, [lambda: sync_loop(K), lambda: device_loop(K)], [lambda: enqueue(K)])
+        else:
+            ((a_rows, a_worst),), _ = interleaved(REPEATS, REPS, None, [lambda: sync_loop(K)])
         rows = out["rows"]["K = %d" % K] = {"(a) %d x orbfe_search_by_bow_kf, synchronous, wall time" % K: {"ms_per_repeat": a_rows, "slowest_loop_ms": a_worst}}
         if have:
             rows["(b) orbfe_enqueue_search_by_bow_kf_batch + copy of counts and pairs into pinned memory + one synchronise, wall time"] = {
@@ -1132,7 +1055,6 @@ def bow_kf_rows(out):
 def map_point_rows(out):
     """Rows of --map-points; arguments prepared once."""
     import ctypes as C
-    import gc
     import subprocess
     import tempfile
     import torch
@@ -1183,7 +1105,6 @@ def map_point_rows(out):
             st.synchronize()
 
     # the device form: directory resident, the lists travel per call
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
     d_desc, d_keys, d_pos = up(h_desc), up(h_keys), up(s["pos"])
     d_rec = up(records(d_desc.data_ptr(), d_keys.data_ptr()))
     lists = np.concatenate([s["obs_off"], s["obs_kf"], s["obs_idx"], s["ref"]]).astype(np.int32)
@@ -1214,33 +1135,8 @@ def map_point_rows(out):
     assert np.array_equal(d_best.cpu().numpy(), h_best)
     out["checked"] = "the device's table and winners equal the host form's bit for bit (%d descriptor rows written)" % int((h_best >= 0).sum())
 
-    def loops(fn):
-        fn()
-        gc.collect()
-        gc.disable()  # the cyclic collector is off inside the window, as in the standard timeit module
-        try:
-            t = []
-            for _ in range(REPS):
-                t0 = time.perf_counter()
-                fn()
-                t.append((time.perf_counter() - t0) * 1e3)
-        finally:
-            gc.enable()
-        return round(sum(t) / REPS, 4), round(max(t), 4)
 
-    a_rows, a_worst, b_wall, b_worst, c_gpu = [], [], [], [], []
-    for _ in range(REPEATS):
-        m, w = loops(host_loop)
-        a_rows.append(m); a_worst.append(w)
-        m, w = loops(device_loop)
-        b_wall.append(m); b_worst.append(w)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(st)
-        for _ in range(REPS):
-            enqueue()
-        e1.record(st)
-        st.synchronize()
-        c_gpu.append(round(e0.elapsed_time(e1) / REPS, 4))
+    ((a_rows, a_worst), (b_wall, b_worst)), (c_gpu,) = interleaved(REPEATS, REPS, st, [host_loop, device_loop], [enqueue])
     rows = out["rows"]
     rows["(a) MapPointUpdate.h on one host thread + upload of the %d rows + one synchronise, wall time" % n_upd] = {"ms_per_repeat": a_rows, "slowest_loop_ms": a_worst}
     rows["(b) upload of the observation lists + orbfe_enqueue_update_map_points + status download + one synchronise, wall time"] = {
@@ -1253,7 +1149,6 @@ def map_point_rows(out):
 def create_new_map_points_rows(out):
     """Rows of --create-new-map-points; arguments prepared once."""
     import ctypes as C
-    import gc
     import subprocess
     import tempfile
     import torch
@@ -1261,7 +1156,6 @@ def create_new_map_points_rows(out):
     from tests import triangulate_scenes as NS
     from tests import triangulation_scenes as S
     dev = torch.device("cuda:0")
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
     N, K, REPS, REPEATS, ROWS, MBF = 2000, 20, 10, 5, 8000, 40.0
     ctx = api.Context(width=640, height=480, nfeatures=2000, fx=S.FX, fy=S.FY, cx=S.CX, cy=S.CY, bf=MBF)
     t = ctx.tables()
@@ -1382,37 +1276,15 @@ def create_new_map_points_rows(out):
     out["checked"] = "both forms create the same %d points bit for bit: codes, positions, d_new, table rows, row counter, has_mp of all %d keyframes" % (total, K + 1)
     out["points_created"] = total
 
-    def loops(fn):
-        fn()
-        gc.collect()
-        gc.disable()  # the cyclic collector is off inside the window, as in the standard timeit module
-        try:
-            ts = []
-            for _ in range(REPS):
-                t0 = time.perf_counter()
-                fn()
-                ts.append((time.perf_counter() - t0) * 1e3)
-        finally:
-            gc.enable()
-        return round(sum(ts) / REPS, 4), round(max(ts), 4)
 
-    a_wall, a_worst, b_wall, b_worst, c_gpu = [], [], [], [], []
     pairs_of_0 = int(small_np[0, :4].view(np.int32)[0])
-    for _ in range(REPEATS):
-        m, w = loops(todays_loop)
-        a_wall.append(m); a_worst.append(w)
-        m, w = loops(queued_loop)
-        b_wall.append(m); b_worst.append(w)
+
+    def neighbour_0():
         with torch.cuda.stream(st):
             reset()
             search(0)                                                      # leaves neighbour 0's pairs and count in place
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(st)
-        for _ in range(REPS):
-            triangulate(0)
-        e1.record(st)
-        st.synchronize()
-        c_gpu.append(round(e0.elapsed_time(e1) / REPS, 4))
+
+    ((a_wall, a_worst), (b_wall, b_worst)), (c_gpu,) = interleaved(REPEATS, REPS, st, [todays_loop, queued_loop], [lambda: triangulate(0)], before=neighbour_0)
     rows = out["rows"]
     rows["(a) today's loop: %d x (enqueue search + download of count and pairs + synchronise + Triangulate.h on one host thread + two has_mp patches queued), wall time" % K] = {
         "ms_per_repeat": a_wall, "slowest_loop_ms": a_worst}
@@ -1426,14 +1298,12 @@ def create_new_map_points_rows(out):
 def initializer_rows(out):
     """Rows of --initializer; arguments prepared once."""
     import ctypes as C
-    import gc
     import subprocess
     import tempfile
     import torch
     from orbslam2_amd import api
     from tests import initializer_scenes as S
     dev = torch.device("cuda:0")
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
     N, ITER, REPS, REPEATS = 500, 200, 10, 5
     p = S.scene("general", N, ITER)
     n1, n2 = len(p["keys1"]), len(p["keys2"])
@@ -1502,33 +1372,10 @@ def initializer_rows(out):
     out["checked"] = "all four forms agree bit for bit: both matrices, scores, winners %s, inlier flags (%d H, %d F), every hypothesis's score" % (
         ho[1]["best"].tolist(), int(ho[1]["nin"][0]), int(ho[1]["nin"][1]))
 
-    def loops(fn):
-        fn()
-        gc.collect()
-        gc.disable()  # the cyclic collector is off inside the window, as in the standard timeit module
-        try:
-            ts = []
-            for _ in range(REPS):
-                t0 = time.perf_counter()
-                fn()
-                ts.append((time.perf_counter() - t0) * 1e3)
-        finally:
-            gc.enable()
-        return round(sum(ts) / REPS, 4), round(max(ts), 4)
 
     forms = [("a", lambda: host_form(1)), ("b", lambda: host_form(2)), ("c", device_form), ("d", sync_form)]
-    wall, worst, e_gpu = {k: [] for k, _ in forms}, {k: [] for k, _ in forms}, []
-    for _ in range(REPEATS):
-        for k, fn in forms:
-            m, w = loops(fn)
-            wall[k].append(m); worst[k].append(w)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(st)
-        for _ in range(REPS):
-            enqueue()
-        e1.record(st)
-        st.synchronize()
-        e_gpu.append(round(e0.elapsed_time(e1) / REPS, 4))
+    timed, (e_gpu,) = interleaved(REPEATS, REPS, st, [fn for _, fn in forms], [enqueue])
+    wall, worst = {k: t[0] for (k, _), t in zip(forms, timed)}, {k: t[1] for (k, _), t in zip(forms, timed)}
     rows = out["rows"]
     names = {"a": "(a) Initializer.h on one host thread (g++ -O2), wall time", "b": "(b) Initializer.h on two host threads, H and F as the reference splits them, wall time",
              "c": "(c) orbfe_enqueue_find_homography_fundamental on resident inputs + download of matrices, scores, winners, counts and flags + one synchronise, wall time",
@@ -1680,15 +1527,15 @@ def main():
             C.c_float(7.0), 0, 1, P(a_out), C.byref(a_nm))  # numpy's .ctypes.data_as costs ~1.5 us per array: outside the timed call
     fn = ctx2.L.orbfe_search_by_projection_last
 
-    def raw_call():
+    def direct_call():
         assert fn(*args) == 0
 
     ref_m, _ = ctx2.search_by_projection_last(v_dev, fs["T_cur"], fs["T_last"], fs["pos"], fs["desc"], fs["valid"], fs["obs"], fs["octave"],
                                               fs["angle"], fs["has"], 7.0, False, True)
-    raw_call()
+    direct_call()
     assert np.array_equal(a_out[: v_dev.n], ref_m)
     out["rows"]["SearchByProjection(Frame, LastFrame), device-resident, C ABI called directly [row 14]"] = {
-        "gpu_ms": round(timeit(raw_call, 200), 4),
+        "gpu_ms": round(timeit(direct_call, 200), 4),
         "note": "inside the call (ORBFE_HOST_TRACE=1): projection of the points 0.006, upload + kernel + download 0.062, replay 0.007 ms"}
     resident_async_rows(ctx2, out, fs, fb, fk, fur, v_dev, {"args": args, "out": a_out})
     if resident_only:
