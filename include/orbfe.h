@@ -1014,8 +1014,8 @@ int orbfe_enqueue_triangulate_pairs(orbfe_context *ctx,
         int patch_has_mp, int32_t *d_status /* [1] */, void *stream);
 /* ---- monocular initialisation: Initializer::FindHomography + Initializer::FindFundamental (orbfe_initializer_device.hip),
  * src/Initializer.cc:123-467, for one frame pair in one call: every RANSAC hypothesis of both models.  The two std::threads of
- * Initializer::Initialize (:103-108) become one call; the RH test (:111-117) on the two fetched scores and ReconstructH / ReconstructF /
- * CheckRT / DecomposeE (:469-930) stay the caller's, as does drawing mvSets (:77-96: DUtils::Random is glibc rand(), process state) --
+ * Initializer::Initialize (:103-108) become one call; the RH test (:111-117) and ReconstructH / ReconstructF / CheckRT / DecomposeE
+ * (:469-930) are orbfe_enqueue_reconstruct_initial below; the caller's are drawing mvSets (:77-96: DUtils::Random is glibc rand(), process state) --
  * mvSets is an INPUT -- and Normalize (:748-794), whose sequential float sums over a frame's keypoints are their own definition: the
  * host passes (meanX, meanY, sX, sY) of each frame (ORB_SLAM2::NormalizeKeys in orbslam2_amd/host/Initializer.h is the literal form).
  * The contract of the enqueue calls above holds: asynchronous on `stream` (NULL: the context's stream), nothing waits for the GPU,
@@ -1082,6 +1082,86 @@ int orbfe_find_homography_fundamental(orbfe_context *ctx, const orbfe_keypoint *
         const int32_t *matches12 /* [n1] */, const int32_t *sets /* [iterations][8] */, int iterations, float sigma,
         float *H21, float *F21, float *score, int32_t *best, uint8_t *inliers_h, uint8_t *inliers_f, int32_t *ninliers, float *all_scores,
         int32_t *n_matches);
+/* ---- monocular initialisation, the stage behind the RANSAC: Initializer::ReconstructF / ReconstructH with DecomposeE, CheckRT and
+ * Triangulate (orbfe_reconstruct_device.hip), src/Initializer.cc:469-746, :797-928, and the RH test of Initialize (:111-117), on the
+ * outputs of orbfe_enqueue_find_homography_fundamental WHERE THEY LIE in HBM: search_for_initialization -> find_homography_fundamental
+ * -> reconstruct_initial is one stream and one synchronise.  The contract of the enqueue calls above holds: asynchronous on `stream`
+ * (NULL: the context's stream), nothing waits for the GPU, nothing is read from host memory on the stream (K is read before the call
+ * returns and travels as kernel arguments).  The hypothesis records, the per-(hypothesis, match) cosines and, without d_codes, the
+ * codes live in the context's scratch: queue the calls of one context on one stream.  One memset of d_status and three launches: one
+ * wave for the RH decision and the 4 or 8 motion hypotheses, one lane per (match, hypothesis) for CheckRT, one workgroup for the
+ * counts, the sorted cosine, the count rules and the chosen hypothesis's points.
+ *
+ * Inputs (device): d_keys1_un[n1], d_keys2_un[n2], d_pairs[N][2] as in the call above; d_H21[9], d_F21[9], d_score[2], d_best[2],
+ * d_inliers_h[N], d_inliers_f[N] as that call wrote them (all required).  Host values: K[4] = fx, fy, cx, cy; sigma; min_triangulated
+ * (the reference passes 50); model: -1 applies the rule of :111-117 on the device (RH = SH / (SH + SF) in float, H when RH > 0.40),
+ * 0 forces H, 1 forces F.
+ * Outputs (device):
+ *   d_model[1]             0 = H, 1 = F
+ *   d_hyp_R[8][9], d_hyp_t[8][3]   the motion hypotheses in the reference's order: F has 4 rows, (R1, t), (R2, t), (R1, -t), (R2, -t);
+ *                          H has 8, vR / vt of :618-685.  Rows past the model's count, and all rows under results 1 and 2, are untouched.
+ *   d_ngood[8]             nGood of CheckRT per hypothesis; 0 past the model's count and under results 1 and 2
+ *   d_cos_parallax[8]      vCosParallax[min(50, size - 1)] after the sort, or 2.0f where nGood == 0
+ *   d_result[1]            0 a hypothesis is chosen under the count rules; 1 the model has no RANSAC winner (d_best < 0); 2
+ *                          d1 / d2 < 1.00001 || d2 / d3 < 1.00001 (:596); 3 the count rules refuse
+ *   d_choice[1]            the chosen hypothesis, or -1
+ *   d_R21[9], d_t21[3]     the chosen motion; untouched without one
+ *   d_p3d[n1][3], d_triangulated[n1]   vP3D / vbTriangulated of the chosen hypothesis, indexed by the first frame's keypoint: all n1
+ *                          entries are written, entries CheckRT did not write hold 0, and without a choice everything holds 0.  The
+ *                          first indices of d_pairs are distinct, as mvMatches12 (:50-62) makes them.
+ *   d_codes[8][N]          optional (may be NULL): which way CheckRT went per (hypothesis, match): 0 not an inlier (or no such
+ *                          hypothesis, or a faulty pair), 1 non-finite point (:840), 2 depth in camera 1 (:856), 3 depth in camera 2
+ *                          (:862), 4 error 1 (:873), 5 error 2 (:884), 6 counted but parallax too low to set vbGood, 7 counted and
+ *                          triangulated
+ *   d_status[1]
+ * The count rules are the reference's, with N the number of set inlier flags of the model, counted by the call.  F (:498-566):
+ * maxGood, nMinGood = max((int)(0.9 * N), min_triangulated), nsimilar against 0.7 * maxGood in double, and the choice is the FIRST
+ * hypothesis whose count equals maxGood (the else-if chain never looks at a later one).  H (:688-720): the running best and second
+ * best in hypothesis order and all of `secondBestGood < 0.75 * bestGood && bestGood > minTriangulated && bestGood > 0.9 * N`.
+ * NOT in the call: the parallax term, `parallax > minParallax` for F and `bestParallax >= minParallax` for H with parallax =
+ * acos(cos) * 180 / CV_PI.  acos is the platform's libm in the reference; the caller applies ORB_SLAM2::ReconstructAccept
+ * (orbslam2_amd/host/Initializer.h) to the one fetched float d_cos_parallax[choice].
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL context, input, K or output other than d_codes; N < 1 or
+ * > ORBFE_INITIALIZER_MAX_MATCHES; n1 or n2 negative or > ORBFE_INITIALIZER_MAX_KEYS; sigma, fx or fy not > 0; min_triangulated < 0;
+ * model outside -1 .. 1.  d_status = ORBFE_ERR_INVALID for a pair index outside [0, n1) / [0, n2), checked before it becomes an
+ * address: that match is code 0 in every hypothesis.  Nothing is written outside the outputs.
+ *
+ * Arithmetic (contract Q4; the OpenCV steps as DESIGN.md section 4m states them, OPENCV-4.5.5-SEMANTICS; the same operation order in
+ * tests/reconstruct_model.py, orbslam2_amd/host/Initializer.h and the kernels, which agree bit for bit):
+ *   K.t() * F21 * K, invK * H21 * K, u * W * vt, U * tp, K * [R|t], R.t() * t and R * p + t are cv::Mat products under the rule above
+ *   orbfe_enqueue_triangulate_pairs: per element a double sum over k in index order (every k, zeros of K included), a `+ t` term added
+ *   in double, rounded once, left to right.  A MatExpr scale is the gemm's alpha, applied in double to the sum before the one
+ *   rounding: s * U * Rp = gemm(U, Rp, alpha = s), then * Vt; -R.t() * t = gemm(R.t(), t, alpha = -1).  K.inv() is the closed 3 x 3
+ *   form of the call above; cv::determinant of a 3 x 3 float matrix is its double expression d; s = (float)(det(U) * det(Vt)).
+ *   The two 3 x 3 SVDs (:587, :911) are the Jacobi of the call above's rank-2 step: w[i] = (float)W[i], u[k][i] = At[i][k] *
+ *   (float)(1 / W[i]), 0 when W[i] <= FLT_MIN.  t = u.col(2) of an essential matrix is the normalised rotated column of rounding size.
+ *   t / cv::norm(t) and x3D.rowRange(0, 3) / x3D.at<float>(3) are scales by (float)(1.0 / d), the norm a double; there is no zero
+ *   test, a zero fourth component gives inf / NaN and code 1.  d1 / d2 is a float divide compared in double; aux1 .. cphi (:607-652)
+ *   are float, left to right, with a float sqrt; tp *= d is a float multiply per element.  vn is never read and is not computed.
+ *   The rows of Triangulate's A are x * P.row(2) - P.row(0) in float, the product rounded and then the difference; vt.row(3) is the
+ *   null vector of orbfe_enqueue_triangulate_pairs, the same code.  CheckRT is literal: dist = (float)norm, cosParallax =
+ *   (float)(dot / (double)(dist1 * dist2)) with a double dot, invZ = (float)(1.0 / (double)z), the reprojections float, left to
+ *   right, th2 = (float)(4.0 * (double)(sigma * sigma)), the comparisons against 0.99998 in double.
+ *   The sorted cosine: the order of the floats, -0 before +0 and any NaN after every number (the reference hands NaN to std::sort).
+ *   Every stored float holds a NaN as 0x7fc00000. */
+int orbfe_enqueue_reconstruct_initial(orbfe_context *ctx,
+        const orbfe_keypoint *d_keys1_un, int n1, const orbfe_keypoint *d_keys2_un, int n2, const int32_t *d_pairs /* [N][2] */, int N,
+        const float *d_H21 /* [9] */, const float *d_F21 /* [9] */, const float *d_score /* [2] */, const int32_t *d_best /* [2] */,
+        const uint8_t *d_inliers_h /* [N] */, const uint8_t *d_inliers_f /* [N] */,
+        const float K[4] /* HOST: fx, fy, cx, cy */, float sigma, int min_triangulated, int model,
+        int32_t *d_model /* [1] */, float *d_hyp_R /* [8][9] */, float *d_hyp_t /* [8][3] */, int32_t *d_ngood /* [8] */,
+        float *d_cos_parallax /* [8] */, int32_t *d_result /* [1] */, int32_t *d_choice /* [1] */, float *d_R21 /* [9] */, float *d_t21 /* [3] */,
+        float *d_p3d /* [n1][3] */, uint8_t *d_triangulated /* [n1] */, uint8_t *d_codes /* [8][N] or NULL */, int32_t *d_status /* [1] */,
+        void *stream);
+/* The same from host arrays, synchronous on the context's stream: uploads, queues the call above, downloads and applies
+ * ORB_SLAM2::ReconstructAccept with min_parallax (the reference passes 1.0): *ok = the reference's bool.  Outputs mirror the device
+ * ones; what the call leaves untouched keeps the caller's values; codes may be NULL.  Returns ORBFE_ERR_INVALID as the call above
+ * does, and also -- after the outputs are written -- when the device reported a faulty pair index. */
+int orbfe_reconstruct_initial(orbfe_context *ctx, const orbfe_keypoint *keys1_un, int n1, const orbfe_keypoint *keys2_un, int n2,
+        const int32_t *pairs /* [N][2] */, int N, const float *H21, const float *F21, const float *score, const int32_t *best,
+        const uint8_t *inliers_h, const uint8_t *inliers_f, const float K[4], float sigma, float min_parallax, int min_triangulated, int model,
+        int32_t *out_model, float *hyp_R, float *hyp_t, int32_t *ngood, float *cos_parallax, int32_t *result, int32_t *choice,
+        float *R21, float *t21, float *p3d, uint8_t *triangulated, uint8_t *codes, int *ok);
 /* KeyFrameDatabase::DetectLoopCandidates(KeyFrame *pKF, float minScore) (src/KeyFrameDatabase.cc:73-194; LoopClosing::DetectLoop,
  * src/LoopClosing.cc:131).  connected[k] != 0 marks the keyframes of pKF->GetConnectedKeyFrames() (may be NULL: none); covisibility
  * lists as for the relocalisation query.  Stateless: mLoopScore is only read for keyframes scored by the same call. */

@@ -46,6 +46,7 @@ EXPORTS = [
     "orbfe_enqueue_update_map_points",
     "orbfe_enqueue_triangulate_pairs",
     "orbfe_enqueue_find_homography_fundamental", "orbfe_find_homography_fundamental",
+    "orbfe_enqueue_reconstruct_initial", "orbfe_reconstruct_initial",
 ]
 NUM_STAGES = 8
 STAGE_NAMES = ["ingest", "pyramid", "blur", "fast", "octree", "describe", "stereo_match", "stereo_median"]  # orbfe_stage_name()
@@ -298,6 +299,10 @@ def load():
     L.orbfe_enqueue_find_homography_fundamental.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_float] + [vp] * 10
     L.orbfe_find_homography_fundamental.restype = C.c_int
     L.orbfe_find_homography_fundamental.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_float] + [vp] * 9
+    L.orbfe_enqueue_reconstruct_initial.restype = C.c_int
+    L.orbfe_enqueue_reconstruct_initial.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int] + [vp] * 7 + [C.c_float, C.c_int, C.c_int] + [vp] * 14
+    L.orbfe_reconstruct_initial.restype = C.c_int
+    L.orbfe_reconstruct_initial.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int] + [vp] * 7 + [C.c_float, C.c_float, C.c_int, C.c_int] + [vp] * 13
     L.orbfe_enqueue_update_map_points.restype = C.c_int
     L.orbfe_enqueue_update_map_points.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int] + [vp] * 8
     _lib = L
@@ -306,6 +311,14 @@ def load():
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def reconstruct_accept(model, cos_parallax, min_parallax):
+    """ORB_SLAM2::ReconstructAccept (orbslam2_amd/host/Initializer.h): the parallax test of ReconstructF / ReconstructH on the chosen
+    hypothesis's cosine, the one comparison enqueue_reconstruct_initial leaves to the host.  2.0 stands for nGood == 0."""
+    f32 = np.float32
+    parallax = f32(0) if cos_parallax == 2.0 else f32(np.float64(f32(np.arccos(f32(cos_parallax))) * f32(180)) / np.float64(np.pi))
+    return bool(parallax >= f32(min_parallax)) if model == 0 else bool(parallax > f32(min_parallax))
 
 
 class Context:
@@ -841,6 +854,47 @@ class Context:
                                                              _p(score), _p(best), _p(ih), _p(jf), _p(nin), _p(scores), C.byref(n)))
         return dict(H21=H.reshape(3, 3), F21=F.reshape(3, 3), score=score, best=best, inliers_h=ih[:n.value], inliers_f=jf[:n.value], ninliers=nin,
                     all_scores=scores, n_matches=n.value)
+
+    def enqueue_reconstruct_initial(self, d_keys1_un, n1, d_keys2_un, n2, d_pairs, n_matches, d_H21, d_F21, d_score, d_best, d_inliers_h, d_inliers_f, K,
+                                    sigma, d_model, d_hyp_R, d_hyp_t, d_ngood, d_cos_parallax, d_result, d_choice, d_R21, d_t21, d_p3d, d_triangulated,
+                                    d_status, d_codes=0, min_triangulated=50, model=-1, stream=0):
+        """Initializer::ReconstructF / ReconstructH (with DecomposeE and CheckRT) on the outputs of enqueue_find_homography_fundamental
+        where they lie in HBM, asynchronous on `stream`.  K = (fx, fy, cx, cy) on the host (None passes as NULL), read before the call
+        returns; model -1 takes the RH decision on the device, 0 / 1 force H / F.  d_model[1], d_hyp_R[8][9], d_hyp_t[8][3], d_ngood[8],
+        d_cos_parallax[8], d_result[1] (0 chosen, 1 no RANSAC winner, 2 the singular-value test, 3 the count rules refuse), d_choice[1],
+        d_R21[9], d_t21[3], d_p3d[n1][3], d_triangulated[n1], d_status[1]; optional d_codes[8][n_matches].  The parallax test stays
+        with the caller: reconstruct_accept(model, cos_parallax[choice], min_parallax).  The scratch is the context's: queue the calls
+        of one context on one stream."""
+        v = C.c_void_p
+        k = None if K is None else (C.c_float * 4)(*[float(x) for x in K])
+        self._check(self.L.orbfe_enqueue_reconstruct_initial(
+            self.h, v(d_keys1_un or None), n1, v(d_keys2_un or None), n2, v(d_pairs or None), n_matches, v(d_H21 or None), v(d_F21 or None),
+            v(d_score or None), v(d_best or None), v(d_inliers_h or None), v(d_inliers_f or None), k, sigma, min_triangulated, model, v(d_model or None),
+            v(d_hyp_R or None), v(d_hyp_t or None), v(d_ngood or None), v(d_cos_parallax or None), v(d_result or None), v(d_choice or None),
+            v(d_R21 or None), v(d_t21 or None), v(d_p3d or None), v(d_triangulated or None), v(d_codes or None), v(d_status or None), v(stream or None)))
+
+    def reconstruct_initial(self, keys1_un, keys2_un, pairs, H21, F21, score, best, inliers_h, inliers_f, K, sigma=1.0, min_parallax=1.0,
+                            min_triangulated=50, model=-1, codes=True):
+        """The same from host arrays, synchronous: pairs int32[N][2] (mvMatches12) and the RANSAC call's outputs.  Returns dict(ok (the
+        reference's bool, the parallax test applied with min_parallax), model, hyp_R[8][9], hyp_t[8][3] (zeros where untouched), ngood[8],
+        cos_parallax[8], result, choice, R21 (3x3), t21 (zeros without a choice), p3d[n1][3], triangulated[n1], codes[8][N] or None)."""
+        k1, k2 = np.ascontiguousarray(keys1_un, KP_DTYPE), np.ascontiguousarray(keys2_un, KP_DTYPE)
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        f32 = lambda a, n: np.ascontiguousarray(a, np.float32).reshape(n)
+        H, F, sc, bs = f32(H21, 9), f32(F21, 9), f32(score, 2), np.ascontiguousarray(best, np.int32).reshape(2)
+        ih, jf = np.ascontiguousarray(inliers_h, np.uint8), np.ascontiguousarray(inliers_f, np.uint8)
+        assert len(ih) == len(pr) and len(jf) == len(pr)
+        kk = f32(K, 4)
+        hyp_R, hyp_t, R21, t21 = np.zeros((8, 9), np.float32), np.zeros((8, 3), np.float32), np.zeros(9, np.float32), np.zeros(3, np.float32)
+        ngood, cosp = np.zeros(8, np.int32), np.zeros(8, np.float32)
+        p3d, tri = np.zeros((max(len(k1), 1), 3), np.float32), np.zeros(max(len(k1), 1), np.uint8)
+        cd = np.zeros((8, len(pr)), np.uint8) if codes else None
+        m, res, ch, ok = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int(0)
+        self._check(self.L.orbfe_reconstruct_initial(self.h, _p(k1), len(k1), _p(k2), len(k2), _p(pr), len(pr), _p(H), _p(F), _p(sc), _p(bs), _p(ih), _p(jf), _p(kk),
+                                                     sigma, min_parallax, min_triangulated, model, C.byref(m), _p(hyp_R), _p(hyp_t), _p(ngood), _p(cosp), C.byref(res),
+                                                     C.byref(ch), _p(R21), _p(t21), _p(p3d), _p(tri), None if cd is None else _p(cd), C.byref(ok)))
+        return dict(ok=bool(ok.value), model=m.value, hyp_R=hyp_R, hyp_t=hyp_t, ngood=ngood, cos_parallax=cosp, result=res.value, choice=ch.value,
+                    R21=R21.reshape(3, 3), t21=t21, p3d=p3d[:len(k1)], triangulated=tri[:len(k1)], codes=cd)
 
     def enqueue_search_by_sim3(self, kf1, T1w, d_pts1, kf2, T2w, d_pts2, s12, R12, t12, th, d_match12, d_n_found, d_status, stream=0):
         """ORBmatcher::SearchBySim3 on two device-resident keyframes (GridKeyframe records on the host, device pointers inside),

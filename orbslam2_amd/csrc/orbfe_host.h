@@ -93,6 +93,7 @@ struct orbfe_context {
     orbfe_bow_state *bow = nullptr;
     orbfe_pose_state *pose = nullptr;
     DevBuf init_scratch, init_sync; // orbfe_enqueue_find_homography_fundamental's per-hypothesis scratch; the synchronous form's arrays
+    DevBuf recon_scratch, recon_sync; // the same of orbfe_enqueue_reconstruct_initial: its own, so that growing one never frees what the call before it still reads
     hipError_t chain_err = hipSuccess; // a launcher's refusal inside run_chain (enqueue_batch reports it)
     char err[512];
 };

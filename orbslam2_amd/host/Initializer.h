@@ -6,14 +6,18 @@
 //     formulation next to the kernel's wave-wide one, and
 //   - the host leg of tools/bench_matchers.py --initializer.
 // Compile with -ffp-contract=off: every float operation below is rounded once (contract Q4), as in the kernel.
-// Not here: drawing mvSets (an input), the RH test, ReconstructH / ReconstructF / CheckRT / DecomposeE.
+// Below them, ReconstructInitial is ReconstructF / ReconstructH / DecomposeE / CheckRT / Triangulate (:469-746, :797-928) with the RH test
+// (:111-117) on the arrays of orbfe_enqueue_reconstruct_initial, and ReconstructAccept the parallax comparison that stays on the host.
+// Not here: drawing mvSets (an input).
 #pragma once
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <utility>
+#include <vector>
 
 #include "../../include/orbfe.h"
 
@@ -320,6 +324,324 @@ inline int FindHomographyFundamental(const orbfe_keypoint *keys1, int n1, const 
         }
         if (ninliers) ninliers[model] = count;
         if (best_it[model] >= 0) std::memcpy(model == 0 ? H21 : F21, best_mat[model], 9 * sizeof(float));
+    }
+    return status;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// ReconstructF / ReconstructH / DecomposeE / CheckRT / Triangulate (:469-746, :797-928) on the flat arrays of
+// orbfe_enqueue_reconstruct_initial (include/orbfe.h): the same arguments, every pointer a HOST pointer.
+
+// a cv::Mat product a[R][Kk] * b[Kk][C]: per element a double sum over k in index order, times *alpha when given (a MatExpr scale is
+// the gemm's alpha), plus (double)plus[r][c] when given, rounded once
+inline void ReconstructMat(const float *a, const float *b, int R, int Kk, int C, float *out, const double *alpha = nullptr, const float *plus = nullptr)
+{
+    for (int r = 0; r < R; r++)
+        for (int c = 0; c < C; c++) {
+            double s = 0;
+            for (int k = 0; k < Kk; k++) s += (double)a[Kk * r + k] * b[C * k + c];
+            if (alpha) s = *alpha * s;
+            if (plus) s += (double)plus[C * r + c];
+            out[C * r + c] = (float)s;
+        }
+}
+
+// cv::determinant of a 3x3 float matrix: the double expression d of InitializerInv3
+inline double ReconstructDet3(const float m[9])
+{
+    const double m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5], m20 = m[6], m21 = m[7], m22 = m[8];
+    return m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20);
+}
+
+// cv::SVD::compute of a 3x3 float matrix: the Jacobi on its columns; w[i] = (float)W[i], u[k][i] = At[i][k] * (float)(1 / W[i])
+inline void ReconstructSvd3(const float A[9], float u[9], float w[3], float vt[9])
+{
+    float At[3 * kInitializerAStride], Vt[3 * kInitializerVStride];
+    double W[3];
+    for (int i = 0; i < 3; i++)
+        for (int k = 0; k < 3; k++) At[i * kInitializerAStride + k] = A[3 * k + i];
+    InitializerJacobi(At, Vt, W, 3, 3);
+    for (int i = 0; i < 3; i++) {
+        const float s = W[i] > (double)FLT_MIN ? (float)(1 / W[i]) : 0.f;
+        w[i] = (float)W[i];
+        for (int k = 0; k < 3; k++) { u[3 * k + i] = At[i * kInitializerAStride + k] * s; vt[3 * i + k] = Vt[i * kInitializerVStride + k]; }
+    }
+}
+
+// t / cv::norm(t): a scale by (float)(1.0 / norm); no zero test
+inline void ReconstructUnit(float t[3])
+{
+    const double d = std::sqrt((double)t[0] * t[0] + (double)t[1] * t[1] + (double)t[2] * t[2]);
+    const float a = (float)(1.0 / d);
+    for (int k = 0; k < 3; k++) t[k] = t[k] * a;
+}
+
+inline void ReconstructK(const float K4[4], float K[9])
+{
+    for (int k = 0; k < 9; k++) K[k] = 0.f;
+    K[0] = K4[0]; K[4] = K4[1]; K[2] = K4[2]; K[5] = K4[3]; K[8] = 1.f;
+}
+
+// a NaN is stored with one bit pattern everywhere
+inline void ReconstructStore(float *dst, const float *src, int n)
+{
+    for (int k = 0; k < n; k++) dst[k] = InitializerStoredScore(src[k]);
+}
+
+// the order of the sorted cosines: that of the floats, -0 before +0, any NaN after every number
+inline uint32_t ReconstructOrderKey(float c)
+{
+    uint32_t b;
+    std::memcpy(&b, &c, 4);
+    if (c != c) return 0xFFFFFFFFu;
+    return (b >> 31) ? ~b : (b | 0x80000000u);
+}
+
+inline float ReconstructKeyValue(uint32_t key)
+{
+    uint32_t b = (key >> 31) ? (key & 0x7FFFFFFFu) : ~key;
+    if (key == 0xFFFFFFFFu) b = 0x7FC00000u;
+    float c;
+    std::memcpy(&c, &b, 4);
+    return c;
+}
+
+// DecomposeE on E21 = K.t() * F21 * K (:478-496, :908-928): the four hypotheses (R1, t), (R2, t), (R1, -t), (R2, -t)
+inline void ReconstructHypothesesF(const float F21[9], const float K[9], float vR[8][9], float vt[8][3])
+{
+    float Kt[9], tmp[9], E[9], u[9], w[3], vtm[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) Kt[3 * r + c] = K[3 * c + r];
+    InitializerMul3(Kt, F21, tmp);
+    InitializerMul3(tmp, K, E);
+    ReconstructSvd3(E, u, w, vtm);
+    float t[3] = {u[2], u[5], u[8]};
+    ReconstructUnit(t);
+    const float W[9] = {0, -1, 0, 1, 0, 0, 0, 0, 1}, Wt[9] = {0, 1, 0, -1, 0, 0, 0, 0, 1};
+    float R[2][9];
+    for (int which = 0; which < 2; which++) {
+        InitializerMul3(u, which ? Wt : W, tmp);
+        InitializerMul3(tmp, vtm, R[which]);
+        if (ReconstructDet3(R[which]) < 0)
+            for (int k = 0; k < 9; k++) R[which][k] = -R[which][k];
+    }
+    for (int h = 0; h < 4; h++) {
+        for (int k = 0; k < 9; k++) vR[h][k] = R[h & 1][k];
+        for (int k = 0; k < 3; k++) vt[h][k] = h < 2 ? t[k] : -t[k];
+    }
+}
+
+// The eight hypotheses of ReconstructH (:583-685).  Returns false under the test of :596.  vn is never read and is not computed.
+inline bool ReconstructHypothesesH(const float H21[9], const float K[9], float vR[8][9], float vt[8][3])
+{
+    float invK[9], tmp[9], A[9], U[9], w[3], Vt[9];
+    InitializerInv3(K, invK);
+    InitializerMul3(invK, H21, tmp);
+    InitializerMul3(tmp, K, A);
+    ReconstructSvd3(A, U, w, Vt);
+    const float s = (float)(ReconstructDet3(U) * ReconstructDet3(Vt));
+    const float d1 = w[0], d2 = w[1], d3 = w[2];
+    if (d1 / d2 < 1.00001 || d2 / d3 < 1.00001) return false;
+    const float aux1 = std::sqrt((d1 * d1 - d2 * d2) / (d1 * d1 - d3 * d3));
+    const float aux3 = std::sqrt((d2 * d2 - d3 * d3) / (d1 * d1 - d3 * d3));
+    const float x1[] = {aux1, aux1, -aux1, -aux1};
+    const float x3[] = {aux3, -aux3, aux3, -aux3};
+    const float aux_stheta = std::sqrt((d1 * d1 - d2 * d2) * (d2 * d2 - d3 * d3)) / ((d1 + d3) * d2);
+    const float ctheta = (d2 * d2 + d1 * d3) / ((d1 + d3) * d2);
+    const float stheta[] = {aux_stheta, -aux_stheta, -aux_stheta, aux_stheta};
+    const float aux_sphi = std::sqrt((d1 * d1 - d2 * d2) * (d2 * d2 - d3 * d3)) / ((d1 - d3) * d2);
+    const float cphi = (d1 * d3 - d2 * d2) / ((d1 - d3) * d2);
+    const float sphi[] = {aux_sphi, -aux_sphi, -aux_sphi, aux_sphi};
+    const double alpha = s;
+    for (int i = 0; i < 8; i++) {
+        float Rp[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tp[3];
+        if (i < 4) { // case d' = d2
+            Rp[0] = ctheta; Rp[2] = -stheta[i]; Rp[6] = stheta[i]; Rp[8] = ctheta;
+            tp[0] = x1[i]; tp[1] = 0; tp[2] = -x3[i];
+            for (int k = 0; k < 3; k++) tp[k] = tp[k] * (d1 - d3);
+        } else {     // case d' = -d2
+            Rp[0] = cphi; Rp[2] = sphi[i - 4]; Rp[4] = -1; Rp[6] = sphi[i - 4]; Rp[8] = -cphi;
+            tp[0] = x1[i - 4]; tp[1] = 0; tp[2] = x3[i - 4];
+            for (int k = 0; k < 3; k++) tp[k] = tp[k] * (d1 + d3);
+        }
+        ReconstructMat(U, Rp, 3, 3, 3, tmp, &alpha); // s * U * Rp: the scale is the gemm's alpha (the reading tagged in include/orbfe.h)
+        InitializerMul3(tmp, Vt, vR[i]);
+        ReconstructMat(U, tp, 3, 3, 1, vt[i]);
+        ReconstructUnit(vt[i]);
+    }
+    return true;
+}
+
+// P2 = K * [R|t] (3x4) and O2 = -R.t() * t of CheckRT (:819-825)
+inline void ReconstructCamera2(const float R[9], const float t[3], const float K[9], float P2[12], float O2[3])
+{
+    float Rt[12], Rtr[9];
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) { Rt[4 * r + c] = R[3 * r + c]; Rtr[3 * r + c] = R[3 * c + r]; }
+        Rt[4 * r + 3] = t[r];
+    }
+    ReconstructMat(K, Rt, 3, 3, 4, P2);
+    const double minus = -1.0;
+    ReconstructMat(Rtr, t, 3, 3, 1, O2, &minus);
+}
+
+// One iteration of CheckRT's loop (:829-893) for an inlier match: the code (1..7 of orbfe_enqueue_reconstruct_initial), its cosine and point.
+inline int ReconstructCheckMatch(const float R[9], const float t[3], const float K4[4], const float P2[12], const float O2[3], float kp1x, float kp1y,
+                                 float kp2x, float kp2y, float th2, float &cosParallax, float p3dC1[3])
+{
+    const float fx = K4[0], fy = K4[1], cx = K4[2], cy = K4[3];
+    const float P1[12] = {fx, 0, cx, 0, 0, fy, cy, 0, 0, 0, 1, 0};
+    // Triangulate (:733-746)
+    float At[4 * kInitializerAStride], Vt[4 * kInitializerVStride];
+    double W[4];
+    for (int c = 0; c < 4; c++) {
+        At[c * kInitializerAStride + 0] = kp1x * P1[8 + c] - P1[c];
+        At[c * kInitializerAStride + 1] = kp1y * P1[8 + c] - P1[4 + c];
+        At[c * kInitializerAStride + 2] = kp2x * P2[8 + c] - P2[c];
+        At[c * kInitializerAStride + 3] = kp2y * P2[8 + c] - P2[4 + c];
+    }
+    InitializerJacobi(At, Vt, W, 4, 4);
+    const float *x3D = Vt + 3 * kInitializerVStride;
+    const float a = (float)(1.0 / x3D[3]);
+    for (int k = 0; k < 3; k++) p3dC1[k] = x3D[k] * a;
+    cosParallax = 0.f;
+    if (!std::isfinite(p3dC1[0]) || !std::isfinite(p3dC1[1]) || !std::isfinite(p3dC1[2])) return 1;
+    // Check parallax
+    float normal2[3];
+    double d1 = 0, d2 = 0, dot = 0;
+    for (int k = 0; k < 3; k++) {
+        normal2[k] = p3dC1[k] - O2[k];
+        d1 += (double)p3dC1[k] * p3dC1[k]; d2 += (double)normal2[k] * normal2[k]; dot += (double)p3dC1[k] * normal2[k];
+    }
+    const float dist1 = (float)std::sqrt(d1), dist2 = (float)std::sqrt(d2);
+    cosParallax = (float)(dot / (double)(dist1 * dist2));
+    // Check depth in front of first camera (only if enough parallax, as "infinite" points can easily go to negative depth)
+    if (p3dC1[2] <= 0 && cosParallax < 0.99998) return 2;
+    // Check depth in front of second camera
+    float p3dC2[3];
+    ReconstructMat(R, p3dC1, 3, 3, 1, p3dC2, nullptr, t);
+    if (p3dC2[2] <= 0 && cosParallax < 0.99998) return 3;
+    // Check reprojection error in first image
+    const float invZ1 = (float)(1.0 / p3dC1[2]);
+    const float im1x = fx * p3dC1[0] * invZ1 + cx, im1y = fy * p3dC1[1] * invZ1 + cy;
+    const float squareError1 = (im1x - kp1x) * (im1x - kp1x) + (im1y - kp1y) * (im1y - kp1y);
+    if (squareError1 > th2) return 4;
+    // Check reprojection error in second image
+    const float invZ2 = (float)(1.0 / p3dC2[2]);
+    const float im2x = fx * p3dC2[0] * invZ2 + cx, im2y = fy * p3dC2[1] * invZ2 + cy;
+    const float squareError2 = (im2x - kp2x) * (im2x - kp2x) + (im2y - kp2y) * (im2y - kp2y);
+    if (squareError2 > th2) return 5;
+    return cosParallax < 0.99998 ? 7 : 6;
+}
+
+// The parallax test of ReconstructF (:524) / ReconstructH (:720) on the chosen hypothesis's cosine: the one comparison that stays on
+// the host (acos is the platform's).  cos_parallax == 2 stands for nGood == 0, parallax = 0.
+inline bool ReconstructAccept(int model, float cos_parallax, float minParallax)
+{
+    float parallax = 0;
+    if (cos_parallax != 2.0f) parallax = (float)(std::acos(cos_parallax) * 180 / 3.1415926535897932384626433832795);
+    return model == 0 ? parallax >= minParallax : parallax > minParallax;
+}
+
+// Returns what the device reports in d_status (0, or ORBFE_ERR_INVALID for a pair index out of range), or ORBFE_ERR_INVALID for refused
+// arguments (then nothing is written).  codes [8][N] may be NULL; every other pointer is required.
+inline int ReconstructInitial(const orbfe_keypoint *keys1, int n1, const orbfe_keypoint *keys2, int n2, const int32_t *pairs, int N, const float *H21,
+                              const float *F21, const float *score, const int32_t *best, const uint8_t *inliers_h, const uint8_t *inliers_f, const float *K4,
+                              float sigma, int min_triangulated, int model, int32_t *out_model, float *hyp_R, float *hyp_t, int32_t *ngood, float *cos_parallax,
+                              int32_t *result, int32_t *choice, float *R21, float *t21, float *p3d, uint8_t *triangulated, uint8_t *codes)
+{
+    if (!keys1 || !keys2 || !pairs || !H21 || !F21 || !score || !best || !inliers_h || !inliers_f || !K4) return ORBFE_ERR_INVALID;
+    if (!out_model || !hyp_R || !hyp_t || !ngood || !cos_parallax || !result || !choice || !R21 || !t21 || !p3d || !triangulated) return ORBFE_ERR_INVALID;
+    if (N < 1 || N > ORBFE_INITIALIZER_MAX_MATCHES || n1 < 0 || n2 < 0 || n1 > ORBFE_INITIALIZER_MAX_KEYS || n2 > ORBFE_INITIALIZER_MAX_KEYS || !(sigma > 0) ||
+        !(K4[0] > 0) || !(K4[1] > 0) || min_triangulated < 0 || model < -1 || model > 1)
+        return ORBFE_ERR_INVALID;
+    int status = 0;
+    if (model == -1) { // :111-117
+        const float SH = score[0], SF = score[1];
+        const float RH = SH / (SH + SF);
+        model = RH > 0.40 ? 0 : 1;
+    }
+    *out_model = model;
+    const uint8_t *vbMatchesInliers = model == 0 ? inliers_h : inliers_f;
+    auto pair_ok = [&](int i) { return pairs[2 * i] >= 0 && pairs[2 * i] < n1 && pairs[2 * i + 1] >= 0 && pairs[2 * i + 1] < n2; };
+    int Ninl = 0;
+    for (int i = 0; i < N; i++) {
+        if (vbMatchesInliers[i]) Ninl++;
+        if (!pair_ok(i)) status = ORBFE_ERR_INVALID;
+    }
+    for (int h = 0; h < 8; h++) { ngood[h] = 0; cos_parallax[h] = 2.0f; }
+    if (codes) std::memset(codes, 0, 8 * (size_t)N);
+    for (int i = 0; i < n1; i++) { p3d[3 * i] = p3d[3 * i + 1] = p3d[3 * i + 2] = 0.f; triangulated[i] = 0; }
+    *choice = -1;
+    if (best[model] < 0) { *result = 1; return status; }
+    float K[9], vR[8][9], vt[8][3];
+    ReconstructK(K4, K);
+    int nhyp = 4;
+    if (model == 0) {
+        if (!ReconstructHypothesesH(H21, K, vR, vt)) { *result = 2; return status; }
+        nhyp = 8;
+    } else
+        ReconstructHypothesesF(F21, K, vR, vt);
+    const float th2 = (float)(4.0 * (sigma * sigma));
+    std::vector<uint32_t> vCosParallax;
+    for (int h = 0; h < nhyp; h++) {
+        ReconstructStore(hyp_R + 9 * h, vR[h], 9);
+        ReconstructStore(hyp_t + 3 * h, vt[h], 3);
+        float P2[12], O2[3];
+        ReconstructCamera2(vR[h], vt[h], K, P2, O2);
+        vCosParallax.clear();
+        int nGood = 0;
+        for (int i = 0; i < N; i++) {
+            if (!vbMatchesInliers[i] || !pair_ok(i)) continue;
+            const orbfe_keypoint &kp1 = keys1[pairs[2 * i]], &kp2 = keys2[pairs[2 * i + 1]];
+            float cosParallax, p3dC1[3];
+            const int code = ReconstructCheckMatch(vR[h], vt[h], K4, P2, O2, kp1.x, kp1.y, kp2.x, kp2.y, th2, cosParallax, p3dC1);
+            if (codes) codes[(size_t)h * N + i] = (uint8_t)code;
+            if (code < 6) continue;
+            vCosParallax.push_back(ReconstructOrderKey(cosParallax));
+            nGood++;
+        }
+        ngood[h] = nGood;
+        if (nGood > 0) {
+            std::sort(vCosParallax.begin(), vCosParallax.end());
+            const size_t idx = std::min(50, int(vCosParallax.size() - 1));
+            cos_parallax[h] = ReconstructKeyValue(vCosParallax[idx]);
+        }
+    }
+    int chosen = -1;
+    if (model == 1) { // :498-566
+        const int maxGood = std::max(ngood[0], std::max(ngood[1], std::max(ngood[2], ngood[3])));
+        const int nMinGood = std::max(static_cast<int>(0.9 * Ninl), min_triangulated);
+        int nsimilar = 0;
+        for (int h = 0; h < 4; h++)
+            if (ngood[h] > 0.7 * maxGood) nsimilar++;
+        if (!(maxGood < nMinGood || nsimilar > 1))
+            for (int h = 3; h >= 0; h--)
+                if (ngood[h] == maxGood) chosen = h; // the else-if chain never looks past the first
+    } else {          // :688-720
+        int bestGood = 0, secondBestGood = 0, bestSolutionIdx = -1;
+        for (int i = 0; i < 8; i++) {
+            if (ngood[i] > bestGood) { secondBestGood = bestGood; bestGood = ngood[i]; bestSolutionIdx = i; }
+            else if (ngood[i] > secondBestGood) secondBestGood = ngood[i];
+        }
+        if (secondBestGood < 0.75 * bestGood && bestGood > min_triangulated && bestGood > 0.9 * Ninl) chosen = bestSolutionIdx;
+    }
+    *choice = chosen;
+    if (chosen < 0) { *result = 3; return status; }
+    *result = 0;
+    ReconstructStore(R21, vR[chosen], 9);
+    ReconstructStore(t21, vt[chosen], 3);
+    float P2[12], O2[3];
+    ReconstructCamera2(vR[chosen], vt[chosen], K, P2, O2);
+    for (int i = 0; i < N; i++) {
+        if (!vbMatchesInliers[i] || !pair_ok(i)) continue;
+        const orbfe_keypoint &kp1 = keys1[pairs[2 * i]], &kp2 = keys2[pairs[2 * i + 1]];
+        float cosParallax, p3dC1[3];
+        const int code = ReconstructCheckMatch(vR[chosen], vt[chosen], K4, P2, O2, kp1.x, kp1.y, kp2.x, kp2.y, th2, cosParallax, p3dC1);
+        if (code < 6) continue;
+        float *dst = p3d + 3 * (size_t)pairs[2 * i];
+        dst[0] = p3dC1[0]; dst[1] = p3dC1[1]; dst[2] = p3dC1[2];
+        triangulated[pairs[2 * i]] = code == 7;
     }
     return status;
 }

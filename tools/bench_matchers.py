@@ -85,6 +85,14 @@ counts, codes and d_new of all neighbours, one of the table rows, and one synchr
 pairs, queued back to back, as GPU time between two events.  Both loops reset has_mp and the row counter inside the window.  (b)'s
 points are compared with (a)'s bit for bit.  Five repeats of each, interleaved; every repeat is the mean of 10 loops, its slowest loop
 beside it.
+
+    python3 tools/bench_matchers.py --reconstruct
+runs only the rows of Initializer's reconstruction stage (profiles/reconstruct_device.json) on the scene of --initializer (500 matches),
+fed with what the RANSAC call leaves: (a) ReconstructInitial of orbslam2_amd/host/Initializer.h on one host thread (g++ -O2); (b)
+orbfe_enqueue_reconstruct_initial on resident inputs with the download of every output and one synchronise; (c) orbfe_reconstruct_initial
+from host arrays; (d) the enqueue alone, queued back to back, as GPU time between two events; (e1) RANSAC and reconstruction queued on one
+stream with one synchronise against (e2) the RANSAC call, its downloads and a synchronise, then (c) on the fetched arrays.  All forms are
+compared bit for bit before anything is timed.  The same protocol: five interleaved repeats of 10 loops after a warm-up loop.
 """
 import json
 import os
@@ -1388,6 +1396,150 @@ def initializer_rows(out):
     ctx.close()
 
 
+def reconstruct_rows(out):
+    """Rows of --reconstruct; arguments prepared once.  The inputs are the RANSAC call's own outputs on the --initializer scene."""
+    import ctypes as C
+    import subprocess
+    import tempfile
+    import torch
+    from orbslam2_amd import api
+    from tests import initializer_scenes as S
+    dev = torch.device("cuda:0")
+    N, ITER, REPS, REPEATS = 500, 200, 10, 5
+    p = S.scene("general", N, ITER)
+    n1, n2 = len(p["keys1"]), len(p["keys2"])
+    out["scene"] = "%d matches between frames of %d and %d keypoints (tests/initializer_scenes.py, general depth), %d sets, sigma 1, min_triangulated 50, model by RH" % (
+        N, n1, n2, ITER)
+    ctx = api.Context(width=S.WIDTH, height=S.HEIGHT, nfeatures=1000, fx=S.FX, fy=S.FY, cx=S.CX, cy=S.CY, bf=40.0)
+    so = os.path.join(os.environ.get("BENCH_OUT") or tempfile.mkdtemp(), "reconstruct_host_shim.so")
+    subprocess.run(["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tools", "reconstruct_host_shim.cpp")], check=True)
+    host = C.CDLL(so).reconstruct_initial_host
+    host.restype = C.c_int
+    host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 12
+    P = lambda a: a.ctypes.data
+    keys1, keys2 = np.ascontiguousarray(p["keys1"]), np.ascontiguousarray(p["keys2"])
+    pairs, sets, m12 = np.ascontiguousarray(p["pairs"]), np.ascontiguousarray(p["sets"]), np.ascontiguousarray(p["matches12"])
+    norm1, norm2 = np.ascontiguousarray(p["norm1"]), np.ascontiguousarray(p["norm2"])
+    K = np.array([S.FX, S.FY, S.CX, S.CY], np.float32)
+    r = ctx.find_homography_fundamental(keys1, keys2, m12, sets, 1.0)      # the inputs of every form: what the RANSAC call leaves
+    H21, F21 = np.ascontiguousarray(r["H21"].reshape(-1)), np.ascontiguousarray(r["F21"].reshape(-1))
+    score, best, ih, jf = r["score"], r["best"], np.ascontiguousarray(r["inliers_h"]), np.ascontiguousarray(r["inliers_f"])
+    names = ("model", "hyp_R", "hyp_t", "ngood", "cos", "result", "choice", "R21", "t21", "p3d", "tri", "codes")
+
+    def outputs():
+        return dict(model=np.zeros(1, np.int32), hyp_R=np.zeros((8, 9), np.float32), hyp_t=np.zeros((8, 3), np.float32), ngood=np.zeros(8, np.int32),
+                    cos=np.zeros(8, np.float32), result=np.zeros(1, np.int32), choice=np.zeros(1, np.int32), R21=np.zeros(9, np.float32), t21=np.zeros(3, np.float32),
+                    p3d=np.zeros((n1, 3), np.float32), tri=np.zeros(n1, np.uint8), codes=np.zeros((8, N), np.uint8))
+
+    ho = outputs()
+
+    def host_form():
+        rc = host(P(keys1), n1, P(keys2), n2, P(pairs), N, P(H21), P(F21), P(score), P(best), P(ih), P(jf), P(K), 1.0, 50, -1, *[P(ho[k]) for k in names])
+        assert rc == 0
+
+    # (b): resident inputs; the small outputs are one block of floats: hyp_R [0, 72), hyp_t [72, 96), R21 [96, 105), t21 [105, 108), cos [108, 116), ngood [116, 124),
+    # model, result, choice, status [124, 128)
+    d_in = [up(keys1), up(keys2), up(pairs), up(sets)]
+    d_ransac = torch.zeros(32, dtype=torch.float32, device=dev)        # as --initializer lays it out
+    d_flags = torch.zeros(2 * N, dtype=torch.uint8, device=dev)
+    d_small = torch.zeros(128, dtype=torch.float32, device=dev)
+    d_p3d, d_tri, d_codes = torch.zeros(3 * n1, dtype=torch.float32, device=dev), torch.zeros(n1, dtype=torch.uint8, device=dev), torch.zeros(8 * N, dtype=torch.uint8, device=dev)
+    h_small, h_p3d = torch.zeros(128, dtype=torch.float32).pin_memory(), torch.zeros(3 * n1, dtype=torch.float32).pin_memory()
+    h_tri, h_codes, h_ransac = torch.zeros(n1, dtype=torch.uint8).pin_memory(), torch.zeros(8 * N, dtype=torch.uint8).pin_memory(), torch.zeros(32, dtype=torch.float32).pin_memory()
+    h_flags = torch.zeros(2 * N, dtype=torch.uint8).pin_memory()
+    st = torch.cuda.Stream()
+    rp, sp = d_ransac.data_ptr(), d_small.data_ptr()
+    torch.cuda.synchronize()
+
+    def enqueue_ransac():
+        ctx.enqueue_find_homography_fundamental(d_in[0].data_ptr(), n1, d_in[1].data_ptr(), n2, d_in[2].data_ptr(), N, d_in[3].data_ptr(), ITER, norm1, norm2, 1.0,
+                                                rp, rp + 36, rp + 72, rp + 80, rp + 96, d_inliers_h=d_flags.data_ptr(), d_inliers_f=d_flags.data_ptr() + N,
+                                                d_ninliers=rp + 88, stream=st.cuda_stream)
+
+    def enqueue():
+        ctx.enqueue_reconstruct_initial(d_in[0].data_ptr(), n1, d_in[1].data_ptr(), n2, d_in[2].data_ptr(), N, rp, rp + 36, rp + 72, rp + 80, d_flags.data_ptr(),
+                                        d_flags.data_ptr() + N, K, 1.0, sp + 4 * 124, sp, sp + 4 * 72, sp + 4 * 116, sp + 4 * 108, sp + 4 * 125, sp + 4 * 126, sp + 4 * 96,
+                                        sp + 4 * 105, d_p3d.data_ptr(), d_tri.data_ptr(), sp + 4 * 127, d_codes=d_codes.data_ptr(), min_triangulated=50, model=-1,
+                                        stream=st.cuda_stream)
+
+    def downloads():
+        h_small.copy_(d_small, non_blocking=True); h_p3d.copy_(d_p3d, non_blocking=True)
+        h_tri.copy_(d_tri, non_blocking=True); h_codes.copy_(d_codes, non_blocking=True)
+
+    def device_form():
+        with torch.cuda.stream(st):
+            enqueue()
+            downloads()
+            st.synchronize()
+
+    sync_out = {}
+
+    def sync_form():
+        sync_out["r"] = ctx.reconstruct_initial(keys1, keys2, pairs, H21, F21, score, best, ih, jf, K, 1.0, 1.0, 50, -1)
+
+    def one_stream():       # (e1): RANSAC and reconstruction queued together, one synchronise
+        with torch.cuda.stream(st):
+            enqueue_ransac()
+            enqueue()
+            downloads()
+            st.synchronize()
+
+    def round_trip():       # (e2): the RANSAC call, its download and synchronise, the host's look at the scores, then this call from host arrays
+        with torch.cuda.stream(st):
+            enqueue_ransac()
+            h_ransac.copy_(d_ransac, non_blocking=True)
+            h_flags.copy_(d_flags, non_blocking=True)
+            st.synchronize()
+        a, f = h_ransac.numpy(), h_flags.numpy()
+        sync_out["r2"] = ctx.reconstruct_initial(keys1, keys2, pairs, a[:9], a[9:18], a[18:20], a[20:22].view(np.int32), f[:N], f[N:], K, 1.0, 1.0, 50, -1)
+
+    with torch.cuda.stream(st):
+        enqueue_ransac()
+        st.synchronize()
+    host_form(); device_form(); sync_form(); one_stream()
+    small = h_small.numpy().copy()
+    got = dict(model=small[124:125].view(np.int32), hyp_R=small[:72], hyp_t=small[72:96], ngood=small[116:124].view(np.int32), cos=small[108:116],
+               result=small[125:126].view(np.int32), choice=small[126:127].view(np.int32), R21=small[96:105], t21=small[105:108], p3d=h_p3d.numpy(), tri=h_tri.numpy(),
+               codes=h_codes.numpy())
+    round_trip()
+    assert small[127:128].view(np.int32)[0] == 0
+    nh = 4 if ho["model"][0] == 1 else 8
+
+    def rows_of(d):
+        return dict(d, hyp_R=np.asarray(d["hyp_R"]).reshape(8, 9)[:nh], hyp_t=np.asarray(d["hyp_t"]).reshape(8, 3)[:nh])
+
+    forms_out = [("device call", got)]
+    for key in ("r", "r2"):
+        s_ = sync_out[key]
+        forms_out.append(("synchronous form" if key == "r" else "round trip", dict(
+            model=np.array([s_["model"]], np.int32), hyp_R=s_["hyp_R"], hyp_t=s_["hyp_t"], ngood=s_["ngood"], cos=s_["cos_parallax"], result=np.array([s_["result"]], np.int32),
+            choice=np.array([s_["choice"]], np.int32), R21=s_["R21"].reshape(-1), t21=s_["t21"], p3d=s_["p3d"], tri=s_["triangulated"], codes=s_["codes"])))
+    want = rows_of(ho)
+    for name, other in forms_out:
+        other = rows_of(other)
+        for k, v in want.items():
+            assert np.array_equal(np.ascontiguousarray(other[k]).view(np.uint8).reshape(-1), np.ascontiguousarray(v).view(np.uint8).reshape(-1)), (name, k)
+    assert sync_out["r"]["ok"] == api.reconstruct_accept(int(ho["model"][0]), float(ho["cos"][max(int(ho["choice"][0]), 0)]), 1.0)
+    out["checked"] = "all forms agree bit for bit: model %d, %d hypotheses, nGood %s, choice %d, every code, every position and flag; accepted at minParallax 1.0: %s" % (
+        int(ho["model"][0]), nh, ho["ngood"][:nh].tolist(), int(ho["choice"][0]), sync_out["r"]["ok"])
+
+    forms = [("a", host_form), ("b", device_form), ("c", sync_form), ("e1", one_stream), ("e2", round_trip)]
+    timed, (d_gpu,) = interleaved(REPEATS, REPS, st, [fn for _, fn in forms], [enqueue])
+    wall, worst = {k: t[0] for (k, _), t in zip(forms, timed)}, {k: t[1] for (k, _), t in zip(forms, timed)}
+    rows = out["rows"]
+    labels = {"a": "(a) ReconstructInitial of Initializer.h on one host thread (g++ -O2), wall time",
+              "b": "(b) orbfe_enqueue_reconstruct_initial on resident inputs + download of every output + one synchronise, wall time",
+              "c": "(c) orbfe_reconstruct_initial from host arrays (uploads, the call, downloads, the parallax test), wall time",
+              "e1": "(e1) RANSAC + reconstruct queued on one stream, downloads, one synchronise, wall time",
+              "e2": "(e2) the RANSAC call, its downloads and a synchronise, then (c) on the fetched arrays: the host round trip between the two, wall time"}
+    for k, _ in forms:
+        rows[labels[k]] = {"ms_per_repeat": wall[k], "slowest_loop_ms": worst[k]}
+    rows["(d) the enqueue call alone, queued back to back, GPU time between two events"] = {"ms_per_repeat": d_gpu}
+    rows["median (a) / median (b)"] = round(float(np.median(wall["a"]) / np.median(wall["b"])), 2)
+    rows["median (e2) - median (e1), ms"] = round(float(np.median(wall["e2"]) - np.median(wall["e1"])), 4)
+    ctx.close()
+
+
 def load_other_build(api, path):
     """api.load() on the library at `path`, which may be older than the package: the prototypes load() sets for entry points
     that build lacks land on stand-ins that are not kept, so hasattr(lib, name) is False afterwards and a call fails loudly."""
@@ -1455,6 +1607,12 @@ def main():
     if "--initializer" in sys.argv[1:]:
         out = {"unit": "ms per frame pair (500 matches, 200 sets, both models)", "rows": {}}
         initializer_rows(out)
+        out["build_id"] = api.build_id()
+        print(json.dumps(out, indent=1))
+        return
+    if "--reconstruct" in sys.argv[1:]:
+        out = {"unit": "ms per frame pair (500 matches, 4 or 8 motion hypotheses)", "rows": {}}
+        reconstruct_rows(out)
         out["build_id"] = api.build_id()
         print(json.dumps(out, indent=1))
         return

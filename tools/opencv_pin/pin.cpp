@@ -419,6 +419,53 @@ void dump_primitives(const std::string &out_dir)
         std::memcpy(b, &z, 4);
         std::printf("  z %08x\n", b[0]);
     }
+    // case reconstruct: the eight vR of Initializer::ReconstructH (src/Initializer.cc:583-685) for a fixed H21 (the RANSAC winner of the
+    // frontal-plane scene of tests/reconstruct_scenes.py) at K = (520, 520, 320, 240).  It pins what DESIGN.md section 4m reads into
+    // `s * U * Rp * Vt` (the scale as the gemm's alpha, in double, before the one rounding), K.inv(), cv::determinant and the 3x3 SVD.
+    // The model's bits (tests/reconstruct_model.py; vR[2] == vR[1], vR[3] == vR[0], vR[6] == vR[5], vR[7] == vR[4]; a LAPACK build may
+    // permute the eight and differ in last bits):
+    //   vR[0]  3f77c552 bb806529 be80c1f3 3bc29f0e 3f7ffd1a 3bee7ece 3e80bcc3 bc0be2da 3f77c40b
+    //   vR[1]  3f784b77 bc08eae2 3e7931c8 3c43fdb1 3f7ff578 bc5a995a be790a4c 3c81db81 3f7847ce
+    //   vR[4]  3f7bad26 bdbb75eb 3e22477a bdbcd294 bf7ee885 bb4f8119 3e21e241 bc3c63fd bf7cc378
+    //   vR[5]  bf76e94a 3b6eb3cf 3e8733d1 bc4bd7e0 bf7fda12 bd01ab4f 3e8710b2 bd0a85d0 3f76c7ae
+    {
+        const float h[9] = {0.486260325f, 0.00350241992f, -45.1502686f, -0.0596336238f, 0.600658357f, 19.0333767f, -0.000278745923f, 1.79557683e-05f, 0.676318884f};
+        const float k[9] = {520, 0, 320, 0, 520, 240, 0, 0, 1};
+        cv::Mat H21(3, 3, CV_32F), K(3, 3, CV_32F);
+        std::memcpy(H21.data, h, sizeof(h));
+        std::memcpy(K.data, k, sizeof(k));
+        cv::Mat invK = K.inv();
+        cv::Mat A = invK * H21 * K;
+        cv::Mat U, sw, Vt;
+        cv::SVD::compute(A, sw, U, Vt, cv::SVD::FULL_UV);
+        float s = cv::determinant(U) * cv::determinant(Vt);
+        float d1 = sw.at<float>(0), d2 = sw.at<float>(1), d3 = sw.at<float>(2);
+        float aux_stheta = sqrt((d1 * d1 - d2 * d2) * (d2 * d2 - d3 * d3)) / ((d1 + d3) * d2);
+        float ctheta = (d2 * d2 + d1 * d3) / ((d1 + d3) * d2);
+        float stheta[] = {aux_stheta, -aux_stheta, -aux_stheta, aux_stheta};
+        float aux_sphi = sqrt((d1 * d1 - d2 * d2) * (d2 * d2 - d3 * d3)) / ((d1 - d3) * d2);
+        float cphi = (d1 * d3 - d2 * d2) / ((d1 - d3) * d2);
+        float sphi[] = {aux_sphi, -aux_sphi, -aux_sphi, aux_sphi};
+        float all[72];
+        for (int i = 0; i < 8; i++) {
+            cv::Mat Rp = cv::Mat::eye(3, 3, CV_32F);
+            if (i < 4) {
+                Rp.at<float>(0, 0) = ctheta; Rp.at<float>(0, 2) = -stheta[i]; Rp.at<float>(2, 0) = stheta[i]; Rp.at<float>(2, 2) = ctheta;
+            } else {
+                Rp.at<float>(0, 0) = cphi; Rp.at<float>(0, 2) = sphi[i - 4]; Rp.at<float>(1, 1) = -1; Rp.at<float>(2, 0) = sphi[i - 4]; Rp.at<float>(2, 2) = -cphi;
+            }
+            cv::Mat R = s * U * Rp * Vt;
+            std::memcpy(all + 9 * i, R.data, 36);
+            uint32_t b[9];
+            std::memcpy(b, R.data, 36);
+            std::printf("reconstruct vR[%d]", i);
+            for (int e = 0; e < 9; e++) std::printf(" %08x", b[e]);
+            std::printf("\n");
+        }
+        w.put("reconstruct_vR", F32, {8, 9}, all);
+        const float sd[4] = {s, d1, d2, d3};
+        w.put("reconstruct_s_d", F32, {4}, sd);
+    }
     std::printf("primitives written (OpenCV %s)\n", CV_VERSION);
 }
 } // namespace

@@ -46,6 +46,7 @@ public:
     Mat clone() const;
     void convertTo(Mat &dst, int type) const;
     MatExpr t() const;
+    MatExpr inv(int method = 0) const;
     double dot(const Mat &m) const;
     static MatExpr ones(int r, int c, int type);
     static MatExpr zeros(int r, int c, int type);
@@ -59,6 +60,7 @@ MatExpr operator+(const Mat &a, const MatExpr &b);
 MatExpr operator/(const Mat &a, double s);
 MatExpr operator*(float s, const Mat &m);
 MatExpr operator*(const Mat &a, const Mat &b);
+MatExpr operator*(const MatExpr &a, const Mat &b);
 MatExpr operator-(const MatExpr &a, const Mat &b);
 MatExpr operator+(const MatExpr &a, const Mat &b);
 struct SVD { enum { MODIFY_A = 1, NO_UV = 2, FULL_UV = 4 }; static void compute(const Mat &src, Mat &w, Mat &u, Mat &vt, int flags = 0); };
@@ -68,5 +70,6 @@ enum { NORM_L1 = 2 };
 enum { BORDER_REFLECT_101 = 4 };
 double norm(const Mat &a, const Mat &b, int type);
 double norm(const Mat &a);
+double determinant(const Mat &m);
 float fastAtan2(float y, float x);
 } // namespace cv
