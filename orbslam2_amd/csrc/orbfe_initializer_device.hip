@@ -19,6 +19,7 @@
 #include "orbfe_config.h"
 #include "orbfe_host.h"
 #include "../host/Initializer.h"
+#include "orbfe_cvmat.hpp"
 #include "orbfe_jacobi_wave.hpp"
 
 #include <cfloat>
@@ -305,7 +306,7 @@ try {
     for (int k = 0; k < 4; k++) { a.norm1[k] = norm1[k]; a.norm2[k] = norm2[k]; }
     ORB_SLAM2::InitializerT(a.norm1, a.T1);
     ORB_SLAM2::InitializerT(a.norm2, T2);
-    ORB_SLAM2::InitializerInv3(T2, a.T2inv);
+    ORB_SLAM2::Inv3(T2, a.T2inv);
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++) a.T2t[3 * r + c] = T2[3 * c + r];
     a.inv_sigma2 = (float)(1.0 / (double)(sigma * sigma));

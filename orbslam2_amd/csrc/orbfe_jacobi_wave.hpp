@@ -1,5 +1,5 @@
 // orbfe_jacobi_wave.hpp -- cv::SVD::compute of an m x N float matrix (N <= 9 columns, m <= 16 rows) by one wave with At, Vt and W in LDS:
-// the one-sided Jacobi of DESIGN.md sections 4k / 4l, and the 3 x 3 cv::Mat product and inverse of section 4l.  Shared by
+// the one-sided Jacobi of DESIGN.md section 4i2 (the per-lane 3 x 3 cv::Mat steps are in orbfe_cvmat.hpp).  Shared by
 // orbfe_initializer_device.hip (the 8-point solutions and the rank-2 step) and orbfe_reconstruct_device.hip (DecomposeE and
 // ReconstructH's decomposition): one definition, the same bits.
 #pragma once
@@ -109,35 +109,4 @@ template <int N, int M> __device__ __forceinline__ void jacobi_wave(float *At, f
             __syncthreads();
         }
     }
-}
-
-// ---------------------------------------------------------------------------------------------------------------- 3 x 3 cv::Mat steps
-// a cv::Mat product: per element a double sum over k in index order, rounded once
-__device__ __forceinline__ void mul3(const float (&a)[9], const float (&b)[9], float (&out)[9])
-{
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            double s = 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) s += (double)a[3 * r + k] * (double)b[3 * k + c];
-            out[3 * r + c] = (float)s;
-        }
-}
-
-// cv::Mat::inv() of a 3 x 3 float matrix: determinant and cofactors in double; det == 0 gives the zero matrix
-__device__ __forceinline__ void inv3(const float (&m)[9], float (&out)[9])
-{
-    const double m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5], m20 = m[6], m21 = m[7], m22 = m[8];
-    double d = m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20);
-    if (d == 0) {
-#pragma unroll
-        for (int k = 0; k < 9; k++) out[k] = 0.f;
-        return;
-    }
-    d = 1. / d;
-    out[0] = (float)((m11 * m22 - m12 * m21) * d); out[1] = (float)((m02 * m21 - m01 * m22) * d); out[2] = (float)((m01 * m12 - m02 * m11) * d);
-    out[3] = (float)((m12 * m20 - m10 * m22) * d); out[4] = (float)((m00 * m22 - m02 * m20) * d); out[5] = (float)((m02 * m10 - m00 * m12) * d);
-    out[6] = (float)((m10 * m21 - m11 * m20) * d); out[7] = (float)((m01 * m20 - m00 * m21) * d); out[8] = (float)((m00 * m11 - m01 * m10) * d);
 }

@@ -19,6 +19,7 @@
 #include "orbfe_config.h"
 #include "orbfe_host.h"
 #include "../host/Initializer.h"
+#include "orbfe_cvmat.hpp"
 #include "orbfe_jacobi4.hpp"
 #include "orbfe_jacobi_wave.hpp"
 
@@ -51,55 +52,7 @@ typedef orbfe_reconstruct_args Args;
 
 static_assert(sizeof(orbfe_keypoint) == 28, "orbfe_keypoint");
 
-__device__ __forceinline__ float one_nan(float v) { return v != v ? __int_as_float(0x7fc00000) : v; } // a NaN is stored with one bit pattern
-
 // ---------------------------------------------------------------------------------------------------------------- the hypotheses
-// cv::determinant of a 3 x 3 float matrix: the double expression d of inv3
-__device__ __forceinline__ double det3(const float (&m)[9])
-{
-    const double m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5], m20 = m[6], m21 = m[7], m22 = m[8];
-    return m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20);
-}
-
-// (alpha * a) * b as one gemm: the double sum times alpha, rounded once
-__device__ __forceinline__ void mul3_alpha(double alpha, const float (&a)[9], const float (&b)[9], float (&out)[9])
-{
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            double s = 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) s += (double)a[3 * r + k] * (double)b[3 * k + c];
-            out[3 * r + c] = (float)(alpha * s);
-        }
-}
-
-// a (3 x 3) * v (3 x 1)
-__device__ __forceinline__ void mul3_vec(const float (&a)[9], const float (&v)[3], float (&out)[3])
-{
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        double s = 0;
-#pragma unroll
-        for (int k = 0; k < 3; k++) s += (double)a[3 * r + k] * (double)v[k];
-        out[r] = (float)s;
-    }
-}
-
-// the float sqrt of :607-650, correctly rounded: the double sqrt is IEEE and rounding it once more changes nothing for a float argument
-// (the __fsqrt_rn intrinsic is the hardware's approximation)
-__device__ __forceinline__ float sqrt_rn(float x) { return (float)sqrt((double)x); }
-
-// t / cv::norm(t): a scale by (float)(1.0 / norm); no zero test
-__device__ __forceinline__ void unit3(float (&t)[3])
-{
-    const double d = sqrt((double)t[0] * (double)t[0] + (double)t[1] * (double)t[1] + (double)t[2] * (double)t[2]);
-    const float a = (float)(1.0 / d);
-#pragma unroll
-    for (int k = 0; k < 3; k++) t[k] = __fmul_rn(t[k], a);
-}
-
 // cv::SVD::compute of the 3 x 3 A that every lane holds: u, w, vt in every lane
 __device__ __forceinline__ void svd3_wave(const float (&A)[9], float *At, float *Vt, double *W, int lane, float (&u)[9], float (&w)[3], float (&vt)[9])
 {
@@ -247,8 +200,6 @@ __global__ __launch_bounds__(64) void reconstruct_hypotheses_kernel(Args a)
 
 // ---------------------------------------------------------------------------------------------------------------- CheckRT
 __device__ __forceinline__ bool pair_ok(const Args &a, int i1, int i2) { return i1 >= 0 && i1 < a.n1 && i2 >= 0 && i2 < a.n2; }
-
-__device__ __forceinline__ bool finite(float v) { return fabsf(v) < __int_as_float(0x7f800000); }
 
 // one iteration of CheckRT's loop (:829-893) for an inlier match under the hypothesis record `rec`: the code (1 .. 7), the cosine, the point
 __device__ __forceinline__ int check_match(const float *rec, const float (&K4)[4], float x1, float y1, float x2, float y2, float th2, float &cosp, float (&p)[3])

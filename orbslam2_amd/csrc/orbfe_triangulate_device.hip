@@ -15,6 +15,7 @@
 #include "../../include/orbfe.h"
 #include "orbfe_config.h"
 #include "orbfe_host.h"
+#include "orbfe_cvmat.hpp"
 #include "orbfe_jacobi4.hpp"
 
 #include <cfloat>
@@ -43,34 +44,6 @@ __global__ __launch_bounds__(64) void triangulate_reset_kernel(int32_t *status, 
         *status = 0;
         if (nnew) *nnew = 0;
     }
-}
-
-// ---------------------------------------------------------------------------------------------------------------- cv::Mat steps
-// Rwc * x (+ Ow): Rwc[i][k] = Tcw[k][i]; a double sum over k, one rounding
-__device__ __forceinline__ void rwc_times(const float (&Tcw)[12], const float (&x)[3], const float *plus, float (&out)[3])
-{
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        double s = 0;
-#pragma unroll
-        for (int k = 0; k < 3; k++) s += (double)Tcw[4 * k + i] * (double)x[k];
-        if (plus) s += (double)plus[i];
-        out[i] = (float)s;
-    }
-}
-
-// Rcw.row(R).dot(x3Dt) + tcw(R)
-template <int R> __device__ __forceinline__ float row_dot_plus(const float (&Tcw)[12], const float (&X)[3])
-{
-    double s = 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) s += (double)Tcw[4 * R + k] * (double)X[k];
-    return (float)(s + (double)Tcw[4 * R + 3]);
-}
-
-__device__ __forceinline__ double norm3(const float (&v)[3])
-{
-    return sqrt((double)v[0] * (double)v[0] + (double)v[1] * (double)v[1] + (double)v[2] * (double)v[2]);
 }
 
 // KeyFrame::UnprojectStereo(i): i is inside [0, n) and depth[i] > 0, both checked by the caller

@@ -20,11 +20,10 @@
 #include <vector>
 
 #include "../../include/orbfe.h"
+#include "CvMat.h"
 
 namespace ORB_SLAM2
 {
-
-enum { kInitializerAStride = 16, kInitializerVStride = 9 };
 
 // Initializer::Normalize (:748-794) of one frame's keypoints: out = (meanX, meanY, sX, sY).  Sequential float sums in keypoint order.
 inline void NormalizeKeys(const orbfe_keypoint *keys, int n, float out[4])
@@ -39,98 +38,6 @@ inline void NormalizeKeys(const orbfe_keypoint *keys, int n, float out[4])
     out[2] = (float)(1.0 / meanDevX); out[3] = (float)(1.0 / meanDevY);
 }
 
-// The one-sided (Hestenes) Jacobi of cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) for an m x n float A, m >= n, held transposed:
-// At[i * 16 + k] = A[k][i] (i < n <= 9, k < m <= 16), Vt[i * 9 + k].  On return W holds the singular values in descending order (strict
-// selection sort) and the rows of At (the rotated columns, NOT normalised) and of Vt are carried with them.
-inline void InitializerJacobi(float *At, float *Vt, double *W, int n, int m)
-{
-    const int as = kInitializerAStride, vs = kInitializerVStride;
-    for (int i = 0; i < n; i++) {
-        double sd = 0;
-        for (int k = 0; k < m; k++) sd += (double)At[i * as + k] * At[i * as + k];
-        W[i] = sd;
-        for (int k = 0; k < n; k++) Vt[i * vs + k] = i == k ? 1.f : 0.f;
-    }
-    const double eps = (double)FLT_EPSILON * 2;
-    for (int iter = 0; iter < 30; iter++) {
-        bool changed = false;
-        for (int i = 0; i < n - 1; i++)
-            for (int j = i + 1; j < n; j++) {
-                float *Ai = At + i * as, *Aj = At + j * as;
-                double a = W[i], b = W[j], p = 0;
-                for (int k = 0; k < m; k++) p += (double)Ai[k] * Aj[k];
-                if (std::fabs(p) <= eps * std::sqrt(a * b)) continue;
-                p *= 2;
-                const double beta = a - b, gamma = std::sqrt(p * p + beta * beta); // not hypot
-                float c, s;
-                if (beta < 0) {
-                    s = (float)std::sqrt(((gamma - beta) * 0.5) / gamma);
-                    c = (float)(p / (gamma * s * 2));
-                } else {
-                    c = (float)std::sqrt((gamma + beta) / (gamma * 2));
-                    s = (float)(p / (gamma * c * 2));
-                }
-                a = b = 0;
-                for (int k = 0; k < m; k++) {
-                    const float t0 = c * Ai[k] + s * Aj[k];
-                    const float t1 = -s * Ai[k] + c * Aj[k];
-                    Ai[k] = t0; Aj[k] = t1;
-                    a += (double)t0 * t0; b += (double)t1 * t1;
-                }
-                W[i] = a; W[j] = b;
-                changed = true;
-                float *Vi = Vt + i * vs, *Vj = Vt + j * vs;
-                for (int k = 0; k < n; k++) {
-                    const float t0 = c * Vi[k] + s * Vj[k];
-                    const float t1 = -s * Vi[k] + c * Vj[k];
-                    Vi[k] = t0; Vj[k] = t1;
-                }
-            }
-        if (!changed) break;
-    }
-    for (int i = 0; i < n; i++) {
-        double sd = 0;
-        for (int k = 0; k < m; k++) sd += (double)At[i * as + k] * At[i * as + k];
-        W[i] = std::sqrt(sd);
-    }
-    for (int i = 0; i < n - 1; i++) {
-        int j = i;
-        for (int k = i + 1; k < n; k++)
-            if (W[j] < W[k]) j = k;
-        if (i != j) {
-            std::swap(W[i], W[j]);
-            for (int k = 0; k < m; k++) std::swap(At[i * as + k], At[j * as + k]);
-            for (int k = 0; k < n; k++) std::swap(Vt[i * vs + k], Vt[j * vs + k]);
-        }
-    }
-}
-
-// a 3x3 cv::Mat product: per element a double sum over k in index order, rounded once
-inline void InitializerMul3(const float a[9], const float b[9], float out[9])
-{
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) {
-            double s = 0;
-            for (int k = 0; k < 3; k++) s += (double)a[3 * r + k] * b[3 * k + c];
-            out[3 * r + c] = (float)s;
-        }
-}
-
-// cv::Mat::inv() of a 3x3 float matrix (DECOMP_LU takes the closed form): determinant and cofactors in double, det == 0 gives zeros
-inline void InitializerInv3(const float m[9], float out[9])
-{
-    const double m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5], m20 = m[6], m21 = m[7], m22 = m[8];
-    double d = m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20);
-    if (d == 0) {
-        for (int k = 0; k < 9; k++) out[k] = 0.f;
-        return;
-    }
-    d = 1. / d;
-    out[0] = (float)((m11 * m22 - m12 * m21) * d); out[1] = (float)((m02 * m21 - m01 * m22) * d); out[2] = (float)((m01 * m12 - m02 * m11) * d);
-    out[3] = (float)((m12 * m20 - m10 * m22) * d); out[4] = (float)((m00 * m22 - m02 * m20) * d); out[5] = (float)((m02 * m10 - m00 * m12) * d);
-    out[6] = (float)((m10 * m21 - m11 * m20) * d); out[7] = (float)((m01 * m20 - m00 * m21) * d); out[8] = (float)((m00 * m11 - m01 * m10) * d);
-}
-
 // T of Normalize (:789-793)
 inline void InitializerT(const float norm[4], float T[9])
 {
@@ -142,46 +49,37 @@ inline void InitializerT(const float norm[4], float T[9])
 // ComputeH21 (:225-265): vt.row(8) of the 16 x 9 DLT matrix
 inline void InitializerComputeH21(const float p1[8][2], const float p2[8][2], float Hn[9])
 {
-    float At[9 * kInitializerAStride], Vt[9 * kInitializerVStride];
+    float At[9 * kCvMatAStride], Vt[9 * kCvMatVStride];
     double W[9];
-    const int as = kInitializerAStride;
+    const int as = kCvMatAStride;
     for (int i = 0; i < 8; i++) {
         const float u1 = p1[i][0], v1 = p1[i][1], u2 = p2[i][0], v2 = p2[i][1];
         const float r0[9] = {0.f, 0.f, 0.f, -u1, -v1, -1.f, v2 * u1, v2 * v1, v2};
         const float r1[9] = {u1, v1, 1.f, 0.f, 0.f, 0.f, -u2 * u1, -u2 * v1, -u2};
         for (int c = 0; c < 9; c++) { At[c * as + 2 * i] = r0[c]; At[c * as + 2 * i + 1] = r1[c]; }
     }
-    InitializerJacobi(At, Vt, W, 9, 16);
-    for (int k = 0; k < 9; k++) Hn[k] = Vt[8 * kInitializerVStride + k];
+    Jacobi(At, Vt, W, 9, 16);
+    for (int k = 0; k < 9; k++) Hn[k] = Vt[8 * kCvMatVStride + k];
 }
 
 // ComputeF21 (:267-302): vt.row(8) of the 8 x 9 matrix padded with a zero ninth row, then the rank-2 step
 inline void InitializerComputeF21(const float p1[8][2], const float p2[8][2], float Fn[9])
 {
-    float At[9 * kInitializerAStride], Vt[9 * kInitializerVStride];
+    float At[9 * kCvMatAStride], Vt[9 * kCvMatVStride];
     double W[9];
-    const int as = kInitializerAStride, vs = kInitializerVStride;
+    const int as = kCvMatAStride;
     for (int i = 0; i < 8; i++) {
         const float u1 = p1[i][0], v1 = p1[i][1], u2 = p2[i][0], v2 = p2[i][1];
         const float r[9] = {u2 * u1, u2 * v1, u2, v2 * u1, v2 * v1, v2, u1, v1, 1.f};
         for (int c = 0; c < 9; c++) At[c * as + i] = r[c];
     }
     for (int c = 0; c < 9; c++) At[c * as + 8] = 0.f;
-    InitializerJacobi(At, Vt, W, 9, 9);
-    float Fpre[9];
-    for (int k = 0; k < 9; k++) Fpre[k] = Vt[8 * vs + k];
-    for (int i = 0; i < 3; i++)
-        for (int k = 0; k < 3; k++) At[i * as + k] = Fpre[3 * k + i];
-    InitializerJacobi(At, Vt, W, 3, 3);
-    float u[9], d[9], vt[9], ud[9];
-    for (int i = 0; i < 3; i++) {
-        const float s = W[i] > (double)FLT_MIN ? (float)(1 / W[i]) : 0.f; // the basis completion of a zero singular value is not restated
-        for (int k = 0; k < 3; k++) u[3 * k + i] = At[i * as + k] * s;
-    }
-    for (int k = 0; k < 9; k++) { d[k] = 0.f; vt[k] = Vt[(k / 3) * vs + k % 3]; }
-    d[0] = (float)W[0]; d[4] = (float)W[1]; // w.at<float>(2) = 0
-    InitializerMul3(u, d, ud);
-    InitializerMul3(ud, vt, Fn);
+    Jacobi(At, Vt, W, 9, 9);
+    float u[9], w[3], vt[9], d[9] = {0.f}, ud[9];
+    Svd3(Vt + 8 * kCvMatVStride, u, w, vt); // Fpre = vt.row(8).reshape(0, 3)
+    d[0] = w[0]; d[4] = w[1];               // w.at<float>(2) = 0
+    MatMul(u, d, 3, 3, 3, ud);
+    MatMul(ud, vt, 3, 3, 3, Fn);
 }
 
 // the two terms of match (u1, v1, u2, v2) in CheckHomography (:336-384): returns bIn; score is the running float sum
@@ -230,13 +128,6 @@ inline bool InitializerScoreF(const float F21[9], float u1, float v1, float u2, 
     return bIn;
 }
 
-// a NaN score is stored with one bit pattern everywhere
-inline float InitializerStoredScore(float s)
-{
-    if (s != s) { const uint32_t q = 0x7fc00000u; std::memcpy(&s, &q, 4); }
-    return s;
-}
-
 // Returns what the device reports in d_status (0, or ORBFE_ERR_INVALID for a pair or set index out of range), or ORBFE_ERR_INVALID for
 // refused arguments (then nothing is written).  H21, F21 [9], score, best [2] (H, F); inliers_h / inliers_f [N], ninliers [2] and
 // all_scores [2][iterations] may be NULL.  models: bit 0 = H, bit 1 = F; the outputs of a model that is left out stay untouched (the
@@ -253,7 +144,7 @@ inline int FindHomographyFundamental(const orbfe_keypoint *keys1, int n1, const 
     float T1[9], T2[9], T2inv[9], T2t[9];
     InitializerT(norm1, T1);
     InitializerT(norm2, T2);
-    InitializerInv3(T2, T2inv);
+    Inv3(T2, T2inv);
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++) T2t[3 * r + c] = T2[3 * c + r];
     const float invSigmaSquare = (float)(1.0 / (sigma * sigma));
@@ -281,14 +172,14 @@ inline int FindHomographyFundamental(const orbfe_keypoint *keys1, int n1, const 
             float Hn[9], Fn[9], t[9];
             if (models & 1) {
                 InitializerComputeH21(p1, p2, Hn);
-                InitializerMul3(T2inv, Hn, t);
-                InitializerMul3(t, T1, mat[0]);
-                InitializerInv3(mat[0], mat[0] + 9);
+                MatMul(T2inv, Hn, 3, 3, 3, t);
+                MatMul(t, T1, 3, 3, 3, mat[0]);
+                Inv3(mat[0], mat[0] + 9);
             }
             if (models & 2) {
                 InitializerComputeF21(p1, p2, Fn);
-                InitializerMul3(T2t, Fn, t);
-                InitializerMul3(t, T1, mat[1]);
+                MatMul(T2t, Fn, 3, 3, 3, t);
+                MatMul(t, T1, 3, 3, 3, mat[1]);
             }
             for (int i = 0; i < N; i++) {
                 if (!pair_ok(i)) continue; // a faulty match adds nothing
@@ -299,7 +190,7 @@ inline int FindHomographyFundamental(const orbfe_keypoint *keys1, int n1, const 
         }
         for (int model = 0; model < 2; model++) {
             if (!(models >> model & 1)) continue;
-            if (all_scores) all_scores[(size_t)model * iterations + it] = InitializerStoredScore(sc[model]);
+            if (all_scores) all_scores[(size_t)model * iterations + it] = Stored(sc[model]);
             if (sc[model] > best_score[model]) {
                 best_score[model] = sc[model]; best_it[model] = it;
                 std::memcpy(best_mat[model], mat[model], sizeof(mat[model]));
@@ -332,50 +223,6 @@ inline int FindHomographyFundamental(const orbfe_keypoint *keys1, int n1, const 
 // ReconstructF / ReconstructH / DecomposeE / CheckRT / Triangulate (:469-746, :797-928) on the flat arrays of
 // orbfe_enqueue_reconstruct_initial (include/orbfe.h): the same arguments, every pointer a HOST pointer.
 
-// a cv::Mat product a[R][Kk] * b[Kk][C]: per element a double sum over k in index order, times *alpha when given (a MatExpr scale is
-// the gemm's alpha), plus (double)plus[r][c] when given, rounded once
-inline void ReconstructMat(const float *a, const float *b, int R, int Kk, int C, float *out, const double *alpha = nullptr, const float *plus = nullptr)
-{
-    for (int r = 0; r < R; r++)
-        for (int c = 0; c < C; c++) {
-            double s = 0;
-            for (int k = 0; k < Kk; k++) s += (double)a[Kk * r + k] * b[C * k + c];
-            if (alpha) s = *alpha * s;
-            if (plus) s += (double)plus[C * r + c];
-            out[C * r + c] = (float)s;
-        }
-}
-
-// cv::determinant of a 3x3 float matrix: the double expression d of InitializerInv3
-inline double ReconstructDet3(const float m[9])
-{
-    const double m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5], m20 = m[6], m21 = m[7], m22 = m[8];
-    return m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20);
-}
-
-// cv::SVD::compute of a 3x3 float matrix: the Jacobi on its columns; w[i] = (float)W[i], u[k][i] = At[i][k] * (float)(1 / W[i])
-inline void ReconstructSvd3(const float A[9], float u[9], float w[3], float vt[9])
-{
-    float At[3 * kInitializerAStride], Vt[3 * kInitializerVStride];
-    double W[3];
-    for (int i = 0; i < 3; i++)
-        for (int k = 0; k < 3; k++) At[i * kInitializerAStride + k] = A[3 * k + i];
-    InitializerJacobi(At, Vt, W, 3, 3);
-    for (int i = 0; i < 3; i++) {
-        const float s = W[i] > (double)FLT_MIN ? (float)(1 / W[i]) : 0.f;
-        w[i] = (float)W[i];
-        for (int k = 0; k < 3; k++) { u[3 * k + i] = At[i * kInitializerAStride + k] * s; vt[3 * i + k] = Vt[i * kInitializerVStride + k]; }
-    }
-}
-
-// t / cv::norm(t): a scale by (float)(1.0 / norm); no zero test
-inline void ReconstructUnit(float t[3])
-{
-    const double d = std::sqrt((double)t[0] * t[0] + (double)t[1] * t[1] + (double)t[2] * t[2]);
-    const float a = (float)(1.0 / d);
-    for (int k = 0; k < 3; k++) t[k] = t[k] * a;
-}
-
 inline void ReconstructK(const float K4[4], float K[9])
 {
     for (int k = 0; k < 9; k++) K[k] = 0.f;
@@ -385,7 +232,7 @@ inline void ReconstructK(const float K4[4], float K[9])
 // a NaN is stored with one bit pattern everywhere
 inline void ReconstructStore(float *dst, const float *src, int n)
 {
-    for (int k = 0; k < n; k++) dst[k] = InitializerStoredScore(src[k]);
+    for (int k = 0; k < n; k++) dst[k] = Stored(src[k]);
 }
 
 // the order of the sorted cosines: that of the floats, -0 before +0, any NaN after every number
@@ -412,17 +259,17 @@ inline void ReconstructHypothesesF(const float F21[9], const float K[9], float v
     float Kt[9], tmp[9], E[9], u[9], w[3], vtm[9];
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++) Kt[3 * r + c] = K[3 * c + r];
-    InitializerMul3(Kt, F21, tmp);
-    InitializerMul3(tmp, K, E);
-    ReconstructSvd3(E, u, w, vtm);
+    MatMul(Kt, F21, 3, 3, 3, tmp);
+    MatMul(tmp, K, 3, 3, 3, E);
+    Svd3(E, u, w, vtm);
     float t[3] = {u[2], u[5], u[8]};
-    ReconstructUnit(t);
+    Unit(t);
     const float W[9] = {0, -1, 0, 1, 0, 0, 0, 0, 1}, Wt[9] = {0, 1, 0, -1, 0, 0, 0, 0, 1};
     float R[2][9];
     for (int which = 0; which < 2; which++) {
-        InitializerMul3(u, which ? Wt : W, tmp);
-        InitializerMul3(tmp, vtm, R[which]);
-        if (ReconstructDet3(R[which]) < 0)
+        MatMul(u, which ? Wt : W, 3, 3, 3, tmp);
+        MatMul(tmp, vtm, 3, 3, 3, R[which]);
+        if (Det3(R[which]) < 0)
             for (int k = 0; k < 9; k++) R[which][k] = -R[which][k];
     }
     for (int h = 0; h < 4; h++) {
@@ -435,11 +282,11 @@ inline void ReconstructHypothesesF(const float F21[9], const float K[9], float v
 inline bool ReconstructHypothesesH(const float H21[9], const float K[9], float vR[8][9], float vt[8][3])
 {
     float invK[9], tmp[9], A[9], U[9], w[3], Vt[9];
-    InitializerInv3(K, invK);
-    InitializerMul3(invK, H21, tmp);
-    InitializerMul3(tmp, K, A);
-    ReconstructSvd3(A, U, w, Vt);
-    const float s = (float)(ReconstructDet3(U) * ReconstructDet3(Vt));
+    Inv3(K, invK);
+    MatMul(invK, H21, 3, 3, 3, tmp);
+    MatMul(tmp, K, 3, 3, 3, A);
+    Svd3(A, U, w, Vt);
+    const float s = (float)(Det3(U) * Det3(Vt));
     const float d1 = w[0], d2 = w[1], d3 = w[2];
     if (d1 / d2 < 1.00001 || d2 / d3 < 1.00001) return false;
     const float aux1 = std::sqrt((d1 * d1 - d2 * d2) / (d1 * d1 - d3 * d3));
@@ -464,10 +311,10 @@ inline bool ReconstructHypothesesH(const float H21[9], const float K[9], float v
             tp[0] = x1[i - 4]; tp[1] = 0; tp[2] = x3[i - 4];
             for (int k = 0; k < 3; k++) tp[k] = tp[k] * (d1 + d3);
         }
-        ReconstructMat(U, Rp, 3, 3, 3, tmp, &alpha); // s * U * Rp: the scale is the gemm's alpha (the reading tagged in include/orbfe.h)
-        InitializerMul3(tmp, Vt, vR[i]);
-        ReconstructMat(U, tp, 3, 3, 1, vt[i]);
-        ReconstructUnit(vt[i]);
+        MatMul(U, Rp, 3, 3, 3, tmp, &alpha); // s * U * Rp: the scale is the gemm's alpha (the reading tagged in include/orbfe.h)
+        MatMul(tmp, Vt, 3, 3, 3, vR[i]);
+        MatMul(U, tp, 3, 3, 1, vt[i]);
+        Unit(vt[i]);
     }
     return true;
 }
@@ -480,9 +327,9 @@ inline void ReconstructCamera2(const float R[9], const float t[3], const float K
         for (int c = 0; c < 3; c++) { Rt[4 * r + c] = R[3 * r + c]; Rtr[3 * r + c] = R[3 * c + r]; }
         Rt[4 * r + 3] = t[r];
     }
-    ReconstructMat(K, Rt, 3, 3, 4, P2);
+    MatMul(K, Rt, 3, 3, 4, P2);
     const double minus = -1.0;
-    ReconstructMat(Rtr, t, 3, 3, 1, O2, &minus);
+    MatMul(Rtr, t, 3, 3, 1, O2, &minus);
 }
 
 // One iteration of CheckRT's loop (:829-893) for an inlier match: the code (1..7 of orbfe_enqueue_reconstruct_initial), its cosine and point.
@@ -492,34 +339,34 @@ inline int ReconstructCheckMatch(const float R[9], const float t[3], const float
     const float fx = K4[0], fy = K4[1], cx = K4[2], cy = K4[3];
     const float P1[12] = {fx, 0, cx, 0, 0, fy, cy, 0, 0, 0, 1, 0};
     // Triangulate (:733-746)
-    float At[4 * kInitializerAStride], Vt[4 * kInitializerVStride];
+    float At[4 * kCvMatAStride], Vt[4 * kCvMatVStride];
     double W[4];
     for (int c = 0; c < 4; c++) {
-        At[c * kInitializerAStride + 0] = kp1x * P1[8 + c] - P1[c];
-        At[c * kInitializerAStride + 1] = kp1y * P1[8 + c] - P1[4 + c];
-        At[c * kInitializerAStride + 2] = kp2x * P2[8 + c] - P2[c];
-        At[c * kInitializerAStride + 3] = kp2y * P2[8 + c] - P2[4 + c];
+        At[c * kCvMatAStride + 0] = kp1x * P1[8 + c] - P1[c];
+        At[c * kCvMatAStride + 1] = kp1y * P1[8 + c] - P1[4 + c];
+        At[c * kCvMatAStride + 2] = kp2x * P2[8 + c] - P2[c];
+        At[c * kCvMatAStride + 3] = kp2y * P2[8 + c] - P2[4 + c];
     }
-    InitializerJacobi(At, Vt, W, 4, 4);
-    const float *x3D = Vt + 3 * kInitializerVStride;
+    Jacobi(At, Vt, W, 4, 4);
+    const float *x3D = Vt + 3 * kCvMatVStride;
     const float a = (float)(1.0 / x3D[3]);
     for (int k = 0; k < 3; k++) p3dC1[k] = x3D[k] * a;
     cosParallax = 0.f;
     if (!std::isfinite(p3dC1[0]) || !std::isfinite(p3dC1[1]) || !std::isfinite(p3dC1[2])) return 1;
     // Check parallax
     float normal2[3];
-    double d1 = 0, d2 = 0, dot = 0;
+    double dot = 0;
     for (int k = 0; k < 3; k++) {
         normal2[k] = p3dC1[k] - O2[k];
-        d1 += (double)p3dC1[k] * p3dC1[k]; d2 += (double)normal2[k] * normal2[k]; dot += (double)p3dC1[k] * normal2[k];
+        dot += (double)p3dC1[k] * normal2[k];
     }
-    const float dist1 = (float)std::sqrt(d1), dist2 = (float)std::sqrt(d2);
+    const float dist1 = (float)Norm3(p3dC1), dist2 = (float)Norm3(normal2);
     cosParallax = (float)(dot / (double)(dist1 * dist2));
     // Check depth in front of first camera (only if enough parallax, as "infinite" points can easily go to negative depth)
     if (p3dC1[2] <= 0 && cosParallax < 0.99998) return 2;
     // Check depth in front of second camera
     float p3dC2[3];
-    ReconstructMat(R, p3dC1, 3, 3, 1, p3dC2, nullptr, t);
+    MatMul(R, p3dC1, 3, 3, 1, p3dC2, nullptr, t);
     if (p3dC2[2] <= 0 && cosParallax < 0.99998) return 3;
     // Check reprojection error in first image
     const float invZ1 = (float)(1.0 / p3dC1[2]);

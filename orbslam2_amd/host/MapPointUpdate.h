@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/orbfe.h"
+#include "CvMat.h"
 
 namespace ORB_SLAM2
 {
@@ -109,8 +110,7 @@ inline int UpdateMapPoints(const orbfe_obs_keyframe *kfs, int n_kfs, int n_upd, 
             for (int o = o0; o < o1; o++) {
                 const float *Owi = kfs[obs_kf[o]].Ow;
                 const float normali[3] = {Pos[0] - Owi[0], Pos[1] - Owi[1], Pos[2] - Owi[2]};
-                const double nrm = std::sqrt((double)normali[0] * normali[0] + (double)normali[1] * normali[1] + (double)normali[2] * normali[2]);
-                const float alpha = (float)(1.0 / nrm); // Mat / double is a scale by 1./s; scaleAdd takes the factor as float
+                const float alpha = (float)(1.0 / Norm3(normali)); // Mat / double is a scale by 1./s; scaleAdd takes the factor as float
                 for (int c = 0; c < 3; c++) {
                     const float term = normali[c] * alpha;
                     acc[c] = term + acc[c];
@@ -119,7 +119,7 @@ inline int UpdateMapPoints(const orbfe_obs_keyframe *kfs, int n_kfs, int n_upd, 
             }
             const float *Owr = kfs[obs_kf[o0 + ref[q]]].Ow;
             const float PC[3] = {Pos[0] - Owr[0], Pos[1] - Owr[1], Pos[2] - Owr[2]};
-            const float dist = (float)std::sqrt((double)PC[0] * PC[0] + (double)PC[1] * PC[1] + (double)PC[2] * PC[2]);
+            const float dist = (float)Norm3(PC);
             const float inv_n = (float)(1.0 / (double)n); // Mat / int: convertTo with a float scale
             max_distance[r] = dist * scale[level];
             min_distance[r] = max_distance[r] / scale[nlevels - 1];

@@ -9,88 +9,18 @@
 // Compile with -ffp-contract=off: every float operation below is rounded once (contract Q4), as in the kernel.
 #pragma once
 
-#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <initializer_list>
-#include <utility>
 
 #include "../../include/orbfe.h"
+#include "CvMat.h"
 
 namespace ORB_SLAM2
 {
 
-// vt.row(3) of cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) for a 4x4 float A: one-sided (Hestenes) Jacobi on the columns of A.
-// Returns the number of sweeps that rotated.
-inline int TriangulateNullVector(const float A[4][4], float v[4])
-{
-    float At[4][4], Vt[4][4];
-    double W[4];
-    for (int i = 0; i < 4; i++) {
-        double sd = 0;
-        for (int k = 0; k < 4; k++) {
-            At[i][k] = A[k][i];
-            Vt[i][k] = i == k ? 1.f : 0.f;
-            sd += (double)At[i][k] * At[i][k];
-        }
-        W[i] = sd;
-    }
-    const double eps = (double)FLT_EPSILON * 2;
-    int sweeps = 0;
-    for (int iter = 0; iter < 30; iter++) {
-        bool changed = false;
-        for (int i = 0; i < 3; i++)
-            for (int j = i + 1; j < 4; j++) {
-                double a = W[i], b = W[j], p = 0;
-                for (int k = 0; k < 4; k++) p += (double)At[i][k] * At[j][k];
-                if (std::fabs(p) <= eps * std::sqrt(a * b)) continue;
-                p *= 2;
-                const double beta = a - b, gamma = std::sqrt(p * p + beta * beta); // not hypot
-                float c, s;
-                if (beta < 0) {
-                    s = (float)std::sqrt(((gamma - beta) * 0.5) / gamma);
-                    c = (float)(p / (gamma * s * 2));
-                } else {
-                    c = (float)std::sqrt((gamma + beta) / (gamma * 2));
-                    s = (float)(p / (gamma * c * 2));
-                }
-                a = b = 0;
-                for (int k = 0; k < 4; k++) {
-                    const float t0 = c * At[i][k] + s * At[j][k];
-                    const float t1 = -s * At[i][k] + c * At[j][k];
-                    At[i][k] = t0; At[j][k] = t1;
-                    a += (double)t0 * t0; b += (double)t1 * t1;
-                }
-                W[i] = a; W[j] = b;
-                changed = true;
-                for (int k = 0; k < 4; k++) {
-                    const float t0 = c * Vt[i][k] + s * Vt[j][k];
-                    const float t1 = -s * Vt[i][k] + c * Vt[j][k];
-                    Vt[i][k] = t0; Vt[j][k] = t1;
-                }
-            }
-        if (!changed) break;
-        sweeps++;
-    }
-    for (int i = 0; i < 4; i++) {
-        double sd = 0;
-        for (int k = 0; k < 4; k++) sd += (double)At[i][k] * At[i][k];
-        W[i] = std::sqrt(sd);
-    }
-    for (int i = 0; i < 3; i++) {
-        int j = i;
-        for (int k = i + 1; k < 4; k++)
-            if (W[j] < W[k]) j = k;
-        if (i != j) {
-            std::swap(W[i], W[j]);
-            for (int k = 0; k < 4; k++) std::swap(Vt[i][k], Vt[j][k]);
-        }
-    }
-    for (int k = 0; k < 4; k++) v[k] = Vt[3][k];
-    return sweeps;
-}
-
-// Rwc * x (+ Ow): Rwc[i][k] = Tcw[k][i]; a cv::Mat product is a double sum over k, rounded once
+// Rwc * x (+ Ow): the product rule of MatMul, its loop kept here because Rwc is read out of Tcw transposed (Rwc[i][k] = Tcw[k][i],
+// row stride 4), which MatMul's dense row-major operands do not express
 inline void TriangulateRwcTimes(const float *Tcw, const float x[3], const float *plus, float out[3])
 {
     for (int i = 0; i < 3; i++) {
@@ -104,16 +34,9 @@ inline void TriangulateRwcTimes(const float *Tcw, const float x[3], const float 
 // Rcw.row(r).dot(x3Dt) + tcw.at<float>(r)
 inline float TriangulateRowDotPlus(const float *Tcw, int r, const float X[3])
 {
-    double s = 0;
-    for (int k = 0; k < 3; k++) s += (double)Tcw[4 * r + k] * X[k];
-    return (float)(s + (double)Tcw[4 * r + 3]);
-}
-
-inline double TriangulateNorm(const float v[3])
-{
-    double s = 0;
-    for (int k = 0; k < 3; k++) s += (double)v[k] * v[k];
-    return std::sqrt(s);
+    float out;
+    MatMul(Tcw + 4 * r, X, 1, 3, 1, &out, nullptr, Tcw + 4 * r + 3);
+    return out;
 }
 
 // KeyFrame::UnprojectStereo(i), z > 0 checked by the caller
@@ -160,7 +83,7 @@ inline int TriangulatePair(const orbfe_newpoint_keyframe &kf1, const orbfe_newpo
     TriangulateRwcTimes(kf2.Tcw, xn2, nullptr, ray2);
     double dot = 0;
     for (int k = 0; k < 3; k++) dot += (double)ray1[k] * ray2[k];
-    const float cosParallaxRays = (float)(dot / (TriangulateNorm(ray1) * TriangulateNorm(ray2)));
+    const float cosParallaxRays = (float)(dot / (Norm3(ray1) * Norm3(ray2)));
 
     float cosParallaxStereo = cosParallaxRays + 1;
     float cosParallaxStereo1 = cosParallaxStereo;
@@ -172,14 +95,16 @@ inline int TriangulatePair(const orbfe_newpoint_keyframe &kf1, const orbfe_newpo
     int code;
     if (cosParallaxRays < cosParallaxStereo && cosParallaxRays > 0 && (bStereo1 || bStereo2 || cosParallaxRays < 0.9998)) {
         // Linear Triangulation Method
-        float A[4][4], v[4];
+        float At[4 * kCvMatAStride], Vt[4 * kCvMatVStride];
+        double W[4];
         for (int c = 0; c < 4; c++) {
-            A[0][c] = xn1[0] * kf1.Tcw[8 + c] - kf1.Tcw[c];
-            A[1][c] = xn1[1] * kf1.Tcw[8 + c] - kf1.Tcw[4 + c];
-            A[2][c] = xn2[0] * kf2.Tcw[8 + c] - kf2.Tcw[c];
-            A[3][c] = xn2[1] * kf2.Tcw[8 + c] - kf2.Tcw[4 + c];
+            At[c * kCvMatAStride + 0] = xn1[0] * kf1.Tcw[8 + c] - kf1.Tcw[c];
+            At[c * kCvMatAStride + 1] = xn1[1] * kf1.Tcw[8 + c] - kf1.Tcw[4 + c];
+            At[c * kCvMatAStride + 2] = xn2[0] * kf2.Tcw[8 + c] - kf2.Tcw[c];
+            At[c * kCvMatAStride + 3] = xn2[1] * kf2.Tcw[8 + c] - kf2.Tcw[4 + c];
         }
-        TriangulateNullVector(A, v);
+        Jacobi(At, Vt, W, 4, 4);
+        const float *v = Vt + 3 * kCvMatVStride; // vt.row(3)
         if (v[3] == 0) return 4;
         // Euclidean coordinates: Mat / float is a scale
         const float alpha = (float)(1.0 / v[3]);
@@ -206,9 +131,9 @@ inline int TriangulatePair(const orbfe_newpoint_keyframe &kf1, const orbfe_newpo
 
     // Check scale consistency
     const float normal1[3] = {x3D[0] - kf1.Ow[0], x3D[1] - kf1.Ow[1], x3D[2] - kf1.Ow[2]};
-    const float dist1 = (float)TriangulateNorm(normal1);
+    const float dist1 = (float)Norm3(normal1);
     const float normal2[3] = {x3D[0] - kf2.Ow[0], x3D[1] - kf2.Ow[1], x3D[2] - kf2.Ow[2]};
-    const float dist2 = (float)TriangulateNorm(normal2);
+    const float dist2 = (float)Norm3(normal2);
     if (dist1 == 0 || dist2 == 0) return 9;
     const float ratioDist = dist2 / dist1;
     const float ratioOctave = scale[kp1.octave] / scale[kp2.octave];

@@ -6,27 +6,22 @@ tests/test_initializer_model.py (against orbslam2_amd/host/Initializer.h) and te
 must equal it bit for bit.  find_f64() is the same pipeline in double with numpy.linalg.svd and numpy.linalg.inv.
 
 Float contract (Q4: no contraction, IEEE divide and sqrt; the OpenCV steps are OPENCV-4.5.5-SEMANTICS, unpinned, stated in DESIGN.md
-section 4l):
+sections 4i2 and 4l; the cv::Mat rules themselves are tests/cvmat_model.py's):
   normalised point          ((x - meanX) * sX, (y - meanY) * sY) in float
   rows of A                 the float products of :238-256 / :280-288; F's 8 x 9 matrix gets a zero ninth row
-  cv::SVDecomp -> vt.row(8) jacobi(): the one-sided Jacobi of section 4k on 9 columns (m = 16 / 9 rows); OpenCV's own m < n path is not restated
-  rank-2 step               the same Jacobi on the 3 x 3 Fpre, u = rotated rows * (float)(1 / W), w[2] = 0, (u * diag(w)) * vt
-  Mat * Mat (3 x 3)         per element a double sum over k in index order, rounded once
-  Mat::inv (3 x 3)          determinant and cofactors in double, det == 0 -> the zero matrix
+  cv::SVDecomp -> vt.row(8) jacobi() on 9 columns (m = 16 / 9 rows); OpenCV's own m < n path is not restated
+  rank-2 step               svd3() of the 3 x 3 Fpre, w[2] = 0, (u * diag(w)) * vt
+  Mat * Mat, Mat::inv       mat(), inv3()
   CheckHomography / CheckFundamental   float, left to right; 1.0 / x in double, rounded; NaN > th is false, so NaN joins the score
   score                     sequential float sum in match order; the winner is the first strict maximum above 0
 """
 import numpy as np
 
-F32, F64 = np.float32, np.float64
+from tests.cvmat_model import AS, F32, F64, MAX_SWEEPS, NAN_BITS, inv3, jacobi, mat, stored, svd3  # noqa: F401 (constants read through this module)
+
 ERR_INVALID = -1
-EPS = F64(np.finfo(F32).eps) * F64(2)   # 2 * FLT_EPSILON, as a double
-FLT_MIN = F64(np.finfo(F32).tiny)
-MAX_SWEEPS = 30
-AS, VS = 16, 9
 TH_H = F32(5.991)
 TH_F, TH_SCORE_F = F32(3.841), F32(5.991)
-NAN_BITS = 0x7FC00000
 MAX_MATCHES, MAX_ITERATIONS, MAX_KEYS = 65535, 65535, 1 << 24
 
 
@@ -51,120 +46,6 @@ def t_matrix(norm):
     T[0, 0], T[1, 1], T[2, 2] = norm[2], norm[3], 1
     T[0, 2], T[1, 2] = F32(-norm[0] * norm[2]), F32(-norm[1] * norm[3])
     return T
-
-
-# ------------------------------------------------------------------ the Jacobi
-def jacobi(At, n, m):
-    """cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) for B independent m x n float matrices held transposed: At float32[B][n][16]
-    (At[b][i][k] = A[k][i]).  Returns (At, Vt float32[B][n][9], W float64[B][n], info): W descending, the rows of At (rotated, not
-    normalised) and Vt carried by the strict selection sort.  info = dict(sweeps[B], rotations[B], first_beta_negative[B] (-1 none), swaps[B])."""
-    At = np.array(At, F32)
-    B = At.shape[0]
-    Vt = np.zeros((B, n, VS), F32)
-    W = np.zeros((B, n), F64)
-    for i in range(n):
-        sd = np.zeros(B, F64)
-        for k in range(m):
-            sd = sd + At[:, i, k].astype(F64) * At[:, i, k].astype(F64)
-        W[:, i] = sd
-        Vt[:, i, i] = 1
-    info = dict(sweeps=np.zeros(B, int), rotations=np.zeros(B, int), first_beta_negative=np.full(B, -1), swaps=np.zeros(B, int))
-    for _ in range(MAX_SWEEPS):
-        changed = np.zeros(B, bool)
-        for i in range(n - 1):
-            for j in range(i + 1, n):
-                a, b, p = W[:, i].copy(), W[:, j].copy(), np.zeros(B, F64)
-                for k in range(m):
-                    p = p + At[:, i, k].astype(F64) * At[:, j, k].astype(F64)
-                rot = ~(np.abs(p) <= EPS * np.sqrt(a * b))
-                if not rot.any():
-                    continue
-                p = p * F64(2)
-                beta = a - b
-                gamma = np.sqrt(p * p + beta * beta)
-                neg = beta < 0
-                first = rot & (info["first_beta_negative"] < 0)
-                info["first_beta_negative"][first] = neg[first]
-                s1 = np.sqrt(((gamma - beta) * F64(0.5)) / gamma).astype(F32)
-                c1 = (p / (gamma * s1.astype(F64) * F64(2))).astype(F32)
-                c2 = np.sqrt((gamma + beta) / (gamma * F64(2))).astype(F32)
-                s2 = (p / (gamma * c2.astype(F64) * F64(2))).astype(F32)
-                c, s = np.where(neg, c1, c2)[:, None], np.where(neg, s1, s2)[:, None]
-                for X, width in ((At, m), (Vt, n)):
-                    xi, xj = X[:, i, :width].copy(), X[:, j, :width].copy()
-                    t0 = (c * xi) + (s * xj)
-                    t1 = ((-s) * xi) + (c * xj)
-                    assert t0.dtype == F32
-                    X[:, i, :width] = np.where(rot[:, None], t0, xi)
-                    X[:, j, :width] = np.where(rot[:, None], t1, xj)
-                na, nb = np.zeros(B, F64), np.zeros(B, F64)
-                for k in range(m):
-                    na = na + At[:, i, k].astype(F64) * At[:, i, k].astype(F64)
-                    nb = nb + At[:, j, k].astype(F64) * At[:, j, k].astype(F64)
-                W[:, i] = np.where(rot, na, a)
-                W[:, j] = np.where(rot, nb, b)
-                changed |= rot
-                info["rotations"] += rot
-        if not changed.any():
-            break
-        info["sweeps"] += changed
-    for i in range(n):
-        sd = np.zeros(B, F64)
-        for k in range(m):
-            sd = sd + At[:, i, k].astype(F64) * At[:, i, k].astype(F64)
-        W[:, i] = np.sqrt(sd)
-    rows = np.arange(B)
-    for i in range(n - 1):
-        j = np.full(B, i)
-        for k in range(i + 1, n):
-            j = np.where(W[rows, j] < W[:, k], k, j)
-        for X in (W, At, Vt):
-            tmp = X[rows, i].copy()
-            X[rows, i] = X[rows, j]
-            X[rows, j] = tmp
-        info["swaps"] += j != i
-    return At, Vt, W, info
-
-
-def null_vector9(A):
-    """vt.row(8) of one m x 9 float matrix (m <= 16; an 8-row matrix gets its zero ninth row here).  Returns (float32[9], info of scalars)."""
-    A = np.asarray(A, F32)
-    m = max(A.shape[0], 9)
-    At = np.zeros((1, 9, AS), F32)
-    At[0, :, :A.shape[0]] = A.T
-    with np.errstate(all="ignore"):
-        _, Vt, _, info = jacobi(At, 9, m)
-    return Vt[0, 8, :9].copy(), {k: int(v[0]) for k, v in info.items()}
-
-
-# ------------------------------------------------------------------ 3 x 3 cv::Mat steps
-def mul3(a, b):
-    """A cv::Mat product of [..., 3, 3] float32 arrays: per element a double sum over k in index order, rounded once."""
-    a, b = np.asarray(a, F32), np.asarray(b, F32)
-    shape = np.broadcast_shapes(a.shape, b.shape)
-    out = np.zeros(shape, F32)
-    for r in range(3):
-        for c in range(3):
-            s = np.zeros(shape[:-2], F64)
-            for k in range(3):
-                s = s + a[..., r, k].astype(F64) * b[..., k, c].astype(F64)
-            out[..., r, c] = s.astype(F32)
-    return out
-
-
-def inv3(m):
-    """cv::Mat::inv() of [..., 3, 3] float32: OpenCV's closed form in double; det == 0 gives the zero matrix."""
-    m = np.asarray(m, F32).astype(F64)
-    m00, m01, m02, m10, m11, m12, m20, m21, m22 = [m[..., r, c] for r in range(3) for c in range(3)]
-    d = m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20)
-    zero = d == 0
-    with np.errstate(all="ignore"):
-        d = F64(1.0) / d
-        t = [(m11 * m22 - m12 * m21) * d, (m02 * m21 - m01 * m22) * d, (m01 * m12 - m02 * m11) * d,
-             (m12 * m20 - m10 * m22) * d, (m00 * m22 - m02 * m20) * d, (m02 * m10 - m00 * m12) * d,
-             (m10 * m21 - m11 * m20) * d, (m01 * m20 - m00 * m21) * d, (m00 * m11 - m01 * m10) * d]
-    out = np.stack([np.where(zero, F64(0), x) for x in t], axis=-1).astype(F32)
-    return out.reshape(m.shape)
 
 
 # ------------------------------------------------------------------ the two 8-point solutions
@@ -194,19 +75,10 @@ def compute_f21(p1, p2):
         for c in range(9):
             At[:, c, i] = r[c]
     _, Vt, _, info = jacobi(At, 9, 9)          # row 8 of A is zero
-    Fpre = Vt[:, 8, :9].reshape(B, 3, 3)
-    At3 = np.zeros((B, 3, AS), F32)
-    for i in range(3):
-        for k in range(3):
-            At3[:, i, k] = Fpre[:, k, i]
-    At3, Vt3, W3, info3 = jacobi(At3, 3, 3)
-    u, d = np.zeros((B, 3, 3), F32), np.zeros((B, 3, 3), F32)
-    for i in range(3):
-        s = np.where(W3[:, i] > FLT_MIN, (F64(1) / W3[:, i]).astype(F32), F32(0)).astype(F32)
-        for k in range(3):
-            u[:, k, i] = At3[:, i, k] * s
-    d[:, 0, 0], d[:, 1, 1] = W3[:, 0].astype(F32), W3[:, 1].astype(F32)      # w.at<float>(2) = 0
-    return mul3(mul3(u, d), Vt3[:, :, :3]), info, info3
+    u, w, vt, info3 = svd3(Vt[:, 8, :9].reshape(B, 3, 3))
+    d = np.zeros((B, 3, 3), F32)
+    d[:, 0, 0], d[:, 1, 1] = w[:, 0], w[:, 1]      # w.at<float>(2) = 0
+    return mat(mat(u, d), vt), info, info3
 
 
 # ------------------------------------------------------------------ the scores
@@ -261,13 +133,6 @@ def check(model, mats, keys1, keys2, pairs, pair_ok, inv_sigma2):
     return score, inl, added
 
 
-def stored(score):
-    """What d_all_scores holds: NaN with one bit pattern."""
-    out = np.array(score, F32)
-    out.view(np.uint32)[np.isnan(out)] = NAN_BITS
-    return out
-
-
 def first_strict_maximum(scores):
     """`if (currentScore > score)` from score = 0 in iteration order (:164, :215).  Returns (iteration or -1, score)."""
     best, score = -1, scores.dtype.type(0)
@@ -305,10 +170,10 @@ def find(keys1, keys2, pairs, sets, norm1, norm2, sigma):
         p2 = np.stack([(keys2["x"][i2].astype(F32) - norm2[0]) * norm2[2], (keys2["y"][i2].astype(F32) - norm2[1]) * norm2[3]], axis=-1)
         assert p1.dtype == F32
         Hn, info_h = compute_h21(p1, p2)
-        H21 = mul3(mul3(T2inv, Hn), T1)
+        H21 = mat(mat(T2inv, Hn), T1)
         H12 = inv3(H21)
         Fn, info_f, info_f3 = compute_f21(p1, p2)
-        F21 = mul3(mul3(T2t, Fn), T1)
+        F21 = mat(mat(T2t, Fn), T1)
         mats = [(H21.reshape(B, 9), H12.reshape(B, 9)), (F21.reshape(B, 9),)]
         out = dict(status=status, ok=ok, mats=mats, infos=(info_h, info_f, info_f3), H21=None, F21=None, score=np.zeros(2, F32), best=np.zeros(2, np.int32),
                    inliers=np.zeros((2, N), np.uint8), ninliers=np.zeros(2, np.int32), all_scores=np.zeros((2, B), F32), added=np.zeros((2, B, N), bool), inliers_all=np.zeros((2, B, N), bool))

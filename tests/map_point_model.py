@@ -4,13 +4,14 @@ np.float32 / np.float64 operation.  It is the reference of tests/test_map_point_
 and tests/test_map_point_device.py (against orbfe_enqueue_update_map_points).
 
 Float contract (Q4 of oracle/orb_oracle_match.c, plus two OPENCV-4.5.5-SEMANTICS steps that DESIGN.md section 2 lists as unpinned):
-  cv::norm(float vector)   double sum of double squares, left to right, one sqrt
+  cv::norm(float vector)   tests/cvmat_model.py's norm(): double sum of double squares, left to right, one sqrt
   Mat / double             a scale by 1./s; `normal + that` is scaleAdd with the factor cast to float: (float)(d * alpha) + acc
   Mat / int                convertTo with the float scale (float)(1.0 / n): a product, not a division
 """
 import numpy as np
 
-F32, F64 = np.float32, np.float64
+from tests.cvmat_model import F32, F64, norm
+
 INT_MAX = 2 ** 31 - 1
 MP_DESCRIPTOR, MP_NORMAL_DEPTH = 1, 2
 ERR_INVALID = -1
@@ -57,13 +58,6 @@ def compute_distinctive_descriptors(descs, bad):
     return where[BestIdx], BestMedian, sharing
 
 
-def _norm(v):
-    """cv::norm of a 3-vector of floats."""
-    s = F64(v[0]) * F64(v[0]) + F64(v[1]) * F64(v[1])
-    s = s + F64(v[2]) * F64(v[2])
-    return np.sqrt(s)
-
-
 def update_normal_and_depth(pos, centres, ref, level, scale, nlevels, divide=False):
     """pos: mWorldPos (3 float32); centres: GetCameraCenter() per observation in the order of mObservations; ref: position of mpRefKF
     in that list; level: its keypoint's octave.  Returns (normal[3], mfMaxDistance, mfMinDistance) as np.float32.  divide=True is the
@@ -73,7 +67,7 @@ def update_normal_and_depth(pos, centres, ref, level, scale, nlevels, divide=Fal
     n = 0
     for Ow in centres:                        # :350-357
         normali = [pos[c] - F32(Ow[c]) for c in range(3)]
-        nrm = _norm(normali)
+        nrm = norm(normali)
         if divide:
             normal = [F32(F64(normali[c]) / nrm) + normal[c] for c in range(3)]
         else:
@@ -81,7 +75,7 @@ def update_normal_and_depth(pos, centres, ref, level, scale, nlevels, divide=Fal
             normal = [F32(normali[c] * alpha) + normal[c] for c in range(3)]
         n += 1
     PC = [pos[c] - F32(centres[ref][c]) for c in range(3)]   # :359
-    dist = F32(_norm(PC))
+    dist = F32(norm(PC))
     mfMaxDistance = dist * F32(scale[level])                  # :367
     mfMinDistance = mfMaxDistance / F32(scale[nlevels - 1])  # :368
     if divide:

@@ -1,7 +1,7 @@
 """Literal model of Initializer::ReconstructF / ReconstructH / DecomposeE / CheckRT / Triangulate (reference src/Initializer.cc:469-746,
 :797-928) on the flat arrays of orbfe_enqueue_reconstruct_initial (include/orbfe.h).  Every float step is an explicit np.float32 /
 np.float64 operation in the reference's order; numpy arrays run ACROSS the independent matches only (axis 0), never along a sum.  The
-Jacobi is tests/initializer_model.py's (the rules of DESIGN.md sections 4k / 4l) with 4 and 3 columns.  It is the reference of
+cv::Mat steps and the Jacobi (with 4 and 3 columns) are tests/cvmat_model.py's.  It is the reference of
 tests/test_reconstruct_model.py (against orbslam2_amd/host/Initializer.h) and tests/test_reconstruct_device.py (against the kernels);
 both must equal it bit for bit.  reconstruct_f64() is the same pipeline in double with numpy.linalg.svd / inv / det.
 
@@ -9,8 +9,8 @@ Float contract (Q4; the OpenCV steps are OPENCV-4.5.5-SEMANTICS, unpinned, state
   model                     RH = SH / (SH + SF) in float, H when (double)RH > 0.40
   Mat * Mat                 per element a double sum over k in index order (+ a `+ t` term in double), rounded once; a MatExpr scale
                             (s * U * Rp, -R.t() * t) is the gemm's alpha: the double sum times (double)alpha, then the one rounding
-  K.inv(), determinant      the closed 3 x 3 form of section 4l in double
-  3 x 3 SVD                 the Jacobi; w[i] = (float)W[i]; u[k][i] = At[i][k] * (float)(1 / W[i]), 0 when W[i] <= FLT_MIN
+  K.inv(), determinant      inv3(), det3(): the closed 3 x 3 form in double
+  3 x 3 SVD                 svd3(): the Jacobi; w[i] = (float)W[i]; u[k][i] = At[i][k] * (float)(1 / W[i]), 0 when W[i] <= FLT_MIN
   t / norm(t), x3D / w      scales by (float)(1.0 / d); no zero test
   rows of Triangulate's A   x * P.row(2) - P.row(0) in float, the product rounded, then the difference
   CheckRT                   literal (see check_rt)
@@ -20,20 +20,12 @@ Float contract (Q4; the OpenCV steps are OPENCV-4.5.5-SEMANTICS, unpinned, state
 import numpy as np
 
 from tests import initializer_model as M
+from tests.cvmat_model import AS, F32, F64, NAN_BITS, det3, inv3, jacobi, mat, norm, stored, svd3, unit  # noqa: F401 (NAN_BITS is read through this module)
 
-F32, F64 = np.float32, np.float64
 ERR_INVALID = -1
-AS = M.AS
-NAN_BITS = 0x7FC00000
 COS_NONE = F32(2.0)
 H_MODEL, F_MODEL = 0, 1
 MAX_MATCHES, MAX_KEYS = M.MAX_MATCHES, M.MAX_KEYS
-
-
-def stored(a):
-    out = np.array(a, F32)
-    out.view(np.uint32)[np.isnan(out)] = NAN_BITS
-    return out
 
 
 def k_matrix(K4):
@@ -42,56 +34,17 @@ def k_matrix(K4):
     return K
 
 
-def mat(a, b, alpha=None, plus=None):
-    """A cv::Mat product a[R][Kk] * b[Kk][C] (float32): per element a double sum over k in index order, times (double)alpha when
-    given, plus (double)plus[R][C] when given, rounded once."""
-    a, b = np.asarray(a, F32), np.asarray(b, F32)
-    out = np.zeros((a.shape[0], b.shape[1]), F32)
-    for r in range(a.shape[0]):
-        for c in range(b.shape[1]):
-            s = F64(0)
-            for k in range(a.shape[1]):
-                s = s + F64(a[r, k]) * F64(b[k, c])
-            if alpha is not None:
-                s = F64(alpha) * s
-            if plus is not None:
-                s = s + F64(plus[r, c])
-            out[r, c] = F32(s)
-    return out
-
-
-def det3(m):
-    """cv::determinant of a 3 x 3 float matrix: the double expression d of the closed inverse."""
-    m = np.asarray(m, F32).astype(F64)
-    return m[0, 0] * (m[1, 1] * m[2, 2] - m[1, 2] * m[2, 1]) - m[0, 1] * (m[1, 0] * m[2, 2] - m[1, 2] * m[2, 0]) + m[0, 2] * (m[1, 0] * m[2, 1] - m[1, 1] * m[2, 0])
-
-
-def svd3(A):
-    """cv::SVD::compute of a 3 x 3 float matrix: (u, w float32[3], vt)."""
-    At = np.zeros((1, 3, AS), F32)
-    for i in range(3):
-        for k in range(3):
-            At[0, i, k] = A[k, i]
-    At, Vt, W, _ = M.jacobi(At, 3, 3)
-    u = np.zeros((3, 3), F32)
-    for i in range(3):
-        s = F32(F64(1) / W[0, i]) if W[0, i] > M.FLT_MIN else F32(0)
-        for k in range(3):
-            u[k, i] = At[0, i, k] * s
-    return u, W[0].astype(F32), Vt[0, :, :3].copy()
-
-
-def unit(t):
-    """t / cv::norm(t): a scale by (float)(1.0 / norm), the norm a double sum of double squares and one sqrt; no zero test."""
-    d = np.sqrt(F64(t[0]) * F64(t[0]) + F64(t[1]) * F64(t[1]) + F64(t[2]) * F64(t[2]))
-    return (np.asarray(t, F32) * F32(F64(1.0) / d)).astype(F32)
+def _svd3(A):
+    """cv::SVD::compute of one 3 x 3 float matrix: (u, w float32[3], vt)."""
+    u, w, vt, _ = svd3(A[None])
+    return u[0], w[0], vt[0]
 
 
 def decompose_e(F21, K4):
     """ReconstructF's four motion hypotheses (:478-496) in the reference's order."""
     K = k_matrix(K4)
     E = mat(mat(K.T, F21), K)
-    u, _, vt = svd3(E)
+    u, _, vt = _svd3(E)
     t = unit(u[:, 2])
     Wm = np.array([[0, -1, 0], [1, 0, 0], [0, 0, 1]], F32)
     R1 = mat(mat(u, Wm), vt)
@@ -106,8 +59,8 @@ def decompose_e(F21, K4):
 def decompose_h(H21, K4):
     """ReconstructH's eight motion hypotheses (:583-685): (early, vR, vt); early = 2 under the test of :596."""
     K = k_matrix(K4)
-    A = mat(mat(M.inv3(K), H21), K)
-    U, w, Vt = svd3(A)
+    A = mat(mat(inv3(K), H21), K)
+    U, w, Vt = _svd3(A)
     s = F32(det3(U) * det3(Vt))
     d1, d2, d3 = w[0], w[1], w[2]
     if F64(d1 / d2) < 1.00001 or F64(d2 / d3) < 1.00001:
@@ -142,13 +95,6 @@ def camera2(R, t, K4):
     return mat(k_matrix(K4), Rt), mat(R.T, np.asarray(t, F32)[:, None], alpha=-1.0)[:, 0]
 
 
-def _norm(v):
-    s = np.zeros(len(v), F64)
-    for k in range(3):
-        s = s + v[:, k].astype(F64) * v[:, k].astype(F64)
-    return np.sqrt(s)
-
-
 def check_rt(R, t, K4, x1, y1, x2, y2, inlier, th2):
     """CheckRT (:797-906) of one hypothesis over n matches (float32[n] coordinates, bool[n] inlier).  Returns (codes uint8[n],
     cos float32[n], p float32[n][3], q: the tested quantities for the margins of the float64 comparison)."""
@@ -165,24 +111,19 @@ def check_rt(R, t, K4, x1, y1, x2, y2, inlier, th2):
         At[:, c, 2] = x2 * P2[2, c] - P2[0, c]
         At[:, c, 3] = y2 * P2[2, c] - P2[1, c]
     assert At.dtype == F32
-    _, Vt, _, _ = M.jacobi(At, 4, 4)
+    _, Vt, _, _ = jacobi(At, 4, 4)
     v = Vt[:, 3, :4]
     p = v[:, :3] * (F64(1.0) / v[:, 3].astype(F64)).astype(F32)[:, None]
     finite = np.isfinite(p).all(axis=1)
-    dist1 = _norm(p).astype(F32)                     # normal1 = p3dC1 - O1, O1 = 0
+    dist1 = norm(p).astype(F32)                     # normal1 = p3dC1 - O1, O1 = 0
     n2 = p - O2[None, :]
-    dist2 = _norm(n2).astype(F32)
+    dist2 = norm(n2).astype(F32)
     dot = np.zeros(n, F64)
     for k in range(3):
         dot = dot + p[:, k].astype(F64) * n2[:, k].astype(F64)
     cos = (dot / (dist1 * dist2).astype(F64)).astype(F32)
     low = cos.astype(F64) < 0.99998
-    p2 = np.zeros((n, 3), F32)
-    for r in range(3):
-        s = np.zeros(n, F64)
-        for k in range(3):
-            s = s + F64(R[r, k]) * p[:, k].astype(F64)
-        p2[:, r] = (s + F64(t[r])).astype(F32)
+    p2 = mat(R, p[:, :, None], plus=np.asarray(t, F32)[:, None])[:, :, 0]      # R * p3dC1 + t
     inv1 = (F64(1.0) / p[:, 2].astype(F64)).astype(F32)
     ex, ey = ((fx * p[:, 0]) * inv1 + cx) - x1, ((fy * p[:, 1]) * inv1 + cy) - y1
     err1 = ex * ex + ey * ey

@@ -1,21 +1,18 @@
-"""Initializer::FindHomography + FindFundamental off the GPU: hand-made known answers for the literal model (tests/initializer_model.py),
-the model against a float64 restatement with numpy.linalg.svd / inv on the committed scenes (tests/initializer_scenes.py), and the C++ host
+"""Initializer::FindHomography + FindFundamental off the GPU: hand-made known answers for the literal model (tests/initializer_model.py;
+those of the Jacobi, the inverse and the product are in tests/test_cvmat_model.py), the model against a float64 restatement with numpy.linalg.svd / inv on the committed scenes (tests/initializer_scenes.py), and the C++ host
 form (orbslam2_amd/host/Initializer.h, driven by tests/initializer_mirror/mirror_main.cpp) equal to the model bit for bit -- built plain and
 as a stand-alone AddressSanitizer + UBSan program."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import host_forms as H
 from tests import initializer_model as M
 from tests import initializer_scenes as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MIRROR = os.path.join(ROOT, "tests", "initializer_mirror", "mirror_main.cpp")
-HEADER = os.path.join(ROOT, "orbslam2_amd", "host", "Initializer.h")
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-O1", "-g"]
 NAMES = ("orbfe_enqueue_find_homography_fundamental", "orbfe_find_homography_fundamental")
 F32 = np.float32
 # The largest relative deviation of a winner's score, model against the float64 restatement, measured over the two committed scenes on the
@@ -28,76 +25,7 @@ MARGIN = 1e-3            # flags are compared where every chi-square lies furthe
 MAX_LEFT_OUT = 0.01      # ... and the (hypothesis, match) entries left out are at most this share of a scene
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-
-
-# ------------------------------------------------------------------ known answers: the nine-column null vector
-def _null(A):
-    v, info = M.null_vector9(np.array(A, F32))
-    return [float(x) for x in v], info
-
-
-def _e(k):
-    return [1.0 if i == k else 0.0 for i in range(9)]
-
-
-def test_null_vector_of_a_diagonal_matrix_needs_no_rotation_and_only_the_sort():
-    v, info = _null(np.diag([9.0, 8, 0.5, 6, 5, 4, 3, 2, 1]))       # orthogonal columns; the smallest is column 2
-    assert v == _e(2) and info["rotations"] == 0 and info["sweeps"] == 0 and info["swaps"] >= 1
-    v, info = _null(np.diag([9.0, 8, 7, 6, 5, 4, 3, 2, 0]))         # sorted already: Vt row 8 is e8
-    assert v == _e(8) and info["swaps"] == 0
-    v, info = _null(np.diag([0.0, 1, 2, 3, 4, 5, 6, 7, 8]))         # ascending: the selection sort swaps (0, 8), (1, 7), (2, 6), (3, 5)
-    assert v == _e(0) and info["swaps"] == 4
-    v, info = _null(np.eye(9))                                      # equal singular values: strict < keeps the first, row 8 stays e8
-    assert v == _e(8) and info["swaps"] == 0
-    tall = np.zeros((16, 9)); tall[3:12] = np.diag([9.0, 8, 7, 6, 0.25, 4, 3, 2, 1])    # 16 rows, as ComputeH21's matrix
-    assert _null(tall)[0] == _e(4)
-
-
-def test_null_vector_first_rotation_takes_either_branch_of_beta():
-    A = np.diag([0.0, 0, 3, 4, 5, 6, 7, 8, 9]); A[0, :2] = 1; A[1, :2] = 2                 # columns 0 and 1 equal: the kernel is (1, -1, 0, ...) / sqrt(2)
-    v, info = _null(A)
-    assert info["first_beta_negative"] == 0 and info["rotations"] >= 1                     # equal norms: beta == 0 takes the else branch
-    assert abs(abs(v[0]) - 2 ** -0.5) < 1e-6 and abs(v[0] + v[1]) < 1e-6 and v[2:] == [0.0] * 7
-    B = np.diag([1.0, 1, 3, 4, 5, 6, 7, 8, 9]); B[0, 1] = 2                                  # |col 0|^2 = 1 < |col 1|^2 = 5
-    assert _null(B)[1]["first_beta_negative"] == 1
-    assert _null(B[:, [1, 0, 2, 3, 4, 5, 6, 7, 8]])[1]["first_beta_negative"] == 0
-    rng = np.random.default_rng(3)
-    for rows in (16, 9):                                            # full rank: Vt row 8 is the right singular vector of the smallest singular value
-        mat = rng.normal(size=(rows, 9)).astype(F32)
-        v = np.array(_null(mat)[0])
-        want = np.linalg.svd(mat.astype(np.float64))[2][8]
-        assert min(np.abs(v - want).max(), np.abs(v + want).max()) < 2e-6
-
-
-def test_an_eight_row_matrix_is_padded_with_a_zero_ninth_row():
-    """ComputeF21's 8 x 9 matrix: the contract pads a zero row.  More zero rows change no bit (x + 0 * 0 == x), which is what lets the
-    kernel run both models on one 16-entry row stride; the answer spans the null space of the eight rows."""
-    rng = np.random.default_rng(4)
-    A = rng.normal(size=(8, 9)).astype(F32)
-    v8, info = M.null_vector9(A)
-    v9 = M.null_vector9(np.concatenate([A, np.zeros((1, 9), F32)]))[0]
-    v16 = M.null_vector9(np.concatenate([A, np.zeros((8, 9), F32)]))[0]
-    assert np.array_equal(_bits(v8), _bits(v9)) and np.array_equal(_bits(v8), _bits(v16))
-    assert abs(np.linalg.norm(v8.astype(np.float64)) - 1) < 1e-6 and np.abs(A.astype(np.float64) @ v8).max() < 2e-6
-    assert info["sweeps"] == M.MAX_SWEEPS        # a column of exact rank deficiency never meets the relative test: the sweep cap ends it
-
-
-# ------------------------------------------------------------------ known answers: 3 x 3 steps
-def test_the_inverse_is_opencv_s_closed_form_and_a_zero_determinant_gives_the_zero_matrix():
-    assert np.array_equal(M.inv3(np.diag([2.0, 4.0, 8.0]).astype(F32)), np.diag([0.5, 0.25, 0.125]).astype(F32))
-    singular = np.array([[1, 2, 3], [2, 4, 6], [0, 0, 0]], F32)
-    assert np.array_equal(M.inv3(singular), np.zeros((3, 3), F32))
-    one_row = np.zeros((3, 3), F32); one_row[0] = [203.65, 0.1, 0.84]
-    assert np.array_equal(M.inv3(one_row), np.zeros((3, 3), F32))
-    T = M.t_matrix(np.array([310.5, 236.25, 0.0078125, 0.0107421875], F32))     # Normalize's T: the inverse is (1 / sX, 1 / sY, meanX, meanY)
-    want = np.array([[128.0, 0, 310.5], [0, 1 / 0.0107421875, 236.25], [0, 0, 1]])
-    assert np.allclose(M.inv3(T), want, rtol=1e-7)
-    batch = np.stack([singular, np.diag([2.0, 4.0, 8.0]).astype(F32)])
-    assert np.array_equal(M.inv3(batch)[0], np.zeros((3, 3), F32)) and M.inv3(batch)[1][0, 0] == 0.5
-    a, b = np.arange(9, dtype=F32).reshape(3, 3), np.array([[1, 0, 2], [0, 3, 0], [4, 0, 5]], F32)
-    assert np.array_equal(M.mul3(a, b), (a.astype(np.float64) @ b.astype(np.float64)).astype(F32))
+_bits = H.bits
 
 
 def test_normalize_is_the_sequential_float_sum():
@@ -259,19 +187,10 @@ def test_a_faulty_index_is_reported_and_skipped(fault):
 
 
 # ------------------------------------------------------------------ the C++ host form
-def _build(tmp_path, name, flags):
-    exe = str(tmp_path / name)
-    r = subprocess.run(["g++", "-std=c++14", "-Wall", "-Wextra", "-ffp-contract=off"] + flags + ["-o", exe, MIRROR], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 def _run(exe, p, tmp_path):
     problem, result = str(tmp_path / "problem.bin"), str(tmp_path / "out.bin")
     S.write_problem_file(p, problem)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, problem, result], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+    H.run(exe, problem, result)
     return S.read_result_file(p, result)
 
 
@@ -284,9 +203,9 @@ def mirror_cases():
     return cases
 
 
-@pytest.mark.parametrize("build", ["plain", "sanitized"])
+@pytest.mark.parametrize("build", H.BUILDS)
 def test_cpp_host_form_equals_the_model_bit_for_bit(tmp_path, build):
-    exe = _build(tmp_path, "mirror_" + build, ["-O2"] if build == "plain" else SAN)
+    exe = H.build(tmp_path, "initializer_mirror", build)
     for what, p in mirror_cases():
         res = S.solve(p)
         want = S.Outputs.expected(p, res)
@@ -309,8 +228,8 @@ def test_cpp_host_form_equals_the_model_bit_for_bit(tmp_path, build):
 
 
 def test_the_host_header_includes_nothing_but_the_c_abi_header():
-    text = open(HEADER).read()
-    assert [ln for ln in text.splitlines() if ln.startswith('#include "')] == ['#include "../../include/orbfe.h"']
+    text = open(H.header("Initializer.h")).read()
+    assert H.project_includes(H.header("Initializer.h")) == H.ABI_AND_CVMAT
     assert "opencv" not in text.lower().replace("opencv's", "").replace("no opencv", "")
 
 

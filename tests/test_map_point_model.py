@@ -2,19 +2,12 @@
 model (tests/map_point_model.py), the census of what the committed scenes decide, and the C++ host mirror
 (orbslam2_amd/host/MapPointUpdate.h, driven by tests/map_point_mirror/mirror_main.cpp) equal to the model bit for bit -- built plain
 and as a stand-alone AddressSanitizer + UBSan program."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+from tests import host_forms as H
 from tests import map_point_model as M
 from tests import map_point_scenes as S
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MIRROR = os.path.join(ROOT, "tests", "map_point_mirror", "mirror_main.cpp")
-HEADER = os.path.join(ROOT, "orbslam2_amd", "host", "MapPointUpdate.h")
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-O1", "-g"]
 
 
 def _d(*bits):
@@ -107,19 +100,10 @@ def test_census_scenes_decide_what_the_kernel_can_get_wrong(census):
 
 
 # ------------------------------------------------------------------ the C++ mirror
-def _build(tmp_path, name, flags):
-    exe = str(tmp_path / name)
-    r = subprocess.run(["g++", "-std=c++14", "-Wall", "-Wextra", "-ffp-contract=off"] + flags + ["-o", exe, MIRROR], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 def _run(exe, s, table, what, tmp_path):
     scene, out = str(tmp_path / "scene.bin"), str(tmp_path / "out.bin")
     S.write_scene_file(s, table, what, scene)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, scene, out], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+    H.run(exe, scene, out)
     return S.read_result_file(s, out)
 
 
@@ -129,10 +113,10 @@ def _same(got, want, what):
         assert np.array_equal(a, b), "%s: column %s differs in rows %s" % (what, k, np.nonzero((a != b).reshape(len(b), -1).any(axis=1))[0][:8].tolist())
 
 
-@pytest.mark.parametrize("build", ["plain", "sanitized"])
+@pytest.mark.parametrize("build", H.BUILDS)
 def test_cpp_mirror_equals_the_model_bit_for_bit(census, tmp_path, build):
     s, before, want, best, status = census
-    exe = _build(tmp_path, "mirror_" + build, ["-O2"] if build == "plain" else SAN)
+    exe = H.build(tmp_path, "map_point_mirror", build)
     got_status, got_best, got = _run(exe, s, before, 3, tmp_path)
     assert got_status == status == 0 and np.array_equal(got_best, best)
     _same(got, want, "census scene")
@@ -154,5 +138,4 @@ def test_cpp_mirror_equals_the_model_bit_for_bit(census, tmp_path, build):
 
 
 def test_the_mirror_header_includes_nothing_but_the_c_abi_header():
-    text = open(HEADER).read()
-    assert [ln for ln in text.splitlines() if ln.startswith('#include "')] == ['#include "../../include/orbfe.h"']
+    assert H.project_includes(H.header("MapPointUpdate.h")) == H.ABI_AND_CVMAT

@@ -6,19 +6,17 @@ program."""
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import host_forms as H
 from tests import initializer_scenes as S
 from tests import reconstruct_model as R
 from tests import reconstruct_scenes as RS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MIRROR = os.path.join(ROOT, "tests", "reconstruct_mirror", "mirror_main.cpp")
 CENSUS = os.path.join(ROOT, "tests", "golden", "reconstruct_census.json")
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-O1", "-g"]
 NAMES = ("orbfe_enqueue_reconstruct_initial", "orbfe_reconstruct_initial")
 F32 = np.float32
 # Measured here, model against the float64 restatement, over the scenes that choose a hypothesis (general, frontal 300, frontal 64,
@@ -44,8 +42,7 @@ EXPECTED = {"general": (1, 228, [1, 2, 227, 2], 0, 2), "planar": (0, 253, [0, 16
             "general forced H": (0, 22, [0, 18, 8, 22, 0, 0, 0, 0], 3, -1)}
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+_bits = H.bits
 
 
 # ------------------------------------------------------------------ problems shared with the device tests
@@ -256,19 +253,10 @@ def test_census_every_code_is_reached_and_the_table_is_the_committed_one():
 
 
 # ------------------------------------------------------------------ the C++ host form
-def _build(tmp_path, name, flags):
-    exe = str(tmp_path / name)
-    r = subprocess.run(["g++", "-std=c++14", "-Wall", "-Wextra", "-ffp-contract=off"] + flags + ["-o", exe, MIRROR], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 def _run(exe, q, tmp_path):
     problem, result = str(tmp_path / "problem.bin"), str(tmp_path / "out.bin")
     RS.write_problem_file(q, problem)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, problem, result], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+    H.run(exe, problem, result)
     return RS.read_result_file(q, result)
 
 
@@ -283,9 +271,9 @@ def mirror_cases():
     return cases
 
 
-@pytest.mark.parametrize("build", ["plain", "sanitized"])
+@pytest.mark.parametrize("build", H.BUILDS)
 def test_cpp_host_form_equals_the_model_bit_for_bit(tmp_path, build):
-    exe = _build(tmp_path, "mirror_" + build, ["-O2"] if build == "plain" else SAN)
+    exe = H.build(tmp_path, "reconstruct_mirror", build)
     for what, q in mirror_cases():
         want = RS.Outputs.expected(q, RS.solve(q))
         got = _run(exe, q, tmp_path)
@@ -305,8 +293,8 @@ def test_cpp_host_form_equals_the_model_bit_for_bit(tmp_path, build):
     # ReconstructAccept: F wants parallax > minParallax, H parallax >= minParallax; 2.0 stands for nGood == 0
     cos5 = float(RS.solved_scene("general")[1]["cos_parallax"][2])
     for model, cos, min_parallax, want in ((1, cos5, 1.0, 1), (1, cos5, 10.0, 0), (0, cos5, 1.0, 1), (1, 2.0, 0.0, 0), (0, 2.0, 0.0, 1), (0, 1.0, 0.0, 1), (1, 1.0, 0.0, 0)):
-        r = subprocess.run([exe, "accept", str(model), repr(cos), repr(min_parallax)], capture_output=True, text=True)
-        assert r.returncode == 0 and int(r.stdout) == want == int(R.accept(model, F32(cos), min_parallax)), (model, cos, min_parallax, r.stdout, r.stderr[-500:])
+        r = H.run(exe, "accept", str(model), repr(cos), repr(min_parallax))
+        assert int(r.stdout) == want == int(R.accept(model, F32(cos), min_parallax)), (model, cos, min_parallax, r.stdout, r.stderr[-500:])
 
 
 # ------------------------------------------------------------------ exports and refusals

@@ -1,23 +1,20 @@
 """The triangulation stage of LocalMapping::CreateNewMapPoints off the GPU: hand-made known answers for the literal model
-(tests/triangulate_model.py), the census of what the committed scenes decide (tests/triangulate_scenes.py), the model against a float64
+(tests/triangulate_model.py; those of its null vector are in tests/test_cvmat_model.py), the census of what the committed scenes decide (tests/triangulate_scenes.py), the model against a float64
 restatement with numpy.linalg.svd, and the C++ host form (orbslam2_amd/host/Triangulate.h, driven by
 tests/triangulate_mirror/mirror_main.cpp) equal to the model bit for bit -- built plain and as a stand-alone AddressSanitizer + UBSan
 program."""
 import collections
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import host_forms as H
 from tests import triangulate_model as M
 from tests import triangulate_scenes as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MIRROR = os.path.join(ROOT, "tests", "triangulate_mirror", "mirror_main.cpp")
-HEADER = os.path.join(ROOT, "orbslam2_amd", "host", "Triangulate.h")
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-O1", "-g"]
 NAME = "orbfe_enqueue_triangulate_pairs"
 F32 = np.float32
 # The largest relative deviation of x3D, model against the float64 restatement, measured over the generic scenes on the CPU is 1.33e-6
@@ -27,40 +24,6 @@ MEASURED_MAX_REL = 1.33e-6
 X3D_REL_TOL = 4 * MEASURED_MAX_REL
 MARGIN = 1e-4            # codes are compared where every gate the float64 form evaluated is decided by more than this, relatively
 MAX_LEFT_OUT = 0.02      # ... and those left out are at most this share of a scene
-
-
-# ------------------------------------------------------------------ known answers: the null vector
-def _null(A):
-    v, info = M.null_vector(np.array(A, F32))
-    return [float(x) for x in v], info
-
-
-def test_null_vector_of_a_diagonal_matrix_needs_no_rotation_and_only_the_sort():
-    v, info = _null(np.diag([3.0, 2.0, 0.5, 1.0]))        # already orthogonal columns; the smallest is column 2
-    assert v == [0.0, 0.0, 1.0, 0.0] and info["rotations"] == 0 and info["sweeps"] == 0 and info["swaps"] == 1
-    v, info = _null(np.diag([4.0, 3.0, 2.0, 0.0]))        # sorted already: Vt row 3 is e3
-    assert v == [0.0, 0.0, 0.0, 1.0] and info["swaps"] == 0
-    v, info = _null(np.diag([0.0, 1.0, 2.0, 3.0]))        # ascending: the selection sort swaps (0, 3) and (1, 2)
-    assert v == [1.0, 0.0, 0.0, 0.0] and info["swaps"] == 2
-    # equal singular values: strict < keeps the first, so the LAST of the equals ends in row 3
-    v, info = _null(np.diag([1.0, 1.0, 1.0, 1.0]))
-    assert v == [0.0, 0.0, 0.0, 1.0] and info["swaps"] == 0
-
-
-def test_null_vector_first_rotation_takes_either_branch_of_beta():
-    """Columns 0 and 1 are not orthogonal; |col 0| < |col 1| gives beta < 0, the swapped matrix beta >= 0.  The null vector of a rank-3
-    matrix with the kernel (1, -1, 0, 0) / sqrt(2) ... is known: columns 0 and 1 equal."""
-    A = np.array([[1, 1, 0, 0], [2, 2, 0, 0], [0, 0, 3, 0], [0, 0, 0, 4]], F32)
-    v, info = _null(A)
-    assert info["first_beta_negative"] is False and info["rotations"] >= 1        # equal norms: beta == 0 takes the else branch
-    assert abs(abs(v[0]) - 2 ** -0.5) < 1e-6 and abs(v[0] + v[1]) < 1e-6 and v[2] == 0 and v[3] == 0
-    B = np.array([[1, 2, 0, 0], [0, 1, 0, 0], [0, 0, 3, 0], [0, 0, 0, 4]], F32)   # |col 0|^2 = 1 < |col 1|^2 = 5
-    assert _null(B)[1]["first_beta_negative"] is True
-    assert _null(B[:, [1, 0, 2, 3]])[1]["first_beta_negative"] is False
-    for mat in (B, B[:, [1, 0, 2, 3]]):                   # full rank: Vt row 3 is the right singular vector of the smallest singular value
-        v = np.array(_null(mat)[0])
-        want = np.linalg.svd(mat.astype(np.float64))[2][3]
-        assert min(np.abs(v - want).max(), np.abs(v + want).max()) < 1e-6
 
 
 # ------------------------------------------------------------------ known answers: one pair per code
@@ -246,24 +209,11 @@ def test_the_call_appends_in_pair_order_and_refuses_a_full_table_whole():
 
 
 # ------------------------------------------------------------------ the C++ host form
-def _build(tmp_path, name, flags):
-    exe = str(tmp_path / name)
-    r = subprocess.run(["g++", "-std=c++14", "-Wall", "-Wextra", "-ffp-contract=off"] + flags + ["-o", exe, MIRROR], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 def _run(exe, p, out, patch, tmp_path):
     problem, result = str(tmp_path / "problem.bin"), str(tmp_path / "out.bin")
     S.write_problem_file(p, out, patch, problem)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, problem, result], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+    H.run(exe, problem, result)
     return S.read_result_file(p, out, result)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
 
 
 def mirror_cases():
@@ -286,9 +236,9 @@ def mirror_cases():
     return cases
 
 
-@pytest.mark.parametrize("build", ["plain", "sanitized"])
+@pytest.mark.parametrize("build", H.BUILDS)
 def test_cpp_host_form_equals_the_model_bit_for_bit(tmp_path, build):
-    exe = _build(tmp_path, "mirror_" + build, ["-O2"] if build == "plain" else SAN)
+    exe = H.build(tmp_path, "triangulate_mirror", build)
     for what, p0, n_rows, rows_used, patch in mirror_cases():
         mine, theirs = S.fresh(p0), S.fresh(p0)
         want = S.Outputs(mine, n_rows, rows_used)
@@ -296,7 +246,7 @@ def test_cpp_host_form_equals_the_model_bit_for_bit(tmp_path, build):
         got_res, got, mp1, mp2 = _run(exe, theirs, S.Outputs(theirs, n_rows, rows_used), patch, tmp_path)
         assert got_res == {k: res[k] for k in ("status", "nnew", "rows_used")}, (what, got_res, res["status"], res["nnew"], res["rows_used"])
         for k in ("code", "x3d", "new") + (("pos",) if n_rows is not None else ()):
-            a, b = _bits(getattr(got, k)), _bits(getattr(want, k))
+            a, b = H.bits(getattr(got, k)), H.bits(getattr(want, k))
             assert np.array_equal(a, b), "%s: %s differs at bytes %s" % (what, k, np.nonzero(a != b)[0][:8].tolist())
         assert np.array_equal(mp1, mine["kf1"]["mp"]) and np.array_equal(mp2, mine["kf2"]["mp"]), what
         if what == "four faulty pairs":
@@ -308,8 +258,7 @@ def test_cpp_host_form_equals_the_model_bit_for_bit(tmp_path, build):
 
 
 def test_the_host_header_includes_nothing_but_the_c_abi_header():
-    text = open(HEADER).read()
-    assert [ln for ln in text.splitlines() if ln.startswith('#include "')] == ['#include "../../include/orbfe.h"']
+    assert H.project_includes(H.header("Triangulate.h")) == H.ABI_AND_CVMAT
 
 
 # ------------------------------------------------------------------ exports

@@ -5,123 +5,38 @@ the reference of tests/test_triangulate_model.py (against orbslam2_amd/host/Tria
 (against the kernel); both must equal it bit for bit.  pair_f64() is the same branch structure in double with numpy.linalg.svd.
 
 Float contract (Q4: no contraction, IEEE divide and sqrt; the OpenCV steps are OPENCV-4.5.5-SEMANTICS, unpinned as DESIGN.md section 2
-says, and stated in section 4k):
+says, and stated in sections 4i2 and 4k; the cv::Mat rules themselves are tests/cvmat_model.py's):
   xn                        ((x - cx) * invfx, (y - cy) * invfy, 1) in float
-  Mat * Mat (3x3 * 3x1)     per element a double sum over k in index order, rounded once to float; `Rwc * x3Dc + Ow` adds Ow in double
-                            before that one rounding
-  Mat::dot, cv::norm        double sums in index order; the norm takes one double sqrt
+  Mat * Mat (3x3 * 3x1)     mat(): `Rwc * x3Dc + Ow` adds Ow in double before the one rounding
+  Mat::dot, cv::norm        double sums in index order; norm() takes one double sqrt
   s * row - row             a float multiply, then a float subtract, per element
-  Mat / float               a scale by (float)(1.0 / w): a product, not a division (section 4j's rule)
+  Mat / float               a scale by (float)(1.0 / w): a product, not a division
   row.dot(x3Dt) + t         double dot + float in double, rounded to float
-  cv::SVD -> vt.row(3)      null_vector(): one-sided Jacobi on the columns of A
+  cv::SVD -> vt.row(3)      null_vector(A): vt.row(3) and info = dict(sweeps, rotations, first_beta_negative (None: no rotation), swaps)
 A keyframe is a dict: keys_un, keys (structured, x / y / octave), ur, depth, cos (float32[n]), mp (uint8[n], writable), n, Tcw
 (float32[12]), Ow (float32[3]), fx, fy, cx, cy, invfx, invfy (np.float32).
 """
 import numpy as np
 
-F32, F64 = np.float32, np.float64
+from tests.cvmat_model import F32, F64, MAX_SWEEPS, mat, norm, null_vector  # noqa: F401 (MAX_SWEEPS is read through this module)
+
 ERR_INVALID, ERR_CAPACITY = -1, -4
 CREATED_MAX = 2          # a pair is created iff its code is <= 2
 (TRIANGULATED, STEREO1, STEREO2, LOW_PARALLAX, W_ZERO, Z1, Z2, REPROJ1, REPROJ2, ZERO_DIST, SCALE, FAULTY) = range(12)
-EPS = F64(np.finfo(F32).eps) * F64(2)   # 2 * FLT_EPSILON, as a double
-MAX_SWEEPS = 30
 TRACE = None
 
 
-# ------------------------------------------------------------------ the null vector
-def null_vector(A):
-    """vt.row(3) of cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) for a 4x4 float A, restated: one-sided (Hestenes) Jacobi on the
-    columns of A.  Returns (the four floats, info) with info = dict(sweeps, rotations, first_beta_negative, swaps)."""
-    At = [[F32(A[k][i]) for k in range(4)] for i in range(4)]
-    Vt = [[F32(1) if i == k else F32(0) for k in range(4)] for i in range(4)]
-    W = [F64(0)] * 4
-    for i in range(4):
-        sd = F64(0)
-        for k in range(4):
-            sd = sd + F64(At[i][k]) * F64(At[i][k])
-        W[i] = sd
-    info = dict(sweeps=0, rotations=0, first_beta_negative=None, swaps=0)
-    for _ in range(MAX_SWEEPS):
-        changed = False
-        for i in range(3):
-            for j in range(i + 1, 4):
-                a, b, p = W[i], W[j], F64(0)
-                for k in range(4):
-                    p = p + F64(At[i][k]) * F64(At[j][k])
-                if abs(p) <= EPS * np.sqrt(a * b):
-                    continue
-                p = p * F64(2)
-                beta = a - b
-                gamma = np.sqrt(p * p + beta * beta)
-                if info["first_beta_negative"] is None:
-                    info["first_beta_negative"] = bool(beta < 0)
-                if beta < 0:
-                    s = F32(np.sqrt(((gamma - beta) * F64(0.5)) / gamma))
-                    c = F32(p / (gamma * F64(s) * F64(2)))
-                else:
-                    c = F32(np.sqrt((gamma + beta) / (gamma * F64(2))))
-                    s = F32(p / (gamma * F64(c) * F64(2)))
-                a, b = F64(0), F64(0)
-                for k in range(4):
-                    t0 = F32(F32(c * At[i][k]) + F32(s * At[j][k]))
-                    t1 = F32(F32(-s * At[i][k]) + F32(c * At[j][k]))
-                    At[i][k], At[j][k] = t0, t1
-                    a = a + F64(t0) * F64(t0)
-                    b = b + F64(t1) * F64(t1)
-                W[i], W[j] = a, b
-                changed = True
-                info["rotations"] += 1
-                for k in range(4):
-                    t0 = F32(F32(c * Vt[i][k]) + F32(s * Vt[j][k]))
-                    t1 = F32(F32(-s * Vt[i][k]) + F32(c * Vt[j][k]))
-                    Vt[i][k], Vt[j][k] = t0, t1
-        if not changed:
-            break
-        info["sweeps"] += 1
-    for i in range(4):
-        sd = F64(0)
-        for k in range(4):
-            sd = sd + F64(At[i][k]) * F64(At[i][k])
-        W[i] = np.sqrt(sd)
-    for i in range(3):
-        j = i
-        for k in range(i + 1, 4):
-            if W[j] < W[k]:
-                j = k
-        if i != j:
-            W[i], W[j] = W[j], W[i]
-            Vt[i], Vt[j] = Vt[j], Vt[i]
-            info["swaps"] += 1
-    return list(Vt[3]), info
-
-
-# ------------------------------------------------------------------ cv::Mat steps
+# ------------------------------------------------------------------ cv::Mat steps (tests/cvmat_model.py's rules on a Tcw of 12 floats)
 def _rwc_times(T, x, plus=None):
-    """Rwc * x (+ Ow): Rwc[i][k] = Tcw[k][i]; a double sum over k, one rounding."""
-    out = []
-    for i in range(3):
-        s = F64(0)
-        for k in range(3):
-            s = s + F64(T[4 * k + i]) * F64(x[k])
-        if plus is not None:
-            s = s + F64(plus[i])
-        out.append(F32(s))
-    return out
+    """Rwc * x (+ Ow): Rwc = Rcw.t()."""
+    Rcw = np.asarray(T, F32).reshape(3, 4)[:, :3]
+    return mat(Rcw.T, np.asarray(x, F32)[:, None], plus=None if plus is None else np.asarray(plus, F32)[:, None])[:, 0]
 
 
 def _row_dot_plus(T, r, X):
     """Rcw.row(r).dot(x3Dt) + tcw(r): the double dot plus the float, rounded to float."""
-    s = F64(0)
-    for k in range(3):
-        s = s + F64(T[4 * r + k]) * F64(X[k])
-    return F32(s + F64(T[4 * r + 3]))
-
-
-def _norm(v):
-    s = F64(0)
-    for k in range(3):
-        s = s + F64(v[k]) * F64(v[k])
-    return np.sqrt(s)
+    T = np.asarray(T, F32).reshape(3, 4)
+    return mat(T[r:r + 1, :3], np.asarray(X, F32)[:, None], plus=T[r:r + 1, 3:])[0, 0]
 
 
 def _xn(kf, kp):
@@ -170,7 +85,7 @@ def pair(kf1, kf2, idx1, idx2, mbf, ratio_factor, sf, s2):
     dot = F64(0)
     for k in range(3):
         dot = dot + F64(ray1[k]) * F64(ray2[k])
-    cos_rays = F32(dot / (_norm(ray1) * _norm(ray2)))
+    cos_rays = F32(dot / (norm(ray1) * norm(ray2)))
     cos_stereo = F32(cos_rays + F32(1))
     cos1 = cos2 = cos_stereo
     if stereo1:
@@ -207,8 +122,8 @@ def pair(kf1, kf2, idx1, idx2, mbf, ratio_factor, sf, s2):
         return REPROJ1, None, info
     if _reprojection_fails(kf2, kp2, ur2, stereo2, X, z2, mbf, s2[o2]):
         return REPROJ2, None, info
-    dist1 = F32(_norm([F32(X[k] - kf1["Ow"][k]) for k in range(3)]))
-    dist2 = F32(_norm([F32(X[k] - kf2["Ow"][k]) for k in range(3)]))
+    dist1 = F32(norm([F32(X[k] - kf1["Ow"][k]) for k in range(3)]))
+    dist2 = F32(norm([F32(X[k] - kf2["Ow"][k]) for k in range(3)]))
     if dist1 == 0 or dist2 == 0:
         return ZERO_DIST, None, info
     ratio_dist = F32(dist2 / dist1)

@@ -146,6 +146,19 @@ def timeit(fn, reps):
     return (time.perf_counter() - t0) / reps * 1e3
 
 
+def host_shim(name, symbol, extra=()):
+    """A host form of orbslam2_amd/host/ behind one C symbol (tools/<name>_host_shim.cpp), built here; returns the ctypes function."""
+    import ctypes as C
+    import subprocess
+    import tempfile
+    so = os.path.join(os.environ.get("BENCH_OUT") or tempfile.mkdtemp(), name + "_host_shim.so")
+    src = os.path.join(ROOT, "tools", name + "_host_shim.cpp")
+    subprocess.run(["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-shared", "-fPIC"] + list(extra) + ["-o", so, src], check=True)
+    host = getattr(C.CDLL(so), symbol)
+    host.restype = C.c_int
+    return host
+
+
 def resident_async_rows(ctx2, out, fs, fb, fk, fur, v_dev, args_sync):
     """Rows (a), (b), (c) of the asynchronous matcher on the resident scene; arguments prepared once, C ABI called directly."""
     import ctypes as C
@@ -1063,8 +1076,6 @@ def bow_kf_rows(out):
 def map_point_rows(out):
     """Rows of --map-points; arguments prepared once."""
     import ctypes as C
-    import subprocess
-    import tempfile
     import torch
     from orbslam2_amd import api
     from tests import map_point_scenes as S
@@ -1077,11 +1088,7 @@ def map_point_rows(out):
     s = S.build(dict(zip(ns.tolist(), cnt.tolist())), n_kfs=60, kp_range=(1500, 1500), bad_fraction=0.05, seed=9, scale=scale)
     n_upd, n_obs, n_kfs = len(s["n_of"]), len(s["obs_kf"]), len(s["kf_n"])
     out["scene"] = "%d points, %d observations (2..40 per point), %d keyframes of 1500 keypoints, %d of them bad" % (n_upd, n_obs, n_kfs, int(s["kf_bad"].sum()))
-    # the host form: MapPointUpdate.h behind one C symbol, built here
-    so = os.path.join(os.environ.get("BENCH_OUT") or tempfile.mkdtemp(), "map_point_host_shim.so")
-    subprocess.run(["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tools", "map_point_host_shim.cpp")], check=True)
-    host = C.CDLL(so).map_point_update_host
-    host.restype = C.c_int
+    host = host_shim("map_point", "map_point_update_host")      # MapPointUpdate.h
     P = lambda a: a.ctypes.data_as(C.c_void_p)
     first = np.concatenate([[0], np.cumsum(s["kf_n"])[:-1]]).astype(np.int64)
     h_desc = np.ascontiguousarray(np.concatenate(s["kf_desc"]))
@@ -1157,8 +1164,6 @@ def map_point_rows(out):
 def create_new_map_points_rows(out):
     """Rows of --create-new-map-points; arguments prepared once."""
     import ctypes as C
-    import subprocess
-    import tempfile
     import torch
     from orbslam2_amd import api
     from tests import triangulate_scenes as NS
@@ -1175,10 +1180,7 @@ def create_new_map_points_rows(out):
     m1 = NS.from_search_keyframe(base["kf1"], poses["T1"], MBF)
     m2s = [NS.from_search_keyframe(sc["kf2"], poses["T2"], MBF) for sc in scs]
     out["scene"] = "KF1 of %d keypoints against %d neighbours of %d (tests/triangulation_scenes.py), bf = 40, half of the keypoints stereo" % (N, K, N)
-    so = os.path.join(os.environ.get("BENCH_OUT") or tempfile.mkdtemp(), "triangulate_host_shim.so")
-    subprocess.run(["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tools", "triangulate_host_shim.cpp")], check=True)
-    host = C.CDLL(so).triangulate_pairs_host
-    host.restype = C.c_int
+    host = host_shim("triangulate", "triangulate_pairs_host")
     host.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + \
         [C.c_int, C.c_void_p, C.c_int]
     st = torch.cuda.Stream()
@@ -1306,8 +1308,6 @@ def create_new_map_points_rows(out):
 def initializer_rows(out):
     """Rows of --initializer; arguments prepared once."""
     import ctypes as C
-    import subprocess
-    import tempfile
     import torch
     from orbslam2_amd import api
     from tests import initializer_scenes as S
@@ -1317,11 +1317,7 @@ def initializer_rows(out):
     n1, n2 = len(p["keys1"]), len(p["keys2"])
     out["scene"] = "%d matches between frames of %d and %d keypoints (tests/initializer_scenes.py, general depth), %d sets, sigma 1" % (N, n1, n2, ITER)
     ctx = api.Context(width=S.WIDTH, height=S.HEIGHT, nfeatures=1000, fx=S.FX, fy=S.FY, cx=S.CX, cy=S.CY, bf=40.0)
-    so = os.path.join(os.environ.get("BENCH_OUT") or tempfile.mkdtemp(), "initializer_host_shim.so")
-    subprocess.run(["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-shared", "-fPIC", "-pthread", "-o", so, os.path.join(ROOT, "tools", "initializer_host_shim.cpp")],
-                   check=True)
-    host = C.CDLL(so).find_homography_fundamental_host
-    host.restype = C.c_int
+    host = host_shim("initializer", "find_homography_fundamental_host", ["-pthread"])
     host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 8 + [C.c_int]
     P = lambda a: a.ctypes.data
     keys1, keys2 = np.ascontiguousarray(p["keys1"]), np.ascontiguousarray(p["keys2"])
@@ -1399,8 +1395,6 @@ def initializer_rows(out):
 def reconstruct_rows(out):
     """Rows of --reconstruct; arguments prepared once.  The inputs are the RANSAC call's own outputs on the --initializer scene."""
     import ctypes as C
-    import subprocess
-    import tempfile
     import torch
     from orbslam2_amd import api
     from tests import initializer_scenes as S
@@ -1411,10 +1405,7 @@ def reconstruct_rows(out):
     out["scene"] = "%d matches between frames of %d and %d keypoints (tests/initializer_scenes.py, general depth), %d sets, sigma 1, min_triangulated 50, model by RH" % (
         N, n1, n2, ITER)
     ctx = api.Context(width=S.WIDTH, height=S.HEIGHT, nfeatures=1000, fx=S.FX, fy=S.FY, cx=S.CX, cy=S.CY, bf=40.0)
-    so = os.path.join(os.environ.get("BENCH_OUT") or tempfile.mkdtemp(), "reconstruct_host_shim.so")
-    subprocess.run(["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tools", "reconstruct_host_shim.cpp")], check=True)
-    host = C.CDLL(so).reconstruct_initial_host
-    host.restype = C.c_int
+    host = host_shim("reconstruct", "reconstruct_initial_host")
     host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 12
     P = lambda a: a.ctypes.data
     keys1, keys2 = np.ascontiguousarray(p["keys1"]), np.ascontiguousarray(p["keys2"])
