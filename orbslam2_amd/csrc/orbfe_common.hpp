@@ -56,14 +56,17 @@ __host__ __forceinline__ int xcd_grid(int blocks_per_unit, int n_units)
 // a / b for 0 <= a < 2^21, b >= 1: exact through the 1-ulp reciprocal (the quotient's distance to the next integer, 0.5 / b,
 // exceeds (a / b) * 2^-22); six VALU operations instead of the compiler's integer-division sequence
 __device__ __forceinline__ int small_div(int a, int b) { return (int)(((float)a + 0.5f) * __builtin_amdgcn_rcpf((float)b)); }
-__device__ __forceinline__ bool xcd_map_of(int bid, int blocks_per_unit, int n_units, int &unit, int &blk); // the same for workgroup `bid` of a grid whose first (multiple of 8) workgroups do something else
+// reverse: every XCD takes its units in the opposite order (round -> rounds - 1 - round; a unit keeps its XCD and its blocks their
+// order), for a launch that reads what an earlier launch with the forward map wrote: the units written last are read first, while
+// they may still be in the Infinity Cache.  The grid is xcd_grid()'s either way; the last, partly filled round then comes first.
+__device__ __forceinline__ bool xcd_map_of(int bid, int blocks_per_unit, int n_units, int &unit, int &blk, bool reverse = false); // the same for workgroup `bid` of a grid whose first (multiple of 8) workgroups do something else
 __device__ __forceinline__ bool xcd_map(int blocks_per_unit, int n_units, int &unit, int &blk) { return xcd_map_of((int)blockIdx.x, blocks_per_unit, n_units, unit, blk); }
-__device__ __forceinline__ bool xcd_map_of(int bid, int blocks_per_unit, int n_units, int &unit, int &blk)
+__device__ __forceinline__ bool xcd_map_of(int bid, int blocks_per_unit, int n_units, int &unit, int &blk, bool reverse)
 {
     const int lg = xcd_split_log2(n_units), xcd = bid & 7, jb = bid >> 3;
     const int per_xcd = (blocks_per_unit + (1 << lg) - 1) >> lg;
     const int round = small_div(jb, per_xcd); // jb < 2^21: at most 2^24 blocks per launch (the planner refuses blocks x images >= 2^23)
-    unit = round * (8 >> lg) + (xcd >> lg);
+    unit = (reverse ? ((n_units + (8 >> lg) - 1) >> (3 - lg)) - 1 - round : round) * (8 >> lg) + (xcd >> lg);
     blk = ((jb - round * per_xcd) << lg) + (xcd & ((1 << lg) - 1));
     return unit < n_units && blk < blocks_per_unit;
 }
@@ -78,13 +81,13 @@ __host__ __forceinline__ uint32_t xcd_map_magic_host(int blocks_per_unit, int n_
     if (per_xcd <= 1 || (unsigned long long)per_xcd * rounds * (unsigned long long)per_xcd >= (1ull << 32)) return 0u;
     return (uint32_t)(((1ull << 32) + (unsigned long long)per_xcd - 1ull) / (unsigned long long)per_xcd);
 }
-__device__ __forceinline__ bool xcd_map_of_magic(int bid, int blocks_per_unit, int n_units, uint32_t magic, int &unit, int &blk)
+__device__ __forceinline__ bool xcd_map_of_magic(int bid, int blocks_per_unit, int n_units, uint32_t magic, int &unit, int &blk, bool reverse = false)
 {
-    if (magic == 0u) return xcd_map_of(bid, blocks_per_unit, n_units, unit, blk);
+    if (magic == 0u) return xcd_map_of(bid, blocks_per_unit, n_units, unit, blk, reverse);
     const int lg = xcd_split_log2(n_units), xcd = bid & 7, jb = bid >> 3;
     const int per_xcd = (blocks_per_unit + (1 << lg) - 1) >> lg;
     const int round = (int)__builtin_amdgcn_readfirstlane((int)(((unsigned long long)(unsigned)jb * (unsigned long long)magic) >> 32)); // uniform: s_mul_hi_u32
-    unit = round * (8 >> lg) + (xcd >> lg);
+    unit = (reverse ? ((n_units + (8 >> lg) - 1) >> (3 - lg)) - 1 - round : round) * (8 >> lg) + (xcd >> lg);
     blk = ((jb - round * per_xcd) << lg) + (xcd & ((1 << lg) - 1));
     return unit < n_units && blk < blocks_per_unit;
 }
@@ -214,16 +217,18 @@ __device__ __forceinline__ const uint8_t *level_image(const DeviceConfig &cfg, c
     return level_image_at(cfg, buf, img, level, L.pitch, L.pyr_off, pitch);
 }
 
-// 16 bytes from an address that is only 4-byte aligned: one global_load_dwordx4 (fine on this memory system).  A plain struct
-// load rather than __builtin_memcpy into an array element, which demotes the array to scratch memory.
-struct __attribute__((packed, aligned(4))) orbfe_u4_unaligned { uint32_t x, y, z, w; };
-__device__ __forceinline__ uint4 load16_unaligned(const uint8_t *p)
+// 16 bytes, one global_load_dwordx4, in two forms named after the alignment the ADDRESS must have:
+//   load16_a4:  a multiple of 4 (not of 16).  The texture addresser serves it like an aligned load.
+//   load16_any: any byte address (the target runs in unaligned access mode).  Off a 4-byte boundary it costs the texture addresser
+//               about two aligned loads (tools/experiments/README.md), so a kernel that is bound by the addresser loads at the
+//               boundary below with load16_a4 and realigns in registers (blur of level 0, level-1 resize, describe_kernel).
+// A plain struct load rather than __builtin_memcpy into an array element, which demotes the array to scratch memory.
+struct __attribute__((packed, aligned(4))) orbfe_u4_a4 { uint32_t x, y, z, w; };
+__device__ __forceinline__ uint4 load16_a4(const uint8_t *p)
 {
-    const orbfe_u4_unaligned t = *(const orbfe_u4_unaligned *)p;
+    const orbfe_u4_a4 t = *(const orbfe_u4_a4 *)p;
     return make_uint4(t.x, t.y, t.z, t.w);
 }
-
-// 16 bytes from ANY byte address (still one global_load_dwordx4: the target runs in unaligned access mode)
 struct __attribute__((packed, aligned(1))) orbfe_u4_any { uint32_t x, y, z, w; };
 __device__ __forceinline__ uint4 load16_any(const uint8_t *p)
 {

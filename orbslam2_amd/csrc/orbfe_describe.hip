@@ -10,8 +10,9 @@
 // The kernel is bound by vector-memory INSTRUCTION issue: the texture addresser spends >= 16 cycles on a wave64 load
 // whatever its width (TA busy 73 % with twelve dword loads per keypoint), so a keypoint's patches are fetched with THREE
 // 128-bit loads and all per-pixel / per-sample accesses are LDS reads:
-//   raw patch (IC_Angle, hp == 15): 31 rows x 32 bytes from column cx - 15 (unaligned 16-byte loads are fine on this memory
-//     system): lane = (row, half), one load for the whole patch, stored lane-linear (row pitch 32 B = the 31 x 8 word grid of
+//   raw patch (IC_Angle, hp == 15): 31 rows x 32 bytes from column cx - 15 (a 16-byte load at any byte address is one
+//     instruction, but off a 4-byte boundary the L1 counts it twice: describe_kernel realigns in registers, this kernel does
+//     not): lane = (row, half), one load for the whole patch, stored lane-linear (row pitch 32 B = the 31 x 8 word grid of
 //     the moment weights, no byte alignment step);
 //   blurred patch (descriptor): 40 rows from a row that is a multiple of 4 = ten tile rows, in each of which the patch's ten
 //     4 x 4 px blocks are 160 contiguous bytes (blur_kernel's layout): lane = (tile row, block), two loads.
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(256, 8) void describe_generic_kernel(DeviceConfig c
         wb[k] = (uint32_t)tr | ((uint32_t)(16 * bl) << 8) | ((uint32_t)(tr * 4 * DS_PATCH_W + 4 * bl) << 16);
     }
     auto fetch_raw = [&](const uint8_t *base /* uniform: pixel (cx - 15, cy - 15) */, int pitch) {
-        pr = load16_unaligned(base + (unsigned)(__mul24(raw_row, pitch) + raw_h16)); // 16 bytes at any alignment: one global_load_dwordx4
+        pr = load16_any(base + (unsigned)(__mul24(raw_row, pitch) + raw_h16)); // 16 bytes at any alignment: one global_load_dwordx4
     };
     // the blurred pyramid is stored in 32 x 4 px tiles of 128 B, each eight 4 x 4 px blocks of 16 B (blur_kernel): the block
     // of pixels X .. X + 3 (X a multiple of 4) x rows 4 T .. 4 T + 3 is at T * tile_row_bytes + 4 * X, its rows 4 bytes apart
@@ -287,7 +288,20 @@ __global__ __launch_bounds__(256, 8) void describe_generic_kernel(DeviceConfig c
 //  * the rBRIEF pattern sits in LDS as four floats per test (one ds_read_b128 instead of a word and eight unpack / convert
 //    instructions per round), and cvRound is one fp32 add of 1.5 * 2^23 (round-half-even in the add's own rounding; exact for
 //    |x| < 2^22): the sum's low bits are the integer, its bias goes into the LDS base address through a 24-bit multiply.
+// Round 7 (profiles/describe_align.json; the kernel is bound by the texture addresser and waits for its patch fills):
+//  * the raw patch's loads start on 4-byte boundaries and the rows are shifted back in registers (pass 1 below): L1 accesses per
+//    keypoint 209 -> 130, - 2.7 us;
+//  * every XCD takes its images in the reverse of the order in which FAST's launch (which also writes the blurred tiles) reached
+//    them, so that the images written last are read first: - 9.9 us.  Outputs go to their final indices, nothing downstream sees it.
 // ---------------------------------------------------------------------------
+// The two measures of tools/experiments/README.md "describe: aligned raw loads, reversed image order", each a compile-time switch so
+// that tools/ab/describe_align_ab.sh can build the kernel with and without it (make describe-ab):
+#ifndef ORBFE_DESC_ALIGN
+#define ORBFE_DESC_ALIGN 1 // raw patch through 4-byte-aligned loads, realigned in registers
+#endif
+#ifndef ORBFE_DESC_REV
+#define ORBFE_DESC_REV 1   // every XCD takes its images in the reverse of FAST's order (xcd_map_of: reverse)
+#endif
 typedef const __attribute__((address_space(3))) uint8_t *ds_lds_cptr; // LDS pointers are 32 bits wide
 #define DS_LGKM0 0xc07f // s_waitcnt lgkmcnt(0) only: vmcnt / expcnt fields at their maxima (prefetches stay in flight)
 __global__ __launch_bounds__(256, 8) void describe_kernel(DeviceConfig cfg, DeviceBuffers buf, int n_images, int stereo /* row-list workgroups ahead of the descriptor ones; 0: no stereo stage */ ORBFE_CUT_PARAM)
@@ -311,7 +325,7 @@ __global__ __launch_bounds__(256, 8) void describe_kernel(DeviceConfig cfg, Devi
     }
     const int bpi = (cfg.sel_total + 4 * DS_KPW - 1) / (4 * DS_KPW); // blocks per image (XCD-aware map: see describe_generic_kernel)
     int img, blk;
-    if (!xcd_map_of_magic(bid, bpi, n_images, cfg.xcd_magic, img, blk)) return;
+    if (!xcd_map_of_magic(bid, bpi, n_images, cfg.xcd_magic, img, blk, ORBFE_DESC_REV != 0)) return;
     const int slot0 = blk * (4 * DS_KPW) + wave * DS_KPW;
     const int *sel_cnt = buf.sel_cnt + (size_t)img * cfg.nlevels;
     if (blk == 0 && tid == 0) {
@@ -381,15 +395,43 @@ __global__ __launch_bounds__(256, 8) void describe_kernel(DeviceConfig cfg, Devi
     // row v = row - 15 (lanes 62 / 63 repeat row 30 with zero weights)
     const int raw_row = (lane >> 1) < 31 ? (lane >> 1) : 30, raw_h16 = (lane & 1) << 4;
     uint4 pr[DS_KPW];
+#if ORBFE_DESC_ALIGN
+    // A row's 32 bytes start at column cx - 15: any byte address (three keypoints of four; level 0 read in place has a pitch of any
+    // value, so there the misalignment o differs from row to row), and a 128-bit load off a 4-byte boundary costs the texture
+    // addresser about two.  So a lane loads its 16 bytes from the 4-byte boundary below, o = address & 3 bytes early, and pass 1
+    // shifts the row back with v_alignbyte_b32 (the word after a lane's four: the other half's first, by DPP).  The two windows
+    // then end at u = 16 - o, and the rows whose circle reaches beyond that (u = 15 with o >= 2, u = 14 with o = 3: |v| <= 3 and
+    // |v| <= 6, read off the lane's own weight word) take the next aligned word as well: at most 13 lanes of the wave.
+    // Bounds: a keypoint lies >= edge_threshold >= 19 px inside its level on every side (orbfe_create refuses less), so the
+    // aligned windows (columns >= cx - 18 of rows >= cy - 15, <= cx + 16 of rows <= cy + 15) and the extra word (columns
+    // <= cx + 18 of rows <= cy + 6) are pixels of the level itself: no byte of a margin, of another image or past the caller's
+    // packed buffer is touched, whatever the pitch.
+    uint32_t pt[DS_KPW]; // the extra word
+    unsigned ro[DS_KPW]; // o
+    const unsigned tail_from = !(lane & 1) ? 3u : ((mw1.w >> 16) & 1u) ? 1u : ((mw1.w >> 8) & 1u) ? 2u : 3u; // o above which this lane needs the extra word (byte j of mw1.w: u = 13 + j)
+#pragma unroll
+    for (int i = 0; i < DS_KPW; i++) {
+        pr[i] = make_uint4(0u, 0u, 0u, 0u); pt[i] = 0u; ro[i] = 0u;
+        if (hv[i]) {
+            int lp;
+            const uint8_t *base = level_image(cfg, buf, img, lvv[i], lp) + (ptrdiff_t)(cyv[i] - 15) * lp + (cxv[i] - 15);
+            const uint8_t *p = base + (unsigned)(__mul24(raw_row, lp) + raw_h16);
+            ro[i] = (unsigned)(uintptr_t)p & 3u;
+            pr[i] = load16_a4(p - ro[i]);
+            if (ro[i] > tail_from) pt[i] = *(const uint32_t *)(p - ro[i] + 16);
+        }
+    }
+#else
 #pragma unroll
     for (int i = 0; i < DS_KPW; i++) {
         pr[i] = make_uint4(0u, 0u, 0u, 0u);
         if (hv[i]) {
             int lp;
             const uint8_t *base = level_image(cfg, buf, img, lvv[i], lp) + (ptrdiff_t)(cyv[i] - 15) * lp + (cxv[i] - 15);
-            pr[i] = load16_unaligned(base + (unsigned)(__mul24(raw_row, lp) + raw_h16)); // 16 bytes at any alignment: one global_load_dwordx4
+            pr[i] = load16_any(base + (unsigned)(__mul24(raw_row, lp) + raw_h16)); // 16 bytes at any alignment: one global_load_dwordx4
         }
     }
+#endif
     // blurred patches: block i = lane + 64 k of the 10 x 10 grid of 4 x 4 px blocks (layout: describe_generic_kernel)
     uint32_t wb[2];
 #pragma unroll
@@ -412,6 +454,16 @@ __global__ __launch_bounds__(256, 8) void describe_kernel(DeviceConfig cfg, Devi
 #pragma unroll
     for (int i = 0; i < DS_KPW; i++) {
         if (!hv[i]) continue;
+#if ORBFE_DESC_ALIGN
+        {   // the lane's 16 pixels from the 20 bytes around them: words 1 .. 4 shifted down by o bytes into words 0 .. 3
+            const uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)pr[i].x, 0xF5, 0xf, 0xf, true); // quad_perm [1,1,3,3]: the odd neighbour's first word
+            const uint32_t w4 = (lane & 1) ? pt[i] : nx;
+            pr[i].x = __builtin_amdgcn_alignbyte(pr[i].y, pr[i].x, ro[i]);
+            pr[i].y = __builtin_amdgcn_alignbyte(pr[i].z, pr[i].y, ro[i]);
+            pr[i].z = __builtin_amdgcn_alignbyte(pr[i].w, pr[i].z, ro[i]);
+            pr[i].w = __builtin_amdgcn_alignbyte(w4, pr[i].w, ro[i]);
+        }
+#endif
         // IC_Angle (src/ORBextractor.cc:72-99): m10 = sum u I = sum (u + 16) I - 16 sum I, m01 = sum v I; integer sums, any order
         unsigned acc_u = __builtin_amdgcn_udot4(pr[i].x, mwu.x, 0u, false);
         acc_u = __builtin_amdgcn_udot4(pr[i].y, mwu.y, acc_u, false);

@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void ingest16_kernel(DeviceConfig cfg, DeviceB
         for (int i = threadIdx.x; i < ni; i += 256) {
             const int r = small_div(i, ci), c = 1 + i - r * ci;
             const int y = y_first + r, x0 = c * 16 - PYR_MX;
-            const uint4 v = load16_unaligned(simg + (size_t)reflect101(y, L.h) * L.w + x0);
+            const uint4 v = load16_any(simg + (size_t)reflect101(y, L.h) * L.w + x0);
             *(uint4 *)(dimg + (ptrdiff_t)y * L.pitch + x0) = v;
         }
     }
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256) void pyr_resize_kernel(DeviceConfig cfg, Devic
             for (int u = 0; u < 4; u++) {
                 const int rr = r < n_src ? r : n_src - 1; // past the block: repeat a chunk of its last row (same bytes, same place)
                 di[u] = __mul24(rr, row_bytes) + 16 * c;
-                v[u] = load16_unaligned(sp + (unsigned)(__mul24(rr, S.pitch) + 16 * c));
+                v[u] = load16_a4(sp + (unsigned)(__mul24(rr, S.pitch) + 16 * c));
                 c += dc; r += dr;
                 if (c >= cpr) { c -= cpr; r++; }
             }
@@ -498,7 +498,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void pyr_tail_kernel(DeviceConfig cfg
                 const int rr = r < S.h ? r : S.h - 1; // past the level: repeat a chunk of its last row (same words, same place)
                 left[u] = src_words - 4 * c;
                 di[u] = __mul24(rr, src_words) + 4 * c;
-                v[u] = load16_unaligned(sp + (unsigned)(__mul24(rr, S.pitch) + 16 * c));
+                v[u] = load16_a4(sp + (unsigned)(__mul24(rr, S.pitch) + 16 * c));
                 c += dc; r += dr;
                 if (c >= cpr) { c -= cpr; r++; }
             }

@@ -94,7 +94,7 @@ __device__ __forceinline__ void rowlist_wave(const DeviceConfig &cfg, const Devi
 #pragma unroll
         for (int u = 0; u < RL_BATCH; u++) { // all in flight: the only global round trip of the scan
             const int q = qb + u * 64 + lane;
-            xy[u] = q < nq ? load16_unaligned((const uint8_t *)(sxy + 4 * q)) : make_uint4(0u, 0u, 0u, 0u); // an image's slots start on a 4-byte boundary only
+            xy[u] = q < nq ? load16_a4((const uint8_t *)(sxy + 4 * q)) : make_uint4(0u, 0u, 0u, 0u); // an image's slots start on a 4-byte boundary only
             lv4[u] = q < nq ? *(const uint32_t *)(buf.slot_level + 4 * q) : 0u;
         }
 #pragma unroll

@@ -231,8 +231,8 @@ __global__ __launch_bounds__(256) void stereo_match_kernel(DeviceConfig cfg, Dev
         uint32_t lw[3] = {0u, 0u, 0u}, rw[6] = {0u, 0u, 0u, 0u, 0u, 0u};
         if (gl < 11) {
             const unsigned ro = (unsigned)__mul24(gl, (int)job.y);
-            const uint4 a = load16_unaligned(pL + ro);
-            const uint4 b0 = load16_unaligned(pR + ro), b1 = load16_unaligned(pR + ro + 16);
+            const uint4 a = load16_any(pL + ro);
+            const uint4 b0 = load16_any(pR + ro), b1 = load16_any(pR + ro + 16);
             lw[0] = a.x; lw[1] = a.y; lw[2] = a.z;
             rw[0] = b0.x; rw[1] = b0.y; rw[2] = b0.z; rw[3] = b0.w; rw[4] = b1.x; rw[5] = b1.y;
         }
