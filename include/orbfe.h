@@ -513,7 +513,10 @@ int orbfe_kfdb_add(orbfe_context *ctx, const uint32_t *words, const float *weigh
 int orbfe_kfdb_erase(orbfe_context *ctx, int kf_index);
 int orbfe_kfdb_size(orbfe_context *ctx);
 /* Per keyframe: number of words shared with the query and fbow::fBow::score(query, keyframe)
- * (Thirdparty/fbow/src/fbow.cpp:206-256: float products summed in double in word order).  Either output may be NULL. */
+ * (Thirdparty/fbow/src/fbow.cpp:206-256: float products summed in double in word order).  Either output may be NULL.
+ * The query of this call and of both orbfe_detect_*_candidates calls must be strictly ascending in word id, as a
+ * keyframe's words in orbfe_kfdb_add: a repeated word or a descending pair returns ORBFE_ERR_INVALID (O(nq) host check;
+ * the kernel binary-searches the query) and writes no output. */
 int orbfe_kfdb_score(orbfe_context *ctx, const uint32_t *q_words, const float *q_w, int nq, int32_t *common, float *score);
 /* KeyFrameDatabase::DetectRelocalizationCandidates(Frame*) (:196-307).  covis_off / covis_idx = every keyframe's
  * GetBestCovisibilityKeyFrames(10) list in its order (CSR over the database indices).  reloc_score = the keyframes'

@@ -505,6 +505,10 @@ try {
 static int kfdb_scores(orbfe_context *ctx, orbfe_bow_state *st, const uint32_t *q_words, const float *q_w, int nq,
                        std::vector<int> &common, std::vector<uint32_t> &first, std::vector<float> &score)
 {
+    // the kernel binary-searches the query, so an unsorted or repeated word would give a silently wrong answer: refused
+    // like a keyframe's words in orbfe_kfdb_add, whatever the database holds
+    for (int i = 1; i < nq; i++)
+        if (q_words[i] <= q_words[i - 1]) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "BoW words must be strictly ascending (std::map order)");
     const int n_kf = (int)st->db_off.size();
     common.assign(n_kf > 0 ? n_kf : 1, 0); first.assign(n_kf > 0 ? n_kf : 1, 0xffffffffu); score.assign(n_kf > 0 ? n_kf : 1, 0.f);
     if (n_kf == 0 || nq == 0) return ORBFE_OK;
