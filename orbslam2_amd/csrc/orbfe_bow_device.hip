@@ -18,6 +18,8 @@
 //                                the greedy rule of :203-229 only skips frame keypoints matched earlier, so it is sequential only
 //                                inside a node: the wave takes the node's KF features in order, its lanes stride over the node's
 //                                frame features, and the "already matched" flags of a lane's features stay in that lane's registers.
+//                                This is bow_shared_node (the merge-join step: checks, then the 64-way probe) and bow_node_walk<Side>,
+//                                shared with the (KeyFrame, KeyFrame) overload; a Side states what differs between the two.
 //   bow_match_tail_kernel        the rotation histogram needs every node: bins, ComputeThreeMaxima, losers removed, the count,
 //                                and the optional has_point / Xw for orbfe_enqueue_pose_optimization
 // orbfe_enqueue_search_by_bow_batch (Relocalization, src/Tracking.cc:1445-1476: the candidates are independent), the same three
@@ -25,20 +27,22 @@
 // (tail: blockIdx.x) of the caller's orbfe_bow_keyframe array and that row of the outputs.
 // orbfe_enqueue_search_for_triangulation (ORBmatcher::SearchForTriangulation, src/ORBmatcher.cc:652-819; the synchronous form is in
 // orbfe_bow.hip), both keyframes device-resident, three launches:
-//   tri_init_kernel              match12 = -1, status, count, the KF2 "taken" flags in scratch
-//   tri_node_match_kernel        one wave per KF1 node, the shape of bow_node_match with the acceptance rule of :731-779: Hamming <= TH_LOW,
-//                                epipole disc, CheckDistEpipolarLine (orbfe_epipolar.h), last of the equal minima, no ratio test
-//   tri_tail_kernel              rotation histogram, ComputeThreeMaxima, the count, vMatchedPairs by an ordered compaction
+//   tri_init_kernel              match12 = -1, status, count
+//   tri_node_match_kernel        one wave per KF1 node: the sweep of KF2's node list and bow_shared_node, then a loop of its own, the
+//                                shape of bow_node_walk with the acceptance rule of :712-750: Hamming <= TH_LOW, then the gates -- epipole
+//                                disc, CheckDistEpipolarLine (orbfe_epipolar.h) --, last of the equal minima, no ratio test
+//   tri_tail_kernel              match12_tail: rotation histogram, ComputeThreeMaxima, the count, vMatchedPairs by an ordered compaction
 // One call per neighbour, never a batch: CreateNewMapPoints adds points to KF1 between two neighbours.
 // orbfe_enqueue_search_by_bow_kf / _batch (ORBmatcher::SearchByFboW(KeyFrame*, KeyFrame*), src/ORBmatcher.cc:517-650; the synchronous form
 // is in orbfe_bow.hip), both keyframes device-resident, three launches for all candidates of LoopClosing::ComputeSim3:
 //   bowkf_init_kernel            rows of match12 = -1, count, status
-//   bowkf_node_match_kernel      one wave per (KF1 node, candidate): bow_node_walk, the walk bow_node_match_kernel runs, with KF1 as the
+//   bowkf_node_match_kernel      one wave per (KF1 node, candidate): sweep, bow_shared_node and bow_node_walk with BowKfSide: KF1 as the
 //                                query side, valid2 on the candidates, the flag on the KF2 side and the strict bound
 //   bowkf_tail_kernel            match12_tail, the tail tri_tail_kernel runs
 #include "../../include/orbfe.h"
 #include "orbfe_device.h"
 #include "orbfe_host.h"
+#include "orbfe_common.hpp"
 #include "orbfe_bow_vocab.h"
 #include "orbfe_match_resolve.h"
 #include "orbfe_epipolar.h"
@@ -52,9 +56,6 @@ using orbfe_resolve::TH_LOW;
 #define BOW_SEG_LDS 4096   // entries per map that bow_segments_kernel stages in LDS: 32 KB
 #define BOW_REG_CHUNKS 2   // a lane keeps the descriptors of its first two features of a node in registers (nodes up to 128 features)
 #define BOW_FLAG_CHUNKS 64 // a lane keeps the flags of its first 64 features of a node in one 64-bit register (nodes up to 4096 features)
-
-
-typedef unsigned long long u64;
 
 __device__ __forceinline__ int slot_count(const int *n_ptr, int cap)
 {
@@ -270,33 +271,6 @@ __device__ __forceinline__ void bow_match_init(const BowSearch &a)
     if (k < n) a.match[k] = -1;
 }
 
-// Minimum over the wave in six DPP steps (no LDS round trip): inside each quad, inside each row of 16 by two rotations, then the
-// last lane of a row into the next row (rows 1 and 3), of row 1 into rows 2 and 3; lane 63 holds the result.  Lanes a step does
-// not write keep their value, and a minimum does not mind seeing a value twice.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned dpp_min_step(unsigned v)
-{
-    const unsigned t = (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xf, false);
-    return t < v ? t : v;
-}
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v)
-{
-    v = dpp_min_step<0xb1, 0xf>(v);  // quad_perm:[1,0,3,2]
-    v = dpp_min_step<0x4e, 0xf>(v);  // quad_perm:[2,3,0,1]
-    v = dpp_min_step<0x124, 0xf>(v); // row_ror:4
-    v = dpp_min_step<0x128, 0xf>(v); // row_ror:8
-    v = dpp_min_step<0x142, 0xa>(v); // row_bcast:15
-    v = dpp_min_step<0x143, 0xc>(v); // row_bcast:31
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ int hamming256(const uint32_t *a, const uint32_t *b)
-{
-    int d = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) d += __popc(a[k] ^ b[k]);
-    return d;
-}
-
 // First of the n ascending node ids that is >= id (n: none), by the whole wave: the lanes probe 64 places at once, the range
 // shrinks 64-fold per load.
 __device__ __forceinline__ int bow_lower_bound(const uint32_t *__restrict__ nodes, int n, uint32_t id, int lane)
@@ -312,6 +286,69 @@ __device__ __forceinline__ int bow_lower_bound(const uint32_t *__restrict__ node
         hi = top < hi ? top : hi;
     }
     return lo;
+}
+
+// One side of a node merge-join as a kernel holds it: the ascending node ids, the CSR offsets into the feature list, and the
+// length n of the keypoint array, which no CSR exceeds (a keypoint lies in one node).
+struct BowNodes {
+    const uint32_t *nodes; const int32_t *off; int nnodes, n;
+};
+
+// The merge-join step (:173-282, :537-616, :676-806) of one wave: node `node` of the query side q and the node of the same id on the
+// candidate side c.  In this order: q's node id strictly above its predecessor (std::map order, which the merge-join relies on) and
+// its CSR range inside [0, q.n); the 64-way probe of c's node list; that node's CSR range inside [0, c.n).  A record that fails a
+// check is reported in *status; false is "nothing to do": refused, past q's list, an id on one side only, or an empty range.
+// EAGER: q's four entries are loaded side by side, the predecessor's id whether or not it is needed, and compared without a branch
+// between them.  It is for bow_node_match_batch_kernel alone, whose keyframe arrays are pointers read from a record: its loads of q
+// are flat loads that the compiler otherwise puts off, one behind the other's comparison (DESIGN.md §4e has the figures).  Where the
+// pointers are kernel arguments the form without EAGER, the one the three kernels had, is the faster one.
+template <bool EAGER>
+__device__ __forceinline__ bool bow_shared_node(const BowNodes &q, const BowNodes &c, int node, int lane, int32_t *status, int &k0, int &k1, int &f0, int &nf)
+{
+    if (node >= q.nnodes) return false;
+    const uint32_t id = q.nodes[node];
+    k0 = q.off[node]; k1 = q.off[node + 1];
+    bool refused;
+    if (EAGER) {
+        const uint32_t before = q.nodes[node > 0 ? node - 1 : 0];
+        refused = (node > 0 && before >= id) | (k0 < 0) | (k1 < k0) | (k1 > q.n);
+    } else refused = (node > 0 && q.nodes[node - 1] >= id) || k0 < 0 || k1 < k0 || k1 > q.n;
+    if (refused) {
+        if (lane == 0) *status = ORBFE_ERR_INVALID;
+        return false;
+    }
+    const int lo = bow_lower_bound(c.nodes, c.nnodes, id, lane);
+    if (lo >= c.nnodes || c.nodes[lo] != id) return false;
+    f0 = c.off[lo];
+    const int f1 = c.off[lo + 1];
+    if (f0 < 0 || f1 < f0 || f1 > c.n) {
+        if (lane == 0) *status = ORBFE_ERR_INVALID;
+        return false;
+    }
+    nf = f1 - f0;
+    return k1 > k0 && nf > 0;
+}
+
+// The candidate side's whole node list and CSR, once over the grid's x axis, for a side that the caller wrote (the frame's is
+// orbfe_enqueue_compute_bow's): the probe above assumes ascending ids whatever node it lands on.
+__device__ __forceinline__ void bow_sweep_nodes(const BowNodes &c, int lane, int32_t *status)
+{
+    bool bad = false;
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < c.nnodes; k += gridDim.x * 256) {
+        const int o0 = c.off[k], o1 = c.off[k + 1];
+        bad = bad || (k > 0 && c.nodes[k - 1] >= c.nodes[k]) || o0 < 0 || o1 < o0 || o1 > c.n;
+    }
+    if (__any(bad) && lane == 0) *status = ORBFE_ERR_INVALID;
+}
+
+// The lane's next candidate in list order, at distance d, against its running best (d1 at chunk c1, index i1; d2 the runner-up): the
+// if-chain of :213-222.  Written as selects on purpose: as an if / else-if behind these references the compiler branches around the
+// update, 2 - 3 % of the kernels' GPU time.
+__device__ __forceinline__ void bow_walk_offer(int d, int c, int idx, int &d1, int &d2, int &c1, int &i1)
+{
+    const bool take = d < d1;
+    d2 = take ? d1 : (d < d2 ? d : d2);
+    d1 = take ? d : d1; c1 = take ? c : c1; i1 = take ? idx : i1;
 }
 
 // The walk of one shared node, by one wave, for both SearchByFboW overloads.  The QUERY side is the outer loop of the reference
@@ -332,12 +369,6 @@ __device__ __forceinline__ bool bow_node_walk(const Side &s, float nnratio, cons
                                               const int32_t *c_list, int f0, int nf, const uint8_t *c_desc, int n, int lane)
 {
     bool bad = false;
-    for (int j = lane; j < nf; j += 64) {
-        const int idx = c_list[f0 + j];
-        const bool out = idx < 0 || idx >= n;
-        bad = bad || out;
-        if (j >= 64 * BOW_FLAG_CHUNKS && !out) s.late_reset(idx);
-    }
     // this lane's first BOW_REG_CHUNKS candidates stay in registers: few nodes hold more than 64 * BOW_REG_CHUNKS
     int idxc[BOW_REG_CHUNKS];
     uint32_t fdc[BOW_REG_CHUNKS][8];
@@ -345,10 +376,18 @@ __device__ __forceinline__ bool bow_node_walk(const Side &s, float nnratio, cons
     for (int c = 0; c < BOW_REG_CHUNKS; c++) {
         const int j = lane + 64 * c;
         idxc[c] = j < nf ? c_list[f0 + j] : -1;
-        if (idxc[c] >= n) idxc[c] = -1;
-        if (idxc[c] >= 0 && !s.usable(idxc[c])) idxc[c] = -1;
+        if (j < nf && (idxc[c] < 0 || idxc[c] >= n)) { bad = true; idxc[c] = -1; }
+        // the descriptor of every entry inside the array, before the Side's verdict: its loads run beside the Side's, not behind them
 #pragma unroll
         for (int k = 0; k < 8; k++) fdc[c][k] = idxc[c] >= 0 ? ((const uint32_t *)(c_desc + (size_t)idxc[c] * 32))[k] : 0u;
+        if (idxc[c] >= 0 && !s.usable(idxc[c])) idxc[c] = -1;
+    }
+    // the rest of the list is read in place by every query: its indices are checked, and its late flags zeroed, once
+    for (int j = lane + 64 * BOW_REG_CHUNKS; j < nf; j += 64) {
+        const int idx = c_list[f0 + j];
+        const bool out = idx < 0 || idx >= n;
+        bad = bad || out;
+        if (j >= 64 * BOW_FLAG_CHUNKS && !out) s.late_reset(idx);
     }
     u64 taken = 0;
     for (int kbase = k0; kbase < k1; kbase += 64) {
@@ -375,26 +414,22 @@ __device__ __forceinline__ bool bow_node_walk(const Side &s, float nnratio, cons
 #pragma unroll
             for (int c = 0; c < BOW_REG_CHUNKS; c++) {
                 if (idxc[c] < 0 || ((taken >> c) & 1ull)) continue;
-                const int d = hamming256(kd, fdc[c]);
-                if (d < d1) { d2 = d1; d1 = d; c1 = c; i1 = idxc[c]; }
-                else if (d < d2) d2 = d;
+                bow_walk_offer(hamming256(kd, fdc[c]), c, idxc[c], d1, d2, c1, i1);
             }
             for (int j = lane + 64 * BOW_REG_CHUNKS, c = BOW_REG_CHUNKS; j < nf; j += 64, c++) {
                 const int idx = c_list[f0 + j];
                 if (idx < 0 || idx >= n) continue;
                 if (!s.usable(idx)) continue;
                 if (c < BOW_FLAG_CHUNKS ? (int)((taken >> c) & 1ull) : (int)s.late_taken(idx)) continue;
-                const int d = hamming256(kd, (const uint32_t *)(c_desc + (size_t)idx * 32));
-                if (d < d1) { d2 = d1; d1 = d; c1 = c; i1 = idx; }
-                else if (d < d2) d2 = d;
+                bow_walk_offer(hamming256(kd, (const uint32_t *)(c_desc + (size_t)idx * 32)), c, idx, d1, d2, c1, i1);
             }
             // bestDist1: the smallest key distance << 16 | list position (chunk * 64 + lane): the first minimum in list order
             const unsigned key = ((unsigned)d1 << 16) | (unsigned)(c1 * 64 + lane);
-            const unsigned m = wave_min_u32(key);
+            const unsigned m = wave_min_u32_dpp(key);
             const int best1 = (int)(m >> 16);
             if (best1 > Side::BOUND) continue; // also: no candidate at all
             const bool winner = key == m; // list positions are unique
-            const int best2 = (int)wave_min_u32((unsigned)(winner ? d2 : d1)); // the smallest of all the others, duplicates of bestDist1 included
+            const int best2 = (int)wave_min_u32_dpp((unsigned)(winner ? d2 : d1)); // the smallest of all the others, duplicates of bestDist1 included
             if (!((float)best1 < nnratio * (float)best2)) continue;
             if (winner) {
                 s.accept(real_kf, i1, c1 >= BOW_FLAG_CHUNKS);
@@ -417,7 +452,12 @@ struct BowFrameSide {
     __device__ __forceinline__ void accept(int q, int idx, bool) const { match[idx] = q; }
 };
 
-// One wave per keyframe node.
+// One wave per keyframe node.  The frame's node count is the device's own, clamped to the capacity, which also bounds its CSR.
+// RECORD: `a` was built from a record in memory (bow_batch_row).  Then the loads of the keyframe's node are flat loads, and that of
+// *f_n_nodes, left to the compiler, sinks behind the node's checks as one more in the wave's chain (2 % of the batch call's GPU time):
+// readfirstlane (the count is wave-uniform) keeps it here, beside the slot's count.  With kernel-argument pointers it stays a scalar
+// load that needs no such help, and the wait that readfirstlane brings costs the single call 1 %.
+template <bool RECORD>
 __device__ __forceinline__ void bow_node_match(const BowSearch &a)
 {
     const int lane = threadIdx.x & 63;
@@ -425,23 +465,11 @@ __device__ __forceinline__ void bow_node_match(const BowSearch &a)
     if (node >= a.kf_nnodes) return;
     const int n = slot_count(a.n_ptr, a.cap);
     if (n == 0) return;
-    int nfn = *a.f_n_nodes;
-    nfn = nfn < 0 ? 0 : (nfn > a.cap ? a.cap : nfn);
-    const uint32_t id = a.kf_nodes[node];
-    if (node > 0 && a.kf_nodes[node - 1] >= id) { // std::map order: the merge-join of :173-282 relies on it
-        if (lane == 0) *a.status = ORBFE_ERR_INVALID;
-        return;
-    }
-    const int lo = bow_lower_bound(a.f_nodes, nfn, id, lane);
-    if (lo >= nfn || a.f_nodes[lo] != id) return;
-    const int k0 = a.kf_off[node], k1 = a.kf_off[node + 1];
-    const int f0 = a.f_off[lo], f1 = a.f_off[lo + 1];
-    if (k0 < 0 || k1 < k0 || k1 > a.n_kf || f0 < 0 || f1 < f0 || f1 > a.cap) { // a keypoint lies in one node: no CSR is longer than its keypoint array
-        if (lane == 0) *a.status = ORBFE_ERR_INVALID;
-        return;
-    }
-    const int nf = f1 - f0;
-    if (k1 == k0 || nf == 0) return;
+    int nfn = slot_count(a.f_n_nodes, a.cap);
+    if (RECORD) nfn = __builtin_amdgcn_readfirstlane(nfn);
+    const BowNodes kf = {a.kf_nodes, a.kf_off, a.kf_nnodes, a.n_kf}, f = {a.f_nodes, a.f_off, nfn, a.cap};
+    int k0, k1, f0, nf;
+    if (!bow_shared_node<RECORD>(kf, f, node, lane, a.status, k0, k1, f0, nf)) return;
     const BowFrameSide side = {a.match};
     const bool bad = bow_node_walk(side, a.nnratio, a.kf_feat, k0, k1, a.kf_valid, a.kf_desc, a.n_kf, a.f_feat, f0, nf, a.desc, n, lane);
     if (__any(bad) && lane == 0) *a.status = ORBFE_ERR_INVALID;
@@ -493,7 +521,7 @@ __device__ __forceinline__ void bow_match_tail(const BowSearch &a)
 }
 
 __global__ __launch_bounds__(256) void bow_match_init_kernel(BowSearch a) { bow_match_init(a); }
-__global__ __launch_bounds__(256) void bow_node_match_kernel(BowSearch a) { bow_node_match(a); }
+__global__ __launch_bounds__(256) void bow_node_match_kernel(BowSearch a) { bow_node_match<false>(a); }
 __global__ __launch_bounds__(1024) void bow_match_tail_kernel(BowSearch a) { bow_match_tail(a); }
 
 // The batch: `a` holds the frame's side, the settings and row 0 of the outputs.  Record k is the same for every lane (k is a
@@ -524,7 +552,7 @@ __global__ __launch_bounds__(256) void bow_match_init_batch_kernel(BowSearch a, 
 __global__ __launch_bounds__(256) void bow_node_match_batch_kernel(BowSearch a, const orbfe_bow_keyframe *__restrict__ kfs, int max_kf_nnodes)
 {
     bool refused;
-    bow_node_match(bow_batch_row(a, kfs, max_kf_nnodes, blockIdx.y, &refused)); // a node at or past kf_nnodes returns first of all
+    bow_node_match<true>(bow_batch_row(a, kfs, max_kf_nnodes, blockIdx.y, &refused)); // a node at or past kf_nnodes returns first of all
 }
 __global__ __launch_bounds__(1024) void bow_match_tail_batch_kernel(BowSearch a, const orbfe_bow_keyframe *__restrict__ kfs, int max_kf_nnodes)
 {
@@ -612,9 +640,6 @@ try {
 // ---------------------------------------------------------------------------------------------
 // SearchForTriangulation(KeyFrame*, KeyFrame*) (src/ORBmatcher.cc:652-819)
 // ---------------------------------------------------------------------------------------------
-#define TRI_REG_CHUNKS 2   // a lane keeps descriptor, position, level thresholds and stereo bit of its first two KF2 features of a node in registers
-#define TRI_FLAG_CHUNKS 64 // and the "taken" flags of its first 64 in one 64-bit register; later ones live in TriSearch::taken2
-
 static_assert(sizeof(orbfe_tri_keyframe) == 64, "orbfe_tri_keyframe: seven pointers and two counts");
 static_assert(sizeof(orbfe_keypoint) == sizeof(KeyPointPOD), "orbfe_keypoint is the extraction's keypoint record");
 
@@ -624,7 +649,7 @@ struct TriSearch {
     float scale[ORBFE_MAX_LEVELS], sigma2[ORBFE_MAX_LEVELS];      // mvScaleFactors, mvLevelSigma2
     int nlevels, only_stereo, check_ori;
     int32_t *match12, *pairs, *nmatches, *status;
-    uint8_t *taken2;                                              // [k2.n] scratch: vbMatched2 beyond the lane-held flags, zeroed by every call
+    uint8_t *taken2;                                              // [k2.n] scratch: vbMatched2 beyond the lane-held flags; NULL when no node can reach that far
 };
 
 __global__ __launch_bounds__(256) void tri_init_kernel(TriSearch a)
@@ -632,7 +657,6 @@ __global__ __launch_bounds__(256) void tri_init_kernel(TriSearch a)
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k == 0) { *a.status = ORBFE_OK; *a.nmatches = 0; }
     if (k < a.k1.n) a.match12[k] = -1;
-    if (k < a.k2.n) a.taken2[k] = 0;
 }
 
 // What a lane knows of one KF2 feature of the node: idx < 0 is no candidate (beyond the list, refused, has a map point, monocular
@@ -664,46 +688,32 @@ __device__ __forceinline__ void tri_load_cand(const TriSearch &a, int f0, int nf
     for (int k = 0; k < 8; k++) c.d[k] = ((const uint32_t *)(a.k2.desc + (size_t)idx * 32))[k];
 }
 
-// One wave per KF1 node.  A KF2 keypoint lies in one node of KF2's feature vector, so vbMatched2 (:748, :800) is read and written
-// only by the KF1 features of the same node: the rule is sequential inside a node and nowhere else.  The wave takes the node's usable
-// KF1 features in list order; position j of the node's KF2 list belongs to lane j & 63 (chunk j >> 6).  The flag "KF2 keypoint
-// taken" of chunk c < TRI_FLAG_CHUNKS is bit c of the lane's `taken`, of a later chunk it is taken2[idx2], which only this lane
-// touches.  The reference's inner loop (:731-779) keeps the LAST candidate of the smallest distance that passes every gate
-// (`dist > bestDist` skips, bestDist starts at TH_LOW, and bestDist only moves when CheckDistEpipolarLine accepts): a lane's
-// candidates come in list order, so `d <= d1` keeps its last minimum, and the wave's winner is the smallest key
-// d << 16 | (0xffff - position).  No ratio test.
+// One wave per KF1 node: the sweep and the merge-join step of the SearchByFboW kernels, then a loop of its own (on bow_node_walk the
+// 20 enqueues of tools/bench_matchers.py --triangulation took 1.3 - 2 % more GPU time than this loop, and neither the resource table
+// nor the disassembly said why: DESIGN.md §4f).  A KF2 keypoint lies in one node of KF2's feature vector, so vbMatched2 (:719, :756)
+// is read and written only by the KF1 features of the same node: the rule is sequential inside a node and nowhere else.  The wave
+// takes the node's usable KF1 features in list order; position j of the node's KF2 list belongs to lane j & 63 (chunk j >> 6).  The
+// flag "KF2 keypoint taken" of chunk c < BOW_FLAG_CHUNKS is bit c of the lane's `taken`, of a later chunk it is taken2[idx2], which
+// this lane zeroes before the first query and which only it touches.  The reference's inner loop (:712-750) keeps the LAST candidate
+// of the smallest distance that passes every gate (`dist > bestDist` skips, bestDist starts at TH_LOW, and bestDist only moves when
+// CheckDistEpipolarLine accepts): a lane's candidates come in list order, so `d <= d1` keeps its last minimum, and the wave's winner
+// is the smallest key d << 16 | (0xffff - position).  No ratio test.
 __global__ __launch_bounds__(256) void tri_node_match_kernel(TriSearch a)
 {
     const int lane = threadIdx.x & 63;
-    const int n1 = a.k1.n, n2 = a.k2.n, nn2 = a.k2.nnodes;
+    const int n1 = a.k1.n;
+    const BowNodes kf1 = {a.k1.nodes, a.k1.off, a.k1.nnodes, n1}, kf2 = {a.k2.nodes, a.k2.off, a.k2.nnodes, a.k2.n};
+    bow_sweep_nodes(kf2, lane, a.status);
+    int k0, k1, f0, nf;
+    if (!bow_shared_node<false>(kf1, kf2, blockIdx.x * 4 + (threadIdx.x >> 6), lane, a.status, k0, k1, f0, nf)) return;
     bool bad = false;
-    // KF2's node list and CSR, once over the grid: the merge-join of :676-806 relies on std::map order
-    for (int k = blockIdx.x * 256 + threadIdx.x; k < nn2; k += gridDim.x * 256) {
-        const int o0 = a.k2.off[k], o1 = a.k2.off[k + 1];
-        bad = bad || (k > 0 && a.k2.nodes[k - 1] >= a.k2.nodes[k]) || o0 < 0 || o1 < o0 || o1 > n2;
+    for (int j = lane + 64 * BOW_FLAG_CHUNKS; j < nf; j += 64) { // the late flags of this lane's positions (nf > 4096: taken2 is not NULL)
+        const int idx = a.k2.feat[f0 + j];
+        if (idx >= 0 && idx < a.k2.n) a.taken2[idx] = 0;
     }
-    if (__any(bad) && lane == 0) *a.status = ORBFE_ERR_INVALID;
-    bad = false;
-    const int node = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (node >= a.k1.nnodes) return;
-    const uint32_t id = a.k1.nodes[node];
-    const int k0 = a.k1.off[node], k1 = a.k1.off[node + 1];
-    if ((node > 0 && a.k1.nodes[node - 1] >= id) || k0 < 0 || k1 < k0 || k1 > n1) {
-        if (lane == 0) *a.status = ORBFE_ERR_INVALID;
-        return;
-    }
-    const int lo = bow_lower_bound(a.k2.nodes, nn2, id, lane);
-    if (lo >= nn2 || a.k2.nodes[lo] != id) return;
-    const int f0 = a.k2.off[lo], f1 = a.k2.off[lo + 1];
-    if (f0 < 0 || f1 < f0 || f1 > n2) { // a keypoint lies in one node: no CSR is longer than its keypoint array
-        if (lane == 0) *a.status = ORBFE_ERR_INVALID;
-        return;
-    }
-    const int nf = f1 - f0;
-    if (k1 == k0 || nf == 0) return;
-    TriCand rc[TRI_REG_CHUNKS];
+    TriCand rc[BOW_REG_CHUNKS];
 #pragma unroll
-    for (int c = 0; c < TRI_REG_CHUNKS; c++) tri_load_cand(a, f0, nf, lane + 64 * c, rc[c], bad);
+    for (int c = 0; c < BOW_REG_CHUNKS; c++) tri_load_cand(a, f0, nf, lane + 64 * c, rc[c], bad);
     u64 taken = 0;
     for (int kbase = k0; kbase < k1; kbase += 64) {
         // 64 KF1 features at a time are fetched by the lanes side by side, so that no load of KF1 sits in the sequential loop below
@@ -736,7 +746,7 @@ __global__ __launch_bounds__(256) void tri_node_match_kernel(TriSearch a)
             for (int k = 0; k < 8; k++) kd[k] = (uint32_t)__builtin_amdgcn_readlane((int)my_d[k], src);
             int d1 = 256, c1 = 0, i2 = -1; // 256 differing bits: no candidate yet
 #pragma unroll
-            for (int c = 0; c < TRI_REG_CHUNKS; c++) {
+            for (int c = 0; c < BOW_REG_CHUNKS; c++) {
                 const TriCand &q = rc[c];
                 if (q.idx < 0 || ((taken >> c) & 1ull)) continue;
                 const int d = hamming256(kd, q.d);
@@ -745,11 +755,11 @@ __global__ __launch_bounds__(256) void tri_node_match_kernel(TriSearch a)
                 if (!orbfe_epipolar::check_dist_epipolar_line(x1, y1, q.x, q.y, a.F12, q.sigma2)) continue;
                 d1 = d; c1 = c; i2 = q.idx;
             }
-            for (int j = lane + 64 * TRI_REG_CHUNKS, c = TRI_REG_CHUNKS; j < nf; j += 64, c++) { // nodes beyond 64 * TRI_REG_CHUNKS features: read in place
+            for (int j = lane + 64 * BOW_REG_CHUNKS, c = BOW_REG_CHUNKS; j < nf; j += 64, c++) { // nodes beyond 64 * BOW_REG_CHUNKS features: read in place
                 TriCand q;
                 tri_load_cand(a, f0, nf, j, q, bad);
                 if (q.idx < 0) continue;
-                if (c < TRI_FLAG_CHUNKS ? (int)((taken >> c) & 1ull) : (int)a.taken2[q.idx]) continue;
+                if (c < BOW_FLAG_CHUNKS ? (int)((taken >> c) & 1ull) : (int)a.taken2[q.idx]) continue;
                 const int d = hamming256(kd, q.d);
                 if (d > TH_LOW || d > d1) continue;
                 if (!stereo1 && !q.stereo && orbfe_epipolar::inside_epipole_disc(a.ex, a.ey, q.x, q.y, q.scale)) continue;
@@ -758,11 +768,11 @@ __global__ __launch_bounds__(256) void tri_node_match_kernel(TriSearch a)
             }
             // the smallest distance; among equals the largest list position (chunk * 64 + lane < 65535): the last one the reference's loop meets
             const unsigned key = ((unsigned)d1 << 16) | (0xffffu - (unsigned)(c1 * 64 + lane));
-            const unsigned m = wave_min_u32(key);
+            const unsigned m = wave_min_u32_dpp(key);
             if ((int)(m >> 16) > TH_LOW) continue; // no candidate at all
             if (key == m) { // list positions are unique
                 a.match12[idx1] = i2;
-                if (c1 < TRI_FLAG_CHUNKS) taken |= 1ull << c1;
+                if (c1 < BOW_FLAG_CHUNKS) taken |= 1ull << c1;
                 else a.taken2[i2] = 1;
             }
         }
@@ -855,14 +865,18 @@ try {
         if (kf->nnodes > 0 && (!kf->nodes || !kf->off || !kf->feat || !kf->keys_un || !kf->u_right || !kf->has_mp || !kf->desc))
             return orbfe_fail(ctx, ORBFE_ERR_INVALID, "null array in a keyframe record with nodes");
     }
-    orbfe_bow_state *st = orbfe_ctx_bow_state(ctx);
-    if (!st) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "out of host memory");
     const int nlevels = ctx->params.nlevels;
     if (nlevels < 1 || nlevels > ORBFE_MAX_LEVELS) return orbfe_fail(ctx, ORBFE_ERR_UNSUPPORTED, "nlevels = %d", nlevels);
     hipStream_t s;
     if (const int rc = orbfe_enqueue_on(ctx, stream, false, &s)) return rc;
-    if (st->resident.ensure((size_t)(kf2->n > 64 ? kf2->n : 64))) return orbfe_fail(ctx, ORBFE_ERR_HIP, "BoW scratch allocation failed");
     TriSearch a;
+    a.taken2 = nullptr;
+    if (kf2->n > 64 * BOW_FLAG_CHUNKS) { // as bowkf_fill: below that no node list reaches a position whose flag needs memory
+        orbfe_bow_state *st = orbfe_ctx_bow_state(ctx);
+        if (!st) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "out of host memory");
+        if (st->resident.ensure((size_t)kf2->n)) return orbfe_fail(ctx, ORBFE_ERR_HIP, "BoW scratch allocation failed");
+        a.taken2 = (uint8_t *)st->resident.p;
+    }
     a.k1 = *kf1; a.k2 = *kf2; // a record without nodes may hold NULL arrays: the tail follows keys_un only through a match
     for (int k = 0; k < 9; k++) a.F12[k] = F12[k];
     orbfe_epipolar::epipole(Cw1, T2w, fx2, fy2, cx2, cy2, &a.ex, &a.ey);
@@ -873,9 +887,7 @@ try {
     }
     a.nlevels = nlevels; a.only_stereo = only_stereo != 0; a.check_ori = check_ori != 0;
     a.match12 = d_match12; a.pairs = d_pairs; a.nmatches = d_nmatches; a.status = d_status;
-    a.taken2 = (uint8_t *)st->resident.p;
-    const int cells = a.k1.n > a.k2.n ? a.k1.n : a.k2.n;
-    hipLaunchKernelGGL(tri_init_kernel, dim3(cells > 0 ? (cells + 255) / 256 : 1), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(tri_init_kernel, dim3(a.k1.n > 0 ? (a.k1.n + 255) / 256 : 1), dim3(256), 0, s, a);
     if (a.k1.nnodes > 0 && a.k2.nnodes > 0) hipLaunchKernelGGL(tri_node_match_kernel, dim3((a.k1.nnodes + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(tri_tail_kernel, dim3(1), dim3(1024), 0, s, a);
     ORBFE_HIP_TRY(ctx, hipGetLastError());
@@ -928,34 +940,13 @@ __device__ __forceinline__ void bowkf_init(const BowKfSearch &a, bool refused)
 __device__ __forceinline__ void bowkf_node_match(const BowKfSearch &a)
 {
     const int lane = threadIdx.x & 63;
-    const int n1 = a.k1.n, n2 = a.k2.n, nn2 = a.k2.nnodes;
-    if (nn2 == 0) return; // the whole workgroup: a candidate without nodes, or a refused record
-    bool bad = false;
-    // KF2's node list and CSR, once over the grid's x axis: the merge-join of :537-616 relies on std::map order
-    for (int k = blockIdx.x * 256 + threadIdx.x; k < nn2; k += gridDim.x * 256) {
-        const int o0 = a.k2.off[k], o1 = a.k2.off[k + 1];
-        bad = bad || (k > 0 && a.k2.nodes[k - 1] >= a.k2.nodes[k]) || o0 < 0 || o1 < o0 || o1 > n2;
-    }
-    if (__any(bad) && lane == 0) *a.status = ORBFE_ERR_INVALID;
-    const int node = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (node >= a.k1.nnodes) return;
-    const uint32_t id = a.k1.nodes[node];
-    const int k0 = a.k1.off[node], k1 = a.k1.off[node + 1];
-    if ((node > 0 && a.k1.nodes[node - 1] >= id) || k0 < 0 || k1 < k0 || k1 > n1) {
-        if (lane == 0) *a.status = ORBFE_ERR_INVALID;
-        return;
-    }
-    const int lo = bow_lower_bound(a.k2.nodes, nn2, id, lane);
-    if (lo >= nn2 || a.k2.nodes[lo] != id) return;
-    const int f0 = a.k2.off[lo], f1 = a.k2.off[lo + 1];
-    if (f0 < 0 || f1 < f0 || f1 > n2) { // a keypoint lies in one node: no CSR is longer than its keypoint array
-        if (lane == 0) *a.status = ORBFE_ERR_INVALID;
-        return;
-    }
-    const int nf = f1 - f0;
-    if (k1 == k0 || nf == 0) return;
+    if (a.k2.nnodes == 0) return; // the whole workgroup: a candidate without nodes, or a refused record
+    const BowNodes kf1 = {a.k1.nodes, a.k1.off, a.k1.nnodes, a.k1.n}, kf2 = {a.k2.nodes, a.k2.off, a.k2.nnodes, a.k2.n};
+    bow_sweep_nodes(kf2, lane, a.status);
+    int k0, k1, f0, nf;
+    if (!bow_shared_node<false>(kf1, kf2, blockIdx.x * 4 + (threadIdx.x >> 6), lane, a.status, k0, k1, f0, nf)) return;
     const BowKfSide side = {a.k2.valid, a.match12, a.taken2};
-    bad = bow_node_walk(side, a.nnratio, a.k1.feat, k0, k1, a.k1.valid, a.k1.desc, n1, a.k2.feat, f0, nf, a.k2.desc, n2, lane);
+    const bool bad = bow_node_walk(side, a.nnratio, a.k1.feat, k0, k1, a.k1.valid, a.k1.desc, a.k1.n, a.k2.feat, f0, nf, a.k2.desc, a.k2.n, lane);
     if (__any(bad) && lane == 0) *a.status = ORBFE_ERR_INVALID;
 }
 

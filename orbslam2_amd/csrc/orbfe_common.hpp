@@ -33,6 +33,27 @@ __device__ __forceinline__ int wave_sum_i32(int v)
     v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false); // row_bcast:31 into rows 2 and 3
     return __builtin_amdgcn_readlane(v, 63);
 }
+// Minimum over the 64 lanes in six DPP steps (no LDS round trip): inside each quad, inside each row of 16 by two rotations, then the
+// last lane of a row into the next row (rows 1 and 3), of row 1 into rows 2 and 3; lane 63 holds the result.  Lanes a step does
+// not write keep their value, and a minimum does not mind seeing a value twice.  Precondition, as for wave_sum_i32: all 64 lanes
+// are active (DPP reads of an inactive lane are not its value); the result is wave-uniform (an SGPR).
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned dpp_min_step(unsigned v)
+{
+    const unsigned t = (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xf, false);
+    return t < v ? t : v;
+}
+__device__ __forceinline__ unsigned wave_min_u32_dpp(unsigned v)
+{
+    v = dpp_min_step<0xb1, 0xf>(v);  // quad_perm:[1,0,3,2]
+    v = dpp_min_step<0x4e, 0xf>(v);  // quad_perm:[2,3,0,1]
+    v = dpp_min_step<0x124, 0xf>(v); // row_ror:4
+    v = dpp_min_step<0x128, 0xf>(v); // row_ror:8
+    v = dpp_min_step<0x142, 0xa>(v); // row_bcast:15
+    v = dpp_min_step<0x143, 0xc>(v); // row_bcast:31
+    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
+// The shuffle form, every lane gets the result: what the quadtree kernels and map_point_kernel call.
 __device__ __forceinline__ unsigned wave_min_u32(unsigned v)
 {
 #pragma unroll

@@ -8,6 +8,8 @@
 
 #include "orbfe_config.h"
 
+typedef unsigned long long u64; // a wave's ballot, a lane's 64 flags
+
 // Profiling cut points (tools/*_phases.sh, tools/*_insts.sh): an extra kernel argument that makes a kernel return after a
 // given phase so that phases can be timed / counted.  They exist ONLY in the -DORBFE_PROFILE_CUTS build (make cuts ->
 // tools/ab/cuts.so); the shipped liborbfe.so has neither the argument nor the branches nor the getenv.

@@ -20,10 +20,9 @@
 #include "../../include/orbfe.h"
 #include "orbfe_config.h"
 #include "orbfe_host.h"
+#include "orbfe_common.hpp"
 
 static_assert(sizeof(orbfe_obs_keyframe) == 40, "orbfe_obs_keyframe: two pointers, the centre, three ints");
-
-typedef unsigned long long u64;
 
 struct MapPointArgs {
     const orbfe_obs_keyframe *kfs;
@@ -78,16 +77,6 @@ __device__ __forceinline__ int count_within(const uint32_t (&rd)[8], const uint3
         cnt += dist <= v;
     }
     return cnt;
-}
-
-__device__ __forceinline__ unsigned wave_min_u32(unsigned w)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned t = (unsigned)__shfl_xor((int)w, o, 64);
-        w = t < w ? t : w;
-    }
-    return w;
 }
 
 __global__ __launch_bounds__(256) void map_point_kernel(MapPointArgs a)

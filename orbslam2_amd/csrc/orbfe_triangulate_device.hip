@@ -22,7 +22,6 @@
 
 static_assert(sizeof(orbfe_newpoint_keyframe) == 136, "orbfe_newpoint_keyframe: six pointers, Tcw, Ow, six camera floats, n");
 
-typedef unsigned long long u64;
 // what every kernel of this file takes; the two keyframe records travel by value, the level tables are the context's
 struct orbfe_triangulate_args {
     orbfe_newpoint_keyframe kf1, kf2;

@@ -157,6 +157,48 @@ def test_gpu_big_node_scene_equals_the_oracle_and_the_synchronous_call():
 
 
 @pytest.mark.gpu
+def test_gpu_flags_another_matcher_left_in_the_shared_scratch_do_not_reach_the_search():
+    """The flags of list positions from 4096 on are bytes of the context's BoW scratch, indexed by idx2, which
+    orbfe_enqueue_search_by_bow_kf uses too and which no launch sweeps: the lane that owns such a position zeroes its byte before the
+    node's first query.  On one context and one stream: the bow_kf big-node call (a KF2 node of 4200 keypoints), whose winners past
+    position 4096 leave set bytes; directly behind it the big-node search in mode (0, 1), some of whose winners lie on those bytes;
+    then the same search again, behind its own set bytes."""
+    import torch
+    from orbslam2_amd import api
+    from tests import bow_kf_scenes as K
+
+    def late(fv):
+        return np.concatenate([fv[2][fv[1][i]:fv[1][i + 1]][4096:] for i in range(len(fv[0]))])
+
+    b1, b2 = K.big_node()
+    sc = S.big_node()
+    bref, bnref = K.oracle(b1, b2, 0.75, True)
+    ref, nref = S.oracle(sc, 0, 1)
+    stale = np.intersect1d(bref[bref >= 0], late(b2["fv"]))
+    assert np.intersect1d(stale, np.intersect1d(ref[ref >= 0], late(sc["kf2"]["fv"]))).size > 0  # a byte left set would cost a winner
+    ctx = _ctx(api)
+    st = torch.cuda.Stream()
+    held, recs = [], []
+    for kf in (b1, b2):
+        t = [upload(v, pad=PAD) for v in (kf["fv"][0], kf["fv"][1], kf["fv"][2], kf["valid"], kf["d"].reshape(-1), kf["ang"])]
+        held.append(t)
+        recs.append(api.BowKeyframe(*[p for _, p in t], None, len(kf["fv"][0]), len(kf["d"])))
+    k1, k2 = _Kf(api, sc["kf1"]), _Kf(api, sc["kf2"])
+    bout = [Guarded.cells(s) for s in (len(b1["d"]), 1, 1)]
+    first, second = _Out(k1.n, k2.n), _Out(k1.n, k2.n)
+    torch.cuda.synchronize()
+    ctx.enqueue_search_by_bow_kf(recs[0], recs[1], 0.75, True, bout[0].ptr, bout[1].ptr, bout[2].ptr, d_pairs=0, stream=st.cuda_stream)
+    _enqueue(ctx, sc, k1, k2, (0, 1), first, st)
+    _enqueue(ctx, sc, k1, k2, (0, 1), second, st)
+    st.synchronize()
+    bm, bnm, bstatus = (g.fetch() for g in bout)
+    assert bstatus[0] == 0 and bnm[0] == bnref and np.array_equal(bm, bref)
+    _check(first, ref, nref, True, "behind bow_kf")
+    _check(second, ref, nref, True, "behind itself")
+    ctx.close()
+
+
+@pytest.mark.gpu
 def test_gpu_node_size_edges_every_step_a_tie_that_takes_a_flag():
     import torch
     from orbslam2_amd import api
