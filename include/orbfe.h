@@ -887,6 +887,49 @@ int orbfe_enqueue_search_by_projection_sim3(orbfe_context *ctx, const orbfe_grid
         const int32_t *d_pt_valid /* [n_pts] */, const uint8_t *d_kf_matched /* [kf->n] or NULL: none */, float th,
         int32_t *d_pt_match /* [n_pts]: keypoint of kf or -1 */, int32_t *d_kf_match /* [kf->n]: the query that took keypoint k, or -1 */,
         int32_t *d_nmatches /* [1] */, int32_t *d_status /* [1] */, void *stream);
+/* Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cc:1090-1285, src/LoopClosing.cc:362) on the same
+ * two keyframes, so that SearchBySim3 -> OptimizeSim3 is one stream and one synchronise (orbfe_sim3_opt.hip).  One launch of one workgroup;
+ * FP64 like g2o, the Jacobians g2o's numeric ones, block sums in a fixed order (bit-reproducible run to run; DESIGN.md states the tolerance
+ * against a float64 model).  Only keys_un and n of the records are read, never the grid, desc or u_right.  T1w, T2w (3x4), R12 (3x3) and
+ * t12 (3) are HOST arrays read before the call returns; d_pos is the map point's GetWorldPos() per keypoint SLOT; d_valid[k] is plain
+ * pMP && !pMP->isBad() (orbfe_bow_keyframe.valid), NOT SearchBySim3's "not already matched" array.  The camera and mvInvLevelSigma2 are
+ * the context's, for both keyframes.  th2 is the chi-square gate and the square of the Huber delta ((float)sqrt(th2), :1139).
+ * With m(i) = (d_prior12 && d_prior12[i] >= 0) ? d_prior12[i] : d_match12[i] -- d_prior12 the RANSAC inliers' vpMapPointMatches
+ * (src/LoopClosing.cc:343-353) as keypoint slots of KF2, d_match12 what SearchBySim3 wrote; the merge happens on the device:
+ *   m(i) == -1                           no correspondence, d_match12[i] = -1
+ *   m(i) outside [-1, kf2->n), or an octave outside [0, nlevels) on either keypoint
+ *                                        d_status = ORBFE_ERR_INVALID; stored as -1, never used as an address, no edge
+ *   !d_valid1[i] || !d_valid2[m(i)]      the reference's `continue` (:1156-1180): no edge, d_match12[i] = m(i) is kept
+ *   otherwise                            one correspondence, two edges (:1184-1221)
+ * then optimize(params->iterations); every correspondence with chi2 > th2 on either edge loses its d_match12 entry (nBad); fewer than
+ * params->min_inliers left: d_n_inliers = 0 and d_S12 = the INPUT Sim3 (the entries cleared so far stay cleared); otherwise
+ * optimize(nBad > 0 ? more_iterations_outliers : more_iterations_clean) without the bad ones, the same test again, d_n_inliers = what
+ * passes and d_S12 = the estimate.  chi2 is the error at the LAST EVALUATED estimate, as in orbfe_enqueue_pose_optimization.
+ * Outputs (device), all written by every call: d_match12[kf1->n] (in/out), d_S12[8] = qx qy qz qw tx ty tz s (g2o::Sim3's members; the
+ * quaternion is not normalised, as g2o leaves it), d_n_inliers[1], d_status[1].  kf1->n == 0 writes count 0, status 0 and the input Sim3.
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL context, record, pose or output; kf->n negative or > 65535; a NULL
+ * array under n > 0; th2 <= 0; any params field < 1.
+ * The correspondences are compacted into a table that lives in the LDS for keyframes of up to ORBFE_SIM3_OPT_LDS_SLOTS keypoint slots
+ * (kf1->n; the launch requests no more LDS than orbfe_enqueue_pose_optimization's) and in the context's grow-only scratch in HBM above
+ * that: queue the calls of one context on one stream. */
+#define ORBFE_SIM3_OPT_LDS_SLOTS 2048
+typedef struct orbfe_sim3_opt_params {   /* Optimizer.sim3Iterations, .additionalIterations, .additionalIterationsNoOutliers, .minimumInliersBeforeFail */
+    int32_t iterations, more_iterations_outliers, more_iterations_clean, min_inliers;   /* src/Optimizer.cc:60-70: 5, 10, 5, 10 */
+} orbfe_sim3_opt_params;
+int orbfe_enqueue_optimize_sim3(orbfe_context *ctx,
+        const orbfe_grid_keyframe *kf1, const float *T1w, const float *d_pos1, const int32_t *d_valid1,
+        const orbfe_grid_keyframe *kf2, const float *T2w, const float *d_pos2, const int32_t *d_valid2,
+        float s12, const float *R12, const float *t12, float th2, int fix_scale,
+        const orbfe_sim3_opt_params *params /* NULL: the defaults above */,
+        const int32_t *d_prior12 /* [kf1->n] or NULL */, int32_t *d_match12 /* [kf1->n], in/out */,
+        double *d_S12 /* [8]: qx qy qz qw tx ty tz s */, int32_t *d_n_inliers /* [1] */, int32_t *d_status /* [1] */, void *stream);
+/* The same from host arrays, synchronous (it uploads, calls the enqueue form on the context's stream and downloads: the same bits).
+ * Returns ORBFE_ERR_INVALID as the call above does, and also -- after the outputs are written -- when the device set d_status. */
+int orbfe_optimize_sim3(orbfe_context *ctx,
+        const orbfe_keypoint *keys_un1, int n1, const float *T1w, const float *pos1, const int32_t *valid1,
+        const orbfe_keypoint *keys_un2, int n2, const float *T2w, const float *pos2, const int32_t *valid2,
+        float s12, const float *R12, const float *t12, float th2, int fix_scale, const orbfe_sim3_opt_params *params,
+        const int32_t *prior12, int32_t *match12, double *S12, int *n_inliers);
 /* ---- the writer of the map-point table (orbfe_map_point_device.hip): MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307)
  * and MapPoint::UpdateNormalAndDepth (:330-371) for chosen rows of the table that orbfe_enqueue_fuse and the Sim3 matchers read, from
  * observation lists over device-resident keyframes.  The contract of the enqueue matchers above holds: asynchronous on `stream` (NULL:

@@ -41,7 +41,7 @@ EXPORTS = [
     "orbfe_enqueue_search_by_projection_kf", "orbfe_enqueue_search_by_projection_kf_batch",
     "orbfe_enqueue_search_for_triangulation",
     "orbfe_enqueue_keyframe_grid", "orbfe_enqueue_fuse", "orbfe_enqueue_fuse_sim3",
-    "orbfe_enqueue_search_by_sim3", "orbfe_enqueue_search_by_projection_sim3",
+    "orbfe_enqueue_search_by_sim3", "orbfe_enqueue_search_by_projection_sim3", "orbfe_enqueue_optimize_sim3", "orbfe_optimize_sim3",
     "orbfe_enqueue_search_by_bow_kf", "orbfe_enqueue_search_by_bow_kf_batch",
     "orbfe_enqueue_update_map_points",
     "orbfe_enqueue_triangulate_pairs",
@@ -98,6 +98,18 @@ class GridKeyframe(C.Structure):
 
 
 assert C.sizeof(GridKeyframe) == 64
+
+
+class Sim3OptParams(C.Structure):
+    """orbfe_sim3_opt_params (include/orbfe.h): Optimizer's sim3Iterations, additionalIterations, additionalIterationsNoOutliers and
+    minimumInliersBeforeFail; the reference's values are the defaults."""
+    _fields_ = [("iterations", C.c_int32), ("more_iterations_outliers", C.c_int32), ("more_iterations_clean", C.c_int32), ("min_inliers", C.c_int32)]
+
+    def __init__(self, iterations=5, more_iterations_outliers=10, more_iterations_clean=5, min_inliers=10):
+        super().__init__(iterations, more_iterations_outliers, more_iterations_clean, min_inliers)
+
+
+SIM3_OPT_LDS_SLOTS = 2048  # ORBFE_SIM3_OPT_LDS_SLOTS
 
 
 class ObsKeyframe(C.Structure):
@@ -285,6 +297,11 @@ def load():
     for fn in (L.orbfe_enqueue_fuse, L.orbfe_enqueue_fuse_sim3):
         fn.restype = C.c_int
         fn.argtypes = [vp, C.POINTER(GridKeyframe), vp, C.c_int, vp, C.c_int] + [vp] * 6 + [C.c_float] + [vp] * 4
+    L.orbfe_enqueue_optimize_sim3.restype = C.c_int
+    L.orbfe_enqueue_optimize_sim3.argtypes = ([vp] + [C.POINTER(GridKeyframe), vp, vp, vp] * 2 + [C.c_float, vp, vp, C.c_float, C.c_int, C.POINTER(Sim3OptParams)]
+                                              + [vp] * 6)
+    L.orbfe_optimize_sim3.restype = C.c_int
+    L.orbfe_optimize_sim3.argtypes = [vp] + [vp, C.c_int, vp, vp, vp] * 2 + [C.c_float, vp, vp, C.c_float, C.c_int, C.POINTER(Sim3OptParams), vp, vp, vp, ip]
     L.orbfe_enqueue_search_by_sim3.restype = C.c_int
     L.orbfe_enqueue_search_by_sim3.argtypes = [vp] + [C.POINTER(GridKeyframe)] + [vp] * 6 + [C.POINTER(GridKeyframe)] + [vp] * 6 + [C.c_float, vp, vp, C.c_float] + [vp] * 4
     L.orbfe_enqueue_search_by_projection_sim3.restype = C.c_int
@@ -908,6 +925,41 @@ class Context:
         self._check(self.L.orbfe_enqueue_search_by_sim3(self.h, C.byref(kf1), _p(t1), *[v(x or None) for x in d_pts1], C.byref(kf2), _p(t2),
                                                         *[v(x or None) for x in d_pts2], float(s12), _p(R), _p(t), th, v(d_match12 or None),
                                                         v(d_n_found or None), v(d_status or None), v(stream or None)))
+
+    def enqueue_optimize_sim3(self, kf1, T1w, d_pos1, d_valid1, kf2, T2w, d_pos2, d_valid2, s12, R12, t12, th2, fix_scale, d_match12, d_S12,
+                              d_n_inliers, d_status, d_prior12=0, params=None, stream=0):
+        """Optimizer::OptimizeSim3 on two device-resident keyframes (GridKeyframe records on the host; only keys_un and n are read),
+        asynchronous on `stream`.  d_pos / d_valid: the map point's position and pMP && !isBad() per keypoint slot; d_match12 (int32
+        [kf1.n], in/out) is what enqueue_search_by_sim3 wrote, d_prior12 (optional) the RANSAC inliers' matches as slots of kf2; T1w,
+        T2w (3x4), R12 (3x3), t12 (3) are host arrays read before the call returns.  d_S12 receives 8 doubles (qx qy qz qw tx ty tz s).
+        params: a Sim3OptParams or None for the reference's values.  Queue the calls of one context on one stream."""
+        v = C.c_void_p
+        t1 = np.ascontiguousarray(T1w, np.float32); t2 = np.ascontiguousarray(T2w, np.float32)
+        R = np.ascontiguousarray(R12, np.float32); t = np.ascontiguousarray(t12, np.float32)
+        assert t1.size >= 12 and t2.size >= 12 and R.size == 9 and t.size == 3
+        self._check(self.L.orbfe_enqueue_optimize_sim3(self.h, C.byref(kf1), _p(t1), v(d_pos1 or None), v(d_valid1 or None), C.byref(kf2), _p(t2),
+                                                       v(d_pos2 or None), v(d_valid2 or None), float(s12), _p(R), _p(t), float(th2), int(fix_scale),
+                                                       None if params is None else C.byref(params), v(d_prior12 or None), v(d_match12 or None),
+                                                       v(d_S12 or None), v(d_n_inliers or None), v(d_status or None), v(stream or None)))
+
+    def optimize_sim3(self, keys_un1, T1w, pos1, valid1, keys_un2, T2w, pos2, valid2, s12, R12, t12, th2, fix_scale, match12, prior12=None,
+                      params=None):
+        """The same from host arrays, synchronous.  Returns (S12 float64[8], match12 int32[n1], n_inliers).  Raises OrbfeError
+        (ERR_INVALID) for what only the device can see -- an entry outside [-1, n2), an octave outside the context's levels."""
+        k1 = np.ascontiguousarray(keys_un1, KP_DTYPE); k2 = np.ascontiguousarray(keys_un2, KP_DTYPE)
+        t1 = np.ascontiguousarray(T1w, np.float32); t2 = np.ascontiguousarray(T2w, np.float32)
+        p1 = np.ascontiguousarray(pos1, np.float32); p2 = np.ascontiguousarray(pos2, np.float32)
+        v1 = np.ascontiguousarray(valid1, np.int32); v2 = np.ascontiguousarray(valid2, np.int32)
+        R = np.ascontiguousarray(R12, np.float32); t = np.ascontiguousarray(t12, np.float32)
+        m = np.ascontiguousarray(match12, np.int32).copy()
+        pr = None if prior12 is None else np.ascontiguousarray(prior12, np.int32)
+        assert t1.size >= 12 and t2.size >= 12 and R.size == 9 and t.size == 3 and len(m) == len(k1) and (pr is None or len(pr) == len(k1))
+        S = np.zeros(8, np.float64); n = C.c_int()
+        ptr = lambda a: _p(a) if a.size else None
+        self._check(self.L.orbfe_optimize_sim3(self.h, ptr(k1), len(k1), _p(t1), ptr(p1), ptr(v1), ptr(k2), len(k2), _p(t2), ptr(p2), ptr(v2), float(s12),
+                                               _p(R), _p(t), float(th2), int(fix_scale), None if params is None else C.byref(params),
+                                               None if pr is None else ptr(pr), ptr(m), _p(S), C.byref(n)))
+        return S, m, n.value
 
     def enqueue_search_by_projection_sim3(self, kf, Scw, n_pts, d_pt_index, n_rows, d_pos, d_normal, d_max_distance, d_min_distance, d_pt_desc,
                                           d_pt_valid, d_kf_matched, th, d_pt_match, d_kf_match, d_nmatches, d_status, stream=0):

@@ -206,11 +206,6 @@ __global__ __launch_bounds__(THREADS) void pose_opt_kernel(const int32_t *__rest
     }
 }
 
-constexpr int PO_LDS_CAP_MAX = 4096; // keypoint slots per problem the LDS edge table holds (29 B each)
-
-template <int THREADS>
-size_t pose_lds_bytes(int cap) { return sizeof(double) * (2 * (THREADS / 16) * 32 + 2 * 32) + (size_t)cap * (7 * sizeof(float) + 1) + 16; }
-
 } // namespace
 
 struct orbfe_pose_state {

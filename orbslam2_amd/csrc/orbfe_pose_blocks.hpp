@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <cfloat>
 #include <cstdint>
+#include <utility>
 
 #include "orbfe_device.h"
 
@@ -157,38 +158,40 @@ __device__ inline void se3_to_cv(const Se3 &q, float *T) // Converter::toCvMat(S
     T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
 }
 
-// Symmetric exchange of rows / columns K and C of a register-resident 6x6 matrix (compile-time indices only).
-template <int K, int C>
-__device__ __forceinline__ void sym_swap(double (&A)[6][6], double (&y)[6])
+// Symmetric exchange of rows / columns K and C of a register-resident N x N matrix (compile-time indices only).
+template <int N, int K, int C>
+__device__ __forceinline__ void sym_swap(double (&A)[N][N], double (&y)[N])
 {
 #pragma unroll
-    for (int j = 0; j < 6; j++) { const double t = A[K][j]; A[K][j] = A[C][j]; A[C][j] = t; }
+    for (int j = 0; j < N; j++) { const double t = A[K][j]; A[K][j] = A[C][j]; A[C][j] = t; }
 #pragma unroll
-    for (int i = 0; i < 6; i++) { const double t = A[i][K]; A[i][K] = A[i][C]; A[i][C] = t; }
+    for (int i = 0; i < N; i++) { const double t = A[i][K]; A[i][K] = A[i][C]; A[i][C] = t; }
     const double t = y[K]; y[K] = y[C]; y[C] = t;
 }
 
 // (Eigen divides the sub-column and the solve's D^-1 step by the pivot; here the pivot's reciprocal is formed once and
-// multiplied in -- 6 divisions per solve instead of 21, a last-bit difference that the tolerance of this stage covers.)
-template <int K>
-__device__ __forceinline__ void ldlt_step(double (&A)[6][6], double (&y)[6], double (&dinv)[6], bool (&usable)[6], int (&perm)[6], bool &positive)
+// multiplied in -- N divisions per solve instead of N (N + 1) / 2, a last-bit difference that the tolerance of this stage covers.)
+template <int N, int K>
+__device__ __forceinline__ void ldlt_step(double (&A)[N][N], double (&y)[N], double (&dinv)[N], bool (&usable)[N], int (&perm)[N], bool &positive)
 {
+    static_assert(N >= 2 && N <= 7, "the exchange switches below name rows 1 .. 6");
     // largest remaining diagonal entry, first one wins (Eigen: maxCoeff over the tail of the diagonal)
     int p = K;
     double big = fabs(A[K][K]);
 #pragma unroll
-    for (int i = K + 1; i < 6; i++)
+    for (int i = K + 1; i < N; i++)
         if (fabs(A[i][i]) > big) { big = fabs(A[i][i]); p = i; }
     p = __builtin_amdgcn_readfirstlane(p); // the matrix is the same in every lane: a scalar branch, no dynamic register indexing
     perm[K] = p;
     // the right-hand side is permuted along (P b), which is what the forward substitution consumes
-    if constexpr (K < 5) {
+    if constexpr (K < N - 1) {
         switch (p) {
-        case 1: if constexpr (K < 1) sym_swap<K, 1>(A, y); break;
-        case 2: if constexpr (K < 2) sym_swap<K, 2>(A, y); break;
-        case 3: if constexpr (K < 3) sym_swap<K, 3>(A, y); break;
-        case 4: if constexpr (K < 4) sym_swap<K, 4>(A, y); break;
-        case 5: sym_swap<K, 5>(A, y); break;
+        case 1: if constexpr (K < 1 && 1 < N) sym_swap<N, K, 1>(A, y); break;
+        case 2: if constexpr (K < 2 && 2 < N) sym_swap<N, K, 2>(A, y); break;
+        case 3: if constexpr (K < 3 && 3 < N) sym_swap<N, K, 3>(A, y); break;
+        case 4: if constexpr (K < 4 && 4 < N) sym_swap<N, K, 4>(A, y); break;
+        case 5: if constexpr (K < 5 && 5 < N) sym_swap<N, K, 5>(A, y); break;
+        case 6: if constexpr (K < 6 && 6 < N) sym_swap<N, K, 6>(A, y); break;
         default: break;
         }
     }
@@ -205,7 +208,7 @@ __device__ __forceinline__ void ldlt_step(double (&A)[6][6], double (&y)[6], dou
     dinv[K] = di;
     usable[K] = ok;
 #pragma unroll
-    for (int i = K + 1; i < 6; i++) {
+    for (int i = K + 1; i < N; i++) {
         double sacc = A[i][K];
 #pragma unroll
         for (int j = 0; j < K; j++) sacc -= A[i][j] * A[K][j] * A[j][j];
@@ -213,66 +216,78 @@ __device__ __forceinline__ void ldlt_step(double (&A)[6][6], double (&y)[6], dou
     }
 }
 
-template <int K>
-__device__ __forceinline__ void unpermute_step(double (&y)[6], const int (&perm)[6])
+template <int N, int K>
+__device__ __forceinline__ void unpermute_step(double (&y)[N], const int (&perm)[N])
 {
-    if constexpr (K < 5) {
+    if constexpr (K < N - 1) {
         double t;
         switch (perm[K]) { // scalar (readfirstlane'd above)
-        case 1: if constexpr (K < 1) { t = y[K]; y[K] = y[1]; y[1] = t; } break;
-        case 2: if constexpr (K < 2) { t = y[K]; y[K] = y[2]; y[2] = t; } break;
-        case 3: if constexpr (K < 3) { t = y[K]; y[K] = y[3]; y[3] = t; } break;
-        case 4: if constexpr (K < 4) { t = y[K]; y[K] = y[4]; y[4] = t; } break;
-        case 5: t = y[K]; y[K] = y[5]; y[5] = t; break;
+        case 1: if constexpr (K < 1 && 1 < N) { t = y[K]; y[K] = y[1]; y[1] = t; } break;
+        case 2: if constexpr (K < 2 && 2 < N) { t = y[K]; y[K] = y[2]; y[2] = t; } break;
+        case 3: if constexpr (K < 3 && 3 < N) { t = y[K]; y[K] = y[3]; y[3] = t; } break;
+        case 4: if constexpr (K < 4 && 4 < N) { t = y[K]; y[K] = y[4]; y[4] = t; } break;
+        case 5: if constexpr (K < 5 && 5 < N) { t = y[K]; y[K] = y[5]; y[5] = t; } break;
+        case 6: if constexpr (K < 6 && 6 < N) { t = y[K]; y[K] = y[6]; y[6] = t; } break;
         default: break;
         }
     }
 }
 
-// LDLT with diagonal pivoting (Eigen::LDLT as LinearSolverDense uses it); returns isPositive().  x is left untouched
-// when the factor is not positive.  Everything is indexed at compile time so the matrix stays in registers.
-__device__ inline bool solve_ldlt6(const double *Hu /*21, upper triangle row-major, then b[6]*/, double lambda, double *x)
+template <int N, int... Ks>
+__device__ __forceinline__ void ldlt_steps(double (&A)[N][N], double (&y)[N], double (&dinv)[N], bool (&usable)[N], int (&perm)[N], bool &positive,
+                                           std::integer_sequence<int, Ks...>)
 {
-    double A[6][6], y[6];
+    (ldlt_step<N, Ks>(A, y, dinv, usable, perm, positive), ...); // steps 0 .. N - 1, in order
+}
+
+template <int N, int... Ks>
+__device__ __forceinline__ void unpermute_steps(double (&y)[N], const int (&perm)[N], std::integer_sequence<int, Ks...>)
+{
+    (unpermute_step<N, N - 2 - Ks>(y, perm), ...); // steps N - 2 .. 0
+}
+
+// LDLT with diagonal pivoting (Eigen::LDLT as LinearSolverDense uses it) of an N x N system; returns isPositive().  x is left
+// untouched when the factor is not positive.  Everything is indexed at compile time so the matrix stays in registers.
+// N = 6: PoseOptimization's vertex; N = 7: OptimizeSim3's (orbfe_sim3_blocks.hpp).
+template <int N>
+__device__ inline bool solve_ldlt(const double *Hu /*N (N + 1) / 2, upper triangle row-major, then b[N]*/, double lambda, double *x)
+{
+    constexpr int NU = N * (N + 1) / 2;
+    double A[N][N], y[N];
     {
         int k = 0;
 #pragma unroll
-        for (int i = 0; i < 6; i++)
+        for (int i = 0; i < N; i++)
 #pragma unroll
-            for (int j = i; j < 6; j++) { A[i][j] = Hu[k]; A[j][i] = Hu[k]; k++; }
+            for (int j = i; j < N; j++) { A[i][j] = Hu[k]; A[j][i] = Hu[k]; k++; }
 #pragma unroll
-        for (int i = 0; i < 6; i++) { A[i][i] += lambda; y[i] = Hu[21 + i]; }
+        for (int i = 0; i < N; i++) { A[i][i] += lambda; y[i] = Hu[NU + i]; }
     }
-    int perm[6] = {0, 1, 2, 3, 4, 5};
-    double dinv[6];
-    bool usable[6];
+    int perm[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) perm[i] = i;
+    double dinv[N];
+    bool usable[N];
     bool positive = true;
-    ldlt_step<0>(A, y, dinv, usable, perm, positive);
-    ldlt_step<1>(A, y, dinv, usable, perm, positive);
-    ldlt_step<2>(A, y, dinv, usable, perm, positive);
-    ldlt_step<3>(A, y, dinv, usable, perm, positive);
-    ldlt_step<4>(A, y, dinv, usable, perm, positive);
-    ldlt_step<5>(A, y, dinv, usable, perm, positive);
+    ldlt_steps<N>(A, y, dinv, usable, perm, positive, std::make_integer_sequence<int, N>());
     if (!positive) return false;
 #pragma unroll
-    for (int i = 0; i < 6; i++)
+    for (int i = 0; i < N; i++)
 #pragma unroll
         for (int j = 0; j < i; j++) y[i] -= A[i][j] * y[j];
 #pragma unroll
-    for (int i = 0; i < 6; i++) y[i] = usable[i] ? y[i] * dinv[i] : 0.0;
+    for (int i = 0; i < N; i++) y[i] = usable[i] ? y[i] * dinv[i] : 0.0;
 #pragma unroll
-    for (int i = 5; i >= 0; i--)
+    for (int i = N - 1; i >= 0; i--)
 #pragma unroll
-        for (int j = i + 1; j < 6; j++) y[i] -= A[j][i] * y[j];
-    unpermute_step<4>(y, perm);
-    unpermute_step<3>(y, perm);
-    unpermute_step<2>(y, perm);
-    unpermute_step<1>(y, perm);
-    unpermute_step<0>(y, perm);
+        for (int j = i + 1; j < N; j++) y[i] -= A[j][i] * y[j];
+    unpermute_steps<N>(y, perm, std::make_integer_sequence<int, N - 1>());
 #pragma unroll
-    for (int i = 0; i < 6; i++) x[i] = y[i];
+    for (int i = 0; i < N; i++) x[i] = y[i];
     return true;
 }
+
+__device__ inline bool solve_ldlt6(const double *Hu /*21, upper triangle row-major, then b[6]*/, double lambda, double *x) { return solve_ldlt<6>(Hu, lambda, x); }
 
 // Per-problem edge table.  EDGES_IN_LDS: seven floats and a state byte per keypoint slot staged once (Xw, observation,
 // information); otherwise the caller's arrays are re-read on every pass (frames with more slots than the LDS holds).
@@ -391,6 +406,13 @@ __device__ long long g_pose_cycles[8]; // [0] solve [1] exp+mul [2] edge loop [3
 #define PO_T(var)
 #define PO_ACC(slot, a, b)
 #endif
+
+// The dynamic LDS of pose_opt_kernel (orbfe_pose.hip): row partials and totals, double-buffered, then the edge table.  Here because
+// orbfe_sim3_opt.hip may not request more than pose_lds_bytes<256>(PO_LDS_CAP_MAX).
+constexpr int PO_LDS_CAP_MAX = 4096; // keypoint slots per problem the LDS edge table holds (29 B each)
+
+template <int THREADS>
+constexpr size_t pose_lds_bytes(int cap) { return sizeof(double) * (2 * (THREADS / 16) * 32 + 2 * 32) + (size_t)cap * (7 * sizeof(float) + 1) + 16; }
 
 template <int THREADS, bool IN_LDS>
 __device__ void eval_pass(const EdgeTable &E, const Se3 &q, const CamD &c, bool robust, double delta_mono, double delta_stereo,

@@ -1,11 +1,18 @@
 // Optimizer.h -- host-side mirror of ORB_SLAM2::Optimizer::PoseOptimization (reference include/Optimizer.h:48,
-// src/Optimizer.cc:283-495) over the C ABI (include/orbfe.h).  The reference takes a Frame*; this mirror takes the
+// src/Optimizer.cc:283-495) and Optimizer::OptimizeSim3 over the C ABI (include/orbfe.h).  The reference takes a Frame*; this mirror takes the
 // fields of the Frame it reads and writes, flattened:
 //   reads   mTcw, N, mvKeysUn, mvuRight, mvpMapPoints[i] != NULL and GetWorldPos() of those, mvInvLevelSigma2 / fx, fy,
 //           cx, cy, mbf (taken from the context the extractor of this camera was built with)
 //   writes  mvbOutlier (entries that hold a map point), the pose handed to SetPose, and returns the inlier count
 // A drop-in Optimizer::PoseOptimization(Frame *pFrame) gathers those fields, calls this, and finishes with
 // pFrame->SetPose(cv::Mat(4, 4, CV_32F, Tcw).clone()) when at least 3 correspondences existed.
+//
+// Optimizer::OptimizeSim3 (include/Optimizer.h, src/Optimizer.cc:1090-1285) likewise, on the fields of the two keyframes it reads:
+//   reads   GetRotation() / GetTranslation() of both (T1w, T2w: 3x4 row major), mvKeysUn, per keypoint slot GetWorldPos() of its map point
+//           and pMP && !pMP->isBad(); vpMatches1 as keypoint slots of KF2 (-1: none); the Sim3 as LoopClosing::ComputeSim3 builds it
+//           (s, R, t of the Sim3Solver: floats); th2, bFixScale
+//   writes  vnMatches12 (outliers become -1), S12 = qx qy qz qw tx ty tz s of the optimised g2o::Sim3 (the input one when the
+//           optimisation gives up), and returns nIn
 #pragma once
 
 #include <cstdint>
@@ -35,6 +42,26 @@ public:
                                                vbOutlier.data(), &nInliers);
         if (rc != ORBFE_OK) throw std::runtime_error(std::string("orbfe: ") + orbfe_last_error(ctx));
         return nInliers;
+    }
+
+    // returns nIn; vnMatches12 (one entry per keypoint of KF1) is updated in place, S12 receives eight doubles.  vnPrior12 may be empty:
+    // otherwise its entries >= 0 take precedence over vnMatches12's (the RANSAC inliers, src/LoopClosing.cc:343-353).
+    static int OptimizeSim3(orbfe_context *ctx, const std::vector<orbfe_keypoint> &vKeysUn1, const float *T1w, const std::vector<float> &vWorldPos1 /* 3 per keypoint */,
+                            const std::vector<int32_t> &vbValid1, const std::vector<orbfe_keypoint> &vKeysUn2, const float *T2w,
+                            const std::vector<float> &vWorldPos2, const std::vector<int32_t> &vbValid2, float s12, const float *R12, const float *t12,
+                            std::vector<int32_t> &vnMatches12, double *S12, float th2, bool bFixScale, const std::vector<int32_t> &vnPrior12 = std::vector<int32_t>(),
+                            const orbfe_sim3_opt_params *params = nullptr)
+    {
+        const size_t N1 = vKeysUn1.size(), N2 = vKeysUn2.size();
+        if (vWorldPos1.size() != 3 * N1 || vbValid1.size() != N1 || vnMatches12.size() != N1 || vWorldPos2.size() != 3 * N2 || vbValid2.size() != N2 ||
+            (!vnPrior12.empty() && vnPrior12.size() != N1))
+            throw std::invalid_argument("Optimizer::OptimizeSim3: per-keypoint arrays differ in length");
+        int nIn = 0;
+        const int rc = orbfe_optimize_sim3(ctx, vKeysUn1.data(), (int)N1, T1w, vWorldPos1.data(), vbValid1.data(), vKeysUn2.data(), (int)N2, T2w,
+                                           vWorldPos2.data(), vbValid2.data(), s12, R12, t12, th2, bFixScale ? 1 : 0, params,
+                                           vnPrior12.empty() ? nullptr : vnPrior12.data(), vnMatches12.data(), S12, &nIn);
+        if (rc != ORBFE_OK) throw std::runtime_error(std::string("orbfe: ") + orbfe_last_error(ctx));
+        return nIn;
     }
 };
 
