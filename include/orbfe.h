@@ -930,6 +930,100 @@ int orbfe_optimize_sim3(orbfe_context *ctx,
         const orbfe_keypoint *keys_un2, int n2, const float *T2w, const float *pos2, const int32_t *valid2,
         float s12, const float *R12, const float *t12, float th2, int fix_scale, const orbfe_sim3_opt_params *params,
         const int32_t *prior12, int32_t *match12, double *S12, int *n_inliers);
+/* ---- Sim3Solver (src/Sim3Solver.cc) of LoopClosing::ComputeSim3 (src/LoopClosing.cc:298-378) for ALL candidates in one call
+ * (orbfe_sim3_ransac.hip).  A hypothesis of Sim3Solver::iterate depends on its three draws only, and iterate returns exactly at the
+ * hypotheses whose inlier count is > min_inliers and >= every earlier count, so every hypothesis of every candidate is evaluated at
+ * once and the 5-iteration round-robin of :322-378 becomes a host walk over the fetched events (ORB_SLAM2::Sim3Solver of
+ * orbslam2_amd/host/Sim3Solver.h does it).  The contract of the enqueue calls above holds: asynchronous on `stream` (NULL: the
+ * context's stream), nothing waits for the GPU, nothing is copied from host memory on the stream.  Three launches whatever n_cands is.
+ *
+ * KF1 is mpCurrentKF: kf1 a HOST record of which only keys_un (octave) and n are read, T1w a HOST 3x4, d_pos1 / d_valid1 as
+ * orbfe_enqueue_optimize_sim3 takes them (GetWorldPos per keypoint slot; plain pMP && !isBad()).  The candidates are a DEVICE array of the
+ * 64-byte records below; pairs / n_pairs are row c of d_pairs and &d_nmatches[c] exactly as orbfe_enqueue_search_by_bow_kf_batch left
+ * them: (idx1, idx2) in strictly ascending idx1, the count still on the device.  max_pairs and max_kf_n are upper bounds that size
+ * the grid and the row strides; the device checks every record against them.  The camera and mvLevelSigma2 are the context's, for
+ * both keyframes.
+ *
+ * The constructor's filter (:63-104): a pair survives iff d_valid1[idx1] && valid[idx2]; survivors keep pair order (mvnIndices1's).
+ * The keypoint read for sigmaSquare is the slot itself, which equals GetIndexInKeyFrame whenever a map point is observed once per
+ * keyframe.  Per survivor X3Dc = Rcw * Xw + tcw on both sides, FromCameraToImage, and the two gates (float)(size_t)(9.210 * (double)sigma2):
+ * mvnMaxError1/2 are std::vector<size_t>, so the reference truncates (9 on level 0, not 9.21).
+ * Draws: draws[max_its][3] raw glibc rand() values; the device applies DUtils::Random::RandomInt and the swap-with-back-and-pop of
+ * :164-178 in FP64.  Each candidate has a draw row of its own (ORB_SLAM2::DrawSim3Sets fills one): the reference's global rand() stream,
+ * shared with PnPsolver and Initializer, is not reproduced; the distribution is.
+ * Iterations: d_its_for_n[N], N in [0, max_pairs], is mRansacMaxIts after SetRansacParameters for N correspondences
+ * (ORB_SLAM2::Sim3RansacIterationTable: 0 below min_inliers -- the bNoMore exit --, 1 at min_inliers); the device clamps it to max_its.
+ * Float contract: DESIGN.md sections 4i2 and 4o.  Every cv::Mat float step is restated (products as double sums rounded once, MatExpr
+ * scales as the gemm's alpha, cv::reduce as a float sum, cv::pow(., 2) as a float product, den as a double sum, ms12i = (float)(nom / den));
+ * cv::eigen is replaced by a cyclic two-sided Jacobi in FP64 and atan2 + cv::Rodrigues by the rotation matrix of the unit quaternion
+ * (R = I where the reference divides 0 / 0).  Everything else is IEEE as written: den == 0, z == 0 and NaN errors that fail `<`.  A NaN is
+ * stored as 0x7fc00000.  Results are bit-reproducible run to run and equal tests/sim3_solver_model.py and the host form bit for bit.
+ *
+ * Outputs, device rows per candidate c, every row written by every call, nothing written outside row c, a fault of record c changes
+ * no other row:
+ *   d_n_corr[c], d_n_its[c]            N; the iterations the solver would run at most (0: bNoMore at once)
+ *   d_corr[c][max_pairs][2]            the surviving (idx1, idx2); (-1, -1) from N on
+ *   d_sets[c][max_its][3]              optional (may be NULL): the drawn correspondence indices; -1 from n_its on
+ *   d_hyp[c][max_its]                  the 64-byte records below; zero from n_its on
+ *   d_inlier_bits[c][max_its][W]       W = ceil(max_pairs / 32): mvbInliersi over the correspondences, tail bits 0; zero from n_its on
+ *   d_events[c][max_its], d_n_events[c] the iterations k at which iterate would return, ascending; -1 from n_events on
+ *   d_status[c]                        0, or ORBFE_ERR_INVALID: a record with n outside [0, max_kf_n], *n_pairs outside [0, max_pairs] or a
+ *                                      NULL pointer (N = 0, no iteration); a pair index out of range or an octave outside [0, nlevels)
+ *                                      (that pair is dropped and never used as an address; the rest of the row is computed without it)
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL context, kf1, T1w or output other than d_sets; d_cands, d_its_for_n
+ * NULL under n_cands > 0; kf1->n negative or > 65535 or > max_kf_n; a NULL array of KF1 under kf1->n > 0; n_cands < 0 or > 65535;
+ * max_pairs < 1 or > 65535; max_kf_n < 0 or > 65535; min_inliers < 3; max_its < 1 or > 65536.  n_cands == 0: ORBFE_OK, nothing queued.
+ * The correspondence table (12 floats per row) lives in the context's grow-only scratch and is staged in the LDS up to
+ * ORBFE_SIM3_RANSAC_LDS_SLOTS correspondences: queue the calls of one context on one stream. */
+#define ORBFE_SIM3_RANSAC_LDS_SLOTS 1024
+typedef struct orbfe_sim3_ransac_candidate {   /* 64 bytes; every pointer is a device pointer */
+    const orbfe_keypoint *keys_un;        /* the candidate keyframe per keypoint slot: mvKeysUn (octave is read) */
+    const float   *pos;                   /* GetWorldPos, 3 floats */
+    const int32_t *valid;                 /* pMP && !isBad() */
+    const float   *T2w;                   /* 12 floats: the candidate's 3x4 pose */
+    const int32_t *pairs;                 /* [*n_pairs][2]: (idx1, idx2), strictly ascending idx1 */
+    const int32_t *n_pairs;               /* [1] */
+    const uint32_t *draws;                /* [max_its][3] raw rand() values */
+    int32_t n;                            /* keypoint slots, <= max_kf_n */
+    int32_t reserved;
+} orbfe_sim3_ransac_candidate;
+typedef struct orbfe_sim3_hypothesis {         /* 64 bytes: mnInliersi, ms12i, mR12i (row-major), mt12i of one iteration */
+    int32_t n_inliers;
+    float s12, R12[9], t12[3];
+    int32_t pad[2];
+} orbfe_sim3_hypothesis;
+int orbfe_enqueue_sim3_ransac_batch(orbfe_context *ctx,
+        const orbfe_grid_keyframe *kf1 /* host */, const float *T1w /* host */, const float *d_pos1, const int32_t *d_valid1,
+        const orbfe_sim3_ransac_candidate *d_cands /* DEVICE array */, int n_cands, int max_pairs, int max_kf_n,
+        int fix_scale, int min_inliers, int max_its, const int32_t *d_its_for_n /* [max_pairs + 1] */,
+        int32_t *d_n_corr /* [n_cands] */, int32_t *d_n_its /* [n_cands] */, int32_t *d_corr /* [n_cands][max_pairs][2] */,
+        int32_t *d_sets /* [n_cands][max_its][3] or NULL */, orbfe_sim3_hypothesis *d_hyp /* [n_cands][max_its] */,
+        uint32_t *d_inlier_bits /* [n_cands][max_its][ceil(max_pairs / 32)] */, int32_t *d_events /* [n_cands][max_its] */,
+        int32_t *d_n_events /* [n_cands] */, int32_t *d_status /* [n_cands] */, void *stream);
+/* What the round of candidate c at iteration k (host ints chosen from the fetched events) hands to orbfe_enqueue_search_by_sim3 and
+ * orbfe_enqueue_optimize_sim3, written on the stream from the rows the call above left in HBM, so that no array is uploaded per round:
+ *   d_prior12[kf1_n]         the KF2 slot where hypothesis k calls the correspondence an inlier, else -1 (src/LoopClosing.cc:349-354)
+ *   d_valid1_round[kf1_n]    d_valid1 && d_prior12 < 0            (the !vbAlreadyMatched1 term of src/ORBmatcher.cc:1125-1152)
+ *   d_valid2_round[max_kf_n] valid && not taken by an inlier, for the record's n slots; the entries from n on are left untouched
+ * d_status[1]: 0, or ORBFE_ERR_INVALID when k >= d_n_its[c] (every d_prior12 entry -1, the valid arrays copied), when the record's n is
+ * outside [0, max_kf_n] (the same, and d_valid2_round is not written), or when a d_corr entry is out of range (that entry is skipped).  R12, t12 and s12 of the next two calls are host
+ * arguments: they come from the fetched d_hyp record.  One launch of one workgroup.
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL pointer (d_valid1 under kf1_n > 0), c outside [0, n_cands), k outside
+ * [0, max_its), kf1_n or max_kf_n outside [0, 65535], max_pairs < 1. */
+int orbfe_enqueue_sim3_ransac_select(orbfe_context *ctx, const orbfe_sim3_ransac_candidate *d_cands, int n_cands, int c, int k,
+        int kf1_n, const int32_t *d_valid1, int max_pairs, int max_kf_n, int max_its,
+        const int32_t *d_n_corr, const int32_t *d_n_its, const int32_t *d_corr, const uint32_t *d_inlier_bits,
+        int32_t *d_prior12 /* [kf1_n] */, int32_t *d_valid1_round /* [kf1_n] */, int32_t *d_valid2_round /* [max_kf_n] */,
+        int32_t *d_status /* [1] */, void *stream);
+/* orbfe_enqueue_sim3_ransac_batch from host arrays for ONE candidate, synchronous (it uploads, calls the enqueue form on the context's
+ * stream and downloads: the same bits).  max_pairs = n_pairs (at least 1), max_kf_n = max(n1, n2).  Outputs are host arrays shaped as
+ * one row of the call above; sets may be NULL.  Returns ORBFE_ERR_INVALID as the call above does, and also -- after the outputs are
+ * written -- when the device set the status. */
+int orbfe_sim3_ransac(orbfe_context *ctx,
+        const orbfe_keypoint *keys_un1, int n1, const float *T1w, const float *pos1, const int32_t *valid1,
+        const orbfe_keypoint *keys_un2, int n2, const float *T2w, const float *pos2, const int32_t *valid2,
+        const int32_t *pairs, int n_pairs, const uint32_t *draws, int fix_scale, int min_inliers, int max_its, const int32_t *its_for_n,
+        int *n_corr, int *n_its, int32_t *corr, int32_t *sets, orbfe_sim3_hypothesis *hyp, uint32_t *inlier_bits, int32_t *events, int *n_events);
 /* ---- the writer of the map-point table (orbfe_map_point_device.hip): MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307)
  * and MapPoint::UpdateNormalAndDepth (:330-371) for chosen rows of the table that orbfe_enqueue_fuse and the Sim3 matchers read, from
  * observation lists over device-resident keyframes.  The contract of the enqueue matchers above holds: asynchronous on `stream` (NULL:

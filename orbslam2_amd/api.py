@@ -42,6 +42,7 @@ EXPORTS = [
     "orbfe_enqueue_search_for_triangulation",
     "orbfe_enqueue_keyframe_grid", "orbfe_enqueue_fuse", "orbfe_enqueue_fuse_sim3",
     "orbfe_enqueue_search_by_sim3", "orbfe_enqueue_search_by_projection_sim3", "orbfe_enqueue_optimize_sim3", "orbfe_optimize_sim3",
+    "orbfe_enqueue_sim3_ransac_batch", "orbfe_enqueue_sim3_ransac_select", "orbfe_sim3_ransac",
     "orbfe_enqueue_search_by_bow_kf", "orbfe_enqueue_search_by_bow_kf_batch",
     "orbfe_enqueue_update_map_points",
     "orbfe_enqueue_triangulate_pairs",
@@ -110,6 +111,20 @@ class Sim3OptParams(C.Structure):
 
 
 SIM3_OPT_LDS_SLOTS = 2048  # ORBFE_SIM3_OPT_LDS_SLOTS
+
+
+class Sim3RansacCandidate(C.Structure):
+    """orbfe_sim3_ransac_candidate (include/orbfe.h): one candidate keyframe of enqueue_sim3_ransac_batch, device pointers; an ARRAY of
+    these records lives in HBM.  pairs / n_pairs: row c of enqueue_search_by_bow_kf_batch's d_pairs and &d_nmatches[c]."""
+    _fields_ = [("keys_un", C.c_void_p), ("pos", C.c_void_p), ("valid", C.c_void_p), ("T2w", C.c_void_p), ("pairs", C.c_void_p), ("n_pairs", C.c_void_p),
+                ("draws", C.c_void_p), ("n", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(Sim3RansacCandidate) == 64
+# orbfe_sim3_hypothesis: one iteration's mnInliersi, ms12i, mR12i (row-major), mt12i
+SIM3_HYP_DTYPE = np.dtype([("n_inliers", "<i4"), ("s12", "<f4"), ("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("pad", "<i4", (2,))])
+assert SIM3_HYP_DTYPE.itemsize == 64
+SIM3_RANSAC_LDS_SLOTS = 1024  # ORBFE_SIM3_RANSAC_LDS_SLOTS
 
 
 class ObsKeyframe(C.Structure):
@@ -302,6 +317,12 @@ def load():
                                               + [vp] * 6)
     L.orbfe_optimize_sim3.restype = C.c_int
     L.orbfe_optimize_sim3.argtypes = [vp] + [vp, C.c_int, vp, vp, vp] * 2 + [C.c_float, vp, vp, C.c_float, C.c_int, C.POINTER(Sim3OptParams), vp, vp, vp, ip]
+    L.orbfe_enqueue_sim3_ransac_batch.restype = C.c_int
+    L.orbfe_enqueue_sim3_ransac_batch.argtypes = [vp, C.POINTER(GridKeyframe), vp, vp, vp, vp] + [C.c_int] * 6 + [vp] * 11
+    L.orbfe_enqueue_sim3_ransac_select.restype = C.c_int
+    L.orbfe_enqueue_sim3_ransac_select.argtypes = [vp, vp] + [C.c_int] * 4 + [vp] + [C.c_int] * 3 + [vp] * 9
+    L.orbfe_sim3_ransac.restype = C.c_int
+    L.orbfe_sim3_ransac.argtypes = [vp] + [vp, C.c_int, vp, vp, vp] * 2 + [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, ip, ip, vp, vp, vp, vp, vp, ip]
     L.orbfe_enqueue_search_by_sim3.restype = C.c_int
     L.orbfe_enqueue_search_by_sim3.argtypes = [vp] + [C.POINTER(GridKeyframe)] + [vp] * 6 + [C.POINTER(GridKeyframe)] + [vp] * 6 + [C.c_float, vp, vp, C.c_float] + [vp] * 4
     L.orbfe_enqueue_search_by_projection_sim3.restype = C.c_int
@@ -328,6 +349,20 @@ def load():
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def sim3_iteration_table(max_pairs, probability=0.99, min_inliers=20, max_its=300):
+    """ORB_SLAM2::Sim3RansacIterationTable (orbslam2_amd/host/Sim3Solver.h): d_its_for_n of enqueue_sim3_ransac_batch, mRansacMaxIts after
+    Sim3Solver::SetRansacParameters for every N in [0, max_pairs]; 0 below min_inliers (iterate's bNoMore exit)."""
+    import math
+    out = np.zeros(max_pairs + 1, np.int32)
+    for N in range(min_inliers, max_pairs + 1):
+        n = 1.0
+        if N != min_inliers:
+            den = math.log(1 - math.pow(float(np.float32(min_inliers) / np.float32(N)), 3))
+            n = math.ceil(math.log(1 - probability) / den) if den != 0 else math.inf
+        out[N] = max(1, min(max_its if not n < max_its else int(n), max_its))
+    return out
 
 
 def reconstruct_accept(model, cos_parallax, min_parallax):
@@ -941,6 +976,49 @@ class Context:
                                                        v(d_pos2 or None), v(d_valid2 or None), float(s12), _p(R), _p(t), float(th2), int(fix_scale),
                                                        None if params is None else C.byref(params), v(d_prior12 or None), v(d_match12 or None),
                                                        v(d_S12 or None), v(d_n_inliers or None), v(d_status or None), v(stream or None)))
+
+    def enqueue_sim3_ransac_batch(self, kf1, T1w, d_pos1, d_valid1, d_cands, n_cands, max_pairs, max_kf_n, fix_scale, min_inliers, max_its, d_its_for_n,
+                                  d_n_corr, d_n_its, d_corr, d_sets, d_hyp, d_inlier_bits, d_events, d_n_events, d_status, stream=0):
+        """Sim3Solver for all candidates of LoopClosing::ComputeSim3 in one call (include/orbfe.h), asynchronous on `stream`.  kf1: a
+        GridKeyframe record on the host (keys_un and n are read), T1w a host 3x4; d_cands: a device array of Sim3RansacCandidate;
+        d_its_for_n: sim3_iteration_table() in HBM.  Every output is a device address; d_sets may be 0."""
+        v = C.c_void_p
+        t1 = np.ascontiguousarray(T1w, np.float32)
+        assert t1.size >= 12
+        self._check(self.L.orbfe_enqueue_sim3_ransac_batch(
+            self.h, C.byref(kf1) if kf1 is not None else None, _p(t1), v(d_pos1 or None), v(d_valid1 or None), v(d_cands or None), n_cands, max_pairs, max_kf_n,
+            int(fix_scale), min_inliers, max_its, *[v(x or None) for x in (d_its_for_n, d_n_corr, d_n_its, d_corr, d_sets, d_hyp, d_inlier_bits, d_events,
+                                                                           d_n_events, d_status, stream)]))
+
+    def enqueue_sim3_ransac_select(self, d_cands, n_cands, c, k, kf1_n, d_valid1, max_pairs, max_kf_n, max_its, d_n_corr, d_n_its, d_corr, d_inlier_bits,
+                                   d_prior12, d_valid1_round, d_valid2_round, d_status, stream=0):
+        """What the round of candidate c at iteration k hands to enqueue_search_by_sim3 and enqueue_optimize_sim3, written on `stream`
+        from the rows enqueue_sim3_ransac_batch left in HBM: d_prior12, d_valid1_round [kf1_n], d_valid2_round [max_kf_n]."""
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_sim3_ransac_select(
+            self.h, v(d_cands or None), n_cands, c, k, kf1_n, v(d_valid1 or None), max_pairs, max_kf_n, max_its,
+            *[v(x or None) for x in (d_n_corr, d_n_its, d_corr, d_inlier_bits, d_prior12, d_valid1_round, d_valid2_round, d_status, stream)]))
+
+    def sim3_ransac(self, keys_un1, T1w, pos1, valid1, keys_un2, T2w, pos2, valid2, pairs, draws, fix_scale, min_inliers, max_its, its_for_n):
+        """enqueue_sim3_ransac_batch from host arrays for one candidate, synchronous; max_pairs = max(len(pairs), 1).  Returns a dict of
+        the candidate's rows.  Raises OrbfeError (ERR_INVALID) for what only the device can see."""
+        k1 = np.ascontiguousarray(keys_un1, KP_DTYPE); k2 = np.ascontiguousarray(keys_un2, KP_DTYPE)
+        t1 = np.ascontiguousarray(T1w, np.float32); t2 = np.ascontiguousarray(T2w, np.float32)
+        p1 = np.ascontiguousarray(pos1, np.float32); p2 = np.ascontiguousarray(pos2, np.float32)
+        v1 = np.ascontiguousarray(valid1, np.int32); v2 = np.ascontiguousarray(valid2, np.int32)
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2); dr = np.ascontiguousarray(draws, np.uint32)
+        tab = np.ascontiguousarray(its_for_n, np.int32)
+        assert t1.size >= 12 and t2.size >= 12 and dr.size >= 3 * max_its and tab.size >= len(pr) + 1
+        mp = max(len(pr), 1)
+        out = dict(corr=np.zeros((mp, 2), np.int32), sets=np.zeros((max_its, 3), np.int32), hyp=np.zeros(max_its, SIM3_HYP_DTYPE),
+                   bits=np.zeros((max_its, (mp + 31) // 32), np.uint32), events=np.zeros(max_its, np.int32))
+        n_corr, n_its, n_ev = C.c_int(), C.c_int(), C.c_int()
+        ptr = lambda a: _p(a) if a.size else None
+        self._check(self.L.orbfe_sim3_ransac(self.h, ptr(k1), len(k1), _p(t1), ptr(p1), ptr(v1), ptr(k2), len(k2), _p(t2), ptr(p2), ptr(v2), ptr(pr), len(pr),
+                                             _p(dr), int(fix_scale), min_inliers, max_its, _p(tab), C.byref(n_corr), C.byref(n_its), _p(out["corr"]),
+                                             _p(out["sets"]), _p(out["hyp"]), _p(out["bits"]), _p(out["events"]), C.byref(n_ev)))
+        out.update(n_corr=n_corr.value, n_its=n_its.value, n_events=n_ev.value, status=0)
+        return out
 
     def optimize_sim3(self, keys_un1, T1w, pos1, valid1, keys_un2, T2w, pos2, valid2, s12, R12, t12, th2, fix_scale, match12, prior12=None,
                       params=None):

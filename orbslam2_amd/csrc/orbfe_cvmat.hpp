@@ -1,7 +1,7 @@
 // orbfe_cvmat.hpp -- the per-lane cv::Mat float steps of DESIGN.md section 4i2 on 3 x 3 matrices and 3-vectors in registers: the product
 // (a double sum over k in index order, one rounding) with its alpha and `+ C` forms, Mat::inv / cv::determinant, cv::norm, the scale by
-// (float)(1.0 / d), and the one stored NaN.  Shared by orbfe_initializer_device.hip, orbfe_reconstruct_device.hip and
-// orbfe_triangulate_device.hip: one definition, the same bits.  The Jacobis are in orbfe_jacobi4.hpp and orbfe_jacobi_wave.hpp.
+// (float)(1.0 / d), cv::reduce / Mat::dot / the sum of cv::pow(., 2) on a 3 x 3, and the one stored NaN.  Shared by
+// orbfe_initializer_device.hip, orbfe_reconstruct_device.hip, orbfe_triangulate_device.hip and orbfe_sim3_ransac.hip: one definition, the same bits.  The Jacobis are in orbfe_jacobi4.hpp and orbfe_jacobi_wave.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -109,6 +109,31 @@ __device__ __forceinline__ double norm3(const float (&v)[3])
 {
     return sqrt((double)v[0] * (double)v[0] + (double)v[1] * (double)v[1] + (double)v[2] * (double)v[2]);
 }
+
+// ---------------------------------------------------------------------------------------------------------------- reductions of a 3 x 3
+// cv::reduce(., CV_REDUCE_SUM) along a row of three floats: a float sum in index order
+__device__ __forceinline__ float reduce_sum3(float a, float b, float c) { return (a + b) + c; }
+
+// Mat::dot of two 3 x 3 float matrices: a double sum of double products in index order
+__device__ __forceinline__ double dot9(const float (&a)[9], const float (&b)[9])
+{
+    double s = 0;
+#pragma unroll
+    for (int k = 0; k < 9; k++) s += (double)a[k] * (double)b[k];
+    return s;
+}
+
+// cv::pow(., 2) on floats is a float product; summing its elements into a double is a double sum of those float squares
+__device__ __forceinline__ double sum_of_squared_floats9(const float (&v)[9])
+{
+    double s = 0;
+#pragma unroll
+    for (int k = 0; k < 9; k++) s += (double)__fmul_rn(v[k], v[k]);
+    return s;
+}
+
+// float = double / double: the double quotient rounded once; den == 0 is IEEE
+__device__ __forceinline__ float ratio(double nom, double den) { return (float)(nom / den); }
 
 // ---------------------------------------------------------------------------------------------------------------- stored floats
 __device__ __forceinline__ float one_nan(float v) { return v != v ? __int_as_float(0x7fc00000) : v; } // a NaN is stored with one bit pattern

@@ -154,6 +154,36 @@ inline void Unit(float t[3])
     for (int k = 0; k < 3; k++) t[k] = t[k] * a;
 }
 
+// cv::reduce(., CV_REDUCE_SUM) of n floats: a float sum in index order
+inline float ReduceSum(const float *v, int n)
+{
+    float s = v[0];
+    for (int k = 1; k < n; k++) s = s + v[k];
+    return s;
+}
+
+// Mat::dot of two float matrices of n elements: a double sum of double products in index order
+inline double Dot(const float *a, const float *b, int n)
+{
+    double s = 0;
+    for (int k = 0; k < n; k++) s += (double)a[k] * b[k];
+    return s;
+}
+
+// cv::pow(., 2) on floats is a float product; the element-wise `den += aux.at<float>(i, j)` over it a double sum of those float squares
+inline double SumOfSquaredFloats(const float *v, int n)
+{
+    double s = 0;
+    for (int k = 0; k < n; k++) {
+        const float sq = v[k] * v[k];
+        s += sq;
+    }
+    return s;
+}
+
+// float = double / double (ms12i = nom / den): the double quotient rounded once; den == 0 is IEEE
+inline float Ratio(double nom, double den) { return (float)(nom / den); }
+
 // a NaN is stored with one bit pattern everywhere
 inline float Stored(float s)
 {

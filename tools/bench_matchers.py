@@ -55,8 +55,11 @@ observes and 13 500 others in the same volume, shuffled) against the current key
 matched closed on entry.  (a) the 15 + 1 synchronous calls; (b) -- when the library has them -- 15 x
 (orbfe_enqueue_search_by_sim3 + download of match12, count and status into pinned memory + stream synchronise: Sim3Solver runs on the
 host) and the same for orbfe_enqueue_search_by_projection_sim3, keyframes, grids and tables uploaded outside the timed window; (c) the
-16 enqueues queued back to back as GPU time between two events, and the SearchByProjection enqueue alone.  (a) and (b) are checked
-against the oracle.  Five repeats of each,
+16 enqueues queued back to back as GPU time between two events, and the SearchByProjection enqueue alone; (b') is (b) with the three
+uploads a round of the host solver costs; (d) -- when the library has orbfe_enqueue_sim3_ransac_batch -- Sim3Solver for the three
+candidates in one call (300 iterations, the first round's matches as pairs), one download of the events and hypotheses, then per round
+orbfe_enqueue_sim3_ransac_select + SearchBySim3 + download + synchronise (profiles/sim3_ransac.json); (e) (f) (g) its parts.  (a) and (b)
+are checked against the oracle.  Five repeats of each,
 interleaved; every repeat is the mean of 10 loops, its slowest loop beside it.
     python3 tools/bench_matchers.py --bow-kf [--lib path/to/another/liborbfe.so]
 runs only the SearchByFboW(KeyFrame, KeyFrame) rows of ComputeSim3 (profiles/bow_kf_device.json): the current keyframe of 1500 keypoints
@@ -105,7 +108,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import oracle as O  # noqa: E402
 from tests import test_matchers as TM  # noqa: E402
-from tests.device_arrays import raw, timed_loops, upload  # noqa: E402
+from tests.device_arrays import raw, timed_loops, upload, upload_records  # noqa: E402
 
 
 def up(a, dtype=None):
@@ -961,14 +964,115 @@ def sim3_rows(out):
                         assert res[1] == 0 and res[0] == ref[1] and np.array_equal(res[2:2 + m], ref[0]), (k, r)
 
         device_loop(check=True)
+        have_ransac = hasattr(ctx.L, "orbfe_enqueue_sim3_ransac_batch") and hasattr(ctx.L, "orbfe_enqueue_sim3_ransac_select")
+        # (b') what (b) leaves out of a round besides the host solver itself: the three arrays Sim3Solver's inliers decide, uploaded
+        # from pinned memory before the SearchBySim3 call that reads them (d_valid1, d_valid2, d_prior12)
+        n2max = max(len(c["k"]) for c in cands)
+        h_round = torch.zeros(2 * n1 + n2max, dtype=torch.int32).pin_memory()
+        d_round = torch.zeros(2 * n1 + n2max, dtype=torch.int32, device=dev)
+
+        def device_loop_uploads():
+            with torch.cuda.stream(st):
+                for k, r in calls:
+                    if k < K:
+                        d_round.copy_(h_round, non_blocking=True)
+                    enqueue(k, r)
+                    m = n1 if k < K else nq
+                    h_res[:2 + m].copy_(d_res[:2 + m], non_blocking=True)
+                    st.synchronize()
+
+        if have_ransac:
+            # Sim3Solver on the device for all three candidates (orbfe_enqueue_sim3_ransac_batch): the pairs are the first round's matches
+            # (what SearchByBoW would hand over), rows of kf1->n pairs as orbfe_enqueue_search_by_bow_kf_batch lays them out
+            MAX_ITS, MIN_INL = 300, 20
+            pos1, valid1 = np.ascontiguousarray(cur["pts1"][0], np.float32).reshape(n1, 3), np.ascontiguousarray(cur["pts1"][4], np.int32)
+            d_pos1, d_valid1 = up(pos1), up(valid1)
+            tab = up(api.sim3_iteration_table(n1, 0.99, MIN_INL, MAX_ITS))
+            rk, rrecs = [], []
+            for k, c in enumerate(cands):
+                m12 = refs[k][0][0]
+                i1 = np.nonzero(m12 >= 0)[0]
+                rows = np.zeros((n1, 2), np.int32)
+                rows[:len(i1)] = np.stack([i1, m12[i1]], 1)
+                n2 = len(c["k"])
+                a = [up(np.ascontiguousarray(c["pts2"][0], np.float32).reshape(n2, 3)), up(np.ones(n2, np.int32)), up(np.ascontiguousarray(c["T_cur"], np.float32)[:3]),
+                     up(rows), up(np.array([len(i1)], np.int32)), up(rng.integers(0, 2 ** 31, (MAX_ITS, 3)).astype(np.uint32).view(np.int32))]
+                rk.append(a)
+                rrecs.append(api.Sim3RansacCandidate(keep[1 + k][0].data_ptr(), *[x.data_ptr() for x in a], n2, 0))
+            d_recs = upload_records(rrecs)
+            words = (n1 + 31) // 32
+            # results: [n_events | events | hyp] in one block (one download), then what stays in HBM
+            hyp_off = 4 * K + 4 * K * MAX_ITS
+            d_fetch = torch.zeros(hyp_off + 64 * K * MAX_ITS, dtype=torch.uint8, device=dev)
+            h_fetch = torch.zeros(hyp_off + 64 * K * MAX_ITS, dtype=torch.uint8).pin_memory()
+            d_cnt = torch.zeros(3 * K, dtype=torch.int32, device=dev)  # n_corr, n_its, status
+            d_corr = torch.zeros(K * n1 * 2, dtype=torch.int32, device=dev)
+            d_bits = torch.zeros(K * MAX_ITS * words, dtype=torch.int32, device=dev)
+            d_sel = torch.zeros(2 * n1 + n2max + 1, dtype=torch.int32, device=dev)  # prior12, valid1_round, valid2_round, status
+            fp, cp, sp = d_fetch.data_ptr(), d_cnt.data_ptr(), d_sel.data_ptr()
+
+            def enqueue_ransac():
+                ctx.enqueue_sim3_ransac_batch(recs[0], cur["T_last"], d_pos1.data_ptr(), d_valid1.data_ptr(), d_recs.data_ptr(), K, n1, max(n1, n2max), 0, MIN_INL,
+                                              MAX_ITS, tab.data_ptr(), cp, cp + 4 * K, d_corr.data_ptr(), 0, fp + hyp_off, d_bits.data_ptr(), fp + 4 * K, fp,
+                                              cp + 8 * K, stream=st.cuda_stream)
+
+            def enqueue_select(k, it):
+                ctx.enqueue_sim3_ransac_select(d_recs.data_ptr(), K, k, it, n1, d_valid1.data_ptr(), n1, max(n1, n2max), MAX_ITS, cp, cp + 4 * K, d_corr.data_ptr(),
+                                               d_bits.data_ptr(), sp, sp + 4 * n1, sp + 8 * n1, sp + 4 * (2 * n1 + n2max), stream=st.cuda_stream)
+
+            fetched = h_fetch.numpy()
+            picked = {}
+
+            def ransac_loop(check=False):
+                with torch.cuda.stream(st):
+                    enqueue_ransac()
+                    h_fetch.copy_(d_fetch, non_blocking=True)
+                    st.synchronize()  # the one download: the host walks the events (ORB_SLAM2::Sim3Solver::iterate)
+                    n_ev = fetched[:4 * K].view(np.int32)
+                    events = fetched[4 * K:hyp_off].view(np.int32).reshape(K, MAX_ITS)
+                    hyp = fetched[hyp_off:].view(api.SIM3_HYP_DTYPE).reshape(K, MAX_ITS)
+                    for k, r in calls:
+                        if k < K:
+                            it = int(events[k][min(r, n_ev[k] - 1)]) if n_ev[k] > 0 else 0
+                            h = hyp[k][it]
+                            enqueue_select(k, it)
+                            pa, pb = p1[:4] + [sp + 4 * n1], p2[k][:4] + [sp + 8 * n1]
+                            ctx.enqueue_search_by_sim3(recs[0], cands[k]["T_last"], pa, recs[1 + k], cands[k]["T_cur"], pb, h["s12"], h["R12"], h["t12"], TH, rp + 8,
+                                                       rp, rp + 4, stream=st.cuda_stream)
+                            picked[(k, r)] = (it, int(h["n_inliers"]))
+                        else:
+                            enqueue(k, r)
+                        m = n1 if k < K else nq
+                        h_res[:2 + m].copy_(d_res[:2 + m], non_blocking=True)
+                        st.synchronize()  # OptimizeSim3's count decides on the host whether the candidate is accepted
+                        if check:
+                            assert res[1] == 0, (k, r)
+                if check:
+                    cnt = d_cnt.cpu().numpy().reshape(3, K)
+                    assert (cnt[2] == 0).all() and (cnt[1] > 0).all(), cnt
+                    out["ransac"] = {"correspondences": cnt[0].tolist(), "iterations": cnt[1].tolist(), "events": n_ev.tolist(),
+                                     "rounds (candidate, round): (iteration, RANSAC inliers)": {"%d,%d" % kr: v for kr, v in sorted(picked.items())}}
+
+            ransac_loop(check=True)
+
+            def ransac_alone():
+                with torch.cuda.stream(st):
+                    enqueue_ransac()
+                    h_fetch.copy_(d_fetch, non_blocking=True)
+                    st.synchronize()
 
 
     def enqueue_all():
         for k, r in calls:
             enqueue(k, r)
 
-    if have:
-        ((a_rows, a_worst), (b_wall, b_worst)), (c_gpu, c_proj) = interleaved(REPEATS, REPS, st, [sync_loop, device_loop], [enqueue_all, lambda: enqueue(K, 0)])
+    if have and have_ransac:
+        (((a_rows, a_worst), (b_wall, b_worst), (b_up, b_up_worst), (d_wall, d_worst), (e_wall, e_worst)), (c_gpu, c_proj, f_gpu, g_gpu)) = interleaved(
+            REPEATS, REPS, st, [sync_loop, device_loop, device_loop_uploads, ransac_loop, ransac_alone],
+            [enqueue_all, lambda: enqueue(K, 0), enqueue_ransac, lambda: enqueue_select(0, 0)])
+    elif have:
+        ((a_rows, a_worst), (b_wall, b_worst), (b_up, b_up_worst)), (c_gpu, c_proj) = interleaved(REPEATS, REPS, st, [sync_loop, device_loop, device_loop_uploads],
+                                                                                                  [enqueue_all, lambda: enqueue(K, 0)])
     else:
         ((a_rows, a_worst),), _ = interleaved(REPEATS, REPS, None, [sync_loop])
     n_calls = K * ROUNDS
@@ -978,6 +1082,14 @@ def sim3_rows(out):
             "ms_per_repeat": b_wall, "slowest_loop_ms": b_worst}
         out["rows"]["(c) the %d enqueues alone, queued back to back, GPU time between two events" % (n_calls + 1)] = {"ms_per_repeat": c_gpu}
         out["rows"]["(c') of which the orbfe_enqueue_search_by_projection_sim3 call, queued back to back on its own"] = {"ms_per_repeat": c_proj}
+        out["rows"]["(b') as (b) with the three uploads of a round (d_valid1, d_valid2, d_prior12 from pinned memory) before each SearchBySim3, wall time"] = {
+            "ms_per_repeat": b_up, "slowest_loop_ms": b_up_worst}
+        if have_ransac:
+            out["rows"]["(d) orbfe_enqueue_sim3_ransac_batch + one download + synchronise, then %d x (orbfe_enqueue_sim3_ransac_select + orbfe_enqueue_search_by_sim3 + download "
+                        "+ synchronise) + the same for orbfe_enqueue_search_by_projection_sim3, wall time" % n_calls] = {"ms_per_repeat": d_wall, "slowest_loop_ms": d_worst}
+            out["rows"]["(e) of which orbfe_enqueue_sim3_ransac_batch + its download + synchronise, wall time"] = {"ms_per_repeat": e_wall, "slowest_loop_ms": e_worst}
+            out["rows"]["(f) orbfe_enqueue_sim3_ransac_batch alone, queued back to back, GPU time between two events"] = {"ms_per_repeat": f_gpu}
+            out["rows"]["(g) orbfe_enqueue_sim3_ransac_select alone, queued back to back, GPU time between two events"] = {"ms_per_repeat": g_gpu}
         out["median (a) / median (b)"] = round(float(np.median(a_rows) / np.median(b_wall)), 2)
         out["max (b) < min (a)"] = bool(max(b_wall) < min(a_rows))
     else:
