@@ -1024,6 +1024,108 @@ int orbfe_sim3_ransac(orbfe_context *ctx,
         const orbfe_keypoint *keys_un2, int n2, const float *T2w, const float *pos2, const int32_t *valid2,
         const int32_t *pairs, int n_pairs, const uint32_t *draws, int fix_scale, int min_inliers, int max_its, const int32_t *its_for_n,
         int *n_corr, int *n_its, int32_t *corr, int32_t *sets, orbfe_sim3_hypothesis *hyp, uint32_t *inlier_bits, int32_t *events, int *n_events);
+/* ---- PnPsolver (src/PnPsolver.cc) of Tracking::Relocalization (src/Tracking.cc:1440-1600) for ALL candidates in one call
+ * (orbfe_pnp_ransac.hip).  Every iteration of PnPsolver::iterate (:166-259) resets vAvailableIndices, draws four correspondences, runs
+ * EPnP on them and CheckInliers: a hypothesis depends on its four draws only.  Refine() (:261-306) reads mvbBestInliers, the inlier set
+ * of the first hypothesis that holds the strict running maximum among those with mnInliersi >= mRansacMinInliers, so it is a function
+ * of that record holder best(k) alone.  Hence every hypothesis of every candidate is evaluated at once, the refinements of the record
+ * holders in a second pass, and iterate becomes a host walk over the fetched events (ORB_SLAM2::PnPsolver of
+ * orbslam2_amd/host/PnPsolver.h).  The contract of the enqueue calls above holds: asynchronous on `stream` (NULL: the context's
+ * stream), nothing waits for the GPU, nothing is copied from host memory on the stream.  Five launches whatever n_cands is.
+ *
+ * The frame is image slot `slot` of the latest extraction call: mvKeysUn as orbfe_device_keys_un gives it, the keypoint count on the
+ * device, capacity = orbfe_keypoint_capacity().  Camera and mvLevelSigma2 are the context's.  The candidates are a DEVICE array of the
+ * 64-byte records below; f_match is row c of d_f_match as orbfe_enqueue_search_by_bow_batch left it.
+ * The constructor's filter (:68-111): keypoint i survives iff f_match[i] >= 0 && valid[f_match[i]]; survivors keep keypoint order.
+ * mvMaxError = sigma2[octave] * th2, a float product.  min_set must be 4 (mRansacMinSet of Tracking).
+ * SetRansacParameters (:122-158) per N: mRansacMinInliers becomes max((int)(N * epsilon), min_inliers, 4) (a float product, truncated);
+ * d_its_for_n[N], N in [0, capacity], is mRansacMaxIts afterwards (ORB_SLAM2::PnPRansacIterationTable; 0 stands for the N <
+ * mRansacMinInliers exit of :174-178).  The loop of :183 is `mnIterations < mRansacMaxIts || nCurrentIterations < nIterations`, so the
+ * first iterate(n_iterations) runs until a refinement succeeds or max(mRansacMaxIts, n_iterations) iterations have run: the device
+ * evaluates n_its = min(max_its, max(d_its_for_n[N], n_iterations)) hypotheses, none where the table holds 0.
+ * Draws: draws[max_its][4] raw glibc rand() values, applied with DUtils::Random::RandomInt and the swap-with-back-and-pop of :192-202;
+ * each candidate has a row of its own (ORB_SLAM2::DrawPnPSets), the global rand() stream is not reproduced.
+ * Arithmetic: DESIGN.md sections 4i2 and 4p.  FP64 wherever the reference's is; the OpenCV steps (cvMulTransposed, cvSVD, cvSolve and
+ * cvInvert with CV_SVD) are restated there.  Results are bit-reproducible and equal tests/pnp_solver_model.py and the host form bit
+ * for bit.  A NaN is stored as 0x7fc00000.
+ *
+ * Outputs, device rows per candidate c, every row written by every call, nothing written outside row c, a fault of record c changes
+ * no other row (W = ceil(capacity / 32)):
+ *   d_n_corr[c], d_n_its[c]               N; the hypotheses evaluated
+ *   d_corr[c][capacity][2]                (frame keypoint, keyframe slot) of the survivors; (-1, -1) from N on
+ *   d_sets[c][max_its][4]                 optional (may be NULL): the drawn correspondences; -1 from n_its on
+ *   d_hyp[c][max_its]                     the 64-byte records below; zero from n_its on (best_k -1 there)
+ *   d_inlier_bits[c][max_its][W]          mvbInliersi of iteration k over the correspondences, tail bits 0
+ *   d_refined[c][max_its]                 zero except where k is a record holder (hyp[k].best_k == k): Refine() on hypothesis k's inliers
+ *   d_refined_bits[c][max_its][W]         mvbRefinedInliers there, zero elsewhere
+ *   d_events[c][max_its], d_n_events[c]   every k at which iterate would return a refined pose (n_inliers >= mRansacMinInliers and
+ *                                         refined[best_k].ok), ascending; -1 from n_events on
+ *   d_exhausted[c]                        the k of mBestTcw's hypothesis (the last record holder), or -1
+ *   d_status[c]                           0, or ORBFE_ERR_INVALID: a record with n outside [0, max_kf_n] or a NULL pointer (N = 0, no
+ *                                         iteration); a match index outside [-1, n) or an octave outside [0, nlevels) (that keypoint is
+ *                                         dropped and never used as an address)
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL context or output other than d_sets; d_cands, d_its_for_n NULL under
+ * n_cands > 0; a slot out of range; n_cands < 0 or > 65535; max_kf_n < 0 or > 65535; min_set != 4; min_inliers < 1; max_its < 1 or
+ * > 65536; n_iterations < 0; epsilon or th2 not finite or negative.  n_cands == 0: ORBFE_OK, nothing queued.
+ * The correspondence table (6 floats per row) and the list of record holders live in the context's grow-only scratch and is staged in the LDS up to
+ * ORBFE_PNP_RANSAC_LDS_SLOTS correspondences: queue the calls of one context on one stream. */
+#define ORBFE_PNP_RANSAC_LDS_SLOTS 1024
+typedef struct orbfe_pnp_candidate {           /* 64 bytes; every pointer is a device pointer */
+    const int32_t *f_match;               /* [capacity]: the keyframe slot matched to frame keypoint i, or -1 */
+    const float   *pos;                   /* GetWorldPos per keyframe slot, 3 floats */
+    const int32_t *valid;                 /* pMP && !isBad() per keyframe slot */
+    const uint32_t *draws;                /* [max_its][4] raw rand() values */
+    int32_t n;                            /* keyframe slots, <= max_kf_n */
+    int32_t reserved[7];
+} orbfe_pnp_candidate;
+typedef struct orbfe_pnp_hypothesis {          /* 64 bytes: one iteration of iterate */
+    int32_t n_inliers;                    /* mnInliersi */
+    int32_t best_k;                       /* the iteration whose inliers mvbBestInliers holds after this one, or -1 */
+    float Rcw[9], tcw[3];                 /* (float) of mRi (row-major), mti */
+    int32_t pad[2];
+} orbfe_pnp_hypothesis;
+typedef struct orbfe_pnp_refined {             /* 64 bytes: Refine() on a record holder's inliers */
+    int32_t ok;                           /* mnRefinedInliers > mRansacMinInliers */
+    int32_t n_inliers;                    /* mnRefinedInliers */
+    float Tcw[12];                        /* (float) of [mRi | mti], 3 x 4 row-major, whether ok or not */
+    int32_t pad[2];
+} orbfe_pnp_refined;
+int orbfe_enqueue_pnp_ransac_batch(orbfe_context *ctx, int slot, const orbfe_pnp_candidate *d_cands /* DEVICE array */, int n_cands, int max_kf_n,
+        int min_set, int min_inliers, int max_its, int n_iterations, float epsilon, float th2, const int32_t *d_its_for_n /* [capacity + 1] */,
+        int32_t *d_n_corr /* [n_cands] */, int32_t *d_n_its /* [n_cands] */, int32_t *d_corr /* [n_cands][capacity][2] */,
+        int32_t *d_sets /* [n_cands][max_its][4] or NULL */, orbfe_pnp_hypothesis *d_hyp /* [n_cands][max_its] */,
+        uint32_t *d_inlier_bits /* [n_cands][max_its][W] */, orbfe_pnp_refined *d_refined /* [n_cands][max_its] */,
+        uint32_t *d_refined_bits /* [n_cands][max_its][W] */, int32_t *d_events /* [n_cands][max_its] */, int32_t *d_n_events /* [n_cands] */,
+        int32_t *d_exhausted /* [n_cands] */, int32_t *d_status /* [n_cands] */, void *stream);
+/* What Relocalization hands to the first PoseOptimization of candidate c (src/Tracking.cc:1515-1540), written on the stream from the
+ * rows the call above left in HBM, so that nothing is uploaded: with which == ORBFE_PNP_EVENT the return of iterate at iteration k (a
+ * host int chosen from the fetched events): the refined pose of best_k(k) and mvbRefinedInliers; with ORBFE_PNP_EXHAUSTED (k is
+ * ignored) the return on exhaustion: mBestTcw and mvbBestInliers of d_exhausted[c].
+ *   d_Tcw_row[16]             the 4 x 4 pose, last row 0 0 0 1
+ *   d_cur_point_row[capacity] the keyframe slot whose map point keypoint i holds: f_match[i] where the correspondence is an inlier,
+ *                             else -1, for the slot's keypoints; entries at or beyond the count are left untouched
+ *   d_has_point_row[capacity] the same as 0 / 1 bytes
+ * The BoW batch's d_Xw row stays as it is: orbfe_enqueue_pose_optimization reads it only where d_has_point is set.
+ * d_status[1]: 0, or ORBFE_ERR_INVALID when nothing can be selected: k outside the candidate's iterations, no record holder at k or its
+ * refinement failed (ok == 0), no best hypothesis on exhaustion, a d_corr entry out of range.  The pose is then the identity and no keypoint holds a point.  One launch.
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL pointer, a slot out of range, c outside [0, n_cands), k outside
+ * [0, max_its) under ORBFE_PNP_EVENT, which neither of the two. */
+#define ORBFE_PNP_EVENT     0
+#define ORBFE_PNP_EXHAUSTED 1
+int orbfe_enqueue_pnp_ransac_select(orbfe_context *ctx, int slot, int n_cands, int c, int which, int k, int max_its,
+        const int32_t *d_n_corr, const int32_t *d_n_its, const int32_t *d_corr, const orbfe_pnp_hypothesis *d_hyp, const uint32_t *d_inlier_bits,
+        const orbfe_pnp_refined *d_refined, const uint32_t *d_refined_bits, const int32_t *d_exhausted,
+        float *d_Tcw_row /* [16] */, int32_t *d_cur_point_row /* [capacity] */, uint8_t *d_has_point_row /* [capacity] */,
+        int32_t *d_status /* [1] */, void *stream);
+/* orbfe_enqueue_pnp_ransac_batch from host arrays for ONE candidate, synchronous (it uploads, calls the same kernels on the context's
+ * stream and downloads: the same bits).  The frame is keys_un[n_keys] with f_match[n_keys]; capacity = max(n_keys, 1) shapes the host
+ * outputs as one row of the call above; sets may be NULL.  Returns ORBFE_ERR_INVALID as the call above does, and also -- after the
+ * outputs are written -- when the device set the status. */
+int orbfe_pnp_ransac(orbfe_context *ctx, const orbfe_keypoint *keys_un, int n_keys, const int32_t *f_match,
+        const float *pos, const int32_t *valid, int n_kf, const uint32_t *draws,
+        int min_set, int min_inliers, int max_its, int n_iterations, float epsilon, float th2, const int32_t *its_for_n,
+        int *n_corr, int *n_its, int32_t *corr, int32_t *sets, orbfe_pnp_hypothesis *hyp, uint32_t *inlier_bits,
+        orbfe_pnp_refined *refined, uint32_t *refined_bits, int32_t *events, int *n_events, int *exhausted);
 /* ---- the writer of the map-point table (orbfe_map_point_device.hip): MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307)
  * and MapPoint::UpdateNormalAndDepth (:330-371) for chosen rows of the table that orbfe_enqueue_fuse and the Sim3 matchers read, from
  * observation lists over device-resident keyframes.  The contract of the enqueue matchers above holds: asynchronous on `stream` (NULL:

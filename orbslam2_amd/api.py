@@ -43,6 +43,7 @@ EXPORTS = [
     "orbfe_enqueue_keyframe_grid", "orbfe_enqueue_fuse", "orbfe_enqueue_fuse_sim3",
     "orbfe_enqueue_search_by_sim3", "orbfe_enqueue_search_by_projection_sim3", "orbfe_enqueue_optimize_sim3", "orbfe_optimize_sim3",
     "orbfe_enqueue_sim3_ransac_batch", "orbfe_enqueue_sim3_ransac_select", "orbfe_sim3_ransac",
+    "orbfe_enqueue_pnp_ransac_batch", "orbfe_enqueue_pnp_ransac_select", "orbfe_pnp_ransac",
     "orbfe_enqueue_search_by_bow_kf", "orbfe_enqueue_search_by_bow_kf_batch",
     "orbfe_enqueue_update_map_points",
     "orbfe_enqueue_triangulate_pairs",
@@ -125,6 +126,21 @@ assert C.sizeof(Sim3RansacCandidate) == 64
 SIM3_HYP_DTYPE = np.dtype([("n_inliers", "<i4"), ("s12", "<f4"), ("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("pad", "<i4", (2,))])
 assert SIM3_HYP_DTYPE.itemsize == 64
 SIM3_RANSAC_LDS_SLOTS = 1024  # ORBFE_SIM3_RANSAC_LDS_SLOTS
+
+
+class PnPCandidate(C.Structure):
+    """orbfe_pnp_candidate (include/orbfe.h): one candidate keyframe of enqueue_pnp_ransac_batch, device pointers; an ARRAY of these
+    records lives in HBM.  f_match: row c of enqueue_search_by_bow_batch's d_f_match; draws: [max_its][4] raw rand() values."""
+    _fields_ = [("f_match", C.c_void_p), ("pos", C.c_void_p), ("valid", C.c_void_p), ("draws", C.c_void_p), ("n", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+assert C.sizeof(PnPCandidate) == 64
+# orbfe_pnp_hypothesis / orbfe_pnp_refined: one iteration of PnPsolver::iterate; Refine() on a record holder's inliers
+PNP_HYP_DTYPE = np.dtype([("n_inliers", "<i4"), ("best_k", "<i4"), ("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("pad", "<i4", (2,))])
+PNP_REFINED_DTYPE = np.dtype([("ok", "<i4"), ("n_inliers", "<i4"), ("Tcw", "<f4", (12,)), ("pad", "<i4", (2,))])
+assert PNP_HYP_DTYPE.itemsize == 64 and PNP_REFINED_DTYPE.itemsize == 64
+PNP_RANSAC_LDS_SLOTS = 1024  # ORBFE_PNP_RANSAC_LDS_SLOTS
+PNP_EVENT, PNP_EXHAUSTED = 0, 1  # ORBFE_PNP_EVENT, ORBFE_PNP_EXHAUSTED
 
 
 class ObsKeyframe(C.Structure):
@@ -321,6 +337,12 @@ def load():
     L.orbfe_enqueue_sim3_ransac_batch.argtypes = [vp, C.POINTER(GridKeyframe), vp, vp, vp, vp] + [C.c_int] * 6 + [vp] * 11
     L.orbfe_enqueue_sim3_ransac_select.restype = C.c_int
     L.orbfe_enqueue_sim3_ransac_select.argtypes = [vp, vp] + [C.c_int] * 4 + [vp] + [C.c_int] * 3 + [vp] * 9
+    L.orbfe_enqueue_pnp_ransac_batch.restype = C.c_int
+    L.orbfe_enqueue_pnp_ransac_batch.argtypes = [vp, C.c_int, vp] + [C.c_int] * 6 + [C.c_float] * 2 + [vp] * 14
+    L.orbfe_enqueue_pnp_ransac_select.restype = C.c_int
+    L.orbfe_enqueue_pnp_ransac_select.argtypes = [vp] + [C.c_int] * 6 + [vp] * 13
+    L.orbfe_pnp_ransac.restype = C.c_int
+    L.orbfe_pnp_ransac.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int, vp] + [C.c_int] * 4 + [C.c_float] * 2 + [vp, ip, ip] + [vp] * 7 + [ip, ip]
     L.orbfe_sim3_ransac.restype = C.c_int
     L.orbfe_sim3_ransac.argtypes = [vp] + [vp, C.c_int, vp, vp, vp] * 2 + [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, ip, ip, vp, vp, vp, vp, vp, ip]
     L.orbfe_enqueue_search_by_sim3.restype = C.c_int
@@ -349,6 +371,26 @@ def load():
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def pnp_iteration_table(capacity, probability=0.99, min_inliers=10, max_its=300, epsilon=0.5):
+    """ORB_SLAM2::PnPRansacIterationTable (orbslam2_amd/host/PnPsolver.h): d_its_for_n of enqueue_pnp_ransac_batch, mRansacMaxIts after
+    PnPsolver::SetRansacParameters for every N in [0, capacity]; 0 where N < mRansacMinInliers (iterate's bNoMore exit).  The defaults
+    are Tracking::Relocalization's."""
+    import math
+    f32 = np.float32
+    out = np.zeros(capacity + 1, np.int32)
+    for N in range(capacity + 1):
+        n_min = max(int(f32(N) * f32(epsilon)), min_inliers, 4)
+        if N < n_min:
+            continue
+        eps = max(f32(epsilon), f32(n_min) / f32(N))
+        n = 1.0
+        if n_min != N:
+            den = math.log(1 - math.pow(float(eps), 3.0))
+            n = math.ceil(math.log(1 - probability) / den) if den != 0 else math.inf
+        out[N] = max(1, min(max_its if not n < max_its else int(n), max_its))
+    return out
 
 
 def sim3_iteration_table(max_pairs, probability=0.99, min_inliers=20, max_its=300):
@@ -1018,6 +1060,47 @@ class Context:
                                              _p(dr), int(fix_scale), min_inliers, max_its, _p(tab), C.byref(n_corr), C.byref(n_its), _p(out["corr"]),
                                              _p(out["sets"]), _p(out["hyp"]), _p(out["bits"]), _p(out["events"]), C.byref(n_ev)))
         out.update(n_corr=n_corr.value, n_its=n_its.value, n_events=n_ev.value, status=0)
+        return out
+
+    def enqueue_pnp_ransac_batch(self, slot, d_cands, n_cands, max_kf_n, min_inliers, max_its, n_iterations, epsilon, th2, d_its_for_n, d_n_corr, d_n_its,
+                                 d_corr, d_sets, d_hyp, d_inlier_bits, d_refined, d_refined_bits, d_events, d_n_events, d_exhausted, d_status, min_set=4, stream=0):
+        """PnPsolver for all candidates of Tracking::Relocalization in one call (include/orbfe.h), asynchronous on `stream`.  The frame is
+        image slot `slot`; d_cands: a device array of PnPCandidate; d_its_for_n: pnp_iteration_table(capacity) in HBM.  Every output is a
+        device address; d_sets may be 0."""
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_pnp_ransac_batch(
+            self.h, slot, v(d_cands or None), n_cands, max_kf_n, min_set, min_inliers, max_its, n_iterations, float(epsilon), float(th2),
+            *[v(x or None) for x in (d_its_for_n, d_n_corr, d_n_its, d_corr, d_sets, d_hyp, d_inlier_bits, d_refined, d_refined_bits, d_events, d_n_events,
+                                     d_exhausted, d_status, stream)]))
+
+    def enqueue_pnp_ransac_select(self, slot, n_cands, c, which, k, max_its, d_n_corr, d_n_its, d_corr, d_hyp, d_inlier_bits, d_refined, d_refined_bits,
+                                  d_exhausted, d_Tcw_row, d_cur_point_row, d_has_point_row, d_status, stream=0):
+        """What candidate c's first pose optimisation reads, written on `stream` from the rows enqueue_pnp_ransac_batch left in HBM:
+        which = PNP_EVENT: the refined pose and inliers of iteration k's record holder; PNP_EXHAUSTED: the best hypothesis's."""
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_pnp_ransac_select(
+            self.h, slot, n_cands, c, which, k, max_its,
+            *[v(x or None) for x in (d_n_corr, d_n_its, d_corr, d_hyp, d_inlier_bits, d_refined, d_refined_bits, d_exhausted, d_Tcw_row, d_cur_point_row,
+                                     d_has_point_row, d_status, stream)]))
+
+    def pnp_ransac(self, keys_un, f_match, pos, valid, draws, min_inliers, max_its, n_iterations, epsilon, th2, its_for_n, min_set=4):
+        """enqueue_pnp_ransac_batch from host arrays for one candidate, synchronous; capacity = max(len(keys_un), 1).  Returns a dict of
+        the candidate's rows.  Raises OrbfeError (ERR_INVALID) for what only the device can see."""
+        k = np.ascontiguousarray(keys_un, KP_DTYPE); fm = np.ascontiguousarray(f_match, np.int32)
+        p = np.ascontiguousarray(pos, np.float32); va = np.ascontiguousarray(valid, np.int32)
+        dr = np.ascontiguousarray(draws, np.uint32); tab = np.ascontiguousarray(its_for_n, np.int32)
+        assert len(fm) == len(k) and p.size == 3 * len(va) and dr.size >= 4 * max_its and tab.size >= len(k) + 1
+        cap = max(len(k), 1)
+        words = (cap + 31) // 32
+        out = dict(corr=np.zeros((cap, 2), np.int32), sets=np.zeros((max_its, 4), np.int32), hyp=np.zeros(max_its, PNP_HYP_DTYPE),
+                   bits=np.zeros((max_its, words), np.uint32), refined=np.zeros(max_its, PNP_REFINED_DTYPE),
+                   refined_bits=np.zeros((max_its, words), np.uint32), events=np.zeros(max_its, np.int32))
+        n_corr, n_its, n_ev, exh = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        ptr = lambda a: _p(a) if a.size else None
+        self._check(self.L.orbfe_pnp_ransac(self.h, ptr(k), len(k), ptr(fm), ptr(p), ptr(va), len(va), _p(dr), min_set, min_inliers, max_its, n_iterations,
+                                            float(epsilon), float(th2), _p(tab), C.byref(n_corr), C.byref(n_its), _p(out["corr"]), _p(out["sets"]), _p(out["hyp"]),
+                                            _p(out["bits"]), _p(out["refined"]), _p(out["refined_bits"]), _p(out["events"]), C.byref(n_ev), C.byref(exh)))
+        out.update(n_corr=n_corr.value, n_its=n_its.value, n_events=n_ev.value, exhausted=exh.value, status=0)
         return out
 
     def optimize_sim3(self, keys_un1, T1w, pos1, valid1, keys_un2, T2w, pos2, valid2, s12, R12, t12, th2, fix_scale, match12, prior12=None,

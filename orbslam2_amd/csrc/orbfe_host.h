@@ -96,6 +96,7 @@ struct orbfe_context {
     DevBuf recon_scratch, recon_sync; // the same of orbfe_enqueue_reconstruct_initial: its own, so that growing one never frees what the call before it still reads
     DevBuf sim3_opt_scratch, sim3_opt_sync; // orbfe_enqueue_optimize_sim3's correspondence table when it does not fit the LDS; the synchronous form's arrays
     DevBuf sim3_ransac_scratch, sim3_ransac_sync; // orbfe_enqueue_sim3_ransac_batch's correspondence tables; the synchronous form's arrays
+    DevBuf pnp_ransac_scratch, pnp_ransac_sync; // orbfe_enqueue_pnp_ransac_batch's correspondence tables; the synchronous form's arrays
     hipError_t chain_err = hipSuccess; // a launcher's refusal inside run_chain (enqueue_batch reports it)
     char err[512];
 };

@@ -191,4 +191,164 @@ inline float Stored(float s)
     return s;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the double rules
+// The CV_64F steps of the C interface that EPnP (host/PnPsolver.h) calls: cvMulTransposed, cvSVD, cvSolve and cvInvert with CV_SVD.
+// DESIGN.md sections 4i2 and 4p state them.  These functions carry ORBFE_CV_HD: orbfe_pnp_ransac.hip compiles this one definition for the
+// device as well, so the kernels and the host form cannot differ in an operation or its order.
+#ifndef ORBFE_CV_HD
+#ifdef __HIPCC__
+#define ORBFE_CV_HD __host__ __device__
+#else
+#define ORBFE_CV_HD
+#endif
+#endif
+
+// cvMulTransposed(M, MtM, 1) one row of M at a time: acc (n x n, row-major, zero before the first row) gains row^T row in its upper
+// triangle, so every element is a double sum over the rows in index order; MulTransposedMirror then copies the upper triangle down
+ORBFE_CV_HD inline void MulTransposedAdd(double *acc, const double *row, int n)
+{
+    for (int a = 0; a < n; a++)
+        for (int b = a; b < n; b++) acc[a * n + b] += row[a] * row[b];
+}
+
+ORBFE_CV_HD inline void MulTransposedMirror(double *acc, int n)
+{
+    for (int a = 1; a < n; a++)
+        for (int b = 0; b < a; b++) acc[a * n + b] = acc[b * n + a];
+}
+
+// Jacobi above instantiated in double (cv::SVD of a CV_64F matrix): At[i * as + k] = A[k][i] (i < n, k < m), Vt[i * vs + k] or NULL where
+// the caller reads no V.  eps = DBL_EPSILON * 10, at most 30 sweeps, the strict selection sort.  The rows of At are NOT normalised.
+ORBFE_CV_HD inline int JacobiD(double *At, int as, double *Vt, int vs, double *W, int n, int m)
+{
+    for (int i = 0; i < n; i++) {
+        double sd = 0;
+        for (int k = 0; k < m; k++) sd += At[i * as + k] * At[i * as + k];
+        W[i] = sd;
+        if (Vt)
+            for (int k = 0; k < n; k++) Vt[i * vs + k] = i == k ? 1.0 : 0.0;
+    }
+    const double eps = DBL_EPSILON * 10;
+    int sweeps = 0;
+    for (int iter = 0; iter < 30; iter++) {
+        bool changed = false;
+        for (int i = 0; i < n - 1; i++)
+            for (int j = i + 1; j < n; j++) {
+                double *Ai = At + i * as, *Aj = At + j * as;
+                double a = W[i], b = W[j], p = 0;
+                for (int k = 0; k < m; k++) p += Ai[k] * Aj[k];
+                if (std::fabs(p) <= eps * std::sqrt(a * b)) continue;
+                p *= 2;
+                const double beta = a - b, gamma = std::sqrt(p * p + beta * beta); // not hypot
+                double c, s;
+                if (beta < 0) {
+                    s = std::sqrt(((gamma - beta) * 0.5) / gamma);
+                    c = p / (gamma * s * 2);
+                } else {
+                    c = std::sqrt((gamma + beta) / (gamma * 2));
+                    s = p / (gamma * c * 2);
+                }
+                a = b = 0;
+                for (int k = 0; k < m; k++) {
+                    const double t0 = c * Ai[k] + s * Aj[k];
+                    const double t1 = -s * Ai[k] + c * Aj[k];
+                    Ai[k] = t0; Aj[k] = t1;
+                    a += t0 * t0; b += t1 * t1;
+                }
+                W[i] = a; W[j] = b;
+                changed = true;
+                if (Vt) {
+                    double *Vi = Vt + i * vs, *Vj = Vt + j * vs;
+                    for (int k = 0; k < n; k++) {
+                        const double t0 = c * Vi[k] + s * Vj[k];
+                        const double t1 = -s * Vi[k] + c * Vj[k];
+                        Vi[k] = t0; Vj[k] = t1;
+                    }
+                }
+            }
+        if (!changed) break;
+        sweeps++;
+    }
+    for (int i = 0; i < n; i++) {
+        double sd = 0;
+        for (int k = 0; k < m; k++) sd += At[i * as + k] * At[i * as + k];
+        W[i] = std::sqrt(sd);
+    }
+    for (int i = 0; i < n - 1; i++) {
+        int j = i;
+        for (int k = i + 1; k < n; k++)
+            if (W[j] < W[k]) j = k;
+        if (i != j) {
+            double t = W[i]; W[i] = W[j]; W[j] = t;
+            for (int k = 0; k < m; k++) { t = At[i * as + k]; At[i * as + k] = At[j * as + k]; At[j * as + k] = t; }
+            if (Vt)
+                for (int k = 0; k < n; k++) { t = Vt[i * vs + k]; Vt[i * vs + k] = Vt[j * vs + k]; Vt[j * vs + k] = t; }
+        }
+    }
+    return sweeps;
+}
+
+// the left singular vectors: u_i = At_i * (1 / W_i), the zero row where W_i <= DBL_MIN (OpenCV completes such a row with random
+// vectors; that is not restated)
+ORBFE_CV_HD inline void JacobiUnitRowsD(double *At, int as, const double *W, int n, int m)
+{
+    for (int i = 0; i < n; i++) {
+        const double s = W[i] > DBL_MIN ? 1 / W[i] : 0.0;
+        for (int k = 0; k < m; k++) At[i * as + k] = At[i * as + k] * s;
+    }
+}
+
+// cvSVD(A, W, Ut, Vt', MODIFY_A | U_T) of a square n x n double matrix A (row-major, n <= 12): w descending, the rows of Ut the left
+// singular vectors, the rows of Vt (or NULL) the right ones
+ORBFE_CV_HD inline int SvdSquareD(const double *A, int n, double *w, double *Ut, double *Vt)
+{
+    for (int i = 0; i < n; i++)
+        for (int k = 0; k < n; k++) Ut[i * n + k] = A[k * n + i];
+    const int sweeps = JacobiD(Ut, n, Vt, n, w, n, n);
+    JacobiUnitRowsD(Ut, n, w, n, n);
+    return sweeps;
+}
+
+// SVBkSb: x (n) = sum over i of ((u_i . b) / w_i) v_i in index order, the terms with w_i <= 2 * DBL_EPSILON * sum(w) left out.
+// Ut: n unit rows of m, Vt: n rows of n.  b == NULL stands for column `unit` of the identity (cvInvert): u_i . b is then Ut[i][unit].
+ORBFE_CV_HD inline void SvBkSbD(const double *Ut, int us, const double *Vt, int vs, const double *w, int n, int m, const double *b, int unit, double *x)
+{
+    double sum = 0;
+    for (int i = 0; i < n; i++) sum += w[i];
+    const double threshold = 2 * DBL_EPSILON * sum;
+    for (int j = 0; j < n; j++) x[j] = 0;
+    for (int i = 0; i < n; i++) {
+        if (w[i] <= threshold) continue;
+        double s = 0;
+        if (b)
+            for (int k = 0; k < m; k++) s += Ut[i * us + k] * b[k];
+        else
+            s = Ut[i * us + unit];
+        s = s / w[i];
+        for (int j = 0; j < n; j++) x[j] += s * Vt[i * vs + j];
+    }
+}
+
+// cvSolve(A, b, x, CV_SVD) of an m x n double A (row-major, m = 6, n <= 5): the Jacobi on A's columns, then the back-substitution
+ORBFE_CV_HD inline void SolveSvdD(const double *A, int m, int n, const double *b, double *x, double *w)
+{
+    double At[5 * 6], Vt[5 * 5];
+    for (int i = 0; i < n; i++)
+        for (int k = 0; k < m; k++) At[i * 6 + k] = A[k * n + i];
+    JacobiD(At, 6, Vt, 5, w, n, m);
+    JacobiUnitRowsD(At, 6, w, n, m);
+    SvBkSbD(At, 6, Vt, 5, w, n, m, b, 0, x);
+}
+
+// cvInvert(A, inv, CV_SVD) of a 3 x 3 double A: the pseudo-inverse by the same two steps, column by column
+ORBFE_CV_HD inline void InvertSvd3D(const double A[9], double inv[9], double w[3])
+{
+    double Ut[9], Vt[9], x[3];
+    SvdSquareD(A, 3, w, Ut, Vt);
+    for (int k = 0; k < 3; k++) {
+        SvBkSbD(Ut, 3, Vt, 3, w, 3, 3, nullptr, k, x);
+        for (int j = 0; j < 3; j++) inv[3 * j + k] = x[j];
+    }
+}
+
 } // namespace ORB_SLAM2

@@ -46,6 +46,12 @@ call's arrays gathered outside the timed window; (b) -- when the library has it 
 the count into pinned memory + stream synchronise), the validity patch queued on the stream, grids and table uploaded outside the
 timed window; (c) the 31 enqueues queued back to back as GPU time between two events.  (a) and (b) are checked against the oracle run
 with the same patches.  Five repeats of each, interleaved; every repeat is the mean of 10 loops, its slowest loop beside it.
+    python3 tools/bench_matchers.py --pnp
+runs only the Relocalization PnP rows (profiles/pnp_ransac.json): K = 3 and 10 candidates against one frame of 1800 keypoints, 150 BoW
+matches each: (a) the path around the host solver that the device call removes (download of the d_f_match rows, upload of the Tcw /
+cur_point / has_point rows; copies only); (b) orbfe_enqueue_pnp_ransac_batch + the download of its events + synchronise; (c) (b) + per
+candidate orbfe_enqueue_pnp_ransac_select and the first pose call; (d) the batch alone as GPU time between two events; (h) the host form
+on one CPU core, a stand-in for the reference's OpenCV solver, which is not built here.
     python3 tools/bench_matchers.py --sim3 [--lib path/to/another/liborbfe.so]
 runs only the ComputeSim3 rows (profiles/sim3_device.json): one current keyframe of 1500 keypoints (one map point each) against three
 candidate keyframes of about 1700 (the camera scene of tests/matcher_census.py seen from three poses), five SearchBySim3 calls per
@@ -1667,6 +1673,148 @@ def load_other_build(api, path):
         C.CDLL = real
 
 
+def pnp_rows(out):
+    """Rows of --pnp: Relocalization's PnP for K = 3 and 10 candidates against one frame of 1800 keypoints, 150 BoW matches each of which
+    60 are gross outliers, Tracking's parameters (0.99, 10, 300, 4, 0.5, 5.991) and iterate(5): 35 hypotheses per candidate."""
+    import ctypes as C
+    import torch
+    from orbslam2_amd import api
+    from tests import pnp_solver_model as PM
+    from tests import pnp_solver_scenes as PS
+    from tests.device_arrays import context, device_buffers
+    from tests.test_matchers_device import _inject
+    dev, REPEATS, REPS, MAX_ITS = "cuda:0", 5, 20, 300
+    ctx = context(api)
+    have = hasattr(ctx.L, "orbfe_enqueue_pnp_ransac_batch")
+    cap, st = ctx.capacity, torch.cuda.Stream()
+    frame = PS.make_frame(900, 1800)
+    scenes = [PS.make(frame, 901 + k, n_kf=1000, n_match=150, n_outliers=60, max_its=MAX_ITS) for k in range(10)]
+    n_keys = len(frame["keys"])
+    _inject(ctx, frame["keys"], np.zeros((n_keys, 32), np.uint8), np.full(n_keys, -1, np.float32))
+    bufs = device_buffers(ctx)
+    keep = []
+
+    def up(a):
+        t = upload(a)[0]
+        keep.append(t)
+        return t
+
+    table = PM.its_table(cap, PS.PROB, PS.MIN_INLIERS, PS.MAX_ITS, PS.EPSILON)
+    d_table = up(table)
+    out["setup"] = {"keypoints": n_keys, "capacity": cap, "matches per candidate": 150, "outliers per candidate": 60, "hypotheses per candidate": int(table[150])}
+    words = (cap + 31) // 32
+    for K in (3, 10):
+        ss = scenes[:K]
+        f_rows = np.full((K, cap), -1, np.int32)
+        for c, s in enumerate(ss):
+            f_rows[c, :n_keys] = s["f_match"]
+        d_f = up(f_rows)
+        h_f = torch.zeros((K, cap), dtype=torch.int32).pin_memory()
+        h_T, h_cur, h_has = torch.zeros((K, 16)).pin_memory(), torch.zeros((K, cap), dtype=torch.int32).pin_memory(), torch.zeros((K, cap), dtype=torch.uint8).pin_memory()
+        d_T, d_cur, d_has = torch.zeros((K, 16), device=dev), torch.zeros((K, cap), dtype=torch.int32, device=dev), torch.zeros((K, cap), dtype=torch.uint8, device=dev)
+
+        def around_the_host_solver():
+            """(a): what the host solver costs besides itself -- the d_f_match rows down, Tcw / cur_point / has_point rows up."""
+            with torch.cuda.stream(st):
+                h_f.copy_(d_f, non_blocking=True)
+                st.synchronize()                                        # PnPsolver::iterate per candidate runs on the host here
+                d_T.copy_(h_T, non_blocking=True); d_cur.copy_(h_cur, non_blocking=True); d_has.copy_(h_has, non_blocking=True)
+                st.synchronize()
+
+        loops, enqueues = [around_the_host_solver], []
+        if have:
+            recs = []
+            for c, s in enumerate(ss):
+                r = api.PnPCandidate()
+                r.f_match, r.pos, r.valid = d_f.data_ptr() + 4 * cap * c, up(s["pos"]).data_ptr(), up(s["valid"].astype(np.int32)).data_ptr()
+                r.draws, r.n = up(np.ascontiguousarray(s["draws"], np.uint32).view(np.int32)).data_ptr(), len(s["valid"])
+                recs.append(r)
+            d_recs = upload_records(recs)
+            # [n_its | n_events | exhausted | status | events] are fetched in one block; d_hyp / d_refined stay (select reads them)
+            d_small = torch.zeros(K * (4 + MAX_ITS), dtype=torch.int32, device=dev)
+            h_small = torch.zeros(K * (4 + MAX_ITS), dtype=torch.int32).pin_memory()
+            d_ncorr, d_corr = torch.zeros(K, dtype=torch.int32, device=dev), torch.zeros(K * cap * 2, dtype=torch.int32, device=dev)
+            d_hyp, d_ref = torch.zeros(K * MAX_ITS * 64, dtype=torch.uint8, device=dev), torch.zeros(K * MAX_ITS * 64, dtype=torch.uint8, device=dev)
+            d_bits, d_rbits = (torch.zeros(K * MAX_ITS * words, dtype=torch.int32, device=dev) for _ in range(2))
+            sp = d_small.data_ptr()
+            d_sel_status = torch.zeros(K, dtype=torch.int32, device=dev)
+            d_keys_rows = torch.zeros(K * cap * 28, dtype=torch.uint8, device=dev)
+            d_ur_rows = torch.full((K * cap,), -1.0, device=dev)
+            d_keys = ctx.device_keys_un(0, st.cuda_stream)
+            for c in range(K):
+                d_keys_rows[c * cap * 28:(c + 1) * cap * 28] = raw(d_keys, 28 * cap)
+            Xw = np.zeros((K, cap, 3), np.float32)
+            for c, s in enumerate(ss):
+                held = s["f_match"] >= 0
+                Xw[c, :n_keys][held] = s["pos"][s["f_match"][held]]
+            d_Xw, d_outl, d_ninl = up(Xw), torch.zeros(K * cap, dtype=torch.uint8, device=dev), torch.zeros(K, dtype=torch.int32, device=dev)
+            # the pose call takes offsets[k] .. offsets[k + 1]: one call per candidate row keeps rows cap apart
+            d_offs = [up(np.array([c * cap, c * cap + n_keys], np.int32)) for c in range(K)]
+            torch.cuda.synchronize()
+
+            def enqueue_batch():
+                ctx.enqueue_pnp_ransac_batch(0, d_recs.data_ptr(), K, 1000, PS.MIN_INLIERS, MAX_ITS, PS.ITERATE, PS.EPSILON, PS.TH2, d_table.data_ptr(), d_ncorr.data_ptr(),
+                                             sp, d_corr.data_ptr(), 0, d_hyp.data_ptr(), d_bits.data_ptr(), d_ref.data_ptr(), d_rbits.data_ptr(), sp + 16 * K,
+                                             sp + 4 * K, sp + 8 * K, sp + 12 * K, stream=st.cuda_stream)
+
+            def batch_and_events():
+                with torch.cuda.stream(st):
+                    enqueue_batch()
+                    h_small.copy_(d_small, non_blocking=True)
+                    st.synchronize()
+
+            def select_and_pose(check=False):
+                with torch.cuda.stream(st):
+                    enqueue_batch()
+                    h_small.copy_(d_small, non_blocking=True)
+                    st.synchronize()                                    # the host picks each candidate's event
+                    small = h_small.numpy()
+                    n_ev, exh, ev = small[K:2 * K], small[2 * K:3 * K], small[4 * K:].reshape(K, MAX_ITS)
+                    for c in range(K):
+                        which, k = (api.PNP_EVENT, int(ev[c, 0])) if n_ev[c] > 0 else (api.PNP_EXHAUSTED, 0)
+                        if n_ev[c] == 0 and exh[c] < 0:
+                            continue
+                        ctx.enqueue_pnp_ransac_select(0, K, c, which, k, MAX_ITS, d_ncorr.data_ptr(), sp, d_corr.data_ptr(), d_hyp.data_ptr(), d_bits.data_ptr(),
+                                                      d_ref.data_ptr(), d_rbits.data_ptr(), sp + 8 * K, d_T.data_ptr() + 64 * c, d_cur.data_ptr() + 4 * cap * c,
+                                                      d_has.data_ptr() + cap * c, d_sel_status.data_ptr() + 4 * c, stream=st.cuda_stream)
+                        ctx._check(ctx.L.orbfe_enqueue_pose_optimization(ctx.h, 1, d_offs[c].data_ptr(), d_keys_rows.data_ptr(), d_ur_rows.data_ptr(), d_has.data_ptr(),
+                                                                         d_Xw.data_ptr(), d_T.data_ptr() + 64 * c, d_outl.data_ptr(), d_ninl.data_ptr() + 4 * c, cap,
+                                                                         st.cuda_stream))
+                    st.synchronize()
+                if check:
+                    small = h_small.numpy()
+                    assert (small[3 * K:4 * K] == 0).all() and (d_sel_status.cpu().numpy() == 0).all()
+                    out.setdefault("ransac", {})["K = %d" % K] = {"iterations": small[:K].tolist(), "events": small[K:2 * K].tolist(),
+                                                                   "pose inliers after the first PoseOptimization": d_ninl.cpu().numpy().tolist()}
+
+            select_and_pose(check=True)
+            loops += [batch_and_events, select_and_pose]
+            enqueues = [enqueue_batch]
+        wall, gpu = interleaved(REPEATS, REPS, st, loops, enqueues)
+        out["rows"]["(a) K = %d: download of the d_f_match rows + synchronise, upload of the Tcw / cur_point / has_point rows + synchronise (the path around the host "
+                    "solver; only copies, the same on the parent commit), wall time" % K] = {"ms_per_repeat": wall[0][0], "slowest_loop_ms": wall[0][1]}
+        if have:
+            out["rows"]["(b) K = %d: orbfe_enqueue_pnp_ransac_batch + download of the events + synchronise, wall time" % K] = {"ms_per_repeat": wall[1][0], "slowest_loop_ms": wall[1][1]}
+            out["rows"]["(c) K = %d: (b) + per candidate orbfe_enqueue_pnp_ransac_select and the first orbfe_enqueue_pose_optimization + synchronise, wall time" % K] = {
+                "ms_per_repeat": wall[2][0], "slowest_loop_ms": wall[2][1]}
+            out["rows"]["(d) K = %d: orbfe_enqueue_pnp_ransac_batch alone, queued back to back, GPU time between two events" % K] = {"ms_per_repeat": gpu[0]}
+        # the host form on the CPU, a STAND-IN for the reference's OpenCV solver, which cannot be built here: no saving is claimed from it
+        fn = host_shim("pnp_solver", "pnp_ransac_host")
+        fn.restype = C.c_int
+        keys = np.ascontiguousarray(frame["keys"])
+        fm = np.ascontiguousarray(np.stack([s["f_match"] for s in ss]), np.int32)
+        pos = np.ascontiguousarray(np.stack([s["pos"] for s in ss]), np.float32)
+        val = np.ascontiguousarray(np.stack([s["valid"] for s in ss]), np.int32)
+        drw = np.ascontiguousarray(np.stack([s["draws"] for s in ss]), np.uint32)
+        tab, sg, cam = np.ascontiguousarray(table[:n_keys + 1]), np.ascontiguousarray(PS.SIGMA2), np.array(PS.CAM, np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        host = lambda: fn(p(keys), n_keys, K, p(fm), p(pos), p(val), 1000, p(drw), PS.MIN_INLIERS, MAX_ITS, PS.ITERATE, C.c_float(PS.EPSILON), C.c_float(PS.TH2), p(tab),
+                          p(sg), len(sg), p(cam))
+        out["rows"]["(h) K = %d: ORB_SLAM2::PnPRansacHost on one CPU core, every hypothesis of the rows (a stand-in for the reference's OpenCV solver, which is not "
+                    "built here and returns at its first success), wall time" % K] = {"ms_per_repeat": [round(timeit(host, 5), 4) for _ in range(REPEATS)]}
+    ctx.close()
+
+
 def main():
     from orbslam2_amd import api
     if "--lib" in sys.argv[1:]:  # another build of the library under this package (load() has not run yet)
@@ -1686,6 +1834,12 @@ def main():
     if "--fuse" in sys.argv[1:]:
         out = {"unit": "ms per keyframe (30 targets and the closing call)", "rows": {}}
         fuse_rows(out)
+        out["build_id"] = api.build_id()
+        print(json.dumps(out, indent=1))
+        return
+    if "--pnp" in sys.argv[1:]:
+        out = {"unit": "ms per Relocalization (K candidates)", "rows": {}}
+        pnp_rows(out)
         out["build_id"] = api.build_id()
         print(json.dumps(out, indent=1))
         return
