@@ -335,7 +335,8 @@ int orbfe_stage_times(orbfe_context *ctx, float *ms, int *calls, int reset);
 
 /* ---- stage taps for parity tests (results of the latest call) ---- */
 /* FAST+NMS candidates of (image, level) in the reference's emission order
- * (src/ORBextractor.cc:783-823); coordinates relative to (minBorderX, minBorderY). */
+ * (src/ORBextractor.cc:783-823); coordinates relative to (minBorderX, minBorderY).  `image` is a slot the
+ * latest extraction call filled: ORBFE_ERR_INVALID for the others (their cell arrays were never written). */
 int orbfe_fetch_candidates(orbfe_context *ctx, int image, int level, int32_t *xs, int32_t *ys,
                            int32_t *scores, int cap, int *n);
 

@@ -70,7 +70,8 @@ struct DeviceConfig {
     int sel_total;         // per image == keypoint capacity
     int blur_tiles_total;
     int proc_order;        // octree3_kernel also writes proc_xy / proc_meta and describe_kernel walks those (0: describe_kernel walks sel_xy; ORBFE_NO_PROC_ORDER=1, other quadtree kernels)
-    int fast_blur_t0;      // blur tiles [fast_blur_t0, blur_tiles_total) ride in the FAST launch (set per launch; blur_tiles_total: none)
+    int fast_blur_t0;      // blur tiles [fast_blur_t0, blur_tiles_total) ride in the FAST launch (set per launch; blur_tiles_total: none);
+                           // negative: the prefix [0, -fast_blur_t0) rides (fast_range_decode)
     uint32_t xcd_magic;    // ceil(2^32 / workgroups per XCD and round of units) of the block map of the launch this copy is passed to (FAST, describe,
                            // stereo match: set by the launcher, xcd_map_magic_host; 0: divide in the kernel)
     int max_nodes;         // quadtree node capacity (LDS)
@@ -98,6 +99,10 @@ struct DeviceConfig {
     // rectification (orbfe_set_rectification): cv::remap's fixed-point form of the float maps, one pair per side
     // (index = image slot & 1 when the right map is set, else 0): rm_xy = sx | sy << 16 (int16 each), rm_a = fy * 32 + fx
     int rm_on, rm_sw, rm_sh;
+    // cells [fast_cell_c0, cells_total) run in the FAST launch this copy is passed to; negative: the prefix [0, -fast_cell_c0)
+    // (set per launch like fast_blur_t0; 0 = every cell, which is what the planner leaves here).  It fills the four bytes that
+    // aligned rm_xy, so the layout every kernel reads is unchanged.
+    int fast_cell_c0;
     const uint32_t *rm_xy[2];
     const uint16_t *rm_a[2];
     // lens distortion of Frame::UndistortKeyPoints (orbfe_set_distortion): k1 k2 p1 p2 k3; n_dist == 0 or dist[0] == 0: none
@@ -110,6 +115,20 @@ struct DeviceConfig {
 static_assert(sizeof(LevelInfo) == 224 && sizeof(DeviceConfig) == 4168, "LevelInfo / DeviceConfig layout changed");
 static_assert(offsetof(DeviceConfig, pyr_bytes) == 440 && offsetof(DeviceConfig, rm_xy) == 512 && offsetof(DeviceConfig, lv) == 584,
               "DeviceConfig layout changed");
+static_assert(offsetof(DeviceConfig, fast_cell_c0) == 508, "DeviceConfig layout changed");
+
+// The range words of a FAST launch (DeviceConfig::fast_cell_c0 / fast_blur_t0): one word states a suffix [v, total) (v >= 0) or a
+// prefix [0, -v) (v < 0) of the cell table / the blur tile table, which is what a launch plan cut at a level boundary needs.
+struct FastRange { int c0, c1, t0, t1; }; // cells [c0, c1) and riding blur tiles [t0, t1) of one FAST launch
+ORBFE_HD void fast_range_decode(int v, int total, int &lo, int &hi) { lo = v < 0 ? 0 : v; hi = v < 0 ? -v : total; }
+// the word for [lo, hi) of [0, total); false when the range is neither a prefix, a suffix nor empty
+static inline bool fast_range_encode(int lo, int hi, int total, int *v)
+{
+    if (lo >= hi) { *v = total; return true; } // empty: the suffix that starts at the end
+    if (hi == total) { *v = lo; return true; }
+    if (lo == 0) { *v = -hi; return true; }
+    return false;
+}
 
 // Quadtree buckets (orbfe_octree3.hip).  A candidate's bucket = its root and quadrant path down to depth 5; the
 // path is separable (x decides the x bits, y the y bits), so it is X[x] | Y[y] from two host-built tables:

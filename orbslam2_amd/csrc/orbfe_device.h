@@ -99,7 +99,7 @@ void orbfe_launch_ingest(const DeviceConfig &cfg, const DeviceBuffers &buf, cons
                          int n_images, hipStream_t s);
 int orbfe_launch_pyramid(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_images, bool fuse_blur, hipStream_t s, int ride_from = ORBFE_MAX_LEVELS); // returns the number of levels (from 0) whose blur it launched too
 void orbfe_launch_blur(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_images, int first_level, hipStream_t s);
-void orbfe_launch_fast(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_images, bool buckets, hipStream_t s, int blur_first_level);
+hipError_t orbfe_launch_fast(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_images, bool buckets, hipStream_t s, const FastRange &r); // an empty range launches nothing; hipErrorInvalidValue: a range the launch cannot state
 // orbfe_octree_generic.hip: nodes_in_hbm selects octree_generic_kernel<true> (node tables in DeviceBuffers::otg_scratch); the error of a
 // refused LDS attribute is returned and nothing is launched
 hipError_t orbfe_launch_octree_generic(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_images, bool nodes_in_hbm, hipStream_t s);

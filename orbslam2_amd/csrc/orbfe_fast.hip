@@ -118,18 +118,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     // uses ~44 B of each line) are served by that XCD's L2 instead of being re-fetched from HBM by 8 XCDs.
     // A workgroup is four independent waves = four consecutive cells (no workgroup barriers: FAST_WAVE_SYNC): horizontally
     // adjacent cells share the 128-B lines of their tile rows, and on one CU those lines are fetched from L2 once.
-    const int bpi_cells = (cfg.cells_total + 3) >> 2;
-    const int bpi = bpi_cells + ((cfg.blur_tiles_total - cfg.fast_blur_t0 + 3) >> 2);
+    // This launch runs cells [c0, c1) and riding blur tiles [t0, t1) (every cell, or one side of a level boundary when the
+    // step's FAST work is cut in two: run_chain); all outputs stay at their absolute cell / tile indices.
+    int c0, c1, t0, t1;
+    fast_range_decode(cfg.fast_cell_c0, cfg.cells_total, c0, c1);
+    fast_range_decode(cfg.fast_blur_t0, cfg.blur_tiles_total, t0, t1);
+    const int bpi_cells = (c1 - c0 + 3) >> 2;
+    const int bpi = bpi_cells + ((t1 - t0 + 3) >> 2);
     int img, blk;
     if (!xcd_map_magic(bpi, n_images, cfg.xcd_magic, img, blk)) return;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (__builtin_expect(blk >= bpi_cells, 0)) { // the image's last workgroups: blur tiles riding in this launch
-        const int u = cfg.fast_blur_t0 + (blk - bpi_cells) * 4 + wave;
-        if (u < cfg.blur_tiles_total) blur_wave(cfg, buf, img, u);
+        const int u = t0 + (blk - bpi_cells) * 4 + wave;
+        if (u < t1) blur_wave(cfg, buf, img, u);
         return;
     }
-    const int cell = blk * 4 + wave;
-    if (cell >= cfg.cells_total) return;
+    const int cell = c0 + blk * 4 + wave;
+    if (cell >= c1) return;
     uint8_t *s_mem = s_mem_all + wave * lds_per_wave;
     // the cell's level, position and clipped tile size from the host-built table (one scalar load instead of the level search,
     // a division and the clipping of src/ORBextractor.cc:783-800 behind a chain of dependent scalar loads)
@@ -491,10 +496,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 
 static inline int max_cell_h(const DeviceConfig &cfg) { int m = 0; for (int l = 0; l < cfg.nlevels; l++) m = cfg.lv[l].h_cell > m ? cfg.lv[l].h_cell : m; return m; }
 
-void orbfe_launch_fast(const DeviceConfig &cfg_in, const DeviceBuffers &buf, int n_images, bool buckets, hipStream_t s, int blur_first_level)
+// Cells [r.c0, r.c1) and riding blur tiles [r.t0, r.t1) of every image: each range is the whole table, a prefix or a suffix of it
+// (fast_range_encode), or empty; two empty ranges launch nothing.
+hipError_t orbfe_launch_fast(const DeviceConfig &cfg_in, const DeviceBuffers &buf, int n_images, bool buckets, hipStream_t s, const FastRange &r)
 {
     DeviceConfig cfg = cfg_in;
-    cfg.fast_blur_t0 = blur_first_level < cfg.nlevels ? cfg.lv[blur_first_level].blur_tile_off : cfg.blur_tiles_total;
+    if (!fast_range_encode(r.c0, r.c1, cfg.cells_total, &cfg.fast_cell_c0) || !fast_range_encode(r.t0, r.t1, cfg.blur_tiles_total, &cfg.fast_blur_t0)) return hipErrorInvalidValue;
+    const int n_cells = r.c1 > r.c0 ? r.c1 - r.c0 : 0, n_tiles = r.t1 > r.t0 ? r.t1 - r.t0 : 0;
+    if (n_cells + n_tiles == 0) return hipSuccess;
     const int mw = max_cell_w(cfg), mh = max_cell_h(cfg);
     const int tile_pitch = orbfe_fast_tile_pitch(cfg);
     const int tile_rows = mh + 6;
@@ -506,7 +515,7 @@ void orbfe_launch_fast(const DeviceConfig &cfg_in, const DeviceBuffers &buf, int
     const int tile_region = tile_bytes > mw * mh ? tile_bytes : ((mw * mh + 15) & ~15);
     const int lds_per_wave = tile_region + sc_bytes + q_bytes + 512;
     const size_t lds = (size_t)4 * lds_per_wave;
-    const int bpi = (cfg.cells_total + 3) / 4 + (cfg.blur_tiles_total - cfg.fast_blur_t0 + 3) / 4;
+    const int bpi = (n_cells + 3) / 4 + (n_tiles + 3) / 4;
     cfg.xcd_magic = xcd_map_magic_host(bpi, n_images);
     dim3 grid(xcd_grid(bpi, n_images));
 #define FAST_LAUNCH(TP)                                                                                                                   \
@@ -521,4 +530,5 @@ void orbfe_launch_fast(const DeviceConfig &cfg_in, const DeviceBuffers &buf, int
     default: FAST_LAUNCH(0); break;
     }
 #undef FAST_LAUNCH
+    return hipSuccess;
 }

@@ -86,6 +86,10 @@ struct orbfe_context {
     int groups = 1;
     hipStream_t gstreams[ORBFE_MAX_GROUPS] = {};
     hipEvent_t ev_fork = nullptr, ev_join[ORBFE_MAX_GROUPS] = {};
+    // FAST's level 0 beside the pyramid's launches (run_chain; LaunchPlan::fast_split_min_images): created on first use
+    hipStream_t side_stream = nullptr;
+    hipEvent_t ev_side_fork = nullptr, ev_side_join = nullptr;
+    int fast_split_traced = -1; // the choice ORBFE_HOST_TRACE printed last (0 single, 1 split)
     int8_t pattern[1024];     // host copy of DeviceBuffers::pattern
     std::vector<void *> allocs;
     orbfe_match_state *match = nullptr;

@@ -33,8 +33,22 @@ PlanKnobs PlanKnobs::from_env()
     k.no_proc_order = first("ORBFE_NO_PROC_ORDER") == '1';
     { const char *v = getenv("ORBFE_OCTREE"); k.octree_generic = v && atoi(v) == 1; k.octree_generic_hbm = v && atoi(v) == 2; }
     { const char *v = getenv("ORBFE_BLUR_RIDE_FROM"); if (v && v[0] >= '0' && v[0] <= '9') k.blur_ride_from = atoi(v); }
+    k.fast_split = tri("ORBFE_FAST_SPLIT");
     k.host_trace = getenv("ORBFE_HOST_TRACE") != nullptr;
     return k;
+}
+
+int orbfe_fast_launches(const DeviceConfig &c, bool split, bool side_blur, int blur_first, FastRange out[2])
+{
+    auto tile_off = [&](int l) { return l < c.nlevels ? c.lv[l].blur_tile_off : c.blur_tiles_total; };
+    const int cut = c.nlevels >= 2 ? c.lv[1].cell_off : 0; // the planner orders cells and blur tiles by level: level 0's are the prefix
+    if (!split || cut <= 0 || cut >= c.cells_total) {
+        out[0] = FastRange{0, c.cells_total, tile_off(blur_first), c.blur_tiles_total};
+        return 1;
+    }
+    out[0] = FastRange{0, cut, 0, side_blur ? tile_off(1) : 0};
+    out[1] = FastRange{cut, c.cells_total, tile_off(side_blur && blur_first < 1 ? 1 : blur_first), c.blur_tiles_total};
+    return 2;
 }
 
 // lo / hi: the smallest and largest source index in the entries [i0, i1) of a resize table (both halves of each word)
@@ -692,5 +706,11 @@ int orbfe_build_plan(const orbfe_params &p, int max_images, const PlanKnobs &kno
     // level 0 read in place: ORBFE_NO_INPLACE=1 keeps the ingest copy
     P.inplace_ok = !knobs.no_inplace && c.nlevels >= 2 && c.lv[1].rs_direct && c.tail_first != 1 && p.width >= 16 && p.height >= 8;
     if (knobs.host_trace) fprintf(stderr, "orbfe: level 0 of packed grey input: %s\n", P.inplace_ok ? "read in place (no ingest launch)" : "copied by ingest16_kernel");
+    // FAST's level 0 on the side stream beside the pyramid's launches (run_chain): from 64 images, the batch of the headline step, where
+    // it is + 3.0 to + 3.2 % (profiles/fast_split.json).  Forced on, 8 pairs per step lose 5 - 6 % and one pair 12 - 13 %, and nothing
+    // between was measured, so the threshold is never below the batch from which every blur rides.  Several chains in flight lose too
+    // (three chains of 64 pairs - 8 %): such callers set ORBFE_FAST_SPLIT=0.  =1 / =0: at every batch size / never
+    P.fast_split_min_images = p.nlevels < 2 || knobs.fast_split == 0 ? INT_MAX : (knobs.fast_split == 1 ? 1 : std::max(64, P.blur_ride_min_images));
+    P.host_trace = knobs.host_trace;
     return ORBFE_OK;
 }

@@ -19,6 +19,7 @@ struct PlanKnobs {
     bool octree_generic = false;// ORBFE_OCTREE=1: the generic node-parallel quadtree kernel, node tables in LDS
     bool octree_generic_hbm = false; // ORBFE_OCTREE=2: the generic quadtree kernel, node tables in HBM scratch
     int blur_ride_from = -1;    // ORBFE_BLUR_RIDE_FROM=<n>: first level whose blur rides in FAST's launch, for every batch size
+    int fast_split = -1;        // ORBFE_FAST_SPLIT: 1 = FAST's level 0 on the side stream at every batch size, 0 = never, -1 = unset
     bool host_trace = false;    // ORBFE_HOST_TRACE set: print the plan's choices to stderr
     static PlanKnobs from_env();
 };
@@ -43,7 +44,17 @@ struct LaunchPlan {
     // by the LDS-free kernel and nothing stages level 0 through pyr_tail_kernel; ORBFE_NO_INPLACE=1 keeps the copy (A/B, tests).
     // Colour / rectified input always goes through ingest (it computes level 0).
     bool inplace_ok = false;
+    // FAST on level 0 needs nothing from the pyramid: for batches of at least fast_split_min_images images (one stream group, no
+    // stage profiling) it is launched on the context's side stream beside the pyramid's launches, and the caller's stream runs the
+    // other levels' cells after them (orbfe_fast_launches; run_chain).  INT_MAX: never (one level, or ORBFE_FAST_SPLIT=0).
+    int fast_split_min_images = 0x7fffffff;
+    bool host_trace = false;       // ORBFE_HOST_TRACE: the per-call choices (run_chain) are printed too
 };
+
+// The FAST launches of one call.  Not split: out[0] = every cell and the blur tiles of the levels >= blur_first (nlevels: none); returns 1.
+// Split: out[0] = level 0's cells, with level 0's blur tiles if side_blur, and out[1] = the other levels' cells with the tiles of the
+// levels >= blur_first that out[0] does not carry; returns 2.  A split that would leave either launch without cells is not made.
+int orbfe_fast_launches(const DeviceConfig &cfg, bool split, bool side_blur, int blur_first, FastRange out[2]);
 
 struct HostPlan : LaunchPlan {
     DeviceConfig cfg;
