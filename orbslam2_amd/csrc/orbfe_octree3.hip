@@ -51,13 +51,23 @@ __device__ __forceinline__ int ot3_off(int d) { return OT3_ROOTS * (((1 << (2 * 
 
 __device__ __forceinline__ int ot3_wave_incl_scan(int v, int lane)
 {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
+    // six DPP adds (row_shr 1, 2, 4, 8 inside the rows of 16 lanes, then row_bcast 15 and 31 across them; lanes without a source
+    // add 0) instead of six ds_bpermute round trips with their lane arithmetic: the scans sit on the critical path of every pass
+    (void)lane;
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
     return v;
 }
+
+// LDS written by a wave made visible to the same wave (no workgroup barrier): fast_cell_kernel's FAST_WAVE_SYNC
+#define OT3_WAVE_SYNC() do { __builtin_amdgcn_s_waitcnt(0xc07f); __builtin_amdgcn_wave_barrier(); } while (0)
+
+// how many of four keys lie below v (counting rank of the largest-first passes)
+__device__ __forceinline__ int ot3_below(const uint4 &q, uint32_t v) { return (int)(q.x < v) + (int)(q.y < v) + (int)(q.z < v) + (int)(q.w < v); }
 
 // exclusive block scan of 4 values per thread; totals in tot[4].  s_w: 4*OT3_WAVES ints.
 __device__ __forceinline__ void ot3_block_scan4(int v[4], int tot[4], int *s_w)
@@ -171,7 +181,7 @@ __global__ __launch_bounds__(OT3_THREADS) __attribute__((amdgpu_waves_per_eu(4))
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_raw[];
     __shared__ int s_w[4 * OT3_WAVES];
-    __shared__ int s_scal[8];
+    __shared__ int s_scal[NODES_IN_HBM ? 8 : 12]; // LDS form: [8] what wave 0's passes ended on, [9] which node array is current
     __shared__ __attribute__((aligned(16))) int s_bin[256]; // step 4a (processing order for describe_kernel): zeroed here, used at the end
     // longest first: the workgroups of level 0 (largest quota, most split passes) are dispatched before those of level 1, ...
     const int img = blockIdx.x, level = (int)blockIdx.y;
@@ -199,7 +209,10 @@ __global__ __launch_bounds__(OT3_THREADS) __attribute__((amdgpu_waves_per_eu(4))
     uint8_t *p = s_raw;
     int *s_chi = (int *)p; p += sizeof(int) * OT3_HI;
     uint16_t *s_c16 = (uint16_t *)p; p += sizeof(uint16_t) * (OT3_PYR - OT3_HI);
-    p = (uint8_t *)(((uintptr_t)p + 15) & ~(uintptr_t)15);
+    // the next 16-byte boundary of the (16-byte aligned) dynamic LDS as an OFFSET from s_raw: rounding the pointer up through an
+    // integer hid from the compiler that everything behind it is LDS, and every access to the best keys and the node tables --
+    // the bucket atomics included -- was a flat instruction (the slower path, and a wait on both counters)
+    p = s_raw + ((sizeof(int) * OT3_HI + sizeof(uint16_t) * (OT3_PYR - OT3_HI) + 15) & ~(size_t)15);
     unsigned *s_best = (unsigned *)p; // best key, all depths (steps 1 and 2 only)
     unsigned *g_best = buf.bk_best + ((size_t)img * cfg.nlevels + level) * OT3_PYR; // ... and where it lives afterwards
     auto cnt_at = [&](int e) -> int { return e < OT3_HI ? s_chi[e] : (int)s_c16[e - OT3_HI]; };
@@ -312,47 +325,188 @@ __global__ __launch_bounds__(OT3_THREADS) __attribute__((amdgpu_waves_per_eu(4))
     __syncthreads();
     OT3_PHASE();
     // ---- 2. pyramid ----
-    for (int d = db - 1; d >= 0; d--) {
+    // LDS form: the workgroup sums depths db-1 .. 3; depths 2, 1 and 0 (64, 16 and 4 entries) are wave 0's, without workgroup barriers
+    auto pyr_entry = [&](int o, int oc, int e) {
+        const int c = oc + 4 * e;
+        const int sum = cnt_at(c) + cnt_at(c + 1) + cnt_at(c + 2) + cnt_at(c + 3);
+        if (o + e < OT3_HI) s_chi[o + e] = sum; else s_c16[o + e - OT3_HI] = (uint16_t)sum;
+        const unsigned b0 = s_best[c], b1 = s_best[c + 1], b2 = s_best[c + 2], b3 = s_best[c + 3];
+        const unsigned m01 = b0 > b1 ? b0 : b1, m23 = b2 > b3 ? b2 : b3;
+        s_best[o + e] = m01 > m23 ? m01 : m23;
+    };
+    for (int d = db - 1; d >= (NODES_IN_HBM ? 0 : 3); d--) {
         const int n_e = OT3_ROOTS << (2 * d);
         const int o = ot3_off(d), oc = ot3_off(d + 1);
-        for (int e = tid; e < n_e; e += OT3_THREADS) {
-            const int c = oc + 4 * e;
-            const int sum = cnt_at(c) + cnt_at(c + 1) + cnt_at(c + 2) + cnt_at(c + 3);
-            if (o + e < OT3_HI) s_chi[o + e] = sum; else s_c16[o + e - OT3_HI] = (uint16_t)sum;
-            const unsigned b0 = s_best[c], b1 = s_best[c + 1], b2 = s_best[c + 2], b3 = s_best[c + 3];
-            const unsigned m01 = b0 > b1 ? b0 : b1, m23 = b2 > b3 ? b2 : b3;
-            s_best[o + e] = m01 > m23 ? m01 : m23;
-        }
+        for (int e = tid; e < n_e; e += OT3_THREADS) pyr_entry(o, oc, e);
         __syncthreads();
     }
     // the best keys leave the LDS: the final selection reads them back from this workgroup's slice (its own stores: same L2),
     // and their LDS region becomes the node tables
-    for (int i = tid; i < OT3_PYR / 4; i += OT3_THREADS) ((uint4 *)g_best)[i] = ((const uint4 *)s_best)[i];
+    if (NODES_IN_HBM) {
+        for (int i = tid; i < OT3_PYR / 4; i += OT3_THREADS) ((uint4 *)g_best)[i] = ((const uint4 *)s_best)[i];
+    } else {
+        constexpr int Q3 = OT3_ROOTS * 21 / 4; // 128-bit words of depths 0..2
+        static_assert(OT3_ROOTS * 16 <= 64 && (OT3_ROOTS * 21) % 4 == 0, "depth 2 fits one wave; depth 3 starts on a 128-bit word");
+        for (int i = Q3 + tid; i < OT3_PYR / 4; i += OT3_THREADS) ((uint4 *)g_best)[i] = ((const uint4 *)s_best)[i];
+        if (tid < 64) {
+#pragma unroll
+            for (int d = 2; d >= 0; d--) {
+                if (tid < (OT3_ROOTS << (2 * d))) pyr_entry(ot3_off(d), ot3_off(d + 1), tid);
+                OT3_WAVE_SYNC();
+            }
+            if (tid < Q3) ((uint4 *)g_best)[tid] = ((const uint4 *)s_best)[tid];
+        }
+    }
     // the region may be overwritten once every wave has READ its part (the stores carry the data in registers): wait for the LDS
     // reads only, not for the stores' round trip (__syncthreads waits for vmcnt(0): 4 us here); the stores have long landed when
     // the final selection reads the slice, many barriers later
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     OT3_PHASE();
     // ---- roots (src/ORBextractor.cc:537-581) ----
-    if (tid == 0) {
-        int n = 0, nc = 0;
-        for (int b = 0; b < n_ini; b++) {
-            const int c = s_chi[b];
-            nc += c;
-            if (c > 0) {
-                A.cnt[n] = c; A.path[n] = 0u; A.dr[n] = b << 4; // the root's box (:541-557) is implied by b: see ot3_path
-                n++;
+    Ot3Nodes cur = A, nxt = B;
+    int sorted_phase = 0;
+    bool passes_done = false;
+    // The node of a thread (registers) written to the next pass's array: its non-empty children n4..n1 at q0 (processed), or itself at q0
+    auto put_node = [&](bool split, int q0, int cnt, unsigned path, int dr, int c0, int c1, int c2, int c3) {
+        if (!split) {
+            nxt.cnt[q0] = cnt; nxt.path[q0] = path; nxt.dr[q0] = dr;
+            return;
+        }
+        const int dr1 = (dr & 15) < 15 ? dr + 1 : dr; // depth 15 = 1-px boxes: never multi-point
+        int q = q0;
+        if (c3 > 0) { nxt.cnt[q] = c3; nxt.path[q] = (path << 2) | 3u; nxt.dr[q] = dr1; q++; }
+        if (c2 > 0) { nxt.cnt[q] = c2; nxt.path[q] = (path << 2) | 2u; nxt.dr[q] = dr1; q++; }
+        if (c1 > 0) { nxt.cnt[q] = c1; nxt.path[q] = (path << 2) | 1u; nxt.dr[q] = dr1; q++; }
+        if (c0 > 0) { nxt.cnt[q] = c0; nxt.path[q] = path << 2; nxt.dr[q] = dr1; }
+    };
+    if (NODES_IN_HBM) {
+        if (tid == 0) {
+            int n = 0, nc = 0;
+            for (int b = 0; b < n_ini; b++) {
+                const int c = s_chi[b];
+                nc += c;
+                if (c > 0) {
+                    A.cnt[n] = c; A.path[n] = 0u; A.dr[n] = b << 4; // the root's box (:541-557) is implied by b: see ot3_path
+                    n++;
+                }
+            }
+            *s_n = n;
+            *s_done = 0;
+            *s_deep = 0;
+            buf.lvl_ncand[ib * cfg.nlevels + level] = nc;
+            s_scal[7] = nc;
+        }
+        __syncthreads();
+    } else {
+        // Wave 0 alone, lane = node, no workgroup barrier: the roots and every pass of at most 64 nodes -- on the benchmark's shapes
+        // the three full passes (3 -> 12 -> 48 -> 192 nodes; on the small levels the largest-first pass at 48 nodes too), which as
+        // workgroup passes were three barriers and their LDS round trips each for a handful of nodes.  The rules are those of the
+        // workgroup passes below; wave 0 leaves on: done, more than 64 nodes, a multi-point node at bucket depth (the deep path is
+        // the workgroup's), or a node count beyond the tables.  The other waves wait at the barrier that follows, and all of them
+        // read there how wave 0 ended, so that every wave executes the same barriers.
+        if (tid < 64) {
+            const int lane = tid;
+            const unsigned long long lt = (1ull << lane) - 1ull;
+            const int rc = lane < n_ini ? s_chi[lane] : 0;
+            const unsigned long long rm = __ballot(rc > 0);
+            const int nc0 = __builtin_amdgcn_readlane(rc, 0) + __builtin_amdgcn_readlane(rc, 1) + __builtin_amdgcn_readlane(rc, 2) + __builtin_amdgcn_readlane(rc, 3);
+            int n = __popcll(rm), code = 0, mode = 0, parity = 0; // code: 0 = the workgroup goes on, 1 = done, 2 = return
+            if (rc > 0) { // the root's box (:541-557) is implied by its index: see ot3_path
+                const int q = __popcll(rm & lt);
+                A.cnt[q] = rc; A.path[q] = 0u; A.dr[q] = lane << 4;
+            }
+            if (lane == 0) buf.lvl_ncand[ib * cfg.nlevels + level] = nc0;
+            if (nc0 == 0) {
+                if (lane == 0) *sel_cnt = 0;
+                code = 2;
+            }
+            OT3_WAVE_SYNC();
+            while (code == 0 && n <= 64) {
+                OT3_PHASE();
+                const bool has = lane < n;
+                const int cnt = has ? cur.cnt[lane] : 0, dr = has ? cur.dr[lane] : 0;
+                const unsigned path = has ? cur.path[lane] : 0u;
+                const bool multi = cnt > 1;
+                const int d = dr & 15, root = dr >> 4;
+                if (__ballot(multi && d >= db)) break; // deep
+                int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+                if (multi) {
+                    const int c = ot3_off(d + 1) + 4 * ((root << (2 * d)) + (int)path);
+                    c0 = cnt_at(c); c1 = cnt_at(c + 1); c2 = cnt_at(c + 2); c3 = cnt_at(c + 3);
+                }
+                const int k = (c0 > 0) + (c1 > 0) + (c2 > 0) + (c3 > 0);
+                const unsigned long long mm = __ballot(multi);
+                const int m = __popcll(mm);
+                int total_k, exk, nexpand = 0;
+                bool split;
+                if (!mode) {
+                    // full pass: list order = processing order; one scan for the children ahead and the multi-point children
+                    const int v = k | (((c0 > 1) + (c1 > 1) + (c2 > 1) + (c3 > 1)) << 16);
+                    const int inc = ot3_wave_incl_scan(v, lane);
+                    const int tot = __builtin_amdgcn_readlane(inc, 63);
+                    total_k = tot & 0xffff; nexpand = tot >> 16;
+                    exk = (inc & 0xffff) - k;
+                    split = multi;
+                } else {
+                    // largest first: rank = nodes with more points, or as many and earlier in the list (contract Q3), counted over
+                    // 32-bit keys read back as 128-bit broadcasts (two instructions per key: with the chip full a wave issues one
+                    // every ~16 cycles, so the instructions of this wave are the pass's length); single-point nodes rank last.  The
+                    // keys are built in the node array of the NEXT pass, as in the workgroup's passes.
+                    if (nc0 >= 65536) break; // 16-bit counts in the keys: otherwise the general path
+                    uint32_t *k32 = (uint32_t *)nxt.cnt;
+                    const int n16 = (n + 15) & ~15; // <= 2 * sort_cap words
+                    const uint32_t mine = ((multi ? 0xffffu - (unsigned)cnt : 0xffffu) << 16) | (unsigned)lane;
+                    if (lane < n16) k32[lane] = mine;
+                    OT3_WAVE_SYNC();
+                    int rank = 0;
+                    for (int j = 0; j < n16; j += 16) {
+                        const uint4 a = *(const uint4 *)(k32 + j), b = *(const uint4 *)(k32 + j + 4), c = *(const uint4 *)(k32 + j + 8), e = *(const uint4 *)(k32 + j + 12);
+                        rank += ot3_below(a, mine) + ot3_below(b, mine) + ot3_below(c, mine) + ot3_below(e, mine);
+                    }
+                    if (multi) s_kk[rank] = k; // non-empty children in processing order
+                    OT3_WAVE_SYNC();
+                    const int kr = lane < m ? s_kk[lane] : 0;
+                    const int inc = ot3_wave_incl_scan(kr, lane);
+                    // first rank with n + sum (k - 1) >= quota (src/ORBextractor.cc:724-725)
+                    const unsigned long long hit = __ballot(lane < m && n + inc - (lane + 1) >= quota);
+                    const int nproc = hit ? (int)__builtin_ctzll(hit) + 1 : m;
+                    total_k = nproc > 0 ? __builtin_amdgcn_readlane(inc, nproc - 1) : 0;
+                    if (lane < m) s_un[lane] = inc - kr;
+                    OT3_WAVE_SYNC();
+                    split = multi && rank < nproc;
+                    exk = split ? s_un[rank] : 0;
+                }
+                const unsigned long long um = __ballot(has && !split);
+                const int n_new = total_k + __popcll(um);
+                if (n_new > MAXN) {
+                    if (lane == 0) { *status = 2; *sel_cnt = 0; }
+                    code = 2;
+                    break;
+                }
+                // blocks of later-processed parents sit nearer the front; the unprocessed nodes follow in list order
+                if (has) put_node(split, split ? total_k - (exk + k) : total_k + __popcll(um & lt), cnt, path, dr, c0, c1, c2, c3);
+                // stop logic (src/ORBextractor.cc:661-731)
+                if (n_new >= quota || n_new == n) code = 1;
+                else if (!mode && n_new + 3 * nexpand > quota) mode = 1;
+                n = n_new;
+                parity ^= 1;
+                { Ot3Nodes t = cur; cur = nxt; nxt = t; }
+                OT3_WAVE_SYNC();
+            }
+            OT3_PHASE();
+            if (lane == 0) {
+                *s_n = n; *s_done = code == 1; *s_deep = 0; *s_mode = mode;
+                s_scal[7] = nc0; s_scal[8] = code; s_scal[9] = parity;
             }
         }
-        *s_n = n;
-        *s_done = 0;
-        *s_deep = 0;
-        buf.lvl_ncand[ib * cfg.nlevels + level] = nc;
-        s_scal[7] = nc;
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (s_scal[8] == 2) return;
+        passes_done = s_scal[8] == 1;
+        sorted_phase = *s_mode;
+        if (s_scal[9]) { cur = B; nxt = A; } else { cur = A; nxt = B; }
     }
-    __syncthreads();
     const int nc = s_scal[7];
-    if (nc == 0) {
+    if (NODES_IN_HBM && nc == 0) {
         if (tid == 0) *sel_cnt = 0;
         return;
     }
@@ -374,11 +528,100 @@ __global__ __launch_bounds__(OT3_THREADS) __attribute__((amdgpu_waves_per_eu(4))
     };
 
     // ---- 3. split passes ----
-    Ot3Nodes cur = A, nxt = B;
-    int sorted_phase = 0;
-    for (int iter = 0; iter < 100000; iter++) { // n grows every pass, so this ends at n >= quota at the latest
+    for (int iter = 0; !passes_done && iter < 100000; iter++) { // n grows every pass, so this ends at n >= quota at the latest
         const int n = *s_n;
         OT3_PHASE();
+        if (!NODES_IN_HBM && sorted_phase && n <= OT3_THREADS && nc < 65536) {
+            // Largest-first pass with thread i = node i (the express pass's form; on the benchmark's large levels the one pass from
+            // 192 nodes to the quota): child counts stay in registers, the rank is a count over the n 32-bit keys (single-point
+            // nodes rank behind every multi-point node), the children ahead come from one block scan in rank order, the first rank
+            // that reaches the quota is the first wave's first hit, the unprocessed nodes ahead are ballots, and every thread works
+            // the pass totals and the stop rule out for itself: six barriers, no single-thread sections.  A multi-point node at
+            // bucket depth sends the pass down the general path.
+            const int lane = tid & 63, wave = tid >> 6;
+            const bool has = tid < n;
+            const int cnt = has ? cur.cnt[tid] : 0, dr = has ? cur.dr[tid] : 0;
+            const unsigned path = has ? cur.path[tid] : 0u;
+            const bool multi = cnt > 1;
+            const int d = dr & 15, root = dr >> 4;
+            int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+            if (multi) {
+                if (d < db) {
+                    const int c = ot3_off(d + 1) + 4 * ((root << (2 * d)) + (int)path);
+                    c0 = cnt_at(c); c1 = cnt_at(c + 1); c2 = cnt_at(c + 2); c3 = cnt_at(c + 3);
+                } else {
+                    *s_deep = 1;
+                }
+            }
+            const int k = (c0 > 0) + (c1 > 0) + (c2 > 0) + (c3 > 0);
+            // keys in the node array of the NEXT pass, as on the general path; all distinct, threads beyond n pad to whole 16s
+            uint32_t *k32 = (uint32_t *)nxt.cnt;
+            const int n16 = (n + 15) & ~15; // <= OT3_THREADS <= 2 * sort_cap words
+            const uint32_t mine = ((multi ? 0xffffu - (unsigned)cnt : 0xffffu) << 16) | (unsigned)tid;
+            if (tid < n16) k32[tid] = mine;
+            __syncthreads();
+            if (!*s_deep) {
+                int rk = 0;
+                for (int j = 0; j < n16; j += 16) {
+                    const uint4 a = *(const uint4 *)(k32 + j), b = *(const uint4 *)(k32 + j + 4), c = *(const uint4 *)(k32 + j + 8), e = *(const uint4 *)(k32 + j + 12);
+                    rk += ot3_below(a, mine) + ot3_below(b, mine) + ot3_below(c, mine) + ot3_below(e, mine);
+                }
+                if (has) s_kk[rk] = k | (multi ? 16 : 0); // rank order (multi-point nodes first)
+                __syncthreads();
+                OT3_PHASE(); // ranked
+                const int pv = has ? s_kk[tid] : 0, kr = pv & 15, mr = pv >> 4;
+                const int v = kr | (mr << 16);
+                const int inc = ot3_wave_incl_scan(v, lane);
+                if (lane == 63) s_w[wave] = inc;
+                __syncthreads();
+                int base = 0, tot = 0;
+#pragma unroll
+                for (int w = 0; w < OT3_WAVES; w++) {
+                    const int x = s_w[w];
+                    if (w < wave) base += x;
+                    tot += x;
+                }
+                const int m = tot >> 16, inck = (base + inc) & 0xffff; // inck: children up to and including this rank
+                // first rank with n + sum (k - 1) >= quota (src/ORBextractor.cc:724-725); monotone in the rank
+                const unsigned long long hit = __ballot(mr && n + inck - (tid + 1) >= quota);
+                const int first = hit ? (int)__builtin_ctzll(hit) : 0;
+                const int inck_first = __shfl(inck, first, 64);
+                if (lane == 0) { s_w[4 + wave] = hit ? 64 * wave + first + 1 : -1; s_w[8 + wave] = inck_first; }
+                if (has) s_un[tid] = inck - kr;
+                __syncthreads();
+                int nproc = m, total_k = tot & 0xffff;
+#pragma unroll
+                for (int w = OT3_WAVES - 1; w >= 0; w--) {
+                    const int x = s_w[4 + w], y = s_w[8 + w];
+                    if (x >= 0) { nproc = x; total_k = y; }
+                }
+                OT3_PHASE(); // nproc
+                const bool split = multi && rk < nproc;
+                const int exk = split ? s_un[rk] : 0;
+                const unsigned long long um = __ballot(has && !split);
+                if (lane == 0) s_w[12 + wave] = __popcll(um);
+                __syncthreads();
+                int un_base = 0, n_un = 0;
+#pragma unroll
+                for (int w = 0; w < OT3_WAVES; w++) {
+                    const int x = s_w[12 + w];
+                    if (w < wave) un_base += x;
+                    n_un += x;
+                }
+                const int n_new = total_k + n_un;
+                if (n_new > MAXN) { // cannot happen for max_nodes >= max(quota+3, 4*n_ini); guard anyway
+                    if (tid == 0) { *status = 2; *sel_cnt = 0; }
+                    return;
+                }
+                if (has) put_node(split, split ? total_k - (exk + k) : total_k + un_base + __popcll(um & ((1ull << lane) - 1ull)), cnt, path, dr, c0, c1, c2, c3);
+                const bool done = n_new >= quota || n_new == n;
+                if (tid == 0) { *s_n = n_new; *s_done = done ? 1 : 0; }
+                __syncthreads();
+                { Ot3Nodes t = cur; cur = nxt; nxt = t; }
+                if (done) break;
+                continue;
+            }
+        }
         // child k of node i as new node q
         auto emit = [&](int q, int i, int k, int cnt) {
             nxt.cnt[q] = cnt;

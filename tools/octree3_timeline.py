@@ -34,5 +34,9 @@ for l in range(8):
     v = ph[l][ph[l] > 0]
     if len(v) > 1:
         d = np.diff(v)
-        # after the roots: one entry per full pass, then the largest-first pass as child counts + scan | ranking | k scan | nproc | flag scan | build
+        # LDS node tables: after the roots one entry per pass of wave 0 (at most 64 nodes, full or largest-first), then the hand-over
+        # to the workgroup (wave 0's last stamp to the first pass head behind the barrier; where wave 0 ended the passes: to the final
+        # selection), then per workgroup pass: a full pass as one entry, a thread-per-node largest-first pass as keys + ranking |
+        # k scan + nproc | flags + build, a general largest-first pass as child counts + scan | ranking | k scan | nproc | flag scan | build.
+        # Node tables in HBM: no wave-0 entries and no hand-over.
         print("level %d phases (us): partials %.1f  points %.1f  pyramid %.1f  roots, passes: %s  final %.1f" % (l, d[0], d[1], d[2], " ".join("%.1f" % x for x in d[3:-1]), d[-1]))
