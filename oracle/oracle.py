@@ -53,6 +53,9 @@ def lib(target: str = "liborb_oracle.so"):
     L.orc_fast_atan2.restype = C.c_float; L.orc_fast_atan2.argtypes = [C.c_float, C.c_float]
     L.orc_sincos_det.restype = None; L.orc_sincos_det.argtypes = [C.c_float, f32p, f32p]
     L.orc_border_reflect101.restype = C.c_int; L.orc_border_reflect101.argtypes = [C.c_int, C.c_int]
+    L.orc_fast_atan2_n.restype = None; L.orc_fast_atan2_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.orc_sincos_det_n.restype = None; L.orc_sincos_det_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.orc_border_reflect101_n.restype = None; L.orc_border_reflect101_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.orc_hamming256.restype = C.c_int; L.orc_hamming256.argtypes = [C.c_void_p, C.c_void_p]
     L.orc_bit_pattern.restype = i32p
     L.orc_gaussian_taps_q8.restype = None; L.orc_gaussian_taps_q8.argtypes = [C.c_int, C.c_double, i32p]
@@ -515,4 +518,32 @@ def remap_bilinear(src, mapx, mapy):
     L.orc_remap_bilinear.restype = None
     L.orc_remap_bilinear.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
     L.orc_remap_bilinear(_ptr(a), a.shape[1], a.shape[0], a.strides[0], _ptr(mx), _ptr(my), dw, dh, _ptr(out), out.strides[0])
+    return out
+
+
+# ------------------------------------------------------------------ array forms of the scalar helpers
+def fast_atan2_n(y, x) -> np.ndarray:
+    """orc_fast_atan2 on float32 arrays of one length (a C loop over the scalar routine)."""
+    y, x = np.ascontiguousarray(y, np.float32), np.ascontiguousarray(x, np.float32)
+    assert y.shape == x.shape and y.ndim == 1
+    out = np.empty(len(y), np.float32)
+    lib().orc_fast_atan2_n(y.ctypes.data, x.ctypes.data, out.ctypes.data, len(y))
+    return out
+
+
+def sincos_det_n(rad):
+    """orc_sincos_det on a float32 array: (sin, cos)."""
+    rad = np.ascontiguousarray(rad, np.float32)
+    assert rad.ndim == 1
+    s, c = np.empty(len(rad), np.float32), np.empty(len(rad), np.float32)
+    lib().orc_sincos_det_n(rad.ctypes.data, s.ctypes.data, c.ctypes.data, len(rad))
+    return s, c
+
+
+def border_reflect101_n(p, length) -> np.ndarray:
+    """orc_border_reflect101 on int32 arrays of one length."""
+    p, length = np.ascontiguousarray(p, np.int32), np.ascontiguousarray(length, np.int32)
+    assert p.shape == length.shape and p.ndim == 1
+    out = np.empty(len(p), np.int32)
+    lib().orc_border_reflect101_n(p.ctypes.data, length.ctypes.data, out.ctypes.data, len(p))
     return out

@@ -100,6 +100,23 @@ int orc_border_reflect101(int p, int len)
     return p;
 }
 
+/* Array forms of the three scalar helpers above: plain loops over the scalar routines, for tests that feed millions of inputs
+ * (tests/test_arith_blocks.py).  s and c of orc_sincos_det_n may not alias. */
+void orc_fast_atan2_n(const float *y, const float *x, float *out, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) out[i] = orc_fast_atan2(y[i], x[i]);
+}
+
+void orc_sincos_det_n(const float *rad, float *s, float *c, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) orc_sincos_det(rad[i], &s[i], &c[i]);
+}
+
+void orc_border_reflect101_n(const int32_t *p, const int32_t *len, int32_t *out, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) out[i] = orc_border_reflect101(p[i], len[i]);
+}
+
 /* ORBmatcher::DescriptorDistance, reference src/ORBmatcher.cc:1643-1659:
  * SWAR popcount over 8 x uint32 == plain 256-bit Hamming distance. */
 int orc_hamming256(const uint8_t *a, const uint8_t *b)

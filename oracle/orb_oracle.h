@@ -69,6 +69,10 @@ int orc_cv_round_d(double v);           /* cvRound(double) */
 float orc_fast_atan2(float y, float x); /* cv::fastAtan2, degrees */
 void orc_sincos_det(float rad, float *s, float *c); /* contract Q4 routine */
 int orc_border_reflect101(int p, int len);
+/* array forms: plain loops over the three scalar routines above */
+void orc_fast_atan2_n(const float *y, const float *x, float *out, size_t n);
+void orc_sincos_det_n(const float *rad, float *s, float *c, size_t n);
+void orc_border_reflect101_n(const int32_t *p, const int32_t *len, int32_t *out, size_t n);
 int orc_hamming256(const uint8_t *a, const uint8_t *b); /* ORBmatcher::DescriptorDistance */
 const int32_t *orc_bit_pattern(void);   /* 1024 ints */
 void orc_gaussian_taps_q8(int ksize, double sigma, int32_t *taps); /* fixed-point 8.8 taps */

@@ -1,6 +1,8 @@
 // mirror_main.cpp -- TEST-ONLY driver of orbslam2_amd/host/CvMat.h: reads the problem file that tests/test_cvmat_model.py writes, runs the
 // shared Jacobi on every matrix and the 3 x 3 steps on every pair of 3 x 3 inputs, and writes the outputs back.  Built twice with g++
-// through tests/host_forms.py, plain and with -fsanitize=address,undefined.
+// through tests/host_forms.py, plain and with -fsanitize=address,undefined.  The file holds the known-answer matrices and, after them, the
+// seeded ones (seeded_jacobi_inputs, seeded_small_inputs: duplicated and zero columns, a NaN and an Inf entry, singular and nearly singular
+// 3 x 3) that tests/test_arith_blocks.py gives the device forms: the counts in the file say how many, so the loops below run them all.
 //   file:  int32 nj;  nj x { int32 n, m;  f32 A[m][n] };  int32 n3;  n3 x { f32 a[9], b[9], plus[9];  f64 alpha };  int32 ns;  f32 v[ns]
 //   out:   nj x { f32 At[n][16], Vt[n][9];  f64 W[n];  int32 sweeps }
 //          n3 x { f32 u[9], w[3], vt[9] (Svd3 of a), inv[9] (Inv3 of a), ab[9] (a * b), abp[9] (alpha * a * b + plus), unit[3] (Unit of a's

@@ -43,3 +43,12 @@ def run(exe, *args):
 
 def bits(a):
     return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+
+
+def bits_one_nan(a):
+    """bits() with every NaN given one bit pattern: which payload and sign an arithmetic step leaves in a NaN is the processor's choice
+    (x86 and gfx950 differ) and no part of the contract, which stores one pattern."""
+    a = np.array(a)
+    if a.dtype.kind == "f":
+        a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])[np.isnan(a)] = {4: 0x7FC00000, 8: 0x7FF8000000000000}[a.dtype.itemsize]
+    return bits(a)

@@ -158,9 +158,56 @@ def small_inputs():
 STORED = np.array([0x3F800000, 0x7FC00000, 0xFFC12345, 0x7F800001, 0x7F800000, 0x80000000], np.uint32).view(F32)
 
 
+SEEDED = 2048                                   # added matrices per size
+
+
+def seeded_jacobi_inputs(n, m, count=SEEDED):
+    """float32[count][m][n], seeded, for the three-way agreement of model, host form and device forms (tests/test_arith_blocks.py): a quarter
+    with a duplicated column, an eighth with a zero column, an eighth one row short (n - 1 random rows, the rest zero), and in the general
+    half one matrix with a NaN entry and one with an Inf entry."""
+    rng = np.random.default_rng(1000 * n + m)
+    A = rng.normal(size=(count, m, n)).astype(F32)
+    q, e = count // 4, count // 8
+    src, dst = rng.integers(0, n, q), rng.integers(1, n, q)
+    dst = (src + dst) % n                                           # another column
+    A[np.arange(q), :, dst] = A[np.arange(q), :, src]
+    A[np.arange(q, q + e), :, rng.integers(0, n, e)] = 0
+    A[q + e:q + 2 * e, n - 1:, :] = 0
+    A[q + 2 * e, m // 2, n // 2] = np.nan
+    A[q + 2 * e + 1, 0, n - 1] = np.inf
+    return A
+
+
+def seeded_small_inputs(count=4096):
+    """(a, b, plus, alpha) arrays for the 3 x 3 steps: `count` seeded full-mantissa matrices, then 512 each of matrices whose determinant
+    expression is exactly 0 (small integers with row 2 = row 0 + row 1: every product and sum is exact), matrices with two equal
+    full-mantissa rows (each cofactor is x * y - y * x = 0) and nearly singular ones (the equal-row
+    matrices with one entry moved by one ulp; and full-mantissa matrices with row 2 = fl(row 0 + row 1), whose determinant of about 1e-8
+    is what cancellation leaves of terms of order 1, so that a last-bit change of one term moves the inverse), and the STORED patterns."""
+    rng = np.random.default_rng(7)
+    a = rng.normal(size=(count, 3, 3)).astype(F32)
+    ints = rng.integers(-1000, 1001, size=(512, 3, 3)).astype(F32)
+    ints[:, 2] = ints[:, 0] + ints[:, 1]
+    twin = rng.normal(size=(512, 3, 3)).astype(F32)
+    twin[:, 2] = twin[:, 1]
+    near = rng.normal(size=(512, 3, 3)).astype(F32)
+    near[:, 2] = near[:, 1]
+    k = rng.integers(0, 3, 512)
+    near[np.arange(512), 2, k] = np.nextafter(near[np.arange(512), 2, k], F32(np.inf))
+    cancel = rng.normal(size=(512, 3, 3)).astype(F32)
+    cancel[:, 2] = cancel[:, 0] + cancel[:, 1]
+    pat = np.stack([np.roll(np.resize(STORED, 9), r).reshape(3, 3) for r in range(len(STORED))])
+    a = np.concatenate([a, ints, twin, near, cancel, pat])
+    b, plus = rng.normal(size=a.shape).astype(F32), rng.normal(size=a.shape).astype(F32)
+    alpha = rng.normal(size=len(a))
+    return a, b, plus, alpha
+
+
 def write_problem_file(path):
     with open(path, "wb") as f:
         J, S3 = jacobi_inputs(), small_inputs()
+        J = J + [A for n, m in SIZES for A in seeded_jacobi_inputs(n, m)]
+        S3 = S3 + list(zip(*seeded_small_inputs()))
         f.write(struct.pack("<i", len(J)))
         for A in J:
             f.write(struct.pack("<ii", A.shape[1], A.shape[0]) + A.tobytes())
@@ -170,20 +217,43 @@ def write_problem_file(path):
         f.write(struct.pack("<i", len(STORED)) + STORED.tobytes())
 
 
+def _jacobi_expected(q0, As):
+    """One batched call of the model for matrices of one shape (the batch gives the bits of single calls, as tested above)."""
+    m, n = As[0].shape
+    At, Vt, W, info = M.jacobi(np.concatenate([M.transposed(A, n) for A in As]), n, m)
+    out = []
+    for b in range(len(As)):
+        out += [("jacobi %d (%d x %d) %s" % (q0 + b, m, n, k), v)
+                for k, v in (("At", At[b]), ("Vt", Vt[b]), ("W", W[b]), ("sweeps", info["sweeps"][b:b + 1].astype(np.int32)))]
+    return out
+
+
+def _small_expected(q0, a, b, plus, alpha):
+    u, w, vt, _ = M.svd3(a)
+    inv, ab, abp, det, norm = M.inv3(a), M.mat(a, b), M.mat(a, b, alpha=float(alpha[0]) if len(a) == 1 else np.asarray(alpha, F64), plus=plus), M.det3(a), M.norm(a[:, 0])
+    out = []
+    for i in range(len(a)):
+        steps = (("u", u[i]), ("w", w[i]), ("vt", vt[i]), ("inv", inv[i]), ("ab", ab[i]), ("abp", abp[i]), ("unit", M.unit(a[i, 0])),
+                 ("det", det[i:i + 1]), ("norm", norm[i:i + 1]))
+        out += [("3 x 3 %d %s" % (q0 + i, k), v) for k, v in steps]
+    return out
+
+
 @pytest.fixture(scope="module")
 def expected():
     """What the model gives for the problem file, in the order of the result file: a list of (name, array)."""
     out = []
     with np.errstate(all="ignore"):
         for q, A in enumerate(jacobi_inputs()):
-            m, n = A.shape
-            At, Vt, W, info = M.jacobi(M.transposed(A, n), n, m)
-            out += [("jacobi %d (%d x %d) %s" % (q, m, n, k), v) for k, v in (("At", At[0]), ("Vt", Vt[0]), ("W", W[0]), ("sweeps", info["sweeps"].astype(np.int32)))]
-        for q, (a, b, plus, alpha) in enumerate(small_inputs()):
-            u, w, vt, _ = M.svd3(a[None])
-            steps = (("u", u[0]), ("w", w[0]), ("vt", vt[0]), ("inv", M.inv3(a)), ("ab", M.mat(a, b)), ("abp", M.mat(a, b, alpha=alpha, plus=plus)),
-                     ("unit", M.unit(a[0])), ("det", np.array([M.det3(a)], F64)), ("norm", np.array([M.norm(a[0])], F64)))
-            out += [("3 x 3 %d %s" % (q, k), v) for k, v in steps]
+            out += _jacobi_expected(q, [A])
+        q = len(jacobi_inputs())
+        for n, m in SIZES:
+            out += _jacobi_expected(q, list(seeded_jacobi_inputs(n, m)))
+            q += SEEDED
+        S3 = small_inputs()
+        for q, (a, b, plus, alpha) in enumerate(S3):
+            out += _small_expected(q, a[None], b[None], plus[None], [alpha])
+        out += _small_expected(len(S3), *seeded_small_inputs())
         out.append(("stored", M.stored(STORED)))
     return out
 
@@ -210,6 +280,8 @@ def test_cpp_host_form_equals_the_model_bit_for_bit(tmp_path, build, expected):
         want = np.ascontiguousarray(want)
         got = raw[at:at + want.nbytes]
         at += want.nbytes
+        if name != "stored" and want.dtype.kind == "f" and np.isnan(want).any():     # the payload of a computed NaN is the processor's
+            got, want = H.bits_one_nan(np.frombuffer(got, want.dtype)).tobytes(), np.frombuffer(H.bits_one_nan(want).tobytes(), want.dtype)
         assert got == want.tobytes(), "%s differs: %s, model %s" % (name, np.frombuffer(got, want.dtype).tolist(), want.reshape(-1).tolist())
     assert at == len(raw)
 
