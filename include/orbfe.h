@@ -252,7 +252,9 @@ int orbfe_quadtree_kernel(const orbfe_context *ctx);
  * tables in LDS, 1 = bucket pyramid with node tables in HBM, 2 = generic with node tables in LDS, 3 = generic with node tables in
  * HBM scratch (any per-level quota up to the keypoint capacity); negative: an ORBFE_ERR_* code. */
 int orbfe_quadtree_plan(const orbfe_context *ctx);
-/* Copy the results of image slot `image` to host.  u_right/depth may be NULL.  The blocking fetch functions
+/* Copy the results of image slot `image` to host.  u_right/depth may be NULL.  A slot the latest extraction call did not fill is
+ * refused with ORBFE_ERR_INVALID (it still holds an earlier call's results), here and by every other fetch of a slot:
+ * orbfe_fetch_counts, _keys_un, _pyramid, _candidates and _batch_packed.  The blocking fetch functions
  * (orbfe_fetch_image / _counts / _keys_un / _pyramid / _candidates) first wait for the stream of the latest
  * orbfe_enqueue_* call, so no orbfe_synchronize is needed in between; orbfe_fetch_batch_async does not wait. */
 int orbfe_fetch_image(orbfe_context *ctx, int image, orbfe_keypoint *kps, uint8_t *desc,

@@ -128,6 +128,8 @@ struct orbfe_match_state {
     unsigned grid_epoch = 0;
     int grid_slot = -1, grid_n = -1;
     float grid_bounds[4] = {0, 0, 0, 0};
+    int grid_ndist = 0;                // ... from keypoints undistorted with these coefficients (orbfe_set_distortion may change them
+    float grid_dist[5] = {0, 0, 0, 0, 0}; // between two calls on one frame), as orbfe_match_device_state::un_dist
     ~orbfe_match_state() { if (h_in) (void)hipHostFree(h_in); if (h_out) (void)hipHostFree(h_out); }
 };
 
@@ -212,6 +214,10 @@ static int run_window_queries(orbfe_context *ctx, const orbfe_frame_view *fv, co
         const unsigned epoch = ctx->epoch;
         build_grid = !(st->grid_epoch == epoch && st->grid_slot == slot && st->grid_n == n && st->grid_bounds[0] == fv->min_x &&
                        st->grid_bounds[1] == fv->max_x && st->grid_bounds[2] == fv->min_y && st->grid_bounds[3] == fv->max_y);
+        // the coefficients are part of the key: with unchanged bounds nothing else tells keys_un and the grid of the setting
+        // before from current ones
+        build_grid = build_grid || st->grid_ndist != cfg->n_dist;
+        for (int k = 0; k < 5; k++) build_grid = build_grid || st->grid_dist[k] != cfg->dist[k];
         if (distorted) { // mvKeysUn: undistorted on the device once per frame (Frame::UndistortKeyPoints)
             if (st->keys_un.ensure(sizeof(KeyPointPOD) * (size_t)cfg->sel_total)) return orbfe_fail(ctx, ORBFE_ERR_HIP, "matcher scratch allocation failed");
             if (build_grid) orbfe_launch_undistort(*cfg, raw, st->keys_un.p, n, s);
@@ -223,6 +229,8 @@ static int run_window_queries(orbfe_context *ctx, const orbfe_frame_view *fv, co
         f.u_right = fv->u_right ? (const float *)(din + i_ur) : nullptr;
         st->grid_epoch = epoch; st->grid_slot = slot; st->grid_n = n;
         st->grid_bounds[0] = fv->min_x; st->grid_bounds[1] = fv->max_x; st->grid_bounds[2] = fv->min_y; st->grid_bounds[3] = fv->max_y;
+        st->grid_ndist = cfg->n_dist;
+        for (int k = 0; k < 5; k++) st->grid_dist[k] = cfg->dist[k];
     } else {
         f.keys = (const KeyPointPOD *)(din + i_keys); f.desc = din + i_desc;
         f.u_right = fv->u_right ? (const float *)(din + i_ur) : nullptr;

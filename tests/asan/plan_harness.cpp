@@ -133,6 +133,8 @@ int main(int argc, char **argv)
                    P->blur_ride_from, (int)P->inplace_ok);
             for (int l = 1; l < nl; l++) printf(" L%d %d,%d,%d", l, P->cfg.lv[l].rs_direct, P->cfg.lv[l].rs_rw, P->cfg.lv[l].pp_ok);
             printf("\n");
+            // the capacities the call-sequence scenes are chosen against (tests/test_call_sequences.py); not part of the digests either
+            printf("caps %s sel_total %d row_cap %d\n", name, P->cfg.sel_total, P->cfg.row_cap);
             check(name, p, *P);
             for (const char *t : {"cell_info", "cell_aux"}) {
                 if (dump.find(t) == std::string::npos) continue;
