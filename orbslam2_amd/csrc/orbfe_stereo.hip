@@ -22,6 +22,7 @@
 #define SM_G 16
 #define SM_GROUPS (256 / SM_G)       // groups of a workgroup
 #define SM_K SM_GROUPS               // consecutive left keypoints whose coarse matches one workgroup pools: one per group
+#define SM_MEDIAN_LDS_MAX (60u * 1024u) // stereo_median_kernel: largest dynamic LDS copy of a pair's SADs (15360 keypoint slots)
 __device__ __forceinline__ unsigned group_min_u32(unsigned v)
 {
 #pragma unroll
@@ -310,9 +311,12 @@ __global__ __launch_bounds__(256) void stereo_match_kernel(DeviceConfig cfg, Dev
 // Median of the accepted SADs, then cut at 1.5*1.4*median (src/Frame.cc:628-641; Q2: skip when empty).
 // The reference sorts (SAD, iL) pairs and reads element size/2; only its SAD matters, so the median is
 // found by a 2-level radix select (8 bits per level, LDS histograms; a SAD fits 16 bits) instead of a sort.
+// VALS_IN_LDS: the pair's SADs are staged in dynamic LDS ([sel_total] words, read from HBM once); false (keypoint capacities whose
+// SADs do not fit the launch's 60 KB: SM_MEDIAN_LDS_MAX): every pass reads them from HBM (at most 256 KB, resident in L2).
+template <bool VALS_IN_LDS>
 __global__ __launch_bounds__(256) void stereo_median_kernel(DeviceConfig cfg, DeviceBuffers buf)
 {
-    extern __shared__ int s_vals[]; // [sel_total] the pair's SADs, read from HBM once
+    extern __shared__ int s_vals_lds[];
     __shared__ int s_hist[256];
     __shared__ int s_sel[3]; // selected digit, rank inside the digit's bucket, count of valid entries
     const int pair = blockIdx.x;
@@ -322,7 +326,9 @@ __global__ __launch_bounds__(256) void stereo_median_kernel(DeviceConfig cfg, De
     float *u_right = buf.u_right + (size_t)imgL * cfg.sel_total;
     float *depth = buf.depth + (size_t)imgL * cfg.sel_total;
     const int *sad = buf.sad + (size_t)imgL * cfg.sel_total;
-    for (int i = tid; i < nL; i += 256) s_vals[i] = sad[i];
+    if (VALS_IN_LDS)
+        for (int i = tid; i < nL; i += 256) s_vals_lds[i] = sad[i];
+    const int *s_vals = VALS_IN_LDS ? s_vals_lds : sad;
     unsigned prefix = 0, mask = 0;
     for (int shift = 8; shift >= 0; shift -= 8) { // SAD <= 121 px * 510 = 61 710 < 2^16: two 8-bit digits
         s_hist[tid] = 0;
@@ -475,7 +481,10 @@ void orbfe_launch_stereo_match(const DeviceConfig &cfg_in, const DeviceBuffers &
 
 void orbfe_launch_stereo_median(const DeviceConfig &cfg, const DeviceBuffers &buf, int n_pairs, hipStream_t s)
 {
-    hipLaunchKernelGGL(stereo_median_kernel, dim3(n_pairs), dim3(256), (size_t)cfg.sel_total * sizeof(int), s, cfg, buf);
+    // the SADs of a pair in LDS while they fit what a launch gets without an attribute (64 KB with the kernel's static arrays)
+    const size_t lds = (size_t)cfg.sel_total * sizeof(int);
+    if (lds <= SM_MEDIAN_LDS_MAX) hipLaunchKernelGGL(stereo_median_kernel<true>, dim3(n_pairs), dim3(256), lds, s, cfg, buf);
+    else hipLaunchKernelGGL(stereo_median_kernel<false>, dim3(n_pairs), dim3(256), 0, s, cfg, buf);
 }
 
 void orbfe_launch_rgbd(const DeviceConfig &cfg, const DeviceBuffers &buf, const float *d_depth, size_t depth_pitch_floats,

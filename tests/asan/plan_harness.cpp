@@ -4,7 +4,8 @@
 // (knobs: "-" or NAME=VALUE,NAME=VALUE of the ORBFE_* environment knobs, set before PlanKnobs::from_env()).  Prints per case
 // the status and FNV-1a digests of the config, the per-level tables and every named device table (tests/test_plan_host.py
 // compares them with tests/golden/plan_digests.json), a "facts" line with the launch choices of an accepted plan (tail, pair and
-// ride thresholds, level 0 in place, per level rs_direct / rs_rw / pp_ok), and a VIOLATION line for every coverage invariant an
+// ride thresholds, level 0 in place, per level rs_direct / rs_rw / pp_ok), a "quadtree" line (the plan number orbfe_quadtree_plan()
+// returns, max_nodes, the sort buffer, per level n_ini and n_cells), and a VIOLATION line for every coverage invariant an
 // accepted plan breaks.
 // --dump NAME[,NAME]: also print those tables' words (cell_info, cell_aux).
 #include "../../orbslam2_amd/csrc/orbfe_plan.h"
@@ -135,6 +136,14 @@ int main(int argc, char **argv)
             printf("\n");
             // the capacities the call-sequence scenes are chosen against (tests/test_call_sequences.py); not part of the digests either
             printf("caps %s sel_total %d row_cap %d\n", name, P->cfg.sel_total, P->cfg.row_cap);
+            // the quadtree kernel and table placement (what orbfe_quadtree_plan() will return) and the geometry its predicates read
+            // (tests/plan_limits.py); not part of the digests
+            printf("quadtree %s plan %d max_nodes %d sort_cap %d n_ini", name, P->use_octree3 ? (P->ot3_nodes_in_hbm ? 1 : 0) : (P->otg_nodes_in_hbm ? 3 : 2),
+                   P->cfg.max_nodes, P->ot_sort_cap);
+            for (int l = 0; l < nl; l++) printf("%c%d", l ? ',' : ' ', P->cfg.lv[l].n_ini);
+            printf(" n_cells");
+            for (int l = 0; l < nl; l++) printf("%c%d", l ? ',' : ' ', P->cfg.lv[l].n_cells);
+            printf("\n");
             check(name, p, *P);
             for (const char *t : {"cell_info", "cell_aux"}) {
                 if (dump.find(t) == std::string::npos) continue;
