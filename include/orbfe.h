@@ -1179,6 +1179,83 @@ int orbfe_enqueue_update_map_points(orbfe_context *ctx,
         const float *d_pos, float *d_normal, float *d_max_distance, float *d_min_distance, uint8_t *d_pt_desc,
         int32_t *d_best /* [n_upd], may be NULL: list position of the chosen descriptor, -1 = descriptor row untouched */,
         int32_t *d_status /* [1] */, void *stream);
+/* ---- Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap) (src/Optimizer.cc:497-822, src/LocalMapping.cc) on device-resident
+ * keyframes and the map-point table (orbfe_lba.hip), the last step of LocalMapping::Run that ran on the host.  The graph walk of :499-548
+ * stays the caller's and arrives flattened: lLocalKeyFrames / lFixedCameras become d_role, lLocalMapPoints and their mObservations become
+ * the point list and observation CSR that orbfe_enqueue_update_map_points takes (lists in the order the reference iterates
+ * mObservations).  The contract of the enqueue calls above holds: asynchronous on `stream` (NULL: the context's), nothing waits for the
+ * GPU, nothing is copied from host memory on the stream; scratch is the context's grow-only scratch, so queue the calls of one context
+ * on one stream.  One launch of one workgroup drives everything; FP64 like g2o; every sum has an order fixed by the inputs, so the same
+ * inputs give the same bits on every run (DESIGN.md section 4r states the tolerances against a float64 model).
+ *
+ * Vertices: one SE3 per keyframe of role 1, 2 or 3, started at Converter::toSE3Quat(d_Tcw row); one point per list, started at its
+ * float position (row d_row[q] of d_pos, row q when d_row is NULL).  Edges: one per list entry whose keyframe has role != 0, mono when
+ * u_right < 0 and stereo otherwise, information mvInvLevelSigma2[octave], Huber deltas (float)sqrt(5.991) / (float)sqrt(7.815); errors and
+ * ANALYTIC Jacobians of g2o's EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ (the stereo edge's `const float invz` included).  Camera, bf
+ * and mvInvLevelSigma2 are the context's.  System and solver: BlockSolver<6,3> with the Schur complement over the points (3 x 3 blocks
+ * inverted as Eigen's inverse()), the reduced system solved by a dense LDLT WITHOUT pivoting that fails only on an exactly zero pivot
+ * (LinearSolverEigen's SimplicialLDLT; its fill-reducing ordering is not restated), Levenberg as in orbfe_enqueue_pose_optimization
+ * with lambda's start taken over pose and point blocks.  Rounds: optimize(5) with Huber; every edge with chi2 > 5.991 (mono) / 7.815
+ * (stereo) || !isDepthPositive() goes to level 1 and the kernel comes off all edges; optimize(10) over level 0; the same test makes
+ * vToErase.  chi2 is the error at the LAST EVALUATED estimate of the edge (a rejected final trial's; round 1's for a level-1 edge),
+ * isDepthPositive reads the current estimates; a vertex without a level-0 edge takes no part in round 2 and keeps its estimate.
+ * Not restated: pbStopFlag / mbAbortBA (the flag exists to cut short a host call of hundreds of milliseconds; this call cannot be
+ * interrupted) and the pMP->isBad() `continue`s (the call sees a snapshot).
+ * max_free_kfs is a host bound on the number of role-1 keyframes (the roles live on the device; the bound sizes the reduced system and
+ * selects the kernel variant: up to ORBFE_LBA_LDS_KEYFRAMES free keyframes the reduced system lives in the LDS, above that in HBM
+ * scratch).  More role-1 keyframes than the bound: d_status = ORBFE_ERR_CAPACITY and nothing else is written.  No count that fits int32
+ * is refused for its size.
+ * Outputs (device): d_Tcw rows of roles 1 and 2 = Converter::toCvMat of the estimate (a role-2 keyframe is held fixed but still goes
+ * through toSE3Quat -> toCvMat); rows of roles 0 and 3 keep their bits.  d_pos rows the points name = (float) of the estimate; other
+ * rows keep their bits.  d_obs_kfs (may be NULL): Ow = -Rwc * tcw of every rewritten keyframe from its new float row (KeyFrame::SetPose,
+ * one gemm with alpha -1); nothing else of the records is touched.  d_edge_code[n_obs]: bit 1 = level 1 in round 2, 2 = in vToErase,
+ * 4 = skipped (role 0), 8 = faulty.  d_edge_chi2[n_obs] (may be NULL): chi2 as above, 0 for an entry that made no edge.  d_erase /
+ * d_n_erase: the (keyframe, point q) pairs of vToErase in the reference's order, all mono edges in edge order and then all stereo
+ * edges.  d_info, d_status.  The caller then runs EraseMapPointMatch / EraseObservation from d_erase, SetPose from the fetched rows, and
+ * orbfe_enqueue_update_map_points(ORBFE_MP_NORMAL_DEPTH) over the same rows with the erased observations removed.
+ * d_status = ORBFE_ERR_INVALID for what only the device can see, each checked before it becomes an address: a faulty edge (obs_kf
+ * outside [0, n_kfs), obs_idx outside [0, n), a NULL array in the record it names, an octave outside [0, nlevels), a role above 3) gets
+ * code 8 and takes no part; a faulty point (row outside [0, n_rows): its entries get code 8; offsets negative, descending or beyond
+ * n_obs) loses all its edges; the rest of the problem runs as if those edges were absent.  The offsets are checked point by point: a
+ * descent after which the lists of two OTHER points overlap (0, 10, 5, 15) leaves the shared entries with two owners; no address leaves
+ * the arrays and the status is set, but the results of such a call are not defined.
+ * n_pts == 0 or no edge at all: status (0 unless something was faulty), d_info of zeros, d_n_erase = 0 and the codes; nothing else.
+ * ORBFE_ERR_INVALID from the call itself, nothing queued: a NULL context, d_info, d_status or d_n_erase; a negative count; n_rows <
+ * n_pts with a NULL d_row; under n_kfs > 0 a NULL d_kfs, d_role or d_Tcw; under n_pts > 0 a NULL d_obs_off or d_pos; under n_obs > 0 a
+ * NULL d_obs_kf, d_obs_idx, d_edge_code or d_erase. */
+#define ORBFE_BA_SKIP        0   /* pKFi->isBad(): its observations make no edge (:633) */
+#define ORBFE_BA_LOCAL       1   /* lLocalKeyFrames, free vertex */
+#define ORBFE_BA_LOCAL_HELD  2   /* lLocalKeyFrames with mnId == 0: setFixed(true) (:573), pose still rewritten (:806-812) */
+#define ORBFE_BA_FIXED       3   /* lFixedCameras */
+#define ORBFE_LBA_LDS_KEYFRAMES 21   /* (6 K + 1) * 6 K doubles <= the 128 KiB of LDS the kernel requests (static_assert in orbfe_lba.hip) */
+typedef struct orbfe_ba_keyframe {          /* 32 bytes, device pointers; the arrays of the keyframe's other records */
+    const orbfe_keypoint *keys_un;          /* x, y, octave */
+    const float *u_right;                   /* < 0: monocular edge */
+    int32_t n; int32_t reserved[3];
+} orbfe_ba_keyframe;
+typedef struct orbfe_lba_info {             /* 64 bytes */
+    int32_t n_mono, n_stereo, n_free, n_points;   /* edges built, free keyframes, point vertices */
+    int32_t iterations[2], trials[2];       /* per optimize(): iterations run, system solves tried */
+    double chi2_start, chi2_first, chi2_second, lambda_last;
+} orbfe_lba_info;
+int orbfe_enqueue_local_bundle_adjustment(orbfe_context *ctx,
+        const orbfe_ba_keyframe *d_kfs /* DEVICE array */, const uint8_t *d_role /* [n_kfs] */, int n_kfs, int max_free_kfs,
+        float *d_Tcw /* [n_kfs][16], row-major 4x4, in/out */,
+        int n_pts, const int32_t *d_row /* [n_pts] or NULL: point q is row q */, int n_rows,
+        const int32_t *d_obs_off /* [n_pts + 1] */, const int32_t *d_obs_kf /* [n_obs] */, const int32_t *d_obs_idx /* [n_obs] */, int n_obs,
+        float *d_pos /* [n_rows][3], the map-point table's position column, in/out */,
+        orbfe_obs_keyframe *d_obs_kfs /* [n_kfs] or NULL: Ow of every rewritten keyframe is patched */,
+        uint8_t *d_edge_code /* [n_obs] */, double *d_edge_chi2 /* [n_obs] or NULL */,
+        int32_t *d_erase /* [2 * n_obs]: (kf, q) */, int32_t *d_n_erase /* [1] */,
+        orbfe_lba_info *d_info, int32_t *d_status /* [1] */, void *stream);
+/* The same from host arrays, synchronous (it uploads, calls the enqueue form on the context's stream with max_free_kfs = the number of
+ * role-1 keyframes, and downloads: the same bits).  keys_un[k], u_right[k] and kf_n[k] are keyframe k's arrays; Ow (may be NULL) is
+ * [n_kfs][3] and only the rows of rewritten keyframes are written.  Returns ORBFE_ERR_INVALID as the call above does, and also -- after
+ * the outputs are written -- when the device set d_status. */
+int orbfe_local_bundle_adjustment(orbfe_context *ctx,
+        const orbfe_keypoint *const *keys_un, const float *const *u_right, const int32_t *kf_n, const uint8_t *role, int n_kfs, float *Tcw,
+        int n_pts, const int32_t *row, int n_rows, const int32_t *obs_off, const int32_t *obs_kf, const int32_t *obs_idx, int n_obs,
+        float *pos, float *Ow, uint8_t *edge_code, double *edge_chi2, int32_t *erase, int32_t *n_erase, orbfe_lba_info *info);
 /* ---- the triangulation stage of LocalMapping::CreateNewMapPoints (orbfe_triangulate_device.hip): src/LocalMapping.cc:286-450 for the
  * pairs that orbfe_enqueue_search_for_triangulation left in HBM.  The contract of the enqueue matchers above holds: asynchronous on
  * `stream` (NULL: the context's stream), nothing waits for the GPU, nothing is copied from host memory on the stream, nothing is

@@ -46,6 +46,7 @@ EXPORTS = [
     "orbfe_enqueue_pnp_ransac_batch", "orbfe_enqueue_pnp_ransac_select", "orbfe_pnp_ransac",
     "orbfe_enqueue_search_by_bow_kf", "orbfe_enqueue_search_by_bow_kf_batch",
     "orbfe_enqueue_update_map_points",
+    "orbfe_enqueue_local_bundle_adjustment", "orbfe_local_bundle_adjustment",
     "orbfe_enqueue_triangulate_pairs",
     "orbfe_enqueue_find_homography_fundamental", "orbfe_find_homography_fundamental",
     "orbfe_enqueue_reconstruct_initial", "orbfe_reconstruct_initial",
@@ -153,6 +154,29 @@ assert C.sizeof(ObsKeyframe) == 40
 OBS_KF_DTYPE = np.dtype([("desc", "<u8"), ("keys_un", "<u8"), ("Ow", "<f4", 3), ("n", "<i4"), ("bad", "<i4"), ("reserved", "<i4")])  # the same, as a numpy record
 assert OBS_KF_DTYPE.itemsize == 40
 MP_DESCRIPTOR, MP_NORMAL_DEPTH = 1, 2  # ORBFE_MP_*
+
+
+class BaKeyframe(C.Structure):
+    """orbfe_ba_keyframe (include/orbfe.h): one keyframe as enqueue_local_bundle_adjustment reads it, device pointers; an ARRAY of
+    these records lives in HBM."""
+    _fields_ = [("keys_un", C.c_void_p), ("u_right", C.c_void_p), ("n", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class LbaInfo(C.Structure):
+    """orbfe_lba_info (include/orbfe.h): edges built, active free keyframes and points, per optimize() the iterations run and the
+    system solves tried, the robust chi2 at entry and after either round, the last lambda."""
+    _fields_ = [("n_mono", C.c_int32), ("n_stereo", C.c_int32), ("n_free", C.c_int32), ("n_points", C.c_int32),
+                ("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2),
+                ("chi2_start", C.c_double), ("chi2_first", C.c_double), ("chi2_second", C.c_double), ("lambda_last", C.c_double)]
+
+
+assert C.sizeof(BaKeyframe) == 32 and C.sizeof(LbaInfo) == 64
+LBA_INFO_DTYPE = np.dtype([("n_mono", "<i4"), ("n_stereo", "<i4"), ("n_free", "<i4"), ("n_points", "<i4"), ("iterations", "<i4", 2), ("trials", "<i4", 2),
+                           ("chi2_start", "<f8"), ("chi2_first", "<f8"), ("chi2_second", "<f8"), ("lambda_last", "<f8")])  # the same, as a numpy record
+assert LBA_INFO_DTYPE.itemsize == 64
+BA_SKIP, BA_LOCAL, BA_LOCAL_HELD, BA_FIXED = 0, 1, 2, 3  # ORBFE_BA_*
+BA_CODE_LEVEL1, BA_CODE_ERASE, BA_CODE_SKIPPED, BA_CODE_FAULTY = 1, 2, 4, 8  # bits of d_edge_code
+LBA_LDS_KEYFRAMES = 21  # ORBFE_LBA_LDS_KEYFRAMES
 
 
 class NewpointKeyframe(C.Structure):
@@ -365,6 +389,10 @@ def load():
     L.orbfe_reconstruct_initial.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int] + [vp] * 7 + [C.c_float, C.c_float, C.c_int, C.c_int] + [vp] * 13
     L.orbfe_enqueue_update_map_points.restype = C.c_int
     L.orbfe_enqueue_update_map_points.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int] + [vp] * 8
+    L.orbfe_enqueue_local_bundle_adjustment.restype = C.c_int
+    L.orbfe_enqueue_local_bundle_adjustment.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 9
+    L.orbfe_local_bundle_adjustment.restype = C.c_int
+    L.orbfe_local_bundle_adjustment.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, ip, C.POINTER(LbaInfo)]
     _lib = L
     return L
 
@@ -1018,6 +1046,49 @@ class Context:
                                                        v(d_pos2 or None), v(d_valid2 or None), float(s12), _p(R), _p(t), float(th2), int(fix_scale),
                                                        None if params is None else C.byref(params), v(d_prior12 or None), v(d_match12 or None),
                                                        v(d_S12 or None), v(d_n_inliers or None), v(d_status or None), v(stream or None)))
+
+    def enqueue_local_bundle_adjustment(self, d_kfs, d_role, n_kfs, max_free_kfs, d_Tcw, n_pts, d_row, n_rows, d_obs_off, d_obs_kf, d_obs_idx, n_obs,
+                                        d_pos, d_obs_kfs, d_edge_code, d_edge_chi2, d_erase, d_n_erase, d_info, d_status, stream=0):
+        """Optimizer::LocalBundleAdjustment on device-resident keyframes and the map-point table (include/orbfe.h), asynchronous on
+        `stream`.  d_kfs: a device array of BaKeyframe; d_role: uint8[n_kfs] of BA_*; max_free_kfs: a host bound on the BA_LOCAL ones;
+        the point list, rows and CSR are enqueue_update_map_points'; d_Tcw float32[n_kfs][16] and d_pos are rewritten in place;
+        d_obs_kfs (0: none) is the ObsKeyframe directory whose Ow is patched; d_info receives one LBA_INFO_DTYPE record.  Every
+        argument is a device address.  Queue the calls of one context on one stream."""
+        v = C.c_void_p
+        self._check(self.L.orbfe_enqueue_local_bundle_adjustment(
+            self.h, v(d_kfs or None), v(d_role or None), n_kfs, max_free_kfs, v(d_Tcw or None), n_pts, v(d_row or None), n_rows, v(d_obs_off or None),
+            v(d_obs_kf or None), v(d_obs_idx or None), n_obs, *[v(x or None) for x in (d_pos, d_obs_kfs, d_edge_code, d_edge_chi2, d_erase, d_n_erase,
+                                                                                       d_info, d_status, stream)]))
+
+    def local_bundle_adjustment(self, keyframes, role, Tcw, row, n_rows, obs_off, obs_kf, obs_idx, pos):
+        """The same from host arrays, synchronous.  keyframes: a sequence of (keys_un KP_DTYPE[n], u_right float32[n]); row may be None.
+        Returns a dict: Tcw float32[n_kfs][16], pos float32[n_rows][3], Ow float32[n_kfs][3] (NaN rows for keyframes that were not
+        rewritten), edge_code uint8[n_obs], edge_chi2 float64[n_obs], erase int32[n_erase][2], info (an LBA_INFO_DTYPE record), status
+        (0, or ERR_INVALID / ERR_CAPACITY as the device set it: the outputs are written all the same, so this form does not raise then)."""
+        ks = [np.ascontiguousarray(k, KP_DTYPE) for k, _ in keyframes]
+        us = [np.ascontiguousarray(u, np.float32) for _, u in keyframes]
+        n_kfs = len(ks)
+        assert all(len(k) == len(u) for k, u in zip(ks, us))
+        kp = (C.c_void_p * max(n_kfs, 1))(*[k.ctypes.data if k.size else None for k in ks])
+        up = (C.c_void_p * max(n_kfs, 1))(*[u.ctypes.data if u.size else None for u in us])
+        kn = np.array([len(k) for k in ks], np.int32)
+        ro = np.ascontiguousarray(role, np.uint8)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(-1, 16).copy()
+        po = np.ascontiguousarray(pos, np.float32).reshape(-1, 3).copy()
+        off = np.ascontiguousarray(obs_off, np.int32); okf = np.ascontiguousarray(obs_kf, np.int32); oidx = np.ascontiguousarray(obs_idx, np.int32)
+        rw = None if row is None else np.ascontiguousarray(row, np.int32)
+        n_pts, n_obs = max(len(off) - 1, 0), len(okf)
+        assert len(ro) == n_kfs and len(T) == n_kfs and len(oidx) == n_obs and len(po) == n_rows and (rw is None or len(rw) == n_pts)
+        Ow = np.full((n_kfs, 3), np.nan, np.float32)
+        code = np.zeros(n_obs, np.uint8); chi = np.zeros(n_obs, np.float64); erase = np.zeros((n_obs, 2), np.int32)
+        n_erase = C.c_int(); info = LbaInfo()
+        ptr = lambda a: _p(a) if a is not None and a.size else None
+        rc = self.L.orbfe_local_bundle_adjustment(self.h, kp, up, ptr(kn), ptr(ro), n_kfs, ptr(T), n_pts, ptr(rw), n_rows, ptr(off), ptr(okf), ptr(oidx),
+                                                  n_obs, ptr(po), ptr(Ow), ptr(code), ptr(chi), ptr(erase), C.byref(n_erase), C.byref(info))
+        if rc not in (OK, ERR_INVALID, ERR_CAPACITY):   # the asserts above leave the call itself nothing to refuse: these two are the device's
+            self._check(rc)
+        return dict(Tcw=T, pos=po, Ow=Ow, edge_code=code, edge_chi2=chi, erase=erase[:n_erase.value].copy(),
+                    info=np.frombuffer(bytes(info), LBA_INFO_DTYPE)[0], status=rc)
 
     def enqueue_sim3_ransac_batch(self, kf1, T1w, d_pos1, d_valid1, d_cands, n_cands, max_pairs, max_kf_n, fix_scale, min_inliers, max_its, d_its_for_n,
                                   d_n_corr, d_n_its, d_corr, d_sets, d_hyp, d_inlier_bits, d_events, d_n_events, d_status, stream=0):

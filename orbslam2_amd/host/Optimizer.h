@@ -13,11 +13,22 @@
 //           (s, R, t of the Sim3Solver: floats); th2, bFixScale
 //   writes  vnMatches12 (outliers become -1), S12 = qx qy qz qw tx ty tz s of the optimised g2o::Sim3 (the input one when the
 //           optimisation gives up), and returns nIn
+//
+// Optimizer::LocalBundleAdjustment (include/Optimizer.h, src/Optimizer.cc:497-822) likewise, after its graph walk (:499-548), which stays
+// the caller's and arrives flattened:
+//   reads   per keyframe of lLocalKeyFrames / lFixedCameras (and of any other keyframe an observation names) mvKeysUn, mvuRight, GetPose()
+//           and its role: ORBFE_BA_LOCAL, ORBFE_BA_LOCAL_HELD (mnId == 0), ORBFE_BA_FIXED, ORBFE_BA_SKIP (isBad()); per point of
+//           lLocalMapPoints GetWorldPos() and GetObservations() as (keyframe index, keypoint index) in mObservations' order
+//   writes  the poses handed to SetPose (roles 1 and 2) with their camera centres, the positions handed to SetWorldPos, vToErase as
+//           (keyframe index, point index) pairs in the reference's order; returns the call's orbfe_lba_info
+// pbStopFlag is not restated: the call cannot be interrupted (include/orbfe.h).  UpdateNormalAndDepth stays a call of its own
+// (MapPointUpdate.h) because erasing an observation can change mpRefKF or kill the point.
 #pragma once
 
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/orbfe.h"
@@ -62,6 +73,51 @@ public:
                                            vnPrior12.empty() ? nullptr : vnPrior12.data(), vnMatches12.data(), S12, &nIn);
         if (rc != ORBFE_OK) throw std::runtime_error(std::string("orbfe: ") + orbfe_last_error(ctx));
         return nIn;
+    }
+
+    struct BAKeyFrame { // what the call reads of one keyframe
+        const std::vector<orbfe_keypoint> *vKeysUn;
+        const std::vector<float> *vuRight;
+        uint8_t role; // ORBFE_BA_*
+    };
+    struct BAResult {
+        std::vector<std::pair<int32_t, int32_t>> vToErase; // (keyframe index, point index)
+        std::vector<uint8_t> vEdgeCode;                    // per observation: 1 level 1 in round 2, 2 erased, 4 skipped
+        std::vector<double> vEdgeChi2;
+        orbfe_lba_info info;
+    };
+
+    // vTcw (16 floats per keyframe, row major) and vWorldPos (3 per point) are updated in place; vOw (3 per keyframe, resized when it
+    // is shorter) receives the camera centre of every rewritten keyframe (roles 1 and 2); the rows of the other keyframes keep what the
+    // caller put there (zeros where the resize added them).  vObsOff (one more entry than points), vObsKF, vObsIdx: the points' observations.
+    static BAResult LocalBundleAdjustment(orbfe_context *ctx, const std::vector<BAKeyFrame> &vKFs, std::vector<float> &vTcw, std::vector<float> &vOw,
+                                          std::vector<float> &vWorldPos, const std::vector<int32_t> &vObsOff, const std::vector<int32_t> &vObsKF,
+                                          const std::vector<int32_t> &vObsIdx)
+    {
+        const size_t K = vKFs.size(), E = vObsKF.size();
+        if (vObsOff.empty() || vTcw.size() != 16 * K || vWorldPos.size() != 3 * (vObsOff.size() - 1) || vObsIdx.size() != E)
+            throw std::invalid_argument("Optimizer::LocalBundleAdjustment: arrays differ in length");
+        const size_t N = vObsOff.size() - 1;
+        std::vector<const orbfe_keypoint *> keys(K);
+        std::vector<const float *> ur(K);
+        std::vector<int32_t> n(K);
+        std::vector<uint8_t> role(K);
+        for (size_t k = 0; k < K; k++) {
+            if (vKFs[k].vKeysUn->size() != vKFs[k].vuRight->size()) throw std::invalid_argument("Optimizer::LocalBundleAdjustment: mvKeysUn and mvuRight differ in length");
+            keys[k] = vKFs[k].vKeysUn->data(); ur[k] = vKFs[k].vuRight->data(); n[k] = (int32_t)vKFs[k].vKeysUn->size(); role[k] = vKFs[k].role;
+        }
+        vOw.resize(3 * K);
+        BAResult r;
+        r.vEdgeCode.assign(E, 0);
+        r.vEdgeChi2.assign(E, 0.0);
+        std::vector<int32_t> erase(2 * E + 2);
+        int32_t n_erase = 0;
+        const int rc = orbfe_local_bundle_adjustment(ctx, keys.data(), ur.data(), n.data(), role.data(), (int)K, vTcw.data(), (int)N, nullptr, (int)N,
+                                                     vObsOff.data(), vObsKF.data(), vObsIdx.data(), (int)E, vWorldPos.data(), vOw.data(),
+                                                     r.vEdgeCode.data(), r.vEdgeChi2.data(), erase.data(), &n_erase, &r.info);
+        if (rc != ORBFE_OK) throw std::runtime_error(std::string("orbfe: ") + orbfe_last_error(ctx));
+        for (int32_t i = 0; i < n_erase; i++) r.vToErase.emplace_back(erase[2 * i], erase[2 * i + 1]);
+        return r;
     }
 };
 
