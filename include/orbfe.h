@@ -65,7 +65,7 @@
 extern "C" {
 #endif
 
-#define ORBFE_ABI_VERSION 6 /* 2: orbfe_frame_view.device_slot_plus1; 3: .keyframe; 4: orbfe_get_camera, orbfe_assign_features_to_grid, orbfe_stereo_batch, orbfe_device_count, orbfe_set_profiling_interval; 5: orbfe_get_packed_layout, orbfe_fetch_batch_packed, orbfe_expand_packed, orbfe_stereo_batch_packed, orbfe_enqueue_rgbd; 6: orbfe_build_id, orbfe_set_pattern, orbfe_get_pattern, orbfe_blur_ride_from, orbfe_set_input_retained (additive: no struct changed; orbfe_fetch_pyramid(level 0) of an in-place batched call now needs the latter); still 6, additive: orbfe_enqueue_search_by_projection_last, orbfe_enqueue_is_in_frustum, orbfe_enqueue_search_by_projection_points, orbfe_device_keys_un; the BoW, relocalisation and triangulation enqueue calls; orbfe_enqueue_keyframe_grid, orbfe_enqueue_fuse, orbfe_enqueue_fuse_sim3 (struct orbfe_grid_keyframe) */
+#define ORBFE_ABI_VERSION 6 /* 2: orbfe_frame_view.device_slot_plus1; 3: .keyframe; 4: orbfe_get_camera, orbfe_assign_features_to_grid, orbfe_stereo_batch, orbfe_device_count, orbfe_set_profiling_interval; 5: orbfe_get_packed_layout, orbfe_fetch_batch_packed, orbfe_expand_packed, orbfe_stereo_batch_packed, orbfe_enqueue_rgbd; 6: orbfe_build_id, orbfe_set_pattern, orbfe_get_pattern, orbfe_blur_ride_from, orbfe_set_input_retained (additive: no struct changed; orbfe_fetch_pyramid(level 0) of an in-place batched call now needs the latter); still 6, additive: orbfe_enqueue_search_by_projection_last, orbfe_enqueue_is_in_frustum, orbfe_enqueue_search_by_projection_points, orbfe_device_keys_un; the BoW, relocalisation and triangulation enqueue calls; orbfe_enqueue_keyframe_grid, orbfe_enqueue_fuse, orbfe_enqueue_fuse_sim3 (struct orbfe_grid_keyframe); orbfe_essential_graph_plan(_size), orbfe_enqueue_optimize_essential_graph, orbfe_optimize_essential_graph */
 
 enum {
     ORBFE_OK = 0,
@@ -1517,6 +1517,79 @@ int orbfe_png_decode(const uint8_t *file, size_t size, uint8_t *dst, size_t dst_
  * dst[i * image_bytes ..]: pinned memory here is the staging block of the upload that feeds orbfe_enqueue_*. */
 int orbfe_png_decode_batch(const uint8_t *const *files, const size_t *sizes, int n, uint8_t *dst, size_t image_bytes,
                            int width, int height, int channels, int bit_depth, int threads);
+
+/* ---- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:825-1088, called by LoopClosing::CorrectLoop, src/LoopClosing.cc:601) on
+ * device-resident keyframes and the map-point table's position column (orbfe_essential_graph.hip).  Additive.
+ *
+ * The edge walk of :891-1027 stays the caller's (ORB_SLAM2::EssentialGraphEdges of orbslam2_amd/host/Optimizer.h restates it on
+ * flattened fields) and arrives as (edge_i, edge_j, kind) in the reference's insertion order: vertex 0 = i, vertex 1 = j, kind 0 = a
+ * LoopConnections edge (measurement vScw[j] * vScw[i].inverse()), kind 1 = a spanning-tree, loop or covisibility edge (the same product
+ * over NonCorrectedSim3 where the keyframe has one, else vScw).  Keyframes are indices 0 .. n_kfs - 1; bad keyframes are not passed in.
+ *
+ * Step 1, on the host: orbfe_essential_graph_plan reads the edge list and writes one relocatable blob (elimination order, block
+ * structure of L with fill, per-edge slots, per-slot edge lists, per-pivot update lists; orbfe_essential_plan.cpp says what lies where).
+ * No GPU call.  ORBFE_ERR_CAPACITY with *blob_bytes = the size needed when blob_capacity is too small; ORBFE_ERR_INVALID for n_kfs < 1
+ * or a fixed_kf outside [0, n_kfs); ORBFE_ERR_UNSUPPORTED when the blob would not fit int32 offsets.  An edge with an end outside
+ * [0, n_kfs) or with i == j is ordinary input: it gets no slot.  The same input gives the same bytes.  The caller uploads the blob once. */
+#define ORBFE_ESSENTIAL_PLAN_MAGIC 0x31504745 /* "EGP1" */
+typedef struct orbfe_essential_plan_header {   /* 80 bytes; offsets count int32 words from the blob's start */
+    int32_t magic, n_kfs, fixed_kf, n_edges, n_free, n_lblocks, n_slot_edges, n_updates, blob_bytes;
+    int32_t off_order, off_pos, off_colptr, off_rowidx, off_edge_slots, off_slot_ptr, off_slot_edges, off_upd_ptr, off_upd;
+    int32_t reserved[2];
+} orbfe_essential_plan_header;
+int orbfe_essential_graph_plan_size(int n_kfs, int fixed_kf, const int32_t *edge_i, const int32_t *edge_j, int n_edges, size_t *blob_bytes);
+int orbfe_essential_graph_plan(int n_kfs, int fixed_kf, const int32_t *edge_i, const int32_t *edge_j, int n_edges, void *blob, size_t blob_capacity,
+                               size_t *blob_bytes);
+
+/* Step 2: the call.  Asynchronous on `stream` (NULL: the context's), nothing is copied from host memory (h_plan_header is read during the
+ * call only, to size the scratch and pick the kernel variant), the same inputs give the same bits on every run.  Two launches: one
+ * workgroup runs the whole optimisation (vertices, measurements, optimize(iterations) with Levenberg and a block-sparse LDLT along the
+ * plan, recovery of the poses); then one lane per point corrects the positions.
+ *   d_Tcw [n_kfs][16] floats       read (the initial estimate of a keyframe without a corrected Sim3) and rewritten for EVERY keyframe, the
+ *                                  fixed one included: toRotationMatrix(), t * (1 / s), Converter::toCvSE3
+ *   d_corrected / d_has_corrected  [n_kfs][8] doubles (qx qy qz qw tx ty tz s) and a flag byte per keyframe: CorrectedSim3; both may be NULL
+ *   d_noncorrected / d_has_noncorrected  the same for NonCorrectedSim3
+ *   d_edge_i, d_edge_j, d_edge_kind      the edges; d_edge_code [n_edges] receives 0, or ORBFE_EG_EDGE_INDEX (an end outside [0, n_kfs) or
+ *                                  i == j) or ORBFE_EG_EDGE_SIM3 (a non-finite Sim3 at one end): that edge is left out, *d_status becomes
+ *                                  ORBFE_ERR_INVALID and the rest of the problem is solved as if the edge were absent.  A keyframe
+ *                                  whose own Sim3 is not finite keeps its d_Tcw row, and so do the points that refer to it.
+ *   d_plan, h_plan_header          the blob in HBM and its header on the host.  The kernel compares the device header with the
+ *                                  arguments (magic, n_kfs, fixed_kf, n_edges, n_lblocks, blob_bytes): on a mismatch *d_status =
+ *                                  ORBFE_ERR_INVALID and NOTHING else is written, by either launch.
+ *   d_pos [n_pts][3] floats        the position column; d_pt_ref [n_pts]: the keyframe whose Sim3s move the point (the caller resolves
+ *                                  mnCorrectedByKF == pCurKF->mnId ? mnCorrectedReference : GetReferenceKeyFrame()); d_pt_valid [n_pts]:
+ *                                  0 = isBad(), the row keeps its bits.  A d_pt_ref outside [0, n_kfs) sets d_pt_code[q] = 1 (else 0)
+ *                                  and *d_status = ORBFE_ERR_INVALID, and the row keeps its bits.  n_pts may be 0.
+ *   d_obs_kfs                      NULL, or the keyframe directory of orbfe_enqueue_update_map_points whose Ow is patched
+ *   lambda_init                    Optimizer::mInitialLambda, (double)(float)1.0e-16 in the reference; must be > 0
+ * UpdateNormalAndDepth remains the caller's orbfe_enqueue_update_map_points over the same rows, on the same stream.  A graph with a
+ * component that no path joins to the fixed keyframe is outside the contract (nearly singular at lambda = 1e-16).  The factorisation's
+ * workspace lives in the LDS while (n_free + n_lblocks) * 49 + n_free * 7 doubles fit ORBFE_EG_LDS_DOUBLES, in the context's grow-only
+ * scratch above that. */
+#define ORBFE_EG_EDGE_INDEX 1
+#define ORBFE_EG_EDGE_SIM3 2
+#define ORBFE_EG_LDS_DOUBLES 16064   /* the 128 KiB of LDS the kernel requests less the 2.5 KiB of its fixed part (static_assert in orbfe_essential_graph.hip) */
+typedef struct orbfe_essential_graph_info {   /* 48 bytes */
+    int32_t iterations, trials;               /* iterations of optimize() begun, Levenberg trials over all of them */
+    int32_t n_active_edges, n_lblocks;        /* edges not left out; off-diagonal blocks of L */
+    double chi2_start, chi2_end, lambda_last;
+    int32_t in_lds, reserved;
+} orbfe_essential_graph_info;
+int orbfe_enqueue_optimize_essential_graph(orbfe_context *ctx, int n_kfs, int fixed_kf, float *d_Tcw,
+        const double *d_corrected, const uint8_t *d_has_corrected, const double *d_noncorrected, const uint8_t *d_has_noncorrected,
+        const int32_t *d_edge_i, const int32_t *d_edge_j, const uint8_t *d_edge_kind, int n_edges,
+        const void *d_plan, const orbfe_essential_plan_header *h_plan_header,
+        int iterations, int fix_scale, double lambda_init,
+        float *d_pos, const int32_t *d_pt_ref, const uint8_t *d_pt_valid, int n_pts, orbfe_obs_keyframe *d_obs_kfs,
+        uint8_t *d_edge_code, uint8_t *d_pt_code, double *d_sim3_out /* NULL or [n_kfs][8]: the final estimates */,
+        orbfe_essential_graph_info *d_info, int32_t *d_status /* [1] */, void *stream);
+/* The same from host arrays, synchronous: plans, uploads, enqueues, downloads; the same bits.  Tcw and pos are rewritten in place; Ow
+ * (NULL or [n_kfs][3]) receives the camera centres.  Returns ORBFE_OK also when *status (what the device set) is ORBFE_ERR_INVALID. */
+int orbfe_optimize_essential_graph(orbfe_context *ctx, int n_kfs, int fixed_kf, float *Tcw,
+        const double *corrected, const uint8_t *has_corrected, const double *noncorrected, const uint8_t *has_noncorrected,
+        const int32_t *edge_i, const int32_t *edge_j, const uint8_t *edge_kind, int n_edges, int iterations, int fix_scale, double lambda_init,
+        float *pos, const int32_t *pt_ref, const uint8_t *pt_valid, int n_pts, float *Ow,
+        uint8_t *edge_code, uint8_t *pt_code, double *sim3_out, orbfe_essential_graph_info *info, int32_t *status);
 
 #ifdef __cplusplus
 }

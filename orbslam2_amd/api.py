@@ -47,6 +47,7 @@ EXPORTS = [
     "orbfe_enqueue_search_by_bow_kf", "orbfe_enqueue_search_by_bow_kf_batch",
     "orbfe_enqueue_update_map_points",
     "orbfe_enqueue_local_bundle_adjustment", "orbfe_local_bundle_adjustment",
+    "orbfe_essential_graph_plan_size", "orbfe_essential_graph_plan", "orbfe_enqueue_optimize_essential_graph", "orbfe_optimize_essential_graph",
     "orbfe_enqueue_triangulate_pairs",
     "orbfe_enqueue_find_homography_fundamental", "orbfe_find_homography_fundamental",
     "orbfe_enqueue_reconstruct_initial", "orbfe_reconstruct_initial",
@@ -177,6 +178,19 @@ assert LBA_INFO_DTYPE.itemsize == 64
 BA_SKIP, BA_LOCAL, BA_LOCAL_HELD, BA_FIXED = 0, 1, 2, 3  # ORBFE_BA_*
 BA_CODE_LEVEL1, BA_CODE_ERASE, BA_CODE_SKIPPED, BA_CODE_FAULTY = 1, 2, 4, 8  # bits of d_edge_code
 LBA_LDS_KEYFRAMES = 21  # ORBFE_LBA_LDS_KEYFRAMES
+
+# orbfe_essential_plan_header and orbfe_essential_graph_info (include/orbfe.h): Optimizer::OptimizeEssentialGraph
+ESSENTIAL_PLAN_MAGIC = 0x31504745
+ESSENTIAL_PLAN_HEADER_DTYPE = np.dtype([(k, "<i4") for k in (
+    "magic", "n_kfs", "fixed_kf", "n_edges", "n_free", "n_lblocks", "n_slot_edges", "n_updates", "blob_bytes", "off_order", "off_pos", "off_colptr",
+    "off_rowidx", "off_edge_slots", "off_slot_ptr", "off_slot_edges", "off_upd_ptr", "off_upd")] + [("reserved", "<i4", 2)])
+assert ESSENTIAL_PLAN_HEADER_DTYPE.itemsize == 80
+EG_INFO_DTYPE = np.dtype([("iterations", "<i4"), ("trials", "<i4"), ("n_active_edges", "<i4"), ("n_lblocks", "<i4"), ("chi2_start", "<f8"),
+                          ("chi2_end", "<f8"), ("lambda_last", "<f8"), ("in_lds", "<i4"), ("reserved", "<i4")])
+assert EG_INFO_DTYPE.itemsize == 48
+EG_EDGE_INDEX, EG_EDGE_SIM3 = 1, 2
+EG_LDS_DOUBLES = 16064  # ORBFE_EG_LDS_DOUBLES
+EG_LAMBDA_INIT = float(np.float32(1.0e-16))  # Optimizer::mInitialLambda
 
 
 class NewpointKeyframe(C.Structure):
@@ -393,8 +407,36 @@ def load():
     L.orbfe_enqueue_local_bundle_adjustment.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 9
     L.orbfe_local_bundle_adjustment.restype = C.c_int
     L.orbfe_local_bundle_adjustment.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, ip, C.POINTER(LbaInfo)]
+    L.orbfe_essential_graph_plan_size.restype = C.c_int
+    L.orbfe_essential_graph_plan_size.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
+    L.orbfe_essential_graph_plan.restype = C.c_int
+    L.orbfe_essential_graph_plan.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.orbfe_enqueue_optimize_essential_graph.restype = C.c_int
+    L.orbfe_enqueue_optimize_essential_graph.argtypes = [vp, C.c_int, C.c_int] + [vp] * 8 + [C.c_int, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp, C.c_int] + [vp] * 7
+    L.orbfe_optimize_essential_graph.restype = C.c_int
+    L.orbfe_optimize_essential_graph.argtypes = [vp, C.c_int, C.c_int] + [vp] * 8 + [C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, C.c_int] + [vp] * 6
     _lib = L
     return L
+
+
+def essential_graph_plan(n_kfs, fixed_kf, edge_i, edge_j, capacity=None):
+    """orbfe_essential_graph_plan (include/orbfe.h): the host-only planner of optimize_essential_graph; needs no GPU.  Returns the blob as
+    int32 words (its first 20 are an ESSENTIAL_PLAN_HEADER_DTYPE record).  capacity: bytes offered instead of what the size query says
+    (an OrbfeError with ERR_CAPACITY when too few)."""
+    L = load()
+    ei = np.ascontiguousarray(edge_i, np.int32); ej = np.ascontiguousarray(edge_j, np.int32)
+    assert ei.shape == ej.shape and ei.ndim == 1
+    n = C.c_size_t()
+    pe = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    rc = L.orbfe_essential_graph_plan_size(int(n_kfs), int(fixed_kf), pe(ei), pe(ej), len(ei), C.byref(n))
+    if rc != OK:
+        raise OrbfeError(rc, "orbfe_essential_graph_plan_size refused n_kfs = %d, fixed_kf = %d" % (n_kfs, fixed_kf))
+    cap = n.value if capacity is None else int(capacity)
+    blob = np.zeros(max(cap // 4, 1), np.int32)
+    rc = L.orbfe_essential_graph_plan(int(n_kfs), int(fixed_kf), pe(ei), pe(ej), len(ei), blob.ctypes.data_as(C.c_void_p), cap, C.byref(n))
+    if rc != OK:
+        raise OrbfeError(rc, "orbfe_essential_graph_plan: %d bytes offered, %d needed" % (cap, n.value))
+    return blob[: n.value // 4]
 
 
 def _p(a):
@@ -1089,6 +1131,46 @@ class Context:
             self._check(rc)
         return dict(Tcw=T, pos=po, Ow=Ow, edge_code=code, edge_chi2=chi, erase=erase[:n_erase.value].copy(),
                     info=np.frombuffer(bytes(info), LBA_INFO_DTYPE)[0], status=rc)
+
+    def enqueue_optimize_essential_graph(self, n_kfs, fixed_kf, d_Tcw, d_corrected, d_has_corrected, d_noncorrected, d_has_noncorrected, d_edge_i, d_edge_j,
+                                         d_edge_kind, n_edges, d_plan, plan_header, iterations, fix_scale, lambda_init, d_pos, d_pt_ref, d_pt_valid, n_pts,
+                                         d_obs_kfs, d_edge_code, d_pt_code, d_sim3_out, d_info, d_status, stream=0):
+        """Optimizer::OptimizeEssentialGraph on device-resident keyframes and the position column (include/orbfe.h), asynchronous on
+        `stream`.  d_plan: essential_graph_plan()'s blob in HBM; plan_header: the blob itself or its first 20 words, on the host.  Every
+        other d_ argument is a device address (0: none, where the header allows it); d_info receives one EG_INFO_DTYPE record."""
+        v = C.c_void_p
+        hdr = np.ascontiguousarray(np.asarray(plan_header).view(np.int32).reshape(-1)[:20])
+        self._check(self.L.orbfe_enqueue_optimize_essential_graph(
+            self.h, n_kfs, fixed_kf, *[v(x or None) for x in (d_Tcw, d_corrected, d_has_corrected, d_noncorrected, d_has_noncorrected, d_edge_i, d_edge_j,
+                                                             d_edge_kind)], n_edges, v(d_plan or None), _p(hdr), int(iterations), int(fix_scale),
+            float(lambda_init), v(d_pos or None), v(d_pt_ref or None), v(d_pt_valid or None), n_pts,
+            *[v(x or None) for x in (d_obs_kfs, d_edge_code, d_pt_code, d_sim3_out, d_info, d_status, stream)]))
+
+    def optimize_essential_graph(self, fixed_kf, Tcw, edge_i, edge_j, edge_kind, corrected=None, has_corrected=None, noncorrected=None,
+                                 has_noncorrected=None, iterations=20, fix_scale=False, lambda_init=EG_LAMBDA_INIT, pos=None, pt_ref=None, pt_valid=None):
+        """The same from host arrays, synchronous (it plans, uploads, enqueues and downloads).  Returns a dict: Tcw float32[n_kfs][16],
+        pos float32[n_pts][3], Ow float32[n_kfs][3], sim3 float64[n_kfs][8] (the final estimates), edge_code uint8[n_edges], pt_code
+        uint8[n_pts], info (an EG_INFO_DTYPE record), status (0 or ERR_INVALID, as the device set it)."""
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(-1, 16).copy()
+        n_kfs = len(T)
+        ei = np.ascontiguousarray(edge_i, np.int32); ej = np.ascontiguousarray(edge_j, np.int32); ek = np.ascontiguousarray(edge_kind, np.uint8)
+        assert len(ei) == len(ej) == len(ek)
+        tab = lambda a: None if a is None else np.ascontiguousarray(a, np.float64).reshape(n_kfs, 8)
+        flg = lambda a: None if a is None else np.ascontiguousarray(a, np.uint8).reshape(n_kfs)
+        co, hc, no, hn = tab(corrected), flg(has_corrected), tab(noncorrected), flg(has_noncorrected)
+        po = np.zeros((0, 3), np.float32) if pos is None else np.ascontiguousarray(pos, np.float32).reshape(-1, 3).copy()
+        n_pts = len(po)
+        pr = np.zeros(0, np.int32) if pt_ref is None else np.ascontiguousarray(pt_ref, np.int32)
+        pv = np.zeros(0, np.uint8) if pt_valid is None else np.ascontiguousarray(pt_valid, np.uint8)
+        assert len(pr) == n_pts and len(pv) == n_pts
+        Ow = np.zeros((n_kfs, 3), np.float32); sim3 = np.zeros((n_kfs, 8), np.float64)
+        ecode = np.zeros(len(ei), np.uint8); pcode = np.zeros(n_pts, np.uint8)
+        info = np.zeros(1, EG_INFO_DTYPE); status = np.zeros(1, np.int32)
+        ptr = lambda a: _p(a) if a is not None and a.size else None
+        self._check(self.L.orbfe_optimize_essential_graph(
+            self.h, n_kfs, int(fixed_kf), ptr(T), ptr(co), ptr(hc), ptr(no), ptr(hn), ptr(ei), ptr(ej), ptr(ek), len(ei), int(iterations), int(fix_scale),
+            float(lambda_init), ptr(po), ptr(pr), ptr(pv), n_pts, ptr(Ow), ptr(ecode), ptr(pcode), ptr(sim3), ptr(info), ptr(status)))
+        return dict(Tcw=T, pos=po, Ow=Ow, sim3=sim3, edge_code=ecode, pt_code=pcode, info=info[0], status=int(status[0]))
 
     def enqueue_sim3_ransac_batch(self, kf1, T1w, d_pos1, d_valid1, d_cands, n_cands, max_pairs, max_kf_n, fix_scale, min_inliers, max_its, d_its_for_n,
                                   d_n_corr, d_n_its, d_corr, d_sets, d_hyp, d_inlier_bits, d_events, d_n_events, d_status, stream=0):

@@ -102,6 +102,7 @@ struct orbfe_context {
     DevBuf sim3_ransac_scratch, sim3_ransac_sync; // orbfe_enqueue_sim3_ransac_batch's correspondence tables; the synchronous form's arrays
     DevBuf pnp_ransac_scratch, pnp_ransac_sync; // orbfe_enqueue_pnp_ransac_batch's correspondence tables; the synchronous form's arrays
     DevBuf lba_scratch, lba_sync; // orbfe_enqueue_local_bundle_adjustment's vertices, per-edge blocks and (above ORBFE_LBA_LDS_KEYFRAMES) reduced system; the synchronous form's arrays
+    DevBuf eg_scratch, eg_sync; // orbfe_enqueue_optimize_essential_graph's vertices, per-edge blocks, H and (above ORBFE_EG_LDS_DOUBLES) the factorisation's workspace; the synchronous form's arrays
     hipError_t chain_err = hipSuccess; // a launcher's refusal inside run_chain (enqueue_batch reports it)
     char err[512];
 };

@@ -1,0 +1,165 @@
+"""ORB_SLAM2::Optimizer::EssentialGraphEdges (orbslam2_amd/host/Optimizer.h), through tests/essential_blocks/optimizer_wrapper.cpp, against a
+literal Python transcription of the edge walk of Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:891-1027) on hand-made
+maps, with exact edge lists.  Host code only: no GPU."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+class KF:
+    def __init__(self, mnId):
+        self.mnId, self.parent, self.loop_edges, self.covisibles, self.children, self.weight, self.bad = mnId, None, [], [], [], {}, False
+
+    def GetWeight(self, other):
+        return self.weight.get(other, 0)
+
+
+def literal_walk(vpKFs, LoopConnections, minFeat, pCurKF, pLoopKF):
+    """:891-1027 line by line; containers iterate in the order the map holds them.  Returns (nIDi, nIDj, kind) with kind 0 for the loop
+    connections: vertex 0 = nIDi, vertex 1 = nIDj."""
+    out = []
+    sInsertedEdges = set()
+    for pKF, spConnections in LoopConnections:                      # :896
+        nIDi = pKF.mnId
+        for pKFn in spConnections:                                   # :904
+            nIDj = pKFn.mnId
+            if (nIDi != pCurKF.mnId or nIDj != pLoopKF.mnId) and pKF.GetWeight(pKFn) < minFeat:   # :907
+                continue
+            out.append((nIDi, nIDj, 0))                              # :913-920
+            sInsertedEdges.add((min(nIDi, nIDj), max(nIDi, nIDj)))   # :922
+    for pKF in vpKFs:                                                # :927
+        nIDi = pKF.mnId
+        pParentKF = pKF.parent
+        if pParentKF:                                                # :945
+            out.append((nIDi, pParentKF.mnId, 1))
+        sLoopEdges = pKF.loop_edges
+        for pLKF in sLoopEdges:                                      # :971
+            if pLKF.mnId < pKF.mnId:
+                out.append((nIDi, pLKF.mnId, 1))
+        for pKFn in pKF.covisibles:                                  # :996-997: GetCovisiblesByWeight(minFeat)
+            if pKFn and pKFn != pParentKF and pKFn not in pKF.children and pKFn not in sLoopEdges:   # :1000
+                if not pKFn.bad and pKFn.mnId < pKF.mnId:            # :1002
+                    if (min(pKF.mnId, pKFn.mnId), max(pKF.mnId, pKFn.mnId)) in sInsertedEdges:      # :1004
+                        continue
+                    out.append((nIDi, pKFn.mnId, 1))
+    return out
+
+
+def make_map(n, ids=None):
+    kfs = [KF(ids[k] if ids else k) for k in range(n)]
+    for k in range(1, n):
+        kfs[k].parent = kfs[k - 1]
+        kfs[k - 1].children.append(kfs[k])
+    return kfs
+
+
+def connect(a, b, w):
+    a.weight[b] = w
+    b.weight[a] = w
+
+
+def map_covisible_already_inserted():
+    """The covisible pair (5, 1) is also a loop connection: inserted once, as a kind-0 edge."""
+    k = make_map(6)
+    connect(k[5], k[0], 40); connect(k[5], k[1], 120); connect(k[4], k[0], 130); connect(k[3], k[1], 150)
+    k[5].covisibles = [k[1], k[4], k[3]]; k[1].covisibles = [k[5], k[3]]; k[3].covisibles = [k[1], k[5]]
+    k[4].covisibles = [k[0]]
+    return k, [(k[5], [k[0], k[1]]), (k[4], [k[0]])], 100, k[5], k[0]
+
+
+def map_parent_is_covisible():
+    """Covisibles that are the parent, a child or a loop edge add nothing; ids that are not the indices; a bad covisible."""
+    k = make_map(5, ids=[3, 7, 8, 20, 21])
+    k[2].covisibles = [k[1], k[3], k[0]]        # parent, child, a plain one
+    k[4].covisibles = [k[3], k[1], None, k[0]]  # parent, a plain one, NULL, a loop edge
+    k[4].loop_edges = [k[0]]; k[0].loop_edges = [k[4]]
+    k[3].covisibles = [k[1]]
+    k[1].bad = False
+    bad = KF(5); bad.bad = True
+    k[3].covisibles.append(bad)
+    return k, [], 100, k[4], k[0]
+
+
+def map_loop_edge_both_ways():
+    """Both ends list the loop edge: only the end with the larger mnId inserts it.  The keyframes are not in mnId order."""
+    k = make_map(5)
+    k[4].loop_edges = [k[1], k[0]]; k[1].loop_edges = [k[4]]; k[0].loop_edges = [k[4]]
+    order = [k[2], k[4], k[0], k[3], k[1]]
+    return order, [], 100, k[4], k[0]
+
+
+def map_weight_below_minfeat():
+    """The current-loop pair is forced at weight minFeat - 1; the same weight on another pair is dropped; minFeat itself stays."""
+    k = make_map(6)
+    connect(k[5], k[0], 99); connect(k[5], k[1], 99); connect(k[4], k[0], 100); connect(k[0], k[5], 99)
+    k[5].covisibles = [k[1]]   # the dropped loop connection comes back as a covisibility edge
+    return k, [(k[5], [k[1], k[0]]), (k[4], [k[0]]), (k[0], [k[5]])], 100, k[5], k[0]
+
+
+MAPS = {"covisible_already_inserted": map_covisible_already_inserted, "parent_is_covisible": map_parent_is_covisible,
+        "loop_edge_both_ways": map_loop_edge_both_ways, "weight_below_minfeat": map_weight_below_minfeat}
+EXPECTED = {
+    "covisible_already_inserted": [(5, 0, 0), (5, 1, 0), (4, 0, 0), (1, 0, 1), (2, 1, 1), (3, 2, 1), (3, 1, 1), (4, 3, 1), (5, 4, 1), (5, 3, 1)],
+    "parent_is_covisible": [(7, 3, 1), (8, 7, 1), (8, 3, 1), (20, 8, 1), (20, 7, 1), (21, 20, 1), (21, 3, 1), (21, 7, 1)],
+    "loop_edge_both_ways": [(2, 1, 1), (4, 3, 1), (4, 1, 1), (4, 0, 1), (3, 2, 1), (1, 0, 1)],
+    "weight_below_minfeat": [(5, 0, 0), (4, 0, 0), (1, 0, 1), (2, 1, 1), (3, 2, 1), (4, 3, 1), (5, 4, 1), (5, 1, 1)],
+}
+
+
+@pytest.fixture(scope="module")
+def lib():
+    path = os.path.join(HERE, "essential_blocks", "libessential_wrapper.so")
+    if not os.path.exists(path):
+        pytest.fail("tests/essential_blocks/libessential_wrapper.so is not built (run build())")
+    L = C.CDLL(path)
+    L.eg_wrapper_edges.restype = C.c_int
+    L.eg_wrapper_edges.argtypes = [C.c_int] + [C.c_void_p] * 8 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int]
+    return L
+
+
+def csr(lists):
+    off = np.zeros(len(lists) + 1, np.int32)
+    off[1:] = np.cumsum([len(l) for l in lists])
+    return off, np.array([v for l in lists for v in l] + [0], np.int32)
+
+
+def wrapper_walk(L, vpKFs, LoopConnections, minFeat, pCurKF, pLoopKF):
+    index = {kf: k for k, kf in enumerate(vpKFs)}
+    ix = lambda kf: -1 if (kf is None or kf.bad or kf not in index) else index[kf]
+    ids = np.array([kf.mnId for kf in vpKFs], np.uint64)
+    parent = np.array([ix(kf.parent) for kf in vpKFs], np.int32)
+    lo, lv = csr([[ix(x) for x in kf.loop_edges] for kf in vpKFs])
+    co, cv = csr([[ix(x) for x in kf.covisibles] for kf in vpKFs])
+    ho, hv = csr([[ix(x) for x in kf.children] for kf in vpKFs])
+    ck = np.array([ix(kf) for kf, _ in LoopConnections] + [0], np.int32)
+    no, nv = csr([[ix(x) for x in conn] for _, conn in LoopConnections])
+    nw = np.array([kf.GetWeight(x) for kf, conn in LoopConnections for x in conn] + [0], np.int32)
+    cap = 64
+    ei, ej, ek = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.uint8)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    n = L.eg_wrapper_edges(len(vpKFs), p(ids), p(parent), p(lo), p(lv), p(co), p(cv), p(ho), p(hv), len(LoopConnections), p(ck), p(no), p(nv), p(nw), minFeat,
+                           index[pCurKF], index[pLoopKF], p(ei), p(ej), p(ek), cap)
+    assert 0 <= n <= cap, n
+    return [(int(vpKFs[ei[e]].mnId), int(vpKFs[ej[e]].mnId), int(ek[e])) for e in range(n)]
+
+
+@pytest.mark.parametrize("name", sorted(MAPS))
+def test_edges_equal_the_literal_walk(lib, name):
+    vpKFs, conns, minFeat, cur, loop = MAPS[name]()
+    want = literal_walk(vpKFs, conns, minFeat, cur, loop)
+    assert want == EXPECTED[name]          # the transcription itself, against the list worked out by hand
+    assert wrapper_walk(lib, vpKFs, conns, minFeat, cur, loop) == want
+
+
+def test_faulty_indices_throw(lib):
+    vpKFs, conns, minFeat, cur, loop = map_loop_edge_both_ways()
+    ids = np.arange(5, dtype=np.uint64)
+    parent = np.array([-1, 0, 1, 2, 9], np.int32)   # a parent outside the map
+    z = np.zeros(6, np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    out = np.zeros(8, np.int32)
+    assert lib.eg_wrapper_edges(5, p(ids), p(parent), p(z), p(z), p(z), p(z), p(z), p(z), 0, p(z), p(z), p(z), p(z), 100, 4, 0, p(out), p(out), p(out.view(np.uint8)), 8) == -100
