@@ -74,15 +74,12 @@ __host__ __device__ inline size_t eg_workspace_doubles(int n_free, int n_lblocks
 size_t eg_carve(EgArgs &a, uint8_t *base, bool workspace_in_hbm)
 {
     const size_t K = (size_t)std::max(a.n_kfs, 1), E = (size_t)std::max(a.n_edges, 1), n_free = K - 1, S = n_free + (size_t)a.n_lblocks;
-    size_t at = 0;
-    auto take = [&](size_t doubles) { double *p = base ? (double *)(base + at) : nullptr; at += sizeof(double) * std::max<size_t>(doubles, 1); return p; };
-    a.init = take(8 * K); a.est[0] = take(8 * K); a.est[1] = take(8 * K); a.invf = take(8 * K);
-    a.meas = take(8 * E); a.pert = take((size_t)EG_PERT_STRIDE * K); a.eblk = take((size_t)EG_EDGE_DOUBLES * E);
-    a.H = take(49 * S); a.b = take(7 * n_free); a.x = take(7 * n_free);
-    a.F = workspace_in_hbm ? take(eg_workspace_doubles((int)n_free, a.n_lblocks)) : nullptr;
-    a.vbad = base ? base + at : nullptr;
-    at += (K + 15) & ~(size_t)15;
-    return at;
+    orbfe::Arena c(base, sizeof(double), sizeof(double)); // an empty field still holds one double
+    a.init = c.take<double>(8 * K); a.est[0] = c.take<double>(8 * K); a.est[1] = c.take<double>(8 * K); a.invf = c.take<double>(8 * K); a.meas = c.take<double>(8 * E);
+    a.pert = c.take<double>((size_t)EG_PERT_STRIDE * K); a.eblk = c.take<double>((size_t)EG_EDGE_DOUBLES * E); a.H = c.take<double>(49 * S);
+    a.b = c.take<double>(7 * n_free); a.x = c.take<double>(7 * n_free);
+    a.F = workspace_in_hbm ? c.take<double>(eg_workspace_doubles((int)n_free, a.n_lblocks)) : nullptr; a.vbad = c.take<uint8_t>(orbfe::round_up(K, 16));
+    return c.bytes();
 }
 
 // the device header against the call's arguments, and the sections against the header: after this every section lies inside the blob
@@ -384,48 +381,43 @@ try {
     if (rc != ORBFE_OK) return orbfe_fail(ctx, rc, "the planner refused the graph (n_kfs = %d, fixed_kf = %d, n_edges = %d)", n_kfs, fixed_kf, n_edges);
     hipStream_t s;
     if ((rc = orbfe_enqueue_on(ctx, nullptr, false, &s))) return rc;
-    // block layout: results first (copied back in one piece), then the inputs
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t K = (size_t)n_kfs, E = (size_t)std::max(n_edges, 1), N = (size_t)std::max(n_pts, 1);
-    const size_t o_info = 0, o_status = up16(o_info + sizeof(orbfe_essential_graph_info)), o_T = up16(o_status + 4), o_pos = up16(o_T + sizeof(float) * 16 * K),
-                 o_okf = up16(o_pos + sizeof(float) * 3 * N), o_sim = up16(o_okf + sizeof(orbfe_obs_keyframe) * K), o_ecode = up16(o_sim + sizeof(double) * 8 * K),
-                 o_pcode = up16(o_ecode + E), down = up16(o_pcode + N);
-    const size_t o_corr = down, o_hc = up16(o_corr + sizeof(double) * 8 * K), o_nonc = up16(o_hc + K), o_hn = up16(o_nonc + sizeof(double) * 8 * K),
-                 o_ei = up16(o_hn + K), o_ej = up16(o_ei + 4 * E), o_kind = up16(o_ej + 4 * E), o_ref = up16(o_kind + E), o_valid = up16(o_ref + 4 * N),
-                 o_plan = up16(o_valid + N), bytes = up16(o_plan + plan_bytes);
-    if (ctx->eg_sync.ensure(bytes)) return orbfe_fail(ctx, ORBFE_ERR_HIP, "essential graph staging allocation failed");
-    std::vector<uint8_t> host(bytes, 0);
-    uint8_t *hb = host.data(), *db = (uint8_t *)ctx->eg_sync.p;
-    memcpy(hb + o_T, Tcw, sizeof(float) * 16 * K);
-    if (n_pts > 0) { memcpy(hb + o_pos, pos, sizeof(float) * 3 * N); memcpy(hb + o_ref, pt_ref, 4 * N); memcpy(hb + o_valid, pt_valid, N); }
-    if (corrected) { memcpy(hb + o_corr, corrected, sizeof(double) * 8 * K); memcpy(hb + o_hc, has_corrected, K); }
-    if (noncorrected) { memcpy(hb + o_nonc, noncorrected, sizeof(double) * 8 * K); memcpy(hb + o_hn, has_noncorrected, K); }
-    if (n_edges > 0) { memcpy(hb + o_ei, edge_i, 4 * E); memcpy(hb + o_ej, edge_j, 4 * E); memcpy(hb + o_kind, edge_kind, E); }
+    // the staging block: results first, then the inputs; the planner writes its blob straight into the host image
+    const size_t K = (size_t)n_kfs;
+    orbfe::StageLayout L;
+    const auto f_info = L.result<orbfe_essential_graph_info>(1); const auto f_status = L.result<int32_t>(1); const auto f_T = L.result<float>(K, 16);
+    const auto f_pos = L.result<float>(n_pts, 3); const auto f_okf = L.result<orbfe_obs_keyframe>(K); const auto f_sim = L.result<double>(K, 8);
+    const auto f_ecode = L.result<uint8_t>(n_edges); const auto f_pcode = L.result<uint8_t>(n_pts);
+    const auto f_corr = L.input<double>(K, 8);
+    const auto f_hc = L.input<uint8_t>(K); const auto f_nonc = L.input<double>(K, 8); const auto f_hn = L.input<uint8_t>(K);
+    const auto f_ei = L.input<int32_t>(n_edges); const auto f_ej = L.input<int32_t>(n_edges); const auto f_kind = L.input<uint8_t>(n_edges);
+    const auto f_ref = L.input<int32_t>(n_pts); const auto f_valid = L.input<uint8_t>(n_pts); const auto f_plan = L.input<uint8_t>(plan_bytes);
+    if (ctx->sync_stage.ensure(L.bytes())) return orbfe_fail(ctx, ORBFE_ERR_HIP, "essential graph staging allocation failed");
+    StageBlock blk(L, ctx->sync_stage);
+    blk.put(f_T, Tcw, 16 * K); blk.put(f_pos, pos, 3 * (size_t)n_pts); blk.put(f_ref, pt_ref, n_pts); blk.put(f_valid, pt_valid, n_pts);
+    if (corrected) { blk.put(f_corr, corrected, 8 * K); blk.put(f_hc, has_corrected, K); }
+    if (noncorrected) { blk.put(f_nonc, noncorrected, 8 * K); blk.put(f_hn, has_noncorrected, K); }
+    blk.put(f_ei, edge_i, n_edges); blk.put(f_ej, edge_j, n_edges); blk.put(f_kind, edge_kind, n_edges);
     size_t got = 0;
-    rc = orbfe_essential_graph_plan(n_kfs, fixed_kf, edge_i, edge_j, n_edges, hb + o_plan, plan_bytes, &got);
+    rc = orbfe_essential_graph_plan(n_kfs, fixed_kf, edge_i, edge_j, n_edges, blk.host(f_plan), f_plan.count, &got);
     if (rc != ORBFE_OK) return orbfe_fail(ctx, rc, "the planner refused the graph");
     orbfe_essential_plan_header hdr;
-    memcpy(&hdr, hb + o_plan, sizeof(hdr));
-    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, s));
-    rc = orbfe_enqueue_optimize_essential_graph(ctx, n_kfs, fixed_kf, (float *)(db + o_T), corrected ? (const double *)(db + o_corr) : nullptr,
-                                                corrected ? db + o_hc : nullptr, noncorrected ? (const double *)(db + o_nonc) : nullptr,
-                                                noncorrected ? db + o_hn : nullptr, (const int32_t *)(db + o_ei), (const int32_t *)(db + o_ej), db + o_kind, n_edges,
-                                                db + o_plan, &hdr, iterations, fix_scale, lambda_init, (float *)(db + o_pos), (const int32_t *)(db + o_ref),
-                                                db + o_valid, n_pts, Ow ? (orbfe_obs_keyframe *)(db + o_okf) : nullptr, db + o_ecode, db + o_pcode,
-                                                (double *)(db + o_sim), (orbfe_essential_graph_info *)(db + o_info), (int32_t *)(db + o_status), nullptr);
+    memcpy(&hdr, blk.host(f_plan), sizeof(hdr));
+    ORBFE_HIP_TRY(ctx, blk.upload(s));
+    rc = orbfe_enqueue_optimize_essential_graph(ctx, n_kfs, fixed_kf, blk.dev(f_T), corrected ? blk.dev(f_corr) : nullptr, corrected ? blk.dev(f_hc) : nullptr,
+                                                noncorrected ? blk.dev(f_nonc) : nullptr, noncorrected ? blk.dev(f_hn) : nullptr, blk.dev(f_ei), blk.dev(f_ej),
+                                                blk.dev(f_kind), n_edges, blk.dev(f_plan), &hdr, iterations, fix_scale, lambda_init, blk.dev(f_pos), blk.dev(f_ref),
+                                                blk.dev(f_valid), n_pts, Ow ? blk.dev(f_okf) : nullptr, blk.dev(f_ecode), blk.dev(f_pcode), blk.dev(f_sim),
+                                                blk.dev(f_info), blk.dev(f_status), nullptr);
     if (rc != ORBFE_OK) return rc;
-    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(hb, db, down, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP_TRY(ctx, blk.download(s));
     ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
-    memcpy(info, hb + o_info, sizeof(*info));
-    memcpy(status, hb + o_status, 4);
-    memcpy(Tcw, hb + o_T, sizeof(float) * 16 * K);
-    if (n_pts > 0) memcpy(pos, hb + o_pos, sizeof(float) * 3 * N);
+    blk.get(f_info, info, 1); blk.get(f_status, status, 1); blk.get(f_T, Tcw, 16 * K); blk.get(f_pos, pos, 3 * (size_t)n_pts);
     if (Ow) {
-        const orbfe_obs_keyframe *okf = (const orbfe_obs_keyframe *)(hb + o_okf);
+        const orbfe_obs_keyframe *okf = blk.host(f_okf);
         for (size_t k = 0; k < K; k++) memcpy(Ow + 3 * k, okf[k].Ow, sizeof(float) * 3);
     }
-    if (sim3_out) memcpy(sim3_out, hb + o_sim, sizeof(double) * 8 * K);
-    if (n_edges > 0) memcpy(edge_code, hb + o_ecode, E);
-    if (n_pts > 0 && pt_code) memcpy(pt_code, hb + o_pcode, N);
+    if (sim3_out) blk.get(f_sim, sim3_out, 8 * K);
+    blk.get(f_ecode, edge_code, n_edges);
+    if (pt_code) blk.get(f_pcode, pt_code, n_pts);
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)

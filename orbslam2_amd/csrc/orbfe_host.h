@@ -1,9 +1,12 @@
 // orbfe_host.h -- the context and the host-side helpers shared by the translation units of liborbfe.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstring>
 #include <mutex>
+#include <stdexcept>
 #include <vector>
 #include "../../include/orbfe.h"
+#include "orbfe_arena.hpp"
 #include "orbfe_device.h"
 #include "orbfe_plan.h"
 
@@ -14,6 +17,7 @@ struct DevBuf {
     int ensure(size_t need)
     {
         if (need <= bytes) return 0;
+        if (need == SIZE_MAX) return -1; // an arena whose size overflowed (orbfe_arena.hpp)
         if (p) (void)hipFree(p);
         p = nullptr; bytes = 0;
         if (hipMalloc(&p, need) != hipSuccess) return -1;
@@ -24,6 +28,34 @@ struct DevBuf {
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
     ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+// The staging block of a synchronous entry point: a layout (orbfe_arena.hpp) bound to a device buffer that already holds
+// layout.bytes() and to its host image -- the block's own zeroed memory, or the caller's pinned block of at least that size.  One
+// copy up, the enqueue form on dev() pointers, one copy of the results down.
+class StageBlock {
+public:
+    StageBlock(const orbfe::StageLayout &layout, const DevBuf &dev, uint8_t *pinned = nullptr) : l_(layout), d_((uint8_t *)dev.p), h_(pinned)
+    {
+        if (!h_) { own_.assign(l_.bytes(), 0); h_ = own_.data(); }
+    }
+    template <class T> T *host(orbfe::Field<T> f) const { return (T *)(h_ + f.offset); }
+    template <class T> T *dev(orbfe::Field<T> f) const { return (T *)(d_ + f.offset); }
+    // n elements into / out of the field, from its element `at` on; they must fit the field
+    template <class T> void put(orbfe::Field<T> f, const void *src, size_t n, size_t at = 0) { if (fits(n, at, f.count)) memcpy(host(f) + at, src, sizeof(T) * n); }
+    template <class T> void get(orbfe::Field<T> f, void *dst, size_t n, size_t at = 0) const { if (fits(n, at, f.count)) memcpy(dst, host(f) + at, sizeof(T) * n); }
+    hipError_t upload(hipStream_t s) const { return hipMemcpyAsync(d_, h_, l_.bytes(), hipMemcpyHostToDevice, s); }
+    hipError_t download(hipStream_t s) const { return hipMemcpyAsync(h_, d_, l_.down(), hipMemcpyDeviceToHost, s); }
+
+private:
+    static bool fits(size_t n, size_t at, size_t count)
+    {
+        if (at > count || n > count - at) throw std::length_error("staging block: more elements than the field holds");
+        return n > 0;
+    }
+    const orbfe::StageLayout &l_;
+    uint8_t *d_, *h_;
+    std::vector<uint8_t> own_;
 };
 
 // lazily created state of the feature files; each is destroyed by orbfe_destroy
@@ -96,13 +128,18 @@ struct orbfe_context {
     orbfe_match_device_state *match_device = nullptr;
     orbfe_bow_state *bow = nullptr;
     orbfe_pose_state *pose = nullptr;
-    DevBuf init_scratch, init_sync; // orbfe_enqueue_find_homography_fundamental's per-hypothesis scratch; the synchronous form's arrays
-    DevBuf recon_scratch, recon_sync; // the same of orbfe_enqueue_reconstruct_initial: its own, so that growing one never frees what the call before it still reads
-    DevBuf sim3_opt_scratch, sim3_opt_sync; // orbfe_enqueue_optimize_sim3's correspondence table when it does not fit the LDS; the synchronous form's arrays
-    DevBuf sim3_ransac_scratch, sim3_ransac_sync; // orbfe_enqueue_sim3_ransac_batch's correspondence tables; the synchronous form's arrays
-    DevBuf pnp_ransac_scratch, pnp_ransac_sync; // orbfe_enqueue_pnp_ransac_batch's correspondence tables; the synchronous form's arrays
-    DevBuf lba_scratch, lba_sync; // orbfe_enqueue_local_bundle_adjustment's vertices, per-edge blocks and (above ORBFE_LBA_LDS_KEYFRAMES) reduced system; the synchronous form's arrays
-    DevBuf eg_scratch, eg_sync; // orbfe_enqueue_optimize_essential_graph's vertices, per-edge blocks, H and (above ORBFE_EG_LDS_DOUBLES) the factorisation's workspace; the synchronous form's arrays
+    // The scratch of the enqueue forms: one buffer each, so that growing one never frees what the call before it still reads.
+    DevBuf init_scratch;        // orbfe_enqueue_find_homography_fundamental's per-hypothesis scratch
+    DevBuf recon_scratch;       // the same of orbfe_enqueue_reconstruct_initial
+    DevBuf sim3_opt_scratch;    // orbfe_enqueue_optimize_sim3's correspondence table when it does not fit the LDS
+    DevBuf sim3_ransac_scratch; // orbfe_enqueue_sim3_ransac_batch's correspondence tables
+    DevBuf pnp_ransac_scratch;  // orbfe_enqueue_pnp_ransac_batch's correspondence tables
+    DevBuf lba_scratch;         // orbfe_enqueue_local_bundle_adjustment's vertices, per-edge blocks and (above ORBFE_LBA_LDS_KEYFRAMES) reduced system
+    DevBuf eg_scratch;          // orbfe_enqueue_optimize_essential_graph's vertices, per-edge blocks, H and (above ORBFE_EG_LDS_DOUBLES) the factorisation's workspace
+    // The arrays of the synchronous forms of all seven: each holds the context's mutex, stages into this buffer, and synchronises its
+    // stream before it returns, and none calls another, so no two blocks are ever live together.  (PoseOptimization and the
+    // matchers keep blocks of their own in their state.)
+    DevBuf sync_stage;
     hipError_t chain_err = hipSuccess; // a launcher's refusal inside run_chain (enqueue_batch reports it)
     char err[512];
 };

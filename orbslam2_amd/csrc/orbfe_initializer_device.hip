@@ -348,12 +348,11 @@ try {
     if (const int rc = orbfe_enqueue_on(ctx, nullptr, false, &s)) return rc;
     // one device block: inputs, then outputs
     const size_t it = (size_t)iterations, kb1 = sizeof(orbfe_keypoint) * (size_t)n1, kb2 = sizeof(orbfe_keypoint) * (size_t)n2;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 15) & ~(size_t)15; return o; };
-    const size_t o_k1 = take(kb1), o_k2 = take(kb2), o_pairs = take(8 * (size_t)N), o_sets = take(32 * it), o_small = take(32 * 4), o_ih = take(N), o_if = take(N),
-                 o_all = take(8 * it);
-    if (ctx->init_sync.ensure(off) != 0) return orbfe_fail(ctx, ORBFE_ERR_HIP, "find_homography_fundamental: device allocation failed");
-    uint8_t *d = (uint8_t *)ctx->init_sync.p;
+    orbfe::Arena c(nullptr, 16, 0);
+    const size_t o_k1 = c.take_bytes(1, kb1), o_k2 = c.take_bytes(1, kb2), o_pairs = c.take_bytes(8, N), o_sets = c.take_bytes(32, it), o_small = c.take_bytes(4, 32),
+                 o_ih = c.take_bytes(1, N), o_if = c.take_bytes(1, N), o_all = c.take_bytes(8, it);
+    if (ctx->sync_stage.ensure(c.bytes()) != 0) return orbfe_fail(ctx, ORBFE_ERR_HIP, "find_homography_fundamental: device allocation failed");
+    uint8_t *d = (uint8_t *)ctx->sync_stage.p;
     if (kb1) ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d + o_k1, keys1_un, kb1, hipMemcpyHostToDevice, s));
     if (kb2) ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d + o_k2, keys2_un, kb2, hipMemcpyHostToDevice, s));
     ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d + o_pairs, pairs.data(), 8 * (size_t)N, hipMemcpyHostToDevice, s));

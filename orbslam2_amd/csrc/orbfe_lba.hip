@@ -110,69 +110,57 @@ try {
     }
     hipStream_t s;
     if (const int rc = orbfe_enqueue_on(ctx, nullptr, false, &s)) return rc;
-    // block layout: results first (copied back in one piece), then the inputs
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t K = (size_t)std::max(n_kfs, 1), N = (size_t)std::max(n_pts, 1), E = (size_t)std::max(n_obs, 1), R = (size_t)std::max(n_rows, 1);
-    const size_t o_info = 0, o_cnt = up16(o_info + sizeof(orbfe_lba_info)), o_T = up16(o_cnt + 2 * sizeof(int32_t)), o_pos = up16(o_T + sizeof(float) * 16 * K),
-                 o_okf = up16(o_pos + sizeof(float) * 3 * R), o_code = up16(o_okf + sizeof(orbfe_obs_keyframe) * K), o_chi = up16(o_code + E),
-                 o_erase = up16(o_chi + sizeof(double) * E), down = up16(o_erase + sizeof(int32_t) * 2 * E);
-    const size_t o_rec = down, o_role = up16(o_rec + sizeof(orbfe_ba_keyframe) * K), o_row = up16(o_role + K), o_off = up16(o_row + sizeof(int32_t) * N),
-                 o_kf = up16(o_off + sizeof(int32_t) * (N + 1)), o_idx = up16(o_kf + sizeof(int32_t) * E), o_keys = up16(o_idx + sizeof(int32_t) * E),
-                 o_ur = up16(o_keys + sizeof(KeyPointPOD) * std::max<size_t>(n_keys, 1)), bytes = up16(o_ur + sizeof(float) * std::max<size_t>(n_keys, 1));
-    if (ctx->lba_sync.ensure(bytes)) return orbfe_fail(ctx, ORBFE_ERR_HIP, "bundle adjustment staging allocation failed");
-    std::vector<uint8_t> host(bytes, 0);
-    uint8_t *hb = host.data(), *db = (uint8_t *)ctx->lba_sync.p;
+    // the staging block: results first, then the inputs
+    orbfe::StageLayout L;
+    const auto f_info = L.result<orbfe_lba_info>(1); const auto f_cnt = L.result<int32_t>(2); // n_erase, status
+    const auto f_T = L.result<float>(n_kfs, 16); const auto f_pos = L.result<float>(n_rows, 3); const auto f_okf = L.result<orbfe_obs_keyframe>(n_kfs);
+    const auto f_code = L.result<uint8_t>(n_obs); const auto f_chi = L.result<double>(n_obs); const auto f_erase = L.result<int32_t>(n_obs, 2);
+    const auto f_rec = L.input<orbfe_ba_keyframe>(n_kfs); const auto f_role = L.input<uint8_t>(n_kfs); const auto f_row = L.input<int32_t>(n_pts);
+    const auto f_off = L.input<int32_t>((size_t)n_pts + 1); const auto f_kf = L.input<int32_t>(n_obs); const auto f_idx = L.input<int32_t>(n_obs);
+    const auto f_keys = L.input<orbfe_keypoint>(n_keys); const auto f_ur = L.input<float>(n_keys);
+    if (ctx->sync_stage.ensure(L.bytes())) return orbfe_fail(ctx, ORBFE_ERR_HIP, "bundle adjustment staging allocation failed");
+    StageBlock blk(L, ctx->sync_stage);
     if (n_kfs > 0) {
-        memcpy(hb + o_T, Tcw, sizeof(float) * 16 * n_kfs);
-        memcpy(hb + o_role, role, n_kfs);
-        orbfe_ba_keyframe *rec = (orbfe_ba_keyframe *)(hb + o_rec);
+        blk.put(f_T, Tcw, 16 * (size_t)n_kfs);
+        blk.put(f_role, role, n_kfs);
+        orbfe_ba_keyframe *rec = blk.host(f_rec);
         size_t at = 0;
         for (int k = 0; k < n_kfs; k++) {
-            rec[k].keys_un = (const orbfe_keypoint *)(db + o_keys) + at;
-            rec[k].u_right = (const float *)(db + o_ur) + at;
+            rec[k].keys_un = blk.dev(f_keys) + at;
+            rec[k].u_right = blk.dev(f_ur) + at;
             rec[k].n = kf_n[k];
-            if (kf_n[k] > 0) {
-                memcpy(hb + o_keys + sizeof(KeyPointPOD) * at, keys_un[k], sizeof(KeyPointPOD) * kf_n[k]);
-                memcpy(hb + o_ur + sizeof(float) * at, u_right[k], sizeof(float) * kf_n[k]);
-            }
+            blk.put(f_keys, keys_un[k], kf_n[k], at);
+            blk.put(f_ur, u_right[k], kf_n[k], at);
             at += (size_t)kf_n[k];
         }
     }
-    if (n_rows > 0 && pos) memcpy(hb + o_pos, pos, sizeof(float) * 3 * n_rows);
+    if (pos) blk.put(f_pos, pos, 3 * (size_t)n_rows);
     if (n_pts > 0) {
-        if (row) memcpy(hb + o_row, row, sizeof(int32_t) * n_pts);
-        memcpy(hb + o_off, obs_off, sizeof(int32_t) * ((size_t)n_pts + 1));
+        if (row) blk.put(f_row, row, n_pts);
+        blk.put(f_off, obs_off, (size_t)n_pts + 1);
     }
-    if (n_obs > 0) {
-        memcpy(hb + o_kf, obs_kf, sizeof(int32_t) * n_obs);
-        memcpy(hb + o_idx, obs_idx, sizeof(int32_t) * n_obs);
-    }
-    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, s));
-    const int rc = orbfe_enqueue_local_bundle_adjustment(ctx, (const orbfe_ba_keyframe *)(db + o_rec), db + o_role, n_kfs, max_free, (float *)(db + o_T), n_pts,
-                                                         row ? (const int32_t *)(db + o_row) : nullptr, n_rows, (const int32_t *)(db + o_off),
-                                                         (const int32_t *)(db + o_kf), (const int32_t *)(db + o_idx), n_obs, (float *)(db + o_pos),
-                                                         Ow ? (orbfe_obs_keyframe *)(db + o_okf) : nullptr, db + o_code, edge_chi2 ? (double *)(db + o_chi) : nullptr,
-                                                         (int32_t *)(db + o_erase), (int32_t *)(db + o_cnt), (orbfe_lba_info *)(db + o_info),
-                                                         (int32_t *)(db + o_cnt) + 1, nullptr);
+    blk.put(f_kf, obs_kf, n_obs); blk.put(f_idx, obs_idx, n_obs);
+    ORBFE_HIP_TRY(ctx, blk.upload(s));
+    const int rc = orbfe_enqueue_local_bundle_adjustment(ctx, blk.dev(f_rec), blk.dev(f_role), n_kfs, max_free, blk.dev(f_T), n_pts, row ? blk.dev(f_row) : nullptr, n_rows,
+                                                         blk.dev(f_off), blk.dev(f_kf), blk.dev(f_idx), n_obs, blk.dev(f_pos), Ow ? blk.dev(f_okf) : nullptr,
+                                                         blk.dev(f_code), edge_chi2 ? blk.dev(f_chi) : nullptr, blk.dev(f_erase), blk.dev(f_cnt), blk.dev(f_info),
+                                                         blk.dev(f_cnt) + 1, nullptr);
     if (rc != ORBFE_OK) return rc;
-    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(hb, db, down, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP_TRY(ctx, blk.download(s));
     ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
     int32_t cnt[2];
-    memcpy(cnt, hb + o_cnt, sizeof(cnt));
-    memcpy(info, hb + o_info, sizeof(orbfe_lba_info));
+    blk.get(f_cnt, cnt, 2); blk.get(f_info, info, 1);
     *n_erase = cnt[0];
-    if (n_kfs > 0) memcpy(Tcw, hb + o_T, sizeof(float) * 16 * n_kfs);
-    if (n_rows > 0 && pos) memcpy(pos, hb + o_pos, sizeof(float) * 3 * n_rows);
+    blk.get(f_T, Tcw, 16 * (size_t)n_kfs);
+    if (pos) blk.get(f_pos, pos, 3 * (size_t)n_rows);
     if (Ow && info->n_mono + info->n_stereo > 0 && cnt[1] != ORBFE_ERR_CAPACITY) { // a call without an edge rewrites no keyframe
-        const orbfe_obs_keyframe *okf = (const orbfe_obs_keyframe *)(hb + o_okf);
+        const orbfe_obs_keyframe *okf = blk.host(f_okf);
         for (int k = 0; k < n_kfs; k++)
             if (role[k] == ORBFE_BA_LOCAL || role[k] == ORBFE_BA_LOCAL_HELD) memcpy(Ow + 3 * (size_t)k, okf[k].Ow, sizeof(float) * 3);
     }
-    if (n_obs > 0) {
-        memcpy(edge_code, hb + o_code, n_obs);
-        if (edge_chi2) memcpy(edge_chi2, hb + o_chi, sizeof(double) * n_obs);
-        memcpy(erase, hb + o_erase, sizeof(int32_t) * 2 * n_obs);
-    }
+    blk.get(f_code, edge_code, n_obs);
+    if (edge_chi2) blk.get(f_chi, edge_chi2, n_obs);
+    blk.get(f_erase, erase, 2 * (size_t)n_obs);
     if (cnt[1] == ORBFE_ERR_CAPACITY) return orbfe_fail(ctx, cnt[1], "more free keyframes than the bound");
     if (cnt[1] != 0) return orbfe_fail(ctx, cnt[1], "a faulty observation, point or role (see the edge codes)");
     return ORBFE_OK;

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "../../include/orbfe.h"
+#include "orbfe_arena.hpp"
 #include "orbfe_pose_blocks.hpp" // Se3, CamD, se3_*, edge_error, and this stage's fp contract(fast) pragma
 
 #pragma clang fp contract(fast)
@@ -859,26 +860,14 @@ __global__ __launch_bounds__(LBA_THREADS) void lba_kernel(const LbaArgs a)
 inline size_t lba_carve(LbaArgs &a, uint8_t *b, bool with_system)
 {
     const size_t E = (size_t)a.n_obs, N = (size_t)a.n_pts, K = (size_t)a.n_kfs, F = (size_t)a.max_free;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = (off + (bytes < 8 ? 8 : bytes) + 255) & ~(size_t)255; return o; };
-    const size_t o_lin = take(sizeof(double) * LBA_LIN * E), o_w = take(sizeof(double) * LBA_W * E), o_chi_a = take(sizeof(double) * E),
-                 o_chi_b = take(sizeof(double) * E), o_chi_f = take(sizeof(double) * E), o_pose_e = take(sizeof(double) * 8 * K),
-                 o_pose_t = take(sizeof(double) * 8 * K), o_fH = take(sizeof(double) * 27 * F), o_fx = take(sizeof(double) * 6 * F),
-                 o_Xe = take(sizeof(double) * 3 * N), o_Xt = take(sizeof(double) * 3 * N), o_plin = take(sizeof(double) * LBA_PT * N),
-                 o_pdinv = take(sizeof(double) * 9 * N), o_pxl = take(sizeof(double) * 3 * N), o_sys = take(with_system ? lba_system_bytes(a.max_free) : 0),
-                 o_eobs = take(sizeof(float) * 4 * E), o_ekf = take(sizeof(int32_t) * E), o_ept = take(sizeof(int32_t) * E),
-                 o_sorted = take(sizeof(int32_t) * E), o_cnt = take(sizeof(int32_t) * LBA_THREADS * F), o_kffree = take(sizeof(int32_t) * K),
-                 o_fkf = take(sizeof(int32_t) * F), o_fstart = take(sizeof(int32_t) * (F + 1)), o_fred = take(sizeof(int32_t) * F),
-                 o_ered = take(sizeof(int32_t) * E), o_eflag = take(E), o_pflag = take(N);
-    if (!b) return off;
-    a.e_lin = (double *)(b + o_lin); a.e_w = (double *)(b + o_w); a.chi_a = (double *)(b + o_chi_a); a.chi_b = (double *)(b + o_chi_b);
-    a.chi_f = (double *)(b + o_chi_f); a.pose_e = (double *)(b + o_pose_e); a.pose_t = (double *)(b + o_pose_t); a.f_H = (double *)(b + o_fH);
-    a.f_x = (double *)(b + o_fx); a.X_e = (double *)(b + o_Xe); a.X_t = (double *)(b + o_Xt); a.p_lin = (double *)(b + o_plin);
-    a.p_dinv = (double *)(b + o_pdinv); a.p_xl = (double *)(b + o_pxl); a.system = (double *)(b + o_sys); a.e_obs = (float *)(b + o_eobs);
-    a.e_kf = (int32_t *)(b + o_ekf); a.e_pt = (int32_t *)(b + o_ept); a.sorted = (int32_t *)(b + o_sorted); a.cnt = (int32_t *)(b + o_cnt);
-    a.kf_free = (int32_t *)(b + o_kffree); a.f_kf = (int32_t *)(b + o_fkf); a.f_start = (int32_t *)(b + o_fstart); a.f_red = (int32_t *)(b + o_fred);
-    a.e_red = (int32_t *)(b + o_ered); a.e_flag = b + o_eflag; a.p_flag = b + o_pflag;
-    return off;
+    orbfe::Arena c(b, 256, 8);
+    a.e_lin = c.take<double>(LBA_LIN * E); a.e_w = c.take<double>(LBA_W * E); a.chi_a = c.take<double>(E); a.chi_b = c.take<double>(E); a.chi_f = c.take<double>(E);
+    a.pose_e = c.take<double>(8 * K); a.pose_t = c.take<double>(8 * K); a.f_H = c.take<double>(27 * F); a.f_x = c.take<double>(6 * F); a.X_e = c.take<double>(3 * N);
+    a.X_t = c.take<double>(3 * N); a.p_lin = c.take<double>(LBA_PT * N); a.p_dinv = c.take<double>(9 * N); a.p_xl = c.take<double>(3 * N);
+    a.system = c.take<double>(with_system ? lba_system_bytes(a.max_free) / sizeof(double) : 0); a.e_obs = c.take<float>(4 * E); a.e_kf = c.take<int32_t>(E);
+    a.e_pt = c.take<int32_t>(E); a.sorted = c.take<int32_t>(E); a.cnt = c.take<int32_t>(LBA_THREADS * F); a.kf_free = c.take<int32_t>(K); a.f_kf = c.take<int32_t>(F);
+    a.f_start = c.take<int32_t>(F + 1); a.f_red = c.take<int32_t>(F); a.e_red = c.take<int32_t>(E); a.e_flag = c.take<uint8_t>(E); a.p_flag = c.take<uint8_t>(N);
+    return c.bytes();
 }
 
 } // namespace

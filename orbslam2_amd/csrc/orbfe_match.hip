@@ -185,16 +185,17 @@ static int run_window_queries(orbfe_context *ctx, const orbfe_frame_view *fv, co
         if (rc != ORBFE_OK) return rc;
         if (n != slot_n) return orbfe_fail(ctx, ORBFE_ERR_INVALID, "frame view holds %d keypoints, device slot %d holds %d (not the latest extraction?)", n, slot, slot_n);
     }
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t fn = resident ? 0 : (size_t)n; // frame rows in the upload block
-    const size_t i_keys = 0, i_desc = up16(i_keys + sizeof(KeyPointPOD) * fn), i_ur = up16(i_desc + (size_t)32 * fn);
-    const size_t i_q = up16(i_ur + (fv->u_right ? sizeof(float) * (size_t)n : 0)), i_qd = up16(i_q + sizeof(MatchQuery) * nq), i_blk = up16(i_qd + (size_t)32 * nq);
-    const size_t in_bytes = up16(i_blk + (topk && topk->blocked0 ? (size_t)n : 0));
+    // the upload block: the frame's rows (none of a resident frame), mvuRight, the queries, the blocked flags
+    const size_t fn = resident ? 0 : (size_t)n;
+    orbfe::Arena in(nullptr, 16, 0), out(nullptr, 16, 0);
+    const size_t i_keys = in.take_bytes(sizeof(KeyPointPOD), fn), i_desc = in.take_bytes(32, fn), i_ur = in.take_bytes(sizeof(float), fv->u_right ? (size_t)n : 0),
+                 i_q = in.take_bytes(sizeof(MatchQuery), nq), i_qd = in.take_bytes(32, nq), i_blk = in.take_bytes(1, topk && topk->blocked0 ? (size_t)n : 0);
+    const size_t in_bytes = in.bytes();
     // results: [cursor | n_static | top-K keys] are what a top-K replay needs; [offsets | counts] follow and are only downloaded
     // with the full list
-    const size_t o_cur = 0, o_ns = 16, o_tk = up16(o_ns + sizeof(int) * nq), o_off = up16(o_tk + sizeof(unsigned long long) * MATCH_TOPK * nq);
-    const size_t o_cnt = up16(o_off + sizeof(int) * nq), out_bytes = up16(o_cnt + sizeof(int) * nq);
-    const size_t topk_bytes = o_off; // prefix of the result block a top-K replay downloads
+    const size_t o_cur = out.take_bytes(sizeof(int), 1), o_ns = out.take_bytes(sizeof(int), nq), o_tk = out.take_bytes(sizeof(unsigned long long), (size_t)MATCH_TOPK * nq),
+                 o_off = out.take_bytes(sizeof(int), nq), o_cnt = out.take_bytes(sizeof(int), nq);
+    const size_t out_bytes = out.bytes(), topk_bytes = o_off; // topk_bytes: the prefix of the result block a top-K replay downloads
     if (st->in_blk.ensure(in_bytes) || st->out_blk.ensure(out_bytes) || st->cells.ensure(sizeof(int) * (size_t)(GRID_CELLS + 1 + n)))
         return orbfe_fail(ctx, ORBFE_ERR_HIP, "matcher scratch allocation failed");
     int rc = ensure_pinned(ctx, st->h_in, st->h_in_bytes, in_bytes);

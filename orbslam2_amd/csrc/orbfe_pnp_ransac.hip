@@ -481,55 +481,40 @@ try {
     hipStream_t s;
     if (const int rc = orbfe_enqueue_on(ctx, nullptr, false, &s)) return rc;
     const int cap = std::max(n_keys, 1), words = (cap + 31) / 32;
-    // block layout: results first (copied back in one piece), then the inputs
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t mk = (size_t)cap, mf = (size_t)std::max(n_kf, 1), rows = (size_t)words * max_its;
-    const size_t o_cnt = 0, o_corr = up16(o_cnt + sizeof(int32_t) * 8), o_sets = up16(o_corr + sizeof(int32_t) * 2 * mk);
-    const size_t o_hyp = up16(o_sets + sizeof(int32_t) * 4 * max_its), o_bits = up16(o_hyp + sizeof(orbfe_pnp_hypothesis) * max_its);
-    const size_t o_ref = up16(o_bits + sizeof(uint32_t) * rows), o_rbits = up16(o_ref + sizeof(orbfe_pnp_refined) * max_its);
-    const size_t o_ev = up16(o_rbits + sizeof(uint32_t) * rows), down = up16(o_ev + sizeof(int32_t) * max_its);
-    const size_t o_rec = down, o_nk = up16(o_rec + sizeof(orbfe_pnp_candidate)), o_keys = up16(o_nk + sizeof(int32_t));
-    const size_t o_fm = up16(o_keys + sizeof(KeyPointPOD) * mk), o_pos = up16(o_fm + sizeof(int32_t) * mk), o_val = up16(o_pos + sizeof(float) * 3 * mf);
-    const size_t o_draws = up16(o_val + sizeof(int32_t) * mf), o_tab = up16(o_draws + sizeof(uint32_t) * 4 * max_its);
-    const size_t bytes = up16(o_tab + sizeof(int32_t) * (mk + 1));
-    if (ctx->pnp_ransac_sync.ensure(bytes)) return orbfe_fail(ctx, ORBFE_ERR_HIP, "PnP RANSAC staging allocation failed");
-    std::vector<uint8_t> host(bytes, 0);
-    uint8_t *hb = host.data(), *db = (uint8_t *)ctx->pnp_ransac_sync.p;
-    if (n_keys > 0) {
-        memcpy(hb + o_keys, keys_un, sizeof(KeyPointPOD) * n_keys);
-        memcpy(hb + o_fm, f_match, sizeof(int32_t) * n_keys);
-    }
-    if (n_kf > 0) {
-        memcpy(hb + o_pos, pos, sizeof(float) * 3 * n_kf);
-        memcpy(hb + o_val, valid, sizeof(int32_t) * n_kf);
-    }
-    memcpy(hb + o_draws, draws, sizeof(uint32_t) * 4 * max_its);
-    memcpy(hb + o_tab, its_for_n, sizeof(int32_t) * ((size_t)n_keys + 1)); // the table covers N <= n_keys
+    // the staging block: results first, then the inputs
+    const size_t its = (size_t)max_its;
+    orbfe::StageLayout L;
+    const auto f_cnt = L.result<int32_t>(8); // n_corr, n_its, n_events, exhausted, status
+    const auto f_corr = L.result<int32_t>(cap, 2); const auto f_sets = L.result<int32_t>(its, 4); const auto f_hyp = L.result<orbfe_pnp_hypothesis>(its);
+    const auto f_bits = L.result<uint32_t>(its, words); const auto f_ref = L.result<orbfe_pnp_refined>(its); const auto f_rbits = L.result<uint32_t>(its, words);
+    const auto f_ev = L.result<int32_t>(its);
+    const auto f_rec = L.input<orbfe_pnp_candidate>(1); const auto f_nk = L.input<int32_t>(1);
+    const auto f_keys = L.input<KeyPointPOD>(n_keys); const auto f_fm = L.input<int32_t>(n_keys); const auto f_pos = L.input<float>(n_kf, 3);
+    const auto f_val = L.input<int32_t>(n_kf); const auto f_draws = L.input<uint32_t>(its, 4); const auto f_tab = L.input<int32_t>((size_t)cap + 1);
+    if (ctx->sync_stage.ensure(L.bytes())) return orbfe_fail(ctx, ORBFE_ERR_HIP, "PnP RANSAC staging allocation failed");
+    StageBlock blk(L, ctx->sync_stage);
+    blk.put(f_keys, keys_un, n_keys); blk.put(f_fm, f_match, n_keys); blk.put(f_pos, pos, 3 * (size_t)n_kf); blk.put(f_val, valid, n_kf);
+    blk.put(f_draws, draws, 4 * its); blk.put(f_tab, its_for_n, (size_t)n_keys + 1); // the table covers N <= n_keys
     const int32_t nk32 = n_keys;
-    memcpy(hb + o_nk, &nk32, sizeof(nk32));
+    blk.put(f_nk, &nk32, 1);
     orbfe_pnp_candidate rec = {};
-    rec.f_match = (const int32_t *)(db + o_fm); rec.pos = (const float *)(db + o_pos); rec.valid = (const int32_t *)(db + o_val);
-    rec.draws = (const uint32_t *)(db + o_draws); rec.n = n_kf;
-    memcpy(hb + o_rec, &rec, sizeof(rec));
-    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, s));
-    int32_t *cnt = (int32_t *)(db + o_cnt); // n_corr, n_its, n_events, exhausted, status
-    const int rc = enqueue_impl(ctx, s, (const KeyPointPOD *)(db + o_keys), (const int32_t *)(db + o_nk), cap, (const orbfe_pnp_candidate *)(db + o_rec), 1, n_kf,
-                                min_inliers, max_its, n_iterations, epsilon, th2, (const int32_t *)(db + o_tab), cnt, cnt + 1, (int32_t *)(db + o_corr),
-                                (int32_t *)(db + o_sets), (orbfe_pnp_hypothesis *)(db + o_hyp), (uint32_t *)(db + o_bits), (orbfe_pnp_refined *)(db + o_ref),
-                                (uint32_t *)(db + o_rbits), (int32_t *)(db + o_ev), cnt + 2, cnt + 3, cnt + 4);
+    rec.f_match = blk.dev(f_fm); rec.pos = blk.dev(f_pos); rec.valid = blk.dev(f_val); rec.draws = blk.dev(f_draws); rec.n = n_kf;
+    blk.put(f_rec, &rec, 1);
+    ORBFE_HIP_TRY(ctx, blk.upload(s));
+    int32_t *cnt = blk.dev(f_cnt);
+    const int rc = enqueue_impl(ctx, s, blk.dev(f_keys), blk.dev(f_nk), cap, blk.dev(f_rec), 1, n_kf, min_inliers, max_its, n_iterations, epsilon, th2, blk.dev(f_tab), cnt,
+                                cnt + 1, blk.dev(f_corr), blk.dev(f_sets), blk.dev(f_hyp), blk.dev(f_bits), blk.dev(f_ref), blk.dev(f_rbits), blk.dev(f_ev), cnt + 2,
+                                cnt + 3, cnt + 4);
     if (rc != ORBFE_OK) return rc;
-    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(hb, db, down, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP_TRY(ctx, blk.download(s));
     ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
     int32_t c5[5];
-    memcpy(c5, hb + o_cnt, sizeof(c5));
+    blk.get(f_cnt, c5, 5);
     *n_corr = c5[0]; *n_its = c5[1]; *n_events = c5[2]; *exhausted = c5[3];
-    memcpy(corr, hb + o_corr, sizeof(int32_t) * 2 * mk);
-    if (sets) memcpy(sets, hb + o_sets, sizeof(int32_t) * 4 * max_its);
-    memcpy(hyp, hb + o_hyp, sizeof(orbfe_pnp_hypothesis) * max_its);
-    memcpy(inlier_bits, hb + o_bits, sizeof(uint32_t) * rows);
-    memcpy(refined, hb + o_ref, sizeof(orbfe_pnp_refined) * max_its);
-    memcpy(refined_bits, hb + o_rbits, sizeof(uint32_t) * rows);
-    memcpy(events, hb + o_ev, sizeof(int32_t) * max_its);
+    blk.get(f_corr, corr, f_corr.count);
+    if (sets) blk.get(f_sets, sets, f_sets.count);
+    blk.get(f_hyp, hyp, f_hyp.count); blk.get(f_bits, inlier_bits, f_bits.count); blk.get(f_ref, refined, f_ref.count); blk.get(f_rbits, refined_bits, f_rbits.count);
+    blk.get(f_ev, events, f_ev.count);
     if (c5[4] != 0) return orbfe_fail(ctx, c5[4], "a match index out of range or a keypoint octave outside the context's %d levels", ctx->params.nlevels);
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)

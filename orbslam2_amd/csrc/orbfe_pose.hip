@@ -291,13 +291,13 @@ try {
     orbfe_pose_state *st = orbfe_ctx_pose_state(ctx);
     hipStream_t s;
     if (const int rc = orbfe_enqueue_on(ctx, nullptr, false, &s)) return rc;
-    const size_t tn = (size_t)(total > 0 ? total : 1);
-    // block layout: results first ([Tcw | n_inliers | outlier], copied back in one piece), then the inputs
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_T = 0, o_n = up16(o_T + sizeof(float) * 16 * n_problems), o_out = up16(o_n + sizeof(int32_t) * n_problems);
-    const size_t o_off = up16(o_out + tn), o_keys = up16(o_off + sizeof(int32_t) * (n_problems + 1));
-    const size_t o_ur = up16(o_keys + sizeof(KeyPointPOD) * tn), o_has = up16(o_ur + sizeof(float) * tn), o_xw = up16(o_has + tn);
-    const size_t bytes = up16(o_xw + sizeof(float) * 3 * tn), down = o_off;
+    // the staging block: results first, then the inputs; its host image is the state's pinned block, kept between calls
+    const size_t np = (size_t)n_problems, tn = (size_t)total;
+    orbfe::StageLayout L;
+    const auto f_T = L.result<float>(np, 16); const auto f_n = L.result<int32_t>(np); const auto f_out = L.result<uint8_t>(tn);
+    const auto f_off = L.input<int32_t>(np + 1); const auto f_keys = L.input<orbfe_keypoint>(tn); const auto f_ur = L.input<float>(tn);
+    const auto f_has = L.input<uint8_t>(tn); const auto f_xw = L.input<float>(tn, 3);
+    const size_t bytes = L.bytes();
     if (st->blk.ensure(bytes)) return orbfe_fail(ctx, ORBFE_ERR_HIP, "pose scratch allocation failed");
     if (st->h_bytes < bytes) {
         if (st->h_blk) (void)hipHostFree(st->h_blk);
@@ -305,28 +305,18 @@ try {
         ORBFE_HIP_TRY(ctx, hipHostMalloc((void **)&st->h_blk, bytes, hipHostMallocDefault));
         st->h_bytes = bytes;
     }
-    uint8_t *hb = st->h_blk, *db = (uint8_t *)st->blk.p;
-    memcpy(hb + o_T, Tcw, sizeof(float) * 16 * n_problems);
-    memcpy(hb + o_off, offsets, sizeof(int32_t) * (n_problems + 1));
-    if (total > 0) {
-        memcpy(hb + o_out, outlier, tn); // entries without a point keep the caller's value
-        memcpy(hb + o_keys, keys_un, sizeof(KeyPointPOD) * tn);
-        memcpy(hb + o_ur, u_right, sizeof(float) * tn);
-        memcpy(hb + o_has, has_point, tn);
-        memcpy(hb + o_xw, Xw, sizeof(float) * 3 * tn);
-    }
-    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, s));
-    int rc = orbfe_enqueue_pose_optimization(ctx, n_problems, (const int32_t *)(db + o_off), (const orbfe_keypoint *)(db + o_keys), (const float *)(db + o_ur),
-                                             (const uint8_t *)(db + o_has), (const float *)(db + o_xw), (float *)(db + o_T), db + o_out,
-                                             (int32_t *)(db + o_n), max_n, nullptr);
+    StageBlock blk(L, st->blk, st->h_blk);
+    blk.put(f_T, Tcw, 16 * np); blk.put(f_off, offsets, np + 1); blk.put(f_out, outlier, tn); // entries without a point keep the caller's value
+    blk.put(f_keys, keys_un, tn); blk.put(f_ur, u_right, tn); blk.put(f_has, has_point, tn); blk.put(f_xw, Xw, 3 * tn);
+    ORBFE_HIP_TRY(ctx, blk.upload(s));
+    int rc = orbfe_enqueue_pose_optimization(ctx, n_problems, blk.dev(f_off), blk.dev(f_keys), blk.dev(f_ur), blk.dev(f_has), blk.dev(f_xw), blk.dev(f_T),
+                                             blk.dev(f_out), blk.dev(f_n), max_n, nullptr);
     if (rc != ORBFE_OK) return rc;
-    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(hb, db, down, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP_TRY(ctx, blk.download(s));
     ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
     // problems with fewer than 3 correspondences leave their pose untouched on the device (the reference returns
     // before SetPose, src/Optimizer.cc:404-405)
-    memcpy(Tcw, hb + o_T, sizeof(float) * 16 * n_problems);
-    memcpy(n_inliers, hb + o_n, sizeof(int32_t) * n_problems);
-    if (total > 0) memcpy(outlier, hb + o_out, tn);
+    blk.get(f_T, Tcw, 16 * np); blk.get(f_n, n_inliers, np); blk.get(f_out, outlier, tn);
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)
 

@@ -479,12 +479,12 @@ try {
     if (const int rc = orbfe_enqueue_on(ctx, nullptr, false, &s)) return rc;
     // one device block: inputs, then outputs
     const size_t kb1 = sizeof(orbfe_keypoint) * (size_t)n1, kb2 = sizeof(orbfe_keypoint) * (size_t)n2, nn = (size_t)N;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 15) & ~(size_t)15; return o; };
-    const size_t o_k1 = take(kb1), o_k2 = take(kb2), o_pairs = take(8 * nn), o_in = take(24 * 4), o_ih = take(nn), o_if = take(nn), o_small = take(160 * 4),
-                 o_p3d = take(12 * (size_t)n1), o_tri = take(n1), o_codes = take(codes ? 8 * nn : 0);
-    if (ctx->recon_sync.ensure(off) != 0) return orbfe_fail(ctx, ORBFE_ERR_HIP, "reconstruct_initial: device allocation failed");
-    uint8_t *d = (uint8_t *)ctx->recon_sync.p;
+    orbfe::Arena c(nullptr, 16, 0);
+    const size_t o_k1 = c.take_bytes(1, kb1), o_k2 = c.take_bytes(1, kb2), o_pairs = c.take_bytes(8, nn), o_in = c.take_bytes(4, 24), o_ih = c.take_bytes(1, nn),
+                 o_if = c.take_bytes(1, nn), o_small = c.take_bytes(4, 160), o_p3d = c.take_bytes(12, n1), o_tri = c.take_bytes(1, n1),
+                 o_codes = c.take_bytes(8, codes ? nn : 0);
+    if (ctx->sync_stage.ensure(c.bytes()) != 0) return orbfe_fail(ctx, ORBFE_ERR_HIP, "reconstruct_initial: device allocation failed");
+    uint8_t *d = (uint8_t *)ctx->sync_stage.p;
     if (kb1) ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d + o_k1, keys1_un, kb1, hipMemcpyHostToDevice, s));
     if (kb2) ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d + o_k2, keys2_un, kb2, hipMemcpyHostToDevice, s));
     ORBFE_HIP_TRY(ctx, hipMemcpyAsync(d + o_pairs, pairs, 8 * nn, hipMemcpyHostToDevice, s));

@@ -349,46 +349,34 @@ try {
         return orbfe_fail(ctx, ORBFE_ERR_INVALID, "every field of orbfe_sim3_opt_params must be at least 1");
     hipStream_t s;
     if (const int rc = orbfe_enqueue_on(ctx, nullptr, false, &s)) return rc;
-    // block layout: results first ([S12 | n_inliers, status | match12], copied back in one piece), then the inputs
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t m1 = (size_t)std::max(n1, 1), m2 = (size_t)std::max(n2, 1);
-    const size_t o_S = 0, o_cnt = up16(o_S + sizeof(double) * 8), o_match = up16(o_cnt + sizeof(int32_t) * 2);
-    const size_t o_prior = up16(o_match + sizeof(int32_t) * m1), down = o_prior;
-    const size_t o_k1 = up16(o_prior + sizeof(int32_t) * m1), o_k2 = up16(o_k1 + sizeof(KeyPointPOD) * m1);
-    const size_t o_p1 = up16(o_k2 + sizeof(KeyPointPOD) * m2), o_p2 = up16(o_p1 + sizeof(float) * 3 * m1);
-    const size_t o_v1 = up16(o_p2 + sizeof(float) * 3 * m2), o_v2 = up16(o_v1 + sizeof(int32_t) * m1);
-    const size_t bytes = up16(o_v2 + sizeof(int32_t) * m2);
-    if (ctx->sim3_opt_sync.ensure(bytes)) return orbfe_fail(ctx, ORBFE_ERR_HIP, "Sim3 optimisation staging allocation failed");
-    std::vector<uint8_t> host(bytes, 0);
-    uint8_t *hb = host.data(), *db = (uint8_t *)ctx->sim3_opt_sync.p;
-    if (n1 > 0) {
-        memcpy(hb + o_match, match12, sizeof(int32_t) * n1);
-        if (prior12) memcpy(hb + o_prior, prior12, sizeof(int32_t) * n1);
-        memcpy(hb + o_k1, keys_un1, sizeof(KeyPointPOD) * n1);
-        memcpy(hb + o_p1, pos1, sizeof(float) * 3 * n1);
-        memcpy(hb + o_v1, valid1, sizeof(int32_t) * n1);
-    }
-    if (n2 > 0) {
-        memcpy(hb + o_k2, keys_un2, sizeof(KeyPointPOD) * n2);
-        memcpy(hb + o_p2, pos2, sizeof(float) * 3 * n2);
-        memcpy(hb + o_v2, valid2, sizeof(int32_t) * n2);
-    }
-    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, s));
+    // the staging block: results first, then the inputs
+    orbfe::StageLayout L;
+    const auto f_S = L.result<double>(8); const auto f_cnt = L.result<int32_t>(2); // n_inliers, status
+    const auto f_match = L.result<int32_t>(n1);
+    const auto f_prior = L.input<int32_t>(n1); const auto f_k1 = L.input<orbfe_keypoint>(n1);
+    const auto f_k2 = L.input<orbfe_keypoint>(n2); const auto f_p1 = L.input<float>(n1, 3); const auto f_p2 = L.input<float>(n2, 3);
+    const auto f_v1 = L.input<int32_t>(n1); const auto f_v2 = L.input<int32_t>(n2);
+    if (ctx->sync_stage.ensure(L.bytes())) return orbfe_fail(ctx, ORBFE_ERR_HIP, "Sim3 optimisation staging allocation failed");
+    StageBlock blk(L, ctx->sync_stage);
+    blk.put(f_match, match12, n1);
+    if (prior12) blk.put(f_prior, prior12, n1);
+    blk.put(f_k1, keys_un1, n1); blk.put(f_p1, pos1, 3 * (size_t)n1); blk.put(f_v1, valid1, n1);
+    blk.put(f_k2, keys_un2, n2); blk.put(f_p2, pos2, 3 * (size_t)n2); blk.put(f_v2, valid2, n2);
+    ORBFE_HIP_TRY(ctx, blk.upload(s));
     orbfe_grid_keyframe kf1 = {}, kf2 = {}; // only keys_un and n are read
-    kf1.keys_un = (const orbfe_keypoint *)(db + o_k1); kf1.n = n1;
-    kf2.keys_un = (const orbfe_keypoint *)(db + o_k2); kf2.n = n2;
-    const int rc = orbfe_enqueue_optimize_sim3(ctx, &kf1, T1w, (const float *)(db + o_p1), (const int32_t *)(db + o_v1), &kf2, T2w, (const float *)(db + o_p2),
-                                               (const int32_t *)(db + o_v2), s12, R12, t12, th2, fix_scale, params,
-                                               prior12 ? (const int32_t *)(db + o_prior) : nullptr, (int32_t *)(db + o_match), (double *)(db + o_S),
-                                               (int32_t *)(db + o_cnt), (int32_t *)(db + o_cnt) + 1, nullptr);
+    kf1.keys_un = blk.dev(f_k1); kf1.n = n1;
+    kf2.keys_un = blk.dev(f_k2); kf2.n = n2;
+    const int rc = orbfe_enqueue_optimize_sim3(ctx, &kf1, T1w, blk.dev(f_p1), blk.dev(f_v1), &kf2, T2w, blk.dev(f_p2), blk.dev(f_v2), s12, R12, t12, th2, fix_scale,
+                                               params, prior12 ? blk.dev(f_prior) : nullptr, blk.dev(f_match), blk.dev(f_S), blk.dev(f_cnt), blk.dev(f_cnt) + 1,
+                                               nullptr);
     if (rc != ORBFE_OK) return rc;
-    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(hb, db, down, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP_TRY(ctx, blk.download(s));
     ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
-    memcpy(S12, hb + o_S, sizeof(double) * 8);
+    blk.get(f_S, S12, 8);
     int32_t cnt[2];
-    memcpy(cnt, hb + o_cnt, sizeof(cnt));
+    blk.get(f_cnt, cnt, 2);
     *n_inliers = cnt[0];
-    if (n1 > 0) memcpy(match12, hb + o_match, sizeof(int32_t) * n1);
+    blk.get(f_match, match12, n1);
     if (cnt[1] != 0) return orbfe_fail(ctx, cnt[1], "a match12 / prior12 entry outside [-1, n2) or a keypoint octave outside the context's %d levels", ctx->params.nlevels);
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)

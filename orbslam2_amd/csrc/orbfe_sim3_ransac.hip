@@ -513,63 +513,45 @@ try {
     hipStream_t s;
     if (const int rc = orbfe_enqueue_on(ctx, nullptr, false, &s)) return rc;
     const int max_pairs = std::max(n_pairs, 1), max_kf_n = std::max(n1, n2), words = (max_pairs + 31) / 32;
-    // block layout: results first (copied back in one piece), then the inputs
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t m1 = (size_t)std::max(n1, 1), m2 = (size_t)std::max(n2, 1);
-    const size_t o_cnt = 0, o_corr = up16(o_cnt + sizeof(int32_t) * 4), o_sets = up16(o_corr + sizeof(int32_t) * 2 * max_pairs);
-    const size_t o_hyp = up16(o_sets + sizeof(int32_t) * 3 * max_its), o_bits = up16(o_hyp + sizeof(orbfe_sim3_hypothesis) * max_its);
-    const size_t o_ev = up16(o_bits + sizeof(uint32_t) * (size_t)words * max_its), down = up16(o_ev + sizeof(int32_t) * max_its);
-    const size_t o_rec = down, o_np = up16(o_rec + sizeof(orbfe_sim3_ransac_candidate)), o_T2 = up16(o_np + sizeof(int32_t));
-    const size_t o_k1 = up16(o_T2 + sizeof(float) * 12), o_k2 = up16(o_k1 + sizeof(KeyPointPOD) * m1);
-    const size_t o_p1 = up16(o_k2 + sizeof(KeyPointPOD) * m2), o_p2 = up16(o_p1 + sizeof(float) * 3 * m1);
-    const size_t o_v1 = up16(o_p2 + sizeof(float) * 3 * m2), o_v2 = up16(o_v1 + sizeof(int32_t) * m1);
-    const size_t o_pairs = up16(o_v2 + sizeof(int32_t) * m2), o_draws = up16(o_pairs + sizeof(int32_t) * 2 * max_pairs);
-    const size_t o_tab = up16(o_draws + sizeof(uint32_t) * 3 * max_its), bytes = up16(o_tab + sizeof(int32_t) * ((size_t)max_pairs + 1));
-    if (ctx->sim3_ransac_sync.ensure(bytes)) return orbfe_fail(ctx, ORBFE_ERR_HIP, "Sim3 RANSAC staging allocation failed");
-    std::vector<uint8_t> host(bytes, 0);
-    uint8_t *hb = host.data(), *db = (uint8_t *)ctx->sim3_ransac_sync.p;
-    if (n1 > 0) {
-        memcpy(hb + o_k1, keys_un1, sizeof(KeyPointPOD) * n1);
-        memcpy(hb + o_p1, pos1, sizeof(float) * 3 * n1);
-        memcpy(hb + o_v1, valid1, sizeof(int32_t) * n1);
-    }
-    if (n2 > 0) {
-        memcpy(hb + o_k2, keys_un2, sizeof(KeyPointPOD) * n2);
-        memcpy(hb + o_p2, pos2, sizeof(float) * 3 * n2);
-        memcpy(hb + o_v2, valid2, sizeof(int32_t) * n2);
-    }
-    if (n_pairs > 0) memcpy(hb + o_pairs, pairs, sizeof(int32_t) * 2 * n_pairs);
-    memcpy(hb + o_draws, draws, sizeof(uint32_t) * 3 * max_its);
-    // the table covers N <= n_pairs; with n_pairs == 0 its entry 1 is never read
-    memcpy(hb + o_tab, its_for_n, sizeof(int32_t) * ((size_t)n_pairs + 1));
-    memcpy(hb + o_T2, T2w, sizeof(float) * 12);
+    // the staging block: results first, then the inputs
+    const size_t its = (size_t)max_its;
+    orbfe::StageLayout L;
+    const auto f_cnt = L.result<int32_t>(4); // n_corr, n_its, n_events, status
+    const auto f_corr = L.result<int32_t>(max_pairs, 2); const auto f_sets = L.result<int32_t>(its, 3); const auto f_hyp = L.result<orbfe_sim3_hypothesis>(its);
+    const auto f_bits = L.result<uint32_t>(its, words); const auto f_ev = L.result<int32_t>(its);
+    const auto f_rec = L.input<orbfe_sim3_ransac_candidate>(1);
+    const auto f_np = L.input<int32_t>(1); const auto f_T2 = L.input<float>(12); const auto f_k1 = L.input<orbfe_keypoint>(n1);
+    const auto f_k2 = L.input<orbfe_keypoint>(n2); const auto f_p1 = L.input<float>(n1, 3); const auto f_p2 = L.input<float>(n2, 3);
+    const auto f_v1 = L.input<int32_t>(n1); const auto f_v2 = L.input<int32_t>(n2); const auto f_pairs = L.input<int32_t>(n_pairs, 2);
+    const auto f_draws = L.input<uint32_t>(its, 3); const auto f_tab = L.input<int32_t>((size_t)max_pairs + 1);
+    if (ctx->sync_stage.ensure(L.bytes())) return orbfe_fail(ctx, ORBFE_ERR_HIP, "Sim3 RANSAC staging allocation failed");
+    StageBlock blk(L, ctx->sync_stage);
+    blk.put(f_k1, keys_un1, n1); blk.put(f_p1, pos1, 3 * (size_t)n1); blk.put(f_v1, valid1, n1);
+    blk.put(f_k2, keys_un2, n2); blk.put(f_p2, pos2, 3 * (size_t)n2); blk.put(f_v2, valid2, n2); blk.put(f_pairs, pairs, 2 * (size_t)n_pairs);
+    blk.put(f_draws, draws, 3 * its); blk.put(f_tab, its_for_n, (size_t)n_pairs + 1); // the table covers N <= n_pairs; with n_pairs == 0 its entry 1 is never read
+    blk.put(f_T2, T2w, 12);
     const int32_t np32 = n_pairs;
-    memcpy(hb + o_np, &np32, sizeof(np32));
+    blk.put(f_np, &np32, 1);
     orbfe_sim3_ransac_candidate rec = {};
-    rec.keys_un = (const orbfe_keypoint *)(db + o_k2); rec.pos = (const float *)(db + o_p2); rec.valid = (const int32_t *)(db + o_v2);
-    rec.T2w = (const float *)(db + o_T2); rec.pairs = (const int32_t *)(db + o_pairs); rec.n_pairs = (const int32_t *)(db + o_np);
-    rec.draws = (const uint32_t *)(db + o_draws); rec.n = n2;
-    memcpy(hb + o_rec, &rec, sizeof(rec));
-    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, s));
+    rec.keys_un = blk.dev(f_k2); rec.pos = blk.dev(f_p2); rec.valid = blk.dev(f_v2); rec.T2w = blk.dev(f_T2); rec.pairs = blk.dev(f_pairs);
+    rec.n_pairs = blk.dev(f_np); rec.draws = blk.dev(f_draws); rec.n = n2;
+    blk.put(f_rec, &rec, 1);
+    ORBFE_HIP_TRY(ctx, blk.upload(s));
     orbfe_grid_keyframe kf1 = {}; // only keys_un and n are read
-    kf1.keys_un = (const orbfe_keypoint *)(db + o_k1); kf1.n = n1;
-    int32_t *cnt = (int32_t *)(db + o_cnt); // n_corr, n_its, n_events, status
-    const int rc = orbfe_enqueue_sim3_ransac_batch(ctx, &kf1, T1w, (const float *)(db + o_p1), (const int32_t *)(db + o_v1),
-                                                   (const orbfe_sim3_ransac_candidate *)(db + o_rec), 1, max_pairs, max_kf_n, fix_scale, min_inliers, max_its,
-                                                   (const int32_t *)(db + o_tab), cnt, cnt + 1, (int32_t *)(db + o_corr), (int32_t *)(db + o_sets),
-                                                   (orbfe_sim3_hypothesis *)(db + o_hyp), (uint32_t *)(db + o_bits), (int32_t *)(db + o_ev), cnt + 2, cnt + 3,
-                                                   nullptr);
+    kf1.keys_un = blk.dev(f_k1); kf1.n = n1;
+    int32_t *cnt = blk.dev(f_cnt);
+    const int rc = orbfe_enqueue_sim3_ransac_batch(ctx, &kf1, T1w, blk.dev(f_p1), blk.dev(f_v1), blk.dev(f_rec), 1, max_pairs, max_kf_n, fix_scale, min_inliers, max_its,
+                                                   blk.dev(f_tab), cnt, cnt + 1, blk.dev(f_corr), blk.dev(f_sets), blk.dev(f_hyp), blk.dev(f_bits), blk.dev(f_ev),
+                                                   cnt + 2, cnt + 3, nullptr);
     if (rc != ORBFE_OK) return rc;
-    ORBFE_HIP_TRY(ctx, hipMemcpyAsync(hb, db, down, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP_TRY(ctx, blk.download(s));
     ORBFE_HIP_TRY(ctx, hipStreamSynchronize(s));
     int32_t c4[4];
-    memcpy(c4, hb + o_cnt, sizeof(c4));
+    blk.get(f_cnt, c4, 4);
     *n_corr = c4[0]; *n_its = c4[1]; *n_events = c4[2];
-    memcpy(corr, hb + o_corr, sizeof(int32_t) * 2 * max_pairs);
-    if (sets) memcpy(sets, hb + o_sets, sizeof(int32_t) * 3 * max_its);
-    memcpy(hyp, hb + o_hyp, sizeof(orbfe_sim3_hypothesis) * max_its);
-    memcpy(inlier_bits, hb + o_bits, sizeof(uint32_t) * (size_t)words * max_its);
-    memcpy(events, hb + o_ev, sizeof(int32_t) * max_its);
+    blk.get(f_corr, corr, f_corr.count);
+    if (sets) blk.get(f_sets, sets, f_sets.count);
+    blk.get(f_hyp, hyp, f_hyp.count); blk.get(f_bits, inlier_bits, f_bits.count); blk.get(f_ev, events, f_ev.count);
     if (c4[3] != 0) return orbfe_fail(ctx, c4[3], "a pair index out of range or a keypoint octave outside the context's %d levels", ctx->params.nlevels);
     return ORBFE_OK;
 } ORBFE_CATCH(ctx)

@@ -219,6 +219,14 @@ def test_two_calls_on_one_stream_the_synchronous_form_and_the_wrapper_give_the_s
         assert rc == 0
         _same(dict(sync, dirs=None), dict(Tcw=T.reshape(-1, 16), pos=pos, edge_code=ecode, pt_code=pcode, sim3=sim3, info=info[0], status=int(status[0]), dirs=None))
         assert Ow.tobytes() == sync["Ow"].tobytes()
+    # no edge and no point: every padded array of the synchronous call is empty.  No vertex is active, so optimize() returns at once and
+    # the poses come back re-derived from their quaternions (the 1e-6 of test_without_optional_tables_and_outputs)
+    s, z = SC.scene("two"), np.zeros(0, np.int32)
+    sync = ctx.optimize_essential_graph(0, s["Tcw"], z, z, np.zeros(0, np.uint8), iterations=2)
+    want = M.run(s["Tcw"], 0, z, z, np.zeros(0, np.uint8), iterations=2)
+    assert sync["status"] == 0 and [int(sync["info"][k]) for k in ("iterations", "trials", "n_active_edges")] == [0, 0, 0]
+    assert len(sync["edge_code"]) == 0 and len(sync["pos"]) == 0 and len(sync["pt_code"]) == 0
+    assert np.abs(sync["Tcw"] - want["Tcw"]).max() < 1e-6 and np.abs(sync["Tcw"] - s["Tcw"]).max() < 1e-6
 
 
 @pytest.mark.gpu

@@ -3,6 +3,7 @@ literal Python transcription of the edge walk of Optimizer::OptimizeEssentialGra
 maps, with exact edge lists.  Host code only: no GPU."""
 import ctypes as C
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -113,8 +114,10 @@ EXPECTED = {
 @pytest.fixture(scope="module")
 def lib():
     path = os.path.join(HERE, "essential_blocks", "libessential_wrapper.so")
-    if not os.path.exists(path):
-        pytest.fail("tests/essential_blocks/libessential_wrapper.so is not built (run build())")
+    if not os.path.exists(path):  # host code only: built here when build()'s copy is not beside this file
+        r = subprocess.run(["make", "-C", os.path.join(HERE, "essential_blocks"), "libessential_wrapper.so"], capture_output=True, text=True)
+        if r.returncode != 0 or not os.path.exists(path):
+            pytest.fail("tests/essential_blocks/libessential_wrapper.so is not built (run build())\n" + r.stdout + r.stderr)
     L = C.CDLL(path)
     L.eg_wrapper_edges.restype = C.c_int
     L.eg_wrapper_edges.argtypes = [C.c_int] + [C.c_void_p] * 8 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int]

@@ -239,6 +239,10 @@ def test_gpu_host_entry_point_equals_the_enqueue_form_bit_for_bit(gpu):
         assert np.array_equal(out["erase"], dev["erase"][:dev["n_erase"]]) and out["info"].tobytes() == dev["info"].tobytes(), name
         rew = S.model(name)["rewritten"]
         assert out["Ow"][rew].tobytes() == dev["dirs"]["Ow"][rew].tobytes() and np.isnan(out["Ow"][~rew]).all(), name
+    # no keyframe, no point, no row, no observation: every padded array of the call is empty; the kernel's "no edge at all" answer
+    z = np.zeros(0, np.int32)
+    out = ctx.local_bundle_adjustment([], np.zeros(0, np.uint8), np.zeros((0, 16), np.float32), None, 0, np.zeros(1, np.int32), z, z, np.zeros((0, 3), np.float32))
+    assert out["status"] == 0 and not any(out["info"].tobytes()) and len(out["erase"]) == 0 and len(out["Tcw"]) == 0 and len(out["edge_code"]) == 0
 
 
 @pytest.mark.gpu

@@ -250,6 +250,11 @@ def test_gpu_synchronous_form_equals_the_enqueue_form(gpu):
                              s["its_for_n"])
         _assert_same(got, _crop(_alone(gpu, s), s["capacity"]), name)
         _assert_same(got, S.model(name), name)
+    s = S.scene("below_min")                                           # a frame without a keypoint, a keyframe without a slot: every padded array of the call is empty
+    s = dict(s, **{k: s[k][:0] for k in ("keys", "f_match", "pos", "valid")}, capacity=1)
+    got = ctx.pnp_ransac(s["keys"], s["f_match"], s["pos"], s["valid"], s["draws"], s["min_inliers"], s["max_its"], s["n_iterations"], s["epsilon"], s["th2"], s["its_for_n"])
+    _assert_same(got, M.run(s), "empty")
+    assert got["n_corr"] == 0 and got["n_its"] == 0 and got["n_events"] == 0 and got["exhausted"] == -1 and (got["corr"] == -1).all()
     s = _bad_match(S.scene("n65"), 5, 4000)                            # what only the device sees comes back as the call's error
     with pytest.raises(api.OrbfeError) as e:
         ctx.pnp_ransac(s["keys"], s["f_match"], s["pos"], s["valid"], s["draws"], s["min_inliers"], s["max_its"], s["n_iterations"], s["epsilon"], s["th2"], s["its_for_n"])

@@ -151,6 +151,10 @@ def test_gpu_host_entry_point_equals_the_enqueue_form_bit_for_bit(gpu):
         S12, m, n = ctx.optimize_sim3(s["keys1"], s["T1w"], s["pos1"], s["valid1"], s["keys2"], s["T2w"], s["pos2"], s["valid2"], s["s12"], s["R12"], s["t12"],
                                       s["th2"], s["fix_scale"], s["match12"], prior12=s["prior12"])
         assert _same_bits(dev, dict(S12=S12, match12=m, n_inliers=n, status=0)), name
+    s = S.scene("kf1_empty")                        # keyframe 2 empty as well: every padded array of the call is empty; still the input Sim3
+    S12, m, n = ctx.optimize_sim3(s["keys1"], s["T1w"], s["pos1"], s["valid1"], s["keys2"][:0], s["T2w"], s["pos2"][:0], s["valid2"][:0], s["s12"], s["R12"], s["t12"],
+                                  s["th2"], s["fix_scale"], s["match12"], prior12=s["prior12"])
+    assert len(s["keys1"]) == 0 and _same_bits(_alone(gpu, "kf1_empty"), dict(S12=S12, match12=m, n_inliers=n, status=0)), "both empty"
     s = S.scene("bad_octave1")                      # what only the device sees comes back as the call's error
     with pytest.raises(api.OrbfeError) as e:
         ctx.optimize_sim3(s["keys1"], s["T1w"], s["pos1"], s["valid1"], s["keys2"], s["T2w"], s["pos2"], s["valid2"], s["s12"], s["R12"], s["t12"], s["th2"], 0,

@@ -207,6 +207,12 @@ def test_gpu_synchronous_form_equals_the_enqueue_form(gpu):
         got = ctx.sim3_ransac(s["keys1"], s["T1w"], s["pos1"], s["valid1"], s["keys2"], s["T2w"], s["pos2"], s["valid2"], s["pairs"], s["draws"], s["fix_scale"],
                               s["min_inliers"], s["max_its"], s["its_for_n"])
         _assert_same(got, _alone(gpu, s), name)
+    s = S.scene("below_min")                                           # no keypoint on either side and n_pairs = 0: every padded array of the call is empty
+    s = dict(s, **{k: s[k][:0] for k in ("keys1", "pos1", "valid1", "keys2", "pos2", "valid2", "pairs")}, max_pairs=1, max_kf_n=0)
+    got = ctx.sim3_ransac(s["keys1"], s["T1w"], s["pos1"], s["valid1"], s["keys2"], s["T2w"], s["pos2"], s["valid2"], s["pairs"], s["draws"], s["fix_scale"],
+                          s["min_inliers"], s["max_its"], s["its_for_n"])
+    _assert_same(got, M.run(s), "empty")
+    assert got["n_corr"] == 0 and got["n_its"] == 0 and got["n_events"] == 0 and (got["corr"] == -1).all()
     s = _bad_pair(S.scene("cand_a"), 5, (0, 4000))                     # what only the device sees comes back as the call's error
     with pytest.raises(api.OrbfeError) as e:
         ctx.sim3_ransac(s["keys1"], s["T1w"], s["pos1"], s["valid1"], s["keys2"], s["T2w"], s["pos2"], s["valid2"], s["pairs"], s["draws"], 0, 20, 12, s["its_for_n"])
